@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- ICP iterations/s on BASELINE.json's 1M <-> 1M workload.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]                 # N >= 1: ONE process drives all N GPUs
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   # N >= 1: ONE process drives all N GPUs
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W                       # one process per GPU over RCCL
+
+A plain run sets up, runs W warm-up iterations, times exactly K, and prints the line.  `--full` adds everything that takes
+runs of its own: the VALU issue ceiling before / after the timed loop (`roofline.measured_issue_ceiling`), the `grid_path`,
+`mfma_experiment`, `surface_path` and `whole_call` legs (N = 1), `c5_path` (N > 1, or `--c5`) and the CPU baseline with its
+tiers (N = 1); the `--no-*` options below trim a `--full` run.  `--dump-outputs DIR` writes what the timed run returned
+(`dump_outputs`) as DIR/<name>.npy; the inputs are seeded, so two builds given the same arguments can be compared array by array.
 
 A "step" is one ICP iteration over the whole workload: nearest-vertex search for every source point against the
 whole target cloud, the fused threshold/accumulate pass, the exchange of 24 doubles between the GPUs (N > 1) and the
@@ -88,7 +94,31 @@ def parse():
     ap.add_argument("--c5-source", type=int, default=10_000_000)
     ap.add_argument("--c5-target", type=int, default=2_000_000)
     ap.add_argument("--c5-steps", type=int, default=20)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also the ceiling, the legs beside the headline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed run's outputs as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+def dump_outputs(out_dir, res):
+    """What the timed `run` returned to its caller (RunResult without its timings), one float32 / float64 .npy per field:
+    the final matrix_world, every iteration's affine matrix, new_mat, K, [mean, std] and translation, and the last
+    iteration's scalars.  Counts are stored as float64 (exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "matrix_world": np.asarray(res.matrix_world, np.float32),
+        "step_M": np.asarray(res.step_M, np.float64),
+        "step_new": np.asarray(res.step_new, np.float32),
+        "step_K": np.asarray(res.step_K, np.float64),
+        "step_stats": np.asarray(res.step_stats, np.float64),
+        "step_trans": np.asarray(res.step_trans, np.float64),
+    }
+    for name in ("iters_done", "converged", "last_K", "last_translation", "mean_dist", "std_dist", "mean_rot_angle"):
+        arrays[name] = np.asarray(float(getattr(res, name)), np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def csrc_sha16():
@@ -528,6 +558,8 @@ def main():
     def ceiling():
         """What the vector ALUs issue right now (5 ms of v_add_f32 / v_min3_f32 on every SIMD, oa_measure_valu_ceiling) and the shader clock
         under that load: taken right before and right after the timed loop, it tells a throttling box from a slower kernel."""
+        if not args.full:
+            return {"skipped": "measured with --full"}
         try:
             return eng.valu_ceiling(5.0)
         except Exception as exc:                                  # never lose the headline line
@@ -548,6 +580,8 @@ def main():
         xinfo = eng.exchange_info()
         exchange, rccl_ranks, host_threads = xinfo["exchange"], xinfo["rccl_ranks"], xinfo["host_threads"]
         res, elapsed, nn_ms = timed(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     ceil_after = ceiling()
     try:
         brute_kind = eng.stat("brute_kernel")                     # which brute-force kernel the timed loop launched
@@ -571,7 +605,7 @@ def main():
     # SURVEY 8f rank 2 ("next" row, reported beside the headline, never instead of it): the same run with the
     # uniform-grid exact search.  Correspondences are identical, so the final matrix must be bitwise the same.
     grid = None
-    if not args.no_grid:
+    if args.full and not args.no_grid:
         try:
             eng.set_search_mode("grid")
             g_steps = max(args.steps, 200)
@@ -582,28 +616,28 @@ def main():
             grid = ("error: %r" % (exc,),)
 
     mfma = None
-    if n_gpus == 1 and not args.no_mfma:
+    if args.full and n_gpus == 1 and not args.no_mfma:
         try:
             mfma = mfma_leg(args, local_rank, src, tgt, mxa, mxb, kw, res.matrix_world)
         except Exception as exc:                                  # never lose the headline line
             mfma = {"error": repr(exc)}
 
     surf = None
-    if n_gpus == 1 and not args.no_surface:
+    if args.full and n_gpus == 1 and not args.no_surface:
         try:
             surf = surface_leg(args, local_rank)
         except Exception as exc:                                  # never lose the headline line
             surf = {"error": repr(exc)}
 
     whole = None
-    if n_gpus == 1 and not args.no_whole_call:
+    if args.full and n_gpus == 1 and not args.no_whole_call:
         try:
             whole = whole_call_leg(local_rank, src, tgt, mxa, mxb)
         except Exception as exc:                                  # never lose the headline line
             whole = {"error": repr(exc)}
 
     c5 = None
-    if (n_gpus > 1 and not args.no_c5) or (n_gpus == 1 and args.c5):
+    if args.full and ((n_gpus > 1 and not args.no_c5) or (n_gpus == 1 and args.c5)):
         try:
             c5 = c5_leg(args, n_gpus, in_process, world, rank, local_rank, devices, dev, backend)
         except Exception as exc:                                  # never lose the headline line
@@ -753,7 +787,7 @@ def main():
             out["whole_call"] = whole
         if c5 is not None:
             out["c5_path"] = c5
-        if n_gpus == 1 and not args.no_cpu_baseline and args.cpu_iters > 0:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline and args.cpu_iters > 0:
             out["cpu_baseline"] = cpu_baseline(src, tgt, mxa, mxb, min(args.cpu_iters, args.steps), res.step_M)
             try:
                 out["cpu_baseline_tiers"] = cpu_tiers(src, tgt, mxa, mxb)

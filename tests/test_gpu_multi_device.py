@@ -361,7 +361,7 @@ def test_bench_self_launches_multi_gpu():
     """`python bench.py --gpus 2` with no launcher: one process, the multi-device context; one JSON line, n_gpus 2."""
     env = dict(os.environ, OA_BENCH_SAME_DEVICE="1")
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--n-source", "120000",
-           "--n-target", "100000", "--no-cpu-baseline", "--no-surface", "--c5-source", "300000", "--c5-target", "100000",
+           "--n-target", "100000", "--full", "--no-cpu-baseline", "--no-surface", "--c5-source", "300000", "--c5-target", "100000",
            "--c5-steps", "3"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600, text=True)
     assert p.returncode == 0, p.stdout[-3000:]
@@ -598,7 +598,7 @@ def test_bench_two_shards_reports_its_exchange(monkeypatch):
     host enqueue time per iteration."""
     env = dict(os.environ, OA_BENCH_SAME_DEVICE="1", OA_MULTI_OWN_STREAMS="1")
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--n-source", "120000",
-           "--n-target", "100000", "--no-cpu-baseline", "--no-surface"]
+           "--n-target", "100000", "--full", "--no-cpu-baseline", "--no-surface"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600, text=True)
     assert p.returncode == 0, p.stdout[-3000:]
     d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])

@@ -23,7 +23,7 @@ def _run(cmd, env):
 
 def test_bench_two_ranks_gloo_same_gpu():
     env = dict(os.environ)
-    common = ["--steps", "4", "--warmup", "1", "--n-source", "120000", "--n-target", "100000", "--no-cpu-baseline"]
+    common = ["--steps", "4", "--warmup", "1", "--n-source", "120000", "--n-target", "100000", "--full", "--no-cpu-baseline"]
     one = _run([sys.executable, "bench.py", "--gpus", "1"] + common, env)
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))

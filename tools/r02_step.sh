@@ -12,7 +12,7 @@ if [ "$1" != "quick" ]; then
 fi
 (echo "# ONLY=surface:auto / surface:grid / vertex:grid python tools/time_surface.py"
  for o in surface:auto surface:grid vertex:grid; do ONLY=$o timeout 300 python tools/time_surface.py 2>&1 | grep -v amdgpu.ids; done) > "$OUT/${TAG}_surface_timings.txt"
-timeout 400 python bench.py --steps 10 --warmup 1 --no-cpu-baseline > "$OUT/${TAG}_bench_quick.json" 2> "$OUT/${TAG}_bench_quick.err"
+timeout 400 python bench.py --steps 10 --warmup 1 --full --no-cpu-baseline > "$OUT/${TAG}_bench_quick.json" 2> "$OUT/${TAG}_bench_quick.err"
 python - <<PY
 import json
 d = json.load(open("$OUT/${TAG}_bench_quick.json"))

@@ -102,7 +102,7 @@ def main():
         shutil.copy(stats, os.path.join(PROF, "%s_bench_1Mx1M_kernel_stats.csv" % tag))
     agg = collect(("prof_pmc_FETCH_SIZE", "prof_pmc_WRITE_SIZE", "prof_pmc_SQ", "prof_pmc_SQ2"), lambda k: k.startswith("k_nn_search"))
     lines = ["# %s: %s" % (tag, header),
-             "# rocprofv3 PMC passes of `python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-surface` (tools/profile.sh); per-dispatch means",
+             "# rocprofv3 PMC passes of `python bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-surface` (tools/profile.sh); per-dispatch means",
              "# commit %s, kernel sources sha16 %s" % (commit, stamp["csrc_sha16"]), ""]
     mean, traffic = table(agg, lines)
     brute = brute_of(traffic)
