@@ -1024,14 +1024,15 @@ __global__ __launch_bounds__(BT, OA_TRI_MIN_WAVES) void k_tri_search_grid(const 
             }
             if (changed) { S.lim = fminf(S.best, cutf); tri_state_refresh(S, delta); if (SHARE) owner_q4[threadIdx.x].w = S.reach; }
         }
-        if (busy) {
-            if (over) busy = false;
-            else if (ring_done) {
-                if (STATS) max_ring = r;
-                const float bound = grid_cube_bound2(gp, q, r);        // everything outside the cube of radius r
-                if (!(bound < INFINITY) || bound * 0.999998f > S.reach2f) { settled = true; busy = false; }   // same test as for a row
-                else { ++r; b0 = 0; if (r > gp.r_max) busy = false; }
-            }
+        // A query's lanes drift apart in rings >= 2 (a lane takes further batches of rows only while its own list has room): one may
+        // be through the ring and settled trips before a sibling lists a crowded cell of the same ring and goes over.  Then the
+        // query is not settled on any of its lanes -- lane 0 decides the hand-over to the tree -- however early it settled.
+        if (over) { busy = false; settled = false; }
+        else if (busy && ring_done) {
+            if (STATS) max_ring = r;
+            const float bound = grid_cube_bound2(gp, q, r);            // everything outside the cube of radius r
+            if (!(bound < INFINITY) || bound * 0.999998f > S.reach2f) { settled = true; busy = false; }   // same test as for a row
+            else { ++r; b0 = 0; if (r > gp.r_max) busy = false; }
         }
         OA_TRI_STAMP(cyc_book);
     }

@@ -1090,6 +1090,7 @@ def test_surface_grid_lane_variants_and_ragged_last_wave(orc, lanes, monkeypatch
         e.set_source(q)
         e.set_matrices(eye, eye)
         idx, d2, _ = e.nn_search()
+        e.make_pairs(1e3)                                                            # plants the seeds (a bare nn_search does not)
         idx2, d22, _ = e.nn_search()                                                 # seeded
     ridx, _, rd2 = orc.nn_tri_brute(q, v, t)
     assert np.array_equal(idx, ridx) and np.array_equal(d2, rd2)
