@@ -37,15 +37,19 @@
     OA_K(X, k_sorted_wave_order, OA_SIG_WAVE_ORDER, 2) OA_K(X, k_sorted_wave_order, OA_SIG_WAVE_ORDER, 4)               \
     OA_K(X, k_sorted_wave_order, OA_SIG_WAVE_ORDER, 8)                                                                  \
     OA_K(X, k_nn_seed_sorted, OA_SIG_SEED_SORTED, 64) OA_K(X, k_nn_seed_sorted, OA_SIG_SEED_SORTED, FTILE_GROUPS)       \
-    OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 1, 64) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 2, 64)
+    OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 1, 64, true) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 2, 64, true)      \
+    OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 1, 64, false) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 2, 64, false)
 // (the unrolled search for 4 points per thread is the longest compile of the default library: a unit each)
-#define OA_FAMILY_BRUTE_B(X) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 4, 64)
+#define OA_FAMILY_BRUTE_B(X) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 4, 64, true) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 4, 64, false)
 #define OA_FAMILY_BRUTE_BIG(X)                                                                                          \
-    OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 1, FTILE_GROUPS) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 2, FTILE_GROUPS)
-#define OA_FAMILY_BRUTE_BIG_B(X) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 4, FTILE_GROUPS)
+    OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 1, FTILE_GROUPS, true) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 2, FTILE_GROUPS, true) \
+    OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 1, FTILE_GROUPS, false) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 2, FTILE_GROUPS, false)
+#define OA_FAMILY_BRUTE_BIG_B(X)                                                                                        \
+    OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 4, FTILE_GROUPS, true) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 4, FTILE_GROUPS, false)
 // 8 points per thread (OA_NN_R=8: measured slower, half the waves per SIMD; 55 s of compile per instantiation): experiments only
-#define OA_FAMILY_EXP_R8(X) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 8, 64)
-#define OA_FAMILY_EXP_R8_BIG(X) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 8, FTILE_GROUPS)
+#define OA_FAMILY_EXP_R8(X) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 8, 64, true) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 8, 64, false)
+#define OA_FAMILY_EXP_R8_BIG(X)                                                                                         \
+    OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 8, FTILE_GROUPS, true) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 8, FTILE_GROUPS, false)
 
 // ---- uniform grid over vertices: oa_fam_grid.hip --------------------------------------------------------------------
 #define OA_FAMILY_GRID(X)                                                                                               \

@@ -423,6 +423,7 @@ struct oa_ctx {
     int *d_perm = nullptr;           // sorted slot -> caller-order slot (nullptr: not sorted)
     unsigned short *d_worder = nullptr;   // k_sorted_wave_order: per wave of k_nn_search_sorted, its slots in the order of u (OA_NN_WAVE_ORDER=0: off)
     int *d_homes = nullptr, *d_qcnt = nullptr;   // k_nn_search_sorted's work queue (oa_kernels.hpp): per block of source points its own split; the queues' counters
+    bool nn_vchunk = true;           // OA_NN_VCHUNK: the sorted images' blocks in the order of v and k_nn_search_sorted's level 0v (0: as until round 6)
     int nn_persist = 4;              // OA_NN_PERSIST: workgroups per CU that work the queue off (0: one workgroup per item, in launch order -- as until round 6)
     int nn_queue_min = -1;           // OA_NN_QUEUE_MIN_ITEMS: launches of at least this many items go through the queue (-1: four per workgroup)
     int last_queue_wgs = 0;          // OA_STAT_BRUTE_QUEUE_WGS
@@ -972,8 +973,10 @@ int launch_nn_impl(oa_ctx *c, bool acc)
         int pass = 0;
 #define OA_LAUNCH_S(RR)                                                                                              \
         do {                                                                                                         \
-            if (small) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, 64>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt);  \
-            else hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, oa::FTILE_GROUPS>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt); \
+            if (small && c->nn_vchunk) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, 64, true>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt);  \
+            else if (small) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, 64, false>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt);  \
+            else if (c->nn_vchunk) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, oa::FTILE_GROUPS, true>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt); \
+            else hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, oa::FTILE_GROUPS, false>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt); \
         } while (0)
 #if defined(OA_EXPERIMENTS)
 #define OA_LAUNCH_S_CASE8 case 8: OA_LAUNCH_S(8); break;
@@ -2042,6 +2045,7 @@ OA_EXPORT int oa_create(oa_ctx **out, int device)
     c->nn_home_pass = env_int("OA_NN_HOME_PASS", 1) != 0;
     c->nn_wave_order = env_int("OA_NN_WAVE_ORDER", 1) != 0;
     c->nn_persist = std::max(0, std::min(16, env_int("OA_NN_PERSIST", 4)));
+    c->nn_vchunk = env_int("OA_NN_VCHUNK", 1) != 0;
     c->nn_queue_min = env_int("OA_NN_QUEUE_MIN_ITEMS", -1);
     c->nn_mfma = env_int("OA_NN_MFMA", 0);
 #if !defined(OA_EXPERIMENTS)
@@ -2304,6 +2308,11 @@ int build_sorted_images(oa_ctx *c)
                        ext > 0.0 ? 1073741823.0 / ext : 0.0, k_in.p, v_in.p);
     HIPCHK(hipGetLastError());
     { const int rcs = sort_pairs30(c, k_in.p, k_out.p, v_in.p, v_out.p, (size_t)c->nt); if (rcs) return rcs; }
+    if (c->nn_vchunk) {                                           // every block of the u order by v, its first vertex kept (k_sort_blocks_v)
+        hipLaunchKernelGGL(oa::k_sort_blocks_v, dim3((unsigned)((c->nt + oa::SORTED_VBLOCK - 1) / oa::SORTED_VBLOCK)), dim3(oa::SORTED_VBLOCK), 0,
+                           c->stream, (const float *)c->d_tgt_xyz, c->nt, c->sax[1], c->tc[c->sax[1]], v_out.p);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(dev_malloc(&c->d_tfs, sizeof(float4) * 3 * (size_t)c->n_groups_pad));
     HIPCHK(dev_malloc(&c->d_tf3s, sizeof(float4) * 2 * (size_t)c->n_groups_pad));
     HIPCHK(dev_malloc(&c->d_tgs, sizeof(float4) * 3 * (size_t)c->n_groups_pad));

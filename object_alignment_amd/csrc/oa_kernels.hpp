@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <type_traits>
 
 namespace oa {
 
@@ -1366,7 +1367,43 @@ constexpr int SORT_ORDER_MAX = 1024;
 #define OA_SORTED_GW 64                   // groups of 4 sorted vertices per skip test of k_nn_search_sorted (a build-time knob for sweeps)
 #endif      // tiles of one split whose middle-out order fits the LDS table (more: ascending)
 
-template <int R, int TG = FTILE_GROUPS>
+// Blocks of the sorted images in the order of v (round 7, OA_NN_VCHUNK=1): the positions of every SORTED_VBLOCK consecutive
+// vertices -- the block level 0 tests in the smallest tile (64 groups) -- ordered by the centred float32 coordinate along the
+// second axis v (ties: the u position), so that level 0v (k_nn_search_sorted) finds a point's few vertices near it in v in a few
+// chunks of 16.  A block holds the same set of vertices as before, so level 0's decisions are unchanged (a minimum does not depend
+// on the order), and position 0 of every block stays where it is: a tile's first vertex is the one the binary searches for a
+// point's home tile read (tfs[3 TG t].x: k_nn_search_sorted's visiting order, k_sorted_block_homes, k_nn_seed_sorted).  Padding
+// (positions >= nt) is only ever at the tail of the last block and stays there.  One workgroup per block, a rank sort in LDS;
+// at upload only.
+constexpr int SORTED_VBLOCK = 4 * (OA_SORTED_GW < 64 ? OA_SORTED_GW : 64);
+#if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
+__global__ __launch_bounds__(SORTED_VBLOCK) void k_sort_blocks_v(const float *__restrict__ xyz, int nt, int av, float cv,
+                                                                 int *__restrict__ order)
+{
+    __shared__ uint32_t key[SORTED_VBLOCK];
+    const int t = threadIdx.x;
+    const long long first = (long long)blockIdx.x * SORTED_VBLOCK;
+    const int n = (int)(nt - first < SORTED_VBLOCK ? nt - first : SORTED_VBLOCK);   // positions of this block that hold vertices
+    int id = -1;
+    uint32_t mine = 0xffffffffu;
+    if (t < n) {
+        id = order[first + t];
+        const uint32_t b = __float_as_uint((float)((double)xyz[3ll * id + av] - (double)cv));   // (k_pack_sorted's rounding)
+        mine = (b & 0x80000000u) ? ~b : (b | 0x80000000u);         // unsigned order = float order
+    }
+    key[t] = mine;
+    __syncthreads();                                               // (every read of order is done: the writes below may land in place)
+    if (t < 1 || t >= n) return;
+    int rank = 1;
+    for (int k = 1; k < n; ++k) {
+        const uint32_t o = key[k];                                 // (broadcast read)
+        rank += (o < mine || (o == mine && k < t)) ? 1 : 0;
+    }
+    order[first + rank] = id;
+}
+#endif  // !OA_FAMILY_TU
+
+template <int R, int TG = FTILE_GROUPS, bool VCHUNK = true>
 __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sorted(const DevState *__restrict__ st,
                                                                  const float4 *__restrict__ src4,
                                                                  const float4 *__restrict__ tgs,
@@ -1514,8 +1551,13 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
         const int cur = t & 1;
         const bool more = (t + 1 < n_tiles);
         if (more) {                                               // next tile: global -> registers, hidden under compute
-            const float4 *nsrc = tsrc + 3ll * TG * OA_TILE_AT(t + 1);
-#define OA_STG_LOAD(k, reg) reg = nsrc[(k) * NN_THREADS + tid]
+            // (VCHUNK: the address from the scalar tile base and the thread's 32-bit offset, formed anew per tile -- held through
+            //  the scan as a 64-bit vector pointer it is one register pair too many beside the larger rare path: scratch)
+            const int nt1 = VCHUNK ? __builtin_amdgcn_readfirstlane(OA_TILE_AT(t + 1)) : OA_TILE_AT(t + 1);
+            const float4 *nsrc = tsrc + 3ll * TG * nt1;
+            int ltid = tid;
+            if (VCHUNK) asm volatile("" : "+v"(ltid));
+#define OA_STG_LOAD(k, reg) reg = nsrc[(k) * NN_THREADS + ltid]
             OA_STG_EACH(OA_STG_LOAD);
 #undef OA_STG_LOAD
         }
@@ -1558,15 +1600,62 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                 hit0 |= hit[r];
             }
             if (!hit0) continue;
-#pragma unroll 1
-            for (int k = 0; k < GW; ++k) {                         // rare from here on: one group of 4 targets at a time
-                const float4 Q = tile[cur][3 * (g + k)], AV = tile[cur][3 * (g + k) + 1], W2 = tile[cur][3 * (g + k) + 2];
-                const float4 AU = make_float4(-2.0f * Q.x, -2.0f * Q.y, -2.0f * Q.z, -2.0f * Q.w);   // exact
+            if constexpr (VCHUNK) {
+                // level 0v (round 7): the block folded again along v, 16 vertices per chunk -- with the blocks sorted by v
+                // (k_sort_blocks_v) the few chunks near a point's own v are the only ones whose gap can pass.  a_j = |fl32(hv - qv_j)|
+                // (fma(0.5, -2qv_j, hv): the halving is exact, so the one rounding is the subtraction's) against the SAME thr1 as
+                // level 0: the distance along any one axis never exceeds the 3-D distance, and level 0's proof (header) holds word
+                // for word with v for u.  A chunk is ruled out only when its minimum > thr1 is true (NaN passes); thr1 only falls
+                // while levels 1-3 run, so a mask taken before them stays conservative.  One point r at a time (the order in which
+                // groups are scored cannot change a lexicographic minimum): the fold -- unrolled, branch-free, one compare and one
+                // ballot per chunk -- leaves the lane's own chunk bits in ONE register and the wave's union in a scalar; then
+                // levels 1-3 for the groups of those chunks.  (All R masks kept at once and a group-major loop cost registers enough
+                // to spill the next tile's staging registers: 56 B of scratch, each tile waiting for its prefetch.)
+                constexpr int NC = GW / 4;                         // chunks of 16 vertices per block
+                using cmask_t = typename std::conditional<(NC > 32), unsigned long long, uint32_t>::type;
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    if (!hit[r]) continue;                         // (a point's run of 64 slots is a quarter of the wave's extent)
-                    sorted_finish_group(AU, AV, W2, gbase + g + k, tf3s, tgs, tidx, px[r], py[r], pz[r], hu[r], hv[r], hd[r], qmax,
-                                        best[r], bidx[r], thr1[r], thr2[r]);
+                    if (!__ballot(hit[r])) continue;               // (uniform: no lane of the wave has this point in the block)
+                    cmask_t cm = 0, todo = 0;
+#pragma unroll 8
+                    for (int c = 0; c < NC; ++c) {
+                        float v = INFINITY;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const float4 A = tile[cur][3 * (g + 4 * c + k) + 1];
+                            const float a0 = __builtin_fabsf(__builtin_fmaf(0.5f, A.x, hv[r])), a1 = __builtin_fabsf(__builtin_fmaf(0.5f, A.y, hv[r]));
+                            const float a2 = __builtin_fabsf(__builtin_fmaf(0.5f, A.z, hv[r])), a3 = __builtin_fabsf(__builtin_fmaf(0.5f, A.w, hv[r]));
+                            v = k == 0 ? __builtin_fminf(__builtin_fminf(a0, a1), a2) : __builtin_fminf(__builtin_fminf(v, a0), a1);   // v_min3_f32
+                            v = k == 0 ? __builtin_fminf(v, a3) : __builtin_fminf(__builtin_fminf(v, a2), a3);
+                        }
+                        const bool pass_c = hit[r] && !(v > thr1[r]);
+                        cm |= (cmask_t)pass_c << c;
+                        if (__ballot(pass_c)) todo |= (cmask_t)1 << c;
+                    }
+                    for (; todo; todo &= todo - 1) {
+                        const int c = (NC > 32) ? __builtin_ctzll((unsigned long long)todo) : __builtin_ctz((uint32_t)todo);
+                        const bool mine = (cm >> c) & 1;
+#pragma unroll 1
+                        for (int k = 4 * c; k < 4 * c + 4; ++k) {  // one group of 4 targets at a time
+                            const float4 Q = tile[cur][3 * (g + k)], AV = tile[cur][3 * (g + k) + 1], W2 = tile[cur][3 * (g + k) + 2];
+                            const float4 AU = make_float4(-2.0f * Q.x, -2.0f * Q.y, -2.0f * Q.z, -2.0f * Q.w);   // exact
+                            if (mine)
+                                sorted_finish_group(AU, AV, W2, gbase + g + k, tf3s, tgs, tidx, px[r], py[r], pz[r], hu[r], hv[r], hd[r],
+                                                    qmax, best[r], bidx[r], thr1[r], thr2[r]);
+                        }
+                    }
+                }
+            } else {                                               // OA_NN_VCHUNK=0: the rare loop of round 6, as it was
+#pragma unroll 1
+                for (int k = 0; k < GW; ++k) {                     // rare from here on: one group of 4 targets at a time
+                    const float4 Q = tile[cur][3 * (g + k)], AV = tile[cur][3 * (g + k) + 1], W2 = tile[cur][3 * (g + k) + 2];
+                    const float4 AU = make_float4(-2.0f * Q.x, -2.0f * Q.y, -2.0f * Q.z, -2.0f * Q.w);   // exact
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        if (!hit[r]) continue;                     // (a point's run of 64 slots is a quarter of the wave's extent)
+                        sorted_finish_group(AU, AV, W2, gbase + g + k, tf3s, tgs, tidx, px[r], py[r], pz[r], hu[r], hv[r], hd[r], qmax,
+                                            best[r], bidx[r], thr1[r], thr2[r]);
+                    }
                 }
             }
         }
