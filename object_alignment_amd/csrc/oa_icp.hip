@@ -973,10 +973,10 @@ int launch_nn_impl(oa_ctx *c, bool acc)
         int pass = 0;
 #define OA_LAUNCH_S(RR)                                                                                              \
         do {                                                                                                         \
-            if (small && c->nn_vchunk) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, 64, true>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt);  \
-            else if (small) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, 64, false>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt);  \
-            else if (c->nn_vchunk) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, oa::FTILE_GROUPS, true>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt); \
-            else hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, oa::FTILE_GROUPS, false>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt); \
+            if (small && c->nn_vchunk) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, 64, true>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt, c->nt);  \
+            else if (small) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, 64, false>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt, c->nt);  \
+            else if (c->nn_vchunk) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, oa::FTILE_GROUPS, true>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt, c->nt); \
+            else hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, oa::FTILE_GROUPS, false>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt, c->nt); \
         } while (0)
 #if defined(OA_EXPERIMENTS)
 #define OA_LAUNCH_S_CASE8 case 8: OA_LAUNCH_S(8); break;

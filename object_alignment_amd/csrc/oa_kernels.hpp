@@ -1123,6 +1123,16 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_filt
 //                       a_j > T1 = round_up(sqrt(base) (1 + 2^-22))  =>  t >= a_j / (1 + 2^-24) > sqrt(base).
 //                       (Flushed denormals only ever make a_j smaller: fewer pairs skipped, never a wrong one.)
 //                       For all slabs but the few around the wave's own u range every pair fails here.
+//   level 0v (rare)     for a block some lane hit (OA_NN_VCHUNK=1): the same gap along v, a_j = fl32(hv - qv_j) against the same
+//                       thr1, from the ENDS of each chunk of 4 OA_SORTED_VCG vertices.  Positions 1 .. n-1 of a block are in the
+//                       order of qv (k_sort_blocks_v), and rounding is monotone, so a_j does not increase along a chunk: with F, L
+//                       its first and last, every |a_j| >= L when L > 0 and >= -F when F < 0.  max(L, -F) > thr1 (true; NaN:
+//                       false) therefore proves min |a_j| > thr1 -- what level 0's proof needs -- and the chunk is ruled out; a
+//                       chunk with F >= 0 >= L passes.  Every chunk the round-7 fold over all its a_j kept is kept (a superset:
+//                       a chunk whose interior straddles hv with no vertex near it passes in vain).  Position 0 of a block is
+//                       not in that order and is tested on its own; a block with padding is not tested (its chunks that hold a
+//                       vertex pass); thr1 = +inf (unseeded) passes every chunk.  (A NaN v sorts to a block's ends; such a
+//                       vertex never wins, and max() of a NaN and a number is the number, which bounds the rest alone.)
 //   levels 1, 2, 3      as k_nn_search_filtered (2-D score, 3-D score, exact metric), reached by ~6 % of the blocks at 1M <-> 1M.
 // Indices: position j of the sorted images holds original vertex tidx[j]; the exact path compares and reports ORIGINAL indices
 // (lowest index on ties, as everywhere).  A split owns a seed when seed index mod splits = split (no position lookup).
@@ -1366,6 +1376,12 @@ constexpr int SORT_ORDER_MAX = 1024;
 #ifndef OA_SORTED_GW
 #define OA_SORTED_GW 64                   // groups of 4 sorted vertices per skip test of k_nn_search_sorted (a build-time knob for sweeps)
 #endif      // tiles of one split whose middle-out order fits the LDS table (more: ascending)
+#ifndef OA_SORTED_VCG
+#define OA_SORTED_VCG 4                   // groups of 4 sorted vertices per chunk of level 0v (a build-time knob for sweeps;
+#endif                                    //  2 / 4 / 8: 25.46 / 24.99 / 24.94 ms at 1M <-> 1M, profiles/r08a_vends.txt)
+#ifndef OA_SORTED_VREFINE
+#define OA_SORTED_VREFINE 0               // 1: level 0v's end test again per group of a passing chunk, ahead of level 1 (25.11 ms)
+#endif
 
 // Blocks of the sorted images in the order of v (round 7, OA_NN_VCHUNK=1): the positions of every SORTED_VBLOCK consecutive
 // vertices -- the block level 0 tests in the smallest tile (64 groups) -- ordered by the centred float32 coordinate along the
@@ -1414,7 +1430,8 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                                                                  int n_groups_pad, int au, int av,
                                                                  unsigned long long *keys, int pass,
                                                                  const unsigned short *__restrict__ order,
-                                                                 int n_splits, int n_blocks, const int *__restrict__ homes, int *qcnt)
+                                                                 int n_splits, int n_blocks, const int *__restrict__ homes, int *qcnt,
+                                                                 int nt)
 {
     // pass 0: seeds from the winner records of the last accumulation (none on the first search of a loop: every split then has to
     // find a best of its own before it can skip anything).  pass 2: seeds from keys, where k_nn_seed_sorted has left every point's
@@ -1601,45 +1618,71 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
             }
             if (!hit0) continue;
             if constexpr (VCHUNK) {
-                // level 0v (round 7): the block folded again along v, 16 vertices per chunk -- with the blocks sorted by v
-                // (k_sort_blocks_v) the few chunks near a point's own v are the only ones whose gap can pass.  a_j = |fl32(hv - qv_j)|
-                // (fma(0.5, -2qv_j, hv): the halving is exact, so the one rounding is the subtraction's) against the SAME thr1 as
-                // level 0: the distance along any one axis never exceeds the 3-D distance, and level 0's proof (header) holds word
-                // for word with v for u.  A chunk is ruled out only when its minimum > thr1 is true (NaN passes); thr1 only falls
-                // while levels 1-3 run, so a mask taken before them stays conservative.  One point r at a time (the order in which
-                // groups are scored cannot change a lexicographic minimum): the fold -- unrolled, branch-free, one compare and one
-                // ballot per chunk -- leaves the lane's own chunk bits in ONE register and the wave's union in a scalar; then
-                // levels 1-3 for the groups of those chunks.  (All R masks kept at once and a group-major loop cost registers enough
-                // to spill the next tile's staging registers: 56 B of scratch, each tile waiting for its prefetch.)
-                constexpr int NC = GW / 4;                         // chunks of 16 vertices per block
+                // level 0v (round 8; proof in the header): which of the block's chunks of 4 CG vertices can hold a vertex within
+                // thr1 of the point along v, from each chunk's two ends -- 2 fma, a max and a compare per chunk where round 7 folded
+                // every vertex again (~430 instructions per block and point).  a_j = fma(0.5, -2qv_j, hv): the halving is exact, the
+                // one rounding is the subtraction's.  thr1 only falls while levels 1-3 run, so a mask taken before them stays
+                // conservative.  One point r at a time (the order in which groups are scored cannot change a lexicographic
+                // minimum): the lane's own chunk bits in ONE register, the wave's union in a scalar; then levels 1-3 for the groups
+                // of those chunks.  (All R masks kept at once and a group-major loop cost registers enough to spill the next tile's
+                // staging registers.)
+                constexpr int CG = OA_SORTED_VCG, NC = GW / CG;    // groups per chunk, chunks per block
+                static_assert(CG >= 1 && GW % CG == 0 && NC <= 64, "k_nn_search_sorted: level 0v's chunks");
                 using cmask_t = typename std::conditional<(NC > 32), unsigned long long, uint32_t>::type;
+                const int blk = __builtin_amdgcn_readfirstlane(gbase + g);   // the block's first group
+                const int n_in = nt - 4 * blk;                     // positions of the block that hold a vertex (when < 4 GW)
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     if (!__ballot(hit[r])) continue;               // (uniform: no lane of the wave has this point in the block)
                     cmask_t cm = 0, todo = 0;
-#pragma unroll 8
-                    for (int c = 0; c < NC; ++c) {
-                        float v = INFINITY;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const float4 A = tile[cur][3 * (g + 4 * c + k) + 1];
-                            const float a0 = __builtin_fabsf(__builtin_fmaf(0.5f, A.x, hv[r])), a1 = __builtin_fabsf(__builtin_fmaf(0.5f, A.y, hv[r]));
-                            const float a2 = __builtin_fabsf(__builtin_fmaf(0.5f, A.z, hv[r])), a3 = __builtin_fabsf(__builtin_fmaf(0.5f, A.w, hv[r]));
-                            v = k == 0 ? __builtin_fminf(__builtin_fminf(a0, a1), a2) : __builtin_fminf(__builtin_fminf(v, a0), a1);   // v_min3_f32
-                            v = k == 0 ? __builtin_fminf(v, a3) : __builtin_fminf(__builtin_fminf(v, a2), a3);
+                    if (n_in >= 4 * GW) {
+                        // chunk c passes for this lane when the lane has this point in the block and the ends do not rule it out
+                        // (& rather than &&: no branch per chunk)
+#define OA_VCHUNK_PASS(c, out)                                                                                                      \
+                        do {                                                                                                        \
+                            const bool p_ = hit[r] & !(out);                                                                       \
+                            cm |= (cmask_t)p_ << (c);                                                                              \
+                            if (__builtin_amdgcn_ballot_w64(p_)) todo |= (cmask_t)1 << (c);                                         \
+                        } while (0)
+                        {                                                  // chunk 0: the block's position 0 on its own
+                            const float4 A0 = tile[cur][3 * g + 1], A1 = tile[cur][3 * (g + CG - 1) + 1];
+                            const float F = __builtin_fmaf(0.5f, A0.y, hv[r]), L = __builtin_fmaf(0.5f, A1.w, hv[r]);
+                            OA_VCHUNK_PASS(0, (__builtin_fmaxf(L, -F) > thr1[r]) & (__builtin_fabsf(__builtin_fmaf(0.5f, A0.x, hv[r])) > thr1[r]));
                         }
-                        const bool pass_c = hit[r] && !(v > thr1[r]);
-                        cm |= (cmask_t)pass_c << c;
-                        if (__ballot(pass_c)) todo |= (cmask_t)1 << c;
+#pragma unroll 5
+                        for (int c = 1; c < NC; ++c) {
+                            const float4 A0 = tile[cur][3 * (g + CG * c) + 1], A1 = tile[cur][3 * (g + CG * c + CG - 1) + 1];
+                            const float L = __builtin_fmaf(0.5f, A1.w, hv[r]);
+                            if ((4 * GW > SORTED_VBLOCK) && (4 * CG * c) % SORTED_VBLOCK == 0) {   // (blocks of more than one: their 0s)
+                                const float F = __builtin_fmaf(0.5f, A0.y, hv[r]);
+                                OA_VCHUNK_PASS(c, (__builtin_fmaxf(L, -F) > thr1[r]) & (__builtin_fabsf(__builtin_fmaf(0.5f, A0.x, hv[r])) > thr1[r]));
+                            } else {
+                                const float F = __builtin_fmaf(0.5f, A0.x, hv[r]);
+                                OA_VCHUNK_PASS(c, __builtin_fmaxf(L, -F) > thr1[r]);
+                            }
+                        }
+#undef OA_VCHUNK_PASS
+                    } else {                                       // padding at the tail (AV = 0 breaks the order): the chunks that hold a vertex
+#pragma unroll 1
+                        for (int c = 0; c < NC && 4 * CG * c < n_in; ++c) {
+                            cm |= (cmask_t)hit[r] << c;
+                            todo |= (cmask_t)1 << c;
+                        }
                     }
                     for (; todo; todo &= todo - 1) {
                         const int c = (NC > 32) ? __builtin_ctzll((unsigned long long)todo) : __builtin_ctz((uint32_t)todo);
                         const bool mine = (cm >> c) & 1;
 #pragma unroll 1
-                        for (int k = 4 * c; k < 4 * c + 4; ++k) {  // one group of 4 targets at a time
+                        for (int k = CG * c; k < CG * c + CG; ++k) {  // one group of 4 targets at a time
                             const float4 Q = tile[cur][3 * (g + k)], AV = tile[cur][3 * (g + k) + 1], W2 = tile[cur][3 * (g + k) + 2];
+                            bool want = mine;
+                            if (OA_SORTED_VREFINE && n_in >= 4 * GW && (4 * k) % SORTED_VBLOCK != 0) {   // the same test, per group
+                                const float F = __builtin_fmaf(0.5f, AV.x, hv[r]), L = __builtin_fmaf(0.5f, AV.w, hv[r]);
+                                want = want && !(__builtin_fmaxf(L, -F) > thr1[r]);
+                                if (!__ballot(want)) continue;
+                            }
                             const float4 AU = make_float4(-2.0f * Q.x, -2.0f * Q.y, -2.0f * Q.z, -2.0f * Q.w);   // exact
-                            if (mine)
+                            if (want)
                                 sorted_finish_group(AU, AV, W2, gbase + g + k, tf3s, tgs, tidx, px[r], py[r], pz[r], hu[r], hv[r], hd[r],
                                                     qmax, best[r], bidx[r], thr1[r], thr2[r]);
                         }
