@@ -29,6 +29,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include <mutex>
 #include <unordered_map>
 #include <thread>
+#include <type_traits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -422,6 +423,7 @@ struct oa_ctx {
     float4 *d_src4o = nullptr;       // the same points in the caller's (vlist) order -- only oa_make_pairs needs it
     int *d_perm = nullptr;           // sorted slot -> caller-order slot (nullptr: not sorted)
     unsigned short *d_worder = nullptr;   // k_sorted_wave_order: per wave of k_nn_search_sorted, its slots in the order of u (OA_NN_WAVE_ORDER=0: off)
+    int homes_cap = 0;               // blocks of source points d_homes holds
     int *d_homes = nullptr, *d_qcnt = nullptr;   // k_nn_search_sorted's work queue (oa_kernels.hpp): per block of source points its own split; the queues' counters
     bool nn_vchunk = true;           // OA_NN_VCHUNK: the sorted images' blocks in the order of v and k_nn_search_sorted's level 0v (0: as until round 6)
     int nn_persist = 4;              // OA_NN_PERSIST: workgroups per CU that work the queue off (0: one workgroup per item, in launch order -- as until round 6)
@@ -650,7 +652,6 @@ int check_ready(oa_ctx *c)
     return OA_OK;
 }
 
-bool grid_active(const oa_ctx *c);
 // every query through the tree: on request, and in auto mode for shards of up to `auto_max` points -- one wave per
 // query has far lower latency than the one-thread-per-query grid kernels until the waves no longer fit the chip
 // (measured crossover after the round-2 grid kernels: 3e3 .. 1.4e4 points for vertices -- the grid kernel spreads a
@@ -671,9 +672,8 @@ inline bool bvh_whole(const oa_ctx *c, bool ok, int auto_max)
 }
 int build_grid(oa_ctx *c);
 int build_safe_radii(oa_ctx *c);
-// Stable argsort of 30-bit Morton keys on the context's stream, no wait: v_out = the indices in the keys' stable ascending order
-// (v_in holds 0, 1, 2, ... at every call site and k_out, the sorted keys, is read by nobody: both stay in the signature for the
-// call sites' sake).  The library's own sorts (oa_sort.hpp): one workgroup up to SORT_SMALL_MAX keys, the three-pass LSD argsort
+// Stable argsort of keys of `bits` bits (30: Morton keys) on the context's stream, no wait: order = the indices in the keys' stable
+// ascending order.  The library's own sorts (oa_sort.hpp): one workgroup up to SORT_SMALL_MAX keys, the three-pass LSD argsort
 // above that; rounds 4-5 still fell back on rocprim outside 65k .. 3M keys -- 628 of the library's 749 kernels were its
 // instantiations.
 int sort_order_bits(oa_ctx *c, const unsigned *keys, int *order, size_t n, int bits)
@@ -682,10 +682,6 @@ int sort_order_bits(oa_ctx *c, const unsigned *keys, int *order, size_t n, int b
     if (n > (size_t)oa::SORT_SMALL_MAX) HIPCHK(tmp.alloc(oa::sort_order_tmp_bytes(n)));
     HIPCHK(oa::sort_order((void *)tmp.p, keys, order, n, bits, c->stream));
     return OA_OK;
-}
-int sort_pairs30(oa_ctx *c, const unsigned *k_in, unsigned *, const int *, int *v_out, size_t n)
-{
-    return sort_order_bits(c, k_in, v_out, n, 30);
 }
 // keys[0 .. n) (non-negative ints below 2^bits) -> sorted[] ascending and order[] = where each came from (stable)
 int sort_ints(oa_ctx *c, const int *keys, int *sorted, int *order, size_t n, int bits)
@@ -725,7 +721,6 @@ int tri_ring_lazy(oa_ctx *c, bool counting)
 }
 int build_bvh(oa_ctx *c, bool tri);
 int scan_counts(oa_ctx *c, const int *d_counts, int n, long long *d_off, DevTmp<char> &tmp);
-int launch_tri_search(oa_ctx *c, bool acc = false);
 
 // one wave per query: 4 queries per workgroup, workgroups loop when there are more queries than that
 inline unsigned bvh_blocks(const oa_ctx *c, bool listed, bool acc = false)
@@ -754,11 +749,13 @@ int launch_bvh(oa_ctx *c, const int *list, const int *list_count, int turn = -1,
         if (acc) { const int rcs = safe_radii_lazy(c); if (rcs) return rcs; }
         if (c->safe_ok && c->d_safe_by_idx && c->d_wsafe) { safe_by_idx = c->d_safe_by_idx; wsafe = c->d_wsafe; }
     }
-#define OA_BVH_ARGS c->d_state, c->d_src4, c->ns, TRI ? c->tbvh : c->bvh, TRI ? c->d_tbvh_box : c->d_bvh_box, TRI ? c->d_tbvh_prims : c->d_bvh_prims, \
-                    c->d_tri9, c->d_prev, TRI ? (float4 *)nullptr : c->d_win, c->d_keys, list, list_count, turn
-    if (acc) hipLaunchKernelGGL((oa::k_bvh_search<TRI, true>), dim3(blocks), dim3(1024), 0, c->stream, OA_BVH_ARGS, normal_test(c), c->d_partials, safe_by_idx, wsafe);
-    else hipLaunchKernelGGL((oa::k_bvh_search<TRI, false>), dim3(blocks), dim3(256), 0, c->stream, OA_BVH_ARGS, oa::NormalTest{}, (double *)nullptr, safe_by_idx, wsafe);
-#undef OA_BVH_ARGS
+    auto launch = [&](auto ACC, unsigned threads, const oa::NormalTest &nrm, double *partials) {
+        hipLaunchKernelGGL((oa::k_bvh_search<TRI, decltype(ACC)::value>), dim3(blocks), dim3(threads), 0, c->stream, c->d_state, c->d_src4, c->ns, TRI ? c->tbvh : c->bvh,
+                           TRI ? c->d_tbvh_box : c->d_bvh_box, TRI ? c->d_tbvh_prims : c->d_bvh_prims, c->d_tri9, c->d_prev, TRI ? (float4 *)nullptr : c->d_win, c->d_keys,
+                           list, list_count, turn, nrm, partials, safe_by_idx, wsafe);
+    };
+    if (acc) launch(std::true_type{}, 1024, normal_test(c), c->d_partials);
+    else launch(std::false_type{}, 256, oa::NormalTest{}, nullptr);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -790,11 +787,6 @@ inline int tri_lanes_for(const oa_ctx *c)
     }
     return lanes;
 }
-// does the loop's surface search go through the triangle grid (and not through the tree alone, or brute force)?
-inline bool tri_grid_active(const oa_ctx *c)
-{
-    return c->surface && c->tri_grid_ok && c->tbvh_ok && c->grid_mode != 0 && !bvh_whole(c, c->tbvh_ok, tri_tree_max(c));
-}
 
 // Workgroups of the canonical accumulation (k_pair_accumulate_canon, and the epilogue of k_nn_search_grid<L, true>): one
 // thread per (slot, lane of the query).  0 = the shard is too large for it (> ACC_MAX_BLOCKS rows before combining) or the
@@ -818,7 +810,31 @@ inline int canon_blocks(const oa_ctx *c)
     return b <= oa::ACC_MAX_BLOCKS ? (int)b : 0;
 }
 
-// What the loop's next search launch looks like.
+// A run-time value as a compile-time constant out of a closed list: f(std::integral_constant<int, V>{}) for the V among Others that
+// equals v, for Fallback when none does.  The list at a call site is what that site can launch; for the kernel templates of the
+// family units it has to stay within oa_families.hpp's list for the flavour (the linker says so when it does not).
+template <int Fallback, int... Others, typename F>
+inline void dispatch(int v, F &&f)
+{
+    const bool hit = ((v == Others ? (f(std::integral_constant<int, Others>{}), true) : false) || ...);
+    if (!hit) f(std::integral_constant<int, Fallback>{});
+}
+template <int V> using int_c = std::integral_constant<int, V>;
+constexpr std::true_type yes{};
+constexpr std::false_type no{};
+
+enum BruteKernel { BRUTE_PLAIN = 0, BRUTE_FILTERED = 1, BRUTE_MFMA = 2, BRUTE_SORTED = 3 };   // brute force over vertices (the values are OA_STAT_BRUTE_KERNEL's)
+BruteKernel brute_kernel(const oa_ctx *c)
+{
+    if (!c->filter_ok || !c->use_filter) return BRUTE_PLAIN;
+#if defined(OA_EXPERIMENTS)
+    if (c->nn_mfma && c->d_tfm && c->R == 4 && c->tile_groups == oa::FTILE_GROUPS) return BRUTE_MFMA;
+    if (!(c->nn_sort && c->d_tfs)) return BRUTE_FILTERED;
+#endif
+    return (c->nn_sort && c->d_tfs) ? BRUTE_SORTED : BRUTE_PLAIN;
+}
+
+// What the next search launch looks like: which search (loop and one-shot calls alike), and the loop's fusion plan.
 //   TREE   every query through the tree, which also accumulates (k_bvh_search<.., true>)
 //   DUAL   tree and grid both enqueued, DevState::tree_turn picks on the device; both accumulate; the grid search finishes
 //          its leftovers itself (it only has the turn once the pose has settled)
@@ -830,25 +846,41 @@ inline int canon_blocks(const oa_ctx *c)
 //          hand-over list, i.e. timing dependent -- never shows in a result.
 //   PLAIN  search, then accumulate (brute force; surface grid; shards too large for the canonical rows)
 enum SearchPlan { PLAN_PLAIN, PLAN_TREE, PLAN_DUAL, PLAN_GRID };
-SearchPlan search_plan(const oa_ctx *c)
+enum SearchKind { SEARCH_TREE, SEARCH_GRID, SEARCH_BRUTE };        // whole-shard tree | vertex / triangle grid, leftovers through the tree | SearchChoice::brute / k_tri_search_all
+struct SearchChoice {
+    SearchKind kind = SEARCH_BRUTE;
+    BruteKernel brute = BRUTE_PLAIN;
+    bool dual = false;              // SEARCH_GRID: tree and grid take turns (DevState::tree_turn)
+    int lanes = 1;                  // SEARCH_GRID: lanes per query
+    // triangle grid, experiments: a front search settles what it can and lists the rest; not while tree and grid take turns
+    bool settle_front = false;      // k_tri_settle (the settled-pose search, oa_tri_fine.hpp)
+    bool accept_front = false;      // k_tri_accept (seed + neighbour lists, oa_tri_ring.hpp), once the lists are built
+    SearchPlan plan = PLAN_PLAIN;   // a loop with fused_acc only
+};
+SearchChoice choose_search(const oa_ctx *c)
 {
-    if (!c->fused_acc || !c->loop_active || c->ns <= 0) return PLAN_PLAIN;
+    SearchChoice s;
+    s.brute = brute_kernel(c);
+    // (the grid searches hand their leftovers to the tree; mode 2 never gets to the grid arm: the whole-shard tree took it, or tree_ok is false)
+    const bool tree_ok = c->surface ? c->tbvh_ok : c->bvh_ok, grid_ok = c->surface ? c->tri_grid_ok : (c->grid_ok && c->filter_ok && c->use_filter);
+    if (bvh_whole(c, tree_ok, c->surface ? tri_tree_max(c) : vertex_tree_max(c))) s.kind = SEARCH_TREE;
+    else if (grid_ok && tree_ok && c->grid_mode != 0) {
+        s.kind = SEARCH_GRID;
+        s.dual = c->grid_mode == -1 && c->turns_on && c->ns <= (c->surface ? tri_tree_early(c) : vertex_tree_early(c));
+        s.lanes = c->surface ? tri_lanes_for(c) : grid_lanes_for(c);
+        s.settle_front = c->surface && c->tri_fine_ok && c->seeded && !s.dual;
+        s.accept_front = c->surface && c->tri_split && c->seeded && !s.dual;
+    }
+    if (!c->fused_acc || !c->loop_active || c->ns <= 0) return s;
     // (the accumulating tree search needs twice the registers of the plain one: worth it while the shard is small enough
     //  that occupancy does not matter -- 12k queries against 1M vertices: 58 us fused, 47 us search + accumulate)
-    const bool small = c->ns <= c->tree_acc_max;
-    if (c->surface) {
-        if (bvh_whole(c, c->tbvh_ok, tri_tree_max(c))) return small ? PLAN_TREE : PLAN_PLAIN;
-        // the triangle grid search with the accumulating epilogue: shards above the zone where tree and grid take turns
-        const bool dual = c->grid_mode == -1 && c->turns_on && c->ns <= tri_tree_early(c);
-        // (with the neighbour lists: k_tri_accept + the search of what it leaves, which has no accumulating form)
-        if (c->tri_ring_ok && c->tri_split && c->seeded) return PLAN_PLAIN;
-        // (the settled-pose search in front, oa_tri_fine.hpp: likewise k_tri_settle + the search of what it leaves)
-        if (c->tri_fine_ok && c->seeded && !dual && tri_grid_active(c)) return PLAN_PLAIN;
-        return (tri_grid_active(c) && !dual && canon_blocks(c) > 0 && c->tri_acc) ? PLAN_GRID : PLAN_PLAIN;
-    }
-    if (bvh_whole(c, c->bvh_ok, vertex_tree_max(c))) return small ? PLAN_TREE : PLAN_PLAIN;
-    if (!grid_active(c) || canon_blocks(c) == 0) return PLAN_PLAIN;
-    return (c->grid_mode == -1 && c->turns_on && c->ns <= vertex_tree_early(c)) ? PLAN_DUAL : PLAN_GRID;
+    if (s.kind == SEARCH_TREE) s.plan = c->ns <= c->tree_acc_max ? PLAN_TREE : PLAN_PLAIN;
+    else if (s.kind != SEARCH_GRID || canon_blocks(c) == 0) s.plan = PLAN_PLAIN;
+    else if (!c->surface) s.plan = s.dual ? PLAN_DUAL : PLAN_GRID;
+    // the triangle grid search with the accumulating epilogue: shards above the zone where tree and grid take turns, and no
+    // front search (k_tri_accept / k_tri_settle + the search of what they leave, which has no accumulating form)
+    else s.plan = (!s.dual && !(s.accept_front && c->tri_ring_ok) && !s.settle_front && c->tri_acc) ? PLAN_GRID : PLAN_PLAIN;
+    return s;
 }
 
 // PLAN_GRID: may this iteration's grid search finish its own leftovers?  Yes while the most any one wave handed over in
@@ -871,197 +903,184 @@ bool grid_fast_now(oa_ctx *c)
     return fast;
 }
 
-int launch_nn_impl(oa_ctx *c, bool acc);
-// acc: the search also accumulates (launch_search_accumulate decided so: no accumulation launch follows)
-int launch_nn(oa_ctx *c, bool acc = false)
-{
-    const int rc = launch_nn_impl(c, acc);
-    if (rc == OA_OK) { c->seeded = true; if (acc && !c->surface) c->win_seeds = true; }
-    return rc;
-}
-int launch_nn_impl(oa_ctx *c, bool acc)
-{
-    if (c->ns <= 0) return OA_OK;
-    if (c->surface) return launch_tri_search(c, acc);
-    dim3 grid(c->n_splits, c->ns_pad / (oa::NN_THREADS * c->R));
-    dim3 block(oa::NN_THREADS);
-    if (bvh_whole(c, c->bvh_ok, vertex_tree_max(c))) return launch_bvh<false>(c, nullptr, nullptr, -1, acc);
-    if (grid_active(c)) {
-        // the grid search settles the queries near the target; the rest (far away, or in crowded cells) go through the
-        // tree: in the loop by the wave that owns them (acc), in one-shot calls through a list that k_bvh_search finishes
-        if (!acc && !c->loop_active) HIPCHK(hipMemsetAsync(c->d_todo_count, 0, 2 * sizeof(int), c->stream));
-        const bool dual = c->grid_mode == -1 && c->turns_on && c->ns <= vertex_tree_early(c);
-        if (dual) { int rcb = launch_bvh<false>(c, nullptr, nullptr, 1, acc); if (rcb) return rcb; }   // runs when DevState::tree_turn
-        const int turn = dual ? 0 : -1;
-        const int lanes = grid_lanes_for(c);
-#define OA_GRID_ARGS c->d_state, c->d_src4, c->ns, c->gp, c->d_cell_start, c->d_sorted, c->d_win, c->d_keys, c->d_todo_list, c->d_todo_count, turn
-#define OA_GRID_ACC_ARGS OA_GRID_ARGS, c->bvh, (const float4 *)c->d_bvh_box, (const float4 *)c->d_bvh_prims, normal_test(c), c->d_partials
-        // {index, safe2} per slot beside the winner records: both or neither (OA_GRID_SAFE=0)
-        if (acc) { const int rcs = safe_radii_lazy(c); if (rcs) return rcs; }
-        const float *safe_by_idx = (c->grid_safe && c->safe_ok) ? c->d_safe_by_idx : nullptr;
-        uint2 *wsafe = safe_by_idx ? c->d_wsafe : nullptr;
-        if (!wsafe) safe_by_idx = nullptr;
-#define OA_GRID_SAFE_ARGS safe_by_idx, wsafe
-        const dim3 gblocks((unsigned)(((long long)c->ns * lanes + 255) / 256));
-        if (acc) {
-            const dim3 ablocks((unsigned)canon_blocks(c));
-            if (canon_threads(c) == 512) {
-                if (lanes == 4) hipLaunchKernelGGL((oa::k_nn_search_grid<4, true, 512>), ablocks, dim3(512), 0, c->stream, OA_GRID_ACC_ARGS, (unsigned long long *)nullptr, OA_GRID_SAFE_ARGS);
-                else if (lanes == 2) hipLaunchKernelGGL((oa::k_nn_search_grid<2, true, 512>), ablocks, dim3(512), 0, c->stream, OA_GRID_ACC_ARGS, (unsigned long long *)nullptr, OA_GRID_SAFE_ARGS);
 #if defined(OA_EXPERIMENTS)
-                else if (c->grid_stats) {                                // OA_GRID_STATS=1: instrumented launch, phase shares to stderr (synchronises)
-                    DevTmp<unsigned long long> d_stats;
-                    const size_t n_waves = (size_t)ablocks.x * 8;
-                    HIPCHK(d_stats.alloc(oa::GRID_STAT_N * n_waves));
-                    HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(unsigned long long) * oa::GRID_STAT_N * n_waves, c->stream));
-                    hipLaunchKernelGGL((oa::k_nn_search_grid<1, true, 512, true>), ablocks, dim3(512), 0, c->stream, OA_GRID_ACC_ARGS, d_stats.p, OA_GRID_SAFE_ARGS);
-                    HIPCHK(hipGetLastError());
-                    std::vector<unsigned long long> rows(oa::GRID_STAT_N * n_waves);
-                    { int rcr = read_small(c, rows.data(), d_stats, sizeof(unsigned long long) * rows.size()); if (rcr) return rcr; }
-                    unsigned long long h[oa::GRID_STAT_N] = { 0 };
-                    for (size_t w = 0; w < n_waves; ++w) for (int k = 0; k < oa::GRID_STAT_N; ++k) h[k] += rows[w * oa::GRID_STAT_N + (size_t)k];
-                    const double nw = (double)std::max(1ull, h[oa::GRID_STAT_WAVES]), ct = (double)std::max(1ull, h[oa::GRID_STAT_CYC_TOTAL]);
-                    fprintf(stderr, "[oa] vertex grid phases: %llu of %d queries settled by the seed's safe radius | per wave %.0f shader cycles, %.2f loop trips, %.2f scan trips, %.1f candidates per query (longest lane of a wave %.1f) | "
-                                    "prologue %.1f%% listing %.1f%% scan %.1f%% bookkeeping %.1f%% finish %.1f%% epilogue %.1f%% (loads + pair test %.1f%%, wave reduction %.1f%%, barrier %.1f%%)\n",
-                            h[oa::GRID_STAT_ACCEPTED], c->ns, ct / nw, h[oa::GRID_STAT_LOOP_TRIPS] / nw, h[oa::GRID_STAT_SCAN_TRIPS] / nw, h[oa::GRID_STAT_CANDIDATES] / (64.0 * nw),
-                            h[oa::GRID_STAT_MAX_LANE_CANDIDATES] / nw, 100.0 * h[oa::GRID_STAT_CYC_PROLOGUE] / ct, 100.0 * h[oa::GRID_STAT_CYC_LIST] / ct,
-                            100.0 * h[oa::GRID_STAT_CYC_SCAN] / ct, 100.0 * h[oa::GRID_STAT_CYC_BOOK] / ct, 100.0 * h[oa::GRID_STAT_CYC_FINISH] / ct,
-                            100.0 * h[oa::GRID_STAT_CYC_EPILOGUE] / ct, 100.0 * h[oa::GRID_STAT_CYC_EPI_PAIR] / ct, 100.0 * h[oa::GRID_STAT_CYC_EPI_REDUCE] / ct,
-                            100.0 * h[oa::GRID_STAT_CYC_EPI_BARRIER] / ct);
-                }
+// OA_GRID_STATS=1: launch(rows) enqueues an instrumented search that keeps one row of n_stat counters per wave (atomics on a dozen
+// shared words slowed the launch 8x); h[0 .. n_stat) = the sums over the n_waves rows.  Synchronises.
+template <typename Launch>
+int wave_stats(oa_ctx *c, int n_stat, size_t n_waves, unsigned long long *h, Launch &&launch)
+{
+    std::vector<unsigned long long> rows((size_t)n_stat * n_waves);
+    DevTmp<unsigned long long> d_rows;
+    HIPCHK(d_rows.alloc(rows.size()));
+    HIPCHK(hipMemsetAsync(d_rows, 0, sizeof(unsigned long long) * rows.size(), c->stream));
+    launch(d_rows.p);
+    HIPCHK(hipGetLastError());
+    { int rcr = read_small(c, rows.data(), d_rows, sizeof(unsigned long long) * rows.size()); if (rcr) return rcr; }
+    std::fill(h, h + n_stat, 0ull);
+    for (size_t w = 0; w < n_waves; ++w) for (int k = 0; k < n_stat; ++k) h[k] += rows[w * (size_t)n_stat + (size_t)k];
+    return OA_OK;
+}
+// the instrumented accumulating vertex grid search (one lane per query, 512 threads: 8 waves per workgroup): phase shares to stderr
+template <typename Launch>
+int vertex_grid_stats(oa_ctx *c, unsigned blocks, Launch &&launch)
+{
+    unsigned long long h[oa::GRID_STAT_N];
+    { const int rcs = wave_stats(c, oa::GRID_STAT_N, (size_t)blocks * 8, h, launch); if (rcs) return rcs; }
+    const double nw = (double)std::max(1ull, h[oa::GRID_STAT_WAVES]), ct = (double)std::max(1ull, h[oa::GRID_STAT_CYC_TOTAL]);
+    fprintf(stderr, "[oa] vertex grid phases: %llu of %d queries settled by the seed's safe radius | per wave %.0f shader cycles, %.2f loop trips, %.2f scan trips, %.1f candidates per query (longest lane of a wave %.1f) | "
+                    "prologue %.1f%% listing %.1f%% scan %.1f%% bookkeeping %.1f%% finish %.1f%% epilogue %.1f%% (loads + pair test %.1f%%, wave reduction %.1f%%, barrier %.1f%%)\n",
+            h[oa::GRID_STAT_ACCEPTED], c->ns, ct / nw, h[oa::GRID_STAT_LOOP_TRIPS] / nw, h[oa::GRID_STAT_SCAN_TRIPS] / nw, h[oa::GRID_STAT_CANDIDATES] / (64.0 * nw),
+            h[oa::GRID_STAT_MAX_LANE_CANDIDATES] / nw, 100.0 * h[oa::GRID_STAT_CYC_PROLOGUE] / ct, 100.0 * h[oa::GRID_STAT_CYC_LIST] / ct,
+            100.0 * h[oa::GRID_STAT_CYC_SCAN] / ct, 100.0 * h[oa::GRID_STAT_CYC_BOOK] / ct, 100.0 * h[oa::GRID_STAT_CYC_FINISH] / ct,
+            100.0 * h[oa::GRID_STAT_CYC_EPILOGUE] / ct, 100.0 * h[oa::GRID_STAT_CYC_EPI_PAIR] / ct, 100.0 * h[oa::GRID_STAT_CYC_EPI_REDUCE] / ct,
+            100.0 * h[oa::GRID_STAT_CYC_EPI_BARRIER] / ct);
+    return OA_OK;
+}
 #endif
-                else hipLaunchKernelGGL((oa::k_nn_search_grid<1, true, 512>), ablocks, dim3(512), 0, c->stream, OA_GRID_ACC_ARGS, (unsigned long long *)nullptr, OA_GRID_SAFE_ARGS);
-            } else {
-                if (lanes == 4) hipLaunchKernelGGL((oa::k_nn_search_grid<4, true, 256>), ablocks, dim3(256), 0, c->stream, OA_GRID_ACC_ARGS, (unsigned long long *)nullptr, OA_GRID_SAFE_ARGS);
-                else if (lanes == 2) hipLaunchKernelGGL((oa::k_nn_search_grid<2, true, 256>), ablocks, dim3(256), 0, c->stream, OA_GRID_ACC_ARGS, (unsigned long long *)nullptr, OA_GRID_SAFE_ARGS);
-                else hipLaunchKernelGGL((oa::k_nn_search_grid<1, true, 256>), ablocks, dim3(256), 0, c->stream, OA_GRID_ACC_ARGS, (unsigned long long *)nullptr, OA_GRID_SAFE_ARGS);
-            }
-            HIPCHK(hipGetLastError());
-            return OA_OK;
-        }
-        if (lanes == 4) hipLaunchKernelGGL((oa::k_nn_search_grid<4, false>), gblocks, dim3(256), 0, c->stream, OA_GRID_ARGS, oa::BvhParams{}, (const float4 *)nullptr, (const float4 *)nullptr, oa::NormalTest{}, (double *)nullptr, (unsigned long long *)nullptr, OA_GRID_SAFE_ARGS);
-        else if (lanes == 2) hipLaunchKernelGGL((oa::k_nn_search_grid<2, false>), gblocks, dim3(256), 0, c->stream, OA_GRID_ARGS, oa::BvhParams{}, (const float4 *)nullptr, (const float4 *)nullptr, oa::NormalTest{}, (double *)nullptr, (unsigned long long *)nullptr, OA_GRID_SAFE_ARGS);
-        else hipLaunchKernelGGL((oa::k_nn_search_grid<1, false>), gblocks, dim3(256), 0, c->stream, OA_GRID_ARGS, oa::BvhParams{}, (const float4 *)nullptr, (const float4 *)nullptr, oa::NormalTest{}, (double *)nullptr, (unsigned long long *)nullptr, OA_GRID_SAFE_ARGS);
-#undef OA_GRID_SAFE_ARGS
-#undef OA_GRID_ACC_ARGS
-#undef OA_GRID_ARGS
+
+// The grid search settles the queries near the target; the rest (far away, or in crowded cells) go through the tree: in the
+// loop by the wave that owns them (acc), in one-shot calls through a list that k_bvh_search finishes.
+int launch_vertex_grid(oa_ctx *c, const SearchChoice &s, bool acc)
+{
+    if (!acc && !c->loop_active) HIPCHK(hipMemsetAsync(c->d_todo_count, 0, 2 * sizeof(int), c->stream));
+    if (s.dual) { int rcb = launch_bvh<false>(c, nullptr, nullptr, 1, acc); if (rcb) return rcb; }   // runs when DevState::tree_turn
+    // {index, safe2} per slot beside the winner records: both or neither (OA_GRID_SAFE=0)
+    if (acc) { const int rcs = safe_radii_lazy(c); if (rcs) return rcs; }
+    const bool safe = c->grid_safe && c->safe_ok && c->d_safe_by_idx && c->d_wsafe;
+    // k_nn_search_grid<L, ACC, BT, STATS>; the accumulating form gets the tree, the pair test and the rows of partials
+    auto launch = [&](auto L, auto ACC, auto BT, auto STATS, unsigned blocks, unsigned long long *stats) {
+        constexpr bool A = decltype(ACC)::value;
+        hipLaunchKernelGGL((oa::k_nn_search_grid<decltype(L)::value, A, decltype(BT)::value, decltype(STATS)::value>), dim3(blocks), dim3(decltype(BT)::value), 0, c->stream,
+                           c->d_state, c->d_src4, c->ns, c->gp, c->d_cell_start, c->d_sorted, c->d_win, c->d_keys, c->d_todo_list, c->d_todo_count, s.dual ? 0 : -1,
+                           A ? c->bvh : oa::BvhParams{}, A ? (const float4 *)c->d_bvh_box : nullptr, A ? (const float4 *)c->d_bvh_prims : nullptr,
+                           A ? normal_test(c) : oa::NormalTest{}, A ? c->d_partials : nullptr, stats, safe ? c->d_safe_by_idx : nullptr, safe ? c->d_wsafe : nullptr);
+    };
+    if (!acc) {
+        dispatch<1, 2, 4>(s.lanes, [&](auto L) { launch(L, no, int_c<256>{}, no, (unsigned)(((long long)c->ns * s.lanes + 255) / 256), nullptr); });
         HIPCHK(hipGetLastError());
         return launch_bvh<false>(c, c->d_todo_list, c->d_todo_count);
     }
-    if (c->ns_pad / (oa::NN_THREADS * c->R) > 65535)               // only the brute-force launch has this limit (grid.y)
-        return fail(OA_E_BAD_ARG, "shard of %d points exceeds the brute-force launch grid (use more shards)", c->ns);
-#define OA_NN_ARGS c->d_state, c->d_src4, c->d_tg, c->n_groups_pad, c->d_keys
-#define OA_NNF_ARGS c->d_state, c->d_src4, c->d_tg, c->d_tf, c->d_tf3, (const float4 *)c->d_win, c->n_groups_pad, c->d_keys
+    const unsigned ablocks = (unsigned)canon_blocks(c);
 #if defined(OA_EXPERIMENTS)
-    if (c->filter_ok && c->use_filter && c->nn_mfma && c->d_tfm && c->R == 4 && c->tile_groups == oa::FTILE_GROUPS) {
-#define OA_MFMA_ARGS c->d_state, c->d_src4, c->d_tg, (const oa::half8 *)c->d_tfm, (const float4 *)c->d_win, c->n_groups_pad, c->mfma_sigma, c->d_keys
-        if (c->mfma_wps == 2) hipLaunchKernelGGL(oa::k_nn_search_mfma<2>, grid, block, 0, c->stream, OA_MFMA_ARGS);
-        else if (c->mfma_wps == 3) hipLaunchKernelGGL(oa::k_nn_search_mfma<3>, grid, block, 0, c->stream, OA_MFMA_ARGS);
-        else hipLaunchKernelGGL(oa::k_nn_search_mfma<4>, grid, block, 0, c->stream, OA_MFMA_ARGS);
-#undef OA_MFMA_ARGS
-    } else
+    if (c->grid_stats && s.lanes == 1 && canon_threads(c) == 512)
+        return vertex_grid_stats(c, ablocks, [&](unsigned long long *stats) { launch(int_c<1>{}, yes, int_c<512>{}, yes, ablocks, stats); });
 #endif
-    if (c->filter_ok && c->use_filter && c->nn_sort && c->d_tfs) {
-        const bool small = (c->tile_groups == 64);
-#define OA_NNS_ARGS c->d_state, c->d_src4, (const float4 *)c->d_tgs, (const float4 *)c->d_tfs, (const float4 *)c->d_tf3s, (const int4 *)c->d_tidx, \
-                    (const float4 *)c->d_win, c->n_groups_pad, c->sax[0], c->sax[1], c->d_keys
-        // with seeds: one launch over n_splits_seeded splits.  Without (the first search of a loop): k_nn_seed_sorted -- every point
-        // against the tile that holds its own slab --, then the whole search seeded from what that left in keys (OA_NN_HOME_PASS=0:
-        // one unseeded launch over n_splits splits, as until r05z)
-        const bool two = !c->win_seeds && c->nn_home_pass && c->n_splits_seeded > 1;
-        dim3 sgrid((unsigned)((c->win_seeds || two) ? c->n_splits_seeded : c->n_splits), grid.y);
-        int pass = 0;
-#define OA_LAUNCH_S(RR)                                                                                              \
-        do {                                                                                                         \
-            if (small && c->nn_vchunk) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, 64, true>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt, c->nt);  \
-            else if (small) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, 64, false>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt, c->nt);  \
-            else if (c->nn_vchunk) hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, oa::FTILE_GROUPS, true>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt, c->nt); \
-            else hipLaunchKernelGGL((oa::k_nn_search_sorted<RR, oa::FTILE_GROUPS, false>), sgrid, block, 0, c->stream, OA_NNS_ARGS, pass, worder, q_splits, q_blocks, homes, qcnt, c->nt); \
-        } while (0)
-#if defined(OA_EXPERIMENTS)
-#define OA_LAUNCH_S_CASE8 case 8: OA_LAUNCH_S(8); break;
-#else
-#define OA_LAUNCH_S_CASE8
-#endif
-#define OA_LAUNCH_S_R()                     \
-        switch (c->R) {                     \
-        case 1: OA_LAUNCH_S(1); break;      \
-        case 2: OA_LAUNCH_S(2); break;      \
-        OA_LAUNCH_S_CASE8                   \
-        default: OA_LAUNCH_S(4); break;     \
-        }
-        // the waves' slots in the order of u at this pose (k_sorted_wave_order: ~10 us in front of a 30 ms search)
-        const unsigned short *worder = nullptr;
-        if (c->d_worder && c->R >= 2) {
-            const dim3 ob((unsigned)(c->ns_pad / (64 * c->R)));
-            switch (c->R) {
-            case 2: hipLaunchKernelGGL(oa::k_sorted_wave_order<2>, ob, dim3(64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->sax[0], c->d_worder); break;
-            case 8: hipLaunchKernelGGL(oa::k_sorted_wave_order<8>, ob, dim3(64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->sax[0], c->d_worder); break;
-            default: hipLaunchKernelGGL(oa::k_sorted_wave_order<4>, ob, dim3(64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->sax[0], c->d_worder); break;
-            }
-            HIPCHK(hipGetLastError());
-            worder = c->d_worder;
-        }
-        // long launches go through the work queue (oa_kernels.hpp): as many workgroups as the chip holds, the long items first
-        const int q_splits = (int)sgrid.x, q_blocks = (int)sgrid.y;
-        const long long q_wgs = (long long)c->n_cu * std::min(c->nn_persist, c->R <= 4 ? 4 : 2);
-        const bool queued = q_wgs > 0 && q_splits > 1 && (long long)q_splits * q_blocks >= (c->nn_queue_min >= 0 ? (long long)c->nn_queue_min : 4 * q_wgs);
-        c->last_queue_wgs = queued ? (int)q_wgs : 0;
-        if (queued) {
-            if (!c->d_homes) HIPCHK(dev_malloc(&c->d_homes, sizeof(int) * (size_t)q_blocks));
-            if (!c->d_qcnt) HIPCHK(dev_malloc(&c->d_qcnt, sizeof(int) * (size_t)(oa::SORTED_QUEUES * oa::SORTED_QUEUE_STRIDE)));
-            hipLaunchKernelGGL(oa::k_sorted_block_homes, dim3((unsigned)((std::max(q_blocks, oa::SORTED_QUEUES) + 63) / 64)), dim3(64), 0, c->stream,
-                               (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, q_blocks, oa::NN_THREADS * c->R, (const float4 *)c->d_tfs,
-                               c->n_groups_pad, c->tile_groups, c->sax[0], q_splits, c->d_homes, c->d_qcnt);
-            HIPCHK(hipGetLastError());
-            sgrid = dim3((unsigned)q_wgs);
-        }
-        const int *homes = queued ? c->d_homes : nullptr;
-        int *qcnt = queued ? c->d_qcnt : nullptr;
-        if (two) {
-            const dim3 sb((unsigned)((c->ns_pad + 255) / 256));
-            if (small) hipLaunchKernelGGL((oa::k_nn_seed_sorted<64>), sb, dim3(256), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->ns_pad,
-                                          (const float4 *)c->d_tgs, (const float4 *)c->d_tfs, (const int4 *)c->d_tidx, c->n_groups_pad, c->sax[0], c->d_keys);
-            else hipLaunchKernelGGL((oa::k_nn_seed_sorted<oa::FTILE_GROUPS>), sb, dim3(256), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->ns_pad,
-                                    (const float4 *)c->d_tgs, (const float4 *)c->d_tfs, (const int4 *)c->d_tidx, c->n_groups_pad, c->sax[0], c->d_keys);
-            HIPCHK(hipGetLastError());
-            pass = 2;
-        }
-        OA_LAUNCH_S_R();
-#undef OA_LAUNCH_S_R
-#undef OA_LAUNCH_S_CASE8
-#undef OA_LAUNCH_S
-#undef OA_NNS_ARGS
-    }
-#if defined(OA_EXPERIMENTS)
-    else if (c->filter_ok && c->use_filter) {
-        const bool small = (c->tile_groups == 64);
-#define OA_LAUNCH_F(RR)                                                                                              \
-        do {                                                                                                         \
-            if (small) hipLaunchKernelGGL((oa::k_nn_search_filtered<RR, 64>), grid, block, 0, c->stream, OA_NNF_ARGS); \
-            else hipLaunchKernelGGL((oa::k_nn_search_filtered<RR, oa::FTILE_GROUPS>), grid, block, 0, c->stream, OA_NNF_ARGS); \
-        } while (0)
-        switch (c->R) {
-        case 1: OA_LAUNCH_F(1); break;
-        case 2: OA_LAUNCH_F(2); break;
-        case 8: OA_LAUNCH_F(8); break;
-        default: OA_LAUNCH_F(4); break;
-        }
-#undef OA_LAUNCH_F
-    }
-#endif
-    else {
-        switch (c->R) {
-        case 1: hipLaunchKernelGGL(oa::k_nn_search<1>, grid, block, 0, c->stream, OA_NN_ARGS); break;
-        case 2: hipLaunchKernelGGL(oa::k_nn_search<2>, grid, block, 0, c->stream, OA_NN_ARGS); break;
-        case 8: hipLaunchKernelGGL(oa::k_nn_search<8>, grid, block, 0, c->stream, OA_NN_ARGS); break;
-        default: hipLaunchKernelGGL(oa::k_nn_search<4>, grid, block, 0, c->stream, OA_NN_ARGS); break;
-        }
-    }
-#undef OA_NN_ARGS
-#undef OA_NNF_ARGS
+    dispatch<256, 512>(canon_threads(c), [&](auto BT) { dispatch<1, 2, 4>(s.lanes, [&](auto L) { launch(L, yes, BT, no, ablocks, nullptr); }); });
     HIPCHK(hipGetLastError());
     return OA_OK;
+}
+
+// k_nn_search_sorted's work queue (oa_kernels.hpp): d_homes for `blocks` blocks of source points + the queues' counters, both rewritten by
+// k_sorted_block_homes in front of every queued launch.  They come with the source in brute-force mode (source_reset, oa_set_search_mode: never
+// inside a loop, see safe_radii_lazy); the other modes get here at first use (a target without usable grid or tree), or should the blocks outgrow them.
+int ensure_queue_buffers(oa_ctx *c, int blocks)
+{
+    if (blocks > c->homes_cap) {
+        dev_free(c->d_homes); c->homes_cap = 0;
+        HIPCHK(dev_malloc(&c->d_homes, sizeof(int) * (size_t)blocks));
+        c->homes_cap = blocks;
+    }
+    if (!c->d_qcnt) HIPCHK(dev_malloc(&c->d_qcnt, sizeof(int) * (size_t)(oa::SORTED_QUEUES * oa::SORTED_QUEUE_STRIDE)));
+    return OA_OK;
+}
+
+// The sorted brute-force search: wave order -> block homes (queued launches) -> seed pass (the first search of a loop) -> search
+int launch_brute_sorted(oa_ctx *c, const dim3 grid)
+{
+    // with seeds: one launch over n_splits_seeded splits.  Without (the first search of a loop): k_nn_seed_sorted -- every point
+    // against the tile that holds its own slab --, then the whole search seeded from what that left in keys (OA_NN_HOME_PASS=0:
+    // one unseeded launch over n_splits splits, as until r05z)
+    const bool two = !c->win_seeds && c->nn_home_pass && c->n_splits_seeded > 1;
+    dim3 sgrid((unsigned)((c->win_seeds || two) ? c->n_splits_seeded : c->n_splits), grid.y);
+    // the waves' slots in the order of u at this pose (k_sorted_wave_order: ~10 us in front of a 30 ms search)
+    const bool ordered = c->d_worder && c->R >= 2;
+    if (ordered) {
+        const dim3 ob((unsigned)(c->ns_pad / (64 * c->R)));
+        dispatch<4, 2, 8>(c->R, [&](auto R) {
+            hipLaunchKernelGGL((oa::k_sorted_wave_order<decltype(R)::value>), ob, dim3(64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->sax[0], c->d_worder);
+        });
+        HIPCHK(hipGetLastError());
+    }
+    // long launches go through the work queue (oa_kernels.hpp): as many workgroups as the chip holds, the long items first
+    const int q_splits = (int)sgrid.x, q_blocks = (int)sgrid.y;
+    const long long q_wgs = (long long)c->n_cu * std::min(c->nn_persist, c->R <= 4 ? 4 : 2);
+    const bool queued = q_wgs > 0 && q_splits > 1 && (long long)q_splits * q_blocks >= (c->nn_queue_min >= 0 ? (long long)c->nn_queue_min : 4 * q_wgs);
+    c->last_queue_wgs = queued ? (int)q_wgs : 0;
+    if (queued) {
+        { const int rcq = ensure_queue_buffers(c, q_blocks); if (rcq) return rcq; }
+        hipLaunchKernelGGL(oa::k_sorted_block_homes, dim3((unsigned)((std::max(q_blocks, oa::SORTED_QUEUES) + 63) / 64)), dim3(64), 0, c->stream,
+                           (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, q_blocks, oa::NN_THREADS * c->R, (const float4 *)c->d_tfs,
+                           c->n_groups_pad, c->tile_groups, c->sax[0], q_splits, c->d_homes, c->d_qcnt);
+        HIPCHK(hipGetLastError());
+        sgrid = dim3((unsigned)q_wgs);
+    }
+    const int pass = two ? 2 : 0;                                   // (seeded from what the seed pass leaves in keys)
+    if (two) {
+        const dim3 sb((unsigned)((c->ns_pad + 255) / 256));
+        dispatch<oa::FTILE_GROUPS, 64>(c->tile_groups, [&](auto TG) {
+            hipLaunchKernelGGL((oa::k_nn_seed_sorted<decltype(TG)::value>), sb, dim3(256), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->ns_pad,
+                               (const float4 *)c->d_tgs, (const float4 *)c->d_tfs, (const int4 *)c->d_tidx, c->n_groups_pad, c->sax[0], c->d_keys);
+        });
+        HIPCHK(hipGetLastError());
+    }
+    auto launch = [&](auto R, auto TG, auto VCHUNK) {
+        hipLaunchKernelGGL((oa::k_nn_search_sorted<decltype(R)::value, decltype(TG)::value, decltype(VCHUNK)::value>), sgrid, dim3(oa::NN_THREADS), 0, c->stream,
+                           c->d_state, c->d_src4, (const float4 *)c->d_tgs, (const float4 *)c->d_tfs, (const float4 *)c->d_tf3s, (const int4 *)c->d_tidx,
+                           (const float4 *)c->d_win, c->n_groups_pad, c->sax[0], c->sax[1], c->d_keys, pass, ordered ? c->d_worder : nullptr, q_splits, q_blocks, queued ? c->d_homes : nullptr, queued ? c->d_qcnt : nullptr, c->nt);
+    };
+    auto search = [&](auto R) { dispatch<oa::FTILE_GROUPS, 64>(c->tile_groups, [&](auto TG) { if (c->nn_vchunk) launch(R, TG, yes); else launch(R, TG, no); }); };
+#if defined(OA_EXPERIMENTS)
+    dispatch<4, 1, 2, 8>(c->R, search);
+#else
+    dispatch<4, 1, 2>(c->R, search);                                // (8 points per thread: an OA_EXPERIMENTS instantiation; oa_create turns OA_NN_R=8 into 4)
+#endif
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+
+// brute force over the target's vertices: one thread per R source points, n_splits slices of the target
+int launch_brute(oa_ctx *c, const SearchChoice &s)
+{
+    const dim3 grid(c->n_splits, c->ns_pad / (oa::NN_THREADS * c->R)), block(oa::NN_THREADS);
+    if (grid.y > 65535)                                             // only the brute-force launch has this limit (grid.y)
+        return fail(OA_E_BAD_ARG, "shard of %d points exceeds the brute-force launch grid (use more shards)", c->ns);
+    switch (s.brute) {
+    case BRUTE_SORTED: return launch_brute_sorted(c, grid);
+#if defined(OA_EXPERIMENTS)
+    case BRUTE_MFMA:
+        dispatch<4, 2, 3>(c->mfma_wps, [&](auto WPS) {
+            hipLaunchKernelGGL((oa::k_nn_search_mfma<decltype(WPS)::value>), grid, block, 0, c->stream, c->d_state, c->d_src4, c->d_tg, (const oa::half8 *)c->d_tfm, (const float4 *)c->d_win, c->n_groups_pad, c->mfma_sigma, c->d_keys);
+        });
+        break;
+    case BRUTE_FILTERED:
+        dispatch<4, 1, 2, 8>(c->R, [&](auto R) {
+            dispatch<oa::FTILE_GROUPS, 64>(c->tile_groups, [&](auto TG) {
+                hipLaunchKernelGGL((oa::k_nn_search_filtered<decltype(R)::value, decltype(TG)::value>), grid, block, 0, c->stream, c->d_state, c->d_src4, c->d_tg, c->d_tf, c->d_tf3, (const float4 *)c->d_win, c->n_groups_pad, c->d_keys);
+            });
+        });
+        break;
+#endif
+    default:
+        dispatch<4, 1, 2, 8>(c->R, [&](auto R) {
+            hipLaunchKernelGGL((oa::k_nn_search<decltype(R)::value>), grid, block, 0, c->stream, c->d_state, c->d_src4, c->d_tg, c->n_groups_pad, c->d_keys);
+        });
+        break;
+    }
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+
+int launch_tri_search(oa_ctx *c, const SearchChoice &s, bool acc);
+// One search of the shard as `s` says.  acc: the search also accumulates (launch_search_accumulate decided so: no accumulation
+// launch follows)
+int launch_nn(oa_ctx *c, const SearchChoice &s, bool acc)
+{
+    int rc = OA_OK;                                                 // (no points: nothing to search; the flags below are set all the same)
+    if (c->ns > 0 && s.kind == SEARCH_TREE) rc = c->surface ? launch_bvh<true>(c, nullptr, nullptr, -1, acc) : launch_bvh<false>(c, nullptr, nullptr, -1, acc);
+    else if (c->ns > 0 && c->surface) rc = launch_tri_search(c, s, acc);
+    else if (c->ns > 0) rc = s.kind == SEARCH_GRID ? launch_vertex_grid(c, s, acc) : launch_brute(c, s);
+    if (rc == OA_OK) { c->seeded = true; if (acc && !c->surface) c->win_seeds = true; }
+    return rc;
 }
 
 int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
@@ -1115,19 +1134,19 @@ int launch_search_accumulate(oa_ctx *c, bool timed, oa::RowSel &sel, bool &fused
     // brute-force kernel (50 ms per launch), not for the grid / tree searches, whose launches are that short
     // themselves -- those are timed on the GPU instead (DevState::t_prev_end / t_acc_start, StepRecord::search_ticks)
     timed = timed && c->time_events;
-    const SearchPlan plan = search_plan(c);
-    fused = plan == PLAN_TREE || plan == PLAN_DUAL || (plan == PLAN_GRID && grid_fast_now(c));
+    const SearchChoice s = choose_search(c);
+    fused = s.plan == PLAN_TREE || s.plan == PLAN_DUAL || (s.plan == PLAN_GRID && grid_fast_now(c));
     c->iter_enq++;
     // the lazy safe radii: counted once per iteration, whatever the plan launches (tree and grid in turns count once; shards too
     // large for the fused path -- BASELINE config 5 on one GPU -- count too: their plain grid search takes seeds on their radii
     // all the same); brute force never reads them
     if (!c->surface && c->grid_ok && c->grid_mode != 0) { ++c->target_iters; if ((rc = safe_radii_lazy(c))) return rc; }
-    if (plan == PLAN_GRID && fused) c->fast_iters++;
+    if (s.plan == PLAN_GRID && fused) c->fast_iters++;
     if (timed) {
         if ((rc = ensure_events(c, c->ev_used + 1))) return rc;
         HIPCHK(hipEventRecord(c->ev[2 * c->ev_used], c->stream));
     }
-    if ((rc = launch_nn(c, fused))) return rc;
+    if ((rc = launch_nn(c, s, fused))) return rc;
     if (timed) {
         HIPCHK(hipEventRecord(c->ev[2 * c->ev_used + 1], c->stream));
         c->ev_used++;
@@ -1138,8 +1157,8 @@ int launch_search_accumulate(oa_ctx *c, bool timed, oa::RowSel &sel, bool &fused
         return OA_OK;
     }
     const int tree_rows = (int)bvh_blocks(c, false, true);
-    if (plan == PLAN_TREE) sel = oa::RowSel{ tree_rows, 0, 0 };
-    else sel = oa::RowSel{ canon_blocks(c), plan == PLAN_DUAL ? tree_rows : 0, plan == PLAN_DUAL ? 1 : 0 };
+    if (s.plan == PLAN_TREE) sel = oa::RowSel{ tree_rows, 0, 0 };
+    else sel = oa::RowSel{ canon_blocks(c), s.plan == PLAN_DUAL ? tree_rows : 0, s.plan == PLAN_DUAL ? 1 : 0 };
     return OA_OK;
 }
 
@@ -1259,8 +1278,8 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
     c->fast_iters = 0;
     c->h_hist_valid = false;
     {
-        const bool brute = !c->surface ? !(bvh_whole(c, c->bvh_ok, vertex_tree_max(c)) || grid_active(c))
-                                       : (c->grid_mode == 0 || !c->tbvh_ok);
+        // (surfaces: NOT kind == SEARCH_BRUTE -- a mesh with a tree but no grid counts as a tree search here, as it always has)
+        const bool brute = !c->surface ? choose_search(c).kind == SEARCH_BRUTE : (c->grid_mode == 0 || !c->tbvh_ok);
         c->time_events = env_int("OA_TIME_EVENTS", brute ? 1 : 0) != 0;
     }
     c->loop_active = true;
@@ -1926,7 +1945,7 @@ int multi_group_loop(oa_ctx *p, size_t g, const oa_settings *st)
     Exchange *x = p->xch;
     oa_ctx *c0 = p->subs[(size_t)group[0]];
     // (the adaptive grid path needs recent news from the device too: then the host stays close even without early exit)
-    bool poll = c0->h_poll && env_int("OA_RUN_POLL", 1) && (st->early_exit || (search_plan(c0) == PLAN_GRID && c0->grid_path == 0));
+    bool poll = c0->h_poll && env_int("OA_RUN_POLL", 1) && (st->early_exit || (choose_search(c0).plan == PLAN_GRID && c0->grid_path == 0));
     const int lag = 2;
     volatile int32_t *progress = c0->h_poll;
     for (int it = 0; it < st->iters; ++it) {
@@ -2232,10 +2251,11 @@ OA_EXPORT int oa_set_search_mode(oa_ctx *c, int mode)
         if (rc) return rc;
         if ((rc = build_sorted_images(c))) return rc;
     }
-    if (mode == 0 && c->nn_wave_order && !c->d_worder && c->ns_pad > 0 && c->d_src4) {   // (a source uploaded for the other modes)
-        const int rc = use_device(c);
+    if (mode == 0 && c->ns_pad > 0 && c->d_src4) {                  // (a source uploaded for the other modes: what source_reset allocates for this one)
+        int rc = use_device(c);
         if (rc) return rc;
-        HIPCHK(dev_malloc(&c->d_worder, sizeof(unsigned short) * (size_t)c->ns_pad));
+        if (c->nn_wave_order && !c->d_worder) HIPCHK(dev_malloc(&c->d_worder, sizeof(unsigned short) * (size_t)c->ns_pad));
+        if ((rc = ensure_queue_buffers(c, c->ns_pad / (oa::NN_THREADS * c->R)))) return rc;
     }
     if (rebuild) {                                   // the grids were skipped when the target was uploaded
         int rc = use_device(c);
@@ -2301,13 +2321,13 @@ int build_sorted_images(oa_ctx *c)
     c->sax[0] = su; c->sax[2] = sd; c->sax[1] = 3 - su - sd;
     const double ext = hi[su] - lo[su];
     const int blocks = (c->n_groups_pad + 255) / 256;
-    DevTmp<unsigned> k_in, k_out;
+    DevTmp<unsigned> k_in;
     DevTmp<int> v_in, v_out;
-    HIPCHK(k_in.alloc((size_t)c->nt)); HIPCHK(k_out.alloc((size_t)c->nt)); HIPCHK(v_in.alloc((size_t)c->nt)); HIPCHK(v_out.alloc((size_t)c->nt));
+    HIPCHK(k_in.alloc((size_t)c->nt)); HIPCHK(v_in.alloc((size_t)c->nt)); HIPCHK(v_out.alloc((size_t)c->nt));
     hipLaunchKernelGGL(oa::k_sort_keys_axis, dim3((c->nt + 255) / 256), dim3(256), 0, c->stream, (const float *)c->d_tgt_xyz, c->nt, su, lo[su],
                        ext > 0.0 ? 1073741823.0 / ext : 0.0, k_in.p, v_in.p);
     HIPCHK(hipGetLastError());
-    { const int rcs = sort_pairs30(c, k_in.p, k_out.p, v_in.p, v_out.p, (size_t)c->nt); if (rcs) return rcs; }
+    { const int rcs = sort_order_bits(c, k_in.p, v_out.p, (size_t)c->nt, 30); if (rcs) return rcs; }
     if (c->nn_vchunk) {                                           // every block of the u order by v, its first vertex kept (k_sort_blocks_v)
         hipLaunchKernelGGL(oa::k_sort_blocks_v, dim3((unsigned)((c->nt + oa::SORTED_VBLOCK - 1) / oa::SORTED_VBLOCK)), dim3(oa::SORTED_VBLOCK), 0,
                            c->stream, (const float *)c->d_tgt_xyz, c->nt, c->sax[1], c->tc[c->sax[1]], v_out.p);
@@ -2490,12 +2510,6 @@ int build_grid(oa_ctx *c)
     return OA_OK;
 }
 
-bool grid_active(const oa_ctx *c)
-{
-    if (!c->grid_ok || !c->bvh_ok || !c->filter_ok || !c->use_filter || c->grid_mode == 0) return false;
-    if (c->grid_mode == 2) return false;
-    return true;                                                      // auto: shards of <= 32768 points took the tree already
-}
 // vertex_index = false: the caller (oa_set_target_mesh) searches triangles; the vertex grid and vertex tree would never
 // be used (their build is ~40 % of a mesh upload)
 int set_target_common(oa_ctx *c, const float *xyz, int64_t n, int on_device, bool vertex_index)
@@ -2611,16 +2625,16 @@ int build_bvh(oa_ctx *c, bool tri)
     bp.scale = scale;
     bp.slack = 1e-10 * scale + 1e-300;
     const int n_pad = bp.cnt[1] * oa::BVH_W;
-    DevTmp<unsigned> k_in, k_out;
+    DevTmp<unsigned> k_in;
     DevTmp<int> v_in, v_out;
-    HIPCHK(k_in.alloc((size_t)n)); HIPCHK(k_out.alloc((size_t)n)); HIPCHK(v_in.alloc((size_t)n)); HIPCHK(v_out.alloc((size_t)n));
+    HIPCHK(k_in.alloc((size_t)n)); HIPCHK(v_in.alloc((size_t)n)); HIPCHK(v_out.alloc((size_t)n));
     const dim3 blk(256), grd((unsigned)((n + 255) / 256));
     if (tri) hipLaunchKernelGGL(oa::k_bvh_keys<true>, grd, blk, 0, c->stream, (const float *)c->d_tgt_xyz, (const float4 *)c->d_tri9,
                                 n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
     else hipLaunchKernelGGL(oa::k_bvh_keys<false>, grd, blk, 0, c->stream, (const float *)c->d_tgt_xyz, (const float4 *)nullptr,
                             n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
     HIPCHK(hipGetLastError());
-    { const int rcs = sort_pairs30(c, k_in.p, k_out.p, v_in.p, v_out.p, (size_t)n); if (rcs) return rcs; }
+    { const int rcs = sort_order_bits(c, k_in.p, v_out.p, (size_t)n, 30); if (rcs) return rcs; }
     HIPCHK(dev_malloc(&d_prims, sizeof(float4) * (tri ? 3 : 1) * (size_t)n_pad));
     HIPCHK(dev_malloc(&d_box, sizeof(float4) * 2 * (size_t)total));
     const dim3 grd_pad((unsigned)((n_pad + 255) / 256));
@@ -2681,15 +2695,15 @@ int spatial_shard_members(oa_ctx *c, const float *d_xyz, long long n_verts, cons
     const int n = (int)n_sel;
     DevTmp<float4> all4;
     DevTmp<int> all_sel, v_in, order, picked;
-    DevTmp<unsigned> k_in, k_out;
+    DevTmp<unsigned> k_in;
     HIPCHK(all4.alloc((size_t)n)); HIPCHK(all_sel.alloc((size_t)n)); HIPCHK(v_in.alloc((size_t)n)); HIPCHK(order.alloc((size_t)n));
-    HIPCHK(k_in.alloc((size_t)n)); HIPCHK(k_out.alloc((size_t)n));
+    HIPCHK(k_in.alloc((size_t)n));
     hipLaunchKernelGGL(oa::k_pack_source, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_xyz, d_vlist, step, 0ll,
                        (const int *)nullptr, n, n, all4.p, all_sel.p);
     hipLaunchKernelGGL(oa::k_morton_keys, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float4 *)all4.p, n,
                        lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
     HIPCHK(hipGetLastError());
-    { const int rcs = sort_pairs30(c, k_in.p, k_out.p, v_in.p, order.p, (size_t)n); if (rcs) return rcs; }
+    { const int rcs = sort_order_bits(c, k_in.p, order.p, (size_t)n, 30); if (rcs) return rcs; }
     // this shard's range of the order, back in ascending selection position (= the caller's order inside the shard)
     HIPCHK(members.alloc((size_t)count));
     DevTmp<int> ord2;
@@ -2705,14 +2719,14 @@ int sort_source_slots(oa_ctx *c, const float *d_xyz, long long n_verts)
     bool ok = false;
     int rcf = morton_frame(c, d_xyz, n_verts, lo, sc, ok);
     if (rcf || !ok) return rcf;
-    DevTmp<unsigned> k_in, k_out;
+    DevTmp<unsigned> k_in;
     DevTmp<int> v_in;
-    HIPCHK(k_in.alloc((size_t)c->ns)); HIPCHK(k_out.alloc((size_t)c->ns)); HIPCHK(v_in.alloc((size_t)c->ns));
+    HIPCHK(k_in.alloc((size_t)c->ns)); HIPCHK(v_in.alloc((size_t)c->ns));
     HIPCHK(dev_malloc(&c->d_perm, sizeof(int) * (size_t)c->ns));
     hipLaunchKernelGGL(oa::k_morton_keys, dim3((c->ns + 255) / 256), dim3(256), 0, c->stream, (const float4 *)c->d_src4, c->ns,
                        lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
     HIPCHK(hipGetLastError());
-    { const int rcs = sort_pairs30(c, k_in.p, k_out.p, v_in.p, c->d_perm, (size_t)c->ns); if (rcs) return rcs; }
+    { const int rcs = sort_order_bits(c, k_in.p, c->d_perm, (size_t)c->ns, 30); if (rcs) return rcs; }
     // d_src4 / d_sel become the sorted images: the packed buffers change names (they ARE the caller-order copy now) and
     // k_apply_perm fills new ones -- every slot up to ns_pad -- instead of two device-to-device copies in front of it
     // (both new buffers first, the context's pointers only when both exist: a failed allocation leaves the unsorted source in
@@ -2980,154 +2994,142 @@ int build_tri_ring(oa_ctx *c)
 #endif
 }
 
-int launch_tri_search(oa_ctx *c, bool acc)
+#if defined(OA_EXPERIMENTS)
+// The settled-pose search (oa_tri_fine.hpp) in front: one thread per query, its own cell's list of whole triangles; what it
+// does not settle (reach beyond the lists' inflation, crowded cells, no seed) is the list the grid search works through
+int launch_tri_settle(oa_ctx *c, int &qcap)
 {
-    if (bvh_whole(c, c->tbvh_ok, tri_tree_max(c))) return launch_bvh<true>(c, nullptr, nullptr, -1, acc);
-    const bool use_grid = c->tri_grid_ok && c->tbvh_ok && c->grid_mode != 0;
+    const dim3 sblocks((unsigned)(((long long)c->ns * 4 + 255) / 256));     // four lanes per query
+    qcap = oa::ulist_cap((int)sblocks.x * 4, 16);                   // 16 queries per wave
+    auto launch = [&](auto STATS, unsigned long long *stats) {
+        hipLaunchKernelGGL((oa::k_tri_settle<decltype(STATS)::value>), sblocks, dim3(256), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->ns, c->tfp,
+                           (const uint4 *)c->d_tfine_table, (const float4 *)c->d_tfine_rec, (const float4 *)c->d_tri9, (const int *)c->d_prev, c->d_keys, c->d_ulist, qcap,
+                           ucount_set(c, c->u_slot), ucount_set(c, c->u_slot ^ 1), stats);
+    };
+    if (c->grid_stats) {                                            // OA_GRID_STATS=1: instrumented launch, totals to stderr (one row of 8 for the launch)
+        unsigned long long h[8];
+        { const int rcs = wave_stats(c, 8, 1, h, [&](unsigned long long *stats) { launch(yes, stats); }); if (rcs) return rcs; }
+        fprintf(stderr, "[oa] tri settle: %llu of %d queries settled (%.2f records each); the others: %llu no seed, %llu reach beyond rho, %llu outside the box, "
+                        "%llu cell not listed / over the cap\n", h[0], c->ns, (double)h[5] / (double)std::max(1ull, h[0]), h[1], h[2], h[3], h[4]);
+    } else launch(no, nullptr);
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+
+// With the neighbour lists and seeds: k_tri_accept settles what seed + neighbours settle and lists the rest, the grid search
+// works through the list (oa_tri.hpp)
+int launch_tri_accept(oa_ctx *c, const int *ring, int &qcap)
+{
+    qcap = oa::ulist_cap((c->ns + 63) / 64, 64);
+    hipLaunchKernelGGL(oa::k_tri_accept, dim3((unsigned)((c->ns + 255) / 256)), dim3(256), 0, c->stream, (const oa::DevState *)c->d_state,
+                       (const float4 *)c->d_src4, c->ns, (float)c->tgp.scale * 1.000001f, (const float4 *)c->d_tri9, (const int *)c->d_prev, ring,
+                       c->d_keys, c->d_ulist, qcap, ucount_set(c, c->u_slot), ucount_set(c, c->u_slot ^ 1));
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+
+// the instrumented plain triangle grid search (one lane per query, workgroups of 256 threads): totals to stderr
+template <typename Launch>
+int tri_grid_stats(oa_ctx *c, unsigned blocks, Launch &&launch)
+{
+    unsigned long long h[oa::TRI_STAT_N];
+    { const int rcs = wave_stats(c, oa::TRI_STAT_N, (size_t)blocks * 4, h, launch); if (rcs) return rcs; }
+    const double nq = (double)std::max(1ull, h[oa::TRI_STAT_QUERIES]), nw = (double)std::max(1ull, h[oa::TRI_STAT_WAVES]);
+    fprintf(stderr, "[oa] tri grid stats: queries %llu | per query: rows %.2f entries %.2f (sphere passes %.2f) survivors %.2f evals %.2f | per wave: "
+                    "eval trips %.1f max-lane entries %.1f max-lane rows %.1f | ring>=2 %.1f%% ring>=3 %.1f%% unsettled %.1f%% over budget %.1f%%\n",
+            h[oa::TRI_STAT_QUERIES], h[oa::TRI_STAT_ROWS] / nq, h[oa::TRI_STAT_ENTRIES] / nq, h[oa::TRI_STAT_SPHERE] / nq, h[oa::TRI_STAT_SURVIVORS] / nq,
+            h[oa::TRI_STAT_EVALS] / nq, h[oa::TRI_STAT_WAVE_TRIPS] / nw, h[oa::TRI_STAT_WAVE_MAX_ENTRIES] / nw,
+            h[oa::TRI_STAT_WAVE_MAX_ROWS] / nw, 100.0 * h[oa::TRI_STAT_RING2] / nq, 100.0 * h[oa::TRI_STAT_RING3] / nq,
+            100.0 * h[oa::TRI_STAT_UNSETTLED] / nq, 100.0 * h[oa::TRI_STAT_OVER] / nq);
+    const double ct = (double)std::max(1ull, h[oa::TRI_STAT_CYC_TOTAL]);
+    fprintf(stderr, "[oa] tri grid phases: per wave %.0f shader cycles, %.2f loop trips | prologue %.1f%% listing %.1f%% scan %.1f%% flush %.1f%% bookkeeping %.1f%% epilogue %.1f%%\n",
+            ct / nw, h[oa::TRI_STAT_LOOP_TRIPS] / nw, 100.0 * h[oa::TRI_STAT_CYC_PROLOGUE] / ct, 100.0 * h[oa::TRI_STAT_CYC_LIST] / ct,
+            100.0 * h[oa::TRI_STAT_CYC_SCAN] / ct, 100.0 * h[oa::TRI_STAT_CYC_FLUSH] / ct, 100.0 * h[oa::TRI_STAT_CYC_BOOK] / ct,
+            100.0 * (ct - h[oa::TRI_STAT_CYC_PROLOGUE] - h[oa::TRI_STAT_CYC_LIST] - h[oa::TRI_STAT_CYC_SCAN] - h[oa::TRI_STAT_CYC_FLUSH] - h[oa::TRI_STAT_CYC_BOOK]) / ct);
+    return OA_OK;
+}
+#endif
+
+// The triangle grid search; the far queries it hands over go through the triangle tree (a list launch behind it, or -- acc -- the wave that owns them)
+int launch_tri_grid(oa_ctx *c, const SearchChoice &s, bool acc)
+{
+    if (!acc && !c->loop_active) { HIPCHK(hipMemsetAsync(c->d_todo_count, 0, TODO_COUNT_INTS * sizeof(int), c->stream)); c->u_slot = 0; }
+    if (c->loop_active) { const int rcr = tri_ring_lazy(c, true); if (rcr) return rcr; }
+    const int *ring = c->tri_ring_ok ? c->d_tri_ring : nullptr;
+    // a front search (SearchChoice) leaves the list of the queries it did not settle: never for the accumulating form
+    bool listed = s.accept_front && ring && !acc && c->d_ulist;
+    const int *qlist = nullptr, *qcount = nullptr;
+    int qcap = 0;
+#if defined(OA_EXPERIMENTS)
+    const bool settle = s.settle_front && !acc && c->d_ulist;
+    if (settle || listed) {
+        const int rcf = settle ? launch_tri_settle(c, qcap) : launch_tri_accept(c, ring, qcap);
+        if (rcf) return rcf;
+        qlist = c->d_ulist; qcount = ucount_set(c, c->u_slot);
+        c->u_slot ^= 1;
+        ring = nullptr;                                             // (the list's queries failed that test already)
+        listed = true;
+    }
+#endif
+    if (s.dual) { int rcb = launch_bvh<true>(c, nullptr, nullptr, 1); if (rcb) return rcb; }    // runs when DevState::tree_turn
+    const int lanes = s.lanes;
+    // k_tri_search_grid<L, STATS, SHARE, ACC, BT>; the accumulating form gets the tree, the pair test and the rows of partials
+    auto launch = [&](auto L, auto STATS, auto SHARE, auto ACC, auto BT, unsigned blocks, unsigned long long *stats, const int *kring, int qmin = 0, int qmax = 0x7FFFFFFF) {
+        constexpr bool A = decltype(ACC)::value;
+        hipLaunchKernelGGL((oa::k_tri_search_grid<decltype(L)::value, decltype(STATS)::value, decltype(SHARE)::value, A, decltype(BT)::value>), dim3(blocks), dim3(decltype(BT)::value), 0, c->stream,
+                           c->d_state, c->d_src4, c->ns, c->tgp, c->d_tcell_start, c->d_tcell_rec, c->d_tri9, c->d_prev, c->d_keys, c->d_todo_list, c->d_todo_count, s.dual ? 0 : -1, stats,
+                           A ? c->tbvh : oa::BvhParams{}, A ? (const float4 *)c->d_tbvh_box : nullptr, A ? (const float4 *)c->d_tbvh_prims : nullptr,
+                           A ? normal_test(c) : oa::NormalTest{}, A ? c->d_partials : nullptr, kring, qlist, qcount, qmin, qmax, qcap);
+    };
+    const unsigned gblocks = (unsigned)(((long long)c->ns * lanes + 255) / 256);
+    if (acc) {
+        // the search finishes its own leftovers through the triangle tree and takes the pair test and the sums in its
+        // epilogue (PLAN_GRID, fast path): no list launch, no accumulation launch
+        dispatch<1, 2, 4>(lanes, [&](auto L) { launch(L, no, yes, yes, int_c<256>{}, gblocks, nullptr, ring); });
+        HIPCHK(hipGetLastError());
+        return OA_OK;
+    }
+    // long plain searches: one wave per workgroup (k_tri_search_grid, BT = 64): a slot is free again when ITS wave is through
+    const long long wblocks = ((long long)c->ns * lanes + 63) / 64;
+    if (listed) {
+        // the list's length decides the lanes per query, on the device (k_tri_search_grid: qmin / qmax): a 4-lane launch for
+        // lists of up to `small` queries, and the shard's own geometry for longer ones
+        const int small = std::min(c->ns, (c->n_tris >= 250000 ? 400 : 128) * c->n_cu);
+        const bool two = lanes != 4 && c->tri_split_lanes;
+        if (two) launch(int_c<4>{}, no, yes, no, int_c<256>{}, (unsigned)(((long long)small * 4 + 255) / 256), nullptr, nullptr, 0, small);
+        dispatch<1, 2, 4>(lanes, [&](auto L) { launch(L, no, yes, no, int_c<256>{}, gblocks, nullptr, nullptr, two ? small : 0, 0x7FFFFFFF); });
+    }
+    else if (c->tri_wave_wgs && !c->grid_stats && c->tri_share && wblocks >= (long long)c->n_cu * 32)
+        dispatch<1, 2, 4>(lanes, [&](auto L) { launch(L, no, yes, no, int_c<64>{}, (unsigned)wblocks, nullptr, ring); });
+#if defined(OA_EXPERIMENTS)
+    else if (lanes == 1 && c->grid_stats) {
+        const int rcs = tri_grid_stats(c, gblocks, [&](unsigned long long *stats) {
+            if (c->tri_share) launch(int_c<1>{}, yes, yes, no, int_c<256>{}, gblocks, stats, ring);
+            else launch(int_c<1>{}, yes, no, no, int_c<256>{}, gblocks, stats, ring);
+        });
+        if (rcs) return rcs;
+    }
+    else if (lanes == 1 && !c->tri_share) launch(int_c<1>{}, no, no, no, int_c<256>{}, gblocks, nullptr, ring);
+#endif
+    else dispatch<1, 2, 4>(lanes, [&](auto L) { launch(L, no, yes, no, int_c<256>{}, gblocks, nullptr, ring); });
+    HIPCHK(hipGetLastError());
+    if (c->debug && !listed) {                                     // how many queries the grid handed over (debug only: syncs)
+        int n_todo = 0;
+        { int rcr = read_small(c, &n_todo, c->d_todo_count, sizeof(int)); if (rcr) return rcr; }
+        fprintf(stderr, "[oa] tri grid handed %d of %d queries to the tree\n", n_todo, c->ns);
+    }
+    return launch_bvh<true>(c, c->d_todo_list, c->d_todo_count);   // the far queries: tree search
+}
+
+int launch_tri_search(oa_ctx *c, const SearchChoice &s, bool acc)
+{
     if (c->debug)
         fprintf(stderr, "[oa] tri search: grid=%d acc=%d ns=%d n_tris=%d state=%p src4=%p tri9=%p prev=%p keys=%p todo=%p/%p cells=%p/%p\n",
-                (int)use_grid, (int)acc, c->ns, c->n_tris, (void *)c->d_state, (void *)c->d_src4, (void *)c->d_tri9, (void *)c->d_prev,
+                (int)(s.kind == SEARCH_GRID), (int)acc, c->ns, c->n_tris, (void *)c->d_state, (void *)c->d_src4, (void *)c->d_tri9, (void *)c->d_prev,
                 (void *)c->d_keys, (void *)c->d_todo_list, (void *)c->d_todo_count, (void *)c->d_tcell_start, (void *)c->d_tcell_rec);
-    if (use_grid) {
-        if (!acc && !c->loop_active) { HIPCHK(hipMemsetAsync(c->d_todo_count, 0, TODO_COUNT_INTS * sizeof(int), c->stream)); c->u_slot = 0; }
-        if (c->loop_active) { const int rcr = tri_ring_lazy(c, true); if (rcr) return rcr; }
-        const int *ring = c->tri_ring_ok ? c->d_tri_ring : nullptr;
-        const bool dual = c->grid_mode == -1 && c->turns_on && c->ns <= tri_tree_early(c);
-        // With the neighbour lists and seeds: k_tri_accept settles what seed + neighbours settle and lists the rest, the grid
-        // search works through the list (oa_tri.hpp).  Not for the accumulating form (its rows go by workgroup), nor while tree
-        // and grid take turns (DevState::tree_turn): those keep the test in the search's own prologue.
-        bool split = ring && !acc && !dual && c->seeded && c->tri_split && c->d_ulist;
-        const int *qlist = nullptr, *qcount = nullptr;
-        int qcap = 0;
-        // The settled-pose search (oa_tri_fine.hpp) in front: one thread per query, its own cell's list of whole triangles; what it
-        // does not settle (reach beyond the lists' inflation, crowded cells, no seed) is the list the grid search works through
-#if defined(OA_EXPERIMENTS)
-        const bool fine = c->tri_fine_ok && !acc && !dual && c->seeded && c->d_ulist;
-        if (fine) {
-            const dim3 sblocks((unsigned)(((long long)c->ns * 4 + 255) / 256));     // four lanes per query
-            qcap = oa::ulist_cap((int)sblocks.x * 4, 16);           // 16 queries per wave
-#define OA_TSETTLE_ARGS (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->ns, c->tfp, (const uint4 *)c->d_tfine_table, (const float4 *)c->d_tfine_rec, \
-                        (const float4 *)c->d_tri9, (const int *)c->d_prev, c->d_keys, c->d_ulist, qcap, ucount_set(c, c->u_slot), ucount_set(c, c->u_slot ^ 1)
-            if (c->grid_stats) {                                     // OA_GRID_STATS=1: instrumented launch, totals to stderr (synchronises)
-                DevTmp<unsigned long long> d_stats;
-                HIPCHK(d_stats.alloc(8));
-                HIPCHK(hipMemsetAsync(d_stats, 0, 8 * sizeof(unsigned long long), c->stream));
-                hipLaunchKernelGGL(oa::k_tri_settle<true>, sblocks, dim3(256), 0, c->stream, OA_TSETTLE_ARGS, d_stats.p);
-                HIPCHK(hipGetLastError());
-                unsigned long long h[8];
-                { int rcr = read_small(c, h, d_stats, sizeof(h)); if (rcr) return rcr; }
-                fprintf(stderr, "[oa] tri settle: %llu of %d queries settled (%.2f records each); the others: %llu no seed, %llu reach beyond rho, %llu outside the box, "
-                                "%llu cell not listed / over the cap\n", h[0], c->ns, (double)h[5] / (double)std::max(1ull, h[0]), h[1], h[2], h[3], h[4]);
-            } else
-            hipLaunchKernelGGL(oa::k_tri_settle<false>, sblocks, dim3(256), 0, c->stream, OA_TSETTLE_ARGS, (unsigned long long *)nullptr);
-#undef OA_TSETTLE_ARGS
-            HIPCHK(hipGetLastError());
-            qlist = c->d_ulist; qcount = ucount_set(c, c->u_slot);
-            c->u_slot ^= 1;
-            ring = nullptr;
-            split = true;
-        }
-        else if (split) {
-            hipLaunchKernelGGL(oa::k_tri_accept, dim3((unsigned)((c->ns + 255) / 256)), dim3(256), 0, c->stream, (const oa::DevState *)c->d_state,
-                               (const float4 *)c->d_src4, c->ns, (float)c->tgp.scale * 1.000001f, (const float4 *)c->d_tri9, (const int *)c->d_prev, ring,
-                               c->d_keys, c->d_ulist, (qcap = oa::ulist_cap((c->ns + 63) / 64, 64)), ucount_set(c, c->u_slot), ucount_set(c, c->u_slot ^ 1));
-            HIPCHK(hipGetLastError());
-            qlist = c->d_ulist; qcount = ucount_set(c, c->u_slot);
-            c->u_slot ^= 1;
-            ring = nullptr;                                          // (the list's queries failed that test already)
-        }
-#endif
-        if (dual) { int rcb = launch_bvh<true>(c, nullptr, nullptr, 1); if (rcb) return rcb; }    // runs when DevState::tree_turn
-        const int turn = dual ? 0 : -1;
-        const int lanes = tri_lanes_for(c);
-#define OA_TGRID_ARGS c->d_state, c->d_src4, c->ns, c->tgp, c->d_tcell_start, c->d_tcell_rec, c->d_tri9, c->d_prev, c->d_keys, c->d_todo_list, c->d_todo_count, turn
-        const dim3 gblocks((unsigned)(((long long)c->ns * lanes + 255) / 256));
-        if (split) {
-            // the list's length decides the lanes per query, on the device (k_tri_search_grid: qmin / qmax): a 4-lane launch for
-            // lists of up to `small` queries, and the shard's own geometry for longer ones
-            const int small = std::min(c->ns, (c->n_tris >= 250000 ? 400 : 128) * c->n_cu);
-#define OA_TGRID_LIST_TAIL(lo, hi) (unsigned long long *)nullptr, oa::BvhParams{}, (const float4 *)nullptr, (const float4 *)nullptr, oa::NormalTest{}, (double *)nullptr, (const int *)nullptr, qlist, qcount, lo, hi, qcap
-            if (lanes != 4 && c->tri_split_lanes) {
-                hipLaunchKernelGGL(oa::k_tri_search_grid<4>, dim3((unsigned)(((long long)small * 4 + 255) / 256)), dim3(256), 0, c->stream, OA_TGRID_ARGS, OA_TGRID_LIST_TAIL(0, small));
-                if (lanes == 2) hipLaunchKernelGGL(oa::k_tri_search_grid<2>, gblocks, dim3(256), 0, c->stream, OA_TGRID_ARGS, OA_TGRID_LIST_TAIL(small, 0x7FFFFFFF));
-                else hipLaunchKernelGGL(oa::k_tri_search_grid<1>, gblocks, dim3(256), 0, c->stream, OA_TGRID_ARGS, OA_TGRID_LIST_TAIL(small, 0x7FFFFFFF));
-            } else {
-                if (lanes == 4) hipLaunchKernelGGL(oa::k_tri_search_grid<4>, gblocks, dim3(256), 0, c->stream, OA_TGRID_ARGS, OA_TGRID_LIST_TAIL(0, 0x7FFFFFFF));
-                else if (lanes == 2) hipLaunchKernelGGL(oa::k_tri_search_grid<2>, gblocks, dim3(256), 0, c->stream, OA_TGRID_ARGS, OA_TGRID_LIST_TAIL(0, 0x7FFFFFFF));
-                else hipLaunchKernelGGL(oa::k_tri_search_grid<1>, gblocks, dim3(256), 0, c->stream, OA_TGRID_ARGS, OA_TGRID_LIST_TAIL(0, 0x7FFFFFFF));
-            }
-#undef OA_TGRID_LIST_TAIL
-            HIPCHK(hipGetLastError());
-            return launch_bvh<true>(c, c->d_todo_list, c->d_todo_count);       // the far queries: tree search
-        }
-        if (acc) {
-            // the search finishes its own leftovers through the triangle tree and takes the pair test and the sums in its
-            // epilogue (search_plan: PLAN_GRID, fast path): no list launch, no accumulation launch
-#define OA_TGRID_ACC_ARGS OA_TGRID_ARGS, (unsigned long long *)nullptr, c->tbvh, (const float4 *)c->d_tbvh_box, (const float4 *)c->d_tbvh_prims, normal_test(c), c->d_partials, ring
-            if (lanes == 4) hipLaunchKernelGGL((oa::k_tri_search_grid<4, false, true, true>), gblocks, dim3(256), 0, c->stream, OA_TGRID_ACC_ARGS);
-            else if (lanes == 2) hipLaunchKernelGGL((oa::k_tri_search_grid<2, false, true, true>), gblocks, dim3(256), 0, c->stream, OA_TGRID_ACC_ARGS);
-            else hipLaunchKernelGGL((oa::k_tri_search_grid<1, false, true, true>), gblocks, dim3(256), 0, c->stream, OA_TGRID_ACC_ARGS);
-#undef OA_TGRID_ACC_ARGS
-            HIPCHK(hipGetLastError());
-            return OA_OK;
-        }
-#define OA_TGRID_TAIL oa::BvhParams{}, (const float4 *)nullptr, (const float4 *)nullptr, oa::NormalTest{}, (double *)nullptr, ring, qlist, qcount
-        // long plain searches: one wave per workgroup (k_tri_search_grid, BT = 64): a slot is free again when ITS wave is through
-        const long long wblocks = ((long long)c->ns * lanes + 63) / 64;
-        const bool wave_wgs = c->tri_wave_wgs && !qlist && !c->grid_stats && c->tri_share && wblocks >= (long long)c->n_cu * 32;
-        if (wave_wgs) {
-            const dim3 wb((unsigned)wblocks);
-            if (lanes == 4) hipLaunchKernelGGL((oa::k_tri_search_grid<4, false, true, false, 64>), wb, dim3(64), 0, c->stream, OA_TGRID_ARGS, (unsigned long long *)nullptr, OA_TGRID_TAIL);
-            else if (lanes == 2) hipLaunchKernelGGL((oa::k_tri_search_grid<2, false, true, false, 64>), wb, dim3(64), 0, c->stream, OA_TGRID_ARGS, (unsigned long long *)nullptr, OA_TGRID_TAIL);
-            else hipLaunchKernelGGL((oa::k_tri_search_grid<1, false, true, false, 64>), wb, dim3(64), 0, c->stream, OA_TGRID_ARGS, (unsigned long long *)nullptr, OA_TGRID_TAIL);
-        }
-        else if (lanes == 4) hipLaunchKernelGGL(oa::k_tri_search_grid<4>, gblocks, dim3(256), 0, c->stream, OA_TGRID_ARGS, (unsigned long long *)nullptr, OA_TGRID_TAIL);
-        else if (lanes == 2) hipLaunchKernelGGL(oa::k_tri_search_grid<2>, gblocks, dim3(256), 0, c->stream, OA_TGRID_ARGS, (unsigned long long *)nullptr, OA_TGRID_TAIL);
-#if defined(OA_EXPERIMENTS)
-        else if (c->grid_stats) {                                   // OA_GRID_STATS=1: instrumented launch, totals to stderr (synchronises)
-            DevTmp<unsigned long long> d_stats;                     // one row of counters per wave (atomics on a dozen shared words slowed the launch 8x)
-            const size_t n_waves = (size_t)gblocks.x * 4;
-            HIPCHK(d_stats.alloc(oa::TRI_STAT_N * n_waves));
-            HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(unsigned long long) * oa::TRI_STAT_N * n_waves, c->stream));
-            if (c->tri_share) hipLaunchKernelGGL((oa::k_tri_search_grid<1, true, true>), gblocks, dim3(256), 0, c->stream, OA_TGRID_ARGS, d_stats.p, OA_TGRID_TAIL);
-            else hipLaunchKernelGGL((oa::k_tri_search_grid<1, true, false>), gblocks, dim3(256), 0, c->stream, OA_TGRID_ARGS, d_stats.p, OA_TGRID_TAIL);
-            HIPCHK(hipGetLastError());
-            unsigned long long h[oa::TRI_STAT_N] = { 0 };
-            {
-                std::vector<unsigned long long> rows(oa::TRI_STAT_N * n_waves);
-                int rcr = read_small(c, rows.data(), d_stats, sizeof(unsigned long long) * rows.size());
-                if (rcr) return rcr;
-                for (size_t w = 0; w < n_waves; ++w) for (int k = 0; k < oa::TRI_STAT_N; ++k) h[k] += rows[w * oa::TRI_STAT_N + (size_t)k];
-            }
-            const double nq = (double)std::max(1ull, h[oa::TRI_STAT_QUERIES]), nw = (double)std::max(1ull, h[oa::TRI_STAT_WAVES]);
-            fprintf(stderr, "[oa] tri grid stats: queries %llu | per query: rows %.2f entries %.2f (sphere passes %.2f) survivors %.2f evals %.2f | per wave: "
-                            "eval trips %.1f max-lane entries %.1f max-lane rows %.1f | ring>=2 %.1f%% ring>=3 %.1f%% unsettled %.1f%% over budget %.1f%%\n",
-                    h[oa::TRI_STAT_QUERIES], h[oa::TRI_STAT_ROWS] / nq, h[oa::TRI_STAT_ENTRIES] / nq, h[oa::TRI_STAT_SPHERE] / nq, h[oa::TRI_STAT_SURVIVORS] / nq,
-                    h[oa::TRI_STAT_EVALS] / nq, h[oa::TRI_STAT_WAVE_TRIPS] / nw, h[oa::TRI_STAT_WAVE_MAX_ENTRIES] / nw,
-                    h[oa::TRI_STAT_WAVE_MAX_ROWS] / nw, 100.0 * h[oa::TRI_STAT_RING2] / nq, 100.0 * h[oa::TRI_STAT_RING3] / nq,
-                    100.0 * h[oa::TRI_STAT_UNSETTLED] / nq, 100.0 * h[oa::TRI_STAT_OVER] / nq);
-            const double ct = (double)std::max(1ull, h[oa::TRI_STAT_CYC_TOTAL]);
-            fprintf(stderr, "[oa] tri grid phases: per wave %.0f shader cycles, %.2f loop trips | prologue %.1f%% listing %.1f%% scan %.1f%% flush %.1f%% bookkeeping %.1f%% epilogue %.1f%%\n",
-                    ct / nw, h[oa::TRI_STAT_LOOP_TRIPS] / nw, 100.0 * h[oa::TRI_STAT_CYC_PROLOGUE] / ct, 100.0 * h[oa::TRI_STAT_CYC_LIST] / ct,
-                    100.0 * h[oa::TRI_STAT_CYC_SCAN] / ct, 100.0 * h[oa::TRI_STAT_CYC_FLUSH] / ct, 100.0 * h[oa::TRI_STAT_CYC_BOOK] / ct,
-                    100.0 * (ct - h[oa::TRI_STAT_CYC_PROLOGUE] - h[oa::TRI_STAT_CYC_LIST] - h[oa::TRI_STAT_CYC_SCAN] - h[oa::TRI_STAT_CYC_FLUSH] - h[oa::TRI_STAT_CYC_BOOK]) / ct);
-        }
-        else if (!c->tri_share) hipLaunchKernelGGL((oa::k_tri_search_grid<1, false, false>), gblocks, dim3(256), 0, c->stream, OA_TGRID_ARGS, (unsigned long long *)nullptr, OA_TGRID_TAIL);
-#endif
-        else hipLaunchKernelGGL(oa::k_tri_search_grid<1>, gblocks, dim3(256), 0, c->stream, OA_TGRID_ARGS, (unsigned long long *)nullptr, OA_TGRID_TAIL);
-#undef OA_TGRID_TAIL
-#undef OA_TGRID_ARGS
-        HIPCHK(hipGetLastError());
-        if (c->debug) {                                            // how many queries the grid handed over (debug only: syncs)
-            int n_todo = 0;
-            { int rcr = read_small(c, &n_todo, c->d_todo_count, sizeof(int)); if (rcr) return rcr; }
-            fprintf(stderr, "[oa] tri grid handed %d of %d queries to the tree\n", n_todo, c->ns);
-        }
-        return launch_bvh<true>(c, c->d_todo_list, c->d_todo_count);       // the far queries: tree search
-    } else {
-        hipLaunchKernelGGL(oa::k_tri_search_all, dim3(std::min((c->ns + 255) / 256, 65535)), dim3(256), 0, c->stream,
-                           c->d_state, c->d_src4, c->ns, c->d_tri9, c->n_tris, c->d_prev, c->d_keys);
-    }
+    if (s.kind == SEARCH_GRID) return launch_tri_grid(c, s, acc);
+    hipLaunchKernelGGL(oa::k_tri_search_all, dim3(std::min((c->ns + 255) / 256, 65535)), dim3(256), 0, c->stream,
+                       c->d_state, c->d_src4, c->ns, c->d_tri9, c->n_tris, c->d_prev, c->d_keys);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -3217,8 +3219,10 @@ int source_reset(oa_ctx *c, long long count, long long begin, long long n_verts)
     HIPCHK(dev_malloc(&c->d_keys, sizeof(unsigned long long) * (size_t)c->ns_pad));
     HIPCHK(dev_malloc(&c->d_prev, sizeof(int) * (size_t)c->ns_pad));
     HIPCHK(dev_malloc(&c->d_win, sizeof(float4) * (size_t)c->ns_pad));
-    dev_free(c->d_worder); dev_free(c->d_homes);
+    dev_free(c->d_worder); dev_free(c->d_homes); dev_free(c->d_qcnt);
+    c->homes_cap = 0;
     if (c->nn_wave_order && c->grid_mode == 0) HIPCHK(dev_malloc(&c->d_worder, sizeof(unsigned short) * (size_t)c->ns_pad));   // (brute force only; never inside a loop)
+    if (c->grid_mode == 0) { const int rcq = ensure_queue_buffers(c, c->ns_pad / chunk); if (rcq) return rcq; }   // (the brute-force launch's q_blocks; whatever the target: a few KB)
     if (c->grid_safe && !c->surface) HIPCHK(dev_malloc(&c->d_wsafe, sizeof(uint2) * (size_t)c->ns_pad));   // (a vertex target set later allocates it: set_target_common)
     c->seeded = false; c->win_seeds = false;
     HIPCHK(dev_malloc(&c->d_sel, sizeof(int) * (size_t)c->ns_pad));
@@ -3336,16 +3340,16 @@ int build_selection_order(oa_ctx *c, const float *xyz, int64_t n_verts, int on_d
     const int n = (int)n_sel;
     DevTmp<float4> all4;
     DevTmp<int> all_sel, v_in;
-    DevTmp<unsigned> k_in, k_out;
+    DevTmp<unsigned> k_in;
     HIPCHK(all4.alloc((size_t)n)); HIPCHK(all_sel.alloc((size_t)n)); HIPCHK(v_in.alloc((size_t)n));
-    HIPCHK(k_in.alloc((size_t)n)); HIPCHK(k_out.alloc((size_t)n));
+    HIPCHK(k_in.alloc((size_t)n));
     HIPCHK(o.pts.alloc((size_t)n)); HIPCHK(o.sel.alloc((size_t)n)); HIPCHK(o.pos.alloc((size_t)n));
     hipLaunchKernelGGL(oa::k_pack_source, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_xyz, (const long long *)d_vlist.p, step, 0ll,
                        (const int *)nullptr, n, n, all4.p, all_sel.p);
     hipLaunchKernelGGL(oa::k_morton_keys, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float4 *)all4.p, n,
                        lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
     HIPCHK(hipGetLastError());
-    { const int rcs = sort_pairs30(c, k_in.p, k_out.p, v_in.p, o.pos.p, (size_t)n); if (rcs) return rcs; }
+    { const int rcs = sort_order_bits(c, k_in.p, o.pos.p, (size_t)n, 30); if (rcs) return rcs; }
     hipLaunchKernelGGL(oa::k_apply_perm, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float4 *)all4.p, (const int *)all_sel.p,
                        (const int *)o.pos.p, n, n, o.pts.p, o.sel.p);
     HIPCHK(hipGetLastError());
@@ -3598,12 +3602,7 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
     case OA_STAT_N_TRIS: *value = (double)c->n_tris; return OA_OK;
     case OA_STAT_SURFACE: *value = c->surface ? 1.0 : 0.0; return OA_OK;
     case OA_STAT_BRUTE_KERNEL:
-#if defined(OA_EXPERIMENTS)
-        *value = !(c->filter_ok && c->use_filter) ? 0.0
-                 : ((c->nn_mfma && c->d_tfm && c->R == 4 && c->tile_groups == oa::FTILE_GROUPS) ? 2.0 : ((c->nn_sort && c->d_tfs) ? 3.0 : 1.0));
-#else
-        *value = (c->filter_ok && c->use_filter && c->nn_sort && c->d_tfs) ? 3.0 : 0.0;       // (launch_nn_impl: the sorted kernel, or the plain one)
-#endif
+        *value = (double)brute_kernel(c);
         return OA_OK;
     case OA_STAT_FAST_ITERATIONS: *value = (double)c->fast_iters; return OA_OK;
     case OA_STAT_HANDOVER_ENTRIES: *value = c->h_poll ? (double)c->h_poll[2] : 0.0; return OA_OK;
@@ -3755,7 +3754,7 @@ OA_EXPORT int oa_nn_search(oa_ctx *c, int64_t *idx, float *d2, double *kernel_ms
     if (idx) HIPCHK(d_idx.alloc((size_t)c->ns));
     if (d2) HIPCHK(d_d2.alloc((size_t)c->ns));
     HIPCHK(hipEventRecord(c->ev[0], c->stream));
-    if ((rc = launch_nn(c))) return rc;
+    if ((rc = launch_nn(c, choose_search(c), false))) return rc;
     HIPCHK(hipEventRecord(c->ev[1], c->stream));
     hipLaunchKernelGGL(oa::k_decode_keys, dim3((c->ns_pad + 255) / 256), dim3(256), 0, c->stream, c->d_keys,
                        c->ns_pad, c->ns, (const int *)c->d_perm, d_idx.p, d_d2.p);
@@ -3860,7 +3859,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
     }
     c->d_pivot0 = 0.0;
     if ((rc = push_state_for_oneshot(c, thresh, true))) return rc;
-    if ((rc = launch_nn(c))) return rc;
+    if ((rc = launch_nn(c, choose_search(c), false))) return rc;
     if ((rc = launch_accumulate(c, true, nullptr, nullptr))) return rc;
     if ((rc = launch_reduce(c, c->d_sums, oa::RowSel{ c->acc_blocks, 0, 0 }, false))) return rc;   // (emitting accumulation: k_pair_accumulate<true>)
     if (calc_stats) {
@@ -3871,7 +3870,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
         if (s1[oa::S_K] > 0.0) {
             c->d_pivot0 = s1[oa::S_D] / s1[oa::S_K];
             if ((rc = push_state_for_oneshot(c, thresh, true))) { c->d_pivot0 = 0.0; return rc; }
-            rc = launch_nn(c);
+            rc = launch_nn(c, choose_search(c), false);
             if (!rc) rc = launch_accumulate(c, true, nullptr, nullptr);
             if (!rc) rc = launch_reduce(c, c->d_sums, oa::RowSel{ c->acc_blocks, 0, 0 }, false);
             if (rc) { c->d_pivot0 = 0.0; return rc; }
@@ -3981,10 +3980,10 @@ OA_EXPORT int oa_affine_from_points(oa_ctx *c, const double *v0, const double *v
                            (long long)K, (long long)K, d_cs.p);
         hipLaunchKernelGGL(oa::k_affine_gram_any, dim3((unsigned)(m * m)), dim3(256), 0, c->stream, (const double *)d0.p, (const double *)d1.p, n, D,
                            (long long)K, (long long)K, (const double *)d_cs.p, d_gram.p);
-#define OA_AFF_SOLVE(DD) hipLaunchKernelGGL((oa::k_affine_solve<DD, true>), dim3(1), dim3(64), 0, c->stream, (const double *)d_cs.p, (const double *)d_gram.p, n, \
-                                            (long long)K, shear ? 1 : 0, with_scale ? 1 : 0, d_out.p, d_ws.p)
-        if (D == 16) OA_AFF_SOLVE(16); else if (D == 32) OA_AFF_SOLVE(32); else OA_AFF_SOLVE(64);
-#undef OA_AFF_SOLVE
+        dispatch<64, 16, 32>(D, [&](auto DD) {
+            hipLaunchKernelGGL((oa::k_affine_solve<decltype(DD)::value, true>), dim3(1), dim3(64), 0, c->stream, (const double *)d_cs.p, (const double *)d_gram.p, n,
+                               (long long)K, shear ? 1 : 0, with_scale ? 1 : 0, d_out.p, d_ws.p);
+        });
         HIPCHK(hipGetLastError());
         std::vector<double> out((size_t)w * w + 1);
         { int rcr = read_small(c, out.data(), d_out, sizeof(double) * out.size()); if (rcr) return rcr; }
@@ -4096,7 +4095,7 @@ OA_EXPORT int oa_run(oa_ctx *c, const oa_settings *st, oa_report *rep)
     // about the halt too late to save anything.  Two iterations are always queued, so the GPU never idles.
     // The adaptive grid path (grid_fast_now) needs recent news from the device as well: then the host stays close even
     // when the loop cannot end early.
-    bool poll = c->h_poll && env_int("OA_RUN_POLL", 1) && (st->early_exit || (search_plan(c) == PLAN_GRID && c->grid_path == 0));
+    bool poll = c->h_poll && env_int("OA_RUN_POLL", 1) && (st->early_exit || (choose_search(c).plan == PLAN_GRID && c->grid_path == 0));
     const int lag = 2;
     volatile int32_t *progress = c->h_poll;
     for (int it = 0; it < st->iters; ++it) {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """GPU box: lanes per query of the two grid kernels (OA_GRID_LANES = 1 / 2 / 4) by shard size -- the data behind the
-lane selection in launch_nn_impl / launch_tri_search.  us per search, 40 iterations from an offset pose (settled)."""
+lane selection (choose_search -> launch_vertex_grid / launch_tri_grid). us per search, 40 iterations from an offset pose (settled)."""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
