@@ -186,6 +186,34 @@ int oa_set_source(oa_ctx *ctx, const float *xyz, int64_t n_verts, int on_device,
  * or an angle outside (0, 180) switches the test off; a new source or target upload switches it off too. */
 int oa_set_normals(oa_ctx *ctx, const float *src_normals, int64_t n_verts, const float *tgt_normals, int64_t nt,
                    double max_angle_deg);
+/* EXTENSION (no counterpart in the reference's code; its citation.txt names Chen & Medioni next to Besl & McKay): what a loop
+ * step minimises.
+ *   OA_METRIC_POINT  the distance of every source point to its correspondence (Besl-McKay; pairs -> Kabsch / SVD): the
+ *                    reference's loop and the default
+ *   OA_METRIC_PLANE  the distance of every source point to the TANGENT PLANE at its correspondence (Chen-Medioni): per pair
+ *                    the residual n . (a - b) and the row [a x n, n] of the linearised step (omega, t) about the context's pivot
+ *                    (oa_get_pivot), n = the correspondence's normal carried to align-local space -- the nearest triangle's
+ *                    geometric normal (surface mode) or the target vertex normal (vertex mode: oa_set_target_normals or
+ *                    oa_set_normals).  The 6 x 6 normal equations are solved through their eigen-decomposition; eigenvalues
+ *                    below 1e-10 of the largest count as zero and the step is the minimum-norm one (a plane, a sphere, a
+ *                    cylinder leave directions the data cannot see: the step does not move along them); the rotation is
+ *                    exp([omega]x), exact.  Pairs are tested as for the point metric (thresh, normal-angle test); a pair whose
+ *                    normal has zero or non-finite length takes no part in the step and is not counted in K.  Everything after
+ *                    the step's matrix -- float32 new_mat, matrix_world @ new_mat, the convergence rings, history, report -- is
+ *                    the point metric's code.  Every search mode serves it.
+ * The metric survives uploads and oa_set_matrices; changing it ends a running oa_iterate sequence (the next call starts a new
+ * one from the current matrix_world).  Under OA_METRIC_PLANE:
+ *   - oa_run / oa_iterate with with_scale != 0 return OA_E_BAD_ARG (the step is rigid); with a vertex-mode target that has no
+ *     normals OA_E_STATE; with a shard of more than 8 388 608 points OA_E_CAPACITY;
+ *   - multi-device contexts (oa_create_multi) and the split-phase calls (oa_run_begin, oa_iter_partial, oa_iter_finish) return
+ *     OA_E_STATE: their exchange carries OA_NSUMS doubles, the plane system needs 32;
+ *   - oa_make_pairs, oa_nn_search, oa_kabsch* do not look at the metric. */
+#define OA_METRIC_POINT 0   /* default: Besl-McKay, today's loop */
+#define OA_METRIC_PLANE 1   /* Chen-Medioni */
+int oa_set_metric(oa_ctx *ctx, int metric);
+/* vertex-mode targets: per-vertex normals (base-local, nt x 3 float32, host) for the plane metric, without switching the
+ * normal-angle test on; a new target upload forgets them.  Normals given through oa_set_normals serve as well. */
+int oa_set_target_normals(oa_ctx *ctx, const float *tgt_normals, int64_t nt);
 /* matrix_world of the align and base objects (functions/general.py:262-263) */
 int oa_set_matrices(oa_ctx *ctx, const float mx_align[16], const float mx_base[16]);
 int oa_get_matrix_world(oa_ctx *ctx, float mx_align[16]);
@@ -236,6 +264,8 @@ int oa_reset_seeds(oa_ctx *ctx);
                                        * workgroup dispatched mid-launch); 0 when that kernel did not run.  Multi-device context: its first device */
 #define OA_STAT_BRUTE_QUEUE_WGS     27   /* workgroups of the last k_nn_search_sorted launch that took their (split, block) items off the work
                                        * queue (long launches: as many as the chip holds); 0 = one workgroup per item, in launch order */
+#define OA_STAT_METRIC          28   /* OA_METRIC_POINT / OA_METRIC_PLANE */
+#define OA_STAT_PLANE_RANK      29   /* eigenvalues the last plane solve kept (6 = fully determined); loop or oa_point_to_plane */
 #define OA_STAT_ENQUEUED_CHILD  1000   /* + i: the same count for child i alone */
 int oa_get_stat(oa_ctx *ctx, int what, double *value);
 /* why the exchange is what it is (AUTO's reason for not taking RCCL, librccl's error, "RCCL was aborted: ..."), or "" */
@@ -269,6 +299,12 @@ int oa_kabsch_from_sums(oa_ctx *ctx, const double sums[OA_NSUMS], const double p
                         double M[16]);
 /* the pivot this context subtracts before accumulating (the first selected source vertex) */
 int oa_get_pivot(oa_ctx *ctx, double pivot[3]);
+
+/* the plane step from caller-supplied pairs: A, B, N are 3 x K row-major doubles, leading dimension ld; N need not be unit.
+ * Pivot c = A's first column (the loop's rule: first selected source vertex) -- the minimum-norm answer of a rank-deficient
+ * system depends on the frame of (omega, t), so the pivot is part of the contract.  M maps A towards B's tangent planes
+ * (the M of oa_kabsch's convention).  K < 3: OA_E_TOO_FEW_PAIRS.  Does not look at the context's metric. */
+int oa_point_to_plane(oa_ctx *ctx, const double *A, const double *B, const double *N, int64_t K, int64_t ld, double M[16]);
 
 /* ---- fused fast path: the operator loop (operators/icp_align.py:91-151) ----------------------- */
 /* one iteration, synchronous (the modal operator's per-tick step, icp_align_feedback.py:250-288):

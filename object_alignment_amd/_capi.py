@@ -27,6 +27,8 @@ OA_EXCHANGE_AUTO = -1
 OA_EXCHANGE_MAILBOX = 0
 OA_EXCHANGE_RCCL = 1
 OA_NSUMS = 24
+OA_METRIC_POINT = 0
+OA_METRIC_PLANE = 1
 
 # every symbol include/oa_icp.h declares (tests check that the library exports all of them)
 SYMBOLS = [
@@ -38,6 +40,7 @@ SYMBOLS = [
     "oa_make_pairs", "oa_nn_search", "oa_kabsch", "oa_affine_from_points", "oa_kabsch_from_sums", "oa_get_pivot",
     "oa_iterate", "oa_run", "oa_get_history", "oa_run_begin", "oa_iter_partial", "oa_iter_finish", "oa_run_end",
     "oa_get_search_ms", "oa_measure_valu_ceiling", "oa_exchange_note",
+    "oa_set_metric", "oa_set_target_normals", "oa_point_to_plane",
 ]
 
 
@@ -132,6 +135,9 @@ def load(experiments: bool = False):
     L.oa_iter_partial.argtypes = [vp, vp]
     L.oa_iter_finish.argtypes = [vp, vp]
     L.oa_run_end.argtypes = [vp, C.POINTER(Report)]
+    L.oa_set_metric.argtypes = [vp, C.c_int]
+    L.oa_set_target_normals.argtypes = [vp, fp, C.c_int64]
+    L.oa_point_to_plane.argtypes = [vp, dp, dp, dp, C.c_int64, C.c_int64, dp]
     _libs[experiments] = L
     return L
 

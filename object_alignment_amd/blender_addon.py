@@ -60,11 +60,14 @@ if bpy is not None:
             default=False)
         align_meth: EnumProperty(items=[("0", "RIGID", "0"), ("1", "ROT_LOC_SCALE", "1")], name="Alignment Method",
                                  description="Rigid, or rotation + translation + uniform scale", default="0")
+        icp_metric: EnumProperty(items=[("point", "POINT_TO_POINT", "Distance to the corresponding point (Besl-McKay)"),
+                                        ("plane", "POINT_TO_PLANE", "Distance to the tangent plane at the corresponding point (Chen-Medioni); rigid only")],
+                                 name="ICP Metric", description="What an ICP step minimises", default="point")
 
         def draw(self, context):
             col = self.layout.column()
             for name in ("icp_iterations", "redraw_frequency", "sample_fraction", "min_start", "target_d", "use_target",
-                         "take_m_with", "align_meth"):
+                         "take_m_with", "align_meth", "icp_metric"):
                 col.prop(self, name)
 
     class VIEW3D_PT_object_alignment(Panel):

@@ -435,6 +435,8 @@ struct oa_ctx {
     float *d_src_n = nullptr, *d_tgt_n = nullptr;
     double cos_min = -2.0;
     bool normals_on = false;
+    int last_plane_rank = 0;         // OA_STAT_PLANE_RANK: eigenvalues the last plane solve kept (loop or oa_point_to_plane)
+    int metric = OA_METRIC_POINT;    // oa_set_metric: what the loop minimises (survives uploads and oa_set_matrices)
     double pivot[3] = { 0, 0, 0 };
     // launch geometry for k_nn_search
     int n_splits = 1, acc_blocks = 1;
@@ -571,8 +573,10 @@ void plan_geometry(oa_ctx *c)
 int ensure_common(oa_ctx *c)
 {
     if (!c->d_state) HIPCHK(dev_malloc(&c->d_state, sizeof(oa::DevState)));
-    if (!c->d_partials) HIPCHK(dev_malloc(&c->d_partials, sizeof(double) * oa::NSUMS * oa::ACC_MAX_BLOCKS));
-    if (!c->d_sums) HIPCHK(dev_malloc(&c->d_sums, sizeof(double) * oa::NSUMS));
+    // (sized for the widest user: the plane metric's rows of NSUMS_PLANE, one per workgroup of k_pair_accumulate_plane)
+    static_assert(oa::NSUMS_PLANE * oa::PLANE_MAX_BLOCKS >= oa::NSUMS * oa::ACC_MAX_BLOCKS, "d_partials");
+    if (!c->d_partials) HIPCHK(dev_malloc(&c->d_partials, sizeof(double) * oa::NSUMS_PLANE * oa::PLANE_MAX_BLOCKS));
+    if (!c->d_sums) HIPCHK(dev_malloc(&c->d_sums, sizeof(double) * oa::NSUMS_PLANE));
     if (!c->d_solve) HIPCHK(dev_malloc(&c->d_solve, sizeof(double) * 32));
     if (!c->h_poll) {
         HIPCHK(hipHostMalloc((void **)&c->h_poll, 8 * sizeof(int32_t), hipHostMallocMapped));
@@ -871,7 +875,8 @@ SearchChoice choose_search(const oa_ctx *c)
         s.settle_front = c->surface && c->tri_fine_ok && c->seeded && !s.dual;
         s.accept_front = c->surface && c->tri_split && c->seeded && !s.dual;
     }
-    if (!c->fused_acc || !c->loop_active || c->ns <= 0) return s;
+    // (the plane metric has no accumulating search epilogue: search, then k_pair_accumulate_plane -- as with fused_acc off)
+    if (!c->fused_acc || !c->loop_active || c->ns <= 0 || c->metric == OA_METRIC_PLANE) return s;
     // (the accumulating tree search needs twice the registers of the plain one: worth it while the shard is small enough
     //  that occupancy does not matter -- 12k queries against 1M vertices: 58 us fused, 47 us search + accumulate)
     if (s.kind == SEARCH_TREE) s.plan = c->ns <= c->tree_acc_max ? PLAN_TREE : PLAN_PLAIN;
@@ -1083,6 +1088,11 @@ int launch_nn(oa_ctx *c, const SearchChoice &s, bool acc)
     return rc;
 }
 
+// the plane metric's accumulation: one thread per source slot, workgroups by the shard size alone (every search mode leaves
+// the same rows); begin_loop refuses shards beyond PLANE_MAX_BLOCKS rows
+inline int plane_threads(const oa_ctx *c) { return c->ns >= 262144 ? oa::PLANE_THREADS : 256; }
+inline int plane_blocks(const oa_ctx *c) { const int t = plane_threads(c); return std::max(1, (c->ns + t - 1) / t); }
+
 int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
 {
     if (!c->surface) c->win_seeds = true;                          // (the winner records of this pass seed the next search)
@@ -1094,6 +1104,11 @@ int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
                            c->d_state, c->d_src4, c->ns, c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
                            c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->d_partials, po,
                            (unsigned long long *)nullptr);
+    } else if (c->metric == OA_METRIC_PLANE) {
+        hipLaunchKernelGGL(oa::k_pair_accumulate_plane, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
+                           (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
+                           c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n,
+                           c->d_partials, c->loop_active ? &c->d_state->t_acc_start : (unsigned long long *)nullptr);
     } else if (canon_blocks(c) > 0) {
         hipLaunchKernelGGL(oa::k_pair_accumulate_canon, dim3((unsigned)canon_blocks(c)), dim3((unsigned)canon_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
                            (const float4 *)c->d_src4, c->ns, canon_lanes(c), (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
@@ -1112,6 +1127,7 @@ int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
 // rows the (non-emitting) accumulation of this context leaves for the reduce launch when it is its own kernel
 inline oa::RowSel plain_rows(const oa_ctx *c)
 {
+    if (c->metric == OA_METRIC_PLANE) return oa::RowSel{ plane_blocks(c), 0, 0 };
     const int cb = canon_blocks(c);
     return oa::RowSel{ cb > 0 ? cb : c->acc_blocks, 0, 0 };
 }
@@ -1245,7 +1261,7 @@ void init_loop_state(oa_ctx *c, const oa_settings *st, int iters, bool cutoff = 
     s.pad1 = 0.f; s.pad2 = 0;
     s.qmax = c->qmax;
     s.d_pivot = c->d_pivot0;
-    s.jac_valid = 0; s.pad4 = 0;                                    // every loop starts its Jacobi from the identity
+    s.jac_valid = 0; s.plane_rank = 0;                                    // every loop starts its Jacobi from the identity
     for (int k = 0; k < 9; ++k) s.jac_v[k] = 0.0;
 }
 
@@ -1258,6 +1274,13 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
     if (rc) return rc;
     if (!st) return fail(OA_E_BAD_ARG, "null settings");
     if (!(st->thresh > 0.0)) return fail(OA_E_BAD_THRESH, "thresh must be > 0 (the reference's make_pairs returns None)");
+    if (c->metric == OA_METRIC_PLANE) {
+        if (st->with_scale) return fail(OA_E_BAD_ARG, "the plane metric solves for a rigid step: with_scale must be 0 (or call oa_set_metric(ctx, OA_METRIC_POINT))");
+        if (!c->surface && !c->d_tgt_n)
+            return fail(OA_E_STATE, "the plane metric needs target normals: call oa_set_target_normals (or oa_set_normals) after oa_set_target, or upload a mesh with oa_set_target_mesh");
+        if ((long long)c->ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
+            return fail(OA_E_CAPACITY, "the plane metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->ns);
+    }
     if ((rc = use_device(c))) return rc;
     if ((rc = ensure_common(c))) return rc;
     if ((rc = ensure_history(c, iters == ITERATE_OPEN ? ITERATE_RING : iters))) return rc;   // oa_iterate: a small ring
@@ -1309,6 +1332,10 @@ int iter_fused(oa_ctx *c, bool timed)
     bool fused;
     const int rc = launch_search_accumulate(c, timed, sel, fused);
     if (rc) return rc;
+    if (c->metric == OA_METRIC_PLANE)
+        hipLaunchKernelGGL(oa::k_reduce_solve_update_plane, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, c->d_state,
+                           (const double *)c->d_partials, sel.n, c->d_sums, c->d_hist, c->d_todo_count);
+    else
     hipLaunchKernelGGL(oa::k_reduce_solve_update, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, c->d_state,
                        (const double *)c->d_partials, sel, c->d_sums, c->d_hist, c->d_todo_count, fused ? 1 : 0);
     HIPCHK(hipGetLastError());
@@ -1320,6 +1347,7 @@ int fetch_state(oa_ctx *c)
     HIPCHK(hipMemcpyAsync(c->h_state_pin, c->d_state, sizeof(oa::DevState), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->h_state = *c->h_state_pin;
+    if (c->metric == OA_METRIC_PLANE && c->h_state.n > 0) c->last_plane_rank = c->h_state.plane_rank;
     return OA_OK;
 }
 
@@ -3478,6 +3506,42 @@ OA_EXPORT int oa_set_normals(oa_ctx *c, const float *src_normals, int64_t n_vert
     return OA_OK;
 }
 
+OA_EXPORT int oa_set_metric(oa_ctx *c, int metric)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    if (metric != OA_METRIC_POINT && metric != OA_METRIC_PLANE) return fail(OA_E_BAD_ARG, "metric %d (use OA_METRIC_POINT / OA_METRIC_PLANE)", metric);
+    if (metric == c->metric) return OA_OK;
+    // a changed metric ends the running sequence: the next oa_iterate starts a new one from the current matrix_world
+    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
+    else if (c->loop_active) {
+        int rc = use_device(c);
+        if (rc) return rc;
+        if ((rc = fetch_state(c))) return rc;
+        c->loop_active = false;
+    }
+    c->metric = metric;
+    OA_ROUTE_ALL(c, oa_set_metric(sub, metric));
+    return OA_OK;
+}
+
+OA_EXPORT int oa_set_target_normals(oa_ctx *c, const float *tgt_normals, int64_t nt)
+{
+    if (!c || !tgt_normals) return fail(OA_E_BAD_ARG, "oa_set_target_normals: null argument");
+    if (!c->subs.empty() && c->loop_active) multi_abort(c);
+    OA_ROUTE_ALL_PAR(c, oa_set_target_normals(sub, tgt_normals, nt));
+    if (c->nt <= 0) return fail(OA_E_STATE, "oa_set_target_normals: call oa_set_target first");
+    if (c->surface) return fail(OA_E_STATE, "oa_set_target_normals: a surface target (oa_set_target_mesh) uses its triangles' geometric normals");
+    if (nt != c->nt) return fail(OA_E_BAD_ARG, "oa_set_target_normals: %lld normals for %d target vertices", (long long)nt, c->nt);
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (c->loop_active) { HIPCHK(hipStreamSynchronize(c->stream)); c->loop_active = false; }
+    if (c->normals_on) HIPCHK(hipStreamSynchronize(c->stream));    // (the array the normal-angle test reads is replaced in place)
+    if (!c->d_tgt_n) HIPCHK(dev_malloc(&c->d_tgt_n, sizeof(float) * 3 * (size_t)nt));
+    HIPCHK(hipMemcpyAsync(c->d_tgt_n, tgt_normals, sizeof(float) * 3 * (size_t)nt, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
 OA_EXPORT int oa_set_matrices(oa_ctx *c, const float mx_align[16], const float mx_base[16])
 {
     if (!c || !mx_align || !mx_base) return fail(OA_E_BAD_ARG, "oa_set_matrices: null argument");
@@ -3609,6 +3673,8 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
     case OA_STAT_HANDOVER_WAVE_MAX: *value = c->h_poll ? (double)c->h_poll[3] : 0.0; return OA_OK;
     case OA_STAT_SAFE_RADII: *value = (c->grid_safe && c->safe_ok) ? 1.0 : 0.0; return OA_OK;
     case OA_STAT_TRI_RING: *value = (c->tri_ring && c->tri_ring_ok) ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_METRIC: *value = (double)c->metric; return OA_OK;
+    case OA_STAT_PLANE_RANK: *value = (double)c->last_plane_rank; return OA_OK;
     default: return fail(OA_E_BAD_ARG, "oa_get_stat: unknown key %d", what);
     }
 }
@@ -3950,6 +4016,41 @@ OA_EXPORT int oa_kabsch(oa_ctx *c, const double *A, const double *B, int64_t K, 
     return rc;
 }
 
+// the plane step from caller-supplied pairs (the plane counterpart of oa_kabsch): k_accumulate_pairs_plane -> k_reduce_partials_plane
+// -> k_solve_only_plane.  Does not look at the context's metric.
+OA_EXPORT int oa_point_to_plane(oa_ctx *c, const double *A, const double *B, const double *N, int64_t K, int64_t ld, double M[16])
+{
+    if (!c || !M) return fail(OA_E_BAD_ARG, "oa_point_to_plane: null argument");
+    OA_ROUTE_FIRST(c, oa_point_to_plane(sub, A, B, N, K, ld, M));
+    if (K < 3) return fail(OA_E_TOO_FEW_PAIRS, "input arrays are of wrong shape or type");   // the point metric's rule (general.py:150-157)
+    if (!A || !B || !N || ld < K) return fail(OA_E_BAD_ARG, "oa_point_to_plane: bad arrays");
+    int rc = use_device(c);
+    if (rc) return rc;
+    if ((rc = ensure_common(c))) return rc;
+    DevTmp<double> dA, dB, dN;
+    HIPCHK(dA.alloc(3 * (size_t)K));
+    HIPCHK(dB.alloc(3 * (size_t)K));
+    HIPCHK(dN.alloc(3 * (size_t)K));
+    for (int a = 0; a < 3; ++a) {
+        HIPCHK(hipMemcpyAsync(dA.p + (size_t)a * K, A + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dB.p + (size_t)a * K, B + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dN.p + (size_t)a * K, N + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
+    }
+    const double pv[3] = { A[0], A[ld], A[2 * ld] };
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(oa::ACC_MAX_BLOCKS, (K + oa::ACC_THREADS - 1) / oa::ACC_THREADS));
+    hipLaunchKernelGGL(oa::k_accumulate_pairs_plane, dim3(blocks), dim3(oa::ACC_THREADS), 0, c->stream, (const double *)dA.p, (const double *)dB.p,
+                       (const double *)dN.p, (long long)K, (long long)K, pv[0], pv[1], pv[2], c->d_partials);
+    hipLaunchKernelGGL(oa::k_reduce_partials_plane, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, (const double *)c->d_partials, blocks, c->d_sums);
+    hipLaunchKernelGGL(oa::k_solve_only_plane, dim3(1), dim3(64), 0, c->stream, (const double *)c->d_sums, pv[0], pv[1], pv[2], c->d_solve);
+    HIPCHK(hipGetLastError());
+    double out[18];
+    { int rcr = read_small(c, out, c->d_solve, sizeof out); if (rcr) return rcr; }
+    if (out[16] != 1.0) return fail(OA_E_TOO_FEW_PAIRS, "input arrays are of wrong shape or type");   // (pairs with unusable normals do not count)
+    memcpy(M, out, sizeof(double) * 16);
+    c->last_plane_rank = (int)out[17];
+    return OA_OK;
+}
+
 // the reference's full signature: any ndims (2..8 on the fixed-size kernels, up to 64 through a device workspace), shear (full
 // affine) or rigid / similarity
 OA_EXPORT int oa_affine_from_points(oa_ctx *c, const double *v0, const double *v1, int ndims, int64_t K, int64_t ld,
@@ -4034,21 +4135,32 @@ OA_EXPORT int oa_kabsch_from_sums(oa_ctx *c, const double sums[OA_NSUMS], const 
 // ================================================================================================
 // the loop
 // ================================================================================================
-OA_EXPORT int oa_run_begin(oa_ctx *c, const oa_settings *st)
+namespace {
+int run_begin(oa_ctx *c, const oa_settings *st)
 {
-    if (!c || !st) return fail(OA_E_BAD_ARG, "oa_run_begin: null argument");
-    OA_NOT_MULTI(c, "oa_run_begin (the split-phase loop is for one process per GPU)");
     int rc = begin_loop(c, st, st->iters);
     if (rc) return rc;
     if ((rc = ensure_events(c, std::max(1, st->iters)))) return rc;
     HIPCHK(hipEventRecord(c->ev_loop0, c->stream));
     return OA_OK;
 }
+// the exchange of the sums between devices and ranks carries OA_NSUMS doubles: the plane metric's wider row does not go through it
+const char *const PLANE_ONE_DEVICE = ": the plane metric runs on a single-device context through oa_run / oa_iterate (call oa_set_metric(ctx, OA_METRIC_POINT) for this path)";
+}  // namespace
+
+OA_EXPORT int oa_run_begin(oa_ctx *c, const oa_settings *st)
+{
+    if (!c || !st) return fail(OA_E_BAD_ARG, "oa_run_begin: null argument");
+    OA_NOT_MULTI(c, "oa_run_begin (the split-phase loop is for one process per GPU)");
+    if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_run_begin%s", PLANE_ONE_DEVICE);
+    return run_begin(c, st);
+}
 
 OA_EXPORT int oa_iter_partial(oa_ctx *c, double *d_sums)
 {
     if (!c || !d_sums) return fail(OA_E_BAD_ARG, "oa_iter_partial: null argument");
     OA_NOT_MULTI(c, "oa_iter_partial");
+    if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_iter_partial%s", PLANE_ONE_DEVICE);
     if (!c->loop_active) return fail(OA_E_STATE, "oa_iter_partial outside oa_run_begin/oa_run_end");
     int rc = use_device(c);
     if (rc) return rc;
@@ -4059,6 +4171,7 @@ OA_EXPORT int oa_iter_finish(oa_ctx *c, const double *d_sums)
 {
     if (!c || !d_sums) return fail(OA_E_BAD_ARG, "oa_iter_finish: null argument");
     OA_NOT_MULTI(c, "oa_iter_finish");
+    if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_iter_finish%s", PLANE_ONE_DEVICE);
     if (!c->loop_active) return fail(OA_E_STATE, "oa_iter_finish outside oa_run_begin/oa_run_end");
     int rc = use_device(c);
     if (rc) return rc;
@@ -4082,8 +4195,9 @@ OA_EXPORT int oa_run_end(oa_ctx *c, oa_report *rep)
 OA_EXPORT int oa_run(oa_ctx *c, const oa_settings *st, oa_report *rep)
 {
     if (!c || !st || !rep) return fail(OA_E_BAD_ARG, "oa_run: null argument");
+    if (!c->subs.empty() && c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_run on a multi-device context%s", PLANE_ONE_DEVICE);
     if (!c->subs.empty()) return multi_run(c, st, rep);
-    int rc = oa_run_begin(c, st);
+    int rc = run_begin(c, st);
     if (rc) return rc;
     // The whole loop is enqueued ahead of the GPU.  With early exit on, iterations after convergence would still cost
     // three empty launches each (the kernels see DevState.halt and return) -- for a small mesh that converges in 7 of 50
@@ -4127,6 +4241,7 @@ OA_EXPORT int oa_iterate(oa_ctx *c, const oa_settings *st, double M_step[16], do
 {
     if (!c || !st) return fail(OA_E_BAD_ARG, "oa_iterate: null argument");
     const bool multi = !c->subs.empty();
+    if (multi && c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_iterate on a multi-device context%s", PLANE_ONE_DEVICE);
     int rc;
     if (c->loop_active && !(c->iterate_mode && same_loop_settings(*st, c->settings))) {
         if (multi) multi_abort(c);

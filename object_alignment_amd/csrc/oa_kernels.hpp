@@ -29,6 +29,13 @@ constexpr int NSUMS = 24;
 //   [0..2] sum a'   [3..5] sum b'   [6..14] sum b'_i a'_j (row i, col j)   [15] sum |a'|^2   [16] sum |b'|^2
 //   [17] K          [18] sum (d - d_pivot)      [19] sum (d - d_pivot)^2        [20..23] reserved (0)
 constexpr int S_A = 0, S_B = 3, S_H = 6, S_AA = 15, S_BB = 16, S_K = 17, S_D = 18, S_DD = 19;
+// the point-to-plane metric (Chen & Medioni; oa_set_metric) sums a wider row.  Per pair, relative to the same pivot: n = the
+// correspondence's unit normal in align-local space, r = n . (a' - b'), J = [a' x n, n] (the row of the linearised step
+// x = (omega, t)):
+//   [0..20] sum J J^T, upper triangle by rows ((0,0) (0,1) .. (0,5) (1,1) .. (5,5))   [21..26] sum J r   [27] K
+//   [28] sum (d - d_pivot)   [29] sum (d - d_pivot)^2   [30] sum r^2   [31] spare (0)
+constexpr int NSUMS_PLANE = 32;
+constexpr int P_JJ = 0, P_JR = 21, P_K = 27, P_D = 28, P_DD = 29, P_RR = 30;
 
 constexpr unsigned long long KEY_EMPTY = ~0ull;
 constexpr uint32_t IDX_NONE = 0xFFFFFFFFu;
@@ -89,7 +96,8 @@ struct DevState {
     // H = sum b a^T ~ R (sum a a^T), so H^T H -- what V diagonalises -- hardly changes from one iteration to the next:
     // started from the last V a solve takes one sweep of small rotations instead of three (8 rotations -> 3).
     double jac_v[9];
-    int32_t jac_valid, pad4;
+    int32_t jac_valid;
+    int32_t plane_rank;       // plane metric: eigenvalues the last solve kept (OA_STAT_PLANE_RANK); 0 otherwise
 };
 
 // Squared local search radius for the query p (rounded up to float).  Derivation: the pair test measures
@@ -413,6 +421,118 @@ __host__ __device__ inline double rotation_angle_3x3(const double M[16])
     double x = (tr - 1.0) * 0.5;
     x = x > 1.0 ? 1.0 : (x < -1.0 ? -1.0 : x);
     return acos(x);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The point-to-plane step from its sums: (sum J J^T) x = -sum J r, minimum-norm solution through the symmetric
+// eigen-decomposition (cyclic Jacobi in fp64, the pattern of rotation_from_covariance_horn), then M = T(c) T(t) R T(-c) with
+// R = exp([omega]x) (Rodrigues: an exact rotation, so the float32 matrix_world never picks up shear from the step).
+// ------------------------------------------------------------------------------------------------
+#if defined(__HIP_DEVICE_COMPILE__)
+#define OA_WAVE_LDS_FENCE() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront")
+#else
+#define OA_WAVE_LDS_FENCE() ((void)0)
+#endif
+
+// position of (i, j), i <= j, in the upper triangle stored by rows
+__host__ __device__ inline int sym6_index(int i, int j) { return 6 * i - (i * (i - 1)) / 2 + (j - i); }
+
+// Eigen-decomposition of the symmetric 6 x 6 in A (row-major, 36 doubles): on return its diagonal holds the eigenvalues and the
+// columns of V the eigenvectors.  Written for ONE WAVEFRONT with A and V in LDS (dynamic indices, no registers spent on 72
+// doubles): every lane computes a rotation's angle from the same three entries, lane k in [k0, k1) applies it to row / column k.
+// The device passes k0 = lane, k1 = lane + 1 for lanes 0..5 and an empty range for the others; a single thread (the host)
+// passes [0, 6) and runs the same arithmetic serially.  Called by all lanes of the wave.
+__host__ __device__ inline void sym6_jacobi(double *A, double *V, int k0, int k1)
+{
+    for (int k = k0; k < k1; ++k)
+        for (int j = 0; j < 6; ++j) V[6 * k + j] = (j == k) ? 1.0 : 0.0;
+    OA_WAVE_LDS_FENCE();
+    for (int sweep = 0; sweep < 32; ++sweep) {
+        double off = 0.0, diag = 0.0;
+        for (int p = 0; p < 6; ++p) { diag += fabs(A[7 * p]); for (int q = p + 1; q < 6; ++q) off += fabs(A[6 * p + q]); }
+        if (!(off > 1e-300) || off <= 1e-18 * diag) break;
+        for (int p = 0; p < 5; ++p)
+            for (int q = p + 1; q < 6; ++q) {
+                const double apq = A[6 * p + q], app = A[7 * p], aqq = A[7 * q];
+                if (apq == 0.0) continue;                                   // (uniform: every lane reads the same entry)
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+                OA_WAVE_LDS_FENCE();                                        // the reads above, before any lane's writes below
+                for (int k = k0; k < k1; ++k) {                             // columns p, q of A and of V
+                    const double a = A[6 * k + p], b = A[6 * k + q]; A[6 * k + p] = c * a - sn * b; A[6 * k + q] = sn * a + c * b;
+                    const double u = V[6 * k + p], w = V[6 * k + q]; V[6 * k + p] = c * u - sn * w; V[6 * k + q] = sn * u + c * w;
+                }
+                OA_WAVE_LDS_FENCE();
+                for (int k = k0; k < k1; ++k) {                             // rows p, q of A
+                    const double a = A[6 * p + k], b = A[6 * q + k]; A[6 * p + k] = c * a - sn * b; A[6 * q + k] = sn * a + c * b;
+                }
+                OA_WAVE_LDS_FENCE();
+            }
+    }
+}
+
+// Eigenvalues below PLANE_EIG_CUT x the largest count as zero: a plane, a sphere, a cylinder leave 3 / 3 / 2 directions of
+// (omega, t) the data cannot see, and the step must not move along them.  A guard, not a tuning knob.
+constexpr double PLANE_EIG_CUT = 1e-10;
+
+// M = T(c) T(t) exp([omega]x) T(-c), x = (omega, t)
+__host__ __device__ inline void plane_step_matrix(const double x[6], const double c[3], double M[16])
+{
+    const double wx = x[0], wy = x[1], wz = x[2];
+    const double th2 = (wx * wx + wy * wy) + wz * wz;
+    double a, b;                                                            // sin(th) / th, (1 - cos(th)) / th^2
+    if (th2 < 1e-8) {                                                       // th < 1e-4: the series, next term th^6 / 5040
+        a = 1.0 - th2 / 6.0 * (1.0 - th2 / 20.0);
+        b = 0.5 - th2 / 24.0 * (1.0 - th2 / 30.0);
+    } else {
+        const double th = sqrt(th2), sh = sin(0.5 * th);
+        a = sin(th) / th;
+        b = 2.0 * sh * sh / th2;
+    }
+    const double d = 1.0 - b * th2;
+    double R[9];
+    R[0] = d + b * wx * wx;      R[1] = b * wx * wy - a * wz; R[2] = b * wx * wz + a * wy;
+    R[3] = b * wx * wy + a * wz; R[4] = d + b * wy * wy;      R[5] = b * wy * wz - a * wx;
+    R[6] = b * wx * wz - a * wy; R[7] = b * wy * wz + a * wx; R[8] = d + b * wz * wz;
+    for (int i = 0; i < 3; ++i) {
+        double t = c[i] + x[3 + i];
+        for (int j = 0; j < 3; ++j) { M[4 * i + j] = R[3 * i + j]; t -= R[3 * i + j] * c[j]; }
+        M[4 * i + 3] = t;
+    }
+    M[12] = 0.0; M[13] = 0.0; M[14] = 0.0; M[15] = 1.0;
+}
+
+// s: the NSUMS_PLANE sums (readable by every caller); A, V: 36 doubles of workspace each, shared by the callers (LDS on the
+// device); [k0, k1): see sym6_jacobi.  Returns false when K < 3 (OA_E_TOO_FEW_PAIRS, as the point metric); rank = the
+// eigenvalues kept (6 = the pairs determine the whole step).  Called by all lanes of one wave / by one host thread.
+__host__ __device__ inline bool plane_solve_from_sums(const double *s, const double pivot[3], double *A, double *V, int k0, int k1,
+                                                      double M[16], int &rank)
+{
+    rank = 0;
+    if (!(s[P_K] >= 3.0)) return false;
+    for (int k = k0; k < k1; ++k)
+        for (int j = 0; j < 6; ++j) A[6 * k + j] = s[P_JJ + (k <= j ? sym6_index(k, j) : sym6_index(j, k))];
+    OA_WAVE_LDS_FENCE();
+    sym6_jacobi(A, V, k0, k1);
+    double lam_max = 0.0;
+    for (int i = 0; i < 6; ++i) lam_max = A[7 * i] > lam_max ? A[7 * i] : lam_max;
+    const double cut = PLANE_EIG_CUT * lam_max;
+    double x[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const double lam = A[7 * i];
+        if (!(lam > cut) || !(lam > 0.0)) continue;
+        ++rank;
+        double d = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) d += V[6 * k + i] * s[P_JR + k];
+        const double f = -d / lam;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) x[j] += f * V[6 * j + i];
+    }
+    plane_step_matrix(x, pivot, M);
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2141,6 +2261,142 @@ __global__ __launch_bounds__(CANON_THREADS) void k_pair_accumulate_canon(const D
 }
 #endif  // !OA_FAMILY_TU
 
+// ---- the point-to-plane metric (oa_set_metric(OA_METRIC_PLANE)): the same pair test, the sums of the plane system ---------
+// The correspondence's normal in align-local space, unit length, fp64: base-local tn -> world with the inverse transpose of
+// mx2 (as normal_angle_ok carries it) -> align-local with mx1^T (the inverse transpose of imx1).  false: zero or non-finite
+// length (a degenerate triangle) -- the pair then takes no part in the step.
+__device__ __forceinline__ bool plane_normal(const DevState *__restrict__ st, const float *tn, double &nx, double &ny, double &nz)
+{
+    double w[3], l[3];
+    for (int k = 0; k < 3; ++k)
+        w[k] = (double)st->imx2[k] * (double)tn[0] + (double)st->imx2[4 + k] * (double)tn[1] + (double)st->imx2[8 + k] * (double)tn[2];
+    for (int k = 0; k < 3; ++k)
+        l[k] = (double)st->mx1[k] * w[0] + (double)st->mx1[4 + k] * w[1] + (double)st->mx1[8 + k] * w[2];
+    const double n2 = (l[0] * l[0] + l[1] * l[1]) + l[2] * l[2];
+    if (!(n2 > 0.0) || !(n2 < INFINITY)) return false;
+    const double inv = 1.0 / sqrt(n2);
+    nx = l[0] * inv; ny = l[1] * inv; nz = l[2] * inv;
+    return true;
+}
+
+// residual and Jacobian row of one pair (a, b relative to the pivot; n unit)
+__device__ __forceinline__ void plane_row(double a0, double a1, double a2, double b0, double b1, double b2, double nx, double ny, double nz,
+                                          double (&j)[6], double &r)
+{
+    r = (nx * (a0 - b0) + ny * (a1 - b1)) + nz * (a2 - b2);
+    j[0] = a1 * nz - a2 * ny; j[1] = a2 * nx - a0 * nz; j[2] = a0 * ny - a1 * nx;
+    j[3] = nx; j[4] = ny; j[5] = nz;
+}
+
+// a pair's contribution to the row, in three slices of 12 + 12 + 8 sums (NSUMS_PLANE's layout)
+__device__ __forceinline__ void plane_terms_0(const double (&j)[6], double (&h)[12])
+{
+    h[0] = j[0] * j[0]; h[1] = j[0] * j[1]; h[2] = j[0] * j[2]; h[3] = j[0] * j[3]; h[4] = j[0] * j[4]; h[5] = j[0] * j[5];
+    h[6] = j[1] * j[1]; h[7] = j[1] * j[2]; h[8] = j[1] * j[3]; h[9] = j[1] * j[4]; h[10] = j[1] * j[5]; h[11] = j[2] * j[2];
+}
+__device__ __forceinline__ void plane_terms_1(const double (&j)[6], double r, double (&h)[12])
+{
+    h[0] = j[2] * j[3]; h[1] = j[2] * j[4]; h[2] = j[2] * j[5]; h[3] = j[3] * j[3]; h[4] = j[3] * j[4]; h[5] = j[3] * j[5];
+    h[6] = j[4] * j[4]; h[7] = j[4] * j[5]; h[8] = j[5] * j[5]; h[9] = j[0] * r; h[10] = j[1] * r; h[11] = j[2] * r;
+}
+__device__ __forceinline__ void plane_terms_2(const double (&j)[6], double r, double one, double dd, double (&h)[8])
+{
+    h[0] = j[3] * r; h[1] = j[4] * r; h[2] = j[5] * r; h[3] = one; h[4] = dd; h[5] = dd * dd; h[6] = r * r; h[7] = 0.0;
+}
+
+// the waves' rows in red -> the workgroup's row, waves in order.  Called by ALL threads, after the last slice.
+__device__ __forceinline__ void block_finish_plane(double (*red)[NSUMS_PLANE], double *__restrict__ row)
+{
+    __syncthreads();
+    if (threadIdx.x < NSUMS_PLANE) {
+        double v = red[0][threadIdx.x];
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) v += red[w][threadIdx.x];
+        row[threadIdx.x] = v;
+    }
+}
+
+// block_store_pair for the plane row: ONE pair per lane, formed and reduced slice by slice (the same reduce-scatter), so the
+// epilogue never holds 32 sums and the butterfly's temporaries at once.  red: __shared__ double[blockDim.x / 64][NSUMS_PLANE].
+__device__ __forceinline__ void block_store_plane(bool valid, const double (&jj)[6], double r, double dd, double (*red)[NSUMS_PLANE],
+                                                  double *__restrict__ row)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double j[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) j[k] = valid ? jj[k] : 0.0;
+    if (!valid) { r = 0.0; dd = 0.0; }
+    { double h[12]; plane_terms_0(j, h); wave_reduce_scatter<12>(h, lane, &red[wave][0]); }
+    { double h[12]; plane_terms_1(j, r, h); wave_reduce_scatter<12>(h, lane, &red[wave][12]); }
+    { double h[8]; plane_terms_2(j, r, valid ? 1.0 : 0.0, dd, h); wave_reduce_scatter<8>(h, lane, &red[wave][24]); }
+    block_finish_plane(red, row);
+}
+
+// k_pair_accumulate_canon for the plane metric: the same reads, the same resetting of keys / prev / win, the same pair test
+// (pair_eval), then the plane row.  One thread per source slot; plane_tn: vertex mode, one base-local normal per target
+// vertex (surface mode: nullptr, the nearest triangle's geometric normal in the operand order of the normal-angle test).
+// Its workgroups depend on the shard size alone, so every search mode leaves the same rows.
+constexpr int PLANE_THREADS = 512;
+constexpr int PLANE_MAX_BLOCKS = 16384;
+#if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
+__global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_plane(const DevState *__restrict__ st, const float4 *__restrict__ src4,
+                                                               int ns, const float *__restrict__ tgt_xyz,
+                                                               unsigned long long *__restrict__ keys, int *__restrict__ prev,
+                                                               float4 *__restrict__ win, const float4 *__restrict__ tri9,
+                                                               NormalTest nrm, const float *__restrict__ plane_tn,
+                                                               double *__restrict__ partials,
+                                                               unsigned long long *__restrict__ t_acc_start)
+{
+    __shared__ double red[PLANE_THREADS / 64][NSUMS_PLANE];
+    if (t_acc_start && blockIdx.x == 0 && threadIdx.x == 0) *t_acc_start = wall_clock64();   // ~ the end of the search
+    if (st->halt) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool valid = false;
+    float bx = 0.f, by = 0.f, bz = 0.f;
+    double dist = 0.0, nx = 0.0, ny = 0.0, nz = 0.0;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < ns) {
+        const unsigned long long key = keys[i];
+        keys[i] = KEY_EMPTY;                                       // ready for the next iteration's atomicMin
+        const uint32_t idx = (uint32_t)key;
+        if (prev) prev[i] = (idx == IDX_NONE) ? -1 : (int)idx;
+        p = src4[i];
+        float4 wrec = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+        if (win) wrec = win[i];
+        if (idx != IDX_NONE) {
+            float cx, cy, cz;
+            co_find(st, p.x, p.y, p.z, cx, cy, cz);           // co_find                   (general.py:287)
+            float qx, qy, qz;
+            float tn[3];
+            if (tri9) {
+                float ta[3], tb[3], tc[3], rr[3];
+                const float cf[3] = { cx, cy, cz };
+                load_tri(tri9, idx, ta, tb, tc);
+                closest_on_tri(cf, ta, tb, tc, rr);
+                qx = rr[0]; qy = rr[1]; qz = rr[2];
+                const float e1[3] = { ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2] };
+                const float e2[3] = { tb[0] - tc[0], tb[1] - tc[1], tb[2] - tc[2] };
+                tn[0] = e1[1] * e2[2] - e1[2] * e2[1];
+                tn[1] = e1[2] * e2[0] - e1[0] * e2[2];
+                tn[2] = e1[0] * e2[1] - e1[1] * e2[0];
+            } else {
+                if ((uint32_t)__float_as_int(wrec.w) == idx) { qx = wrec.x; qy = wrec.y; qz = wrec.z; }
+                else {
+                    qx = tgt_xyz[3ll * idx]; qy = tgt_xyz[3ll * idx + 1]; qz = tgt_xyz[3ll * idx + 2];
+                    if (win) win[i] = make_float4(qx, qy, qz, __int_as_float((int)idx));
+                }
+                tn[0] = plane_tn[3ll * idx]; tn[1] = plane_tn[3ll * idx + 1]; tn[2] = plane_tn[3ll * idx + 2];
+            }
+            valid = pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, tn, st->thresh, bx, by, bz, dist);
+            if (valid) valid = plane_normal(st, tn, nx, ny, nz);
+        }
+    }
+    const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
+    double j[6], r;
+    plane_row((double)p.x - pvx, (double)p.y - pvy, (double)p.z - pvz, (double)bx - pvx, (double)by - pvy, (double)bz - pvz, nx, ny, nz, j, r);
+    block_store_plane(valid, j, r, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE);
+}
+#endif  // !OA_FAMILY_TU
+
 // ---- fixed-order reduction of the rows of per-workgroup partials (bitwise reproducible, no float atomics) -------------
 // A row is NSUMS doubles = 12 x 16 bytes.  1024 threads = 85 slices of 12 threads: slice s adds rows s, s + 85, ... in
 // order (thread c of a slice owns columns 2c, 2c + 1 and loads them as one 16-byte word, 16 rows in flight per thread),
@@ -2148,21 +2404,25 @@ __global__ __launch_bounds__(CANON_THREADS) void k_pair_accumulate_canon(const D
 // <= 512 rows of k_pair_accumulate; the search kernels that accumulate in their epilogue write one row per workgroup,
 // up to 4096 of them, and a chain of 16 round trips per thread would cost more than the launch the fusion saves.
 constexpr int RED_THREADS = 1024;
-constexpr int RED_SLICES = RED_THREADS / 12;        // 85
 
-// rows [0, n_rows) of `rows` -> out[0 .. NSUMS) (shared or global).  Called by all RED_THREADS threads of a workgroup.
+// rows [0, n_rows) of `rows` -> out[0 .. W) (shared or global).  Called by all RED_THREADS threads of a workgroup.
+// W = doubles per row: NSUMS (the numbers above) or NSUMS_PLANE (16 threads per row, 64 slices; same scheme).
+template <int W = NSUMS>
 __device__ __forceinline__ void reduce_rows_block(const double *__restrict__ rows, int n_rows, double *out)
 {
-    __shared__ double red[RED_SLICES][NSUMS];
-    const int s = threadIdx.x / 12, c = threadIdx.x - 12 * s;
+    static_assert(W % 2 == 0 && W <= 64, "a thread owns two columns of a row");
+    constexpr int TPR = W / 2;                          // threads per row: 12
+    constexpr int RED_SLICES = RED_THREADS / TPR;       // 85
+    __shared__ double red[RED_SLICES][W];
+    const int s = threadIdx.x / TPR, c = threadIdx.x - TPR * s;
     if (s < RED_SLICES) {
         double v0 = 0.0, v1 = 0.0;
-        const double2 *__restrict__ col = (const double2 *)rows + c;       // row r, columns 2c, 2c+1: col[12 r]
+        const double2 *__restrict__ col = (const double2 *)rows + c;       // row r, columns 2c, 2c+1: col[TPR r]
         int r = s;
         for (; r + 15 * RED_SLICES < n_rows; r += 16 * RED_SLICES) {
             double2 p[16];
 #pragma unroll
-            for (int u = 0; u < 16; ++u) p[u] = col[12ll * (r + RED_SLICES * u)];
+            for (int u = 0; u < 16; ++u) p[u] = col[(long long)TPR * (r + RED_SLICES * u)];
 #pragma unroll
             for (int u = 0; u < 16; ++u) { v0 += p[u].x; v1 += p[u].y; }
         }
@@ -2175,7 +2435,7 @@ __device__ __forceinline__ void reduce_rows_block(const double *__restrict__ row
             for (int u = 0; u < 16; ++u) {
                 const int rr = r + RED_SLICES * u;
                 p[u] = make_double2(0.0, 0.0);
-                if (rr < n_rows) p[u] = col[12ll * rr];
+                if (rr < n_rows) p[u] = col[(long long)TPR * rr];
             }
 #pragma unroll
             for (int u = 0; u < 16; ++u)
@@ -2186,7 +2446,7 @@ __device__ __forceinline__ void reduce_rows_block(const double *__restrict__ row
             for (int u = 0; u < 4; ++u) {
                 const int rr = r + RED_SLICES * u;
                 p[u] = make_double2(0.0, 0.0);
-                if (rr < n_rows) p[u] = col[12ll * rr];
+                if (rr < n_rows) p[u] = col[(long long)TPR * rr];
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u)
@@ -2195,7 +2455,7 @@ __device__ __forceinline__ void reduce_rows_block(const double *__restrict__ row
         red[s][2 * c] = v0; red[s][2 * c + 1] = v1;
     }
     __syncthreads();
-    if (threadIdx.x < NSUMS) {
+    if (threadIdx.x < W) {
         double t = red[0][threadIdx.x];
         for (int k = 1; k < RED_SLICES; ++k) t += red[k][threadIdx.x];
         out[threadIdx.x] = t;
@@ -2266,6 +2526,62 @@ __global__ void k_solve_only(const double *__restrict__ sums, double pvx, double
     for (int k = 0; k < 16; ++k) out[k] = ok ? M[k] : 0.0;
     out[16] = ok ? 1.0 : 0.0;
 }
+
+// the plane row over explicit pairs (oa_point_to_plane).  A, B, N: 3 x K row-major with leading dimension ld; N need not be unit
+// (a pair whose normal has zero or non-finite length is left out, as in the loop).  No distances: sums P_D, P_DD stay 0.
+__global__ __launch_bounds__(ACC_THREADS) void k_accumulate_pairs_plane(const double *__restrict__ A, const double *__restrict__ B,
+                                                                        const double *__restrict__ N, long long K, long long ld,
+                                                                        double pvx, double pvy, double pvz, double *__restrict__ partials)
+{
+    __shared__ double red[ACC_THREADS / 64][NSUMS_PLANE];
+    double acc0[12], acc1[12], acc2[8];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { acc0[k] = 0.0; acc1[k] = 0.0; }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc2[k] = 0.0;
+    for (long long i = (long long)blockIdx.x * ACC_THREADS + threadIdx.x; i < K; i += (long long)gridDim.x * ACC_THREADS) {
+        const double l0 = N[i], l1 = N[ld + i], l2 = N[2 * ld + i];
+        const double n2 = (l0 * l0 + l1 * l1) + l2 * l2;
+        if (!(n2 > 0.0) || !(n2 < INFINITY)) continue;
+        const double inv = 1.0 / sqrt(n2);
+        double j[6], r, h0[12], h1[12], h2[8];
+        plane_row(A[i] - pvx, A[ld + i] - pvy, A[2 * ld + i] - pvz, B[i] - pvx, B[ld + i] - pvy, B[2 * ld + i] - pvz, l0 * inv, l1 * inv, l2 * inv, j, r);
+        plane_terms_0(j, h0); plane_terms_1(j, r, h1); plane_terms_2(j, r, 1.0, 0.0, h2);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { acc0[k] += h0[k]; acc1[k] += h1[k]; }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc2[k] += h2[k];
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    wave_reduce_scatter<12>(acc0, lane, &red[wave][0]);
+    wave_reduce_scatter<12>(acc1, lane, &red[wave][12]);
+    wave_reduce_scatter<8>(acc2, lane, &red[wave][24]);
+    block_finish_plane(red, partials + (long long)blockIdx.x * NSUMS_PLANE);
+}
+
+// rows of the plane layout -> sums (oa_point_to_plane; the loop reduces inside k_reduce_solve_update_plane)
+__global__ __launch_bounds__(RED_THREADS) void k_reduce_partials_plane(const double *__restrict__ partials, int n_rows, double *__restrict__ sums_out)
+{
+    reduce_rows_block<NSUMS_PLANE>(partials, n_rows, sums_out);
+}
+
+// one wave: the plane solve only (oa_point_to_plane).  out[0..15] = M, out[16] = ok flag, out[17] = rank
+__global__ __launch_bounds__(64) void k_solve_only_plane(const double *__restrict__ sums, double pvx, double pvy, double pvz, double *__restrict__ out)
+{
+    __shared__ double sh_s[NSUMS_PLANE], sh_A[36], sh_V[36];
+    const int lane = threadIdx.x;
+    if (lane < NSUMS_PLANE) sh_s[lane] = sums[lane];
+    __syncthreads();
+    const double pv[3] = { pvx, pvy, pvz };
+    double M[16];
+    int rank;
+    const bool ok = plane_solve_from_sums(sh_s, pv, sh_A, sh_V, lane < 6 ? lane : 6, lane < 6 ? lane + 1 : 6, M, rank);
+    if (lane == 0) {
+        for (int k = 0; k < 16; ++k) out[k] = ok ? M[k] : 0.0;
+        out[16] = ok ? 1.0 : 0.0;
+        out[17] = (double)rank;
+    }
+}
 #endif  // !OA_FAMILY_TU
 
 // ------------------------------------------------------------------------------------------------
@@ -2307,10 +2623,14 @@ __device__ __forceinline__ void snapshot_state(const DevState *__restrict__ st, 
     for (int t = threadIdx.x; t < (int)(sizeof(DevState) / 4); t += blockDim.x) ((uint32_t *)sh)[t] = ((const uint32_t *)st)[t];
 }
 
+// PLANE: `sums` is a row of NSUMS_PLANE and the solve is plane_solve_from_sums (all of wave 0 together, its 6 x 6 in LDS); what
+// follows M is the same code for both metrics.
+template <bool PLANE = false>
 __device__ __forceinline__ void solve_update_block(DevState *__restrict__ st, const DevState *cs, const double *sums,
                                                    StepRecord *__restrict__ hist, int *__restrict__ todo_count,
                                                    unsigned long long t_sums_in_hand = 0ull)
 {
+    constexpr int I_K = PLANE ? P_K : S_K, I_D = PLANE ? P_D : S_D, I_DD = PLANE ? P_DD : S_DD;
     // st: the loop state in global memory (written); cs: its snapshot from the start of this launch (read)
     __shared__ double sh_M[16];
     __shared__ float sh_new[16], sh_mw[16];
@@ -2327,20 +2647,31 @@ __device__ __forceinline__ void solve_update_block(DevState *__restrict__ st, co
     __syncthreads();
     if (!sh_go) return;                                             // (uniform)
     if (wave == 0) {
-        double s[NSUMS], M[16];
-        for (int k = 0; k < NSUMS; ++k) s[k] = sums[k];
+        double M[16];
         double jv[9];
-        const bool jv_valid = cs->jac_valid != 0;
-        for (int k = 0; k < 9; ++k) jv[k] = jv_valid ? cs->jac_v[k] : 0.0;
-        const bool ok = solve_from_sums(s, cs->pivot, cs->with_scale != 0, M, jv, jv_valid);
+        bool ok;
+        if constexpr (PLANE) {
+            __shared__ double sh_A[36], sh_V[36];
+            int rank;
+            ok = plane_solve_from_sums(sums, cs->pivot, sh_A, sh_V, lane < 6 ? lane : 6, lane < 6 ? lane + 1 : 6, M, rank);
+            if (lane == 0) st->plane_rank = rank;
+        } else {
+            double s[NSUMS];
+            for (int k = 0; k < NSUMS; ++k) s[k] = sums[k];
+            const bool jv_valid = cs->jac_valid != 0;
+            for (int k = 0; k < 9; ++k) jv[k] = jv_valid ? cs->jac_v[k] : 0.0;
+            ok = solve_from_sums(s, cs->pivot, cs->with_scale != 0, M, jv, jv_valid);
+        }
         if (lane == 0) {
             if (!ok) {                                              // K < 3 -> ValueError in the reference: OA_E_TOO_FEW_PAIRS
                 st->status = -3; st->halt = 1; sh_go = 0;
                 if (cs->host_halt) cs->host_halt[0] = 1;            // the enqueuing host stops here too (it would wait for progress that never comes)
             }
             else {
-                for (int k = 0; k < 9; ++k) st->jac_v[k] = jv[k];
-                st->jac_valid = 1;
+                if constexpr (!PLANE) {
+                    for (int k = 0; k < 9; ++k) st->jac_v[k] = jv[k];
+                    st->jac_valid = 1;
+                }
                 for (int k = 0; k < 16; ++k) { sh_M[k] = M[k]; sh_new[k] = (float)M[k]; }   // new_mat[y][z] = M[y][z]  (:116-119)
             }
         }
@@ -2391,10 +2722,10 @@ __device__ __forceinline__ void solve_update_block(DevState *__restrict__ st, co
         for (int k = 0; k < 16; ++k) M[k] = sh_M[k];
         const double trans = v3_length(sh_new[3], sh_new[7], sh_new[11]);
         const double angle = rotation_angle_3x3(M);
-        const double K = sums[S_K];
-        const double mean_dd = sums[S_D] / K;                       // mean of (d - d_pivot)
+        const double K = sums[I_K];
+        const double mean_dd = sums[I_D] / K;                       // mean of (d - d_pivot)
         const double mean_d = mean_dd + cs->d_pivot;
-        double var = sums[S_DD] / K - mean_dd * mean_dd;
+        double var = sums[I_DD] / K - mean_dd * mean_dd;
         if (var < 0.0) var = 0.0;
         if (hist && cs->max_records > 0) {
             StepRecord &r = hist[n % cs->max_records];
@@ -2447,6 +2778,21 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce_solve_update(DevState *_
     if (stamp && threadIdx.x == 0) cs.t_acc_start = t_start;       // the search + accumulate part ended where this launch began
     if (threadIdx.x < NSUMS && sums_out) sums_out[threadIdx.x] = sums[threadIdx.x];
     solve_update_block(st, &cs, sums, hist, todo_count);
+}
+
+// the same launch for the plane metric: rows of NSUMS_PLANE, the 6 x 6 solve, the shared tail.  (Its accumulation is always a
+// launch of its own, which stamps the end of the search.)
+__global__ __launch_bounds__(RED_THREADS) void k_reduce_solve_update_plane(DevState *__restrict__ st, const double *__restrict__ partials,
+                                                                           int n_rows, double *__restrict__ sums_out,
+                                                                           StepRecord *__restrict__ hist, int *__restrict__ todo_count)
+{
+    __shared__ double sums[NSUMS_PLANE];
+    __shared__ DevState cs;
+    snapshot_state(st, &cs);
+    reduce_rows_block<NSUMS_PLANE>(partials, n_rows, sums);        // (its barrier also publishes the snapshot)
+    __syncthreads();
+    if (threadIdx.x < NSUMS_PLANE && sums_out) sums_out[threadIdx.x] = sums[threadIdx.x];
+    solve_update_block<true>(st, &cs, sums, hist, todo_count);
 }
 #endif  // !OA_FAMILY_TU
 

@@ -32,6 +32,9 @@ class EngineShard:
 
     def begin(self):
         import torch
+        if int(self.engine.stat("metric")) != capi.OA_METRIC_POINT:
+            # (oa_run_begin refuses too: the all-reduce carries OA_NSUMS doubles, the plane system needs 32)
+            raise RuntimeError("the plane metric runs on a single-device engine through run() / iterate(): call set_metric('point') for a sharded loop")
         self.engine.set_stream(torch.cuda.current_stream().cuda_stream)
         self.engine.run_begin(**self.kw)
 

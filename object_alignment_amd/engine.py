@@ -176,6 +176,24 @@ class IcpEngine:
         self._chk(self._L.oa_set_normals(self._h, capi.fptr(sn), len(sn), capi.fptr(tn) if tn is not None else None,
                                           len(tn) if tn is not None else 0, float(max_angle_deg)))
 
+    METRICS = {"point": capi.OA_METRIC_POINT, "plane": capi.OA_METRIC_PLANE}
+
+    def set_metric(self, metric):
+        """What a loop step minimises: 'point' (Besl-McKay, the reference's loop, default) or 'plane' (Chen-Medioni: the distance
+        to the tangent plane at the correspondence; single-device contexts, run() / iterate(), no scale).  Survives uploads
+        and set_matrices; stat("metric") reads it back."""
+        if isinstance(metric, str):
+            if metric not in self.METRICS:
+                raise ValueError("metric %r (use 'point' or 'plane')" % (metric,))
+            metric = self.METRICS[metric]
+        self._chk(self._L.oa_set_metric(self._h, int(metric)))
+
+    def set_target_normals(self, tgt_normals):
+        """Vertex-mode targets: one base-local normal per target vertex, for the plane metric (the normal-angle test stays as
+        it is).  Call after set_target; a new target upload forgets them."""
+        tn = capi.as_f32(tgt_normals).reshape(-1, 3)
+        self._chk(self._L.oa_set_target_normals(self._h, capi.fptr(tn), len(tn)))
+
     def set_matrices(self, mx_align, mx_base):
         a, b = capi.as_f32(mx_align, (4, 4)), capi.as_f32(mx_base, (4, 4))
         self._chk(self._L.oa_set_matrices(self._h, capi.fptr(a), capi.fptr(b)))
@@ -188,7 +206,8 @@ class IcpEngine:
              "brute_kernel": 7, "exchange": 8, "rccl_ranks": 9, "enqueue_us": 10, "host_threads": 11,
              "fast_iterations": 12, "handover_entries": 13, "handover_wave_max": 14, "enqueued_min": 15, "enqueued_max": 16,
              "watchdog_aborts": 17, "nn_ms_min": 18, "nn_ms_max": 19, "safe_radii": 20,
-             "tri_ring": 21, "tri_ring_accepts": 22, "exchange_us": 23, "rccl_fallbacks": 24, "rccl_ranks_last": 25, "search_clock_mhz": 26, "brute_queue_wgs": 27}
+             "tri_ring": 21, "tri_ring_accepts": 22, "exchange_us": 23, "rccl_fallbacks": 24, "rccl_ranks_last": 25, "search_clock_mhz": 26, "brute_queue_wgs": 27,
+             "metric": 28, "plane_rank": 29}
     EXCHANGE_NAMES = {-1: None, 0: "mailbox (pinned host memory)", 1: "rccl", 2: "mailbox (peer-mapped device memory)"}
 
     def exchange_info(self):
@@ -288,6 +307,22 @@ class IcpEngine:
         M = np.empty((4, 4), np.float64)
         rc = self._L.oa_kabsch_from_sums(self._h, capi.dptr(s), capi.dptr(pv) if pv is not None else None,
                                          int(bool(scale)), capi.dptr(M))
+        if rc == capi.OA_E_TOO_FEW_PAIRS:
+            raise ValueError(REF_VALUEERROR)
+        self._chk(rc)
+        return M
+
+    def point_to_plane(self, A, B, N) -> np.ndarray:
+        """The plane step from explicit pairs (3 x K each; N: the correspondences' normals, any length): the 4 x 4 that moves A
+        towards the tangent planes at B, about the pivot A[:, 0]; minimum-norm where the pairs leave the step undetermined
+        (stat("plane_rank") says how many directions they fix)."""
+        A = np.ascontiguousarray(A, np.float64)
+        B = np.ascontiguousarray(B, np.float64)
+        N = np.ascontiguousarray(N, np.float64)
+        if A.ndim != 2 or A.shape[0] != 3 or B.shape != A.shape or N.shape != A.shape:
+            raise ValueError(REF_VALUEERROR)
+        M = np.empty((4, 4), np.float64)
+        rc = self._L.oa_point_to_plane(self._h, capi.dptr(A), capi.dptr(B), capi.dptr(N), A.shape[1], A.shape[1], capi.dptr(M))
         if rc == capi.OA_E_TOO_FEW_PAIRS:
             raise ValueError(REF_VALUEERROR)
         self._chk(rc)

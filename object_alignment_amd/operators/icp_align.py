@@ -37,6 +37,10 @@ class IcpSettings:
     # not a preference of the reference: which GPUs the loop may use.  None = one GPU (or what the OA_DEVICES environment
     # variable lists); "all" / [0, 1, ...] = the source cloud is sharded over those GPUs inside the library
     devices: object = None
+    # not a preference of the reference either (its citation.txt names both papers, its loop implements the first): what a
+    # step minimises -- "point": the distance to the correspondence (Besl-McKay, the reference's loop); "plane": the distance
+    # to the tangent plane at the correspondence (Chen-Medioni; rigid only, one GPU), which lets a surface slide along itself
+    metric: str = "point"
 
 
 _prefs = IcpSettings()
@@ -45,6 +49,22 @@ _prefs = IcpSettings()
 def get_addon_preferences() -> IcpSettings:
     """Stand-in for functions/common/blender.py:48-55; returns the process-wide settings object."""
     return _prefs
+
+
+def metric_of(settings) -> str:
+    """IcpSettings.metric, or the `icp_metric` enum of the registered add-on preferences; "point" when neither is there."""
+    return str(getattr(settings, "metric", None) or getattr(settings, "icp_metric", None) or "point")
+
+
+def apply_metric(engine, settings) -> None:
+    """Hand the settings' metric to the engine -- every time: the engine is shared and remembers the last one.  An engine
+    without set_metric (a stand-in that only knows the reference's loop) is a point-metric engine."""
+    metric = metric_of(settings)
+    setter = getattr(engine, "set_metric", None)
+    if setter is not None:
+        setter(metric)
+    elif metric != "point":
+        raise RuntimeError("this engine has no %r metric" % metric)
 
 
 def build_vlist(align_obj):
@@ -103,9 +123,10 @@ class IcpAlign:
         self.engine = engine if engine is not None else default_engine(devices=getattr(self.settings, "devices", None))
 
     def run(self, source_xyz, target_xyz, mx_align, mx_base, vlist=None, early_exit=True,
-            target_tris=None) -> RunResult:
+            target_tris=None, target_normals=None) -> RunResult:
         """target_tris: (n, 3) triangles of the base mesh -> closest point on the surface (the reference's BVH
-        semantics); None -> nearest target vertex (point-cloud targets, BASELINE's configurations)."""
+        semantics); None -> nearest target vertex (point-cloud targets, BASELINE's configurations).
+        target_normals: one normal per target vertex -- what settings.metric == "plane" needs of a point-cloud target."""
         s = self.settings
         thresh = s.min_start                                   # :83
         factor = round(1 / s.sample_fraction)                  # :89  (ZeroDivisionError at 0, as the reference)
@@ -117,6 +138,9 @@ class IcpAlign:
             eng.set_target_mesh(target_xyz, target_tris)
         else:
             eng.set_target(target_xyz)
+            if target_normals is not None:
+                eng.set_target_normals(target_normals)
+        apply_metric(eng, s)
         eng.set_source(source_xyz, vlist=vlist, stride=factor)
         eng.set_matrices(mx_align, mx_base)
         return eng.run(iters=s.icp_iterations, thresh=thresh, target_d=s.target_d, use_target=s.use_target,
