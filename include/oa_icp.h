@@ -214,6 +214,40 @@ int oa_set_metric(oa_ctx *ctx, int metric);
 /* vertex-mode targets: per-vertex normals (base-local, nt x 3 float32, host) for the plane metric, without switching the
  * normal-angle test on; a new target upload forgets them.  Normals given through oa_set_normals serve as well. */
 int oa_set_target_normals(oa_ctx *ctx, const float *tgt_normals, int64_t nt);
+/* EXTENSION (no counterpart in the reference, whose only protection against bad correspondences is the hard cut thresh): pair
+ * weights.  Every pair of a loop step (oa_run, oa_iterate, the split-phase calls) carries the weight
+ *   w = w_vertex * psi(r),   c = scale (world units, like thresh):
+ *   OA_LOSS_NONE    psi = 1 (default)
+ *   OA_LOSS_HUBER   psi = 1 for r <= c, else c / r
+ *   OA_LOSS_TUKEY   psi = (1 - (r/c)^2)^2 for r < c, else 0
+ *   OA_LOSS_CAUCHY  psi = 1 / (1 + (r/c)^2)
+ * (fixed scale, an iteratively re-weighted step; all three continuous in r).  The residual r is
+ *   OA_METRIC_POINT  the world-space pair distance the thresh test measures;
+ *   OA_METRIC_PLANE  s |n . (a - b)|, the distance to the tangent plane, s = cbrt(|det(mx_align[:3,:3])|) carrying the
+ *                    align-local residual to world units (taken when the loop starts; the plane step is rigid).
+ * Point metric: the sums of a, b, b a^T, |a|^2, |b|^2 are weighted and slot 20 of the OA_NSUMS row holds sum w, from which the
+ * solve takes its mass (centroids, covariance, scale); plane metric: sum J J^T and sum J r are weighted.  K (oa_report.last_K,
+ * stats[0]) stays the COUNT of pairs -- a pair of weight 0 is counted -- and mean_dist / std_dist stay unweighted.  A step fails
+ * with OA_E_TOO_FEW_PAIRS when K < 3, as ever, and when sum w is not > 0.
+ * With OA_LOSS_NONE and no vertex weights nothing changes: the same kernels, the same bits, slot 20 = 0.  Otherwise the loop
+ * runs search -> accumulate (no accumulating search epilogue) and takes shards of up to 8 388 608 points (OA_E_CAPACITY).
+ * The weighted point metric runs on every kind of context -- single-device, oa_create_multi (mailbox and RCCL), oa_run_begin /
+ * oa_iter_partial / oa_iter_finish: the row is still OA_NSUMS doubles; the weighted plane metric on single-device contexts, as
+ * the plane metric itself.  oa_make_pairs, oa_nn_search, oa_kabsch*, oa_point_to_plane do not look at the loss or the weights
+ * (oa_kabsch_from_sums ignores slot 20).
+ * oa_set_robust: OA_E_BAD_ARG for an unknown loss, and for a loss other than NONE with a scale that is not finite and > 0.  The
+ * setting survives uploads and oa_set_matrices; changing it ends a running oa_iterate sequence, as oa_set_metric does. */
+#define OA_LOSS_NONE   0
+#define OA_LOSS_HUBER  1
+#define OA_LOSS_TUKEY  2
+#define OA_LOSS_CAUCHY 3
+int oa_set_robust(oa_ctx *ctx, int loss, double scale);
+/* EXTENSION: one weight per source vertex (host, float32, n_verts as uploaded with oa_set_source; finite and >= 0), gathered
+ * into the selection's order -- "trust this region less", where vlist can only say yes or no.  w == NULL switches the weights
+ * off (every w_vertex = 1); a new source upload forgets them.  OA_E_STATE before oa_set_source; OA_E_BAD_ARG for a count other
+ * than the uploaded n_verts and for a negative or non-finite weight (the weights in force stay).  Multi-device contexts: every
+ * child gathers its own shard. */
+int oa_set_source_weights(oa_ctx *ctx, const float *w, int64_t n_verts);
 /* matrix_world of the align and base objects (functions/general.py:262-263) */
 int oa_set_matrices(oa_ctx *ctx, const float mx_align[16], const float mx_base[16]);
 int oa_get_matrix_world(oa_ctx *ctx, float mx_align[16]);
@@ -266,6 +300,8 @@ int oa_reset_seeds(oa_ctx *ctx);
                                        * queue (long launches: as many as the chip holds); 0 = one workgroup per item, in launch order */
 #define OA_STAT_METRIC          28   /* OA_METRIC_POINT / OA_METRIC_PLANE */
 #define OA_STAT_PLANE_RANK      29   /* eigenvalues the last plane solve kept (6 = fully determined); loop or oa_point_to_plane */
+#define OA_STAT_ROBUST_LOSS     30   /* OA_LOSS_* */
+#define OA_STAT_WEIGHT_SUM      31   /* sum w of the last step (loop or iterate); K when weighting is off */
 #define OA_STAT_ENQUEUED_CHILD  1000   /* + i: the same count for child i alone */
 int oa_get_stat(oa_ctx *ctx, int what, double *value);
 /* why the exchange is what it is (AUTO's reason for not taking RCCL, librccl's error, "RCCL was aborted: ..."), or "" */

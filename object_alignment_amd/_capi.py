@@ -29,6 +29,10 @@ OA_EXCHANGE_RCCL = 1
 OA_NSUMS = 24
 OA_METRIC_POINT = 0
 OA_METRIC_PLANE = 1
+OA_LOSS_NONE = 0
+OA_LOSS_HUBER = 1
+OA_LOSS_TUKEY = 2
+OA_LOSS_CAUCHY = 3
 
 # every symbol include/oa_icp.h declares (tests check that the library exports all of them)
 SYMBOLS = [
@@ -41,6 +45,7 @@ SYMBOLS = [
     "oa_iterate", "oa_run", "oa_get_history", "oa_run_begin", "oa_iter_partial", "oa_iter_finish", "oa_run_end",
     "oa_get_search_ms", "oa_measure_valu_ceiling", "oa_exchange_note",
     "oa_set_metric", "oa_set_target_normals", "oa_point_to_plane",
+    "oa_set_robust", "oa_set_source_weights",
 ]
 
 
@@ -138,6 +143,8 @@ def load(experiments: bool = False):
     L.oa_set_metric.argtypes = [vp, C.c_int]
     L.oa_set_target_normals.argtypes = [vp, fp, C.c_int64]
     L.oa_point_to_plane.argtypes = [vp, dp, dp, dp, C.c_int64, C.c_int64, dp]
+    L.oa_set_robust.argtypes = [vp, C.c_int, C.c_double]
+    L.oa_set_source_weights.argtypes = [vp, fp, C.c_int64]
     _libs[experiments] = L
     return L
 

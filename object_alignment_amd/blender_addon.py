@@ -63,11 +63,18 @@ if bpy is not None:
         icp_metric: EnumProperty(items=[("point", "POINT_TO_POINT", "Distance to the corresponding point (Besl-McKay)"),
                                         ("plane", "POINT_TO_PLANE", "Distance to the tangent plane at the corresponding point (Chen-Medioni); rigid only")],
                                  name="ICP Metric", description="What an ICP step minimises", default="point")
+        icp_robust_loss: EnumProperty(items=[("none", "NONE", "Every pair inside the starting distance weighs one"),
+                                             ("huber", "HUBER", "Weight 1 up to the scale, then scale / residual"),
+                                             ("tukey", "TUKEY", "Weight (1 - (residual / scale)^2)^2, zero beyond the scale"),
+                                             ("cauchy", "CAUCHY", "Weight 1 / (1 + (residual / scale)^2)")],
+                                      name="ICP Robust Loss", description="How a pair's weight falls with its residual", default="none")
+        icp_robust_scale: FloatProperty(
+            name="ICP Robust Scale", description="Residual (world units) at which the robust loss takes hold", default=0.0, min=0, max=20)
 
         def draw(self, context):
             col = self.layout.column()
             for name in ("icp_iterations", "redraw_frequency", "sample_fraction", "min_start", "target_d", "use_target",
-                         "take_m_with", "align_meth", "icp_metric"):
+                         "take_m_with", "align_meth", "icp_metric", "icp_robust_loss", "icp_robust_scale"):
                 col.prop(self, name)
 
     class VIEW3D_PT_object_alignment(Panel):

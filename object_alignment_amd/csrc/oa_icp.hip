@@ -437,6 +437,11 @@ struct oa_ctx {
     bool normals_on = false;
     int last_plane_rank = 0;         // OA_STAT_PLANE_RANK: eigenvalues the last plane solve kept (loop or oa_point_to_plane)
     int metric = OA_METRIC_POINT;    // oa_set_metric: what the loop minimises (survives uploads and oa_set_matrices)
+    // weighted steps: a pair's weight is w_vertex * psi(residual).  Off (every weight 1, the unweighted kernels) unless set
+    int loss = OA_LOSS_NONE;         // oa_set_robust (survives uploads and oa_set_matrices)
+    double robust_c = 0.0;           // ... its scale, world units
+    float *d_w = nullptr;            // oa_set_source_weights: one weight per slot (gathered through d_sel), or nullptr; a new source forgets it
+    double last_weight_sum = 0.0;    // OA_STAT_WEIGHT_SUM
     double pivot[3] = { 0, 0, 0 };
     // launch geometry for k_nn_search
     int n_splits = 1, acc_blocks = 1;
@@ -861,6 +866,9 @@ struct SearchChoice {
     bool accept_front = false;      // k_tri_accept (seed + neighbour lists, oa_tri_ring.hpp), once the lists are built
     SearchPlan plan = PLAN_PLAIN;   // a loop with fused_acc only
 };
+// a loss or per-vertex weights are set: the loop's pairs carry weights (weighted kernels, the PLAIN plan)
+inline bool weighted(const oa_ctx *c) { return c->loss != OA_LOSS_NONE || c->d_w != nullptr; }
+
 SearchChoice choose_search(const oa_ctx *c)
 {
     SearchChoice s;
@@ -875,8 +883,9 @@ SearchChoice choose_search(const oa_ctx *c)
         s.settle_front = c->surface && c->tri_fine_ok && c->seeded && !s.dual;
         s.accept_front = c->surface && c->tri_split && c->seeded && !s.dual;
     }
-    // (the plane metric has no accumulating search epilogue: search, then k_pair_accumulate_plane -- as with fused_acc off)
-    if (!c->fused_acc || !c->loop_active || c->ns <= 0 || c->metric == OA_METRIC_PLANE) return s;
+    // (the plane metric has no accumulating search epilogue: search, then k_pair_accumulate_plane -- as with fused_acc off;
+    //  nor does a weighted step: no search epilogue knows about weights)
+    if (!c->fused_acc || !c->loop_active || c->ns <= 0 || c->metric == OA_METRIC_PLANE || weighted(c)) return s;
     // (the accumulating tree search needs twice the registers of the plain one: worth it while the shard is small enough
     //  that occupancy does not matter -- 12k queries against 1M vertices: 58 us fused, 47 us search + accumulate)
     if (s.kind == SEARCH_TREE) s.plan = c->ns <= c->tree_acc_max ? PLAN_TREE : PLAN_PLAIN;
@@ -1088,8 +1097,8 @@ int launch_nn(oa_ctx *c, const SearchChoice &s, bool acc)
     return rc;
 }
 
-// the plane metric's accumulation: one thread per source slot, workgroups by the shard size alone (every search mode leaves
-// the same rows); begin_loop refuses shards beyond PLANE_MAX_BLOCKS rows
+// the plane metric's accumulation, and the weighted one of the point metric: one thread per source slot, workgroups by the
+// shard size alone (every search mode leaves the same rows); begin_loop refuses shards beyond PLANE_MAX_BLOCKS rows
 inline int plane_threads(const oa_ctx *c) { return c->ns >= 262144 ? oa::PLANE_THREADS : 256; }
 inline int plane_blocks(const oa_ctx *c) { const int t = plane_threads(c); return std::max(1, (c->ns + t - 1) / t); }
 
@@ -1105,9 +1114,16 @@ int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
                            c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->d_partials, po,
                            (unsigned long long *)nullptr);
     } else if (c->metric == OA_METRIC_PLANE) {
-        hipLaunchKernelGGL(oa::k_pair_accumulate_plane, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
+        auto *kern = weighted(c) ? oa::k_pair_accumulate_plane<true> : oa::k_pair_accumulate_plane<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
                            (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
                            c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n,
+                           (const float *)c->d_w, c->d_partials, c->loop_active ? &c->d_state->t_acc_start : (unsigned long long *)nullptr);
+    } else if (weighted(c)) {
+        static_assert(oa::WEIGHTED_THREADS == oa::PLANE_THREADS, "plane_threads / plane_blocks size both launches");
+        hipLaunchKernelGGL(oa::k_pair_accumulate_weighted, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
+                           (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
+                           c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, (const float *)c->d_w,
                            c->d_partials, c->loop_active ? &c->d_state->t_acc_start : (unsigned long long *)nullptr);
     } else if (canon_blocks(c) > 0) {
         hipLaunchKernelGGL(oa::k_pair_accumulate_canon, dim3((unsigned)canon_blocks(c)), dim3((unsigned)canon_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
@@ -1127,7 +1143,7 @@ int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
 // rows the (non-emitting) accumulation of this context leaves for the reduce launch when it is its own kernel
 inline oa::RowSel plain_rows(const oa_ctx *c)
 {
-    if (c->metric == OA_METRIC_PLANE) return oa::RowSel{ plane_blocks(c), 0, 0 };
+    if (c->metric == OA_METRIC_PLANE || weighted(c)) return oa::RowSel{ plane_blocks(c), 0, 0 };
     const int cb = canon_blocks(c);
     return oa::RowSel{ cb > 0 ? cb : c->acc_blocks, 0, 0 };
 }
@@ -1263,6 +1279,18 @@ void init_loop_state(oa_ctx *c, const oa_settings *st, int iters, bool cutoff = 
     s.d_pivot = c->d_pivot0;
     s.jac_valid = 0; s.plane_rank = 0;                                    // every loop starts its Jacobi from the identity
     for (int k = 0; k < 9; ++k) s.jac_v[k] = 0.0;
+    s.weighted = weighted(c) ? 1 : 0;
+    s.loss = c->loss;
+    s.robust_c = c->robust_c;
+    {   // the plane residual is in align-local units, the loss's scale in world units: cbrt(|det|) of the float32 matrix, in fp64
+        // (the plane step is rigid: the determinant does not change during a loop)
+        const float *m = s.mx1;
+        const double det = (double)m[0] * ((double)m[5] * (double)m[10] - (double)m[6] * (double)m[9])
+                         - (double)m[1] * ((double)m[4] * (double)m[10] - (double)m[6] * (double)m[8])
+                         + (double)m[2] * ((double)m[4] * (double)m[9] - (double)m[5] * (double)m[8]);
+        s.res_scale = cbrt(fabs(det));
+    }
+    s.weight_sum = 0.0;
 }
 
 // oa_iterate opens a loop without an end; its history is a ring of the last ITERATE_RING iterations
@@ -1280,7 +1308,8 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
             return fail(OA_E_STATE, "the plane metric needs target normals: call oa_set_target_normals (or oa_set_normals) after oa_set_target, or upload a mesh with oa_set_target_mesh");
         if ((long long)c->ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
             return fail(OA_E_CAPACITY, "the plane metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->ns);
-    }
+    } else if (weighted(c) && (long long)c->ns > (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS)
+        return fail(OA_E_CAPACITY, "a weighted loop takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS, c->ns);
     if ((rc = use_device(c))) return rc;
     if ((rc = ensure_common(c))) return rc;
     if ((rc = ensure_history(c, iters == ITERATE_OPEN ? ITERATE_RING : iters))) return rc;   // oa_iterate: a small ring
@@ -1348,6 +1377,7 @@ int fetch_state(oa_ctx *c)
     HIPCHK(hipStreamSynchronize(c->stream));
     c->h_state = *c->h_state_pin;
     if (c->metric == OA_METRIC_PLANE && c->h_state.n > 0) c->last_plane_rank = c->h_state.plane_rank;
+    if (c->h_state.n > 0) c->last_weight_sum = c->h_state.weight_sum;
     return OA_OK;
 }
 
@@ -2251,7 +2281,7 @@ OA_EXPORT void oa_destroy(oa_ctx *c)
     OA_FREE(d_valid); OA_FREE(d_b); OA_FREE(d_dist); OA_FREE(d_counts); OA_FREE(d_offsets); OA_FREE(d_A); OA_FREE(d_B);
     OA_FREE(d_bvh_box); OA_FREE(d_bvh_prims); OA_FREE(d_tbvh_box); OA_FREE(d_tbvh_prims);
     OA_FREE(d_tri9); OA_FREE(d_tcell_start); OA_FREE(d_tcell_rec); OA_FREE(d_tri_ring); OA_FREE(d_tfine_table); OA_FREE(d_tfine_rec);
-    OA_FREE(d_sel); OA_FREE(d_src_n); OA_FREE(d_tgt_n); OA_FREE(d_src4o); OA_FREE(d_perm);
+    OA_FREE(d_sel); OA_FREE(d_src_n); OA_FREE(d_tgt_n); OA_FREE(d_w); OA_FREE(d_src4o); OA_FREE(d_perm);
 #undef OA_FREE
     if (c->h_hist_map) (void)hipHostFree(c->h_hist_map);
     if (c->h_state_pin) (void)hipHostFree(c->h_state_pin);
@@ -3228,7 +3258,7 @@ int source_reset(oa_ctx *c, long long count, long long begin, long long n_verts)
 {
     HIPCHK(hipStreamSynchronize(c->stream));
     c->loop_active = false;                                         // an open oa_iterate sequence ends with the old source
-    dev_free(c->d_src4); dev_free(c->d_keys); dev_free(c->d_prev); dev_free(c->d_win); dev_free(c->d_wsafe); dev_free(c->d_sel); dev_free(c->d_src_n);
+    dev_free(c->d_src4); dev_free(c->d_keys); dev_free(c->d_prev); dev_free(c->d_win); dev_free(c->d_wsafe); dev_free(c->d_sel); dev_free(c->d_src_n); dev_free(c->d_w);
     dev_free(c->d_src4o); dev_free(c->d_perm); dev_free(c->d_members); dev_free(c->d_pos);
     c->h_members.clear();
     c->shard_begin = begin;
@@ -3524,6 +3554,62 @@ OA_EXPORT int oa_set_metric(oa_ctx *c, int metric)
     return OA_OK;
 }
 
+OA_EXPORT int oa_set_robust(oa_ctx *c, int loss, double scale)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    if (loss != OA_LOSS_NONE && loss != OA_LOSS_HUBER && loss != OA_LOSS_TUKEY && loss != OA_LOSS_CAUCHY)
+        return fail(OA_E_BAD_ARG, "oa_set_robust: loss %d (use OA_LOSS_NONE / OA_LOSS_HUBER / OA_LOSS_TUKEY / OA_LOSS_CAUCHY)", loss);
+    if (loss != OA_LOSS_NONE && !(scale > 0.0 && scale < INFINITY))
+        return fail(OA_E_BAD_ARG, "oa_set_robust: the scale must be finite and > 0 (world units, like thresh)");
+    if (loss == OA_LOSS_NONE) scale = 0.0;
+    if (loss == c->loss && scale == c->robust_c) return OA_OK;
+    // a changed loss ends the running sequence, as a changed metric does
+    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
+    else if (c->loop_active) {
+        int rc = use_device(c);
+        if (rc) return rc;
+        if ((rc = fetch_state(c))) return rc;
+        c->loop_active = false;
+    }
+    c->loss = loss;
+    c->robust_c = scale;
+    OA_ROUTE_ALL(c, oa_set_robust(sub, loss, scale));
+    return OA_OK;
+}
+
+OA_EXPORT int oa_set_source_weights(oa_ctx *c, const float *w, int64_t n_verts)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    if (!c->subs.empty() && c->loop_active) multi_abort(c);
+    OA_ROUTE_ALL_PAR(c, oa_set_source_weights(sub, w, n_verts));      // every child gathers its own shard
+    if (c->loop_active) {
+        int rc = use_device(c);
+        if (rc) return rc;
+        if ((rc = fetch_state(c))) return rc;
+        c->loop_active = false;
+    }
+    if (!w) {                                                        // switched off
+        if (c->d_w) { int rc = use_device(c); if (rc) return rc; HIPCHK(hipStreamSynchronize(c->stream)); dev_free(c->d_w); }
+        return OA_OK;
+    }
+    if (!c->d_src4 || !c->d_sel) return fail(OA_E_STATE, "oa_set_source_weights: call oa_set_source first");
+    if (n_verts != c->src_n_verts) return fail(OA_E_BAD_ARG, "oa_set_source_weights: %lld weights for %lld vertices", (long long)n_verts, c->src_n_verts);
+    for (int64_t i = 0; i < n_verts; ++i)
+        if (!(w[i] >= 0.f && w[i] < INFINITY)) return fail(OA_E_BAD_ARG, "oa_set_source_weights: weight %lld is negative or not finite", (long long)i);
+    int rc = use_device(c);
+    if (rc) return rc;
+    DevTmp<float> tmp;
+    HIPCHK(tmp.alloc((size_t)std::max<int64_t>(1, n_verts)));
+    HIPCHK(hipMemcpyAsync(tmp, w, sizeof(float) * (size_t)n_verts, hipMemcpyHostToDevice, c->stream));
+    if (!c->d_w) HIPCHK(dev_malloc(&c->d_w, sizeof(float) * (size_t)std::max(1, c->ns)));
+    if (c->ns > 0)
+        hipLaunchKernelGGL(oa::k_gather_rows1, dim3((c->ns + 255) / 256), dim3(256), 0, c->stream, (const float *)tmp.p,
+                           (const int *)c->d_sel, c->ns, c->d_w);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
 OA_EXPORT int oa_set_target_normals(oa_ctx *c, const float *tgt_normals, int64_t nt)
 {
     if (!c || !tgt_normals) return fail(OA_E_BAD_ARG, "oa_set_target_normals: null argument");
@@ -3675,6 +3761,8 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
     case OA_STAT_TRI_RING: *value = (c->tri_ring && c->tri_ring_ok) ? 1.0 : 0.0; return OA_OK;
     case OA_STAT_METRIC: *value = (double)c->metric; return OA_OK;
     case OA_STAT_PLANE_RANK: *value = (double)c->last_plane_rank; return OA_OK;
+    case OA_STAT_ROBUST_LOSS: *value = (double)c->loss; return OA_OK;
+    case OA_STAT_WEIGHT_SUM: *value = c->last_weight_sum; return OA_OK;
     default: return fail(OA_E_BAD_ARG, "oa_get_stat: unknown key %d", what);
     }
 }

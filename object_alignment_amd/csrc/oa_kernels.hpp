@@ -27,15 +27,30 @@ namespace oa {
 constexpr int NSUMS = 24;
 // layout of the per-iteration sums (all relative to `pivot`, a' = a - pivot, b' = b - pivot):
 //   [0..2] sum a'   [3..5] sum b'   [6..14] sum b'_i a'_j (row i, col j)   [15] sum |a'|^2   [16] sum |b'|^2
-//   [17] K          [18] sum (d - d_pivot)      [19] sum (d - d_pivot)^2        [20..23] reserved (0)
-constexpr int S_A = 0, S_B = 3, S_H = 6, S_AA = 15, S_BB = 16, S_K = 17, S_D = 18, S_DD = 19;
+//   [17] K          [18] sum (d - d_pivot)      [19] sum (d - d_pivot)^2        [20] sum w (0 unless weighted)   [21..23] reserved (0)
+// Weighted steps (oa_set_robust / oa_set_source_weights, DevState::weighted): every pair carries w = w_vertex * psi(r); sums
+// [0..16] are then weighted, [20] is their mass, and [17..19] stay what they are -- the COUNT of pairs and the plain distances.
+constexpr int S_A = 0, S_B = 3, S_H = 6, S_AA = 15, S_BB = 16, S_K = 17, S_D = 18, S_DD = 19, S_W = 20;
 // the point-to-plane metric (Chen & Medioni; oa_set_metric) sums a wider row.  Per pair, relative to the same pivot: n = the
 // correspondence's unit normal in align-local space, r = n . (a' - b'), J = [a' x n, n] (the row of the linearised step
 // x = (omega, t)):
 //   [0..20] sum J J^T, upper triangle by rows ((0,0) (0,1) .. (0,5) (1,1) .. (5,5))   [21..26] sum J r   [27] K
-//   [28] sum (d - d_pivot)   [29] sum (d - d_pivot)^2   [30] sum r^2   [31] spare (0)
+//   [28] sum (d - d_pivot)   [29] sum (d - d_pivot)^2   [30] sum r^2   [31] sum w (0 unless weighted)
+// Weighted steps: [0..26] are sums of w J J^T and w J r; [27..30] stay unweighted.
 constexpr int NSUMS_PLANE = 32;
-constexpr int P_JJ = 0, P_JR = 21, P_K = 27, P_D = 28, P_DD = 29, P_RR = 30;
+constexpr int P_JJ = 0, P_JR = 21, P_K = 27, P_D = 28, P_DD = 29, P_RR = 30, P_W = 31;
+
+// the robust losses (oa_set_robust; OA_LOSS_* of oa_icp.h) as weights of an iteratively re-weighted step: psi(r), r >= 0 the
+// pair's residual in world units, c the loss's scale.  All three are continuous in r.
+constexpr int LOSS_NONE = 0, LOSS_HUBER = 1, LOSS_TUKEY = 2, LOSS_CAUCHY = 3;
+__host__ __device__ inline double robust_psi(int loss, double r, double c)
+{
+    if (loss == LOSS_NONE) return 1.0;
+    if (loss == LOSS_HUBER) return r <= c ? 1.0 : c / r;
+    const double q = r / c, q2 = q * q;
+    if (loss == LOSS_TUKEY) { const double u = 1.0 - q2; return r < c ? u * u : 0.0; }
+    return 1.0 / (1.0 + q2);                                        // LOSS_CAUCHY
+}
 
 constexpr unsigned long long KEY_EMPTY = ~0ull;
 constexpr uint32_t IDX_NONE = 0xFFFFFFFFu;
@@ -98,6 +113,12 @@ struct DevState {
     double jac_v[9];
     int32_t jac_valid;
     int32_t plane_rank;       // plane metric: eigenvalues the last solve kept (OA_STAT_PLANE_RANK); 0 otherwise
+    // weighted steps (oa_set_robust / oa_set_source_weights): off (0) unless a loss or vertex weights are set
+    int32_t weighted;         // 1: the pairs carry weights -- the solve takes its mass from S_W / P_W instead of the pair count
+    int32_t loss;             // LOSS_*
+    double robust_c;          // the loss's scale, world units
+    double res_scale;         // plane metric: cbrt(|det mx1[:3,:3]|), align-local residual -> world units (set when the loop starts)
+    double weight_sum;        // sum w of the last step; K when weighting is off (OA_STAT_WEIGHT_SUM)
 };
 
 // Squared local search radius for the query p (rounded up to float).  Derivation: the pair test measures
@@ -378,11 +399,14 @@ __host__ __device__ inline void rotation_from_covariance_horn(const double H[9],
     R[6] = x * z - y * w;       R[7] = y * z + x * w;       R[8] = 1.0 - x * x - y * y;
 }
 
+// weighted: the sums [0..16] carry the pairs' weights and S_W their mass -- centroids, covariance and the scale branch are the
+// weighted ones; the rule K >= 3 still counts pairs, and a mass that is not > 0 fails like it.
 __host__ __device__ inline bool solve_from_sums(const double *s, const double pivot[3], bool with_scale, double M[16],
-                                                double *v_io = nullptr, bool v_valid = false, bool horn = false)
+                                                double *v_io = nullptr, bool v_valid = false, bool horn = false, bool weighted = false)
 {
-    const double K = s[S_K];
-    if (!(K >= 3.0)) return false;
+    if (!(s[S_K] >= 3.0)) return false;
+    const double K = weighted ? s[S_W] : s[S_K];
+    if (!(K > 0.0)) return false;
     double ca[3], cb[3];
     const double inv_K = 1.0 / K;
     for (int i = 0; i < 3; ++i) { ca[i] = s[S_A + i] * inv_K; cb[i] = s[S_B + i] * inv_K; }     // centroids (:160,:164)
@@ -507,10 +531,11 @@ __host__ __device__ inline void plane_step_matrix(const double x[6], const doubl
 // device); [k0, k1): see sym6_jacobi.  Returns false when K < 3 (OA_E_TOO_FEW_PAIRS, as the point metric); rank = the
 // eigenvalues kept (6 = the pairs determine the whole step).  Called by all lanes of one wave / by one host thread.
 __host__ __device__ inline bool plane_solve_from_sums(const double *s, const double pivot[3], double *A, double *V, int k0, int k1,
-                                                      double M[16], int &rank)
+                                                      double M[16], int &rank, bool weighted = false)
 {
     rank = 0;
     if (!(s[P_K] >= 3.0)) return false;
+    if (weighted && !(s[P_W] > 0.0)) return false;                          // (weighted rows: a mass that is not > 0 fails like K < 3)
     for (int k = k0; k < k1; ++k)
         for (int j = 0; j < 6; ++j) A[6 * k + j] = s[P_JJ + (k <= j ? sym6_index(k, j) : sym6_index(j, k))];
     OA_WAVE_LDS_FENCE();
@@ -645,6 +670,13 @@ __global__ void k_gather_rows3(const float *__restrict__ rows, const int *__rest
     if (i >= n) return;
     const long long v = sel[i];
     out[3ll * i] = rows[3 * v]; out[3ll * i + 1] = rows[3 * v + 1]; out[3ll * i + 2] = rows[3 * v + 2];
+}
+// the same for one value per vertex (oa_set_source_weights)
+__global__ void k_gather_rows1(const float *__restrict__ vals, const int *__restrict__ sel, int n, float *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = vals[(long long)sel[i]];
 }
 #endif  // !OA_FAMILY_TU
 
@@ -2261,6 +2293,113 @@ __global__ __launch_bounds__(CANON_THREADS) void k_pair_accumulate_canon(const D
 }
 #endif  // !OA_FAMILY_TU
 
+// ---- weighted steps of the point metric (oa_set_robust / oa_set_source_weights) -----------------------------------------
+// the wave's total of ONE value in every lane: the halving steps of wave_reduce_scatter with both operands the same register
+// (each half receives the other half's copy), then the butterfly inside a row of 16 lanes.  Fixed pattern.
+__device__ __forceinline__ double wave_sum_all(double t)
+{
+    t = halve_add32(t, t);
+    t = halve_add16(t, t);
+    t += row_xor<8>(t); t += row_xor<4>(t); t += row_xor<2>(t); t += row_xor<1>(t);
+    return t;
+}
+
+// block_store_pair with a weight per pair: sums 0 .. 16 carry w, K and the distance sums do not, S_W = sum w.  The same two
+// slices of 12 + 8 through the same reduce-scatter, and one more value.  red: __shared__ double[blockDim.x / 64][NSUMS].
+__device__ __forceinline__ void block_store_pair_weighted(bool valid, double w, double a0, double a1, double a2, double b0, double b1,
+                                                          double b2, double dd, double (*red)[NSUMS], double *__restrict__ row)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (!valid) { a0 = a1 = a2 = b0 = b1 = b2 = dd = w = 0.0; }
+    const double wb0 = w * b0, wb1 = w * b1, wb2 = w * b2;
+    {
+        double h[12] = { w * a0, w * a1, w * a2, wb0, wb1, wb2, wb0 * a0, wb0 * a1, wb0 * a2, wb1 * a0, wb1 * a1, wb1 * a2 };   // sums 0 .. 11
+        wave_reduce_scatter<12>(h, lane, &red[wave][0]);
+    }
+    {
+        double h[8] = { wb2 * a0, wb2 * a1, wb2 * a2, w * ((a0 * a0 + a1 * a1) + a2 * a2), w * ((b0 * b0 + b1 * b1) + b2 * b2),
+                        valid ? 1.0 : 0.0, dd, dd * dd };                                                           // sums 12 .. 19
+        wave_reduce_scatter<8>(h, lane, &red[wave][12]);
+    }
+    const double wsum = wave_sum_all(w);
+    if (lane < 4) red[wave][S_W + lane] = lane == 0 ? wsum : 0.0;                                                   // sum 20, reserved
+    __syncthreads();
+    if (threadIdx.x < NSUMS) {
+        double v = red[0][threadIdx.x];
+        for (int k = 1; k < (int)(blockDim.x >> 6); ++k) v += red[k][threadIdx.x];
+        row[threadIdx.x] = v;
+    }
+}
+
+// k_pair_accumulate_canon with a weight per pair: the same reads, the same resetting of keys / prev / win, the same pair test
+// (pair_eval), ONE thread per source slot, the same fixed-order reduction (no float atomics).  w = w_vertex * psi(dist):
+// dist = the world-space pair distance of pair_eval; w_slot = one weight per slot (nullptr: all 1); the loss and its scale are
+// launch-uniform (DevState).  Its workgroups depend on the shard size alone, so every search mode leaves the same rows.
+constexpr int WEIGHTED_THREADS = 512;
+#if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
+__global__ __launch_bounds__(WEIGHTED_THREADS) void k_pair_accumulate_weighted(const DevState *__restrict__ st, const float4 *__restrict__ src4,
+                                                               int ns, const float *__restrict__ tgt_xyz,
+                                                               unsigned long long *__restrict__ keys, int *__restrict__ prev,
+                                                               float4 *__restrict__ win, const float4 *__restrict__ tri9,
+                                                               NormalTest nrm, const float *__restrict__ w_slot,
+                                                               double *__restrict__ partials,
+                                                               unsigned long long *__restrict__ t_acc_start)
+{
+    __shared__ double red[WEIGHTED_THREADS / 64][NSUMS];
+    if (t_acc_start && blockIdx.x == 0 && threadIdx.x == 0) *t_acc_start = wall_clock64();   // ~ the end of the search
+    if (st->halt) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool valid = false;
+    float bx = 0.f, by = 0.f, bz = 0.f;
+    double dist = 0.0, w = 0.0;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < ns) {
+        const unsigned long long key = keys[i];
+        keys[i] = KEY_EMPTY;                                       // ready for the next iteration's atomicMin
+        const uint32_t idx = (uint32_t)key;
+        if (prev) prev[i] = (idx == IDX_NONE) ? -1 : (int)idx;
+        p = src4[i];
+        float4 wrec = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+        if (win) wrec = win[i];
+        if (idx != IDX_NONE) {
+            float cx, cy, cz;
+            co_find(st, p.x, p.y, p.z, cx, cy, cz);           // co_find                   (general.py:287)
+            float qx, qy, qz;
+            float tn[3] = { 0.f, 0.f, 0.f };
+            if (tri9) {
+                float ta[3], tb[3], tc[3], rr[3];
+                const float cf[3] = { cx, cy, cz };
+                load_tri(tri9, idx, ta, tb, tc);
+                closest_on_tri(cf, ta, tb, tc, rr);
+                qx = rr[0]; qy = rr[1]; qz = rr[2];
+                if (nrm.src_n) {
+                    const float e1[3] = { ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2] };
+                    const float e2[3] = { tb[0] - tc[0], tb[1] - tc[1], tb[2] - tc[2] };
+                    tn[0] = e1[1] * e2[2] - e1[2] * e2[1];
+                    tn[1] = e1[2] * e2[0] - e1[0] * e2[2];
+                    tn[2] = e1[0] * e2[1] - e1[1] * e2[0];
+                }
+            } else {
+                if ((uint32_t)__float_as_int(wrec.w) == idx) { qx = wrec.x; qy = wrec.y; qz = wrec.z; }
+                else {
+                    qx = tgt_xyz[3ll * idx]; qy = tgt_xyz[3ll * idx + 1]; qz = tgt_xyz[3ll * idx + 2];
+                    if (win) win[i] = make_float4(qx, qy, qz, __int_as_float((int)idx));
+                }
+                if (nrm.src_n) { tn[0] = nrm.tgt_n[3ll * idx]; tn[1] = nrm.tgt_n[3ll * idx + 1]; tn[2] = nrm.tgt_n[3ll * idx + 2]; }
+            }
+            valid = pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, tn, st->thresh, bx, by, bz, dist);
+            if (valid) {
+                w = robust_psi(st->loss, dist, st->robust_c);
+                if (w_slot) w *= (double)w_slot[i];
+            }
+        }
+    }
+    const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
+    block_store_pair_weighted(valid, w, (double)p.x - pvx, (double)p.y - pvy, (double)p.z - pvz, (double)bx - pvx, (double)by - pvy,
+                              (double)bz - pvz, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS);
+}
+#endif  // !OA_FAMILY_TU
+
 // ---- the point-to-plane metric (oa_set_metric(OA_METRIC_PLANE)): the same pair test, the sums of the plane system ---------
 // The correspondence's normal in align-local space, unit length, fp64: base-local tn -> world with the inverse transpose of
 // mx2 (as normal_angle_ok carries it) -> align-local with mx1^T (the inverse transpose of imx1).  false: zero or non-finite
@@ -2317,17 +2456,42 @@ __device__ __forceinline__ void block_finish_plane(double (*red)[NSUMS_PLANE], d
 
 // block_store_pair for the plane row: ONE pair per lane, formed and reduced slice by slice (the same reduce-scatter), so the
 // epilogue never holds 32 sums and the butterfly's temporaries at once.  red: __shared__ double[blockDim.x / 64][NSUMS_PLANE].
+// WEIGHTED: the pair's w multiplies its J J^T and J r terms and is itself summed into P_W; K, the distance sums and sum r^2 stay
+// as they are.  The unweighted instance is the code it was.
+template <bool WEIGHTED = false>
 __device__ __forceinline__ void block_store_plane(bool valid, const double (&jj)[6], double r, double dd, double (*red)[NSUMS_PLANE],
-                                                  double *__restrict__ row)
+                                                  double *__restrict__ row, double w = 0.0)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double j[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) j[k] = valid ? jj[k] : 0.0;
     if (!valid) { r = 0.0; dd = 0.0; }
-    { double h[12]; plane_terms_0(j, h); wave_reduce_scatter<12>(h, lane, &red[wave][0]); }
-    { double h[12]; plane_terms_1(j, r, h); wave_reduce_scatter<12>(h, lane, &red[wave][12]); }
-    { double h[8]; plane_terms_2(j, r, valid ? 1.0 : 0.0, dd, h); wave_reduce_scatter<8>(h, lane, &red[wave][24]); }
+    if constexpr (WEIGHTED) { if (!valid) w = 0.0; }
+    {
+        double h[12];
+        plane_terms_0(j, h);
+        if constexpr (WEIGHTED) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) h[k] *= w;
+        }
+        wave_reduce_scatter<12>(h, lane, &red[wave][0]);
+    }
+    {
+        double h[12];
+        plane_terms_1(j, r, h);
+        if constexpr (WEIGHTED) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) h[k] *= w;
+        }
+        wave_reduce_scatter<12>(h, lane, &red[wave][12]);
+    }
+    {
+        double h[8];
+        plane_terms_2(j, r, valid ? 1.0 : 0.0, dd, h);
+        if constexpr (WEIGHTED) { h[0] *= w; h[1] *= w; h[2] *= w; h[7] = w; }
+        wave_reduce_scatter<8>(h, lane, &red[wave][24]);
+    }
     block_finish_plane(red, row);
 }
 
@@ -2335,15 +2499,19 @@ __device__ __forceinline__ void block_store_plane(bool valid, const double (&jj)
 // (pair_eval), then the plane row.  One thread per source slot; plane_tn: vertex mode, one base-local normal per target
 // vertex (surface mode: nullptr, the nearest triangle's geometric normal in the operand order of the normal-angle test).
 // Its workgroups depend on the shard size alone, so every search mode leaves the same rows.
+// WEIGHTED (oa_set_robust / oa_set_source_weights): w = w_vertex * psi(res_scale * |r|), r the plane residual the row is built
+// from -- the distance to the tangent plane in world units, NOT the pair distance, which would down-weight exactly the sliding
+// pairs this metric exists for; w_slot = one weight per slot (nullptr: all 1).  The unweighted instance never reads either.
 constexpr int PLANE_THREADS = 512;
 constexpr int PLANE_MAX_BLOCKS = 16384;
 #if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
+template <bool WEIGHTED>
 __global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_plane(const DevState *__restrict__ st, const float4 *__restrict__ src4,
                                                                int ns, const float *__restrict__ tgt_xyz,
                                                                unsigned long long *__restrict__ keys, int *__restrict__ prev,
                                                                float4 *__restrict__ win, const float4 *__restrict__ tri9,
                                                                NormalTest nrm, const float *__restrict__ plane_tn,
-                                                               double *__restrict__ partials,
+                                                               const float *__restrict__ w_slot, double *__restrict__ partials,
                                                                unsigned long long *__restrict__ t_acc_start)
 {
     __shared__ double red[PLANE_THREADS / 64][NSUMS_PLANE];
@@ -2393,6 +2561,14 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_plane(const D
     const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
     double j[6], r;
     plane_row((double)p.x - pvx, (double)p.y - pvy, (double)p.z - pvz, (double)bx - pvx, (double)by - pvy, (double)bz - pvz, nx, ny, nz, j, r);
+    if constexpr (WEIGHTED) {
+        double w = 0.0;
+        if (valid) {
+            w = robust_psi(st->loss, st->res_scale * fabs(r), st->robust_c);
+            if (w_slot) w *= (double)w_slot[i];
+        }
+        block_store_plane<true>(valid, j, r, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE, w);
+    } else
     block_store_plane(valid, j, r, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE);
 }
 #endif  // !OA_FAMILY_TU
@@ -2630,7 +2806,7 @@ __device__ __forceinline__ void solve_update_block(DevState *__restrict__ st, co
                                                    StepRecord *__restrict__ hist, int *__restrict__ todo_count,
                                                    unsigned long long t_sums_in_hand = 0ull)
 {
-    constexpr int I_K = PLANE ? P_K : S_K, I_D = PLANE ? P_D : S_D, I_DD = PLANE ? P_DD : S_DD;
+    constexpr int I_K = PLANE ? P_K : S_K, I_D = PLANE ? P_D : S_D, I_DD = PLANE ? P_DD : S_DD, I_W = PLANE ? P_W : S_W;
     // st: the loop state in global memory (written); cs: its snapshot from the start of this launch (read)
     __shared__ double sh_M[16];
     __shared__ float sh_new[16], sh_mw[16];
@@ -2653,14 +2829,14 @@ __device__ __forceinline__ void solve_update_block(DevState *__restrict__ st, co
         if constexpr (PLANE) {
             __shared__ double sh_A[36], sh_V[36];
             int rank;
-            ok = plane_solve_from_sums(sums, cs->pivot, sh_A, sh_V, lane < 6 ? lane : 6, lane < 6 ? lane + 1 : 6, M, rank);
+            ok = plane_solve_from_sums(sums, cs->pivot, sh_A, sh_V, lane < 6 ? lane : 6, lane < 6 ? lane + 1 : 6, M, rank, cs->weighted != 0);
             if (lane == 0) st->plane_rank = rank;
         } else {
             double s[NSUMS];
             for (int k = 0; k < NSUMS; ++k) s[k] = sums[k];
             const bool jv_valid = cs->jac_valid != 0;
             for (int k = 0; k < 9; ++k) jv[k] = jv_valid ? cs->jac_v[k] : 0.0;
-            ok = solve_from_sums(s, cs->pivot, cs->with_scale != 0, M, jv, jv_valid);
+            ok = solve_from_sums(s, cs->pivot, cs->with_scale != 0, M, jv, jv_valid, false, cs->weighted != 0);
         }
         if (lane == 0) {
             if (!ok) {                                              // K < 3 -> ValueError in the reference: OA_E_TOO_FEW_PAIRS
@@ -2739,6 +2915,7 @@ __device__ __forceinline__ void solve_update_block(DevState *__restrict__ st, co
         if (lane == 0) {
             if (cs->use_target) st->ring_r[n % 5] = angle;
             st->d_pivot = mean_d;                                   // next iteration sums d relative to this mean
+            st->weight_sum = cs->weighted ? sums[I_W] : K;
             // whose turn is the next search (DevState::tree_turn)
             const double moved = cs->use_target ? (trans + angle * cs->turn_scale) * cs->local_per_world : 0.0;
             st->tree_turn = (moved > cs->turn_limit) ? 1 : 0;

@@ -194,6 +194,28 @@ class IcpEngine:
         tn = capi.as_f32(tgt_normals).reshape(-1, 3)
         self._chk(self._L.oa_set_target_normals(self._h, capi.fptr(tn), len(tn)))
 
+    LOSSES = {"none": capi.OA_LOSS_NONE, "huber": capi.OA_LOSS_HUBER, "tukey": capi.OA_LOSS_TUKEY, "cauchy": capi.OA_LOSS_CAUCHY}
+
+    def set_robust(self, loss, scale=0.0):
+        """Weight every pair of a loop step by a robust loss of its residual: 'none' (default), 'huber', 'tukey' or 'cauchy' (or
+        the OA_LOSS_* integer), with the fixed scale `scale` in world units, like thresh.  The residual is the pair distance
+        (point metric) or the distance to the tangent plane (plane metric).  K and mean / std distance stay unweighted.
+        Survives uploads and set_matrices; stat("robust_loss") reads it back, stat("weight_sum") the last step's sum of weights."""
+        if isinstance(loss, str):
+            if loss not in self.LOSSES:
+                raise ValueError("loss %r (use 'none', 'huber', 'tukey' or 'cauchy')" % (loss,))
+            loss = self.LOSSES[loss]
+        self._chk(self._L.oa_set_robust(self._h, int(loss), float(scale)))
+
+    def set_source_weights(self, weights):
+        """One weight per source vertex (finite, >= 0; the array uploaded with set_source, not the selection): a pair's weight
+        is this times the robust loss's.  None switches them off; a new set_source forgets them.  Call after set_source."""
+        if weights is None:
+            self._chk(self._L.oa_set_source_weights(self._h, None, 0))
+            return
+        w = capi.as_f32(weights).reshape(-1)
+        self._chk(self._L.oa_set_source_weights(self._h, capi.fptr(w), len(w)))
+
     def set_matrices(self, mx_align, mx_base):
         a, b = capi.as_f32(mx_align, (4, 4)), capi.as_f32(mx_base, (4, 4))
         self._chk(self._L.oa_set_matrices(self._h, capi.fptr(a), capi.fptr(b)))
@@ -207,7 +229,7 @@ class IcpEngine:
              "fast_iterations": 12, "handover_entries": 13, "handover_wave_max": 14, "enqueued_min": 15, "enqueued_max": 16,
              "watchdog_aborts": 17, "nn_ms_min": 18, "nn_ms_max": 19, "safe_radii": 20,
              "tri_ring": 21, "tri_ring_accepts": 22, "exchange_us": 23, "rccl_fallbacks": 24, "rccl_ranks_last": 25, "search_clock_mhz": 26, "brute_queue_wgs": 27,
-             "metric": 28, "plane_rank": 29}
+             "metric": 28, "plane_rank": 29, "robust_loss": 30, "weight_sum": 31}
     EXCHANGE_NAMES = {-1: None, 0: "mailbox (pinned host memory)", 1: "rccl", 2: "mailbox (peer-mapped device memory)"}
 
     def exchange_info(self):

@@ -41,6 +41,11 @@ class IcpSettings:
     # step minimises -- "point": the distance to the correspondence (Besl-McKay, the reference's loop); "plane": the distance
     # to the tangent plane at the correspondence (Chen-Medioni; rigid only, one GPU), which lets a surface slide along itself
     metric: str = "point"
+    # nor these: the weight of a pair in a step is a robust loss of its residual -- "none" (every pair weighs one, the
+    # reference's loop), "huber", "tukey" or "cauchy" with the fixed scale robust_scale in world units, like min_start --
+    # so that scan noise, a blob of wax or the rim of a partial overlap inside min_start pulls less than a good pair
+    robust_loss: str = "none"
+    robust_scale: float = 0.0
 
 
 _prefs = IcpSettings()
@@ -65,6 +70,27 @@ def apply_metric(engine, settings) -> None:
         setter(metric)
     elif metric != "point":
         raise RuntimeError("this engine has no %r metric" % metric)
+
+
+def robust_of(settings):
+    """(loss, scale) from IcpSettings.robust_loss / robust_scale, or the `icp_robust_loss` / `icp_robust_scale` preferences of
+    the registered add-on; ("none", 0.0) when neither is there."""
+    loss = getattr(settings, "robust_loss", None) or getattr(settings, "icp_robust_loss", None) or "none"
+    scale = getattr(settings, "robust_scale", None)
+    if scale is None:
+        scale = getattr(settings, "icp_robust_scale", 0.0)
+    return str(loss), float(scale or 0.0)
+
+
+def apply_robust(engine, settings) -> None:
+    """Hand the settings' robust loss to the engine -- every time: the engine is shared and remembers the last one.  An engine
+    without set_robust counts as loss-none."""
+    loss, scale = robust_of(settings)
+    setter = getattr(engine, "set_robust", None)
+    if setter is not None:
+        setter(loss, scale)
+    elif loss != "none":
+        raise RuntimeError("this engine has no %r loss" % loss)
 
 
 def build_vlist(align_obj):
@@ -123,10 +149,11 @@ class IcpAlign:
         self.engine = engine if engine is not None else default_engine(devices=getattr(self.settings, "devices", None))
 
     def run(self, source_xyz, target_xyz, mx_align, mx_base, vlist=None, early_exit=True,
-            target_tris=None, target_normals=None) -> RunResult:
+            target_tris=None, target_normals=None, source_weights=None) -> RunResult:
         """target_tris: (n, 3) triangles of the base mesh -> closest point on the surface (the reference's BVH
         semantics); None -> nearest target vertex (point-cloud targets, BASELINE's configurations).
-        target_normals: one normal per target vertex -- what settings.metric == "plane" needs of a point-cloud target."""
+        target_normals: one normal per target vertex -- what settings.metric == "plane" needs of a point-cloud target.
+        source_weights: one weight per vertex of source_xyz (finite, >= 0) -- "trust this region less"; None = all one."""
         s = self.settings
         thresh = s.min_start                                   # :83
         factor = round(1 / s.sample_fraction)                  # :89  (ZeroDivisionError at 0, as the reference)
@@ -141,7 +168,10 @@ class IcpAlign:
             if target_normals is not None:
                 eng.set_target_normals(target_normals)
         apply_metric(eng, s)
+        apply_robust(eng, s)
         eng.set_source(source_xyz, vlist=vlist, stride=factor)
+        if source_weights is not None:
+            eng.set_source_weights(source_weights)
         eng.set_matrices(mx_align, mx_base)
         return eng.run(iters=s.icp_iterations, thresh=thresh, target_d=s.target_d, use_target=s.use_target,
                        with_scale=(s.align_meth == "1"), early_exit=early_exit)
