@@ -242,6 +242,27 @@ int oa_set_target_normals(oa_ctx *ctx, const float *tgt_normals, int64_t nt);
 #define OA_LOSS_TUKEY  2
 #define OA_LOSS_CAUCHY 3
 int oa_set_robust(oa_ctx *ctx, int loss, double scale);
+/* EXTENSION: the loss's scale from each step's own residuals instead of a fixed one -- residuals are centimetres when an
+ * alignment starts and tens of microns when it ends, and no fixed c suits both.  With quantile p in (0, 1] and a floor
+ * scale_min (world units, finite and > 0), step i uses
+ *   c_i = max(m * q_i, scale_min),   m = the `scale` of oa_set_robust, now a dimensionless multiplier,
+ *   q_i = the k-th smallest, k = ceil(p * K_q) (1-based, fp64), of the float32-rounded residuals r of THIS step's pairs at THIS
+ *         step's pose -- the r the loss is applied to (see oa_set_robust) -- over the K_q pairs that are counted in K and carry
+ *         a vertex weight > 0 (zero/one vertex weights stay a vlist); a plain order statistic: no interpolation, no weighting.
+ *         K_q = 0: c_i = scale_min.  c_i is formed in fp64 from (double)q_i.
+ * p = 0.5 with m = 1.4826 x the loss's usual tuning constant is the median-absolute-deviation scale ("tukey" and nothing else
+ * to tune).  The selection is exact and runs on the device between the search and the weighted accumulation (a radix select
+ * over the residuals' bits, integer counts only: the same bits on every run), without a host round trip; nothing else about
+ * the step changes, and OA_STAT_ROBUST_SCALE reads c_i back.
+ * quantile == 0 switches it off (the default; scale_min is then ignored) and nothing changes: the same kernels, the same bits.
+ * OA_E_BAD_ARG for a quantile outside [0, 1] and, with quantile > 0, a floor that is not finite and > 0.  With OA_LOSS_NONE the
+ * setting is remembered and inert.  It survives uploads and oa_set_matrices; changing it ends a running oa_iterate sequence, as
+ * oa_set_robust does.
+ * Single-device contexts, oa_run / oa_iterate only: a quantile of the world's residuals needs the world's histogram, and the
+ * exchange between devices carries OA_NSUMS doubles -- with the setting on and a loss set, oa_run / oa_iterate of a multi-device
+ * context and oa_run_begin / oa_iter_partial fail with OA_E_STATE (the context stays usable; oa_set_robust_auto(ctx, 0, 0)
+ * brings the fixed scale back). */
+int oa_set_robust_auto(oa_ctx *ctx, double quantile, double scale_min);
 /* EXTENSION: one weight per source vertex (host, float32, n_verts as uploaded with oa_set_source; finite and >= 0), gathered
  * into the selection's order -- "trust this region less", where vlist can only say yes or no.  w == NULL switches the weights
  * off (every w_vertex = 1); a new source upload forgets them.  OA_E_STATE before oa_set_source; OA_E_BAD_ARG for a count other
@@ -302,6 +323,8 @@ int oa_reset_seeds(oa_ctx *ctx);
 #define OA_STAT_PLANE_RANK      29   /* eigenvalues the last plane solve kept (6 = fully determined); loop or oa_point_to_plane */
 #define OA_STAT_ROBUST_LOSS     30   /* OA_LOSS_* */
 #define OA_STAT_WEIGHT_SUM      31   /* sum w of the last step (loop or iterate); K when weighting is off */
+#define OA_STAT_ROBUST_SCALE    32   /* the c the last step used: oa_set_robust's scale, or c_i of oa_set_robust_auto; 0 with OA_LOSS_NONE */
+#define OA_STAT_ROBUST_QUANTILE 33   /* oa_set_robust_auto's quantile (0 = off) */
 #define OA_STAT_ENQUEUED_CHILD  1000   /* + i: the same count for child i alone */
 int oa_get_stat(oa_ctx *ctx, int what, double *value);
 /* why the exchange is what it is (AUTO's reason for not taking RCCL, librccl's error, "RCCL was aborted: ..."), or "" */

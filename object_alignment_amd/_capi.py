@@ -45,7 +45,7 @@ SYMBOLS = [
     "oa_iterate", "oa_run", "oa_get_history", "oa_run_begin", "oa_iter_partial", "oa_iter_finish", "oa_run_end",
     "oa_get_search_ms", "oa_measure_valu_ceiling", "oa_exchange_note",
     "oa_set_metric", "oa_set_target_normals", "oa_point_to_plane",
-    "oa_set_robust", "oa_set_source_weights",
+    "oa_set_robust", "oa_set_source_weights", "oa_set_robust_auto",
 ]
 
 
@@ -145,6 +145,7 @@ def load(experiments: bool = False):
     L.oa_point_to_plane.argtypes = [vp, dp, dp, dp, C.c_int64, C.c_int64, dp]
     L.oa_set_robust.argtypes = [vp, C.c_int, C.c_double]
     L.oa_set_source_weights.argtypes = [vp, fp, C.c_int64]
+    L.oa_set_robust_auto.argtypes = [vp, C.c_double, C.c_double]
     _libs[experiments] = L
     return L
 

@@ -69,12 +69,17 @@ if bpy is not None:
                                              ("cauchy", "CAUCHY", "Weight 1 / (1 + (residual / scale)^2)")],
                                       name="ICP Robust Loss", description="How a pair's weight falls with its residual", default="none")
         icp_robust_scale: FloatProperty(
-            name="ICP Robust Scale", description="Residual (world units) at which the robust loss takes hold", default=0.0, min=0, max=20)
+            name="ICP Robust Scale", description="Residual (world units) at which the robust loss takes hold; with a robust quantile: the multiple of that quantile", default=0.0, min=0, max=20)
+        icp_robust_quantile: FloatProperty(
+            name="ICP Robust Quantile", description="Take the robust scale from this quantile of each step's residuals (0.5 = the median); 0 = fixed scale", default=0.0, min=0, max=1)
+        icp_robust_scale_min: FloatProperty(
+            name="ICP Robust Scale Floor", description="Smallest robust scale (world units) an estimated scale may fall to; 0 = the target translation", default=0.0, min=0, max=20)
 
         def draw(self, context):
             col = self.layout.column()
             for name in ("icp_iterations", "redraw_frequency", "sample_fraction", "min_start", "target_d", "use_target",
-                         "take_m_with", "align_meth", "icp_metric", "icp_robust_loss", "icp_robust_scale"):
+                         "take_m_with", "align_meth", "icp_metric", "icp_robust_loss", "icp_robust_scale", "icp_robust_quantile",
+                         "icp_robust_scale_min"):
                 col.prop(self, name)
 
     class VIEW3D_PT_object_alignment(Panel):

@@ -442,6 +442,12 @@ struct oa_ctx {
     double robust_c = 0.0;           // ... its scale, world units
     float *d_w = nullptr;            // oa_set_source_weights: one weight per slot (gathered through d_sel), or nullptr; a new source forgets it
     double last_weight_sum = 0.0;    // OA_STAT_WEIGHT_SUM
+    // oa_set_robust_auto: the loss's scale from each step's own residuals, c = max(robust_c * q, robust_cmin) -- robust_c is then
+    // the multiplier m.  Off while robust_p == 0; inert while the loss is NONE (survives uploads and oa_set_matrices)
+    double robust_p = 0.0, robust_cmin = 0.0;
+    uint32_t *d_rkeys = nullptr;     // one residual key per slot (k_residual_keys), allocated when a loop with the setting on begins
+    uint32_t *d_sel_hist = nullptr;  // the radix select's SEL_LEVELS histograms
+    double last_robust_c = 0.0;      // OA_STAT_ROBUST_SCALE: the c the last step used
     double pivot[3] = { 0, 0, 0 };
     // launch geometry for k_nn_search
     int n_splits = 1, acc_blocks = 1;
@@ -868,6 +874,8 @@ struct SearchChoice {
 };
 // a loss or per-vertex weights are set: the loop's pairs carry weights (weighted kernels, the PLAIN plan)
 inline bool weighted(const oa_ctx *c) { return c->loss != OA_LOSS_NONE || c->d_w != nullptr; }
+// ... and the loss takes its scale from the step's own residuals (oa_set_robust_auto; inert without a loss)
+inline bool auto_scale(const oa_ctx *c) { return c->loss != OA_LOSS_NONE && c->robust_p > 0.0; }
 
 SearchChoice choose_search(const oa_ctx *c)
 {
@@ -1114,17 +1122,20 @@ int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
                            c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->d_partials, po,
                            (unsigned long long *)nullptr);
     } else if (c->metric == OA_METRIC_PLANE) {
+        // (the end of the search: with the scale taken from the residuals, launch_robust_scale has stamped it already)
+        unsigned long long *stamp = c->loop_active && !auto_scale(c) ? &c->d_state->t_acc_start : (unsigned long long *)nullptr;
         auto *kern = weighted(c) ? oa::k_pair_accumulate_plane<true> : oa::k_pair_accumulate_plane<false>;
         hipLaunchKernelGGL(kern, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
                            (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
                            c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n,
-                           (const float *)c->d_w, c->d_partials, c->loop_active ? &c->d_state->t_acc_start : (unsigned long long *)nullptr);
+                           (const float *)c->d_w, c->d_partials, stamp);
     } else if (weighted(c)) {
+        unsigned long long *stamp = c->loop_active && !auto_scale(c) ? &c->d_state->t_acc_start : (unsigned long long *)nullptr;
         static_assert(oa::WEIGHTED_THREADS == oa::PLANE_THREADS, "plane_threads / plane_blocks size both launches");
         hipLaunchKernelGGL(oa::k_pair_accumulate_weighted, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
                            (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
                            c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, (const float *)c->d_w,
-                           c->d_partials, c->loop_active ? &c->d_state->t_acc_start : (unsigned long long *)nullptr);
+                           c->d_partials, stamp);
     } else if (canon_blocks(c) > 0) {
         hipLaunchKernelGGL(oa::k_pair_accumulate_canon, dim3((unsigned)canon_blocks(c)), dim3((unsigned)canon_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
                            (const float4 *)c->d_src4, c->ns, canon_lanes(c), (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
@@ -1135,6 +1146,29 @@ int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
                            c->d_state, c->d_src4, c->ns, c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
                            c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->d_partials, po,
                            c->loop_active ? &c->d_state->t_acc_start : (unsigned long long *)nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+
+// oa_set_robust_auto: between the search and the weighted accumulation of a loop step, the loss's scale from the residuals of
+// the pairs that accumulation is about to form -- six launches, all on the loop's stream (oa_kernels.hpp, k_residual_keys)
+int launch_robust_scale(oa_ctx *c)
+{
+    const oa::NormalTest nrm = normal_test(c);
+    const bool plane = c->metric == OA_METRIC_PLANE;
+    auto *kern = plane ? oa::k_residual_keys<true> : oa::k_residual_keys<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
+                       (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, (const unsigned long long *)c->d_keys,
+                       c->surface ? (const float4 *)nullptr : (const float4 *)c->d_win, c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm,
+                       (plane && !c->surface) ? (const float *)c->d_tgt_n : (const float *)nullptr, (const float *)c->d_w, c->d_rkeys, c->d_sel_hist,
+                       &c->d_state->t_acc_start);
+    const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
+    for (int level = 0; level < oa::SEL_LEVELS; ++level) {
+        if (level > 0)
+            hipLaunchKernelGGL(oa::k_select_hist, dim3(hist_blocks), dim3(oa::SEL_THREADS), 0, c->stream, (const oa::DevState *)c->d_state,
+                               (const uint32_t *)c->d_rkeys, c->ns, level, c->d_sel_hist);
+        hipLaunchKernelGGL(oa::k_select_scan, dim3(1), dim3(oa::SEL_THREADS), 0, c->stream, c->d_state, c->d_sel_hist, level);
     }
     HIPCHK(hipGetLastError());
     return OA_OK;
@@ -1184,6 +1218,7 @@ int launch_search_accumulate(oa_ctx *c, bool timed, oa::RowSel &sel, bool &fused
         c->ev_used++;
     }
     if (!fused) {
+        if (auto_scale(c) && (rc = launch_robust_scale(c))) return rc;
         if ((rc = launch_accumulate(c, false, nullptr, nullptr))) return rc;
         sel = plain_rows(c);
         return OA_OK;
@@ -1291,6 +1326,14 @@ void init_loop_state(oa_ctx *c, const oa_settings *st, int iters, bool cutoff = 
         s.res_scale = cbrt(fabs(det));
     }
     s.weight_sum = 0.0;
+    // the scale from the residuals: robust_c is then the multiplier, and k_select_scan writes the scale before every accumulation
+    const bool auto_c = auto_scale(c);
+    s.robust_mult = auto_c ? c->robust_c : 0.0;
+    s.robust_p = auto_c ? c->robust_p : 0.0;
+    s.robust_cmin = auto_c ? c->robust_cmin : 0.0;
+    if (auto_c) s.robust_c = c->robust_cmin;
+    s.robust_q = 0.0;
+    s.robust_kq = 0; s.sel_prefix = 0; s.sel_rank = 0; s.pad3 = 0;
 }
 
 // oa_iterate opens a loop without an end; its history is a ring of the last ITERATE_RING iterations
@@ -1313,6 +1356,11 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
     if ((rc = use_device(c))) return rc;
     if ((rc = ensure_common(c))) return rc;
     if ((rc = ensure_history(c, iters == ITERATE_OPEN ? ITERATE_RING : iters))) return rc;   // oa_iterate: a small ring
+    if (auto_scale(c)) {                                          // the selection's buffers; its histograms start (and are kept) at zero
+        if (!c->d_rkeys) HIPCHK(dev_malloc(&c->d_rkeys, sizeof(uint32_t) * (size_t)std::max(1, c->ns)));
+        if (!c->d_sel_hist) HIPCHK(dev_malloc(&c->d_sel_hist, sizeof(uint32_t) * oa::SEL_LEVELS * oa::SEL_BINS));
+        HIPCHK(hipMemsetAsync(c->d_sel_hist, 0, sizeof(uint32_t) * oa::SEL_LEVELS * oa::SEL_BINS, c->stream));
+    }
     c->settings = *st;
     c->iterate_mode = false;
     HIPCHK(hipStreamSynchronize(c->stream));                    // nothing of an earlier loop may still write the host flag
@@ -1378,6 +1426,7 @@ int fetch_state(oa_ctx *c)
     c->h_state = *c->h_state_pin;
     if (c->metric == OA_METRIC_PLANE && c->h_state.n > 0) c->last_plane_rank = c->h_state.plane_rank;
     if (c->h_state.n > 0) c->last_weight_sum = c->h_state.weight_sum;
+    if (c->h_state.n > 0) c->last_robust_c = c->h_state.robust_c;
     return OA_OK;
 }
 
@@ -2281,7 +2330,7 @@ OA_EXPORT void oa_destroy(oa_ctx *c)
     OA_FREE(d_valid); OA_FREE(d_b); OA_FREE(d_dist); OA_FREE(d_counts); OA_FREE(d_offsets); OA_FREE(d_A); OA_FREE(d_B);
     OA_FREE(d_bvh_box); OA_FREE(d_bvh_prims); OA_FREE(d_tbvh_box); OA_FREE(d_tbvh_prims);
     OA_FREE(d_tri9); OA_FREE(d_tcell_start); OA_FREE(d_tcell_rec); OA_FREE(d_tri_ring); OA_FREE(d_tfine_table); OA_FREE(d_tfine_rec);
-    OA_FREE(d_sel); OA_FREE(d_src_n); OA_FREE(d_tgt_n); OA_FREE(d_w); OA_FREE(d_src4o); OA_FREE(d_perm);
+    OA_FREE(d_sel); OA_FREE(d_src_n); OA_FREE(d_tgt_n); OA_FREE(d_w); OA_FREE(d_rkeys); OA_FREE(d_sel_hist); OA_FREE(d_src4o); OA_FREE(d_perm);
 #undef OA_FREE
     if (c->h_hist_map) (void)hipHostFree(c->h_hist_map);
     if (c->h_state_pin) (void)hipHostFree(c->h_state_pin);
@@ -3258,7 +3307,7 @@ int source_reset(oa_ctx *c, long long count, long long begin, long long n_verts)
 {
     HIPCHK(hipStreamSynchronize(c->stream));
     c->loop_active = false;                                         // an open oa_iterate sequence ends with the old source
-    dev_free(c->d_src4); dev_free(c->d_keys); dev_free(c->d_prev); dev_free(c->d_win); dev_free(c->d_wsafe); dev_free(c->d_sel); dev_free(c->d_src_n); dev_free(c->d_w);
+    dev_free(c->d_src4); dev_free(c->d_keys); dev_free(c->d_prev); dev_free(c->d_win); dev_free(c->d_wsafe); dev_free(c->d_sel); dev_free(c->d_src_n); dev_free(c->d_w); dev_free(c->d_rkeys);
     dev_free(c->d_src4o); dev_free(c->d_perm); dev_free(c->d_members); dev_free(c->d_pos);
     c->h_members.clear();
     c->shard_begin = begin;
@@ -3573,7 +3622,32 @@ OA_EXPORT int oa_set_robust(oa_ctx *c, int loss, double scale)
     }
     c->loss = loss;
     c->robust_c = scale;
+    c->last_robust_c = 0.0;
     OA_ROUTE_ALL(c, oa_set_robust(sub, loss, scale));
+    return OA_OK;
+}
+
+OA_EXPORT int oa_set_robust_auto(oa_ctx *c, double quantile, double scale_min)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    if (!(quantile >= 0.0 && quantile <= 1.0))
+        return fail(OA_E_BAD_ARG, "oa_set_robust_auto: the quantile must be in (0, 1], or 0 to switch the estimated scale off");
+    if (quantile > 0.0 && !(scale_min > 0.0 && scale_min < INFINITY))
+        return fail(OA_E_BAD_ARG, "oa_set_robust_auto: the floor of the scale must be finite and > 0 (world units, like thresh)");
+    if (quantile == 0.0) scale_min = 0.0;
+    if (quantile == c->robust_p && scale_min == c->robust_cmin) return OA_OK;
+    // a changed setting ends the running sequence, as oa_set_robust does
+    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
+    else if (c->loop_active) {
+        int rc = use_device(c);
+        if (rc) return rc;
+        if ((rc = fetch_state(c))) return rc;
+        c->loop_active = false;
+    }
+    c->robust_p = quantile;
+    c->robust_cmin = scale_min;
+    c->last_robust_c = 0.0;
+    OA_ROUTE_ALL(c, oa_set_robust_auto(sub, quantile, scale_min));
     return OA_OK;
 }
 
@@ -3763,6 +3837,8 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
     case OA_STAT_PLANE_RANK: *value = (double)c->last_plane_rank; return OA_OK;
     case OA_STAT_ROBUST_LOSS: *value = (double)c->loss; return OA_OK;
     case OA_STAT_WEIGHT_SUM: *value = c->last_weight_sum; return OA_OK;
+    case OA_STAT_ROBUST_SCALE: *value = c->loss == OA_LOSS_NONE ? 0.0 : (auto_scale(c) ? c->last_robust_c : c->robust_c); return OA_OK;
+    case OA_STAT_ROBUST_QUANTILE: *value = c->robust_p; return OA_OK;
     default: return fail(OA_E_BAD_ARG, "oa_get_stat: unknown key %d", what);
     }
 }
@@ -4234,6 +4310,8 @@ int run_begin(oa_ctx *c, const oa_settings *st)
 }
 // the exchange of the sums between devices and ranks carries OA_NSUMS doubles: the plane metric's wider row does not go through it
 const char *const PLANE_ONE_DEVICE = ": the plane metric runs on a single-device context through oa_run / oa_iterate (call oa_set_metric(ctx, OA_METRIC_POINT) for this path)";
+// ... and a quantile of the world's residuals needs the world's histogram, not OA_NSUMS doubles
+const char *const AUTO_ONE_DEVICE = ": a robust scale estimated from the residuals runs on a single-device context through oa_run / oa_iterate (call oa_set_robust_auto(ctx, 0, 0) for this path)";
 }  // namespace
 
 OA_EXPORT int oa_run_begin(oa_ctx *c, const oa_settings *st)
@@ -4241,6 +4319,7 @@ OA_EXPORT int oa_run_begin(oa_ctx *c, const oa_settings *st)
     if (!c || !st) return fail(OA_E_BAD_ARG, "oa_run_begin: null argument");
     OA_NOT_MULTI(c, "oa_run_begin (the split-phase loop is for one process per GPU)");
     if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_run_begin%s", PLANE_ONE_DEVICE);
+    if (auto_scale(c)) return fail(OA_E_STATE, "oa_run_begin%s", AUTO_ONE_DEVICE);
     return run_begin(c, st);
 }
 
@@ -4249,6 +4328,7 @@ OA_EXPORT int oa_iter_partial(oa_ctx *c, double *d_sums)
     if (!c || !d_sums) return fail(OA_E_BAD_ARG, "oa_iter_partial: null argument");
     OA_NOT_MULTI(c, "oa_iter_partial");
     if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_iter_partial%s", PLANE_ONE_DEVICE);
+    if (auto_scale(c)) return fail(OA_E_STATE, "oa_iter_partial%s", AUTO_ONE_DEVICE);
     if (!c->loop_active) return fail(OA_E_STATE, "oa_iter_partial outside oa_run_begin/oa_run_end");
     int rc = use_device(c);
     if (rc) return rc;
@@ -4284,6 +4364,7 @@ OA_EXPORT int oa_run(oa_ctx *c, const oa_settings *st, oa_report *rep)
 {
     if (!c || !st || !rep) return fail(OA_E_BAD_ARG, "oa_run: null argument");
     if (!c->subs.empty() && c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_run on a multi-device context%s", PLANE_ONE_DEVICE);
+    if (!c->subs.empty() && auto_scale(c)) return fail(OA_E_STATE, "oa_run on a multi-device context%s", AUTO_ONE_DEVICE);
     if (!c->subs.empty()) return multi_run(c, st, rep);
     int rc = run_begin(c, st);
     if (rc) return rc;
@@ -4330,6 +4411,7 @@ OA_EXPORT int oa_iterate(oa_ctx *c, const oa_settings *st, double M_step[16], do
     if (!c || !st) return fail(OA_E_BAD_ARG, "oa_iterate: null argument");
     const bool multi = !c->subs.empty();
     if (multi && c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_iterate on a multi-device context%s", PLANE_ONE_DEVICE);
+    if (multi && auto_scale(c)) return fail(OA_E_STATE, "oa_iterate on a multi-device context%s", AUTO_ONE_DEVICE);
     int rc;
     if (c->loop_active && !(c->iterate_mode && same_loop_settings(*st, c->settings))) {
         if (multi) multi_abort(c);

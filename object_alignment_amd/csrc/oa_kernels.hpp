@@ -119,6 +119,15 @@ struct DevState {
     double robust_c;          // the loss's scale, world units
     double res_scale;         // plane metric: cbrt(|det mx1[:3,:3]|), align-local residual -> world units (set when the loop starts)
     double weight_sum;        // sum w of the last step; K when weighting is off (OA_STAT_WEIGHT_SUM)
+    // the loss's scale from the step's own residuals (oa_set_robust_auto): c = max(robust_mult * q, robust_cmin), q the
+    // ceil(robust_p * K_q)-th smallest of the K_q float32 residuals that take part; k_select_scan writes robust_c from them
+    // before the accumulation reads it.  robust_p = 0: off, robust_c stays what the host wrote
+    double robust_mult, robust_p, robust_cmin;
+    double robust_q;          // the last step's order statistic (0 when K_q = 0)
+    uint32_t robust_kq;       // ... and how many residuals took part
+    uint32_t sel_prefix;      // radix select, between its launches: the key's leading bits found so far ...
+    uint32_t sel_rank;        // ... and the 0-based rank wanted among the keys that share them
+    uint32_t pad3;
 };
 
 // Squared local search radius for the query p (rounded up to float).  Derivation: the pair test measures
@@ -2570,6 +2579,211 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_plane(const D
         block_store_plane<true>(valid, j, r, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE, w);
     } else
     block_store_plane(valid, j, r, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE);
+}
+#endif  // !OA_FAMILY_TU
+
+// ---- the loss's scale from the step's own residuals (oa_set_robust_auto): an exact order statistic on the device --------
+// c = max(m q, c_min), q the k-th smallest (k = ceil(p K_q), 1-based) of the K_q residuals of this step's pairs that are counted
+// in K and carry a vertex weight > 0, each rounded to float32.  The bits of a non-negative float order as unsigned integers, so
+// q is found by a radix select over its 32-bit key, most significant digit first, 11 + 11 + 10 bits: count the keys per digit
+// (SEL_BINS bins: in LDS per workgroup, merged with integer atomicAdd -- any order gives the same counts), walk the counts to
+// the bin that holds rank k, go on among the keys that share the digits found so far.  Per iteration, between the search and
+// the weighted accumulation:
+//   k_residual_keys   one thread per slot: the pair k_pair_accumulate_weighted / _plane<true> is about to form, read-only
+//                     (keys, prev, win stay as the search left them) -> its key (RKEY_NONE: takes no part) + level 0's counts
+//   k_select_scan 0   one workgroup: K_q, k, level 0's bin
+//   k_select_hist 1, k_select_scan 1, k_select_hist 2     over the 4-byte keys only
+//   k_select_scan 2   q, robust_c = max(m q, c_min) into DevState (what the accumulation reads), the three histograms zeroed
+// i.e. six short launches, no host round trip, no float atomics: the same bits whatever order the workgroups run in.
+constexpr uint32_t RKEY_NONE = 0xFFFFFFFFu;
+constexpr int SEL_BINS = 2048, SEL_LEVELS = 3;
+constexpr int SEL_THREADS = 256;          // k_select_hist, k_select_scan
+constexpr int SEL_HIST_MAX_BLOCKS = 1024; // k_select_hist strides over the keys
+__host__ __device__ inline uint32_t sel_digit(uint32_t key, int level)
+{
+    return level == 0 ? key >> 21 : level == 1 ? (key >> 10) & 2047u : key & 1023u;
+}
+// the digits above `level`'s: what sel_prefix holds when that level is counted
+__host__ __device__ inline uint32_t sel_above(uint32_t key, int level) { return level == 1 ? key >> 21 : key >> 10; }
+
+#if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
+// one key into the workgroup's LDS counts.  The residuals of a step share their exponent, so the lanes of a wave hit a
+// handful of bins at level 0 and same-address LDS atomics take turns: up to four rounds in which the first pending lane's bin
+// is counted for every lane that shares it by ONE add, and whatever is left adds for itself.  Called by ALL lanes of the wave.
+__device__ __forceinline__ void sel_count(uint32_t *bins, bool active, uint32_t b)
+{
+    const int lane = threadIdx.x & 63;
+    for (int round = 0; round < 4; ++round) {
+        const unsigned long long pending = __ballot(active);
+        if (!pending) break;                                        // (wave-uniform)
+        const int leader = __ffsll((long long)pending) - 1;
+        const uint32_t lb = (uint32_t)__shfl((int)b, leader, 64);
+        const bool mine = active && b == lb;
+        const unsigned long long same = __ballot(mine);
+        if (lane == leader) atomicAdd(&bins[lb], (uint32_t)__popcll(same));
+        if (mine) active = false;
+    }
+    if (active) atomicAdd(&bins[b], 1u);
+}
+__device__ __forceinline__ void sel_clear(uint32_t *bins)
+{
+    for (int b = threadIdx.x; b < SEL_BINS; b += blockDim.x) bins[b] = 0u;
+    __syncthreads();
+}
+__device__ __forceinline__ void sel_flush(const uint32_t *bins, uint32_t *__restrict__ hist)
+{
+    __syncthreads();
+    for (int b = threadIdx.x; b < SEL_BINS; b += blockDim.x) {
+        const uint32_t v = bins[b];
+        if (v) atomicAdd(&hist[b], v);
+    }
+}
+
+// The residual of every slot's pair, as the weighted accumulation of this metric will see it: the same reads (keys, src4, win
+// or tri9, the normals), the same co_find, closest_on_tri, pair_eval and -- PLANE -- plane_normal / plane_row, and NO write to
+// keys, prev or win.  rkeys[i] = the bits of (float)residual (point: pair_eval's dist; plane: res_scale |n . (a' - b')|), or
+// RKEY_NONE for a slot without a pair counted in K or with vertex weight 0.  Launched like the accumulation (plane_threads /
+// plane_blocks); stamps the end of the search in its place.
+template <bool PLANE>
+__global__ __launch_bounds__(PLANE_THREADS) void k_residual_keys(const DevState *__restrict__ st, const float4 *__restrict__ src4, int ns,
+                                                             const float *__restrict__ tgt_xyz,
+                                                             const unsigned long long *__restrict__ keys,
+                                                             const float4 *__restrict__ win, const float4 *__restrict__ tri9,
+                                                             NormalTest nrm, const float *__restrict__ plane_tn,
+                                                             const float *__restrict__ w_slot, uint32_t *__restrict__ rkeys,
+                                                             uint32_t *__restrict__ hist, unsigned long long *__restrict__ t_acc_start)
+{
+    __shared__ uint32_t bins[SEL_BINS];
+    if (t_acc_start && blockIdx.x == 0 && threadIdx.x == 0) *t_acc_start = wall_clock64();   // ~ the end of the search
+    if (st->halt) return;
+    sel_clear(bins);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t rkey = RKEY_NONE;
+    if (i < ns) {
+        const uint32_t idx = (uint32_t)keys[i];
+        if (idx != IDX_NONE) {
+            const float4 p = src4[i];
+            float cx, cy, cz;
+            co_find(st, p.x, p.y, p.z, cx, cy, cz);
+            float qx, qy, qz;
+            float tn[3] = { 0.f, 0.f, 0.f };
+            if (tri9) {
+                float ta[3], tb[3], tc[3], rr[3];
+                const float cf[3] = { cx, cy, cz };
+                load_tri(tri9, idx, ta, tb, tc);
+                closest_on_tri(cf, ta, tb, tc, rr);
+                qx = rr[0]; qy = rr[1]; qz = rr[2];
+                if (PLANE || nrm.src_n) {
+                    const float e1[3] = { ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2] };
+                    const float e2[3] = { tb[0] - tc[0], tb[1] - tc[1], tb[2] - tc[2] };
+                    tn[0] = e1[1] * e2[2] - e1[2] * e2[1];
+                    tn[1] = e1[2] * e2[0] - e1[0] * e2[2];
+                    tn[2] = e1[0] * e2[1] - e1[1] * e2[0];
+                }
+            } else {
+                float4 wrec = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+                if (win) wrec = win[i];
+                if ((uint32_t)__float_as_int(wrec.w) == idx) { qx = wrec.x; qy = wrec.y; qz = wrec.z; }   // (the record holds the vertex's own coordinates)
+                else { qx = tgt_xyz[3ll * idx]; qy = tgt_xyz[3ll * idx + 1]; qz = tgt_xyz[3ll * idx + 2]; }
+                if constexpr (PLANE) { tn[0] = plane_tn[3ll * idx]; tn[1] = plane_tn[3ll * idx + 1]; tn[2] = plane_tn[3ll * idx + 2]; }
+                else if (nrm.src_n) { tn[0] = nrm.tgt_n[3ll * idx]; tn[1] = nrm.tgt_n[3ll * idx + 1]; tn[2] = nrm.tgt_n[3ll * idx + 2]; }
+            }
+            float bx, by, bz;
+            double dist;
+            bool valid = pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, tn, st->thresh, bx, by, bz, dist);
+            double res = dist;
+            if constexpr (PLANE) {
+                double nx = 0.0, ny = 0.0, nz = 0.0;
+                if (valid) valid = plane_normal(st, tn, nx, ny, nz);
+                const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
+                double j[6], r;
+                plane_row((double)p.x - pvx, (double)p.y - pvy, (double)p.z - pvz, (double)bx - pvx, (double)by - pvy, (double)bz - pvz,
+                          nx, ny, nz, j, r);
+                res = st->res_scale * fabs(r);
+            }
+            if (valid && w_slot) valid = w_slot[i] > 0.f;
+            if (valid) rkey = (uint32_t)__float_as_int((float)res);
+        }
+        rkeys[i] = rkey;
+    }
+    sel_count(bins, rkey != RKEY_NONE, sel_digit(rkey, 0));
+    sel_flush(bins, hist);
+}
+
+// levels 1 and 2: the counts of this level's digit among the keys whose higher digits are the ones found so far
+__global__ __launch_bounds__(SEL_THREADS) void k_select_hist(const DevState *__restrict__ st, const uint32_t *__restrict__ rkeys, int ns,
+                                                          int level, uint32_t *__restrict__ hist)
+{
+    __shared__ uint32_t bins[SEL_BINS];
+    if (st->halt || st->robust_kq == 0u) return;
+    sel_clear(bins);
+    const uint32_t prefix = st->sel_prefix;
+    // (whole waves leave the loop together: sel_count is a wave's business)
+    for (long long base = (long long)blockIdx.x * blockDim.x; base < ns; base += (long long)gridDim.x * blockDim.x) {
+        const long long i = base + threadIdx.x;
+        const uint32_t key = i < ns ? rkeys[i] : RKEY_NONE;
+        sel_count(bins, key != RKEY_NONE && sel_above(key, level) == prefix, sel_digit(key, level));
+    }
+    sel_flush(bins, hist + (long long)level * SEL_BINS);
+}
+
+// one workgroup: walk `level`'s counts to the bin that holds the wanted rank.  Level 0 first takes K_q (all its counts) and the
+// rank k - 1 = ceil(p K_q) - 1 from it; level 2 ends the selection: q, robust_c, the histograms back to zero.
+__global__ __launch_bounds__(SEL_THREADS) void k_select_scan(DevState *__restrict__ st, uint32_t *__restrict__ hist, int level)
+{
+    constexpr int PER = SEL_BINS / SEL_THREADS;                     // consecutive bins per thread
+    __shared__ uint32_t wave_tot[SEL_THREADS / 64];
+    if (st->halt) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t *h = hist + (long long)level * SEL_BINS;
+    uint32_t cnt[PER], mine = 0u;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) { cnt[k] = h[threadIdx.x * PER + k]; mine += cnt[k]; }
+    uint32_t incl = mine;                                           // inclusive scan over the wave, then the waves in order
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    uint32_t before = incl - mine, total = 0u;
+    for (int w = 0; w < SEL_THREADS / 64; ++w) { if (w < wave) before += wave_tot[w]; total += wave_tot[w]; }
+    uint32_t rank = st->sel_rank, prefix = st->sel_prefix, kq = st->robust_kq;
+    if (level == 0) {
+        kq = total;
+        prefix = 0u;
+        double k = ceil(st->robust_p * (double)kq);
+        k = k < 1.0 ? 1.0 : (k > (double)kq ? (double)kq : k);
+        rank = (uint32_t)k - 1u;
+    }
+    __syncthreads();                                                // (every thread has read DevState before one of them writes it)
+    if (kq != 0u && rank >= before && rank - before < mine) {       // exactly one thread
+        uint32_t r = rank - before, bin = threadIdx.x * PER;
+        bool found = false;
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {                             // (unrolled: cnt stays in registers)
+            if (!found && r < cnt[k]) found = true;
+            if (!found) { r -= cnt[k]; ++bin; }
+        }
+        prefix = level == 2 ? (prefix << 10) | bin : (prefix << 11) | bin;
+        st->sel_prefix = prefix;
+        st->sel_rank = r;
+        if (level == 0) st->robust_kq = kq;
+        if (level == SEL_LEVELS - 1) {
+            const double q = (double)__uint_as_float(prefix);
+            const double c = st->robust_mult * q;
+            st->robust_q = q;
+            st->robust_c = c > st->robust_cmin ? c : st->robust_cmin;
+        }
+    }
+    if (kq == 0u && threadIdx.x == 0 && level == 0) {               // nothing took part: the floor (the later launches return at once)
+        st->robust_kq = 0u; st->sel_prefix = 0u; st->sel_rank = 0u;
+        st->robust_q = 0.0;
+        st->robust_c = st->robust_cmin;
+    }
+    if (level == SEL_LEVELS - 1 || kq == 0u)
+        for (int b = threadIdx.x; b < SEL_LEVELS * SEL_BINS; b += SEL_THREADS) hist[b] = 0u;
 }
 #endif  // !OA_FAMILY_TU
 

@@ -207,6 +207,14 @@ class IcpEngine:
             loss = self.LOSSES[loss]
         self._chk(self._L.oa_set_robust(self._h, int(loss), float(scale)))
 
+    def set_robust_auto(self, quantile=0.0, scale_min=0.0):
+        """Take the loss's scale from each step's own residuals: c = max(scale * q, scale_min), q the ceil(quantile * K_q)-th
+        smallest float32 residual of the step's pairs (those of vertex weight 0 left out) and `scale` the multiplier given to
+        set_robust -- quantile 0.5 with 1.4826 x the loss's tuning constant is the MAD scale.  scale_min (world units, > 0) keeps
+        c off zero on exact data.  quantile 0 (default) switches it off; inert while the loss is 'none'.  Single-device
+        contexts, run / iterate only.  stat("robust_scale") reads the last step's c back, stat("robust_quantile") the setting."""
+        self._chk(self._L.oa_set_robust_auto(self._h, float(quantile), float(scale_min)))
+
     def set_source_weights(self, weights):
         """One weight per source vertex (finite, >= 0; the array uploaded with set_source, not the selection): a pair's weight
         is this times the robust loss's.  None switches them off; a new set_source forgets them.  Call after set_source."""
@@ -229,7 +237,8 @@ class IcpEngine:
              "fast_iterations": 12, "handover_entries": 13, "handover_wave_max": 14, "enqueued_min": 15, "enqueued_max": 16,
              "watchdog_aborts": 17, "nn_ms_min": 18, "nn_ms_max": 19, "safe_radii": 20,
              "tri_ring": 21, "tri_ring_accepts": 22, "exchange_us": 23, "rccl_fallbacks": 24, "rccl_ranks_last": 25, "search_clock_mhz": 26, "brute_queue_wgs": 27,
-             "metric": 28, "plane_rank": 29, "robust_loss": 30, "weight_sum": 31}
+             "metric": 28, "plane_rank": 29, "robust_loss": 30, "weight_sum": 31,
+             "robust_scale": 32, "robust_quantile": 33}
     EXCHANGE_NAMES = {-1: None, 0: "mailbox (pinned host memory)", 1: "rccl", 2: "mailbox (peer-mapped device memory)"}
 
     def exchange_info(self):

@@ -46,6 +46,17 @@ class IcpSettings:
     # so that scan noise, a blob of wax or the rim of a partial overlap inside min_start pulls less than a good pair
     robust_loss: str = "none"
     robust_scale: float = 0.0
+    # robust_quantile > 0: the loss's scale comes from each step's own residuals, c = max(robust_scale * q, robust_scale_min) with
+    # q their robust_quantile-th order statistic, and robust_scale is a dimensionless multiplier (MAD_TUNING).  The floor is in
+    # world units; None = target_d, the length the loop converges to
+    robust_quantile: float = 0.0
+    robust_scale_min: float | None = None
+
+
+MAD_TUNING = {"huber": 1.345 * 1.4826, "tukey": 4.685 * 1.4826, "cauchy": 2.385 * 1.4826}
+"""The usual constant-times-median choices of robust_scale for robust_quantile = 0.5: each loss's 95 %-efficiency tuning constant
+times 1.4826, which carries the median of |residual| to the standard deviation of Gaussian noise (the MAD scale).
+IcpSettings(robust_loss="tukey", robust_scale=MAD_TUNING["tukey"], robust_quantile=0.5) is the parameter-free setting."""
 
 
 _prefs = IcpSettings()
@@ -82,15 +93,40 @@ def robust_of(settings):
     return str(loss), float(scale or 0.0)
 
 
+def robust_auto_of(settings):
+    """(quantile, floor) from IcpSettings.robust_quantile / robust_scale_min, or the `icp_robust_quantile` /
+    `icp_robust_scale_min` preferences of the registered add-on; (0.0, 0.0) -- off -- when neither is there.  A floor of None
+    (or 0, the preference's "not set") is the settings' target_d."""
+    quantile = getattr(settings, "robust_quantile", None)
+    if quantile is None:
+        quantile = getattr(settings, "icp_robust_quantile", 0.0)
+    quantile = float(quantile or 0.0)
+    if quantile == 0.0:
+        return 0.0, 0.0
+    floor = getattr(settings, "robust_scale_min", None)
+    if floor is None:
+        floor = getattr(settings, "icp_robust_scale_min", None)
+    if not floor:
+        floor = getattr(settings, "target_d", None)
+    return quantile, float(floor or 0.0)
+
+
 def apply_robust(engine, settings) -> None:
-    """Hand the settings' robust loss to the engine -- every time: the engine is shared and remembers the last one.  An engine
-    without set_robust counts as loss-none."""
+    """Hand the settings' robust loss and its estimated-scale setting to the engine -- every time, off included: the engine is
+    shared and remembers the last ones.  An engine without set_robust counts as loss-none, one without set_robust_auto as a
+    fixed-scale engine."""
     loss, scale = robust_of(settings)
     setter = getattr(engine, "set_robust", None)
     if setter is not None:
         setter(loss, scale)
     elif loss != "none":
         raise RuntimeError("this engine has no %r loss" % loss)
+    quantile, floor = robust_auto_of(settings)
+    setter = getattr(engine, "set_robust_auto", None)
+    if setter is not None:
+        setter(quantile, floor)
+    elif quantile != 0.0:
+        raise RuntimeError("this engine cannot estimate the robust scale")
 
 
 def build_vlist(align_obj):

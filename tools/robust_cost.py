@@ -1,8 +1,10 @@
-"""What a weighted loop costs per iteration: loss none against Tukey, same build, same GPU, same inputs.
+"""What a weighted loop costs per iteration: loss none against Tukey at a fixed scale against Tukey with the scale taken
+from each step's residuals (oa_set_robust_auto: the median, times MAD_TUNING["tukey"]), same build, same GPU, same inputs.
 
 A weighted step runs search -> accumulate (no accumulating search epilogue knows about weights), so besides the weighted
-accumulation itself it gives up the fused epilogue of the grid and tree searches.  Two legs, each timed as loop_ms / iters_done
-of a loop that cannot end early:
+accumulation itself it gives up the fused epilogue of the grid and tree searches.  The estimated scale adds a read-only pair
+fetch, the radix select over the 4-byte keys and its scans (six launches) between the search and the weighted accumulation.
+Two legs, each timed as loop_ms / iters_done of a loop that cannot end early:
   point  1M <-> 1M random clouds (bench.py's flagship inputs), grid search, point metric
   plane  1M bunny points on the 1.96M-triangle lattice mesh (bench.py's surface leg), plane metric
 Prints one JSON line.  No pass/fail bar: DESIGN.md 3.10 records the numbers.
@@ -20,6 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from object_alignment_amd import synth                      # noqa: E402
 from object_alignment_amd.engine import IcpEngine           # noqa: E402
+from object_alignment_amd.operators.icp_align import MAD_TUNING   # noqa: E402
 
 
 def per_iteration_ms(e, steps, warmup, mxa, mxb, reps=3):
@@ -35,12 +38,15 @@ def per_iteration_ms(e, steps, warmup, mxa, mxb, reps=3):
 
 def leg(e, steps, scale, mxa, mxb):
     out = {}
-    for loss in ("none", "tukey"):
-        e.set_robust(loss, scale if loss != "none" else 0.0)
+    for name in ("none", "tukey", "tukey_auto"):
+        e.set_robust("none" if name == "none" else "tukey", {"none": 0.0, "tukey": scale, "tukey_auto": MAD_TUNING["tukey"]}[name])
+        e.set_robust_auto(0.5 if name == "tukey_auto" else 0.0, 1e-4)
         ms, r = per_iteration_ms(e, steps, 1, mxa, mxb)
-        out[loss] = {"ms_per_iteration": round(ms, 4), "iters": r.iters_done, "last_K": r.last_K, "weight_sum": e.stat("weight_sum"),
-                     "fast_iterations": int(e.stat("fast_iterations"))}
+        out[name] = {"ms_per_iteration": round(ms, 4), "iters": r.iters_done, "last_K": r.last_K, "weight_sum": e.stat("weight_sum"),
+                     "robust_scale": e.stat("robust_scale"), "fast_iterations": int(e.stat("fast_iterations"))}
+    e.set_robust_auto(0.0)
     out["tukey_over_none"] = round(out["tukey"]["ms_per_iteration"] / out["none"]["ms_per_iteration"], 3)
+    out["auto_over_fixed"] = round(out["tukey_auto"]["ms_per_iteration"] / out["tukey"]["ms_per_iteration"], 3)
     return out
 
 
