@@ -403,6 +403,55 @@ int oa_iter_finish(oa_ctx *ctx, const double *d_sums);
 /* synchronise and fetch the report. */
 int oa_run_end(oa_ctx *ctx, oa_report *rep);
 
+/* ---- EXTENSION: coarse global alignment (no counterpart in the reference, whose only remedy for a bad start is picking
+ *      landmarks by hand, operators/align_pick_points.py) -- DESIGN.md 3.11 ------------------------------------------ */
+/* Scores of n_poses candidate align matrices (host, n_poses x 16 float32, row-major) in ONE launch: per pose a cold nearest-
+ * primitive query (vertex or surface mode, the context's correspondence rule, through the target's box tree) for every sample
+ * point -- the selection's points whose position in the caller's (vlist) order is a multiple of stride (stride <= 1: all; S of
+ * them) -- with the pose in place of matrix_world: the query is co_find's, the distance and its test `dist < thresh` are
+ * make_pairs'.  No normal-angle test, no weights.  Per pose, OA_POSE_NSCORE doubles:
+ *   K          sample points with dist < thresh
+ *   mean_dist  } the d_stats oa_make_pairs(thresh, calc_stats = 1) reports for that pose and that sample (population std);
+ *   std_dist   } NaN when K = 0
+ *   cost       (sum of the passing dist + (S - K) thresh) / S: the mean of min(dist, thresh); finite, lower is better
+ * Fixed-order fp64 sums: the same bits on every run.  No side effects: the call reads the base matrix of oa_set_matrices and
+ * writes nothing a loop reads -- a running oa_iterate sequence continues, a later oa_run returns the bits it would have.
+ * OA_E_STATE without target, source or matrices, without the box tree (OA_SEARCH_BRUTE), with an empty selection, and on a
+ * multi-device context; OA_E_BAD_THRESH for thresh <= 0; OA_E_BAD_ARG for null pointers, n_poses outside 1 .. 65536, a non-finite
+ * entry, or S x n_poses >= 2^31. */
+#define OA_POSE_NSCORE 4   /* per pose: K, mean_dist, std_dist, cost */
+int oa_score_poses(oa_ctx *ctx, const float *mx_align /* n_poses x 16, host */, int32_t n_poses,
+                   double thresh, int32_t stride, double *scores /* n_poses x OA_POSE_NSCORE */);
+/* n_rot candidate align matrices: candidate k = float32(T(c_t) R_k T(-c_s) mx_align), formed in fp64; c_s = the world-space
+ * centroid of the selected source points under the current matrix_world (oa_get_matrix_world), c_t = that of the target's
+ * vertices (sums of the float32 matrix @ vertex products, accumulated in fp64 on the device in a fixed order); R_k = rotation k
+ * of the n_rot-point super-Fibonacci set on SO(3) (Alexa 2022): s = k + 1/2, r = sqrt(s/n), R = sqrt(1 - s/n),
+ * alpha = 2 pi s / sqrt(2), beta = 2 pi s / 1.533751168755204288118041, quaternion (x, y, z, w) = (r sin alpha, r cos alpha,
+ * R sin beta, R cos beta).  1 <= n_rot <= 65536.  No side effects; single-device contexts. */
+int oa_coarse_candidates(oa_ctx *ctx, int32_t n_rot, float *mx_align_out /* n_rot x 16 */);
+typedef struct oa_coarse_settings {
+    int32_t n_rot;         /* rotation candidates (256) */
+    int32_t n_refine;      /* best candidates that get a short loop (8) */
+    int32_t refine_iters;  /* iterations of that loop (10) */
+    int32_t stride;        /* sample stride for scoring and refining (4) */
+    double  thresh;        /* truncation / pair distance of the coarse stage, world units */
+} oa_coarse_settings;
+typedef struct oa_coarse_report {
+    int32_t n_candidates, best_candidate, best_rank, status;   /* best_candidate: the winner's origin (n_candidates = the incoming pose); best_rank: its place among the first scores */
+    double  cost_start, cost_best_candidate, cost_refined;     /* cost of the incoming pose, of the winner before and after its loop */
+    int64_t K_refined;
+    double  score_ms, total_ms;                                /* host time of the first scoring call / of the whole call */
+} oa_coarse_report;
+/* Multi-start: oa_coarse_candidates(n_rot) plus the incoming pose -> one scoring launch -> the n_refine lowest costs (ties to
+ * the lower index; the incoming pose always among them) each get refine_iters iterations of the plain point loop over the
+ * sample (thresh, rigid, no early exit; never the context's metric, loss, weights or normal test; a step with fewer than three
+ * pairs leaves its pose where it is) -> one more scoring launch -> matrix_world becomes the lowest cost, so that the caller's
+ * oa_run starts there.  When nothing beats the incoming pose it stays in force.  The refinement runs on kernels of its own, all
+ * poses at once: the selection, the seeds (kept, not reset), the metric and the robust settings are not touched.  Ends a
+ * running oa_iterate sequence, as oa_set_matrices does.  Single-device contexts (else OA_E_STATE); OA_E_BAD_THRESH for
+ * thresh <= 0, OA_E_BAD_ARG for n_rot outside 1 .. 65536, n_refine outside 1 .. 4096, refine_iters outside 0 .. 10000. */
+int oa_coarse_align(oa_ctx *ctx, const oa_coarse_settings *cs, oa_coarse_report *rep);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ OA_LOSS_NONE = 0
 OA_LOSS_HUBER = 1
 OA_LOSS_TUKEY = 2
 OA_LOSS_CAUCHY = 3
+OA_POSE_NSCORE = 4
 
 # every symbol include/oa_icp.h declares (tests check that the library exports all of them)
 SYMBOLS = [
@@ -46,6 +47,7 @@ SYMBOLS = [
     "oa_get_search_ms", "oa_measure_valu_ceiling", "oa_exchange_note",
     "oa_set_metric", "oa_set_target_normals", "oa_point_to_plane",
     "oa_set_robust", "oa_set_source_weights", "oa_set_robust_auto",
+    "oa_score_poses", "oa_coarse_candidates", "oa_coarse_align",
 ]
 
 
@@ -59,6 +61,17 @@ class Report(C.Structure):
                 ("reserved", C.c_int32), ("last_K", C.c_int64), ("last_translation", C.c_double),
                 ("mean_dist", C.c_double), ("std_dist", C.c_double), ("mean_rot_angle", C.c_double),
                 ("nn_ms_total", C.c_double), ("loop_ms", C.c_double)]
+
+
+class CoarseSettings(C.Structure):
+    _fields_ = [("n_rot", C.c_int32), ("n_refine", C.c_int32), ("refine_iters", C.c_int32), ("stride", C.c_int32),
+                ("thresh", C.c_double)]
+
+
+class CoarseReport(C.Structure):
+    _fields_ = [("n_candidates", C.c_int32), ("best_candidate", C.c_int32), ("best_rank", C.c_int32), ("status", C.c_int32),
+                ("cost_start", C.c_double), ("cost_best_candidate", C.c_double), ("cost_refined", C.c_double),
+                ("K_refined", C.c_int64), ("score_ms", C.c_double), ("total_ms", C.c_double)]
 
 
 class OaError(RuntimeError):
@@ -146,6 +159,9 @@ def load(experiments: bool = False):
     L.oa_set_robust.argtypes = [vp, C.c_int, C.c_double]
     L.oa_set_source_weights.argtypes = [vp, fp, C.c_int64]
     L.oa_set_robust_auto.argtypes = [vp, C.c_double, C.c_double]
+    L.oa_score_poses.argtypes = [vp, fp, C.c_int32, C.c_double, C.c_int32, dp]
+    L.oa_coarse_candidates.argtypes = [vp, C.c_int32, fp]
+    L.oa_coarse_align.argtypes = [vp, C.POINTER(CoarseSettings), C.POINTER(CoarseReport)]
     _libs[experiments] = L
     return L
 

@@ -24,6 +24,7 @@
 #define OA_SIG_TRI_SETTLE const DevState *, const float4 *, int, FineParams, const uint4 *, const float4 *, const float4 *, const int *, unsigned long long *, int *, int, int *, int *, unsigned long long *
 #define OA_SIG_TRI_RING_BUILD float4 *, int, GridParams, const int *, const float4 *, double, int *, unsigned long long *
 #define OA_SIG_BVH_SEARCH const DevState *, const float4 *, int, BvhParams, const float4 *, const float4 *, const float4 *, int *, float4 *, unsigned long long *, const int *, const int *, int, NormalTest, double *, const float *, uint2 *
+#define OA_SIG_POSE_SCORE PoseBase, const float *, const float *, const float4 *, const int *, int, int, BvhParams, const float4 *, const float4 *, const float4 *, double *
 #define OA_SIG_AFFINE_SOLVE const double *, const double *, int, long long, int, int, double *, double *
 #define OA_SIG_NN_MFMA const DevState *, const float4 *, const float4 *, const half8 *, const float4 *, int, double, unsigned long long *
 
@@ -75,6 +76,11 @@
     OA_K(X, k_bvh_search, OA_SIG_BVH_SEARCH, false, false) OA_K(X, k_bvh_search, OA_SIG_BVH_SEARCH, false, true)        \
     OA_K(X, k_bvh_search, OA_SIG_BVH_SEARCH, true, false) OA_K(X, k_bvh_search, OA_SIG_BVH_SEARCH, true, true)
 
+// ---- batched pose scoring / refinement through the box trees (the coarse stage): oa_fam_pose.hip ---------------------
+#define OA_FAMILY_POSE(X)                                                                                               \
+    OA_K(X, k_pose_score, OA_SIG_POSE_SCORE, false, false) OA_K(X, k_pose_score, OA_SIG_POSE_SCORE, false, true)        \
+    OA_K(X, k_pose_score, OA_SIG_POSE_SCORE, true, false) OA_K(X, k_pose_score, OA_SIG_POSE_SCORE, true, true)
+
 // ---- affine_matrix_from_points beyond the loop's 3-D solve: oa_fam_affine.hip ---------------------------------------
 #define OA_FAMILY_AFFINE(X)                                                                                             \
     OA_K(X, k_affine_solve, OA_SIG_AFFINE_SOLVE, AFF_MAXD, false) OA_K(X, k_affine_solve, OA_SIG_AFFINE_SOLVE, 16, true) \
@@ -104,6 +110,7 @@ OA_FAMILY_GRID(extern)
 OA_FAMILY_TRI(extern)
 OA_FAMILY_TRI_ACC(extern)
 OA_FAMILY_BVH(extern)
+OA_FAMILY_POSE(extern)
 OA_FAMILY_AFFINE(extern)
 #if defined(OA_EXPERIMENTS)
 OA_FAMILY_EXP(extern)

@@ -1257,6 +1257,27 @@ double min_singular_3x3(const float *M)
     return sqrt(m);
 }
 
+// The search radius of the grid / tree searches for a given thresh (DevState::cut_a / cut_b, search_cutoff2) and
+// 1 / sigma_min(mx2); the arguments are left as they are where no radius applies.
+void search_radius(const oa_ctx *c, const float *mx2, double thresh, double &cut_a, double &cut_b, double &local_per_world)
+{
+    if (!(c->filter_ok && c->grid_mode != 0 && env_int("OA_NN_CUTOFF", 1))) return;
+    const double smin = min_singular_3x3(mx2) * (1.0 - 1e-9);
+    if (smin > 0.0) local_per_world = 1.0 / smin;
+    double m2norm = 0.0, tmax = 0.0, tscale = 0.0;
+    for (int i = 0; i < 3; ++i) {
+        m2norm = std::max(m2norm, fabs((double)mx2[4 * i]) + fabs((double)mx2[4 * i + 1]) + fabs((double)mx2[4 * i + 2]));
+        tmax = std::max(tmax, fabs((double)mx2[4 * i + 3]));
+        tscale = std::max(tscale, std::max(fabs(c->bb_lo[i]), fabs(c->bb_hi[i])));
+    }
+    const double u64 = 64.0 * 5.9604644775390625e-08;
+    if (smin > 0.0 && thresh > 0.0 && thresh < 1e300) {
+        cut_a = (thresh + u64 * (m2norm * 3.0 * tscale + tmax)) / smin * (1.0 + 1e-5);
+        cut_b = u64 * m2norm / smin * (1.0 + 1e-5);
+        if (!(cut_a < 1e300) || !(cut_b < 1e300)) { cut_a = INFINITY; cut_b = 0.0; }
+    }
+}
+
 void init_loop_state(oa_ctx *c, const oa_settings *st, int iters, bool cutoff = true)
 {
     oa::DevState &s = c->h_state;
@@ -1282,22 +1303,7 @@ void init_loop_state(oa_ctx *c, const oa_settings *st, int iters, bool cutoff = 
         if (hipHostGetDevicePointer(&dp, c->h_poll, 0) == hipSuccess) { s.host_halt = (int32_t *)dp; c->poll_mapped = true; }
         else (void)hipGetLastError();
     }
-    if (cutoff && c->filter_ok && c->grid_mode != 0 && env_int("OA_NN_CUTOFF", 1)) {
-        const double smin = min_singular_3x3(s.mx2) * (1.0 - 1e-9);
-        if (smin > 0.0) s.local_per_world = 1.0 / smin;
-        double m2norm = 0.0, tmax = 0.0, tscale = 0.0;
-        for (int i = 0; i < 3; ++i) {
-            m2norm = std::max(m2norm, fabs((double)s.mx2[4 * i]) + fabs((double)s.mx2[4 * i + 1]) + fabs((double)s.mx2[4 * i + 2]));
-            tmax = std::max(tmax, fabs((double)s.mx2[4 * i + 3]));
-            tscale = std::max(tscale, std::max(fabs(c->bb_lo[i]), fabs(c->bb_hi[i])));
-        }
-        const double u64 = 64.0 * 5.9604644775390625e-08;
-        if (smin > 0.0 && st->thresh > 0.0 && st->thresh < 1e300) {
-            s.cut_a = (st->thresh + u64 * (m2norm * 3.0 * tscale + tmax)) / smin * (1.0 + 1e-5);
-            s.cut_b = u64 * m2norm / smin * (1.0 + 1e-5);
-            if (!(s.cut_a < 1e300) || !(s.cut_b < 1e300)) { s.cut_a = INFINITY; s.cut_b = 0.0; }
-        }
-    }
+    if (cutoff) search_radius(c, s.mx2, st->thresh, s.cut_a, s.cut_b, s.local_per_world);
     for (int k = 0; k < 3; ++k) s.pivot[k] = c->pivot[k];
     s.thresh = st->thresh;
     s.target_d = st->target_d;
@@ -4489,4 +4495,289 @@ OA_EXPORT int oa_get_history(oa_ctx *c, int32_t max_n, double *step_M, float *st
         if (step_trans) step_trans[i] = r.trans;
     }
     return n;
+}
+
+// ================================================================================================
+// coarse global alignment (EXTENSION): batched pose scoring, candidates, multi-start refinement (oa_pose.hpp)
+// ================================================================================================
+namespace {
+// what the launches of one call share: the sample list, the base matrices, the call's own thresh and search radius
+struct PoseJob {
+    oa::PoseBase pb{};
+    DevTmp<int> sample;
+    int S = 0;
+    bool tri = false;
+};
+
+// workgroups per pose: enough to fill the chip over all poses, at most one per POSE_WPB sample points
+inline int pose_bpp(const oa_ctx *c, int n_poses, int S)
+{
+    const int want = (c->n_cu * 16 + n_poses - 1) / n_poses;
+    const int per = (S + oa::POSE_WPB - 1) / oa::POSE_WPB;
+    return std::max(1, std::min(want, std::min(per, oa::POSE_MAX_BPP)));
+}
+
+int pose_job_begin(oa_ctx *c, double thresh, int32_t stride, PoseJob &job)
+{
+    job.tri = c->surface;
+    const bool tree = job.tri ? (c->tbvh_ok && c->d_tbvh_box && c->d_tbvh_prims && c->d_tri9) : (c->bvh_ok && c->d_bvh_box && c->d_bvh_prims);
+    if (!tree) return fail(OA_E_STATE, "pose scoring searches through the target's box tree: none was built (OA_SEARCH_BRUTE, or a target with non-finite coordinates)");
+    if (c->ns <= 0) return fail(OA_E_STATE, "pose scoring: the selection is empty");
+    const int step = stride > 1 ? stride : 1;
+    job.S = (c->ns + step - 1) / step;
+    const oa::DevState &s = c->h_state;
+    memcpy(job.pb.mx2, s.mx2, sizeof s.mx2);
+    memcpy(job.pb.imx2, s.imx2, sizeof s.imx2);
+    static const float eye16[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+    job.pb.mx2_identity = (memcmp(s.mx2, eye16, sizeof eye16) == 0 && !env_int("OA_NO_IDENTITY_PATH", 0)) ? 1 : 0;
+    job.pb.thresh = thresh;
+    job.pb.cut_a = INFINITY; job.pb.cut_b = 0.0;
+    double lpw = 0.0;
+    search_radius(c, s.mx2, thresh, job.pb.cut_a, job.pb.cut_b, lpw);
+    for (int k = 0; k < 3; ++k) job.pb.pivot[k] = c->pivot[k];
+    HIPCHK(job.sample.alloc((size_t)job.S));
+    hipLaunchKernelGGL(oa::k_pose_sample, dim3((unsigned)((c->ns + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->d_perm, c->ns, step, job.sample.p);
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+
+// rows: n_poses x bpp rows of NSUMS (full) / POSE_NSCORE doubles
+int pose_launch(oa_ctx *c, const PoseJob &job, bool full, const float *d_poses, const float *d_iposes, int n_poses, int bpp, double *d_rows)
+{
+    const dim3 grid((unsigned)((long long)n_poses * bpp)), block(oa::POSE_WPB * 64);
+    auto launch = [&](auto TRI, auto FULL) {
+        constexpr bool tri = decltype(TRI)::value;
+        hipLaunchKernelGGL((oa::k_pose_score<tri, decltype(FULL)::value>), grid, block, 0, c->stream, job.pb, d_poses, d_iposes, (const float4 *)c->d_src4,
+                           (const int *)job.sample.p, job.S, bpp, tri ? c->tbvh : c->bvh, (const float4 *)(tri ? c->d_tbvh_box : c->d_bvh_box),
+                           (const float4 *)(tri ? c->d_tbvh_prims : c->d_bvh_prims), (const float4 *)c->d_tri9, d_rows);
+    };
+    if (job.tri) { if (full) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{}); }
+    else { if (full) launch(std::false_type{}, std::true_type{}); else launch(std::false_type{}, std::false_type{}); }
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+
+// scores of n_poses poses in device memory: n_poses x OA_POSE_NSCORE {K, mean_dist, std_dist, cost}
+int pose_scores(oa_ctx *c, const PoseJob &job, const float *d_poses, int n_poses, double *scores)
+{
+    const int bpp = pose_bpp(c, n_poses, job.S);
+    DevTmp<double> rows, sums;
+    HIPCHK(rows.alloc((size_t)n_poses * bpp * oa::POSE_NSCORE));
+    HIPCHK(sums.alloc((size_t)n_poses * oa::POSE_NSCORE));
+    int rc = pose_launch(c, job, false, d_poses, nullptr, n_poses, bpp, rows.p);
+    if (rc) return rc;
+    hipLaunchKernelGGL(oa::k_pose_rows_sum, dim3((unsigned)n_poses), dim3(64), 0, c->stream, (const double *)rows.p, bpp, oa::POSE_NSCORE, sums.p);
+    HIPCHK(hipGetLastError());
+    std::vector<double> h((size_t)n_poses * oa::POSE_NSCORE);
+    if ((rc = read_small(c, h.data(), sums.p, sizeof(double) * h.size()))) return rc;
+    const double S = (double)job.S;
+    for (int p = 0; p < n_poses; ++p) {
+        const double K = h[3 * (size_t)p], sd = h[3 * (size_t)p + 1], sdd = h[3 * (size_t)p + 2];
+        double *o = scores + (size_t)OA_POSE_NSCORE * p;
+        o[0] = K; o[1] = NAN; o[2] = NAN;
+        if (K > 0.0) {
+            const double mean = sd / K;
+            double var = sdd / K - mean * mean;
+            if (var < 0.0) var = 0.0;
+            o[1] = mean; o[2] = sqrt(var);
+        }
+        o[3] = K > 0.0 ? (sd + (S - K) * job.pb.thresh) / S : job.pb.thresh;   // (no pair: thresh itself, not S thresh / S)
+    }
+    return OA_OK;
+}
+
+// sum of M @ v over n points (float32 m4_mul_v3 images, fp64 sums, fixed order) -> their centroid
+template <int STRIDE>
+int centroid_of(oa_ctx *c, const float *d_pts, int n, const float *M, double out[3], const char *what)
+{
+    const int blocks = std::max(1, std::min(1024, (n + 255) / 256));
+    DevTmp<double> rows, sum;
+    HIPCHK(rows.alloc((size_t)blocks * 4));
+    HIPCHK(sum.alloc(4));
+    oa::Mat4f mx;
+    memcpy(mx.m, M, sizeof mx.m);
+    hipLaunchKernelGGL((oa::k_centroid_rows<STRIDE>), dim3((unsigned)blocks), dim3(256), 0, c->stream, d_pts, n, mx, rows.p);
+    hipLaunchKernelGGL(oa::k_pose_rows_sum, dim3(1), dim3(64), 0, c->stream, (const double *)rows.p, blocks, 4, sum.p);
+    HIPCHK(hipGetLastError());
+    double h[4];
+    const int rc = read_small(c, h, sum.p, sizeof h);
+    if (rc) return rc;
+    if (!(h[3] > 0.0)) return fail(OA_E_STATE, "oa_coarse_candidates: the %s has no finite point", what);
+    for (int k = 0; k < 3; ++k) out[k] = h[k] / h[3];
+    return OA_OK;
+}
+
+void mul4d(const double *A, const double *B, double *out)
+{
+    double r[16];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double a = 0.0;
+            for (int k = 0; k < 4; ++k) a += A[4 * i + k] * B[4 * k + j];
+            r[4 * i + j] = a;
+        }
+    memcpy(out, r, sizeof r);
+}
+
+// candidate k = float32(T(c_t) R_k T(-c_s) mx_align), R_k = rotation k of the n_rot-point super-Fibonacci set (Alexa 2022)
+int coarse_candidates(oa_ctx *c, int n_rot, float *out)
+{
+    double cs[3], ct[3];
+    int rc = centroid_of<4>(c, (const float *)c->d_src4, c->ns, c->h_state.mx1, cs, "selection");
+    if (rc) return rc;
+    if ((rc = centroid_of<3>(c, c->d_tgt_xyz, c->nt, c->h_state.mx2, ct, "target"))) return rc;
+    double A[16], Tt[16] = { 1, 0, 0, ct[0], 0, 1, 0, ct[1], 0, 0, 1, ct[2], 0, 0, 0, 1 }, Ts[16] = { 1, 0, 0, -cs[0], 0, 1, 0, -cs[1], 0, 0, 1, -cs[2], 0, 0, 0, 1 };
+    for (int k = 0; k < 16; ++k) A[k] = (double)c->h_state.mx1[k];
+    double right[16];
+    mul4d(Ts, A, right);
+    const double two_pi = 6.283185307179586476925286766559, psi = 1.533751168755204288118041;
+    for (int k = 0; k < n_rot; ++k) {
+        const double s = (double)k + 0.5, t = s / (double)n_rot;
+        const double r = sqrt(t), R = sqrt(1.0 - t), alpha = two_pi * s / sqrt(2.0), beta = two_pi * s / psi;
+        const double x = r * sin(alpha), y = r * cos(alpha), z = R * sin(beta), w = R * cos(beta);
+        const double Rm[16] = { 1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w), 0.0,
+                                2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w), 0.0,
+                                2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y), 0.0,
+                                0.0, 0.0, 0.0, 1.0 };
+        double M[16];
+        mul4d(Rm, right, M);
+        mul4d(Tt, M, M);
+        for (int e = 0; e < 16; ++e) out[16 * (size_t)k + e] = (float)M[e];
+    }
+    return OA_OK;
+}
+
+int pose_call_ready(oa_ctx *c)
+{
+    int rc = check_ready(c);
+    if (rc) return rc;
+    if ((rc = use_device(c))) return rc;
+    return ensure_common(c);
+}
+}  // namespace
+
+OA_EXPORT int oa_score_poses(oa_ctx *c, const float *mx_align, int32_t n_poses, double thresh, int32_t stride, double *scores)
+{
+    if (!c || !mx_align || !scores) return fail(OA_E_BAD_ARG, "oa_score_poses: null argument");
+    OA_NOT_MULTI(c, "oa_score_poses");
+    int rc = pose_call_ready(c);
+    if (rc) return rc;
+    if (!(thresh > 0.0)) return fail(OA_E_BAD_THRESH, "thresh must be > 0 (the reference's make_pairs returns None)");
+    if (!(thresh < INFINITY)) return fail(OA_E_BAD_ARG, "oa_score_poses: thresh must be finite");
+    if (n_poses < 1 || n_poses > 65536) return fail(OA_E_BAD_ARG, "oa_score_poses: %d poses (1 .. 65536)", n_poses);
+    for (size_t k = 0; k < 16 * (size_t)n_poses; ++k)
+        if (!(fabsf(mx_align[k]) < INFINITY)) return fail(OA_E_BAD_ARG, "oa_score_poses: entry %zu of pose %zu is not finite", k % 16, k / 16);
+    {
+        const long long step = stride > 1 ? stride : 1, S = (c->ns + step - 1) / step;
+        if (S * n_poses >= (1ll << 31)) return fail(OA_E_BAD_ARG, "oa_score_poses: %lld sample points x %d poses: 2^31 queries or more", S, n_poses);
+    }
+    PoseJob job;
+    if ((rc = pose_job_begin(c, thresh, stride, job))) return rc;
+    DevTmp<float> d_poses;
+    HIPCHK(d_poses.alloc(16 * (size_t)n_poses));
+    HIPCHK(hipMemcpyAsync(d_poses.p, mx_align, sizeof(float) * 16 * (size_t)n_poses, hipMemcpyHostToDevice, c->stream));
+    rc = pose_scores(c, job, d_poses.p, n_poses, scores);
+    if (rc) (void)hipStreamSynchronize(c->stream);                // (the caller's matrices may still be on their way)
+    return rc;
+}
+
+OA_EXPORT int oa_coarse_candidates(oa_ctx *c, int32_t n_rot, float *mx_align_out)
+{
+    if (!c || !mx_align_out) return fail(OA_E_BAD_ARG, "oa_coarse_candidates: null argument");
+    OA_NOT_MULTI(c, "oa_coarse_candidates");
+    int rc = pose_call_ready(c);
+    if (rc) return rc;
+    if (n_rot < 1 || n_rot > 65536) return fail(OA_E_BAD_ARG, "oa_coarse_candidates: %d rotations (1 .. 65536)", n_rot);
+    if (c->ns <= 0) return fail(OA_E_STATE, "oa_coarse_candidates: the selection is empty");
+    return coarse_candidates(c, n_rot, mx_align_out);
+}
+
+OA_EXPORT int oa_coarse_align(oa_ctx *c, const oa_coarse_settings *cs, oa_coarse_report *rep)
+{
+    if (!c || !cs || !rep) return fail(OA_E_BAD_ARG, "oa_coarse_align: null argument");
+    OA_NOT_MULTI(c, "oa_coarse_align");
+    int rc = pose_call_ready(c);
+    if (rc) return rc;
+    if (!(cs->thresh > 0.0)) return fail(OA_E_BAD_THRESH, "thresh must be > 0 (the reference's make_pairs returns None)");
+    if (!(cs->thresh < INFINITY) || cs->n_rot < 1 || cs->n_rot > 65536 || cs->n_refine < 1 || cs->n_refine > 4096 || cs->refine_iters < 0 || cs->refine_iters > 10000)
+        return fail(OA_E_BAD_ARG, "oa_coarse_align: n_rot 1 .. 65536, n_refine 1 .. 4096, refine_iters 0 .. 10000 and a finite thresh");
+    memset(rep, 0, sizeof *rep);
+    // the call ends a running sequence, as oa_set_matrices does; the pose it reached is the incoming one
+    if (c->loop_active) {
+        if ((rc = fetch_state(c))) return rc;
+        c->loop_active = false;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    const int n_rot = cs->n_rot, P = n_rot + 1;                     // the incoming pose is candidate n_rot
+    const int n_ref = std::min((int)cs->n_refine, P);
+    std::vector<float> cand(16 * (size_t)P);
+    if ((rc = coarse_candidates(c, n_rot, cand.data()))) return rc;
+    memcpy(cand.data() + 16 * (size_t)n_rot, c->h_state.mx1, sizeof(float) * 16);
+    {
+        const long long step = cs->stride > 1 ? cs->stride : 1, S = (c->ns + step - 1) / step;
+        if (S * P >= (1ll << 31)) return fail(OA_E_BAD_ARG, "oa_coarse_align: %lld sample points x %d poses: 2^31 queries or more", S, P);
+    }
+    PoseJob job;
+    if ((rc = pose_job_begin(c, cs->thresh, cs->stride, job))) return rc;
+    DevTmp<float> d_poses, d_iposes;
+    HIPCHK(d_poses.alloc(16 * (size_t)P));
+    HIPCHK(hipMemcpyAsync(d_poses.p, cand.data(), sizeof(float) * cand.size(), hipMemcpyHostToDevice, c->stream));
+    std::vector<double> sc((size_t)OA_POSE_NSCORE * P);
+    const auto t1 = std::chrono::steady_clock::now();
+    if ((rc = pose_scores(c, job, d_poses.p, P, sc.data()))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    rep->score_ms = ms_since(t1);
+    // the n_refine lowest costs, ties to the lower index; the incoming pose is always among them
+    std::vector<int> order((size_t)P);
+    for (int k = 0; k < P; ++k) order[(size_t)k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return sc[4 * (size_t)a + 3] < sc[4 * (size_t)b + 3]; });
+    std::vector<int> pick(order.begin(), order.begin() + n_ref);
+    if (std::find(pick.begin(), pick.end(), n_rot) == pick.end()) pick.back() = n_rot;
+    std::vector<float> ref(16 * (size_t)n_ref), iref(16 * (size_t)n_ref);
+    for (int k = 0; k < n_ref; ++k) {
+        memcpy(&ref[16 * (size_t)k], &cand[16 * (size_t)pick[(size_t)k]], sizeof(float) * 16);
+        if (!oa::m4_inverted(&ref[16 * (size_t)k], &iref[16 * (size_t)k])) return fail(OA_E_SINGULAR, "oa_coarse_align: candidate %d has no inverse", pick[(size_t)k]);
+    }
+    HIPCHK(d_iposes.alloc(16 * (size_t)n_ref));
+    HIPCHK(hipStreamSynchronize(c->stream));                      // (d_poses is reused: the first upload has been read)
+    HIPCHK(hipMemcpyAsync(d_poses.p, ref.data(), sizeof(float) * ref.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_iposes.p, iref.data(), sizeof(float) * iref.size(), hipMemcpyHostToDevice, c->stream));
+    if (cs->refine_iters > 0) {
+        const int bpp = pose_bpp(c, n_ref, job.S);
+        DevTmp<double> rows;
+        HIPCHK(rows.alloc((size_t)n_ref * bpp * oa::NSUMS));
+        for (int it = 0; it < cs->refine_iters; ++it) {
+            if ((rc = pose_launch(c, job, true, d_poses.p, d_iposes.p, n_ref, bpp, rows.p))) { (void)hipStreamSynchronize(c->stream); return rc; }
+            hipLaunchKernelGGL(oa::k_pose_solve, dim3((unsigned)n_ref), dim3(64), 0, c->stream, (const double *)rows.p, bpp, c->pivot[0], c->pivot[1], c->pivot[2],
+                               d_poses.p, d_iposes.p);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    std::vector<double> sr((size_t)OA_POSE_NSCORE * n_ref);
+    if ((rc = pose_scores(c, job, d_poses.p, n_ref, sr.data()))) { (void)hipStreamSynchronize(c->stream); return rc; }
+    if ((rc = read_small(c, ref.data(), d_poses.p, sizeof(float) * ref.size()))) return rc;
+    int win = 0;
+    for (int k = 1; k < n_ref; ++k) if (sr[4 * (size_t)k + 3] < sr[4 * (size_t)win + 3]) win = k;
+    const double cost_start = sc[4 * (size_t)n_rot + 3];
+    rep->n_candidates = n_rot;
+    rep->cost_start = cost_start;
+    float inv[16];
+    const bool better = sr[4 * (size_t)win + 3] < cost_start && oa::m4_inverted(&ref[16 * (size_t)win], inv);
+    const int origin = better ? pick[(size_t)win] : n_rot;
+    rep->best_candidate = origin;
+    rep->best_rank = (int32_t)(std::find(order.begin(), order.end(), origin) - order.begin());
+    rep->cost_best_candidate = sc[4 * (size_t)origin + 3];
+    if (better) {
+        rep->cost_refined = sr[4 * (size_t)win + 3];
+        rep->K_refined = (int64_t)sr[4 * (size_t)win];
+        memcpy(c->h_state.mx1, &ref[16 * (size_t)win], sizeof inv);
+        memcpy(c->h_state.imx1, inv, sizeof inv);
+        c->last_todo_wave_max = -1;                                 // a new pose (oa_set_matrices)
+    } else {                                                        // nothing beats the incoming pose: it stays in force
+        rep->cost_refined = cost_start;
+        rep->K_refined = (int64_t)sc[4 * (size_t)n_rot];
+    }
+    rep->status = OA_OK;
+    rep->total_ms = ms_since(t0);
+    return OA_OK;
 }

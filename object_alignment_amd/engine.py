@@ -411,6 +411,35 @@ class IcpEngine:
         return M, dict(K=int(s[0]), mean_dist=s[1], std_dist=s[2], translation=s[3], rot_angle=s[4],
                        converged=bool(s[5]))
 
+    # ---- coarse global alignment (extension; single-device contexts)
+    def score_poses(self, mx_align_list, thresh, stride=1) -> np.ndarray:
+        """Scores of P candidate align matrices in one launch: (P, 4) float64 [K, mean_dist, std_dist, cost] per pose over the
+        selection's points at positions 0, stride, 2 stride, ... -- K / mean / std are what make_pairs(thresh, calc_stats=True)
+        reports for that pose and sample, cost is the mean of min(dist, thresh) (lower is better).  No side effects."""
+        m = capi.as_f32(mx_align_list).reshape(-1, 4, 4)
+        out = np.empty((max(1, len(m)), capi.OA_POSE_NSCORE), np.float64)
+        self._chk(self._L.oa_score_poses(self._h, capi.fptr(m), len(m), float(thresh), int(stride), capi.dptr(out)))
+        return out[: len(m)]
+
+    def coarse_candidates(self, n_rot) -> np.ndarray:
+        """(n_rot, 4, 4) float32 align matrices: the current matrix_world turned about the selection's world centroid by the
+        n_rot-point super-Fibonacci rotations, its centroid moved onto the target's.  No side effects."""
+        n = int(n_rot)
+        out = np.empty((max(1, n), 4, 4), np.float32)
+        self._chk(self._L.oa_coarse_candidates(self._h, n, capi.fptr(out)))
+        return out[:n]
+
+    def coarse_align(self, thresh, n_rot=256, n_refine=8, refine_iters=10, stride=4) -> dict:
+        """Multi-start: score n_rot candidates and the current pose, refine the n_refine cheapest for refine_iters point
+        iterations over the sample, make the cheapest matrix_world (the current pose stays when nothing beats it).  Returns the
+        report as a dict, with the new "matrix_world"."""
+        cs = capi.CoarseSettings(int(n_rot), int(n_refine), int(refine_iters), int(stride), float(thresh))
+        rep = capi.CoarseReport()
+        self._chk(self._L.oa_coarse_align(self._h, C.byref(cs), C.byref(rep)))
+        out = {name: getattr(rep, name) for name, _ in capi.CoarseReport._fields_}
+        out["matrix_world"] = self.matrix_world()
+        return out
+
     # ---- split phase (one process per GPU)
     def run_begin(self, iters=50, thresh=0.5, target_d=0.01, use_target=True, with_scale=False, early_exit=True):
         st = self._settings(iters, thresh, target_d, use_target, with_scale, early_exit)

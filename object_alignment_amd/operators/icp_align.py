@@ -185,11 +185,13 @@ class IcpAlign:
         self.engine = engine if engine is not None else default_engine(devices=getattr(self.settings, "devices", None))
 
     def run(self, source_xyz, target_xyz, mx_align, mx_base, vlist=None, early_exit=True,
-            target_tris=None, target_normals=None, source_weights=None) -> RunResult:
+            target_tris=None, target_normals=None, source_weights=None, coarse=None) -> RunResult:
         """target_tris: (n, 3) triangles of the base mesh -> closest point on the surface (the reference's BVH
         semantics); None -> nearest target vertex (point-cloud targets, BASELINE's configurations).
         target_normals: one normal per target vertex -- what settings.metric == "plane" needs of a point-cloud target.
-        source_weights: one weight per vertex of source_xyz (finite, >= 0) -- "trust this region less"; None = all one."""
+        source_weights: one weight per vertex of source_xyz (finite, >= 0) -- "trust this region less"; None = all one.
+        coarse: a CoarseSettings (operators/coarse_align.py) -- the coarse global stage runs on the same engine in front of the
+        loop, which then starts from the pose it found (self.last_coarse holds its report); None: the loop alone."""
         s = self.settings
         thresh = s.min_start                                   # :83
         factor = round(1 / s.sample_fraction)                  # :89  (ZeroDivisionError at 0, as the reference)
@@ -209,6 +211,10 @@ class IcpAlign:
         if source_weights is not None:
             eng.set_source_weights(source_weights)
         eng.set_matrices(mx_align, mx_base)
+        self.last_coarse = None
+        if coarse is not None:
+            from .coarse_align import coarse_stage
+            self.last_coarse = coarse_stage(eng, coarse, target_xyz, mx_base)
         return eng.run(iters=s.icp_iterations, thresh=thresh, target_d=s.target_d, use_target=s.use_target,
                        with_scale=(s.align_meth == "1"), early_exit=early_exit)
 
