@@ -182,7 +182,8 @@ int oa_set_source(oa_ctx *ctx, const float *xyz, int64_t n_verts, int on_device,
 /* EXTENSION (no counterpart in the reference): reject a pair when the angle between the world-space
  * normals of the source vertex and of its correspondence exceeds max_angle_deg.  src_normals: n_verts x 3 (align-
  * local, host); tgt_normals: nt x 3 per target vertex (vertex mode; ignored in surface mode, where the geometric
- * normal of the nearest triangle is used).  Call after oa_set_source / oa_set_target; passing src_normals == NULL
+ * normal of the nearest triangle is used; NULL in vertex mode: the normals the target already has -- oa_set_target_normals,
+ * oa_estimate_target_normals(install) -- stay in force, OA_E_BAD_ARG when it has none).  Call after oa_set_source / oa_set_target; passing src_normals == NULL
  * or an angle outside (0, 180) switches the test off; a new source or target upload switches it off too. */
 int oa_set_normals(oa_ctx *ctx, const float *src_normals, int64_t n_verts, const float *tgt_normals, int64_t nt,
                    double max_angle_deg);
@@ -214,6 +215,36 @@ int oa_set_metric(oa_ctx *ctx, int metric);
 /* vertex-mode targets: per-vertex normals (base-local, nt x 3 float32, host) for the plane metric, without switching the
  * normal-angle test on; a new target upload forgets them.  Normals given through oa_set_normals serve as well. */
 int oa_set_target_normals(oa_ctx *ctx, const float *tgt_normals, int64_t nt);
+/* EXTENSION: normals for a point-cloud target, estimated on the device -- a raw scan has none to bring.
+ *
+ * oa_target_knn: vertex-mode targets.  For every target vertex i, its k nearest target vertices (itself included) in the
+ * library's exact order: ascending (d2_metric(v_i, v_j), j), lowest index first on ties.  Outputs in the caller's vertex order
+ * and indexing, row-major nt x k, host memory; either may be NULL.  Coordinates are the target's own (base-local), no matrices
+ * needed.  1 <= k <= min(64, nt), else OA_E_BAD_ARG; OA_E_STATE without a target and for a surface target.  A vertex with a
+ * non-finite coordinate has no finite distance to anything: its row is empty (index -1, d2 +inf) and it is in nobody's row; a row
+ * with fewer than k finite distances is padded the same way.  The search walks the target's box tree; a context that has none
+ * (OA_SEARCH_BRUTE, non-finite coordinates) builds one for the call. */
+int oa_target_knn(oa_ctx *ctx, int k, int32_t *out_idx, float *out_d2);
+
+#define OA_ORIENT_NONE   0   /* canonical sign: the component of largest magnitude is positive (lowest axis on equal magnitude) */
+#define OA_ORIENT_TOWARD 1   /* n . (orient_point - v) >= 0   (a scanner position) */
+#define OA_ORIENT_AWAY   2   /* n . (v - orient_point) >= 0   (an interior point; NULL orient_point = the target's fp64 centroid) */
+/* PCA normals from each vertex's k nearest neighbours (oa_target_knn's rows): unit eigenvector of the smallest eigenvalue of the
+ * neighbourhood's covariance, float32, base-local (what oa_set_target_normals takes); curvature = l0 / (l0 + l1 + l2) ("surface
+ * variation").  The covariance is fp64 and two-pass (the mean of the k points, then centred products, both summed in list
+ * order), the eigen-solve a cyclic Jacobi in fp64, the vector normalised in fp64 and rounded once; no atomics: two calls give
+ * the same bits.  The sign is the canonical one, then flipped where the orientation rule asks for it (evaluated in fp64).
+ * Degenerate neighbourhoods -- with l0 <= l1 <= l2: l1 <= 1e-12 l2, l2 zero or not finite (collinear or identical points), or
+ * fewer than three neighbours at a finite distance (non-finite coordinates) -- get the normal (0, 0, 0) and curvature 0; the
+ * plane metric drops pairs with a zero normal and does not count them in K.
+ * install != 0: the result becomes the context's target normals on the device, as after oa_set_target_normals, without a host
+ * round trip; a new target upload forgets them.  out_normals (nt x 3) / out_curvature (nt) may be NULL.
+ * 3 <= k <= min(64, nt) and orient in 0 .. 2, else OA_E_BAD_ARG; OA_ORIENT_TOWARD with a NULL point OA_E_BAD_ARG; OA_E_STATE
+ * without a target and for a surface target (oa_set_target_mesh: it uses its triangles' normals).
+ * Both calls end a running oa_iterate sequence, as oa_set_target_normals does.  Multi-device contexts route them to every child
+ * (the target is replicated: the same bits everywhere); the host outputs are the first child's. */
+int oa_estimate_target_normals(oa_ctx *ctx, int k, int orient, const float orient_point[3], int install,
+                               float *out_normals, float *out_curvature);
 /* EXTENSION (no counterpart in the reference, whose only protection against bad correspondences is the hard cut thresh): pair
  * weights.  Every pair of a loop step (oa_run, oa_iterate, the split-phase calls) carries the weight
  *   w = w_vertex * psi(r),   c = scale (world units, like thresh):

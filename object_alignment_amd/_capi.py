@@ -34,6 +34,9 @@ OA_LOSS_HUBER = 1
 OA_LOSS_TUKEY = 2
 OA_LOSS_CAUCHY = 3
 OA_POSE_NSCORE = 4
+OA_ORIENT_NONE = 0
+OA_ORIENT_TOWARD = 1
+OA_ORIENT_AWAY = 2
 
 # every symbol include/oa_icp.h declares (tests check that the library exports all of them)
 SYMBOLS = [
@@ -48,6 +51,7 @@ SYMBOLS = [
     "oa_set_metric", "oa_set_target_normals", "oa_point_to_plane",
     "oa_set_robust", "oa_set_source_weights", "oa_set_robust_auto",
     "oa_score_poses", "oa_coarse_candidates", "oa_coarse_align",
+    "oa_target_knn", "oa_estimate_target_normals",
 ]
 
 
@@ -162,6 +166,8 @@ def load(experiments: bool = False):
     L.oa_score_poses.argtypes = [vp, fp, C.c_int32, C.c_double, C.c_int32, dp]
     L.oa_coarse_candidates.argtypes = [vp, C.c_int32, fp]
     L.oa_coarse_align.argtypes = [vp, C.POINTER(CoarseSettings), C.POINTER(CoarseReport)]
+    L.oa_target_knn.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), fp]
+    L.oa_estimate_target_normals.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, fp, fp]
     _libs[experiments] = L
     return L
 

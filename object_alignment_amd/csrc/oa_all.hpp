@@ -8,6 +8,7 @@
 #include "oa_tri_fine.hpp"
 #include "oa_bvh.hpp"
 #include "oa_pose.hpp"
+#include "oa_knn.hpp"
 #include "oa_affine.hpp"
 #include "oa_mfma.hpp"
 #include "oa_families.hpp"

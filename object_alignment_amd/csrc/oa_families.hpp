@@ -25,6 +25,7 @@
 #define OA_SIG_TRI_RING_BUILD float4 *, int, GridParams, const int *, const float4 *, double, int *, unsigned long long *
 #define OA_SIG_BVH_SEARCH const DevState *, const float4 *, int, BvhParams, const float4 *, const float4 *, const float4 *, int *, float4 *, unsigned long long *, const int *, const int *, int, NormalTest, double *, const float *, uint2 *
 #define OA_SIG_POSE_SCORE PoseBase, const float *, const float *, const float4 *, const int *, int, int, BvhParams, const float4 *, const float4 *, const float4 *, double *
+#define OA_SIG_BVH_KNN BvhParams, const float4 *, const float4 *, int, int32_t *, float *, const float *, KnnOrient, float *, float *
 #define OA_SIG_AFFINE_SOLVE const double *, const double *, int, long long, int, int, double *, double *
 #define OA_SIG_NN_MFMA const DevState *, const float4 *, const float4 *, const half8 *, const float4 *, int, double, unsigned long long *
 
@@ -81,6 +82,9 @@
     OA_K(X, k_pose_score, OA_SIG_POSE_SCORE, false, false) OA_K(X, k_pose_score, OA_SIG_POSE_SCORE, false, true)        \
     OA_K(X, k_pose_score, OA_SIG_POSE_SCORE, true, false) OA_K(X, k_pose_score, OA_SIG_POSE_SCORE, true, true)
 
+// ---- k nearest target vertices of every target vertex / PCA normals from them (oa_knn.hpp): oa_fam_knn.hip ----------
+#define OA_FAMILY_KNN(X) OA_K(X, k_bvh_knn, OA_SIG_BVH_KNN, false) OA_K(X, k_bvh_knn, OA_SIG_BVH_KNN, true)
+
 // ---- affine_matrix_from_points beyond the loop's 3-D solve: oa_fam_affine.hip ---------------------------------------
 #define OA_FAMILY_AFFINE(X)                                                                                             \
     OA_K(X, k_affine_solve, OA_SIG_AFFINE_SOLVE, AFF_MAXD, false) OA_K(X, k_affine_solve, OA_SIG_AFFINE_SOLVE, 16, true) \
@@ -111,6 +115,7 @@ OA_FAMILY_TRI(extern)
 OA_FAMILY_TRI_ACC(extern)
 OA_FAMILY_BVH(extern)
 OA_FAMILY_POSE(extern)
+OA_FAMILY_KNN(extern)
 OA_FAMILY_AFFINE(extern)
 #if defined(OA_EXPERIMENTS)
 OA_FAMILY_EXP(extern)

@@ -735,6 +735,8 @@ int tri_ring_lazy(oa_ctx *c, bool counting)
     return c->tri_iters > TRI_RING_LAZY_ITERS ? build_tri_ring(c) : OA_OK;
 }
 int build_bvh(oa_ctx *c, bool tri);
+int build_bvh_arrays(oa_ctx *c, bool tri, int n, const double frame_lo[3], const double frame_hi[3], oa::BvhParams &bp, float4 *&d_box,
+                     float4 *&d_prims, bool &ok);
 int scan_counts(oa_ctx *c, const int *d_counts, int n, long long *d_off, DevTmp<char> &tmp);
 
 // one wave per query: 4 queries per workgroup, workgroups loop when there are more queries than that
@@ -2714,6 +2716,14 @@ int build_bvh(oa_ctx *c, bool tri)
     dev_free(d_box); dev_free(d_prims);
     const int n = tri ? c->n_tris : c->nt;
     if (!c->filter_ok || c->grid_mode == 0 || n < 1) return OA_OK;
+    return build_bvh_arrays(c, tri, n, c->bb_lo, c->bb_hi, bp, d_box, d_prims, ok);
+}
+
+// the tree itself over n primitives: level sizes, Morton order inside the frame [lo, hi], primitive images, boxes.  ok stays
+// false (and nothing is allocated) when the tree would need more than BVH_MAX_LEVELS levels.
+int build_bvh_arrays(oa_ctx *c, bool tri, int n, const double frame_lo[3], const double frame_hi[3], oa::BvhParams &bp, float4 *&d_box,
+                     float4 *&d_prims, bool &ok)
+{
     bp = oa::BvhParams{};
     bp.n_prims = n;
     long long total = 0;
@@ -2730,9 +2740,9 @@ int build_bvh(oa_ctx *c, bool tri)
     double scale = 0.0;
     float lo[3], sc[3];
     for (int a = 0; a < 3; ++a) {
-        scale = std::max(scale, std::max(fabs(c->bb_lo[a]), fabs(c->bb_hi[a])));
-        lo[a] = (float)c->bb_lo[a];
-        const double ext = c->bb_hi[a] - c->bb_lo[a];
+        scale = std::max(scale, std::max(fabs(frame_lo[a]), fabs(frame_hi[a])));
+        lo[a] = (float)frame_lo[a];
+        const double ext = frame_hi[a] - frame_lo[a];
         sc[a] = ext > 0.0 ? (float)(1023.0 / ext) : 0.f;
     }
     bp.scale = scale;
@@ -3569,19 +3579,23 @@ OA_EXPORT int oa_set_normals(oa_ctx *c, const float *src_normals, int64_t n_vert
     if (!c->d_src4 || !c->d_sel) return fail(OA_E_STATE, "oa_set_normals: call oa_set_source first");
     if (c->nt <= 0) return fail(OA_E_STATE, "oa_set_normals: call oa_set_target first");
     if (n_verts != c->src_n_verts) return fail(OA_E_BAD_ARG, "oa_set_normals: %lld source normals for %lld vertices", (long long)n_verts, c->src_n_verts);
-    if (!c->surface && (!tgt_normals || nt != c->nt)) return fail(OA_E_BAD_ARG, "oa_set_normals: vertex mode needs one normal per target vertex");
+    // vertex mode without tgt_normals: the target's own normals (oa_set_target_normals, oa_estimate_target_normals) stay in force
+    const bool keep_tgt = !c->surface && !tgt_normals && c->d_tgt_n;
+    if (!c->surface && !keep_tgt && (!tgt_normals || nt != c->nt))
+        return fail(OA_E_BAD_ARG, "oa_set_normals: vertex mode needs one normal per target vertex (given here, or set / estimated before)");
     int rc = use_device(c);
     if (rc) return rc;
     DevTmp<float> tmp;
     HIPCHK(tmp.alloc(3 * (size_t)n_verts));
     HIPCHK(hipMemcpyAsync(tmp, src_normals, sizeof(float) * 3 * (size_t)n_verts, hipMemcpyHostToDevice, c->stream));
-    dev_free(c->d_src_n); dev_free(c->d_tgt_n);
+    dev_free(c->d_src_n);
+    if (!keep_tgt) dev_free(c->d_tgt_n);
     HIPCHK(dev_malloc(&c->d_src_n, sizeof(float) * 3 * (size_t)std::max(1, c->ns)));
     if (c->ns > 0)
         hipLaunchKernelGGL(oa::k_gather_rows3, dim3((c->ns + 255) / 256), dim3(256), 0, c->stream, (const float *)tmp.p,
                            (const int *)c->d_sel, c->ns, c->d_src_n);
     HIPCHK(hipGetLastError());
-    if (!c->surface) {
+    if (!c->surface && !keep_tgt) {
         HIPCHK(dev_malloc(&c->d_tgt_n, sizeof(float) * 3 * (size_t)nt));
         HIPCHK(hipMemcpyAsync(c->d_tgt_n, tgt_normals, sizeof(float) * 3 * (size_t)nt, hipMemcpyHostToDevice, c->stream));
     }
@@ -4602,7 +4616,7 @@ int centroid_of(oa_ctx *c, const float *d_pts, int n, const float *M, double out
     double h[4];
     const int rc = read_small(c, h, sum.p, sizeof h);
     if (rc) return rc;
-    if (!(h[3] > 0.0)) return fail(OA_E_STATE, "oa_coarse_candidates: the %s has no finite point", what);
+    if (!(h[3] > 0.0)) return fail(OA_E_STATE, "%s has no finite point", what);
     for (int k = 0; k < 3; ++k) out[k] = h[k] / h[3];
     return OA_OK;
 }
@@ -4623,9 +4637,9 @@ void mul4d(const double *A, const double *B, double *out)
 int coarse_candidates(oa_ctx *c, int n_rot, float *out)
 {
     double cs[3], ct[3];
-    int rc = centroid_of<4>(c, (const float *)c->d_src4, c->ns, c->h_state.mx1, cs, "selection");
+    int rc = centroid_of<4>(c, (const float *)c->d_src4, c->ns, c->h_state.mx1, cs, "oa_coarse_candidates: the selection");
     if (rc) return rc;
-    if ((rc = centroid_of<3>(c, c->d_tgt_xyz, c->nt, c->h_state.mx2, ct, "target"))) return rc;
+    if ((rc = centroid_of<3>(c, c->d_tgt_xyz, c->nt, c->h_state.mx2, ct, "oa_coarse_candidates: the target"))) return rc;
     double A[16], Tt[16] = { 1, 0, 0, ct[0], 0, 1, 0, ct[1], 0, 0, 1, ct[2], 0, 0, 0, 1 }, Ts[16] = { 1, 0, 0, -cs[0], 0, 1, 0, -cs[1], 0, 0, 1, -cs[2], 0, 0, 0, 1 };
     for (int k = 0; k < 16; ++k) A[k] = (double)c->h_state.mx1[k];
     double right[16];
@@ -4779,5 +4793,136 @@ OA_EXPORT int oa_coarse_align(oa_ctx *c, const oa_coarse_settings *cs, oa_coarse
     }
     rep->status = OA_OK;
     rep->total_ms = ms_since(t0);
+    return OA_OK;
+}
+
+// ================================================================================================
+// k nearest target vertices / PCA normals of a point-cloud target (EXTENSION; oa_knn.hpp)
+// ================================================================================================
+namespace {
+// the vertex tree a k-nearest call walks: the context's own when it has one, else a tree of the call's own (OA_SEARCH_BRUTE
+// skips the build with the upload; a target with non-finite coordinates has no bounding box -- its tree is laid out over
+// the box of the finite coordinates, the others sit in leaves whose boxes ignore them)
+struct KnnTree {
+    oa::BvhParams bp{};
+    const float4 *box = nullptr, *prims = nullptr;
+    float4 *own_box = nullptr, *own_prims = nullptr;
+    KnnTree() = default;
+    KnnTree(const KnnTree &) = delete;
+    KnnTree &operator=(const KnnTree &) = delete;
+    ~KnnTree() { dev_free(own_box); dev_free(own_prims); }
+};
+
+int knn_tree(oa_ctx *c, KnnTree &t)
+{
+    if (c->bvh_ok && c->d_bvh_box && c->d_bvh_prims) { t.bp = c->bvh; t.box = c->d_bvh_box; t.prims = c->d_bvh_prims; return OA_OK; }
+    double lo[3] = { 0.0, 0.0, 0.0 }, hi[3] = { 0.0, 0.0, 0.0 };
+    if (c->filter_ok) { for (int a = 0; a < 3; ++a) { lo[a] = c->bb_lo[a]; hi[a] = c->bb_hi[a]; } }
+    else {
+        const int nb = 256;
+        DevTmp<float> d_bb;
+        HIPCHK(d_bb.alloc(6 * (size_t)nb));
+        hipLaunchKernelGGL(oa::k_bbox_finite, dim3(nb), dim3(256), 0, c->stream, (const float *)c->d_tgt_xyz, c->nt, d_bb.p);
+        HIPCHK(hipGetLastError());
+        std::vector<float> bb(6 * (size_t)nb);
+        const int rc = read_small(c, bb.data(), d_bb.p, sizeof(float) * bb.size());
+        if (rc) return rc;
+        float l[3] = { INFINITY, INFINITY, INFINITY }, h[3] = { -INFINITY, -INFINITY, -INFINITY };
+        for (int b = 0; b < nb; ++b)
+            for (int a = 0; a < 3; ++a) { l[a] = std::min(l[a], bb[6 * (size_t)b + a]); h[a] = std::max(h[a], bb[6 * (size_t)b + 3 + a]); }
+        for (int a = 0; a < 3; ++a) if (l[a] <= h[a]) { lo[a] = l[a]; hi[a] = h[a]; }     // (no finite coordinate: any frame will do)
+    }
+    bool ok = false;
+    const int rc = build_bvh_arrays(c, false, c->nt, lo, hi, t.bp, t.own_box, t.own_prims, ok);
+    if (rc) return rc;
+    if (!ok) return fail(OA_E_CAPACITY, "the target's box tree would need more than %d levels", oa::BVH_MAX_LEVELS);
+    t.box = t.own_box; t.prims = t.own_prims;
+    return OA_OK;
+}
+
+// what both calls check and do first; a running sequence ends the way oa_set_target_normals ends one
+int knn_call_begin(oa_ctx *c, const char *who, int k, int k_min)
+{
+    if (c->nt <= 0) return fail(OA_E_STATE, "%s: call oa_set_target first", who);
+    if (c->surface) return fail(OA_E_STATE, "%s: a surface target (oa_set_target_mesh) uses its triangles' geometric normals", who);
+    if (k < k_min || k > oa::KNN_MAX_K || k > c->nt)
+        return fail(OA_E_BAD_ARG, "%s: k = %d outside %d .. min(%d, %d target vertices)", who, k, k_min, oa::KNN_MAX_K, c->nt);
+    const int rc = use_device(c);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->loop_active = false;
+    return OA_OK;
+}
+
+template <bool PCA>
+int knn_launch(oa_ctx *c, const KnnTree &t, int k, int32_t *d_idx, float *d_d2, const oa::KnnOrient &orient, float *d_n, float *d_curv)
+{
+    const int wpb = oa::knn_waves_per_block(k);
+    const int leaves = t.bp.cnt[1];
+    const unsigned blocks = (unsigned)std::max(1, std::min((leaves + wpb - 1) / wpb, c->n_cu * 32));
+    hipLaunchKernelGGL((oa::k_bvh_knn<PCA>), dim3(blocks), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, k, d_idx, d_d2,
+                       (const float *)c->d_tgt_xyz, orient, d_n, d_curv);
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+}  // namespace
+
+OA_EXPORT int oa_target_knn(oa_ctx *c, int k, int32_t *out_idx, float *out_d2)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    if (!c->subs.empty() && c->loop_active) multi_abort(c);
+    // (the target is replicated: every child computes the same bits; the first one's go out)
+    OA_ROUTE_ALL_PAR(c, oa_target_knn(sub, k, sub->rank == 0 ? out_idx : nullptr, sub->rank == 0 ? out_d2 : nullptr));
+    int rc = knn_call_begin(c, "oa_target_knn", k, 1);
+    if (rc) return rc;
+    KnnTree tree;
+    if ((rc = knn_tree(c, tree))) return rc;
+    const size_t n = (size_t)c->nt * (size_t)k;
+    DevTmp<int32_t> d_idx;
+    DevTmp<float> d_d2;
+    if (out_idx) HIPCHK(d_idx.alloc(n));
+    if (out_d2) HIPCHK(d_d2.alloc(n));
+    if ((rc = knn_launch<false>(c, tree, k, d_idx.p, d_d2.p, oa::KnnOrient{}, nullptr, nullptr))) return rc;
+    if (out_idx) HIPCHK(hipMemcpyAsync(out_idx, d_idx.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+    if (out_d2) HIPCHK(hipMemcpyAsync(out_d2, d_d2.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
+OA_EXPORT int oa_estimate_target_normals(oa_ctx *c, int k, int orient, const float orient_point[3], int install, float *out_normals,
+                                         float *out_curvature)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    if (orient != OA_ORIENT_NONE && orient != OA_ORIENT_TOWARD && orient != OA_ORIENT_AWAY)
+        return fail(OA_E_BAD_ARG, "oa_estimate_target_normals: orient %d (use OA_ORIENT_NONE / OA_ORIENT_TOWARD / OA_ORIENT_AWAY)", orient);
+    if (orient == OA_ORIENT_TOWARD && !orient_point) return fail(OA_E_BAD_ARG, "oa_estimate_target_normals: OA_ORIENT_TOWARD needs a point");
+    if (!c->subs.empty() && c->loop_active) multi_abort(c);
+    OA_ROUTE_ALL_PAR(c, oa_estimate_target_normals(sub, k, orient, orient_point, install, sub->rank == 0 ? out_normals : nullptr,
+                                                   sub->rank == 0 ? out_curvature : nullptr));
+    int rc = knn_call_begin(c, "oa_estimate_target_normals", k, 3);
+    if (rc) return rc;
+    KnnTree tree;
+    if ((rc = knn_tree(c, tree))) return rc;
+    oa::KnnOrient ko{};
+    ko.mode = orient;
+    if (orient != OA_ORIENT_NONE) {
+        if (orient_point) { for (int a = 0; a < 3; ++a) ko.p[a] = (double)orient_point[a]; }
+        else {
+            static const float eye16[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+            if ((rc = centroid_of<3>(c, c->d_tgt_xyz, c->nt, eye16, ko.p, "oa_estimate_target_normals: the target"))) return rc;
+        }
+    }
+    const size_t nt = (size_t)c->nt;
+    DevTmp<float> tmp_n, d_curv;
+    float *d_n = nullptr;
+    if (install) {                                                   // (the stream is idle: the array the loops read is replaced in place)
+        if (!c->d_tgt_n) HIPCHK(dev_malloc(&c->d_tgt_n, sizeof(float) * 3 * nt));
+        d_n = c->d_tgt_n;
+    } else if (out_normals) { HIPCHK(tmp_n.alloc(3 * nt)); d_n = tmp_n.p; }
+    if (out_curvature) HIPCHK(d_curv.alloc(nt));
+    if ((rc = knn_launch<true>(c, tree, k, nullptr, nullptr, ko, d_n, d_curv.p))) return rc;
+    if (out_normals) HIPCHK(hipMemcpyAsync(out_normals, d_n, sizeof(float) * 3 * nt, hipMemcpyDeviceToHost, c->stream));
+    if (out_curvature) HIPCHK(hipMemcpyAsync(out_curvature, d_curv.p, sizeof(float) * nt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return OA_OK;
 }

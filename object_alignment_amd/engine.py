@@ -194,6 +194,34 @@ class IcpEngine:
         tn = capi.as_f32(tgt_normals).reshape(-1, 3)
         self._chk(self._L.oa_set_target_normals(self._h, capi.fptr(tn), len(tn)))
 
+    ORIENTS = {"none": capi.OA_ORIENT_NONE, "toward": capi.OA_ORIENT_TOWARD, "away": capi.OA_ORIENT_AWAY}
+
+    def target_knn(self, k):
+        """Vertex-mode targets: the k nearest target vertices of every target vertex (itself included), exact and ordered by
+        (d2, index): (idx int32 (nt, k), d2 float32 (nt, k)), in the caller's vertex order.  1 <= k <= min(64, nt)."""
+        k = int(k)
+        shape = (max(1, self.n_target), max(1, k))
+        idx = np.empty(shape, np.int32)
+        d2 = np.empty(shape, np.float32)
+        self._chk(self._L.oa_target_knn(self._h, k, idx.ctypes.data_as(C.POINTER(C.c_int32)), capi.fptr(d2)))
+        return idx[: self.n_target], d2[: self.n_target]
+
+    def estimate_target_normals(self, k=16, orient="none", orient_point=None, install=True):
+        """Vertex-mode targets: PCA normals from every vertex's k nearest neighbours, computed on the device: (normals float32
+        (nt, 3), curvature float32 (nt,)).  orient: 'none' (canonical sign), 'toward' orient_point (a scanner position) or 'away'
+        from it (an interior point; None = the target's centroid).  install: the normals become the target's (as after
+        set_target_normals) without a host round trip.  Degenerate neighbourhoods give the zero normal.  3 <= k <= min(64, nt)."""
+        if isinstance(orient, str):
+            if orient not in self.ORIENTS:
+                raise ValueError("orient %r (use 'none', 'toward' or 'away')" % (orient,))
+            orient = self.ORIENTS[orient]
+        pt = capi.as_f32(orient_point).reshape(3) if orient_point is not None else None
+        nrm = np.empty((max(1, self.n_target), 3), np.float32)
+        curv = np.empty(max(1, self.n_target), np.float32)
+        self._chk(self._L.oa_estimate_target_normals(self._h, int(k), int(orient), capi.fptr(pt) if pt is not None else None,
+                                                      int(bool(install)), capi.fptr(nrm), capi.fptr(curv)))
+        return nrm[: self.n_target], curv[: self.n_target]
+
     LOSSES = {"none": capi.OA_LOSS_NONE, "huber": capi.OA_LOSS_HUBER, "tukey": capi.OA_LOSS_TUKEY, "cauchy": capi.OA_LOSS_CAUCHY}
 
     def set_robust(self, loss, scale=0.0):

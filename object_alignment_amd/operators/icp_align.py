@@ -51,6 +51,8 @@ class IcpSettings:
     # world units; None = target_d, the length the loop converges to
     robust_quantile: float = 0.0
     robust_scale_min: float | None = None
+    # neighbours per vertex when run(..., target_normals="estimate") estimates a point-cloud target's normals on the device
+    normal_k: int = 16
 
 
 MAD_TUNING = {"huber": 1.345 * 1.4826, "tukey": 4.685 * 1.4826, "cauchy": 2.385 * 1.4826}
@@ -182,17 +184,35 @@ class IcpAlign:
 
     def __init__(self, settings: IcpSettings | None = None, engine: IcpEngine | None = None):
         self.settings = settings if settings is not None else get_addon_preferences()
-        self.engine = engine if engine is not None else default_engine(devices=getattr(self.settings, "devices", None))
+        self._engine = engine
+
+    @property
+    def engine(self):
+        """The engine the loop runs on: the one given, else the process-wide default one, opened on first use."""
+        if self._engine is None:
+            self._engine = default_engine(devices=getattr(self.settings, "devices", None))
+        return self._engine
+
+    @engine.setter
+    def engine(self, engine):
+        self._engine = engine
 
     def run(self, source_xyz, target_xyz, mx_align, mx_base, vlist=None, early_exit=True,
             target_tris=None, target_normals=None, source_weights=None, coarse=None) -> RunResult:
         """target_tris: (n, 3) triangles of the base mesh -> closest point on the surface (the reference's BVH
         semantics); None -> nearest target vertex (point-cloud targets, BASELINE's configurations).
-        target_normals: one normal per target vertex -- what settings.metric == "plane" needs of a point-cloud target.
+        target_normals: one normal per target vertex -- what settings.metric == "plane" needs of a point-cloud target -- or
+        "estimate": PCA normals from every target vertex's settings.normal_k nearest neighbours, computed on the device after
+        the upload and oriented away from the target's centroid (point-cloud targets only: a mesh has its triangles').
         source_weights: one weight per vertex of source_xyz (finite, >= 0) -- "trust this region less"; None = all one.
         coarse: a CoarseSettings (operators/coarse_align.py) -- the coarse global stage runs on the same engine in front of the
         loop, which then starts from the pose it found (self.last_coarse holds its report); None: the loop alone."""
         s = self.settings
+        estimate = isinstance(target_normals, str)
+        if estimate and target_normals != "estimate":
+            raise ValueError("target_normals %r (an array of normals, or 'estimate')" % (target_normals,))
+        if estimate and target_tris is not None:
+            raise ValueError("target_normals='estimate' is for point-cloud targets: a mesh (target_tris) uses its triangles' normals")
         thresh = s.min_start                                   # :83
         factor = round(1 / s.sample_fraction)                  # :89  (ZeroDivisionError at 0, as the reference)
         if not thresh > 0:
@@ -203,7 +223,9 @@ class IcpAlign:
             eng.set_target_mesh(target_xyz, target_tris)
         else:
             eng.set_target(target_xyz)
-            if target_normals is not None:
+            if estimate:
+                eng.estimate_target_normals(k=int(getattr(s, "normal_k", 16)), orient="away", install=True)
+            elif target_normals is not None:
                 eng.set_target_normals(target_normals)
         apply_metric(eng, s)
         apply_robust(eng, s)
