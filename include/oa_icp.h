@@ -211,7 +211,39 @@ int oa_set_normals(oa_ctx *ctx, const float *src_normals, int64_t n_verts, const
  *   - oa_make_pairs, oa_nn_search, oa_kabsch* do not look at the metric. */
 #define OA_METRIC_POINT 0   /* default: Besl-McKay, today's loop */
 #define OA_METRIC_PLANE 1   /* Chen-Medioni */
+#define OA_METRIC_GICP  2   /* plane-to-plane (Generalized-ICP: Segal, Haehnel, Thrun 2009), see oa_set_gicp */
 int oa_set_metric(oa_ctx *ctx, int metric);
+/* OA_METRIC_GICP: every pair is weighted by a 3 x 3 matrix built from the local surface of BOTH sides.  For a
+ * pair that passes the point metric's tests (thresh, the normal-angle test when it is on), with a', b' the pair about the
+ * context's pivot, n_b the correspondence's unit normal in align-local space (exactly the plane metric's: the nearest triangle's
+ * geometric normal, or the target vertex normal) and n_a the source vertex's normal (oa_set_source_normals / oa_set_normals:
+ * align-local float32, normalised in fp64 the way n_b is: n * (1 / sqrt((x x + y y) + z z))):
+ *   M = 2 I - (1 - epsilon)(n_a n_a^T + n_b n_b^T)    the sum of the paper's regularised covariances (eigenvalues 1, 1, epsilon)
+ *   W = 2 epsilon M^-1                                  symmetric, fp64, adjugate over determinant (one division)
+ *   e = a' - b',   J = [ -[a']x , I3 ],   step x = (omega, t):   minimise sum w (e + J x)^T W (e + J x)
+ * The factor 2 epsilon does not move the step; with it e^T W e -> (n . e)^2 for n_a = n_b as epsilon -> 0, so residuals are in
+ * the plane metric's units, and W = n n^T would give the plane metric's row exactly.  Normals that agree make a point-to-plane
+ * pair; normals that disagree (an edge, a wrong correspondence, the rim of an overlap) leave a weak point-to-point pull.  Only
+ * n n^T enters: the SIGNS of the normals drop out.  epsilon = 1 gives W = I, the Gauss-Newton point-to-point step.
+ * A pair whose n_a or n_b has zero or non-finite length takes no part in the step and is not counted in K.  The normal
+ * equations have the plane metric's shape: the same 32-double row, 6 x 6 minimum-norm solve (OA_STAT_PLANE_RANK) and code
+ * after the step's matrix.  Pair weights (oa_set_robust with a fixed scale, oa_set_source_weights) take the residual
+ * s sqrt(e^T W e), s as under OA_METRIC_PLANE.  Under OA_METRIC_GICP, when a loop starts:
+ *   - with_scale != 0: OA_E_BAD_ARG; a shard of more than 8 388 608 points: OA_E_CAPACITY;
+ *   - a vertex-mode target without normals, or a source without normals: OA_E_STATE;
+ *   - oa_set_robust_auto switched on together with a loss: OA_E_STATE (the scale's selection knows the other two metrics only);
+ *   - multi-device contexts and the split-phase calls: OA_E_STATE, as under OA_METRIC_PLANE.
+ * Each refusal leaves the context usable.  oa_make_pairs, oa_nn_search, oa_kabsch*, oa_point_to_plane, oa_coarse_align do not
+ * look at the metric.
+ * oa_set_gicp: epsilon must be finite and in [1e-6, 1], else OA_E_BAD_ARG; default 1e-3 (the paper's).  It survives uploads and
+ * oa_set_matrices; changing it ends a running oa_iterate sequence, as oa_set_metric does. */
+int oa_set_gicp(oa_ctx *ctx, double epsilon);
+/* per-vertex source normals (align-local, n_verts x 3 float32, host; n_verts as given to oa_set_source) for OA_METRIC_GICP,
+ * without switching the normal-angle test on: the counterpart of oa_set_target_normals.  The array is the one oa_set_normals
+ * fills and the normal-angle test reads -- either call overwrites it, switching the test off keeps it, a new source upload
+ * forgets it.  Call after oa_set_source (OA_E_STATE otherwise); a wrong n_verts is OA_E_BAD_ARG.  Ends a running oa_iterate
+ * sequence, as oa_set_target_normals does.  Multi-device contexts route it to every child. */
+int oa_set_source_normals(oa_ctx *ctx, const float *src_normals, int64_t n_verts);
 /* vertex-mode targets: per-vertex normals (base-local, nt x 3 float32, host) for the plane metric, without switching the
  * normal-angle test on; a new target upload forgets them.  Normals given through oa_set_normals serve as well. */
 int oa_set_target_normals(oa_ctx *ctx, const float *tgt_normals, int64_t nt);
@@ -350,7 +382,7 @@ int oa_reset_seeds(oa_ctx *ctx);
                                        * workgroup dispatched mid-launch); 0 when that kernel did not run.  Multi-device context: its first device */
 #define OA_STAT_BRUTE_QUEUE_WGS     27   /* workgroups of the last k_nn_search_sorted launch that took their (split, block) items off the work
                                        * queue (long launches: as many as the chip holds); 0 = one workgroup per item, in launch order */
-#define OA_STAT_METRIC          28   /* OA_METRIC_POINT / OA_METRIC_PLANE */
+#define OA_STAT_METRIC          28   /* OA_METRIC_POINT / OA_METRIC_PLANE / OA_METRIC_GICP */
 #define OA_STAT_PLANE_RANK      29   /* eigenvalues the last plane solve kept (6 = fully determined); loop or oa_point_to_plane */
 #define OA_STAT_ROBUST_LOSS     30   /* OA_LOSS_* */
 #define OA_STAT_WEIGHT_SUM      31   /* sum w of the last step (loop or iterate); K when weighting is off */

@@ -29,6 +29,7 @@ OA_EXCHANGE_RCCL = 1
 OA_NSUMS = 24
 OA_METRIC_POINT = 0
 OA_METRIC_PLANE = 1
+OA_METRIC_GICP = 2
 OA_LOSS_NONE = 0
 OA_LOSS_HUBER = 1
 OA_LOSS_TUKEY = 2
@@ -52,6 +53,7 @@ SYMBOLS = [
     "oa_set_robust", "oa_set_source_weights", "oa_set_robust_auto",
     "oa_score_poses", "oa_coarse_candidates", "oa_coarse_align",
     "oa_target_knn", "oa_estimate_target_normals",
+    "oa_set_gicp", "oa_set_source_normals",
 ]
 
 
@@ -159,6 +161,8 @@ def load(experiments: bool = False):
     L.oa_run_end.argtypes = [vp, C.POINTER(Report)]
     L.oa_set_metric.argtypes = [vp, C.c_int]
     L.oa_set_target_normals.argtypes = [vp, fp, C.c_int64]
+    L.oa_set_gicp.argtypes = [vp, C.c_double]
+    L.oa_set_source_normals.argtypes = [vp, fp, C.c_int64]
     L.oa_point_to_plane.argtypes = [vp, dp, dp, dp, C.c_int64, C.c_int64, dp]
     L.oa_set_robust.argtypes = [vp, C.c_int, C.c_double]
     L.oa_set_source_weights.argtypes = [vp, fp, C.c_int64]

@@ -437,6 +437,7 @@ struct oa_ctx {
     bool normals_on = false;
     int last_plane_rank = 0;         // OA_STAT_PLANE_RANK: eigenvalues the last plane solve kept (loop or oa_point_to_plane)
     int metric = OA_METRIC_POINT;    // oa_set_metric: what the loop minimises (survives uploads and oa_set_matrices)
+    double gicp_eps = 1e-3;          // oa_set_gicp: the small eigenvalue of the GICP metric's covariances (survives uploads and oa_set_matrices)
     // weighted steps: a pair's weight is w_vertex * psi(residual).  Off (every weight 1, the unweighted kernels) unless set
     int loss = OA_LOSS_NONE;         // oa_set_robust (survives uploads and oa_set_matrices)
     double robust_c = 0.0;           // ... its scale, world units
@@ -876,6 +877,8 @@ struct SearchChoice {
 };
 // a loss or per-vertex weights are set: the loop's pairs carry weights (weighted kernels, the PLAIN plan)
 inline bool weighted(const oa_ctx *c) { return c->loss != OA_LOSS_NONE || c->d_w != nullptr; }
+// the metrics that sum the wide row (NSUMS_PLANE) and take the 6 x 6 solve: point-to-plane and plane-to-plane (GICP)
+inline bool plane_row_metric(const oa_ctx *c) { return c->metric == OA_METRIC_PLANE || c->metric == OA_METRIC_GICP; }
 // ... and the loss takes its scale from the step's own residuals (oa_set_robust_auto; inert without a loss)
 inline bool auto_scale(const oa_ctx *c) { return c->loss != OA_LOSS_NONE && c->robust_p > 0.0; }
 
@@ -893,9 +896,9 @@ SearchChoice choose_search(const oa_ctx *c)
         s.settle_front = c->surface && c->tri_fine_ok && c->seeded && !s.dual;
         s.accept_front = c->surface && c->tri_split && c->seeded && !s.dual;
     }
-    // (the plane metric has no accumulating search epilogue: search, then k_pair_accumulate_plane -- as with fused_acc off;
-    //  nor does a weighted step: no search epilogue knows about weights)
-    if (!c->fused_acc || !c->loop_active || c->ns <= 0 || c->metric == OA_METRIC_PLANE || weighted(c)) return s;
+    // (the plane and GICP metrics have no accumulating search epilogue: search, then k_pair_accumulate_plane / _gicp -- as with
+    //  fused_acc off; nor does a weighted step: no search epilogue knows about weights)
+    if (!c->fused_acc || !c->loop_active || c->ns <= 0 || plane_row_metric(c) || weighted(c)) return s;
     // (the accumulating tree search needs twice the registers of the plain one: worth it while the shard is small enough
     //  that occupancy does not matter -- 12k queries against 1M vertices: 58 us fused, 47 us search + accumulate)
     if (s.kind == SEARCH_TREE) s.plan = c->ns <= c->tree_acc_max ? PLAN_TREE : PLAN_PLAIN;
@@ -1131,6 +1134,14 @@ int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
                            (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
                            c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n,
                            (const float *)c->d_w, c->d_partials, stamp);
+    } else if (c->metric == OA_METRIC_GICP) {
+        // (begin_loop refuses an estimated scale under this metric: the search always ends here)
+        unsigned long long *stamp = c->loop_active ? &c->d_state->t_acc_start : (unsigned long long *)nullptr;
+        auto *kern = weighted(c) ? oa::k_pair_accumulate_gicp<true> : oa::k_pair_accumulate_gicp<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
+                           (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
+                           c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n,
+                           (const float *)c->d_src_n, (const float *)c->d_w, c->d_partials, stamp);
     } else if (weighted(c)) {
         unsigned long long *stamp = c->loop_active && !auto_scale(c) ? &c->d_state->t_acc_start : (unsigned long long *)nullptr;
         static_assert(oa::WEIGHTED_THREADS == oa::PLANE_THREADS, "plane_threads / plane_blocks size both launches");
@@ -1179,7 +1190,7 @@ int launch_robust_scale(oa_ctx *c)
 // rows the (non-emitting) accumulation of this context leaves for the reduce launch when it is its own kernel
 inline oa::RowSel plain_rows(const oa_ctx *c)
 {
-    if (c->metric == OA_METRIC_PLANE || weighted(c)) return oa::RowSel{ plane_blocks(c), 0, 0 };
+    if (plane_row_metric(c) || weighted(c)) return oa::RowSel{ plane_blocks(c), 0, 0 };
     const int cb = canon_blocks(c);
     return oa::RowSel{ cb > 0 ? cb : c->acc_blocks, 0, 0 };
 }
@@ -1334,6 +1345,7 @@ void init_loop_state(oa_ctx *c, const oa_settings *st, int iters, bool cutoff = 
         s.res_scale = cbrt(fabs(det));
     }
     s.weight_sum = 0.0;
+    s.gicp_eps = c->gicp_eps;
     // the scale from the residuals: robust_c is then the multiplier, and k_select_scan writes the scale before every accumulation
     const bool auto_c = auto_scale(c);
     s.robust_mult = auto_c ? c->robust_c : 0.0;
@@ -1359,6 +1371,16 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
             return fail(OA_E_STATE, "the plane metric needs target normals: call oa_set_target_normals (or oa_set_normals) after oa_set_target, or upload a mesh with oa_set_target_mesh");
         if ((long long)c->ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
             return fail(OA_E_CAPACITY, "the plane metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->ns);
+    } else if (c->metric == OA_METRIC_GICP) {
+        if (st->with_scale) return fail(OA_E_BAD_ARG, "the GICP metric solves for a rigid step: with_scale must be 0 (or call oa_set_metric(ctx, OA_METRIC_POINT))");
+        if (!c->surface && !c->d_tgt_n)
+            return fail(OA_E_STATE, "the GICP metric needs target normals: call oa_set_target_normals (or oa_set_normals) after oa_set_target, or upload a mesh with oa_set_target_mesh");
+        if (!c->d_src_n)
+            return fail(OA_E_STATE, "the GICP metric needs source normals: call oa_set_source_normals (or oa_set_normals) after oa_set_source");
+        if (auto_scale(c))
+            return fail(OA_E_STATE, "the GICP metric takes a robust loss with a fixed scale only: call oa_set_robust_auto(ctx, 0, 0) (or oa_set_metric(ctx, OA_METRIC_PLANE))");
+        if ((long long)c->ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
+            return fail(OA_E_CAPACITY, "the GICP metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->ns);
     } else if (weighted(c) && (long long)c->ns > (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS)
         return fail(OA_E_CAPACITY, "a weighted loop takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS, c->ns);
     if ((rc = use_device(c))) return rc;
@@ -1417,7 +1439,7 @@ int iter_fused(oa_ctx *c, bool timed)
     bool fused;
     const int rc = launch_search_accumulate(c, timed, sel, fused);
     if (rc) return rc;
-    if (c->metric == OA_METRIC_PLANE)
+    if (plane_row_metric(c))
         hipLaunchKernelGGL(oa::k_reduce_solve_update_plane, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, c->d_state,
                            (const double *)c->d_partials, sel.n, c->d_sums, c->d_hist, c->d_todo_count);
     else
@@ -1432,7 +1454,7 @@ int fetch_state(oa_ctx *c)
     HIPCHK(hipMemcpyAsync(c->h_state_pin, c->d_state, sizeof(oa::DevState), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->h_state = *c->h_state_pin;
-    if (c->metric == OA_METRIC_PLANE && c->h_state.n > 0) c->last_plane_rank = c->h_state.plane_rank;
+    if (plane_row_metric(c) && c->h_state.n > 0) c->last_plane_rank = c->h_state.plane_rank;
     if (c->h_state.n > 0) c->last_weight_sum = c->h_state.weight_sum;
     if (c->h_state.n > 0) c->last_robust_c = c->h_state.robust_c;
     return OA_OK;
@@ -3608,7 +3630,8 @@ OA_EXPORT int oa_set_normals(oa_ctx *c, const float *src_normals, int64_t n_vert
 OA_EXPORT int oa_set_metric(oa_ctx *c, int metric)
 {
     if (!c) return fail(OA_E_BAD_ARG, "null context");
-    if (metric != OA_METRIC_POINT && metric != OA_METRIC_PLANE) return fail(OA_E_BAD_ARG, "metric %d (use OA_METRIC_POINT / OA_METRIC_PLANE)", metric);
+    if (metric != OA_METRIC_POINT && metric != OA_METRIC_PLANE && metric != OA_METRIC_GICP)
+        return fail(OA_E_BAD_ARG, "metric %d (use OA_METRIC_POINT / OA_METRIC_PLANE / OA_METRIC_GICP)", metric);
     if (metric == c->metric) return OA_OK;
     // a changed metric ends the running sequence: the next oa_iterate starts a new one from the current matrix_world
     if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
@@ -3620,6 +3643,24 @@ OA_EXPORT int oa_set_metric(oa_ctx *c, int metric)
     }
     c->metric = metric;
     OA_ROUTE_ALL(c, oa_set_metric(sub, metric));
+    return OA_OK;
+}
+
+OA_EXPORT int oa_set_gicp(oa_ctx *c, double epsilon)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    if (!(epsilon >= 1e-6 && epsilon <= 1.0)) return fail(OA_E_BAD_ARG, "oa_set_gicp: epsilon must be finite and in [1e-6, 1]");
+    if (epsilon == c->gicp_eps) return OA_OK;
+    // a changed setting ends the running sequence, as a changed metric does
+    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
+    else if (c->loop_active) {
+        int rc = use_device(c);
+        if (rc) return rc;
+        if ((rc = fetch_state(c))) return rc;
+        c->loop_active = false;
+    }
+    c->gicp_eps = epsilon;
+    OA_ROUTE_ALL(c, oa_set_gicp(sub, epsilon));
     return OA_OK;
 }
 
@@ -3718,6 +3759,29 @@ OA_EXPORT int oa_set_target_normals(oa_ctx *c, const float *tgt_normals, int64_t
     if (c->normals_on) HIPCHK(hipStreamSynchronize(c->stream));    // (the array the normal-angle test reads is replaced in place)
     if (!c->d_tgt_n) HIPCHK(dev_malloc(&c->d_tgt_n, sizeof(float) * 3 * (size_t)nt));
     HIPCHK(hipMemcpyAsync(c->d_tgt_n, tgt_normals, sizeof(float) * 3 * (size_t)nt, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
+OA_EXPORT int oa_set_source_normals(oa_ctx *c, const float *src_normals, int64_t n_verts)
+{
+    if (!c || !src_normals) return fail(OA_E_BAD_ARG, "oa_set_source_normals: null argument");
+    if (!c->subs.empty() && c->loop_active) multi_abort(c);
+    OA_ROUTE_ALL_PAR(c, oa_set_source_normals(sub, src_normals, n_verts));      // every child gathers its own shard
+    if (!c->d_src4 || !c->d_sel) return fail(OA_E_STATE, "oa_set_source_normals: call oa_set_source first");
+    if (n_verts != c->src_n_verts) return fail(OA_E_BAD_ARG, "oa_set_source_normals: %lld source normals for %lld vertices", (long long)n_verts, c->src_n_verts);
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (c->loop_active) { HIPCHK(hipStreamSynchronize(c->stream)); c->loop_active = false; }
+    if (c->normals_on) HIPCHK(hipStreamSynchronize(c->stream));    // (the array the normal-angle test reads is replaced in place)
+    DevTmp<float> tmp;
+    HIPCHK(tmp.alloc(3 * (size_t)std::max<int64_t>(1, n_verts)));
+    HIPCHK(hipMemcpyAsync(tmp, src_normals, sizeof(float) * 3 * (size_t)n_verts, hipMemcpyHostToDevice, c->stream));
+    if (!c->d_src_n) HIPCHK(dev_malloc(&c->d_src_n, sizeof(float) * 3 * (size_t)std::max(1, c->ns)));
+    if (c->ns > 0)
+        hipLaunchKernelGGL(oa::k_gather_rows3, dim3((c->ns + 255) / 256), dim3(256), 0, c->stream, (const float *)tmp.p,
+                           (const int *)c->d_sel, c->ns, c->d_src_n);
+    HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     return OA_OK;
 }
@@ -4329,6 +4393,7 @@ int run_begin(oa_ctx *c, const oa_settings *st)
     return OA_OK;
 }
 // the exchange of the sums between devices and ranks carries OA_NSUMS doubles: the plane metric's wider row does not go through it
+const char *const GICP_ONE_DEVICE = ": the GICP metric runs on a single-device context through oa_run / oa_iterate (call oa_set_metric(ctx, OA_METRIC_POINT) for this path)";
 const char *const PLANE_ONE_DEVICE = ": the plane metric runs on a single-device context through oa_run / oa_iterate (call oa_set_metric(ctx, OA_METRIC_POINT) for this path)";
 // ... and a quantile of the world's residuals needs the world's histogram, not OA_NSUMS doubles
 const char *const AUTO_ONE_DEVICE = ": a robust scale estimated from the residuals runs on a single-device context through oa_run / oa_iterate (call oa_set_robust_auto(ctx, 0, 0) for this path)";
@@ -4339,6 +4404,7 @@ OA_EXPORT int oa_run_begin(oa_ctx *c, const oa_settings *st)
     if (!c || !st) return fail(OA_E_BAD_ARG, "oa_run_begin: null argument");
     OA_NOT_MULTI(c, "oa_run_begin (the split-phase loop is for one process per GPU)");
     if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_run_begin%s", PLANE_ONE_DEVICE);
+    if (c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "oa_run_begin%s", GICP_ONE_DEVICE);
     if (auto_scale(c)) return fail(OA_E_STATE, "oa_run_begin%s", AUTO_ONE_DEVICE);
     return run_begin(c, st);
 }
@@ -4348,6 +4414,7 @@ OA_EXPORT int oa_iter_partial(oa_ctx *c, double *d_sums)
     if (!c || !d_sums) return fail(OA_E_BAD_ARG, "oa_iter_partial: null argument");
     OA_NOT_MULTI(c, "oa_iter_partial");
     if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_iter_partial%s", PLANE_ONE_DEVICE);
+    if (c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "oa_iter_partial%s", GICP_ONE_DEVICE);
     if (auto_scale(c)) return fail(OA_E_STATE, "oa_iter_partial%s", AUTO_ONE_DEVICE);
     if (!c->loop_active) return fail(OA_E_STATE, "oa_iter_partial outside oa_run_begin/oa_run_end");
     int rc = use_device(c);
@@ -4360,6 +4427,7 @@ OA_EXPORT int oa_iter_finish(oa_ctx *c, const double *d_sums)
     if (!c || !d_sums) return fail(OA_E_BAD_ARG, "oa_iter_finish: null argument");
     OA_NOT_MULTI(c, "oa_iter_finish");
     if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_iter_finish%s", PLANE_ONE_DEVICE);
+    if (c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "oa_iter_finish%s", GICP_ONE_DEVICE);
     if (!c->loop_active) return fail(OA_E_STATE, "oa_iter_finish outside oa_run_begin/oa_run_end");
     int rc = use_device(c);
     if (rc) return rc;
@@ -4384,6 +4452,7 @@ OA_EXPORT int oa_run(oa_ctx *c, const oa_settings *st, oa_report *rep)
 {
     if (!c || !st || !rep) return fail(OA_E_BAD_ARG, "oa_run: null argument");
     if (!c->subs.empty() && c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_run on a multi-device context%s", PLANE_ONE_DEVICE);
+    if (!c->subs.empty() && c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "oa_run on a multi-device context%s", GICP_ONE_DEVICE);
     if (!c->subs.empty() && auto_scale(c)) return fail(OA_E_STATE, "oa_run on a multi-device context%s", AUTO_ONE_DEVICE);
     if (!c->subs.empty()) return multi_run(c, st, rep);
     int rc = run_begin(c, st);
@@ -4431,6 +4500,7 @@ OA_EXPORT int oa_iterate(oa_ctx *c, const oa_settings *st, double M_step[16], do
     if (!c || !st) return fail(OA_E_BAD_ARG, "oa_iterate: null argument");
     const bool multi = !c->subs.empty();
     if (multi && c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_iterate on a multi-device context%s", PLANE_ONE_DEVICE);
+    if (multi && c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "oa_iterate on a multi-device context%s", GICP_ONE_DEVICE);
     if (multi && auto_scale(c)) return fail(OA_E_STATE, "oa_iterate on a multi-device context%s", AUTO_ONE_DEVICE);
     int rc;
     if (c->loop_active && !(c->iterate_mode && same_loop_settings(*st, c->settings))) {

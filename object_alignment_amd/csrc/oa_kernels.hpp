@@ -37,6 +37,8 @@ constexpr int S_A = 0, S_B = 3, S_H = 6, S_AA = 15, S_BB = 16, S_K = 17, S_D = 1
 //   [0..20] sum J J^T, upper triangle by rows ((0,0) (0,1) .. (0,5) (1,1) .. (5,5))   [21..26] sum J r   [27] K
 //   [28] sum (d - d_pivot)   [29] sum (d - d_pivot)^2   [30] sum r^2   [31] sum w (0 unless weighted)
 // Weighted steps: [0..26] are sums of w J J^T and w J r; [27..30] stay unweighted.
+// The plane-to-plane metric (Generalized-ICP; OA_METRIC_GICP) fills the same row from J = [-[a']x, I3] (3 x 6), e = a' - b' and
+// the pair's 3 x 3 weight W: [0..20] sum w J^T W J, [21..26] sum w J^T W e, [30] sum e^T W e; W = n n^T is the plane row exactly.
 constexpr int NSUMS_PLANE = 32;
 constexpr int P_JJ = 0, P_JR = 21, P_K = 27, P_D = 28, P_DD = 29, P_RR = 30, P_W = 31;
 
@@ -128,6 +130,7 @@ struct DevState {
     uint32_t sel_prefix;      // radix select, between its launches: the key's leading bits found so far ...
     uint32_t sel_rank;        // ... and the 0-based rank wanted among the keys that share them
     uint32_t pad3;
+    double gicp_eps;          // GICP metric (oa_set_gicp): the covariances' small eigenvalue, C = I - (1 - eps) n n^T; set when the loop starts
 };
 
 // Squared local search radius for the query p (rounded up to float).  Derivation: the pair test measures
@@ -2579,6 +2582,164 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_plane(const D
         block_store_plane<true>(valid, j, r, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE, w);
     } else
     block_store_plane(valid, j, r, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE);
+}
+#endif  // !OA_FAMILY_TU
+
+// ---- the plane-to-plane metric (Generalized-ICP, Segal et al. 2009; oa_set_metric(OA_METRIC_GICP)) ---------------------------
+// A pair is weighted by W = 2 eps M^-1, M = C_a + C_b = 2 I - (1 - eps)(n_a n_a^T + n_b n_b^T): the regularised covariances of
+// the paper (eigenvalues 1, 1, eps, the eps-axis along the normal) of both sides, both in align-local space.  M is symmetric
+// with eigenvalues in [2 eps, 2]: adjugate over determinant, ONE division.  The factor 2 eps does not move the step; with it
+// e^T W e -> (n . e)^2 for n_a = n_b as eps -> 0, the plane metric's residual.  Only n n^T enters: the normals' signs drop out.
+// na, nb unit.  W: (0,0) (0,1) (0,2) (1,1) (1,2) (2,2).
+__device__ __forceinline__ void gicp_weight(double eps, double ax, double ay, double az, double bx, double by, double bz, double (&W)[6])
+{
+    const double k = 1.0 - eps;
+    const double m00 = 2.0 - k * (ax * ax + bx * bx), m01 = -k * (ax * ay + bx * by), m02 = -k * (ax * az + bx * bz);
+    const double m11 = 2.0 - k * (ay * ay + by * by), m12 = -k * (ay * az + by * bz), m22 = 2.0 - k * (az * az + bz * bz);
+    const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
+    const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+    const double det = (m00 * c00 + m01 * c01) + m02 * c02;
+    const double s = (2.0 * eps) / det;
+    W[0] = s * c00; W[1] = s * c01; W[2] = s * c02; W[3] = s * c11; W[4] = s * c12; W[5] = s * c22;
+}
+
+// row i of C = [a]x W (the upper right block of J^T W J: column k of C is a x W_k)
+__device__ __forceinline__ void gicp_c_row(int i, double a0, double a1, double a2, const double (&W)[6], double (&c)[3])
+{
+    if (i == 0)      { c[0] = a1 * W[2] - a2 * W[1]; c[1] = a1 * W[4] - a2 * W[3]; c[2] = a1 * W[5] - a2 * W[4]; }
+    else if (i == 1) { c[0] = a2 * W[0] - a0 * W[2]; c[1] = a2 * W[1] - a0 * W[4]; c[2] = a2 * W[2] - a0 * W[5]; }
+    else             { c[0] = a0 * W[1] - a1 * W[0]; c[1] = a0 * W[3] - a1 * W[1]; c[2] = a0 * W[4] - a1 * W[2]; }
+}
+
+// block_store_plane for this metric.  The row is not rank one, so the 21 + 6 terms are formed from a', W and u = W e inside
+// each slice (the upper left block of J^T W J: row i is a x (row i of C)); what stays live across the slices is a', W, u and
+// four scalars -- never 32 sums and the butterfly's temporaries at once.  rr = e^T W e; w: as in block_store_plane.
+template <bool WEIGHTED>
+__device__ __forceinline__ void block_store_gicp(bool valid, double a0, double a1, double a2, const double (&Wp)[6], double u0, double u1,
+                                                 double u2, double rr, double dd, double (*red)[NSUMS_PLANE], double *__restrict__ row,
+                                                 double w = 0.0)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double W[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) W[k] = valid ? Wp[k] : 0.0;
+    if (!valid) { a0 = a1 = a2 = 0.0; u0 = u1 = u2 = 0.0; rr = 0.0; dd = 0.0; w = 0.0; }
+    {
+        double h[12], c0[3], c1[3], c2[3];
+        gicp_c_row(0, a0, a1, a2, W, c0);
+        gicp_c_row(1, a0, a1, a2, W, c1);
+        gicp_c_row(2, a0, a1, a2, W, c2);
+        h[0] = a1 * c0[2] - a2 * c0[1]; h[1] = a2 * c0[0] - a0 * c0[2]; h[2] = a0 * c0[1] - a1 * c0[0];      // (0,0) (0,1) (0,2)
+        h[3] = c0[0]; h[4] = c0[1]; h[5] = c0[2];                                                            // (0,3) (0,4) (0,5)
+        h[6] = a2 * c1[0] - a0 * c1[2]; h[7] = a0 * c1[1] - a1 * c1[0];                                      // (1,1) (1,2)
+        h[8] = c1[0]; h[9] = c1[1]; h[10] = c1[2];                                                           // (1,3) (1,4) (1,5)
+        h[11] = a0 * c2[1] - a1 * c2[0];                                                                     // (2,2)
+        if constexpr (WEIGHTED) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) h[k] *= w;
+        }
+        wave_reduce_scatter<12>(h, lane, &red[wave][0]);
+    }
+    {
+        double h[12], c2[3];
+        gicp_c_row(2, a0, a1, a2, W, c2);
+        h[0] = c2[0]; h[1] = c2[1]; h[2] = c2[2];                                                            // (2,3) (2,4) (2,5)
+        h[3] = W[0]; h[4] = W[1]; h[5] = W[2]; h[6] = W[3]; h[7] = W[4]; h[8] = W[5];                        // (3,3) .. (5,5)
+        h[9] = a1 * u2 - a2 * u1; h[10] = a2 * u0 - a0 * u2; h[11] = a0 * u1 - a1 * u0;                      // a' x u
+        if constexpr (WEIGHTED) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) h[k] *= w;
+        }
+        wave_reduce_scatter<12>(h, lane, &red[wave][12]);
+    }
+    {
+        double h[8] = { u0, u1, u2, valid ? 1.0 : 0.0, dd, dd * dd, rr, 0.0 };
+        if constexpr (WEIGHTED) { h[0] *= w; h[1] *= w; h[2] *= w; h[7] = w; }
+        wave_reduce_scatter<8>(h, lane, &red[wave][24]);
+    }
+    block_finish_plane(red, row);
+}
+
+// k_pair_accumulate_plane for this metric: the same reads and resets, the same pair test and plane_normal for n_b, plus the
+// slot's source normal (src_n: float32, align-local, slot order; normalised in fp64 in plane_normal's order, n * (1 / sqrt(n2));
+// zero or non-finite length drops the pair from the step and from K, as a zero n_b does).  Launched like the plane kernel
+// (plane_threads / plane_blocks).  WEIGHTED: w = w_vertex * psi(res_scale * sqrt(e^T W e)).
+#if !defined(OA_FAMILY_TU)
+template <bool WEIGHTED>
+__global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_gicp(const DevState *__restrict__ st, const float4 *__restrict__ src4,
+                                                              int ns, const float *__restrict__ tgt_xyz,
+                                                              unsigned long long *__restrict__ keys, int *__restrict__ prev,
+                                                              float4 *__restrict__ win, const float4 *__restrict__ tri9,
+                                                              NormalTest nrm, const float *__restrict__ plane_tn,
+                                                              const float *__restrict__ src_n, const float *__restrict__ w_slot,
+                                                              double *__restrict__ partials, unsigned long long *__restrict__ t_acc_start)
+{
+    __shared__ double red[PLANE_THREADS / 64][NSUMS_PLANE];
+    if (t_acc_start && blockIdx.x == 0 && threadIdx.x == 0) *t_acc_start = wall_clock64();   // ~ the end of the search
+    if (st->halt) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool valid = false;
+    float bx = 0.f, by = 0.f, bz = 0.f;
+    double dist = 0.0, nx = 0.0, ny = 0.0, nz = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (i < ns) {
+        const unsigned long long key = keys[i];
+        keys[i] = KEY_EMPTY;                                       // ready for the next iteration's atomicMin
+        const uint32_t idx = (uint32_t)key;
+        if (prev) prev[i] = (idx == IDX_NONE) ? -1 : (int)idx;
+        p = src4[i];
+        float4 wrec = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+        if (win) wrec = win[i];
+        if (idx != IDX_NONE) {
+            float cx, cy, cz;
+            co_find(st, p.x, p.y, p.z, cx, cy, cz);           // co_find                   (general.py:287)
+            float qx, qy, qz;
+            float tn[3];
+            if (tri9) {
+                float ta[3], tb[3], tc[3], rr[3];
+                const float cf[3] = { cx, cy, cz };
+                load_tri(tri9, idx, ta, tb, tc);
+                closest_on_tri(cf, ta, tb, tc, rr);
+                qx = rr[0]; qy = rr[1]; qz = rr[2];
+                const float e1[3] = { ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2] };
+                const float e2[3] = { tb[0] - tc[0], tb[1] - tc[1], tb[2] - tc[2] };
+                tn[0] = e1[1] * e2[2] - e1[2] * e2[1];
+                tn[1] = e1[2] * e2[0] - e1[0] * e2[2];
+                tn[2] = e1[0] * e2[1] - e1[1] * e2[0];
+            } else {
+                if ((uint32_t)__float_as_int(wrec.w) == idx) { qx = wrec.x; qy = wrec.y; qz = wrec.z; }
+                else {
+                    qx = tgt_xyz[3ll * idx]; qy = tgt_xyz[3ll * idx + 1]; qz = tgt_xyz[3ll * idx + 2];
+                    if (win) win[i] = make_float4(qx, qy, qz, __int_as_float((int)idx));
+                }
+                tn[0] = plane_tn[3ll * idx]; tn[1] = plane_tn[3ll * idx + 1]; tn[2] = plane_tn[3ll * idx + 2];
+            }
+            valid = pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, tn, st->thresh, bx, by, bz, dist);
+            if (valid) valid = plane_normal(st, tn, nx, ny, nz);
+            if (valid) {
+                const double s0 = (double)src_n[3ll * i], s1 = (double)src_n[3ll * i + 1], s2 = (double)src_n[3ll * i + 2];
+                const double n2 = (s0 * s0 + s1 * s1) + s2 * s2;
+                valid = (n2 > 0.0) && (n2 < INFINITY);
+                const double inv = 1.0 / sqrt(n2);
+                sx = s0 * inv; sy = s1 * inv; sz = s2 * inv;
+            }
+        }
+    }
+    const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
+    const double a0 = (double)p.x - pvx, a1 = (double)p.y - pvy, a2 = (double)p.z - pvz;
+    const double e0 = a0 - ((double)bx - pvx), e1 = a1 - ((double)by - pvy), e2 = a2 - ((double)bz - pvz);
+    double W[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    if (valid) gicp_weight(st->gicp_eps, sx, sy, sz, nx, ny, nz, W);
+    const double u0 = (W[0] * e0 + W[1] * e1) + W[2] * e2, u1 = (W[1] * e0 + W[3] * e1) + W[4] * e2, u2 = (W[2] * e0 + W[4] * e1) + W[5] * e2;
+    const double rr = (e0 * u0 + e1 * u1) + e2 * u2;
+    double w = 0.0;
+    if constexpr (WEIGHTED) {
+        if (valid) {
+            w = robust_psi(st->loss, st->res_scale * sqrt(fmax(rr, 0.0)), st->robust_c);
+            if (w_slot) w *= (double)w_slot[i];
+        }
+    }
+    block_store_gicp<WEIGHTED>(valid, a0, a1, a2, W, u0, u1, u2, rr, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE, w);
 }
 #endif  // !OA_FAMILY_TU
 

@@ -176,15 +176,16 @@ class IcpEngine:
         self._chk(self._L.oa_set_normals(self._h, capi.fptr(sn), len(sn), capi.fptr(tn) if tn is not None else None,
                                           len(tn) if tn is not None else 0, float(max_angle_deg)))
 
-    METRICS = {"point": capi.OA_METRIC_POINT, "plane": capi.OA_METRIC_PLANE}
+    METRICS = {"point": capi.OA_METRIC_POINT, "plane": capi.OA_METRIC_PLANE, "gicp": capi.OA_METRIC_GICP}
 
     def set_metric(self, metric):
-        """What a loop step minimises: 'point' (Besl-McKay, the reference's loop, default) or 'plane' (Chen-Medioni: the distance
-        to the tangent plane at the correspondence; single-device contexts, run() / iterate(), no scale).  Survives uploads
-        and set_matrices; stat("metric") reads it back."""
+        """What a loop step minimises: 'point' (Besl-McKay, the reference's loop, default), 'plane' (Chen-Medioni: the distance
+        to the tangent plane at the correspondence) or 'gicp' (plane-to-plane, Generalized-ICP: every pair weighted by both sides'
+        normals -- needs set_source_normals, see set_gicp); the last two on single-device contexts, run() / iterate(), no scale.
+        Survives uploads and set_matrices; stat("metric") reads it back."""
         if isinstance(metric, str):
             if metric not in self.METRICS:
-                raise ValueError("metric %r (use 'point' or 'plane')" % (metric,))
+                raise ValueError("metric %r (use 'point', 'plane' or 'gicp')" % (metric,))
             metric = self.METRICS[metric]
         self._chk(self._L.oa_set_metric(self._h, int(metric)))
 
@@ -193,6 +194,17 @@ class IcpEngine:
         it is).  Call after set_target; a new target upload forgets them."""
         tn = capi.as_f32(tgt_normals).reshape(-1, 3)
         self._chk(self._L.oa_set_target_normals(self._h, capi.fptr(tn), len(tn)))
+
+    def set_gicp(self, epsilon=1e-3):
+        """The 'gicp' metric's epsilon: the small eigenvalue of each side's covariance I - (1 - epsilon) n n^T, in [1e-6, 1]
+        (1e-3: the paper's; 1 makes the step the Gauss-Newton point-to-point one).  Survives uploads and set_matrices."""
+        self._chk(self._L.oa_set_gicp(self._h, float(epsilon)))
+
+    def set_source_normals(self, src_normals):
+        """One align-local normal per source vertex (the array uploaded with set_source, not the selection), for the 'gicp'
+        metric; the normal-angle test stays as it is.  Call after set_source; a new source upload forgets them."""
+        sn = capi.as_f32(src_normals).reshape(-1, 3)
+        self._chk(self._L.oa_set_source_normals(self._h, capi.fptr(sn), len(sn)))
 
     ORIENTS = {"none": capi.OA_ORIENT_NONE, "toward": capi.OA_ORIENT_TOWARD, "away": capi.OA_ORIENT_AWAY}
 

@@ -40,7 +40,10 @@ class IcpSettings:
     # not a preference of the reference either (its citation.txt names both papers, its loop implements the first): what a
     # step minimises -- "point": the distance to the correspondence (Besl-McKay, the reference's loop); "plane": the distance
     # to the tangent plane at the correspondence (Chen-Medioni; rigid only, one GPU), which lets a surface slide along itself
+    # "gicp": plane-to-plane (Generalized-ICP; rigid only, one GPU): every pair weighted by the normals of both sides -- needs
+    # run(..., source_normals=...); gicp_epsilon is the small eigenvalue of its covariances, in [1e-6, 1]
     metric: str = "point"
+    gicp_epsilon: float = 1e-3
     # nor these: the weight of a pair in a step is a robust loss of its residual -- "none" (every pair weighs one, the
     # reference's loop), "huber", "tukey" or "cauchy" with the fixed scale robust_scale in world units, like min_start --
     # so that scan noise, a blob of wax or the rim of a partial overlap inside min_start pulls less than a good pair
@@ -83,6 +86,9 @@ def apply_metric(engine, settings) -> None:
         setter(metric)
     elif metric != "point":
         raise RuntimeError("this engine has no %r metric" % metric)
+    setter = getattr(engine, "set_gicp", None)
+    if metric == "gicp" and setter is not None:
+        setter(float(getattr(settings, "gicp_epsilon", 1e-3)))
 
 
 def robust_of(settings):
@@ -198,13 +204,16 @@ class IcpAlign:
         self._engine = engine
 
     def run(self, source_xyz, target_xyz, mx_align, mx_base, vlist=None, early_exit=True,
-            target_tris=None, target_normals=None, source_weights=None, coarse=None) -> RunResult:
+            target_tris=None, target_normals=None, source_weights=None, coarse=None, source_normals=None) -> RunResult:
         """target_tris: (n, 3) triangles of the base mesh -> closest point on the surface (the reference's BVH
         semantics); None -> nearest target vertex (point-cloud targets, BASELINE's configurations).
         target_normals: one normal per target vertex -- what settings.metric == "plane" needs of a point-cloud target -- or
         "estimate": PCA normals from every target vertex's settings.normal_k nearest neighbours, computed on the device after
         the upload and oriented away from the target's centroid (point-cloud targets only: a mesh has its triangles').
         source_weights: one weight per vertex of source_xyz (finite, >= 0) -- "trust this region less"; None = all one.
+        source_normals: one align-local normal per vertex of source_xyz -- what settings.metric == "gicp" needs -- or "estimate":
+        object_alignment_amd.estimate_normals(source_xyz, k=settings.normal_k), in a context of its own (that metric does not
+        look at the normals' signs, so they are left unoriented).
         coarse: a CoarseSettings (operators/coarse_align.py) -- the coarse global stage runs on the same engine in front of the
         loop, which then starts from the pose it found (self.last_coarse holds its report); None: the loop alone."""
         s = self.settings
@@ -213,6 +222,8 @@ class IcpAlign:
             raise ValueError("target_normals %r (an array of normals, or 'estimate')" % (target_normals,))
         if estimate and target_tris is not None:
             raise ValueError("target_normals='estimate' is for point-cloud targets: a mesh (target_tris) uses its triangles' normals")
+        if isinstance(source_normals, str) and source_normals != "estimate":
+            raise ValueError("source_normals %r (an array of normals, or 'estimate')" % (source_normals,))
         thresh = s.min_start                                   # :83
         factor = round(1 / s.sample_fraction)                  # :89  (ZeroDivisionError at 0, as the reference)
         if not thresh > 0:
@@ -232,6 +243,11 @@ class IcpAlign:
         eng.set_source(source_xyz, vlist=vlist, stride=factor)
         if source_weights is not None:
             eng.set_source_weights(source_weights)
+        if isinstance(source_normals, str):
+            from .. import estimate_normals
+            source_normals = estimate_normals(source_xyz, k=int(getattr(s, "normal_k", 16)))[0]
+        if source_normals is not None:
+            eng.set_source_normals(source_normals)
         eng.set_matrices(mx_align, mx_base)
         self.last_coarse = None
         if coarse is not None:
