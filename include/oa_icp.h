@@ -388,6 +388,8 @@ int oa_reset_seeds(oa_ctx *ctx);
 #define OA_STAT_WEIGHT_SUM      31   /* sum w of the last step (loop or iterate); K when weighting is off */
 #define OA_STAT_ROBUST_SCALE    32   /* the c the last step used: oa_set_robust's scale, or c_i of oa_set_robust_auto; 0 with OA_LOSS_NONE */
 #define OA_STAT_ROBUST_QUANTILE 33   /* oa_set_robust_auto's quantile (0 = off) */
+#define OA_STAT_TARGET_NORMALS  34   /* 1 when a vertex-mode target has normals installed (oa_set_target_normals, oa_set_normals, an estimate) */
+#define OA_STAT_TARGET_FEATURES 35   /* 1 when oa_target_fpfh(keep) left descriptors resident */
 #define OA_STAT_ENQUEUED_CHILD  1000   /* + i: the same count for child i alone */
 int oa_get_stat(oa_ctx *ctx, int what, double *value);
 /* why the exchange is what it is (AUTO's reason for not taking RCCL, librccl's error, "RCCL was aborted: ..."), or "" */
@@ -514,6 +516,74 @@ typedef struct oa_coarse_report {
  * running oa_iterate sequence, as oa_set_matrices does.  Single-device contexts (else OA_E_STATE); OA_E_BAD_THRESH for
  * thresh <= 0, OA_E_BAD_ARG for n_rot outside 1 .. 65536, n_refine outside 1 .. 4096, refine_iters outside 0 .. 10000. */
 int oa_coarse_align(oa_ctx *ctx, const oa_coarse_settings *cs, oa_coarse_report *rep);
+/* The recipe of oa_coarse_align with the candidates supplied instead of generated: mx_align (n_poses x 16 float32, host; 1 ..
+ * 65535 of them, every entry finite) plus the incoming pose -> one scoring launch -> the n_refine best -> refine_iters x (score,
+ * solve) -> rescore -> matrix_world = the lowest cost, or the incoming pose when nothing beats it.  cs->n_rot is ignored;
+ * rep->n_candidates = n_poses, and best_candidate = n_poses names the incoming pose.  Fed oa_coarse_candidates(n)'s output it
+ * leaves the bits oa_coarse_align(n_rot = n) leaves.  Everything else as oa_coarse_align. */
+int oa_coarse_align_poses(oa_ctx *ctx, const float *mx_align /* n_poses x 16, host */, int32_t n_poses,
+                          const oa_coarse_settings *cs, oa_coarse_report *rep);
+
+/* ---- EXTENSION: candidate poses from matched descriptors, for sources that are a PART of the target (their centroids are far
+ *      apart: no rotation about the centroid is near the answer) -- DESIGN.md 3.14.  The matching takes any local shape
+ *      descriptor of up to 64 floats per vertex; the library's own is FPFH (33). ------------------------------------------------- */
+/* Fast Point Feature Histograms (Rusu, Blodow & Beetz 2009) of the resident vertex-mode target: out (nt x 33 float32, host, may
+ * be NULL), from every vertex's k nearest neighbours in the order of oa_target_knn (4 <= k <= min(64, nt)) and the target's
+ * normals (oa_set_target_normals, oa_set_normals or an installed estimate; OA_E_STATE without them, on a surface target and on
+ * a multi-device context).  fp64 arithmetic, sums in list order, one rounding to float32:
+ *   pair feature of vertex p (normal n_p) and list neighbour q != p (normal n_q): d = q - p, l = |d|; skipped when l = 0 or not
+ *     finite or when a normal is zero (or not finite).  e = d / l.  If |n_p.e| < |n_q.e|: (n1, n2, e) = (n_q, n_p, -e), else
+ *     (n_p, n_q, e).  f3 = n1.e, v = e x n1 (the pair is skipped when |v| = 0), v <- v / |v|, w = n1 x v, f2 = v.n2,
+ *     f1 = atan2(w.n2, n1.n2).  Bins floor(11 (f1 + pi) / 2 pi), floor(11 (f2 + 1) / 2), floor(11 (f3 + 1) / 2), clamped to 0 .. 10.
+ *   SPFH(p), 3 x 11 bins: (pairs in the bin) x (100 / m), m = p's number of valid pairs; m = 0: the zero row.
+ *   FPFH(p) = SPFH(p) + (1 / m) sum over p's valid pairs of SPFH(q) / l_q^2; then every third is scaled to sum to 100 (a third
+ *     that sums to 0 stays zero).  A vertex with a zero normal, a non-finite coordinate or m = 0 has the zero row: "no descriptor".
+ * No atomics: the same bits on every call.  keep != 0 leaves the descriptors resident for oa_feature_candidates(tgt_feat =
+ * NULL); a new target forgets them.  Ends a running sequence, as oa_estimate_target_normals does. */
+int oa_target_fpfh(oa_ctx *ctx, int k, float *out /* nt x 33, or NULL */, int keep);
+/* For every row of fa (na x dim float32, host) the row of fb (nb x dim) at the smallest squared L2 distance, that distance
+ * and the second smallest distance (it feeds a ratio test; with exact duplicates in fb it equals the smallest).  The distance
+ * is the float32 sum, in column order, of the squared float32 differences; ties go to the lowest index.  Rows that are entirely
+ * zero mean "no descriptor": they neither query nor answer -- index -1, both distances +inf; so does a query with no row left
+ * to answer, and the second distance is +inf when only one row answers.  The same bits on every run.  Outputs may be NULL.
+ * Needs no target, source or matrices.  OA_E_BAD_ARG: dim outside 1 .. 64, na or nb outside 1 .. 2^24; OA_E_STATE on a
+ * multi-device context. */
+int oa_match_features(oa_ctx *ctx, const float *fa, int64_t na, const float *fb, int64_t nb, int32_t dim,
+                      int32_t *out_idx /* na */, float *out_d2 /* na */, float *out_d2_second /* na */);
+typedef struct oa_feature_settings {
+    int32_t  dim;        /* floats per descriptor row, 1 .. 64 (33) */
+    int32_t  n_hyp;      /* hypotheses = triples of kept pairs, 1 .. 65535 (4096) */
+    int32_t  mutual;     /* 1: a pair must be the nearest row in both directions AND pass the ratio test; 0: the ratio test alone (1) */
+    uint32_t seed;       /* of the hashed draw (0) */
+    double   ratio;      /* keep (s, t) when d2 <= ratio^2 d2_second; a ratio >= 1 switches the test off (0.9) */
+    double   edge_tol;   /* a triple's three edge-length ratios |a_i - a_j| / |b_i - b_j| must lie in [edge_tol, 1 / edge_tol] (0.9) */
+    double   min_edge;   /* shortest edge on either side, world units; <= 0: 0.05 x the diagonal of the target's bounding box */
+} oa_feature_settings;
+#define OA_FEAT_TOO_FEW_PAIRS 1   /* oa_feature_report::status: fewer than three pairs were kept */
+#define OA_FEAT_NO_POSE       2   /* every hypothesis was rejected */
+typedef struct oa_feature_report {
+    int32_t n_pairs, n_accepted, status, reserved;   /* pairs kept; hypotheses that gave a pose (= *n_out); OA_OK or OA_FEAT_* */
+    double  match_ms, total_ms;                      /* host time of the matching / of the whole call */
+} oa_feature_report;
+/* src_feat: n_verts x dim in the caller's source vertex order, as oa_set_source_normals takes its rows; only the selection's
+ * rows are used.  tgt_feat: nt x dim in the target's vertex order; NULL: the descriptors oa_target_fpfh kept (dim must be
+ * 33; OA_E_STATE when there are none).  Vertex-mode targets, single-device contexts (else OA_E_STATE).
+ *  1. oa_match_features selection -> target (and target -> selection when `mutual`); the kept pairs (see the settings) are
+ *     ordered by source vertex index.  Fewer than three: *n_out = 0, status OA_FEAT_TOO_FEW_PAIRS, the call returns OA_OK.
+ *  2. World-space points a = matrix_world @ src, b = mx_base @ tgt (the float32 products of the loop).
+ *  3. n_hyp triples of pair indices: `triples` (n_hyp x 3 int32; an index outside 0 .. n_pairs - 1 rejects the hypothesis), or,
+ *     when NULL, index = hash(seed, hypothesis h, position k = 0, 1, 2) in uint32 arithmetic (wrapping):
+ *       x = seed ^ (h * 0x9E3779B9) ^ ((k + 1) * 0x85EBCA6B)
+ *       x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16
+ *       index = (uint64(x) * n_pairs) >> 32
+ *  4. A hypothesis is rejected when two of its indices coincide, when an edge on either side is shorter than min_edge, when an
+ *     edge ratio leaves [edge_tol, 1 / edge_tol], or when the solve fails.  Else M = the rigid least-squares motion a -> b of its
+ *     three pairs (the loop's solve on sums taken about a_0) and the candidate is float32(M @ mx_align), formed in fp64.
+ *  5. mx_align_out (room for n_hyp x 16) receives the accepted candidates in hypothesis order, *n_out their number.
+ * No side effects, as oa_coarse_candidates. */
+int oa_feature_candidates(oa_ctx *ctx, const float *src_feat, int64_t n_verts, const float *tgt_feat,
+                          const oa_feature_settings *settings, const int32_t *triples /* n_hyp x 3, or NULL */,
+                          float *mx_align_out /* n_hyp x 16 */, int32_t *n_out, oa_feature_report *report);
 
 #ifdef __cplusplus
 }

@@ -9,3 +9,28 @@ def estimate_normals(xyz, k=16, orient="none", orient_point=None, device=0):
     with IcpEngine(int(device)) as eng:
         eng.set_target(xyz)
         return eng.estimate_target_normals(k=k, orient=orient, orient_point=orient_point, install=False)
+
+
+def fpfh(xyz, normals=None, k=16, normal_k=16, device=0):
+    """Fast Point Feature Histograms of ANY point cloud (the source's included), computed on the GPU: (n, 33) float32, an
+    all-zero row meaning "no descriptor".  Opens a context of its own on `device` and uploads xyz as its target; without
+    `normals` (n, 3) they are estimated from every point's normal_k nearest neighbours, oriented away from the centroid."""
+    import numpy as np
+    from .engine import IcpEngine, _fpfh_k
+    k = _fpfh_k(k)
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or len(xyz) < 4:
+        raise ValueError("fpfh: xyz must be (n >= 4, 3), got shape %s" % (xyz.shape,))
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, dtype=np.float32)
+        if normals.shape != xyz.shape:
+            raise ValueError("fpfh: %s normals for %s points" % (normals.shape, xyz.shape))
+    elif int(normal_k) != normal_k or not 3 <= int(normal_k) <= 64:
+        raise ValueError("fpfh: normal_k = %r outside 3 .. 64" % (normal_k,))
+    with IcpEngine(int(device)) as eng:
+        eng.set_target(xyz)
+        if normals is None:
+            eng.estimate_target_normals(k=min(int(normal_k), len(xyz)), orient="away", install=True)
+        else:
+            eng.set_target_normals(normals)
+        return eng.target_fpfh(k=min(k, len(xyz)), keep=False)

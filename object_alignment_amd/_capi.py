@@ -38,6 +38,9 @@ OA_POSE_NSCORE = 4
 OA_ORIENT_NONE = 0
 OA_ORIENT_TOWARD = 1
 OA_ORIENT_AWAY = 2
+OA_FPFH_DIM = 33
+OA_FEAT_TOO_FEW_PAIRS = 1
+OA_FEAT_NO_POSE = 2
 
 # every symbol include/oa_icp.h declares (tests check that the library exports all of them)
 SYMBOLS = [
@@ -54,6 +57,7 @@ SYMBOLS = [
     "oa_score_poses", "oa_coarse_candidates", "oa_coarse_align",
     "oa_target_knn", "oa_estimate_target_normals",
     "oa_set_gicp", "oa_set_source_normals",
+    "oa_coarse_align_poses", "oa_target_fpfh", "oa_match_features", "oa_feature_candidates",
 ]
 
 
@@ -78,6 +82,16 @@ class CoarseReport(C.Structure):
     _fields_ = [("n_candidates", C.c_int32), ("best_candidate", C.c_int32), ("best_rank", C.c_int32), ("status", C.c_int32),
                 ("cost_start", C.c_double), ("cost_best_candidate", C.c_double), ("cost_refined", C.c_double),
                 ("K_refined", C.c_int64), ("score_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class FeatureSettings(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("n_hyp", C.c_int32), ("mutual", C.c_int32), ("seed", C.c_uint32),
+                ("ratio", C.c_double), ("edge_tol", C.c_double), ("min_edge", C.c_double)]
+
+
+class FeatureReport(C.Structure):
+    _fields_ = [("n_pairs", C.c_int32), ("n_accepted", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32),
+                ("match_ms", C.c_double), ("total_ms", C.c_double)]
 
 
 class OaError(RuntimeError):
@@ -172,6 +186,11 @@ def load(experiments: bool = False):
     L.oa_coarse_align.argtypes = [vp, C.POINTER(CoarseSettings), C.POINTER(CoarseReport)]
     L.oa_target_knn.argtypes = [vp, C.c_int, C.POINTER(C.c_int32), fp]
     L.oa_estimate_target_normals.argtypes = [vp, C.c_int, C.c_int, fp, C.c_int, fp, fp]
+    i32p = C.POINTER(C.c_int32)
+    L.oa_coarse_align_poses.argtypes = [vp, fp, C.c_int32, C.POINTER(CoarseSettings), C.POINTER(CoarseReport)]
+    L.oa_target_fpfh.argtypes = [vp, C.c_int, fp, C.c_int]
+    L.oa_match_features.argtypes = [vp, fp, C.c_int64, fp, C.c_int64, C.c_int32, i32p, fp, fp]
+    L.oa_feature_candidates.argtypes = [vp, fp, C.c_int64, fp, C.POINTER(FeatureSettings), i32p, fp, i32p, C.POINTER(FeatureReport)]
     _libs[experiments] = L
     return L
 

@@ -26,6 +26,9 @@
 #define OA_SIG_BVH_SEARCH const DevState *, const float4 *, int, BvhParams, const float4 *, const float4 *, const float4 *, int *, float4 *, unsigned long long *, const int *, const int *, int, NormalTest, double *, const float *, uint2 *
 #define OA_SIG_POSE_SCORE PoseBase, const float *, const float *, const float4 *, const int *, int, int, BvhParams, const float4 *, const float4 *, const float4 *, double *
 #define OA_SIG_BVH_KNN BvhParams, const float4 *, const float4 *, int, int32_t *, float *, const float *, KnnOrient, float *, float *
+#define OA_SIG_FPFH const float *, const float *, const int32_t *, int, int, double *, float *
+#define OA_SIG_MATCH_FEATURES const float *, const float *, const float *, int, int, int, unsigned long long *, unsigned long long *, float *
+#define OA_SIG_TRIPLE_POSES const int *, const int *, int, const int *, int, const float4 *, const float *, Mat4f, Mat4f, Mat4d, double, double, float *, int *
 #define OA_SIG_AFFINE_SOLVE const double *, const double *, int, long long, int, int, double *, double *
 #define OA_SIG_NN_MFMA const DevState *, const float4 *, const float4 *, const half8 *, const float4 *, int, double, unsigned long long *
 
@@ -85,6 +88,12 @@
 // ---- k nearest target vertices of every target vertex / PCA normals from them (oa_knn.hpp): oa_fam_knn.hip ----------
 #define OA_FAMILY_KNN(X) OA_K(X, k_bvh_knn, OA_SIG_BVH_KNN, false) OA_K(X, k_bvh_knn, OA_SIG_BVH_KNN, true)
 
+// ---- nearest rows in descriptor space / poses from triples of matched points (oa_feat.hpp): oa_fam_feat.hip -----------
+#define OA_FAMILY_FEAT(X)                                                                                               \
+    OA_K(X, k_match_features, OA_SIG_MATCH_FEATURES, 8) OA_K(X, k_match_features, OA_SIG_MATCH_FEATURES, 16)            \
+    OA_K(X, k_match_features, OA_SIG_MATCH_FEATURES, 36) OA_K(X, k_match_features, OA_SIG_MATCH_FEATURES, 64)           \
+    OA_K(X, k_triple_poses, OA_SIG_TRIPLE_POSES, 4) OA_K(X, k_fpfh, OA_SIG_FPFH, false) OA_K(X, k_fpfh, OA_SIG_FPFH, true)
+
 // ---- affine_matrix_from_points beyond the loop's 3-D solve: oa_fam_affine.hip ---------------------------------------
 #define OA_FAMILY_AFFINE(X)                                                                                             \
     OA_K(X, k_affine_solve, OA_SIG_AFFINE_SOLVE, AFF_MAXD, false) OA_K(X, k_affine_solve, OA_SIG_AFFINE_SOLVE, 16, true) \
@@ -116,6 +125,7 @@ OA_FAMILY_TRI_ACC(extern)
 OA_FAMILY_BVH(extern)
 OA_FAMILY_POSE(extern)
 OA_FAMILY_KNN(extern)
+OA_FAMILY_FEAT(extern)
 OA_FAMILY_AFFINE(extern)
 #if defined(OA_EXPERIMENTS)
 OA_FAMILY_EXP(extern)

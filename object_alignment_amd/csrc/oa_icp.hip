@@ -433,6 +433,7 @@ struct oa_ctx {
     long long src_n_verts = 0;
     // normal-angle rejection (extension)
     float *d_src_n = nullptr, *d_tgt_n = nullptr;
+    float *d_tgt_feat = nullptr;     // oa_target_fpfh(keep): nt x 33 descriptors of the resident target, or nullptr; a new target forgets them
     double cos_min = -2.0;
     bool normals_on = false;
     int last_plane_rank = 0;         // OA_STAT_PLANE_RANK: eigenvalues the last plane solve kept (loop or oa_point_to_plane)
@@ -2360,7 +2361,7 @@ OA_EXPORT void oa_destroy(oa_ctx *c)
     OA_FREE(d_valid); OA_FREE(d_b); OA_FREE(d_dist); OA_FREE(d_counts); OA_FREE(d_offsets); OA_FREE(d_A); OA_FREE(d_B);
     OA_FREE(d_bvh_box); OA_FREE(d_bvh_prims); OA_FREE(d_tbvh_box); OA_FREE(d_tbvh_prims);
     OA_FREE(d_tri9); OA_FREE(d_tcell_start); OA_FREE(d_tcell_rec); OA_FREE(d_tri_ring); OA_FREE(d_tfine_table); OA_FREE(d_tfine_rec);
-    OA_FREE(d_sel); OA_FREE(d_src_n); OA_FREE(d_tgt_n); OA_FREE(d_w); OA_FREE(d_rkeys); OA_FREE(d_sel_hist); OA_FREE(d_src4o); OA_FREE(d_perm);
+    OA_FREE(d_sel); OA_FREE(d_src_n); OA_FREE(d_tgt_n); OA_FREE(d_tgt_feat); OA_FREE(d_w); OA_FREE(d_rkeys); OA_FREE(d_sel_hist); OA_FREE(d_src4o); OA_FREE(d_perm);
 #undef OA_FREE
     if (c->h_hist_map) (void)hipHostFree(c->h_hist_map);
     if (c->h_state_pin) (void)hipHostFree(c->h_state_pin);
@@ -2665,7 +2666,7 @@ int set_target_common(oa_ctx *c, const float *xyz, int64_t n, int on_device, boo
     c->tri_ring_ok = false; c->tri_fine_ok = false;
     dev_free(c->d_bvh_box); dev_free(c->d_bvh_prims); dev_free(c->d_tbvh_box); dev_free(c->d_tbvh_prims);
     c->surface = false; c->tri_grid_ok = false; c->n_tris = 0; c->bvh_ok = false; c->tbvh_ok = false;
-    dev_free(c->d_tgt_n);
+    dev_free(c->d_tgt_n); dev_free(c->d_tgt_feat);
     c->normals_on = false;
     c->filter_ok = false;
     c->nt = (int)n;
@@ -3923,6 +3924,8 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
     case OA_STAT_WEIGHT_SUM: *value = c->last_weight_sum; return OA_OK;
     case OA_STAT_ROBUST_SCALE: *value = c->loss == OA_LOSS_NONE ? 0.0 : (auto_scale(c) ? c->last_robust_c : c->robust_c); return OA_OK;
     case OA_STAT_ROBUST_QUANTILE: *value = c->robust_p; return OA_OK;
+    case OA_STAT_TARGET_NORMALS: *value = (!c->surface && c->d_tgt_n) ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_TARGET_FEATURES: *value = c->d_tgt_feat ? 1.0 : 0.0; return OA_OK;
     default: return fail(OA_E_BAD_ARG, "oa_get_stat: unknown key %d", what);
     }
 }
@@ -4776,31 +4779,36 @@ OA_EXPORT int oa_coarse_candidates(oa_ctx *c, int32_t n_rot, float *mx_align_out
     return coarse_candidates(c, n_rot, mx_align_out);
 }
 
-OA_EXPORT int oa_coarse_align(oa_ctx *c, const oa_coarse_settings *cs, oa_coarse_report *rep)
+namespace {
+// what oa_coarse_align and oa_coarse_align_poses check first
+int coarse_call_begin(oa_ctx *c, const char *who, const oa_coarse_settings *cs, oa_coarse_report *rep, bool uses_n_rot)
 {
-    if (!c || !cs || !rep) return fail(OA_E_BAD_ARG, "oa_coarse_align: null argument");
-    OA_NOT_MULTI(c, "oa_coarse_align");
     int rc = pose_call_ready(c);
     if (rc) return rc;
     if (!(cs->thresh > 0.0)) return fail(OA_E_BAD_THRESH, "thresh must be > 0 (the reference's make_pairs returns None)");
-    if (!(cs->thresh < INFINITY) || cs->n_rot < 1 || cs->n_rot > 65536 || cs->n_refine < 1 || cs->n_refine > 4096 || cs->refine_iters < 0 || cs->refine_iters > 10000)
-        return fail(OA_E_BAD_ARG, "oa_coarse_align: n_rot 1 .. 65536, n_refine 1 .. 4096, refine_iters 0 .. 10000 and a finite thresh");
+    if (!(cs->thresh < INFINITY) || (uses_n_rot && (cs->n_rot < 1 || cs->n_rot > 65536)) || cs->n_refine < 1 || cs->n_refine > 4096 || cs->refine_iters < 0 || cs->refine_iters > 10000)
+        return fail(OA_E_BAD_ARG, "%s: n_rot 1 .. 65536, n_refine 1 .. 4096, refine_iters 0 .. 10000 and a finite thresh", who);
     memset(rep, 0, sizeof *rep);
     // the call ends a running sequence, as oa_set_matrices does; the pose it reached is the incoming one
     if (c->loop_active) {
         if ((rc = fetch_state(c))) return rc;
         c->loop_active = false;
     }
-    const auto t0 = std::chrono::steady_clock::now();
+    return OA_OK;
+}
+
+// The multi-start recipe over cand = n_rot candidates followed by the incoming pose (P = n_rot + 1 matrices): one scoring launch,
+// the n_refine best refined, rescored, matrix_world <- the lowest cost (or left alone).  t0: when the call began.
+int coarse_align_body(oa_ctx *c, const char *who, const oa_coarse_settings *cs, oa_coarse_report *rep, const std::vector<float> &cand, int n_rot,
+                      std::chrono::steady_clock::time_point t0)
+{
+    int rc = OA_OK;
     auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    const int n_rot = cs->n_rot, P = n_rot + 1;                     // the incoming pose is candidate n_rot
+    const int P = n_rot + 1;                                        // the incoming pose is candidate n_rot
     const int n_ref = std::min((int)cs->n_refine, P);
-    std::vector<float> cand(16 * (size_t)P);
-    if ((rc = coarse_candidates(c, n_rot, cand.data()))) return rc;
-    memcpy(cand.data() + 16 * (size_t)n_rot, c->h_state.mx1, sizeof(float) * 16);
     {
         const long long step = cs->stride > 1 ? cs->stride : 1, S = (c->ns + step - 1) / step;
-        if (S * P >= (1ll << 31)) return fail(OA_E_BAD_ARG, "oa_coarse_align: %lld sample points x %d poses: 2^31 queries or more", S, P);
+        if (S * P >= (1ll << 31)) return fail(OA_E_BAD_ARG, "%s: %lld sample points x %d poses: 2^31 queries or more", who, S, P);
     }
     PoseJob job;
     if ((rc = pose_job_begin(c, cs->thresh, cs->stride, job))) return rc;
@@ -4820,7 +4828,7 @@ OA_EXPORT int oa_coarse_align(oa_ctx *c, const oa_coarse_settings *cs, oa_coarse
     std::vector<float> ref(16 * (size_t)n_ref), iref(16 * (size_t)n_ref);
     for (int k = 0; k < n_ref; ++k) {
         memcpy(&ref[16 * (size_t)k], &cand[16 * (size_t)pick[(size_t)k]], sizeof(float) * 16);
-        if (!oa::m4_inverted(&ref[16 * (size_t)k], &iref[16 * (size_t)k])) return fail(OA_E_SINGULAR, "oa_coarse_align: candidate %d has no inverse", pick[(size_t)k]);
+        if (!oa::m4_inverted(&ref[16 * (size_t)k], &iref[16 * (size_t)k])) return fail(OA_E_SINGULAR, "%s: candidate %d has no inverse", who, pick[(size_t)k]);
     }
     HIPCHK(d_iposes.alloc(16 * (size_t)n_ref));
     HIPCHK(hipStreamSynchronize(c->stream));                      // (d_poses is reused: the first upload has been read)
@@ -4865,6 +4873,37 @@ OA_EXPORT int oa_coarse_align(oa_ctx *c, const oa_coarse_settings *cs, oa_coarse
     rep->total_ms = ms_since(t0);
     return OA_OK;
 }
+}  // namespace
+
+OA_EXPORT int oa_coarse_align(oa_ctx *c, const oa_coarse_settings *cs, oa_coarse_report *rep)
+{
+    if (!c || !cs || !rep) return fail(OA_E_BAD_ARG, "oa_coarse_align: null argument");
+    OA_NOT_MULTI(c, "oa_coarse_align");
+    int rc = coarse_call_begin(c, "oa_coarse_align", cs, rep, true);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int n_rot = cs->n_rot;
+    std::vector<float> cand(16 * ((size_t)n_rot + 1));
+    if ((rc = coarse_candidates(c, n_rot, cand.data()))) return rc;
+    memcpy(cand.data() + 16 * (size_t)n_rot, c->h_state.mx1, sizeof(float) * 16);
+    return coarse_align_body(c, "oa_coarse_align", cs, rep, cand, n_rot, t0);
+}
+
+OA_EXPORT int oa_coarse_align_poses(oa_ctx *c, const float *mx_align, int32_t n_poses, const oa_coarse_settings *cs, oa_coarse_report *rep)
+{
+    if (!c || !mx_align || !cs || !rep) return fail(OA_E_BAD_ARG, "oa_coarse_align_poses: null argument");
+    OA_NOT_MULTI(c, "oa_coarse_align_poses");
+    int rc = coarse_call_begin(c, "oa_coarse_align_poses", cs, rep, false);
+    if (rc) return rc;
+    if (n_poses < 1 || n_poses > 65535) return fail(OA_E_BAD_ARG, "oa_coarse_align_poses: %d poses (1 .. 65535)", n_poses);
+    for (size_t k = 0; k < 16 * (size_t)n_poses; ++k)
+        if (!(fabsf(mx_align[k]) < INFINITY)) return fail(OA_E_BAD_ARG, "oa_coarse_align_poses: entry %zu of pose %zu is not finite", k % 16, k / 16);
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<float> cand(16 * ((size_t)n_poses + 1));
+    memcpy(cand.data(), mx_align, sizeof(float) * 16 * (size_t)n_poses);
+    memcpy(cand.data() + 16 * (size_t)n_poses, c->h_state.mx1, sizeof(float) * 16);
+    return coarse_align_body(c, "oa_coarse_align_poses", cs, rep, cand, n_poses, t0);
+}
 
 // ================================================================================================
 // k nearest target vertices / PCA normals of a point-cloud target (EXTENSION; oa_knn.hpp)
@@ -4883,25 +4922,31 @@ struct KnnTree {
     ~KnnTree() { dev_free(own_box); dev_free(own_prims); }
 };
 
+// the box of the target's finite coordinates, base-local (all zero when there is none)
+int target_bbox(oa_ctx *c, double lo[3], double hi[3])
+{
+    for (int a = 0; a < 3; ++a) { lo[a] = 0.0; hi[a] = 0.0; }
+    if (c->filter_ok) { for (int a = 0; a < 3; ++a) { lo[a] = c->bb_lo[a]; hi[a] = c->bb_hi[a]; } return OA_OK; }
+    const int nb = 256;
+    DevTmp<float> d_bb;
+    HIPCHK(d_bb.alloc(6 * (size_t)nb));
+    hipLaunchKernelGGL(oa::k_bbox_finite, dim3(nb), dim3(256), 0, c->stream, (const float *)c->d_tgt_xyz, c->nt, d_bb.p);
+    HIPCHK(hipGetLastError());
+    std::vector<float> bb(6 * (size_t)nb);
+    const int rc = read_small(c, bb.data(), d_bb.p, sizeof(float) * bb.size());
+    if (rc) return rc;
+    float l[3] = { INFINITY, INFINITY, INFINITY }, h[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (int b = 0; b < nb; ++b)
+        for (int a = 0; a < 3; ++a) { l[a] = std::min(l[a], bb[6 * (size_t)b + a]); h[a] = std::max(h[a], bb[6 * (size_t)b + 3 + a]); }
+    for (int a = 0; a < 3; ++a) if (l[a] <= h[a]) { lo[a] = l[a]; hi[a] = h[a]; }     // (no finite coordinate: any frame will do)
+    return OA_OK;
+}
+
 int knn_tree(oa_ctx *c, KnnTree &t)
 {
     if (c->bvh_ok && c->d_bvh_box && c->d_bvh_prims) { t.bp = c->bvh; t.box = c->d_bvh_box; t.prims = c->d_bvh_prims; return OA_OK; }
-    double lo[3] = { 0.0, 0.0, 0.0 }, hi[3] = { 0.0, 0.0, 0.0 };
-    if (c->filter_ok) { for (int a = 0; a < 3; ++a) { lo[a] = c->bb_lo[a]; hi[a] = c->bb_hi[a]; } }
-    else {
-        const int nb = 256;
-        DevTmp<float> d_bb;
-        HIPCHK(d_bb.alloc(6 * (size_t)nb));
-        hipLaunchKernelGGL(oa::k_bbox_finite, dim3(nb), dim3(256), 0, c->stream, (const float *)c->d_tgt_xyz, c->nt, d_bb.p);
-        HIPCHK(hipGetLastError());
-        std::vector<float> bb(6 * (size_t)nb);
-        const int rc = read_small(c, bb.data(), d_bb.p, sizeof(float) * bb.size());
-        if (rc) return rc;
-        float l[3] = { INFINITY, INFINITY, INFINITY }, h[3] = { -INFINITY, -INFINITY, -INFINITY };
-        for (int b = 0; b < nb; ++b)
-            for (int a = 0; a < 3; ++a) { l[a] = std::min(l[a], bb[6 * (size_t)b + a]); h[a] = std::max(h[a], bb[6 * (size_t)b + 3 + a]); }
-        for (int a = 0; a < 3; ++a) if (l[a] <= h[a]) { lo[a] = l[a]; hi[a] = h[a]; }     // (no finite coordinate: any frame will do)
-    }
+    double lo[3], hi[3];
+    { const int rcb = target_bbox(c, lo, hi); if (rcb) return rcb; }
     bool ok = false;
     const int rc = build_bvh_arrays(c, false, c->nt, lo, hi, t.bp, t.own_box, t.own_prims, ok);
     if (rc) return rc;
@@ -4994,5 +5039,241 @@ OA_EXPORT int oa_estimate_target_normals(oa_ctx *c, int k, int orient, const flo
     if (out_normals) HIPCHK(hipMemcpyAsync(out_normals, d_n, sizeof(float) * 3 * nt, hipMemcpyDeviceToHost, c->stream));
     if (out_curvature) HIPCHK(hipMemcpyAsync(out_curvature, d_curv.p, sizeof(float) * nt, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
+// ================================================================================================
+// coarse alignment from matched descriptors (EXTENSION; oa_feat.hpp)
+// ================================================================================================
+namespace {
+bool row_is_zero(const float *row, int dim)
+{
+    for (int k = 0; k < dim; ++k) if (row[k] != 0.0f) return false;
+    return true;
+}
+
+// nearest and second nearest row of fb for every row of fa (host arrays in, host arrays out; any of the outputs may be null)
+int match_rows(oa_ctx *c, const float *fa, int na, const float *fb, int nb, int dim, int32_t *out_idx, float *out_d2, float *out_second)
+{
+    const int DP = oa::feat_padded_dim(dim);
+    const int na_pad = (na + oa::FEAT_QPB - 1) / oa::FEAT_QPB * oa::FEAT_QPB, nb_pad = (nb + oa::FEAT_TB - 1) / oa::FEAT_TB * oa::FEAT_TB;
+    std::vector<float> ha((size_t)na_pad * DP, 0.0f), hb((size_t)nb_pad * DP, 0.0f), pen((size_t)nb_pad, INFINITY);
+    for (int i = 0; i < na; ++i) memcpy(&ha[(size_t)i * DP], fa + (size_t)i * dim, sizeof(float) * (size_t)dim);
+    for (int j = 0; j < nb; ++j) {
+        memcpy(&hb[(size_t)j * DP], fb + (size_t)j * dim, sizeof(float) * (size_t)dim);
+        if (!row_is_zero(fb + (size_t)j * dim, dim)) pen[(size_t)j] = 0.0f;
+    }
+    const int qblocks = na_pad / oa::FEAT_QPB, tiles = nb_pad / oa::FEAT_TB;
+    int splits = std::max(1, std::min(std::min(tiles, oa::FEAT_MAX_SPLITS), (c->n_cu * 4 + qblocks - 1) / qblocks));
+    const int tps = (tiles + splits - 1) / splits;
+    splits = (tiles + tps - 1) / tps;                               // every split has a tile
+    DevTmp<float> d_a, d_b, d_pen, d_psec, d_d2, d_sec;
+    DevTmp<unsigned long long> d_keys, d_pkey;
+    DevTmp<int32_t> d_idx;
+    HIPCHK(d_a.alloc(ha.size())); HIPCHK(d_b.alloc(hb.size())); HIPCHK(d_pen.alloc(pen.size()));
+    HIPCHK(d_keys.alloc((size_t)na_pad)); HIPCHK(d_pkey.alloc((size_t)splits * na_pad)); HIPCHK(d_psec.alloc((size_t)splits * na_pad));
+    HIPCHK(d_idx.alloc((size_t)na)); HIPCHK(d_d2.alloc((size_t)na)); HIPCHK(d_sec.alloc((size_t)na));
+    HIPCHK(hipMemcpyAsync(d_a.p, ha.data(), sizeof(float) * ha.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_b.p, hb.data(), sizeof(float) * hb.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_pen.p, pen.data(), sizeof(float) * pen.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(d_keys.p, 0xff, sizeof(unsigned long long) * (size_t)na_pad, c->stream));
+    const dim3 grid((unsigned)qblocks, (unsigned)splits), block(oa::FEAT_THREADS);
+    auto launch = [&](auto DPc) {
+        hipLaunchKernelGGL((oa::k_match_features<decltype(DPc)::value>), grid, block, 0, c->stream, (const float *)d_a.p, (const float *)d_b.p,
+                           (const float *)d_pen.p, na_pad, tiles, tps, d_keys.p, d_pkey.p, d_psec.p);
+    };
+    if (DP == 8) launch(std::integral_constant<int, 8>{});
+    else if (DP == 16) launch(std::integral_constant<int, 16>{});
+    else if (DP == 36) launch(std::integral_constant<int, 36>{});
+    else launch(std::integral_constant<int, 64>{});
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(oa::k_match_finalize, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, c->stream, (const unsigned long long *)d_keys.p,
+                       (const unsigned long long *)d_pkey.p, (const float *)d_psec.p, na, na_pad, splits, d_idx.p, d_d2.p, d_sec.p);
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> h_idx((size_t)na);
+    std::vector<float> h_d2((size_t)na), h_sec((size_t)na);
+    HIPCHK(hipMemcpyAsync(h_idx.data(), d_idx.p, sizeof(int32_t) * (size_t)na, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_d2.data(), d_d2.p, sizeof(float) * (size_t)na, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h_sec.data(), d_sec.p, sizeof(float) * (size_t)na, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < na; ++i) {
+        const bool none = row_is_zero(fa + (size_t)i * dim, dim);   // a zero row does not query
+        if (out_idx) out_idx[i] = none ? -1 : h_idx[(size_t)i];
+        if (out_d2) out_d2[i] = none ? INFINITY : h_d2[(size_t)i];
+        if (out_second) out_second[i] = none ? INFINITY : h_sec[(size_t)i];
+    }
+    return OA_OK;
+}
+
+int match_args(const char *who, const float *fa, int64_t na, const float *fb, int64_t nb, int dim)
+{
+    if (!fa || !fb) return fail(OA_E_BAD_ARG, "%s: null argument", who);
+    if (dim < 1 || dim > oa::FEAT_MAX_DIM) return fail(OA_E_BAD_ARG, "%s: dim %d outside 1 .. %d", who, dim, oa::FEAT_MAX_DIM);
+    if (na < 1 || nb < 1 || na > (1 << 24) || nb > (1 << 24)) return fail(OA_E_BAD_ARG, "%s: %lld and %lld rows (1 .. 2^24 each)", who, (long long)na, (long long)nb);
+    return OA_OK;
+}
+}  // namespace
+
+OA_EXPORT int oa_target_fpfh(oa_ctx *c, int k, float *out, int keep)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    OA_NOT_MULTI(c, "oa_target_fpfh");
+    int rc = knn_call_begin(c, "oa_target_fpfh", k, 4);
+    if (rc) return rc;
+    if (!c->d_tgt_n) return fail(OA_E_STATE, "oa_target_fpfh: the target has no normals (oa_set_target_normals, oa_set_normals or oa_estimate_target_normals with install)");
+    KnnTree tree;
+    if ((rc = knn_tree(c, tree))) return rc;
+    const size_t nt = (size_t)c->nt;
+    DevTmp<int32_t> d_idx;
+    DevTmp<double> d_spfh;
+    DevTmp<float> tmp;
+    HIPCHK(d_idx.alloc(nt * (size_t)k));
+    HIPCHK(d_spfh.alloc(nt * oa::FPFH_DIM));
+    float *d_out = nullptr;
+    if (keep) {                                                     // (the stream is idle: a kept table is replaced in place)
+        if (!c->d_tgt_feat) HIPCHK(dev_malloc(&c->d_tgt_feat, sizeof(float) * oa::FPFH_DIM * nt));
+        d_out = c->d_tgt_feat;
+    } else { HIPCHK(tmp.alloc(oa::FPFH_DIM * nt)); d_out = tmp.p; }
+    if ((rc = knn_launch<false>(c, tree, k, d_idx.p, nullptr, oa::KnnOrient{}, nullptr, nullptr))) return rc;
+    const dim3 grid((unsigned)((nt + oa::FPFH_THREADS - 1) / oa::FPFH_THREADS)), block(oa::FPFH_THREADS);
+    hipLaunchKernelGGL((oa::k_fpfh<false>), grid, block, 0, c->stream, (const float *)c->d_tgt_xyz, (const float *)c->d_tgt_n, (const int32_t *)d_idx.p,
+                       c->nt, k, d_spfh.p, (float *)nullptr);
+    hipLaunchKernelGGL((oa::k_fpfh<true>), grid, block, 0, c->stream, (const float *)c->d_tgt_xyz, (const float *)c->d_tgt_n, (const int32_t *)d_idx.p,
+                       c->nt, k, d_spfh.p, d_out);
+    HIPCHK(hipGetLastError());
+    if (out) HIPCHK(hipMemcpyAsync(out, d_out, sizeof(float) * oa::FPFH_DIM * nt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
+OA_EXPORT int oa_match_features(oa_ctx *c, const float *fa, int64_t na, const float *fb, int64_t nb, int32_t dim, int32_t *out_idx, float *out_d2,
+                                float *out_d2_second)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    OA_NOT_MULTI(c, "oa_match_features");
+    int rc = match_args("oa_match_features", fa, na, fb, nb, dim);
+    if (rc) return rc;
+    if ((rc = use_device(c))) return rc;
+    return match_rows(c, fa, (int)na, fb, (int)nb, dim, out_idx, out_d2, out_d2_second);
+}
+
+OA_EXPORT int oa_feature_candidates(oa_ctx *c, const float *src_feat, int64_t n_verts, const float *tgt_feat, const oa_feature_settings *fs,
+                                    const int32_t *triples, float *mx_align_out, int32_t *n_out, oa_feature_report *rep)
+{
+    if (!c || !src_feat || !fs || !mx_align_out || !n_out || !rep) return fail(OA_E_BAD_ARG, "oa_feature_candidates: null argument");
+    OA_NOT_MULTI(c, "oa_feature_candidates");
+    int rc = pose_call_ready(c);
+    if (rc) return rc;
+    if (c->surface) return fail(OA_E_STATE, "oa_feature_candidates: a surface target (oa_set_target_mesh) has no per-vertex descriptors");
+    if (!tgt_feat && !c->d_tgt_feat) return fail(OA_E_STATE, "oa_feature_candidates: no descriptors are resident for the target (oa_target_fpfh with keep), and none were passed");
+    if (!tgt_feat && fs->dim != oa::FPFH_DIM) return fail(OA_E_BAD_ARG, "oa_feature_candidates: the resident descriptors have %d floats, the settings say %d", oa::FPFH_DIM, fs->dim);
+    if (c->ns <= 0) return fail(OA_E_STATE, "oa_feature_candidates: the selection is empty");
+    if (n_verts != c->src_n_verts) return fail(OA_E_BAD_ARG, "oa_feature_candidates: %lld descriptor rows for %lld source vertices", (long long)n_verts, c->src_n_verts);
+    const int dim = fs->dim;
+    if (dim < 1 || dim > oa::FEAT_MAX_DIM || fs->n_hyp < 1 || fs->n_hyp > 65535 || !(fs->ratio > 0.0) || !(fs->edge_tol > 0.0) || !(fs->edge_tol <= 1.0) ||
+        !(fs->min_edge < INFINITY))
+        return fail(OA_E_BAD_ARG, "oa_feature_candidates: dim 1 .. %d, n_hyp 1 .. 65535, ratio > 0, 0 < edge_tol <= 1 and a finite min_edge", oa::FEAT_MAX_DIM);
+    if (c->ns > (1 << 24) || c->nt > (1 << 24)) return fail(OA_E_BAD_ARG, "oa_feature_candidates: more than 2^24 rows on a side");
+    memset(rep, 0, sizeof *rep);
+    *n_out = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    const int ns = c->ns, nt = c->nt, n_hyp = fs->n_hyp;
+    // the selection's rows, in slot order
+    std::vector<int> sel((size_t)ns);
+    HIPCHK(hipMemcpyAsync(sel.data(), c->d_sel, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::vector<float> fsel((size_t)ns * dim);
+    for (int s = 0; s < ns; ++s) {
+        if (sel[(size_t)s] < 0 || sel[(size_t)s] >= n_verts) return fail(OA_E_STATE, "oa_feature_candidates: slot %d holds vertex %d of %lld", s, sel[(size_t)s], (long long)n_verts);
+        memcpy(&fsel[(size_t)s * dim], src_feat + (size_t)sel[(size_t)s] * dim, sizeof(float) * (size_t)dim);
+    }
+    std::vector<float> kept;
+    if (!tgt_feat) {                                                // the kept table (matching takes host rows)
+        kept.resize((size_t)nt * oa::FPFH_DIM);
+        HIPCHK(hipMemcpyAsync(kept.data(), c->d_tgt_feat, sizeof(float) * kept.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        tgt_feat = kept.data();
+    }
+    // 1. both directions
+    std::vector<int32_t> st((size_t)ns), ts((size_t)nt);
+    std::vector<float> st_d2((size_t)ns), st_sec((size_t)ns);
+    const auto t1 = std::chrono::steady_clock::now();
+    if ((rc = match_rows(c, fsel.data(), ns, tgt_feat, nt, dim, st.data(), st_d2.data(), st_sec.data()))) return rc;
+    if (fs->mutual && (rc = match_rows(c, tgt_feat, nt, fsel.data(), ns, dim, ts.data(), nullptr, nullptr))) return rc;
+    rep->match_ms = ms_since(t1);
+    // 2., 3. the kept pairs
+    std::vector<int> pair_s, pair_t;
+    const double r2 = fs->ratio * fs->ratio;
+    for (int s = 0; s < ns; ++s) {
+        const int t = st[(size_t)s];
+        if (t < 0) continue;
+        if (!((double)st_d2[(size_t)s] <= r2 * (double)st_sec[(size_t)s])) continue;
+        if (fs->mutual && ts[(size_t)t] != s) continue;
+        pair_s.push_back(s); pair_t.push_back(t);
+    }
+    {   // by source vertex index: the slots are in the search's own order, the caller knows the vertices
+        std::vector<int> order(pair_s.size());
+        for (size_t k = 0; k < order.size(); ++k) order[k] = (int)k;
+        std::sort(order.begin(), order.end(), [&](int a, int b) { return sel[(size_t)pair_s[(size_t)a]] < sel[(size_t)pair_s[(size_t)b]]; });
+        std::vector<int> ps(order.size()), pt(order.size());
+        for (size_t k = 0; k < order.size(); ++k) { ps[k] = pair_s[(size_t)order[k]]; pt[k] = pair_t[(size_t)order[k]]; }
+        pair_s.swap(ps); pair_t.swap(pt);
+    }
+    const int n_pairs = (int)pair_s.size();
+    rep->n_pairs = n_pairs;
+    if (n_pairs < 3) {                                              // 4. not an error
+        rep->status = OA_FEAT_TOO_FEW_PAIRS;
+        rep->total_ms = ms_since(t0);
+        return OA_OK;
+    }
+    // 6. the triples
+    std::vector<int32_t> tri(3 * (size_t)n_hyp);
+    if (triples) memcpy(tri.data(), triples, sizeof(int32_t) * tri.size());
+    else
+        for (int h = 0; h < n_hyp; ++h)
+            for (int k = 0; k < 3; ++k) tri[3 * (size_t)h + k] = (int32_t)oa::feat_hash_index(fs->seed, (uint32_t)h, (uint32_t)k, (uint32_t)n_pairs);
+    double min_edge = fs->min_edge;
+    if (!(min_edge > 0.0)) {                                        // 0.05 x the target's diagonal, in world units
+        double lo[3], hi[3];
+        if ((rc = target_bbox(c, lo, hi))) return rc;
+        const float *B = c->h_state.mx2;
+        double d2 = 0.0;
+        for (int i = 0; i < 3; ++i) {
+            double v = 0.0;
+            for (int k = 0; k < 3; ++k) v += (double)B[4 * i + k] * (hi[k] - lo[k]);
+            d2 += v * v;
+        }
+        min_edge = 0.05 * sqrt(d2);
+    }
+    // 7. one wave per hypothesis, then the accepted ones in order
+    DevTmp<int> d_ps, d_pt, d_tri, d_flags, d_n;
+    DevTmp<float> d_poses, d_out;
+    HIPCHK(d_ps.alloc((size_t)n_pairs)); HIPCHK(d_pt.alloc((size_t)n_pairs)); HIPCHK(d_tri.alloc(tri.size()));
+    HIPCHK(d_flags.alloc((size_t)n_hyp)); HIPCHK(d_n.alloc(1));
+    HIPCHK(d_poses.alloc(16 * (size_t)n_hyp)); HIPCHK(d_out.alloc(16 * (size_t)n_hyp));
+    HIPCHK(hipMemcpyAsync(d_ps.p, pair_s.data(), sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_pt.p, pair_t.data(), sizeof(int) * (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_tri.p, tri.data(), sizeof(int32_t) * tri.size(), hipMemcpyHostToDevice, c->stream));
+    oa::Mat4f m1, m2;
+    oa::Mat4d ma;
+    memcpy(m1.m, c->h_state.mx1, sizeof m1.m);
+    memcpy(m2.m, c->h_state.mx2, sizeof m2.m);
+    for (int k = 0; k < 16; ++k) ma.m[k] = (double)c->h_state.mx1[k];
+    constexpr int WPB = 4;
+    hipLaunchKernelGGL((oa::k_triple_poses<WPB>), dim3((unsigned)((n_hyp + WPB - 1) / WPB)), dim3(WPB * 64), 0, c->stream, (const int *)d_ps.p,
+                       (const int *)d_pt.p, n_pairs, (const int *)d_tri.p, n_hyp, (const float4 *)c->d_src4, (const float *)c->d_tgt_xyz, m1, m2, ma,
+                       fs->edge_tol, min_edge, d_poses.p, d_flags.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(oa::k_triple_compact, dim3(1), dim3(256), 0, c->stream, (const float *)d_poses.p, (const int *)d_flags.p, n_hyp, d_out.p, d_n.p);
+    HIPCHK(hipGetLastError());
+    int n_acc = 0;
+    if ((rc = read_small(c, &n_acc, d_n.p, sizeof n_acc))) return rc;
+    if (n_acc < 0 || n_acc > n_hyp) return fail(OA_E_HIP, "oa_feature_candidates: %d poses out of %d hypotheses", n_acc, n_hyp);
+    if (n_acc > 0 && (rc = read_small(c, mx_align_out, d_out.p, sizeof(float) * 16 * (size_t)n_acc))) return rc;
+    *n_out = n_acc;
+    rep->n_accepted = n_acc;
+    rep->status = n_acc > 0 ? OA_OK : OA_FEAT_NO_POSE;
+    rep->total_ms = ms_since(t0);
     return OA_OK;
 }

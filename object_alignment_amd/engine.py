@@ -48,6 +48,20 @@ def _device_ptr(x):
     return C.c_void_p(a.ctypes.data), 0, a, a.shape[0]
 
 
+def _fpfh_k(k):
+    if int(k) != k or not 4 <= int(k) <= 64:
+        raise ValueError("fpfh: k = %r outside 4 .. 64" % (k,))
+    return int(k)
+
+
+def _feature_rows(f, name):
+    """(n, dim) float32 descriptor rows, checked before any call reaches the library."""
+    f = np.ascontiguousarray(f, dtype=np.float32)
+    if f.ndim != 2 or f.shape[0] < 1 or not 1 <= f.shape[1] <= 64:
+        raise ValueError("%s: descriptor rows must be (n >= 1, 1 <= dim <= 64), got shape %s" % (name, f.shape))
+    return f
+
+
 def resolve_devices(spec):
     """A device list from an int, a sequence, "all", or a string like "0,1,2,3" (what OA_DEVICES may hold)."""
     if spec is None:
@@ -278,7 +292,8 @@ class IcpEngine:
              "watchdog_aborts": 17, "nn_ms_min": 18, "nn_ms_max": 19, "safe_radii": 20,
              "tri_ring": 21, "tri_ring_accepts": 22, "exchange_us": 23, "rccl_fallbacks": 24, "rccl_ranks_last": 25, "search_clock_mhz": 26, "brute_queue_wgs": 27,
              "metric": 28, "plane_rank": 29, "robust_loss": 30, "weight_sum": 31,
-             "robust_scale": 32, "robust_quantile": 33}
+             "robust_scale": 32, "robust_quantile": 33, "target_normals": 34,
+             "target_features": 35}
     EXCHANGE_NAMES = {-1: None, 0: "mailbox (pinned host memory)", 1: "rccl", 2: "mailbox (peer-mapped device memory)"}
 
     def exchange_info(self):
@@ -479,6 +494,74 @@ class IcpEngine:
         out = {name: getattr(rep, name) for name, _ in capi.CoarseReport._fields_}
         out["matrix_world"] = self.matrix_world()
         return out
+
+    def coarse_align_poses(self, mx_align_list, thresh, n_refine=8, refine_iters=10, stride=4) -> dict:
+        """coarse_align's recipe over caller-supplied candidates (P x 4 x 4) instead of the rotation set: score them and the
+        current pose, refine the n_refine cheapest, make the cheapest matrix_world.  Returns the report as a dict, with the new
+        "matrix_world"; best_candidate == P names the incoming pose."""
+        m = capi.as_f32(mx_align_list).reshape(-1, 4, 4)
+        cs = capi.CoarseSettings(0, int(n_refine), int(refine_iters), int(stride), float(thresh))
+        rep = capi.CoarseReport()
+        self._chk(self._L.oa_coarse_align_poses(self._h, capi.fptr(m), len(m), C.byref(cs), C.byref(rep)))
+        out = {name: getattr(rep, name) for name, _ in capi.CoarseReport._fields_}
+        out["matrix_world"] = self.matrix_world()
+        return out
+
+    def target_fpfh(self, k=16, keep=True):
+        """Vertex-mode targets with normals: the Fast Point Feature Histogram of every target vertex from its k nearest
+        neighbours, (nt, 33) float32; an all-zero row means "no descriptor".  keep: the descriptors stay on the device for
+        feature_candidates(tgt_feat=None) until the next set_target.  4 <= k <= min(64, nt)."""
+        k = _fpfh_k(k)
+        out = np.empty((max(1, self.n_target), capi.OA_FPFH_DIM), np.float32)
+        self._chk(self._L.oa_target_fpfh(self._h, k, capi.fptr(out), int(bool(keep))))
+        return out[: self.n_target]
+
+    def match_features(self, fa, fb):
+        """Nearest rows in descriptor space: for every row of fa (na, dim) the row of fb (nb, dim) at the smallest squared L2
+        distance: (idx int32 (na,), d2 float32 (na,), d2_second float32 (na,)).  Ties go to the lowest index; all-zero rows mean
+        "no descriptor" and neither query nor answer (index -1, +inf).  1 <= dim <= 64."""
+        fa, fb = _feature_rows(fa, "fa"), _feature_rows(fb, "fb")
+        if fa.shape[1] != fb.shape[1]:
+            raise ValueError("match_features: rows of %d and of %d floats" % (fa.shape[1], fb.shape[1]))
+        idx = np.empty(len(fa), np.int32)
+        d2 = np.empty(len(fa), np.float32)
+        sec = np.empty(len(fa), np.float32)
+        self._chk(self._L.oa_match_features(self._h, capi.fptr(fa), len(fa), capi.fptr(fb), len(fb), fa.shape[1],
+                                            idx.ctypes.data_as(C.POINTER(C.c_int32)), capi.fptr(d2), capi.fptr(sec)))
+        return idx, d2, sec
+
+    def feature_candidates(self, src_feat, tgt_feat=None, n_hyp=4096, ratio=0.9, mutual=True, edge_tol=0.9, min_edge=0.0, seed=0,
+                           triples=None):
+        """Candidate align matrices from matched descriptors: src_feat (one row per SOURCE VERTEX, as set_source_normals takes
+        its rows), tgt_feat (one row per target vertex; None: what target_fpfh(keep=True) left on the device).  Pairs that are mutual nearest rows and pass the ratio test (mutual
+        False: the ratio test alone), ordered by source vertex; n_hyp triples of them (`triples`, (n_hyp, 3) pair indices, or a
+        hashed draw from `seed`); every triple whose edge lengths agree within edge_tol and exceed min_edge (0: 5 % of the
+        target's diagonal) gives the rigid motion of its three pairs.  Returns ((n, 4, 4) float32, report dict); n may be 0."""
+        src_feat = _feature_rows(src_feat, "src_feat")
+        if tgt_feat is not None:
+            tgt_feat = _feature_rows(tgt_feat, "tgt_feat")
+            if src_feat.shape[1] != tgt_feat.shape[1]:
+                raise ValueError("feature_candidates: rows of %d and of %d floats" % (src_feat.shape[1], tgt_feat.shape[1]))
+            if tgt_feat.shape[0] != self.n_target:
+                raise ValueError("feature_candidates: %d descriptor rows for %d target vertices" % (tgt_feat.shape[0], self.n_target))
+        tri = None
+        if triples is not None:
+            tri = np.ascontiguousarray(triples, dtype=np.int32)
+            if tri.ndim != 2 or tri.shape[1] != 3 or len(tri) < 1:
+                raise ValueError("feature_candidates: triples must be (n_hyp, 3) pair indices")
+            n_hyp = len(tri)
+        n_hyp = int(n_hyp)
+        if not 1 <= n_hyp <= 65535:
+            raise ValueError("feature_candidates: n_hyp %d outside 1 .. 65535" % n_hyp)
+        fs = capi.FeatureSettings(src_feat.shape[1], n_hyp, int(bool(mutual)), int(seed) & 0xFFFFFFFF, float(ratio), float(edge_tol),
+                                  float(min_edge))
+        rep = capi.FeatureReport()
+        out = np.empty((n_hyp, 4, 4), np.float32)
+        n = C.c_int32(0)
+        self._chk(self._L.oa_feature_candidates(self._h, capi.fptr(src_feat), len(src_feat), capi.fptr(tgt_feat) if tgt_feat is not None else None, C.byref(fs),
+                                                tri.ctypes.data_as(C.POINTER(C.c_int32)) if tri is not None else None,
+                                                capi.fptr(out), C.byref(n), C.byref(rep)))
+        return out[: n.value].copy(), {name: getattr(rep, name) for name, _ in capi.FeatureReport._fields_ if name != "reserved"}
 
     # ---- split phase (one process per GPU)
     def run_begin(self, iters=50, thresh=0.5, target_d=0.01, use_target=True, with_scale=False, early_exit=True):

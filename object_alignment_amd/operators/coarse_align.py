@@ -5,6 +5,12 @@ landmarks by hand, operators/align_pick_points.py).
 centroid by a super-Fibonacci set of rotations, centroid on centroid -- are scored on the GPU in one launch by the truncated mean
 distance of a sample to the target, the best few get a short point loop, and the cheapest becomes matrix_world
 (oa_coarse_align).  `IcpAlign.run(..., coarse=CoarseSettings())` runs it on the same engine in front of the usual loop.
+
+A source that is a PART of the target (one tooth against an arch, two passes that overlap by half) has its centroid far from the
+target's: no rotation about it is near the answer.  `CoarseSettings(method="features")` takes the candidates from matched local
+shape descriptors instead (FPFH of both clouds, mutual nearest rows, rigid motions of triples of matched points:
+oa_target_fpfh, oa_feature_candidates) and hands them to the same scoring and refinement (oa_coarse_align_poses);
+`method="both"` scores the two lists together.
 """
 from __future__ import annotations
 
@@ -14,6 +20,7 @@ import numpy as np
 
 from ..functions.general import default_engine
 
+METHODS = ("rotations", "features", "both")
 THRESH_FRACTION = 0.1       # thresh=None: this part of the target's world-space bounding-box diagonal
 
 
@@ -24,8 +31,28 @@ class CoarseSettings:
     refine_iters: int = 10          # iterations of that loop
     stride: int = 4                 # every stride-th point of the selection is scored and refined
     thresh: float | None = None     # truncation / pair distance, world units; None = THRESH_FRACTION x the target's diagonal
+    method: str = "rotations"       # where the candidates come from: "rotations", "features" (vertex-mode targets) or "both"
+    feature_k: int = 16             # neighbours per FPFH descriptor
+    normal_k: int = 16              # neighbours per estimated normal (the source's; the target's when none are installed)
+    n_hyp: int = 4096               # triples of matched points
+    edge_tol: float = 0.9           # a triple's edge lengths must agree within [edge_tol, 1 / edge_tol]
+    ratio: float = 0.9              # nearest / second nearest descriptor distance (not squared) a match may have
+    mutual: bool = True             # a match must be the nearest row in both directions
+    seed: int = 0                   # of the hashed draw of the triples
 
     def __post_init__(self):
+        if self.method not in METHODS:
+            raise ValueError("CoarseSettings.method = %r (one of %s)" % (self.method, ", ".join(repr(m) for m in METHODS)))
+        for name, lo, hi in (("feature_k", 4, 64), ("normal_k", 3, 64), ("n_hyp", 1, 65535), ("seed", 0, 0xFFFFFFFF)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError("CoarseSettings.%s = %r (an integer in %d .. %d)" % (name, v, lo, hi))
+        if not (isinstance(self.edge_tol, (int, float)) and 0.0 < self.edge_tol <= 1.0):
+            raise ValueError("CoarseSettings.edge_tol = %r (in (0, 1])" % (self.edge_tol,))
+        if not (isinstance(self.ratio, (int, float)) and np.isfinite(self.ratio) and self.ratio > 0.0):
+            raise ValueError("CoarseSettings.ratio = %r (finite and > 0)" % (self.ratio,))
+        if not isinstance(self.mutual, (bool, np.bool_)):
+            raise ValueError("CoarseSettings.mutual = %r (True or False)" % (self.mutual,))
         for name, lo, hi in (("n_rot", 1, 65536), ("n_refine", 1, 4096), ("refine_iters", 0, 10000), ("stride", 1, 1 << 30)):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
@@ -45,11 +72,47 @@ def default_thresh(target_xyz, mx_base) -> float:
     return THRESH_FRACTION * float(np.linalg.norm(w.max(axis=0) - w.min(axis=0)))
 
 
-def coarse_stage(engine, settings: CoarseSettings, target_xyz, mx_base) -> dict:
-    """The coarse stage on an engine whose target, source and matrices are set: matrix_world moves to the pose it found."""
+def feature_poses(engine, settings: CoarseSettings, source_xyz) -> tuple:
+    """Candidate poses from matched FPFH descriptors on an engine whose vertex-mode target, source and matrices are set:
+    ((n, 4, 4) float32, report dict).  Installs estimated target normals (away from the centroid) when the target has none."""
+    from .. import fpfh
+    rep = {"estimated_target_normals": False}
+    if engine.stat("target_normals") == 0.0:
+        engine.estimate_target_normals(k=min(settings.normal_k, engine.n_target), orient="away", install=True)
+        rep["estimated_target_normals"] = True
+    engine.target_fpfh(k=min(settings.feature_k, engine.n_target), keep=True)
+    src_feat = fpfh(source_xyz, k=settings.feature_k, normal_k=settings.normal_k, device=engine.device)
+    poses, frep = engine.feature_candidates(src_feat, None, n_hyp=settings.n_hyp, ratio=settings.ratio, mutual=settings.mutual,
+                                            edge_tol=settings.edge_tol, seed=settings.seed)
+    rep.update(("feature_" + k, v) for k, v in frep.items())
+    return poses, rep
+
+
+def coarse_stage(engine, settings: CoarseSettings, target_xyz, mx_base, source_xyz=None) -> dict:
+    """The coarse stage on an engine whose target, source and matrices are set: matrix_world moves to the pose it found.
+    source_xyz: all vertices of the source, what method "features" / "both" computes the source's descriptors from.
+    report["status"]: "ok", or "fallback: ..." when the features gave no candidate and (method "features") the incoming pose
+    stays or (method "both") the rotations alone were scored.  Never raises for want of features."""
     thresh = settings.thresh if settings.thresh is not None else default_thresh(target_xyz, mx_base)
-    return engine.coarse_align(thresh, n_rot=settings.n_rot, n_refine=settings.n_refine, refine_iters=settings.refine_iters,
-                               stride=settings.stride)
+    kw = dict(n_refine=settings.n_refine, refine_iters=settings.refine_iters, stride=settings.stride)
+    if settings.method == "rotations":
+        return engine.coarse_align(thresh, n_rot=settings.n_rot, **kw)
+    if source_xyz is None:
+        raise ValueError("CoarseSettings.method = %r needs source_xyz" % (settings.method,))
+    poses, frep = feature_poses(engine, settings, source_xyz)
+    status = "ok"
+    if len(poses) == 0:
+        status = "fallback: no candidate from the features (%d matched pairs)" % frep["feature_n_pairs"]
+    if settings.method == "both":
+        poses = np.concatenate([engine.coarse_candidates(settings.n_rot), poses.reshape(-1, 4, 4)])
+    if len(poses) == 0:
+        rep = {"n_candidates": 0, "matrix_world": engine.matrix_world()}
+    else:
+        rep = engine.coarse_align_poses(poses, thresh, **kw)
+    rep.update(frep)
+    rep["status"] = status
+    rep["method"] = settings.method
+    return rep
 
 
 class CoarseAlign:
@@ -68,5 +131,5 @@ class CoarseAlign:
             eng.set_target(target_xyz)
         eng.set_source(source_xyz, vlist=vlist, stride=1)
         eng.set_matrices(mx_align, mx_base)
-        rep = coarse_stage(eng, self.settings, target_xyz, mx_base)
+        rep = coarse_stage(eng, self.settings, target_xyz, mx_base, source_xyz=source_xyz)
         return rep["matrix_world"], rep

@@ -252,7 +252,7 @@ class IcpAlign:
         self.last_coarse = None
         if coarse is not None:
             from .coarse_align import coarse_stage
-            self.last_coarse = coarse_stage(eng, coarse, target_xyz, mx_base)
+            self.last_coarse = coarse_stage(eng, coarse, target_xyz, mx_base, source_xyz=source_xyz)
         return eng.run(iters=s.icp_iterations, thresh=thresh, target_d=s.target_d, use_target=s.use_target,
                        with_scale=(s.align_meth == "1"), early_exit=early_exit)
 
