@@ -1121,45 +1121,35 @@ int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
     if (!c->surface) c->win_seeds = true;                          // (the winner records of this pass seed the next search)
     oa::PairOut po{};
     const oa::NormalTest nrm = normal_test(c);
+    // the leading arguments of every kernel that opens with pair_fetch (oa_kernels.hpp); each arm adds its own behind them
+    float4 *win = c->surface ? (float4 *)nullptr : c->d_win;
+    const float4 *tri9 = c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr;
+    const float *plane_tn = c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n;
+    auto launch = [&](auto *kern, int blocks, int threads, auto... tail) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3((unsigned)threads), 0, c->stream, (const oa::DevState *)c->d_state,
+                           (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, win, tri9, nrm, tail...);
+    };
+    // the end of the search, for the step record (with the scale taken from the residuals, launch_robust_scale has stamped it)
+    unsigned long long *stamp = c->loop_active ? &c->d_state->t_acc_start : (unsigned long long *)nullptr;
+    unsigned long long *stamp_w = auto_scale(c) ? (unsigned long long *)nullptr : stamp;
+    const float *w_slot = c->d_w;
     if (emit) {
         po.valid = c->d_valid; po.b = c->d_b; po.dist = c->d_dist; po.nn_idx = nn_idx; po.nn_d2 = nn_d2; po.perm = c->d_perm;
-        hipLaunchKernelGGL(oa::k_pair_accumulate<true>, dim3(c->acc_blocks), dim3(oa::ACC_THREADS), 0, c->stream,
-                           c->d_state, c->d_src4, c->ns, c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
-                           c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->d_partials, po,
-                           (unsigned long long *)nullptr);
+        launch(oa::k_pair_accumulate<true>, c->acc_blocks, oa::ACC_THREADS, c->d_partials, po, (unsigned long long *)nullptr);
     } else if (c->metric == OA_METRIC_PLANE) {
-        // (the end of the search: with the scale taken from the residuals, launch_robust_scale has stamped it already)
-        unsigned long long *stamp = c->loop_active && !auto_scale(c) ? &c->d_state->t_acc_start : (unsigned long long *)nullptr;
         auto *kern = weighted(c) ? oa::k_pair_accumulate_plane<true> : oa::k_pair_accumulate_plane<false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
-                           (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
-                           c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n,
-                           (const float *)c->d_w, c->d_partials, stamp);
+        launch(kern, plane_blocks(c), plane_threads(c), plane_tn, w_slot, c->d_partials, stamp_w);
     } else if (c->metric == OA_METRIC_GICP) {
         // (begin_loop refuses an estimated scale under this metric: the search always ends here)
-        unsigned long long *stamp = c->loop_active ? &c->d_state->t_acc_start : (unsigned long long *)nullptr;
         auto *kern = weighted(c) ? oa::k_pair_accumulate_gicp<true> : oa::k_pair_accumulate_gicp<false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
-                           (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
-                           c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n,
-                           (const float *)c->d_src_n, (const float *)c->d_w, c->d_partials, stamp);
+        launch(kern, plane_blocks(c), plane_threads(c), plane_tn, (const float *)c->d_src_n, w_slot, c->d_partials, stamp);
     } else if (weighted(c)) {
-        unsigned long long *stamp = c->loop_active && !auto_scale(c) ? &c->d_state->t_acc_start : (unsigned long long *)nullptr;
         static_assert(oa::WEIGHTED_THREADS == oa::PLANE_THREADS, "plane_threads / plane_blocks size both launches");
-        hipLaunchKernelGGL(oa::k_pair_accumulate_weighted, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
-                           (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
-                           c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, (const float *)c->d_w,
-                           c->d_partials, stamp);
+        launch(oa::k_pair_accumulate_weighted, plane_blocks(c), plane_threads(c), w_slot, c->d_partials, stamp_w);
     } else if (canon_blocks(c) > 0) {
-        hipLaunchKernelGGL(oa::k_pair_accumulate_canon, dim3((unsigned)canon_blocks(c)), dim3((unsigned)canon_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
-                           (const float4 *)c->d_src4, c->ns, canon_lanes(c), (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
-                           c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->d_partials,
-                           c->loop_active ? &c->d_state->t_acc_start : (unsigned long long *)nullptr);
+        launch(oa::k_pair_accumulate_canon, canon_blocks(c), canon_threads(c), canon_lanes(c), c->d_partials, stamp);
     } else {
-        hipLaunchKernelGGL(oa::k_pair_accumulate<false>, dim3(c->acc_blocks), dim3(oa::ACC_THREADS), 0, c->stream,
-                           c->d_state, c->d_src4, c->ns, c->d_tgt_xyz, c->d_keys, c->d_prev, c->surface ? (float4 *)nullptr : c->d_win,
-                           c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm, c->d_partials, po,
-                           c->loop_active ? &c->d_state->t_acc_start : (unsigned long long *)nullptr);
+        launch(oa::k_pair_accumulate<false>, c->acc_blocks, oa::ACC_THREADS, c->d_partials, po, stamp);
     }
     HIPCHK(hipGetLastError());
     return OA_OK;
@@ -1170,12 +1160,12 @@ int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
 int launch_robust_scale(oa_ctx *c)
 {
     const oa::NormalTest nrm = normal_test(c);
-    const bool plane = c->metric == OA_METRIC_PLANE;
-    auto *kern = plane ? oa::k_residual_keys<true> : oa::k_residual_keys<false>;
+    // (launch_accumulate's leading arguments and selections, read-only and without prev; <false> never reads plane_tn)
+    auto *kern = c->metric == OA_METRIC_PLANE ? oa::k_residual_keys<true> : oa::k_residual_keys<false>;
     hipLaunchKernelGGL(kern, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
                        (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, (const unsigned long long *)c->d_keys,
                        c->surface ? (const float4 *)nullptr : (const float4 *)c->d_win, c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm,
-                       (plane && !c->surface) ? (const float *)c->d_tgt_n : (const float *)nullptr, (const float *)c->d_w, c->d_rkeys, c->d_sel_hist,
+                       c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n, (const float *)c->d_w, c->d_rkeys, c->d_sel_hist,
                        &c->d_state->t_acc_start);
     const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
     for (int level = 0; level < oa::SEL_LEVELS; ++level) {
@@ -1444,8 +1434,8 @@ int iter_fused(oa_ctx *c, bool timed)
         hipLaunchKernelGGL(oa::k_reduce_solve_update_plane, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, c->d_state,
                            (const double *)c->d_partials, sel.n, c->d_sums, c->d_hist, c->d_todo_count);
     else
-    hipLaunchKernelGGL(oa::k_reduce_solve_update, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, c->d_state,
-                       (const double *)c->d_partials, sel, c->d_sums, c->d_hist, c->d_todo_count, fused ? 1 : 0);
+        hipLaunchKernelGGL(oa::k_reduce_solve_update, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, c->d_state,
+                           (const double *)c->d_partials, sel, c->d_sums, c->d_hist, c->d_todo_count, fused ? 1 : 0);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }

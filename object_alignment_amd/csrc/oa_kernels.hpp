@@ -2012,6 +2012,80 @@ __device__ __forceinline__ bool pair_eval(const DevState *__restrict__ st, float
     return valid;
 }
 
+// ---- the per-slot correspondence fetch: what "the same pair" means for every stand-alone accumulation kernel and for
+// k_residual_keys.  Slot i's search result keys[i] (distance bits << 32 | index) -> co_find = the source point in base-local
+// space (general.py:287) -> co1 = its correspondence there (general.py:297) and that correspondence's normal tn -> pair_eval.
+//   surface mode (tri9):  co1 = the closest point on triangle idx; tn = the geometric face normal, in the operand order of
+//                         Blender's normal_tri_v3 (cross(a - b, b - c), not normalised).
+//   vertex mode:          co1 = target vertex idx, from the slot's winner record (coordinates + index) when its index matches,
+//                         else gathered from tgt_xyz.  The grid and tree searches leave this search's winner in the record;
+//                         after a brute-force search it still holds the previous winner, which in a converging loop is mostly
+//                         the same vertex.  win == nullptr: no records (surface mode), every slot gathers.
+// The two switches are the ONLY differences between the callers:
+//   WRITES    true  (the accumulating kernels): keys[i] is reset to KEY_EMPTY for the next iteration's atomicMin, prev[i]
+//                   (if given) takes the index as the seed of the next filtered search, a record that missed is rewritten.
+//             false (k_residual_keys): keys, prev and win stay as the search left them; prev is not read at all.
+//   METRIC_N  false (point metric): tn is read by the normal-angle test alone -- nrm.tgt_n[idx] resp. the face normal when
+//                   nrm.src_n is set, zeros otherwise.
+//             true  (plane, GICP): tn is the metric's normal -- plane_tn[idx] resp. the face normal, always.
+// f.p is loaded before the IDX_NONE test (the callers use it for a slot without a pair too); a slot without a pair leaves
+// tn, b and dist zero.  Returns pair_eval's verdict.
+struct PairFetch {
+    float4 p;                   // src4[i]
+    unsigned long long key;     // keys[i] as the search left it
+    uint32_t idx;               // its index part (IDX_NONE: no candidate)
+    float tn[3];                // the correspondence's normal, base-local
+    float bx, by, bz;           // imx1 @ (mx2 @ co1)
+    double dist;                // the world-space pair distance
+};
+
+template <bool WRITES, bool METRIC_N>
+__device__ __forceinline__ bool pair_fetch(const DevState *__restrict__ st, const float4 *__restrict__ src4, int i,
+                                           const float *__restrict__ tgt_xyz,
+                                           std::conditional_t<WRITES, unsigned long long, const unsigned long long> *__restrict__ keys,
+                                           int *__restrict__ prev, std::conditional_t<WRITES, float4, const float4> *__restrict__ win,
+                                           const float4 *__restrict__ tri9, const NormalTest &nrm,
+                                           const float *__restrict__ plane_tn, double thresh, PairFetch &f)
+{
+    f.key = keys[i];
+    if constexpr (WRITES) keys[i] = KEY_EMPTY;
+    const uint32_t idx = f.idx = (uint32_t)f.key;
+    if constexpr (WRITES) { if (prev) prev[i] = (idx == IDX_NONE) ? -1 : (int)idx; }
+    f.bx = f.by = f.bz = 0.f;
+    f.dist = 0.0;
+    f.tn[0] = f.tn[1] = f.tn[2] = 0.f;
+    f.p = src4[i];
+    float4 wrec = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+    if (win) wrec = win[i];
+    if (idx == IDX_NONE) return false;
+    float cx, cy, cz;
+    co_find(st, f.p.x, f.p.y, f.p.z, cx, cy, cz);
+    float qx, qy, qz;
+    if (tri9) {
+        float ta[3], tb[3], tc[3], rr[3];
+        const float cf[3] = { cx, cy, cz };
+        load_tri(tri9, idx, ta, tb, tc);
+        closest_on_tri(cf, ta, tb, tc, rr);
+        qx = rr[0]; qy = rr[1]; qz = rr[2];
+        if (METRIC_N || nrm.src_n) {
+            const float e1[3] = { ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2] };
+            const float e2[3] = { tb[0] - tc[0], tb[1] - tc[1], tb[2] - tc[2] };
+            f.tn[0] = e1[1] * e2[2] - e1[2] * e2[1];
+            f.tn[1] = e1[2] * e2[0] - e1[0] * e2[2];
+            f.tn[2] = e1[0] * e2[1] - e1[1] * e2[0];
+        }
+    } else {
+        if ((uint32_t)__float_as_int(wrec.w) == idx) { qx = wrec.x; qy = wrec.y; qz = wrec.z; }
+        else {
+            qx = tgt_xyz[3ll * idx]; qy = tgt_xyz[3ll * idx + 1]; qz = tgt_xyz[3ll * idx + 2];
+            if constexpr (WRITES) { if (win) win[i] = make_float4(qx, qy, qz, __int_as_float((int)idx)); }
+        }
+        if constexpr (METRIC_N) { f.tn[0] = plane_tn[3ll * idx]; f.tn[1] = plane_tn[3ll * idx + 1]; f.tn[2] = plane_tn[3ll * idx + 2]; }
+        else if (nrm.src_n) { f.tn[0] = nrm.tgt_n[3ll * idx]; f.tn[1] = nrm.tgt_n[3ll * idx + 1]; f.tn[2] = nrm.tgt_n[3ll * idx + 2]; }
+    }
+    return pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, f.tn, thresh, f.bx, f.by, f.bz, f.dist);
+}
+
 __device__ __forceinline__ void pair_add(double (&acc)[NSUMS], float p_x, float p_y, float p_z, float bx, float by, float bz,
                                          double dist, double pvx, double pvy, double pvz, double d_pivot)
 {
@@ -2181,55 +2255,16 @@ __global__ __launch_bounds__(ACC_THREADS) void k_pair_accumulate(const DevState 
 
     if (!halted) {
         for (int i = blockIdx.x * ACC_THREADS + threadIdx.x; i < ns; i += gridDim.x * ACC_THREADS) {
-            const unsigned long long key = keys[i];
-            keys[i] = KEY_EMPTY;                                   // ready for the next iteration's atomicMin
-            const uint32_t idx = (uint32_t)key;
-            if (prev) prev[i] = (idx == IDX_NONE) ? -1 : (int)idx;  // seed for the next iteration's filtered search
-            bool valid = false;
-            float bx = 0.f, by = 0.f, bz = 0.f;
-            double dist = 0.0;
-            const float4 p = src4[i];
-            // vertex mode: the slot's winner record (coordinates + index).  The grid and tree searches leave this
-            // search's winner there; after a brute-force search it still holds the previous winner, which in a
-            // converging loop is mostly the same vertex.  A matching index saves the gather from the target array.
-            float4 wrec = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-            if (win) wrec = win[i];
-            if (idx != IDX_NONE) {
-                float cx, cy, cz;
-                co_find(st, p.x, p.y, p.z, cx, cy, cz);       // co_find                   (general.py:287)
-                float qx, qy, qz;                                    // co1 (general.py:297)
-                float tn[3] = { 0.f, 0.f, 0.f };                     // correspondence normal (only for the extension)
-                if (tri9) {                                          // surface mode: closest point on triangle `idx`
-                    float ta[3], tb[3], tc[3], rr[3];
-                    const float cf[3] = { cx, cy, cz };
-                    load_tri(tri9, idx, ta, tb, tc);
-                    closest_on_tri(cf, ta, tb, tc, rr);
-                    qx = rr[0]; qy = rr[1]; qz = rr[2];
-                    if (nrm.src_n) {                                 // geometric face normal (Blender normal_tri_v3 order)
-                        const float e1[3] = { ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2] };
-                        const float e2[3] = { tb[0] - tc[0], tb[1] - tc[1], tb[2] - tc[2] };
-                        tn[0] = e1[1] * e2[2] - e1[2] * e2[1];
-                        tn[1] = e1[2] * e2[0] - e1[0] * e2[2];
-                        tn[2] = e1[0] * e2[1] - e1[1] * e2[0];
-                    }
-                } else {                                             // vertex mode: target vertex `idx`
-                    if ((uint32_t)__float_as_int(wrec.w) == idx) { qx = wrec.x; qy = wrec.y; qz = wrec.z; }
-                    else {
-                        qx = tgt_xyz[3ll * idx]; qy = tgt_xyz[3ll * idx + 1]; qz = tgt_xyz[3ll * idx + 2];
-                        if (win) win[i] = make_float4(qx, qy, qz, __int_as_float((int)idx));
-                    }
-                    if (nrm.src_n) { tn[0] = nrm.tgt_n[3ll * idx]; tn[1] = nrm.tgt_n[3ll * idx + 1]; tn[2] = nrm.tgt_n[3ll * idx + 2]; }
-                }
-                valid = pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, tn, thresh, bx, by, bz, dist);
-            }
+            PairFetch f;
+            const bool valid = pair_fetch<true, false>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, nullptr, thresh, f);
             if (EMIT) {
                 const long long o = out.perm ? out.perm[i] : i;
                 out.valid[o] = valid ? 1 : 0;
-                out.b[3 * o] = bx; out.b[3 * o + 1] = by; out.b[3 * o + 2] = bz;
-                out.dist[o] = dist;
-                if (out.nn_idx) { out.nn_idx[o] = (int)idx; out.nn_d2[o] = __uint_as_float((uint32_t)(key >> 32)); }
+                out.b[3 * o] = f.bx; out.b[3 * o + 1] = f.by; out.b[3 * o + 2] = f.bz;
+                out.dist[o] = f.dist;
+                if (out.nn_idx) { out.nn_idx[o] = (int)f.idx; out.nn_d2[o] = __uint_as_float((uint32_t)(f.key >> 32)); }
             }
-            if (valid) pair_add(acc, p.x, p.y, p.z, bx, by, bz, dist, pvx, pvy, pvz, d_pivot);
+            if (valid) pair_add(acc, f.p.x, f.p.y, f.p.z, f.bx, f.by, f.bz, f.dist, pvx, pvy, pvz, d_pivot);
         }
     }
     block_store_partial(acc, red, partials + (long long)blockIdx.x * NSUMS);
@@ -2246,10 +2281,10 @@ __global__ __launch_bounds__(ACC_THREADS) void k_pair_accumulate(const DevState 
 constexpr int CANON_THREADS = 512;
 #if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
 __global__ __launch_bounds__(CANON_THREADS) void k_pair_accumulate_canon(const DevState *__restrict__ st, const float4 *__restrict__ src4,
-                                                               int ns, int L, const float *__restrict__ tgt_xyz,
+                                                               int ns, const float *__restrict__ tgt_xyz,
                                                                unsigned long long *__restrict__ keys, int *__restrict__ prev,
                                                                float4 *__restrict__ win, const float4 *__restrict__ tri9,
-                                                               NormalTest nrm, double *__restrict__ partials,
+                                                               NormalTest nrm, int L, double *__restrict__ partials,
                                                                unsigned long long *__restrict__ t_acc_start)
 {
     __shared__ double red[CANON_THREADS / 64][NSUMS];
@@ -2259,49 +2294,11 @@ __global__ __launch_bounds__(CANON_THREADS) void k_pair_accumulate_canon(const D
     const int i = gt / L;
     const bool mine = (gt - i * L) == 0 && i < ns;
     bool valid = false;
-    float bx = 0.f, by = 0.f, bz = 0.f;
-    double dist = 0.0;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (mine) {
-        const unsigned long long key = keys[i];
-        keys[i] = KEY_EMPTY;                                       // ready for the next iteration's atomicMin
-        const uint32_t idx = (uint32_t)key;
-        if (prev) prev[i] = (idx == IDX_NONE) ? -1 : (int)idx;
-        p = src4[i];
-        float4 wrec = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-        if (win) wrec = win[i];
-        if (idx != IDX_NONE) {
-            float cx, cy, cz;
-            co_find(st, p.x, p.y, p.z, cx, cy, cz);           // co_find                   (general.py:287)
-            float qx, qy, qz;
-            float tn[3] = { 0.f, 0.f, 0.f };
-            if (tri9) {
-                float ta[3], tb[3], tc[3], rr[3];
-                const float cf[3] = { cx, cy, cz };
-                load_tri(tri9, idx, ta, tb, tc);
-                closest_on_tri(cf, ta, tb, tc, rr);
-                qx = rr[0]; qy = rr[1]; qz = rr[2];
-                if (nrm.src_n) {
-                    const float e1[3] = { ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2] };
-                    const float e2[3] = { tb[0] - tc[0], tb[1] - tc[1], tb[2] - tc[2] };
-                    tn[0] = e1[1] * e2[2] - e1[2] * e2[1];
-                    tn[1] = e1[2] * e2[0] - e1[0] * e2[2];
-                    tn[2] = e1[0] * e2[1] - e1[1] * e2[0];
-                }
-            } else {
-                if ((uint32_t)__float_as_int(wrec.w) == idx) { qx = wrec.x; qy = wrec.y; qz = wrec.z; }
-                else {
-                    qx = tgt_xyz[3ll * idx]; qy = tgt_xyz[3ll * idx + 1]; qz = tgt_xyz[3ll * idx + 2];
-                    if (win) win[i] = make_float4(qx, qy, qz, __int_as_float((int)idx));
-                }
-                if (nrm.src_n) { tn[0] = nrm.tgt_n[3ll * idx]; tn[1] = nrm.tgt_n[3ll * idx + 1]; tn[2] = nrm.tgt_n[3ll * idx + 2]; }
-            }
-            valid = pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, tn, st->thresh, bx, by, bz, dist);
-        }
-    }
+    PairFetch f = {};
+    if (mine) valid = pair_fetch<true, false>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, nullptr, st->thresh, f);
     const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
-    block_store_pair(valid, (double)p.x - pvx, (double)p.y - pvy, (double)p.z - pvz, (double)bx - pvx, (double)by - pvy,
-                     (double)bz - pvz, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS);
+    block_store_pair(valid, (double)f.p.x - pvx, (double)f.p.y - pvy, (double)f.p.z - pvz, (double)f.bx - pvx, (double)f.by - pvy,
+                     (double)f.bz - pvz, f.dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS);
 }
 #endif  // !OA_FAMILY_TU
 
@@ -2343,8 +2340,8 @@ __device__ __forceinline__ void block_store_pair_weighted(bool valid, double w, 
     }
 }
 
-// k_pair_accumulate_canon with a weight per pair: the same reads, the same resetting of keys / prev / win, the same pair test
-// (pair_eval), ONE thread per source slot, the same fixed-order reduction (no float atomics).  w = w_vertex * psi(dist):
+// k_pair_accumulate_canon with a weight per pair: the same pair (pair_fetch<true, false>), ONE thread per source slot, the
+// same fixed-order reduction (no float atomics).  w = w_vertex * psi(dist):
 // dist = the world-space pair distance of pair_eval; w_slot = one weight per slot (nullptr: all 1); the loss and its scale are
 // launch-uniform (DevState).  Its workgroups depend on the shard size alone, so every search mode leaves the same rows.
 constexpr int WEIGHTED_THREADS = 512;
@@ -2362,53 +2359,18 @@ __global__ __launch_bounds__(WEIGHTED_THREADS) void k_pair_accumulate_weighted(c
     if (st->halt) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     bool valid = false;
-    float bx = 0.f, by = 0.f, bz = 0.f;
-    double dist = 0.0, w = 0.0;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    double w = 0.0;
+    PairFetch f = {};
     if (i < ns) {
-        const unsigned long long key = keys[i];
-        keys[i] = KEY_EMPTY;                                       // ready for the next iteration's atomicMin
-        const uint32_t idx = (uint32_t)key;
-        if (prev) prev[i] = (idx == IDX_NONE) ? -1 : (int)idx;
-        p = src4[i];
-        float4 wrec = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-        if (win) wrec = win[i];
-        if (idx != IDX_NONE) {
-            float cx, cy, cz;
-            co_find(st, p.x, p.y, p.z, cx, cy, cz);           // co_find                   (general.py:287)
-            float qx, qy, qz;
-            float tn[3] = { 0.f, 0.f, 0.f };
-            if (tri9) {
-                float ta[3], tb[3], tc[3], rr[3];
-                const float cf[3] = { cx, cy, cz };
-                load_tri(tri9, idx, ta, tb, tc);
-                closest_on_tri(cf, ta, tb, tc, rr);
-                qx = rr[0]; qy = rr[1]; qz = rr[2];
-                if (nrm.src_n) {
-                    const float e1[3] = { ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2] };
-                    const float e2[3] = { tb[0] - tc[0], tb[1] - tc[1], tb[2] - tc[2] };
-                    tn[0] = e1[1] * e2[2] - e1[2] * e2[1];
-                    tn[1] = e1[2] * e2[0] - e1[0] * e2[2];
-                    tn[2] = e1[0] * e2[1] - e1[1] * e2[0];
-                }
-            } else {
-                if ((uint32_t)__float_as_int(wrec.w) == idx) { qx = wrec.x; qy = wrec.y; qz = wrec.z; }
-                else {
-                    qx = tgt_xyz[3ll * idx]; qy = tgt_xyz[3ll * idx + 1]; qz = tgt_xyz[3ll * idx + 2];
-                    if (win) win[i] = make_float4(qx, qy, qz, __int_as_float((int)idx));
-                }
-                if (nrm.src_n) { tn[0] = nrm.tgt_n[3ll * idx]; tn[1] = nrm.tgt_n[3ll * idx + 1]; tn[2] = nrm.tgt_n[3ll * idx + 2]; }
-            }
-            valid = pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, tn, st->thresh, bx, by, bz, dist);
-            if (valid) {
-                w = robust_psi(st->loss, dist, st->robust_c);
-                if (w_slot) w *= (double)w_slot[i];
-            }
+        valid = pair_fetch<true, false>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, nullptr, st->thresh, f);
+        if (valid) {
+            w = robust_psi(st->loss, f.dist, st->robust_c);
+            if (w_slot) w *= (double)w_slot[i];
         }
     }
     const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
-    block_store_pair_weighted(valid, w, (double)p.x - pvx, (double)p.y - pvy, (double)p.z - pvz, (double)bx - pvx, (double)by - pvy,
-                              (double)bz - pvz, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS);
+    block_store_pair_weighted(valid, w, (double)f.p.x - pvx, (double)f.p.y - pvy, (double)f.p.z - pvz, (double)f.bx - pvx, (double)f.by - pvy,
+                              (double)f.bz - pvz, f.dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS);
 }
 #endif  // !OA_FAMILY_TU
 
@@ -2507,8 +2469,8 @@ __device__ __forceinline__ void block_store_plane(bool valid, const double (&jj)
     block_finish_plane(red, row);
 }
 
-// k_pair_accumulate_canon for the plane metric: the same reads, the same resetting of keys / prev / win, the same pair test
-// (pair_eval), then the plane row.  One thread per source slot; plane_tn: vertex mode, one base-local normal per target
+// k_pair_accumulate_canon for the plane metric: the same pair with the metric's normal (pair_fetch<true, true>), then the
+// plane row.  One thread per source slot; plane_tn: vertex mode, one base-local normal per target
 // vertex (surface mode: nullptr, the nearest triangle's geometric normal in the operand order of the normal-angle test).
 // Its workgroups depend on the shard size alone, so every search mode leaves the same rows.
 // WEIGHTED (oa_set_robust / oa_set_source_weights): w = w_vertex * psi(res_scale * |r|), r the plane residual the row is built
@@ -2531,57 +2493,24 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_plane(const D
     if (st->halt) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     bool valid = false;
-    float bx = 0.f, by = 0.f, bz = 0.f;
-    double dist = 0.0, nx = 0.0, ny = 0.0, nz = 0.0;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    double nx = 0.0, ny = 0.0, nz = 0.0;
+    PairFetch f = {};
     if (i < ns) {
-        const unsigned long long key = keys[i];
-        keys[i] = KEY_EMPTY;                                       // ready for the next iteration's atomicMin
-        const uint32_t idx = (uint32_t)key;
-        if (prev) prev[i] = (idx == IDX_NONE) ? -1 : (int)idx;
-        p = src4[i];
-        float4 wrec = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-        if (win) wrec = win[i];
-        if (idx != IDX_NONE) {
-            float cx, cy, cz;
-            co_find(st, p.x, p.y, p.z, cx, cy, cz);           // co_find                   (general.py:287)
-            float qx, qy, qz;
-            float tn[3];
-            if (tri9) {
-                float ta[3], tb[3], tc[3], rr[3];
-                const float cf[3] = { cx, cy, cz };
-                load_tri(tri9, idx, ta, tb, tc);
-                closest_on_tri(cf, ta, tb, tc, rr);
-                qx = rr[0]; qy = rr[1]; qz = rr[2];
-                const float e1[3] = { ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2] };
-                const float e2[3] = { tb[0] - tc[0], tb[1] - tc[1], tb[2] - tc[2] };
-                tn[0] = e1[1] * e2[2] - e1[2] * e2[1];
-                tn[1] = e1[2] * e2[0] - e1[0] * e2[2];
-                tn[2] = e1[0] * e2[1] - e1[1] * e2[0];
-            } else {
-                if ((uint32_t)__float_as_int(wrec.w) == idx) { qx = wrec.x; qy = wrec.y; qz = wrec.z; }
-                else {
-                    qx = tgt_xyz[3ll * idx]; qy = tgt_xyz[3ll * idx + 1]; qz = tgt_xyz[3ll * idx + 2];
-                    if (win) win[i] = make_float4(qx, qy, qz, __int_as_float((int)idx));
-                }
-                tn[0] = plane_tn[3ll * idx]; tn[1] = plane_tn[3ll * idx + 1]; tn[2] = plane_tn[3ll * idx + 2];
-            }
-            valid = pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, tn, st->thresh, bx, by, bz, dist);
-            if (valid) valid = plane_normal(st, tn, nx, ny, nz);
-        }
+        valid = pair_fetch<true, true>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, plane_tn, st->thresh, f);
+        if (valid) valid = plane_normal(st, f.tn, nx, ny, nz);
     }
     const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
     double j[6], r;
-    plane_row((double)p.x - pvx, (double)p.y - pvy, (double)p.z - pvz, (double)bx - pvx, (double)by - pvy, (double)bz - pvz, nx, ny, nz, j, r);
+    plane_row((double)f.p.x - pvx, (double)f.p.y - pvy, (double)f.p.z - pvz, (double)f.bx - pvx, (double)f.by - pvy, (double)f.bz - pvz, nx, ny, nz, j, r);
     if constexpr (WEIGHTED) {
         double w = 0.0;
         if (valid) {
             w = robust_psi(st->loss, st->res_scale * fabs(r), st->robust_c);
             if (w_slot) w *= (double)w_slot[i];
         }
-        block_store_plane<true>(valid, j, r, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE, w);
+        block_store_plane<true>(valid, j, r, f.dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE, w);
     } else
-    block_store_plane(valid, j, r, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE);
+        block_store_plane(valid, j, r, f.dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE);
 }
 #endif  // !OA_FAMILY_TU
 
@@ -2660,7 +2589,7 @@ __device__ __forceinline__ void block_store_gicp(bool valid, double a0, double a
     block_finish_plane(red, row);
 }
 
-// k_pair_accumulate_plane for this metric: the same reads and resets, the same pair test and plane_normal for n_b, plus the
+// k_pair_accumulate_plane for this metric: the same pair_fetch<true, true> and plane_normal for n_b, plus the
 // slot's source normal (src_n: float32, align-local, slot order; normalised in fp64 in plane_normal's order, n * (1 / sqrt(n2));
 // zero or non-finite length drops the pair from the step and from K, as a zero n_b does).  Launched like the plane kernel
 // (plane_threads / plane_blocks).  WEIGHTED: w = w_vertex * psi(res_scale * sqrt(e^T W e)).
@@ -2679,55 +2608,22 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_gicp(const De
     if (st->halt) return;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     bool valid = false;
-    float bx = 0.f, by = 0.f, bz = 0.f;
-    double dist = 0.0, nx = 0.0, ny = 0.0, nz = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
-    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    double nx = 0.0, ny = 0.0, nz = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+    PairFetch f = {};
     if (i < ns) {
-        const unsigned long long key = keys[i];
-        keys[i] = KEY_EMPTY;                                       // ready for the next iteration's atomicMin
-        const uint32_t idx = (uint32_t)key;
-        if (prev) prev[i] = (idx == IDX_NONE) ? -1 : (int)idx;
-        p = src4[i];
-        float4 wrec = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-        if (win) wrec = win[i];
-        if (idx != IDX_NONE) {
-            float cx, cy, cz;
-            co_find(st, p.x, p.y, p.z, cx, cy, cz);           // co_find                   (general.py:287)
-            float qx, qy, qz;
-            float tn[3];
-            if (tri9) {
-                float ta[3], tb[3], tc[3], rr[3];
-                const float cf[3] = { cx, cy, cz };
-                load_tri(tri9, idx, ta, tb, tc);
-                closest_on_tri(cf, ta, tb, tc, rr);
-                qx = rr[0]; qy = rr[1]; qz = rr[2];
-                const float e1[3] = { ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2] };
-                const float e2[3] = { tb[0] - tc[0], tb[1] - tc[1], tb[2] - tc[2] };
-                tn[0] = e1[1] * e2[2] - e1[2] * e2[1];
-                tn[1] = e1[2] * e2[0] - e1[0] * e2[2];
-                tn[2] = e1[0] * e2[1] - e1[1] * e2[0];
-            } else {
-                if ((uint32_t)__float_as_int(wrec.w) == idx) { qx = wrec.x; qy = wrec.y; qz = wrec.z; }
-                else {
-                    qx = tgt_xyz[3ll * idx]; qy = tgt_xyz[3ll * idx + 1]; qz = tgt_xyz[3ll * idx + 2];
-                    if (win) win[i] = make_float4(qx, qy, qz, __int_as_float((int)idx));
-                }
-                tn[0] = plane_tn[3ll * idx]; tn[1] = plane_tn[3ll * idx + 1]; tn[2] = plane_tn[3ll * idx + 2];
-            }
-            valid = pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, tn, st->thresh, bx, by, bz, dist);
-            if (valid) valid = plane_normal(st, tn, nx, ny, nz);
-            if (valid) {
-                const double s0 = (double)src_n[3ll * i], s1 = (double)src_n[3ll * i + 1], s2 = (double)src_n[3ll * i + 2];
-                const double n2 = (s0 * s0 + s1 * s1) + s2 * s2;
-                valid = (n2 > 0.0) && (n2 < INFINITY);
-                const double inv = 1.0 / sqrt(n2);
-                sx = s0 * inv; sy = s1 * inv; sz = s2 * inv;
-            }
+        valid = pair_fetch<true, true>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, plane_tn, st->thresh, f);
+        if (valid) valid = plane_normal(st, f.tn, nx, ny, nz);
+        if (valid) {
+            const double s0 = (double)src_n[3ll * i], s1 = (double)src_n[3ll * i + 1], s2 = (double)src_n[3ll * i + 2];
+            const double n2 = (s0 * s0 + s1 * s1) + s2 * s2;
+            valid = (n2 > 0.0) && (n2 < INFINITY);
+            const double inv = 1.0 / sqrt(n2);
+            sx = s0 * inv; sy = s1 * inv; sz = s2 * inv;
         }
     }
     const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
-    const double a0 = (double)p.x - pvx, a1 = (double)p.y - pvy, a2 = (double)p.z - pvz;
-    const double e0 = a0 - ((double)bx - pvx), e1 = a1 - ((double)by - pvy), e2 = a2 - ((double)bz - pvz);
+    const double a0 = (double)f.p.x - pvx, a1 = (double)f.p.y - pvy, a2 = (double)f.p.z - pvz;
+    const double e0 = a0 - ((double)f.bx - pvx), e1 = a1 - ((double)f.by - pvy), e2 = a2 - ((double)f.bz - pvz);
     double W[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
     if (valid) gicp_weight(st->gicp_eps, sx, sy, sz, nx, ny, nz, W);
     const double u0 = (W[0] * e0 + W[1] * e1) + W[2] * e2, u1 = (W[1] * e0 + W[3] * e1) + W[4] * e2, u2 = (W[2] * e0 + W[4] * e1) + W[5] * e2;
@@ -2739,7 +2635,7 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_gicp(const De
             if (w_slot) w *= (double)w_slot[i];
         }
     }
-    block_store_gicp<WEIGHTED>(valid, a0, a1, a2, W, u0, u1, u2, rr, dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE, w);
+    block_store_gicp<WEIGHTED>(valid, a0, a1, a2, W, u0, u1, u2, rr, f.dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE, w);
 }
 #endif  // !OA_FAMILY_TU
 
@@ -2800,9 +2696,8 @@ __device__ __forceinline__ void sel_flush(const uint32_t *bins, uint32_t *__rest
     }
 }
 
-// The residual of every slot's pair, as the weighted accumulation of this metric will see it: the same reads (keys, src4, win
-// or tri9, the normals), the same co_find, closest_on_tri, pair_eval and -- PLANE -- plane_normal / plane_row, and NO write to
-// keys, prev or win.  rkeys[i] = the bits of (float)residual (point: pair_eval's dist; plane: res_scale |n . (a' - b')|), or
+// The residual of every slot's pair, as the weighted accumulation of this metric will see it: pair_fetch<false, PLANE> (the same
+// pair, NO write to keys, prev or win) and -- PLANE -- plane_normal / plane_row.  rkeys[i] = the bits of (float)residual (point: pair_eval's dist; plane: res_scale |n . (a' - b')|), or
 // RKEY_NONE for a slot without a pair counted in K or with vertex weight 0.  Launched like the accumulation (plane_threads /
 // plane_blocks); stamps the end of the search in its place.
 template <bool PLANE>
@@ -2821,44 +2716,16 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_residual_keys(const DevState 
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t rkey = RKEY_NONE;
     if (i < ns) {
-        const uint32_t idx = (uint32_t)keys[i];
-        if (idx != IDX_NONE) {
-            const float4 p = src4[i];
-            float cx, cy, cz;
-            co_find(st, p.x, p.y, p.z, cx, cy, cz);
-            float qx, qy, qz;
-            float tn[3] = { 0.f, 0.f, 0.f };
-            if (tri9) {
-                float ta[3], tb[3], tc[3], rr[3];
-                const float cf[3] = { cx, cy, cz };
-                load_tri(tri9, idx, ta, tb, tc);
-                closest_on_tri(cf, ta, tb, tc, rr);
-                qx = rr[0]; qy = rr[1]; qz = rr[2];
-                if (PLANE || nrm.src_n) {
-                    const float e1[3] = { ta[0] - tb[0], ta[1] - tb[1], ta[2] - tb[2] };
-                    const float e2[3] = { tb[0] - tc[0], tb[1] - tc[1], tb[2] - tc[2] };
-                    tn[0] = e1[1] * e2[2] - e1[2] * e2[1];
-                    tn[1] = e1[2] * e2[0] - e1[0] * e2[2];
-                    tn[2] = e1[0] * e2[1] - e1[1] * e2[0];
-                }
-            } else {
-                float4 wrec = make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-                if (win) wrec = win[i];
-                if ((uint32_t)__float_as_int(wrec.w) == idx) { qx = wrec.x; qy = wrec.y; qz = wrec.z; }   // (the record holds the vertex's own coordinates)
-                else { qx = tgt_xyz[3ll * idx]; qy = tgt_xyz[3ll * idx + 1]; qz = tgt_xyz[3ll * idx + 2]; }
-                if constexpr (PLANE) { tn[0] = plane_tn[3ll * idx]; tn[1] = plane_tn[3ll * idx + 1]; tn[2] = plane_tn[3ll * idx + 2]; }
-                else if (nrm.src_n) { tn[0] = nrm.tgt_n[3ll * idx]; tn[1] = nrm.tgt_n[3ll * idx + 1]; tn[2] = nrm.tgt_n[3ll * idx + 2]; }
-            }
-            float bx, by, bz;
-            double dist;
-            bool valid = pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, tn, st->thresh, bx, by, bz, dist);
-            double res = dist;
+        PairFetch f;
+        if (pair_fetch<false, PLANE>(st, src4, i, tgt_xyz, keys, nullptr, win, tri9, nrm, plane_tn, st->thresh, f)) {
+            bool valid = true;
+            double res = f.dist;
             if constexpr (PLANE) {
                 double nx = 0.0, ny = 0.0, nz = 0.0;
-                if (valid) valid = plane_normal(st, tn, nx, ny, nz);
+                valid = plane_normal(st, f.tn, nx, ny, nz);
                 const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
                 double j[6], r;
-                plane_row((double)p.x - pvx, (double)p.y - pvy, (double)p.z - pvz, (double)bx - pvx, (double)by - pvy, (double)bz - pvz,
+                plane_row((double)f.p.x - pvx, (double)f.p.y - pvy, (double)f.p.z - pvz, (double)f.bx - pvx, (double)f.by - pvy, (double)f.bz - pvz,
                           nx, ny, nz, j, r);
                 res = st->res_scale * fabs(r);
             }
