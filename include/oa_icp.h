@@ -585,6 +585,47 @@ int oa_feature_candidates(oa_ctx *ctx, const float *src_feat, int64_t n_verts, c
                           const oa_feature_settings *settings, const int32_t *triples /* n_hyp x 3, or NULL */,
                           float *mx_align_out /* n_hyp x 16 */, int32_t *n_out, oa_feature_report *report);
 
+/* ---- EXTENSION: voxel-grid downsampling -- spatially uniform thinning of a cloud, where oa_set_source's stride thins by index
+ *      and keeps the density skew of a scan -- DESIGN.md 3.15.  Needs no target, source or matrices (as oa_match_features) and
+ *      touches nothing a loop reads: a running oa_iterate sequence continues with the bits it would have had.  OA_E_STATE on a
+ *      multi-device context. ------------------------------------------------------------------------------------------------- */
+typedef struct oa_voxel_report {
+    int64_t n_in, n_finite, n_voxels;   /* points given; with three finite coordinates; occupied voxels */
+    int64_t max_members;                /* most points in one voxel */
+    int32_t dims[3]; int32_t reserved;  /* cells per axis */
+    double  origin[3];                  /* the origin used */
+    double  total_ms;                   /* host time of the call */
+} oa_voxel_report;
+/* xyz: n x 3 float32, host or (on_device != 0) device memory; normals: n x 3 on the same side, or NULL.  Outputs: host memory,
+ * each may be NULL.
+ * Cells.  A point with a non-finite coordinate takes no part (it is counted in n_in - n_finite).  Origin o: the caller's, or
+ * (NULL) the componentwise minimum of the finite points.  Per axis, in fp64: c = floor(((double)x - o) / voxel) -- an IEEE
+ * subtraction, an IEEE division and floor.  dims[a] = max c_a + 1; key = (c_z dims_y + c_y) dims_x + c_x, a 64-bit integer.
+ * OA_E_BAD_ARG: voxel not finite and > 0; n outside 1 .. 2^31 - 2^20; normals without out_normals; a non-finite origin; with a
+ * caller's origin, a point with a negative c; a dims[a] above 2^21; no finite point.
+ * Rows: one per occupied voxel, in ascending key order; members = the voxel's points.
+ *   out_xyz      the members' mean: per coordinate an fp64 sum, divided once by the count in fp64, rounded once to float32
+ *   out_count    the number of members
+ *   out_rep      the original index of the member nearest to the row's FLOAT32 mean: d2 = (dx dx + dy dy) + dz dz in fp64 with
+ *                dx = (double)x - (double)mean32_x, no fused multiply-add; ties go to the lowest index
+ *   out_normals  (when normals are given) the fp64 sum of the members' normals, normalised in fp64 as n * (1 / sqrt((x x + y y) +
+ *                z z)) and rounded once; a sum of zero or non-finite length gives (0, 0, 0)
+ * The order of the sums depends on the input alone -- no float atomics, two calls give the same bits -- and is, for a row of L
+ * members listed by ascending original index m_0 < m_1 < ...:
+ *   L <= 512: eight sums s_j = m_j + m_(j+8) + m_(j+16) + ... (each from +0, ascending), joined as
+ *             ((s_0 + s_4) + (s_2 + s_6)) + ((s_1 + s_5) + (s_3 + s_7));
+ *   L >  512: the list is cut into chunks of 512 (the last one shorter); per chunk 64 sums s_l = m_l + m_(l+64) + ..., joined by
+ *             the butterfly t_l = s_l + s_(l ^ 32), then strides 16, 8, 4, 2, 1 likewise; the chunks' sums are added in chunk
+ *             order, from +0.
+ * Whenever the members' fp64 sum is exact (float32 values within one voxel share their exponent range: nearly always), the
+ * result is that of any order.
+ * *n_out = n_voxels (<= n_finite).  cap < n_voxels: OA_E_CAPACITY with *n_out and the report filled and no rows written.  Only
+ * n_voxels rows are copied to the host. */
+int oa_voxel_downsample(oa_ctx *ctx, const float *xyz, int64_t n, int on_device, const float *normals /* n x 3 or NULL, same side as xyz */,
+                        double voxel, const double origin[3] /* or NULL */, int64_t cap,
+                        float *out_xyz /* cap x 3 */, float *out_normals /* cap x 3 */, int32_t *out_count /* cap */,
+                        int64_t *out_rep /* cap */, int64_t *n_out, oa_voxel_report *rep);
+
 #ifdef __cplusplus
 }
 #endif

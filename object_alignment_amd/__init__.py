@@ -34,3 +34,13 @@ def fpfh(xyz, normals=None, k=16, normal_k=16, device=0):
         else:
             eng.set_target_normals(normals)
         return eng.target_fpfh(k=min(k, len(xyz)), keep=False)
+
+
+def voxel_downsample(xyz, voxel, normals=None, origin=None, device=0):
+    """Voxel-grid downsample of ANY point cloud on the GPU: one row per occupied cell of edge `voxel` -- the members' mean, the
+    normalised sum of their normals, their number and the index of the member nearest to the mean (a dict: xyz, normals or
+    None, count, rep, report; IcpEngine.voxel_downsample).  Opens a context of its own on `device`."""
+    from .engine import IcpEngine, _voxel_args
+    xyz, normals, origin = _voxel_args(xyz, voxel, normals, origin)
+    with IcpEngine(int(device)) as eng:
+        return eng.voxel_downsample(xyz, voxel, normals=normals, origin=origin)

@@ -58,6 +58,7 @@ SYMBOLS = [
     "oa_target_knn", "oa_estimate_target_normals",
     "oa_set_gicp", "oa_set_source_normals",
     "oa_coarse_align_poses", "oa_target_fpfh", "oa_match_features", "oa_feature_candidates",
+    "oa_voxel_downsample",
 ]
 
 
@@ -92,6 +93,11 @@ class FeatureSettings(C.Structure):
 class FeatureReport(C.Structure):
     _fields_ = [("n_pairs", C.c_int32), ("n_accepted", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32),
                 ("match_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+class VoxelReport(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_finite", C.c_int64), ("n_voxels", C.c_int64), ("max_members", C.c_int64),
+                ("dims", C.c_int32 * 3), ("reserved", C.c_int32), ("origin", C.c_double * 3), ("total_ms", C.c_double)]
 
 
 class OaError(RuntimeError):
@@ -191,6 +197,8 @@ def load(experiments: bool = False):
     L.oa_target_fpfh.argtypes = [vp, C.c_int, fp, C.c_int]
     L.oa_match_features.argtypes = [vp, fp, C.c_int64, fp, C.c_int64, C.c_int32, i32p, fp, fp]
     L.oa_feature_candidates.argtypes = [vp, fp, C.c_int64, fp, C.POINTER(FeatureSettings), i32p, fp, i32p, C.POINTER(FeatureReport)]
+    L.oa_voxel_downsample.argtypes = [vp, vp, C.c_int64, C.c_int, vp, C.c_double, dp, C.c_int64, fp, fp, i32p, ip, ip,
+                                      C.POINTER(VoxelReport)]
     _libs[experiments] = L
     return L
 

@@ -18,6 +18,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 
 #include "oa_all.hpp"                // every kernel header + oa_families.hpp: the heavy templates are `extern` here, compiled in oa_fam_*.hip
 #include "oa_sort.hpp"
+#include "oa_voxel.hpp"
 #include "../../include/oa_icp.h"
 
 #include <algorithm>
@@ -5265,5 +5266,180 @@ OA_EXPORT int oa_feature_candidates(oa_ctx *c, const float *src_feat, int64_t n_
     rep->n_accepted = n_acc;
     rep->status = n_acc > 0 ? OA_OK : OA_FEAT_NO_POSE;
     rep->total_ms = ms_since(t0);
+    return OA_OK;
+}
+
+// ================================================================================================
+// voxel-grid downsampling (EXTENSION; oa_voxel.hpp)
+// ================================================================================================
+namespace {
+// the cell of a coordinate, as k_voxel_keys computes it (the same three fp64 operations), kept a double: it may be huge
+inline double voxel_cell_of(float x, double o, double h) { return floor(((double)x - o) / h); }
+
+// order[0 .. n) = the stable ascending order of the keys' low `bits` bits (1 .. 64): one argsort for up to 32 bits, else an LSD
+// sort in stages of 30 bits -- argsort the slice read through the order so far, compose the two orders (stability does the rest)
+int voxel_sort_keys(oa_ctx *c, const unsigned long long *d_keys, int n, int bits, DevTmp<int> &order)
+{
+    const unsigned blocks = (unsigned)(((size_t)n + oa::VOX_THREADS - 1) / oa::VOX_THREADS);
+    const int width = bits <= 32 ? bits : 30;
+    DevTmp<uint32_t> part;
+    DevTmp<int> stage_order, composed;
+    HIPCHK(part.alloc((size_t)n)); HIPCHK(order.alloc((size_t)n));
+    if (bits > width) { HIPCHK(stage_order.alloc((size_t)n)); HIPCHK(composed.alloc((size_t)n)); }
+    for (int shift = 0; shift < bits; shift += width) {
+        const int w = std::min(width, bits - shift);
+        const unsigned mask = w >= 32 ? 0xFFFFFFFFu : ((1u << w) - 1u);
+        hipLaunchKernelGGL(oa::k_voxel_key_part, dim3(blocks), dim3(oa::VOX_THREADS), 0, c->stream, d_keys, shift ? (const int *)order.p : (const int *)nullptr, n,
+                           shift, mask, part.p);
+        HIPCHK(hipGetLastError());
+        if (shift == 0) { const int rc = sort_order_bits(c, part.p, order.p, (size_t)n, w); if (rc) return rc; continue; }
+        { const int rc = sort_order_bits(c, part.p, stage_order.p, (size_t)n, w); if (rc) return rc; }
+        hipLaunchKernelGGL(oa::k_gather_int, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, c->stream, (const int *)order.p, (const int *)stage_order.p, n, composed.p);
+        HIPCHK(hipGetLastError());
+        std::swap(order.p, composed.p);
+    }
+    return OA_OK;
+}
+}  // namespace
+
+OA_EXPORT int oa_voxel_downsample(oa_ctx *c, const float *xyz, int64_t n, int on_device, const float *normals, double voxel, const double origin[3],
+                                  int64_t cap, float *out_xyz, float *out_normals, int32_t *out_count, int64_t *out_rep, int64_t *n_out, oa_voxel_report *rep)
+{
+    if (!c || !xyz) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: null argument");
+    OA_NOT_MULTI(c, "oa_voxel_downsample");
+    if (!(voxel > 0.0) || !(voxel < (double)INFINITY)) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: voxel = %g (finite and > 0)", voxel);
+    if (n < 1 || n > (int64_t)2147483648ll - (1 << 20)) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: %lld points (1 .. 2^31 - 2^20)", (long long)n);
+    if (normals && !out_normals) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: normals given and nowhere to put the rows' normals");
+    if (origin)
+        for (int a = 0; a < 3; ++a)
+            if (!(fabs(origin[a]) < (double)INFINITY)) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: origin[%d] = %g", a, origin[a]);
+    if (cap < 0) cap = 0;
+    int rc = use_device(c);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    oa_voxel_report r;
+    memset(&r, 0, sizeof r);
+    r.n_in = n;
+    if (n_out) *n_out = 0;
+    if (rep) *rep = r;
+    const int ni = (int)n;
+    const unsigned pt_blocks = (unsigned)(((size_t)n + oa::VOX_THREADS - 1) / oa::VOX_THREADS);
+    DevTmp<float> tmp_xyz, tmp_nrm;
+    const float *d_xyz = nullptr, *d_nrm = nullptr;
+    if ((rc = stage_floats(c, xyz, 3 * (size_t)n, on_device, tmp_xyz, d_xyz))) return rc;
+    if (normals && (rc = stage_floats(c, normals, 3 * (size_t)n, on_device, tmp_nrm, d_nrm))) return rc;
+    // 1. the box of the finite points and their number
+    oa::VoxelGrid g{};
+    long long dims[3];
+    {
+        const int nb = (int)std::min<long long>(oa::VOX_BBOX_BLOCKS, pt_blocks);
+        DevTmp<float> d_bb;
+        DevTmp<int> d_cnt;
+        HIPCHK(d_bb.alloc(6 * (size_t)nb)); HIPCHK(d_cnt.alloc((size_t)nb));
+        hipLaunchKernelGGL(oa::k_voxel_bbox, dim3((unsigned)nb), dim3(oa::VOX_THREADS), 0, c->stream, d_xyz, ni, d_bb.p, d_cnt.p);
+        HIPCHK(hipGetLastError());
+        std::vector<float> bb(6 * (size_t)nb);
+        std::vector<int> cnt((size_t)nb);
+        HIPCHK(hipMemcpyAsync(bb.data(), d_bb.p, sizeof(float) * bb.size(), hipMemcpyDeviceToHost, c->stream));
+        if ((rc = read_small(c, cnt.data(), d_cnt.p, sizeof(int) * cnt.size()))) return rc;
+        float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+        for (int b = 0; b < nb; ++b) {
+            r.n_finite += cnt[(size_t)b];
+            for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], bb[6 * (size_t)b + a]); hi[a] = std::max(hi[a], bb[6 * (size_t)b + 3 + a]); }
+        }
+        if (rep) *rep = r;
+        if (r.n_finite < 1) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: none of the %lld points has three finite coordinates", (long long)n);
+        g.h = voxel;
+        for (int a = 0; a < 3; ++a) {
+            g.o[a] = origin ? origin[a] : (double)lo[a];
+            r.origin[a] = g.o[a];
+            // floor, the division by voxel > 0 and the subtraction are monotone: the extreme cells are the extreme coordinates'
+            const double c_lo = voxel_cell_of(lo[a], g.o[a], voxel), c_hi = voxel_cell_of(hi[a], g.o[a], voxel);
+            if (c_lo < 0.0) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: a point lies below the origin on axis %d (%g < %g)", a, (double)lo[a], g.o[a]);
+            if (!(c_hi + 1.0 <= (double)oa::VOX_MAX_DIM))
+                return fail(OA_E_BAD_ARG, "oa_voxel_downsample: %g cells on axis %d (at most %d: use a larger voxel)", c_hi + 1.0, a, oa::VOX_MAX_DIM);
+            dims[a] = (long long)c_hi + 1;
+            r.dims[a] = (int32_t)dims[a];
+        }
+        g.dx = dims[0]; g.dy = dims[1];
+        if (rep) *rep = r;
+    }
+    const int nf = (int)r.n_finite;
+    // 2., 3. keys and their stable order; the points that take no part carry the all-ones key and sort last: `bits` is what the
+    // number of cells itself needs, so that the all-ones slice is above every cell's
+    const unsigned long long cells = (unsigned long long)dims[0] * (unsigned long long)dims[1] * (unsigned long long)dims[2];   // <= 2^63
+    int bits = 1;
+    while (bits < 64 && (cells >> bits) != 0ull) ++bits;
+    DevTmp<unsigned long long> d_keys;
+    DevTmp<int> d_order;
+    HIPCHK(d_keys.alloc((size_t)n));
+    hipLaunchKernelGGL(oa::k_voxel_keys, dim3(pt_blocks), dim3(oa::VOX_THREADS), 0, c->stream, d_xyz, ni, g, d_keys.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = voxel_sort_keys(c, d_keys.p, ni, bits, d_order))) return rc;
+    // 4. rows
+    const unsigned f_blocks = (unsigned)(((size_t)nf + oa::VOX_THREADS - 1) / oa::VOX_THREADS);
+    DevTmp<int> d_head;
+    DevTmp<long long> d_off;
+    DevTmp<char> scan_tmp, scan_tmp2;
+    HIPCHK(d_head.alloc((size_t)nf)); HIPCHK(d_off.alloc((size_t)nf + 1));
+    hipLaunchKernelGGL(oa::k_voxel_heads, dim3(f_blocks), dim3(oa::VOX_THREADS), 0, c->stream, (const unsigned long long *)d_keys.p, (const int *)d_order.p, nf, d_head.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = scan_counts(c, d_head.p, nf, d_off.p, scan_tmp))) return rc;
+    long long n_rows = 0;
+    if ((rc = read_small(c, &n_rows, d_off.p + nf, sizeof n_rows))) return rc;
+    if (n_rows < 1 || n_rows > nf) return fail(OA_E_HIP, "oa_voxel_downsample: %lld rows from %d points", n_rows, nf);
+    const int nr = (int)n_rows;
+    const unsigned r_blocks = (unsigned)(((size_t)nr + oa::VOX_THREADS - 1) / oa::VOX_THREADS);
+    const unsigned g_blocks = (unsigned)(((size_t)nr * oa::VOX_GROUP + oa::VOX_THREADS - 1) / oa::VOX_THREADS);
+    const size_t max_chunks = oa::voxel_max_chunks((size_t)nf);
+    const unsigned l_blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((max_chunks + 3) / 4, (size_t)c->n_cu * 16));
+    DevTmp<int> d_row_start, d_nchunks, d_count, d_rep, d_max, d_pidx;
+    DevTmp<long long> d_chunk_off;
+    DevTmp<double> d_partial, d_pd2;
+    DevTmp<float> d_oxyz, d_onrm;
+    HIPCHK(d_row_start.alloc((size_t)nr + 1)); HIPCHK(d_nchunks.alloc((size_t)nr)); HIPCHK(d_chunk_off.alloc((size_t)nr + 1));
+    HIPCHK(d_count.alloc((size_t)nr)); HIPCHK(d_rep.alloc((size_t)nr)); HIPCHK(d_max.alloc(1));
+    HIPCHK(d_partial.alloc(6 * max_chunks)); HIPCHK(d_pd2.alloc(max_chunks)); HIPCHK(d_pidx.alloc(max_chunks));
+    HIPCHK(d_oxyz.alloc(3 * (size_t)nr));
+    if (d_nrm) HIPCHK(d_onrm.alloc(3 * (size_t)nr));
+    HIPCHK(hipMemsetAsync(d_max.p, 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(oa::k_voxel_row_start, dim3(f_blocks), dim3(oa::VOX_THREADS), 0, c->stream, (const int *)d_head.p, (const long long *)d_off.p, nf, d_row_start.p);
+    hipLaunchKernelGGL(oa::k_voxel_row_chunks, dim3(r_blocks), dim3(oa::VOX_THREADS), 0, c->stream, (const int *)d_row_start.p, nr, d_nchunks.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = scan_counts(c, d_nchunks.p, nr, d_chunk_off.p, scan_tmp2))) return rc;
+    // 5. means and normals: short rows, long rows' chunks, long rows' chunk sums in chunk order
+    hipLaunchKernelGGL(oa::k_voxel_reduce, dim3(g_blocks), dim3(oa::VOX_THREADS), 0, c->stream, d_xyz, d_nrm, (const int *)d_order.p, (const int *)d_row_start.p, nr,
+                       d_oxyz.p, d_onrm.p, d_count.p, d_max.p);
+    hipLaunchKernelGGL(oa::k_voxel_reduce_long, dim3(l_blocks), dim3(oa::VOX_THREADS), 0, c->stream, d_xyz, d_nrm, (const int *)d_order.p, (const int *)d_row_start.p,
+                       (const long long *)d_chunk_off.p, nr, d_partial.p);
+    hipLaunchKernelGGL(oa::k_voxel_finish_long, dim3(r_blocks), dim3(oa::VOX_THREADS), 0, c->stream, (const int *)d_row_start.p, (const long long *)d_chunk_off.p, nr,
+                       (const double *)d_partial.p, d_nrm != nullptr, d_oxyz.p, d_onrm.p);
+    HIPCHK(hipGetLastError());
+    // 6. representatives, against the rounded means
+    hipLaunchKernelGGL(oa::k_voxel_rep, dim3(g_blocks), dim3(oa::VOX_THREADS), 0, c->stream, d_xyz, (const int *)d_order.p, (const int *)d_row_start.p, nr,
+                       (const float *)d_oxyz.p, d_rep.p);
+    hipLaunchKernelGGL(oa::k_voxel_rep_long, dim3(l_blocks), dim3(oa::VOX_THREADS), 0, c->stream, d_xyz, (const int *)d_order.p, (const int *)d_row_start.p,
+                       (const long long *)d_chunk_off.p, nr, (const float *)d_oxyz.p, d_pd2.p, d_pidx.p);
+    hipLaunchKernelGGL(oa::k_voxel_rep_finish_long, dim3(r_blocks), dim3(oa::VOX_THREADS), 0, c->stream, (const long long *)d_chunk_off.p, nr, (const double *)d_pd2.p,
+                       (const int *)d_pidx.p, d_rep.p);
+    HIPCHK(hipGetLastError());
+    // 7. out
+    const bool fits = cap >= n_rows;
+    std::vector<int> h_rep;
+    if (fits) {
+        if (out_xyz) HIPCHK(hipMemcpyAsync(out_xyz, d_oxyz.p, sizeof(float) * 3 * (size_t)nr, hipMemcpyDeviceToHost, c->stream));
+        if (out_normals && d_nrm) HIPCHK(hipMemcpyAsync(out_normals, d_onrm.p, sizeof(float) * 3 * (size_t)nr, hipMemcpyDeviceToHost, c->stream));
+        if (out_count) HIPCHK(hipMemcpyAsync(out_count, d_count.p, sizeof(int32_t) * (size_t)nr, hipMemcpyDeviceToHost, c->stream));
+        if (out_rep) { h_rep.resize((size_t)nr); HIPCHK(hipMemcpyAsync(h_rep.data(), d_rep.p, sizeof(int) * (size_t)nr, hipMemcpyDeviceToHost, c->stream)); }
+    }
+    int max_members = 0;
+    if ((rc = read_small(c, &max_members, d_max.p, sizeof max_members))) return rc;      // (waits for everything above)
+    if (fits && out_rep) for (size_t k = 0; k < (size_t)nr; ++k) out_rep[k] = (int64_t)h_rep[k];
+    r.n_voxels = n_rows;
+    r.max_members = max_members;
+    r.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (n_out) *n_out = n_rows;
+    if (rep) *rep = r;
+    if (!fits) return fail(OA_E_CAPACITY, "oa_voxel_downsample: %lld occupied voxels, room for %lld rows", n_rows, (long long)cap);
     return OA_OK;
 }

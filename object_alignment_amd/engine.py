@@ -62,6 +62,38 @@ def _feature_rows(f, name):
     return f
 
 
+def _voxel_args(xyz, voxel, normals, origin, name="voxel_downsample"):
+    """The arguments of a voxel downsample, checked before any call reaches the library: (xyz, normals, origin) with host
+    arrays made contiguous float32 (n, 3) and torch device tensors left as they are."""
+    if isinstance(voxel, bool) or not isinstance(voxel, (int, float, np.integer, np.floating)) or not (np.isfinite(voxel) and voxel > 0):
+        raise ValueError("%s: voxel = %r (finite and > 0)" % (name, voxel))
+
+    def points(a, what):
+        if hasattr(a, "data_ptr") and hasattr(a, "is_cuda"):      # torch tensor, without importing torch
+            if a.dim() != 2 or a.shape[1] != 3 or a.shape[0] < 1 or "float32" not in str(a.dtype):
+                raise ValueError("%s: %s must be (n >= 1, 3) float32, got %s %s" % (name, what, tuple(a.shape), a.dtype))
+            return a
+        a = np.asarray(a)
+        if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 1:
+            raise ValueError("%s: %s must be (n >= 1, 3), got shape %s" % (name, what, a.shape))
+        if a.dtype.kind not in "fiu":
+            raise ValueError("%s: %s has dtype %s (numbers)" % (name, what, a.dtype))
+        return np.ascontiguousarray(a, dtype=np.float32)
+
+    xyz = points(xyz, "xyz")
+    if normals is not None:
+        normals = points(normals, "normals")
+        if tuple(normals.shape) != tuple(xyz.shape):
+            raise ValueError("%s: %s normals for %s points" % (name, tuple(normals.shape), tuple(xyz.shape)))
+        if bool(getattr(xyz, "is_cuda", False)) != bool(getattr(normals, "is_cuda", False)):
+            raise ValueError("%s: xyz and normals must be on the same side (both host arrays or both device tensors)" % name)
+    if origin is not None:
+        origin = np.ascontiguousarray(origin, dtype=np.float64)
+        if origin.shape != (3,) or not np.all(np.isfinite(origin)):
+            raise ValueError("%s: origin must be three finite numbers, got %r" % (name, origin))
+    return xyz, normals, origin
+
+
 def resolve_devices(spec):
     """A device list from an int, a sequence, "all", or a string like "0,1,2,3" (what OA_DEVICES may hold)."""
     if spec is None:
@@ -562,6 +594,36 @@ class IcpEngine:
                                                 tri.ctypes.data_as(C.POINTER(C.c_int32)) if tri is not None else None,
                                                 capi.fptr(out), C.byref(n), C.byref(rep)))
         return out[: n.value].copy(), {name: getattr(rep, name) for name, _ in capi.FeatureReport._fields_ if name != "reserved"}
+
+    def voxel_downsample(self, xyz, voxel, normals=None, origin=None):
+        """Voxel-grid downsample of ANY cloud (no target, source or matrices needed; nothing a loop reads is touched): one row per
+        occupied cell of edge `voxel`, in ascending cell order.  xyz / normals: (n, 3) host arrays or torch device tensors;
+        origin: the grid's corner, None = the minimum of the finite points.  Returns a dict: xyz float32 (m, 3) the members'
+        means, normals float32 (m, 3) the normalised sums of their normals (None without normals), count int32 (m,), rep int64
+        (m,) the index of the member nearest to each mean (what makes a downsample a vlist), report."""
+        xyz, normals, origin = _voxel_args(xyz, voxel, normals, origin)
+        p, on_dev, keep, n = _device_ptr(xyz)
+        pn, keep_n = None, None
+        if normals is not None:
+            pn, _, keep_n, _ = _device_ptr(normals)
+        rep = capi.VoxelReport()
+        m = C.c_int64(0)
+        i32p = C.POINTER(C.c_int32)
+        po = capi.dptr(origin) if origin is not None else None
+        # room for the most rows there can be (untouched pages cost nothing; the library copies n_voxels rows)
+        out = np.empty((n, 3), np.float32)
+        out_n = np.empty((n, 3), np.float32) if normals is not None else None
+        cnt = np.empty(n, np.int32)
+        idx = np.empty(n, np.int64)
+        self._chk(self._L.oa_voxel_downsample(self._h, p, n, on_dev, pn, float(voxel), po, n, capi.fptr(out),
+                                              capi.fptr(out_n) if out_n is not None else None, cnt.ctypes.data_as(i32p), capi.iptr(idx),
+                                              C.byref(m), C.byref(rep)))
+        rows = int(m.value)
+        del keep, keep_n
+        report = {"n_in": rep.n_in, "n_finite": rep.n_finite, "n_voxels": rep.n_voxels, "max_members": rep.max_members,
+                  "dims": tuple(rep.dims), "origin": tuple(rep.origin), "total_ms": rep.total_ms}
+        return {"xyz": out[:rows].copy(), "normals": out_n[:rows].copy() if out_n is not None else None, "count": cnt[:rows].copy(),
+                "rep": idx[:rows].copy(), "report": report}
 
     # ---- split phase (one process per GPU)
     def run_begin(self, iters=50, thresh=0.5, target_d=0.01, use_target=True, with_scale=False, early_exit=True):

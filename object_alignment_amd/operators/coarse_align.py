@@ -39,6 +39,9 @@ class CoarseSettings:
     ratio: float = 0.9              # nearest / second nearest descriptor distance (not squared) a match may have
     mutual: bool = True             # a match must be the nearest row in both directions
     seed: int = 0                   # of the hashed draw of the triples
+    # method "features" / "both": None = descriptors of every target and source vertex; a length in world units = descriptors
+    # of the two clouds' voxel downsamples of that edge (the coarse stage needs no more, and the matching is quadratic)
+    voxel: float | None = None
 
     def __post_init__(self):
         if self.method not in METHODS:
@@ -59,6 +62,9 @@ class CoarseSettings:
                 raise ValueError("CoarseSettings.%s = %r (an integer in %d .. %d)" % (name, v, lo, hi))
         if self.thresh is not None and not (np.isfinite(self.thresh) and self.thresh > 0):
             raise ValueError("CoarseSettings.thresh = %r (finite and > 0, or None)" % (self.thresh,))
+        if self.voxel is not None and not (isinstance(self.voxel, (int, float, np.integer, np.floating)) and not isinstance(self.voxel, bool)
+                                           and np.isfinite(self.voxel) and self.voxel > 0):
+            raise ValueError("CoarseSettings.voxel = %r (finite and > 0, or None)" % (self.voxel,))
 
 
 def default_thresh(target_xyz, mx_base) -> float:
@@ -88,6 +94,39 @@ def feature_poses(engine, settings: CoarseSettings, source_xyz) -> tuple:
     return poses, rep
 
 
+def feature_poses_downsampled(engine, settings: CoarseSettings, target_xyz, mx_base, source_xyz) -> tuple:
+    """feature_poses with the descriptors taken from voxel downsamples of both clouds (settings.voxel, world units): the
+    candidates are world motions applied to the incoming matrix_world and do not depend on which points produced them, so they
+    suit the main engine's scoring unchanged.  Everything runs on a side engine on the same device; `engine` is only read
+    (its matrix_world).  The source's cloud is ALL of source_xyz, as feature_poses computes its descriptors.
+    Fewer than 4 rows on a side: no poses and rep["feature_note"] says why."""
+    from .. import fpfh
+    from ..engine import IcpEngine
+    from .icp_align import world_scale
+    mx_align = engine.matrix_world()
+    h = float(settings.voxel)
+    rep = {"estimated_target_normals": True, "feature_voxel": h, "feature_n_target": 0, "feature_n_source": 0, "feature_n_pairs": 0,
+           "feature_n_accepted": 0}
+    none = np.zeros((0, 4, 4), np.float32)
+    with IcpEngine(engine.device) as side:
+        down_tgt = side.voxel_downsample(target_xyz, h / world_scale(mx_base))["xyz"]
+        down_src = side.voxel_downsample(source_xyz, h / world_scale(mx_align))["xyz"]
+        rep["feature_n_target"], rep["feature_n_source"] = len(down_tgt), len(down_src)
+        if len(down_tgt) < 4 or len(down_src) < 4:
+            rep["feature_note"] = "%d target and %d source rows after the downsample (4 needed)" % (len(down_tgt), len(down_src))
+            return none, rep
+        side.set_target(down_tgt)
+        side.estimate_target_normals(k=min(settings.normal_k, len(down_tgt)), orient="away", install=True)
+        side.target_fpfh(k=min(settings.feature_k, len(down_tgt)), keep=True)
+        src_feat = fpfh(down_src, k=settings.feature_k, normal_k=settings.normal_k, device=engine.device)
+        side.set_source(down_src, stride=1)
+        side.set_matrices(mx_align, mx_base)
+        poses, frep = side.feature_candidates(src_feat, None, n_hyp=settings.n_hyp, ratio=settings.ratio, mutual=settings.mutual,
+                                              edge_tol=settings.edge_tol, seed=settings.seed)
+    rep.update(("feature_" + k, v) for k, v in frep.items())
+    return poses, rep
+
+
 def coarse_stage(engine, settings: CoarseSettings, target_xyz, mx_base, source_xyz=None) -> dict:
     """The coarse stage on an engine whose target, source and matrices are set: matrix_world moves to the pose it found.
     source_xyz: all vertices of the source, what method "features" / "both" computes the source's descriptors from.
@@ -99,10 +138,15 @@ def coarse_stage(engine, settings: CoarseSettings, target_xyz, mx_base, source_x
         return engine.coarse_align(thresh, n_rot=settings.n_rot, **kw)
     if source_xyz is None:
         raise ValueError("CoarseSettings.method = %r needs source_xyz" % (settings.method,))
-    poses, frep = feature_poses(engine, settings, source_xyz)
+    if settings.voxel is None:
+        poses, frep = feature_poses(engine, settings, source_xyz)
+    else:
+        poses, frep = feature_poses_downsampled(engine, settings, target_xyz, mx_base, source_xyz)
     status = "ok"
     if len(poses) == 0:
         status = "fallback: no candidate from the features (%d matched pairs)" % frep["feature_n_pairs"]
+        if "feature_note" in frep:
+            status = "fallback: " + frep.pop("feature_note")
     if settings.method == "both":
         poses = np.concatenate([engine.coarse_candidates(settings.n_rot), poses.reshape(-1, 4, 4)])
     if len(poses) == 0:

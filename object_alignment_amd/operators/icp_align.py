@@ -56,6 +56,11 @@ class IcpSettings:
     robust_scale_min: float | None = None
     # neighbours per vertex when run(..., target_normals="estimate") estimates a point-cloud target's normals on the device
     normal_k: int = 16
+    # nor this: > 0 thins the selection in SPACE before the loop -- one vertex per occupied cell of a grid of this edge (world
+    # units, like min_start): the member nearest to the cell's mean (IcpEngine.voxel_downsample) -- so that a region the scanner
+    # covered twice does not weigh twice; sample_fraction then applies to that list, as to any vlist.  0 = off: the selection is
+    # thinned by index alone, as in the reference
+    sample_voxel: float = 0.0
 
 
 MAD_TUNING = {"huber": 1.345 * 1.4826, "tukey": 4.685 * 1.4826, "cauchy": 2.385 * 1.4826}
@@ -137,6 +142,46 @@ def apply_robust(engine, settings) -> None:
         raise RuntimeError("this engine cannot estimate the robust scale")
 
 
+def sample_voxel_of(settings) -> float:
+    """IcpSettings.sample_voxel, checked: 0.0 (off) or a finite length > 0 in world units."""
+    v = getattr(settings, "sample_voxel", 0.0)
+    if v is None:
+        return 0.0
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (np.isfinite(v) and v >= 0):
+        raise ValueError("IcpSettings.sample_voxel = %r (0 = off, or finite and > 0)" % (v,))
+    return float(v)
+
+
+def world_scale(mx) -> float:
+    """cbrt(|det(mx[:3, :3])|): what carries a world-space length to the object's local space."""
+    return float(np.cbrt(abs(np.linalg.det(np.asarray(mx, np.float64).reshape(4, 4)[:3, :3]))))
+
+
+def voxel_vlist(engine, source_xyz, vlist, mx_align, sample_voxel):
+    """One vertex per occupied voxel of edge sample_voxel (world units) among the vertices vlist selects (None: all): the
+    representatives, as indices into source_xyz, ascending -- a vlist.  Vertices with a non-finite coordinate are in no voxel."""
+    s = world_scale(mx_align)
+    if not (np.isfinite(s) and s > 0):
+        raise ValueError("sample_voxel needs an invertible matrix_world (scale %r)" % (s,))
+    sel = None
+    pts = source_xyz
+    if vlist is not None:
+        sel = np.ascontiguousarray(vlist, dtype=np.int64)
+        if hasattr(pts, "is_cuda"):
+            pts = pts.detach().cpu().numpy()
+        pts = np.asarray(pts, np.float32).reshape(-1, 3)[sel]
+    if getattr(engine, "multi", False):                        # (a multi-device context has no call of its own for it)
+        from .. import voxel_downsample
+        down = voxel_downsample(pts, sample_voxel / s, device=engine.device)
+    else:
+        call = getattr(engine, "voxel_downsample", None)
+        if call is None:
+            raise RuntimeError("this engine has no voxel downsample")
+        down = call(pts, sample_voxel / s)
+    rep = down["rep"]
+    return np.sort(sel[rep] if sel is not None else rep)
+
+
 def build_vlist(align_obj):
     """Vertex indices the operator aligns with, from the object's `icp_include` / `icp_exclude` vertex groups
     (semantics of operators/icp_align.py:56-80): an include group wins and keeps memberships heavier than 0.9;
@@ -215,7 +260,9 @@ class IcpAlign:
         object_alignment_amd.estimate_normals(source_xyz, k=settings.normal_k), in a context of its own (that metric does not
         look at the normals' signs, so they are left unoriented).
         coarse: a CoarseSettings (operators/coarse_align.py) -- the coarse global stage runs on the same engine in front of the
-        loop, which then starts from the pose it found (self.last_coarse holds its report); None: the loop alone."""
+        loop, which then starts from the pose it found (self.last_coarse holds its report); None: the loop alone.
+        settings.sample_voxel > 0: the vertices vlist selects are first thinned to one representative per voxel of that edge
+        (voxel_vlist); sample_fraction then applies to that list."""
         s = self.settings
         estimate = isinstance(target_normals, str)
         if estimate and target_normals != "estimate":
@@ -224,6 +271,7 @@ class IcpAlign:
             raise ValueError("target_normals='estimate' is for point-cloud targets: a mesh (target_tris) uses its triangles' normals")
         if isinstance(source_normals, str) and source_normals != "estimate":
             raise ValueError("source_normals %r (an array of normals, or 'estimate')" % (source_normals,))
+        sample_voxel = sample_voxel_of(s)
         thresh = s.min_start                                   # :83
         factor = round(1 / s.sample_fraction)                  # :89  (ZeroDivisionError at 0, as the reference)
         if not thresh > 0:
@@ -240,6 +288,8 @@ class IcpAlign:
                 eng.set_target_normals(target_normals)
         apply_metric(eng, s)
         apply_robust(eng, s)
+        if sample_voxel > 0.0:
+            vlist = voxel_vlist(eng, source_xyz, vlist, mx_align, sample_voxel)
         eng.set_source(source_xyz, vlist=vlist, stride=factor)
         if source_weights is not None:
             eng.set_source_weights(source_weights)
