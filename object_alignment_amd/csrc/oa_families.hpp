@@ -16,9 +16,9 @@
 // ---- signatures (explicit instantiation needs the parameter types) --------------------------------------------------
 #define OA_SIG_NN_SEARCH const DevState *, const float4 *, const float4 *, int, unsigned long long *
 #define OA_SIG_NN_FILTERED const DevState *, const float4 *, const float4 *, const float4 *, const float4 *, const float4 *, int, unsigned long long *
-#define OA_SIG_WAVE_ORDER const DevState *, const float4 *, int, unsigned short *
+#define OA_SIG_POINT_SETUP const DevState *, const float4 *, const float4 *, const unsigned long long *, int, int, int, int, int, float4 *
 #define OA_SIG_SEED_SORTED const DevState *, const float4 *, int, const float4 *, const float4 *, const int4 *, int, int, unsigned long long *
-#define OA_SIG_NN_SORTED const DevState *, const float4 *, const float4 *, const float4 *, const float4 *, const int4 *, const float4 *, int, int, int, unsigned long long *, int, const unsigned short *, int, int, const int *, int *, int
+#define OA_SIG_NN_SORTED const DevState *, const float4 *, const float4 *, const float4 *, const int4 *, int, unsigned long long *, int, const float4 *, int, int, const int *, int *, int
 #define OA_SIG_NN_GRID const DevState *, const float4 *, int, GridParams, const int *, const float4 *, float4 *, unsigned long long *, int *, int *, int, BvhParams, const float4 *, const float4 *, NormalTest, double *, unsigned long long *, const float *, uint2 *
 #define OA_SIG_TRI_GRID const DevState *, const float4 *, int, GridParams, const int *, const float4 *, const float4 *, int *, unsigned long long *, int *, int *, int, unsigned long long *, BvhParams, const float4 *, const float4 *, NormalTest, double *, const int *, const int *, const int *, int, int, int
 #define OA_SIG_TRI_SETTLE const DevState *, const float4 *, int, FineParams, const uint4 *, const float4 *, const float4 *, const int *, unsigned long long *, int *, int, int *, int *, unsigned long long *
@@ -39,8 +39,8 @@
 #define OA_FAMILY_BRUTE(X)                                                                                              \
     OA_K(X, k_nn_search, OA_SIG_NN_SEARCH, 1) OA_K(X, k_nn_search, OA_SIG_NN_SEARCH, 2)                                 \
     OA_K(X, k_nn_search, OA_SIG_NN_SEARCH, 4) OA_K(X, k_nn_search, OA_SIG_NN_SEARCH, 8)                                 \
-    OA_K(X, k_sorted_wave_order, OA_SIG_WAVE_ORDER, 2) OA_K(X, k_sorted_wave_order, OA_SIG_WAVE_ORDER, 4)               \
-    OA_K(X, k_sorted_wave_order, OA_SIG_WAVE_ORDER, 8)                                                                  \
+    OA_K(X, k_sorted_point_setup, OA_SIG_POINT_SETUP, 1) OA_K(X, k_sorted_point_setup, OA_SIG_POINT_SETUP, 2)           \
+    OA_K(X, k_sorted_point_setup, OA_SIG_POINT_SETUP, 4) OA_K(X, k_sorted_point_setup, OA_SIG_POINT_SETUP, 8)           \
     OA_K(X, k_nn_seed_sorted, OA_SIG_SEED_SORTED, 64) OA_K(X, k_nn_seed_sorted, OA_SIG_SEED_SORTED, FTILE_GROUPS)       \
     OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 1, 64, true) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 2, 64, true)      \
     OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 1, 64, false) OA_K(X, k_nn_search_sorted, OA_SIG_NN_SORTED, 2, 64, false)

@@ -423,8 +423,9 @@ struct oa_ctx {
     int *d_sel = nullptr;            // vertex index held by each source slot
     float4 *d_src4o = nullptr;       // the same points in the caller's (vlist) order -- only oa_make_pairs needs it
     int *d_perm = nullptr;           // sorted slot -> caller-order slot (nullptr: not sorted)
-    unsigned short *d_worder = nullptr;   // k_sorted_wave_order: per wave of k_nn_search_sorted, its slots in the order of u (OA_NN_WAVE_ORDER=0: off)
-    int homes_cap = 0;               // blocks of source points d_homes holds
+    float4 *d_prec = nullptr;        // k_sorted_point_setup: k_nn_search_sorted's point records, 3 float4 per slot in the order its lanes read them (OA_NN_WAVE_ORDER=0: the slots' own order)
+    int prec_cap = 0;                // slots d_prec holds
+    int homes_cap = 0;               // blocks of source points d_homes holds (two ints each: home split, home tile)
     int *d_homes = nullptr, *d_qcnt = nullptr;   // k_nn_search_sorted's work queue (oa_kernels.hpp): per block of source points its own split; the queues' counters
     bool nn_vchunk = true;           // OA_NN_VCHUNK: the sorted images' blocks in the order of v and k_nn_search_sorted's level 0v (0: as until round 6)
     int nn_persist = 4;              // OA_NN_PERSIST: workgroups per CU that work the queue off (0: one workgroup per item, in launch order -- as until round 6)
@@ -999,21 +1000,27 @@ int launch_vertex_grid(oa_ctx *c, const SearchChoice &s, bool acc)
     return OA_OK;
 }
 
-// k_nn_search_sorted's work queue (oa_kernels.hpp): d_homes for `blocks` blocks of source points + the queues' counters, both rewritten by
-// k_sorted_block_homes in front of every queued launch.  They come with the source in brute-force mode (source_reset, oa_set_search_mode: never
-// inside a loop, see safe_radii_lazy); the other modes get here at first use (a target without usable grid or tree), or should the blocks outgrow them.
-int ensure_queue_buffers(oa_ctx *c, int blocks)
+// What k_nn_search_sorted reads beside the images (oa_kernels.hpp): the point records of k_sorted_point_setup for ns_pad slots, d_homes for
+// `blocks` blocks of source points + the work queue's counters, both rewritten by k_sorted_block_homes.  They come with the source in
+// brute-force mode (source_reset, oa_set_search_mode: never inside a loop, see safe_radii_lazy); the other modes get here at first use (a
+// target without usable grid or tree), or should the blocks outgrow them.
+int ensure_sorted_buffers(oa_ctx *c, int blocks)
 {
+    if (c->ns_pad > c->prec_cap) {
+        dev_free(c->d_prec); c->prec_cap = 0;
+        HIPCHK(dev_malloc(&c->d_prec, sizeof(float4) * 3 * (size_t)c->ns_pad));
+        c->prec_cap = c->ns_pad;
+    }
     if (blocks > c->homes_cap) {
         dev_free(c->d_homes); c->homes_cap = 0;
-        HIPCHK(dev_malloc(&c->d_homes, sizeof(int) * (size_t)blocks));
+        HIPCHK(dev_malloc(&c->d_homes, sizeof(int) * 2 * (size_t)blocks));
         c->homes_cap = blocks;
     }
     if (!c->d_qcnt) HIPCHK(dev_malloc(&c->d_qcnt, sizeof(int) * (size_t)(oa::SORTED_QUEUES * oa::SORTED_QUEUE_STRIDE)));
     return OA_OK;
 }
 
-// The sorted brute-force search: wave order -> block homes (queued launches) -> seed pass (the first search of a loop) -> search
+// The sorted brute-force search: seed pass (the first search of a loop) -> point setup -> block homes -> search
 int launch_brute_sorted(oa_ctx *c, const dim3 grid)
 {
     // with seeds: one launch over n_splits_seeded splits.  Without (the first search of a loop): k_nn_seed_sorted -- every point
@@ -1021,28 +1028,12 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
     // one unseeded launch over n_splits splits, as until r05z)
     const bool two = !c->win_seeds && c->nn_home_pass && c->n_splits_seeded > 1;
     dim3 sgrid((unsigned)((c->win_seeds || two) ? c->n_splits_seeded : c->n_splits), grid.y);
-    // the waves' slots in the order of u at this pose (k_sorted_wave_order: ~10 us in front of a 30 ms search)
-    const bool ordered = c->d_worder && c->R >= 2;
-    if (ordered) {
-        const dim3 ob((unsigned)(c->ns_pad / (64 * c->R)));
-        dispatch<4, 2, 8>(c->R, [&](auto R) {
-            hipLaunchKernelGGL((oa::k_sorted_wave_order<decltype(R)::value>), ob, dim3(64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->sax[0], c->d_worder);
-        });
-        HIPCHK(hipGetLastError());
-    }
     // long launches go through the work queue (oa_kernels.hpp): as many workgroups as the chip holds, the long items first
     const int q_splits = (int)sgrid.x, q_blocks = (int)sgrid.y;
     const long long q_wgs = (long long)c->n_cu * std::min(c->nn_persist, c->R <= 4 ? 4 : 2);
     const bool queued = q_wgs > 0 && q_splits > 1 && (long long)q_splits * q_blocks >= (c->nn_queue_min >= 0 ? (long long)c->nn_queue_min : 4 * q_wgs);
     c->last_queue_wgs = queued ? (int)q_wgs : 0;
-    if (queued) {
-        { const int rcq = ensure_queue_buffers(c, q_blocks); if (rcq) return rcq; }
-        hipLaunchKernelGGL(oa::k_sorted_block_homes, dim3((unsigned)((std::max(q_blocks, oa::SORTED_QUEUES) + 63) / 64)), dim3(64), 0, c->stream,
-                           (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, q_blocks, oa::NN_THREADS * c->R, (const float4 *)c->d_tfs,
-                           c->n_groups_pad, c->tile_groups, c->sax[0], q_splits, c->d_homes, c->d_qcnt);
-        HIPCHK(hipGetLastError());
-        sgrid = dim3((unsigned)q_wgs);
-    }
+    { const int rcq = ensure_sorted_buffers(c, q_blocks); if (rcq) return rcq; }
     const int pass = two ? 2 : 0;                                   // (seeded from what the seed pass leaves in keys)
     if (two) {
         const dim3 sb((unsigned)((c->ns_pad + 255) / 256));
@@ -1052,10 +1043,28 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
         });
         HIPCHK(hipGetLastError());
     }
+    // every point's record at this pose, the waves' slots in the order of u (k_sorted_point_setup: once per search what every item of
+    // the search used to work out for itself)
+    {
+        const dim3 ob((unsigned)(c->ns_pad / (64 * c->R)));
+        dispatch<4, 1, 2, 8>(c->R, [&](auto R) {
+            hipLaunchKernelGGL((oa::k_sorted_point_setup<decltype(R)::value>), ob, dim3(64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4,
+                               (const float4 *)c->d_win, (const unsigned long long *)c->d_keys, c->sax[0], c->sax[1], pass, c->nn_wave_order ? 1 : 0, c->ns_pad, c->d_prec);
+        });
+        HIPCHK(hipGetLastError());
+    }
+    // the blocks' home splits (the queue's order of items) and home tiles (where an item starts its visit of the split's tiles)
+    {
+        hipLaunchKernelGGL(oa::k_sorted_block_homes, dim3((unsigned)((std::max(q_blocks, oa::SORTED_QUEUES) + 63) / 64)), dim3(64), 0, c->stream,
+                           (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, q_blocks, oa::NN_THREADS * c->R, (const float4 *)c->d_tfs,
+                           c->n_groups_pad, c->tile_groups, c->sax[0], q_splits, c->d_homes, c->d_qcnt);
+        HIPCHK(hipGetLastError());
+    }
+    if (queued) sgrid = dim3((unsigned)q_wgs);
     auto launch = [&](auto R, auto TG, auto VCHUNK) {
         hipLaunchKernelGGL((oa::k_nn_search_sorted<decltype(R)::value, decltype(TG)::value, decltype(VCHUNK)::value>), sgrid, dim3(oa::NN_THREADS), 0, c->stream,
-                           c->d_state, c->d_src4, (const float4 *)c->d_tgs, (const float4 *)c->d_tfs, (const float4 *)c->d_tf3s, (const int4 *)c->d_tidx,
-                           (const float4 *)c->d_win, c->n_groups_pad, c->sax[0], c->sax[1], c->d_keys, pass, ordered ? c->d_worder : nullptr, q_splits, q_blocks, queued ? c->d_homes : nullptr, queued ? c->d_qcnt : nullptr, c->nt);
+                           c->d_state, (const float4 *)c->d_tgs, (const float4 *)c->d_tfs, (const float4 *)c->d_tf3s, (const int4 *)c->d_tidx,
+                           c->n_groups_pad, c->d_keys, pass, (const float4 *)c->d_prec, q_splits, q_blocks, c->d_homes, queued ? c->d_qcnt : nullptr, c->nt);
     };
     auto search = [&](auto R) { dispatch<oa::FTILE_GROUPS, 64>(c->tile_groups, [&](auto TG) { if (c->nn_vchunk) launch(R, TG, yes); else launch(R, TG, no); }); };
 #if defined(OA_EXPERIMENTS)
@@ -2346,7 +2355,7 @@ OA_EXPORT void oa_destroy(oa_ctx *c)
     (void)hipDeviceSynchronize();
     tl_stream_known = false;                                        // the stream below is about to go away
 #define OA_FREE(x) dev_free(c->x, true)
-    OA_FREE(d_tgt_xyz); OA_FREE(d_tg); OA_FREE(d_tf); OA_FREE(d_tf3); OA_FREE(d_tfs); OA_FREE(d_tf3s); OA_FREE(d_tgs); OA_FREE(d_tidx); OA_FREE(d_tfm); OA_FREE(d_members); OA_FREE(d_pos); OA_FREE(d_prev); OA_FREE(d_win); OA_FREE(d_worder); OA_FREE(d_homes); OA_FREE(d_qcnt); OA_FREE(d_wsafe); OA_FREE(d_safe_by_idx); OA_FREE(d_cell_start);
+    OA_FREE(d_tgt_xyz); OA_FREE(d_tg); OA_FREE(d_tf); OA_FREE(d_tf3); OA_FREE(d_tfs); OA_FREE(d_tf3s); OA_FREE(d_tgs); OA_FREE(d_tidx); OA_FREE(d_tfm); OA_FREE(d_members); OA_FREE(d_pos); OA_FREE(d_prev); OA_FREE(d_win); OA_FREE(d_prec); OA_FREE(d_homes); OA_FREE(d_qcnt); OA_FREE(d_wsafe); OA_FREE(d_safe_by_idx); OA_FREE(d_cell_start);
     OA_FREE(d_sorted); OA_FREE(d_todo_list); OA_FREE(d_todo_count); OA_FREE(d_ulist); OA_FREE(d_src4); OA_FREE(d_keys); OA_FREE(d_state);
     OA_FREE(d_partials); OA_FREE(d_sums); OA_FREE(d_solve);
     OA_FREE(d_valid); OA_FREE(d_b); OA_FREE(d_dist); OA_FREE(d_counts); OA_FREE(d_offsets); OA_FREE(d_A); OA_FREE(d_B);
@@ -2383,8 +2392,7 @@ OA_EXPORT int oa_set_search_mode(oa_ctx *c, int mode)
     if (mode == 0 && c->ns_pad > 0 && c->d_src4) {                  // (a source uploaded for the other modes: what source_reset allocates for this one)
         int rc = use_device(c);
         if (rc) return rc;
-        if (c->nn_wave_order && !c->d_worder) HIPCHK(dev_malloc(&c->d_worder, sizeof(unsigned short) * (size_t)c->ns_pad));
-        if ((rc = ensure_queue_buffers(c, c->ns_pad / (oa::NN_THREADS * c->R)))) return rc;
+        if ((rc = ensure_sorted_buffers(c, c->ns_pad / (oa::NN_THREADS * c->R)))) return rc;
     }
     if (rebuild) {                                   // the grids were skipped when the target was uploaded
         int rc = use_device(c);
@@ -3356,10 +3364,9 @@ int source_reset(oa_ctx *c, long long count, long long begin, long long n_verts)
     HIPCHK(dev_malloc(&c->d_keys, sizeof(unsigned long long) * (size_t)c->ns_pad));
     HIPCHK(dev_malloc(&c->d_prev, sizeof(int) * (size_t)c->ns_pad));
     HIPCHK(dev_malloc(&c->d_win, sizeof(float4) * (size_t)c->ns_pad));
-    dev_free(c->d_worder); dev_free(c->d_homes); dev_free(c->d_qcnt);
-    c->homes_cap = 0;
-    if (c->nn_wave_order && c->grid_mode == 0) HIPCHK(dev_malloc(&c->d_worder, sizeof(unsigned short) * (size_t)c->ns_pad));   // (brute force only; never inside a loop)
-    if (c->grid_mode == 0) { const int rcq = ensure_queue_buffers(c, c->ns_pad / chunk); if (rcq) return rcq; }   // (the brute-force launch's q_blocks; whatever the target: a few KB)
+    dev_free(c->d_prec); dev_free(c->d_homes); dev_free(c->d_qcnt);
+    c->prec_cap = 0; c->homes_cap = 0;
+    if (c->grid_mode == 0) { const int rcq = ensure_sorted_buffers(c, c->ns_pad / chunk); if (rcq) return rcq; }   // (brute force only, never inside a loop: 48 B per slot + the brute-force launch's q_blocks, a few KB)
     if (c->grid_safe && !c->surface) HIPCHK(dev_malloc(&c->d_wsafe, sizeof(uint2) * (size_t)c->ns_pad));   // (a vertex target set later allocates it: set_target_common)
     c->seeded = false; c->win_seeds = false;
     HIPCHK(dev_malloc(&c->d_sel, sizeof(int) * (size_t)c->ns_pad));

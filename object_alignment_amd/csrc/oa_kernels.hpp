@@ -1301,7 +1301,8 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_filt
 // Indices: position j of the sorted images holds original vertex tidx[j]; the exact path compares and reports ORIGINAL indices
 // (lowest index on ties, as everywhere).  A split owns a seed when seed index mod splits = split (no position lookup).
 // Tiles are visited middle-out from the slab nearest to the workgroup's first point: an unseeded search (the first iteration of a
-// loop) then finds a tight best at once instead of sweeping towards it; with seeds the order is immaterial.
+// loop) then finds a tight best at once instead of sweeping towards it, and a seeded one tightens its seeds at once (the order
+// never changes an answer, only how soon the thresholds are final).
 #if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
 __global__ void k_sort_keys_axis(const float *__restrict__ xyz, int nt, int axis, double lo, double scale, unsigned *__restrict__ keys,
                                  int *__restrict__ ids)
@@ -1376,7 +1377,7 @@ __device__ __forceinline__ void sorted_thresholds(float best, float hu, float hv
 // qu^2+qv^2).  Returns true when the point's best improved (its thresholds are then already renewed).
 __device__ __forceinline__ bool sorted_finish_group(const float4 AU, const float4 AV, const float4 W2, long long group,
                                                     const float4 *__restrict__ tf3s, const float4 *__restrict__ tgs,
-                                                    const int4 *__restrict__ tidx, float px, float py, float pz, float hu, float hv,
+                                                    const int4 *__restrict__ tidx, const float4 *__restrict__ pco, float hu, float hv,
                                                     float hd, double qmax, float &best, uint32_t &bidx, float &thr1, float &thr2)
 {
     // level 1: the 2-D score
@@ -1401,6 +1402,8 @@ __device__ __forceinline__ bool sorted_finish_group(const float4 AU, const float
     const float4 *eg = tgs + 3ll * group;
     const float4 X = eg[0], Y = eg[1], Z = eg[2];
     const int4 J = tidx[group];
+    const float4 P = *pco;                                         // co_find of the point, from its record: only here is it needed
+    const float px = P.x, py = P.y, pz = P.z;
     const float e0 = d2_metric(px, py, pz, X.x, Y.x, Z.x);
     const float e1 = d2_metric(px, py, pz, X.y, Y.y, Z.y);
     const float e2 = d2_metric(px, py, pz, X.z, Y.z, Z.z);
@@ -1416,45 +1419,87 @@ __device__ __forceinline__ bool sorted_finish_group(const float4 AU, const float
     return improved;
 }
 
-// Which of a wave's 64 R slots each lane takes as its point r, for k_nn_search_sorted: the slots in the order of their u (the
-// coordinate the target is sorted along) AT THE CURRENT POSE, so that point r of all lanes is the r-th slice of the wave's extent
-// in u -- a quarter (R = 4) of the slabs a plain run of 64 consecutive slots reaches into (level 1 runs per point r and wave).
-// One wave per 64 R slots; rank = number of slots with a smaller (key, position): a permutation whatever the values (NaN
-// included).  order[first + rank] = position of the slot within the wave's range.
-// (The same over a whole workgroup's 256 R slots -- sixteen thinner slices -- measured slower, 32.0 against 31.1 ms per iteration at
-// 1M <-> 1M: the lanes of a point r then spread over the workgroup's whole extent in the other two axes and levels 2 / 3 run for more
-// (wave, group) combinations.)
+// Everything k_nn_search_sorted needs to know about a point that does not depend on the split, once per search instead of once
+// per (split, block) item -- 136 times per point in a seeded 1M <-> 1M launch: co_find, the centred coordinates, the seed and
+// its distance, the thresholds.  One RECORD per slot, three float4 in three arrays of ns_pad entries (rec, rec + ns_pad,
+// rec + 2 ns_pad):
+//   [0] hu, hv, hd, the slot's index (int bits)     [1] best, bidx (uint bits), thr1, thr2     [2] px, py, pz (co_find), 0
+// The seed is the slot's winner record (pass 0) or what k_nn_seed_sorted left in keys (pass 2: this kernel runs after it).
+// The arithmetic is the item prologue's of before, through the same device functions: the same floats.
+// WHERE a slot's record lies decides which lane takes it as its point r: record first + 64 r + lane of a wave's 64 R records
+// is point r of that lane.  ranked: the wave's slots in the order of their u (the coordinate the target is sorted along) AT THE
+// CURRENT POSE, so that point r of all lanes is the r-th slice of the wave's extent in u -- a quarter (R = 4) of the slabs a
+// plain run of 64 consecutive slots reaches into (level 1 runs per point r and wave).  rank = number of slots with a smaller
+// (key, position): a permutation whatever the values (NaN included).  Not ranked (OA_NN_WAVE_ORDER=0): record i is slot i.
+// One wave per 64 R slots.
+// (The order over a whole workgroup's 256 R slots -- sixteen thinner slices -- measured slower in round 5, 32.0 against 31.1 ms
+// per iteration at 1M <-> 1M: the lanes of a point r then spread over the workgroup's whole extent in the other two axes and
+// levels 2 / 3 run for more (wave, group) combinations.)
 template <int R>
-__global__ __launch_bounds__(64) void k_sorted_wave_order(const DevState *__restrict__ st, const float4 *__restrict__ src4, int au,
-                                                          unsigned short *__restrict__ order)
+__global__ __launch_bounds__(64) void k_sorted_point_setup(const DevState *__restrict__ st, const float4 *__restrict__ src4,
+                                                           const float4 *__restrict__ win, const unsigned long long *__restrict__ keys,
+                                                           int au, int av, int pass, int ranked, int ns_pad, float4 *__restrict__ rec)
 {
-    constexpr int WAVES = 1;
-    constexpr int N = 64 * R * WAVES;
+    if (st->halt) return;
+    constexpr int N = 64 * R;
     __shared__ uint32_t key[N];
     const int t = threadIdx.x;
-    const long long first = (long long)blockIdx.x * N;
+    const int first = (int)blockIdx.x * N;
+    const double qmax = st->qmax;
+    const float cx = st->tc[0], cy = st->tc[1], cz = st->tc[2];
+    float4 ra[R], rb[R], rc[R];
     uint32_t mine[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const float4 p = src4[first + r * (64 * WAVES) + t];
+        const int i = first + r * 64 + t;
+        const float4 p = src4[i];
         float px, py, pz;
-        co_find(st, p.x, p.y, p.z, px, py, pz);
-        const float hu = au == 0 ? (float)((double)px - (double)st->tc[0]) : (au == 1 ? (float)((double)py - (double)st->tc[1]) : (float)((double)pz - (double)st->tc[2]));
+        co_find(st, p.x, p.y, p.z, px, py, pz);                    // co_find (general.py:287)
+        const float h0 = (float)((double)px - (double)cx);
+        const float h1 = (float)((double)py - (double)cy);
+        const float h2 = (float)((double)pz - (double)cz);
+        const float hu = au == 0 ? h0 : (au == 1 ? h1 : h2);
+        const float hv = av == 0 ? h0 : (av == 1 ? h1 : h2);
+        const float hd = (au + av == 1) ? h2 : ((au + av == 2) ? h1 : h0);
+        float best = INFINITY;
+        uint32_t bidx = IDX_NONE;
+        const float4 sw = (win && pass == 0) ? win[i] : make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
+        if (__float_as_int(sw.w) >= 0) {
+            const float d = d2_metric(px, py, pz, sw.x, sw.y, sw.z);
+            if (d < INFINITY) { best = d; bidx = (uint32_t)__float_as_int(sw.w); }
+        }
+        if (pass == 2) {
+            const unsigned long long k = keys[i];
+            const float kd = __uint_as_float((uint32_t)(k >> 32));
+            if ((uint32_t)k != IDX_NONE && kd < INFINITY) { best = kd; bidx = (uint32_t)k; }
+        }
+        float thr1, thr2;
+        sorted_thresholds(best, hu, hv, hd, qmax, thr1, thr2);
+        ra[r] = make_float4(hu, hv, hd, __int_as_float(i));
+        rb[r] = make_float4(best, __uint_as_float(bidx), thr1, thr2);
+        rc[r] = make_float4(px, py, pz, 0.f);
         const uint32_t b = __float_as_uint(hu);
         mine[r] = (b & 0x80000000u) ? ~b : (b | 0x80000000u);     // unsigned order = float order (NaNs at the ends: still a total order)
-        key[r * (64 * WAVES) + t] = mine[r];
     }
-    __syncthreads();
     int rank[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) rank[r] = 0;
-    for (int j = 0; j < N; ++j) {
-        const uint32_t k = key[j];                                 // (broadcast read)
+    for (int r = 0; r < R; ++r) rank[r] = ranked ? 0 : r * 64 + t;
+    if (ranked) {                                                  // (uniform)
 #pragma unroll
-        for (int r = 0; r < R; ++r) rank[r] += (k < mine[r] || (k == mine[r] && j < r * (64 * WAVES) + t)) ? 1 : 0;
+        for (int r = 0; r < R; ++r) key[r * 64 + t] = mine[r];
+        __syncthreads();
+        for (int j = 0; j < N; ++j) {
+            const uint32_t k = key[j];                             // (broadcast read)
+#pragma unroll
+            for (int r = 0; r < R; ++r) rank[r] += (k < mine[r] || (k == mine[r] && j < r * 64 + t)) ? 1 : 0;
+        }
     }
 #pragma unroll
-    for (int r = 0; r < R; ++r) order[first + rank[r]] = (unsigned short)(r * (64 * WAVES) + t);
+    for (int r = 0; r < R; ++r) {                                  // (rank < 64 R: inside the wave's own records)
+        rec[first + rank[r]] = ra[r];
+        rec[ns_pad + first + rank[r]] = rb[r];
+        rec[2 * ns_pad + first + rank[r]] = rc[r];
+    }
 }
 
 // Seeds for the first search of a loop: every point against the ONE tile of the sorted images whose slab holds its own u (exact
@@ -1510,8 +1555,9 @@ __global__ __launch_bounds__(256) void k_nn_seed_sorted(const DevState *__restri
 // index mod 8, and a workgroup serves the queue of its own XCD first (XCC_ID): a split's tiles stay in one L2, as they did when the
 // launch order itself was the mapping.  The answers cannot depend on who does what: keys[] is merged with atomicMin.
 // Measured (profiles/r06h): 1M <-> 1M 27.6 -> 26.6 ms per search, config 5's shard 58.7 -> 57.3, the 125k shard 3.98 -> 3.93.
-// k_sorted_block_homes: per block of NN_THREADS x R slots the split that holds the u of its first point at the current pose, and
-// the queues' counters back to zero (it runs in front of every queued launch).
+// k_sorted_block_homes: per block of NN_THREADS x R slots the split that holds the u of its slot 0 at the current pose
+// (homes[2 y]) and the tile that does (homes[2 y + 1]: where an item starts its middle-out visit), and the queues' counters back
+// to zero (it runs in front of every launch).
 constexpr int SORTED_QUEUES = 8, SORTED_QUEUE_STRIDE = 16;       // (counters 64 bytes apart)
 #if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
 __global__ void k_sorted_block_homes(const DevState *__restrict__ st, const float4 *__restrict__ src4, int n_blocks, int block_slots,
@@ -1532,14 +1578,14 @@ __global__ void k_sorted_block_homes(const DevState *__restrict__ st, const floa
     int sp = (int)(tile * n_splits / tiles);                       // the split whose range [s tiles / S, (s + 1) tiles / S) holds the tile
     while (sp + 1 < n_splits && (long long)(sp + 1) * tiles / n_splits <= tile) ++sp;
     while (sp > 0 && (long long)sp * tiles / n_splits > tile) --sp;
-    homes[y] = sp;
+    homes[2 * y] = sp;
+    homes[2 * y + 1] = (int)tile;
 }
 #endif  // !OA_FAMILY_TU
 
-constexpr int SORT_ORDER_MAX = 1024;
 #ifndef OA_SORTED_GW
 #define OA_SORTED_GW 64                   // groups of 4 sorted vertices per skip test of k_nn_search_sorted (a build-time knob for sweeps)
-#endif      // tiles of one split whose middle-out order fits the LDS table (more: ascending)
+#endif
 #ifndef OA_SORTED_VCG
 #define OA_SORTED_VCG 4                   // groups of 4 sorted vertices per chunk of level 0v (a build-time knob for sweeps;
 #endif                                    //  2 / 4 / 8: 25.46 / 24.99 / 24.94 ms at 1M <-> 1M, profiles/r08a_vends.txt)
@@ -1552,7 +1598,7 @@ constexpr int SORT_ORDER_MAX = 1024;
 // second axis v (ties: the u position), so that level 0v (k_nn_search_sorted) finds a point's few vertices near it in v in a few
 // chunks of 16.  A block holds the same set of vertices as before, so level 0's decisions are unchanged (a minimum does not depend
 // on the order), and position 0 of every block stays where it is: a tile's first vertex is the one the binary searches for a
-// point's home tile read (tfs[3 TG t].x: k_nn_search_sorted's visiting order, k_sorted_block_homes, k_nn_seed_sorted).  Padding
+// point's home tile read (tfs[3 TG t].x: k_sorted_block_homes, k_nn_seed_sorted).  Padding
 // (positions >= nt) is only ever at the tail of the last block and stays there.  One workgroup per block, a rank sort in LDS;
 // at upload only.
 constexpr int SORTED_VBLOCK = 4 * (OA_SORTED_GW < 64 ? OA_SORTED_GW : 64);
@@ -1585,15 +1631,13 @@ __global__ __launch_bounds__(SORTED_VBLOCK) void k_sort_blocks_v(const float *__
 
 template <int R, int TG = FTILE_GROUPS, bool VCHUNK = true>
 __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sorted(const DevState *__restrict__ st,
-                                                                 const float4 *__restrict__ src4,
                                                                  const float4 *__restrict__ tgs,
                                                                  const float4 *__restrict__ tfs,
                                                                  const float4 *__restrict__ tf3s,
                                                                  const int4 *__restrict__ tidx,
-                                                                 const float4 *__restrict__ win,
-                                                                 int n_groups_pad, int au, int av,
+                                                                 int n_groups_pad,
                                                                  unsigned long long *keys, int pass,
-                                                                 const unsigned short *__restrict__ order,
+                                                                 const float4 *__restrict__ rec,
                                                                  int n_splits, int n_blocks, const int *__restrict__ homes, int *qcnt,
                                                                  int nt)
 {
@@ -1605,7 +1649,6 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
     constexpr bool WHOLE = TILE_F4 % NN_THREADS == 0;
     static_assert(LOADS >= 1 && LOADS <= 3, "k_nn_search_sorted: 1 .. 3 float4 per thread and tile");
     __shared__ float4 tile[2][TILE_F4];
-    __shared__ short ord[SORT_ORDER_MAX];
     __shared__ unsigned long long clk0[2];
     __shared__ int s_item[3];                                       // the workgroup's item {split, block}; [2]: the queues found empty so far
     const int tid0 = threadIdx.x;
@@ -1635,7 +1678,7 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                 if (pos >= q_len) { q_dry |= 1u << q; continue; }
                 got_y = pos / per_q;
                 const int k = pos - got_y * per_q;
-                int j0 = (homes[got_y] - q + nq / 2) / nq;          // the queue's split nearest to the block's own
+                int j0 = (homes[2 * got_y] - q + nq / 2) / nq;          // the queue's split nearest to the block's own
                 j0 = j0 < 0 ? 0 : (j0 >= per_q ? per_q - 1 : j0);
                 int j = (j0 + ((k & 1) ? (k + 1) / 2 : -(k / 2))) % per_q;
                 if (j < 0) j += per_q;
@@ -1650,40 +1693,30 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
     const bool clk_wg = (split == 0 && yblk == n_blocks / 2 && tid == 0);   // one workgroup's item from the middle of the launch
     if (clk_wg) { clk0[0] = (unsigned long long)__builtin_readcyclecounter(); clk0[1] = wall_clock64(); }
     const double qmax = st->qmax;
-    const float cx = st->tc[0], cy = st->tc[1], cz = st->tc[2];
-    const int base = yblk * (NN_THREADS * R);
-    // a wave owns R x 64 CONSECUTIVE slots (neighbours in space: the smallest extent in u, the fewest slabs it must look into);
-    // point r of a lane is slot base + slot_of(r)
-    // ... and WHICH of them is a lane's point r says k_sorted_wave_order: the wave's slots in the order of u, so that point r of all
-    // lanes is one slice of the wave's extent (order == nullptr: slot r * 64 + lane)
-    const int wave_first = base + (tid >> 6) * (64 * R);
-#define OA_SLOT(r) (wave_first + (order ? (int)order[wave_first + (r) * 64 + (tid & 63)] : (r) * 64 + (tid & 63)))
-    float px[R], py[R], pz[R], hu[R], hv[R], hd[R], best[R], thr1[R], thr2[R];
+    // a wave owns R x 64 CONSECUTIVE slots (neighbours in space: the smallest extent in u, the fewest slabs it must look into), and
+    // so R x 64 consecutive records (k_sorted_point_setup, which also decides WHICH of the wave's slots a lane takes as its point
+    // r): record rec0 + 64 r is point r of this lane -- coalesced loads, nothing to compute.  co_find itself (the record's third
+    // float4) is loaded where level 3 needs it: twelve registers (R = 4) not held through the scan, and no scratch left
+    const int ns_pad = n_blocks * (NN_THREADS * R);
+    const int rec0 = yblk * (NN_THREADS * R) + (tid >> 6) * (64 * R) + (tid & 63);
+    float hu[R], hv[R], hd[R], best[R], thr1[R], thr2[R];
     uint32_t bidx[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const int i = OA_SLOT(r);
-        const float4 p = src4[i];
-        co_find(st, p.x, p.y, p.z, px[r], py[r], pz[r]);    // co_find (general.py:287)
-        const float h0 = (float)((double)px[r] - (double)cx);
-        const float h1 = (float)((double)py[r] - (double)cy);
-        const float h2 = (float)((double)pz[r] - (double)cz);
-        hu[r] = au == 0 ? h0 : (au == 1 ? h1 : h2);
-        hv[r] = av == 0 ? h0 : (av == 1 ? h1 : h2);
-        hd[r] = (au + av == 1) ? h2 : ((au + av == 2) ? h1 : h0);
-        best[r] = INFINITY;
-        bidx[r] = IDX_NONE;
-        const float4 sw = (win && pass == 0) ? win[i] : make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-        if (__float_as_int(sw.w) >= 0) {
-            const float d = d2_metric(px[r], py[r], pz[r], sw.x, sw.y, sw.z);
-            if (d < INFINITY) { best[r] = d; bidx[r] = (uint32_t)__float_as_int(sw.w); }
-        }
-        if (pass == 2) {                                           // (a 64-bit load: whatever another split has merged by now is as good)
-            const unsigned long long k = __hip_atomic_load(keys + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const float4 ra = rec[rec0 + 64 * r], rb = rec[ns_pad + rec0 + 64 * r];
+        hu[r] = ra.x; hv[r] = ra.y; hd[r] = ra.z;
+        best[r] = rb.x; bidx[r] = __float_as_uint(rb.y); thr1[r] = rb.z; thr2[r] = rb.w;
+        if (pass == 2) {
+            // (a 64-bit load: whatever another split has merged by now is as good.  keys only fall, so the key is the record's
+            //  seed or beats it; the thresholds depend on the distance alone)
+            const unsigned long long k = __hip_atomic_load(keys + __float_as_int(ra.w), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const float kd = __uint_as_float((uint32_t)(k >> 32));
-            if ((uint32_t)k != IDX_NONE && kd < INFINITY) { best[r] = kd; bidx[r] = (uint32_t)k; }
+            if ((uint32_t)k != IDX_NONE && kd < INFINITY && k < (((unsigned long long)__float_as_uint(best[r]) << 32) | bidx[r])) {
+                const bool nearer = kd < best[r];
+                best[r] = kd; bidx[r] = (uint32_t)k;
+                if (nearer) sorted_thresholds(best[r], hu[r], hv[r], hd[r], qmax, thr1[r], thr2[r]);
+            }
         }
-        sorted_thresholds(best[r], hu[r], hv[r], hd[r], qmax, thr1[r], thr2[r]);
     }
 
     int g_begin, g_end;
@@ -1691,26 +1724,17 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
     const int n_tiles = (g_end - g_begin) / TG;
     const float4 *tsrc = tfs + 3ll * g_begin;
 
-    // visiting order of this split's tiles: middle-out from the slab nearest (in u) to the workgroup's first point
-    const bool ordered = n_tiles <= SORT_ORDER_MAX;
-    if (ordered && tid == 0) {
-        // the first vertex of tile t has u = tsrc[3 TG t].x, rising with t (the images are sorted by u): binary search for
-        // the first tile that starts beyond the point -- the slab before it holds the point's u (an approximate start is fine)
-        int a = 0, b = n_tiles;                                    // tiles [0, a) start at or before the point
-        while (a < b) {
-            const int mid = (a + b) >> 1;
-            if (tsrc[3ll * TG * mid].x <= hu[0]) a = mid + 1; else b = mid;
-        }
-        const int s = a > 0 ? a - 1 : 0;
-        int lo = s - 1, hi = s + 1, n = 0;
-        ord[n++] = (short)s;
-        while (n < n_tiles) {
-            if (hi < n_tiles) ord[n++] = (short)hi++;
-            if (lo >= 0 && n < n_tiles) ord[n++] = (short)lo--;
-        }
-    }
-    __syncthreads();
-#define OA_TILE_AT(k) (ordered ? (int)ord[(k)] : (k))
+    // visiting order of this split's tiles: middle-out from the tile that holds the u of the block's slot 0
+    // (k_sorted_block_homes), or the split's end nearest to it -- tile_s, then tile_s + 1, tile_s - 1, ... for tile_m steps on
+    // both sides, then the longer side alone; all of it scalar arithmetic, no loads beyond the block's home.  With seeds too: a
+    // seed is the nearest vertex of the LAST pose, and the sooner the item meets the point's own slab, the sooner its thresholds
+    // are final (seeded items in plain order: 25.1 against 24.0 ms per iteration at 1M <-> 1M, profiles/r10a_point_setup.txt).
+    int tile_s = homes[2 * yblk + 1] - g_begin / TG;
+    tile_s = tile_s < 0 ? 0 : (tile_s >= n_tiles ? n_tiles - 1 : tile_s);
+    const bool tile_up = n_tiles - 1 - tile_s > tile_s;
+    const int tile_m = tile_up ? tile_s : n_tiles - 1 - tile_s;
+#define OA_TILE_AT(k) ((k) > 2 * tile_m ? (tile_up ? tile_s + (k) - tile_m : tile_s + tile_m - (k))                                  \
+                                        : (((k) & 1) ? tile_s + (((k) + 1) >> 1) : tile_s - ((k) >> 1)))
 
     float4 stg0 = make_float4(0.f, 0.f, 0.f, 0.f), stg1 = stg0, stg2 = stg0;
 #define OA_STG_ON(k) (WHOLE || (k) * NN_THREADS + tid < TILE_F4)
@@ -1847,7 +1871,7 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                             }
                             const float4 AU = make_float4(-2.0f * Q.x, -2.0f * Q.y, -2.0f * Q.z, -2.0f * Q.w);   // exact
                             if (want)
-                                sorted_finish_group(AU, AV, W2, gbase + g + k, tf3s, tgs, tidx, px[r], py[r], pz[r], hu[r], hv[r], hd[r],
+                                sorted_finish_group(AU, AV, W2, gbase + g + k, tf3s, tgs, tidx, rec + 2 * ns_pad + rec0 + 64 * r, hu[r], hv[r], hd[r],
                                                     qmax, best[r], bidx[r], thr1[r], thr2[r]);
                         }
                     }
@@ -1860,7 +1884,7 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         if (!hit[r]) continue;                     // (a point's run of 64 slots is a quarter of the wave's extent)
-                        sorted_finish_group(AU, AV, W2, gbase + g + k, tf3s, tgs, tidx, px[r], py[r], pz[r], hu[r], hv[r], hd[r], qmax,
+                        sorted_finish_group(AU, AV, W2, gbase + g + k, tf3s, tgs, tidx, rec + 2 * ns_pad + rec0 + 64 * r, hu[r], hv[r], hd[r], qmax,
                                             best[r], bidx[r], thr1[r], thr2[r]);
                     }
                 }
@@ -1882,24 +1906,23 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
         ws->search_clk[0] = (unsigned long long)__builtin_readcyclecounter() - clk0[0];
         ws->search_clk[1] = wall_clock64() - clk0[1];
     }
-    // a split reports when it has something to say (k_nn_search_filtered); the seed's owner: seed index mod splits
+    // a split reports when it has something to say (k_nn_search_filtered); the seed's owner: seed index mod splits.
+    // (The slot's index and the seed again from the record, instead of three registers per point held through the scan: the
+    //  laundered index below makes these loads new ones the compiler cannot merge with the prologue's, and that reload is what
+    //  keeps the kernel at 0 B of scratch.)
+    int rec1 = rec0;
+    asm volatile("" : "+v"(rec1));
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const unsigned long long key = ((unsigned long long)__float_as_uint(best[r]) << 32) | bidx[r];
-        unsigned long long *dst = keys + OA_SLOT(r);
+        unsigned long long *dst = keys + __float_as_int(rec[rec1 + 64 * r].w);
         if (pass != 0) {                                           // merges into whatever keys holds: monotone
             if (key < __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(dst, key);
         } else if (n_splits == 1) *dst = key;
         else {
-            // (the seed again, from the slot's record -- the same arithmetic as at the start -- instead of two registers per point
-            //  held through the scan)
-            uint32_t seed_idx = IDX_NONE;
-            float seed_d = INFINITY;
-            const float4 sw = win ? win[OA_SLOT(r)] : make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
-            if (__float_as_int(sw.w) >= 0) {
-                const float d = d2_metric(px[r], py[r], pz[r], sw.x, sw.y, sw.z);
-                if (d < INFINITY) { seed_d = d; seed_idx = (uint32_t)__float_as_int(sw.w); }
-            }
+            const float4 rb = rec[ns_pad + rec1 + 64 * r];
+            const float seed_d = rb.x;
+            const uint32_t seed_idx = __float_as_uint(rb.y);
             const bool seeded = seed_idx != IDX_NONE;
             const bool improved = bidx[r] != seed_idx || best[r] != seed_d;
             const bool owner = seeded && (int)(seed_idx % (uint32_t)n_splits) == split;
@@ -1909,8 +1932,6 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
     if (!queued) break;
   }
 }
-
-#undef OA_SLOT
 
 // ------------------------------------------------------------------------------------------------
 // k_pair_accumulate

@@ -1,4 +1,6 @@
 // oa_sorted16.hpp -- k_nn_search_sorted16: k_nn_search_sorted with its level 0 in packed half precision (round 5).
+// (Shelved as of round 8: written against k_sorted_wave_order's order table and sorted_finish_group(.., px, py, pz, ..); since
+//  round 10 the search reads k_sorted_point_setup's records -- port the prologue before reviving it.)
 //
 // EXPERIMENT, NOT BUILT INTO liboa_icp.so.  Kept as the record of a negative result (tools/experiments/README.md): wired in
 // (include after oa_kernels.hpp, launch instead of k_nn_search_sorted<R, 256>) it answered the sorted-kernel tests it was run on
