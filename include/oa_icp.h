@@ -390,6 +390,7 @@ int oa_reset_seeds(oa_ctx *ctx);
 #define OA_STAT_ROBUST_QUANTILE 33   /* oa_set_robust_auto's quantile (0 = off) */
 #define OA_STAT_TARGET_NORMALS  34   /* 1 when a vertex-mode target has normals installed (oa_set_target_normals, oa_set_normals, an estimate) */
 #define OA_STAT_TARGET_FEATURES 35   /* 1 when oa_target_fpfh(keep) left descriptors resident */
+#define OA_STAT_MESH_PSEUDONORMALS 36 /* 1 when the mesh's pseudo-normals are built (oa_deviation, oa_get_mesh_pseudonormals); a new upload forgets them */
 #define OA_STAT_ENQUEUED_CHILD  1000   /* + i: the same count for child i alone */
 int oa_get_stat(oa_ctx *ctx, int what, double *value);
 /* why the exchange is what it is (AUTO's reason for not taking RCCL, librccl's error, "RCCL was aborted: ..."), or "" */
@@ -625,6 +626,71 @@ int oa_voxel_downsample(oa_ctx *ctx, const float *xyz, int64_t n, int on_device,
                         double voxel, const double origin[3] /* or NULL */, int64_t cap,
                         float *out_xyz /* cap x 3 */, float *out_normals /* cap x 3 */, int32_t *out_count /* cap */,
                         int64_t *out_rep /* cap */, int64_t *n_out, oa_voxel_report *rep);
+
+/* ---- EXTENSION: the deviation report -- how good is this alignment, and where does it deviate?    The loop's
+ *      report carries the mean of the last step's pairs UNDER thresh, so a pose that lost half of its overlap reports a better
+ *      mean; this call measures every selected point at the pose in force and says on which side of the target it lies. ----------- */
+typedef struct oa_deviation_settings {
+    double  thresh;         /* inlier test dist < thresh (the reference's); +inf: every pair is an inlier.  Must be > 0 */
+    int32_t signed_mode;    /* -1 signed when possible (default), 0 never, 1 required (OA_E_STATE for a vertex-mode target without normals) */
+    int32_t n_quantiles;    /* 0 .. 8 */
+    double  quantiles[8];   /* each in (0, 1] */
+    int32_t n_bins;         /* 0 .. 1024 histogram bins over [hist_lo, hist_hi) of signed_d; 0 = no histogram */
+    int32_t reserved;
+    double  hist_lo, hist_hi;
+} oa_deviation_settings;
+typedef struct oa_deviation_report {
+    int64_t n, n_valid, n_inlier;   /* slots; with a correspondence; with dist < thresh */
+    int64_t n_inside, n_unsigned;   /* signed_d < 0; signed slots whose normal was zero or not finite (they count as +dist) */
+    int64_t max_index;              /* lowest caller-order position that attains max_dist (-1: no valid slot) */
+    double  fitness;                /* n_inlier / n */
+    double  mean, rms, std, mean_signed;   /* over the inliers; std = sqrt(max(rms^2 - mean^2, 0)); NaN without inliers */
+    double  max_dist;               /* over the valid slots: the one-sided Hausdorff distance source -> target */
+    double  quantile_values[8];     /* value k: the ceil(q_k n_valid)-th smallest of (float)dist over the valid slots */
+    int32_t n_quantiles;
+    int32_t signed_used;            /* 0 unsigned, 1 the mesh's pseudo-normals, 2 the target vertices' normals */
+    int32_t surface, reserved;      /* 1: surface mode */
+    double  search_ms, total_ms;    /* device time of the search; host time of the call */
+    double  pseudonormal_ms;        /* host time of the pseudo-normal build when this call did it, else 0 */
+} oa_deviation_report;
+/* At the context's current matrix_world / mx_base, over the selected source points of the shard: ONE correspondence search (any
+ * search mode, seeded or cold: the same answer), then for every slot, in the caller's (vlist) order -- every output pointer may
+ * be NULL:
+ *   idx       int64      what oa_nn_search returns for the slot; -1 = no correspondence (a non-finite source point)
+ *   closest   float32 x3 co1: the closest point on triangle idx (surface mode; closest_on_tri's bits) or target vertex idx, base-local
+ *   dist      float64    the world-space pair distance exactly as the accumulation kernels form it (the same bits); NaN without a
+ *                        correspondence (closest and signed_d are NaN there too)
+ *   signed_d  float64    dist with the sign below
+ *   feature   int8       surface mode: where on the triangle the closest point lies -- 0 face; 1 / 2 / 3 edge ab / bc / ca; 4 / 5 / 6
+ *                        vertex a / b / c (the region closest_on_tri's tests end in).  Vertex mode or no correspondence: -1
+ * Sign.  p = co_find, r = co1 (float32, base-local), N the angle-weighted pseudo-normal (Baerentzen & Aanaes 2005) of the feature:
+ *   s = ((p - r)_x N_x + (p - r)_y N_y) + (p - r)_z N_z in fp64;  signed_d = -dist if s < 0, else +dist.
+ * Outside a counter-clockwise-wound (Blender's convention) closed mesh is positive.  A zero or non-finite N gives +dist and the
+ * slot is counted in n_unsigned.  The sign is decided in base-local space: a mirrored mx_base does not flip it.
+ * Pseudo-normals of the mesh: built on the device once per mesh, at the first signed call; a new upload forgets them
+ * (OA_STAT_MESH_PSEUDONORMALS).  fp64 arithmetic on the float32 vertices, no fused multiply-add, no atomics -- two builds give the
+ * same bits:
+ *   n_t  = cross(b - a, c - a) * (1 / sqrt((x x + y y) + z z)); a triangle whose squared length is zero or not finite has
+ *          n_t = 0 and corner angles 0: it takes part in nothing
+ *   corner angle = atan2(|u x v|, u . v), u and v the corner's two edges
+ *   N_v  = sum angle n_t over the corners at vertex INDEX v, added in ascending (triangle, corner) order
+ *   N_uv = sum n_t over ALL triangles that have the undirected edge {u, v} (matched by vertex index), in ascending triangle order:
+ *          the same bits for every triangle of the edge; a boundary edge has its one face, a non-manifold edge all of them
+ * Faces use n_t in fp64; N_v and N_uv are stored as float32 (what oa_get_mesh_pseudonormals returns) and widened.
+ * Vertex mode: N = the target vertex's normal (oa_set_target_normals, oa_set_normals, an estimate); without normals the result is
+ * unsigned (signed_d = dist, signed_used = 0) -- or, with signed_mode = 1, OA_E_STATE.
+ * Statistics (oa_deviation_report): integer counts, fixed-order fp64 sums (the same bits on every run and in every search mode);
+ * the quantiles are exact order statistics by the rule and the radix select of oa_set_robust_auto.  Histogram (hist: n_bins + 2
+ * int64 counts, the first for signed_d < hist_lo, the last for signed_d >= hist_hi): a valid slot with lo <= d < hi goes to bin
+ * min(floor((d - lo) * (n_bins / (hi - lo))), n_bins - 1), fp64.
+ * The call does not look at the normal-angle test, the robust loss, the weights or the metric.  It stages the device state as
+ * oa_nn_search does (a running oa_iterate sequence ends).  OA_E_STATE on a multi-device context (it stays usable);
+ * OA_E_BAD_THRESH for a thresh that is not > 0; OA_E_BAD_ARG for the other settings out of range. */
+int oa_deviation(oa_ctx *ctx, const oa_deviation_settings *settings, double *signed_d, double *dist, float *closest /* n x 3 */,
+                 int64_t *idx, int8_t *feature, int64_t *hist /* n_bins + 2 */, oa_deviation_report *report);
+/* the mesh's pseudo-normals (built if needed): vertex_n nt x 3, edge_n n_tris x 3 edges (ab, bc, ca) x 3, host, either may be
+ * NULL.  OA_E_STATE without a mesh target. */
+int oa_get_mesh_pseudonormals(oa_ctx *ctx, float *vertex_n /* nv x 3 */, float *edge_n /* nt x 3 x 3 */);
 
 #ifdef __cplusplus
 }

@@ -44,3 +44,24 @@ def voxel_downsample(xyz, voxel, normals=None, origin=None, device=0):
     xyz, normals, origin = _voxel_args(xyz, voxel, normals, origin)
     with IcpEngine(int(device)) as eng:
         return eng.voxel_downsample(xyz, voxel, normals=normals, origin=origin)
+
+
+def deviation(source_xyz, target_xyz, target_tris=None, mx_align=None, mx_base=None, target_normals=None, device=0, **kw):
+    """The deviation report of a source against a target at given matrices (identity when None): signed per-point distances and
+    fit statistics (IcpEngine.deviation; **kw are its arguments).  target_tris: the target is a mesh and the sign comes from its
+    pseudo-normals; else target_normals (one per target vertex) sign a point-cloud target.  Opens a context of its own on
+    `device`."""
+    import numpy as np
+    from .engine import IcpEngine, _deviation_args
+    _deviation_args(**kw)
+    eye = np.eye(4, dtype=np.float32)
+    with IcpEngine(int(device)) as eng:
+        if target_tris is not None:
+            eng.set_target_mesh(target_xyz, target_tris)
+        else:
+            eng.set_target(target_xyz)
+            if target_normals is not None:
+                eng.set_target_normals(target_normals)
+        eng.set_source(source_xyz)
+        eng.set_matrices(eye if mx_align is None else mx_align, eye if mx_base is None else mx_base)
+        return eng.deviation(**kw)

@@ -41,6 +41,7 @@ OA_ORIENT_AWAY = 2
 OA_FPFH_DIM = 33
 OA_FEAT_TOO_FEW_PAIRS = 1
 OA_FEAT_NO_POSE = 2
+OA_STAT_MESH_PSEUDONORMALS = 36
 
 # every symbol include/oa_icp.h declares (tests check that the library exports all of them)
 SYMBOLS = [
@@ -59,6 +60,7 @@ SYMBOLS = [
     "oa_set_gicp", "oa_set_source_normals",
     "oa_coarse_align_poses", "oa_target_fpfh", "oa_match_features", "oa_feature_candidates",
     "oa_voxel_downsample",
+    "oa_deviation", "oa_get_mesh_pseudonormals",
 ]
 
 
@@ -98,6 +100,19 @@ class FeatureReport(C.Structure):
 class VoxelReport(C.Structure):
     _fields_ = [("n_in", C.c_int64), ("n_finite", C.c_int64), ("n_voxels", C.c_int64), ("max_members", C.c_int64),
                 ("dims", C.c_int32 * 3), ("reserved", C.c_int32), ("origin", C.c_double * 3), ("total_ms", C.c_double)]
+
+
+class DeviationSettings(C.Structure):
+    _fields_ = [("thresh", C.c_double), ("signed_mode", C.c_int32), ("n_quantiles", C.c_int32), ("quantiles", C.c_double * 8),
+                ("n_bins", C.c_int32), ("reserved", C.c_int32), ("hist_lo", C.c_double), ("hist_hi", C.c_double)]
+
+
+class DeviationReport(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_valid", C.c_int64), ("n_inlier", C.c_int64), ("n_inside", C.c_int64), ("n_unsigned", C.c_int64),
+                ("max_index", C.c_int64), ("fitness", C.c_double), ("mean", C.c_double), ("rms", C.c_double), ("std", C.c_double),
+                ("mean_signed", C.c_double), ("max_dist", C.c_double), ("quantile_values", C.c_double * 8), ("n_quantiles", C.c_int32),
+                ("signed_used", C.c_int32), ("surface", C.c_int32), ("reserved", C.c_int32), ("search_ms", C.c_double),
+                ("total_ms", C.c_double), ("pseudonormal_ms", C.c_double)]
 
 
 class OaError(RuntimeError):
@@ -199,6 +214,8 @@ def load(experiments: bool = False):
     L.oa_feature_candidates.argtypes = [vp, fp, C.c_int64, fp, C.POINTER(FeatureSettings), i32p, fp, i32p, C.POINTER(FeatureReport)]
     L.oa_voxel_downsample.argtypes = [vp, vp, C.c_int64, C.c_int, vp, C.c_double, dp, C.c_int64, fp, fp, i32p, ip, ip,
                                       C.POINTER(VoxelReport)]
+    L.oa_deviation.argtypes = [vp, C.POINTER(DeviationSettings), dp, dp, fp, ip, C.POINTER(C.c_int8), ip, C.POINTER(DeviationReport)]
+    L.oa_get_mesh_pseudonormals.argtypes = [vp, fp, fp]
     _libs[experiments] = L
     return L
 

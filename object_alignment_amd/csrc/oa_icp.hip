@@ -19,6 +19,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "oa_all.hpp"                // every kernel header + oa_families.hpp: the heavy templates are `extern` here, compiled in oa_fam_*.hip
 #include "oa_sort.hpp"
 #include "oa_voxel.hpp"
+#include "oa_deviation.hpp"
 #include "../../include/oa_icp.h"
 
 #include <algorithm>
@@ -360,6 +361,12 @@ struct oa_ctx {
     bool surface = false, tri_grid_ok = false;
     int n_tris = 0;
     float4 *d_tri9 = nullptr;
+    int *d_tris = nullptr;           // the mesh's vertex indices, n_tris x 3 (the pseudo-normals are built from them, oa_deviation.hpp)
+    // angle-weighted pseudo-normals of the mesh (oa_deviation / oa_get_mesh_pseudonormals): built at the first signed call, forgotten by a new upload
+    bool pn_ok = false;
+    double *d_pn_face = nullptr;     // n_tris x 3: unit face normals
+    float *d_pn_vertex = nullptr, *d_pn_edge = nullptr;   // nt x 3; n_tris x 3 edges x 3
+    double last_pn_ms = 0.0;         // host time of the last build
     oa::GridParams tgp;
     int *d_tcell_start = nullptr;
     float4 *d_tcell_rec = nullptr;   // two float4 per cell-list entry: {disc centre, radius} {unit normal, triangle index}
@@ -2362,6 +2369,7 @@ OA_EXPORT void oa_destroy(oa_ctx *c)
     OA_FREE(d_bvh_box); OA_FREE(d_bvh_prims); OA_FREE(d_tbvh_box); OA_FREE(d_tbvh_prims);
     OA_FREE(d_tri9); OA_FREE(d_tcell_start); OA_FREE(d_tcell_rec); OA_FREE(d_tri_ring); OA_FREE(d_tfine_table); OA_FREE(d_tfine_rec);
     OA_FREE(d_sel); OA_FREE(d_src_n); OA_FREE(d_tgt_n); OA_FREE(d_tgt_feat); OA_FREE(d_w); OA_FREE(d_rkeys); OA_FREE(d_sel_hist); OA_FREE(d_src4o); OA_FREE(d_perm);
+    OA_FREE(d_tris); OA_FREE(d_pn_face); OA_FREE(d_pn_vertex); OA_FREE(d_pn_edge);
 #undef OA_FREE
     if (c->h_hist_map) (void)hipHostFree(c->h_hist_map);
     if (c->h_state_pin) (void)hipHostFree(c->h_state_pin);
@@ -2662,6 +2670,8 @@ int set_target_common(oa_ctx *c, const float *xyz, int64_t n, int on_device, boo
     dev_free(c->d_tfs); dev_free(c->d_tf3s); dev_free(c->d_tgs); dev_free(c->d_tidx);
     dev_free(c->d_tri9); dev_free(c->d_tcell_start); dev_free(c->d_tcell_rec); dev_free(c->d_tri_ring);
     dev_free(c->d_tfine_table); dev_free(c->d_tfine_rec);
+    dev_free(c->d_tris); dev_free(c->d_pn_face); dev_free(c->d_pn_vertex); dev_free(c->d_pn_edge);
+    c->pn_ok = false;
     c->tri_ring_ok = false; c->tri_fine_ok = false;
     dev_free(c->d_bvh_box); dev_free(c->d_bvh_prims); dev_free(c->d_tbvh_box); dev_free(c->d_tbvh_prims);
     c->surface = false; c->tri_grid_ok = false; c->n_tris = 0; c->bvh_ok = false; c->tbvh_ok = false;
@@ -3291,16 +3301,16 @@ OA_EXPORT int oa_set_target_mesh(oa_ctx *c, const float *xyz, int64_t n_verts, i
     int rc = set_target_common(c, xyz, n_verts, on_device, false);  // vertex images + bbox + filter; no vertex grid / tree
     if (rc) return rc;
     if (n_verts < 1) return fail(OA_E_BAD_ARG, "oa_set_target_mesh: no vertices");
-    DevTmp<int> d_tris;
+    int *&d_tris = c->d_tris;                                      // kept: the pseudo-normals are built from the indices (set_target_common freed the old ones)
     constexpr size_t SLOT_WORDS = (size_t)oa::TOTAL_SLOTS * oa::TOTAL_STRIDE;
     DevTmp<double> d_chk;                                           // [0]: (as int) corners that index outside the vertices; [1 ...]: the spread sum of the bounding-box diagonals (oa_tri.hpp: TOTAL_SLOTS)
-    HIPCHK(d_tris.alloc(3 * (size_t)n_tris));
+    HIPCHK(dev_malloc(&d_tris, sizeof(int) * 3 * (size_t)n_tris));
     HIPCHK(d_chk.alloc(1 + SLOT_WORDS));
     HIPCHK(hipMemcpyAsync(d_tris, tris, sizeof(int) * 3 * (size_t)n_tris, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemsetAsync(d_chk, 0, (1 + SLOT_WORDS) * sizeof(double), c->stream));
     HIPCHK(dev_malloc(&c->d_tri9, sizeof(float4) * 3 * (size_t)n_tris));
     hipLaunchKernelGGL(oa::k_pack_tris, dim3((unsigned)((n_tris + 255) / 256)), dim3(256), 0, c->stream, c->d_tgt_xyz,
-                       (int)n_verts, (const int *)d_tris.p, (int)n_tris, c->d_tri9, (int *)d_chk.p);
+                       (int)n_verts, (const int *)d_tris, (int)n_tris, c->d_tri9, (int *)d_chk.p);
     // the triangle grid's cell size comes from the mean bounding-box diagonal: summed here, so that the index check and the
     // sum come back in ONE host round trip (a bad index leaves a triangle of garbage corners: the sum is not used then)
     hipLaunchKernelGGL(oa::k_tri_diag_sum, dim3((unsigned)((n_tris + 255) / 256)), dim3(256), 0, c->stream, c->d_tri9, (int)n_tris, d_chk.p + 1);
@@ -3311,7 +3321,7 @@ OA_EXPORT int oa_set_target_mesh(oa_ctx *c, const float *xyz, int64_t n_verts, i
     memcpy(&bad, &chk[0], sizeof(int));
     double diag_sum = 0.0;
     for (int k = 0; k < oa::TOTAL_SLOTS; ++k) diag_sum += chk[1 + (size_t)k * oa::TOTAL_STRIDE];
-    if (bad) { dev_free(c->d_tri9); return fail(OA_E_BAD_ARG, "oa_set_target_mesh: %d triangle corners index outside 0..%lld", bad, (long long)n_verts - 1); }
+    if (bad) { dev_free(c->d_tri9); dev_free(c->d_tris); return fail(OA_E_BAD_ARG, "oa_set_target_mesh: %d triangle corners index outside 0..%lld", bad, (long long)n_verts - 1); }
     c->n_tris = (int)n_tris;
     c->surface = true;
     if ((rc = build_bvh(c, true))) return rc;
@@ -3924,6 +3934,7 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
     case OA_STAT_ROBUST_QUANTILE: *value = c->robust_p; return OA_OK;
     case OA_STAT_TARGET_NORMALS: *value = (!c->surface && c->d_tgt_n) ? 1.0 : 0.0; return OA_OK;
     case OA_STAT_TARGET_FEATURES: *value = c->d_tgt_feat ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_MESH_PSEUDONORMALS: *value = (c->surface && c->pn_ok) ? 1.0 : 0.0; return OA_OK;
     default: return fail(OA_E_BAD_ARG, "oa_get_stat: unknown key %d", what);
     }
 }
@@ -5448,5 +5459,197 @@ OA_EXPORT int oa_voxel_downsample(oa_ctx *c, const float *xyz, int64_t n, int on
     if (n_out) *n_out = n_rows;
     if (rep) *rep = r;
     if (!fits) return fail(OA_E_CAPACITY, "oa_voxel_downsample: %lld occupied voxels, room for %lld rows", n_rows, (long long)cap);
+    return OA_OK;
+}
+
+// ================================================================================================
+// deviation report (EXTENSION; oa_deviation.hpp)
+// ================================================================================================
+namespace {
+// the mesh's pseudo-normals, once per upload: face normals and corner angles, the stable order of the corners by vertex (a CSR
+// row per vertex, ascending by (triangle, corner)), then one thread per vertex and per (triangle, edge)
+int ensure_pseudonormals(oa_ctx *c)
+{
+    if (c->pn_ok) return OA_OK;
+    if (!c->surface || !c->d_tris || c->n_tris < 1 || c->nt < 1) return fail(OA_E_STATE, "pseudo-normals need a mesh target (oa_set_target_mesh)");
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n_tris = (size_t)c->n_tris, n_corners = 3 * n_tris, nv = (size_t)c->nt;
+    if (n_corners > (size_t)0x7FF00000) return fail(OA_E_CAPACITY, "pseudo-normals: %zu corners (the sort takes fewer than 2^31 - 2^20)", n_corners);
+    dev_free(c->d_pn_face); dev_free(c->d_pn_vertex); dev_free(c->d_pn_edge);
+    HIPCHK(dev_malloc(&c->d_pn_face, sizeof(double) * 3 * n_tris));
+    HIPCHK(dev_malloc(&c->d_pn_vertex, sizeof(float) * 3 * nv));
+    HIPCHK(dev_malloc(&c->d_pn_edge, sizeof(float) * 9 * n_tris));
+    DevTmp<double> d_angle;
+    DevTmp<int> d_order;
+    DevTmp<long long> d_row;
+    HIPCHK(d_angle.alloc(n_corners)); HIPCHK(d_order.alloc(n_corners)); HIPCHK(d_row.alloc(nv + 1));
+    const unsigned t_blocks = (unsigned)((n_tris + 255) / 256), c_blocks = (unsigned)((n_corners + 255) / 256);
+    hipLaunchKernelGGL(oa::k_pn_face, dim3(t_blocks), dim3(256), 0, c->stream, (const float *)c->d_tgt_xyz, (const int *)c->d_tris, (int)n_tris, c->d_pn_face,
+                       d_angle.p);
+    HIPCHK(hipGetLastError());
+    // (the indices were checked at upload: all in 0 .. nt - 1, so they are their own keys; oa_sort.hpp adds 10-bit passes as the bits ask)
+    int rc = sort_order_bits(c, (const unsigned *)c->d_tris, d_order.p, n_corners, bits_for((long long)nv));
+    if (rc) return rc;
+    hipLaunchKernelGGL(oa::k_pn_row_start, dim3((unsigned)((nv + 1 + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->d_tris, (const int *)d_order.p,
+                       (long long)n_corners, (int)nv, d_row.p);
+    hipLaunchKernelGGL(oa::k_pn_vertex, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream, (const int *)d_order.p, (const long long *)d_row.p, (int)nv,
+                       (const double *)c->d_pn_face, (const double *)d_angle.p, c->d_pn_vertex);
+    hipLaunchKernelGGL(oa::k_pn_edge, dim3(c_blocks), dim3(256), 0, c->stream, (const int *)c->d_tris, (int)n_tris, (const int *)d_order.p,
+                       (const long long *)d_row.p, (const double *)c->d_pn_face, c->d_pn_edge);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));                        // (the temporaries go back to the cache behind this)
+    c->pn_ok = true;
+    c->last_pn_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return OA_OK;
+}
+}  // namespace
+
+OA_EXPORT int oa_get_mesh_pseudonormals(oa_ctx *c, float *vertex_n, float *edge_n)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    OA_ROUTE_FIRST(c, oa_get_mesh_pseudonormals(sub, vertex_n, edge_n));   // (the target is replicated: the same bits everywhere)
+    if (!c->surface || c->nt <= 0) return fail(OA_E_STATE, "oa_get_mesh_pseudonormals: no mesh target (oa_set_target_mesh)");
+    int rc = use_device(c);
+    if (rc) return rc;
+    if ((rc = ensure_pseudonormals(c))) return rc;
+    if (vertex_n) HIPCHK(hipMemcpyAsync(vertex_n, c->d_pn_vertex, sizeof(float) * 3 * (size_t)c->nt, hipMemcpyDeviceToHost, c->stream));
+    if (edge_n) HIPCHK(hipMemcpyAsync(edge_n, c->d_pn_edge, sizeof(float) * 9 * (size_t)c->n_tris, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
+OA_EXPORT int oa_deviation(oa_ctx *c, const oa_deviation_settings *ds, double *signed_d, double *dist, float *closest, int64_t *idx, int8_t *feature,
+                           int64_t *hist, oa_deviation_report *rep)
+{
+    if (!c || !ds) return fail(OA_E_BAD_ARG, "oa_deviation: null argument");
+    OA_NOT_MULTI(c, "oa_deviation");
+    if (!(ds->thresh > 0.0)) return fail(OA_E_BAD_THRESH, "oa_deviation: thresh = %g (> 0; +inf counts every pair)", ds->thresh);
+    if (ds->signed_mode < -1 || ds->signed_mode > 1) return fail(OA_E_BAD_ARG, "oa_deviation: signed_mode %d (-1 when possible, 0 never, 1 required)", ds->signed_mode);
+    if (ds->n_quantiles < 0 || ds->n_quantiles > oa::DEV_MAX_Q) return fail(OA_E_BAD_ARG, "oa_deviation: %d quantiles (0 .. %d)", ds->n_quantiles, oa::DEV_MAX_Q);
+    for (int k = 0; k < ds->n_quantiles; ++k)
+        if (!(ds->quantiles[k] > 0.0 && ds->quantiles[k] <= 1.0)) return fail(OA_E_BAD_ARG, "oa_deviation: quantile %g outside (0, 1]", ds->quantiles[k]);
+    if (ds->n_bins < 0 || ds->n_bins > oa::DEV_MAX_BINS) return fail(OA_E_BAD_ARG, "oa_deviation: %d bins (0 .. %d)", ds->n_bins, oa::DEV_MAX_BINS);
+    if (ds->n_bins > 0 && !(ds->hist_lo < ds->hist_hi && fabs(ds->hist_lo) < (double)INFINITY && fabs(ds->hist_hi) < (double)INFINITY))
+        return fail(OA_E_BAD_ARG, "oa_deviation: histogram range [%g, %g) (finite, lo < hi)", ds->hist_lo, ds->hist_hi);
+    int rc = check_ready(c);
+    if (rc) return rc;
+    int sign_mode = oa::DEV_SIGN_NONE;
+    if (ds->signed_mode != 0) {
+        if (c->surface) sign_mode = oa::DEV_SIGN_MESH;
+        else if (c->d_tgt_n) sign_mode = oa::DEV_SIGN_VERTEX;
+        else if (ds->signed_mode == 1)
+            return fail(OA_E_STATE, "oa_deviation: signed distances to a point-cloud target need its normals (oa_set_target_normals, oa_set_normals or an estimate)");
+    }
+    if ((rc = use_device(c))) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    if ((rc = ensure_common(c))) return rc;
+    if ((rc = ensure_events(c, 1))) return rc;
+    oa_deviation_report r;
+    memset(&r, 0, sizeof r);
+    r.n = c->ns;
+    r.max_index = -1;
+    r.surface = c->surface ? 1 : 0;
+    r.signed_used = sign_mode;
+    r.n_quantiles = ds->n_quantiles;
+    const double nan = std::nan("");
+    r.fitness = r.mean = r.rms = r.std = r.mean_signed = r.max_dist = nan;
+    for (int k = 0; k < oa::DEV_MAX_Q; ++k) r.quantile_values[k] = nan;
+    const bool with_hist = hist && ds->n_bins > 0;
+    if (with_hist) for (int b = 0; b < ds->n_bins + 2; ++b) hist[b] = 0;
+    if (sign_mode == oa::DEV_SIGN_MESH) {
+        const bool built = c->pn_ok;
+        if ((rc = ensure_pseudonormals(c))) return rc;
+        if (!built) r.pseudonormal_ms = c->last_pn_ms;
+    }
+    // the device state as oa_nn_search stages it (no search radius: every slot gets its nearest primitive); a running sequence ends
+    if ((rc = push_state_for_oneshot(c, 1.0, false))) return rc;
+    if (c->ns <= 0) { r.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); if (rep) *rep = r; return OA_OK; }
+    const size_t ns = (size_t)c->ns;
+    const int n_rows = (c->ns_pad + oa::DEV_THREADS - 1) / oa::DEV_THREADS, nq = ds->n_quantiles;
+    DevTmp<long long> d_idx;
+    DevTmp<float> d_closest;
+    DevTmp<double> d_dist, d_signed;
+    DevTmp<signed char> d_feature;
+    DevTmp<uint32_t> d_dkeys, d_qhist;
+    DevTmp<unsigned long long> d_hist;
+    DevTmp<oa::DevRow> d_rows;
+    DevTmp<oa::DevSelect> d_sel;
+    if (idx) HIPCHK(d_idx.alloc(ns));
+    if (closest) HIPCHK(d_closest.alloc(3 * ns));
+    if (dist) HIPCHK(d_dist.alloc(ns));
+    if (signed_d) HIPCHK(d_signed.alloc(ns));
+    if (feature) HIPCHK(d_feature.alloc(ns));
+    HIPCHK(d_dkeys.alloc(ns)); HIPCHK(d_rows.alloc((size_t)n_rows + 1));
+    oa::DevHist hg{};
+    if (with_hist) {
+        hg.lo = ds->hist_lo; hg.hi = ds->hist_hi; hg.n_bins = ds->n_bins;
+        hg.scale = (double)ds->n_bins / (ds->hist_hi - ds->hist_lo);
+        HIPCHK(d_hist.alloc((size_t)ds->n_bins + 2));
+        HIPCHK(hipMemsetAsync(d_hist.p, 0, sizeof(unsigned long long) * ((size_t)ds->n_bins + 2), c->stream));
+    }
+    oa::DevSelect h_sel[oa::DEV_MAX_Q];
+    if (nq > 0) {
+        memset(h_sel, 0, sizeof h_sel);
+        for (int k = 0; k < nq; ++k) { h_sel[k].p = ds->quantiles[k]; h_sel[k].q = nan; }
+        HIPCHK(d_sel.alloc((size_t)nq)); HIPCHK(d_qhist.alloc((size_t)nq * oa::SEL_LEVELS * oa::SEL_BINS));
+        HIPCHK(hipMemcpyAsync(d_sel.p, h_sel, sizeof(oa::DevSelect) * (size_t)nq, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(d_qhist.p, 0, sizeof(uint32_t) * (size_t)nq * oa::SEL_LEVELS * oa::SEL_BINS, c->stream));
+    }
+    HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    if ((rc = launch_nn(c, choose_search(c), false))) return rc;
+    HIPCHK(hipEventRecord(c->ev[1], c->stream));
+    const oa::DevOut out{ d_idx.p, d_closest.p, d_dist.p, d_signed.p, d_feature.p };
+    hipLaunchKernelGGL(oa::k_deviation, dim3((unsigned)n_rows), dim3(oa::DEV_THREADS), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4,
+                       c->ns, c->ns_pad, (const float *)c->d_tgt_xyz, c->d_keys, c->surface ? (const float4 *)nullptr : (const float4 *)c->d_win,
+                       c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, ds->thresh, sign_mode, (const int *)c->d_tris,
+                       (const double *)c->d_pn_face, (const float *)c->d_pn_vertex, (const float *)c->d_pn_edge, (const float *)c->d_tgt_n,
+                       (const int *)c->d_perm, out, d_dkeys.p, hg, with_hist ? d_hist.p : (unsigned long long *)nullptr, d_rows.p);
+    hipLaunchKernelGGL(oa::k_dev_finish, dim3(1), dim3(oa::DEV_FIN_THREADS), 0, c->stream, (const oa::DevRow *)d_rows.p, n_rows, d_rows.p + n_rows);
+    HIPCHK(hipGetLastError());
+    if (nq > 0) {
+        const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
+        for (int level = 0; level < oa::SEL_LEVELS; ++level) {
+            hipLaunchKernelGGL(oa::k_dev_select_hist, dim3(hist_blocks, (unsigned)nq), dim3(oa::SEL_THREADS), 0, c->stream, (const oa::DevSelect *)d_sel.p,
+                               (const uint32_t *)d_dkeys.p, c->ns, level, d_qhist.p);
+            hipLaunchKernelGGL(oa::k_dev_select_scan, dim3((unsigned)nq), dim3(oa::SEL_THREADS), 0, c->stream, d_sel.p, (const uint32_t *)d_qhist.p, level);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h_sel, d_sel.p, sizeof(oa::DevSelect) * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
+    }
+    std::vector<unsigned long long> h_hist;
+    if (with_hist) {
+        h_hist.resize((size_t)ds->n_bins + 2);
+        HIPCHK(hipMemcpyAsync(h_hist.data(), d_hist.p, sizeof(unsigned long long) * h_hist.size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (idx) HIPCHK(hipMemcpyAsync(idx, d_idx.p, sizeof(long long) * ns, hipMemcpyDeviceToHost, c->stream));
+    if (closest) HIPCHK(hipMemcpyAsync(closest, d_closest.p, sizeof(float) * 3 * ns, hipMemcpyDeviceToHost, c->stream));
+    if (dist) HIPCHK(hipMemcpyAsync(dist, d_dist.p, sizeof(double) * ns, hipMemcpyDeviceToHost, c->stream));
+    if (signed_d) HIPCHK(hipMemcpyAsync(signed_d, d_signed.p, sizeof(double) * ns, hipMemcpyDeviceToHost, c->stream));
+    if (feature) HIPCHK(hipMemcpyAsync(feature, d_feature.p, ns, hipMemcpyDeviceToHost, c->stream));
+    oa::DevRow tot;
+    if ((rc = read_small(c, &tot, d_rows.p + n_rows, sizeof tot))) return rc;   // (waits for everything above)
+    {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        r.search_ms = ms;
+    }
+    r.n_valid = tot.n_valid; r.n_inlier = tot.n_inlier; r.n_inside = tot.n_inside; r.n_unsigned = tot.n_unsigned;
+    r.fitness = (double)tot.n_inlier / (double)r.n;
+    if (tot.n_inlier > 0) {
+        const double k = (double)tot.n_inlier;
+        r.mean = tot.sum_d / k;
+        r.rms = sqrt(tot.sum_dd / k);
+        r.mean_signed = tot.sum_signed / k;
+        const double var = r.rms * r.rms - r.mean * r.mean;
+        r.std = sqrt(var > 0.0 ? var : 0.0);
+    }
+    if (tot.max_index >= 0) {
+        r.max_index = tot.max_index;
+        memcpy(&r.max_dist, &tot.max_bits, sizeof(double));
+    }
+    for (int k = 0; k < nq; ++k) r.quantile_values[k] = h_sel[k].q;
+    if (with_hist) for (size_t b = 0; b < h_hist.size(); ++b) hist[b] = (int64_t)h_hist[b];
+    r.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rep) *rep = r;
     return OA_OK;
 }

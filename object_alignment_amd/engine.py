@@ -31,6 +31,7 @@ class RunResult:
     step_K: np.ndarray
     step_stats: np.ndarray            # n x 2 [mean, std]
     step_trans: np.ndarray
+    deviation: dict | None = None     # IcpAlign.run(..., deviation=DeviationSettings()): IcpEngine.deviation at the final pose
 
 
 def _device_ptr(x):
@@ -92,6 +93,50 @@ def _voxel_args(xyz, voxel, normals, origin, name="voxel_downsample"):
         if origin.shape != (3,) or not np.all(np.isfinite(origin)):
             raise ValueError("%s: origin must be three finite numbers, got %r" % (name, origin))
     return xyz, normals, origin
+
+
+DEVIATION_OUTPUTS = ("signed_d", "dist", "closest", "idx", "feature")
+DEVIATION_SIGNED = {"auto": -1, "never": 0, "required": 1, None: -1, False: 0, True: 1}
+
+
+def _deviation_args(thresh=float("inf"), signed="auto", quantiles=(0.5, 0.9, 0.95, 0.99), bins=0, hist_range=None,
+                    outputs=("signed_d", "closest", "idx", "feature"), name="deviation"):
+    """The arguments of a deviation report, checked before any call reaches the library: (thresh, signed_mode, quantiles, bins,
+    (lo, hi), outputs)."""
+    def number(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+
+    if not number(thresh) or np.isnan(thresh) or not thresh > 0:
+        raise ValueError("%s: thresh = %r (> 0; inf counts every pair)" % (name, thresh))
+    try:
+        signed_mode = DEVIATION_SIGNED[signed]
+    except (KeyError, TypeError):
+        raise ValueError("%s: signed = %r (use 'auto', True / 'required' or False / 'never')" % (name, signed)) from None
+    quantiles = tuple(quantiles) if quantiles is not None else ()
+    if len(quantiles) > 8:
+        raise ValueError("%s: %d quantiles (at most 8)" % (name, len(quantiles)))
+    for q in quantiles:
+        if not number(q) or not (q > 0 and q <= 1):
+            raise ValueError("%s: quantile %r outside (0, 1]" % (name, q))
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 0 <= int(bins) <= 1024:
+        raise ValueError("%s: bins = %r (0 .. 1024)" % (name, bins))
+    lo, hi = 0.0, 0.0
+    if hist_range is not None:
+        try:
+            lo, hi = hist_range
+        except (TypeError, ValueError):
+            raise ValueError("%s: hist_range = %r (lo, hi)" % (name, hist_range)) from None
+        if not number(lo) or not number(hi) or not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+            raise ValueError("%s: hist_range = %r (finite, lo < hi)" % (name, hist_range))
+    elif int(bins) > 0:
+        raise ValueError("%s: %d bins need a hist_range" % (name, int(bins)))
+    if isinstance(outputs, str):
+        outputs = (outputs,)
+    outputs = tuple(outputs) if outputs is not None else ()
+    for o in outputs:
+        if o not in DEVIATION_OUTPUTS:
+            raise ValueError("%s: unknown output %r (of %s)" % (name, o, ", ".join(DEVIATION_OUTPUTS)))
+    return float(thresh), signed_mode, tuple(float(q) for q in quantiles), int(bins), (float(lo), float(hi)), outputs
 
 
 def resolve_devices(spec):
@@ -325,7 +370,7 @@ class IcpEngine:
              "tri_ring": 21, "tri_ring_accepts": 22, "exchange_us": 23, "rccl_fallbacks": 24, "rccl_ranks_last": 25, "search_clock_mhz": 26, "brute_queue_wgs": 27,
              "metric": 28, "plane_rank": 29, "robust_loss": 30, "weight_sum": 31,
              "robust_scale": 32, "robust_quantile": 33, "target_normals": 34,
-             "target_features": 35}
+             "target_features": 35, "mesh_pseudonormals": 36}
     EXCHANGE_NAMES = {-1: None, 0: "mailbox (pinned host memory)", 1: "rccl", 2: "mailbox (peer-mapped device memory)"}
 
     def exchange_info(self):
@@ -624,6 +669,54 @@ class IcpEngine:
                   "dims": tuple(rep.dims), "origin": tuple(rep.origin), "total_ms": rep.total_ms}
         return {"xyz": out[:rows].copy(), "normals": out_n[:rows].copy() if out_n is not None else None, "count": cnt[:rows].copy(),
                 "rep": idx[:rows].copy(), "report": report}
+
+    def deviation(self, thresh=float("inf"), signed="auto", quantiles=(0.5, 0.9, 0.95, 0.99), bins=0, hist_range=None,
+                  outputs=("signed_d", "closest", "idx", "feature")):
+        """How good is the alignment at the current matrices, and where does it deviate: one correspondence search, then per
+        selected source point (caller order) the arrays named in `outputs` -- signed_d float64 (negative inside a mesh target,
+        or behind a point-cloud target's normals), dist float64 (the world-space pair distance the loop sees), closest float32
+        (n, 3) base-local, idx int64 (-1: no correspondence), feature int8 (0 face, 1-3 edge ab / bc / ca, 4-6 vertex a / b / c;
+        -1 in vertex mode) -- plus "report" (fitness = inliers with dist < thresh over all points, mean / rms / std / mean_signed
+        over the inliers, max_dist and max_index over all valid points, "quantiles": {q: exact order statistic}, counts, which
+        sign rule was used) and "hist" (bins + 2 int64 counts over hist_range of signed_d, under- and overflow first and last;
+        None without bins).  signed: "auto" (when possible), True (required) or False.  Single-device contexts."""
+        thresh, signed_mode, quantiles, bins, (lo, hi), outputs = _deviation_args(thresh, signed, quantiles, bins, hist_range, outputs)
+        n = self.n_selected
+        m = max(1, n)
+        st = capi.DeviationSettings()
+        st.thresh, st.signed_mode, st.n_quantiles, st.n_bins, st.hist_lo, st.hist_hi = thresh, signed_mode, len(quantiles), bins, lo, hi
+        for k, q in enumerate(quantiles):
+            st.quantiles[k] = q
+        arr = {"signed_d": np.empty(m, np.float64) if "signed_d" in outputs else None,
+               "dist": np.empty(m, np.float64) if "dist" in outputs else None,
+               "closest": np.empty((m, 3), np.float32) if "closest" in outputs else None,
+               "idx": np.empty(m, np.int64) if "idx" in outputs else None,
+               "feature": np.empty(m, np.int8) if "feature" in outputs else None}
+        hist = np.zeros(bins + 2, np.int64) if bins > 0 else None
+        rep = capi.DeviationReport()
+        self._chk(self._L.oa_deviation(
+            self._h, C.byref(st),
+            capi.dptr(arr["signed_d"]) if arr["signed_d"] is not None else None, capi.dptr(arr["dist"]) if arr["dist"] is not None else None,
+            capi.fptr(arr["closest"]) if arr["closest"] is not None else None, capi.iptr(arr["idx"]) if arr["idx"] is not None else None,
+            arr["feature"].ctypes.data_as(C.POINTER(C.c_int8)) if arr["feature"] is not None else None,
+            capi.iptr(hist) if hist is not None else None, C.byref(rep)))
+        report = {name: getattr(rep, name) for name, _ in capi.DeviationReport._fields_ if name not in ("reserved", "quantile_values", "n_quantiles")}
+        report["quantiles"] = {q: float(rep.quantile_values[k]) for k, q in enumerate(quantiles)}
+        report["thresh"] = thresh
+        out = {name: a[:n] for name, a in arr.items() if a is not None}
+        out["report"] = report
+        out["hist"] = hist
+        return out
+
+    def mesh_pseudonormals(self):
+        """Surface-mode targets: the angle-weighted pseudo-normals the signed distance uses, built on the device if they are not
+        there yet: (vertex_n float32 (n_verts, 3), edge_n float32 (n_tris, 3, 3) -- one per triangle and local edge ab / bc / ca,
+        the same bits on both sides of a shared edge).  Not normalised."""
+        nt = int(self.stat("n_tris"))
+        vn = np.empty((max(1, self.n_target), 3), np.float32)
+        en = np.empty((max(1, nt), 3, 3), np.float32)
+        self._chk(self._L.oa_get_mesh_pseudonormals(self._h, capi.fptr(vn), capi.fptr(en)))
+        return vn[: self.n_target], en[:nt]
 
     # ---- split phase (one process per GPU)
     def run_begin(self, iters=50, thresh=0.5, target_d=0.01, use_target=True, with_scale=False, early_exit=True):

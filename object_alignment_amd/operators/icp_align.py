@@ -63,6 +63,26 @@ class IcpSettings:
     sample_voxel: float = 0.0
 
 
+@dataclass
+class DeviationSettings:
+    """What IcpAlign.run(..., deviation=DeviationSettings()) measures at the final pose (IcpEngine.deviation's arguments; checked
+    here, before any engine opens).  thresh None = the loop's min_start."""
+    thresh: float | None = None
+    signed: object = "auto"           # "auto" (when possible), True (required) or False
+    quantiles: tuple = (0.5, 0.9, 0.95, 0.99)
+    bins: int = 0
+    hist_range: tuple | None = None
+    outputs: tuple = ("signed_d", "closest", "idx", "feature")
+
+    def __post_init__(self):
+        from ..engine import _deviation_args
+        _deviation_args(**self.kwargs(1.0), name="DeviationSettings")
+
+    def kwargs(self, default_thresh):
+        return dict(thresh=default_thresh if self.thresh is None else self.thresh, signed=self.signed, quantiles=self.quantiles,
+                    bins=self.bins, hist_range=self.hist_range, outputs=self.outputs)
+
+
 MAD_TUNING = {"huber": 1.345 * 1.4826, "tukey": 4.685 * 1.4826, "cauchy": 2.385 * 1.4826}
 """The usual constant-times-median choices of robust_scale for robust_quantile = 0.5: each loss's 95 %-efficiency tuning constant
 times 1.4826, which carries the median of |residual| to the standard deviation of Gaussian noise (the MAD scale).
@@ -249,7 +269,7 @@ class IcpAlign:
         self._engine = engine
 
     def run(self, source_xyz, target_xyz, mx_align, mx_base, vlist=None, early_exit=True,
-            target_tris=None, target_normals=None, source_weights=None, coarse=None, source_normals=None) -> RunResult:
+            target_tris=None, target_normals=None, source_weights=None, coarse=None, source_normals=None, deviation=None) -> RunResult:
         """target_tris: (n, 3) triangles of the base mesh -> closest point on the surface (the reference's BVH
         semantics); None -> nearest target vertex (point-cloud targets, BASELINE's configurations).
         target_normals: one normal per target vertex -- what settings.metric == "plane" needs of a point-cloud target -- or
@@ -262,7 +282,9 @@ class IcpAlign:
         coarse: a CoarseSettings (operators/coarse_align.py) -- the coarse global stage runs on the same engine in front of the
         loop, which then starts from the pose it found (self.last_coarse holds its report); None: the loop alone.
         settings.sample_voxel > 0: the vertices vlist selects are first thinned to one representative per voxel of that edge
-        (voxel_vlist); sample_fraction then applies to that list."""
+        (voxel_vlist); sample_fraction then applies to that list.
+        deviation: a DeviationSettings -- after the loop the deviation report and its arrays are taken at the final pose on the same
+        engine (over the points the loop used) and attached as RunResult.deviation; None: nothing else changes."""
         s = self.settings
         estimate = isinstance(target_normals, str)
         if estimate and target_normals != "estimate":
@@ -271,6 +293,8 @@ class IcpAlign:
             raise ValueError("target_normals='estimate' is for point-cloud targets: a mesh (target_tris) uses its triangles' normals")
         if isinstance(source_normals, str) and source_normals != "estimate":
             raise ValueError("source_normals %r (an array of normals, or 'estimate')" % (source_normals,))
+        if deviation is not None and not isinstance(deviation, DeviationSettings):
+            raise TypeError("deviation %r (a DeviationSettings, or None)" % (deviation,))
         sample_voxel = sample_voxel_of(s)
         thresh = s.min_start                                   # :83
         factor = round(1 / s.sample_fraction)                  # :89  (ZeroDivisionError at 0, as the reference)
@@ -303,8 +327,11 @@ class IcpAlign:
         if coarse is not None:
             from .coarse_align import coarse_stage
             self.last_coarse = coarse_stage(eng, coarse, target_xyz, mx_base, source_xyz=source_xyz)
-        return eng.run(iters=s.icp_iterations, thresh=thresh, target_d=s.target_d, use_target=s.use_target,
-                       with_scale=(s.align_meth == "1"), early_exit=early_exit)
+        res = eng.run(iters=s.icp_iterations, thresh=thresh, target_d=s.target_d, use_target=s.use_target,
+                      with_scale=(s.align_meth == "1"), early_exit=early_exit)
+        if deviation is not None:
+            res.deviation = eng.deviation(**deviation.kwargs(thresh))
+        return res
 
 
 def report_lines(res: RunResult, settings, seconds=None):
