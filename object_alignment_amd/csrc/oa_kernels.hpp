@@ -411,6 +411,23 @@ __host__ __device__ inline void rotation_from_covariance_horn(const double H[9],
     R[6] = x * z - y * w;       R[7] = y * z + x * w;       R[8] = 1.0 - x * x - y * y;
 }
 
+// x -= a b / k for x = hi + lo held in two doubles.  The product, the quotient and the difference each keep their own rounding
+// error (the fused multiply-adds return the exact remainders), so what is lost is a rounding of the RESULT, not of the operands.
+__host__ __device__ inline void dd_sub_prod_quot(double &hi, double &lo, double a, double b, double k)
+{
+    const double p = a * b, pe = __builtin_fma(a, b, -p);
+    const double q = p / k, qe = (__builtin_fma(-q, k, p) + pe) / k;
+    const double s = hi - q, bb = s - hi;
+    lo += ((hi - (s - bb)) - (q + bb)) - qe;
+    hi = s;
+}
+// The centred moments below are differences of sums about the pivot: S_H - K c_b c_a^T, S_AA - K |c_a|^2.  With the pivot inside
+// the cloud (every loop: the first source vertex) the two terms differ by a small factor and nothing is lost.  A pivot far from
+// the cloud (oa_kabsch_from_sums about the origin, a cloud 3e4 away: the terms are 1e9 times the difference) loses that factor
+// of the 53 bits -- 1e-7 in R where 1e-16 was due.  Where a difference is more than CANCEL_GATE times smaller than its first term
+// it is redone in two doubles; below the gate (at most 6 bits lost) the plain result stands, bit for bit what it always was.
+constexpr double CANCEL_GATE = 64.0;
+
 // weighted: the sums [0..16] carry the pairs' weights and S_W their mass -- centroids, covariance and the scale branch are the
 // weighted ones; the rule K >= 3 still counts pairs, and a mass that is not > 0 fails like it.
 __host__ __device__ inline bool solve_from_sums(const double *s, const double pivot[3], bool with_scale, double M[16],
@@ -422,16 +439,36 @@ __host__ __device__ inline bool solve_from_sums(const double *s, const double pi
     double ca[3], cb[3];
     const double inv_K = 1.0 / K;
     for (int i = 0; i < 3; ++i) { ca[i] = s[S_A + i] * inv_K; cb[i] = s[S_B + i] * inv_K; }     // centroids (:160,:164)
-    double H[9];
+    double H[9], h_max = 0.0, s_max = 0.0;
     for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) H[3 * i + j] = s[S_H + 3 * i + j] - K * cb[i] * ca[j];  // dot(v1c, v0c.T) (:181)
+        for (int j = 0; j < 3; ++j) {
+            H[3 * i + j] = s[S_H + 3 * i + j] - K * cb[i] * ca[j];                            // dot(v1c, v0c.T) (:181)
+            h_max = fmax(h_max, fabs(H[3 * i + j])); s_max = fmax(s_max, fabs(s[S_H + 3 * i + j]));
+        }
+    if (s_max > CANCEL_GATE * h_max)                                                        // (false for NaN: the plain result stands)
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) {
+                double hi = s[S_H + 3 * i + j], lo = 0.0;
+                dd_sub_prod_quot(hi, lo, s[S_B + i], s[S_A + j], K);
+                H[3 * i + j] = hi + lo;
+            }
     double R[9];
     if (horn) rotation_from_covariance_horn(H, R);                  // usesvd=False (:191-206)
     else rotation_from_covariance(H, R, v_io, v_valid);
     double sc = 1.0;
     if (with_scale) {                                                                    // :208-212
-        const double n0 = s[S_AA] - K * (ca[0] * ca[0] + ca[1] * ca[1] + ca[2] * ca[2]);
-        const double n1 = s[S_BB] - K * (cb[0] * cb[0] + cb[1] * cb[1] + cb[2] * cb[2]);
+        double n0 = s[S_AA] - K * (ca[0] * ca[0] + ca[1] * ca[1] + ca[2] * ca[2]);
+        double n1 = s[S_BB] - K * (cb[0] * cb[0] + cb[1] * cb[1] + cb[2] * cb[2]);
+        if (s[S_AA] > CANCEL_GATE * fabs(n0)) {
+            double hi = s[S_AA], lo = 0.0;
+            for (int i = 0; i < 3; ++i) dd_sub_prod_quot(hi, lo, s[S_A + i], s[S_A + i], K);
+            n0 = hi + lo;
+        }
+        if (s[S_BB] > CANCEL_GATE * fabs(n1)) {
+            double hi = s[S_BB], lo = 0.0;
+            for (int i = 0; i < 3; ++i) dd_sub_prod_quot(hi, lo, s[S_B + i], s[S_B + i], K);
+            n1 = hi + lo;
+        }
         sc = sqrt(n1 / n0);
     }
     // back to un-pivoted coordinates: c0 = ca + pivot, c1 = cb + pivot;  t = c1 - sR c0   (:215)
