@@ -1,6 +1,7 @@
 // oa_families.hpp -- which translation unit compiles which kernel.
 //
-// liboa_icp.so is built from one host translation unit (oa_icp.hip: context, uploads, launch geometry, the C-ABI, and
+// liboa_icp.so is built from one host translation unit (oa_icp.hip: context, uploads, launch geometry, the C-ABI -- its
+// knobs read once through oa_tunables.hpp -- and
 // every PLAIN kernel -- those are guarded by !OA_FAMILY_TU in the headers) and one translation unit per family of
 // heavy kernel TEMPLATES (oa_fam_*.hip), compiled in parallel by __graft_entry__.build_hip / the Makefile.  A family
 // unit explicitly instantiates its list below; the host unit declares the same list `extern`, so it launches the

@@ -20,6 +20,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "oa_sort.hpp"
 #include "oa_voxel.hpp"
 #include "oa_deviation.hpp"
+#include "oa_tunables.hpp"            // every OA_* knob: read once, oa_ctx::tune (plain C++)
 #include "../../include/oa_icp.h"
 
 #include <algorithm>
@@ -103,9 +104,10 @@ struct DevCache {
     int contexts = 0;                                           // live oa_ctx objects (single-device ones)
     static constexpr unsigned long long CACHE_MAX_AGE = 512;
 
-    const bool enabled = !(getenv("OA_DEV_CACHE") && atoi(getenv("OA_DEV_CACHE")) == 0);   // OA_DEV_CACHE=0: plain hipMalloc / hipFree
-    const bool cap_given = getenv("OA_DEV_CACHE_MB") && *getenv("OA_DEV_CACHE_MB");
-    const size_t max_bytes = (size_t)(cap_given ? std::max(0.0, atof(getenv("OA_DEV_CACHE_MB"))) : 256.0) << 20;
+    const oa_tune::CacheTunables tune = oa_tune::read_cache_tunables();   // (at the process's first allocation: dev_cache())
+    const bool enabled = tune.enabled;                          // OA_DEV_CACHE=0: plain hipMalloc / hipFree
+    const bool cap_given = tune.cap_given;
+    const size_t max_bytes = (size_t)tune.cap_mb << 20;
     // The cap follows what the process has had allocated AT ONCE (round 6): a 1.96M-triangle mesh is ~0.5 GB of images, lists and
     // trees, and with a fixed 256 MiB every re-upload of it really freed and really allocated most of that -- 2.9 of the 4.8 ms of
     // oa_set_target_mesh.  Idle, the cache never holds more than the library already needed live; an explicit OA_DEV_CACHE_MB wins.
@@ -225,18 +227,6 @@ template <typename T> struct DevTmp {
     operator T *() const { return p; }
 };
 
-int env_int(const char *name, int dflt)
-{
-    const char *v = getenv(name);
-    return (v && *v) ? atoi(v) : dflt;
-}
-
-double env_double(const char *name, double dflt)
-{
-    const char *v = getenv(name);
-    return (v && *v) ? atof(v) : dflt;
-}
-
 // Host threads of a multi-device context.  One PERSISTENT worker per listed GPU (children that share a GPU share a
 // worker and stay sequential): uploads and index builds (20+ ms of copies, sorts and builds per device at 1M) run on all
 // GPUs at the same time, and oa_run hands every worker the whole loop of its device -- each GPU is fed by its own
@@ -331,6 +321,7 @@ template <typename F> int route_all_parallel(oa_ctx *c, F f);
 }  // namespace
 
 struct oa_ctx {
+    const oa_tune::Tunables tune = oa_tune::read_tunables();   // configuration: fixed for the context's life.  Everything below is state
     int device = 0;
     int n_cu = 256;
     hipStream_t own_stream = nullptr, stream = nullptr;
@@ -344,12 +335,11 @@ struct oa_ctx {
     float4 *d_tfs = nullptr, *d_tf3s = nullptr, *d_tgs = nullptr;   // 3 / 2 / 3 float4 per group of 4 sorted positions
     int4 *d_tidx = nullptr;          // original index of every sorted position
     int sax[3] = { 0, 1, 2 };        // its axes: longest (sorted along), second, thinnest
-    bool nn_sort = true;             // OA_NN_SORT=0 (A/B): the brute-force search stays k_nn_search_filtered (rounds 1-4)
     int fax[3] = { 0, 1, 2 };
     double bb_lo[3] = { 0, 0, 0 }, bb_hi[3] = { 0, 0, 0 };
     // uniform grid (k_nn_search_grid)
     bool grid_ok = false;
-    int grid_mode = -1;              // OA_NN_GRID: -1 auto, 0 never, 1 whenever possible
+    int grid_mode = -1;              // -1 auto, 0 never, 1 whenever possible: tune.nn_grid at oa_create, then oa_set_search_mode
     oa::GridParams gp;
     int n_cells = 0;
     int *d_cell_start = nullptr;
@@ -373,8 +363,6 @@ struct oa_ctx {
     long long n_tri_entries = 0;     // entries of the triangle grid's cell lists
     double tri_mean_diag = 0.0;      // mean bounding-box diagonal of the triangles (the cell sizes are multiples of it)
     // the settled-pose search (oa_tri_fine.hpp): a sparse fine grid with inflated lists of whole triangles
-    int tri_fine = 0;                // OA_TRI_FINE (EXPERIMENT, off): 0 = never, 1 = built with the mesh when it has >= tri_fine_min_tris triangles, 2 = always
-    int tri_fine_min_tris = 200000;  // OA_TRI_FINE_MIN_TRIS (smaller meshes: short calls would pay ~80 us of build for a search they never reach)
     bool tri_fine_ok = false;
     oa::FineParams tfp;
     uint4 *d_tfine_table = nullptr;
@@ -383,11 +371,6 @@ struct oa_ctx {
     // seed + neighbours settle a query (oa_tri_ring.hpp): per triangle its neighbours' indices; the accept radius lives in d_tri9
     int *d_tri_ring = nullptr;
     bool tri_ring_ok = false;        // built for the current mesh
-    int tri_ring = 0;                // OA_TRI_RING (EXPERIMENT, off: exact, measured, not faster -- docs/HISTORY.md 4.5): 0 = never; 1 = built once a mesh has seen TRI_RING_LAZY_ITERS searches of a loop; 2 = built with the grid
-    double tri_ring_cap = 0.25;      // OA_TRI_RING_CAP: clearances are looked for up to this fraction of a cell edge
-    bool tri_wave_wgs = true;        // OA_TRI_WAVE_WGS=0 (A/B): the plain surface search in workgroups of 256 queries also for long launches, as until round 6
-    bool tri_split_lanes = true;     // OA_TRI_SPLIT_LANES=0 (A/B): the list is always searched with the shard's own lanes per query
-    bool tri_split = true;           // OA_TRI_SPLIT=0 (A/B): the seed + neighbours test stays in the grid search's prologue (no k_tri_accept launch)
     long long tri_iters = 0;         // loop searches enqueued since the mesh was set
     // bounding-box trees (oa_bvh.hpp): over the vertices, and over the triangles in surface mode
     bool bvh_ok = false, tbvh_ok = false;
@@ -400,32 +383,18 @@ struct oa_ctx {
     long long shard_begin = 0;
     int *d_pos = nullptr;            // oa_make_pairs on a shard: whole-selection position of every pair
     std::vector<int> h_members;      // host copy of d_members (children of a multi-device context)
-    int mfma_wps = 4;                // OA_MFMA_WPS: waves per SIMD k_nn_search_mfma is built for (4: 128 registers, 3: 168, 2: 256)
-    int nn_mfma = 0;                 // OA_NN_MFMA=1 (experiment): first filter level of the brute-force search on the matrix cores (oa_mfma.hpp)
     oa::half8 *d_tfm = nullptr;      // its image of the target
     double mfma_sigma = 1.0;
     // source (this shard)
-    int ns = 0, ns_pad = 0, R = 4;
+    int ns = 0, ns_pad = 0, R = 4;   // R: tune.nn_r, or chosen from the shard size
     float4 *d_src4 = nullptr;
     unsigned long long *d_keys = nullptr;
-    int grid_lanes = 0;              // OA_GRID_LANES: lanes per query of k_nn_search_grid (0 = by shard size)
-    double turn_frac = 0.1;          // OA_TURN_FRAC: the tree keeps its turn while the pose moves by more than this part of a cell
-    bool debug = false;              // OA_DEBUG (read at oa_create)
-    bool grid_stats = false;         // OA_GRID_STATS: instrumented triangle-grid launches print what the queries did
-    bool tri_share = true;           // OA_TRI_SHARE=0 (A/B): every lane of the triangle-grid search walks its own records (rounds 2-3)
-    int list_blocks_per_cu = 16;     // OA_LIST_BLOCKS_PER_CU: workgroups (of four waves) per CU of the tree search over the hand-over list
-    bool tri_canon = true;           // OA_TRI_CANON=0 (A/B): surface loops accumulate through the grid-stride k_pair_accumulate (rounds 1-3)
-    bool tri_acc = true;             // OA_TRI_ACC=0 (A/B): the triangle grid search never accumulates in its epilogue
-    int turns_on = 1;                // OA_SEARCH_TURNS: tree while the pose moves, grid afterwards (mid-size shards, AUTO)
     bool seeded = false;             // a search has run since the last set_source / set_target (seeds exist)
     int *d_prev = nullptr;           // nearest index of the previous search (seed), -1 = none
     float4 *d_win = nullptr;         // vertex mode: per slot, the last winner's coordinates + index in .w (-1 = none)
     uint2 *d_wsafe = nullptr;        // vertex grid: per slot {index, safe2 bits} of a winner the grid scan found (k_grid_safe_radius); 0xFF.. = none
     float *d_safe_by_idx = nullptr;  // vertex grid: safe2 per target vertex (original index); allocated with the grid, filled by build_safe_radii
     bool safe_ok = false;            // ... and filled
-    int grid_safe = 1;               // OA_GRID_SAFE: 0 = the vertex searches (grid, whole-shard tree) never take a seed on its safe radius (A/B);
-                                     // 1 = the radii are built once a target has seen SAFE_LAZY_ITERS accumulating searches (a 5-iteration
-                                     // call at 1M vertices would pay 50-80 us to save 10); 2 = built with the grid
     long long target_iters = 0;      // accumulating grid searches enqueued since the target was set
     int *d_sel = nullptr;            // vertex index held by each source slot
     float4 *d_src4o = nullptr;       // the same points in the caller's (vlist) order -- only oa_make_pairs needs it
@@ -434,11 +403,7 @@ struct oa_ctx {
     int prec_cap = 0;                // slots d_prec holds
     int homes_cap = 0;               // blocks of source points d_homes holds (two ints each: home split, home tile)
     int *d_homes = nullptr, *d_qcnt = nullptr;   // k_nn_search_sorted's work queue (oa_kernels.hpp): per block of source points its own split; the queues' counters
-    bool nn_vchunk = true;           // OA_NN_VCHUNK: the sorted images' blocks in the order of v and k_nn_search_sorted's level 0v (0: as until round 6)
-    int nn_persist = 4;              // OA_NN_PERSIST: workgroups per CU that work the queue off (0: one workgroup per item, in launch order -- as until round 6)
-    int nn_queue_min = -1;           // OA_NN_QUEUE_MIN_ITEMS: launches of at least this many items go through the queue (-1: four per workgroup)
     int last_queue_wgs = 0;          // OA_STAT_BRUTE_QUEUE_WGS
-    bool nn_wave_order = true;
     long long src_n_verts = 0;
     // normal-angle rejection (extension)
     float *d_src_n = nullptr, *d_tgt_n = nullptr;
@@ -463,11 +428,8 @@ struct oa_ctx {
     // launch geometry for k_nn_search
     int n_splits = 1, acc_blocks = 1;
     int n_splits_seeded = 1;         // k_nn_search_sorted once the winner records hold seeds: more, shorter splits (plan_geometry)
-    bool nn_home_pass = true;        // the first search of a loop: k_nn_seed_sorted + a seeded launch (OA_NN_HOME_PASS=0: ONE unseeded launch)
     bool win_seeds = false;          // an accumulation has written winner records since the last upload / oa_reset_seeds
     int tile_groups = oa::FTILE_GROUPS;   // LDS tile of k_nn_search_filtered: 256 groups, 64 for small targets
-    int R_env = 0;                      // OA_NN_R override (0 = choose from the shard size)
-    bool use_filter = true;
     double d_pivot0 = 0.0;           // initial distance pivot for the next loop / one-shot (see DevState::d_pivot)
     // device state
     oa::DevState h_state;
@@ -485,10 +447,6 @@ struct oa_ctx {
     bool h_hist_valid = false;
     int max_records = 0;
     double *d_partials = nullptr, *d_sums = nullptr, *d_solve = nullptr;
-    int fused_acc = 1;                      // OA_FUSED_ACC: grid / tree searches of the loop accumulate in their epilogue
-    int tree_acc_max = 4096;                // OA_TREE_ACC_MAX: largest shard whose whole-shard tree search also accumulates
-    int acc_threads = 0;                    // OA_ACC_THREADS: 256 / 512 threads per workgroup of the accumulating grid search and k_pair_accumulate_canon (0 = by shard size)
-    int grid_path = 0;                      // OA_GRID_PATH: 0 = adaptive (see grid_fast_now), 1 = always the fused path, 2 = never
     int iter_enq = 0;                       // iterations enqueued since the loop began
     int fast_iters = 0;                     // ... of which the grid search finished its own leftovers and accumulated (OA_STAT_FAST_ITERATIONS)
     bool fast_prev = false;                 // what the last iteration's grid search did
@@ -564,16 +522,16 @@ void plan_geometry(oa_ctx *c)
     if (c->ns <= 0 || c->nt <= 0) return;
     const int src_blocks = c->ns_pad / (oa::NN_THREADS * c->R);
     // small targets: quarter-size tiles give 4x more (and 4x shorter) workgroups; the unfiltered kernel keeps 256
-    c->tile_groups = (c->filter_ok && c->use_filter && c->nt <= 65536 && !env_int("OA_NN_BIGTILE", 0)) ? 64 : oa::FTILE_GROUPS;
+    c->tile_groups = (c->filter_ok && c->tune.nn_filter && c->nt <= 65536 && !c->tune.nn_bigtile) ? 64 : oa::FTILE_GROUPS;
     const int tiles_total = c->n_groups_pad / c->tile_groups;
     // workgroups wanted: ~2e5 pairs each (below that the prologue and the atomicMin merge dominate), at most 64 per CU
     const double pairs = (double)c->ns * (double)c->nt;
     const int want_auto = (int)std::min((double)c->n_cu * 64.0, std::max((double)c->n_cu * 2.0, pairs / 2e5));
-    const int want = env_int("OA_NN_TARGET_BLOCKS", want_auto);
+    const int want = c->tune.nn_target_blocks == oa_tune::UNSET ? want_auto : c->tune.nn_target_blocks;
     int splits = (want + src_blocks - 1) / src_blocks;
     splits = std::max(1, std::min(splits, tiles_total));
     if (splits > 8) splits = std::min(tiles_total, ((splits + 7) / 8) * 8);   // multiple of 8: one XCD per split residue
-    const int forced = env_int("OA_NN_SPLITS", 0);
+    const int forced = c->tune.nn_splits;
     if (forced > 0) splits = std::min(forced, tiles_total);
     c->n_splits = splits;                                          // the kernels cut the tiles into exactly this many ranges (split_range)
     // k_nn_search_sorted with seeds: a workgroup's points reach levels 1-3 only in the split that holds their own slab, so short
@@ -584,11 +542,11 @@ void plan_geometry(oa_ctx *c)
     int seeded = std::min(tiles_total / 3, (c->n_cu * 512 + src_blocks - 1) / src_blocks);
     if (seeded > 8) seeded = std::min(tiles_total, ((seeded + 7) / 8) * 8);
     seeded = std::max(splits, seeded);
-    const int forced_seeded = env_int("OA_NN_SPLITS_SEEDED", 0);
+    const int forced_seeded = c->tune.nn_splits_seeded;
     if (forced > 0) seeded = splits;
     if (forced_seeded > 0) seeded = std::min(forced_seeded, tiles_total);
     c->n_splits_seeded = seeded;
-    const int acc_cap = std::max(1, std::min(oa::ACC_MAX_BLOCKS, env_int("OA_ACC_BLOCKS", 512)));
+    const int acc_cap = std::max(1, std::min(oa::ACC_MAX_BLOCKS, c->tune.acc_blocks));
     c->acc_blocks = std::max(1, std::min(acc_cap, (c->ns + oa::ACC_THREADS - 1) / oa::ACC_THREADS));
 }
 
@@ -618,7 +576,7 @@ constexpr size_t RESULT_BYTES = 1 << 16;
 int result_buffer(oa_ctx *c, size_t bytes, void **dev_view, const void **host_view)
 {
     *dev_view = nullptr; *host_view = nullptr;
-    if (bytes > RESULT_BYTES || !env_int("OA_MAPPED_RESULTS", 1)) return OA_OK;
+    if (bytes > RESULT_BYTES || !c->tune.mapped_results) return OA_OK;
     if (!c->h_result) {
         HIPCHK(hipHostMalloc((void **)&c->h_result, RESULT_BYTES, hipHostMallocMapped));
         void *dp = nullptr;
@@ -727,7 +685,7 @@ constexpr long long SAFE_LAZY_ITERS = 8;   // OA_GRID_SAFE=1: loop iterations a 
 // for the post this thread has not enqueued yet -- children therefore built between loops only).
 int safe_radii_lazy(oa_ctx *c)
 {
-    if (c->grid_safe != 1 || c->safe_ok || !c->d_safe_by_idx) return OA_OK;
+    if (c->tune.grid_safe != 1 || c->safe_ok || !c->d_safe_by_idx) return OA_OK;
     return c->target_iters > SAFE_LAZY_ITERS ? build_safe_radii(c) : OA_OK;
 }
 int build_sorted_images(oa_ctx *c);
@@ -741,7 +699,7 @@ int build_tri_fine(oa_ctx *c);
 constexpr long long TRI_RING_LAZY_ITERS = 4;
 int tri_ring_lazy(oa_ctx *c, bool counting)
 {
-    if (c->tri_ring != 1 || c->tri_ring_ok || !c->d_tri_ring) return OA_OK;
+    if (c->tune.tri_ring != 1 || c->tri_ring_ok || !c->d_tri_ring) return OA_OK;
     if (counting) ++c->tri_iters;
     return c->tri_iters > TRI_RING_LAZY_ITERS ? build_tri_ring(c) : OA_OK;
 }
@@ -755,7 +713,7 @@ inline unsigned bvh_blocks(const oa_ctx *c, bool listed, bool acc = false)
 {
     const int items = listed ? std::min(c->ns, 1 << 17) : c->ns;
     if (acc) return (unsigned)std::max(1, std::min((items + 15) / 16, c->n_cu * 4));   // workgroups of 16 waves
-    return (unsigned)std::max(1, std::min((items + 3) / 4, c->n_cu * (listed ? c->list_blocks_per_cu : 16)));   // 16 waves per SIMD: enough to fill the chip, cheap to dispatch when the list is empty
+    return (unsigned)std::max(1, std::min((items + 3) / 4, c->n_cu * (listed ? c->tune.list_blocks_per_cu : 16)));   // 16 waves per SIMD: enough to fill the chip, cheap to dispatch when the list is empty
 }
 
 oa::NormalTest normal_test(const oa_ctx *c)
@@ -773,7 +731,7 @@ int launch_bvh(oa_ctx *c, const int *list, const int *list_count, int turn = -1,
     // whole-shard vertex searches take seeds on their safe radii (docs/HISTORY.md 4.4 / 4.8): both arrays or neither
     const float *safe_by_idx = nullptr;
     uint2 *wsafe = nullptr;
-    if (!TRI && !list && c->grid_safe) {
+    if (!TRI && !list && c->tune.grid_safe) {
         if (acc) { const int rcs = safe_radii_lazy(c); if (rcs) return rcs; }
         if (c->safe_ok && c->d_safe_by_idx && c->d_wsafe) { safe_by_idx = c->d_safe_by_idx; wsafe = c->d_wsafe; }
     }
@@ -795,7 +753,7 @@ int launch_bvh(oa_ctx *c, const int *list, const int *list_count, int turn = -1,
 // ~700k; 1M queries lose 7 % with 2
 inline int grid_lanes_for(const oa_ctx *c)
 {
-    int lanes = c->grid_lanes;
+    int lanes = c->tune.grid_lanes;
     if (lanes != 1 && lanes != 2 && lanes != 4) {
         const bool big = c->nt >= 500000;
         lanes = (c->ns <= (big ? 400 : 80) * c->n_cu) ? 4 : ((c->ns <= (big ? 2800 : 1400) * c->n_cu) ? 2 : 1);
@@ -808,7 +766,7 @@ inline int grid_lanes_for(const oa_ctx *c)
 // 4 up to ~100k, 2 up to ~800k)
 inline int tri_lanes_for(const oa_ctx *c)
 {
-    int lanes = c->grid_lanes;
+    int lanes = c->tune.grid_lanes;
     if (lanes != 1 && lanes != 2 && lanes != 4) {
         const bool big = c->n_tris >= 250000;
         lanes = (c->ns <= (big ? 400 : 128) * c->n_cu) ? 4 : ((c->ns <= (big ? 3200 : 700) * c->n_cu) ? 2 : 1);
@@ -827,12 +785,12 @@ inline int canon_lanes(const oa_ctx *c) { return c->surface ? tri_lanes_for(c) :
 inline int canon_threads(const oa_ctx *c)
 {
     if (c->surface) return 256;
-    if (c->acc_threads == 256 || c->acc_threads == 512) return c->acc_threads;   // OA_ACC_THREADS (A/B)
+    if (c->tune.acc_threads == 256 || c->tune.acc_threads == 512) return c->tune.acc_threads;   // OA_ACC_THREADS (A/B)
     return (long long)c->ns * grid_lanes_for(c) >= 262144 ? 512 : 256;
 }
 inline int canon_blocks(const oa_ctx *c)
 {
-    if (c->ns <= 0 || (c->surface && !c->tri_canon)) return 0;
+    if (c->ns <= 0 || (c->surface && !c->tune.tri_canon)) return 0;
     const int t = canon_threads(c);
     const long long b = ((long long)c->ns * canon_lanes(c) + t - 1) / t;
     return b <= oa::ACC_MAX_BLOCKS ? (int)b : 0;
@@ -854,12 +812,12 @@ constexpr std::false_type no{};
 enum BruteKernel { BRUTE_PLAIN = 0, BRUTE_FILTERED = 1, BRUTE_MFMA = 2, BRUTE_SORTED = 3 };   // brute force over vertices (the values are OA_STAT_BRUTE_KERNEL's)
 BruteKernel brute_kernel(const oa_ctx *c)
 {
-    if (!c->filter_ok || !c->use_filter) return BRUTE_PLAIN;
+    if (!c->filter_ok || !c->tune.nn_filter) return BRUTE_PLAIN;
 #if defined(OA_EXPERIMENTS)
-    if (c->nn_mfma && c->d_tfm && c->R == 4 && c->tile_groups == oa::FTILE_GROUPS) return BRUTE_MFMA;
-    if (!(c->nn_sort && c->d_tfs)) return BRUTE_FILTERED;
+    if (c->tune.nn_mfma && c->d_tfm && c->R == 4 && c->tile_groups == oa::FTILE_GROUPS) return BRUTE_MFMA;
+    if (!(c->tune.nn_sort && c->d_tfs)) return BRUTE_FILTERED;
 #endif
-    return (c->nn_sort && c->d_tfs) ? BRUTE_SORTED : BRUTE_PLAIN;
+    return (c->tune.nn_sort && c->d_tfs) ? BRUTE_SORTED : BRUTE_PLAIN;
 }
 
 // What the next search launch looks like: which search (loop and one-shot calls alike), and the loop's fusion plan.
@@ -897,27 +855,34 @@ SearchChoice choose_search(const oa_ctx *c)
     SearchChoice s;
     s.brute = brute_kernel(c);
     // (the grid searches hand their leftovers to the tree; mode 2 never gets to the grid arm: the whole-shard tree took it, or tree_ok is false)
-    const bool tree_ok = c->surface ? c->tbvh_ok : c->bvh_ok, grid_ok = c->surface ? c->tri_grid_ok : (c->grid_ok && c->filter_ok && c->use_filter);
+    const bool tree_ok = c->surface ? c->tbvh_ok : c->bvh_ok, grid_ok = c->surface ? c->tri_grid_ok : (c->grid_ok && c->filter_ok && c->tune.nn_filter);
     if (bvh_whole(c, tree_ok, c->surface ? tri_tree_max(c) : vertex_tree_max(c))) s.kind = SEARCH_TREE;
     else if (grid_ok && tree_ok && c->grid_mode != 0) {
         s.kind = SEARCH_GRID;
-        s.dual = c->grid_mode == -1 && c->turns_on && c->ns <= (c->surface ? tri_tree_early(c) : vertex_tree_early(c));
+        s.dual = c->grid_mode == -1 && c->tune.search_turns && c->ns <= (c->surface ? tri_tree_early(c) : vertex_tree_early(c));
         s.lanes = c->surface ? tri_lanes_for(c) : grid_lanes_for(c);
         s.settle_front = c->surface && c->tri_fine_ok && c->seeded && !s.dual;
-        s.accept_front = c->surface && c->tri_split && c->seeded && !s.dual;
+        s.accept_front = c->surface && c->tune.tri_split && c->seeded && !s.dual;
     }
     // (the plane and GICP metrics have no accumulating search epilogue: search, then k_pair_accumulate_plane / _gicp -- as with
     //  fused_acc off; nor does a weighted step: no search epilogue knows about weights)
-    if (!c->fused_acc || !c->loop_active || c->ns <= 0 || plane_row_metric(c) || weighted(c)) return s;
+    if (!c->tune.fused_acc || !c->loop_active || c->ns <= 0 || plane_row_metric(c) || weighted(c)) return s;
     // (the accumulating tree search needs twice the registers of the plain one: worth it while the shard is small enough
     //  that occupancy does not matter -- 12k queries against 1M vertices: 58 us fused, 47 us search + accumulate)
-    if (s.kind == SEARCH_TREE) s.plan = c->ns <= c->tree_acc_max ? PLAN_TREE : PLAN_PLAIN;
+    if (s.kind == SEARCH_TREE) s.plan = c->ns <= c->tune.tree_acc_max ? PLAN_TREE : PLAN_PLAIN;
     else if (s.kind != SEARCH_GRID || canon_blocks(c) == 0) s.plan = PLAN_PLAIN;
     else if (!c->surface) s.plan = s.dual ? PLAN_DUAL : PLAN_GRID;
     // the triangle grid search with the accumulating epilogue: shards above the zone where tree and grid take turns, and no
     // front search (k_tri_accept / k_tri_settle + the search of what they leave, which has no accumulating form)
-    else s.plan = (!s.dual && !(s.accept_front && c->tri_ring_ok) && !s.settle_front && c->tri_acc) ? PLAN_GRID : PLAN_PLAIN;
+    else s.plan = (!s.dual && !(s.accept_front && c->tri_ring_ok) && !s.settle_front && c->tune.tri_acc) ? PLAN_GRID : PLAN_PLAIN;
     return s;
+}
+
+// Does the enqueuing host wait for news from the device (h_poll) before each iteration of a loop?  With early exit on -- a
+// halt it hears of saves the empty launches after it -- and on the adaptive grid path, which decides from recent news
+bool loop_polls(const oa_ctx *c, const oa_settings *st)
+{
+    return c->h_poll && c->tune.run_poll && (st->early_exit || (choose_search(c).plan == PLAN_GRID && c->tune.grid_path == 0));
 }
 
 // PLAN_GRID: may this iteration's grid search finish its own leftovers?  Yes while the most any one wave handed over in
@@ -927,15 +892,15 @@ SearchChoice choose_search(const oa_ctx *c)
 constexpr int FAST_WAVE_MAX = 3;
 bool grid_fast_now(oa_ctx *c)
 {
-    if (c->grid_path == 1) return true;
-    if (c->grid_path == 2) return false;
+    if (c->tune.grid_path == 1) return true;
+    if (c->tune.grid_path == 2) return false;
     bool fast = c->fast_prev;
     const volatile int32_t *poll = c->h_poll;
     const int n_done = poll ? poll[1] : 0;
     if (n_done > 0 && n_done >= c->iter_enq - 4) fast = poll[3] <= FAST_WAVE_MAX;
     else if (c->iter_enq == 0) fast = c->seeded && c->last_todo_wave_max >= 0 && c->last_todo_wave_max <= FAST_WAVE_MAX;
     else if (n_done <= 0 && c->iter_enq > 4) fast = false;          // the host ran far ahead of the device: no news, no risk
-    if (c->debug) fprintf(stderr, "[oa] grid path: iteration %d enqueued, device at %d, last hand-over %d entries / %d per wave (previous loop: %d) -> %s\n", c->iter_enq, n_done, poll ? poll[2] : -1, poll ? poll[3] : -1, c->last_todo_wave_max, fast ? "fast" : "safe");
+    if (c->tune.debug) fprintf(stderr, "[oa] grid path: iteration %d enqueued, device at %d, last hand-over %d entries / %d per wave (previous loop: %d) -> %s\n", c->iter_enq, n_done, poll ? poll[2] : -1, poll ? poll[3] : -1, c->last_todo_wave_max, fast ? "fast" : "safe");
     c->fast_prev = fast;
     return fast;
 }
@@ -983,7 +948,7 @@ int launch_vertex_grid(oa_ctx *c, const SearchChoice &s, bool acc)
     if (s.dual) { int rcb = launch_bvh<false>(c, nullptr, nullptr, 1, acc); if (rcb) return rcb; }   // runs when DevState::tree_turn
     // {index, safe2} per slot beside the winner records: both or neither (OA_GRID_SAFE=0)
     if (acc) { const int rcs = safe_radii_lazy(c); if (rcs) return rcs; }
-    const bool safe = c->grid_safe && c->safe_ok && c->d_safe_by_idx && c->d_wsafe;
+    const bool safe = c->tune.grid_safe && c->safe_ok && c->d_safe_by_idx && c->d_wsafe;
     // k_nn_search_grid<L, ACC, BT, STATS>; the accumulating form gets the tree, the pair test and the rows of partials
     auto launch = [&](auto L, auto ACC, auto BT, auto STATS, unsigned blocks, unsigned long long *stats) {
         constexpr bool A = decltype(ACC)::value;
@@ -999,7 +964,7 @@ int launch_vertex_grid(oa_ctx *c, const SearchChoice &s, bool acc)
     }
     const unsigned ablocks = (unsigned)canon_blocks(c);
 #if defined(OA_EXPERIMENTS)
-    if (c->grid_stats && s.lanes == 1 && canon_threads(c) == 512)
+    if (c->tune.grid_stats && s.lanes == 1 && canon_threads(c) == 512)
         return vertex_grid_stats(c, ablocks, [&](unsigned long long *stats) { launch(int_c<1>{}, yes, int_c<512>{}, yes, ablocks, stats); });
 #endif
     dispatch<256, 512>(canon_threads(c), [&](auto BT) { dispatch<1, 2, 4>(s.lanes, [&](auto L) { launch(L, yes, BT, no, ablocks, nullptr); }); });
@@ -1033,12 +998,12 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
     // with seeds: one launch over n_splits_seeded splits.  Without (the first search of a loop): k_nn_seed_sorted -- every point
     // against the tile that holds its own slab --, then the whole search seeded from what that left in keys (OA_NN_HOME_PASS=0:
     // one unseeded launch over n_splits splits, as until r05z)
-    const bool two = !c->win_seeds && c->nn_home_pass && c->n_splits_seeded > 1;
+    const bool two = !c->win_seeds && c->tune.nn_home_pass && c->n_splits_seeded > 1;
     dim3 sgrid((unsigned)((c->win_seeds || two) ? c->n_splits_seeded : c->n_splits), grid.y);
     // long launches go through the work queue (oa_kernels.hpp): as many workgroups as the chip holds, the long items first
     const int q_splits = (int)sgrid.x, q_blocks = (int)sgrid.y;
-    const long long q_wgs = (long long)c->n_cu * std::min(c->nn_persist, c->R <= 4 ? 4 : 2);
-    const bool queued = q_wgs > 0 && q_splits > 1 && (long long)q_splits * q_blocks >= (c->nn_queue_min >= 0 ? (long long)c->nn_queue_min : 4 * q_wgs);
+    const long long q_wgs = (long long)c->n_cu * std::min(c->tune.nn_persist, c->R <= 4 ? 4 : 2);
+    const bool queued = q_wgs > 0 && q_splits > 1 && (long long)q_splits * q_blocks >= (c->tune.nn_queue_min >= 0 ? (long long)c->tune.nn_queue_min : 4 * q_wgs);
     c->last_queue_wgs = queued ? (int)q_wgs : 0;
     { const int rcq = ensure_sorted_buffers(c, q_blocks); if (rcq) return rcq; }
     const int pass = two ? 2 : 0;                                   // (seeded from what the seed pass leaves in keys)
@@ -1056,7 +1021,7 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
         const dim3 ob((unsigned)(c->ns_pad / (64 * c->R)));
         dispatch<4, 1, 2, 8>(c->R, [&](auto R) {
             hipLaunchKernelGGL((oa::k_sorted_point_setup<decltype(R)::value>), ob, dim3(64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4,
-                               (const float4 *)c->d_win, (const unsigned long long *)c->d_keys, c->sax[0], c->sax[1], pass, c->nn_wave_order ? 1 : 0, c->ns_pad, c->d_prec);
+                               (const float4 *)c->d_win, (const unsigned long long *)c->d_keys, c->sax[0], c->sax[1], pass, c->tune.nn_wave_order ? 1 : 0, c->ns_pad, c->d_prec);
         });
         HIPCHK(hipGetLastError());
     }
@@ -1073,7 +1038,7 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
                            c->d_state, (const float4 *)c->d_tgs, (const float4 *)c->d_tfs, (const float4 *)c->d_tf3s, (const int4 *)c->d_tidx,
                            c->n_groups_pad, c->d_keys, pass, (const float4 *)c->d_prec, q_splits, q_blocks, c->d_homes, queued ? c->d_qcnt : nullptr, c->nt);
     };
-    auto search = [&](auto R) { dispatch<oa::FTILE_GROUPS, 64>(c->tile_groups, [&](auto TG) { if (c->nn_vchunk) launch(R, TG, yes); else launch(R, TG, no); }); };
+    auto search = [&](auto R) { dispatch<oa::FTILE_GROUPS, 64>(c->tile_groups, [&](auto TG) { if (c->tune.nn_vchunk) launch(R, TG, yes); else launch(R, TG, no); }); };
 #if defined(OA_EXPERIMENTS)
     dispatch<4, 1, 2, 8>(c->R, search);
 #else
@@ -1093,7 +1058,7 @@ int launch_brute(oa_ctx *c, const SearchChoice &s)
     case BRUTE_SORTED: return launch_brute_sorted(c, grid);
 #if defined(OA_EXPERIMENTS)
     case BRUTE_MFMA:
-        dispatch<4, 2, 3>(c->mfma_wps, [&](auto WPS) {
+        dispatch<4, 2, 3>(c->tune.mfma_wps, [&](auto WPS) {
             hipLaunchKernelGGL((oa::k_nn_search_mfma<decltype(WPS)::value>), grid, block, 0, c->stream, c->d_state, c->d_src4, c->d_tg, (const oa::half8 *)c->d_tfm, (const float4 *)c->d_win, c->n_groups_pad, c->mfma_sigma, c->d_keys);
         });
         break;
@@ -1282,7 +1247,7 @@ double min_singular_3x3(const float *M)
 // 1 / sigma_min(mx2); the arguments are left as they are where no radius applies.
 void search_radius(const oa_ctx *c, const float *mx2, double thresh, double &cut_a, double &cut_b, double &local_per_world)
 {
-    if (!(c->filter_ok && c->grid_mode != 0 && env_int("OA_NN_CUTOFF", 1))) return;
+    if (!(c->filter_ok && c->grid_mode != 0 && c->tune.nn_cutoff)) return;
     const double smin = min_singular_3x3(mx2) * (1.0 - 1e-9);
     if (smin > 0.0) local_per_world = 1.0 / smin;
     double m2norm = 0.0, tmax = 0.0, tscale = 0.0;
@@ -1299,6 +1264,13 @@ void search_radius(const oa_ctx *c, const float *mx2, double thresh, double &cut
     }
 }
 
+// DevState / PoseBatch::mx2_identity: the target's matrix is the identity, bit for bit -- the searches skip its products
+int mx2_identity(const oa_ctx *c, const float *mx2)
+{
+    static const float eye16[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+    return (memcmp(mx2, eye16, sizeof eye16) == 0 && !c->tune.no_identity_path) ? 1 : 0;
+}
+
 void init_loop_state(oa_ctx *c, const oa_settings *st, int iters, bool cutoff = true)
 {
     oa::DevState &s = c->h_state;
@@ -1313,11 +1285,10 @@ void init_loop_state(oa_ctx *c, const oa_settings *st, int iters, bool cutoff = 
     {   // first search of a loop: the tree (cold or stale seeds); a one-shot call on warm seeds: the grid
         const bool grid_up = c->surface ? c->tri_grid_ok : c->grid_ok;
         const oa::GridParams &g = c->surface ? c->tgp : c->gp;
-        s.turn_limit = grid_up ? c->turn_frac * g.h : 0.0;
+        s.turn_limit = grid_up ? c->tune.turn_frac * g.h : 0.0;
         s.turn_scale = grid_up ? g.scale : 0.0;
         s.tree_turn = (iters > 1 || !c->seeded) ? 1 : 0;
-        static const float eye16[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
-        s.mx2_identity = (memcmp(s.mx2, eye16, sizeof eye16) == 0 && !env_int("OA_NO_IDENTITY_PATH", 0)) ? 1 : 0;
+        s.mx2_identity = mx2_identity(c, s.mx2);
     }
     if (c->h_poll) {
         void *dp = nullptr;
@@ -1418,7 +1389,7 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
     {
         // (surfaces: NOT kind == SEARCH_BRUTE -- a mesh with a tree but no grid counts as a tree search here, as it always has)
         const bool brute = !c->surface ? choose_search(c).kind == SEARCH_BRUTE : (c->grid_mode == 0 || !c->tbvh_ok);
-        c->time_events = env_int("OA_TIME_EVENTS", brute ? 1 : 0) != 0;
+        c->time_events = c->tune.time_events < 0 ? brute : c->tune.time_events != 0;
     }
     c->loop_active = true;
     return OA_OK;
@@ -1621,7 +1592,7 @@ void exchange_abort_rccl(oa_ctx *p, const char *why)
     Exchange *x = p->xch;
     if (x->h_release) { __atomic_store_n(x->h_release, 1, __ATOMIC_RELEASE); }   // (test hook: the stalled stream goes on)
     if (x->comms.empty()) return;
-    if (p->subs.empty() ? false : p->subs[0]->debug) fprintf(stderr, "[oa] RCCL communicators aborted: %s\n", why);
+    if (p->subs.empty() ? false : p->subs[0]->tune.debug) fprintf(stderr, "[oa] RCCL communicators aborted: %s\n", why);
     for (size_t i = 0; i < x->comms.size(); ++i)
         if (x->comms[i] && x->CommAbort) { if (i < p->subs.size()) (void)hipSetDevice(p->subs[i]->device); (void)x->CommAbort(x->comms[i]); }
     x->comms.clear();
@@ -1806,7 +1777,7 @@ int exchange_resolve(oa_ctx *p)
         x->mode = OA_EXCHANGE_MAILBOX;
     } else {
         x->mode = OA_EXCHANGE_MAILBOX;
-        const bool any = env_int("OA_AUTO_RCCL_ANY", 0) != 0;       // test hook: AUTO takes RCCL for a world of one too (the fallback of multi_run on a one-GPU box)
+        const bool any = p->tune.auto_rccl_any;                // test hook: AUTO takes RCCL for a world of one too (the fallback of multi_run on a one-GPU box)
         if (p->subs.size() < 2 && !any) x->auto_note = "one device: nothing to exchange";
         else if (!devices_distinct(p)) x->auto_note = "a device is listed more than once";
         else if (x->rccl_aborted) { /* auto_note says why: a communicator that hung once is not trusted again unasked */ }
@@ -1846,8 +1817,7 @@ int exchange_setup_mailboxes(oa_ctx *p)
     Exchange *x = p->xch;
     const int world = x->world;
     const size_t bytes = sizeof(oa::MailSlot) * 2 * (size_t)world;
-    const char *want = getenv("OA_MAILBOX");
-    const bool force_host = want && !strcmp(want, "host"), force_dev = want && !strcmp(want, "device");
+    const bool force_host = p->tune.mailbox == 1, force_dev = p->tune.mailbox == 2;
     bool dev_ok = !force_host;
     std::string why;
     if (dev_ok) {
@@ -2090,7 +2060,7 @@ int multi_group_loop(oa_ctx *p, size_t g, const oa_settings *st)
     Exchange *x = p->xch;
     oa_ctx *c0 = p->subs[(size_t)group[0]];
     // (the adaptive grid path needs recent news from the device too: then the host stays close even without early exit)
-    bool poll = c0->h_poll && env_int("OA_RUN_POLL", 1) && (st->early_exit || (choose_search(c0).plan == PLAN_GRID && c0->grid_path == 0));
+    bool poll = loop_polls(c0, st);
     const int lag = 2;
     volatile int32_t *progress = c0->h_poll;
     for (int it = 0; it < st->iters; ++it) {
@@ -2135,7 +2105,7 @@ int multi_run(oa_ctx *p, const oa_settings *st, oa_report *rep)
         // An explicit oa_set_exchange(RCCL) gets the error.  (the RCCL path has never run on distinct GPUs.)
         if (rc == OA_E_RCCL && attempt == 0 && was_rccl && p->xch->requested == OA_EXCHANGE_AUTO && p->xch->rccl_aborted) {
             p->xch->rccl_fallbacks++;
-            if (!p->subs.empty() && p->subs[0]->debug) fprintf(stderr, "[oa] RCCL failed (%s): the loop runs again through the mailboxes\n", keep.c_str());
+            if (!p->subs.empty() && p->subs[0]->tune.debug) fprintf(stderr, "[oa] RCCL failed (%s): the loop runs again through the mailboxes\n", keep.c_str());
             continue;
         }
         g_err = keep;
@@ -2183,48 +2153,8 @@ OA_EXPORT int oa_create(oa_ctx **out, int device)
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete c; return fail(OA_E_HIP, "oa_create: %s", hipGetErrorString(e)); }
     c->stream = c->own_stream;
-    c->R_env = env_int("OA_NN_R", 0);
-    if (c->R_env != 1 && c->R_env != 2 && c->R_env != 4 && c->R_env != 8) c->R_env = 0;
-    c->R = c->R_env ? c->R_env : 4;
-    c->grid_lanes = env_int("OA_GRID_LANES", 0);
-    c->acc_threads = env_int("OA_ACC_THREADS", 0);
-    c->turns_on = env_int("OA_SEARCH_TURNS", 1);
-    c->debug = getenv("OA_DEBUG") != nullptr;
-    c->grid_stats = env_int("OA_GRID_STATS", 0) != 0;
-    c->tri_share = env_int("OA_TRI_SHARE", 1) != 0;
-    c->grid_safe = std::max(0, std::min(2, env_int("OA_GRID_SAFE", 1)));
-    c->tri_ring = std::max(0, std::min(2, env_int("OA_TRI_RING", 0)));
-    c->tri_ring_cap = env_double("OA_TRI_RING_CAP", 0.25);
-    c->tri_split = env_int("OA_TRI_SPLIT", 1) != 0;
-    c->tri_wave_wgs = env_int("OA_TRI_WAVE_WGS", 1) != 0;
-    c->tri_fine = std::max(0, std::min(2, env_int("OA_TRI_FINE", 0)));   // EXPERIMENT (liboa_icp_exp.so), off: measured slower than the search it fronts, docs/HISTORY.md
-    c->tri_fine_min_tris = std::max(64, env_int("OA_TRI_FINE_MIN_TRIS", 200000));
-    c->tri_split_lanes = env_int("OA_TRI_SPLIT_LANES", 1) != 0;
-    c->tri_canon = env_int("OA_TRI_CANON", 1) != 0;
-    c->list_blocks_per_cu = std::max(1, std::min(64, env_int("OA_LIST_BLOCKS_PER_CU", 16)));
-    c->tri_acc = env_int("OA_TRI_ACC", 1) != 0;
-    c->turn_frac = env_double("OA_TURN_FRAC", 0.1);
-    c->use_filter = env_int("OA_NN_FILTER", 1) != 0;
-    c->nn_sort = env_int("OA_NN_SORT", 1) != 0;
-    c->nn_home_pass = env_int("OA_NN_HOME_PASS", 1) != 0;
-    c->nn_wave_order = env_int("OA_NN_WAVE_ORDER", 1) != 0;
-    c->nn_persist = std::max(0, std::min(16, env_int("OA_NN_PERSIST", 4)));
-    c->nn_vchunk = env_int("OA_NN_VCHUNK", 1) != 0;
-    c->nn_queue_min = env_int("OA_NN_QUEUE_MIN_ITEMS", -1);
-    c->nn_mfma = env_int("OA_NN_MFMA", 0);
-#if !defined(OA_EXPERIMENTS)
-    // the default library does not carry the experiments (oa_families.hpp): their knobs are inert here, liboa_icp_exp.so has them
-    c->nn_mfma = 0; c->tri_ring = 0; c->tri_fine = 0; c->nn_sort = true; c->grid_stats = false; c->tri_share = true;
-    if (c->R_env == 8) { c->R_env = 4; c->R = 4; }              // (8 points per thread: an OA_EXPERIMENTS instantiation)
-#endif
-    c->mfma_wps = env_int("OA_MFMA_WPS", 4);
-    c->grid_mode = env_int("OA_NN_GRID", -1);
-    c->fused_acc = env_int("OA_FUSED_ACC", 1);
-    c->tree_acc_max = env_int("OA_TREE_ACC_MAX", 4096);
-    {
-        const char *gp = getenv("OA_GRID_PATH");
-        c->grid_path = (gp && !strcmp(gp, "fast")) ? 1 : ((gp && !strcmp(gp, "safe")) ? 2 : 0);
-    }
+    c->R = c->tune.nn_r ? c->tune.nn_r : 4;
+    c->grid_mode = c->tune.nn_grid;
     dev_cache().context_created();
     *out = c;
     return OA_OK;
@@ -2250,7 +2180,7 @@ OA_EXPORT int oa_create_multi(oa_ctx **out, const int *devices, int n_dev)
     if (!x) { delete p; return fail(OA_E_HIP, "out of host memory"); }
     p->xch = x;
     x->world = n_dev;
-    const bool own_streams = env_int("OA_MULTI_OWN_STREAMS", 0) != 0;
+    const bool own_streams = p->tune.multi_own_streams;
     int rc = OA_OK;
     for (int i = 0; i < n_dev && !rc; ++i) {
         oa_ctx *c = nullptr;
@@ -2263,29 +2193,28 @@ OA_EXPORT int oa_create_multi(oa_ctx **out, const int *devices, int n_dev)
     }
     if (!rc) rc = exchange_setup_mailboxes(p);
     if (!rc) {
-        const double secs = std::max(0.05, env_double("OA_EXCHANGE_TIMEOUT_S", 30.0));
+        const double secs = p->tune.exchange_timeout_s;
         x->timeout_ticks = (unsigned long long)(secs * p->subs[0]->wall_clock_khz * 1e3);
         x->seq_next = 0;
         x->timeout_s = secs;
-        x->fault_skip_rank = env_int("OA_FAULT_SKIP_POST_RANK", -1);
-        x->agree_on = env_int("OA_MULTI_AGREE", 1) != 0;
-        x->fault_lag_group = env_int("OA_FAULT_LAG_GROUP", -1);
-        x->fault_lag_us = env_int("OA_FAULT_LAG_US", 0);
-        x->fault_fail_group.store(env_int("OA_FAULT_FAIL_GROUP", -1));
-        x->fault_fail_iter = env_int("OA_FAULT_FAIL_ITER", -1);
-        x->fault_stall_rank.store(env_int("OA_FAULT_STALL_RANK", -1));
-        x->fault_stall_iter = env_int("OA_FAULT_STALL_ITER", 2);
+        x->fault_skip_rank = p->tune.fault_skip_post_rank;
+        x->agree_on = p->tune.multi_agree;
+        x->fault_lag_group = p->tune.fault_lag_group;
+        x->fault_lag_us = p->tune.fault_lag_us;
+        x->fault_fail_group.store(p->tune.fault_fail_group);
+        x->fault_fail_iter = p->tune.fault_fail_iter;
+        x->fault_stall_rank.store(p->tune.fault_stall_rank);
+        x->fault_stall_iter = p->tune.fault_stall_iter;
         if (x->fault_stall_rank.load() >= 0) {
             if (hipHostMalloc((void **)&x->h_release, sizeof(int32_t), hipHostMallocPortable | hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); x->h_release = nullptr; }
             else *x->h_release = 0;
         }
-        const char *m = getenv("OA_EXCHANGE");
-        if (m && (!strcmp(m, "rccl") || !strcmp(m, "RCCL") || !strcmp(m, "1"))) x->requested = OA_EXCHANGE_RCCL;
-        else if (m && (!strcmp(m, "mailbox") || !strcmp(m, "MAILBOX") || !strcmp(m, "0"))) x->requested = OA_EXCHANGE_MAILBOX;
+        static_assert(OA_EXCHANGE_AUTO == -1 && OA_EXCHANGE_MAILBOX == 0 && OA_EXCHANGE_RCCL == 1, "Tunables::exchange holds these values");
+        x->requested = p->tune.exchange;
         // host threads: one group of children per GPU (OA_MULTI_THREADS=1: per child, 0: a single group).  In the loop
         // children that share a STREAM always share a thread: enqueued from two threads, one child's gather could land
         // in front of the post it waits for.
-        const int threads = env_int("OA_MULTI_THREADS", -1);
+        const int threads = p->tune.multi_threads;
         auto deal = [&](std::vector<std::vector<int>> &groups, bool per_child) {
             for (int i = 0; i < n_dev; ++i) {
                 size_t g = groups.size();
@@ -2457,7 +2386,7 @@ int bbox_partials(oa_ctx *c, const float *d_xyz, long long n, int nb, float *out
 int build_sorted_images(oa_ctx *c)
 {
     dev_free(c->d_tfs); dev_free(c->d_tf3s); dev_free(c->d_tgs); dev_free(c->d_tidx);
-    if (!(c->filter_ok && c->nn_sort && c->nt >= 2)) return OA_OK;
+    if (!(c->filter_ok && c->tune.nn_sort && c->nt >= 2)) return OA_OK;
     const double *lo = c->bb_lo, *hi = c->bb_hi;
     const int ad = c->fax[2];
     int su = 0;
@@ -2473,7 +2402,7 @@ int build_sorted_images(oa_ctx *c)
                        ext > 0.0 ? 1073741823.0 / ext : 0.0, k_in.p, v_in.p);
     HIPCHK(hipGetLastError());
     { const int rcs = sort_order_bits(c, k_in.p, v_out.p, (size_t)c->nt, 30); if (rcs) return rcs; }
-    if (c->nn_vchunk) {                                           // every block of the u order by v, its first vertex kept (k_sort_blocks_v)
+    if (c->tune.nn_vchunk) {                                           // every block of the u order by v, its first vertex kept (k_sort_blocks_v)
         hipLaunchKernelGGL(oa::k_sort_blocks_v, dim3((unsigned)((c->nt + oa::SORTED_VBLOCK - 1) / oa::SORTED_VBLOCK)), dim3(oa::SORTED_VBLOCK), 0,
                            c->stream, (const float *)c->d_tgt_xyz, c->nt, c->sax[1], c->tc[c->sax[1]], v_out.p);
         HIPCHK(hipGetLastError());
@@ -2541,7 +2470,7 @@ int build_filter(oa_ctx *c, bool vertex_target)
     if (c->grid_mode == 0 && vertex_target) { const int rcs = build_sorted_images(c); if (rcs) return rcs; }
     dev_free(c->d_tfm);
 #if defined(OA_EXPERIMENTS)
-    if (c->filter_ok && c->nn_mfma) {                            // experiment: the MFMA image (32 B per target)
+    if (c->filter_ok && c->tune.nn_mfma) {                            // experiment: the MFMA image (32 B per target)
         int e = 0;
         if (c->qmax > 0.0) { frexp(c->qmax, &e); }               // qmax = f 2^e, f in [0.5, 1)  ->  qmax 2^-e < 1
         c->mfma_sigma = ldexp(1.0, -e);
@@ -2582,7 +2511,7 @@ int build_grid(oa_ctx *c)
         if (ext[a] > 0.0) { vol *= ext[a]; ++nz; }
         scale = std::max(scale, std::max(fabs(c->bb_lo[a]), fabs(c->bb_hi[a])));
     }
-    const double ppc = env_double("OA_GRID_PPC", 2.0);               // target vertices per cell
+    const double ppc = c->tune.grid_ppc;                          // target vertices per cell
     double h = nz ? pow(vol * ppc / (double)c->nt, 1.0 / nz) : 1.0;
     if (!(h > 0.0) || !(h < INFINITY)) return OA_OK;
     const long long max_cells = 1ll << 24;
@@ -2606,12 +2535,12 @@ int build_grid(oa_ctx *c)
         // a clamped axis (1024 cells) needs a cell edge that still covers the extent
         for (int a = 0; a < 3; ++a) if (ext[a] > 0.0 && ext[a] / h >= gp.n[a]) h = std::max(h, ext[a] / (gp.n[a] - 0.5));
         gp.h = h; gp.inv_h = 1.0 / h;
-        gp.r_max = std::min(env_int("OA_GRID_RMAX", 3), 3);
-        gp.seeded_start = env_int("OA_GRID_SEEDED_START", 1) ? 1 : 0;
+        gp.r_max = c->tune.grid_rmax;
+        gp.seeded_start = c->tune.grid_seeded_start ? 1 : 0;
         // (256: 128 was tuned in round 2, when a hand-over was a list entry; surface-like clouds -- C5 -- keep ~1000 queries per
         //  search above 128 once the doubling for a moving pose ends, and every one of them costs the iteration its fast path)
-        gp.budget = env_int("OA_GRID_BUDGET", 256);
-        gp.budget_moving = (int)(gp.budget * env_double("OA_GRID_BUDGET_MOVING", 2.0));
+        gp.budget = c->tune.grid_budget;
+        gp.budget_moving = (int)(gp.budget * c->tune.grid_budget_moving);
         gp.moving_h = 0.25 * gp.h;
         gp.slack = 1e-10 * scale + 1e-300;
         gp.scale = scale;
@@ -2650,8 +2579,8 @@ int build_grid(oa_ctx *c)
     HIPCHK(hipStreamSynchronize(c->stream));
     c->gp = gp; c->n_cells = n_cells; c->grid_ok = true;
     c->target_iters = 0;
-    if (c->grid_safe) HIPCHK(dev_malloc(&c->d_safe_by_idx, sizeof(float) * (size_t)c->nt));
-    if (c->grid_safe == 2) return build_safe_radii(c);
+    if (c->tune.grid_safe) HIPCHK(dev_malloc(&c->d_safe_by_idx, sizeof(float) * (size_t)c->nt));
+    if (c->tune.grid_safe == 2) return build_safe_radii(c);
     return OA_OK;
 }
 
@@ -2682,7 +2611,7 @@ int set_target_common(oa_ctx *c, const float *xyz, int64_t n, int on_device, boo
     c->n_groups_pad = 0;
     c->seeded = false; c->win_seeds = false;
     // {index, safe radius} per slot: only the vertex searches read it (8 bytes per source point)
-    if (!vertex_index || !c->grid_safe) dev_free(c->d_wsafe);
+    if (!vertex_index || !c->tune.grid_safe) dev_free(c->d_wsafe);
     else if (c->d_prev && !c->d_wsafe) HIPCHK(dev_malloc(&c->d_wsafe, sizeof(uint2) * (size_t)c->ns_pad));
     if (c->d_prev) {   // seeds index the old target
         // (the safe radii beside the winner records belong to the old target's indices too)
@@ -2838,6 +2767,12 @@ int morton_frame(oa_ctx *c, const float *d_xyz, long long n_verts, float lo[3], 
     return OA_OK;
 }
 
+// Are the shards of a selection ranges of its Morton order (compact regions of space), or of the caller's order?
+bool spatial_sharding(const oa_ctx *c, long long n_sel, int shards)
+{
+    return shards > 1 && n_sel < 0x7FF00000ll && c->tune.sort_source && c->tune.shard_spatial;
+}
+
 // Positions (in the selection) of the points shard [begin, begin + count) of the Morton-ordered selection holds, in
 // ascending order -> members (device).  Left empty (caller falls back to contiguous ranges) for non-finite input.
 int spatial_shard_members(oa_ctx *c, const float *d_xyz, long long n_verts, const long long *d_vlist, long long step,
@@ -2937,11 +2872,11 @@ int build_tri_grid(oa_ctx *c, const double *diag_sum_known)
         scale = std::max(scale, std::max(fabs(c->bb_lo[a]), fabs(c->bb_hi[a])));
     }
     c->tri_mean_diag = diag_sum / (double)c->n_tris;
-    double h = env_double("OA_TRI_CELL", 1.25) * diag_sum / (double)c->n_tris;  // mean triangle bbox diagonals per cell edge (1.5 until the scan
+    double h = c->tune.tri_cell * diag_sum / (double)c->n_tris;            // mean triangle bbox diagonals per cell edge (1.5 until the scan
                                                                                  // became VALU-bound at the end of round 3: fewer records per cell now pay)
     if (!(h > 0.0) || !(h < INFINITY)) h = max_ext > 0.0 ? max_ext / 64.0 : 1.0;
     h = std::max(h, max_ext / 1023.0);
-    const long long max_cells = 1ll << std::max(16, std::min(29, env_int("OA_TRI_MAX_CELLS_LOG2", 24)));
+    const long long max_cells = 1ll << c->tune.tri_max_cells_log2;
     DevTmp<int> d_counts;
     DevTmp<long long> d_off;
     oa::GridParams gp{};
@@ -2958,18 +2893,18 @@ int build_tri_grid(oa_ctx *c, const double *diag_sum_known)
         }
         if (total > max_cells) { h *= 1.3; n_cells = 0; continue; }
         gp.h = h; gp.inv_h = 1.0 / h;
-        gp.r_max = std::min(env_int("OA_GRID_RMAX", 3), 3);
-        gp.seeded_start = env_int("OA_TRI_SEEDED_START", 1) ? 1 : 0;
-        gp.budget = std::max(1, std::min(env_int("OA_GRID_BUDGET", 192), 30000));
-        gp.budget_moving = std::max(1, std::min((int)(gp.budget * env_double("OA_GRID_BUDGET_MOVING", 3.0)), 60000));   // (range lengths are 16-bit in the kernel; 2.0 until the scan was shared by the wave)
+        gp.r_max = c->tune.grid_rmax;
+        gp.seeded_start = c->tune.tri_seeded_start ? 1 : 0;
+        gp.budget = c->tune.tri_budget;
+        gp.budget_moving = std::max(1, std::min((int)(gp.budget * c->tune.tri_budget_moving), 60000));   // (range lengths are 16-bit in the kernel; 2.0 until the scan was shared by the wave)
         gp.scale = scale;
         gp.slack = 1e-10 * scale + 1e-300;
         oa::grid_params_finish(gp);
         gp.eps_plane = (float)(8.0 * 5.9604644775390625e-08 * scale + 1e-37);
-        gp.drop_over = env_int("OA_TRI_DROP_OVER", 1);
-        gp.moving_h = env_double("OA_TRI_MOVING_FRAC", 0.25) * gp.h;
-        gp.xcd_chunk = std::max(0, std::min(4096, env_int("OA_TRI_XCD_CHUNK", 8)));
-        gp.xcd_moving_h = env_double("OA_TRI_XCD_MOVING_FRAC", 0.5) * gp.h;
+        gp.drop_over = c->tune.tri_drop_over;
+        gp.moving_h = c->tune.tri_moving_frac * gp.h;
+        gp.xcd_chunk = c->tune.tri_xcd_chunk;
+        gp.xcd_moving_h = c->tune.tri_xcd_moving_frac * gp.h;
         n_cells = (int)total;
         // (the entry total behind the counts, 8-byte aligned: one memset for both)
         const size_t total_at = ((size_t)n_cells + 2) & ~(size_t)1;
@@ -3006,14 +2941,14 @@ int build_tri_grid(oa_ctx *c, const double *diag_sum_known)
     c->tgp = gp;
     c->n_tri_entries = (long long)entries;
     c->tri_grid_ok = true;
-    if (c->debug)
+    if (c->tune.debug)
         fprintf(stderr, "[oa] tri grid: h=%g cells=%dx%dx%d entries=%llu (%.2f per triangle)\n", gp.h, gp.n[0], gp.n[1], gp.n[2],
                 entries, (double)entries / c->n_tris);
-    if (c->tri_ring) {
+    if (c->tune.tri_ring) {
         HIPCHK(dev_malloc(&c->d_tri_ring, sizeof(int) * (size_t)oa::TRI_RING_STRIDE * (size_t)c->n_tris));
-        if (c->tri_ring == 2) { const int rcr = build_tri_ring(c); if (rcr) return rcr; }
+        if (c->tune.tri_ring == 2) { const int rcr = build_tri_ring(c); if (rcr) return rcr; }
     }
-    if (c->tri_fine == 2 || (c->tri_fine == 1 && c->n_tris >= c->tri_fine_min_tris)) return build_tri_fine(c);
+    if (c->tune.tri_fine == 2 || (c->tune.tri_fine == 1 && c->n_tris >= c->tune.tri_fine_min_tris)) return build_tri_fine(c);
     return OA_OK;
 }
 
@@ -3029,15 +2964,15 @@ int build_tri_fine(oa_ctx *c)
 #else
     if (!c->tri_grid_ok || !c->tbvh_ok || !(c->tri_mean_diag > 0.0) || !(c->tri_mean_diag < INFINITY)) return OA_OK;
     oa::FineParams fp{};
-    double h = env_double("OA_TRI_FINE_CELL", 0.5) * c->tri_mean_diag;
-    const double rho_frac = std::max(0.01, std::min(env_double("OA_TRI_FINE_RHO", 0.3), 4.0));
+    double h = c->tune.tri_fine_cell * c->tri_mean_diag;
+    const double rho_frac = c->tune.tri_fine_rho;
     double ext[3], scale = 0.0, max_ext = 0.0;
     for (int a = 0; a < 3; ++a) {
         ext[a] = c->bb_hi[a] - c->bb_lo[a];
         max_ext = std::max(max_ext, ext[a]);
         scale = std::max(scale, std::max(fabs(c->bb_lo[a]), fabs(c->bb_hi[a])));
     }
-    const unsigned long long max_entries = (unsigned long long)(std::max(16.0, env_double("OA_TRI_FINE_MAX_MB", 8192.0)) * 1048576.0 / 48.0);
+    const unsigned long long max_entries = (unsigned long long)(c->tune.tri_fine_max_mb * 1048576.0 / 48.0);
     constexpr size_t SLOT_WORDS = (size_t)oa::TOTAL_SLOTS * oa::TOTAL_STRIDE;
     DevTmp<unsigned long long> d_total;
     HIPCHK(d_total.alloc(SLOT_WORDS));
@@ -3069,8 +3004,8 @@ int build_tri_fine(oa_ctx *c)
         sized = true;
     }
     if (!sized) return OA_OK;
-    fp.cap = std::max(1, std::min(env_int("OA_TRI_FINE_CAP", 192), 1 << 20));
-    fp.gate = env_double("OA_TRI_FINE_GATE", 1e30) * fp.rho;
+    fp.cap = c->tune.tri_fine_cap;
+    fp.gate = c->tune.tri_fine_gate * fp.rho;
     // the table: a power of two of slots, at most a third full for ordinary meshes (7-10 entries per occupied cell); a mesh whose
     // cells hold one entry each overflows the probe limit instead -- then four times the slots, twice
     unsigned long long want = std::max(1024ull, entries / 3ull);
@@ -3104,7 +3039,7 @@ int build_tri_fine(oa_ctx *c)
             c->tfp = fp;
             c->n_fine_entries = (long long)entries;
             c->tri_fine_ok = true;
-            if (c->debug)
+            if (c->tune.debug)
                 fprintf(stderr, "[oa] tri fine grid: h=%g (%.2f mean diagonals) rho=%g cells=%dx%dx%d entries=%llu (%.2f per triangle, %.0f MB) table 2^%d slots\n",
                         fp.h, fp.h / c->tri_mean_diag, fp.rho, fp.n[0], fp.n[1], fp.n[2], entries, (double)entries / c->n_tris, entries * 48.0 / 1048576.0, log2);
             return OA_OK;
@@ -3124,9 +3059,9 @@ int build_tri_ring(oa_ctx *c)
     return OA_OK;                                                   // (OA_TRI_RING is inert in the default library)
 #else
     if (!c->tri_grid_ok || !c->d_tri_ring || c->tri_ring_ok) return OA_OK;
-    const double cap = std::max(0.01, std::min(c->tri_ring_cap, 1.0)) * c->tgp.h;
+    const double cap = std::max(0.01, std::min(c->tune.tri_ring_cap, 1.0)) * c->tgp.h;
     const dim3 blocks((unsigned)((c->n_tris + 255) / 256));
-    if (c->grid_stats || c->debug) {
+    if (c->tune.grid_stats || c->tune.debug) {
         DevTmp<unsigned long long> d_stats;
         HIPCHK(d_stats.alloc(oa::RING_STAT_N));
         HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(unsigned long long) * oa::RING_STAT_N, c->stream));
@@ -3161,7 +3096,7 @@ int launch_tri_settle(oa_ctx *c, int &qcap)
                            (const uint4 *)c->d_tfine_table, (const float4 *)c->d_tfine_rec, (const float4 *)c->d_tri9, (const int *)c->d_prev, c->d_keys, c->d_ulist, qcap,
                            ucount_set(c, c->u_slot), ucount_set(c, c->u_slot ^ 1), stats);
     };
-    if (c->grid_stats) {                                            // OA_GRID_STATS=1: instrumented launch, totals to stderr (one row of 8 for the launch)
+    if (c->tune.grid_stats) {                                            // OA_GRID_STATS=1: instrumented launch, totals to stderr (one row of 8 for the launch)
         unsigned long long h[8];
         { const int rcs = wave_stats(c, 8, 1, h, [&](unsigned long long *stats) { launch(yes, stats); }); if (rcs) return rcs; }
         fprintf(stderr, "[oa] tri settle: %llu of %d queries settled (%.2f records each); the others: %llu no seed, %llu reach beyond rho, %llu outside the box, "
@@ -3250,25 +3185,25 @@ int launch_tri_grid(oa_ctx *c, const SearchChoice &s, bool acc)
         // the list's length decides the lanes per query, on the device (k_tri_search_grid: qmin / qmax): a 4-lane launch for
         // lists of up to `small` queries, and the shard's own geometry for longer ones
         const int small = std::min(c->ns, (c->n_tris >= 250000 ? 400 : 128) * c->n_cu);
-        const bool two = lanes != 4 && c->tri_split_lanes;
+        const bool two = lanes != 4 && c->tune.tri_split_lanes;
         if (two) launch(int_c<4>{}, no, yes, no, int_c<256>{}, (unsigned)(((long long)small * 4 + 255) / 256), nullptr, nullptr, 0, small);
         dispatch<1, 2, 4>(lanes, [&](auto L) { launch(L, no, yes, no, int_c<256>{}, gblocks, nullptr, nullptr, two ? small : 0, 0x7FFFFFFF); });
     }
-    else if (c->tri_wave_wgs && !c->grid_stats && c->tri_share && wblocks >= (long long)c->n_cu * 32)
+    else if (c->tune.tri_wave_wgs && !c->tune.grid_stats && c->tune.tri_share && wblocks >= (long long)c->n_cu * 32)
         dispatch<1, 2, 4>(lanes, [&](auto L) { launch(L, no, yes, no, int_c<64>{}, (unsigned)wblocks, nullptr, ring); });
 #if defined(OA_EXPERIMENTS)
-    else if (lanes == 1 && c->grid_stats) {
+    else if (lanes == 1 && c->tune.grid_stats) {
         const int rcs = tri_grid_stats(c, gblocks, [&](unsigned long long *stats) {
-            if (c->tri_share) launch(int_c<1>{}, yes, yes, no, int_c<256>{}, gblocks, stats, ring);
+            if (c->tune.tri_share) launch(int_c<1>{}, yes, yes, no, int_c<256>{}, gblocks, stats, ring);
             else launch(int_c<1>{}, yes, no, no, int_c<256>{}, gblocks, stats, ring);
         });
         if (rcs) return rcs;
     }
-    else if (lanes == 1 && !c->tri_share) launch(int_c<1>{}, no, no, no, int_c<256>{}, gblocks, nullptr, ring);
+    else if (lanes == 1 && !c->tune.tri_share) launch(int_c<1>{}, no, no, no, int_c<256>{}, gblocks, nullptr, ring);
 #endif
     else dispatch<1, 2, 4>(lanes, [&](auto L) { launch(L, no, yes, no, int_c<256>{}, gblocks, nullptr, ring); });
     HIPCHK(hipGetLastError());
-    if (c->debug && !listed) {                                     // how many queries the grid handed over (debug only: syncs)
+    if (c->tune.debug && !listed) {                                     // how many queries the grid handed over (debug only: syncs)
         int n_todo = 0;
         { int rcr = read_small(c, &n_todo, c->d_todo_count, sizeof(int)); if (rcr) return rcr; }
         fprintf(stderr, "[oa] tri grid handed %d of %d queries to the tree\n", n_todo, c->ns);
@@ -3278,7 +3213,7 @@ int launch_tri_grid(oa_ctx *c, const SearchChoice &s, bool acc)
 
 int launch_tri_search(oa_ctx *c, const SearchChoice &s, bool acc)
 {
-    if (c->debug)
+    if (c->tune.debug)
         fprintf(stderr, "[oa] tri search: grid=%d acc=%d ns=%d n_tris=%d state=%p src4=%p tri9=%p prev=%p keys=%p todo=%p/%p cells=%p/%p\n",
                 (int)(s.kind == SEARCH_GRID), (int)acc, c->ns, c->n_tris, (void *)c->d_state, (void *)c->d_src4, (void *)c->d_tri9, (void *)c->d_prev,
                 (void *)c->d_keys, (void *)c->d_todo_list, (void *)c->d_todo_count, (void *)c->d_tcell_start, (void *)c->d_tcell_rec);
@@ -3366,7 +3301,7 @@ int source_reset(oa_ctx *c, long long count, long long begin, long long n_verts)
     c->emit_cap = 0;
     c->ns = (int)count;
     // points per thread: 4 for big shards; small shards take 2 or 1 so that the launch still has enough workgroups
-    c->R = c->R_env ? c->R_env : (count >= 65536 ? 4 : (count >= 16384 ? 2 : 1));
+    c->R = c->tune.nn_r ? c->tune.nn_r : (count >= 65536 ? 4 : (count >= 16384 ? 2 : 1));
     const int chunk = oa::NN_THREADS * c->R;
     c->ns_pad = (int)(((count + chunk - 1) / chunk) * chunk);
     if (c->ns_pad == 0) c->ns_pad = chunk;
@@ -3377,7 +3312,7 @@ int source_reset(oa_ctx *c, long long count, long long begin, long long n_verts)
     dev_free(c->d_prec); dev_free(c->d_homes); dev_free(c->d_qcnt);
     c->prec_cap = 0; c->homes_cap = 0;
     if (c->grid_mode == 0) { const int rcq = ensure_sorted_buffers(c, c->ns_pad / chunk); if (rcq) return rcq; }   // (brute force only, never inside a loop: 48 B per slot + the brute-force launch's q_blocks, a few KB)
-    if (c->grid_safe && !c->surface) HIPCHK(dev_malloc(&c->d_wsafe, sizeof(uint2) * (size_t)c->ns_pad));   // (a vertex target set later allocates it: set_target_common)
+    if (c->tune.grid_safe && !c->surface) HIPCHK(dev_malloc(&c->d_wsafe, sizeof(uint2) * (size_t)c->ns_pad));   // (a vertex target set later allocates it: set_target_common)
     c->seeded = false; c->win_seeds = false;
     HIPCHK(dev_malloc(&c->d_sel, sizeof(int) * (size_t)c->ns_pad));
     dev_free(c->d_todo_list); dev_free(c->d_todo_count); dev_free(c->d_ulist);
@@ -3427,7 +3362,7 @@ int set_source_single(oa_ctx *c, const float *xyz, int64_t n_verts, int on_devic
         // whole cloud costs 16 % more per pair (1/8 of 1M: 7.3 ms vs 6.3 ms).  Fallback (non-finite coordinates,
         // OA_SHARD_SPATIAL=0): contiguous ranges of the selection in the caller's order.
         DevTmp<int> d_members;
-        if (shard_count > 1 && c->ns > 0 && n_sel < 0x7FF00000ll && env_int("OA_SORT_SOURCE", 1) && env_int("OA_SHARD_SPATIAL", 1)) {
+        if (c->ns > 0 && spatial_sharding(c, n_sel, shard_count)) {
             int rcm = spatial_shard_members(c, d_xyz, n_verts, (const long long *)d_vlist.p, step, n_sel, begin, c->ns, d_members);
             if (rcm) return rcm;
             if (d_members.p) {                                      // kept: per-point outputs of a shard go back to vlist order through it
@@ -3446,7 +3381,7 @@ int set_source_single(oa_ctx *c, const float *xyz, int64_t n_verts, int on_devic
         } else HIPCHK(hipMemsetAsync(c->d_src4, 0, sizeof(float4) * (size_t)c->ns_pad, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         for (int k = 0; k < 3; ++k) c->pivot[k] = (double)p0[k];
-        if (c->ns > 1 && env_int("OA_SORT_SOURCE", 1)) {
+        if (c->ns > 1 && c->tune.sort_source) {
             int rcs = sort_source_slots(c, d_xyz, n_verts);
             if (rcs) return rcs;
         }
@@ -3577,8 +3512,7 @@ OA_EXPORT int oa_set_source(oa_ctx *c, const float *xyz, int64_t n_verts, int on
     c->loop_active = false;
     const int n_dev = (int)c->subs.size();
     const long long per = (n_sel + n_dev - 1) / n_dev;
-    if (n_dev > 1 && n_sel > 1 && n_sel < 0x7FF00000ll && env_int("OA_SORT_SOURCE", 1) && env_int("OA_SHARD_SPATIAL", 1) &&
-        env_int("OA_PARTITION_ONCE", 1)) {
+    if (n_sel > 1 && spatial_sharding(c, n_sel, n_dev) && c->tune.partition_once) {
         // one Morton sort of the selection on the first device, then every device adopts its range of it
         oa_ctx *stage = c->subs[0];
         SelectionOrder order;
@@ -3870,12 +3804,12 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
         HIPCHK(hipMemsetAsync(d_n, 0, 16 * sizeof(unsigned long long), c->stream));
         hipLaunchKernelGGL(oa::k_tri_ring_count, dim3((unsigned)((c->ns + 255) / 256)), dim3(256), 0, c->stream, (const oa::DevState *)c->d_state,
                            (const float4 *)c->d_src4, c->ns, c->tgp.scale, (const float4 *)c->d_tri9, (const int *)c->d_prev, d_n.p,
-                           c->debug ? d_n.p : (unsigned long long *)nullptr);
+                           c->tune.debug ? d_n.p : (unsigned long long *)nullptr);
         HIPCHK(hipGetLastError());
         unsigned long long n[16];
         if ((rc = read_small(c, n, d_n, sizeof(n)))) return rc;
         *value = (double)n[0];
-        if (c->debug)
+        if (c->tune.debug)
             fprintf(stderr, "[oa] tri ring: %llu of %d queries settled by seed + neighbours; the others: %llu no seed, %llu seeds that never accept, %llu not certified, "
                             "distance + margins within 1x / 2x / 4x / 8x of the radius %llu / %llu / %llu / %llu, farther %llu\n",
                     n[0], c->ns, n[1], n[2], n[3], n[4], n[5], n[6], n[7], n[8]);
@@ -3924,8 +3858,8 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
     case OA_STAT_FAST_ITERATIONS: *value = (double)c->fast_iters; return OA_OK;
     case OA_STAT_HANDOVER_ENTRIES: *value = c->h_poll ? (double)c->h_poll[2] : 0.0; return OA_OK;
     case OA_STAT_HANDOVER_WAVE_MAX: *value = c->h_poll ? (double)c->h_poll[3] : 0.0; return OA_OK;
-    case OA_STAT_SAFE_RADII: *value = (c->grid_safe && c->safe_ok) ? 1.0 : 0.0; return OA_OK;
-    case OA_STAT_TRI_RING: *value = (c->tri_ring && c->tri_ring_ok) ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_SAFE_RADII: *value = (c->tune.grid_safe && c->safe_ok) ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_TRI_RING: *value = (c->tune.tri_ring && c->tri_ring_ok) ? 1.0 : 0.0; return OA_OK;
     case OA_STAT_METRIC: *value = (double)c->metric; return OA_OK;
     case OA_STAT_PLANE_RANK: *value = (double)c->last_plane_rank; return OA_OK;
     case OA_STAT_ROBUST_LOSS: *value = (double)c->loss; return OA_OK;
@@ -4409,28 +4343,32 @@ const char *const GICP_ONE_DEVICE = ": the GICP metric runs on a single-device c
 const char *const PLANE_ONE_DEVICE = ": the plane metric runs on a single-device context through oa_run / oa_iterate (call oa_set_metric(ctx, OA_METRIC_POINT) for this path)";
 // ... and a quantile of the world's residuals needs the world's histogram, not OA_NSUMS doubles
 const char *const AUTO_ONE_DEVICE = ": a robust scale estimated from the residuals runs on a single-device context through oa_run / oa_iterate (call oa_set_robust_auto(ctx, 0, 0) for this path)";
+// `who` (the split-phase loop, or a loop on a multi-device context) cannot carry these rows: the error that says so, or OA_OK
+int refuse_wide_row(const oa_ctx *c, const char *who, bool estimated_scale_too = true)
+{
+    if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "%s%s", who, PLANE_ONE_DEVICE);
+    if (c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "%s%s", who, GICP_ONE_DEVICE);
+    if (estimated_scale_too && auto_scale(c)) return fail(OA_E_STATE, "%s%s", who, AUTO_ONE_DEVICE);
+    return OA_OK;
+}
 }  // namespace
 
 OA_EXPORT int oa_run_begin(oa_ctx *c, const oa_settings *st)
 {
     if (!c || !st) return fail(OA_E_BAD_ARG, "oa_run_begin: null argument");
     OA_NOT_MULTI(c, "oa_run_begin (the split-phase loop is for one process per GPU)");
-    if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_run_begin%s", PLANE_ONE_DEVICE);
-    if (c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "oa_run_begin%s", GICP_ONE_DEVICE);
-    if (auto_scale(c)) return fail(OA_E_STATE, "oa_run_begin%s", AUTO_ONE_DEVICE);
-    return run_begin(c, st);
+    const int rc = refuse_wide_row(c, "oa_run_begin");
+    return rc ? rc : run_begin(c, st);
 }
 
 OA_EXPORT int oa_iter_partial(oa_ctx *c, double *d_sums)
 {
     if (!c || !d_sums) return fail(OA_E_BAD_ARG, "oa_iter_partial: null argument");
     OA_NOT_MULTI(c, "oa_iter_partial");
-    if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_iter_partial%s", PLANE_ONE_DEVICE);
-    if (c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "oa_iter_partial%s", GICP_ONE_DEVICE);
-    if (auto_scale(c)) return fail(OA_E_STATE, "oa_iter_partial%s", AUTO_ONE_DEVICE);
-    if (!c->loop_active) return fail(OA_E_STATE, "oa_iter_partial outside oa_run_begin/oa_run_end");
-    int rc = use_device(c);
+    int rc = refuse_wide_row(c, "oa_iter_partial");
     if (rc) return rc;
+    if (!c->loop_active) return fail(OA_E_STATE, "oa_iter_partial outside oa_run_begin/oa_run_end");
+    if ((rc = use_device(c))) return rc;
     return iter_partial(c, d_sums, true);
 }
 
@@ -4438,11 +4376,10 @@ OA_EXPORT int oa_iter_finish(oa_ctx *c, const double *d_sums)
 {
     if (!c || !d_sums) return fail(OA_E_BAD_ARG, "oa_iter_finish: null argument");
     OA_NOT_MULTI(c, "oa_iter_finish");
-    if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_iter_finish%s", PLANE_ONE_DEVICE);
-    if (c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "oa_iter_finish%s", GICP_ONE_DEVICE);
-    if (!c->loop_active) return fail(OA_E_STATE, "oa_iter_finish outside oa_run_begin/oa_run_end");
-    int rc = use_device(c);
+    int rc = refuse_wide_row(c, "oa_iter_finish", false);       // (the estimated scale is oa_iter_partial's to refuse)
     if (rc) return rc;
+    if (!c->loop_active) return fail(OA_E_STATE, "oa_iter_finish outside oa_run_begin/oa_run_end");
+    if ((rc = use_device(c))) return rc;
     return iter_finish(c, d_sums);
 }
 
@@ -4463,12 +4400,9 @@ OA_EXPORT int oa_run_end(oa_ctx *c, oa_report *rep)
 OA_EXPORT int oa_run(oa_ctx *c, const oa_settings *st, oa_report *rep)
 {
     if (!c || !st || !rep) return fail(OA_E_BAD_ARG, "oa_run: null argument");
-    if (!c->subs.empty() && c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_run on a multi-device context%s", PLANE_ONE_DEVICE);
-    if (!c->subs.empty() && c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "oa_run on a multi-device context%s", GICP_ONE_DEVICE);
-    if (!c->subs.empty() && auto_scale(c)) return fail(OA_E_STATE, "oa_run on a multi-device context%s", AUTO_ONE_DEVICE);
-    if (!c->subs.empty()) return multi_run(c, st, rep);
-    int rc = run_begin(c, st);
-    if (rc) return rc;
+    int rc;
+    if (!c->subs.empty()) return (rc = refuse_wide_row(c, "oa_run on a multi-device context")) ? rc : multi_run(c, st, rep);
+    if ((rc = run_begin(c, st))) return rc;
     // The whole loop is enqueued ahead of the GPU.  With early exit on, iterations after convergence would still cost
     // three empty launches each (the kernels see DevState.halt and return) -- for a small mesh that converges in 7 of 50
     // iterations, more than the real work.  k_solve_update therefore mirrors the halt flag into a pinned host word,
@@ -4479,7 +4413,7 @@ OA_EXPORT int oa_run(oa_ctx *c, const oa_settings *st, oa_report *rep)
     // about the halt too late to save anything.  Two iterations are always queued, so the GPU never idles.
     // The adaptive grid path (grid_fast_now) needs recent news from the device as well: then the host stays close even
     // when the loop cannot end early.
-    bool poll = c->h_poll && env_int("OA_RUN_POLL", 1) && (st->early_exit || (choose_search(c).plan == PLAN_GRID && c->grid_path == 0));
+    bool poll = loop_polls(c, st);
     const int lag = 2;
     volatile int32_t *progress = c->h_poll;
     for (int it = 0; it < st->iters; ++it) {
@@ -4511,10 +4445,8 @@ OA_EXPORT int oa_iterate(oa_ctx *c, const oa_settings *st, double M_step[16], do
 {
     if (!c || !st) return fail(OA_E_BAD_ARG, "oa_iterate: null argument");
     const bool multi = !c->subs.empty();
-    if (multi && c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "oa_iterate on a multi-device context%s", PLANE_ONE_DEVICE);
-    if (multi && c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "oa_iterate on a multi-device context%s", GICP_ONE_DEVICE);
-    if (multi && auto_scale(c)) return fail(OA_E_STATE, "oa_iterate on a multi-device context%s", AUTO_ONE_DEVICE);
     int rc;
+    if (multi && (rc = refuse_wide_row(c, "oa_iterate on a multi-device context"))) return rc;
     if (c->loop_active && !(c->iterate_mode && same_loop_settings(*st, c->settings))) {
         if (multi) multi_abort(c);
         else { (void)hipSetDevice(c->device); (void)hipStreamSynchronize(c->stream); c->loop_active = false; }
@@ -4624,8 +4556,7 @@ int pose_job_begin(oa_ctx *c, double thresh, int32_t stride, PoseJob &job)
     const oa::DevState &s = c->h_state;
     memcpy(job.pb.mx2, s.mx2, sizeof s.mx2);
     memcpy(job.pb.imx2, s.imx2, sizeof s.imx2);
-    static const float eye16[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
-    job.pb.mx2_identity = (memcmp(s.mx2, eye16, sizeof eye16) == 0 && !env_int("OA_NO_IDENTITY_PATH", 0)) ? 1 : 0;
+    job.pb.mx2_identity = mx2_identity(c, s.mx2);
     job.pb.thresh = thresh;
     job.pb.cut_a = INFINITY; job.pb.cut_b = 0.0;
     double lpw = 0.0;

@@ -1782,6 +1782,41 @@ def test_identity_base_matrix_shortcut_is_bit_exact(monkeypatch):
 
 
 @pytest.mark.gpu
+def test_a_context_keeps_the_knobs_it_was_created_with(monkeypatch):
+    """The OA_* knobs are read when the context is created (csrc/oa_tunables.hpp), not where they are used: an engine created
+    under OA_GRID_PPC=6 builds the coarser vertex grid also when the variable is gone by the time the target arrives.  The knob
+    changes the grid and not the answers."""
+    from object_alignment_amd import synth
+    from object_alignment_amd.engine import IcpEngine
+    rng = np.random.default_rng(31)
+    tgt = rng.uniform(-1, 1, size=(20000, 3)).astype(np.float32)
+    src = (tgt[rng.permutation(20000)[:6000]] + rng.normal(size=(6000, 3)).astype(np.float32) * np.float32(2e-3)).astype(np.float32)
+    mxa = synth.rigid4(synth.rotation_from_rotvec([0.01, -0.02, 0.015]), [0.004, -0.003, 0.002])
+    eye = np.identity(4, dtype=np.float32)
+
+    def use(e):
+        e.set_search_mode("grid")
+        e.set_target(tgt); e.set_source(src); e.set_matrices(mxa, eye)
+        idx, d2, _ = e.nn_search()
+        return e.stat("grid_cells"), idx, d2
+
+    monkeypatch.setenv("OA_GRID_PPC", "6")
+    with IcpEngine(0) as a:
+        monkeypatch.delenv("OA_GRID_PPC")                           # A: created under the knob, used without it
+        cells_a, idx_a, d2_a = use(a)
+    with IcpEngine(0) as b:                                         # B: never saw it
+        cells_b, idx_b, d2_b = use(b)
+    monkeypatch.setenv("OA_GRID_PPC", "6")
+    with IcpEngine(0) as c:                                         # C: created and used under it
+        cells_c, idx_c, d2_c = use(c)
+    print("grid cells: A %g, B %g, C %g" % (cells_a, cells_b, cells_c))
+    assert cells_b > 0
+    assert cells_a == cells_c != cells_b
+    for idx, d2 in ((idx_a, d2_a), (idx_c, d2_c)):
+        assert np.array_equal(idx, idx_b) and np.array_equal(d2, d2_b)
+
+
+@pytest.mark.gpu
 def test_wave_reduction_keeps_the_bits_of_the_shuffle_form():
     """The pair sums of every accumulating kernel go through wave_reduce_scatter (oa_kernels.hpp): v_permlane32_swap /
     v_permlane16_swap halvings and DPP butterflies.  tools/reduce_check.hip holds the form it replaced (ds_bpermute shuffles
