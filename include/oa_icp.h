@@ -326,6 +326,37 @@ int oa_set_robust(oa_ctx *ctx, int loss, double scale);
  * context and oa_run_begin / oa_iter_partial fail with OA_E_STATE (the context stays usable; oa_set_robust_auto(ctx, 0, 0)
  * brings the fixed scale back). */
 int oa_set_robust_auto(oa_ctx *ctx, double quantile, double scale_min);
+
+/* EXTENSION (not in the reference; PCL's and libpointmatcher's reciprocal correspondence filter): keep a pair only if it is
+ * mutual.  Every step pairs each selected source point with its nearest target point; with the check on, the opposite question
+ * is asked too: is this source point also the nearest one to its correspondence?  Where the source reaches beyond the target
+ * (a whole model against a partial scan, two partial scans) every source point outside the overlap pairs with the target's rim;
+ * those pairs are not mutual, and with the check on they no longer drag the fit.
+ *
+ * Definition.  Slot i holds a pair when pair_eval accepts it: dist < thresh, and the normal-angle test when it is on.  Let
+ * b = imx1 @ (mx2 @ co1) be the float32 point that make_pairs emits in B.  It is PairFetch::bx, by, bz, identical in vertex mode
+ * and in surface mode.  Let p_k be the selected source points.  These are the packed src4 rows: the selection after vlist, stride
+ * and sample_voxel.
+ *   - d2(b, p) = d2_metric(b, p) is the project's fp32 difference form with its two fmas.  It is symmetric in its arguments.
+ *   - m = min_k d2(b, p_k) over all selected slots.  A non-finite d2 never wins.
+ *   - The pair is kept iff d2(b, p_i) <= r2 * m, with r2 = (float)(ratio * ratio) and one fp32 multiply.
+ *   - With ratio = 1, the default, this reads "p_i is a nearest selected source point of its own correspondence".  Ties are
+ *     kept.  The result does not depend on index order.
+ *   - ratio lies in [1, 16]; anything else is OA_E_BAD_ARG.
+ * A rejected pair takes no part in anything that pair_eval's verdict feeds: the sums of all three metrics, the weighted kernels,
+ * the automatic robust scale's residuals, oa_make_pairs, and K, mean and std in the report.  oa_nn_search, oa_deviation,
+ * oa_score_poses, and the scoring and refinement inside oa_coarse_align* do not apply the check: their results are the same bits
+ * whether it is set or not.  The check is exact (a box tree over the selected source points in align-local space, built by the
+ * first step after an oa_set_source and valid at every pose) and runs on the device between the search and the accumulation; a
+ * step with the check on runs search -> check -> accumulate (no accumulating search epilogue).  Fewer than 3 surviving pairs is
+ * OA_E_TOO_FEW_PAIRS, as ever; a source whose tree would need more than 6 levels OA_E_CAPACITY.  on == 0 (the default) changes
+ * nothing: the same kernels, the same bits.  The setting survives uploads and oa_set_matrices; changing it ends a running
+ * oa_iterate sequence, as oa_set_robust does.
+ * Single-device contexts holding the whole selection, oa_run / oa_iterate / oa_make_pairs: a context that holds only a shard
+ * cannot see the other shards' source points -- with the check on, loops and oa_make_pairs of a multi-device context,
+ * oa_run_begin / oa_iter_partial, and any loop over a source uploaded with shard_count > 1 fail with OA_E_STATE (the context
+ * stays usable; oa_set_reciprocal(ctx, 0, 1) brings the plain pairs back). */
+int oa_set_reciprocal(oa_ctx *ctx, int on, double ratio);
 /* EXTENSION: one weight per source vertex (host, float32, n_verts as uploaded with oa_set_source; finite and >= 0), gathered
  * into the selection's order -- "trust this region less", where vlist can only say yes or no.  w == NULL switches the weights
  * off (every w_vertex = 1); a new source upload forgets them.  OA_E_STATE before oa_set_source; OA_E_BAD_ARG for a count other
@@ -391,6 +422,10 @@ int oa_reset_seeds(oa_ctx *ctx);
 #define OA_STAT_TARGET_NORMALS  34   /* 1 when a vertex-mode target has normals installed (oa_set_target_normals, oa_set_normals, an estimate) */
 #define OA_STAT_TARGET_FEATURES 35   /* 1 when oa_target_fpfh(keep) left descriptors resident */
 #define OA_STAT_MESH_PSEUDONORMALS 36 /* 1 when the mesh's pseudo-normals are built (oa_deviation, oa_get_mesh_pseudonormals); a new upload forgets them */
+#define OA_STAT_RECIPROCAL      37   /* 1 when oa_set_reciprocal is on */
+#define OA_STAT_RECIPROCAL_RATIO 38  /* its ratio */
+#define OA_STAT_RECIP_REJECTED  39   /* pairs of the last step (loop, oa_iterate or oa_make_pairs) that passed everything else and failed the
+                                      * reciprocal check; 0 when the check is off, and after oa_set_source or oa_set_reciprocal until a step runs */
 #define OA_STAT_ENQUEUED_CHILD  1000   /* + i: the same count for child i alone */
 int oa_get_stat(oa_ctx *ctx, int what, double *value);
 /* why the exchange is what it is (AUTO's reason for not taking RCCL, librccl's error, "RCCL was aborted: ..."), or "" */

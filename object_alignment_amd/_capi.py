@@ -42,6 +42,9 @@ OA_FPFH_DIM = 33
 OA_FEAT_TOO_FEW_PAIRS = 1
 OA_FEAT_NO_POSE = 2
 OA_STAT_MESH_PSEUDONORMALS = 36
+OA_STAT_RECIPROCAL = 37
+OA_STAT_RECIPROCAL_RATIO = 38
+OA_STAT_RECIP_REJECTED = 39
 
 # every symbol include/oa_icp.h declares (tests check that the library exports all of them)
 SYMBOLS = [
@@ -61,6 +64,7 @@ SYMBOLS = [
     "oa_coarse_align_poses", "oa_target_fpfh", "oa_match_features", "oa_feature_candidates",
     "oa_voxel_downsample",
     "oa_deviation", "oa_get_mesh_pseudonormals",
+    "oa_set_reciprocal",
 ]
 
 
@@ -216,6 +220,7 @@ def load(experiments: bool = False):
                                       C.POINTER(VoxelReport)]
     L.oa_deviation.argtypes = [vp, C.POINTER(DeviationSettings), dp, dp, fp, ip, C.POINTER(C.c_int8), ip, C.POINTER(DeviationReport)]
     L.oa_get_mesh_pseudonormals.argtypes = [vp, fp, fp]
+    L.oa_set_reciprocal.argtypes = [vp, C.c_int, C.c_double]
     _libs[experiments] = L
     return L
 

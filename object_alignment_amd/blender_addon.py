@@ -74,12 +74,17 @@ if bpy is not None:
             name="ICP Robust Quantile", description="Take the robust scale from this quantile of each step's residuals (0.5 = the median); 0 = fixed scale", default=0.0, min=0, max=1)
         icp_robust_scale_min: FloatProperty(
             name="ICP Robust Scale Floor", description="Smallest robust scale (world units) an estimated scale may fall to; 0 = the target translation", default=0.0, min=0, max=20)
+        icp_reciprocal: BoolProperty(
+            name="ICP Reciprocal Pairs", description="Keep a pair only if it is mutual: for an object that reaches beyond the one it is aligned to (a whole model onto a partial scan)",
+            default=False)
+        icp_reciprocal_ratio: FloatProperty(
+            name="ICP Reciprocal Ratio", description="1 = strictly mutual; larger keeps a pair whose point is within this multiple of the nearest distance", default=1.0, min=1, max=16)
 
         def draw(self, context):
             col = self.layout.column()
             for name in ("icp_iterations", "redraw_frequency", "sample_fraction", "min_start", "target_d", "use_target",
                          "take_m_with", "align_meth", "icp_metric", "icp_robust_loss", "icp_robust_scale", "icp_robust_quantile",
-                         "icp_robust_scale_min"):
+                         "icp_robust_scale_min", "icp_reciprocal", "icp_reciprocal_ratio"):
                 col.prop(self, name)
 
     class VIEW3D_PT_object_alignment(Panel):
@@ -96,7 +101,8 @@ if bpy is not None:
             prefs = _addon_prefs()
             if prefs is not None:
                 box = self.layout.box()
-                for name in ("icp_iterations", "sample_fraction", "min_start", "target_d", "use_target"):
+                for name in ("icp_iterations", "sample_fraction", "min_start", "target_d", "use_target", "icp_reciprocal",
+                             "icp_reciprocal_ratio"):
                     box.prop(prefs, name)
 
     def _addon_prefs():

@@ -63,9 +63,10 @@ __device__ __forceinline__ unsigned bvh_spread10(unsigned v)
     return v;
 }
 
-// Morton key of a primitive's centre (vertex: the point; triangle: centre of its bounding box)
+// Morton key of a primitive's centre (vertex: the point; triangle: centre of its bounding box).  xyz: rows of `stride` floats
+// (the target: 3; the packed source rows of the reciprocal check's tree, oa_recip.hpp: 4)
 template <bool TRI>
-__global__ void k_bvh_keys(const float *__restrict__ xyz, const float4 *__restrict__ tri9, int n, float lx, float ly,
+__global__ void k_bvh_keys(const float *__restrict__ xyz, int stride, const float4 *__restrict__ tri9, int n, float lx, float ly,
                            float lz, float sx, float sy, float sz, unsigned *__restrict__ keys, int *__restrict__ ids)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -78,7 +79,7 @@ __global__ void k_bvh_keys(const float *__restrict__ xyz, const float4 *__restri
         cy = 0.5f * (fminf(fminf(a[1], b[1]), c[1]) + fmaxf(fmaxf(a[1], b[1]), c[1]));
         cz = 0.5f * (fminf(fminf(a[2], b[2]), c[2]) + fmaxf(fmaxf(a[2], b[2]), c[2]));
     } else {
-        cx = xyz[3ll * i]; cy = xyz[3ll * i + 1]; cz = xyz[3ll * i + 2];
+        cx = xyz[(long long)stride * i]; cy = xyz[(long long)stride * i + 1]; cz = xyz[(long long)stride * i + 2];
     }
     const float fx = fminf(fmaxf((cx - lx) * sx, 0.f), 1023.f), fy = fminf(fmaxf((cy - ly) * sy, 0.f), 1023.f),
                 fz = fminf(fmaxf((cz - lz) * sz, 0.f), 1023.f);      // NaN -> 0 through fmaxf
@@ -89,7 +90,7 @@ __global__ void k_bvh_keys(const float *__restrict__ xyz, const float4 *__restri
 // sorted primitive images.  vertex: float4 {x, y, z, bits(original index)}; triangle: the tri9 image with the original
 // index in the second lane of its third float4.  Slots past n are NaN (never selected) with index IDX_NONE.
 template <bool TRI>
-__global__ void k_bvh_gather(const float *__restrict__ xyz, const float4 *__restrict__ tri9, const int *__restrict__ order,
+__global__ void k_bvh_gather(const float *__restrict__ xyz, int stride, const float4 *__restrict__ tri9, const int *__restrict__ order,
                              int n, int n_pad, float4 *__restrict__ prims)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -108,7 +109,8 @@ __global__ void k_bvh_gather(const float *__restrict__ xyz, const float4 *__rest
     } else {
         if (j < n) {
             const int v = order[j];
-            prims[j] = make_float4(xyz[3ll * v], xyz[3ll * v + 1], xyz[3ll * v + 2], __uint_as_float((uint32_t)v));
+            const long long o = (long long)stride * v;
+            prims[j] = make_float4(xyz[o], xyz[o + 1], xyz[o + 2], __uint_as_float((uint32_t)v));
         } else {
             prims[j] = make_float4(NAN, NAN, NAN, __uint_as_float(IDX_NONE));
         }

@@ -31,6 +31,7 @@
 #define OA_SIG_MATCH_FEATURES const float *, const float *, const float *, int, int, int, unsigned long long *, unsigned long long *, float *
 #define OA_SIG_TRIPLE_POSES const int *, const int *, int, const int *, int, const float4 *, const float *, Mat4f, Mat4f, Mat4d, double, double, float *, int *
 #define OA_SIG_AFFINE_SOLVE const double *, const double *, int, long long, int, int, double *, double *
+#define OA_SIG_RECIP_CHECK const DevState *, const float4 *, int, const float *, const unsigned long long *, const float4 *, const float4 *, NormalTest, const float *, BvhParams, const float4 *, const float4 *, float, unsigned char *, unsigned *
 #define OA_SIG_NN_MFMA const DevState *, const float4 *, const float4 *, const half8 *, const float4 *, int, double, unsigned long long *
 
 // X = `extern` (host unit) or empty (the family's own unit)
@@ -100,6 +101,9 @@
     OA_K(X, k_affine_solve, OA_SIG_AFFINE_SOLVE, AFF_MAXD, false) OA_K(X, k_affine_solve, OA_SIG_AFFINE_SOLVE, 16, true) \
     OA_K(X, k_affine_solve, OA_SIG_AFFINE_SOLVE, 32, true) OA_K(X, k_affine_solve, OA_SIG_AFFINE_SOLVE, 64, true)
 
+// ---- the reciprocal check: one wave per slot through the source's box tree (oa_recip.hpp): oa_fam_recip.hip -----------
+#define OA_FAMILY_RECIP(X) OA_K(X, k_recip_check, OA_SIG_RECIP_CHECK, false) OA_K(X, k_recip_check, OA_SIG_RECIP_CHECK, true)
+
 // ---- experiments (OA_EXPERIMENTS only): oa_fam_exp.hip --------------------------------------------------------------
 #define OA_FAMILY_EXP(X)                                                                                                \
     OA_K(X, k_nn_search_filtered, OA_SIG_NN_FILTERED, 1, 64) OA_K(X, k_nn_search_filtered, OA_SIG_NN_FILTERED, 2, 64)   \
@@ -128,6 +132,7 @@ OA_FAMILY_POSE(extern)
 OA_FAMILY_KNN(extern)
 OA_FAMILY_FEAT(extern)
 OA_FAMILY_AFFINE(extern)
+OA_FAMILY_RECIP(extern)
 #if defined(OA_EXPERIMENTS)
 OA_FAMILY_EXP(extern)
 OA_FAMILY_EXP_R8(extern)

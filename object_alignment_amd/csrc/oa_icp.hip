@@ -424,6 +424,15 @@ struct oa_ctx {
     uint32_t *d_rkeys = nullptr;     // one residual key per slot (k_residual_keys), allocated when a loop with the setting on begins
     uint32_t *d_sel_hist = nullptr;  // the radix select's SEL_LEVELS histograms
     double last_robust_c = 0.0;      // OA_STAT_ROBUST_SCALE: the c the last step used
+    // oa_set_reciprocal: keep a pair only if it is mutual (oa_recip.hpp; survives uploads and oa_set_matrices)
+    bool recip_on = false;
+    double recip_ratio = 1.0;
+    int src_shards = 1;              // shard_count of the last oa_set_source: a shard cannot see the other shards' source points
+    oa::BvhParams sbvh{};            // the box tree over the selected source points (align-local, primitive index = slot) ...
+    float4 *d_sbvh_box = nullptr, *d_sbvh_prims = nullptr;
+    bool sbvh_ok = false;            // ... built by the first step with the check on, kept until the next oa_set_source
+    unsigned char *d_recip_ok = nullptr;   // k_recip_check's verdict, one byte per slot
+    unsigned *d_recip_count = nullptr;     // its counters (RECIP_COUNT_WORDS): word 2 = slots the last step rejected
     double pivot[3] = { 0, 0, 0 };
     // launch geometry for k_nn_search
     int n_splits = 1, acc_blocks = 1;
@@ -704,8 +713,8 @@ int tri_ring_lazy(oa_ctx *c, bool counting)
     return c->tri_iters > TRI_RING_LAZY_ITERS ? build_tri_ring(c) : OA_OK;
 }
 int build_bvh(oa_ctx *c, bool tri);
-int build_bvh_arrays(oa_ctx *c, bool tri, int n, const double frame_lo[3], const double frame_hi[3], oa::BvhParams &bp, float4 *&d_box,
-                     float4 *&d_prims, bool &ok);
+int build_bvh_arrays(oa_ctx *c, bool tri, const float *d_xyz, int stride, int n, const double frame_lo[3], const double frame_hi[3],
+                     oa::BvhParams &bp, float4 *&d_box, float4 *&d_prims, bool &ok);
 int scan_counts(oa_ctx *c, const int *d_counts, int n, long long *d_off, DevTmp<char> &tmp);
 
 // one wave per query: 4 queries per workgroup, workgroups loop when there are more queries than that
@@ -721,6 +730,87 @@ oa::NormalTest normal_test(const oa_ctx *c)
     oa::NormalTest nrm{};
     if (c->normals_on) { nrm.src_n = c->d_src_n; nrm.tgt_n = c->surface ? nullptr : c->d_tgt_n; nrm.cos_min = c->cos_min; }
     return nrm;
+}
+
+// what pair_fetch's callers behind a search pass on: the normal-angle test and, RECIP (oa_set_reciprocal on), k_recip_check's verdict
+template <bool RECIP>
+oa::PairTest<RECIP> pair_test(const oa_ctx *c)
+{
+    oa::PairTest<RECIP> nrm{};
+    static_cast<oa::NormalTest &>(nrm) = normal_test(c);
+    if constexpr (RECIP) nrm.recip_ok = c->d_recip_ok;
+    return nrm;
+}
+
+// oa_set_reciprocal: what a step with the check on needs, before its loop starts (allocations, and the tree build waits for the
+// stream): the verdict bytes, the counters, and -- once per oa_set_source -- the box tree over the selected source points in
+// align-local space, inside the box of their finite coordinates.  The pose never enters: oa_set_matrices does not touch it.
+// k_recip_check's counters back to zero, and the host waits: whatever stream the next step runs on finds them cleared.  Called
+// with no step in flight (a new source, a changed setting, the allocation): OA_STAT_RECIP_REJECTED never speaks of an older one
+int recip_clear_count(oa_ctx *c)
+{
+    if (!c->d_recip_count) return OA_OK;
+    HIPCHK(hipMemsetAsync(c->d_recip_count, 0, sizeof(unsigned) * oa::RECIP_COUNT_WORDS, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
+int ensure_recip(oa_ctx *c)
+{
+    if (!c->recip_on) return OA_OK;
+    if (!c->d_recip_count) {                                        // (whatever ns is: an empty selection still reads the stat)
+        HIPCHK(dev_malloc(&c->d_recip_count, sizeof(unsigned) * oa::RECIP_COUNT_WORDS));
+        const int rcc = recip_clear_count(c);
+        if (rcc) return rcc;
+    }
+    if (c->ns <= 0) return OA_OK;                                   // an empty selection: no slot, no verdict, no tree -- and no launch (launch_recip)
+    if (!c->d_recip_ok) HIPCHK(dev_malloc(&c->d_recip_ok, (size_t)c->ns));
+    if (c->sbvh_ok) return OA_OK;
+    dev_free(c->d_sbvh_box); dev_free(c->d_sbvh_prims);
+    const int nb = oa::RECIP_FRAME_BLOCKS;
+    DevTmp<float> d_bb;
+    HIPCHK(d_bb.alloc(6 * (size_t)nb));
+    hipLaunchKernelGGL(oa::k_recip_frame, dim3(nb), dim3(256), 0, c->stream, (const float4 *)c->d_src4, c->ns, d_bb.p);
+    HIPCHK(hipGetLastError());
+    std::vector<float> bb(6 * (size_t)nb);
+    int rc = read_small(c, bb.data(), d_bb.p, sizeof(float) * bb.size());
+    if (rc) return rc;
+    float l[3] = { INFINITY, INFINITY, INFINITY }, h[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (int b = 0; b < nb; ++b)
+        for (int a = 0; a < 3; ++a) { l[a] = std::min(l[a], bb[6 * (size_t)b + a]); h[a] = std::max(h[a], bb[6 * (size_t)b + 3 + a]); }
+    double lo[3] = { 0.0, 0.0, 0.0 }, hi[3] = { 0.0, 0.0, 0.0 };
+    for (int a = 0; a < 3; ++a) if (l[a] <= h[a]) { lo[a] = l[a]; hi[a] = h[a]; }     // (no finite coordinate: any frame will do)
+    bool ok = false;
+    if ((rc = build_bvh_arrays(c, false, (const float *)c->d_src4, 4, c->ns, lo, hi, c->sbvh, c->d_sbvh_box, c->d_sbvh_prims, ok))) return rc;
+    if (!ok) return fail(OA_E_CAPACITY, "oa_set_reciprocal: the source's box tree would need more than %d levels", oa::BVH_MAX_LEVELS);
+    c->sbvh_ok = true;
+    return OA_OK;
+}
+
+// search -> THIS -> the accumulation (or k_residual_keys first): one wave per slot, the verdict bytes and the step's count.
+// metric_n: the pair_fetch<.., METRIC_N> of the accumulation that follows (the plane and GICP metrics; never the emitting one)
+int launch_recip(oa_ctx *c, bool metric_n)
+{
+    if (c->ns <= 0) return OA_OK;                                   // no slot to judge: nothing is allocated for it either (ensure_recip)
+    const oa::NormalTest nrm = normal_test(c);                      // (without the verdict: this launch forms it)
+    auto *kern = metric_n ? oa::k_recip_check<true> : oa::k_recip_check<false>;
+    const unsigned blocks = (unsigned)std::max(1, std::min((c->ns + oa::RECIP_WPB - 1) / oa::RECIP_WPB, c->n_cu * 16));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(oa::RECIP_WPB * 64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->ns,
+                       (const float *)c->d_tgt_xyz, (const unsigned long long *)c->d_keys,
+                       c->surface ? (const float4 *)nullptr : (const float4 *)c->d_win, c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm,
+                       c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n, c->sbvh, (const float4 *)c->d_sbvh_box,
+                       (const float4 *)c->d_sbvh_prims, (float)(c->recip_ratio * c->recip_ratio), c->d_recip_ok, c->d_recip_count);
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+
+// the check needs every selected source point: a context that holds only a shard cannot see the other shards' 
+const char *const RECIP_ONE_DEVICE = ": the reciprocal check needs every selected source point on one device: it runs on a single-device context through oa_run / oa_iterate / oa_make_pairs (call oa_set_reciprocal(ctx, 0, 1) for this path)";
+int refuse_recip_shard(const oa_ctx *c, const char *who)
+{
+    if (c->recip_on && (c->parent || c->src_shards > 1))
+        return fail(OA_E_STATE, "%s with the reciprocal check on needs the whole selection on one context: this one holds a shard (upload shard 0 of 1, or call oa_set_reciprocal(ctx, 0, 1))", who);
+    return OA_OK;
 }
 
 // acc: a whole-shard search of the loop that also takes the pair test and the sums (k_bvh_search<TRI, true>)
@@ -865,8 +955,8 @@ SearchChoice choose_search(const oa_ctx *c)
         s.accept_front = c->surface && c->tune.tri_split && c->seeded && !s.dual;
     }
     // (the plane and GICP metrics have no accumulating search epilogue: search, then k_pair_accumulate_plane / _gicp -- as with
-    //  fused_acc off; nor does a weighted step: no search epilogue knows about weights)
-    if (!c->tune.fused_acc || !c->loop_active || c->ns <= 0 || plane_row_metric(c) || weighted(c)) return s;
+    //  fused_acc off; nor does a weighted step: no search epilogue knows about weights -- nor about the reciprocal check)
+    if (!c->tune.fused_acc || !c->loop_active || c->ns <= 0 || plane_row_metric(c) || weighted(c) || c->recip_on) return s;
     // (the accumulating tree search needs twice the registers of the plain one: worth it while the shard is small enough
     //  that occupancy does not matter -- 12k queries against 1M vertices: 58 us fused, 47 us search + accumulate)
     if (s.kind == SEARCH_TREE) s.plan = c->ns <= c->tune.tree_acc_max ? PLAN_TREE : PLAN_PLAIN;
@@ -1098,11 +1188,13 @@ int launch_nn(oa_ctx *c, const SearchChoice &s, bool acc)
 inline int plane_threads(const oa_ctx *c) { return c->ns >= 262144 ? oa::PLANE_THREADS : 256; }
 inline int plane_blocks(const oa_ctx *c) { const int t = plane_threads(c); return std::max(1, (c->ns + t - 1) / t); }
 
-int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
+// RECIP: every arm's variant that reads k_recip_check's verdict (oa_set_reciprocal on); <false> launches what it always has
+template <bool RECIP>
+int launch_accumulate_as(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
 {
     if (!c->surface) c->win_seeds = true;                          // (the winner records of this pass seed the next search)
     oa::PairOut po{};
-    const oa::NormalTest nrm = normal_test(c);
+    const oa::PairTest<RECIP> nrm = pair_test<RECIP>(c);
     // the leading arguments of every kernel that opens with pair_fetch (oa_kernels.hpp); each arm adds its own behind them
     float4 *win = c->surface ? (float4 *)nullptr : c->d_win;
     const float4 *tri9 = c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr;
@@ -1117,38 +1209,47 @@ int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
     const float *w_slot = c->d_w;
     if (emit) {
         po.valid = c->d_valid; po.b = c->d_b; po.dist = c->d_dist; po.nn_idx = nn_idx; po.nn_d2 = nn_d2; po.perm = c->d_perm;
-        launch(oa::k_pair_accumulate<true>, c->acc_blocks, oa::ACC_THREADS, c->d_partials, po, (unsigned long long *)nullptr);
+        launch(oa::k_pair_accumulate<true, RECIP>, c->acc_blocks, oa::ACC_THREADS, c->d_partials, po, (unsigned long long *)nullptr);
     } else if (c->metric == OA_METRIC_PLANE) {
-        auto *kern = weighted(c) ? oa::k_pair_accumulate_plane<true> : oa::k_pair_accumulate_plane<false>;
+        auto *kern = weighted(c) ? oa::k_pair_accumulate_plane<true, RECIP> : oa::k_pair_accumulate_plane<false, RECIP>;
         launch(kern, plane_blocks(c), plane_threads(c), plane_tn, w_slot, c->d_partials, stamp_w);
     } else if (c->metric == OA_METRIC_GICP) {
         // (begin_loop refuses an estimated scale under this metric: the search always ends here)
-        auto *kern = weighted(c) ? oa::k_pair_accumulate_gicp<true> : oa::k_pair_accumulate_gicp<false>;
+        auto *kern = weighted(c) ? oa::k_pair_accumulate_gicp<true, RECIP> : oa::k_pair_accumulate_gicp<false, RECIP>;
         launch(kern, plane_blocks(c), plane_threads(c), plane_tn, (const float *)c->d_src_n, w_slot, c->d_partials, stamp);
     } else if (weighted(c)) {
         static_assert(oa::WEIGHTED_THREADS == oa::PLANE_THREADS, "plane_threads / plane_blocks size both launches");
-        launch(oa::k_pair_accumulate_weighted, plane_blocks(c), plane_threads(c), w_slot, c->d_partials, stamp_w);
+        launch(oa::k_pair_accumulate_weighted<RECIP>, plane_blocks(c), plane_threads(c), w_slot, c->d_partials, stamp_w);
     } else if (canon_blocks(c) > 0) {
-        launch(oa::k_pair_accumulate_canon, canon_blocks(c), canon_threads(c), canon_lanes(c), c->d_partials, stamp);
+        launch(oa::k_pair_accumulate_canon<RECIP>, canon_blocks(c), canon_threads(c), canon_lanes(c), c->d_partials, stamp);
     } else {
-        launch(oa::k_pair_accumulate<false>, c->acc_blocks, oa::ACC_THREADS, c->d_partials, po, stamp);
+        launch(oa::k_pair_accumulate<false, RECIP>, c->acc_blocks, oa::ACC_THREADS, c->d_partials, po, stamp);
     }
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
+int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
+{
+    return c->recip_on ? launch_accumulate_as<true>(c, emit, nn_idx, nn_d2) : launch_accumulate_as<false>(c, emit, nn_idx, nn_d2);
+}
 
 // oa_set_robust_auto: between the search and the weighted accumulation of a loop step, the loss's scale from the residuals of
 // the pairs that accumulation is about to form -- six launches, all on the loop's stream (oa_kernels.hpp, k_residual_keys)
-int launch_robust_scale(oa_ctx *c)
+template <bool RECIP>
+void launch_residual_keys(oa_ctx *c)
 {
-    const oa::NormalTest nrm = normal_test(c);
+    const oa::PairTest<RECIP> nrm = pair_test<RECIP>(c);
     // (launch_accumulate's leading arguments and selections, read-only and without prev; <false> never reads plane_tn)
-    auto *kern = c->metric == OA_METRIC_PLANE ? oa::k_residual_keys<true> : oa::k_residual_keys<false>;
+    auto *kern = c->metric == OA_METRIC_PLANE ? oa::k_residual_keys<true, RECIP> : oa::k_residual_keys<false, RECIP>;
     hipLaunchKernelGGL(kern, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
                        (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, (const unsigned long long *)c->d_keys,
                        c->surface ? (const float4 *)nullptr : (const float4 *)c->d_win, c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm,
                        c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n, (const float *)c->d_w, c->d_rkeys, c->d_sel_hist,
                        &c->d_state->t_acc_start);
+}
+int launch_robust_scale(oa_ctx *c)
+{
+    if (c->recip_on) launch_residual_keys<true>(c); else launch_residual_keys<false>(c);
     const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
     for (int level = 0; level < oa::SEL_LEVELS; ++level) {
         if (level > 0)
@@ -1204,6 +1305,7 @@ int launch_search_accumulate(oa_ctx *c, bool timed, oa::RowSel &sel, bool &fused
         c->ev_used++;
     }
     if (!fused) {
+        if (c->recip_on && (rc = launch_recip(c, plane_row_metric(c)))) return rc;
         if (auto_scale(c) && (rc = launch_robust_scale(c))) return rc;
         if ((rc = launch_accumulate(c, false, nullptr, nullptr))) return rc;
         sel = plain_rows(c);
@@ -1362,8 +1464,10 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
             return fail(OA_E_CAPACITY, "the GICP metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->ns);
     } else if (weighted(c) && (long long)c->ns > (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS)
         return fail(OA_E_CAPACITY, "a weighted loop takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS, c->ns);
+    if ((rc = refuse_recip_shard(c, "a loop"))) return rc;
     if ((rc = use_device(c))) return rc;
     if ((rc = ensure_common(c))) return rc;
+    if ((rc = ensure_recip(c))) return rc;                          // (the source tree: before the loop starts, never inside it)
     if ((rc = ensure_history(c, iters == ITERATE_OPEN ? ITERATE_RING : iters))) return rc;   // oa_iterate: a small ring
     if (auto_scale(c)) {                                          // the selection's buffers; its histograms start (and are kept) at zero
         if (!c->d_rkeys) HIPCHK(dev_malloc(&c->d_rkeys, sizeof(uint32_t) * (size_t)std::max(1, c->ns)));
@@ -2298,6 +2402,7 @@ OA_EXPORT void oa_destroy(oa_ctx *c)
     OA_FREE(d_bvh_box); OA_FREE(d_bvh_prims); OA_FREE(d_tbvh_box); OA_FREE(d_tbvh_prims);
     OA_FREE(d_tri9); OA_FREE(d_tcell_start); OA_FREE(d_tcell_rec); OA_FREE(d_tri_ring); OA_FREE(d_tfine_table); OA_FREE(d_tfine_rec);
     OA_FREE(d_sel); OA_FREE(d_src_n); OA_FREE(d_tgt_n); OA_FREE(d_tgt_feat); OA_FREE(d_w); OA_FREE(d_rkeys); OA_FREE(d_sel_hist); OA_FREE(d_src4o); OA_FREE(d_perm);
+    OA_FREE(d_sbvh_box); OA_FREE(d_sbvh_prims); OA_FREE(d_recip_ok); OA_FREE(d_recip_count);
     OA_FREE(d_tris); OA_FREE(d_pn_face); OA_FREE(d_pn_vertex); OA_FREE(d_pn_edge);
 #undef OA_FREE
     if (c->h_hist_map) (void)hipHostFree(c->h_hist_map);
@@ -2677,13 +2782,14 @@ int build_bvh(oa_ctx *c, bool tri)
     dev_free(d_box); dev_free(d_prims);
     const int n = tri ? c->n_tris : c->nt;
     if (!c->filter_ok || c->grid_mode == 0 || n < 1) return OA_OK;
-    return build_bvh_arrays(c, tri, n, c->bb_lo, c->bb_hi, bp, d_box, d_prims, ok);
+    return build_bvh_arrays(c, tri, c->d_tgt_xyz, 3, n, c->bb_lo, c->bb_hi, bp, d_box, d_prims, ok);
 }
 
 // the tree itself over n primitives: level sizes, Morton order inside the frame [lo, hi], primitive images, boxes.  ok stays
-// false (and nothing is allocated) when the tree would need more than BVH_MAX_LEVELS levels.
-int build_bvh_arrays(oa_ctx *c, bool tri, int n, const double frame_lo[3], const double frame_hi[3], oa::BvhParams &bp, float4 *&d_box,
-                     float4 *&d_prims, bool &ok)
+// false (and nothing is allocated) when the tree would need more than BVH_MAX_LEVELS levels.  Vertices: rows of `stride` floats
+// at d_xyz (the target: 3; the packed source rows: 4); triangles: c->d_tri9.
+int build_bvh_arrays(oa_ctx *c, bool tri, const float *d_xyz, int stride, int n, const double frame_lo[3], const double frame_hi[3],
+                     oa::BvhParams &bp, float4 *&d_box, float4 *&d_prims, bool &ok)
 {
     bp = oa::BvhParams{};
     bp.n_prims = n;
@@ -2713,18 +2819,18 @@ int build_bvh_arrays(oa_ctx *c, bool tri, int n, const double frame_lo[3], const
     DevTmp<int> v_in, v_out;
     HIPCHK(k_in.alloc((size_t)n)); HIPCHK(v_in.alloc((size_t)n)); HIPCHK(v_out.alloc((size_t)n));
     const dim3 blk(256), grd((unsigned)((n + 255) / 256));
-    if (tri) hipLaunchKernelGGL(oa::k_bvh_keys<true>, grd, blk, 0, c->stream, (const float *)c->d_tgt_xyz, (const float4 *)c->d_tri9,
+    if (tri) hipLaunchKernelGGL(oa::k_bvh_keys<true>, grd, blk, 0, c->stream, d_xyz, stride, (const float4 *)c->d_tri9,
                                 n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
-    else hipLaunchKernelGGL(oa::k_bvh_keys<false>, grd, blk, 0, c->stream, (const float *)c->d_tgt_xyz, (const float4 *)nullptr,
+    else hipLaunchKernelGGL(oa::k_bvh_keys<false>, grd, blk, 0, c->stream, d_xyz, stride, (const float4 *)nullptr,
                             n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
     HIPCHK(hipGetLastError());
     { const int rcs = sort_order_bits(c, k_in.p, v_out.p, (size_t)n, 30); if (rcs) return rcs; }
     HIPCHK(dev_malloc(&d_prims, sizeof(float4) * (tri ? 3 : 1) * (size_t)n_pad));
     HIPCHK(dev_malloc(&d_box, sizeof(float4) * 2 * (size_t)total));
     const dim3 grd_pad((unsigned)((n_pad + 255) / 256));
-    if (tri) hipLaunchKernelGGL(oa::k_bvh_gather<true>, grd_pad, blk, 0, c->stream, (const float *)c->d_tgt_xyz, (const float4 *)c->d_tri9,
+    if (tri) hipLaunchKernelGGL(oa::k_bvh_gather<true>, grd_pad, blk, 0, c->stream, d_xyz, stride, (const float4 *)c->d_tri9,
                                 (const int *)v_out.p, n, n_pad, d_prims);
-    else hipLaunchKernelGGL(oa::k_bvh_gather<false>, grd_pad, blk, 0, c->stream, (const float *)c->d_tgt_xyz, (const float4 *)nullptr,
+    else hipLaunchKernelGGL(oa::k_bvh_gather<false>, grd_pad, blk, 0, c->stream, d_xyz, stride, (const float4 *)nullptr,
                             (const int *)v_out.p, n, n_pad, d_prims);
     HIPCHK(hipGetLastError());
     const dim3 grd1((unsigned)((bp.cnt[1] + 3) / 4));               // one wave per box
@@ -3291,6 +3397,8 @@ int source_reset(oa_ctx *c, long long count, long long begin, long long n_verts)
     HIPCHK(hipStreamSynchronize(c->stream));
     c->loop_active = false;                                         // an open oa_iterate sequence ends with the old source
     dev_free(c->d_src4); dev_free(c->d_keys); dev_free(c->d_prev); dev_free(c->d_win); dev_free(c->d_wsafe); dev_free(c->d_sel); dev_free(c->d_src_n); dev_free(c->d_w); dev_free(c->d_rkeys);
+    dev_free(c->d_sbvh_box); dev_free(c->d_sbvh_prims); dev_free(c->d_recip_ok); c->sbvh_ok = false;   // (the source tree: a new source forgets it)
+    { const int rcc = recip_clear_count(c); if (rcc) return rcc; }  // ... and the old source's count
     dev_free(c->d_src4o); dev_free(c->d_perm); dev_free(c->d_members); dev_free(c->d_pos);
     c->h_members.clear();
     c->shard_begin = begin;
@@ -3341,6 +3449,7 @@ int set_source_single(oa_ctx *c, const float *xyz, int64_t n_verts, int on_devic
     int rc = use_device(c);
     if (rc) return rc;
     if ((rc = source_reset(c, count, begin, n_verts))) return rc;
+    c->src_shards = shard_count;
     if (n_sel > 0) {
         const float *d_xyz = xyz;
         DevTmp<float> tmp_xyz;
@@ -3655,6 +3764,31 @@ OA_EXPORT int oa_set_robust_auto(oa_ctx *c, double quantile, double scale_min)
     return OA_OK;
 }
 
+OA_EXPORT int oa_set_reciprocal(oa_ctx *c, int on, double ratio)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    if (!(ratio >= 1.0 && ratio <= 16.0)) return fail(OA_E_BAD_ARG, "oa_set_reciprocal: the ratio must be in [1, 16] (1: strictly mutual)");
+    const bool want = on != 0;
+    if (want == c->recip_on && ratio == c->recip_ratio) return OA_OK;
+    // a changed setting ends the running sequence, as oa_set_robust does
+    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
+    else if (c->loop_active) {
+        int rc = use_device(c);
+        if (rc) return rc;
+        if ((rc = fetch_state(c))) return rc;
+        c->loop_active = false;
+    }
+    // (a multi-device parent keeps the setting itself and refuses the loops: its children never see it)
+    c->recip_on = want;
+    c->recip_ratio = ratio;
+    if (c->d_recip_count) {                                         // the last step's count was the old setting's
+        int rc = use_device(c);
+        if (rc) return rc;
+        if ((rc = recip_clear_count(c))) return rc;
+    }
+    return OA_OK;
+}
+
 OA_EXPORT int oa_set_source_weights(oa_ctx *c, const float *w, int64_t n_verts)
 {
     if (!c) return fail(OA_E_BAD_ARG, "null context");
@@ -3843,6 +3977,18 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
         if (!c->loop_active) { const int rcx = exchange_resolve(c); if (rcx) return rcx; }
         if (what == OA_STAT_EXCHANGE) *value = c->xch->mode == OA_EXCHANGE_RCCL ? 1.0 : (c->xch->device_box ? 2.0 : 0.0);
         else *value = (double)exchange_rccl_ranks(c->xch);
+        return OA_OK;
+    }
+    if (what == OA_STAT_RECIPROCAL) { *value = c->recip_on ? 1.0 : 0.0; return OA_OK; }
+    if (what == OA_STAT_RECIPROCAL_RATIO) { *value = c->recip_ratio; return OA_OK; }
+    if (what == OA_STAT_RECIP_REJECTED) {
+        *value = 0.0;
+        if (!c->recip_on || !c->d_recip_count) return OA_OK;
+        int rc = use_device(c);
+        if (rc) return rc;
+        unsigned n = 0;
+        if ((rc = read_small(c, &n, c->d_recip_count + 2, sizeof n))) return rc;
+        *value = (double)n;
         return OA_OK;
     }
     OA_ROUTE_FIRST(c, oa_get_stat(sub, what, value));
@@ -4036,6 +4182,7 @@ OA_EXPORT int oa_nn_search(oa_ctx *c, int64_t *idx, float *d2, double *kernel_ms
 OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A, double *B, int64_t cap, int64_t *K,
                             double dstats[2])
 {
+    if (c && !c->subs.empty() && c->recip_on) return fail(OA_E_STATE, "oa_make_pairs on a multi-device context%s", RECIP_ONE_DEVICE);
     if (c && !c->subs.empty()) {
         // multi-device: every child pairs its shard (its pairs come out in ascending selection position, with that
         // position); the shards are merged back into vlist order on the host.  Statistics: the children's two-pass
@@ -4097,8 +4244,10 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
     if (rc) return rc;
     if (!K || cap < 0 || (cap > 0 && (!A || !B))) return fail(OA_E_BAD_ARG, "oa_make_pairs: bad output arguments");
     if (!(thresh > 0.0)) return fail(OA_E_BAD_THRESH, "thresh must be > 0 (the reference's make_pairs returns None)");
+    if ((rc = refuse_recip_shard(c, "oa_make_pairs"))) return rc;
     if ((rc = use_device(c))) return rc;
     if ((rc = ensure_common(c))) return rc;
+    if ((rc = ensure_recip(c))) return rc;
     *K = 0;
     if (dstats) { dstats[0] = NAN; dstats[1] = NAN; }
     if (c->ns == 0) return OA_OK;
@@ -4120,6 +4269,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
     c->d_pivot0 = 0.0;
     if ((rc = push_state_for_oneshot(c, thresh, true))) return rc;
     if ((rc = launch_nn(c, choose_search(c), false))) return rc;
+    if (c->recip_on && (rc = launch_recip(c, false))) return rc;
     if ((rc = launch_accumulate(c, true, nullptr, nullptr))) return rc;
     if ((rc = launch_reduce(c, c->d_sums, oa::RowSel{ c->acc_blocks, 0, 0 }, false))) return rc;   // (emitting accumulation: k_pair_accumulate<true>)
     if (calc_stats) {
@@ -4131,6 +4281,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
             c->d_pivot0 = s1[oa::S_D] / s1[oa::S_K];
             if ((rc = push_state_for_oneshot(c, thresh, true))) { c->d_pivot0 = 0.0; return rc; }
             rc = launch_nn(c, choose_search(c), false);
+            if (!rc && c->recip_on) rc = launch_recip(c, false);
             if (!rc) rc = launch_accumulate(c, true, nullptr, nullptr);
             if (!rc) rc = launch_reduce(c, c->d_sums, oa::RowSel{ c->acc_blocks, 0, 0 }, false);
             if (rc) { c->d_pivot0 = 0.0; return rc; }
@@ -4346,6 +4497,7 @@ const char *const AUTO_ONE_DEVICE = ": a robust scale estimated from the residua
 // `who` (the split-phase loop, or a loop on a multi-device context) cannot carry these rows: the error that says so, or OA_OK
 int refuse_wide_row(const oa_ctx *c, const char *who, bool estimated_scale_too = true)
 {
+    if (c->recip_on) return fail(OA_E_STATE, "%s%s", who, RECIP_ONE_DEVICE);
     if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "%s%s", who, PLANE_ONE_DEVICE);
     if (c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "%s%s", who, GICP_ONE_DEVICE);
     if (estimated_scale_too && auto_scale(c)) return fail(OA_E_STATE, "%s%s", who, AUTO_ONE_DEVICE);
@@ -4888,7 +5040,7 @@ int knn_tree(oa_ctx *c, KnnTree &t)
     double lo[3], hi[3];
     { const int rcb = target_bbox(c, lo, hi); if (rcb) return rcb; }
     bool ok = false;
-    const int rc = build_bvh_arrays(c, false, c->nt, lo, hi, t.bp, t.own_box, t.own_prims, ok);
+    const int rc = build_bvh_arrays(c, false, c->d_tgt_xyz, 3, c->nt, lo, hi, t.bp, t.own_box, t.own_prims, ok);
     if (rc) return rc;
     if (!ok) return fail(OA_E_CAPACITY, "the target's box tree would need more than %d levels", oa::BVH_MAX_LEVELS);
     t.box = t.own_box; t.prims = t.own_prims;

@@ -1988,6 +1988,14 @@ struct NormalTest {
     const float *tgt_n;     // nt x 3 per target vertex (vertex mode); nullptr in surface mode = geometric face normal
     double cos_min;
 };
+// ... and, for the kernels that open with pair_fetch, the reciprocal check's verdict beside it (oa_set_reciprocal, oa_recip.hpp:
+// k_recip_check): one byte per slot, 0 = the pair is not mutual.  A COMPILE-TIME switch, not a nullable pointer in NormalTest: the
+// extra pointer cost k_pair_accumulate_canon, _plane<false> and k_residual_keys<true> two VGPRs each (and _plane<false> a wave of
+// occupancy) with the check off.  PairTest<false> IS NormalTest: the kernels<.., false> are the ones from before the check.
+struct NormalTestRecip : NormalTest {
+    const unsigned char *recip_ok;
+};
+template <bool RECIP> using PairTest = std::conditional_t<RECIP, NormalTestRecip, NormalTest>;
 
 __device__ __forceinline__ bool normal_angle_ok(const float *imx1, const float *imx2, const float *ns, const float *nt,
                                                 double cos_min)
@@ -2087,7 +2095,8 @@ __device__ __forceinline__ bool pair_eval(const DevState *__restrict__ st, float
 //                   nrm.src_n is set, zeros otherwise.
 //             true  (plane, GICP): tn is the metric's normal -- plane_tn[idx] resp. the face normal, always.
 // f.p is loaded before the IDX_NONE test (the callers use it for a slot without a pair too); a slot without a pair leaves
-// tn, b and dist zero.  Returns pair_eval's verdict.
+// tn, b and dist zero.  Returns pair_eval's verdict -- and, RECIP, false for a slot the reciprocal check rejected
+// (nrm.recip_ok[i] == 0), after everything above: the WRITES side effects are the same, so seeds survive a rejection.
 struct PairFetch {
     float4 p;                   // src4[i]
     unsigned long long key;     // keys[i] as the search left it
@@ -2097,12 +2106,12 @@ struct PairFetch {
     double dist;                // the world-space pair distance
 };
 
-template <bool WRITES, bool METRIC_N>
+template <bool WRITES, bool METRIC_N, bool RECIP = false>
 __device__ __forceinline__ bool pair_fetch(const DevState *__restrict__ st, const float4 *__restrict__ src4, int i,
                                            const float *__restrict__ tgt_xyz,
                                            std::conditional_t<WRITES, unsigned long long, const unsigned long long> *__restrict__ keys,
                                            int *__restrict__ prev, std::conditional_t<WRITES, float4, const float4> *__restrict__ win,
-                                           const float4 *__restrict__ tri9, const NormalTest &nrm,
+                                           const float4 *__restrict__ tri9, const PairTest<RECIP> &nrm,
                                            const float *__restrict__ plane_tn, double thresh, PairFetch &f)
 {
     f.key = keys[i];
@@ -2141,7 +2150,9 @@ __device__ __forceinline__ bool pair_fetch(const DevState *__restrict__ st, cons
         if constexpr (METRIC_N) { f.tn[0] = plane_tn[3ll * idx]; f.tn[1] = plane_tn[3ll * idx + 1]; f.tn[2] = plane_tn[3ll * idx + 2]; }
         else if (nrm.src_n) { f.tn[0] = nrm.tgt_n[3ll * idx]; f.tn[1] = nrm.tgt_n[3ll * idx + 1]; f.tn[2] = nrm.tgt_n[3ll * idx + 2]; }
     }
-    return pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, f.tn, thresh, f.bx, f.by, f.bz, f.dist);
+    const bool valid = pair_eval(st, cx, cy, cz, qx, qy, qz, nrm, i, f.tn, thresh, f.bx, f.by, f.bz, f.dist);
+    if constexpr (RECIP) return valid && nrm.recip_ok[i] != 0;
+    else return valid;
 }
 
 __device__ __forceinline__ void pair_add(double (&acc)[NSUMS], float p_x, float p_y, float p_z, float bx, float by, float bz,
@@ -2291,13 +2302,13 @@ __device__ __forceinline__ void block_store_pair(bool valid, double a0, double a
     }
 }
 
-template <bool EMIT>
+template <bool EMIT, bool RECIP = false>
 __global__ __launch_bounds__(ACC_THREADS) void k_pair_accumulate(const DevState *__restrict__ st,
                                                                  const float4 *__restrict__ src4, int ns,
                                                                  const float *__restrict__ tgt_xyz,
                                                                  unsigned long long *__restrict__ keys,
                                                                  int *__restrict__ prev, float4 *__restrict__ win,
-                                                                 const float4 *__restrict__ tri9, NormalTest nrm,
+                                                                 const float4 *__restrict__ tri9, PairTest<RECIP> nrm,
                                                                  double *__restrict__ partials, PairOut out,
                                                                  unsigned long long *__restrict__ t_acc_start)
 {
@@ -2314,7 +2325,7 @@ __global__ __launch_bounds__(ACC_THREADS) void k_pair_accumulate(const DevState 
     if (!halted) {
         for (int i = blockIdx.x * ACC_THREADS + threadIdx.x; i < ns; i += gridDim.x * ACC_THREADS) {
             PairFetch f;
-            const bool valid = pair_fetch<true, false>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, nullptr, thresh, f);
+            const bool valid = pair_fetch<true, false, RECIP>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, nullptr, thresh, f);
             if (EMIT) {
                 const long long o = out.perm ? out.perm[i] : i;
                 out.valid[o] = valid ? 1 : 0;
@@ -2337,12 +2348,13 @@ __global__ __launch_bounds__(ACC_THREADS) void k_pair_accumulate(const DevState 
 // Launched with the workgroup size the accumulating grid search of this shard uses (256 or 512 threads, oa_icp.hip:
 // canon_threads): the same workgroups, hence the same rows.
 constexpr int CANON_THREADS = 512;
-#if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
+// (RECIP: the variant behind k_recip_check, see PairTest; <false> is the kernel the fused searches are twins of)
+template <bool RECIP = false>
 __global__ __launch_bounds__(CANON_THREADS) void k_pair_accumulate_canon(const DevState *__restrict__ st, const float4 *__restrict__ src4,
                                                                int ns, const float *__restrict__ tgt_xyz,
                                                                unsigned long long *__restrict__ keys, int *__restrict__ prev,
                                                                float4 *__restrict__ win, const float4 *__restrict__ tri9,
-                                                               NormalTest nrm, int L, double *__restrict__ partials,
+                                                               PairTest<RECIP> nrm, int L, double *__restrict__ partials,
                                                                unsigned long long *__restrict__ t_acc_start)
 {
     __shared__ double red[CANON_THREADS / 64][NSUMS];
@@ -2353,12 +2365,11 @@ __global__ __launch_bounds__(CANON_THREADS) void k_pair_accumulate_canon(const D
     const bool mine = (gt - i * L) == 0 && i < ns;
     bool valid = false;
     PairFetch f = {};
-    if (mine) valid = pair_fetch<true, false>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, nullptr, st->thresh, f);
+    if (mine) valid = pair_fetch<true, false, RECIP>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, nullptr, st->thresh, f);
     const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
     block_store_pair(valid, (double)f.p.x - pvx, (double)f.p.y - pvy, (double)f.p.z - pvz, (double)f.bx - pvx, (double)f.by - pvy,
                      (double)f.bz - pvz, f.dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS);
 }
-#endif  // !OA_FAMILY_TU
 
 // ---- weighted steps of the point metric (oa_set_robust / oa_set_source_weights) -----------------------------------------
 // the wave's total of ONE value in every lane: the halving steps of wave_reduce_scatter with both operands the same register
@@ -2403,12 +2414,12 @@ __device__ __forceinline__ void block_store_pair_weighted(bool valid, double w, 
 // dist = the world-space pair distance of pair_eval; w_slot = one weight per slot (nullptr: all 1); the loss and its scale are
 // launch-uniform (DevState).  Its workgroups depend on the shard size alone, so every search mode leaves the same rows.
 constexpr int WEIGHTED_THREADS = 512;
-#if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
+template <bool RECIP = false>
 __global__ __launch_bounds__(WEIGHTED_THREADS) void k_pair_accumulate_weighted(const DevState *__restrict__ st, const float4 *__restrict__ src4,
                                                                int ns, const float *__restrict__ tgt_xyz,
                                                                unsigned long long *__restrict__ keys, int *__restrict__ prev,
                                                                float4 *__restrict__ win, const float4 *__restrict__ tri9,
-                                                               NormalTest nrm, const float *__restrict__ w_slot,
+                                                               PairTest<RECIP> nrm, const float *__restrict__ w_slot,
                                                                double *__restrict__ partials,
                                                                unsigned long long *__restrict__ t_acc_start)
 {
@@ -2420,7 +2431,7 @@ __global__ __launch_bounds__(WEIGHTED_THREADS) void k_pair_accumulate_weighted(c
     double w = 0.0;
     PairFetch f = {};
     if (i < ns) {
-        valid = pair_fetch<true, false>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, nullptr, st->thresh, f);
+        valid = pair_fetch<true, false, RECIP>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, nullptr, st->thresh, f);
         if (valid) {
             w = robust_psi(st->loss, f.dist, st->robust_c);
             if (w_slot) w *= (double)w_slot[i];
@@ -2430,7 +2441,6 @@ __global__ __launch_bounds__(WEIGHTED_THREADS) void k_pair_accumulate_weighted(c
     block_store_pair_weighted(valid, w, (double)f.p.x - pvx, (double)f.p.y - pvy, (double)f.p.z - pvz, (double)f.bx - pvx, (double)f.by - pvy,
                               (double)f.bz - pvz, f.dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS);
 }
-#endif  // !OA_FAMILY_TU
 
 // ---- the point-to-plane metric (oa_set_metric(OA_METRIC_PLANE)): the same pair test, the sums of the plane system ---------
 // The correspondence's normal in align-local space, unit length, fp64: base-local tn -> world with the inverse transpose of
@@ -2537,12 +2547,12 @@ __device__ __forceinline__ void block_store_plane(bool valid, const double (&jj)
 constexpr int PLANE_THREADS = 512;
 constexpr int PLANE_MAX_BLOCKS = 16384;
 #if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
-template <bool WEIGHTED>
+template <bool WEIGHTED, bool RECIP = false>
 __global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_plane(const DevState *__restrict__ st, const float4 *__restrict__ src4,
                                                                int ns, const float *__restrict__ tgt_xyz,
                                                                unsigned long long *__restrict__ keys, int *__restrict__ prev,
                                                                float4 *__restrict__ win, const float4 *__restrict__ tri9,
-                                                               NormalTest nrm, const float *__restrict__ plane_tn,
+                                                               PairTest<RECIP> nrm, const float *__restrict__ plane_tn,
                                                                const float *__restrict__ w_slot, double *__restrict__ partials,
                                                                unsigned long long *__restrict__ t_acc_start)
 {
@@ -2554,7 +2564,7 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_plane(const D
     double nx = 0.0, ny = 0.0, nz = 0.0;
     PairFetch f = {};
     if (i < ns) {
-        valid = pair_fetch<true, true>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, plane_tn, st->thresh, f);
+        valid = pair_fetch<true, true, RECIP>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, plane_tn, st->thresh, f);
         if (valid) valid = plane_normal(st, f.tn, nx, ny, nz);
     }
     const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
@@ -2652,12 +2662,12 @@ __device__ __forceinline__ void block_store_gicp(bool valid, double a0, double a
 // zero or non-finite length drops the pair from the step and from K, as a zero n_b does).  Launched like the plane kernel
 // (plane_threads / plane_blocks).  WEIGHTED: w = w_vertex * psi(res_scale * sqrt(e^T W e)).
 #if !defined(OA_FAMILY_TU)
-template <bool WEIGHTED>
+template <bool WEIGHTED, bool RECIP = false>
 __global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_gicp(const DevState *__restrict__ st, const float4 *__restrict__ src4,
                                                               int ns, const float *__restrict__ tgt_xyz,
                                                               unsigned long long *__restrict__ keys, int *__restrict__ prev,
                                                               float4 *__restrict__ win, const float4 *__restrict__ tri9,
-                                                              NormalTest nrm, const float *__restrict__ plane_tn,
+                                                              PairTest<RECIP> nrm, const float *__restrict__ plane_tn,
                                                               const float *__restrict__ src_n, const float *__restrict__ w_slot,
                                                               double *__restrict__ partials, unsigned long long *__restrict__ t_acc_start)
 {
@@ -2669,7 +2679,7 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_gicp(const De
     double nx = 0.0, ny = 0.0, nz = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
     PairFetch f = {};
     if (i < ns) {
-        valid = pair_fetch<true, true>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, plane_tn, st->thresh, f);
+        valid = pair_fetch<true, true, RECIP>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, plane_tn, st->thresh, f);
         if (valid) valid = plane_normal(st, f.tn, nx, ny, nz);
         if (valid) {
             const double s0 = (double)src_n[3ll * i], s1 = (double)src_n[3ll * i + 1], s2 = (double)src_n[3ll * i + 2];
@@ -2758,12 +2768,12 @@ __device__ __forceinline__ void sel_flush(const uint32_t *bins, uint32_t *__rest
 // pair, NO write to keys, prev or win) and -- PLANE -- plane_normal / plane_row.  rkeys[i] = the bits of (float)residual (point: pair_eval's dist; plane: res_scale |n . (a' - b')|), or
 // RKEY_NONE for a slot without a pair counted in K or with vertex weight 0.  Launched like the accumulation (plane_threads /
 // plane_blocks); stamps the end of the search in its place.
-template <bool PLANE>
+template <bool PLANE, bool RECIP = false>
 __global__ __launch_bounds__(PLANE_THREADS) void k_residual_keys(const DevState *__restrict__ st, const float4 *__restrict__ src4, int ns,
                                                              const float *__restrict__ tgt_xyz,
                                                              const unsigned long long *__restrict__ keys,
                                                              const float4 *__restrict__ win, const float4 *__restrict__ tri9,
-                                                             NormalTest nrm, const float *__restrict__ plane_tn,
+                                                             PairTest<RECIP> nrm, const float *__restrict__ plane_tn,
                                                              const float *__restrict__ w_slot, uint32_t *__restrict__ rkeys,
                                                              uint32_t *__restrict__ hist, unsigned long long *__restrict__ t_acc_start)
 {
@@ -2775,7 +2785,7 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_residual_keys(const DevState 
     uint32_t rkey = RKEY_NONE;
     if (i < ns) {
         PairFetch f;
-        if (pair_fetch<false, PLANE>(st, src4, i, tgt_xyz, keys, nullptr, win, tri9, nrm, plane_tn, st->thresh, f)) {
+        if (pair_fetch<false, PLANE, RECIP>(st, src4, i, tgt_xyz, keys, nullptr, win, tri9, nrm, plane_tn, st->thresh, f)) {
             bool valid = true;
             double res = f.dist;
             if constexpr (PLANE) {

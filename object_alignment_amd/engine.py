@@ -346,6 +346,15 @@ class IcpEngine:
         contexts, run / iterate only.  stat("robust_scale") reads the last step's c back, stat("robust_quantile") the setting."""
         self._chk(self._L.oa_set_robust_auto(self._h, float(quantile), float(scale_min)))
 
+    def set_reciprocal(self, on=True, ratio=1.0):
+        """Keep a pair of a step only if it is mutual: the source point must also be the nearest selected source point of its
+        own correspondence (ratio 1, ties kept), or within `ratio` times that nearest distance (ratio in [1, 16]).  What a whole
+        model against a partial scan needs: the source points outside the overlap pair with the target's rim, and those pairs
+        are not mutual.  Applies to run / iterate / make_pairs on single-device engines that hold the whole selection; nn_search,
+        deviation, score_poses and coarse_align do not look at it.  Survives uploads and set_matrices; stat("reciprocal") /
+        stat("reciprocal_ratio") read it back, stat("recip_rejected") the pairs the last step dropped for it."""
+        self._chk(self._L.oa_set_reciprocal(self._h, int(bool(on)), float(ratio)))
+
     def set_source_weights(self, weights):
         """One weight per source vertex (finite, >= 0; the array uploaded with set_source, not the selection): a pair's weight
         is this times the robust loss's.  None switches them off; a new set_source forgets them.  Call after set_source."""
@@ -370,7 +379,8 @@ class IcpEngine:
              "tri_ring": 21, "tri_ring_accepts": 22, "exchange_us": 23, "rccl_fallbacks": 24, "rccl_ranks_last": 25, "search_clock_mhz": 26, "brute_queue_wgs": 27,
              "metric": 28, "plane_rank": 29, "robust_loss": 30, "weight_sum": 31,
              "robust_scale": 32, "robust_quantile": 33, "target_normals": 34,
-             "target_features": 35, "mesh_pseudonormals": 36}
+             "target_features": 35, "mesh_pseudonormals": 36,
+             "reciprocal": 37, "reciprocal_ratio": 38, "recip_rejected": 39}
     EXCHANGE_NAMES = {-1: None, 0: "mailbox (pinned host memory)", 1: "rccl", 2: "mailbox (peer-mapped device memory)"}
 
     def exchange_info(self):

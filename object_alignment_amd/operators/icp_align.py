@@ -54,6 +54,12 @@ class IcpSettings:
     # world units; None = target_d, the length the loop converges to
     robust_quantile: float = 0.0
     robust_scale_min: float | None = None
+    # nor these: reciprocal=True keeps a pair of a step only if it is mutual -- the source point is also the nearest selected
+    # source point of its own correspondence (reciprocal_ratio 1; up to 16: within that multiple of the nearest distance).  For
+    # a source that reaches beyond the target (a whole model against a partial scan, two partial scans): the points outside the
+    # overlap pair with the target's rim inside min_start, and those pairs are not mutual.  One GPU
+    reciprocal: bool = False
+    reciprocal_ratio: float = 1.0
     # neighbours per vertex when run(..., target_normals="estimate") estimates a point-cloud target's normals on the device
     normal_k: int = 16
     # nor this: > 0 thins the selection in SPACE before the loop -- one vertex per occupied cell of a grid of this edge (world
@@ -160,6 +166,29 @@ def apply_robust(engine, settings) -> None:
         setter(quantile, floor)
     elif quantile != 0.0:
         raise RuntimeError("this engine cannot estimate the robust scale")
+
+
+def reciprocal_of(settings):
+    """(on, ratio) from IcpSettings.reciprocal / reciprocal_ratio, or the `icp_reciprocal` / `icp_reciprocal_ratio` preferences
+    of the registered add-on; (False, 1.0) when neither is there."""
+    on = getattr(settings, "reciprocal", None)
+    if on is None:
+        on = getattr(settings, "icp_reciprocal", False)
+    ratio = getattr(settings, "reciprocal_ratio", None)
+    if ratio is None:
+        ratio = getattr(settings, "icp_reciprocal_ratio", 1.0)
+    return bool(on), float(ratio or 1.0)
+
+
+def apply_reciprocal(engine, settings) -> None:
+    """Hand the settings' reciprocal check to the engine -- every time, off included: the engine is shared and remembers the
+    last setting.  An engine without set_reciprocal counts as one with the check off."""
+    on, ratio = reciprocal_of(settings)
+    setter = getattr(engine, "set_reciprocal", None)
+    if setter is not None:
+        setter(on, ratio)
+    elif on:
+        raise RuntimeError("this engine has no reciprocal check")
 
 
 def sample_voxel_of(settings) -> float:
@@ -312,6 +341,7 @@ class IcpAlign:
                 eng.set_target_normals(target_normals)
         apply_metric(eng, s)
         apply_robust(eng, s)
+        apply_reciprocal(eng, s)
         if sample_voxel > 0.0:
             vlist = voxel_vlist(eng, source_xyz, vlist, mx_align, sample_voxel)
         eng.set_source(source_xyz, vlist=vlist, stride=factor)

@@ -21,7 +21,7 @@ import numpy as np
 
 from .. import _hostmath
 from ..functions.general import _coords_of, _matrix_to_np, _tris_of, default_engine, evaluated_base
-from .icp_align import _OperatorBase, _assign_matrix, _bpy, execute_alignment, apply_metric, apply_robust, get_addon_preferences, vlist_for_engine
+from .icp_align import _OperatorBase, _assign_matrix, _bpy, execute_alignment, apply_metric, apply_reciprocal, apply_robust, get_addon_preferences, vlist_for_engine
 
 RING = 5
 
@@ -150,6 +150,7 @@ class OBJECT_OT_icp_align_feedback(_OperatorBase):
         eng.set_matrices(_matrix_to_np(run.align_obj.matrix_world), _matrix_to_np(run.base_obj.matrix_world))
         apply_metric(eng, get_addon_preferences())
         apply_robust(eng, get_addon_preferences())
+        apply_reciprocal(eng, get_addon_preferences())
         eng.target_owner = eng.source_owner = self                  # GpuBVH and this operator check these before they trust the engine
 
     @staticmethod
