@@ -333,6 +333,7 @@ struct oa_ctx {
     float4 *d_tf3 = nullptr;         // filter image, level 2: 2 float4 per group
     // the same images in the order of the coordinate along the cloud's longest axis (k_nn_search_sorted, round 5)
     float4 *d_tfs = nullptr, *d_tf3s = nullptr, *d_tgs = nullptr;   // 3 / 2 / 3 float4 per group of 4 sorted positions
+    float4 *d_tmw = nullptr;         // level 0's pair images, 1 float4 per group: {m, w} of positions (0, 1) and (2, 3) (oa_pairgap.hpp)
     int4 *d_tidx = nullptr;          // original index of every sorted position
     int sax[3] = { 0, 1, 2 };        // its axes: longest (sorted along), second, thinnest
     int fax[3] = { 0, 1, 2 };
@@ -1126,7 +1127,7 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
     auto launch = [&](auto R, auto TG, auto VCHUNK) {
         hipLaunchKernelGGL((oa::k_nn_search_sorted<decltype(R)::value, decltype(TG)::value, decltype(VCHUNK)::value>), sgrid, dim3(oa::NN_THREADS), 0, c->stream,
                            c->d_state, (const float4 *)c->d_tgs, (const float4 *)c->d_tfs, (const float4 *)c->d_tf3s, (const int4 *)c->d_tidx,
-                           c->n_groups_pad, c->d_keys, pass, (const float4 *)c->d_prec, q_splits, q_blocks, c->d_homes, queued ? c->d_qcnt : nullptr, c->nt);
+                           c->n_groups_pad, c->d_keys, pass, (const float4 *)c->d_prec, q_splits, q_blocks, c->d_homes, queued ? c->d_qcnt : nullptr, c->nt, (const float4 *)c->d_tmw);
     };
     auto search = [&](auto R) { dispatch<oa::FTILE_GROUPS, 64>(c->tile_groups, [&](auto TG) { if (c->tune.nn_vchunk) launch(R, TG, yes); else launch(R, TG, no); }); };
 #if defined(OA_EXPERIMENTS)
@@ -2395,7 +2396,7 @@ OA_EXPORT void oa_destroy(oa_ctx *c)
     (void)hipDeviceSynchronize();
     tl_stream_known = false;                                        // the stream below is about to go away
 #define OA_FREE(x) dev_free(c->x, true)
-    OA_FREE(d_tgt_xyz); OA_FREE(d_tg); OA_FREE(d_tf); OA_FREE(d_tf3); OA_FREE(d_tfs); OA_FREE(d_tf3s); OA_FREE(d_tgs); OA_FREE(d_tidx); OA_FREE(d_tfm); OA_FREE(d_members); OA_FREE(d_pos); OA_FREE(d_prev); OA_FREE(d_win); OA_FREE(d_prec); OA_FREE(d_homes); OA_FREE(d_qcnt); OA_FREE(d_wsafe); OA_FREE(d_safe_by_idx); OA_FREE(d_cell_start);
+    OA_FREE(d_tgt_xyz); OA_FREE(d_tg); OA_FREE(d_tf); OA_FREE(d_tf3); OA_FREE(d_tfs); OA_FREE(d_tf3s); OA_FREE(d_tgs); OA_FREE(d_tmw); OA_FREE(d_tidx); OA_FREE(d_tfm); OA_FREE(d_members); OA_FREE(d_pos); OA_FREE(d_prev); OA_FREE(d_win); OA_FREE(d_prec); OA_FREE(d_homes); OA_FREE(d_qcnt); OA_FREE(d_wsafe); OA_FREE(d_safe_by_idx); OA_FREE(d_cell_start);
     OA_FREE(d_sorted); OA_FREE(d_todo_list); OA_FREE(d_todo_count); OA_FREE(d_ulist); OA_FREE(d_src4); OA_FREE(d_keys); OA_FREE(d_state);
     OA_FREE(d_partials); OA_FREE(d_sums); OA_FREE(d_solve);
     OA_FREE(d_valid); OA_FREE(d_b); OA_FREE(d_dist); OA_FREE(d_counts); OA_FREE(d_offsets); OA_FREE(d_A); OA_FREE(d_B);
@@ -2490,7 +2491,7 @@ int bbox_partials(oa_ctx *c, const float *d_xyz, long long n, int nb, float *out
 // inside a loop.
 int build_sorted_images(oa_ctx *c)
 {
-    dev_free(c->d_tfs); dev_free(c->d_tf3s); dev_free(c->d_tgs); dev_free(c->d_tidx);
+    dev_free(c->d_tfs); dev_free(c->d_tf3s); dev_free(c->d_tgs); dev_free(c->d_tmw); dev_free(c->d_tidx);
     if (!(c->filter_ok && c->tune.nn_sort && c->nt >= 2)) return OA_OK;
     const double *lo = c->bb_lo, *hi = c->bb_hi;
     const int ad = c->fax[2];
@@ -2516,8 +2517,9 @@ int build_sorted_images(oa_ctx *c)
     HIPCHK(dev_malloc(&c->d_tf3s, sizeof(float4) * 2 * (size_t)c->n_groups_pad));
     HIPCHK(dev_malloc(&c->d_tgs, sizeof(float4) * 3 * (size_t)c->n_groups_pad));
     HIPCHK(dev_malloc(&c->d_tidx, sizeof(int4) * (size_t)c->n_groups_pad));
+    HIPCHK(dev_malloc(&c->d_tmw, sizeof(float4) * (size_t)c->n_groups_pad));
     hipLaunchKernelGGL(oa::k_pack_sorted, dim3((unsigned)blocks), dim3(256), 0, c->stream, (const float *)c->d_tgt_xyz, c->nt, c->n_groups_pad,
-                       (const int *)v_out.p, c->tc[0], c->tc[1], c->tc[2], c->sax[0], c->sax[1], c->sax[2], c->d_tfs, c->d_tf3s, c->d_tgs, c->d_tidx);
+                       (const int *)v_out.p, c->tc[0], c->tc[1], c->tc[2], c->sax[0], c->sax[1], c->sax[2], c->d_tfs, c->d_tf3s, c->d_tgs, c->d_tidx, c->d_tmw);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));                      // (the temporaries are released on return)
     return OA_OK;
@@ -2568,7 +2570,7 @@ int build_filter(oa_ctx *c, bool vertex_target)
     for (double v : mx) if (v > m) m = v;
     c->qmax = sqrt(m) * (1.0 + 1e-6);
     c->filter_ok = (c->qmax < 1e18);
-    dev_free(c->d_tfs); dev_free(c->d_tf3s); dev_free(c->d_tgs); dev_free(c->d_tidx);
+    dev_free(c->d_tfs); dev_free(c->d_tf3s); dev_free(c->d_tgs); dev_free(c->d_tmw); dev_free(c->d_tidx);
     // k_nn_search_sorted's images are built for the search mode that uses them: a target uploaded for the grid / tree searches
     // (OA_SEARCH_AUTO, the default) does not pay for them; oa_set_search_mode(OA_SEARCH_BRUTE) builds them when it finds none
     // (a mesh's surface searches never launch k_nn_search_sorted: no images, no sort -- ~36 B per vertex)
@@ -2701,7 +2703,7 @@ int set_target_common(oa_ctx *c, const float *xyz, int64_t n, int on_device, boo
     HIPCHK(hipStreamSynchronize(c->stream));
     c->loop_active = false;                                         // an open oa_iterate sequence ends with the old target
     dev_free(c->d_tgt_xyz); dev_free(c->d_tg); dev_free(c->d_tf); dev_free(c->d_tf3); dev_free(c->d_tfm);
-    dev_free(c->d_tfs); dev_free(c->d_tf3s); dev_free(c->d_tgs); dev_free(c->d_tidx);
+    dev_free(c->d_tfs); dev_free(c->d_tf3s); dev_free(c->d_tgs); dev_free(c->d_tmw); dev_free(c->d_tidx);
     dev_free(c->d_tri9); dev_free(c->d_tcell_start); dev_free(c->d_tcell_rec); dev_free(c->d_tri_ring);
     dev_free(c->d_tfine_table); dev_free(c->d_tfine_rec);
     dev_free(c->d_tris); dev_free(c->d_pn_face); dev_free(c->d_pn_vertex); dev_free(c->d_pn_edge);

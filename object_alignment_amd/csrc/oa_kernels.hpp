@@ -21,6 +21,7 @@
 #include <stdint.h>
 #include <math.h>
 #include <type_traits>
+#include "oa_pairgap.hpp"
 
 namespace oa {
 
@@ -1324,6 +1325,20 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_filt
 //                       a_j > T1 = round_up(sqrt(base) (1 + 2^-22))  =>  t >= a_j / (1 + 2^-24) > sqrt(base).
 //                       (Flushed denormals only ever make a_j smaller: fewer pairs skipped, never a wrong one.)
 //                       For all slabs but the few around the wave's own u range every pair fails here.
+//                       Round 11 (VCHUNK = true): level 0 on PAIRS of vertices.  For positions (4g, 4g+1) and (4g+2, 4g+3) of the
+//                       order the upload keeps the midpoint and half-width {m, w} of their u (tmw, k_pack_sorted), and
+//                           min(|q1 - hu|, |q2 - hu|) = | |M - hu| - W |                       (oa_pairgap.hpp)
+//                       is the smaller of the pair's two gaps in closed form: two subtractions per pair, as before, and a min tree
+//                       of half the leaves -- 63 v_min3_f32 per 256 vertices and point instead of 127, 1.25 instructions per pair
+//                       instead of 1.5.  Every vertex is still in an arithmetic test with every point; nothing is decided from a
+//                       block's bounds, and the vertex order still cannot change an answer.  In float32, a = fl(|fl(m - hu)| - w):
+//                           |a| <= (g + A)(1 + 2^-24),   A = 2^-24 (3 qmax + |hu|) >= 2^-24 (|M| + |m - hu| + W),
+//                       g the real smaller gap (proof: oa_pairgap.hpp).  With
+//                           T1 = round_up((sqrt(base) + A)(1 + 2^-22)),
+//                       |a| > T1  =>  (g + A)(1 + 2^-24) > (sqrt(base) + A)(1 + 2^-22)  =>  g > sqrt(base): both vertices of the
+//                       pair are proven losers.  A pair with padding has w = 0 and is the single gap of above.  The same T1 serves
+//                       level 0v and the VCHUNK = false instances (single gaps: they need no A, and a larger threshold only
+//                       prunes less).
 //   level 0v (rare)     for a block some lane hit (OA_NN_VCHUNK=1): the same gap along v, a_j = fl32(hv - qv_j) against the same
 //                       thr1, from the ENDS of each chunk of 4 OA_SORTED_VCG vertices.  Positions 1 .. n-1 of a block are in the
 //                       order of qv (k_sort_blocks_v), and rounding is monotone, so a_j does not increase along a chunk: with F, L
@@ -1354,9 +1369,11 @@ __global__ void k_sort_keys_axis(const float *__restrict__ xyz, int nt, int axis
 
 // images in sorted order, per group of 4 positions: tfs [qu][-2qv][qu^2+qv^2] (LDS tiles; -2qu is exact from qu), tf3s [-2qd][|q|^2],
 // tgs [x][y][z] (exact), tidx original indices.  Same centring and roundings as k_pack_filter / k_pack_target.
+// tmw (round 11): level 0's pair images {m01, w01, m23, w23} of the group's positions (0, 1) and (2, 3), from the same qu
+// (pair_image, oa_pairgap.hpp) -- positions of the FINAL order, k_sort_blocks_v's included.
 __global__ void k_pack_sorted(const float *__restrict__ xyz, int nt, int n_groups_pad, const int *__restrict__ order, float cx, float cy,
                               float cz, int au, int av, int ad, float4 *__restrict__ tfs, float4 *__restrict__ tf3s,
-                              float4 *__restrict__ tgs, int4 *__restrict__ tidx)
+                              float4 *__restrict__ tgs, int4 *__restrict__ tidx, float4 *__restrict__ tmw)
 {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_groups_pad) return;
@@ -1381,7 +1398,7 @@ __global__ void k_pack_sorted(const float *__restrict__ xyz, int nt, int n_group
             id[k] = -1;
             e[0][k] = e[1][k] = e[2][k] = INFINITY;
             a[0][k] = a[1][k] = a[2][k] = 0.f;
-            qu[k] = 1.0e18f;                                      // (far, and -2 qu stays finite; the tail of the order -- keys clamp)
+            qu[k] = PAIR_PAD_U;                                   // (1e18: far, and -2 qu stays finite; the tail of the order -- keys clamp)
             w2[k] = w3[k] = 3.0e38f;
         }
     }
@@ -1394,11 +1411,16 @@ __global__ void k_pack_sorted(const float *__restrict__ xyz, int nt, int n_group
     tgs[3ll * g + 1] = make_float4(e[1][0], e[1][1], e[1][2], e[1][3]);
     tgs[3ll * g + 2] = make_float4(e[2][0], e[2][1], e[2][2], e[2][3]);
     tidx[g] = make_int4(id[0], id[1], id[2], id[3]);
+    float4 mw;
+    pair_image(qu[0], id[0] >= 0, qu[1], id[1] >= 0, mw.x, mw.y);
+    pair_image(qu[2], id[2] >= 0, qu[3], id[3] >= 0, mw.z, mw.w);
+    tmw[g] = mw;
 }
 #endif  // !OA_FAMILY_TU
 
-// thr1: the 1-D gap's threshold (header above); thr2: the 2-D score's (filter_thresholds).  The 3-D score's is derived from thr2
-// where it is needed.
+// thr1: the 1-D gap's threshold (header above; with level 0's allowance for a pair's gap, which the single gaps of level 0v and of
+// the VCHUNK = false instances do not need -- a threshold that is too high only prunes less); thr2: the 2-D score's
+// (filter_thresholds).  The 3-D score's is derived from thr2 where it is needed.
 __device__ __forceinline__ void sorted_thresholds(float best, float hu, float hv, float hd, double qmax, float &thr1, float &thr2)
 {
     if (!(best < INFINITY)) { thr1 = INFINITY; thr2 = INFINITY; return; }
@@ -1406,7 +1428,7 @@ __device__ __forceinline__ void sorted_thresholds(float best, float hu, float hv
     const double P3 = P2 + (double)hd * (double)hd;
     const double G = sqrt(P3) * (1.0 + 1e-12) + qmax;
     const double base = (double)best * (1.0 + FILTER_K) + FILTER_K * G * G + FILTER_ABS;
-    thr1 = round_up_to_float(sqrt(base) * (1.0 + 0x1p-22));
+    thr1 = round_up_to_float((sqrt(base) + pair_allowance(qmax, hu)) * (1.0 + 0x1p-22));
     thr2 = round_up_to_float(base - P2);
 }
 
@@ -1676,7 +1698,7 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                                                                  unsigned long long *keys, int pass,
                                                                  const float4 *__restrict__ rec,
                                                                  int n_splits, int n_blocks, const int *__restrict__ homes, int *qcnt,
-                                                                 int nt)
+                                                                 int nt, const float4 *__restrict__ tmw)
 {
     // pass 0: seeds from the winner records of the last accumulation (none on the first search of a loop: every split then has to
     // find a best of its own before it can skip anything).  pass 2: seeds from keys, where k_nn_seed_sorted has left every point's
@@ -1686,6 +1708,10 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
     constexpr bool WHOLE = TILE_F4 % NN_THREADS == 0;
     static_assert(LOADS >= 1 && LOADS <= 3, "k_nn_search_sorted: 1 .. 3 float4 per thread and tile");
     __shared__ float4 tile[2][TILE_F4];
+    // level 0's own tile (VCHUNK): the pair images of the same groups, one float4 per group -- beside the three of tfs, which
+    // levels 0v-3 go on reading
+    constexpr bool PAIRS = VCHUNK;
+    __shared__ float4 tilew[2][PAIRS ? TG : 1];
     __shared__ unsigned long long clk0[2];
     __shared__ int s_item[3];                                       // the workgroup's item {split, block}; [2]: the queues found empty so far
     const int tid0 = threadIdx.x;
@@ -1773,7 +1799,10 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
 #define OA_TILE_AT(k) ((k) > 2 * tile_m ? (tile_up ? tile_s + (k) - tile_m : tile_s + tile_m - (k))                                  \
                                         : (((k) & 1) ? tile_s + (((k) + 1) >> 1) : tile_s - ((k) >> 1)))
 
-    float4 stg0 = make_float4(0.f, 0.f, 0.f, 0.f), stg1 = stg0, stg2 = stg0;
+    float4 stg0 = make_float4(0.f, 0.f, 0.f, 0.f), stg1 = stg0, stg2 = stg0, stgw = stg0;
+    const float4 *wsrc = tmw + g_begin;
+#define OA_STGW_ON (PAIRS && (TG >= NN_THREADS || tid < TG))
+    static_assert(TG <= NN_THREADS, "k_nn_search_sorted: one float4 of pair images per thread and tile");
 #define OA_STG_ON(k) (WHOLE || (k) * NN_THREADS + tid < TILE_F4)
 #define OA_STG_EACH(OP)                                       \
     do {                                                      \
@@ -1786,6 +1815,7 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
 #define OA_STG_FIRST(k, reg) reg = fsrc[(k) * NN_THREADS + tid]; tile[0][(k) * NN_THREADS + tid] = reg
         OA_STG_EACH(OA_STG_FIRST);
 #undef OA_STG_FIRST
+        if (OA_STGW_ON) { stgw = wsrc[TG * OA_TILE_AT(0) + tid]; tilew[0][tid] = stgw; }
     }
     __syncthreads();
 
@@ -1802,6 +1832,7 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
 #define OA_STG_LOAD(k, reg) reg = nsrc[(k) * NN_THREADS + ltid]
             OA_STG_EACH(OA_STG_LOAD);
 #undef OA_STG_LOAD
+            if (OA_STGW_ON) stgw = wsrc[TG * nt1 + ltid];
         }
         const int gbase = g_begin + OA_TILE_AT(t) * TG;
         // 4 GW = 256 vertices x R points per skip test.  On gfx950 v_sub_f32 issues at full rate, v_min_f32, v_min3_f32 and v_cmp_*_f32
@@ -1817,22 +1848,44 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
             float m[R], odd[R];
 #pragma unroll
             for (int c = 0; c < GW / 4; ++c) {
-                float4 QU[4];
+                if constexpr (PAIRS) {
+                    // level 0 on pairs of vertices (round 11; proof in the header): per 16 vertices 4 float4 of pair images,
+                    // 16 subtracts (8 of them with |.| on their first source) and 4 min3 per point -- a quarter of a min3 per
+                    // pair where the single gaps below take half of one
+                    float4 MW[4];
 #pragma unroll
-                for (int k = 0; k < 4; ++k) QU[k] = tile[cur][3 * (g + 4 * c + k)];
+                    for (int k = 0; k < 4; ++k) MW[k] = tilew[cur][g + 4 * c + k];
 #pragma unroll
-                for (int r = 0; r < R; ++r) {                      // level 0: one subtract + half a min3 per pair, no branch inside
-                    float a[16];
+                    for (int r = 0; r < R; ++r) {
+                        float a[8];
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        a[4 * k] = __builtin_fabsf(QU[k].x - hu[r]); a[4 * k + 1] = __builtin_fabsf(QU[k].y - hu[r]);
-                        a[4 * k + 2] = __builtin_fabsf(QU[k].z - hu[r]); a[4 * k + 3] = __builtin_fabsf(QU[k].w - hu[r]);
+                        for (int k = 0; k < 4; ++k) {
+                            a[2 * k] = pair_gap(MW[k].x, MW[k].y, hu[r]); a[2 * k + 1] = pair_gap(MW[k].z, MW[k].w, hu[r]);
+                        }
+                        float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(m[r], odd[r]), a[0]);
+#pragma unroll
+                        for (int k = 1; k + 1 < 8; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);   // v_min3_f32
+                        m[r] = v;
+                        odd[r] = a[7];
                     }
-                    float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(m[r], odd[r]), a[0]);
+                } else {
+                    float4 QU[4];
 #pragma unroll
-                    for (int k = 1; k + 1 < 16; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);   // v_min3_f32
-                    m[r] = v;
-                    odd[r] = a[15];
+                    for (int k = 0; k < 4; ++k) QU[k] = tile[cur][3 * (g + 4 * c + k)];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {                  // level 0: one subtract + half a min3 per pair, no branch inside
+                        float a[16];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            a[4 * k] = __builtin_fabsf(QU[k].x - hu[r]); a[4 * k + 1] = __builtin_fabsf(QU[k].y - hu[r]);
+                            a[4 * k + 2] = __builtin_fabsf(QU[k].z - hu[r]); a[4 * k + 3] = __builtin_fabsf(QU[k].w - hu[r]);
+                        }
+                        float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(m[r], odd[r]), a[0]);
+#pragma unroll
+                        for (int k = 1; k + 1 < 16; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);   // v_min3_f32
+                        m[r] = v;
+                        odd[r] = a[15];
+                    }
                 }
             }
             bool hit0 = false, hit[R];
@@ -1931,11 +1984,13 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
 #define OA_STG_STORE(k, reg) tile[cur ^ 1][(k) * NN_THREADS + tid] = reg
             OA_STG_EACH(OA_STG_STORE);
 #undef OA_STG_STORE
+            if (OA_STGW_ON) tilew[cur ^ 1][tid] = stgw;
         }
         __syncthreads();
     }
 #undef OA_STG_EACH
 #undef OA_STG_ON
+#undef OA_STGW_ON
 #undef OA_TILE_AT
 
     if (clk_wg) {

@@ -52,13 +52,63 @@ template <int OP> __global__ __launch_bounds__(256) void burn(float *out, int tr
                 if (OP == 33) asm volatile("v_pk_sub_u16 %0, %1, %0" : "+v"(a[k]) : "v"(b));
                 if (OP == 34) asm volatile("v_min_u16 %0, %1, %0" : "+v"(a[k]) : "v"(b));
                 if (OP == 35) asm volatile("v_max_f16 %0, %1, %0" : "+v"(a[k]) : "v"(b));
+                if (OP == 40) asm volatile("v_sub_f32_e64 %0, |%0|, %1" : "+v"(a[k]) : "v"(b));          // round 11: the pair gap's second subtract
+                if (OP == 41) asm volatile("v_sub_f32 %0, %0, %1\n\tv_sub_f32_e64 %0, |%0|, %2" : "+v"(a[k]) : "v"(b), "v"(c));   // (two instructions)
+                if (OP == 42) asm volatile("v_fma_f32 %0, |%0|, 1.0, -%1" : "+v"(a[k]) : "v"(b));         // the same value through the fma pipe
                 if (OP == 19) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(*(double*)&a[k & ~1]) : "v"(*(double*)&b));
             }
     }
     float s = 0; for (int k = 0; k < 16; ++k) s += a[k] + (float)p[k].x + (float)p[k].y;
     if (s == 12345.678f) out[0] = s;
 }
-template <int OP> void run(const char *name)
+// Level 0 of k_nn_search_sorted as an instruction MIX, 16 independent min chains per lane over 32 "tile" registers:
+//   MIX 0 (until round 10)  per 2 vertices  sub, sub, min3(acc, |t0|, |t1|)                          2 full-rate : 1 half-rate
+//   MIX 1 (round 11)        per 4 vertices  sub, sub |.|, sub, sub |.|, min3(acc, |t0|, |t1|)        4 : 1
+//   MIX 2                   MIX 1 with v_fma_f32 d, |a|, 1.0, -w for the second subtract
+template <int MIX> __global__ __launch_bounds__(256) void mix(float *out, int trips, float seed)
+{
+    float a[16], q[32];
+    for (int k = 0; k < 16; ++k) a[k] = seed + k + threadIdx.x;
+    for (int k = 0; k < 32; ++k) q[k] = seed * 0.5f + k;
+    const float h = seed * 0.25f;
+    for (int t = 0; t < trips; ++t) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                float t0, t1;
+                if (MIX == 0)
+                    asm volatile("v_sub_f32 %1, %3, %5\n\tv_sub_f32 %2, %4, %5\n\tv_min3_f32 %0, %0, |%1|, |%2|"
+                                 : "+v"(a[k]), "=&v"(t0), "=&v"(t1) : "v"(q[2 * k]), "v"(q[2 * k + 1]), "v"(h));
+                if (MIX == 1)
+                    asm volatile("v_sub_f32 %1, %3, %5\n\tv_sub_f32 %2, %4, %5\n\tv_sub_f32_e64 %1, |%1|, %4\n\tv_sub_f32_e64 %2, |%2|, %3\n\t"
+                                 "v_min3_f32 %0, %0, |%1|, |%2|"
+                                 : "+v"(a[k]), "=&v"(t0), "=&v"(t1) : "v"(q[2 * k]), "v"(q[2 * k + 1]), "v"(h));
+                if (MIX == 2)
+                    asm volatile("v_sub_f32 %1, %3, %5\n\tv_sub_f32 %2, %4, %5\n\tv_fma_f32 %1, |%1|, 1.0, -%4\n\tv_fma_f32 %2, |%2|, 1.0, -%3\n\t"
+                                 "v_min3_f32 %0, %0, |%1|, |%2|"
+                                 : "+v"(a[k]), "=&v"(t0), "=&v"(t1) : "v"(q[2 * k]), "v"(q[2 * k + 1]), "v"(h));
+            }
+    }
+    float s = 0; for (int k = 0; k < 16; ++k) s += a[k];
+    if (s == 12345.678f) out[0] = s;
+}
+// wps waves per SIMD (the search kernel runs at 4); per_step instructions and vertices per inner step
+template <int MIX> void run_mix(const char *name, int wps, int per_step, int vertices)
+{
+    float *d; (void)hipMalloc(&d, 4);
+    hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    const int trips = 10000, blocks = 256 * wps;
+    mix<MIX><<<blocks, 256>>>(d, 100, 1.0f);
+    (void)hipDeviceSynchronize();
+    (void)hipEventRecord(e0); mix<MIX><<<blocks, 256>>>(d, trips, 1.0f); (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
+    float ms; (void)hipEventElapsedTime(&ms, e0, e1);
+    const double steps = (double)blocks * 4 * trips * 64 / 1024.0;    // inner steps per SIMD
+    printf("%-34s %8.3f ms  %d waves/SIMD  %.3f ns per instr per SIMD  %.3f ns per vertex per SIMD\n", name, ms, wps,
+           ms * 1e6 / (steps * per_step), ms * 1e6 / (steps * vertices));
+    (void)hipFree(d);
+}
+template <int OP> void run(const char *name, int per_step = 1)
 {
     float *d; (void)hipMalloc(&d, 4);
     hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
@@ -67,7 +117,7 @@ template <int OP> void run(const char *name)
     (void)hipDeviceSynchronize();
     (void)hipEventRecord(e0); burn<OP><<<blocks, 256>>>(d, trips, 1.0f); (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
     float ms; (void)hipEventElapsedTime(&ms, e0, e1);
-    const double winst = (double)blocks * 4 * trips * 64;            // wave-instructions
+    const double winst = (double)blocks * 4 * trips * 64 * per_step;            // wave-instructions
     const double per_simd = winst / 1024.0;
     printf("%-34s %8.3f ms  %7.2f G wave-instr/s/SIMD  (%.3f ns per instr per SIMD)\n", name, ms, per_simd / ms / 1e6, ms * 1e6 / per_simd);
     (void)hipFree(d);
@@ -81,5 +131,9 @@ int main()
     run<20>("v_min3_f16"); run<29>("v_min3_f16 abs op_sel"); run<21>("v_sub_f16"); run<22>("v_pk_minimum3_f16"); run<23>("v_minimum3_f32"); run<24>("v_min3_u16"); run<25>("v_min3_u32");
     run<26>("v_or3_b32"); run<27>("v_sad_u16"); run<28>("v_cvt_pkrtz_f16_f32"); run<30>("v_med3_f32"); run<31>("v_sub_u16"); run<32>("v_sub_u32"); run<33>("v_pk_sub_u16"); run<34>("v_min_u16"); run<35>("v_max_f16");
     run<0>("v_add_f32 2src (again)");
+    // round 11 (profiles/r11a_pair_gap.txt): the pair gap | |m - h| - w |
+    run<17>("v_sub_f32 (again)"); run<40>("v_sub_f32_e64 |a|, b"); run<41>("v_sub_f32 -> v_sub_f32_e64 |.|", 2); run<42>("v_fma_f32 |a|, 1.0, -b");
+    run_mix<0>("level 0 until round 10 (2:1)", 4, 3, 2); run_mix<1>("level 0 on pairs, sub (4:1)", 4, 5, 4); run_mix<2>("level 0 on pairs, fma (4:1)", 4, 5, 4);
+    run_mix<0>("level 0 until round 10 (2:1)", 8, 3, 2); run_mix<1>("level 0 on pairs, sub (4:1)", 8, 5, 4);
     return 0;
 }
