@@ -8,7 +8,7 @@ LIB    := object_alignment_amd/liboa_icp.so
 LIBEXP := object_alignment_amd/liboa_icp_exp.so
 FLAGS  := --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form -fno-slp-vectorize -fPIC -fvisibility=hidden -pthread -Wall
 LINK   := --offload-arch=gfx950 -shared -fPIC -fvisibility=hidden -pthread
-FAMS   := brute brute_b brute_big brute_big_b grid tri tri_acc bvh pose knn feat affine recip
+FAMS   := brute brute_b brute_big brute_big_b grid tri tri_acc bvh pose knn feat affine recip trim
 FAMOBJ := $(FAMS:%=$(OBJ)/oa_fam_%.o)
 HDRS   := $(wildcard $(CSRC)/*.hpp) include/oa_icp.h
 

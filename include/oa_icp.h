@@ -357,6 +357,39 @@ int oa_set_robust_auto(oa_ctx *ctx, double quantile, double scale_min);
  * oa_run_begin / oa_iter_partial, and any loop over a source uploaded with shard_count > 1 fail with OA_E_STATE (the context
  * stays usable; oa_set_reciprocal(ctx, 0, 1) brings the plain pairs back). */
 int oa_set_reciprocal(oa_ctx *ctx, int on, double ratio);
+
+/* EXTENSION (not in the reference; Trimmed ICP, Chetverikov et al. 2002/2005, and its fractional form, Phillips, Liu and Tomasi
+ * 2007; PCL's CorrespondenceRejectorTrimmed, libpointmatcher's TrimmedDist / VarTrimmedDist filters): every step keeps only the
+ * pairs with the smallest residuals.  The share kept is the overlap of the two clouds -- given (fraction in (0, 1]) or estimated
+ * by every step itself (fraction = OA_TRIM_AUTO).  Unlike a robust loss it needs no scale in world units; unlike the reciprocal
+ * check no tree over the source, and it drops displaced outliers as well as the rim of an overlap.
+ *
+ * Candidates.  The K_q pairs of a step that would be counted in K and carry a vertex weight > 0 (oa_set_robust_auto's
+ * population; with oa_set_reciprocal on, the pairs that passed it).  Each has the float32-rounded residual r the losses use:
+ * the world-space pair distance (point metric), s |n . (a - b)| (plane), s sqrt(e^T W e) (GICP).
+ *   - Fixed share: k = clamp(ceil(fraction K_q), min(3, K_q), K_q) in fp64, 1-based; the cut q is the k-th smallest r.
+ *   - Estimated share: with r_(1) <= ... <= r_(K_q), S_j = sum_{i <= j} (double)r_(i)^2 and J(j) = S_j j^-(1 + 2 lambda) (FICP's
+ *     FRMSD^2 up to a factor without j): k = the smallest j in [k_min, K_q] that minimises J, k_min = clamp(ceil(fraction_min
+ *     K_q), min(3, K_q), K_q); q = r_(k).  S_j is summed in fp64 in a fixed order (bitwise repeatable); against a sequential
+ *     sum J differs by parts in 1e-10 at most, which can move k only between ranks whose J agree that closely.
+ *   - A candidate stays iff r <= q, compared in float32: ties stay, at least k pairs stay, and nothing depends on slot order.
+ *     A slot that is no candidate keeps the verdict it had (weight 0; a zero normal under the plane metrics).  K_q = 0: q = 0.
+ * A trimmed pair is a rejected pair in oa_set_reciprocal's sense: it leaves the sums of all three metrics, the weighted kernels,
+ * K, mean_dist / std_dist (so the convergence test runs on the trimmed statistics) and oa_set_robust_auto's population.  The step
+ * runs search -> [reciprocal check] -> trim -> [robust scale] -> accumulate, never the accumulating search epilogue.
+ * oa_make_pairs applies the trim with the point residual (it does not look at the metric); fewer than 3 surviving pairs is
+ * OA_E_TOO_FEW_PAIRS.  oa_nn_search, oa_deviation, oa_score_poses and the coarse stages do not look at the setting.
+ * Arguments: fraction = 0 (off, the default), a value in (0, 1], or OA_TRIM_AUTO; fraction_min in (0, 1] when the share is
+ * estimated (ignored otherwise); lambda finite and in [0.5, 8] (2 is a sound default).  Anything else is OA_E_BAD_ARG and the
+ * setting in force stays.  fraction = 0 changes nothing: the same launches, the same bits.  The setting survives uploads and
+ * oa_set_matrices; changing it ends a running oa_iterate sequence.  The estimated share takes selections of up to 8 388 608
+ * points (OA_E_CAPACITY beyond).
+ * Single-device contexts holding the whole selection, oa_run / oa_iterate / oa_make_pairs: the cut is an order statistic of the
+ * world's residuals -- with the trim on, loops and oa_make_pairs of a multi-device context, oa_run_begin / oa_iter_partial, and
+ * any loop over a source uploaded with shard_count > 1 fail with OA_E_STATE (the context stays usable; oa_set_trim(ctx, 0, 0, 2)
+ * brings the plain pairs back). */
+#define OA_TRIM_AUTO (-1.0)
+int oa_set_trim(oa_ctx *ctx, double fraction, double fraction_min, double lambda);
 /* EXTENSION: one weight per source vertex (host, float32, n_verts as uploaded with oa_set_source; finite and >= 0), gathered
  * into the selection's order -- "trust this region less", where vlist can only say yes or no.  w == NULL switches the weights
  * off (every w_vertex = 1); a new source upload forgets them.  OA_E_STATE before oa_set_source; OA_E_BAD_ARG for a count other
@@ -426,6 +459,11 @@ int oa_reset_seeds(oa_ctx *ctx);
 #define OA_STAT_RECIPROCAL_RATIO 38  /* its ratio */
 #define OA_STAT_RECIP_REJECTED  39   /* pairs of the last step (loop, oa_iterate or oa_make_pairs) that passed everything else and failed the
                                       * reciprocal check; 0 when the check is off, and after oa_set_source or oa_set_reciprocal until a step runs */
+#define OA_STAT_TRIM            40   /* oa_set_trim's setting: 0 (off), the fraction, or -1 (OA_TRIM_AUTO) */
+#define OA_STAT_TRIM_CANDIDATES 41   /* K_q of the last step (loop, oa_iterate or oa_make_pairs); 0 when the trim is off, and after
+                                      * oa_set_source or oa_set_trim until a step runs -- as are the next two */
+#define OA_STAT_TRIM_KEPT       42   /* candidates of the last step that stayed */
+#define OA_STAT_TRIM_CUT        43   /* the cut q of the last step, as a double; 0 when off or K_q = 0 */
 #define OA_STAT_ENQUEUED_CHILD  1000   /* + i: the same count for child i alone */
 int oa_get_stat(oa_ctx *ctx, int what, double *value);
 /* why the exchange is what it is (AUTO's reason for not taking RCCL, librccl's error, "RCCL was aborted: ..."), or "" */

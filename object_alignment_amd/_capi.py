@@ -45,6 +45,11 @@ OA_STAT_MESH_PSEUDONORMALS = 36
 OA_STAT_RECIPROCAL = 37
 OA_STAT_RECIPROCAL_RATIO = 38
 OA_STAT_RECIP_REJECTED = 39
+OA_STAT_TRIM = 40
+OA_STAT_TRIM_CANDIDATES = 41
+OA_STAT_TRIM_KEPT = 42
+OA_STAT_TRIM_CUT = 43
+OA_TRIM_AUTO = -1.0
 
 # every symbol include/oa_icp.h declares (tests check that the library exports all of them)
 SYMBOLS = [
@@ -64,7 +69,7 @@ SYMBOLS = [
     "oa_coarse_align_poses", "oa_target_fpfh", "oa_match_features", "oa_feature_candidates",
     "oa_voxel_downsample",
     "oa_deviation", "oa_get_mesh_pseudonormals",
-    "oa_set_reciprocal",
+    "oa_set_reciprocal", "oa_set_trim",
 ]
 
 
@@ -221,6 +226,7 @@ def load(experiments: bool = False):
     L.oa_deviation.argtypes = [vp, C.POINTER(DeviationSettings), dp, dp, fp, ip, C.POINTER(C.c_int8), ip, C.POINTER(DeviationReport)]
     L.oa_get_mesh_pseudonormals.argtypes = [vp, fp, fp]
     L.oa_set_reciprocal.argtypes = [vp, C.c_int, C.c_double]
+    L.oa_set_trim.argtypes = [vp, C.c_double, C.c_double, C.c_double]
     _libs[experiments] = L
     return L
 

@@ -79,12 +79,19 @@ if bpy is not None:
             default=False)
         icp_reciprocal_ratio: FloatProperty(
             name="ICP Reciprocal Ratio", description="1 = strictly mutual; larger keeps a pair whose point is within this multiple of the nearest distance", default=1.0, min=1, max=16)
+        icp_trim: FloatProperty(
+            name="ICP Trim Share", description="Keep only this share of every step's pairs, the closest ones (the overlap of the two objects); 0 = keep all", default=0.0, min=0, max=1)
+        icp_trim_auto: BoolProperty(
+            name="ICP Trim Estimated", description="Let every step estimate the share of pairs to keep (for an unknown overlap); overrides the trim share",
+            default=False)
+        icp_trim_min: FloatProperty(
+            name="ICP Trim Floor", description="Smallest share an estimated trim may fall to", default=0.3, min=0.01, max=1)
 
         def draw(self, context):
             col = self.layout.column()
             for name in ("icp_iterations", "redraw_frequency", "sample_fraction", "min_start", "target_d", "use_target",
                          "take_m_with", "align_meth", "icp_metric", "icp_robust_loss", "icp_robust_scale", "icp_robust_quantile",
-                         "icp_robust_scale_min", "icp_reciprocal", "icp_reciprocal_ratio"):
+                         "icp_robust_scale_min", "icp_reciprocal", "icp_reciprocal_ratio", "icp_trim", "icp_trim_auto", "icp_trim_min"):
                 col.prop(self, name)
 
     class VIEW3D_PT_object_alignment(Panel):
@@ -102,7 +109,7 @@ if bpy is not None:
             if prefs is not None:
                 box = self.layout.box()
                 for name in ("icp_iterations", "sample_fraction", "min_start", "target_d", "use_target", "icp_reciprocal",
-                             "icp_reciprocal_ratio"):
+                             "icp_reciprocal_ratio", "icp_trim", "icp_trim_auto", "icp_trim_min"):
                     box.prop(prefs, name)
 
     def _addon_prefs():

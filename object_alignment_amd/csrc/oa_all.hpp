@@ -12,5 +12,6 @@
 #include "oa_feat.hpp"
 #include "oa_affine.hpp"
 #include "oa_recip.hpp"
+#include "oa_trim.hpp"
 #include "oa_mfma.hpp"
 #include "oa_families.hpp"

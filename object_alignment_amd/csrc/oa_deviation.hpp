@@ -100,7 +100,8 @@ struct DevRow {
 
 struct DevSelect {                        // the state of one quantile's radix select, between its launches
     double p, q;                          // the quantile asked for; the order statistic found
-    uint32_t prefix, rank, kq, pad;
+    uint32_t prefix, rank, kq;
+    uint32_t k_min;                       // the smallest 1-based rank the select may land on (oa_set_trim: 3); 0 = no floor
 };
 
 struct DevOut {                           // per-slot outputs, caller order; each may be nullptr
@@ -422,6 +423,8 @@ __global__ __launch_bounds__(SEL_THREADS) void k_dev_select_scan(DevSelect *__re
         double k = ceil(st->p * (double)kq);                        // the rule of oa_set_robust_auto: the ceil(p K)-th smallest, 1-based
         k = k < 1.0 ? 1.0 : (k > (double)kq ? (double)kq : k);
         rank = (uint32_t)k - 1u;
+        const uint32_t floor_k = st->k_min < kq ? st->k_min : kq;   // (k_min = 0, the quantiles: rank stays what it was)
+        if (floor_k > 0u && rank < floor_k - 1u) rank = floor_k - 1u;
     }
     __syncthreads();                                                // (every thread has read the state before one of them writes it)
     if (kq != 0u && rank >= before && rank - before < mine) {       // exactly one thread

@@ -104,6 +104,12 @@
 // ---- the reciprocal check: one wave per slot through the source's box tree (oa_recip.hpp): oa_fam_recip.hip -----------
 #define OA_FAMILY_RECIP(X) OA_K(X, k_recip_check, OA_SIG_RECIP_CHECK, false) OA_K(X, k_recip_check, OA_SIG_RECIP_CHECK, true)
 
+// ---- Trimmed ICP: the GICP instance of the residual keys (oa_trim.hpp): oa_fam_trim.hip --------------------------------
+#define OA_SIG_RKEYS_GICP(TEST) const DevState *, const float4 *, int, const float *, const unsigned long long *, const float4 *, const float4 *, TEST, const float *, const float *, const float *, uint32_t *, uint32_t *, unsigned long long *
+// (RECIP = true alone: the trim always hands the verdict bytes over -- all ones unless k_recip_check wrote them)
+#define OA_FAMILY_TRIM(X)                                                                                               \
+    OA_K(X, k_residual_keys_gicp, OA_SIG_RKEYS_GICP(NormalTestRecip), true)
+
 // ---- experiments (OA_EXPERIMENTS only): oa_fam_exp.hip --------------------------------------------------------------
 #define OA_FAMILY_EXP(X)                                                                                                \
     OA_K(X, k_nn_search_filtered, OA_SIG_NN_FILTERED, 1, 64) OA_K(X, k_nn_search_filtered, OA_SIG_NN_FILTERED, 2, 64)   \
@@ -133,6 +139,7 @@ OA_FAMILY_KNN(extern)
 OA_FAMILY_FEAT(extern)
 OA_FAMILY_AFFINE(extern)
 OA_FAMILY_RECIP(extern)
+OA_FAMILY_TRIM(extern)
 #if defined(OA_EXPERIMENTS)
 OA_FAMILY_EXP(extern)
 OA_FAMILY_EXP_R8(extern)

@@ -434,6 +434,14 @@ struct oa_ctx {
     bool sbvh_ok = false;            // ... built by the first step with the check on, kept until the next oa_set_source
     unsigned char *d_recip_ok = nullptr;   // k_recip_check's verdict, one byte per slot
     unsigned *d_recip_count = nullptr;     // its counters (RECIP_COUNT_WORDS): word 2 = slots the last step rejected
+    // oa_set_trim: every step keeps its best pairs only (oa_trim.hpp; survives uploads and oa_set_matrices).  The verdict goes into
+    // d_recip_ok, the keys into d_rkeys; the rest is the trim's own, allocated when a loop (or oa_make_pairs) with the setting on begins
+    double trim_fraction = 0.0;      // 0 = off, (0, 1] = the share kept, OA_TRIM_AUTO = estimated every step
+    double trim_min = 0.3, trim_lambda = 2.0;
+    oa::DevTrim *d_trim = nullptr;   // its state between the launches, and the last step's figures (OA_STAT_TRIM_*)
+    uint32_t *d_trim_hist = nullptr; // fixed share: the select's SEL_LEVELS histograms
+    uint32_t *d_trim_sorted = nullptr; int *d_trim_order = nullptr; char *d_trim_tmp = nullptr;   // estimated share: the sorted keys, their order, the sort's scratch
+    double *d_trim_tiles = nullptr; oa::TrimTileMin *d_trim_min = nullptr;                        // ... the scan's tile sums / bases and the tiles' minima
     double pivot[3] = { 0, 0, 0 };
     // launch geometry for k_nn_search
     int n_splits = 1, acc_blocks = 1;
@@ -814,6 +822,71 @@ int refuse_recip_shard(const oa_ctx *c, const char *who)
     return OA_OK;
 }
 
+// oa_set_trim (oa_trim.hpp): the verdict bytes are the reciprocal check's, so a trimmed step accumulates through the RECIP kernels
+inline bool trim_on(const oa_ctx *c) { return c->trim_fraction != 0.0; }
+inline bool trim_auto(const oa_ctx *c) { return c->trim_fraction < 0.0; }
+inline bool verdict_on(const oa_ctx *c) { return c->recip_on || trim_on(c); }
+
+// the cut is an order statistic of the world's residuals: a context that holds only a shard cannot form it
+const char *const TRIM_ONE_DEVICE = ": oa_set_trim needs every selected source point's residual on one device: it runs on a single-device context through oa_run / oa_iterate / oa_make_pairs (call oa_set_trim(ctx, 0, 0, 2) for this path)";
+int refuse_trim_shard(const oa_ctx *c, const char *who)
+{
+    if (trim_on(c) && (c->parent || c->src_shards > 1))
+        return fail(OA_E_STATE, "%s with oa_set_trim on needs the whole selection on one context: this one holds a shard (upload shard 0 of 1, or call oa_set_trim(ctx, 0, 0, 2))", who);
+    return OA_OK;
+}
+
+// the last step's figures and the running counters back to zero, and the host waits (recip_clear_count's reasons)
+int trim_clear(oa_ctx *c)
+{
+    if (!c->d_trim) return OA_OK;
+    HIPCHK(hipMemsetAsync(c->d_trim, 0, sizeof(oa::DevTrim), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
+// what a step with the trim on needs, before its loop starts: the verdict bytes, the keys, the trim's state with the setting in
+// it, and the buffers of the mode in force -- never allocated inside the loop
+int ensure_trim(oa_ctx *c)
+{
+    if (!trim_on(c)) return OA_OK;
+    if (trim_auto(c) && (long long)c->ns > oa::TRIM_AUTO_MAX)
+        return fail(OA_E_CAPACITY, "oa_set_trim: the estimated share takes up to %lld points (this selection: %d)", oa::TRIM_AUTO_MAX, c->ns);
+    if (!c->d_trim) {
+        HIPCHK(dev_malloc(&c->d_trim, sizeof(oa::DevTrim)));
+        const int rcc = trim_clear(c);
+        if (rcc) return rcc;
+    }
+    {   // the setting: everything in front of the counters (the stream is idle or about to be waited for; the figures stay)
+        oa::DevTrim h{};
+        h.sel.p = trim_auto(c) ? 0.0 : c->trim_fraction;
+        h.sel.k_min = 3u;
+        h.lambda = c->trim_lambda;
+        h.fraction_min = c->trim_min;
+        HIPCHK(hipMemcpyAsync(c->d_trim, &h, offsetof(oa::DevTrim, running), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    if (c->ns <= 0) return OA_OK;                                   // an empty selection: no slot, no launch (launch_trim)
+    const size_t ns = (size_t)c->ns;
+    if (!c->d_recip_ok) HIPCHK(dev_malloc(&c->d_recip_ok, ns));
+    if (!c->d_rkeys) HIPCHK(dev_malloc(&c->d_rkeys, sizeof(uint32_t) * ns));
+    if (!c->d_trim_hist) HIPCHK(dev_malloc(&c->d_trim_hist, sizeof(uint32_t) * oa::SEL_LEVELS * oa::SEL_BINS));
+    if (trim_auto(c)) {
+        const size_t n_tiles = (size_t)oa::trim_tiles(c->ns);
+        if (!c->d_trim_sorted) HIPCHK(dev_malloc(&c->d_trim_sorted, sizeof(uint32_t) * ns));
+        if (!c->d_trim_order) HIPCHK(dev_malloc(&c->d_trim_order, sizeof(int) * ns));
+        if (!c->d_trim_tmp && ns > (size_t)oa::SORT_SMALL_MAX) HIPCHK(dev_malloc(&c->d_trim_tmp, oa::sort_order_tmp_bytes(ns)));
+        if (!c->d_trim_tiles) HIPCHK(dev_malloc(&c->d_trim_tiles, sizeof(double) * n_tiles));
+        if (!c->d_trim_min) HIPCHK(dev_malloc(&c->d_trim_min, sizeof(oa::TrimTileMin) * n_tiles));
+    }
+    return OA_OK;
+}
+// the buffers sized by the selection: a new source forgets them
+void trim_free_sized(oa_ctx *c)
+{
+    dev_free(c->d_trim_sorted); dev_free(c->d_trim_order); dev_free(c->d_trim_tmp); dev_free(c->d_trim_tiles); dev_free(c->d_trim_min);
+}
+
 // acc: a whole-shard search of the loop that also takes the pair test and the sums (k_bvh_search<TRI, true>)
 template <bool TRI>
 int launch_bvh(oa_ctx *c, const int *list, const int *list_count, int turn = -1, bool acc = false)
@@ -956,8 +1029,8 @@ SearchChoice choose_search(const oa_ctx *c)
         s.accept_front = c->surface && c->tune.tri_split && c->seeded && !s.dual;
     }
     // (the plane and GICP metrics have no accumulating search epilogue: search, then k_pair_accumulate_plane / _gicp -- as with
-    //  fused_acc off; nor does a weighted step: no search epilogue knows about weights -- nor about the reciprocal check)
-    if (!c->tune.fused_acc || !c->loop_active || c->ns <= 0 || plane_row_metric(c) || weighted(c) || c->recip_on) return s;
+    //  fused_acc off; nor does a weighted step: no search epilogue knows about weights -- nor about the reciprocal check or the trim)
+    if (!c->tune.fused_acc || !c->loop_active || c->ns <= 0 || plane_row_metric(c) || weighted(c) || verdict_on(c)) return s;
     // (the accumulating tree search needs twice the registers of the plain one: worth it while the shard is small enough
     //  that occupancy does not matter -- 12k queries against 1M vertices: 58 us fused, 47 us search + accumulate)
     if (s.kind == SEARCH_TREE) s.plan = c->ns <= c->tune.tree_acc_max ? PLAN_TREE : PLAN_PLAIN;
@@ -1189,7 +1262,7 @@ int launch_nn(oa_ctx *c, const SearchChoice &s, bool acc)
 inline int plane_threads(const oa_ctx *c) { return c->ns >= 262144 ? oa::PLANE_THREADS : 256; }
 inline int plane_blocks(const oa_ctx *c) { const int t = plane_threads(c); return std::max(1, (c->ns + t - 1) / t); }
 
-// RECIP: every arm's variant that reads k_recip_check's verdict (oa_set_reciprocal on); <false> launches what it always has
+// RECIP: every arm's variant that reads the verdict bytes (oa_set_reciprocal or oa_set_trim on); <false> launches what it always has
 template <bool RECIP>
 int launch_accumulate_as(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
 {
@@ -1231,26 +1304,30 @@ int launch_accumulate_as(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
 }
 int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
 {
-    return c->recip_on ? launch_accumulate_as<true>(c, emit, nn_idx, nn_d2) : launch_accumulate_as<false>(c, emit, nn_idx, nn_d2);
+    return verdict_on(c) ? launch_accumulate_as<true>(c, emit, nn_idx, nn_d2) : launch_accumulate_as<false>(c, emit, nn_idx, nn_d2);
 }
 
 // oa_set_robust_auto: between the search and the weighted accumulation of a loop step, the loss's scale from the residuals of
 // the pairs that accumulation is about to form -- six launches, all on the loop's stream (oa_kernels.hpp, k_residual_keys)
+// metric: whose residual (OA_METRIC_*; GICP: the trim's alone); hist: the level-0 counts of the select that follows
 template <bool RECIP>
-void launch_residual_keys(oa_ctx *c)
+void launch_residual_keys(oa_ctx *c, int metric, uint32_t *hist)
 {
     const oa::PairTest<RECIP> nrm = pair_test<RECIP>(c);
     // (launch_accumulate's leading arguments and selections, read-only and without prev; <false> never reads plane_tn)
-    auto *kern = c->metric == OA_METRIC_PLANE ? oa::k_residual_keys<true, RECIP> : oa::k_residual_keys<false, RECIP>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
-                       (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, (const unsigned long long *)c->d_keys,
-                       c->surface ? (const float4 *)nullptr : (const float4 *)c->d_win, c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm,
-                       c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n, (const float *)c->d_w, c->d_rkeys, c->d_sel_hist,
-                       &c->d_state->t_acc_start);
+    auto launch = [&](auto *kern, auto... tail) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
+                           (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, (const unsigned long long *)c->d_keys,
+                           c->surface ? (const float4 *)nullptr : (const float4 *)c->d_win, c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm,
+                           c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n, tail..., (const float *)c->d_w, c->d_rkeys, hist,
+                           &c->d_state->t_acc_start);
+    };
+    if constexpr (RECIP) { if (metric == OA_METRIC_GICP) { launch(oa::k_residual_keys_gicp<true>, (const float *)c->d_src_n); return; } }
+    if (metric == OA_METRIC_PLANE) launch(oa::k_residual_keys<true, RECIP>); else launch(oa::k_residual_keys<false, RECIP>);
 }
 int launch_robust_scale(oa_ctx *c)
 {
-    if (c->recip_on) launch_residual_keys<true>(c); else launch_residual_keys<false>(c);
+    if (verdict_on(c)) launch_residual_keys<true>(c, c->metric, c->d_sel_hist); else launch_residual_keys<false>(c, c->metric, c->d_sel_hist);
     const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
     for (int level = 0; level < oa::SEL_LEVELS; ++level) {
         if (level > 0)
@@ -1258,6 +1335,44 @@ int launch_robust_scale(oa_ctx *c)
                                (const uint32_t *)c->d_rkeys, c->ns, level, c->d_sel_hist);
         hipLaunchKernelGGL(oa::k_select_scan, dim3(1), dim3(oa::SEL_THREADS), 0, c->stream, c->d_state, c->d_sel_hist, level);
     }
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+
+// oa_set_trim: search -> [k_recip_check] -> THIS -> [launch_robust_scale, over the survivors] -> the accumulation.  The keys of the
+// candidates, the cut (fixed share: the radix select with DevTrim::sel as its state; estimated: sort, prefix sums of r^2, argmin of
+// J), the verdict bytes -- all on the loop's stream (oa_trim.hpp).  metric: whose residual (oa_make_pairs: the point metric's)
+int launch_trim(oa_ctx *c, int metric)
+{
+    if (c->ns <= 0) return OA_OK;                                   // no slot to judge: nothing is allocated for it either (ensure_trim)
+    if (!c->recip_on) HIPCHK(hipMemsetAsync(c->d_recip_ok, 1, (size_t)c->ns, c->stream));   // (else k_recip_check has just written every byte)
+    HIPCHK(hipMemsetAsync(c->d_trim_hist, 0, sizeof(uint32_t) * oa::SEL_LEVELS * oa::SEL_BINS, c->stream));
+    launch_residual_keys<true>(c, metric, c->d_trim_hist);
+    const oa::DevState *st = c->d_state;
+    if (!trim_auto(c)) {
+        const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
+        for (int level = 0; level < oa::SEL_LEVELS; ++level) {
+            if (level > 0)
+                hipLaunchKernelGGL(oa::k_dev_select_hist, dim3(hist_blocks, 1), dim3(oa::SEL_THREADS), 0, c->stream, (const oa::DevSelect *)&c->d_trim->sel,
+                                   (const uint32_t *)c->d_rkeys, c->ns, level, c->d_trim_hist);
+            hipLaunchKernelGGL(oa::k_dev_select_scan, dim3(1), dim3(oa::SEL_THREADS), 0, c->stream, &c->d_trim->sel, (const uint32_t *)c->d_trim_hist, level);
+        }
+    } else {
+        const int n_tiles = oa::trim_tiles(c->ns);
+        // (all 32 bits: RKEY_NONE sorts last, and the one-workgroup sort and the LSD passes agree on every key)
+        HIPCHK(oa::sort_order((void *)c->d_trim_tmp, (const uint32_t *)c->d_rkeys, c->d_trim_order, (size_t)c->ns, 32, c->stream));
+        hipLaunchKernelGGL(oa::k_gather_int, dim3((unsigned)((c->ns + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->d_rkeys,
+                           (const int *)c->d_trim_order, c->ns, (int *)c->d_trim_sorted);
+        hipLaunchKernelGGL(oa::k_trim_tile_sums, dim3((unsigned)n_tiles), dim3(oa::TRIM_THREADS), 0, c->stream, st, (const uint32_t *)c->d_trim_sorted, c->ns, c->d_trim_tiles);
+        hipLaunchKernelGGL(oa::k_trim_tile_bases, dim3(1), dim3(oa::TRIM_BASE_THREADS), 0, c->stream, st, c->d_trim, (const uint32_t *)c->d_trim_sorted, c->ns,
+                           c->d_trim_tiles, n_tiles);
+        hipLaunchKernelGGL(oa::k_trim_apply, dim3((unsigned)n_tiles), dim3(oa::TRIM_THREADS), 0, c->stream, st, (const oa::DevTrim *)c->d_trim,
+                           (const uint32_t *)c->d_trim_sorted, c->ns, (const double *)c->d_trim_tiles, c->d_trim_min);
+        hipLaunchKernelGGL(oa::k_trim_argmin, dim3(1), dim3(oa::TRIM_THREADS), 0, c->stream, st, c->d_trim, (const uint32_t *)c->d_trim_sorted,
+                           (const oa::TrimTileMin *)c->d_trim_min, n_tiles);
+    }
+    const unsigned vblocks = (unsigned)std::min(oa::TRIM_VERDICT_MAX_BLOCKS, std::max(1, (c->ns + oa::TRIM_THREADS - 1) / oa::TRIM_THREADS));
+    hipLaunchKernelGGL(oa::k_trim_verdict, dim3(vblocks), dim3(oa::TRIM_THREADS), 0, c->stream, st, c->d_trim, (const uint32_t *)c->d_rkeys, c->ns, c->d_recip_ok);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -1307,6 +1422,7 @@ int launch_search_accumulate(oa_ctx *c, bool timed, oa::RowSel &sel, bool &fused
     }
     if (!fused) {
         if (c->recip_on && (rc = launch_recip(c, plane_row_metric(c)))) return rc;
+        if (trim_on(c) && (rc = launch_trim(c, c->metric))) return rc;
         if (auto_scale(c) && (rc = launch_robust_scale(c))) return rc;
         if ((rc = launch_accumulate(c, false, nullptr, nullptr))) return rc;
         sel = plain_rows(c);
@@ -1466,9 +1582,11 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
     } else if (weighted(c) && (long long)c->ns > (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS)
         return fail(OA_E_CAPACITY, "a weighted loop takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS, c->ns);
     if ((rc = refuse_recip_shard(c, "a loop"))) return rc;
+    if ((rc = refuse_trim_shard(c, "a loop"))) return rc;
     if ((rc = use_device(c))) return rc;
     if ((rc = ensure_common(c))) return rc;
     if ((rc = ensure_recip(c))) return rc;                          // (the source tree: before the loop starts, never inside it)
+    if ((rc = ensure_trim(c))) return rc;
     if ((rc = ensure_history(c, iters == ITERATE_OPEN ? ITERATE_RING : iters))) return rc;   // oa_iterate: a small ring
     if (auto_scale(c)) {                                          // the selection's buffers; its histograms start (and are kept) at zero
         if (!c->d_rkeys) HIPCHK(dev_malloc(&c->d_rkeys, sizeof(uint32_t) * (size_t)std::max(1, c->ns)));
@@ -2404,6 +2522,7 @@ OA_EXPORT void oa_destroy(oa_ctx *c)
     OA_FREE(d_tri9); OA_FREE(d_tcell_start); OA_FREE(d_tcell_rec); OA_FREE(d_tri_ring); OA_FREE(d_tfine_table); OA_FREE(d_tfine_rec);
     OA_FREE(d_sel); OA_FREE(d_src_n); OA_FREE(d_tgt_n); OA_FREE(d_tgt_feat); OA_FREE(d_w); OA_FREE(d_rkeys); OA_FREE(d_sel_hist); OA_FREE(d_src4o); OA_FREE(d_perm);
     OA_FREE(d_sbvh_box); OA_FREE(d_sbvh_prims); OA_FREE(d_recip_ok); OA_FREE(d_recip_count);
+    OA_FREE(d_trim); OA_FREE(d_trim_hist); OA_FREE(d_trim_sorted); OA_FREE(d_trim_order); OA_FREE(d_trim_tmp); OA_FREE(d_trim_tiles); OA_FREE(d_trim_min);
     OA_FREE(d_tris); OA_FREE(d_pn_face); OA_FREE(d_pn_vertex); OA_FREE(d_pn_edge);
 #undef OA_FREE
     if (c->h_hist_map) (void)hipHostFree(c->h_hist_map);
@@ -3401,6 +3520,8 @@ int source_reset(oa_ctx *c, long long count, long long begin, long long n_verts)
     dev_free(c->d_src4); dev_free(c->d_keys); dev_free(c->d_prev); dev_free(c->d_win); dev_free(c->d_wsafe); dev_free(c->d_sel); dev_free(c->d_src_n); dev_free(c->d_w); dev_free(c->d_rkeys);
     dev_free(c->d_sbvh_box); dev_free(c->d_sbvh_prims); dev_free(c->d_recip_ok); c->sbvh_ok = false;   // (the source tree: a new source forgets it)
     { const int rcc = recip_clear_count(c); if (rcc) return rcc; }  // ... and the old source's count
+    trim_free_sized(c);
+    { const int rcc = trim_clear(c); if (rcc) return rcc; }         // (oa_set_trim's figures spoke of the old source)
     dev_free(c->d_src4o); dev_free(c->d_perm); dev_free(c->d_members); dev_free(c->d_pos);
     c->h_members.clear();
     c->shard_begin = begin;
@@ -3791,6 +3912,36 @@ OA_EXPORT int oa_set_reciprocal(oa_ctx *c, int on, double ratio)
     return OA_OK;
 }
 
+OA_EXPORT int oa_set_trim(oa_ctx *c, double fraction, double fraction_min, double lambda)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    const bool est = fraction == OA_TRIM_AUTO;
+    if (!(fraction == 0.0 || est || (fraction > 0.0 && fraction <= 1.0)))
+        return fail(OA_E_BAD_ARG, "oa_set_trim: the fraction must be 0 (off), in (0, 1], or OA_TRIM_AUTO");
+    if (est && !(fraction_min > 0.0 && fraction_min <= 1.0)) return fail(OA_E_BAD_ARG, "oa_set_trim: fraction_min must be in (0, 1] when the share is estimated");
+    if (!(lambda >= 0.5 && lambda <= 8.0)) return fail(OA_E_BAD_ARG, "oa_set_trim: lambda must be in [0.5, 8]");
+    if (!est) fraction_min = c->trim_min;                           // (ignored: the stored one stays)
+    if (fraction == c->trim_fraction && fraction_min == c->trim_min && lambda == c->trim_lambda) return OA_OK;
+    // a changed setting ends the running sequence, as oa_set_reciprocal does
+    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
+    else if (c->loop_active) {
+        int rc = use_device(c);
+        if (rc) return rc;
+        if ((rc = fetch_state(c))) return rc;
+        c->loop_active = false;
+    }
+    // (a multi-device parent keeps the setting itself and refuses the loops: its children never see it)
+    c->trim_fraction = fraction;
+    c->trim_min = fraction_min;
+    c->trim_lambda = lambda;
+    if (c->d_trim) {                                                // the last step's figures were the old setting's
+        int rc = use_device(c);
+        if (rc) return rc;
+        if ((rc = trim_clear(c))) return rc;
+    }
+    return OA_OK;
+}
+
 OA_EXPORT int oa_set_source_weights(oa_ctx *c, const float *w, int64_t n_verts)
 {
     if (!c) return fail(OA_E_BAD_ARG, "null context");
@@ -3993,6 +4144,17 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
         *value = (double)n;
         return OA_OK;
     }
+    if (what == OA_STAT_TRIM) { *value = c->trim_fraction; return OA_OK; }
+    if (what == OA_STAT_TRIM_CANDIDATES || what == OA_STAT_TRIM_KEPT || what == OA_STAT_TRIM_CUT) {
+        *value = 0.0;
+        if (!trim_on(c) || !c->d_trim) return OA_OK;
+        int rc = use_device(c);
+        if (rc) return rc;
+        oa::DevTrim t;
+        if ((rc = read_small(c, &t, c->d_trim, sizeof t))) return rc;
+        *value = what == OA_STAT_TRIM_CANDIDATES ? (double)t.stat_kq : what == OA_STAT_TRIM_KEPT ? (double)t.stat_kept : t.stat_q;
+        return OA_OK;
+    }
     OA_ROUTE_FIRST(c, oa_get_stat(sub, what, value));
     switch (what) {
     case OA_STAT_GRID_CELLS: *value = c->grid_ok ? (double)c->n_cells : 0.0; return OA_OK;
@@ -4185,6 +4347,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
                             double dstats[2])
 {
     if (c && !c->subs.empty() && c->recip_on) return fail(OA_E_STATE, "oa_make_pairs on a multi-device context%s", RECIP_ONE_DEVICE);
+    if (c && !c->subs.empty() && trim_on(c)) return fail(OA_E_STATE, "oa_make_pairs on a multi-device context%s", TRIM_ONE_DEVICE);
     if (c && !c->subs.empty()) {
         // multi-device: every child pairs its shard (its pairs come out in ascending selection position, with that
         // position); the shards are merged back into vlist order on the host.  Statistics: the children's two-pass
@@ -4247,9 +4410,11 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
     if (!K || cap < 0 || (cap > 0 && (!A || !B))) return fail(OA_E_BAD_ARG, "oa_make_pairs: bad output arguments");
     if (!(thresh > 0.0)) return fail(OA_E_BAD_THRESH, "thresh must be > 0 (the reference's make_pairs returns None)");
     if ((rc = refuse_recip_shard(c, "oa_make_pairs"))) return rc;
+    if ((rc = refuse_trim_shard(c, "oa_make_pairs"))) return rc;
     if ((rc = use_device(c))) return rc;
     if ((rc = ensure_common(c))) return rc;
     if ((rc = ensure_recip(c))) return rc;
+    if ((rc = ensure_trim(c))) return rc;
     *K = 0;
     if (dstats) { dstats[0] = NAN; dstats[1] = NAN; }
     if (c->ns == 0) return OA_OK;
@@ -4272,6 +4437,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
     if ((rc = push_state_for_oneshot(c, thresh, true))) return rc;
     if ((rc = launch_nn(c, choose_search(c), false))) return rc;
     if (c->recip_on && (rc = launch_recip(c, false))) return rc;
+    if (trim_on(c) && (rc = launch_trim(c, OA_METRIC_POINT))) return rc;   // (the point residual: oa_make_pairs does not look at the metric)
     if ((rc = launch_accumulate(c, true, nullptr, nullptr))) return rc;
     if ((rc = launch_reduce(c, c->d_sums, oa::RowSel{ c->acc_blocks, 0, 0 }, false))) return rc;   // (emitting accumulation: k_pair_accumulate<true>)
     if (calc_stats) {
@@ -4284,6 +4450,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
             if ((rc = push_state_for_oneshot(c, thresh, true))) { c->d_pivot0 = 0.0; return rc; }
             rc = launch_nn(c, choose_search(c), false);
             if (!rc && c->recip_on) rc = launch_recip(c, false);
+            if (!rc && trim_on(c)) rc = launch_trim(c, OA_METRIC_POINT);
             if (!rc) rc = launch_accumulate(c, true, nullptr, nullptr);
             if (!rc) rc = launch_reduce(c, c->d_sums, oa::RowSel{ c->acc_blocks, 0, 0 }, false);
             if (rc) { c->d_pivot0 = 0.0; return rc; }
@@ -4500,6 +4667,7 @@ const char *const AUTO_ONE_DEVICE = ": a robust scale estimated from the residua
 int refuse_wide_row(const oa_ctx *c, const char *who, bool estimated_scale_too = true)
 {
     if (c->recip_on) return fail(OA_E_STATE, "%s%s", who, RECIP_ONE_DEVICE);
+    if (trim_on(c)) return fail(OA_E_STATE, "%s%s", who, TRIM_ONE_DEVICE);
     if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "%s%s", who, PLANE_ONE_DEVICE);
     if (c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "%s%s", who, GICP_ONE_DEVICE);
     if (estimated_scale_too && auto_scale(c)) return fail(OA_E_STATE, "%s%s", who, AUTO_ONE_DEVICE);

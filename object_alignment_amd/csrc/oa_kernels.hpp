@@ -2786,7 +2786,7 @@ __host__ __device__ inline uint32_t sel_digit(uint32_t key, int level)
 // the digits above `level`'s: what sel_prefix holds when that level is counted
 __host__ __device__ inline uint32_t sel_above(uint32_t key, int level) { return level == 1 ? key >> 21 : key >> 10; }
 
-#if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
+// (sel_count / sel_clear / sel_flush are inlined helpers: the family units see them too -- oa_trim.hpp's GICP keys kernel)
 // one key into the workgroup's LDS counts.  The residuals of a step share their exponent, so the lanes of a wave hit a
 // handful of bins at level 0 and same-address LDS atomics take turns: up to four rounds in which the first pending lane's bin
 // is counted for every lane that shares it by ONE add, and whatever is left adds for itself.  Called by ALL lanes of the wave.
@@ -2819,6 +2819,7 @@ __device__ __forceinline__ void sel_flush(const uint32_t *bins, uint32_t *__rest
     }
 }
 
+#if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
 // The residual of every slot's pair, as the weighted accumulation of this metric will see it: pair_fetch<false, PLANE> (the same
 // pair, NO write to keys, prev or win) and -- PLANE -- plane_normal / plane_row.  rkeys[i] = the bits of (float)residual (point: pair_eval's dist; plane: res_scale |n . (a' - b')|), or
 // RKEY_NONE for a slot without a pair counted in K or with vertex weight 0.  Launched like the accumulation (plane_threads /

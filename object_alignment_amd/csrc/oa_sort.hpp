@@ -173,7 +173,8 @@ inline size_t sort_order_tmp_bytes(size_t n)
 }
 
 #if defined(__HIPCC__)
-// order[0 .. n) = the STABLE ascending order of keys[0 .. n) on their low `bits` bits (bits <= 30, the bits above them zero):
+// order[0 .. n) = the STABLE ascending order of keys[0 .. n) on their low `bits` bits (bits <= 32: a pass per 10 bits, the fourth
+// takes what is left -- oa_set_trim sorts whole float keys; the bits above `bits` zero):
 // order[j] = index of the j-th smallest key, equal keys by index -- what a stable sort_pairs returns for the values 0, 1, 2, ...
 // The keys are left as they are.  tmp: sort_order_tmp_bytes(n) bytes, 8-byte aligned.  Everything on `stream`, no wait.
 inline hipError_t sort_order_lsd(void *tmp, const uint32_t *keys, int *order, size_t n, int bits, hipStream_t stream)

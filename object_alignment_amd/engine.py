@@ -355,6 +355,20 @@ class IcpEngine:
         stat("reciprocal_ratio") read it back, stat("recip_rejected") the pairs the last step dropped for it."""
         self._chk(self._L.oa_set_reciprocal(self._h, int(bool(on)), float(ratio)))
 
+    def set_trim(self, fraction=0.0, fraction_min=0.3, lam=2.0):
+        """Trimmed ICP: every step keeps only the pairs with the smallest residuals.  fraction: 0 = off, a share in (0, 1] (the
+        overlap of the two clouds), or "auto": every step estimates the share itself (fractional ICP: the share that minimises
+        FRMSD with exponent `lam`, searched from fraction_min up).  Needs no scale in world units and no tree over the source, and
+        drops displaced outliers as well as the rim of an overlap.  Applies to run / iterate / make_pairs on single-device engines
+        that hold the whole selection; nn_search, deviation, score_poses and coarse_align do not look at it.  Survives uploads and
+        set_matrices; stat("trim") reads the setting back (-1: auto), stat("trim_candidates") / stat("trim_kept") /
+        stat("trim_cut") the last step's candidates, survivors and cut."""
+        if isinstance(fraction, str):
+            if fraction != "auto":
+                raise ValueError('fraction must be a number or "auto"')
+            fraction = capi.OA_TRIM_AUTO
+        self._chk(self._L.oa_set_trim(self._h, float(fraction), float(fraction_min), float(lam)))
+
     def set_source_weights(self, weights):
         """One weight per source vertex (finite, >= 0; the array uploaded with set_source, not the selection): a pair's weight
         is this times the robust loss's.  None switches them off; a new set_source forgets them.  Call after set_source."""
@@ -380,7 +394,8 @@ class IcpEngine:
              "metric": 28, "plane_rank": 29, "robust_loss": 30, "weight_sum": 31,
              "robust_scale": 32, "robust_quantile": 33, "target_normals": 34,
              "target_features": 35, "mesh_pseudonormals": 36,
-             "reciprocal": 37, "reciprocal_ratio": 38, "recip_rejected": 39}
+             "reciprocal": 37, "reciprocal_ratio": 38, "recip_rejected": 39,
+             "trim": 40, "trim_candidates": 41, "trim_kept": 42, "trim_cut": 43}
     EXCHANGE_NAMES = {-1: None, 0: "mailbox (pinned host memory)", 1: "rccl", 2: "mailbox (peer-mapped device memory)"}
 
     def exchange_info(self):

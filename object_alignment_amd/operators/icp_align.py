@@ -60,6 +60,13 @@ class IcpSettings:
     # overlap pair with the target's rim inside min_start, and those pairs are not mutual.  One GPU
     reciprocal: bool = False
     reciprocal_ratio: float = 1.0
+    # nor these: Trimmed ICP -- trim > 0 keeps only that share of every step's pairs, the ones with the smallest residuals (the
+    # overlap of the two clouds, if it is known); trim="auto" lets every step estimate the share itself (fractional ICP: the share
+    # that minimises FRMSD with exponent trim_lambda, searched from trim_min up).  No scale in world units to choose, no tree over
+    # the source, and displaced outliers go as well as the rim of an overlap.  0 = off.  One GPU
+    trim: object = 0.0
+    trim_min: float = 0.3
+    trim_lambda: float = 2.0
     # neighbours per vertex when run(..., target_normals="estimate") estimates a point-cloud target's normals on the device
     normal_k: int = 16
     # nor this: > 0 thins the selection in SPACE before the loop -- one vertex per occupied cell of a grid of this edge (world
@@ -189,6 +196,36 @@ def apply_reciprocal(engine, settings) -> None:
         setter(on, ratio)
     elif on:
         raise RuntimeError("this engine has no reciprocal check")
+
+
+def trim_of(settings):
+    """(fraction, fraction_min, lam) from IcpSettings.trim / trim_min / trim_lambda, or the `icp_trim` / `icp_trim_auto` /
+    `icp_trim_min` preferences of the registered add-on; fraction is 0.0 (off), a share in (0, 1] or "auto".  (0.0, 0.3, 2.0)
+    when neither is there."""
+    frac = getattr(settings, "trim", None)
+    if frac is None:
+        frac = "auto" if getattr(settings, "icp_trim_auto", False) else getattr(settings, "icp_trim", 0.0)
+    fmin = getattr(settings, "trim_min", None)
+    if fmin is None:
+        fmin = getattr(settings, "icp_trim_min", 0.3)
+    lam = getattr(settings, "trim_lambda", None)
+    if isinstance(frac, str):
+        if frac != "auto":
+            raise ValueError('trim must be a number or "auto", not %r' % (frac,))
+    else:
+        frac = float(frac or 0.0)
+    return frac, float(fmin or 0.3), float(lam or 2.0)
+
+
+def apply_trim(engine, settings) -> None:
+    """Hand the settings' trim to the engine -- every time, off included: the engine is shared and remembers the last setting.
+    An engine without set_trim counts as one with the trim off."""
+    frac, fmin, lam = trim_of(settings)
+    setter = getattr(engine, "set_trim", None)
+    if setter is not None:
+        setter(frac, fmin, lam)
+    elif frac != 0.0:
+        raise RuntimeError("this engine cannot trim its pairs")
 
 
 def sample_voxel_of(settings) -> float:
@@ -342,6 +379,7 @@ class IcpAlign:
         apply_metric(eng, s)
         apply_robust(eng, s)
         apply_reciprocal(eng, s)
+        apply_trim(eng, s)
         if sample_voxel > 0.0:
             vlist = voxel_vlist(eng, source_xyz, vlist, mx_align, sample_voxel)
         eng.set_source(source_xyz, vlist=vlist, stride=factor)
