@@ -400,7 +400,7 @@ struct oa_ctx {
     int *d_sel = nullptr;            // vertex index held by each source slot
     float4 *d_src4o = nullptr;       // the same points in the caller's (vlist) order -- only oa_make_pairs needs it
     int *d_perm = nullptr;           // sorted slot -> caller-order slot (nullptr: not sorted)
-    float4 *d_prec = nullptr;        // k_sorted_point_setup: k_nn_search_sorted's point records, 3 float4 per slot in the order its lanes read them (OA_NN_WAVE_ORDER=0: the slots' own order)
+    float4 *d_prec = nullptr;        // k_sorted_point_setup: k_nn_search_sorted's point records, 3 float4 per slot in the order its lanes read them + a fourth array, one float4 per lane and pair of its points (oa_quadgap.hpp) (OA_NN_WAVE_ORDER=0: the slots' own order)
     int prec_cap = 0;                // slots d_prec holds
     int homes_cap = 0;               // blocks of source points d_homes holds (two ints each: home split, home tile)
     int *d_homes = nullptr, *d_qcnt = nullptr;   // k_nn_search_sorted's work queue (oa_kernels.hpp): per block of source points its own split; the queues' counters
@@ -1144,7 +1144,7 @@ int ensure_sorted_buffers(oa_ctx *c, int blocks)
 {
     if (c->ns_pad > c->prec_cap) {
         dev_free(c->d_prec); c->prec_cap = 0;
-        HIPCHK(dev_malloc(&c->d_prec, sizeof(float4) * 3 * (size_t)c->ns_pad));
+        HIPCHK(dev_malloc(&c->d_prec, sizeof(float4) * 4 * (size_t)c->ns_pad));   // (three float4 per slot + the lanes' point pairs)
         c->prec_cap = c->ns_pad;
     }
     if (blocks > c->homes_cap) {
@@ -1185,7 +1185,7 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
         const dim3 ob((unsigned)(c->ns_pad / (64 * c->R)));
         dispatch<4, 1, 2, 8>(c->R, [&](auto R) {
             hipLaunchKernelGGL((oa::k_sorted_point_setup<decltype(R)::value>), ob, dim3(64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4,
-                               (const float4 *)c->d_win, (const unsigned long long *)c->d_keys, c->sax[0], c->sax[1], pass, c->tune.nn_wave_order ? 1 : 0, c->ns_pad, c->d_prec);
+                               (const float4 *)c->d_win, (const unsigned long long *)c->d_keys, c->sax[0], c->sax[1], pass, c->tune.nn_wave_order ? 1 : 0, c->ns_pad, c->ns, c->d_prec);
         });
         HIPCHK(hipGetLastError());
     }
@@ -3542,7 +3542,7 @@ int source_reset(oa_ctx *c, long long count, long long begin, long long n_verts)
     HIPCHK(dev_malloc(&c->d_win, sizeof(float4) * (size_t)c->ns_pad));
     dev_free(c->d_prec); dev_free(c->d_homes); dev_free(c->d_qcnt);
     c->prec_cap = 0; c->homes_cap = 0;
-    if (c->grid_mode == 0) { const int rcq = ensure_sorted_buffers(c, c->ns_pad / chunk); if (rcq) return rcq; }   // (brute force only, never inside a loop: 48 B per slot + the brute-force launch's q_blocks, a few KB)
+    if (c->grid_mode == 0) { const int rcq = ensure_sorted_buffers(c, c->ns_pad / chunk); if (rcq) return rcq; }   // (brute force only, never inside a loop: 64 B per slot + the brute-force launch's q_blocks, a few KB)
     if (c->tune.grid_safe && !c->surface) HIPCHK(dev_malloc(&c->d_wsafe, sizeof(uint2) * (size_t)c->ns_pad));   // (a vertex target set later allocates it: set_target_common)
     c->seeded = false; c->win_seeds = false;
     HIPCHK(dev_malloc(&c->d_sel, sizeof(int) * (size_t)c->ns_pad));

@@ -22,6 +22,7 @@
 #include <math.h>
 #include <type_traits>
 #include "oa_pairgap.hpp"
+#include "oa_quadgap.hpp"
 
 namespace oa {
 
@@ -1339,6 +1340,16 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_filt
 //                       pair are proven losers.  A pair with padding has w = 0 and is the single gap of above.  The same T1 serves
 //                       level 0v and the VCHUNK = false instances (single gaps: they need no A, and a larger threshold only
 //                       prunes less).
+//                       Round 13 (VCHUNK = true, R >= 2): the same identity once more, on the lane's own points.  Points 2p and
+//                       2p + 1 of a lane have the midpoint hm and half-width hw along u (k_sorted_point_setup), and
+//                           t = | |m - hm| - hw | - w     (signed; three subtractions for four (vertex, point) pairs)
+//                       never exceeds the smallest of the four gaps by more than the pair's allowance (oa_quadgap.hpp, for either
+//                       order of hw and w): t > quad_threshold(thr1 of the two points, allowance) proves both vertices losers
+//                       for both points -- 384 v_sub + 63 v_min3 + v_min + v_cmp per point PAIR and 256 vertices, 0.88
+//                       instructions per pair where round 11 takes 1.25.  Still every vertex's and every point's own coordinate
+//                       in an arithmetic test, nothing from a block's bounds, any permutation of either side the same answers.
+//                       A pair that is not ruled out marks the block for both its points; level 0v and levels 1-3 then decide per
+//                       point, with their own thr1, as before.  OA_SORTED_QUAD=0 (build time): round 11's fold per point.
 //   level 0v (rare)     for a block some lane hit (OA_NN_VCHUNK=1): the same gap along v, a_j = fl32(hv - qv_j) against the same
 //                       thr1, from the ENDS of each chunk of 4 OA_SORTED_VCG vertices.  Positions 1 .. n-1 of a block are in the
 //                       order of qv (k_sort_blocks_v), and rounding is monotone, so a_j does not increase along a chunk: with F, L
@@ -1483,6 +1494,8 @@ __device__ __forceinline__ bool sorted_finish_group(const float4 AU, const float
 // its distance, the thresholds.  One RECORD per slot, three float4 in three arrays of ns_pad entries (rec, rec + ns_pad,
 // rec + 2 ns_pad):
 //   [0] hu, hv, hd, the slot's index (int bits)     [1] best, bidx (uint bits), thr1, thr2     [2] px, py, pz (co_find), 0
+// and (R >= 2, round 13) a fourth array, rec + 3 ns_pad: per lane and pair of its points (2p, 2p + 1), at first + 64 p + lane of the
+// wave's records, {hm, hw, allowance, 0} -- the pair's image along u and what rounding can add to its gap (oa_quadgap.hpp).
 // The seed is the slot's winner record (pass 0) or what k_nn_seed_sorted left in keys (pass 2: this kernel runs after it).
 // The arithmetic is the item prologue's of before, through the same device functions: the same floats.
 // WHERE a slot's record lies decides which lane takes it as its point r: record first + 64 r + lane of a wave's 64 R records
@@ -1497,11 +1510,12 @@ __device__ __forceinline__ bool sorted_finish_group(const float4 AU, const float
 template <int R>
 __global__ __launch_bounds__(64) void k_sorted_point_setup(const DevState *__restrict__ st, const float4 *__restrict__ src4,
                                                            const float4 *__restrict__ win, const unsigned long long *__restrict__ keys,
-                                                           int au, int av, int pass, int ranked, int ns_pad, float4 *__restrict__ rec)
+                                                           int au, int av, int pass, int ranked, int ns_pad, int ns, float4 *__restrict__ rec)
 {
     if (st->halt) return;
     constexpr int N = 64 * R;
     __shared__ uint32_t key[N];
+    __shared__ float pu[R >= 2 ? N : 1];                           // round 13: the records' hu in the order the lanes read them
     const int t = threadIdx.x;
     const int first = (int)blockIdx.x * N;
     const double qmax = st->qmax;
@@ -1558,6 +1572,26 @@ __global__ __launch_bounds__(64) void k_sorted_point_setup(const DevState *__res
         rec[first + rank[r]] = ra[r];
         rec[ns_pad + first + rank[r]] = rb[r];
         rec[2 * ns_pad + first + rank[r]] = rc[r];
+    }
+    if constexpr (R >= 2) {
+        // round 13: the lane's point pairs (2p, 2p + 1) -- {hm, hw, allowance, 0} in record first + 64 p + lane of a fourth array
+        // -- formed from the records the search's lane will hold, first + 64 r + lane, so after the ranking.  A pair without a
+        // claim (oa_quadgap.hpp, (6): a hu that is not finite; a padding slot of the source beside a real one) gets the
+        // allowance +inf: its threshold is +inf whatever its points' thr1 become
+        __syncthreads();                                           // (the ranking's reads of key are done)
+#pragma unroll
+        for (int r = 0; r < R; ++r) pu[rank[r]] = ra[r].x;
+#pragma unroll
+        for (int r = 0; r < R; ++r) key[rank[r]] = (first + r * 64 + t < ns) ? 1u : 0u;
+        __syncthreads();
+#pragma unroll
+        for (int p = 0; p < R / 2; ++p) {
+            const float h1 = pu[128 * p + t], h2 = pu[128 * p + 64 + t];
+            const bool claim = (h1 - h1 == 0.0f) && (h2 - h2 == 0.0f) && key[128 * p + t] == key[128 * p + 64 + t];
+            float hm, hw;
+            point_pair_image(h1, h2, hm, hw);
+            rec[3 * ns_pad + first + 64 * p + t] = make_float4(hm, hw, claim ? round_up_to_float(quad_allowance(qmax, h1, h2)) : INFINITY, 0.f);
+        }
     }
 }
 
@@ -1648,6 +1682,9 @@ __global__ void k_sorted_block_homes(const DevState *__restrict__ st, const floa
 #ifndef OA_SORTED_VCG
 #define OA_SORTED_VCG 4                   // groups of 4 sorted vertices per chunk of level 0v (a build-time knob for sweeps;
 #endif                                    //  2 / 4 / 8: 25.46 / 24.99 / 24.94 ms at 1M <-> 1M, profiles/r08a_vends.txt)
+#ifndef OA_SORTED_QUAD
+#define OA_SORTED_QUAD 1                  // 1: level 0 of the <R >= 2, TG, true> instances on pairs of the lane's points (round 13,
+#endif                                    //  oa_quadgap.hpp); 0: round 11's per-point fold alone (a build-time knob for sweeps)
 #ifndef OA_SORTED_VREFINE
 #define OA_SORTED_VREFINE 0               // 1: level 0v's end test again per group of a passing chunk, ahead of level 1 (25.11 ms)
 #endif
@@ -1781,6 +1818,18 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
             }
         }
     }
+    // round 13: the lane's point pairs (2p, 2p + 1) for level 0 -- image and allowance from the set-up, the threshold from the two
+    // points' thr1 as they stand now (after pass 2's refresh above); renewed wherever thr1 can change (the end of the rare path)
+    constexpr bool QUAD = PAIRS && R >= 2 && OA_SORTED_QUAD;
+    float qhm[QUAD ? R / 2 : 1], qhw[QUAD ? R / 2 : 1], qthr[QUAD ? R / 2 : 1];
+    if constexpr (QUAD) {
+#pragma unroll
+        for (int p = 0; p < R / 2; ++p) {
+            const float4 rq = rec[3 * ns_pad + rec0 + 64 * p];
+            qhm[p] = rq.x; qhw[p] = rq.y;
+            qthr[p] = quad_threshold(thr1[2 * p], thr1[2 * p + 1], rq.z);
+        }
+    }
 
     int g_begin, g_end;
     split_range_of(split, n_splits, n_groups_pad, TG, g_begin, g_end);
@@ -1845,56 +1894,103 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
         constexpr int GW = OA_SORTED_GW < TG ? OA_SORTED_GW : TG;
         static_assert(GW % 4 == 0 && TG % GW == 0, "k_nn_search_sorted: blocks of whole chunks of 16 vertices");
         for (int g = 0; g < TG; g += GW) {
-            float m[R], odd[R];
+            bool hit0 = false, hit[R];
+            if constexpr (QUAD) {
+                // level 0 on pairs of vertices AND pairs of the lane's points (round 13; proof in oa_quadgap.hpp): the signed
+                // t = ||m - hm| - hw| - w never exceeds the smallest of the four gaps by more than the pair's allowance, so
+                // t > qthr rules out both vertices for both points.  Per 16 vertices and point pair 24 subtracts and 4 min3 (no
+                // modifier on their sources) where the per-point fold below spends 32 and 8; the same tile reads
+                float qm[R / 2], qodd[R / 2];
 #pragma unroll
-            for (int c = 0; c < GW / 4; ++c) {
-                if constexpr (PAIRS) {
-                    // level 0 on pairs of vertices (round 11; proof in the header): per 16 vertices 4 float4 of pair images,
-                    // 16 subtracts (8 of them with |.| on their first source) and 4 min3 per point -- a quarter of a min3 per
-                    // pair where the single gaps below take half of one
+                for (int c = 0; c < GW / 4; ++c) {
                     float4 MW[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) MW[k] = tilew[cur][g + 4 * c + k];
 #pragma unroll
-                    for (int r = 0; r < R; ++r) {
+                    for (int p = 0; p < R / 2; ++p) {
                         float a[8];
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
-                            a[2 * k] = pair_gap(MW[k].x, MW[k].y, hu[r]); a[2 * k + 1] = pair_gap(MW[k].z, MW[k].w, hu[r]);
+                            a[2 * k] = quad_gap(MW[k].x, MW[k].y, qhm[p], qhw[p]); a[2 * k + 1] = quad_gap(MW[k].z, MW[k].w, qhm[p], qhw[p]);
                         }
-                        float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(m[r], odd[r]), a[0]);
+                        float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(qm[p], qodd[p]), a[0]);
 #pragma unroll
                         for (int k = 1; k + 1 < 8; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);   // v_min3_f32
-                        m[r] = v;
-                        odd[r] = a[7];
-                    }
-                } else {
-                    float4 QU[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) QU[k] = tile[cur][3 * (g + 4 * c + k)];
-#pragma unroll
-                    for (int r = 0; r < R; ++r) {                  // level 0: one subtract + half a min3 per pair, no branch inside
-                        float a[16];
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            a[4 * k] = __builtin_fabsf(QU[k].x - hu[r]); a[4 * k + 1] = __builtin_fabsf(QU[k].y - hu[r]);
-                            a[4 * k + 2] = __builtin_fabsf(QU[k].z - hu[r]); a[4 * k + 3] = __builtin_fabsf(QU[k].w - hu[r]);
-                        }
-                        float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(m[r], odd[r]), a[0]);
-#pragma unroll
-                        for (int k = 1; k + 1 < 16; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);   // v_min3_f32
-                        m[r] = v;
-                        odd[r] = a[15];
+                        qm[p] = v;
+                        qodd[p] = a[7];
                     }
                 }
-            }
-            bool hit0 = false, hit[R];
+                // a pair that cannot rule the block out marks BOTH its points: level 0v and levels 1-3 decide per point as they
+                // always did (a hit that the per-point fold of round 11 would not have given is wasted work there, never a
+                // wrong answer).  Folding the block again per point for exactly round 11's hit[r] measured slower: 17.17 against
+                // 16.03 ms per step at 1M <-> 1M (profiles/r13a_point_pairs.txt)
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                hit[r] = !(__builtin_fminf(m[r], odd[r]) > thr1[r]);
-                hit0 |= hit[r];
+                for (int p = 0; p < R / 2; ++p) {
+                    hit[2 * p] = hit[2 * p + 1] = !(__builtin_fminf(qm[p], qodd[p]) > qthr[p]);
+                    hit0 |= hit[2 * p];
+                }
+                if (!hit0) continue;
+                // the points' own coordinates from their records again, through a laundered index: the scan itself needs only
+                // the pairs' images, and 3 R registers held through it for the rare path's sake are what pushed <4, 256, true>
+                // into scratch
+                int rh = rec0;
+                asm volatile("" : "+v"(rh));
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const float4 ra = rec[rh + 64 * r];
+                    hu[r] = ra.x; hv[r] = ra.y; hd[r] = ra.z;
+                }
+            } else {
+                float m[R], odd[R];
+#pragma unroll
+                for (int c = 0; c < GW / 4; ++c) {
+                    if constexpr (PAIRS) {
+                        // level 0 on pairs of vertices (round 11; proof in the header): per 16 vertices 4 float4 of pair images,
+                        // 16 subtracts (8 of them with |.| on their first source) and 4 min3 per point -- a quarter of a min3 per
+                        // pair where the single gaps below take half of one
+                        float4 MW[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) MW[k] = tilew[cur][g + 4 * c + k];
+#pragma unroll
+                        for (int r = 0; r < R; ++r) {
+                            float a[8];
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                a[2 * k] = pair_gap(MW[k].x, MW[k].y, hu[r]); a[2 * k + 1] = pair_gap(MW[k].z, MW[k].w, hu[r]);
+                            }
+                            float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(m[r], odd[r]), a[0]);
+#pragma unroll
+                            for (int k = 1; k + 1 < 8; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);   // v_min3_f32
+                            m[r] = v;
+                            odd[r] = a[7];
+                        }
+                    } else {
+                        float4 QU[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) QU[k] = tile[cur][3 * (g + 4 * c + k)];
+#pragma unroll
+                        for (int r = 0; r < R; ++r) {                  // level 0: one subtract + half a min3 per pair, no branch inside
+                            float a[16];
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                a[4 * k] = __builtin_fabsf(QU[k].x - hu[r]); a[4 * k + 1] = __builtin_fabsf(QU[k].y - hu[r]);
+                                a[4 * k + 2] = __builtin_fabsf(QU[k].z - hu[r]); a[4 * k + 3] = __builtin_fabsf(QU[k].w - hu[r]);
+                            }
+                            float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(m[r], odd[r]), a[0]);
+#pragma unroll
+                            for (int k = 1; k + 1 < 16; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);   // v_min3_f32
+                            m[r] = v;
+                            odd[r] = a[15];
+                        }
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    hit[r] = !(__builtin_fminf(m[r], odd[r]) > thr1[r]);
+                    hit0 |= hit[r];
+                }
+                if (!hit0) continue;
             }
-            if (!hit0) continue;
             if constexpr (VCHUNK) {
                 // level 0v (round 8; proof in the header): which of the block's chunks of 4 CG vertices can hold a vertex within
                 // thr1 of the point along v, from each chunk's two ends -- 2 fma, a max and a compare per chunk where round 7 folded
@@ -1965,6 +2061,14 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                                                     qmax, best[r], bidx[r], thr1[r], thr2[r]);
                         }
                     }
+                }
+                if constexpr (QUAD) {
+                    // thr1 may have fallen: the point pairs' thresholds anew (the allowance again from the set-up's record, through
+                    // a laundered index, instead of a register per pair held through the scan)
+                    int rq = rec0;
+                    asm volatile("" : "+v"(rq));
+#pragma unroll
+                    for (int p = 0; p < R / 2; ++p) qthr[p] = quad_threshold(thr1[2 * p], thr1[2 * p + 1], rec[3 * ns_pad + rq + 64 * p].z);
                 }
             } else {                                               // OA_NN_VCHUNK=0: the rare loop of round 6, as it was
 #pragma unroll 1

@@ -55,6 +55,8 @@ template <int OP> __global__ __launch_bounds__(256) void burn(float *out, int tr
                 if (OP == 40) asm volatile("v_sub_f32_e64 %0, |%0|, %1" : "+v"(a[k]) : "v"(b));          // round 11: the pair gap's second subtract
                 if (OP == 41) asm volatile("v_sub_f32 %0, %0, %1\n\tv_sub_f32_e64 %0, |%0|, %2" : "+v"(a[k]) : "v"(b), "v"(c));   // (two instructions)
                 if (OP == 42) asm volatile("v_fma_f32 %0, |%0|, 1.0, -%1" : "+v"(a[k]) : "v"(b));         // the same value through the fma pipe
+                if (OP == 43) asm volatile("v_sub_f32 %0, %0, %1\n\tv_sub_f32_e64 %0, |%0|, %2\n\tv_sub_f32_e64 %0, |%0|, %1"    // round 13: the quad gap's chain
+                                           : "+v"(a[k]) : "v"(b), "v"(c));                                   // (three instructions)
                 if (OP == 19) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(*(double*)&a[k & ~1]) : "v"(*(double*)&b));
             }
     }
@@ -65,12 +67,14 @@ template <int OP> __global__ __launch_bounds__(256) void burn(float *out, int tr
 //   MIX 0 (until round 10)  per 2 vertices  sub, sub, min3(acc, |t0|, |t1|)                          2 full-rate : 1 half-rate
 //   MIX 1 (round 11)        per 4 vertices  sub, sub |.|, sub, sub |.|, min3(acc, |t0|, |t1|)        4 : 1
 //   MIX 2                   MIX 1 with v_fma_f32 d, |a|, 1.0, -w for the second subtract
+//   MIX 3 (round 13)        per 8 (vertex, point) pairs: two chains sub, sub |.|, sub |.| and min3(acc, t0, t1), no modifier
+//                           on the min's sources (oa_quadgap.hpp)                                      6 : 1
 template <int MIX> __global__ __launch_bounds__(256) void mix(float *out, int trips, float seed)
 {
     float a[16], q[32];
     for (int k = 0; k < 16; ++k) a[k] = seed + k + threadIdx.x;
     for (int k = 0; k < 32; ++k) q[k] = seed * 0.5f + k;
-    const float h = seed * 0.25f;
+    const float h = seed * 0.25f, hw = seed * 0.125f;
     for (int t = 0; t < trips; ++t) {
 #pragma unroll
         for (int u = 0; u < 4; ++u)
@@ -88,6 +92,10 @@ template <int MIX> __global__ __launch_bounds__(256) void mix(float *out, int tr
                     asm volatile("v_sub_f32 %1, %3, %5\n\tv_sub_f32 %2, %4, %5\n\tv_fma_f32 %1, |%1|, 1.0, -%4\n\tv_fma_f32 %2, |%2|, 1.0, -%3\n\t"
                                  "v_min3_f32 %0, %0, |%1|, |%2|"
                                  : "+v"(a[k]), "=&v"(t0), "=&v"(t1) : "v"(q[2 * k]), "v"(q[2 * k + 1]), "v"(h));
+                if (MIX == 3)
+                    asm volatile("v_sub_f32 %1, %3, %5\n\tv_sub_f32 %2, %4, %5\n\tv_sub_f32_e64 %1, |%1|, %6\n\tv_sub_f32_e64 %2, |%2|, %6\n\t"
+                                 "v_sub_f32_e64 %1, |%1|, %4\n\tv_sub_f32_e64 %2, |%2|, %3\n\tv_min3_f32 %0, %0, %1, %2"
+                                 : "+v"(a[k]), "=&v"(t0), "=&v"(t1) : "v"(q[2 * k]), "v"(q[2 * k + 1]), "v"(h), "v"(hw));
             }
     }
     float s = 0; for (int k = 0; k < 16; ++k) s += a[k];
@@ -135,5 +143,9 @@ int main()
     run<17>("v_sub_f32 (again)"); run<40>("v_sub_f32_e64 |a|, b"); run<41>("v_sub_f32 -> v_sub_f32_e64 |.|", 2); run<42>("v_fma_f32 |a|, 1.0, -b");
     run_mix<0>("level 0 until round 10 (2:1)", 4, 3, 2); run_mix<1>("level 0 on pairs, sub (4:1)", 4, 5, 4); run_mix<2>("level 0 on pairs, fma (4:1)", 4, 5, 4);
     run_mix<0>("level 0 until round 10 (2:1)", 8, 3, 2); run_mix<1>("level 0 on pairs, sub (4:1)", 8, 5, 4);
+    // round 13 (profiles/r13a_point_pairs.txt): the quad gap | |m - hm| - hw | - w, three dependent subtracts, two with |.| on a source
+    run<17>("v_sub_f32 (again)"); run<43>("v_sub -> v_sub_e64 |.| -> v_sub_e64 |.|", 3);
+    run_mix<1>("level 0 on pairs, sub (4:1)", 4, 5, 4); run_mix<3>("level 0 on point pairs (6:1)", 4, 7, 8);
+    run_mix<1>("level 0 on pairs, sub (4:1)", 8, 5, 4); run_mix<3>("level 0 on point pairs (6:1)", 8, 7, 8);
     return 0;
 }
