@@ -390,6 +390,50 @@ int oa_set_reciprocal(oa_ctx *ctx, int on, double ratio);
  * brings the plain pairs back). */
 #define OA_TRIM_AUTO (-1.0)
 int oa_set_trim(oa_ctx *ctx, double fraction, double fraction_min, double lambda);
+
+/* EXTENSION (not in the reference; Turk & Levoy 1994, Rusinkiewicz & Levoy 2001 "Efficient variants of ICP" 3.4): the target's
+ * BOUNDARY, and the rejection of pairs whose correspondence lies on it.  Where the source reaches beyond a partial scan every
+ * source point outside the overlap pairs with the scan's rim; the rim is a property of the target alone, found once.
+ *
+ * Mesh targets (oa_set_target_mesh): exact, integers only.
+ *   - Local edge j of triangle t joins corners j and (j + 1) mod 3 (ab, bc, ca: the order of oa_deviation's edge features).
+ *   - An undirected edge {u, v} with u != v is a boundary edge iff exactly one triangle, each triangle counted once, lists both
+ *     u and v.  Edges with u == v are never boundary; edges shared by three or more triangles are not boundary.
+ *   - A vertex is a boundary vertex iff it is an end of a boundary edge.
+ *   - edge_mask[n_tris]: uint8, bit j = local edge j is a boundary edge.  vertex_mask[n_verts]: uint8, 0 or 1.
+ *   - Coordinates play no part: zero-area triangles count like any other.
+ * Point-cloud targets (oa_set_target): the angle criterion with parameters k and angle_deg.  The target's normals must be
+ * installed (oa_set_target_normals, oa_set_normals, or an installed estimate), else OA_E_STATE.  For vertex i with float32
+ * normal n, everything in fp64 on the float32 values:
+ *   - Its neighbours are the first k entries of oa_target_knn's row of k + 1 whose index is not i.
+ *   - The tangent basis is u = normalise(n x e) and v = n^ x u, e the coordinate axis of n's smallest-magnitude component
+ *     (lowest axis on ties).
+ *   - A neighbour whose tangent projection (d.u, d.v) is (0, 0) or not finite is skipped.
+ *   - theta = atan2(d.v, d.u), sorted ascending; the gaps are the consecutive differences plus the wrap-around gap
+ *     (theta_0 + 2 pi - theta_last).  The vertex is flagged iff the largest gap is greater than angle_deg pi / 180.
+ *   - A vertex with a zero or non-finite normal, or with fewer than 3 usable neighbours, is flagged.
+ *   - 3 <= k <= min(63, nt - 1) and 0 < angle_deg < 360, else OA_E_BAD_ARG.  The defaults of the bindings are 16 and 90.
+ *
+ * oa_target_boundary builds the masks if need be and copies them out; either pointer may be NULL.  k and angle_deg are ignored
+ * for a mesh; edge_mask must be NULL for a cloud (OA_E_BAD_ARG).  OA_E_STATE without a target, and on a multi-device context
+ * (single-device).  The masks are kept until a new target upload; a cloud's also until its normals or (k, angle_deg) change.
+ * Ends a running oa_iterate sequence.
+ *
+ * oa_set_reject_boundary(on): a pair that pair_eval accepts (dist < thresh, and the normal-angle test when it is on) is dropped
+ * when it lies on the boundary.  Surface mode: the closest point on the winning triangle lies on an edge whose bit is set, or on
+ * a vertex whose mask is 1 (the region is oa_deviation's `feature`; a face is never on the boundary).  Vertex mode: the winning
+ * vertex is flagged.  A step runs search -> [reciprocal check] -> boundary verdict -> [trim] -> [estimated robust scale] ->
+ * accumulate; a rejected pair is rejected as the reciprocal check rejects one: it leaves the sums of all three metrics, the
+ * weighted kernels, K, mean and std, the trim's candidates, the automatic scale's quantile, and oa_make_pairs.  oa_nn_search,
+ * oa_deviation, oa_score_poses and the coarse stages do not look at the setting.  Fewer than 3 survivors is OA_E_TOO_FEW_PAIRS.
+ * The masks are built before the loop starts, with the setting's (k, angle_deg): the setter checks 3 <= k <= 63 and the angle, the
+ * build holds k against the target (k > nt - 1: OA_E_BAD_ARG from the loop, the context stays usable).  on == 0 (the default) changes nothing: the same
+ * launches, the same bits.  The setting survives uploads and oa_set_matrices; changing it ends a running oa_iterate sequence.
+ * Single-device contexts holding the whole selection: with the setting on, loops and oa_make_pairs of a multi-device context,
+ * oa_run_begin / oa_iter_partial, and any loop over a source uploaded with shard_count > 1 fail with OA_E_STATE (the context
+ * stays usable; oa_set_reject_boundary(ctx, 0, 16, 90) brings the plain pairs back). */
+int oa_target_boundary(oa_ctx *ctx, int k, double angle_deg, uint8_t *vertex_mask, uint8_t *edge_mask);
+int oa_set_reject_boundary(oa_ctx *ctx, int on, int k, double angle_deg);
 /* EXTENSION: one weight per source vertex (host, float32, n_verts as uploaded with oa_set_source; finite and >= 0), gathered
  * into the selection's order -- "trust this region less", where vlist can only say yes or no.  w == NULL switches the weights
  * off (every w_vertex = 1); a new source upload forgets them.  OA_E_STATE before oa_set_source; OA_E_BAD_ARG for a count other
@@ -464,7 +508,13 @@ int oa_reset_seeds(oa_ctx *ctx);
                                       * oa_set_source or oa_set_trim until a step runs -- as are the next two */
 #define OA_STAT_TRIM_KEPT       42   /* candidates of the last step that stayed */
 #define OA_STAT_TRIM_CUT        43   /* the cut q of the last step, as a double; 0 when off or K_q = 0 */
-#define OA_STAT_ENQUEUED_CHILD  1000   /* + i: the same count for child i alone */
+#define OA_STAT_REJECT_BOUNDARY 44   /* 1 when oa_set_reject_boundary is on */
+#define OA_STAT_BOUNDARY_REJECTED 45 /* pairs of the last step that passed everything before the verdict, the reciprocal check included,
+                                      * and lay on the target's boundary; 0 when off, and after oa_set_source or oa_set_reject_boundary until a step runs */
+#define OA_STAT_TARGET_BOUNDARY 46   /* 1 when the boundary masks are built for the current target */
+#define OA_STAT_BOUNDARY_VERTICES 47 /* flagged vertices of the built masks (0 when not built) */
+#define OA_STAT_BOUNDARY_EDGES  48   /* boundary edges of the built masks (0 for a cloud, or when not built) */
+#define OA_STAT_ENQUEUED_CHILD  1000  /* + i: the same count for child i alone */
 int oa_get_stat(oa_ctx *ctx, int what, double *value);
 /* why the exchange is what it is (AUTO's reason for not taking RCCL, librccl's error, "RCCL was aborted: ..."), or "" */
 const char *oa_exchange_note(oa_ctx *ctx);

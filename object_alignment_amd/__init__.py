@@ -36,6 +36,33 @@ def fpfh(xyz, normals=None, k=16, normal_k=16, device=0):
         return eng.target_fpfh(k=min(k, len(xyz)), keep=False)
 
 
+def mesh_boundary(verts, tris, device=0):
+    """The boundary of ANY triangle mesh, found on the GPU: (vertex_mask uint8 (n_verts,), edge_mask uint8 (n_tris,)) -- bit j of
+    edge_mask[t] says that local edge j of triangle t (ab, bc, ca) belongs to exactly one triangle, vertex_mask marks the ends of
+    such edges (IcpEngine.target_boundary).  Opens a context of its own on `device` and uploads the mesh as its target."""
+    from .engine import IcpEngine
+    with IcpEngine(int(device)) as eng:
+        eng.set_target_mesh(verts, tris)
+        return eng.target_boundary()
+
+
+def cloud_boundary(xyz, normals, k=16, angle_deg=90.0, device=0):
+    """The rim of ANY point cloud by the angle criterion, found on the GPU: vertex_mask uint8 (n,), 1 where the largest angular
+    gap between a point's k nearest neighbours, seen in its tangent plane, exceeds angle_deg (IcpEngine.target_boundary).
+    normals: (n, 3), or "estimate" (PCA normals from every point's k nearest neighbours).  Opens a context of its own on
+    `device` and uploads xyz as its target."""
+    from .engine import IcpEngine
+    if isinstance(normals, str) and normals != "estimate":
+        raise ValueError("cloud_boundary: normals %r (an array of normals, or 'estimate')" % (normals,))
+    with IcpEngine(int(device)) as eng:
+        eng.set_target(xyz)
+        if isinstance(normals, str):
+            eng.estimate_target_normals(k=int(k), orient="none", install=True)
+        else:
+            eng.set_target_normals(normals)
+        return eng.target_boundary(k=k, angle_deg=angle_deg)[0]
+
+
 def voxel_downsample(xyz, voxel, normals=None, origin=None, device=0):
     """Voxel-grid downsample of ANY point cloud on the GPU: one row per occupied cell of edge `voxel` -- the members' mean, the
     normalised sum of their normals, their number and the index of the member nearest to the mean (a dict: xyz, normals or

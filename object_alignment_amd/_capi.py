@@ -50,6 +50,11 @@ OA_STAT_TRIM_CANDIDATES = 41
 OA_STAT_TRIM_KEPT = 42
 OA_STAT_TRIM_CUT = 43
 OA_TRIM_AUTO = -1.0
+OA_STAT_REJECT_BOUNDARY = 44
+OA_STAT_BOUNDARY_REJECTED = 45
+OA_STAT_TARGET_BOUNDARY = 46
+OA_STAT_BOUNDARY_VERTICES = 47
+OA_STAT_BOUNDARY_EDGES = 48
 
 # every symbol include/oa_icp.h declares (tests check that the library exports all of them)
 SYMBOLS = [
@@ -70,6 +75,7 @@ SYMBOLS = [
     "oa_voxel_downsample",
     "oa_deviation", "oa_get_mesh_pseudonormals",
     "oa_set_reciprocal", "oa_set_trim",
+    "oa_target_boundary", "oa_set_reject_boundary",
 ]
 
 
@@ -226,6 +232,8 @@ def load(experiments: bool = False):
     L.oa_deviation.argtypes = [vp, C.POINTER(DeviationSettings), dp, dp, fp, ip, C.POINTER(C.c_int8), ip, C.POINTER(DeviationReport)]
     L.oa_get_mesh_pseudonormals.argtypes = [vp, fp, fp]
     L.oa_set_reciprocal.argtypes = [vp, C.c_int, C.c_double]
+    L.oa_target_boundary.argtypes = [vp, C.c_int, C.c_double, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
+    L.oa_set_reject_boundary.argtypes = [vp, C.c_int, C.c_int, C.c_double]
     L.oa_set_trim.argtypes = [vp, C.c_double, C.c_double, C.c_double]
     _libs[experiments] = L
     return L

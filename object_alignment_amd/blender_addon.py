@@ -86,12 +86,16 @@ if bpy is not None:
             default=False)
         icp_trim_min: FloatProperty(
             name="ICP Trim Floor", description="Smallest share an estimated trim may fall to", default=0.3, min=0.01, max=1)
+        icp_reject_boundary: BoolProperty(
+            name="ICP Reject Boundary Pairs", description="Drop a pair whose closest point lies on the open edge of the object aligned to (a whole model onto a partial scan)",
+            default=False)
 
         def draw(self, context):
             col = self.layout.column()
             for name in ("icp_iterations", "redraw_frequency", "sample_fraction", "min_start", "target_d", "use_target",
                          "take_m_with", "align_meth", "icp_metric", "icp_robust_loss", "icp_robust_scale", "icp_robust_quantile",
-                         "icp_robust_scale_min", "icp_reciprocal", "icp_reciprocal_ratio", "icp_trim", "icp_trim_auto", "icp_trim_min"):
+                         "icp_robust_scale_min", "icp_reciprocal", "icp_reciprocal_ratio", "icp_trim", "icp_trim_auto", "icp_trim_min",
+                         "icp_reject_boundary"):
                 col.prop(self, name)
 
     class VIEW3D_PT_object_alignment(Panel):
@@ -109,7 +113,7 @@ if bpy is not None:
             if prefs is not None:
                 box = self.layout.box()
                 for name in ("icp_iterations", "sample_fraction", "min_start", "target_d", "use_target", "icp_reciprocal",
-                             "icp_reciprocal_ratio", "icp_trim", "icp_trim_auto", "icp_trim_min"):
+                             "icp_reciprocal_ratio", "icp_trim", "icp_trim_auto", "icp_trim_min", "icp_reject_boundary"):
                     box.prop(prefs, name)
 
     def _addon_prefs():

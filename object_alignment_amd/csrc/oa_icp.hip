@@ -20,6 +20,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "oa_sort.hpp"
 #include "oa_voxel.hpp"
 #include "oa_deviation.hpp"
+#include "oa_boundary.hpp"
 #include "oa_tunables.hpp"            // every OA_* knob: read once, oa_ctx::tune (plain C++)
 #include "../../include/oa_icp.h"
 
@@ -442,6 +443,19 @@ struct oa_ctx {
     uint32_t *d_trim_hist = nullptr; // fixed share: the select's SEL_LEVELS histograms
     uint32_t *d_trim_sorted = nullptr; int *d_trim_order = nullptr; char *d_trim_tmp = nullptr;   // estimated share: the sorted keys, their order, the sort's scratch
     double *d_trim_tiles = nullptr; oa::TrimTileMin *d_trim_min = nullptr;                        // ... the scan's tile sums / bases and the tiles' minima
+    // oa_set_reject_boundary / oa_target_boundary: the target's rim (oa_boundary.hpp).  The setting survives uploads and
+    // oa_set_matrices; the masks are built on demand and kept until a new target (the cloud's also until its normals or (k, angle) change)
+    bool bnd_on = false;
+    int bnd_k = 16;
+    double bnd_angle = 90.0;
+    unsigned char *d_bnd_vmask = nullptr, *d_bnd_emask = nullptr;   // nt bytes; n_tris bytes (mesh targets)
+    bool bnd_ok = false;
+    int bnd_built_k = 0; double bnd_built_angle = 0.0;              // what a cloud's mask was built with
+    long long bnd_n_vertices = 0, bnd_n_edges = 0;                  // OA_STAT_BOUNDARY_VERTICES / _EDGES
+    double last_bnd_ms = 0.0;                                       // host time of the last mask build
+    unsigned *d_bnd_count = nullptr;                                // k_boundary_verdict's counters (BND_COUNT_WORDS): word 2 = slots the last step rejected
+    int *d_corner_order = nullptr; long long *d_corner_row = nullptr;   // the mesh's corners by vertex (CSR rows): the pseudo-normals and the
+    bool corner_ok = false;                                             // boundary share them; a new target forgets them
     double pivot[3] = { 0, 0, 0 };
     // launch geometry for k_nn_search
     int n_splits = 1, acc_blocks = 1;
@@ -722,6 +736,7 @@ int tri_ring_lazy(oa_ctx *c, bool counting)
     return c->tri_iters > TRI_RING_LAZY_ITERS ? build_tri_ring(c) : OA_OK;
 }
 int build_bvh(oa_ctx *c, bool tri);
+int ensure_boundary(oa_ctx *c, int k, double angle_deg);
 int build_bvh_arrays(oa_ctx *c, bool tri, const float *d_xyz, int stride, int n, const double frame_lo[3], const double frame_hi[3],
                      oa::BvhParams &bp, float4 *&d_box, float4 *&d_prims, bool &ok);
 int scan_counts(oa_ctx *c, const int *d_counts, int n, long long *d_off, DevTmp<char> &tmp);
@@ -825,7 +840,54 @@ int refuse_recip_shard(const oa_ctx *c, const char *who)
 // oa_set_trim (oa_trim.hpp): the verdict bytes are the reciprocal check's, so a trimmed step accumulates through the RECIP kernels
 inline bool trim_on(const oa_ctx *c) { return c->trim_fraction != 0.0; }
 inline bool trim_auto(const oa_ctx *c) { return c->trim_fraction < 0.0; }
-inline bool verdict_on(const oa_ctx *c) { return c->recip_on || trim_on(c); }
+inline bool verdict_on(const oa_ctx *c) { return c->recip_on || trim_on(c) || c->bnd_on; }
+
+// oa_set_reject_boundary (oa_boundary.hpp): the verdict goes into the reciprocal check's bytes too.  The target is replicated, so a
+// shard could answer for itself -- but the verdict byte's path has never run in shards
+const char *const BND_ONE_DEVICE = ": oa_set_reject_boundary runs on a single-device context through oa_run / oa_iterate / oa_make_pairs (call oa_set_reject_boundary(ctx, 0, 16, 90) for this path)";
+int refuse_bnd_shard(const oa_ctx *c, const char *who)
+{
+    if (c->bnd_on && (c->parent || c->src_shards > 1))
+        return fail(OA_E_STATE, "%s with oa_set_reject_boundary on needs the whole selection on one context: this one holds a shard (upload shard 0 of 1, or call oa_set_reject_boundary(ctx, 0, 16, 90))", who);
+    return OA_OK;
+}
+
+// k_boundary_verdict's counters back to zero, and the host waits (recip_clear_count's reasons)
+int bnd_clear_count(oa_ctx *c)
+{
+    if (!c->d_bnd_count) return OA_OK;
+    HIPCHK(hipMemsetAsync(c->d_bnd_count, 0, sizeof(unsigned) * oa::BND_COUNT_WORDS, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
+// what a step with the setting on needs, before its loop starts: the counters, the verdict bytes and the target's masks
+int ensure_bnd_step(oa_ctx *c)
+{
+    if (!c->bnd_on) return OA_OK;
+    if (!c->d_bnd_count) {
+        HIPCHK(dev_malloc(&c->d_bnd_count, sizeof(unsigned) * oa::BND_COUNT_WORDS));
+        const int rcc = bnd_clear_count(c);
+        if (rcc) return rcc;
+    }
+    if (c->ns > 0 && !c->d_recip_ok) HIPCHK(dev_malloc(&c->d_recip_ok, (size_t)c->ns));
+    return ensure_boundary(c, c->bnd_k, c->bnd_angle);
+}
+
+// search -> [k_recip_check] -> THIS -> [the trim] -> ... -> the accumulation: byte 0 for every pair on the target's boundary
+int launch_boundary(oa_ctx *c)
+{
+    if (c->ns <= 0) return OA_OK;                                   // no slot to judge
+    if (!c->recip_on) HIPCHK(hipMemsetAsync(c->d_recip_ok, 1, (size_t)c->ns, c->stream));   // (else k_recip_check has just written every byte)
+    const unsigned blocks = (unsigned)std::max(1, std::min((c->ns + oa::BND_VERDICT_THREADS - 1) / oa::BND_VERDICT_THREADS, c->n_cu * 2));
+    hipLaunchKernelGGL(oa::k_boundary_verdict, dim3(blocks), dim3(oa::BND_VERDICT_THREADS), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4,
+                       c->ns, (const float *)c->d_tgt_xyz, (const unsigned long long *)c->d_keys,
+                       c->surface ? (const float4 *)nullptr : (const float4 *)c->d_win, c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr,
+                       normal_test(c), (const int *)c->d_tris, (const unsigned char *)c->d_bnd_emask, (const unsigned char *)c->d_bnd_vmask,
+                       c->d_recip_ok, c->d_bnd_count);
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
 
 // the cut is an order statistic of the world's residuals: a context that holds only a shard cannot form it
 const char *const TRIM_ONE_DEVICE = ": oa_set_trim needs every selected source point's residual on one device: it runs on a single-device context through oa_run / oa_iterate / oa_make_pairs (call oa_set_trim(ctx, 0, 0, 2) for this path)";
@@ -1345,7 +1407,7 @@ int launch_robust_scale(oa_ctx *c)
 int launch_trim(oa_ctx *c, int metric)
 {
     if (c->ns <= 0) return OA_OK;                                   // no slot to judge: nothing is allocated for it either (ensure_trim)
-    if (!c->recip_on) HIPCHK(hipMemsetAsync(c->d_recip_ok, 1, (size_t)c->ns, c->stream));   // (else k_recip_check has just written every byte)
+    if (!c->recip_on && !c->bnd_on) HIPCHK(hipMemsetAsync(c->d_recip_ok, 1, (size_t)c->ns, c->stream));   // (else k_recip_check / launch_boundary has just written every byte)
     HIPCHK(hipMemsetAsync(c->d_trim_hist, 0, sizeof(uint32_t) * oa::SEL_LEVELS * oa::SEL_BINS, c->stream));
     launch_residual_keys<true>(c, metric, c->d_trim_hist);
     const oa::DevState *st = c->d_state;
@@ -1422,6 +1484,7 @@ int launch_search_accumulate(oa_ctx *c, bool timed, oa::RowSel &sel, bool &fused
     }
     if (!fused) {
         if (c->recip_on && (rc = launch_recip(c, plane_row_metric(c)))) return rc;
+        if (c->bnd_on && (rc = launch_boundary(c))) return rc;
         if (trim_on(c) && (rc = launch_trim(c, c->metric))) return rc;
         if (auto_scale(c) && (rc = launch_robust_scale(c))) return rc;
         if ((rc = launch_accumulate(c, false, nullptr, nullptr))) return rc;
@@ -1583,10 +1646,12 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
         return fail(OA_E_CAPACITY, "a weighted loop takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS, c->ns);
     if ((rc = refuse_recip_shard(c, "a loop"))) return rc;
     if ((rc = refuse_trim_shard(c, "a loop"))) return rc;
+    if ((rc = refuse_bnd_shard(c, "a loop"))) return rc;
     if ((rc = use_device(c))) return rc;
     if ((rc = ensure_common(c))) return rc;
     if ((rc = ensure_recip(c))) return rc;                          // (the source tree: before the loop starts, never inside it)
     if ((rc = ensure_trim(c))) return rc;
+    if ((rc = ensure_bnd_step(c))) return rc;                       // (the target's masks: on this stream, before the loop starts)
     if ((rc = ensure_history(c, iters == ITERATE_OPEN ? ITERATE_RING : iters))) return rc;   // oa_iterate: a small ring
     if (auto_scale(c)) {                                          // the selection's buffers; its histograms start (and are kept) at zero
         if (!c->d_rkeys) HIPCHK(dev_malloc(&c->d_rkeys, sizeof(uint32_t) * (size_t)std::max(1, c->ns)));
@@ -2523,6 +2588,7 @@ OA_EXPORT void oa_destroy(oa_ctx *c)
     OA_FREE(d_sel); OA_FREE(d_src_n); OA_FREE(d_tgt_n); OA_FREE(d_tgt_feat); OA_FREE(d_w); OA_FREE(d_rkeys); OA_FREE(d_sel_hist); OA_FREE(d_src4o); OA_FREE(d_perm);
     OA_FREE(d_sbvh_box); OA_FREE(d_sbvh_prims); OA_FREE(d_recip_ok); OA_FREE(d_recip_count);
     OA_FREE(d_trim); OA_FREE(d_trim_hist); OA_FREE(d_trim_sorted); OA_FREE(d_trim_order); OA_FREE(d_trim_tmp); OA_FREE(d_trim_tiles); OA_FREE(d_trim_min);
+    OA_FREE(d_bnd_vmask); OA_FREE(d_bnd_emask); OA_FREE(d_bnd_count); OA_FREE(d_corner_order); OA_FREE(d_corner_row);
     OA_FREE(d_tris); OA_FREE(d_pn_face); OA_FREE(d_pn_vertex); OA_FREE(d_pn_edge);
 #undef OA_FREE
     if (c->h_hist_map) (void)hipHostFree(c->h_hist_map);
@@ -2827,6 +2893,8 @@ int set_target_common(oa_ctx *c, const float *xyz, int64_t n, int on_device, boo
     dev_free(c->d_tfine_table); dev_free(c->d_tfine_rec);
     dev_free(c->d_tris); dev_free(c->d_pn_face); dev_free(c->d_pn_vertex); dev_free(c->d_pn_edge);
     c->pn_ok = false;
+    dev_free(c->d_corner_order); dev_free(c->d_corner_row); c->corner_ok = false;
+    dev_free(c->d_bnd_vmask); dev_free(c->d_bnd_emask); c->bnd_ok = false;   // (the masks are the old target's)
     c->tri_ring_ok = false; c->tri_fine_ok = false;
     dev_free(c->d_bvh_box); dev_free(c->d_bvh_prims); dev_free(c->d_tbvh_box); dev_free(c->d_tbvh_prims);
     c->surface = false; c->tri_grid_ok = false; c->n_tris = 0; c->bvh_ok = false; c->tbvh_ok = false;
@@ -3520,6 +3588,7 @@ int source_reset(oa_ctx *c, long long count, long long begin, long long n_verts)
     dev_free(c->d_src4); dev_free(c->d_keys); dev_free(c->d_prev); dev_free(c->d_win); dev_free(c->d_wsafe); dev_free(c->d_sel); dev_free(c->d_src_n); dev_free(c->d_w); dev_free(c->d_rkeys);
     dev_free(c->d_sbvh_box); dev_free(c->d_sbvh_prims); dev_free(c->d_recip_ok); c->sbvh_ok = false;   // (the source tree: a new source forgets it)
     { const int rcc = recip_clear_count(c); if (rcc) return rcc; }  // ... and the old source's count
+    { const int rcc = bnd_clear_count(c); if (rcc) return rcc; }
     trim_free_sized(c);
     { const int rcc = trim_clear(c); if (rcc) return rcc; }         // (oa_set_trim's figures spoke of the old source)
     dev_free(c->d_src4o); dev_free(c->d_perm); dev_free(c->d_members); dev_free(c->d_pos);
@@ -3787,6 +3856,7 @@ OA_EXPORT int oa_set_normals(oa_ctx *c, const float *src_normals, int64_t n_vert
     HIPCHK(hipMemcpyAsync(tmp, src_normals, sizeof(float) * 3 * (size_t)n_verts, hipMemcpyHostToDevice, c->stream));
     dev_free(c->d_src_n);
     if (!keep_tgt) dev_free(c->d_tgt_n);
+    if (!keep_tgt && !c->surface) c->bnd_ok = false;                // (a cloud's boundary mask was built from the old normals)
     HIPCHK(dev_malloc(&c->d_src_n, sizeof(float) * 3 * (size_t)std::max(1, c->ns)));
     if (c->ns > 0)
         hipLaunchKernelGGL(oa::k_gather_rows3, dim3((c->ns + 255) / 256), dim3(256), 0, c->stream, (const float *)tmp.p,
@@ -3942,6 +4012,44 @@ OA_EXPORT int oa_set_trim(oa_ctx *c, double fraction, double fraction_min, doubl
     return OA_OK;
 }
 
+namespace {
+// (k, angle_deg) of the cloud criterion; nt = the resident cloud's size, or 0 when there is none to hold k against
+int check_boundary_params(const char *who, int k, double angle_deg, int nt)
+{
+    if (k < 3 || k > oa::BND_MAX_K || (nt > 0 && k > nt - 1))
+        return fail(OA_E_BAD_ARG, "%s: k = %d outside 3 .. min(%d, target vertices - 1)", who, k, oa::BND_MAX_K);
+    if (!(angle_deg > 0.0 && angle_deg < 360.0)) return fail(OA_E_BAD_ARG, "%s: angle_deg = %g outside (0, 360)", who, angle_deg);
+    return OA_OK;
+}
+}  // namespace
+
+OA_EXPORT int oa_set_reject_boundary(oa_ctx *c, int on, int k, double angle_deg)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    // (k is held against the target where the masks are built, ensure_boundary: the setting outlives targets, and switching it
+    //  off must work on a cloud of any size)
+    int rc = check_boundary_params("oa_set_reject_boundary", k, angle_deg, 0);
+    if (rc) return rc;
+    const bool want = on != 0;
+    if (want == c->bnd_on && k == c->bnd_k && angle_deg == c->bnd_angle) return OA_OK;
+    // a changed setting ends the running sequence, as oa_set_reciprocal does
+    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
+    else if (c->loop_active) {
+        if ((rc = use_device(c))) return rc;
+        if ((rc = fetch_state(c))) return rc;
+        c->loop_active = false;
+    }
+    // (a multi-device parent keeps the setting itself and refuses the loops: its children never see it)
+    c->bnd_on = want;
+    c->bnd_k = k;
+    c->bnd_angle = angle_deg;
+    if (c->d_bnd_count) {                                           // the last step's count was the old setting's
+        if ((rc = use_device(c))) return rc;
+        if ((rc = bnd_clear_count(c))) return rc;
+    }
+    return OA_OK;
+}
+
 OA_EXPORT int oa_set_source_weights(oa_ctx *c, const float *w, int64_t n_verts)
 {
     if (!c) return fail(OA_E_BAD_ARG, "null context");
@@ -3988,6 +4096,7 @@ OA_EXPORT int oa_set_target_normals(oa_ctx *c, const float *tgt_normals, int64_t
     if (c->loop_active) { HIPCHK(hipStreamSynchronize(c->stream)); c->loop_active = false; }
     if (c->normals_on) HIPCHK(hipStreamSynchronize(c->stream));    // (the array the normal-angle test reads is replaced in place)
     if (!c->d_tgt_n) HIPCHK(dev_malloc(&c->d_tgt_n, sizeof(float) * 3 * (size_t)nt));
+    c->bnd_ok = false;                                              // (a boundary mask was built from the old normals)
     HIPCHK(hipMemcpyAsync(c->d_tgt_n, tgt_normals, sizeof(float) * 3 * (size_t)nt, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return OA_OK;
@@ -4144,6 +4253,17 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
         *value = (double)n;
         return OA_OK;
     }
+    if (what == OA_STAT_REJECT_BOUNDARY) { *value = c->bnd_on ? 1.0 : 0.0; return OA_OK; }
+    if (what == OA_STAT_BOUNDARY_REJECTED) {
+        *value = 0.0;
+        if (!c->bnd_on || !c->d_bnd_count) return OA_OK;
+        int rc = use_device(c);
+        if (rc) return rc;
+        unsigned n = 0;
+        if ((rc = read_small(c, &n, c->d_bnd_count + 2, sizeof n))) return rc;
+        *value = (double)n;
+        return OA_OK;
+    }
     if (what == OA_STAT_TRIM) { *value = c->trim_fraction; return OA_OK; }
     if (what == OA_STAT_TRIM_CANDIDATES || what == OA_STAT_TRIM_KEPT || what == OA_STAT_TRIM_CUT) {
         *value = 0.0;
@@ -4178,6 +4298,9 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
     case OA_STAT_ROBUST_QUANTILE: *value = c->robust_p; return OA_OK;
     case OA_STAT_TARGET_NORMALS: *value = (!c->surface && c->d_tgt_n) ? 1.0 : 0.0; return OA_OK;
     case OA_STAT_TARGET_FEATURES: *value = c->d_tgt_feat ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_TARGET_BOUNDARY: *value = c->bnd_ok ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_BOUNDARY_VERTICES: *value = c->bnd_ok ? (double)c->bnd_n_vertices : 0.0; return OA_OK;
+    case OA_STAT_BOUNDARY_EDGES: *value = c->bnd_ok ? (double)c->bnd_n_edges : 0.0; return OA_OK;
     case OA_STAT_MESH_PSEUDONORMALS: *value = (c->surface && c->pn_ok) ? 1.0 : 0.0; return OA_OK;
     default: return fail(OA_E_BAD_ARG, "oa_get_stat: unknown key %d", what);
     }
@@ -4348,6 +4471,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
 {
     if (c && !c->subs.empty() && c->recip_on) return fail(OA_E_STATE, "oa_make_pairs on a multi-device context%s", RECIP_ONE_DEVICE);
     if (c && !c->subs.empty() && trim_on(c)) return fail(OA_E_STATE, "oa_make_pairs on a multi-device context%s", TRIM_ONE_DEVICE);
+    if (c && !c->subs.empty() && c->bnd_on) return fail(OA_E_STATE, "oa_make_pairs on a multi-device context%s", BND_ONE_DEVICE);
     if (c && !c->subs.empty()) {
         // multi-device: every child pairs its shard (its pairs come out in ascending selection position, with that
         // position); the shards are merged back into vlist order on the host.  Statistics: the children's two-pass
@@ -4411,10 +4535,12 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
     if (!(thresh > 0.0)) return fail(OA_E_BAD_THRESH, "thresh must be > 0 (the reference's make_pairs returns None)");
     if ((rc = refuse_recip_shard(c, "oa_make_pairs"))) return rc;
     if ((rc = refuse_trim_shard(c, "oa_make_pairs"))) return rc;
+    if ((rc = refuse_bnd_shard(c, "oa_make_pairs"))) return rc;
     if ((rc = use_device(c))) return rc;
     if ((rc = ensure_common(c))) return rc;
     if ((rc = ensure_recip(c))) return rc;
     if ((rc = ensure_trim(c))) return rc;
+    if ((rc = ensure_bnd_step(c))) return rc;
     *K = 0;
     if (dstats) { dstats[0] = NAN; dstats[1] = NAN; }
     if (c->ns == 0) return OA_OK;
@@ -4437,6 +4563,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
     if ((rc = push_state_for_oneshot(c, thresh, true))) return rc;
     if ((rc = launch_nn(c, choose_search(c), false))) return rc;
     if (c->recip_on && (rc = launch_recip(c, false))) return rc;
+    if (c->bnd_on && (rc = launch_boundary(c))) return rc;
     if (trim_on(c) && (rc = launch_trim(c, OA_METRIC_POINT))) return rc;   // (the point residual: oa_make_pairs does not look at the metric)
     if ((rc = launch_accumulate(c, true, nullptr, nullptr))) return rc;
     if ((rc = launch_reduce(c, c->d_sums, oa::RowSel{ c->acc_blocks, 0, 0 }, false))) return rc;   // (emitting accumulation: k_pair_accumulate<true>)
@@ -4450,6 +4577,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
             if ((rc = push_state_for_oneshot(c, thresh, true))) { c->d_pivot0 = 0.0; return rc; }
             rc = launch_nn(c, choose_search(c), false);
             if (!rc && c->recip_on) rc = launch_recip(c, false);
+            if (!rc && c->bnd_on) rc = launch_boundary(c);
             if (!rc && trim_on(c)) rc = launch_trim(c, OA_METRIC_POINT);
             if (!rc) rc = launch_accumulate(c, true, nullptr, nullptr);
             if (!rc) rc = launch_reduce(c, c->d_sums, oa::RowSel{ c->acc_blocks, 0, 0 }, false);
@@ -4668,6 +4796,7 @@ int refuse_wide_row(const oa_ctx *c, const char *who, bool estimated_scale_too =
 {
     if (c->recip_on) return fail(OA_E_STATE, "%s%s", who, RECIP_ONE_DEVICE);
     if (trim_on(c)) return fail(OA_E_STATE, "%s%s", who, TRIM_ONE_DEVICE);
+    if (c->bnd_on) return fail(OA_E_STATE, "%s%s", who, BND_ONE_DEVICE);
     if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "%s%s", who, PLANE_ONE_DEVICE);
     if (c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "%s%s", who, GICP_ONE_DEVICE);
     if (estimated_scale_too && auto_scale(c)) return fail(OA_E_STATE, "%s%s", who, AUTO_ONE_DEVICE);
@@ -5294,6 +5423,7 @@ OA_EXPORT int oa_estimate_target_normals(oa_ctx *c, int k, int orient, const flo
     float *d_n = nullptr;
     if (install) {                                                   // (the stream is idle: the array the loops read is replaced in place)
         if (!c->d_tgt_n) HIPCHK(dev_malloc(&c->d_tgt_n, sizeof(float) * 3 * nt));
+        c->bnd_ok = false;                                           // (a boundary mask was built from the old normals)
         d_n = c->d_tgt_n;
     } else if (out_normals) { HIPCHK(tmp_n.alloc(3 * nt)); d_n = tmp_n.p; }
     if (out_curvature) HIPCHK(d_curv.alloc(nt));
@@ -5719,43 +5849,141 @@ OA_EXPORT int oa_voxel_downsample(oa_ctx *c, const float *xyz, int64_t n, int on
 // deviation report (EXTENSION; oa_deviation.hpp)
 // ================================================================================================
 namespace {
-// the mesh's pseudo-normals, once per upload: face normals and corner angles, the stable order of the corners by vertex (a CSR
-// row per vertex, ascending by (triangle, corner)), then one thread per vertex and per (triangle, edge)
+// the stable order of the mesh's 3 n_tris corners by vertex: a CSR row per vertex, ascending by (triangle, corner).  Once per
+// upload, shared by the pseudo-normals and the boundary masks (both walk the rows)
+int ensure_corner_rows(oa_ctx *c)
+{
+    if (c->corner_ok) return OA_OK;
+    const size_t n_corners = 3 * (size_t)c->n_tris, nv = (size_t)c->nt;
+    if (n_corners > (size_t)0x7FF00000) return fail(OA_E_CAPACITY, "the mesh's corner rows: %zu corners (the sort takes fewer than 2^31 - 2^20)", n_corners);
+    dev_free(c->d_corner_order); dev_free(c->d_corner_row);
+    HIPCHK(dev_malloc(&c->d_corner_order, sizeof(int) * n_corners));
+    HIPCHK(dev_malloc(&c->d_corner_row, sizeof(long long) * (nv + 1)));
+    // (the indices were checked at upload: all in 0 .. nt - 1, so they are their own keys; oa_sort.hpp adds 10-bit passes as the bits ask)
+    const int rc = sort_order_bits(c, (const unsigned *)c->d_tris, c->d_corner_order, n_corners, bits_for((long long)nv));
+    if (rc) return rc;
+    hipLaunchKernelGGL(oa::k_pn_row_start, dim3((unsigned)((nv + 1 + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->d_tris, (const int *)c->d_corner_order,
+                       (long long)n_corners, (int)nv, c->d_corner_row);
+    HIPCHK(hipGetLastError());
+    c->corner_ok = true;
+    return OA_OK;
+}
+
+// the mesh's pseudo-normals, once per upload: face normals and corner angles, the corner rows, then one thread per vertex and
+// per (triangle, edge)
 int ensure_pseudonormals(oa_ctx *c)
 {
     if (c->pn_ok) return OA_OK;
     if (!c->surface || !c->d_tris || c->n_tris < 1 || c->nt < 1) return fail(OA_E_STATE, "pseudo-normals need a mesh target (oa_set_target_mesh)");
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n_tris = (size_t)c->n_tris, n_corners = 3 * n_tris, nv = (size_t)c->nt;
-    if (n_corners > (size_t)0x7FF00000) return fail(OA_E_CAPACITY, "pseudo-normals: %zu corners (the sort takes fewer than 2^31 - 2^20)", n_corners);
     dev_free(c->d_pn_face); dev_free(c->d_pn_vertex); dev_free(c->d_pn_edge);
     HIPCHK(dev_malloc(&c->d_pn_face, sizeof(double) * 3 * n_tris));
     HIPCHK(dev_malloc(&c->d_pn_vertex, sizeof(float) * 3 * nv));
     HIPCHK(dev_malloc(&c->d_pn_edge, sizeof(float) * 9 * n_tris));
     DevTmp<double> d_angle;
-    DevTmp<int> d_order;
-    DevTmp<long long> d_row;
-    HIPCHK(d_angle.alloc(n_corners)); HIPCHK(d_order.alloc(n_corners)); HIPCHK(d_row.alloc(nv + 1));
+    HIPCHK(d_angle.alloc(n_corners));
     const unsigned t_blocks = (unsigned)((n_tris + 255) / 256), c_blocks = (unsigned)((n_corners + 255) / 256);
     hipLaunchKernelGGL(oa::k_pn_face, dim3(t_blocks), dim3(256), 0, c->stream, (const float *)c->d_tgt_xyz, (const int *)c->d_tris, (int)n_tris, c->d_pn_face,
                        d_angle.p);
     HIPCHK(hipGetLastError());
-    // (the indices were checked at upload: all in 0 .. nt - 1, so they are their own keys; oa_sort.hpp adds 10-bit passes as the bits ask)
-    int rc = sort_order_bits(c, (const unsigned *)c->d_tris, d_order.p, n_corners, bits_for((long long)nv));
+    const int rc = ensure_corner_rows(c);
     if (rc) return rc;
-    hipLaunchKernelGGL(oa::k_pn_row_start, dim3((unsigned)((nv + 1 + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->d_tris, (const int *)d_order.p,
-                       (long long)n_corners, (int)nv, d_row.p);
-    hipLaunchKernelGGL(oa::k_pn_vertex, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream, (const int *)d_order.p, (const long long *)d_row.p, (int)nv,
+    hipLaunchKernelGGL(oa::k_pn_vertex, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->d_corner_order, (const long long *)c->d_corner_row, (int)nv,
                        (const double *)c->d_pn_face, (const double *)d_angle.p, c->d_pn_vertex);
-    hipLaunchKernelGGL(oa::k_pn_edge, dim3(c_blocks), dim3(256), 0, c->stream, (const int *)c->d_tris, (int)n_tris, (const int *)d_order.p,
-                       (const long long *)d_row.p, (const double *)c->d_pn_face, c->d_pn_edge);
+    hipLaunchKernelGGL(oa::k_pn_edge, dim3(c_blocks), dim3(256), 0, c->stream, (const int *)c->d_tris, (int)n_tris, (const int *)c->d_corner_order,
+                       (const long long *)c->d_corner_row, (const double *)c->d_pn_face, c->d_pn_edge);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));                        // (the temporaries go back to the cache behind this)
     c->pn_ok = true;
     c->last_pn_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return OA_OK;
 }
+
+// the set bits of a mask, counted on the device (k_boundary_count)
+int boundary_count(oa_ctx *c, const unsigned char *d_mask, size_t n, long long &out)
+{
+    DevTmp<unsigned> d_n;
+    HIPCHK(d_n.alloc(1));
+    HIPCHK(hipMemsetAsync(d_n.p, 0, sizeof(unsigned), c->stream));
+    const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((n + oa::BND_THREADS - 1) / oa::BND_THREADS, 256));   // (one atomic per wave on one word)
+    hipLaunchKernelGGL(oa::k_boundary_count, dim3(blocks), dim3(oa::BND_THREADS), 0, c->stream, d_mask, (long long)n, d_n.p);
+    HIPCHK(hipGetLastError());
+    unsigned h = 0;
+    const int rc = read_small(c, &h, d_n.p, sizeof h);
+    if (rc) return rc;
+    out = (long long)h;
+    return OA_OK;
+}
 }  // namespace
+
+namespace {
+// the target's boundary masks (oa_boundary.hpp), built on the context's stream and kept: a mesh's until the next upload, a cloud's
+// also until its normals or (k, angle_deg) change.  The device and the stream are the caller's (use_device); no loop is running
+int ensure_boundary(oa_ctx *c, int k, double angle_deg)
+{
+    if (c->nt <= 0) return fail(OA_E_STATE, "the target's boundary: call oa_set_target or oa_set_target_mesh first");
+    if (c->surface) {
+        if (c->bnd_ok) return OA_OK;
+        if (!c->d_tris || c->n_tris < 1) return fail(OA_E_STATE, "the target's boundary: the mesh has no triangles");
+    } else {
+        if (!c->d_tgt_n)
+            return fail(OA_E_STATE, "the boundary of a point-cloud target needs its normals: call oa_set_target_normals (or oa_set_normals, or install an estimate) first");
+        const int rcp = check_boundary_params("the target's boundary", k, angle_deg, c->nt);
+        if (rcp) return rcp;
+        if (c->bnd_ok && c->bnd_built_k == k && c->bnd_built_angle == angle_deg) return OA_OK;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    c->bnd_ok = false;
+    const size_t nv = (size_t)c->nt;
+    if (!c->d_bnd_vmask) HIPCHK(dev_malloc(&c->d_bnd_vmask, nv));
+    int rc;
+    if (c->surface) {
+        const size_t n_tris = (size_t)c->n_tris;
+        if (!c->d_bnd_emask) HIPCHK(dev_malloc(&c->d_bnd_emask, n_tris));
+        if ((rc = ensure_corner_rows(c))) return rc;
+        HIPCHK(hipMemsetAsync(c->d_bnd_vmask, 0, nv, c->stream));
+        constexpr size_t per_block = (size_t)(oa::BND_EDGES_PER_WAVE / 3) * (oa::BND_THREADS / 64);
+        hipLaunchKernelGGL(oa::k_mesh_boundary, dim3((unsigned)((n_tris + per_block - 1) / per_block)), dim3(oa::BND_THREADS), 0, c->stream, (const int *)c->d_tris,
+                           (int)n_tris, (const int *)c->d_corner_order, (const long long *)c->d_corner_row, c->d_bnd_emask, c->d_bnd_vmask);
+        HIPCHK(hipGetLastError());
+        if ((rc = boundary_count(c, c->d_bnd_emask, n_tris, c->bnd_n_edges))) return rc;
+    } else {
+        KnnTree tree;
+        if ((rc = knn_tree(c, tree))) return rc;
+        DevTmp<int32_t> d_idx;
+        HIPCHK(d_idx.alloc(nv * (size_t)(k + 1)));
+        if ((rc = knn_launch<false>(c, tree, k + 1, d_idx.p, nullptr, oa::KnnOrient{}, nullptr, nullptr))) return rc;
+        const unsigned blocks = (unsigned)std::max(1, std::min((c->nt + oa::BND_WPB - 1) / oa::BND_WPB, c->n_cu * 32));
+        hipLaunchKernelGGL(oa::k_cloud_boundary, dim3(blocks), dim3(oa::BND_WPB * 64), 0, c->stream, (const float *)c->d_tgt_xyz, (const float *)c->d_tgt_n,
+                           (const int32_t *)d_idx.p, c->nt, k, angle_deg * 3.14159265358979323846 / 180.0, c->d_bnd_vmask);
+        HIPCHK(hipGetLastError());
+        c->bnd_n_edges = 0;
+        c->bnd_built_k = k; c->bnd_built_angle = angle_deg;
+        if ((rc = boundary_count(c, c->d_bnd_vmask, nv, c->bnd_n_vertices))) return rc;   // (waits: the temporaries go back behind it)
+    }
+    if (c->surface && (rc = boundary_count(c, c->d_bnd_vmask, nv, c->bnd_n_vertices))) return rc;
+    c->bnd_ok = true;
+    c->last_bnd_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return OA_OK;
+}
+}  // namespace
+
+OA_EXPORT int oa_target_boundary(oa_ctx *c, int k, double angle_deg, uint8_t *vertex_mask, uint8_t *edge_mask)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    OA_NOT_MULTI(c, "oa_target_boundary (single-device)");
+    if (c->nt <= 0) return fail(OA_E_STATE, "oa_target_boundary: call oa_set_target or oa_set_target_mesh first");
+    if (!c->surface && edge_mask) return fail(OA_E_BAD_ARG, "oa_target_boundary: a point-cloud target has no edges (pass edge_mask = NULL)");
+    int rc = use_device(c);
+    if (rc) return rc;
+    if (c->loop_active) { HIPCHK(hipStreamSynchronize(c->stream)); c->loop_active = false; }   // a running sequence ends, as with oa_target_knn
+    if ((rc = ensure_boundary(c, k, angle_deg))) return rc;
+    if (vertex_mask) HIPCHK(hipMemcpyAsync(vertex_mask, c->d_bnd_vmask, (size_t)c->nt, hipMemcpyDeviceToHost, c->stream));
+    if (edge_mask) HIPCHK(hipMemcpyAsync(edge_mask, c->d_bnd_emask, (size_t)c->n_tris, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
 
 OA_EXPORT int oa_get_mesh_pseudonormals(oa_ctx *c, float *vertex_n, float *edge_n)
 {

@@ -369,6 +369,31 @@ class IcpEngine:
             fraction = capi.OA_TRIM_AUTO
         self._chk(self._L.oa_set_trim(self._h, float(fraction), float(fraction_min), float(lam)))
 
+    def set_reject_boundary(self, on=True, k=16, angle_deg=90.0):
+        """Drop a pair of a step whose correspondence lies on the target's boundary (target_boundary's masks, built before the
+        loop starts): on a mesh target the closest point lies on an edge only one triangle owns, or on an end of one; on a cloud
+        target the winning vertex is flagged by the angle criterion (k, angle_deg; the target needs its normals).  What a whole
+        model against a partial scan needs: the source points outside the overlap pair with the target's rim.  Applies to run /
+        iterate / make_pairs on single-device engines that hold the whole selection; nn_search, deviation, score_poses and
+        coarse_align do not look at it.  Survives uploads and set_matrices; stat("reject_boundary") reads it back,
+        stat("boundary_rejected") the pairs the last step dropped for it."""
+        self._chk(self._L.oa_set_reject_boundary(self._h, int(bool(on)), int(k), float(angle_deg)))
+
+    def target_boundary(self, k=16, angle_deg=90.0):
+        """The boundary of the resident target, built on the device if it is not there yet: (vertex_mask uint8 (n_verts,),
+        edge_mask uint8 (n_tris,) or None).  Mesh targets: exact -- bit j of edge_mask[t] = local edge j (ab, bc, ca) of triangle
+        t belongs to exactly one triangle; vertex_mask = the ends of such edges; k and angle_deg are ignored.  Cloud targets (with
+        normals installed): vertex_mask by the angle criterion -- the largest gap between the tangent-plane directions to the k
+        nearest neighbours exceeds angle_deg -- and edge_mask is None.  3 <= k <= min(63, nt - 1), 0 < angle_deg < 360.
+        stat("target_boundary") / stat("boundary_vertices") / stat("boundary_edges") describe the built masks."""
+        u8 = C.POINTER(C.c_uint8)
+        vm = np.empty(max(1, self.n_target), np.uint8)
+        n_tris = int(self.stat("n_tris")) if int(self.stat("surface")) else 0
+        em = np.empty(max(1, n_tris), np.uint8) if n_tris > 0 else None
+        self._chk(self._L.oa_target_boundary(self._h, int(k), float(angle_deg), vm.ctypes.data_as(u8),
+                                             em.ctypes.data_as(u8) if em is not None else None))
+        return vm[: self.n_target], (em[:n_tris] if em is not None else None)
+
     def set_source_weights(self, weights):
         """One weight per source vertex (finite, >= 0; the array uploaded with set_source, not the selection): a pair's weight
         is this times the robust loss's.  None switches them off; a new set_source forgets them.  Call after set_source."""
@@ -395,7 +420,8 @@ class IcpEngine:
              "robust_scale": 32, "robust_quantile": 33, "target_normals": 34,
              "target_features": 35, "mesh_pseudonormals": 36,
              "reciprocal": 37, "reciprocal_ratio": 38, "recip_rejected": 39,
-             "trim": 40, "trim_candidates": 41, "trim_kept": 42, "trim_cut": 43}
+             "trim": 40, "trim_candidates": 41, "trim_kept": 42, "trim_cut": 43,
+             "reject_boundary": 44, "boundary_rejected": 45, "target_boundary": 46, "boundary_vertices": 47, "boundary_edges": 48}
     EXCHANGE_NAMES = {-1: None, 0: "mailbox (pinned host memory)", 1: "rccl", 2: "mailbox (peer-mapped device memory)"}
 
     def exchange_info(self):

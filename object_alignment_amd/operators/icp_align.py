@@ -67,6 +67,13 @@ class IcpSettings:
     trim: object = 0.0
     trim_min: float = 0.3
     trim_lambda: float = 2.0
+    # nor these: reject_boundary=True drops a pair of a step whose correspondence lies on the target's boundary -- an edge of an
+    # open mesh that one triangle owns, or a point on the rim of a cloud (the largest angular gap between its boundary_k nearest
+    # neighbours, seen in the tangent plane, exceeds boundary_angle degrees; a cloud target then needs its normals).  The rim is a
+    # property of the target alone, found once: the cheapest answer to a source that reaches beyond a partial scan.  One GPU
+    reject_boundary: bool = False
+    boundary_k: int = 16
+    boundary_angle: float = 90.0
     # neighbours per vertex when run(..., target_normals="estimate") estimates a point-cloud target's normals on the device
     normal_k: int = 16
     # nor this: > 0 thins the selection in SPACE before the loop -- one vertex per occupied cell of a grid of this edge (world
@@ -228,6 +235,28 @@ def apply_trim(engine, settings) -> None:
         raise RuntimeError("this engine cannot trim its pairs")
 
 
+def boundary_of(settings):
+    """(on, k, angle_deg) from IcpSettings.reject_boundary / boundary_k / boundary_angle, or the `icp_reject_boundary` preference
+    of the registered add-on; (False, 16, 90.0) when neither is there."""
+    on = getattr(settings, "reject_boundary", None)
+    if on is None:
+        on = getattr(settings, "icp_reject_boundary", False)
+    k = getattr(settings, "boundary_k", None)
+    angle = getattr(settings, "boundary_angle", None)
+    return bool(on), 16 if k is None else int(k), 90.0 if angle is None else float(angle)
+
+
+def apply_boundary(engine, settings) -> None:
+    """Hand the settings' boundary rejection to the engine -- every time, off included: the engine is shared and remembers the
+    last setting.  An engine without set_reject_boundary counts as one with the setting off."""
+    on, k, angle = boundary_of(settings)
+    setter = getattr(engine, "set_reject_boundary", None)
+    if setter is not None:
+        setter(on, k, angle)
+    elif on:
+        raise RuntimeError("this engine cannot reject pairs on the target's boundary")
+
+
 def sample_voxel_of(settings) -> float:
     """IcpSettings.sample_voxel, checked: 0.0 (off) or a finite length > 0 in world units."""
     v = getattr(settings, "sample_voxel", 0.0)
@@ -380,6 +409,7 @@ class IcpAlign:
         apply_robust(eng, s)
         apply_reciprocal(eng, s)
         apply_trim(eng, s)
+        apply_boundary(eng, s)
         if sample_voxel > 0.0:
             vlist = voxel_vlist(eng, source_xyz, vlist, mx_align, sample_voxel)
         eng.set_source(source_xyz, vlist=vlist, stride=factor)

@@ -21,7 +21,7 @@ import numpy as np
 
 from .. import _hostmath
 from ..functions.general import _coords_of, _matrix_to_np, _tris_of, default_engine, evaluated_base
-from .icp_align import _OperatorBase, _assign_matrix, _bpy, execute_alignment, apply_metric, apply_reciprocal, apply_robust, apply_trim, get_addon_preferences, vlist_for_engine
+from .icp_align import _OperatorBase, _assign_matrix, _bpy, execute_alignment, apply_boundary, apply_metric, apply_reciprocal, apply_robust, apply_trim, get_addon_preferences, vlist_for_engine
 
 RING = 5
 
@@ -152,6 +152,7 @@ class OBJECT_OT_icp_align_feedback(_OperatorBase):
         apply_robust(eng, get_addon_preferences())
         apply_reciprocal(eng, get_addon_preferences())
         apply_trim(eng, get_addon_preferences())
+        apply_boundary(eng, get_addon_preferences())
         eng.target_owner = eng.source_owner = self                  # GpuBVH and this operator check these before they trust the engine
 
     @staticmethod
