@@ -22,6 +22,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "oa_deviation.hpp"
 #include "oa_boundary.hpp"
 #include "oa_tunables.hpp"            // every OA_* knob: read once, oa_ctx::tune (plain C++)
+#include "oa_devbuf.hpp"              // DevBuf<T>: the owner of every block of device memory (plain C++)
 #include "../../include/oa_icp.h"
 
 #include <algorithm>
@@ -75,7 +76,7 @@ int fail(int code, const char *fmt, ...)
 
 #define HIPCHK(expr)                                                                                   \
     do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
+        const hipError_t e_ = (hipError_t)(expr);       /* (a DevBuf's alloc returns the code as an int) */ \
         if (e_ != hipSuccess)                                                                          \
             return fail(OA_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
@@ -209,24 +210,17 @@ DevCache &dev_cache()
     return *cache;
 }
 
-template <typename T> hipError_t dev_malloc(T **p, size_t bytes) { return dev_cache().alloc((void **)p, bytes); }
+}  // namespace
 
-template <typename T> void dev_free(T *&p, bool synced = false)
-{
-    if (p) { dev_cache().release((void *)p, synced); p = nullptr; }
-}
+int oa::dev_block_alloc(void **out, size_t bytes) { return (int)dev_cache().alloc(out, bytes); }
+void oa::dev_block_release(void *p, bool settled) { dev_cache().release(p, settled); }
 
-// temporary device buffer, released on every exit path
-template <typename T> struct DevTmp {
-    T *p = nullptr;
-    DevTmp() = default;
-    DevTmp(const DevTmp &) = delete;
-    DevTmp &operator=(const DevTmp &) = delete;
-    ~DevTmp() { reset(); }
-    hipError_t alloc(size_t n) { reset(); return dev_malloc(&p, sizeof(T) * (n ? n : 1)); }
-    void reset() { dev_free(p); }
-    operator T *() const { return p; }
-};
+namespace {
+
+// every block has one owner (oa_devbuf.hpp): a member of oa_ctx's lifetime groups, or a local released on every exit path (DevTmp)
+using oa::DevBuf;
+template <typename T> using DevTmp = DevBuf<T>;
+template <typename T> hipError_t dev_malloc(DevBuf<T> *b, size_t bytes) { return (hipError_t)b->alloc_bytes(bytes); }
 
 // Host threads of a multi-device context.  One PERSISTENT worker per listed GPU (children that share a GPU share a
 // worker and stay sequential): uploads and index builds (20+ ms of copies, sorts and builds per device at 1M) run on all
@@ -321,151 +315,172 @@ template <typename F> int route_all_parallel(oa_ctx *c, F f);
 
 }  // namespace
 
-struct oa_ctx {
-    const oa_tune::Tunables tune = oa_tune::read_tunables();   // configuration: fixed for the context's life.  Everything below is state
-    int device = 0;
-    int n_cu = 256;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    // target
+// Device memory is owned by lifetime.  A group's members are handles and plain values with default initialisers:
+// the upload that ends the lifetime assigns `{}` to the group, the context's destructor releases what is left.
+// The resident target: set_target_common forgets all of it.
+struct oa_target {
     int nt = 0, n_groups_pad = 0;
-    float *d_tgt_xyz = nullptr;
-    float4 *d_tg = nullptr;
-    float4 *d_tf = nullptr;          // filter image, level 1: 3 float4 per group (k_nn_search_filtered)
-    float4 *d_tf3 = nullptr;         // filter image, level 2: 2 float4 per group
+    DevBuf<float> d_tgt_xyz;
+    DevBuf<float4> d_tg;
+    DevBuf<float4> d_tf;             // filter image, level 1: 3 float4 per group (k_nn_search_filtered)
+    DevBuf<float4> d_tf3;            // filter image, level 2: 2 float4 per group
     // the same images in the order of the coordinate along the cloud's longest axis (k_nn_search_sorted, round 5)
-    float4 *d_tfs = nullptr, *d_tf3s = nullptr, *d_tgs = nullptr;   // 3 / 2 / 3 float4 per group of 4 sorted positions
-    float4 *d_tmw = nullptr;         // level 0's pair images, 1 float4 per group: {m, w} of positions (0, 1) and (2, 3) (oa_pairgap.hpp)
-    int4 *d_tidx = nullptr;          // original index of every sorted position
-    int sax[3] = { 0, 1, 2 };        // its axes: longest (sorted along), second, thinnest
-    int fax[3] = { 0, 1, 2 };
-    double bb_lo[3] = { 0, 0, 0 }, bb_hi[3] = { 0, 0, 0 };
+    DevBuf<float4> d_tfs, d_tf3s, d_tgs;   // 3 / 2 / 3 float4 per group of 4 sorted positions
+    DevBuf<float4> d_tmw;            // level 0's pair images, 1 float4 per group: {m, w} of positions (0, 1) and (2, 3) (oa_pairgap.hpp)
+    DevBuf<int4> d_tidx;             // original index of every sorted position
+    DevBuf<oa::half8> d_tfm;         // the MFMA experiment's image of the target
+    bool filter_ok = false;
     // uniform grid (k_nn_search_grid)
     bool grid_ok = false;
-    int grid_mode = -1;              // -1 auto, 0 never, 1 whenever possible: tune.nn_grid at oa_create, then oa_set_search_mode
     oa::GridParams gp;
     int n_cells = 0;
-    int *d_cell_start = nullptr;
-    float4 *d_sorted = nullptr;
-    int *d_todo_list = nullptr, *d_todo_count = nullptr;   // d_todo_count: {entries, most per wave} of the hand-over list; from TODO_WORDS on: the two counter sets of d_ulist
-    int *d_ulist = nullptr;          // surface mode: the queries the front search (k_tri_settle) did not settle -> k_tri_search_grid (oa_tri.hpp: ulist_*)
-    int u_slot = 0;                  // which of the two counter sets the next front launch fills (it zeroes the other one)
+    DevBuf<int> d_cell_start;
+    DevBuf<float4> d_sorted;
+    DevBuf<float> d_safe_by_idx;     // vertex grid: safe2 per target vertex (original index); allocated with the grid, filled by build_safe_radii
+    bool safe_ok = false;            // ... and filled
+    long long target_iters = 0;      // accumulating grid searches enqueued since the target was set
     // surface mode (closest point on triangle, oa_tri.hpp)
     bool surface = false, tri_grid_ok = false;
     int n_tris = 0;
-    float4 *d_tri9 = nullptr;
-    int *d_tris = nullptr;           // the mesh's vertex indices, n_tris x 3 (the pseudo-normals are built from them, oa_deviation.hpp)
-    // angle-weighted pseudo-normals of the mesh (oa_deviation / oa_get_mesh_pseudonormals): built at the first signed call, forgotten by a new upload
+    DevBuf<float4> d_tri9;
+    DevBuf<int> d_tris;              // the mesh's vertex indices, n_tris x 3 (the pseudo-normals are built from them, oa_deviation.hpp)
+    // angle-weighted pseudo-normals of the mesh (oa_deviation / oa_get_mesh_pseudonormals): built at the first signed call
     bool pn_ok = false;
-    double *d_pn_face = nullptr;     // n_tris x 3: unit face normals
-    float *d_pn_vertex = nullptr, *d_pn_edge = nullptr;   // nt x 3; n_tris x 3 edges x 3
-    double last_pn_ms = 0.0;         // host time of the last build
+    DevBuf<double> d_pn_face;        // n_tris x 3: unit face normals
+    DevBuf<float> d_pn_vertex, d_pn_edge;   // nt x 3; n_tris x 3 edges x 3
     oa::GridParams tgp;
-    int *d_tcell_start = nullptr;
-    float4 *d_tcell_rec = nullptr;   // two float4 per cell-list entry: {disc centre, radius} {unit normal, triangle index}
+    DevBuf<int> d_tcell_start;
+    DevBuf<float4> d_tcell_rec;      // two float4 per cell-list entry: {disc centre, radius} {unit normal, triangle index}
     long long n_tri_entries = 0;     // entries of the triangle grid's cell lists
     double tri_mean_diag = 0.0;      // mean bounding-box diagonal of the triangles (the cell sizes are multiples of it)
     // the settled-pose search (oa_tri_fine.hpp): a sparse fine grid with inflated lists of whole triangles
     bool tri_fine_ok = false;
     oa::FineParams tfp;
-    uint4 *d_tfine_table = nullptr;
-    float4 *d_tfine_rec = nullptr;
+    DevBuf<uint4> d_tfine_table;
+    DevBuf<float4> d_tfine_rec;
     long long n_fine_entries = 0;
     // seed + neighbours settle a query (oa_tri_ring.hpp): per triangle its neighbours' indices; the accept radius lives in d_tri9
-    int *d_tri_ring = nullptr;
-    bool tri_ring_ok = false;        // built for the current mesh
+    DevBuf<int> d_tri_ring;
+    bool tri_ring_ok = false;
     long long tri_iters = 0;         // loop searches enqueued since the mesh was set
     // bounding-box trees (oa_bvh.hpp): over the vertices, and over the triangles in surface mode
     bool bvh_ok = false, tbvh_ok = false;
     oa::BvhParams bvh, tbvh;
-    float4 *d_bvh_box = nullptr, *d_bvh_prims = nullptr, *d_tbvh_box = nullptr, *d_tbvh_prims = nullptr;
-    bool filter_ok = false;
-    float tc[3] = { 0, 0, 0 };
-    double qmax = 0.0;
-    int *d_members = nullptr;        // shard of a spatially sharded selection: position in the whole selection of every caller-order slot (ascending); nullptr = shard_begin + slot
-    long long shard_begin = 0;
-    int *d_pos = nullptr;            // oa_make_pairs on a shard: whole-selection position of every pair
-    std::vector<int> h_members;      // host copy of d_members (children of a multi-device context)
-    oa::half8 *d_tfm = nullptr;      // its image of the target
-    double mfma_sigma = 1.0;
-    // source (this shard)
-    int ns = 0, ns_pad = 0, R = 4;   // R: tune.nn_r, or chosen from the shard size
-    float4 *d_src4 = nullptr;
-    unsigned long long *d_keys = nullptr;
-    bool seeded = false;             // a search has run since the last set_source / set_target (seeds exist)
-    int *d_prev = nullptr;           // nearest index of the previous search (seed), -1 = none
-    float4 *d_win = nullptr;         // vertex mode: per slot, the last winner's coordinates + index in .w (-1 = none)
-    uint2 *d_wsafe = nullptr;        // vertex grid: per slot {index, safe2 bits} of a winner the grid scan found (k_grid_safe_radius); 0xFF.. = none
-    float *d_safe_by_idx = nullptr;  // vertex grid: safe2 per target vertex (original index); allocated with the grid, filled by build_safe_radii
-    bool safe_ok = false;            // ... and filled
-    long long target_iters = 0;      // accumulating grid searches enqueued since the target was set
-    int *d_sel = nullptr;            // vertex index held by each source slot
-    float4 *d_src4o = nullptr;       // the same points in the caller's (vlist) order -- only oa_make_pairs needs it
-    int *d_perm = nullptr;           // sorted slot -> caller-order slot (nullptr: not sorted)
-    float4 *d_prec = nullptr;        // k_sorted_point_setup: k_nn_search_sorted's point records, 3 float4 per slot in the order its lanes read them + a fourth array, one float4 per lane and pair of its points (oa_quadgap.hpp) (OA_NN_WAVE_ORDER=0: the slots' own order)
-    int prec_cap = 0;                // slots d_prec holds
-    int homes_cap = 0;               // blocks of source points d_homes holds (two ints each: home split, home tile)
-    int *d_homes = nullptr, *d_qcnt = nullptr;   // k_nn_search_sorted's work queue (oa_kernels.hpp): per block of source points its own split; the queues' counters
-    int last_queue_wgs = 0;          // OA_STAT_BRUTE_QUEUE_WGS
-    long long src_n_verts = 0;
-    // normal-angle rejection (extension)
-    float *d_src_n = nullptr, *d_tgt_n = nullptr;
-    float *d_tgt_feat = nullptr;     // oa_target_fpfh(keep): nt x 33 descriptors of the resident target, or nullptr; a new target forgets them
-    double cos_min = -2.0;
-    bool normals_on = false;
-    int last_plane_rank = 0;         // OA_STAT_PLANE_RANK: eigenvalues the last plane solve kept (loop or oa_point_to_plane)
-    int metric = OA_METRIC_POINT;    // oa_set_metric: what the loop minimises (survives uploads and oa_set_matrices)
-    double gicp_eps = 1e-3;          // oa_set_gicp: the small eigenvalue of the GICP metric's covariances (survives uploads and oa_set_matrices)
-    // weighted steps: a pair's weight is w_vertex * psi(residual).  Off (every weight 1, the unweighted kernels) unless set
-    int loss = OA_LOSS_NONE;         // oa_set_robust (survives uploads and oa_set_matrices)
-    double robust_c = 0.0;           // ... its scale, world units
-    float *d_w = nullptr;            // oa_set_source_weights: one weight per slot (gathered through d_sel), or nullptr; a new source forgets it
-    double last_weight_sum = 0.0;    // OA_STAT_WEIGHT_SUM
-    // oa_set_robust_auto: the loss's scale from each step's own residuals, c = max(robust_c * q, robust_cmin) -- robust_c is then
-    // the multiplier m.  Off while robust_p == 0; inert while the loss is NONE (survives uploads and oa_set_matrices)
-    double robust_p = 0.0, robust_cmin = 0.0;
-    uint32_t *d_rkeys = nullptr;     // one residual key per slot (k_residual_keys), allocated when a loop with the setting on begins
-    uint32_t *d_sel_hist = nullptr;  // the radix select's SEL_LEVELS histograms
-    double last_robust_c = 0.0;      // OA_STAT_ROBUST_SCALE: the c the last step used
-    // oa_set_reciprocal: keep a pair only if it is mutual (oa_recip.hpp; survives uploads and oa_set_matrices)
-    bool recip_on = false;
-    double recip_ratio = 1.0;
-    int src_shards = 1;              // shard_count of the last oa_set_source: a shard cannot see the other shards' source points
-    oa::BvhParams sbvh{};            // the box tree over the selected source points (align-local, primitive index = slot) ...
-    float4 *d_sbvh_box = nullptr, *d_sbvh_prims = nullptr;
-    bool sbvh_ok = false;            // ... built by the first step with the check on, kept until the next oa_set_source
-    unsigned char *d_recip_ok = nullptr;   // k_recip_check's verdict, one byte per slot
-    unsigned *d_recip_count = nullptr;     // its counters (RECIP_COUNT_WORDS): word 2 = slots the last step rejected
-    // oa_set_trim: every step keeps its best pairs only (oa_trim.hpp; survives uploads and oa_set_matrices).  The verdict goes into
-    // d_recip_ok, the keys into d_rkeys; the rest is the trim's own, allocated when a loop (or oa_make_pairs) with the setting on begins
-    double trim_fraction = 0.0;      // 0 = off, (0, 1] = the share kept, OA_TRIM_AUTO = estimated every step
-    double trim_min = 0.3, trim_lambda = 2.0;
-    oa::DevTrim *d_trim = nullptr;   // its state between the launches, and the last step's figures (OA_STAT_TRIM_*)
-    uint32_t *d_trim_hist = nullptr; // fixed share: the select's SEL_LEVELS histograms
-    uint32_t *d_trim_sorted = nullptr; int *d_trim_order = nullptr; char *d_trim_tmp = nullptr;   // estimated share: the sorted keys, their order, the sort's scratch
-    double *d_trim_tiles = nullptr; oa::TrimTileMin *d_trim_min = nullptr;                        // ... the scan's tile sums / bases and the tiles' minima
-    // oa_set_reject_boundary / oa_target_boundary: the target's rim (oa_boundary.hpp).  The setting survives uploads and
-    // oa_set_matrices; the masks are built on demand and kept until a new target (the cloud's also until its normals or (k, angle) change)
-    bool bnd_on = false;
-    int bnd_k = 16;
-    double bnd_angle = 90.0;
-    unsigned char *d_bnd_vmask = nullptr, *d_bnd_emask = nullptr;   // nt bytes; n_tris bytes (mesh targets)
+    DevBuf<float4> d_bvh_box, d_bvh_prims, d_tbvh_box, d_tbvh_prims;
+    DevBuf<float> d_tgt_n;           // normal-angle rejection (extension)
+    DevBuf<float> d_tgt_feat;        // oa_target_fpfh(keep): nt x 33 descriptors of the resident target, or empty
+    // oa_target_boundary: the target's rim (oa_boundary.hpp).  The masks are built on demand (the cloud's again when its normals or (k, angle) change)
+    DevBuf<unsigned char> d_bnd_vmask, d_bnd_emask;                 // nt bytes; n_tris bytes (mesh targets)
     bool bnd_ok = false;
     int bnd_built_k = 0; double bnd_built_angle = 0.0;              // what a cloud's mask was built with
     long long bnd_n_vertices = 0, bnd_n_edges = 0;                  // OA_STAT_BOUNDARY_VERTICES / _EDGES
-    double last_bnd_ms = 0.0;                                       // host time of the last mask build
-    unsigned *d_bnd_count = nullptr;                                // k_boundary_verdict's counters (BND_COUNT_WORDS): word 2 = slots the last step rejected
-    int *d_corner_order = nullptr; long long *d_corner_row = nullptr;   // the mesh's corners by vertex (CSR rows): the pseudo-normals and the
-    bool corner_ok = false;                                             // boundary share them; a new target forgets them
+    DevBuf<int> d_corner_order; DevBuf<long long> d_corner_row;     // the mesh's corners by vertex (CSR rows): the pseudo-normals and the
+    bool corner_ok = false;                                         // boundary share them
+};
+
+// The source shard: source_reset forgets all of it.
+struct oa_source {
+    int ns = 0, ns_pad = 0, R = 4;   // R: tune.nn_r, or chosen from the shard size
+    DevBuf<float4> d_src4;
+    DevBuf<unsigned long long> d_keys;
+    DevBuf<int> d_prev;              // nearest index of the previous search (seed), -1 = none
+    DevBuf<float4> d_win;            // vertex mode: per slot, the last winner's coordinates + index in .w (-1 = none)
+    DevBuf<uint2> d_wsafe;           // vertex grid: per slot {index, safe2 bits} of a winner the grid scan found (k_grid_safe_radius); 0xFF.. = none.  Sized by the source, held only against a vertex target: set_target_common frees or allocates it too
+    DevBuf<int> d_sel;               // vertex index held by each source slot
+    DevBuf<float4> d_src4o;          // the same points in the caller's (vlist) order -- only oa_make_pairs needs it
+    DevBuf<int> d_perm;              // sorted slot -> caller-order slot (empty: not sorted)
+    DevBuf<int> d_members;           // shard of a spatially sharded selection: position in the whole selection of every caller-order slot (ascending); empty = shard_begin + slot
+    long long shard_begin = 0;
+    DevBuf<int> d_pos;               // oa_make_pairs on a shard: whole-selection position of every pair
+    std::vector<int> h_members;      // host copy of d_members (children of a multi-device context)
+    DevBuf<float4> d_prec;           // k_sorted_point_setup: k_nn_search_sorted's point records, 3 float4 per slot in the order its lanes read them + a fourth array, one float4 per lane and pair of its points (oa_quadgap.hpp) (OA_NN_WAVE_ORDER=0: the slots' own order)
+    int prec_cap = 0;                // slots d_prec holds
+    int homes_cap = 0;               // blocks of source points d_homes holds (two ints each: home split, home tile)
+    DevBuf<int> d_homes, d_qcnt;     // k_nn_search_sorted's work queue (oa_kernels.hpp): per block of source points its own split; the queues' counters
+    long long src_n_verts = 0;
+    DevBuf<int> d_todo_list, d_todo_count;   // d_todo_count: {entries, most per wave} of the hand-over list; from TODO_WORDS on: the two counter sets of d_ulist
+    DevBuf<int> d_ulist;             // surface mode: the queries the front search (k_tri_settle) did not settle -> k_tri_search_grid (oa_tri.hpp: ulist_*)
+    int u_slot = 0;                  // which of the two counter sets the next front launch fills (it zeroes the other one)
+    DevBuf<float> d_src_n;           // normal-angle rejection (extension)
+    DevBuf<float> d_w;               // oa_set_source_weights: one weight per slot (gathered through d_sel), or empty
+    DevBuf<uint32_t> d_rkeys;        // one residual key per slot (k_residual_keys), allocated when a loop with oa_set_robust_auto or oa_set_trim on begins
+    oa::BvhParams sbvh{};            // oa_set_reciprocal: the box tree over the selected source points (align-local, primitive index = slot) ...
+    DevBuf<float4> d_sbvh_box, d_sbvh_prims;
+    bool sbvh_ok = false;            // ... built by the first step with the check on
+    DevBuf<unsigned char> d_recip_ok;   // k_recip_check's verdict, one byte per slot (the trim's and the boundary's go into it too)
+    DevBuf<uint32_t> d_trim_sorted; DevBuf<int> d_trim_order; DevBuf<char> d_trim_tmp;   // oa_set_trim, estimated share: the sorted keys, their order, the sort's scratch
+    DevBuf<double> d_trim_tiles; DevBuf<oa::TrimTileMin> d_trim_min;                       // ... the scan's tile sums / bases and the tiles' minima
     double pivot[3] = { 0, 0, 0 };
+    // make_pairs scratch (sized to ns)
+    int emit_cap = 0;
+    DevBuf<unsigned char> d_valid;
+    DevBuf<float> d_b;
+    DevBuf<double> d_dist;
+    DevBuf<int> d_counts;
+    DevBuf<long long> d_offsets;
+    DevBuf<double> d_A, d_B;
+};
+
+struct oa_ctx {
+    const oa_tune::Tunables tune = oa_tune::read_tunables();   // configuration: fixed for the context's life.  Everything below is state
+    int device = 0;
+    int n_cu = 256;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    oa_target tgt;
+    oa_source src;
+    // Context-wide from here on: settings (they survive uploads and oa_set_matrices), the loop's state, buffers no upload resizes,
+    // statistics -- and what build_filter found: a non-finite target leaves the old values in place, unread while !filter_ok
+    int sax[3] = { 0, 1, 2 };        // the sorted images' axes: longest (sorted along), second, thinnest
+    int fax[3] = { 0, 1, 2 };
+    double bb_lo[3] = { 0, 0, 0 }, bb_hi[3] = { 0, 0, 0 };
+    float tc[3] = { 0, 0, 0 };
+    double qmax = 0.0;
+    double mfma_sigma = 1.0;
+    int grid_mode = -1;              // -1 auto, 0 never, 1 whenever possible: tune.nn_grid at oa_create, then oa_set_search_mode
+    double last_pn_ms = 0.0;         // host time of the last pseudo-normal build
+    // both uploads reset these three and loop_active, each explicitly: they speak of the pair of target and source
+    bool seeded = false;             // a search has run since the last set_source / set_target (seeds exist)
+    bool win_seeds = false;          // an accumulation has written winner records since the last upload / oa_reset_seeds
+    bool normals_on = false;
+    int last_queue_wgs = 0;          // OA_STAT_BRUTE_QUEUE_WGS
+    double cos_min = -2.0;           // normal-angle rejection (extension)
+    int last_plane_rank = 0;         // OA_STAT_PLANE_RANK: eigenvalues the last plane solve kept (loop or oa_point_to_plane)
+    int metric = OA_METRIC_POINT;    // oa_set_metric: what the loop minimises
+    double gicp_eps = 1e-3;          // oa_set_gicp: the small eigenvalue of the GICP metric's covariances
+    // weighted steps: a pair's weight is w_vertex * psi(residual).  Off (every weight 1, the unweighted kernels) unless set
+    int loss = OA_LOSS_NONE;         // oa_set_robust
+    double robust_c = 0.0;           // ... its scale, world units
+    double last_weight_sum = 0.0;    // OA_STAT_WEIGHT_SUM
+    // oa_set_robust_auto: the loss's scale from each step's own residuals, c = max(robust_c * q, robust_cmin) -- robust_c is then
+    // the multiplier m.  Off while robust_p == 0; inert while the loss is NONE
+    double robust_p = 0.0, robust_cmin = 0.0;
+    DevBuf<uint32_t> d_sel_hist;     // the radix select's SEL_LEVELS histograms
+    double last_robust_c = 0.0;      // OA_STAT_ROBUST_SCALE: the c the last step used
+    // oa_set_reciprocal: keep a pair only if it is mutual (oa_recip.hpp)
+    bool recip_on = false;
+    double recip_ratio = 1.0;
+    int src_shards = 1;              // shard_count of the last oa_set_source: a shard cannot see the other shards' source points
+    DevBuf<unsigned> d_recip_count;  // k_recip_check's counters (RECIP_COUNT_WORDS): word 2 = slots the last step rejected
+    // oa_set_trim: every step keeps its best pairs only (oa_trim.hpp).  The verdict goes into src.d_recip_ok, the keys into
+    // src.d_rkeys; the rest is the trim's own, allocated when a loop (or oa_make_pairs) with the setting on begins
+    double trim_fraction = 0.0;      // 0 = off, (0, 1] = the share kept, OA_TRIM_AUTO = estimated every step
+    double trim_min = 0.3, trim_lambda = 2.0;
+    DevBuf<oa::DevTrim> d_trim;      // its state between the launches, and the last step's figures (OA_STAT_TRIM_*)
+    DevBuf<uint32_t> d_trim_hist;    // fixed share: the select's SEL_LEVELS histograms
+    // oa_set_reject_boundary: drop pairs on the target's rim (the masks: oa_target)
+    bool bnd_on = false;
+    int bnd_k = 16;
+    double bnd_angle = 90.0;
+    double last_bnd_ms = 0.0;                                       // host time of the last mask build
+    DevBuf<unsigned> d_bnd_count;                                   // k_boundary_verdict's counters (BND_COUNT_WORDS): word 2 = slots the last step rejected
     // launch geometry for k_nn_search
     int n_splits = 1, acc_blocks = 1;
     int n_splits_seeded = 1;         // k_nn_search_sorted once the winner records hold seeds: more, shorter splits (plan_geometry)
-    bool win_seeds = false;          // an accumulation has written winner records since the last upload / oa_reset_seeds
     int tile_groups = oa::FTILE_GROUPS;   // LDS tile of k_nn_search_filtered: 256 groups, 64 for small targets
     double d_pivot0 = 0.0;           // initial distance pivot for the next loop / one-shot (see DevState::d_pivot)
     // device state
     oa::DevState h_state;
-    oa::DevState *d_state = nullptr;
+    DevBuf<oa::DevState> d_state;
     bool have_mats = false, loop_active = false;
     oa::StepRecord *d_hist = nullptr;       // device view of h_hist_map: the solve kernel writes the records straight into host memory
     oa::StepRecord *h_hist_map = nullptr;   // pinned, device-mapped history (read after a stream sync, no copy)
@@ -478,19 +493,11 @@ struct oa_ctx {
     std::vector<oa::StepRecord> h_hist;   // host copy of the executed iterations' records, filled by fill_report
     bool h_hist_valid = false;
     int max_records = 0;
-    double *d_partials = nullptr, *d_sums = nullptr, *d_solve = nullptr;
+    DevBuf<double> d_partials, d_sums, d_solve;
     int iter_enq = 0;                       // iterations enqueued since the loop began
     int fast_iters = 0;                     // ... of which the grid search finished its own leftovers and accumulated (OA_STAT_FAST_ITERATIONS)
     bool fast_prev = false;                 // what the last iteration's grid search did
     int last_todo_wave_max = -1;            // most queries one wave handed over in the last iteration the host heard of (-1: unknown)
-    // make_pairs scratch (sized to ns)
-    int emit_cap = 0;
-    unsigned char *d_valid = nullptr;
-    float *d_b = nullptr;
-    double *d_dist = nullptr;
-    int *d_counts = nullptr;
-    long long *d_offsets = nullptr;
-    double *d_A = nullptr, *d_B = nullptr;
     // timing
     std::vector<hipEvent_t> ev;
     int ev_used = 0;
@@ -519,7 +526,7 @@ namespace {
 
 // d_todo_count: TODO_WORDS ints for the tree's hand-over list, then two sets of the front search's list counters (ulist_*)
 constexpr int TODO_WORDS = 32, UCOUNT_WORDS = oa::ULIST_PARTS * oa::ULIST_STRIDE, TODO_COUNT_INTS = TODO_WORDS + 2 * UCOUNT_WORDS;
-[[maybe_unused]] inline int *ucount_set(const oa_ctx *c, int slot) { return c->d_todo_count + TODO_WORDS + slot * UCOUNT_WORDS; }
+[[maybe_unused]] inline int *ucount_set(const oa_ctx *c, int slot) { return c->src.d_todo_count + TODO_WORDS + slot * UCOUNT_WORDS; }
 
 int use_device(oa_ctx *c)
 {
@@ -551,13 +558,13 @@ template <typename F> int route_all_parallel(oa_ctx *c, F f)
 
 void plan_geometry(oa_ctx *c)
 {
-    if (c->ns <= 0 || c->nt <= 0) return;
-    const int src_blocks = c->ns_pad / (oa::NN_THREADS * c->R);
+    if (c->src.ns <= 0 || c->tgt.nt <= 0) return;
+    const int src_blocks = c->src.ns_pad / (oa::NN_THREADS * c->src.R);
     // small targets: quarter-size tiles give 4x more (and 4x shorter) workgroups; the unfiltered kernel keeps 256
-    c->tile_groups = (c->filter_ok && c->tune.nn_filter && c->nt <= 65536 && !c->tune.nn_bigtile) ? 64 : oa::FTILE_GROUPS;
-    const int tiles_total = c->n_groups_pad / c->tile_groups;
+    c->tile_groups = (c->tgt.filter_ok && c->tune.nn_filter && c->tgt.nt <= 65536 && !c->tune.nn_bigtile) ? 64 : oa::FTILE_GROUPS;
+    const int tiles_total = c->tgt.n_groups_pad / c->tile_groups;
     // workgroups wanted: ~2e5 pairs each (below that the prologue and the atomicMin merge dominate), at most 64 per CU
-    const double pairs = (double)c->ns * (double)c->nt;
+    const double pairs = (double)c->src.ns * (double)c->tgt.nt;
     const int want_auto = (int)std::min((double)c->n_cu * 64.0, std::max((double)c->n_cu * 2.0, pairs / 2e5));
     const int want = c->tune.nn_target_blocks == oa_tune::UNSET ? want_auto : c->tune.nn_target_blocks;
     int splits = (want + src_blocks - 1) / src_blocks;
@@ -579,7 +586,7 @@ void plan_geometry(oa_ctx *c)
     if (forced_seeded > 0) seeded = std::min(forced_seeded, tiles_total);
     c->n_splits_seeded = seeded;
     const int acc_cap = std::max(1, std::min(oa::ACC_MAX_BLOCKS, c->tune.acc_blocks));
-    c->acc_blocks = std::max(1, std::min(acc_cap, (c->ns + oa::ACC_THREADS - 1) / oa::ACC_THREADS));
+    c->acc_blocks = std::max(1, std::min(acc_cap, (c->src.ns + oa::ACC_THREADS - 1) / oa::ACC_THREADS));
 }
 
 int ensure_common(oa_ctx *c)
@@ -662,8 +669,8 @@ int ensure_events(oa_ctx *c, int n_pairs)
 int check_ready(oa_ctx *c)
 {
     if (!c) return fail(OA_E_BAD_ARG, "null context");
-    if (c->nt <= 0 || !c->d_tg) return fail(OA_E_STATE, "target not set (oa_set_target)");
-    if (!c->d_src4) return fail(OA_E_STATE, "source not set (oa_set_source)");
+    if (c->tgt.nt <= 0 || !c->tgt.d_tg) return fail(OA_E_STATE, "target not set (oa_set_target)");
+    if (!c->src.d_src4) return fail(OA_E_STATE, "source not set (oa_set_source)");
     if (!c->have_mats) return fail(OA_E_STATE, "matrices not set (oa_set_matrices)");
     return OA_OK;
 }
@@ -673,18 +680,18 @@ int check_ready(oa_ctx *c)
 // (measured crossover after the round-2 grid kernels: 3e3 .. 1.4e4 points for vertices -- the grid kernel spreads a
 // query over 2 or 4 lanes when the shard is small --, 1.5e4 .. 2e4 for triangles, later for big targets whose grid no
 // longer sits in cache; profiles/r02l_search_mode_crossover.txt.  Round 1: 1.2e4 .. 2.4e4 and 2.8e4 .. 4e4.)
-inline int vertex_tree_max(const oa_ctx *c) { return c->nt >= 500000 ? 14336 : 3072; }
-inline int tri_tree_max(const oa_ctx *c) { return c->n_tris >= 1000000 ? 20480 : (c->n_tris >= 250000 ? 18432 : 15360); }
+inline int vertex_tree_max(const oa_ctx *c) { return c->tgt.nt >= 500000 ? 14336 : 3072; }
+inline int tri_tree_max(const oa_ctx *c) { return c->tgt.n_tris >= 1000000 ? 20480 : (c->tgt.n_tris >= 250000 ? 18432 : 15360); }
 // ... and while the pose still moves by a good part of a cell per iteration (stale seeds, long reach: the first
 // iterations of a run, i.e. ALL of a typical early-exit run) the tree wins up to much larger shards (5-iteration runs
 // from a cold start, profiles/r02l_search_mode_crossover_short_runs.txt): shards between the two limits get both
 // searches enqueued and DevState::tree_turn decides on the device
-inline int vertex_tree_early(const oa_ctx *c) { return c->nt >= 500000 ? 28672 : 8192; }
-inline int tri_tree_early(const oa_ctx *c) { return c->n_tris >= 1000000 ? 57344 : (c->n_tris >= 250000 ? 40960 : 22528); }
+inline int vertex_tree_early(const oa_ctx *c) { return c->tgt.nt >= 500000 ? 28672 : 8192; }
+inline int tri_tree_early(const oa_ctx *c) { return c->tgt.n_tris >= 1000000 ? 57344 : (c->tgt.n_tris >= 250000 ? 40960 : 22528); }
 inline bool bvh_whole(const oa_ctx *c, bool ok, int auto_max)
 {
     if (!ok) return false;
-    return c->grid_mode == 2 || (c->grid_mode == -1 && c->ns <= auto_max);
+    return c->grid_mode == 2 || (c->grid_mode == -1 && c->src.ns <= auto_max);
 }
 int build_grid(oa_ctx *c);
 int build_safe_radii(oa_ctx *c);
@@ -717,8 +724,8 @@ constexpr long long SAFE_LAZY_ITERS = 8;   // OA_GRID_SAFE=1: loop iterations a 
 // for the post this thread has not enqueued yet -- children therefore built between loops only).
 int safe_radii_lazy(oa_ctx *c)
 {
-    if (c->tune.grid_safe != 1 || c->safe_ok || !c->d_safe_by_idx) return OA_OK;
-    return c->target_iters > SAFE_LAZY_ITERS ? build_safe_radii(c) : OA_OK;
+    if (c->tune.grid_safe != 1 || c->tgt.safe_ok || !c->tgt.d_safe_by_idx) return OA_OK;
+    return c->tgt.target_iters > SAFE_LAZY_ITERS ? build_safe_radii(c) : OA_OK;
 }
 int build_sorted_images(oa_ctx *c);
 int build_tri_grid(oa_ctx *c, const double *diag_sum_known = nullptr);
@@ -731,20 +738,20 @@ int build_tri_fine(oa_ctx *c);
 constexpr long long TRI_RING_LAZY_ITERS = 4;
 int tri_ring_lazy(oa_ctx *c, bool counting)
 {
-    if (c->tune.tri_ring != 1 || c->tri_ring_ok || !c->d_tri_ring) return OA_OK;
-    if (counting) ++c->tri_iters;
-    return c->tri_iters > TRI_RING_LAZY_ITERS ? build_tri_ring(c) : OA_OK;
+    if (c->tune.tri_ring != 1 || c->tgt.tri_ring_ok || !c->tgt.d_tri_ring) return OA_OK;
+    if (counting) ++c->tgt.tri_iters;
+    return c->tgt.tri_iters > TRI_RING_LAZY_ITERS ? build_tri_ring(c) : OA_OK;
 }
 int build_bvh(oa_ctx *c, bool tri);
 int ensure_boundary(oa_ctx *c, int k, double angle_deg);
 int build_bvh_arrays(oa_ctx *c, bool tri, const float *d_xyz, int stride, int n, const double frame_lo[3], const double frame_hi[3],
-                     oa::BvhParams &bp, float4 *&d_box, float4 *&d_prims, bool &ok);
+                     oa::BvhParams &bp, DevBuf<float4> &d_box, DevBuf<float4> &d_prims, bool &ok);
 int scan_counts(oa_ctx *c, const int *d_counts, int n, long long *d_off, DevTmp<char> &tmp);
 
 // one wave per query: 4 queries per workgroup, workgroups loop when there are more queries than that
 inline unsigned bvh_blocks(const oa_ctx *c, bool listed, bool acc = false)
 {
-    const int items = listed ? std::min(c->ns, 1 << 17) : c->ns;
+    const int items = listed ? std::min(c->src.ns, 1 << 17) : c->src.ns;
     if (acc) return (unsigned)std::max(1, std::min((items + 15) / 16, c->n_cu * 4));   // workgroups of 16 waves
     return (unsigned)std::max(1, std::min((items + 3) / 4, c->n_cu * (listed ? c->tune.list_blocks_per_cu : 16)));   // 16 waves per SIMD: enough to fill the chip, cheap to dispatch when the list is empty
 }
@@ -752,7 +759,7 @@ inline unsigned bvh_blocks(const oa_ctx *c, bool listed, bool acc = false)
 oa::NormalTest normal_test(const oa_ctx *c)
 {
     oa::NormalTest nrm{};
-    if (c->normals_on) { nrm.src_n = c->d_src_n; nrm.tgt_n = c->surface ? nullptr : c->d_tgt_n; nrm.cos_min = c->cos_min; }
+    if (c->normals_on) { nrm.src_n = c->src.d_src_n; nrm.tgt_n = c->tgt.surface ? nullptr : c->tgt.d_tgt_n; nrm.cos_min = c->cos_min; }
     return nrm;
 }
 
@@ -762,7 +769,7 @@ oa::PairTest<RECIP> pair_test(const oa_ctx *c)
 {
     oa::PairTest<RECIP> nrm{};
     static_cast<oa::NormalTest &>(nrm) = normal_test(c);
-    if constexpr (RECIP) nrm.recip_ok = c->d_recip_ok;
+    if constexpr (RECIP) nrm.recip_ok = c->src.d_recip_ok;
     return nrm;
 }
 
@@ -787,14 +794,14 @@ int ensure_recip(oa_ctx *c)
         const int rcc = recip_clear_count(c);
         if (rcc) return rcc;
     }
-    if (c->ns <= 0) return OA_OK;                                   // an empty selection: no slot, no verdict, no tree -- and no launch (launch_recip)
-    if (!c->d_recip_ok) HIPCHK(dev_malloc(&c->d_recip_ok, (size_t)c->ns));
-    if (c->sbvh_ok) return OA_OK;
-    dev_free(c->d_sbvh_box); dev_free(c->d_sbvh_prims);
+    if (c->src.ns <= 0) return OA_OK;                                   // an empty selection: no slot, no verdict, no tree -- and no launch (launch_recip)
+    if (!c->src.d_recip_ok) HIPCHK(dev_malloc(&c->src.d_recip_ok, (size_t)c->src.ns));
+    if (c->src.sbvh_ok) return OA_OK;
+    c->src.d_sbvh_box.reset(); c->src.d_sbvh_prims.reset();
     const int nb = oa::RECIP_FRAME_BLOCKS;
     DevTmp<float> d_bb;
     HIPCHK(d_bb.alloc(6 * (size_t)nb));
-    hipLaunchKernelGGL(oa::k_recip_frame, dim3(nb), dim3(256), 0, c->stream, (const float4 *)c->d_src4, c->ns, d_bb.p);
+    hipLaunchKernelGGL(oa::k_recip_frame, dim3(nb), dim3(256), 0, c->stream, (const float4 *)c->src.d_src4, c->src.ns, d_bb.p);
     HIPCHK(hipGetLastError());
     std::vector<float> bb(6 * (size_t)nb);
     int rc = read_small(c, bb.data(), d_bb.p, sizeof(float) * bb.size());
@@ -805,9 +812,9 @@ int ensure_recip(oa_ctx *c)
     double lo[3] = { 0.0, 0.0, 0.0 }, hi[3] = { 0.0, 0.0, 0.0 };
     for (int a = 0; a < 3; ++a) if (l[a] <= h[a]) { lo[a] = l[a]; hi[a] = h[a]; }     // (no finite coordinate: any frame will do)
     bool ok = false;
-    if ((rc = build_bvh_arrays(c, false, (const float *)c->d_src4, 4, c->ns, lo, hi, c->sbvh, c->d_sbvh_box, c->d_sbvh_prims, ok))) return rc;
+    if ((rc = build_bvh_arrays(c, false, (const float *)c->src.d_src4, 4, c->src.ns, lo, hi, c->src.sbvh, c->src.d_sbvh_box, c->src.d_sbvh_prims, ok))) return rc;
     if (!ok) return fail(OA_E_CAPACITY, "oa_set_reciprocal: the source's box tree would need more than %d levels", oa::BVH_MAX_LEVELS);
-    c->sbvh_ok = true;
+    c->src.sbvh_ok = true;
     return OA_OK;
 }
 
@@ -815,15 +822,15 @@ int ensure_recip(oa_ctx *c)
 // metric_n: the pair_fetch<.., METRIC_N> of the accumulation that follows (the plane and GICP metrics; never the emitting one)
 int launch_recip(oa_ctx *c, bool metric_n)
 {
-    if (c->ns <= 0) return OA_OK;                                   // no slot to judge: nothing is allocated for it either (ensure_recip)
+    if (c->src.ns <= 0) return OA_OK;                                   // no slot to judge: nothing is allocated for it either (ensure_recip)
     const oa::NormalTest nrm = normal_test(c);                      // (without the verdict: this launch forms it)
     auto *kern = metric_n ? oa::k_recip_check<true> : oa::k_recip_check<false>;
-    const unsigned blocks = (unsigned)std::max(1, std::min((c->ns + oa::RECIP_WPB - 1) / oa::RECIP_WPB, c->n_cu * 16));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(oa::RECIP_WPB * 64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->ns,
-                       (const float *)c->d_tgt_xyz, (const unsigned long long *)c->d_keys,
-                       c->surface ? (const float4 *)nullptr : (const float4 *)c->d_win, c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm,
-                       c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n, c->sbvh, (const float4 *)c->d_sbvh_box,
-                       (const float4 *)c->d_sbvh_prims, (float)(c->recip_ratio * c->recip_ratio), c->d_recip_ok, c->d_recip_count);
+    const unsigned blocks = (unsigned)std::max(1, std::min((c->src.ns + oa::RECIP_WPB - 1) / oa::RECIP_WPB, c->n_cu * 16));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(oa::RECIP_WPB * 64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->src.d_src4, c->src.ns,
+                       (const float *)c->tgt.d_tgt_xyz, (const unsigned long long *)c->src.d_keys,
+                       c->tgt.surface ? (const float4 *)nullptr : (const float4 *)c->src.d_win, c->tgt.surface ? (const float4 *)c->tgt.d_tri9 : (const float4 *)nullptr, nrm,
+                       c->tgt.surface ? (const float *)nullptr : (const float *)c->tgt.d_tgt_n, c->src.sbvh, (const float4 *)c->src.d_sbvh_box,
+                       (const float4 *)c->src.d_sbvh_prims, (float)(c->recip_ratio * c->recip_ratio), c->src.d_recip_ok, c->d_recip_count);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -870,21 +877,21 @@ int ensure_bnd_step(oa_ctx *c)
         const int rcc = bnd_clear_count(c);
         if (rcc) return rcc;
     }
-    if (c->ns > 0 && !c->d_recip_ok) HIPCHK(dev_malloc(&c->d_recip_ok, (size_t)c->ns));
+    if (c->src.ns > 0 && !c->src.d_recip_ok) HIPCHK(dev_malloc(&c->src.d_recip_ok, (size_t)c->src.ns));
     return ensure_boundary(c, c->bnd_k, c->bnd_angle);
 }
 
 // search -> [k_recip_check] -> THIS -> [the trim] -> ... -> the accumulation: byte 0 for every pair on the target's boundary
 int launch_boundary(oa_ctx *c)
 {
-    if (c->ns <= 0) return OA_OK;                                   // no slot to judge
-    if (!c->recip_on) HIPCHK(hipMemsetAsync(c->d_recip_ok, 1, (size_t)c->ns, c->stream));   // (else k_recip_check has just written every byte)
-    const unsigned blocks = (unsigned)std::max(1, std::min((c->ns + oa::BND_VERDICT_THREADS - 1) / oa::BND_VERDICT_THREADS, c->n_cu * 2));
-    hipLaunchKernelGGL(oa::k_boundary_verdict, dim3(blocks), dim3(oa::BND_VERDICT_THREADS), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4,
-                       c->ns, (const float *)c->d_tgt_xyz, (const unsigned long long *)c->d_keys,
-                       c->surface ? (const float4 *)nullptr : (const float4 *)c->d_win, c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr,
-                       normal_test(c), (const int *)c->d_tris, (const unsigned char *)c->d_bnd_emask, (const unsigned char *)c->d_bnd_vmask,
-                       c->d_recip_ok, c->d_bnd_count);
+    if (c->src.ns <= 0) return OA_OK;                                   // no slot to judge
+    if (!c->recip_on) HIPCHK(hipMemsetAsync(c->src.d_recip_ok, 1, (size_t)c->src.ns, c->stream));   // (else k_recip_check has just written every byte)
+    const unsigned blocks = (unsigned)std::max(1, std::min((c->src.ns + oa::BND_VERDICT_THREADS - 1) / oa::BND_VERDICT_THREADS, c->n_cu * 2));
+    hipLaunchKernelGGL(oa::k_boundary_verdict, dim3(blocks), dim3(oa::BND_VERDICT_THREADS), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->src.d_src4,
+                       c->src.ns, (const float *)c->tgt.d_tgt_xyz, (const unsigned long long *)c->src.d_keys,
+                       c->tgt.surface ? (const float4 *)nullptr : (const float4 *)c->src.d_win, c->tgt.surface ? (const float4 *)c->tgt.d_tri9 : (const float4 *)nullptr,
+                       normal_test(c), (const int *)c->tgt.d_tris, (const unsigned char *)c->tgt.d_bnd_emask, (const unsigned char *)c->tgt.d_bnd_vmask,
+                       c->src.d_recip_ok, c->d_bnd_count);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -912,8 +919,8 @@ int trim_clear(oa_ctx *c)
 int ensure_trim(oa_ctx *c)
 {
     if (!trim_on(c)) return OA_OK;
-    if (trim_auto(c) && (long long)c->ns > oa::TRIM_AUTO_MAX)
-        return fail(OA_E_CAPACITY, "oa_set_trim: the estimated share takes up to %lld points (this selection: %d)", oa::TRIM_AUTO_MAX, c->ns);
+    if (trim_auto(c) && (long long)c->src.ns > oa::TRIM_AUTO_MAX)
+        return fail(OA_E_CAPACITY, "oa_set_trim: the estimated share takes up to %lld points (this selection: %d)", oa::TRIM_AUTO_MAX, c->src.ns);
     if (!c->d_trim) {
         HIPCHK(dev_malloc(&c->d_trim, sizeof(oa::DevTrim)));
         const int rcc = trim_clear(c);
@@ -928,25 +935,20 @@ int ensure_trim(oa_ctx *c)
         HIPCHK(hipMemcpyAsync(c->d_trim, &h, offsetof(oa::DevTrim, running), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    if (c->ns <= 0) return OA_OK;                                   // an empty selection: no slot, no launch (launch_trim)
-    const size_t ns = (size_t)c->ns;
-    if (!c->d_recip_ok) HIPCHK(dev_malloc(&c->d_recip_ok, ns));
-    if (!c->d_rkeys) HIPCHK(dev_malloc(&c->d_rkeys, sizeof(uint32_t) * ns));
+    if (c->src.ns <= 0) return OA_OK;                                   // an empty selection: no slot, no launch (launch_trim)
+    const size_t ns = (size_t)c->src.ns;
+    if (!c->src.d_recip_ok) HIPCHK(dev_malloc(&c->src.d_recip_ok, ns));
+    if (!c->src.d_rkeys) HIPCHK(dev_malloc(&c->src.d_rkeys, sizeof(uint32_t) * ns));
     if (!c->d_trim_hist) HIPCHK(dev_malloc(&c->d_trim_hist, sizeof(uint32_t) * oa::SEL_LEVELS * oa::SEL_BINS));
     if (trim_auto(c)) {
-        const size_t n_tiles = (size_t)oa::trim_tiles(c->ns);
-        if (!c->d_trim_sorted) HIPCHK(dev_malloc(&c->d_trim_sorted, sizeof(uint32_t) * ns));
-        if (!c->d_trim_order) HIPCHK(dev_malloc(&c->d_trim_order, sizeof(int) * ns));
-        if (!c->d_trim_tmp && ns > (size_t)oa::SORT_SMALL_MAX) HIPCHK(dev_malloc(&c->d_trim_tmp, oa::sort_order_tmp_bytes(ns)));
-        if (!c->d_trim_tiles) HIPCHK(dev_malloc(&c->d_trim_tiles, sizeof(double) * n_tiles));
-        if (!c->d_trim_min) HIPCHK(dev_malloc(&c->d_trim_min, sizeof(oa::TrimTileMin) * n_tiles));
+        const size_t n_tiles = (size_t)oa::trim_tiles(c->src.ns);
+        if (!c->src.d_trim_sorted) HIPCHK(dev_malloc(&c->src.d_trim_sorted, sizeof(uint32_t) * ns));
+        if (!c->src.d_trim_order) HIPCHK(dev_malloc(&c->src.d_trim_order, sizeof(int) * ns));
+        if (!c->src.d_trim_tmp && ns > (size_t)oa::SORT_SMALL_MAX) HIPCHK(dev_malloc(&c->src.d_trim_tmp, oa::sort_order_tmp_bytes(ns)));
+        if (!c->src.d_trim_tiles) HIPCHK(dev_malloc(&c->src.d_trim_tiles, sizeof(double) * n_tiles));
+        if (!c->src.d_trim_min) HIPCHK(dev_malloc(&c->src.d_trim_min, sizeof(oa::TrimTileMin) * n_tiles));
     }
     return OA_OK;
-}
-// the buffers sized by the selection: a new source forgets them
-void trim_free_sized(oa_ctx *c)
-{
-    dev_free(c->d_trim_sorted); dev_free(c->d_trim_order); dev_free(c->d_trim_tmp); dev_free(c->d_trim_tiles); dev_free(c->d_trim_min);
 }
 
 // acc: a whole-shard search of the loop that also takes the pair test and the sums (k_bvh_search<TRI, true>)
@@ -959,11 +961,11 @@ int launch_bvh(oa_ctx *c, const int *list, const int *list_count, int turn = -1,
     uint2 *wsafe = nullptr;
     if (!TRI && !list && c->tune.grid_safe) {
         if (acc) { const int rcs = safe_radii_lazy(c); if (rcs) return rcs; }
-        if (c->safe_ok && c->d_safe_by_idx && c->d_wsafe) { safe_by_idx = c->d_safe_by_idx; wsafe = c->d_wsafe; }
+        if (c->tgt.safe_ok && c->tgt.d_safe_by_idx && c->src.d_wsafe) { safe_by_idx = c->tgt.d_safe_by_idx; wsafe = c->src.d_wsafe; }
     }
     auto launch = [&](auto ACC, unsigned threads, const oa::NormalTest &nrm, double *partials) {
-        hipLaunchKernelGGL((oa::k_bvh_search<TRI, decltype(ACC)::value>), dim3(blocks), dim3(threads), 0, c->stream, c->d_state, c->d_src4, c->ns, TRI ? c->tbvh : c->bvh,
-                           TRI ? c->d_tbvh_box : c->d_bvh_box, TRI ? c->d_tbvh_prims : c->d_bvh_prims, c->d_tri9, c->d_prev, TRI ? (float4 *)nullptr : c->d_win, c->d_keys,
+        hipLaunchKernelGGL((oa::k_bvh_search<TRI, decltype(ACC)::value>), dim3(blocks), dim3(threads), 0, c->stream, c->d_state, c->src.d_src4, c->src.ns, TRI ? c->tgt.tbvh : c->tgt.bvh,
+                           TRI ? c->tgt.d_tbvh_box : c->tgt.d_bvh_box, TRI ? c->tgt.d_tbvh_prims : c->tgt.d_bvh_prims, c->tgt.d_tri9, c->src.d_prev, TRI ? (float4 *)nullptr : c->src.d_win, c->src.d_keys,
                            list, list_count, turn, nrm, partials, safe_by_idx, wsafe);
     };
     if (acc) launch(std::true_type{}, 1024, normal_test(c), c->d_partials);
@@ -981,8 +983,8 @@ inline int grid_lanes_for(const oa_ctx *c)
 {
     int lanes = c->tune.grid_lanes;
     if (lanes != 1 && lanes != 2 && lanes != 4) {
-        const bool big = c->nt >= 500000;
-        lanes = (c->ns <= (big ? 400 : 80) * c->n_cu) ? 4 : ((c->ns <= (big ? 2800 : 1400) * c->n_cu) ? 2 : 1);
+        const bool big = c->tgt.nt >= 500000;
+        lanes = (c->src.ns <= (big ? 400 : 80) * c->n_cu) ? 4 : ((c->src.ns <= (big ? 2800 : 1400) * c->n_cu) ? 2 : 1);
     }
     return lanes;
 }
@@ -994,8 +996,8 @@ inline int tri_lanes_for(const oa_ctx *c)
 {
     int lanes = c->tune.grid_lanes;
     if (lanes != 1 && lanes != 2 && lanes != 4) {
-        const bool big = c->n_tris >= 250000;
-        lanes = (c->ns <= (big ? 400 : 128) * c->n_cu) ? 4 : ((c->ns <= (big ? 3200 : 700) * c->n_cu) ? 2 : 1);
+        const bool big = c->tgt.n_tris >= 250000;
+        lanes = (c->src.ns <= (big ? 400 : 128) * c->n_cu) ? 4 : ((c->src.ns <= (big ? 3200 : 700) * c->n_cu) ? 2 : 1);
     }
     return lanes;
 }
@@ -1007,18 +1009,18 @@ inline int tri_lanes_for(const oa_ctx *c)
 //  finer workgroups balance better)
 // (surface targets, round 4: the triangle grid search accumulates in its epilogue too -- k_tri_search_grid<L, .., ACC> --, always
 //  in workgroups of 256 threads, with ITS lanes per query)
-inline int canon_lanes(const oa_ctx *c) { return c->surface ? tri_lanes_for(c) : grid_lanes_for(c); }
+inline int canon_lanes(const oa_ctx *c) { return c->tgt.surface ? tri_lanes_for(c) : grid_lanes_for(c); }
 inline int canon_threads(const oa_ctx *c)
 {
-    if (c->surface) return 256;
+    if (c->tgt.surface) return 256;
     if (c->tune.acc_threads == 256 || c->tune.acc_threads == 512) return c->tune.acc_threads;   // OA_ACC_THREADS (A/B)
-    return (long long)c->ns * grid_lanes_for(c) >= 262144 ? 512 : 256;
+    return (long long)c->src.ns * grid_lanes_for(c) >= 262144 ? 512 : 256;
 }
 inline int canon_blocks(const oa_ctx *c)
 {
-    if (c->ns <= 0 || (c->surface && !c->tune.tri_canon)) return 0;
+    if (c->src.ns <= 0 || (c->tgt.surface && !c->tune.tri_canon)) return 0;
     const int t = canon_threads(c);
-    const long long b = ((long long)c->ns * canon_lanes(c) + t - 1) / t;
+    const long long b = ((long long)c->src.ns * canon_lanes(c) + t - 1) / t;
     return b <= oa::ACC_MAX_BLOCKS ? (int)b : 0;
 }
 
@@ -1038,12 +1040,12 @@ constexpr std::false_type no{};
 enum BruteKernel { BRUTE_PLAIN = 0, BRUTE_FILTERED = 1, BRUTE_MFMA = 2, BRUTE_SORTED = 3 };   // brute force over vertices (the values are OA_STAT_BRUTE_KERNEL's)
 BruteKernel brute_kernel(const oa_ctx *c)
 {
-    if (!c->filter_ok || !c->tune.nn_filter) return BRUTE_PLAIN;
+    if (!c->tgt.filter_ok || !c->tune.nn_filter) return BRUTE_PLAIN;
 #if defined(OA_EXPERIMENTS)
-    if (c->tune.nn_mfma && c->d_tfm && c->R == 4 && c->tile_groups == oa::FTILE_GROUPS) return BRUTE_MFMA;
-    if (!(c->tune.nn_sort && c->d_tfs)) return BRUTE_FILTERED;
+    if (c->tune.nn_mfma && c->tgt.d_tfm && c->src.R == 4 && c->tile_groups == oa::FTILE_GROUPS) return BRUTE_MFMA;
+    if (!(c->tune.nn_sort && c->tgt.d_tfs)) return BRUTE_FILTERED;
 #endif
-    return (c->tune.nn_sort && c->d_tfs) ? BRUTE_SORTED : BRUTE_PLAIN;
+    return (c->tune.nn_sort && c->tgt.d_tfs) ? BRUTE_SORTED : BRUTE_PLAIN;
 }
 
 // What the next search launch looks like: which search (loop and one-shot calls alike), and the loop's fusion plan.
@@ -1070,7 +1072,7 @@ struct SearchChoice {
     SearchPlan plan = PLAN_PLAIN;   // a loop with fused_acc only
 };
 // a loss or per-vertex weights are set: the loop's pairs carry weights (weighted kernels, the PLAIN plan)
-inline bool weighted(const oa_ctx *c) { return c->loss != OA_LOSS_NONE || c->d_w != nullptr; }
+inline bool weighted(const oa_ctx *c) { return c->loss != OA_LOSS_NONE || c->src.d_w != nullptr; }
 // the metrics that sum the wide row (NSUMS_PLANE) and take the 6 x 6 solve: point-to-plane and plane-to-plane (GICP)
 inline bool plane_row_metric(const oa_ctx *c) { return c->metric == OA_METRIC_PLANE || c->metric == OA_METRIC_GICP; }
 // ... and the loss takes its scale from the step's own residuals (oa_set_robust_auto; inert without a loss)
@@ -1081,26 +1083,26 @@ SearchChoice choose_search(const oa_ctx *c)
     SearchChoice s;
     s.brute = brute_kernel(c);
     // (the grid searches hand their leftovers to the tree; mode 2 never gets to the grid arm: the whole-shard tree took it, or tree_ok is false)
-    const bool tree_ok = c->surface ? c->tbvh_ok : c->bvh_ok, grid_ok = c->surface ? c->tri_grid_ok : (c->grid_ok && c->filter_ok && c->tune.nn_filter);
-    if (bvh_whole(c, tree_ok, c->surface ? tri_tree_max(c) : vertex_tree_max(c))) s.kind = SEARCH_TREE;
+    const bool tree_ok = c->tgt.surface ? c->tgt.tbvh_ok : c->tgt.bvh_ok, grid_ok = c->tgt.surface ? c->tgt.tri_grid_ok : (c->tgt.grid_ok && c->tgt.filter_ok && c->tune.nn_filter);
+    if (bvh_whole(c, tree_ok, c->tgt.surface ? tri_tree_max(c) : vertex_tree_max(c))) s.kind = SEARCH_TREE;
     else if (grid_ok && tree_ok && c->grid_mode != 0) {
         s.kind = SEARCH_GRID;
-        s.dual = c->grid_mode == -1 && c->tune.search_turns && c->ns <= (c->surface ? tri_tree_early(c) : vertex_tree_early(c));
-        s.lanes = c->surface ? tri_lanes_for(c) : grid_lanes_for(c);
-        s.settle_front = c->surface && c->tri_fine_ok && c->seeded && !s.dual;
-        s.accept_front = c->surface && c->tune.tri_split && c->seeded && !s.dual;
+        s.dual = c->grid_mode == -1 && c->tune.search_turns && c->src.ns <= (c->tgt.surface ? tri_tree_early(c) : vertex_tree_early(c));
+        s.lanes = c->tgt.surface ? tri_lanes_for(c) : grid_lanes_for(c);
+        s.settle_front = c->tgt.surface && c->tgt.tri_fine_ok && c->seeded && !s.dual;
+        s.accept_front = c->tgt.surface && c->tune.tri_split && c->seeded && !s.dual;
     }
     // (the plane and GICP metrics have no accumulating search epilogue: search, then k_pair_accumulate_plane / _gicp -- as with
     //  fused_acc off; nor does a weighted step: no search epilogue knows about weights -- nor about the reciprocal check or the trim)
-    if (!c->tune.fused_acc || !c->loop_active || c->ns <= 0 || plane_row_metric(c) || weighted(c) || verdict_on(c)) return s;
+    if (!c->tune.fused_acc || !c->loop_active || c->src.ns <= 0 || plane_row_metric(c) || weighted(c) || verdict_on(c)) return s;
     // (the accumulating tree search needs twice the registers of the plain one: worth it while the shard is small enough
     //  that occupancy does not matter -- 12k queries against 1M vertices: 58 us fused, 47 us search + accumulate)
-    if (s.kind == SEARCH_TREE) s.plan = c->ns <= c->tune.tree_acc_max ? PLAN_TREE : PLAN_PLAIN;
+    if (s.kind == SEARCH_TREE) s.plan = c->src.ns <= c->tune.tree_acc_max ? PLAN_TREE : PLAN_PLAIN;
     else if (s.kind != SEARCH_GRID || canon_blocks(c) == 0) s.plan = PLAN_PLAIN;
-    else if (!c->surface) s.plan = s.dual ? PLAN_DUAL : PLAN_GRID;
+    else if (!c->tgt.surface) s.plan = s.dual ? PLAN_DUAL : PLAN_GRID;
     // the triangle grid search with the accumulating epilogue: shards above the zone where tree and grid take turns, and no
     // front search (k_tri_accept / k_tri_settle + the search of what they leave, which has no accumulating form)
-    else s.plan = (!s.dual && !(s.accept_front && c->tri_ring_ok) && !s.settle_front && c->tune.tri_acc) ? PLAN_GRID : PLAN_PLAIN;
+    else s.plan = (!s.dual && !(s.accept_front && c->tgt.tri_ring_ok) && !s.settle_front && c->tune.tri_acc) ? PLAN_GRID : PLAN_PLAIN;
     return s;
 }
 
@@ -1157,7 +1159,7 @@ int vertex_grid_stats(oa_ctx *c, unsigned blocks, Launch &&launch)
     const double nw = (double)std::max(1ull, h[oa::GRID_STAT_WAVES]), ct = (double)std::max(1ull, h[oa::GRID_STAT_CYC_TOTAL]);
     fprintf(stderr, "[oa] vertex grid phases: %llu of %d queries settled by the seed's safe radius | per wave %.0f shader cycles, %.2f loop trips, %.2f scan trips, %.1f candidates per query (longest lane of a wave %.1f) | "
                     "prologue %.1f%% listing %.1f%% scan %.1f%% bookkeeping %.1f%% finish %.1f%% epilogue %.1f%% (loads + pair test %.1f%%, wave reduction %.1f%%, barrier %.1f%%)\n",
-            h[oa::GRID_STAT_ACCEPTED], c->ns, ct / nw, h[oa::GRID_STAT_LOOP_TRIPS] / nw, h[oa::GRID_STAT_SCAN_TRIPS] / nw, h[oa::GRID_STAT_CANDIDATES] / (64.0 * nw),
+            h[oa::GRID_STAT_ACCEPTED], c->src.ns, ct / nw, h[oa::GRID_STAT_LOOP_TRIPS] / nw, h[oa::GRID_STAT_SCAN_TRIPS] / nw, h[oa::GRID_STAT_CANDIDATES] / (64.0 * nw),
             h[oa::GRID_STAT_MAX_LANE_CANDIDATES] / nw, 100.0 * h[oa::GRID_STAT_CYC_PROLOGUE] / ct, 100.0 * h[oa::GRID_STAT_CYC_LIST] / ct,
             100.0 * h[oa::GRID_STAT_CYC_SCAN] / ct, 100.0 * h[oa::GRID_STAT_CYC_BOOK] / ct, 100.0 * h[oa::GRID_STAT_CYC_FINISH] / ct,
             100.0 * h[oa::GRID_STAT_CYC_EPILOGUE] / ct, 100.0 * h[oa::GRID_STAT_CYC_EPI_PAIR] / ct, 100.0 * h[oa::GRID_STAT_CYC_EPI_REDUCE] / ct,
@@ -1170,23 +1172,23 @@ int vertex_grid_stats(oa_ctx *c, unsigned blocks, Launch &&launch)
 // loop by the wave that owns them (acc), in one-shot calls through a list that k_bvh_search finishes.
 int launch_vertex_grid(oa_ctx *c, const SearchChoice &s, bool acc)
 {
-    if (!acc && !c->loop_active) HIPCHK(hipMemsetAsync(c->d_todo_count, 0, 2 * sizeof(int), c->stream));
+    if (!acc && !c->loop_active) HIPCHK(hipMemsetAsync(c->src.d_todo_count, 0, 2 * sizeof(int), c->stream));
     if (s.dual) { int rcb = launch_bvh<false>(c, nullptr, nullptr, 1, acc); if (rcb) return rcb; }   // runs when DevState::tree_turn
     // {index, safe2} per slot beside the winner records: both or neither (OA_GRID_SAFE=0)
     if (acc) { const int rcs = safe_radii_lazy(c); if (rcs) return rcs; }
-    const bool safe = c->tune.grid_safe && c->safe_ok && c->d_safe_by_idx && c->d_wsafe;
+    const bool safe = c->tune.grid_safe && c->tgt.safe_ok && c->tgt.d_safe_by_idx && c->src.d_wsafe;
     // k_nn_search_grid<L, ACC, BT, STATS>; the accumulating form gets the tree, the pair test and the rows of partials
     auto launch = [&](auto L, auto ACC, auto BT, auto STATS, unsigned blocks, unsigned long long *stats) {
         constexpr bool A = decltype(ACC)::value;
         hipLaunchKernelGGL((oa::k_nn_search_grid<decltype(L)::value, A, decltype(BT)::value, decltype(STATS)::value>), dim3(blocks), dim3(decltype(BT)::value), 0, c->stream,
-                           c->d_state, c->d_src4, c->ns, c->gp, c->d_cell_start, c->d_sorted, c->d_win, c->d_keys, c->d_todo_list, c->d_todo_count, s.dual ? 0 : -1,
-                           A ? c->bvh : oa::BvhParams{}, A ? (const float4 *)c->d_bvh_box : nullptr, A ? (const float4 *)c->d_bvh_prims : nullptr,
-                           A ? normal_test(c) : oa::NormalTest{}, A ? c->d_partials : nullptr, stats, safe ? c->d_safe_by_idx : nullptr, safe ? c->d_wsafe : nullptr);
+                           c->d_state, c->src.d_src4, c->src.ns, c->tgt.gp, c->tgt.d_cell_start, c->tgt.d_sorted, c->src.d_win, c->src.d_keys, c->src.d_todo_list, c->src.d_todo_count, s.dual ? 0 : -1,
+                           A ? c->tgt.bvh : oa::BvhParams{}, A ? (const float4 *)c->tgt.d_bvh_box : nullptr, A ? (const float4 *)c->tgt.d_bvh_prims : nullptr,
+                           A ? normal_test(c) : oa::NormalTest{}, A ? c->d_partials : nullptr, stats, safe ? c->tgt.d_safe_by_idx : nullptr, safe ? c->src.d_wsafe : nullptr);
     };
     if (!acc) {
-        dispatch<1, 2, 4>(s.lanes, [&](auto L) { launch(L, no, int_c<256>{}, no, (unsigned)(((long long)c->ns * s.lanes + 255) / 256), nullptr); });
+        dispatch<1, 2, 4>(s.lanes, [&](auto L) { launch(L, no, int_c<256>{}, no, (unsigned)(((long long)c->src.ns * s.lanes + 255) / 256), nullptr); });
         HIPCHK(hipGetLastError());
-        return launch_bvh<false>(c, c->d_todo_list, c->d_todo_count);
+        return launch_bvh<false>(c, c->src.d_todo_list, c->src.d_todo_count);
     }
     const unsigned ablocks = (unsigned)canon_blocks(c);
 #if defined(OA_EXPERIMENTS)
@@ -1204,17 +1206,17 @@ int launch_vertex_grid(oa_ctx *c, const SearchChoice &s, bool acc)
 // target without usable grid or tree), or should the blocks outgrow them.
 int ensure_sorted_buffers(oa_ctx *c, int blocks)
 {
-    if (c->ns_pad > c->prec_cap) {
-        dev_free(c->d_prec); c->prec_cap = 0;
-        HIPCHK(dev_malloc(&c->d_prec, sizeof(float4) * 4 * (size_t)c->ns_pad));   // (three float4 per slot + the lanes' point pairs)
-        c->prec_cap = c->ns_pad;
+    if (c->src.ns_pad > c->src.prec_cap) {
+        c->src.d_prec.reset(); c->src.prec_cap = 0;
+        HIPCHK(dev_malloc(&c->src.d_prec, sizeof(float4) * 4 * (size_t)c->src.ns_pad));   // (three float4 per slot + the lanes' point pairs)
+        c->src.prec_cap = c->src.ns_pad;
     }
-    if (blocks > c->homes_cap) {
-        dev_free(c->d_homes); c->homes_cap = 0;
-        HIPCHK(dev_malloc(&c->d_homes, sizeof(int) * 2 * (size_t)blocks));
-        c->homes_cap = blocks;
+    if (blocks > c->src.homes_cap) {
+        c->src.d_homes.reset(); c->src.homes_cap = 0;
+        HIPCHK(dev_malloc(&c->src.d_homes, sizeof(int) * 2 * (size_t)blocks));
+        c->src.homes_cap = blocks;
     }
-    if (!c->d_qcnt) HIPCHK(dev_malloc(&c->d_qcnt, sizeof(int) * (size_t)(oa::SORTED_QUEUES * oa::SORTED_QUEUE_STRIDE)));
+    if (!c->src.d_qcnt) HIPCHK(dev_malloc(&c->src.d_qcnt, sizeof(int) * (size_t)(oa::SORTED_QUEUES * oa::SORTED_QUEUE_STRIDE)));
     return OA_OK;
 }
 
@@ -1228,47 +1230,47 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
     dim3 sgrid((unsigned)((c->win_seeds || two) ? c->n_splits_seeded : c->n_splits), grid.y);
     // long launches go through the work queue (oa_kernels.hpp): as many workgroups as the chip holds, the long items first
     const int q_splits = (int)sgrid.x, q_blocks = (int)sgrid.y;
-    const long long q_wgs = (long long)c->n_cu * std::min(c->tune.nn_persist, c->R <= 4 ? 4 : 2);
+    const long long q_wgs = (long long)c->n_cu * std::min(c->tune.nn_persist, c->src.R <= 4 ? 4 : 2);
     const bool queued = q_wgs > 0 && q_splits > 1 && (long long)q_splits * q_blocks >= (c->tune.nn_queue_min >= 0 ? (long long)c->tune.nn_queue_min : 4 * q_wgs);
     c->last_queue_wgs = queued ? (int)q_wgs : 0;
     { const int rcq = ensure_sorted_buffers(c, q_blocks); if (rcq) return rcq; }
     const int pass = two ? 2 : 0;                                   // (seeded from what the seed pass leaves in keys)
     if (two) {
-        const dim3 sb((unsigned)((c->ns_pad + 255) / 256));
+        const dim3 sb((unsigned)((c->src.ns_pad + 255) / 256));
         dispatch<oa::FTILE_GROUPS, 64>(c->tile_groups, [&](auto TG) {
-            hipLaunchKernelGGL((oa::k_nn_seed_sorted<decltype(TG)::value>), sb, dim3(256), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->ns_pad,
-                               (const float4 *)c->d_tgs, (const float4 *)c->d_tfs, (const int4 *)c->d_tidx, c->n_groups_pad, c->sax[0], c->d_keys);
+            hipLaunchKernelGGL((oa::k_nn_seed_sorted<decltype(TG)::value>), sb, dim3(256), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->src.d_src4, c->src.ns_pad,
+                               (const float4 *)c->tgt.d_tgs, (const float4 *)c->tgt.d_tfs, (const int4 *)c->tgt.d_tidx, c->tgt.n_groups_pad, c->sax[0], c->src.d_keys);
         });
         HIPCHK(hipGetLastError());
     }
     // every point's record at this pose, the waves' slots in the order of u (k_sorted_point_setup: once per search what every item of
     // the search used to work out for itself)
     {
-        const dim3 ob((unsigned)(c->ns_pad / (64 * c->R)));
-        dispatch<4, 1, 2, 8>(c->R, [&](auto R) {
-            hipLaunchKernelGGL((oa::k_sorted_point_setup<decltype(R)::value>), ob, dim3(64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4,
-                               (const float4 *)c->d_win, (const unsigned long long *)c->d_keys, c->sax[0], c->sax[1], pass, c->tune.nn_wave_order ? 1 : 0, c->ns_pad, c->ns, c->d_prec);
+        const dim3 ob((unsigned)(c->src.ns_pad / (64 * c->src.R)));
+        dispatch<4, 1, 2, 8>(c->src.R, [&](auto R) {
+            hipLaunchKernelGGL((oa::k_sorted_point_setup<decltype(R)::value>), ob, dim3(64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->src.d_src4,
+                               (const float4 *)c->src.d_win, (const unsigned long long *)c->src.d_keys, c->sax[0], c->sax[1], pass, c->tune.nn_wave_order ? 1 : 0, c->src.ns_pad, c->src.ns, c->src.d_prec);
         });
         HIPCHK(hipGetLastError());
     }
     // the blocks' home splits (the queue's order of items) and home tiles (where an item starts its visit of the split's tiles)
     {
         hipLaunchKernelGGL(oa::k_sorted_block_homes, dim3((unsigned)((std::max(q_blocks, oa::SORTED_QUEUES) + 63) / 64)), dim3(64), 0, c->stream,
-                           (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, q_blocks, oa::NN_THREADS * c->R, (const float4 *)c->d_tfs,
-                           c->n_groups_pad, c->tile_groups, c->sax[0], q_splits, c->d_homes, c->d_qcnt);
+                           (const oa::DevState *)c->d_state, (const float4 *)c->src.d_src4, q_blocks, oa::NN_THREADS * c->src.R, (const float4 *)c->tgt.d_tfs,
+                           c->tgt.n_groups_pad, c->tile_groups, c->sax[0], q_splits, c->src.d_homes, c->src.d_qcnt);
         HIPCHK(hipGetLastError());
     }
     if (queued) sgrid = dim3((unsigned)q_wgs);
     auto launch = [&](auto R, auto TG, auto VCHUNK) {
         hipLaunchKernelGGL((oa::k_nn_search_sorted<decltype(R)::value, decltype(TG)::value, decltype(VCHUNK)::value>), sgrid, dim3(oa::NN_THREADS), 0, c->stream,
-                           c->d_state, (const float4 *)c->d_tgs, (const float4 *)c->d_tfs, (const float4 *)c->d_tf3s, (const int4 *)c->d_tidx,
-                           c->n_groups_pad, c->d_keys, pass, (const float4 *)c->d_prec, q_splits, q_blocks, c->d_homes, queued ? c->d_qcnt : nullptr, c->nt, (const float4 *)c->d_tmw);
+                           c->d_state, (const float4 *)c->tgt.d_tgs, (const float4 *)c->tgt.d_tfs, (const float4 *)c->tgt.d_tf3s, (const int4 *)c->tgt.d_tidx,
+                           c->tgt.n_groups_pad, c->src.d_keys, pass, (const float4 *)c->src.d_prec, q_splits, q_blocks, c->src.d_homes, queued ? c->src.d_qcnt : nullptr, c->tgt.nt, (const float4 *)c->tgt.d_tmw);
     };
     auto search = [&](auto R) { dispatch<oa::FTILE_GROUPS, 64>(c->tile_groups, [&](auto TG) { if (c->tune.nn_vchunk) launch(R, TG, yes); else launch(R, TG, no); }); };
 #if defined(OA_EXPERIMENTS)
-    dispatch<4, 1, 2, 8>(c->R, search);
+    dispatch<4, 1, 2, 8>(c->src.R, search);
 #else
-    dispatch<4, 1, 2>(c->R, search);                                // (8 points per thread: an OA_EXPERIMENTS instantiation; oa_create turns OA_NN_R=8 into 4)
+    dispatch<4, 1, 2>(c->src.R, search);                                // (8 points per thread: an OA_EXPERIMENTS instantiation; oa_create turns OA_NN_R=8 into 4)
 #endif
     HIPCHK(hipGetLastError());
     return OA_OK;
@@ -1277,28 +1279,28 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
 // brute force over the target's vertices: one thread per R source points, n_splits slices of the target
 int launch_brute(oa_ctx *c, const SearchChoice &s)
 {
-    const dim3 grid(c->n_splits, c->ns_pad / (oa::NN_THREADS * c->R)), block(oa::NN_THREADS);
+    const dim3 grid(c->n_splits, c->src.ns_pad / (oa::NN_THREADS * c->src.R)), block(oa::NN_THREADS);
     if (grid.y > 65535)                                             // only the brute-force launch has this limit (grid.y)
-        return fail(OA_E_BAD_ARG, "shard of %d points exceeds the brute-force launch grid (use more shards)", c->ns);
+        return fail(OA_E_BAD_ARG, "shard of %d points exceeds the brute-force launch grid (use more shards)", c->src.ns);
     switch (s.brute) {
     case BRUTE_SORTED: return launch_brute_sorted(c, grid);
 #if defined(OA_EXPERIMENTS)
     case BRUTE_MFMA:
         dispatch<4, 2, 3>(c->tune.mfma_wps, [&](auto WPS) {
-            hipLaunchKernelGGL((oa::k_nn_search_mfma<decltype(WPS)::value>), grid, block, 0, c->stream, c->d_state, c->d_src4, c->d_tg, (const oa::half8 *)c->d_tfm, (const float4 *)c->d_win, c->n_groups_pad, c->mfma_sigma, c->d_keys);
+            hipLaunchKernelGGL((oa::k_nn_search_mfma<decltype(WPS)::value>), grid, block, 0, c->stream, c->d_state, c->src.d_src4, c->tgt.d_tg, (const oa::half8 *)c->tgt.d_tfm, (const float4 *)c->src.d_win, c->tgt.n_groups_pad, c->mfma_sigma, c->src.d_keys);
         });
         break;
     case BRUTE_FILTERED:
-        dispatch<4, 1, 2, 8>(c->R, [&](auto R) {
+        dispatch<4, 1, 2, 8>(c->src.R, [&](auto R) {
             dispatch<oa::FTILE_GROUPS, 64>(c->tile_groups, [&](auto TG) {
-                hipLaunchKernelGGL((oa::k_nn_search_filtered<decltype(R)::value, decltype(TG)::value>), grid, block, 0, c->stream, c->d_state, c->d_src4, c->d_tg, c->d_tf, c->d_tf3, (const float4 *)c->d_win, c->n_groups_pad, c->d_keys);
+                hipLaunchKernelGGL((oa::k_nn_search_filtered<decltype(R)::value, decltype(TG)::value>), grid, block, 0, c->stream, c->d_state, c->src.d_src4, c->tgt.d_tg, c->tgt.d_tf, c->tgt.d_tf3, (const float4 *)c->src.d_win, c->tgt.n_groups_pad, c->src.d_keys);
             });
         });
         break;
 #endif
     default:
-        dispatch<4, 1, 2, 8>(c->R, [&](auto R) {
-            hipLaunchKernelGGL((oa::k_nn_search<decltype(R)::value>), grid, block, 0, c->stream, c->d_state, c->d_src4, c->d_tg, c->n_groups_pad, c->d_keys);
+        dispatch<4, 1, 2, 8>(c->src.R, [&](auto R) {
+            hipLaunchKernelGGL((oa::k_nn_search<decltype(R)::value>), grid, block, 0, c->stream, c->d_state, c->src.d_src4, c->tgt.d_tg, c->tgt.n_groups_pad, c->src.d_keys);
         });
         break;
     }
@@ -1312,39 +1314,39 @@ int launch_tri_search(oa_ctx *c, const SearchChoice &s, bool acc);
 int launch_nn(oa_ctx *c, const SearchChoice &s, bool acc)
 {
     int rc = OA_OK;                                                 // (no points: nothing to search; the flags below are set all the same)
-    if (c->ns > 0 && s.kind == SEARCH_TREE) rc = c->surface ? launch_bvh<true>(c, nullptr, nullptr, -1, acc) : launch_bvh<false>(c, nullptr, nullptr, -1, acc);
-    else if (c->ns > 0 && c->surface) rc = launch_tri_search(c, s, acc);
-    else if (c->ns > 0) rc = s.kind == SEARCH_GRID ? launch_vertex_grid(c, s, acc) : launch_brute(c, s);
-    if (rc == OA_OK) { c->seeded = true; if (acc && !c->surface) c->win_seeds = true; }
+    if (c->src.ns > 0 && s.kind == SEARCH_TREE) rc = c->tgt.surface ? launch_bvh<true>(c, nullptr, nullptr, -1, acc) : launch_bvh<false>(c, nullptr, nullptr, -1, acc);
+    else if (c->src.ns > 0 && c->tgt.surface) rc = launch_tri_search(c, s, acc);
+    else if (c->src.ns > 0) rc = s.kind == SEARCH_GRID ? launch_vertex_grid(c, s, acc) : launch_brute(c, s);
+    if (rc == OA_OK) { c->seeded = true; if (acc && !c->tgt.surface) c->win_seeds = true; }
     return rc;
 }
 
 // the plane metric's accumulation, and the weighted one of the point metric: one thread per source slot, workgroups by the
 // shard size alone (every search mode leaves the same rows); begin_loop refuses shards beyond PLANE_MAX_BLOCKS rows
-inline int plane_threads(const oa_ctx *c) { return c->ns >= 262144 ? oa::PLANE_THREADS : 256; }
-inline int plane_blocks(const oa_ctx *c) { const int t = plane_threads(c); return std::max(1, (c->ns + t - 1) / t); }
+inline int plane_threads(const oa_ctx *c) { return c->src.ns >= 262144 ? oa::PLANE_THREADS : 256; }
+inline int plane_blocks(const oa_ctx *c) { const int t = plane_threads(c); return std::max(1, (c->src.ns + t - 1) / t); }
 
 // RECIP: every arm's variant that reads the verdict bytes (oa_set_reciprocal or oa_set_trim on); <false> launches what it always has
 template <bool RECIP>
 int launch_accumulate_as(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
 {
-    if (!c->surface) c->win_seeds = true;                          // (the winner records of this pass seed the next search)
+    if (!c->tgt.surface) c->win_seeds = true;                          // (the winner records of this pass seed the next search)
     oa::PairOut po{};
     const oa::PairTest<RECIP> nrm = pair_test<RECIP>(c);
     // the leading arguments of every kernel that opens with pair_fetch (oa_kernels.hpp); each arm adds its own behind them
-    float4 *win = c->surface ? (float4 *)nullptr : c->d_win;
-    const float4 *tri9 = c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr;
-    const float *plane_tn = c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n;
-    auto launch = [&](auto *kern, int blocks, int threads, auto... tail) {
+    float4 *win = c->tgt.surface ? (float4 *)nullptr : c->src.d_win;
+    const float4 *tri9 = c->tgt.surface ? (const float4 *)c->tgt.d_tri9 : (const float4 *)nullptr;
+    const float *plane_tn = c->tgt.surface ? (const float *)nullptr : (const float *)c->tgt.d_tgt_n;
+    auto launch = [&](auto *kern, int blocks, int threads, const auto &... tail) {
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3((unsigned)threads), 0, c->stream, (const oa::DevState *)c->d_state,
-                           (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, c->d_keys, c->d_prev, win, tri9, nrm, tail...);
+                           (const float4 *)c->src.d_src4, c->src.ns, (const float *)c->tgt.d_tgt_xyz, c->src.d_keys, c->src.d_prev, win, tri9, nrm, tail...);
     };
     // the end of the search, for the step record (with the scale taken from the residuals, launch_robust_scale has stamped it)
     unsigned long long *stamp = c->loop_active ? &c->d_state->t_acc_start : (unsigned long long *)nullptr;
     unsigned long long *stamp_w = auto_scale(c) ? (unsigned long long *)nullptr : stamp;
-    const float *w_slot = c->d_w;
+    const float *w_slot = c->src.d_w;
     if (emit) {
-        po.valid = c->d_valid; po.b = c->d_b; po.dist = c->d_dist; po.nn_idx = nn_idx; po.nn_d2 = nn_d2; po.perm = c->d_perm;
+        po.valid = c->src.d_valid; po.b = c->src.d_b; po.dist = c->src.d_dist; po.nn_idx = nn_idx; po.nn_d2 = nn_d2; po.perm = c->src.d_perm;
         launch(oa::k_pair_accumulate<true, RECIP>, c->acc_blocks, oa::ACC_THREADS, c->d_partials, po, (unsigned long long *)nullptr);
     } else if (c->metric == OA_METRIC_PLANE) {
         auto *kern = weighted(c) ? oa::k_pair_accumulate_plane<true, RECIP> : oa::k_pair_accumulate_plane<false, RECIP>;
@@ -1352,7 +1354,7 @@ int launch_accumulate_as(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
     } else if (c->metric == OA_METRIC_GICP) {
         // (begin_loop refuses an estimated scale under this metric: the search always ends here)
         auto *kern = weighted(c) ? oa::k_pair_accumulate_gicp<true, RECIP> : oa::k_pair_accumulate_gicp<false, RECIP>;
-        launch(kern, plane_blocks(c), plane_threads(c), plane_tn, (const float *)c->d_src_n, w_slot, c->d_partials, stamp);
+        launch(kern, plane_blocks(c), plane_threads(c), plane_tn, (const float *)c->src.d_src_n, w_slot, c->d_partials, stamp);
     } else if (weighted(c)) {
         static_assert(oa::WEIGHTED_THREADS == oa::PLANE_THREADS, "plane_threads / plane_blocks size both launches");
         launch(oa::k_pair_accumulate_weighted<RECIP>, plane_blocks(c), plane_threads(c), w_slot, c->d_partials, stamp_w);
@@ -1379,22 +1381,22 @@ void launch_residual_keys(oa_ctx *c, int metric, uint32_t *hist)
     // (launch_accumulate's leading arguments and selections, read-only and without prev; <false> never reads plane_tn)
     auto launch = [&](auto *kern, auto... tail) {
         hipLaunchKernelGGL(kern, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
-                           (const float4 *)c->d_src4, c->ns, (const float *)c->d_tgt_xyz, (const unsigned long long *)c->d_keys,
-                           c->surface ? (const float4 *)nullptr : (const float4 *)c->d_win, c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, nrm,
-                           c->surface ? (const float *)nullptr : (const float *)c->d_tgt_n, tail..., (const float *)c->d_w, c->d_rkeys, hist,
+                           (const float4 *)c->src.d_src4, c->src.ns, (const float *)c->tgt.d_tgt_xyz, (const unsigned long long *)c->src.d_keys,
+                           c->tgt.surface ? (const float4 *)nullptr : (const float4 *)c->src.d_win, c->tgt.surface ? (const float4 *)c->tgt.d_tri9 : (const float4 *)nullptr, nrm,
+                           c->tgt.surface ? (const float *)nullptr : (const float *)c->tgt.d_tgt_n, tail..., (const float *)c->src.d_w, c->src.d_rkeys, hist,
                            &c->d_state->t_acc_start);
     };
-    if constexpr (RECIP) { if (metric == OA_METRIC_GICP) { launch(oa::k_residual_keys_gicp<true>, (const float *)c->d_src_n); return; } }
+    if constexpr (RECIP) { if (metric == OA_METRIC_GICP) { launch(oa::k_residual_keys_gicp<true>, (const float *)c->src.d_src_n); return; } }
     if (metric == OA_METRIC_PLANE) launch(oa::k_residual_keys<true, RECIP>); else launch(oa::k_residual_keys<false, RECIP>);
 }
 int launch_robust_scale(oa_ctx *c)
 {
     if (verdict_on(c)) launch_residual_keys<true>(c, c->metric, c->d_sel_hist); else launch_residual_keys<false>(c, c->metric, c->d_sel_hist);
-    const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
+    const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->src.ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
     for (int level = 0; level < oa::SEL_LEVELS; ++level) {
         if (level > 0)
             hipLaunchKernelGGL(oa::k_select_hist, dim3(hist_blocks), dim3(oa::SEL_THREADS), 0, c->stream, (const oa::DevState *)c->d_state,
-                               (const uint32_t *)c->d_rkeys, c->ns, level, c->d_sel_hist);
+                               (const uint32_t *)c->src.d_rkeys, c->src.ns, level, c->d_sel_hist);
         hipLaunchKernelGGL(oa::k_select_scan, dim3(1), dim3(oa::SEL_THREADS), 0, c->stream, c->d_state, c->d_sel_hist, level);
     }
     HIPCHK(hipGetLastError());
@@ -1406,35 +1408,35 @@ int launch_robust_scale(oa_ctx *c)
 // J), the verdict bytes -- all on the loop's stream (oa_trim.hpp).  metric: whose residual (oa_make_pairs: the point metric's)
 int launch_trim(oa_ctx *c, int metric)
 {
-    if (c->ns <= 0) return OA_OK;                                   // no slot to judge: nothing is allocated for it either (ensure_trim)
-    if (!c->recip_on && !c->bnd_on) HIPCHK(hipMemsetAsync(c->d_recip_ok, 1, (size_t)c->ns, c->stream));   // (else k_recip_check / launch_boundary has just written every byte)
+    if (c->src.ns <= 0) return OA_OK;                                   // no slot to judge: nothing is allocated for it either (ensure_trim)
+    if (!c->recip_on && !c->bnd_on) HIPCHK(hipMemsetAsync(c->src.d_recip_ok, 1, (size_t)c->src.ns, c->stream));   // (else k_recip_check / launch_boundary has just written every byte)
     HIPCHK(hipMemsetAsync(c->d_trim_hist, 0, sizeof(uint32_t) * oa::SEL_LEVELS * oa::SEL_BINS, c->stream));
     launch_residual_keys<true>(c, metric, c->d_trim_hist);
     const oa::DevState *st = c->d_state;
     if (!trim_auto(c)) {
-        const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
+        const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->src.ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
         for (int level = 0; level < oa::SEL_LEVELS; ++level) {
             if (level > 0)
                 hipLaunchKernelGGL(oa::k_dev_select_hist, dim3(hist_blocks, 1), dim3(oa::SEL_THREADS), 0, c->stream, (const oa::DevSelect *)&c->d_trim->sel,
-                                   (const uint32_t *)c->d_rkeys, c->ns, level, c->d_trim_hist);
+                                   (const uint32_t *)c->src.d_rkeys, c->src.ns, level, c->d_trim_hist);
             hipLaunchKernelGGL(oa::k_dev_select_scan, dim3(1), dim3(oa::SEL_THREADS), 0, c->stream, &c->d_trim->sel, (const uint32_t *)c->d_trim_hist, level);
         }
     } else {
-        const int n_tiles = oa::trim_tiles(c->ns);
+        const int n_tiles = oa::trim_tiles(c->src.ns);
         // (all 32 bits: RKEY_NONE sorts last, and the one-workgroup sort and the LSD passes agree on every key)
-        HIPCHK(oa::sort_order((void *)c->d_trim_tmp, (const uint32_t *)c->d_rkeys, c->d_trim_order, (size_t)c->ns, 32, c->stream));
-        hipLaunchKernelGGL(oa::k_gather_int, dim3((unsigned)((c->ns + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->d_rkeys,
-                           (const int *)c->d_trim_order, c->ns, (int *)c->d_trim_sorted);
-        hipLaunchKernelGGL(oa::k_trim_tile_sums, dim3((unsigned)n_tiles), dim3(oa::TRIM_THREADS), 0, c->stream, st, (const uint32_t *)c->d_trim_sorted, c->ns, c->d_trim_tiles);
-        hipLaunchKernelGGL(oa::k_trim_tile_bases, dim3(1), dim3(oa::TRIM_BASE_THREADS), 0, c->stream, st, c->d_trim, (const uint32_t *)c->d_trim_sorted, c->ns,
-                           c->d_trim_tiles, n_tiles);
+        HIPCHK(oa::sort_order((void *)c->src.d_trim_tmp, (const uint32_t *)c->src.d_rkeys, c->src.d_trim_order, (size_t)c->src.ns, 32, c->stream));
+        hipLaunchKernelGGL(oa::k_gather_int, dim3((unsigned)((c->src.ns + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->src.d_rkeys,
+                           (const int *)c->src.d_trim_order, c->src.ns, (int *)c->src.d_trim_sorted);
+        hipLaunchKernelGGL(oa::k_trim_tile_sums, dim3((unsigned)n_tiles), dim3(oa::TRIM_THREADS), 0, c->stream, st, (const uint32_t *)c->src.d_trim_sorted, c->src.ns, c->src.d_trim_tiles);
+        hipLaunchKernelGGL(oa::k_trim_tile_bases, dim3(1), dim3(oa::TRIM_BASE_THREADS), 0, c->stream, st, c->d_trim, (const uint32_t *)c->src.d_trim_sorted, c->src.ns,
+                           c->src.d_trim_tiles, n_tiles);
         hipLaunchKernelGGL(oa::k_trim_apply, dim3((unsigned)n_tiles), dim3(oa::TRIM_THREADS), 0, c->stream, st, (const oa::DevTrim *)c->d_trim,
-                           (const uint32_t *)c->d_trim_sorted, c->ns, (const double *)c->d_trim_tiles, c->d_trim_min);
-        hipLaunchKernelGGL(oa::k_trim_argmin, dim3(1), dim3(oa::TRIM_THREADS), 0, c->stream, st, c->d_trim, (const uint32_t *)c->d_trim_sorted,
-                           (const oa::TrimTileMin *)c->d_trim_min, n_tiles);
+                           (const uint32_t *)c->src.d_trim_sorted, c->src.ns, (const double *)c->src.d_trim_tiles, c->src.d_trim_min);
+        hipLaunchKernelGGL(oa::k_trim_argmin, dim3(1), dim3(oa::TRIM_THREADS), 0, c->stream, st, c->d_trim, (const uint32_t *)c->src.d_trim_sorted,
+                           (const oa::TrimTileMin *)c->src.d_trim_min, n_tiles);
     }
-    const unsigned vblocks = (unsigned)std::min(oa::TRIM_VERDICT_MAX_BLOCKS, std::max(1, (c->ns + oa::TRIM_THREADS - 1) / oa::TRIM_THREADS));
-    hipLaunchKernelGGL(oa::k_trim_verdict, dim3(vblocks), dim3(oa::TRIM_THREADS), 0, c->stream, st, c->d_trim, (const uint32_t *)c->d_rkeys, c->ns, c->d_recip_ok);
+    const unsigned vblocks = (unsigned)std::min(oa::TRIM_VERDICT_MAX_BLOCKS, std::max(1, (c->src.ns + oa::TRIM_THREADS - 1) / oa::TRIM_THREADS));
+    hipLaunchKernelGGL(oa::k_trim_verdict, dim3(vblocks), dim3(oa::TRIM_THREADS), 0, c->stream, st, c->d_trim, (const uint32_t *)c->src.d_rkeys, c->src.ns, c->src.d_recip_ok);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -1471,7 +1473,7 @@ int launch_search_accumulate(oa_ctx *c, bool timed, oa::RowSel &sel, bool &fused
     // the lazy safe radii: counted once per iteration, whatever the plan launches (tree and grid in turns count once; shards too
     // large for the fused path -- BASELINE config 5 on one GPU -- count too: their plain grid search takes seeds on their radii
     // all the same); brute force never reads them
-    if (!c->surface && c->grid_ok && c->grid_mode != 0) { ++c->target_iters; if ((rc = safe_radii_lazy(c))) return rc; }
+    if (!c->tgt.surface && c->tgt.grid_ok && c->grid_mode != 0) { ++c->tgt.target_iters; if ((rc = safe_radii_lazy(c))) return rc; }
     if (s.plan == PLAN_GRID && fused) c->fast_iters++;
     if (timed) {
         if ((rc = ensure_events(c, c->ev_used + 1))) return rc;
@@ -1529,7 +1531,7 @@ double min_singular_3x3(const float *M)
 // 1 / sigma_min(mx2); the arguments are left as they are where no radius applies.
 void search_radius(const oa_ctx *c, const float *mx2, double thresh, double &cut_a, double &cut_b, double &local_per_world)
 {
-    if (!(c->filter_ok && c->grid_mode != 0 && c->tune.nn_cutoff)) return;
+    if (!(c->tgt.filter_ok && c->grid_mode != 0 && c->tune.nn_cutoff)) return;
     const double smin = min_singular_3x3(mx2) * (1.0 - 1e-9);
     if (smin > 0.0) local_per_world = 1.0 / smin;
     double m2norm = 0.0, tmax = 0.0, tscale = 0.0;
@@ -1565,8 +1567,8 @@ void init_loop_state(oa_ctx *c, const oa_settings *st, int iters, bool cutoff = 
     s.t_xchg_start = 0;                                             // (a stale stamp would leak into the first exchange_ticks of this loop)
     s.search_clk[0] = 0; s.search_clk[1] = 0;                       // OA_STAT_SEARCH_CLOCK_MHZ: 0 unless THIS loop's search stamps it
     {   // first search of a loop: the tree (cold or stale seeds); a one-shot call on warm seeds: the grid
-        const bool grid_up = c->surface ? c->tri_grid_ok : c->grid_ok;
-        const oa::GridParams &g = c->surface ? c->tgp : c->gp;
+        const bool grid_up = c->tgt.surface ? c->tgt.tri_grid_ok : c->tgt.grid_ok;
+        const oa::GridParams &g = c->tgt.surface ? c->tgt.tgp : c->tgt.gp;
         s.turn_limit = grid_up ? c->tune.turn_frac * g.h : 0.0;
         s.turn_scale = grid_up ? g.scale : 0.0;
         s.tree_turn = (iters > 1 || !c->seeded) ? 1 : 0;
@@ -1578,7 +1580,7 @@ void init_loop_state(oa_ctx *c, const oa_settings *st, int iters, bool cutoff = 
         else (void)hipGetLastError();
     }
     if (cutoff) search_radius(c, s.mx2, st->thresh, s.cut_a, s.cut_b, s.local_per_world);
-    for (int k = 0; k < 3; ++k) s.pivot[k] = c->pivot[k];
+    for (int k = 0; k < 3; ++k) s.pivot[k] = c->src.pivot[k];
     s.thresh = st->thresh;
     s.target_d = st->target_d;
     for (int k = 0; k < 5; ++k) { s.ring_t[k] = st->target_d * 2.0; s.ring_r[k] = 0.0; }   // icp_align.py:93-94
@@ -1628,22 +1630,22 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
     if (!(st->thresh > 0.0)) return fail(OA_E_BAD_THRESH, "thresh must be > 0 (the reference's make_pairs returns None)");
     if (c->metric == OA_METRIC_PLANE) {
         if (st->with_scale) return fail(OA_E_BAD_ARG, "the plane metric solves for a rigid step: with_scale must be 0 (or call oa_set_metric(ctx, OA_METRIC_POINT))");
-        if (!c->surface && !c->d_tgt_n)
+        if (!c->tgt.surface && !c->tgt.d_tgt_n)
             return fail(OA_E_STATE, "the plane metric needs target normals: call oa_set_target_normals (or oa_set_normals) after oa_set_target, or upload a mesh with oa_set_target_mesh");
-        if ((long long)c->ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
-            return fail(OA_E_CAPACITY, "the plane metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->ns);
+        if ((long long)c->src.ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
+            return fail(OA_E_CAPACITY, "the plane metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->src.ns);
     } else if (c->metric == OA_METRIC_GICP) {
         if (st->with_scale) return fail(OA_E_BAD_ARG, "the GICP metric solves for a rigid step: with_scale must be 0 (or call oa_set_metric(ctx, OA_METRIC_POINT))");
-        if (!c->surface && !c->d_tgt_n)
+        if (!c->tgt.surface && !c->tgt.d_tgt_n)
             return fail(OA_E_STATE, "the GICP metric needs target normals: call oa_set_target_normals (or oa_set_normals) after oa_set_target, or upload a mesh with oa_set_target_mesh");
-        if (!c->d_src_n)
+        if (!c->src.d_src_n)
             return fail(OA_E_STATE, "the GICP metric needs source normals: call oa_set_source_normals (or oa_set_normals) after oa_set_source");
         if (auto_scale(c))
             return fail(OA_E_STATE, "the GICP metric takes a robust loss with a fixed scale only: call oa_set_robust_auto(ctx, 0, 0) (or oa_set_metric(ctx, OA_METRIC_PLANE))");
-        if ((long long)c->ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
-            return fail(OA_E_CAPACITY, "the GICP metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->ns);
-    } else if (weighted(c) && (long long)c->ns > (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS)
-        return fail(OA_E_CAPACITY, "a weighted loop takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS, c->ns);
+        if ((long long)c->src.ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
+            return fail(OA_E_CAPACITY, "the GICP metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->src.ns);
+    } else if (weighted(c) && (long long)c->src.ns > (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS)
+        return fail(OA_E_CAPACITY, "a weighted loop takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS, c->src.ns);
     if ((rc = refuse_recip_shard(c, "a loop"))) return rc;
     if ((rc = refuse_trim_shard(c, "a loop"))) return rc;
     if ((rc = refuse_bnd_shard(c, "a loop"))) return rc;
@@ -1654,7 +1656,7 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
     if ((rc = ensure_bnd_step(c))) return rc;                       // (the target's masks: on this stream, before the loop starts)
     if ((rc = ensure_history(c, iters == ITERATE_OPEN ? ITERATE_RING : iters))) return rc;   // oa_iterate: a small ring
     if (auto_scale(c)) {                                          // the selection's buffers; its histograms start (and are kept) at zero
-        if (!c->d_rkeys) HIPCHK(dev_malloc(&c->d_rkeys, sizeof(uint32_t) * (size_t)std::max(1, c->ns)));
+        if (!c->src.d_rkeys) HIPCHK(dev_malloc(&c->src.d_rkeys, sizeof(uint32_t) * (size_t)std::max(1, c->src.ns)));
         if (!c->d_sel_hist) HIPCHK(dev_malloc(&c->d_sel_hist, sizeof(uint32_t) * oa::SEL_LEVELS * oa::SEL_BINS));
         HIPCHK(hipMemsetAsync(c->d_sel_hist, 0, sizeof(uint32_t) * oa::SEL_LEVELS * oa::SEL_BINS, c->stream));
     }
@@ -1665,9 +1667,9 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
     init_loop_state(c, st, iters);
     *c->h_state_pin = c->h_state;                               // pinned staging copy (the stream is idle, see above)
     HIPCHK(hipMemcpyAsync(c->d_state, c->h_state_pin, sizeof(oa::DevState), hipMemcpyHostToDevice, c->stream));
-    if (c->d_todo_count) HIPCHK(hipMemsetAsync(c->d_todo_count, 0, TODO_COUNT_INTS * sizeof(int), c->stream));   // kept at zero by k_solve_update (the front search's counters: by its launches)
-    c->u_slot = 0;
-    if (!c->surface && (rc = safe_radii_lazy(c))) return rc;
+    if (c->src.d_todo_count) HIPCHK(hipMemsetAsync(c->src.d_todo_count, 0, TODO_COUNT_INTS * sizeof(int), c->stream));   // kept at zero by k_solve_update (the front search's counters: by its launches)
+    c->src.u_slot = 0;
+    if (!c->tgt.surface && (rc = safe_radii_lazy(c))) return rc;
     hipLaunchKernelGGL(oa::k_stamp_start, dim3(1), dim3(64), 0, c->stream, c->d_state);
     HIPCHK(hipGetLastError());
     c->ev_used = 0;
@@ -1676,7 +1678,7 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
     c->h_hist_valid = false;
     {
         // (surfaces: NOT kind == SEARCH_BRUTE -- a mesh with a tree but no grid counts as a tree search here, as it always has)
-        const bool brute = !c->surface ? choose_search(c).kind == SEARCH_BRUTE : (c->grid_mode == 0 || !c->tbvh_ok);
+        const bool brute = !c->tgt.surface ? choose_search(c).kind == SEARCH_BRUTE : (c->grid_mode == 0 || !c->tgt.tbvh_ok);
         c->time_events = c->tune.time_events < 0 ? brute : c->tune.time_events != 0;
     }
     c->loop_active = true;
@@ -1694,7 +1696,7 @@ int iter_partial(oa_ctx *c, double *d_sums, bool timed)
 
 int iter_finish(oa_ctx *c, const double *d_sums)
 {
-    hipLaunchKernelGGL(oa::k_solve_update, dim3(1), dim3(128), 0, c->stream, c->d_state, d_sums, c->d_hist, c->d_todo_count);
+    hipLaunchKernelGGL(oa::k_solve_update, dim3(1), dim3(128), 0, c->stream, c->d_state, d_sums, c->d_hist, c->src.d_todo_count);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -1708,10 +1710,10 @@ int iter_fused(oa_ctx *c, bool timed)
     if (rc) return rc;
     if (plane_row_metric(c))
         hipLaunchKernelGGL(oa::k_reduce_solve_update_plane, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, c->d_state,
-                           (const double *)c->d_partials, sel.n, c->d_sums, c->d_hist, c->d_todo_count);
+                           (const double *)c->d_partials, sel.n, c->d_sums, c->d_hist, c->src.d_todo_count);
     else
         hipLaunchKernelGGL(oa::k_reduce_solve_update, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, c->d_state,
-                           (const double *)c->d_partials, sel, c->d_sums, c->d_hist, c->d_todo_count, fused ? 1 : 0);
+                           (const double *)c->d_partials, sel, c->d_sums, c->d_hist, c->src.d_todo_count, fused ? 1 : 0);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -2220,7 +2222,7 @@ int multi_iteration_group(oa_ctx *p, const std::vector<int> &group, bool timed)
         if (x->mode == OA_EXCHANGE_RCCL) rc = iter_finish(c, c->d_sums);
         else {
             hipLaunchKernelGGL(oa::k_gather_solve_update, dim3(1), dim3(128), 0, c->stream, c->d_state, x->box[(size_t)c->rank],
-                               x->world, c->d_sums, c->d_hist, c->d_todo_count, x->timeout_ticks);
+                               x->world, c->d_sums, c->d_hist, c->src.d_todo_count, x->timeout_ticks);
             HIPCHK(hipGetLastError());
         }
         if (rc) return rc;
@@ -2441,7 +2443,7 @@ OA_EXPORT int oa_create(oa_ctx **out, int device)
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
     if (e != hipSuccess) { delete c; return fail(OA_E_HIP, "oa_create: %s", hipGetErrorString(e)); }
     c->stream = c->own_stream;
-    c->R = c->tune.nn_r ? c->tune.nn_r : 4;
+    c->src.R = c->tune.nn_r ? c->tune.nn_r : 4;
     c->grid_mode = c->tune.nn_grid;
     dev_cache().context_created();
     *out = c;
@@ -2578,19 +2580,7 @@ OA_EXPORT void oa_destroy(oa_ctx *c)
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     tl_stream_known = false;                                        // the stream below is about to go away
-#define OA_FREE(x) dev_free(c->x, true)
-    OA_FREE(d_tgt_xyz); OA_FREE(d_tg); OA_FREE(d_tf); OA_FREE(d_tf3); OA_FREE(d_tfs); OA_FREE(d_tf3s); OA_FREE(d_tgs); OA_FREE(d_tmw); OA_FREE(d_tidx); OA_FREE(d_tfm); OA_FREE(d_members); OA_FREE(d_pos); OA_FREE(d_prev); OA_FREE(d_win); OA_FREE(d_prec); OA_FREE(d_homes); OA_FREE(d_qcnt); OA_FREE(d_wsafe); OA_FREE(d_safe_by_idx); OA_FREE(d_cell_start);
-    OA_FREE(d_sorted); OA_FREE(d_todo_list); OA_FREE(d_todo_count); OA_FREE(d_ulist); OA_FREE(d_src4); OA_FREE(d_keys); OA_FREE(d_state);
-    OA_FREE(d_partials); OA_FREE(d_sums); OA_FREE(d_solve);
-    OA_FREE(d_valid); OA_FREE(d_b); OA_FREE(d_dist); OA_FREE(d_counts); OA_FREE(d_offsets); OA_FREE(d_A); OA_FREE(d_B);
-    OA_FREE(d_bvh_box); OA_FREE(d_bvh_prims); OA_FREE(d_tbvh_box); OA_FREE(d_tbvh_prims);
-    OA_FREE(d_tri9); OA_FREE(d_tcell_start); OA_FREE(d_tcell_rec); OA_FREE(d_tri_ring); OA_FREE(d_tfine_table); OA_FREE(d_tfine_rec);
-    OA_FREE(d_sel); OA_FREE(d_src_n); OA_FREE(d_tgt_n); OA_FREE(d_tgt_feat); OA_FREE(d_w); OA_FREE(d_rkeys); OA_FREE(d_sel_hist); OA_FREE(d_src4o); OA_FREE(d_perm);
-    OA_FREE(d_sbvh_box); OA_FREE(d_sbvh_prims); OA_FREE(d_recip_ok); OA_FREE(d_recip_count);
-    OA_FREE(d_trim); OA_FREE(d_trim_hist); OA_FREE(d_trim_sorted); OA_FREE(d_trim_order); OA_FREE(d_trim_tmp); OA_FREE(d_trim_tiles); OA_FREE(d_trim_min);
-    OA_FREE(d_bnd_vmask); OA_FREE(d_bnd_emask); OA_FREE(d_bnd_count); OA_FREE(d_corner_order); OA_FREE(d_corner_row);
-    OA_FREE(d_tris); OA_FREE(d_pn_face); OA_FREE(d_pn_vertex); OA_FREE(d_pn_edge);
-#undef OA_FREE
+    const oa::DevTeardown settled;                                  // the device is idle: `delete c` hands every block back without a synchronisation each
     if (c->h_hist_map) (void)hipHostFree(c->h_hist_map);
     if (c->h_state_pin) (void)hipHostFree(c->h_state_pin);
     if (c->h_scratch) (void)hipHostFree(c->h_scratch);
@@ -2609,26 +2599,26 @@ OA_EXPORT int oa_set_search_mode(oa_ctx *c, int mode)
     if (!c) return fail(OA_E_BAD_ARG, "null context");
     if (mode < -1 || mode > 2) return fail(OA_E_BAD_ARG, "search mode %d (use OA_SEARCH_AUTO/BRUTE/GRID/BVH)", mode);
     OA_ROUTE_ALL(c, oa_set_search_mode(sub, mode));
-    const bool rebuild = (c->grid_mode == 0 && mode != 0 && c->nt > 0);
-    const bool sorted_now = (mode == 0 && c->nt > 0 && !c->surface && !c->d_tfs);   // (skipped when the target was uploaded)
+    const bool rebuild = (c->grid_mode == 0 && mode != 0 && c->tgt.nt > 0);
+    const bool sorted_now = (mode == 0 && c->tgt.nt > 0 && !c->tgt.surface && !c->tgt.d_tfs);   // (skipped when the target was uploaded)
     c->grid_mode = mode;
     if (sorted_now) {
         int rc = use_device(c);
         if (rc) return rc;
         if ((rc = build_sorted_images(c))) return rc;
     }
-    if (mode == 0 && c->ns_pad > 0 && c->d_src4) {                  // (a source uploaded for the other modes: what source_reset allocates for this one)
+    if (mode == 0 && c->src.ns_pad > 0 && c->src.d_src4) {                  // (a source uploaded for the other modes: what source_reset allocates for this one)
         int rc = use_device(c);
         if (rc) return rc;
-        if ((rc = ensure_sorted_buffers(c, c->ns_pad / (oa::NN_THREADS * c->R)))) return rc;
+        if ((rc = ensure_sorted_buffers(c, c->src.ns_pad / (oa::NN_THREADS * c->src.R)))) return rc;
     }
     if (rebuild) {                                   // the grids were skipped when the target was uploaded
         int rc = use_device(c);
         if (rc) return rc;
-        if (!c->grid_ok && (rc = build_grid(c))) return rc;
-        if (!c->bvh_ok && (rc = build_bvh(c, false))) return rc;
-        if (c->surface && !c->tri_grid_ok && (rc = build_tri_grid(c))) return rc;
-        if (c->surface && !c->tbvh_ok && (rc = build_bvh(c, true))) return rc;
+        if (!c->tgt.grid_ok && (rc = build_grid(c))) return rc;
+        if (!c->tgt.bvh_ok && (rc = build_bvh(c, false))) return rc;
+        if (c->tgt.surface && !c->tgt.tri_grid_ok && (rc = build_tri_grid(c))) return rc;
+        if (c->tgt.surface && !c->tgt.tbvh_ok && (rc = build_bvh(c, true))) return rc;
     }
     return OA_OK;
 }
@@ -2676,8 +2666,8 @@ int bbox_partials(oa_ctx *c, const float *d_xyz, long long n, int nb, float *out
 // inside a loop.
 int build_sorted_images(oa_ctx *c)
 {
-    dev_free(c->d_tfs); dev_free(c->d_tf3s); dev_free(c->d_tgs); dev_free(c->d_tmw); dev_free(c->d_tidx);
-    if (!(c->filter_ok && c->tune.nn_sort && c->nt >= 2)) return OA_OK;
+    c->tgt.d_tfs.reset(); c->tgt.d_tf3s.reset(); c->tgt.d_tgs.reset(); c->tgt.d_tmw.reset(); c->tgt.d_tidx.reset();
+    if (!(c->tgt.filter_ok && c->tune.nn_sort && c->tgt.nt >= 2)) return OA_OK;
     const double *lo = c->bb_lo, *hi = c->bb_hi;
     const int ad = c->fax[2];
     int su = 0;
@@ -2685,26 +2675,26 @@ int build_sorted_images(oa_ctx *c)
     const int sd = ad != su ? ad : (su + 1) % 3;                   // (all extents equal: any other axis)
     c->sax[0] = su; c->sax[2] = sd; c->sax[1] = 3 - su - sd;
     const double ext = hi[su] - lo[su];
-    const int blocks = (c->n_groups_pad + 255) / 256;
+    const int blocks = (c->tgt.n_groups_pad + 255) / 256;
     DevTmp<unsigned> k_in;
     DevTmp<int> v_in, v_out;
-    HIPCHK(k_in.alloc((size_t)c->nt)); HIPCHK(v_in.alloc((size_t)c->nt)); HIPCHK(v_out.alloc((size_t)c->nt));
-    hipLaunchKernelGGL(oa::k_sort_keys_axis, dim3((c->nt + 255) / 256), dim3(256), 0, c->stream, (const float *)c->d_tgt_xyz, c->nt, su, lo[su],
+    HIPCHK(k_in.alloc((size_t)c->tgt.nt)); HIPCHK(v_in.alloc((size_t)c->tgt.nt)); HIPCHK(v_out.alloc((size_t)c->tgt.nt));
+    hipLaunchKernelGGL(oa::k_sort_keys_axis, dim3((c->tgt.nt + 255) / 256), dim3(256), 0, c->stream, (const float *)c->tgt.d_tgt_xyz, c->tgt.nt, su, lo[su],
                        ext > 0.0 ? 1073741823.0 / ext : 0.0, k_in.p, v_in.p);
     HIPCHK(hipGetLastError());
-    { const int rcs = sort_order_bits(c, k_in.p, v_out.p, (size_t)c->nt, 30); if (rcs) return rcs; }
+    { const int rcs = sort_order_bits(c, k_in.p, v_out.p, (size_t)c->tgt.nt, 30); if (rcs) return rcs; }
     if (c->tune.nn_vchunk) {                                           // every block of the u order by v, its first vertex kept (k_sort_blocks_v)
-        hipLaunchKernelGGL(oa::k_sort_blocks_v, dim3((unsigned)((c->nt + oa::SORTED_VBLOCK - 1) / oa::SORTED_VBLOCK)), dim3(oa::SORTED_VBLOCK), 0,
-                           c->stream, (const float *)c->d_tgt_xyz, c->nt, c->sax[1], c->tc[c->sax[1]], v_out.p);
+        hipLaunchKernelGGL(oa::k_sort_blocks_v, dim3((unsigned)((c->tgt.nt + oa::SORTED_VBLOCK - 1) / oa::SORTED_VBLOCK)), dim3(oa::SORTED_VBLOCK), 0,
+                           c->stream, (const float *)c->tgt.d_tgt_xyz, c->tgt.nt, c->sax[1], c->tc[c->sax[1]], v_out.p);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(dev_malloc(&c->d_tfs, sizeof(float4) * 3 * (size_t)c->n_groups_pad));
-    HIPCHK(dev_malloc(&c->d_tf3s, sizeof(float4) * 2 * (size_t)c->n_groups_pad));
-    HIPCHK(dev_malloc(&c->d_tgs, sizeof(float4) * 3 * (size_t)c->n_groups_pad));
-    HIPCHK(dev_malloc(&c->d_tidx, sizeof(int4) * (size_t)c->n_groups_pad));
-    HIPCHK(dev_malloc(&c->d_tmw, sizeof(float4) * (size_t)c->n_groups_pad));
-    hipLaunchKernelGGL(oa::k_pack_sorted, dim3((unsigned)blocks), dim3(256), 0, c->stream, (const float *)c->d_tgt_xyz, c->nt, c->n_groups_pad,
-                       (const int *)v_out.p, c->tc[0], c->tc[1], c->tc[2], c->sax[0], c->sax[1], c->sax[2], c->d_tfs, c->d_tf3s, c->d_tgs, c->d_tidx, c->d_tmw);
+    HIPCHK(dev_malloc(&c->tgt.d_tfs, sizeof(float4) * 3 * (size_t)c->tgt.n_groups_pad));
+    HIPCHK(dev_malloc(&c->tgt.d_tf3s, sizeof(float4) * 2 * (size_t)c->tgt.n_groups_pad));
+    HIPCHK(dev_malloc(&c->tgt.d_tgs, sizeof(float4) * 3 * (size_t)c->tgt.n_groups_pad));
+    HIPCHK(dev_malloc(&c->tgt.d_tidx, sizeof(int4) * (size_t)c->tgt.n_groups_pad));
+    HIPCHK(dev_malloc(&c->tgt.d_tmw, sizeof(float4) * (size_t)c->tgt.n_groups_pad));
+    hipLaunchKernelGGL(oa::k_pack_sorted, dim3((unsigned)blocks), dim3(256), 0, c->stream, (const float *)c->tgt.d_tgt_xyz, c->tgt.nt, c->tgt.n_groups_pad,
+                       (const int *)v_out.p, c->tc[0], c->tc[1], c->tc[2], c->sax[0], c->sax[1], c->sax[2], c->tgt.d_tfs, c->tgt.d_tf3s, c->tgt.d_tgs, c->tgt.d_tidx, c->tgt.d_tmw);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));                      // (the temporaries are released on return)
     return OA_OK;
@@ -2712,10 +2702,10 @@ int build_sorted_images(oa_ctx *c)
 
 int build_filter(oa_ctx *c, bool vertex_target)
 {
-    c->filter_ok = false;
+    c->tgt.filter_ok = false;
     const int nb = 256;
     std::vector<float> bb(6 * nb);
-    { int rcb = bbox_partials(c, c->d_tgt_xyz, c->nt, nb, bb.data()); if (rcb) return rcb; }
+    { int rcb = bbox_partials(c, c->tgt.d_tgt_xyz, c->tgt.nt, nb, bb.data()); if (rcb) return rcb; }
     double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
     bool finite = true;
     for (int b = 0; b < nb; ++b)
@@ -2733,11 +2723,11 @@ int build_filter(oa_ctx *c, bool vertex_target)
     for (int a = 1; a < 3; ++a) if (hi[a] - lo[a] < hi[ad] - lo[ad]) ad = a;
     c->fax[2] = ad; c->fax[0] = (ad + 1) % 3; c->fax[1] = (ad + 2) % 3;
     if (c->fax[0] > c->fax[1]) std::swap(c->fax[0], c->fax[1]);
-    const int blocks = (c->n_groups_pad + 255) / 256;
+    const int blocks = (c->tgt.n_groups_pad + 255) / 256;
     DevTmp<double> d_mx;
 #if defined(OA_EXPERIMENTS)        // the images in the caller's order are k_nn_search_filtered's (OA_NN_SORT=0); the launch below still finds qmax
-    HIPCHK(dev_malloc(&c->d_tf, sizeof(float4) * 3 * (size_t)c->n_groups_pad));
-    HIPCHK(dev_malloc(&c->d_tf3, sizeof(float4) * 2 * (size_t)c->n_groups_pad));
+    HIPCHK(dev_malloc(&c->tgt.d_tf, sizeof(float4) * 3 * (size_t)c->tgt.n_groups_pad));
+    HIPCHK(dev_malloc(&c->tgt.d_tf3, sizeof(float4) * 2 * (size_t)c->tgt.n_groups_pad));
 #endif
     std::vector<double> mx((size_t)blocks);
     {
@@ -2745,8 +2735,8 @@ int build_filter(oa_ctx *c, bool vertex_target)
         void *dv; const void *hv;
         { int rcv = result_buffer(c, sizeof(double) * (size_t)blocks, &dv, &hv); if (rcv) return rcv; }
         if (!dv) HIPCHK(d_mx.alloc((size_t)blocks));
-        hipLaunchKernelGGL(oa::k_pack_filter, dim3(blocks), dim3(256), 0, c->stream, c->d_tgt_xyz, c->nt, c->n_groups_pad,
-                           c->tc[0], c->tc[1], c->tc[2], c->fax[0], c->fax[1], c->fax[2], c->d_tf, c->d_tf3, dv ? (double *)dv : d_mx.p);
+        hipLaunchKernelGGL(oa::k_pack_filter, dim3(blocks), dim3(256), 0, c->stream, c->tgt.d_tgt_xyz, c->tgt.nt, c->tgt.n_groups_pad,
+                           c->tc[0], c->tc[1], c->tc[2], c->fax[0], c->fax[1], c->fax[2], c->tgt.d_tf, c->tgt.d_tf3, dv ? (double *)dv : d_mx.p);
         HIPCHK(hipGetLastError());
         if (dv) { HIPCHK(hipStreamSynchronize(c->stream)); memcpy(mx.data(), hv, sizeof(double) * (size_t)blocks); }
         else { int rcr = read_small(c, mx.data(), d_mx, sizeof(double) * (size_t)blocks); if (rcr) return rcr; }
@@ -2754,22 +2744,22 @@ int build_filter(oa_ctx *c, bool vertex_target)
     double m = 0.0;
     for (double v : mx) if (v > m) m = v;
     c->qmax = sqrt(m) * (1.0 + 1e-6);
-    c->filter_ok = (c->qmax < 1e18);
-    dev_free(c->d_tfs); dev_free(c->d_tf3s); dev_free(c->d_tgs); dev_free(c->d_tmw); dev_free(c->d_tidx);
+    c->tgt.filter_ok = (c->qmax < 1e18);
+    c->tgt.d_tfs.reset(); c->tgt.d_tf3s.reset(); c->tgt.d_tgs.reset(); c->tgt.d_tmw.reset(); c->tgt.d_tidx.reset();
     // k_nn_search_sorted's images are built for the search mode that uses them: a target uploaded for the grid / tree searches
     // (OA_SEARCH_AUTO, the default) does not pay for them; oa_set_search_mode(OA_SEARCH_BRUTE) builds them when it finds none
     // (a mesh's surface searches never launch k_nn_search_sorted: no images, no sort -- ~36 B per vertex)
     if (c->grid_mode == 0 && vertex_target) { const int rcs = build_sorted_images(c); if (rcs) return rcs; }
-    dev_free(c->d_tfm);
+    c->tgt.d_tfm.reset();
 #if defined(OA_EXPERIMENTS)
-    if (c->filter_ok && c->tune.nn_mfma) {                            // experiment: the MFMA image (32 B per target)
+    if (c->tgt.filter_ok && c->tune.nn_mfma) {                            // experiment: the MFMA image (32 B per target)
         int e = 0;
         if (c->qmax > 0.0) { frexp(c->qmax, &e); }               // qmax = f 2^e, f in [0.5, 1)  ->  qmax 2^-e < 1
         c->mfma_sigma = ldexp(1.0, -e);
-        const int n_targets_pad = c->n_groups_pad * 4;
-        HIPCHK(dev_malloc(&c->d_tfm, sizeof(oa::half8) * 2 * (size_t)n_targets_pad));
-        hipLaunchKernelGGL(oa::k_pack_filter_mfma, dim3((unsigned)((n_targets_pad + 255) / 256)), dim3(256), 0, c->stream, c->d_tgt_xyz,
-                           c->nt, n_targets_pad, c->tc[0], c->tc[1], c->tc[2], c->fax[0], c->fax[1], c->fax[2], c->mfma_sigma, c->d_tfm);
+        const int n_targets_pad = c->tgt.n_groups_pad * 4;
+        HIPCHK(dev_malloc(&c->tgt.d_tfm, sizeof(oa::half8) * 2 * (size_t)n_targets_pad));
+        hipLaunchKernelGGL(oa::k_pack_filter_mfma, dim3((unsigned)((n_targets_pad + 255) / 256)), dim3(256), 0, c->stream, c->tgt.d_tgt_xyz,
+                           c->tgt.nt, n_targets_pad, c->tc[0], c->tc[1], c->tc[2], c->fax[0], c->fax[1], c->fax[2], c->mfma_sigma, c->tgt.d_tfm);
         HIPCHK(hipGetLastError());
     }
 #endif
@@ -2780,22 +2770,22 @@ int build_filter(oa_ctx *c, bool vertex_target)
 // launch on the context's stream, no wait: the searches that use the radii are enqueued behind it.
 int build_safe_radii(oa_ctx *c)
 {
-    if (!c->grid_ok || c->safe_ok || !c->d_safe_by_idx || c->nt < 2) return OA_OK;
-    hipLaunchKernelGGL(oa::k_grid_safe_radius, dim3((c->nt + 255) / 256), dim3(256), 0, c->stream, (const float4 *)c->d_sorted, c->nt, c->gp,
-                       (const int *)c->d_cell_start, c->d_safe_by_idx);
+    if (!c->tgt.grid_ok || c->tgt.safe_ok || !c->tgt.d_safe_by_idx || c->tgt.nt < 2) return OA_OK;
+    hipLaunchKernelGGL(oa::k_grid_safe_radius, dim3((c->tgt.nt + 255) / 256), dim3(256), 0, c->stream, (const float4 *)c->tgt.d_sorted, c->tgt.nt, c->tgt.gp,
+                       (const int *)c->tgt.d_cell_start, c->tgt.d_safe_by_idx);
     HIPCHK(hipGetLastError());
-    c->safe_ok = true;
+    c->tgt.safe_ok = true;
     return OA_OK;
 }
 
 // uniform grid over the target for k_nn_search_grid (needs the finite bbox build_filter found)
 int build_grid(oa_ctx *c)
 {
-    c->grid_ok = false;
-    dev_free(c->d_cell_start); dev_free(c->d_sorted); dev_free(c->d_safe_by_idx);
-    c->safe_ok = false;
-    if (!c->filter_ok || c->grid_mode == 0 || c->nt < 2) return OA_OK;
-    if ((long long)c->nt > oa::GRID_MAX_TARGETS) return OA_OK;       // k_nn_search_grid addresses `sorted` through 32-bit byte offsets; the tree takes over
+    c->tgt.grid_ok = false;
+    c->tgt.d_cell_start.reset(); c->tgt.d_sorted.reset(); c->tgt.d_safe_by_idx.reset();
+    c->tgt.safe_ok = false;
+    if (!c->tgt.filter_ok || c->grid_mode == 0 || c->tgt.nt < 2) return OA_OK;
+    if ((long long)c->tgt.nt > oa::GRID_MAX_TARGETS) return OA_OK;       // k_nn_search_grid addresses `sorted` through 32-bit byte offsets; the tree takes over
     double ext[3], vol = 1.0, scale = 0.0;
     int nz = 0;
     for (int a = 0; a < 3; ++a) {
@@ -2804,14 +2794,14 @@ int build_grid(oa_ctx *c)
         scale = std::max(scale, std::max(fabs(c->bb_lo[a]), fabs(c->bb_hi[a])));
     }
     const double ppc = c->tune.grid_ppc;                          // target vertices per cell
-    double h = nz ? pow(vol * ppc / (double)c->nt, 1.0 / nz) : 1.0;
+    double h = nz ? pow(vol * ppc / (double)c->tgt.nt, 1.0 / nz) : 1.0;
     if (!(h > 0.0) || !(h < INFINITY)) return OA_OK;
     const long long max_cells = 1ll << 24;
     static_assert((1ll << 24) <= oa::GRID_MAX_CELLS, "cell_start is addressed through 32-bit byte offsets");
     DevTmp<int2> d_cell_of;                                         // per vertex {cell, rank inside the cell}
     DevTmp<int> d_counts;
     DevTmp<long long> d_off;
-    HIPCHK(d_cell_of.alloc((size_t)c->nt));
+    HIPCHK(d_cell_of.alloc((size_t)c->tgt.nt));
     oa::GridParams gp{};
     int n_cells = 0;
     for (int attempt = 0; attempt < 6; ++attempt) {
@@ -2847,7 +2837,7 @@ int build_grid(oa_ctx *c)
         { int rcv = result_buffer(c, sizeof(int) * (size_t)nz_blocks, &dv, &hv); if (rcv) return rcv; }
         int *d_nz = dv ? (int *)dv : d_counts.p + n_cells + 1;
         HIPCHK(hipMemsetAsync(d_counts, 0, sizeof(int) * ((size_t)n_cells + 1), c->stream));
-        hipLaunchKernelGGL(oa::k_grid_count, dim3((c->nt + 255) / 256), dim3(256), 0, c->stream, c->d_tgt_xyz, c->nt, gp, d_cell_of.p, d_counts.p);
+        hipLaunchKernelGGL(oa::k_grid_count, dim3((c->tgt.nt + 255) / 256), dim3(256), 0, c->stream, c->tgt.d_tgt_xyz, c->tgt.nt, gp, d_cell_of.p, d_counts.p);
         hipLaunchKernelGGL(oa::k_count_nonzero, dim3((unsigned)nz_blocks), dim3(1024), 0, c->stream, d_counts.p, n_cells, d_nz);
         HIPCHK(hipGetLastError());
         std::vector<int> nz((size_t)nz_blocks);
@@ -2855,23 +2845,23 @@ int build_grid(oa_ctx *c)
         else { int rcr = read_small(c, nz.data(), d_nz, sizeof(int) * (size_t)nz_blocks); if (rcr) return rcr; }
         long long occupied = 0;
         for (int v : nz) occupied += v;
-        const double avg = occupied > 0 ? (double)c->nt / occupied : 0.0;
+        const double avg = occupied > 0 ? (double)c->tgt.nt / occupied : 0.0;
         // surfaces fill few cells: refine until occupied cells hold a handful of vertices each
         if (avg > 6.0 && total * 8 <= max_cells && attempt < 5) { h *= 0.5; continue; }
         break;
     }
     if (n_cells <= 0) return OA_OK;
-    HIPCHK(dev_malloc(&c->d_cell_start, sizeof(int) * (size_t)(n_cells + 1)));
-    HIPCHK(dev_malloc(&c->d_sorted, sizeof(float4) * (size_t)c->nt));
+    HIPCHK(dev_malloc(&c->tgt.d_cell_start, sizeof(int) * (size_t)(n_cells + 1)));
+    HIPCHK(dev_malloc(&c->tgt.d_sorted, sizeof(float4) * (size_t)c->tgt.nt));
     DevTmp<char> scan_tmp;                                           // released on return, behind the wait below
     { int rcs = scan_counts(c, d_counts.p, n_cells, d_off.p, scan_tmp); if (rcs) return rcs; }
-    hipLaunchKernelGGL(oa::k_grid_starts, dim3((n_cells + 256) / 256), dim3(256), 0, c->stream, d_off.p, n_cells, c->d_cell_start, (int *)nullptr);
-    hipLaunchKernelGGL(oa::k_grid_scatter, dim3((c->nt + 255) / 256), dim3(256), 0, c->stream, c->d_tgt_xyz, c->nt, (const int2 *)d_cell_of.p, (const int *)c->d_cell_start, c->d_sorted);
+    hipLaunchKernelGGL(oa::k_grid_starts, dim3((n_cells + 256) / 256), dim3(256), 0, c->stream, d_off.p, n_cells, c->tgt.d_cell_start, (int *)nullptr);
+    hipLaunchKernelGGL(oa::k_grid_scatter, dim3((c->tgt.nt + 255) / 256), dim3(256), 0, c->stream, c->tgt.d_tgt_xyz, c->tgt.nt, (const int2 *)d_cell_of.p, (const int *)c->tgt.d_cell_start, c->tgt.d_sorted);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
-    c->gp = gp; c->n_cells = n_cells; c->grid_ok = true;
-    c->target_iters = 0;
-    if (c->tune.grid_safe) HIPCHK(dev_malloc(&c->d_safe_by_idx, sizeof(float) * (size_t)c->nt));
+    c->tgt.gp = gp; c->tgt.n_cells = n_cells; c->tgt.grid_ok = true;
+    c->tgt.target_iters = 0;
+    if (c->tune.grid_safe) HIPCHK(dev_malloc(&c->tgt.d_safe_by_idx, sizeof(float) * (size_t)c->tgt.nt));
     if (c->tune.grid_safe == 2) return build_safe_radii(c);
     return OA_OK;
 }
@@ -2887,50 +2877,37 @@ int set_target_common(oa_ctx *c, const float *xyz, int64_t n, int on_device, boo
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     c->loop_active = false;                                         // an open oa_iterate sequence ends with the old target
-    dev_free(c->d_tgt_xyz); dev_free(c->d_tg); dev_free(c->d_tf); dev_free(c->d_tf3); dev_free(c->d_tfm);
-    dev_free(c->d_tfs); dev_free(c->d_tf3s); dev_free(c->d_tgs); dev_free(c->d_tmw); dev_free(c->d_tidx);
-    dev_free(c->d_tri9); dev_free(c->d_tcell_start); dev_free(c->d_tcell_rec); dev_free(c->d_tri_ring);
-    dev_free(c->d_tfine_table); dev_free(c->d_tfine_rec);
-    dev_free(c->d_tris); dev_free(c->d_pn_face); dev_free(c->d_pn_vertex); dev_free(c->d_pn_edge);
-    c->pn_ok = false;
-    dev_free(c->d_corner_order); dev_free(c->d_corner_row); c->corner_ok = false;
-    dev_free(c->d_bnd_vmask); dev_free(c->d_bnd_emask); c->bnd_ok = false;   // (the masks are the old target's)
-    c->tri_ring_ok = false; c->tri_fine_ok = false;
-    dev_free(c->d_bvh_box); dev_free(c->d_bvh_prims); dev_free(c->d_tbvh_box); dev_free(c->d_tbvh_prims);
-    c->surface = false; c->tri_grid_ok = false; c->n_tris = 0; c->bvh_ok = false; c->tbvh_ok = false;
-    dev_free(c->d_tgt_n); dev_free(c->d_tgt_feat);
+    c->tgt = {};                                                    // every image, index and mask of the old target, and what was counted for it
     c->normals_on = false;
-    c->filter_ok = false;
-    c->nt = (int)n;
-    c->n_groups_pad = 0;
+    c->tgt.nt = (int)n;
     c->seeded = false; c->win_seeds = false;
     // {index, safe radius} per slot: only the vertex searches read it (8 bytes per source point)
-    if (!vertex_index || !c->tune.grid_safe) dev_free(c->d_wsafe);
-    else if (c->d_prev && !c->d_wsafe) HIPCHK(dev_malloc(&c->d_wsafe, sizeof(uint2) * (size_t)c->ns_pad));
-    if (c->d_prev) {   // seeds index the old target
+    if (!vertex_index || !c->tune.grid_safe) c->src.d_wsafe.reset();
+    else if (c->src.d_prev && !c->src.d_wsafe) HIPCHK(dev_malloc(&c->src.d_wsafe, sizeof(uint2) * (size_t)c->src.ns_pad));
+    if (c->src.d_prev) {   // seeds index the old target
         // (the safe radii beside the winner records belong to the old target's indices too)
-        hipLaunchKernelGGL(oa::k_init_slots, dim3((c->ns_pad + 255) / 256), dim3(256), 0, c->stream, c->d_prev, c->d_win, c->d_wsafe,
-                           (unsigned long long *)nullptr, (int *)nullptr, (int *)nullptr, c->ns_pad);
+        hipLaunchKernelGGL(oa::k_init_slots, dim3((c->src.ns_pad + 255) / 256), dim3(256), 0, c->stream, c->src.d_prev, c->src.d_win, c->src.d_wsafe,
+                           (unsigned long long *)nullptr, (int *)nullptr, (int *)nullptr, c->src.ns_pad);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     if (n == 0) return OA_OK;
-    HIPCHK(dev_malloc(&c->d_tgt_xyz, sizeof(float) * 3 * (size_t)n));
+    HIPCHK(dev_malloc(&c->tgt.d_tgt_xyz, sizeof(float) * 3 * (size_t)n));
     {
         // a device pointer may live on another GPU of the process (multi-device contexts replicate the target)
         const int src_dev = on_device ? pointer_device(xyz) : -1;
         if (on_device && src_dev >= 0 && src_dev != c->device)
-            HIPCHK(hipMemcpyPeerAsync(c->d_tgt_xyz, c->device, xyz, src_dev, sizeof(float) * 3 * (size_t)n, c->stream));
+            HIPCHK(hipMemcpyPeerAsync(c->tgt.d_tgt_xyz, c->device, xyz, src_dev, sizeof(float) * 3 * (size_t)n, c->stream));
         else
-            HIPCHK(hipMemcpyAsync(c->d_tgt_xyz, xyz, sizeof(float) * 3 * (size_t)n,
+            HIPCHK(hipMemcpyAsync(c->tgt.d_tgt_xyz, xyz, sizeof(float) * 3 * (size_t)n,
                                   on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     }
     const long long groups = (n + 3) / 4;
     const long long tiles = (groups + oa::TILE_GROUPS - 1) / oa::TILE_GROUPS;
-    c->n_groups_pad = (int)(tiles * oa::TILE_GROUPS);
-    HIPCHK(dev_malloc(&c->d_tg, sizeof(float4) * 3 * (size_t)c->n_groups_pad));
-    hipLaunchKernelGGL(oa::k_pack_target, dim3((c->n_groups_pad + 255) / 256), dim3(256), 0, c->stream, c->d_tgt_xyz,
-                       c->nt, c->n_groups_pad, c->d_tg);
+    c->tgt.n_groups_pad = (int)(tiles * oa::TILE_GROUPS);
+    HIPCHK(dev_malloc(&c->tgt.d_tg, sizeof(float4) * 3 * (size_t)c->tgt.n_groups_pad));
+    hipLaunchKernelGGL(oa::k_pack_target, dim3((c->tgt.n_groups_pad + 255) / 256), dim3(256), 0, c->stream, c->tgt.d_tgt_xyz,
+                       c->tgt.nt, c->tgt.n_groups_pad, c->tgt.d_tg);
     HIPCHK(hipGetLastError());
     int rcf = build_filter(c, vertex_index);                                      // (waits for the stream when it reads the bounding box: the copy above is done by then)
     if (rcf) return rcf;
@@ -2963,22 +2940,22 @@ int scan_counts(oa_ctx *c, const int *d_counts, int n, long long *d_off, DevTmp<
 // 64-ary bounding-box tree over the Morton-sorted vertices (tri = false) or triangles (tri = true), oa_bvh.hpp
 int build_bvh(oa_ctx *c, bool tri)
 {
-    bool &ok = tri ? c->tbvh_ok : c->bvh_ok;
-    float4 *&d_box = tri ? c->d_tbvh_box : c->d_bvh_box;
-    float4 *&d_prims = tri ? c->d_tbvh_prims : c->d_bvh_prims;
-    oa::BvhParams &bp = tri ? c->tbvh : c->bvh;
+    bool &ok = tri ? c->tgt.tbvh_ok : c->tgt.bvh_ok;
+    DevBuf<float4> &d_box = tri ? c->tgt.d_tbvh_box : c->tgt.d_bvh_box;
+    DevBuf<float4> &d_prims = tri ? c->tgt.d_tbvh_prims : c->tgt.d_bvh_prims;
+    oa::BvhParams &bp = tri ? c->tgt.tbvh : c->tgt.bvh;
     ok = false;
-    dev_free(d_box); dev_free(d_prims);
-    const int n = tri ? c->n_tris : c->nt;
-    if (!c->filter_ok || c->grid_mode == 0 || n < 1) return OA_OK;
-    return build_bvh_arrays(c, tri, c->d_tgt_xyz, 3, n, c->bb_lo, c->bb_hi, bp, d_box, d_prims, ok);
+    d_box.reset(); d_prims.reset();
+    const int n = tri ? c->tgt.n_tris : c->tgt.nt;
+    if (!c->tgt.filter_ok || c->grid_mode == 0 || n < 1) return OA_OK;
+    return build_bvh_arrays(c, tri, c->tgt.d_tgt_xyz, 3, n, c->bb_lo, c->bb_hi, bp, d_box, d_prims, ok);
 }
 
 // the tree itself over n primitives: level sizes, Morton order inside the frame [lo, hi], primitive images, boxes.  ok stays
 // false (and nothing is allocated) when the tree would need more than BVH_MAX_LEVELS levels.  Vertices: rows of `stride` floats
-// at d_xyz (the target: 3; the packed source rows: 4); triangles: c->d_tri9.
+// at d_xyz (the target: 3; the packed source rows: 4); triangles: c->tgt.d_tri9.
 int build_bvh_arrays(oa_ctx *c, bool tri, const float *d_xyz, int stride, int n, const double frame_lo[3], const double frame_hi[3],
-                     oa::BvhParams &bp, float4 *&d_box, float4 *&d_prims, bool &ok)
+                     oa::BvhParams &bp, DevBuf<float4> &d_box, DevBuf<float4> &d_prims, bool &ok)
 {
     bp = oa::BvhParams{};
     bp.n_prims = n;
@@ -3008,7 +2985,7 @@ int build_bvh_arrays(oa_ctx *c, bool tri, const float *d_xyz, int stride, int n,
     DevTmp<int> v_in, v_out;
     HIPCHK(k_in.alloc((size_t)n)); HIPCHK(v_in.alloc((size_t)n)); HIPCHK(v_out.alloc((size_t)n));
     const dim3 blk(256), grd((unsigned)((n + 255) / 256));
-    if (tri) hipLaunchKernelGGL(oa::k_bvh_keys<true>, grd, blk, 0, c->stream, d_xyz, stride, (const float4 *)c->d_tri9,
+    if (tri) hipLaunchKernelGGL(oa::k_bvh_keys<true>, grd, blk, 0, c->stream, d_xyz, stride, (const float4 *)c->tgt.d_tri9,
                                 n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
     else hipLaunchKernelGGL(oa::k_bvh_keys<false>, grd, blk, 0, c->stream, d_xyz, stride, (const float4 *)nullptr,
                             n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
@@ -3017,7 +2994,7 @@ int build_bvh_arrays(oa_ctx *c, bool tri, const float *d_xyz, int stride, int n,
     HIPCHK(dev_malloc(&d_prims, sizeof(float4) * (tri ? 3 : 1) * (size_t)n_pad));
     HIPCHK(dev_malloc(&d_box, sizeof(float4) * 2 * (size_t)total));
     const dim3 grd_pad((unsigned)((n_pad + 255) / 256));
-    if (tri) hipLaunchKernelGGL(oa::k_bvh_gather<true>, grd_pad, blk, 0, c->stream, d_xyz, stride, (const float4 *)c->d_tri9,
+    if (tri) hipLaunchKernelGGL(oa::k_bvh_gather<true>, grd_pad, blk, 0, c->stream, d_xyz, stride, (const float4 *)c->tgt.d_tri9,
                                 (const int *)v_out.p, n, n_pad, d_prims);
     else hipLaunchKernelGGL(oa::k_bvh_gather<false>, grd_pad, blk, 0, c->stream, d_xyz, stride, (const float4 *)nullptr,
                             (const int *)v_out.p, n, n_pad, d_prims);
@@ -3106,30 +3083,29 @@ int sort_source_slots(oa_ctx *c, const float *d_xyz, long long n_verts)
     if (rcf || !ok) return rcf;
     DevTmp<unsigned> k_in;
     DevTmp<int> v_in;
-    HIPCHK(k_in.alloc((size_t)c->ns)); HIPCHK(v_in.alloc((size_t)c->ns));
-    HIPCHK(dev_malloc(&c->d_perm, sizeof(int) * (size_t)c->ns));
-    hipLaunchKernelGGL(oa::k_morton_keys, dim3((c->ns + 255) / 256), dim3(256), 0, c->stream, (const float4 *)c->d_src4, c->ns,
+    HIPCHK(k_in.alloc((size_t)c->src.ns)); HIPCHK(v_in.alloc((size_t)c->src.ns));
+    HIPCHK(dev_malloc(&c->src.d_perm, sizeof(int) * (size_t)c->src.ns));
+    hipLaunchKernelGGL(oa::k_morton_keys, dim3((c->src.ns + 255) / 256), dim3(256), 0, c->stream, (const float4 *)c->src.d_src4, c->src.ns,
                        lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
     HIPCHK(hipGetLastError());
-    { const int rcs = sort_order_bits(c, k_in.p, c->d_perm, (size_t)c->ns, 30); if (rcs) return rcs; }
+    { const int rcs = sort_order_bits(c, k_in.p, c->src.d_perm, (size_t)c->src.ns, 30); if (rcs) return rcs; }
     // d_src4 / d_sel become the sorted images: the packed buffers change names (they ARE the caller-order copy now) and
     // k_apply_perm fills new ones -- every slot up to ns_pad -- instead of two device-to-device copies in front of it
     // (both new buffers first, the context's pointers only when both exist: a failed allocation leaves the unsorted source in
     //  place -- d_perm without sorted images would send later launches through null pointers)
-    float4 *src_sorted = nullptr;
-    int *sel_sorted = nullptr;
+    DevTmp<float4> src_sorted;
+    DevTmp<int> sel_sorted;
     {
-        const hipError_t e1 = dev_malloc(&src_sorted, sizeof(float4) * (size_t)c->ns_pad);
-        const hipError_t e2 = e1 == hipSuccess ? dev_malloc(&sel_sorted, sizeof(int) * (size_t)c->ns_pad) : e1;
-        if (e2 != hipSuccess) { dev_free(src_sorted); dev_free(sel_sorted); dev_free(c->d_perm); return fail(OA_E_HIP, "sort_source_slots: %s", hipGetErrorString(e2)); }
+        const hipError_t e1 = dev_malloc(&src_sorted, sizeof(float4) * (size_t)c->src.ns_pad);
+        const hipError_t e2 = e1 == hipSuccess ? dev_malloc(&sel_sorted, sizeof(int) * (size_t)c->src.ns_pad) : e1;
+        if (e2 != hipSuccess) { c->src.d_perm.reset(); return fail(OA_E_HIP, "sort_source_slots: %s", hipGetErrorString(e2)); }
     }
-    dev_free(c->d_src4o);
-    c->d_src4o = c->d_src4; c->d_src4 = src_sorted;
-    int *selo = c->d_sel; c->d_sel = sel_sorted;
-    hipLaunchKernelGGL(oa::k_apply_perm, dim3((c->ns_pad + 255) / 256), dim3(256), 0, c->stream, (const float4 *)c->d_src4o,
-                       (const int *)selo, (const int *)c->d_perm, c->ns, c->ns_pad, c->d_src4, c->d_sel);
+    c->src.d_src4o = std::move(c->src.d_src4); c->src.d_src4 = std::move(src_sorted);
+    DevTmp<int> selo = std::move(c->src.d_sel); c->src.d_sel = std::move(sel_sorted);
+    hipLaunchKernelGGL(oa::k_apply_perm, dim3((c->src.ns_pad + 255) / 256), dim3(256), 0, c->stream, (const float4 *)c->src.d_src4o,
+                       (const int *)selo.p, (const int *)c->src.d_perm, c->src.ns, c->src.ns_pad, c->src.d_src4, c->src.d_sel);
     const hipError_t el = hipGetLastError();
-    dev_free(selo);                                                // (stream ordered: behind the launch above; freed on every path)
+    selo.reset();                                                // (stream ordered: behind the launch above; freed on every path)
     if (el != hipSuccess) return fail(OA_E_HIP, "k_apply_perm: %s", hipGetErrorString(el));
     HIPCHK(hipStreamSynchronize(c->stream));
     return OA_OK;
@@ -3140,13 +3116,13 @@ int sort_source_slots(oa_ctx *c, const float *d_xyz, long long n_verts)
 // it back together with its index check: one host round trip instead of two)
 int build_tri_grid(oa_ctx *c, const double *diag_sum_known)
 {
-    c->tri_grid_ok = false;
-    c->tri_ring_ok = false; c->tri_iters = 0;
-    c->tri_fine_ok = false;
-    dev_free(c->d_tcell_start); dev_free(c->d_tcell_rec); dev_free(c->d_tri_ring);
-    dev_free(c->d_tfine_table); dev_free(c->d_tfine_rec);
-    if (!c->filter_ok || c->grid_mode == 0 || c->n_tris < 64) return OA_OK;
-    if ((long long)c->n_tris > (long long)oa::TRI_REC_INDEX_MASK || (long long)c->n_tris > (long long)oa::TRI_POOL_MAX_TRIS) return OA_OK;     // (28-bit indices in the records, 26 in the pool entries: the tree takes such meshes)
+    c->tgt.tri_grid_ok = false;
+    c->tgt.tri_ring_ok = false; c->tgt.tri_iters = 0;
+    c->tgt.tri_fine_ok = false;
+    c->tgt.d_tcell_start.reset(); c->tgt.d_tcell_rec.reset(); c->tgt.d_tri_ring.reset();
+    c->tgt.d_tfine_table.reset(); c->tgt.d_tfine_rec.reset();
+    if (!c->tgt.filter_ok || c->grid_mode == 0 || c->tgt.n_tris < 64) return OA_OK;
+    if ((long long)c->tgt.n_tris > (long long)oa::TRI_REC_INDEX_MASK || (long long)c->tgt.n_tris > (long long)oa::TRI_POOL_MAX_TRIS) return OA_OK;     // (28-bit indices in the records, 26 in the pool entries: the tree takes such meshes)
     double diag_sum = 0.0;
     if (diag_sum_known) diag_sum = *diag_sum_known;
     else {
@@ -3154,7 +3130,7 @@ int build_tri_grid(oa_ctx *c, const double *diag_sum_known)
         DevTmp<double> d_sum;
         HIPCHK(d_sum.alloc(SLOT_WORDS));
         HIPCHK(hipMemsetAsync(d_sum, 0, sizeof(double) * SLOT_WORDS, c->stream));
-        hipLaunchKernelGGL(oa::k_tri_diag_sum, dim3((c->n_tris + 255) / 256), dim3(256), 0, c->stream, c->d_tri9, c->n_tris, d_sum.p);
+        hipLaunchKernelGGL(oa::k_tri_diag_sum, dim3((c->tgt.n_tris + 255) / 256), dim3(256), 0, c->stream, c->tgt.d_tri9, c->tgt.n_tris, d_sum.p);
         HIPCHK(hipGetLastError());
         double slots[SLOT_WORDS];
         { int rcr = read_small(c, slots, d_sum, sizeof(slots)); if (rcr) return rcr; }
@@ -3166,8 +3142,8 @@ int build_tri_grid(oa_ctx *c, const double *diag_sum_known)
         max_ext = std::max(max_ext, ext[a]);
         scale = std::max(scale, std::max(fabs(c->bb_lo[a]), fabs(c->bb_hi[a])));
     }
-    c->tri_mean_diag = diag_sum / (double)c->n_tris;
-    double h = c->tune.tri_cell * diag_sum / (double)c->n_tris;            // mean triangle bbox diagonals per cell edge (1.5 until the scan
+    c->tgt.tri_mean_diag = diag_sum / (double)c->tgt.n_tris;
+    double h = c->tune.tri_cell * diag_sum / (double)c->tgt.n_tris;            // mean triangle bbox diagonals per cell edge (1.5 until the scan
                                                                                  // became VALU-bound at the end of round 3: fewer records per cell now pay)
     if (!(h > 0.0) || !(h < INFINITY)) h = max_ext > 0.0 ? max_ext / 64.0 : 1.0;
     h = std::max(h, max_ext / 1023.0);
@@ -3207,8 +3183,8 @@ int build_tri_grid(oa_ctx *c, const double *diag_sum_known)
         HIPCHK(d_counts.alloc(total_at + 2 * SLOT_WORDS));
         unsigned long long *d_total = (unsigned long long *)(d_counts.p + total_at);
         HIPCHK(hipMemsetAsync(d_counts, 0, sizeof(int) * (total_at + 2 * SLOT_WORDS), c->stream));
-        hipLaunchKernelGGL(oa::k_tri_grid_bin<false>, dim3((c->n_tris + 255) / 256), dim3(256), 0, c->stream, c->d_tri9,
-                           c->n_tris, gp, d_counts.p, (const int *)nullptr, (float4 *)nullptr, d_total);
+        hipLaunchKernelGGL(oa::k_tri_grid_bin<false>, dim3((c->tgt.n_tris + 255) / 256), dim3(256), 0, c->stream, c->tgt.d_tri9,
+                           c->tgt.n_tris, gp, d_counts.p, (const int *)nullptr, (float4 *)nullptr, d_total);
         HIPCHK(hipGetLastError());
         {
             unsigned long long slots[SLOT_WORDS];
@@ -3218,32 +3194,32 @@ int build_tri_grid(oa_ctx *c, const double *diag_sum_known)
             for (int k = 0; k < oa::TOTAL_SLOTS; ++k) entries += slots[(size_t)k * oa::TOTAL_STRIDE];
         }
         // triangles much larger than a cell explode the lists: coarsen
-        if (entries > 32ull * (unsigned long long)c->n_tris + (1ull << 20) || entries > (unsigned long long)oa::TRI_REC_MAX_ENTRIES) { h *= 2.0; n_cells = 0; continue; }
+        if (entries > 32ull * (unsigned long long)c->tgt.n_tris + (1ull << 20) || entries > (unsigned long long)oa::TRI_REC_MAX_ENTRIES) { h *= 2.0; n_cells = 0; continue; }
         break;
     }
     if (n_cells <= 0 || entries == 0) return OA_OK;
     HIPCHK(d_off.alloc((size_t)n_cells + 1));
-    HIPCHK(dev_malloc(&c->d_tcell_start, sizeof(int) * (size_t)(n_cells + 1)));
-    HIPCHK(dev_malloc(&c->d_tcell_rec, sizeof(float4) * 2 * ((size_t)entries + oa::TRI_REC_PAD)));
-    HIPCHK(hipMemsetAsync(c->d_tcell_rec + 2 * (size_t)entries, 0, sizeof(float4) * 2 * oa::TRI_REC_PAD, c->stream));   // triangle 0, see tri_scan_shared
+    HIPCHK(dev_malloc(&c->tgt.d_tcell_start, sizeof(int) * (size_t)(n_cells + 1)));
+    HIPCHK(dev_malloc(&c->tgt.d_tcell_rec, sizeof(float4) * 2 * ((size_t)entries + oa::TRI_REC_PAD)));
+    HIPCHK(hipMemsetAsync(c->tgt.d_tcell_rec + 2 * (size_t)entries, 0, sizeof(float4) * 2 * oa::TRI_REC_PAD, c->stream));   // triangle 0, see tri_scan_shared
     DevTmp<char> scan_tmp;                                           // released on return, behind the wait below
     { int rcs = scan_counts(c, d_counts.p, n_cells, d_off.p, scan_tmp); if (rcs) return rcs; }
-    hipLaunchKernelGGL(oa::k_grid_starts, dim3((n_cells + 256) / 256), dim3(256), 0, c->stream, d_off.p, n_cells, c->d_tcell_start, d_counts.p);
-    hipLaunchKernelGGL(oa::k_tri_grid_bin<true>, dim3((c->n_tris + 255) / 256), dim3(256), 0, c->stream, c->d_tri9, c->n_tris,
-                       gp, d_counts.p, (const int *)c->d_tcell_start, c->d_tcell_rec, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL(oa::k_grid_starts, dim3((n_cells + 256) / 256), dim3(256), 0, c->stream, d_off.p, n_cells, c->tgt.d_tcell_start, d_counts.p);
+    hipLaunchKernelGGL(oa::k_tri_grid_bin<true>, dim3((c->tgt.n_tris + 255) / 256), dim3(256), 0, c->stream, c->tgt.d_tri9, c->tgt.n_tris,
+                       gp, d_counts.p, (const int *)c->tgt.d_tcell_start, c->tgt.d_tcell_rec, (unsigned long long *)nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
-    c->tgp = gp;
-    c->n_tri_entries = (long long)entries;
-    c->tri_grid_ok = true;
+    c->tgt.tgp = gp;
+    c->tgt.n_tri_entries = (long long)entries;
+    c->tgt.tri_grid_ok = true;
     if (c->tune.debug)
         fprintf(stderr, "[oa] tri grid: h=%g cells=%dx%dx%d entries=%llu (%.2f per triangle)\n", gp.h, gp.n[0], gp.n[1], gp.n[2],
-                entries, (double)entries / c->n_tris);
+                entries, (double)entries / c->tgt.n_tris);
     if (c->tune.tri_ring) {
-        HIPCHK(dev_malloc(&c->d_tri_ring, sizeof(int) * (size_t)oa::TRI_RING_STRIDE * (size_t)c->n_tris));
+        HIPCHK(dev_malloc(&c->tgt.d_tri_ring, sizeof(int) * (size_t)oa::TRI_RING_STRIDE * (size_t)c->tgt.n_tris));
         if (c->tune.tri_ring == 2) { const int rcr = build_tri_ring(c); if (rcr) return rcr; }
     }
-    if (c->tune.tri_fine == 2 || (c->tune.tri_fine == 1 && c->n_tris >= c->tune.tri_fine_min_tris)) return build_tri_fine(c);
+    if (c->tune.tri_fine == 2 || (c->tune.tri_fine == 1 && c->tgt.n_tris >= c->tune.tri_fine_min_tris)) return build_tri_fine(c);
     return OA_OK;
 }
 
@@ -3252,14 +3228,14 @@ int build_tri_grid(oa_ctx *c, const double *diag_sum_known)
 // (triangles much larger than a cell after six coarsenings) or take more than OA_TRI_FINE_MAX_MB.
 int build_tri_fine(oa_ctx *c)
 {
-    c->tri_fine_ok = false;
-    dev_free(c->d_tfine_table); dev_free(c->d_tfine_rec);
+    c->tgt.tri_fine_ok = false;
+    c->tgt.d_tfine_table.reset(); c->tgt.d_tfine_rec.reset();
 #if !defined(OA_EXPERIMENTS)
     return OA_OK;                                                   // (OA_TRI_FINE is inert in the default library)
 #else
-    if (!c->tri_grid_ok || !c->tbvh_ok || !(c->tri_mean_diag > 0.0) || !(c->tri_mean_diag < INFINITY)) return OA_OK;
+    if (!c->tgt.tri_grid_ok || !c->tgt.tbvh_ok || !(c->tgt.tri_mean_diag > 0.0) || !(c->tgt.tri_mean_diag < INFINITY)) return OA_OK;
     oa::FineParams fp{};
-    double h = c->tune.tri_fine_cell * c->tri_mean_diag;
+    double h = c->tune.tri_fine_cell * c->tgt.tri_mean_diag;
     const double rho_frac = c->tune.tri_fine_rho;
     double ext[3], scale = 0.0, max_ext = 0.0;
     for (int a = 0; a < 3; ++a) {
@@ -3288,14 +3264,14 @@ int build_tri_fine(oa_ctx *c)
         fp.scale = scale;
         fp.slack = 1e-10 * scale + 1e-300;
         HIPCHK(hipMemsetAsync(d_total, 0, sizeof(unsigned long long) * SLOT_WORDS, c->stream));
-        hipLaunchKernelGGL(oa::k_tfine_total, dim3((unsigned)((c->n_tris + 255) / 256)), dim3(256), 0, c->stream, (const float4 *)c->d_tri9, c->n_tris, fp, d_total.p);
+        hipLaunchKernelGGL(oa::k_tfine_total, dim3((unsigned)((c->tgt.n_tris + 255) / 256)), dim3(256), 0, c->stream, (const float4 *)c->tgt.d_tri9, c->tgt.n_tris, fp, d_total.p);
         HIPCHK(hipGetLastError());
         unsigned long long slots[SLOT_WORDS];
         { int rcr = read_small(c, slots, d_total, sizeof(slots)); if (rcr) return rcr; }
         entries = 0;
         for (int k = 0; k < oa::TOTAL_SLOTS; ++k) entries += slots[(size_t)k * oa::TOTAL_STRIDE];
         if (entries == 0) return OA_OK;
-        if (entries > 40ull * (unsigned long long)c->n_tris + (1ull << 16) || entries > max_entries || entries >= (1ull << 31)) { h *= 1.5; continue; }
+        if (entries > 40ull * (unsigned long long)c->tgt.n_tris + (1ull << 16) || entries > max_entries || entries >= (1ull << 31)) { h *= 1.5; continue; }
         sized = true;
     }
     if (!sized) return OA_OK;
@@ -3313,33 +3289,33 @@ int build_tri_fine(oa_ctx *c)
         DevTmp<int> d_counts;                                        // [n_slots] counts, then the overflow flag
         DevTmp<long long> d_off;
         DevTmp<char> scan_tmp;
-        HIPCHK(dev_malloc(&c->d_tfine_table, sizeof(uint4) * n_slots));
-        HIPCHK(dev_malloc(&c->d_tfine_rec, sizeof(float4) * 3 * (size_t)entries));
+        HIPCHK(dev_malloc(&c->tgt.d_tfine_table, sizeof(uint4) * n_slots));
+        HIPCHK(dev_malloc(&c->tgt.d_tfine_rec, sizeof(float4) * 3 * (size_t)entries));
         HIPCHK(d_counts.alloc(n_slots + 2));
         HIPCHK(d_off.alloc(n_slots + 1));
-        HIPCHK(hipMemsetAsync(c->d_tfine_table, 0xFF, sizeof(uint4) * n_slots, c->stream));
+        HIPCHK(hipMemsetAsync(c->tgt.d_tfine_table, 0xFF, sizeof(uint4) * n_slots, c->stream));
         HIPCHK(hipMemsetAsync(d_counts, 0, sizeof(int) * (n_slots + 2), c->stream));
-        const dim3 tb((unsigned)((c->n_tris + 255) / 256));
-        hipLaunchKernelGGL(oa::k_tfine_count, tb, dim3(256), 0, c->stream, (const float4 *)c->d_tri9, c->n_tris, fp, c->d_tfine_table, d_counts.p, d_counts.p + n_slots + 1);
+        const dim3 tb((unsigned)((c->tgt.n_tris + 255) / 256));
+        hipLaunchKernelGGL(oa::k_tfine_count, tb, dim3(256), 0, c->stream, (const float4 *)c->tgt.d_tri9, c->tgt.n_tris, fp, c->tgt.d_tfine_table, d_counts.p, d_counts.p + n_slots + 1);
         HIPCHK(hipGetLastError());
         { int rcs = scan_counts(c, d_counts.p, (int)n_slots, d_off.p, scan_tmp); if (rcs) return rcs; }
-        hipLaunchKernelGGL(oa::k_tfine_fill, tb, dim3(256), 0, c->stream, (const float4 *)c->d_tri9, c->n_tris, fp, c->d_tfine_table, d_counts.p,
-                           (const long long *)d_off.p, c->d_tfine_rec);
-        hipLaunchKernelGGL(oa::k_tfine_finish, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, c->stream, c->d_tfine_table, (int)n_slots,
+        hipLaunchKernelGGL(oa::k_tfine_fill, tb, dim3(256), 0, c->stream, (const float4 *)c->tgt.d_tri9, c->tgt.n_tris, fp, c->tgt.d_tfine_table, d_counts.p,
+                           (const long long *)d_off.p, c->tgt.d_tfine_rec);
+        hipLaunchKernelGGL(oa::k_tfine_finish, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, c->stream, c->tgt.d_tfine_table, (int)n_slots,
                            (const long long *)d_off.p);
         HIPCHK(hipGetLastError());
         int overflow = 0;
         { int rcr = read_small(c, &overflow, d_counts.p + n_slots + 1, sizeof(int)); if (rcr) return rcr; }   // (waits for the stream: the temporaries may go)
         if (!overflow) {
-            c->tfp = fp;
-            c->n_fine_entries = (long long)entries;
-            c->tri_fine_ok = true;
+            c->tgt.tfp = fp;
+            c->tgt.n_fine_entries = (long long)entries;
+            c->tgt.tri_fine_ok = true;
             if (c->tune.debug)
                 fprintf(stderr, "[oa] tri fine grid: h=%g (%.2f mean diagonals) rho=%g cells=%dx%dx%d entries=%llu (%.2f per triangle, %.0f MB) table 2^%d slots\n",
-                        fp.h, fp.h / c->tri_mean_diag, fp.rho, fp.n[0], fp.n[1], fp.n[2], entries, (double)entries / c->n_tris, entries * 48.0 / 1048576.0, log2);
+                        fp.h, fp.h / c->tgt.tri_mean_diag, fp.rho, fp.n[0], fp.n[1], fp.n[2], entries, (double)entries / c->tgt.n_tris, entries * 48.0 / 1048576.0, log2);
             return OA_OK;
         }
-        dev_free(c->d_tfine_table); dev_free(c->d_tfine_rec);
+        c->tgt.d_tfine_table.reset(); c->tgt.d_tfine_rec.reset();
     }
     return OA_OK;
 #endif
@@ -3353,15 +3329,15 @@ int build_tri_ring(oa_ctx *c)
     (void)c;
     return OA_OK;                                                   // (OA_TRI_RING is inert in the default library)
 #else
-    if (!c->tri_grid_ok || !c->d_tri_ring || c->tri_ring_ok) return OA_OK;
-    const double cap = std::max(0.01, std::min(c->tune.tri_ring_cap, 1.0)) * c->tgp.h;
-    const dim3 blocks((unsigned)((c->n_tris + 255) / 256));
+    if (!c->tgt.tri_grid_ok || !c->tgt.d_tri_ring || c->tgt.tri_ring_ok) return OA_OK;
+    const double cap = std::max(0.01, std::min(c->tune.tri_ring_cap, 1.0)) * c->tgt.tgp.h;
+    const dim3 blocks((unsigned)((c->tgt.n_tris + 255) / 256));
     if (c->tune.grid_stats || c->tune.debug) {
         DevTmp<unsigned long long> d_stats;
         HIPCHK(d_stats.alloc(oa::RING_STAT_N));
         HIPCHK(hipMemsetAsync(d_stats, 0, sizeof(unsigned long long) * oa::RING_STAT_N, c->stream));
-        hipLaunchKernelGGL(oa::k_tri_ring_build<true>, blocks, dim3(256), 0, c->stream, c->d_tri9, c->n_tris, c->tgp, (const int *)c->d_tcell_start,
-                           (const float4 *)c->d_tcell_rec, cap, c->d_tri_ring, d_stats.p);
+        hipLaunchKernelGGL(oa::k_tri_ring_build<true>, blocks, dim3(256), 0, c->stream, c->tgt.d_tri9, c->tgt.n_tris, c->tgt.tgp, (const int *)c->tgt.d_tcell_start,
+                           (const float4 *)c->tgt.d_tcell_rec, cap, c->tgt.d_tri_ring, d_stats.p);
         HIPCHK(hipGetLastError());
         unsigned long long h[oa::RING_STAT_N];
         { int rcr = read_small(c, h, d_stats, sizeof(h)); if (rcr) return rcr; }
@@ -3370,11 +3346,11 @@ int build_tri_ring(oa_ctx *c)
                 h[oa::RING_STAT_TRIS], 100.0 * h[oa::RING_STAT_NEVER] / nt, 100.0 * h[oa::RING_STAT_CAPPED] / nt, cap, h[oa::RING_STAT_RECORDS] / nt,
                 h[oa::RING_STAT_TESTS] / nt, h[oa::RING_STAT_NEIGHBOURS] / nt);
     } else {
-        hipLaunchKernelGGL(oa::k_tri_ring_build<false>, blocks, dim3(256), 0, c->stream, c->d_tri9, c->n_tris, c->tgp, (const int *)c->d_tcell_start,
-                           (const float4 *)c->d_tcell_rec, cap, c->d_tri_ring, (unsigned long long *)nullptr);
+        hipLaunchKernelGGL(oa::k_tri_ring_build<false>, blocks, dim3(256), 0, c->stream, c->tgt.d_tri9, c->tgt.n_tris, c->tgt.tgp, (const int *)c->tgt.d_tcell_start,
+                           (const float4 *)c->tgt.d_tcell_rec, cap, c->tgt.d_tri_ring, (unsigned long long *)nullptr);
         HIPCHK(hipGetLastError());
     }
-    c->tri_ring_ok = true;
+    c->tgt.tri_ring_ok = true;
     return OA_OK;
 #endif
 }
@@ -3384,18 +3360,18 @@ int build_tri_ring(oa_ctx *c)
 // does not settle (reach beyond the lists' inflation, crowded cells, no seed) is the list the grid search works through
 int launch_tri_settle(oa_ctx *c, int &qcap)
 {
-    const dim3 sblocks((unsigned)(((long long)c->ns * 4 + 255) / 256));     // four lanes per query
+    const dim3 sblocks((unsigned)(((long long)c->src.ns * 4 + 255) / 256));     // four lanes per query
     qcap = oa::ulist_cap((int)sblocks.x * 4, 16);                   // 16 queries per wave
     auto launch = [&](auto STATS, unsigned long long *stats) {
-        hipLaunchKernelGGL((oa::k_tri_settle<decltype(STATS)::value>), sblocks, dim3(256), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4, c->ns, c->tfp,
-                           (const uint4 *)c->d_tfine_table, (const float4 *)c->d_tfine_rec, (const float4 *)c->d_tri9, (const int *)c->d_prev, c->d_keys, c->d_ulist, qcap,
-                           ucount_set(c, c->u_slot), ucount_set(c, c->u_slot ^ 1), stats);
+        hipLaunchKernelGGL((oa::k_tri_settle<decltype(STATS)::value>), sblocks, dim3(256), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->src.d_src4, c->src.ns, c->tgt.tfp,
+                           (const uint4 *)c->tgt.d_tfine_table, (const float4 *)c->tgt.d_tfine_rec, (const float4 *)c->tgt.d_tri9, (const int *)c->src.d_prev, c->src.d_keys, c->src.d_ulist, qcap,
+                           ucount_set(c, c->src.u_slot), ucount_set(c, c->src.u_slot ^ 1), stats);
     };
     if (c->tune.grid_stats) {                                            // OA_GRID_STATS=1: instrumented launch, totals to stderr (one row of 8 for the launch)
         unsigned long long h[8];
         { const int rcs = wave_stats(c, 8, 1, h, [&](unsigned long long *stats) { launch(yes, stats); }); if (rcs) return rcs; }
         fprintf(stderr, "[oa] tri settle: %llu of %d queries settled (%.2f records each); the others: %llu no seed, %llu reach beyond rho, %llu outside the box, "
-                        "%llu cell not listed / over the cap\n", h[0], c->ns, (double)h[5] / (double)std::max(1ull, h[0]), h[1], h[2], h[3], h[4]);
+                        "%llu cell not listed / over the cap\n", h[0], c->src.ns, (double)h[5] / (double)std::max(1ull, h[0]), h[1], h[2], h[3], h[4]);
     } else launch(no, nullptr);
     HIPCHK(hipGetLastError());
     return OA_OK;
@@ -3405,10 +3381,10 @@ int launch_tri_settle(oa_ctx *c, int &qcap)
 // works through the list (oa_tri.hpp)
 int launch_tri_accept(oa_ctx *c, const int *ring, int &qcap)
 {
-    qcap = oa::ulist_cap((c->ns + 63) / 64, 64);
-    hipLaunchKernelGGL(oa::k_tri_accept, dim3((unsigned)((c->ns + 255) / 256)), dim3(256), 0, c->stream, (const oa::DevState *)c->d_state,
-                       (const float4 *)c->d_src4, c->ns, (float)c->tgp.scale * 1.000001f, (const float4 *)c->d_tri9, (const int *)c->d_prev, ring,
-                       c->d_keys, c->d_ulist, qcap, ucount_set(c, c->u_slot), ucount_set(c, c->u_slot ^ 1));
+    qcap = oa::ulist_cap((c->src.ns + 63) / 64, 64);
+    hipLaunchKernelGGL(oa::k_tri_accept, dim3((unsigned)((c->src.ns + 255) / 256)), dim3(256), 0, c->stream, (const oa::DevState *)c->d_state,
+                       (const float4 *)c->src.d_src4, c->src.ns, (float)c->tgt.tgp.scale * 1.000001f, (const float4 *)c->tgt.d_tri9, (const int *)c->src.d_prev, ring,
+                       c->src.d_keys, c->src.d_ulist, qcap, ucount_set(c, c->src.u_slot), ucount_set(c, c->src.u_slot ^ 1));
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -3438,20 +3414,20 @@ int tri_grid_stats(oa_ctx *c, unsigned blocks, Launch &&launch)
 // The triangle grid search; the far queries it hands over go through the triangle tree (a list launch behind it, or -- acc -- the wave that owns them)
 int launch_tri_grid(oa_ctx *c, const SearchChoice &s, bool acc)
 {
-    if (!acc && !c->loop_active) { HIPCHK(hipMemsetAsync(c->d_todo_count, 0, TODO_COUNT_INTS * sizeof(int), c->stream)); c->u_slot = 0; }
+    if (!acc && !c->loop_active) { HIPCHK(hipMemsetAsync(c->src.d_todo_count, 0, TODO_COUNT_INTS * sizeof(int), c->stream)); c->src.u_slot = 0; }
     if (c->loop_active) { const int rcr = tri_ring_lazy(c, true); if (rcr) return rcr; }
-    const int *ring = c->tri_ring_ok ? c->d_tri_ring : nullptr;
+    const int *ring = c->tgt.tri_ring_ok ? c->tgt.d_tri_ring : nullptr;
     // a front search (SearchChoice) leaves the list of the queries it did not settle: never for the accumulating form
-    bool listed = s.accept_front && ring && !acc && c->d_ulist;
+    bool listed = s.accept_front && ring && !acc && c->src.d_ulist;
     const int *qlist = nullptr, *qcount = nullptr;
     int qcap = 0;
 #if defined(OA_EXPERIMENTS)
-    const bool settle = s.settle_front && !acc && c->d_ulist;
+    const bool settle = s.settle_front && !acc && c->src.d_ulist;
     if (settle || listed) {
         const int rcf = settle ? launch_tri_settle(c, qcap) : launch_tri_accept(c, ring, qcap);
         if (rcf) return rcf;
-        qlist = c->d_ulist; qcount = ucount_set(c, c->u_slot);
-        c->u_slot ^= 1;
+        qlist = c->src.d_ulist; qcount = ucount_set(c, c->src.u_slot);
+        c->src.u_slot ^= 1;
         ring = nullptr;                                             // (the list's queries failed that test already)
         listed = true;
     }
@@ -3462,11 +3438,11 @@ int launch_tri_grid(oa_ctx *c, const SearchChoice &s, bool acc)
     auto launch = [&](auto L, auto STATS, auto SHARE, auto ACC, auto BT, unsigned blocks, unsigned long long *stats, const int *kring, int qmin = 0, int qmax = 0x7FFFFFFF) {
         constexpr bool A = decltype(ACC)::value;
         hipLaunchKernelGGL((oa::k_tri_search_grid<decltype(L)::value, decltype(STATS)::value, decltype(SHARE)::value, A, decltype(BT)::value>), dim3(blocks), dim3(decltype(BT)::value), 0, c->stream,
-                           c->d_state, c->d_src4, c->ns, c->tgp, c->d_tcell_start, c->d_tcell_rec, c->d_tri9, c->d_prev, c->d_keys, c->d_todo_list, c->d_todo_count, s.dual ? 0 : -1, stats,
-                           A ? c->tbvh : oa::BvhParams{}, A ? (const float4 *)c->d_tbvh_box : nullptr, A ? (const float4 *)c->d_tbvh_prims : nullptr,
+                           c->d_state, c->src.d_src4, c->src.ns, c->tgt.tgp, c->tgt.d_tcell_start, c->tgt.d_tcell_rec, c->tgt.d_tri9, c->src.d_prev, c->src.d_keys, c->src.d_todo_list, c->src.d_todo_count, s.dual ? 0 : -1, stats,
+                           A ? c->tgt.tbvh : oa::BvhParams{}, A ? (const float4 *)c->tgt.d_tbvh_box : nullptr, A ? (const float4 *)c->tgt.d_tbvh_prims : nullptr,
                            A ? normal_test(c) : oa::NormalTest{}, A ? c->d_partials : nullptr, kring, qlist, qcount, qmin, qmax, qcap);
     };
-    const unsigned gblocks = (unsigned)(((long long)c->ns * lanes + 255) / 256);
+    const unsigned gblocks = (unsigned)(((long long)c->src.ns * lanes + 255) / 256);
     if (acc) {
         // the search finishes its own leftovers through the triangle tree and takes the pair test and the sums in its
         // epilogue (PLAN_GRID, fast path): no list launch, no accumulation launch
@@ -3475,11 +3451,11 @@ int launch_tri_grid(oa_ctx *c, const SearchChoice &s, bool acc)
         return OA_OK;
     }
     // long plain searches: one wave per workgroup (k_tri_search_grid, BT = 64): a slot is free again when ITS wave is through
-    const long long wblocks = ((long long)c->ns * lanes + 63) / 64;
+    const long long wblocks = ((long long)c->src.ns * lanes + 63) / 64;
     if (listed) {
         // the list's length decides the lanes per query, on the device (k_tri_search_grid: qmin / qmax): a 4-lane launch for
         // lists of up to `small` queries, and the shard's own geometry for longer ones
-        const int small = std::min(c->ns, (c->n_tris >= 250000 ? 400 : 128) * c->n_cu);
+        const int small = std::min(c->src.ns, (c->tgt.n_tris >= 250000 ? 400 : 128) * c->n_cu);
         const bool two = lanes != 4 && c->tune.tri_split_lanes;
         if (two) launch(int_c<4>{}, no, yes, no, int_c<256>{}, (unsigned)(((long long)small * 4 + 255) / 256), nullptr, nullptr, 0, small);
         dispatch<1, 2, 4>(lanes, [&](auto L) { launch(L, no, yes, no, int_c<256>{}, gblocks, nullptr, nullptr, two ? small : 0, 0x7FFFFFFF); });
@@ -3500,21 +3476,21 @@ int launch_tri_grid(oa_ctx *c, const SearchChoice &s, bool acc)
     HIPCHK(hipGetLastError());
     if (c->tune.debug && !listed) {                                     // how many queries the grid handed over (debug only: syncs)
         int n_todo = 0;
-        { int rcr = read_small(c, &n_todo, c->d_todo_count, sizeof(int)); if (rcr) return rcr; }
-        fprintf(stderr, "[oa] tri grid handed %d of %d queries to the tree\n", n_todo, c->ns);
+        { int rcr = read_small(c, &n_todo, c->src.d_todo_count, sizeof(int)); if (rcr) return rcr; }
+        fprintf(stderr, "[oa] tri grid handed %d of %d queries to the tree\n", n_todo, c->src.ns);
     }
-    return launch_bvh<true>(c, c->d_todo_list, c->d_todo_count);   // the far queries: tree search
+    return launch_bvh<true>(c, c->src.d_todo_list, c->src.d_todo_count);   // the far queries: tree search
 }
 
 int launch_tri_search(oa_ctx *c, const SearchChoice &s, bool acc)
 {
     if (c->tune.debug)
         fprintf(stderr, "[oa] tri search: grid=%d acc=%d ns=%d n_tris=%d state=%p src4=%p tri9=%p prev=%p keys=%p todo=%p/%p cells=%p/%p\n",
-                (int)(s.kind == SEARCH_GRID), (int)acc, c->ns, c->n_tris, (void *)c->d_state, (void *)c->d_src4, (void *)c->d_tri9, (void *)c->d_prev,
-                (void *)c->d_keys, (void *)c->d_todo_list, (void *)c->d_todo_count, (void *)c->d_tcell_start, (void *)c->d_tcell_rec);
+                (int)(s.kind == SEARCH_GRID), (int)acc, c->src.ns, c->tgt.n_tris, (void *)c->d_state, (void *)c->src.d_src4, (void *)c->tgt.d_tri9, (void *)c->src.d_prev,
+                (void *)c->src.d_keys, (void *)c->src.d_todo_list, (void *)c->src.d_todo_count, (void *)c->tgt.d_tcell_start, (void *)c->tgt.d_tcell_rec);
     if (s.kind == SEARCH_GRID) return launch_tri_grid(c, s, acc);
-    hipLaunchKernelGGL(oa::k_tri_search_all, dim3(std::min((c->ns + 255) / 256, 65535)), dim3(256), 0, c->stream,
-                       c->d_state, c->d_src4, c->ns, c->d_tri9, c->n_tris, c->d_prev, c->d_keys);
+    hipLaunchKernelGGL(oa::k_tri_search_all, dim3(std::min((c->src.ns + 255) / 256, 65535)), dim3(256), 0, c->stream,
+                       c->d_state, c->src.d_src4, c->src.ns, c->tgt.d_tri9, c->tgt.n_tris, c->src.d_prev, c->src.d_keys);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -3531,19 +3507,19 @@ OA_EXPORT int oa_set_target_mesh(oa_ctx *c, const float *xyz, int64_t n_verts, i
     int rc = set_target_common(c, xyz, n_verts, on_device, false);  // vertex images + bbox + filter; no vertex grid / tree
     if (rc) return rc;
     if (n_verts < 1) return fail(OA_E_BAD_ARG, "oa_set_target_mesh: no vertices");
-    int *&d_tris = c->d_tris;                                      // kept: the pseudo-normals are built from the indices (set_target_common freed the old ones)
+    DevBuf<int> &d_tris = c->tgt.d_tris;                                      // kept: the pseudo-normals are built from the indices (set_target_common freed the old ones)
     constexpr size_t SLOT_WORDS = (size_t)oa::TOTAL_SLOTS * oa::TOTAL_STRIDE;
     DevTmp<double> d_chk;                                           // [0]: (as int) corners that index outside the vertices; [1 ...]: the spread sum of the bounding-box diagonals (oa_tri.hpp: TOTAL_SLOTS)
     HIPCHK(dev_malloc(&d_tris, sizeof(int) * 3 * (size_t)n_tris));
     HIPCHK(d_chk.alloc(1 + SLOT_WORDS));
     HIPCHK(hipMemcpyAsync(d_tris, tris, sizeof(int) * 3 * (size_t)n_tris, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemsetAsync(d_chk, 0, (1 + SLOT_WORDS) * sizeof(double), c->stream));
-    HIPCHK(dev_malloc(&c->d_tri9, sizeof(float4) * 3 * (size_t)n_tris));
-    hipLaunchKernelGGL(oa::k_pack_tris, dim3((unsigned)((n_tris + 255) / 256)), dim3(256), 0, c->stream, c->d_tgt_xyz,
-                       (int)n_verts, (const int *)d_tris, (int)n_tris, c->d_tri9, (int *)d_chk.p);
+    HIPCHK(dev_malloc(&c->tgt.d_tri9, sizeof(float4) * 3 * (size_t)n_tris));
+    hipLaunchKernelGGL(oa::k_pack_tris, dim3((unsigned)((n_tris + 255) / 256)), dim3(256), 0, c->stream, c->tgt.d_tgt_xyz,
+                       (int)n_verts, (const int *)d_tris, (int)n_tris, c->tgt.d_tri9, (int *)d_chk.p);
     // the triangle grid's cell size comes from the mean bounding-box diagonal: summed here, so that the index check and the
     // sum come back in ONE host round trip (a bad index leaves a triangle of garbage corners: the sum is not used then)
-    hipLaunchKernelGGL(oa::k_tri_diag_sum, dim3((unsigned)((n_tris + 255) / 256)), dim3(256), 0, c->stream, c->d_tri9, (int)n_tris, d_chk.p + 1);
+    hipLaunchKernelGGL(oa::k_tri_diag_sum, dim3((unsigned)((n_tris + 255) / 256)), dim3(256), 0, c->stream, c->tgt.d_tri9, (int)n_tris, d_chk.p + 1);
     HIPCHK(hipGetLastError());
     double chk[1 + SLOT_WORDS];
     { int rcr = read_small(c, chk, d_chk, sizeof(chk)); if (rcr) return rcr; }
@@ -3551,9 +3527,9 @@ OA_EXPORT int oa_set_target_mesh(oa_ctx *c, const float *xyz, int64_t n_verts, i
     memcpy(&bad, &chk[0], sizeof(int));
     double diag_sum = 0.0;
     for (int k = 0; k < oa::TOTAL_SLOTS; ++k) diag_sum += chk[1 + (size_t)k * oa::TOTAL_STRIDE];
-    if (bad) { dev_free(c->d_tri9); dev_free(c->d_tris); return fail(OA_E_BAD_ARG, "oa_set_target_mesh: %d triangle corners index outside 0..%lld", bad, (long long)n_verts - 1); }
-    c->n_tris = (int)n_tris;
-    c->surface = true;
+    if (bad) { c->tgt.d_tri9.reset(); c->tgt.d_tris.reset(); return fail(OA_E_BAD_ARG, "oa_set_target_mesh: %d triangle corners index outside 0..%lld", bad, (long long)n_verts - 1); }
+    c->tgt.n_tris = (int)n_tris;
+    c->tgt.surface = true;
     if ((rc = build_bvh(c, true))) return rc;
     return build_tri_grid(c, &diag_sum);
 }
@@ -3585,47 +3561,35 @@ int source_reset(oa_ctx *c, long long count, long long begin, long long n_verts)
 {
     HIPCHK(hipStreamSynchronize(c->stream));
     c->loop_active = false;                                         // an open oa_iterate sequence ends with the old source
-    dev_free(c->d_src4); dev_free(c->d_keys); dev_free(c->d_prev); dev_free(c->d_win); dev_free(c->d_wsafe); dev_free(c->d_sel); dev_free(c->d_src_n); dev_free(c->d_w); dev_free(c->d_rkeys);
-    dev_free(c->d_sbvh_box); dev_free(c->d_sbvh_prims); dev_free(c->d_recip_ok); c->sbvh_ok = false;   // (the source tree: a new source forgets it)
-    { const int rcc = recip_clear_count(c); if (rcc) return rcc; }  // ... and the old source's count
+    c->src = {};                                                    // the old shard: its points, seeds, tree, verdicts and scratch
+    { const int rcc = recip_clear_count(c); if (rcc) return rcc; }  // ... and the old source's counts
     { const int rcc = bnd_clear_count(c); if (rcc) return rcc; }
-    trim_free_sized(c);
     { const int rcc = trim_clear(c); if (rcc) return rcc; }         // (oa_set_trim's figures spoke of the old source)
-    dev_free(c->d_src4o); dev_free(c->d_perm); dev_free(c->d_members); dev_free(c->d_pos);
-    c->h_members.clear();
-    c->shard_begin = begin;
+    c->src.shard_begin = begin;
     c->normals_on = false;
-    c->src_n_verts = n_verts;
-    dev_free(c->d_valid); dev_free(c->d_b); dev_free(c->d_dist); dev_free(c->d_counts); dev_free(c->d_offsets);
-    dev_free(c->d_A); dev_free(c->d_B);
-    c->emit_cap = 0;
-    c->ns = (int)count;
+    c->src.src_n_verts = n_verts;
+    c->src.ns = (int)count;
     // points per thread: 4 for big shards; small shards take 2 or 1 so that the launch still has enough workgroups
-    c->R = c->tune.nn_r ? c->tune.nn_r : (count >= 65536 ? 4 : (count >= 16384 ? 2 : 1));
-    const int chunk = oa::NN_THREADS * c->R;
-    c->ns_pad = (int)(((count + chunk - 1) / chunk) * chunk);
-    if (c->ns_pad == 0) c->ns_pad = chunk;
-    HIPCHK(dev_malloc(&c->d_src4, sizeof(float4) * (size_t)c->ns_pad));
-    HIPCHK(dev_malloc(&c->d_keys, sizeof(unsigned long long) * (size_t)c->ns_pad));
-    HIPCHK(dev_malloc(&c->d_prev, sizeof(int) * (size_t)c->ns_pad));
-    HIPCHK(dev_malloc(&c->d_win, sizeof(float4) * (size_t)c->ns_pad));
-    dev_free(c->d_prec); dev_free(c->d_homes); dev_free(c->d_qcnt);
-    c->prec_cap = 0; c->homes_cap = 0;
-    if (c->grid_mode == 0) { const int rcq = ensure_sorted_buffers(c, c->ns_pad / chunk); if (rcq) return rcq; }   // (brute force only, never inside a loop: 64 B per slot + the brute-force launch's q_blocks, a few KB)
-    if (c->tune.grid_safe && !c->surface) HIPCHK(dev_malloc(&c->d_wsafe, sizeof(uint2) * (size_t)c->ns_pad));   // (a vertex target set later allocates it: set_target_common)
+    c->src.R = c->tune.nn_r ? c->tune.nn_r : (count >= 65536 ? 4 : (count >= 16384 ? 2 : 1));
+    const int chunk = oa::NN_THREADS * c->src.R;
+    c->src.ns_pad = (int)(((count + chunk - 1) / chunk) * chunk);
+    if (c->src.ns_pad == 0) c->src.ns_pad = chunk;
+    HIPCHK(dev_malloc(&c->src.d_src4, sizeof(float4) * (size_t)c->src.ns_pad));
+    HIPCHK(dev_malloc(&c->src.d_keys, sizeof(unsigned long long) * (size_t)c->src.ns_pad));
+    HIPCHK(dev_malloc(&c->src.d_prev, sizeof(int) * (size_t)c->src.ns_pad));
+    HIPCHK(dev_malloc(&c->src.d_win, sizeof(float4) * (size_t)c->src.ns_pad));
+    if (c->grid_mode == 0) { const int rcq = ensure_sorted_buffers(c, c->src.ns_pad / chunk); if (rcq) return rcq; }   // (brute force only, never inside a loop: 64 B per slot + the brute-force launch's q_blocks, a few KB)
+    if (c->tune.grid_safe && !c->tgt.surface) HIPCHK(dev_malloc(&c->src.d_wsafe, sizeof(uint2) * (size_t)c->src.ns_pad));   // (a vertex target set later allocates it: set_target_common)
     c->seeded = false; c->win_seeds = false;
-    HIPCHK(dev_malloc(&c->d_sel, sizeof(int) * (size_t)c->ns_pad));
-    dev_free(c->d_todo_list); dev_free(c->d_todo_count); dev_free(c->d_ulist);
-    HIPCHK(dev_malloc(&c->d_todo_list, sizeof(int) * (size_t)c->ns_pad));
-    HIPCHK(dev_malloc(&c->d_ulist, sizeof(int) * ((size_t)c->ns_pad + 64 * (size_t)oa::ULIST_PARTS)));   // (ULIST_PARTS regions, each rounded up to whole waves)
-    HIPCHK(dev_malloc(&c->d_todo_count, TODO_COUNT_INTS * sizeof(int)));      // {entries of the hand-over list, most handed over by one wave, ...}, the two counter sets of d_ulist
-    HIPCHK(hipMemsetAsync(c->d_todo_count, 0, TODO_COUNT_INTS * sizeof(int), c->stream));
-    c->u_slot = 0;
+    HIPCHK(dev_malloc(&c->src.d_sel, sizeof(int) * (size_t)c->src.ns_pad));
+    HIPCHK(dev_malloc(&c->src.d_todo_list, sizeof(int) * (size_t)c->src.ns_pad));
+    HIPCHK(dev_malloc(&c->src.d_ulist, sizeof(int) * ((size_t)c->src.ns_pad + 64 * (size_t)oa::ULIST_PARTS)));   // (ULIST_PARTS regions, each rounded up to whole waves)
+    HIPCHK(dev_malloc(&c->src.d_todo_count, TODO_COUNT_INTS * sizeof(int)));      // {entries of the hand-over list, most handed over by one wave, ...}, the two counter sets of d_ulist
+    HIPCHK(hipMemsetAsync(c->src.d_todo_count, 0, TODO_COUNT_INTS * sizeof(int), c->stream));
     // no seeds, empty keys, sel = 0, hand-over counters at zero: one launch
-    hipLaunchKernelGGL(oa::k_init_slots, dim3((c->ns_pad + 255) / 256), dim3(256), 0, c->stream, c->d_prev, c->d_win, c->d_wsafe, c->d_keys, c->d_sel,
-                       c->d_todo_count, c->ns_pad);
+    hipLaunchKernelGGL(oa::k_init_slots, dim3((c->src.ns_pad + 255) / 256), dim3(256), 0, c->stream, c->src.d_prev, c->src.d_win, c->src.d_wsafe, c->src.d_keys, c->src.d_sel,
+                       c->src.d_todo_count, c->src.ns_pad);
     HIPCHK(hipGetLastError());
-    c->pivot[0] = c->pivot[1] = c->pivot[2] = 0.0;
     return OA_OK;
 }
 
@@ -3663,31 +3627,31 @@ int set_source_single(oa_ctx *c, const float *xyz, int64_t n_verts, int on_devic
         // whole cloud costs 16 % more per pair (1/8 of 1M: 7.3 ms vs 6.3 ms).  Fallback (non-finite coordinates,
         // OA_SHARD_SPATIAL=0): contiguous ranges of the selection in the caller's order.
         DevTmp<int> d_members;
-        if (c->ns > 0 && spatial_sharding(c, n_sel, shard_count)) {
-            int rcm = spatial_shard_members(c, d_xyz, n_verts, (const long long *)d_vlist.p, step, n_sel, begin, c->ns, d_members);
+        if (c->src.ns > 0 && spatial_sharding(c, n_sel, shard_count)) {
+            int rcm = spatial_shard_members(c, d_xyz, n_verts, (const long long *)d_vlist.p, step, n_sel, begin, c->src.ns, d_members);
             if (rcm) return rcm;
             if (d_members.p) {                                      // kept: per-point outputs of a shard go back to vlist order through it
-                HIPCHK(dev_malloc(&c->d_members, sizeof(int) * (size_t)c->ns));
-                HIPCHK(hipMemcpyAsync(c->d_members, d_members.p, sizeof(int) * (size_t)c->ns, hipMemcpyDeviceToDevice, c->stream));
+                HIPCHK(dev_malloc(&c->src.d_members, sizeof(int) * (size_t)c->src.ns));
+                HIPCHK(hipMemcpyAsync(c->src.d_members, d_members.p, sizeof(int) * (size_t)c->src.ns, hipMemcpyDeviceToDevice, c->stream));
                 if (c->parent) {
-                    c->h_members.resize((size_t)c->ns);
-                    HIPCHK(hipMemcpyAsync(c->h_members.data(), d_members.p, sizeof(int) * (size_t)c->ns, hipMemcpyDeviceToHost, c->stream));
+                    c->src.h_members.resize((size_t)c->src.ns);
+                    HIPCHK(hipMemcpyAsync(c->src.h_members.data(), d_members.p, sizeof(int) * (size_t)c->src.ns, hipMemcpyDeviceToHost, c->stream));
                 }
             }
         }
-        if (c->ns > 0) {
-            hipLaunchKernelGGL(oa::k_pack_source, dim3((c->ns_pad + 255) / 256), dim3(256), 0, c->stream, d_xyz,
-                               (const long long *)d_vlist.p, step, begin, (const int *)d_members.p, c->ns, c->ns_pad, c->d_src4, c->d_sel);
+        if (c->src.ns > 0) {
+            hipLaunchKernelGGL(oa::k_pack_source, dim3((c->src.ns_pad + 255) / 256), dim3(256), 0, c->stream, d_xyz,
+                               (const long long *)d_vlist.p, step, begin, (const int *)d_members.p, c->src.ns, c->src.ns_pad, c->src.d_src4, c->src.d_sel);
             HIPCHK(hipGetLastError());
-        } else HIPCHK(hipMemsetAsync(c->d_src4, 0, sizeof(float4) * (size_t)c->ns_pad, c->stream));
+        } else HIPCHK(hipMemsetAsync(c->src.d_src4, 0, sizeof(float4) * (size_t)c->src.ns_pad, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
-        for (int k = 0; k < 3; ++k) c->pivot[k] = (double)p0[k];
-        if (c->ns > 1 && c->tune.sort_source) {
+        for (int k = 0; k < 3; ++k) c->src.pivot[k] = (double)p0[k];
+        if (c->src.ns > 1 && c->tune.sort_source) {
             int rcs = sort_source_slots(c, d_xyz, n_verts);
             if (rcs) return rcs;
         }
     } else {
-        HIPCHK(hipMemsetAsync(c->d_src4, 0, sizeof(float4) * (size_t)c->ns_pad, c->stream));
+        HIPCHK(hipMemsetAsync(c->src.d_src4, 0, sizeof(float4) * (size_t)c->src.ns_pad, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     plan_geometry(c);
@@ -3755,9 +3719,9 @@ int adopt_shard(oa_ctx *c, const oa_ctx *stage, const SelectionOrder &o, long lo
     int rc = use_device(c);
     if (rc) return rc;
     if ((rc = source_reset(c, count, begin, n_verts))) return rc;
-    for (int k = 0; k < 3; ++k) c->pivot[k] = (double)o.p0[k];
+    for (int k = 0; k < 3; ++k) c->src.pivot[k] = (double)o.p0[k];
     if (count == 0) {
-        HIPCHK(hipMemsetAsync(c->d_src4, 0, sizeof(float4) * (size_t)c->ns_pad, c->stream));
+        HIPCHK(hipMemsetAsync(c->src.d_src4, 0, sizeof(float4) * (size_t)c->src.ns_pad, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         plan_geometry(c);
         return OA_OK;
@@ -3769,21 +3733,21 @@ int adopt_shard(oa_ctx *c, const oa_ctx *stage, const SelectionOrder &o, long lo
 #define OA_RANGE_COPY(dst, src, bytes)                                                                                   \
     HIPCHK(local ? hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, c->stream)                             \
                  : hipMemcpyPeerAsync((dst), c->device, (src), stage->device, (bytes), c->stream))
-    OA_RANGE_COPY(c->d_src4, o.pts.p + begin, sizeof(float4) * (size_t)n);
-    OA_RANGE_COPY(c->d_sel, o.sel.p + begin, sizeof(int) * (size_t)n);
+    OA_RANGE_COPY(c->src.d_src4, o.pts.p + begin, sizeof(float4) * (size_t)n);
+    OA_RANGE_COPY(c->src.d_sel, o.sel.p + begin, sizeof(int) * (size_t)n);
     OA_RANGE_COPY(pos.p, o.pos.p + begin, sizeof(int) * (size_t)n);
 #undef OA_RANGE_COPY
     // caller order inside the shard = ascending selection position
-    HIPCHK(dev_malloc(&c->d_members, sizeof(int) * (size_t)n));
-    HIPCHK(dev_malloc(&c->d_perm, sizeof(int) * (size_t)n));
-    HIPCHK(dev_malloc(&c->d_src4o, sizeof(float4) * (size_t)c->ns_pad));
+    HIPCHK(dev_malloc(&c->src.d_members, sizeof(int) * (size_t)n));
+    HIPCHK(dev_malloc(&c->src.d_perm, sizeof(int) * (size_t)n));
+    HIPCHK(dev_malloc(&c->src.d_src4o, sizeof(float4) * (size_t)c->src.ns_pad));
     // (inv = the shard's slots in ascending selection position: a stable argsort of pos; d_members = pos in that order)
-    { const int rcs = sort_ints(c, pos.p, c->d_members, inv.p, (size_t)n, 31); if (rcs) return rcs; }
-    hipLaunchKernelGGL(oa::k_finish_shard, dim3((c->ns_pad + 255) / 256), dim3(256), 0, c->stream, (const int *)inv.p, n, c->ns_pad,
-                       c->d_src4, c->d_sel, c->d_src4o, c->d_perm);
+    { const int rcs = sort_ints(c, pos.p, c->src.d_members, inv.p, (size_t)n, 31); if (rcs) return rcs; }
+    hipLaunchKernelGGL(oa::k_finish_shard, dim3((c->src.ns_pad + 255) / 256), dim3(256), 0, c->stream, (const int *)inv.p, n, c->src.ns_pad,
+                       c->src.d_src4, c->src.d_sel, c->src.d_src4o, c->src.d_perm);
     HIPCHK(hipGetLastError());
-    c->h_members.resize((size_t)n);
-    HIPCHK(hipMemcpyAsync(c->h_members.data(), c->d_members, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    c->src.h_members.resize((size_t)n);
+    HIPCHK(hipMemcpyAsync(c->src.h_members.data(), c->src.d_members, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     plan_geometry(c);
     return OA_OK;
@@ -3842,29 +3806,28 @@ OA_EXPORT int oa_set_normals(oa_ctx *c, const float *src_normals, int64_t n_vert
     if (c->loop_active) { HIPCHK(hipSetDevice(c->device)); HIPCHK(hipStreamSynchronize(c->stream)); c->loop_active = false; }
     c->normals_on = false;
     if (!src_normals || !(max_angle_deg > 0.0) || !(max_angle_deg < 180.0)) return OA_OK;       // switched off
-    if (!c->d_src4 || !c->d_sel) return fail(OA_E_STATE, "oa_set_normals: call oa_set_source first");
-    if (c->nt <= 0) return fail(OA_E_STATE, "oa_set_normals: call oa_set_target first");
-    if (n_verts != c->src_n_verts) return fail(OA_E_BAD_ARG, "oa_set_normals: %lld source normals for %lld vertices", (long long)n_verts, c->src_n_verts);
+    if (!c->src.d_src4 || !c->src.d_sel) return fail(OA_E_STATE, "oa_set_normals: call oa_set_source first");
+    if (c->tgt.nt <= 0) return fail(OA_E_STATE, "oa_set_normals: call oa_set_target first");
+    if (n_verts != c->src.src_n_verts) return fail(OA_E_BAD_ARG, "oa_set_normals: %lld source normals for %lld vertices", (long long)n_verts, c->src.src_n_verts);
     // vertex mode without tgt_normals: the target's own normals (oa_set_target_normals, oa_estimate_target_normals) stay in force
-    const bool keep_tgt = !c->surface && !tgt_normals && c->d_tgt_n;
-    if (!c->surface && !keep_tgt && (!tgt_normals || nt != c->nt))
+    const bool keep_tgt = !c->tgt.surface && !tgt_normals && c->tgt.d_tgt_n;
+    if (!c->tgt.surface && !keep_tgt && (!tgt_normals || nt != c->tgt.nt))
         return fail(OA_E_BAD_ARG, "oa_set_normals: vertex mode needs one normal per target vertex (given here, or set / estimated before)");
     int rc = use_device(c);
     if (rc) return rc;
     DevTmp<float> tmp;
     HIPCHK(tmp.alloc(3 * (size_t)n_verts));
     HIPCHK(hipMemcpyAsync(tmp, src_normals, sizeof(float) * 3 * (size_t)n_verts, hipMemcpyHostToDevice, c->stream));
-    dev_free(c->d_src_n);
-    if (!keep_tgt) dev_free(c->d_tgt_n);
-    if (!keep_tgt && !c->surface) c->bnd_ok = false;                // (a cloud's boundary mask was built from the old normals)
-    HIPCHK(dev_malloc(&c->d_src_n, sizeof(float) * 3 * (size_t)std::max(1, c->ns)));
-    if (c->ns > 0)
-        hipLaunchKernelGGL(oa::k_gather_rows3, dim3((c->ns + 255) / 256), dim3(256), 0, c->stream, (const float *)tmp.p,
-                           (const int *)c->d_sel, c->ns, c->d_src_n);
+    if (!keep_tgt) c->tgt.d_tgt_n.reset();
+    if (!keep_tgt && !c->tgt.surface) c->tgt.bnd_ok = false;                // (a cloud's boundary mask was built from the old normals)
+    HIPCHK(dev_malloc(&c->src.d_src_n, sizeof(float) * 3 * (size_t)std::max(1, c->src.ns)));
+    if (c->src.ns > 0)
+        hipLaunchKernelGGL(oa::k_gather_rows3, dim3((c->src.ns + 255) / 256), dim3(256), 0, c->stream, (const float *)tmp.p,
+                           (const int *)c->src.d_sel, c->src.ns, c->src.d_src_n);
     HIPCHK(hipGetLastError());
-    if (!c->surface && !keep_tgt) {
-        HIPCHK(dev_malloc(&c->d_tgt_n, sizeof(float) * 3 * (size_t)nt));
-        HIPCHK(hipMemcpyAsync(c->d_tgt_n, tgt_normals, sizeof(float) * 3 * (size_t)nt, hipMemcpyHostToDevice, c->stream));
+    if (!c->tgt.surface && !keep_tgt) {
+        HIPCHK(dev_malloc(&c->tgt.d_tgt_n, sizeof(float) * 3 * (size_t)nt));
+        HIPCHK(hipMemcpyAsync(c->tgt.d_tgt_n, tgt_normals, sizeof(float) * 3 * (size_t)nt, hipMemcpyHostToDevice, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     c->cos_min = cos(max_angle_deg * 3.14159265358979323846 / 180.0);
@@ -4062,11 +4025,11 @@ OA_EXPORT int oa_set_source_weights(oa_ctx *c, const float *w, int64_t n_verts)
         c->loop_active = false;
     }
     if (!w) {                                                        // switched off
-        if (c->d_w) { int rc = use_device(c); if (rc) return rc; HIPCHK(hipStreamSynchronize(c->stream)); dev_free(c->d_w); }
+        if (c->src.d_w) { int rc = use_device(c); if (rc) return rc; HIPCHK(hipStreamSynchronize(c->stream)); c->src.d_w.reset(); }
         return OA_OK;
     }
-    if (!c->d_src4 || !c->d_sel) return fail(OA_E_STATE, "oa_set_source_weights: call oa_set_source first");
-    if (n_verts != c->src_n_verts) return fail(OA_E_BAD_ARG, "oa_set_source_weights: %lld weights for %lld vertices", (long long)n_verts, c->src_n_verts);
+    if (!c->src.d_src4 || !c->src.d_sel) return fail(OA_E_STATE, "oa_set_source_weights: call oa_set_source first");
+    if (n_verts != c->src.src_n_verts) return fail(OA_E_BAD_ARG, "oa_set_source_weights: %lld weights for %lld vertices", (long long)n_verts, c->src.src_n_verts);
     for (int64_t i = 0; i < n_verts; ++i)
         if (!(w[i] >= 0.f && w[i] < INFINITY)) return fail(OA_E_BAD_ARG, "oa_set_source_weights: weight %lld is negative or not finite", (long long)i);
     int rc = use_device(c);
@@ -4074,10 +4037,10 @@ OA_EXPORT int oa_set_source_weights(oa_ctx *c, const float *w, int64_t n_verts)
     DevTmp<float> tmp;
     HIPCHK(tmp.alloc((size_t)std::max<int64_t>(1, n_verts)));
     HIPCHK(hipMemcpyAsync(tmp, w, sizeof(float) * (size_t)n_verts, hipMemcpyHostToDevice, c->stream));
-    if (!c->d_w) HIPCHK(dev_malloc(&c->d_w, sizeof(float) * (size_t)std::max(1, c->ns)));
-    if (c->ns > 0)
-        hipLaunchKernelGGL(oa::k_gather_rows1, dim3((c->ns + 255) / 256), dim3(256), 0, c->stream, (const float *)tmp.p,
-                           (const int *)c->d_sel, c->ns, c->d_w);
+    if (!c->src.d_w) HIPCHK(dev_malloc(&c->src.d_w, sizeof(float) * (size_t)std::max(1, c->src.ns)));
+    if (c->src.ns > 0)
+        hipLaunchKernelGGL(oa::k_gather_rows1, dim3((c->src.ns + 255) / 256), dim3(256), 0, c->stream, (const float *)tmp.p,
+                           (const int *)c->src.d_sel, c->src.ns, c->src.d_w);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     return OA_OK;
@@ -4088,16 +4051,16 @@ OA_EXPORT int oa_set_target_normals(oa_ctx *c, const float *tgt_normals, int64_t
     if (!c || !tgt_normals) return fail(OA_E_BAD_ARG, "oa_set_target_normals: null argument");
     if (!c->subs.empty() && c->loop_active) multi_abort(c);
     OA_ROUTE_ALL_PAR(c, oa_set_target_normals(sub, tgt_normals, nt));
-    if (c->nt <= 0) return fail(OA_E_STATE, "oa_set_target_normals: call oa_set_target first");
-    if (c->surface) return fail(OA_E_STATE, "oa_set_target_normals: a surface target (oa_set_target_mesh) uses its triangles' geometric normals");
-    if (nt != c->nt) return fail(OA_E_BAD_ARG, "oa_set_target_normals: %lld normals for %d target vertices", (long long)nt, c->nt);
+    if (c->tgt.nt <= 0) return fail(OA_E_STATE, "oa_set_target_normals: call oa_set_target first");
+    if (c->tgt.surface) return fail(OA_E_STATE, "oa_set_target_normals: a surface target (oa_set_target_mesh) uses its triangles' geometric normals");
+    if (nt != c->tgt.nt) return fail(OA_E_BAD_ARG, "oa_set_target_normals: %lld normals for %d target vertices", (long long)nt, c->tgt.nt);
     int rc = use_device(c);
     if (rc) return rc;
     if (c->loop_active) { HIPCHK(hipStreamSynchronize(c->stream)); c->loop_active = false; }
     if (c->normals_on) HIPCHK(hipStreamSynchronize(c->stream));    // (the array the normal-angle test reads is replaced in place)
-    if (!c->d_tgt_n) HIPCHK(dev_malloc(&c->d_tgt_n, sizeof(float) * 3 * (size_t)nt));
-    c->bnd_ok = false;                                              // (a boundary mask was built from the old normals)
-    HIPCHK(hipMemcpyAsync(c->d_tgt_n, tgt_normals, sizeof(float) * 3 * (size_t)nt, hipMemcpyHostToDevice, c->stream));
+    if (!c->tgt.d_tgt_n) HIPCHK(dev_malloc(&c->tgt.d_tgt_n, sizeof(float) * 3 * (size_t)nt));
+    c->tgt.bnd_ok = false;                                              // (a boundary mask was built from the old normals)
+    HIPCHK(hipMemcpyAsync(c->tgt.d_tgt_n, tgt_normals, sizeof(float) * 3 * (size_t)nt, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return OA_OK;
 }
@@ -4107,8 +4070,8 @@ OA_EXPORT int oa_set_source_normals(oa_ctx *c, const float *src_normals, int64_t
     if (!c || !src_normals) return fail(OA_E_BAD_ARG, "oa_set_source_normals: null argument");
     if (!c->subs.empty() && c->loop_active) multi_abort(c);
     OA_ROUTE_ALL_PAR(c, oa_set_source_normals(sub, src_normals, n_verts));      // every child gathers its own shard
-    if (!c->d_src4 || !c->d_sel) return fail(OA_E_STATE, "oa_set_source_normals: call oa_set_source first");
-    if (n_verts != c->src_n_verts) return fail(OA_E_BAD_ARG, "oa_set_source_normals: %lld source normals for %lld vertices", (long long)n_verts, c->src_n_verts);
+    if (!c->src.d_src4 || !c->src.d_sel) return fail(OA_E_STATE, "oa_set_source_normals: call oa_set_source first");
+    if (n_verts != c->src.src_n_verts) return fail(OA_E_BAD_ARG, "oa_set_source_normals: %lld source normals for %lld vertices", (long long)n_verts, c->src.src_n_verts);
     int rc = use_device(c);
     if (rc) return rc;
     if (c->loop_active) { HIPCHK(hipStreamSynchronize(c->stream)); c->loop_active = false; }
@@ -4116,10 +4079,10 @@ OA_EXPORT int oa_set_source_normals(oa_ctx *c, const float *src_normals, int64_t
     DevTmp<float> tmp;
     HIPCHK(tmp.alloc(3 * (size_t)std::max<int64_t>(1, n_verts)));
     HIPCHK(hipMemcpyAsync(tmp, src_normals, sizeof(float) * 3 * (size_t)n_verts, hipMemcpyHostToDevice, c->stream));
-    if (!c->d_src_n) HIPCHK(dev_malloc(&c->d_src_n, sizeof(float) * 3 * (size_t)std::max(1, c->ns)));
-    if (c->ns > 0)
-        hipLaunchKernelGGL(oa::k_gather_rows3, dim3((c->ns + 255) / 256), dim3(256), 0, c->stream, (const float *)tmp.p,
-                           (const int *)c->d_sel, c->ns, c->d_src_n);
+    if (!c->src.d_src_n) HIPCHK(dev_malloc(&c->src.d_src_n, sizeof(float) * 3 * (size_t)std::max(1, c->src.ns)));
+    if (c->src.ns > 0)
+        hipLaunchKernelGGL(oa::k_gather_rows3, dim3((c->src.ns + 255) / 256), dim3(256), 0, c->stream, (const float *)tmp.p,
+                           (const int *)c->src.d_sel, c->src.ns, c->src.d_src_n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     return OA_OK;
@@ -4150,11 +4113,11 @@ OA_EXPORT int oa_reset_seeds(oa_ctx *c)
     OA_ROUTE_ALL(c, oa_reset_seeds(sub));
     c->seeded = false; c->win_seeds = false;
     c->loop_active = false;
-    if (!c->d_prev) return OA_OK;
+    if (!c->src.d_prev) return OA_OK;
     int rc = use_device(c);
     if (rc) return rc;
-    hipLaunchKernelGGL(oa::k_init_slots, dim3((c->ns_pad + 255) / 256), dim3(256), 0, c->stream, c->d_prev, c->d_win, c->d_wsafe,
-                       (unsigned long long *)nullptr, (int *)nullptr, (int *)nullptr, c->ns_pad);
+    hipLaunchKernelGGL(oa::k_init_slots, dim3((c->src.ns_pad + 255) / 256), dim3(256), 0, c->stream, c->src.d_prev, c->src.d_win, c->src.d_wsafe,
+                       (unsigned long long *)nullptr, (int *)nullptr, (int *)nullptr, c->src.ns_pad);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -4191,15 +4154,15 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
             for (oa_ctx *sub : c->subs) { double v = 0.0; const int rc = oa_get_stat(sub, what, &v); if (rc) return rc; *value += v; }
             return OA_OK;
         }
-        if (!c->surface || !c->tri_ring_ok || !c->d_tri_ring || !c->d_prev || !c->d_state || c->ns <= 0 || !c->seeded) return OA_OK;
+        if (!c->tgt.surface || !c->tgt.tri_ring_ok || !c->tgt.d_tri_ring || !c->src.d_prev || !c->d_state || c->src.ns <= 0 || !c->seeded) return OA_OK;
 #if defined(OA_EXPERIMENTS)
         int rc = use_device(c);
         if (rc) return rc;
         DevTmp<unsigned long long> d_n;
         HIPCHK(d_n.alloc(16));
         HIPCHK(hipMemsetAsync(d_n, 0, 16 * sizeof(unsigned long long), c->stream));
-        hipLaunchKernelGGL(oa::k_tri_ring_count, dim3((unsigned)((c->ns + 255) / 256)), dim3(256), 0, c->stream, (const oa::DevState *)c->d_state,
-                           (const float4 *)c->d_src4, c->ns, c->tgp.scale, (const float4 *)c->d_tri9, (const int *)c->d_prev, d_n.p,
+        hipLaunchKernelGGL(oa::k_tri_ring_count, dim3((unsigned)((c->src.ns + 255) / 256)), dim3(256), 0, c->stream, (const oa::DevState *)c->d_state,
+                           (const float4 *)c->src.d_src4, c->src.ns, c->tgt.tgp.scale, (const float4 *)c->tgt.d_tri9, (const int *)c->src.d_prev, d_n.p,
                            c->tune.debug ? d_n.p : (unsigned long long *)nullptr);
         HIPCHK(hipGetLastError());
         unsigned long long n[16];
@@ -4208,7 +4171,7 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
         if (c->tune.debug)
             fprintf(stderr, "[oa] tri ring: %llu of %d queries settled by seed + neighbours; the others: %llu no seed, %llu seeds that never accept, %llu not certified, "
                             "distance + margins within 1x / 2x / 4x / 8x of the radius %llu / %llu / %llu / %llu, farther %llu\n",
-                    n[0], c->ns, n[1], n[2], n[3], n[4], n[5], n[6], n[7], n[8]);
+                    n[0], c->src.ns, n[1], n[2], n[3], n[4], n[5], n[6], n[7], n[8]);
 #endif
         return OA_OK;
     }
@@ -4277,31 +4240,31 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
     }
     OA_ROUTE_FIRST(c, oa_get_stat(sub, what, value));
     switch (what) {
-    case OA_STAT_GRID_CELLS: *value = c->grid_ok ? (double)c->n_cells : 0.0; return OA_OK;
-    case OA_STAT_TRI_GRID_CELLS: *value = c->tri_grid_ok ? (double)c->tgp.n[0] * c->tgp.n[1] * c->tgp.n[2] : 0.0; return OA_OK;
-    case OA_STAT_TRI_GRID_ENTRIES: *value = c->tri_grid_ok ? (double)c->n_tri_entries : 0.0; return OA_OK;
-    case OA_STAT_N_TRIS: *value = (double)c->n_tris; return OA_OK;
-    case OA_STAT_SURFACE: *value = c->surface ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_GRID_CELLS: *value = c->tgt.grid_ok ? (double)c->tgt.n_cells : 0.0; return OA_OK;
+    case OA_STAT_TRI_GRID_CELLS: *value = c->tgt.tri_grid_ok ? (double)c->tgt.tgp.n[0] * c->tgt.tgp.n[1] * c->tgt.tgp.n[2] : 0.0; return OA_OK;
+    case OA_STAT_TRI_GRID_ENTRIES: *value = c->tgt.tri_grid_ok ? (double)c->tgt.n_tri_entries : 0.0; return OA_OK;
+    case OA_STAT_N_TRIS: *value = (double)c->tgt.n_tris; return OA_OK;
+    case OA_STAT_SURFACE: *value = c->tgt.surface ? 1.0 : 0.0; return OA_OK;
     case OA_STAT_BRUTE_KERNEL:
         *value = (double)brute_kernel(c);
         return OA_OK;
     case OA_STAT_FAST_ITERATIONS: *value = (double)c->fast_iters; return OA_OK;
     case OA_STAT_HANDOVER_ENTRIES: *value = c->h_poll ? (double)c->h_poll[2] : 0.0; return OA_OK;
     case OA_STAT_HANDOVER_WAVE_MAX: *value = c->h_poll ? (double)c->h_poll[3] : 0.0; return OA_OK;
-    case OA_STAT_SAFE_RADII: *value = (c->tune.grid_safe && c->safe_ok) ? 1.0 : 0.0; return OA_OK;
-    case OA_STAT_TRI_RING: *value = (c->tune.tri_ring && c->tri_ring_ok) ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_SAFE_RADII: *value = (c->tune.grid_safe && c->tgt.safe_ok) ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_TRI_RING: *value = (c->tune.tri_ring && c->tgt.tri_ring_ok) ? 1.0 : 0.0; return OA_OK;
     case OA_STAT_METRIC: *value = (double)c->metric; return OA_OK;
     case OA_STAT_PLANE_RANK: *value = (double)c->last_plane_rank; return OA_OK;
     case OA_STAT_ROBUST_LOSS: *value = (double)c->loss; return OA_OK;
     case OA_STAT_WEIGHT_SUM: *value = c->last_weight_sum; return OA_OK;
     case OA_STAT_ROBUST_SCALE: *value = c->loss == OA_LOSS_NONE ? 0.0 : (auto_scale(c) ? c->last_robust_c : c->robust_c); return OA_OK;
     case OA_STAT_ROBUST_QUANTILE: *value = c->robust_p; return OA_OK;
-    case OA_STAT_TARGET_NORMALS: *value = (!c->surface && c->d_tgt_n) ? 1.0 : 0.0; return OA_OK;
-    case OA_STAT_TARGET_FEATURES: *value = c->d_tgt_feat ? 1.0 : 0.0; return OA_OK;
-    case OA_STAT_TARGET_BOUNDARY: *value = c->bnd_ok ? 1.0 : 0.0; return OA_OK;
-    case OA_STAT_BOUNDARY_VERTICES: *value = c->bnd_ok ? (double)c->bnd_n_vertices : 0.0; return OA_OK;
-    case OA_STAT_BOUNDARY_EDGES: *value = c->bnd_ok ? (double)c->bnd_n_edges : 0.0; return OA_OK;
-    case OA_STAT_MESH_PSEUDONORMALS: *value = (c->surface && c->pn_ok) ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_TARGET_NORMALS: *value = (!c->tgt.surface && c->tgt.d_tgt_n) ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_TARGET_FEATURES: *value = c->tgt.d_tgt_feat ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_TARGET_BOUNDARY: *value = c->tgt.bnd_ok ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_BOUNDARY_VERTICES: *value = c->tgt.bnd_ok ? (double)c->tgt.bnd_n_vertices : 0.0; return OA_OK;
+    case OA_STAT_BOUNDARY_EDGES: *value = c->tgt.bnd_ok ? (double)c->tgt.bnd_n_edges : 0.0; return OA_OK;
+    case OA_STAT_MESH_PSEUDONORMALS: *value = (c->tgt.surface && c->tgt.pn_ok) ? 1.0 : 0.0; return OA_OK;
     default: return fail(OA_E_BAD_ARG, "oa_get_stat: unknown key %d", what);
     }
 }
@@ -4318,9 +4281,9 @@ OA_EXPORT int oa_get_matrix_world(oa_ctx *c, float mx_align[16])
 OA_EXPORT int64_t oa_num_selected(oa_ctx *c)
 {
     if (!c) return 0;
-    if (c->subs.empty()) return c->ns;
+    if (c->subs.empty()) return c->src.ns;
     int64_t n = 0;
-    for (oa_ctx *sub : c->subs) n += sub->ns;                       // all shards
+    for (oa_ctx *sub : c->subs) n += sub->src.ns;                       // all shards
     return n;
 }
 
@@ -4328,7 +4291,7 @@ OA_EXPORT int oa_get_pivot(oa_ctx *c, double pivot[3])
 {
     if (!c || !pivot) return fail(OA_E_BAD_ARG, "null argument");
     OA_ROUTE_FIRST(c, oa_get_pivot(sub, pivot));
-    for (int k = 0; k < 3; ++k) pivot[k] = c->pivot[k];
+    for (int k = 0; k < 3; ++k) pivot[k] = c->src.pivot[k];
     return OA_OK;
 }
 
@@ -4419,7 +4382,7 @@ OA_EXPORT int oa_nn_search(oa_ctx *c, int64_t *idx, float *d2, double *kernel_ms
         std::vector<int64_t> ic;
         std::vector<float> dc;
         for (oa_ctx *sub : c->subs) {
-            const size_t n = (size_t)sub->ns;
+            const size_t n = (size_t)sub->src.ns;
             if (idx) ic.resize(std::max<size_t>(1, n));
             if (d2) dc.resize(std::max<size_t>(1, n));
             double ms = 0.0;
@@ -4427,7 +4390,7 @@ OA_EXPORT int oa_nn_search(oa_ctx *c, int64_t *idx, float *d2, double *kernel_ms
             if (rc) return rc;
             if (kernel_ms && ms > *kernel_ms) *kernel_ms = ms;
             for (size_t k = 0; k < n; ++k) {
-                const long long g = sub->h_members.empty() ? sub->shard_begin + (long long)k : (long long)sub->h_members[k];
+                const long long g = sub->src.h_members.empty() ? sub->src.shard_begin + (long long)k : (long long)sub->src.h_members[k];
                 if (idx) idx[g] = ic[k];
                 if (d2) d2[g] = dc[k];
             }
@@ -4441,19 +4404,19 @@ OA_EXPORT int oa_nn_search(oa_ctx *c, int64_t *idx, float *d2, double *kernel_ms
     if ((rc = ensure_events(c, 1))) return rc;
     if ((rc = push_state_for_oneshot(c, 1.0, false))) return rc;
     if (kernel_ms) *kernel_ms = 0.0;
-    if (c->ns <= 0) return OA_OK;
+    if (c->src.ns <= 0) return OA_OK;
     DevTmp<long long> d_idx;
     DevTmp<float> d_d2;
-    if (idx) HIPCHK(d_idx.alloc((size_t)c->ns));
-    if (d2) HIPCHK(d_d2.alloc((size_t)c->ns));
+    if (idx) HIPCHK(d_idx.alloc((size_t)c->src.ns));
+    if (d2) HIPCHK(d_d2.alloc((size_t)c->src.ns));
     HIPCHK(hipEventRecord(c->ev[0], c->stream));
     if ((rc = launch_nn(c, choose_search(c), false))) return rc;
     HIPCHK(hipEventRecord(c->ev[1], c->stream));
-    hipLaunchKernelGGL(oa::k_decode_keys, dim3((c->ns_pad + 255) / 256), dim3(256), 0, c->stream, c->d_keys,
-                       c->ns_pad, c->ns, (const int *)c->d_perm, d_idx.p, d_d2.p);
+    hipLaunchKernelGGL(oa::k_decode_keys, dim3((c->src.ns_pad + 255) / 256), dim3(256), 0, c->stream, c->src.d_keys,
+                       c->src.ns_pad, c->src.ns, (const int *)c->src.d_perm, d_idx.p, d_d2.p);
     HIPCHK(hipGetLastError());
-    if (idx) HIPCHK(hipMemcpyAsync(idx, d_idx, sizeof(long long) * (size_t)c->ns, hipMemcpyDeviceToHost, c->stream));
-    if (d2) HIPCHK(hipMemcpyAsync(d2, d_d2, sizeof(float) * (size_t)c->ns, hipMemcpyDeviceToHost, c->stream));
+    if (idx) HIPCHK(hipMemcpyAsync(idx, d_idx, sizeof(long long) * (size_t)c->src.ns, hipMemcpyDeviceToHost, c->stream));
+    if (d2) HIPCHK(hipMemcpyAsync(d2, d_d2, sizeof(float) * (size_t)c->src.ns, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (kernel_ms) {
         float ms = 0.f;
@@ -4490,7 +4453,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
         int64_t total = 0;
         for (size_t r = 0; r < n_dev; ++r) {
             oa_ctx *sub = c->subs[r];
-            const int64_t capc = std::max(1, sub->ns);
+            const int64_t capc = std::max(1, sub->src.ns);
             Ac[r].resize(3 * (size_t)capc); Bc[r].resize(3 * (size_t)capc);
             double st[2] = { NAN, NAN };
             int rc = oa_make_pairs(sub, thresh, calc_stats, Ac[r].data(), Bc[r].data(), capc, &Kc[r], st);
@@ -4499,7 +4462,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
             Pc[r].resize((size_t)std::max<int64_t>(1, Kc[r]));
             if (Kc[r] > 0) {
                 if ((rc = use_device(sub))) return rc;
-                HIPCHK(hipMemcpyAsync(Pc[r].data(), sub->d_pos, sizeof(int) * (size_t)Kc[r], hipMemcpyDeviceToHost, sub->stream));
+                HIPCHK(hipMemcpyAsync(Pc[r].data(), sub->src.d_pos, sizeof(int) * (size_t)Kc[r], hipMemcpyDeviceToHost, sub->stream));
                 HIPCHK(hipStreamSynchronize(sub->stream));
             }
             total += Kc[r];
@@ -4510,7 +4473,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
             size_t best = n_dev;
             for (size_t r = 0; r < n_dev; ++r)
                 if (head[r] < Kc[r] && (best == n_dev || Pc[r][(size_t)head[r]] < Pc[best][(size_t)head[best]])) best = r;
-            const int64_t h = head[best]++, capc = std::max(1, c->subs[best]->ns);
+            const int64_t h = head[best]++, capc = std::max(1, c->subs[best]->src.ns);
             for (int a = 0; a < 3; ++a) {
                 A[(size_t)a * cap + k] = Ac[best][(size_t)a * capc + h];
                 B[(size_t)a * cap + k] = Bc[best][(size_t)a * capc + h];
@@ -4543,21 +4506,19 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
     if ((rc = ensure_bnd_step(c))) return rc;
     *K = 0;
     if (dstats) { dstats[0] = NAN; dstats[1] = NAN; }
-    if (c->ns == 0) return OA_OK;
-    const int n_blocks = (c->ns + 255) / 256;
-    if (c->emit_cap < c->ns) {
-        dev_free(c->d_valid); dev_free(c->d_b); dev_free(c->d_dist); dev_free(c->d_counts); dev_free(c->d_offsets);
-        dev_free(c->d_A); dev_free(c->d_B);
-        HIPCHK(dev_malloc(&c->d_valid, (size_t)c->ns));
-        HIPCHK(dev_malloc(&c->d_b, sizeof(float) * 3 * (size_t)c->ns));
-        HIPCHK(dev_malloc(&c->d_dist, sizeof(double) * (size_t)c->ns));
-        HIPCHK(dev_malloc(&c->d_counts, sizeof(int) * (size_t)n_blocks));
-        HIPCHK(dev_malloc(&c->d_offsets, sizeof(long long) * (size_t)(n_blocks + 1)));
-        HIPCHK(dev_malloc(&c->d_A, sizeof(double) * 3 * (size_t)c->ns));
-        HIPCHK(dev_malloc(&c->d_B, sizeof(double) * 3 * (size_t)c->ns));
-        dev_free(c->d_pos);
-        if (c->parent) HIPCHK(dev_malloc(&c->d_pos, sizeof(int) * (size_t)c->ns));
-        c->emit_cap = c->ns;
+    if (c->src.ns == 0) return OA_OK;
+    const int n_blocks = (c->src.ns + 255) / 256;
+    if (c->src.emit_cap < c->src.ns) {
+        HIPCHK(dev_malloc(&c->src.d_valid, (size_t)c->src.ns));
+        HIPCHK(dev_malloc(&c->src.d_b, sizeof(float) * 3 * (size_t)c->src.ns));
+        HIPCHK(dev_malloc(&c->src.d_dist, sizeof(double) * (size_t)c->src.ns));
+        HIPCHK(dev_malloc(&c->src.d_counts, sizeof(int) * (size_t)n_blocks));
+        HIPCHK(dev_malloc(&c->src.d_offsets, sizeof(long long) * (size_t)(n_blocks + 1)));
+        HIPCHK(dev_malloc(&c->src.d_A, sizeof(double) * 3 * (size_t)c->src.ns));
+        HIPCHK(dev_malloc(&c->src.d_B, sizeof(double) * 3 * (size_t)c->src.ns));
+        c->src.d_pos.reset();
+        if (c->parent) HIPCHK(dev_malloc(&c->src.d_pos, sizeof(int) * (size_t)c->src.ns));
+        c->src.emit_cap = c->src.ns;
     }
     c->d_pivot0 = 0.0;
     if ((rc = push_state_for_oneshot(c, thresh, true))) return rc;
@@ -4584,21 +4545,21 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
             if (rc) { c->d_pivot0 = 0.0; return rc; }
         }
     }
-    hipLaunchKernelGGL(oa::k_block_counts, dim3(n_blocks), dim3(256), 0, c->stream, c->d_valid, c->ns, c->d_counts);
-    hipLaunchKernelGGL(oa::k_scan_counts, dim3(1), dim3(1024), 0, c->stream, c->d_counts, n_blocks, c->d_offsets);
-    hipLaunchKernelGGL(oa::k_scatter_pairs, dim3(n_blocks), dim3(256), 0, c->stream, c->d_valid, c->ns,
-                       c->d_perm ? c->d_src4o : c->d_src4,
-                       c->d_b, c->d_offsets, (long long)c->ns, c->d_A, c->d_B, (const int *)c->d_members, c->shard_begin,
-                       c->parent ? c->d_pos : (int *)nullptr);
+    hipLaunchKernelGGL(oa::k_block_counts, dim3(n_blocks), dim3(256), 0, c->stream, c->src.d_valid, c->src.ns, c->src.d_counts);
+    hipLaunchKernelGGL(oa::k_scan_counts, dim3(1), dim3(1024), 0, c->stream, c->src.d_counts, n_blocks, c->src.d_offsets);
+    hipLaunchKernelGGL(oa::k_scatter_pairs, dim3(n_blocks), dim3(256), 0, c->stream, c->src.d_valid, c->src.ns,
+                       c->src.d_perm ? c->src.d_src4o : c->src.d_src4,
+                       c->src.d_b, c->src.d_offsets, (long long)c->src.ns, c->src.d_A, c->src.d_B, (const int *)c->src.d_members, c->src.shard_begin,
+                       c->parent ? c->src.d_pos : (int *)nullptr);
     HIPCHK(hipGetLastError());
     double sums[oa::NSUMS];
     long long total = 0;
     HIPCHK(hipMemcpyAsync(sums, c->d_sums, sizeof sums, hipMemcpyDeviceToHost, c->stream));
-    { int rcr = read_small(c, &total, c->d_offsets + n_blocks, sizeof total); if (rcr) return rcr; }
+    { int rcr = read_small(c, &total, c->src.d_offsets + n_blocks, sizeof total); if (rcr) return rcr; }
     if (total > cap) return fail(OA_E_CAPACITY, "oa_make_pairs: %lld pairs but capacity %lld", total, (long long)cap);
     for (int a = 0; a < 3 && total > 0; ++a) {
-        HIPCHK(hipMemcpyAsync(A + (size_t)a * cap, c->d_A + (size_t)a * c->ns, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(B + (size_t)a * cap, c->d_B + (size_t)a * c->ns, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(A + (size_t)a * cap, c->src.d_A + (size_t)a * c->src.ns, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(B + (size_t)a * cap, c->src.d_B + (size_t)a * c->src.ns, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     *K = total;
@@ -4998,12 +4959,12 @@ inline int pose_bpp(const oa_ctx *c, int n_poses, int S)
 
 int pose_job_begin(oa_ctx *c, double thresh, int32_t stride, PoseJob &job)
 {
-    job.tri = c->surface;
-    const bool tree = job.tri ? (c->tbvh_ok && c->d_tbvh_box && c->d_tbvh_prims && c->d_tri9) : (c->bvh_ok && c->d_bvh_box && c->d_bvh_prims);
+    job.tri = c->tgt.surface;
+    const bool tree = job.tri ? (c->tgt.tbvh_ok && c->tgt.d_tbvh_box && c->tgt.d_tbvh_prims && c->tgt.d_tri9) : (c->tgt.bvh_ok && c->tgt.d_bvh_box && c->tgt.d_bvh_prims);
     if (!tree) return fail(OA_E_STATE, "pose scoring searches through the target's box tree: none was built (OA_SEARCH_BRUTE, or a target with non-finite coordinates)");
-    if (c->ns <= 0) return fail(OA_E_STATE, "pose scoring: the selection is empty");
+    if (c->src.ns <= 0) return fail(OA_E_STATE, "pose scoring: the selection is empty");
     const int step = stride > 1 ? stride : 1;
-    job.S = (c->ns + step - 1) / step;
+    job.S = (c->src.ns + step - 1) / step;
     const oa::DevState &s = c->h_state;
     memcpy(job.pb.mx2, s.mx2, sizeof s.mx2);
     memcpy(job.pb.imx2, s.imx2, sizeof s.imx2);
@@ -5012,9 +4973,9 @@ int pose_job_begin(oa_ctx *c, double thresh, int32_t stride, PoseJob &job)
     job.pb.cut_a = INFINITY; job.pb.cut_b = 0.0;
     double lpw = 0.0;
     search_radius(c, s.mx2, thresh, job.pb.cut_a, job.pb.cut_b, lpw);
-    for (int k = 0; k < 3; ++k) job.pb.pivot[k] = c->pivot[k];
+    for (int k = 0; k < 3; ++k) job.pb.pivot[k] = c->src.pivot[k];
     HIPCHK(job.sample.alloc((size_t)job.S));
-    hipLaunchKernelGGL(oa::k_pose_sample, dim3((unsigned)((c->ns + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->d_perm, c->ns, step, job.sample.p);
+    hipLaunchKernelGGL(oa::k_pose_sample, dim3((unsigned)((c->src.ns + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->src.d_perm, c->src.ns, step, job.sample.p);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -5025,9 +4986,9 @@ int pose_launch(oa_ctx *c, const PoseJob &job, bool full, const float *d_poses, 
     const dim3 grid((unsigned)((long long)n_poses * bpp)), block(oa::POSE_WPB * 64);
     auto launch = [&](auto TRI, auto FULL) {
         constexpr bool tri = decltype(TRI)::value;
-        hipLaunchKernelGGL((oa::k_pose_score<tri, decltype(FULL)::value>), grid, block, 0, c->stream, job.pb, d_poses, d_iposes, (const float4 *)c->d_src4,
-                           (const int *)job.sample.p, job.S, bpp, tri ? c->tbvh : c->bvh, (const float4 *)(tri ? c->d_tbvh_box : c->d_bvh_box),
-                           (const float4 *)(tri ? c->d_tbvh_prims : c->d_bvh_prims), (const float4 *)c->d_tri9, d_rows);
+        hipLaunchKernelGGL((oa::k_pose_score<tri, decltype(FULL)::value>), grid, block, 0, c->stream, job.pb, d_poses, d_iposes, (const float4 *)c->src.d_src4,
+                           (const int *)job.sample.p, job.S, bpp, tri ? c->tgt.tbvh : c->tgt.bvh, (const float4 *)(tri ? c->tgt.d_tbvh_box : c->tgt.d_bvh_box),
+                           (const float4 *)(tri ? c->tgt.d_tbvh_prims : c->tgt.d_bvh_prims), (const float4 *)c->tgt.d_tri9, d_rows);
     };
     if (job.tri) { if (full) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{}); }
     else { if (full) launch(std::false_type{}, std::true_type{}); else launch(std::false_type{}, std::false_type{}); }
@@ -5101,9 +5062,9 @@ void mul4d(const double *A, const double *B, double *out)
 int coarse_candidates(oa_ctx *c, int n_rot, float *out)
 {
     double cs[3], ct[3];
-    int rc = centroid_of<4>(c, (const float *)c->d_src4, c->ns, c->h_state.mx1, cs, "oa_coarse_candidates: the selection");
+    int rc = centroid_of<4>(c, (const float *)c->src.d_src4, c->src.ns, c->h_state.mx1, cs, "oa_coarse_candidates: the selection");
     if (rc) return rc;
-    if ((rc = centroid_of<3>(c, c->d_tgt_xyz, c->nt, c->h_state.mx2, ct, "oa_coarse_candidates: the target"))) return rc;
+    if ((rc = centroid_of<3>(c, c->tgt.d_tgt_xyz, c->tgt.nt, c->h_state.mx2, ct, "oa_coarse_candidates: the target"))) return rc;
     double A[16], Tt[16] = { 1, 0, 0, ct[0], 0, 1, 0, ct[1], 0, 0, 1, ct[2], 0, 0, 0, 1 }, Ts[16] = { 1, 0, 0, -cs[0], 0, 1, 0, -cs[1], 0, 0, 1, -cs[2], 0, 0, 0, 1 };
     for (int k = 0; k < 16; ++k) A[k] = (double)c->h_state.mx1[k];
     double right[16];
@@ -5146,7 +5107,7 @@ OA_EXPORT int oa_score_poses(oa_ctx *c, const float *mx_align, int32_t n_poses, 
     for (size_t k = 0; k < 16 * (size_t)n_poses; ++k)
         if (!(fabsf(mx_align[k]) < INFINITY)) return fail(OA_E_BAD_ARG, "oa_score_poses: entry %zu of pose %zu is not finite", k % 16, k / 16);
     {
-        const long long step = stride > 1 ? stride : 1, S = (c->ns + step - 1) / step;
+        const long long step = stride > 1 ? stride : 1, S = (c->src.ns + step - 1) / step;
         if (S * n_poses >= (1ll << 31)) return fail(OA_E_BAD_ARG, "oa_score_poses: %lld sample points x %d poses: 2^31 queries or more", S, n_poses);
     }
     PoseJob job;
@@ -5166,7 +5127,7 @@ OA_EXPORT int oa_coarse_candidates(oa_ctx *c, int32_t n_rot, float *mx_align_out
     int rc = pose_call_ready(c);
     if (rc) return rc;
     if (n_rot < 1 || n_rot > 65536) return fail(OA_E_BAD_ARG, "oa_coarse_candidates: %d rotations (1 .. 65536)", n_rot);
-    if (c->ns <= 0) return fail(OA_E_STATE, "oa_coarse_candidates: the selection is empty");
+    if (c->src.ns <= 0) return fail(OA_E_STATE, "oa_coarse_candidates: the selection is empty");
     return coarse_candidates(c, n_rot, mx_align_out);
 }
 
@@ -5198,7 +5159,7 @@ int coarse_align_body(oa_ctx *c, const char *who, const oa_coarse_settings *cs, 
     const int P = n_rot + 1;                                        // the incoming pose is candidate n_rot
     const int n_ref = std::min((int)cs->n_refine, P);
     {
-        const long long step = cs->stride > 1 ? cs->stride : 1, S = (c->ns + step - 1) / step;
+        const long long step = cs->stride > 1 ? cs->stride : 1, S = (c->src.ns + step - 1) / step;
         if (S * P >= (1ll << 31)) return fail(OA_E_BAD_ARG, "%s: %lld sample points x %d poses: 2^31 queries or more", who, S, P);
     }
     PoseJob job;
@@ -5231,7 +5192,7 @@ int coarse_align_body(oa_ctx *c, const char *who, const oa_coarse_settings *cs, 
         HIPCHK(rows.alloc((size_t)n_ref * bpp * oa::NSUMS));
         for (int it = 0; it < cs->refine_iters; ++it) {
             if ((rc = pose_launch(c, job, true, d_poses.p, d_iposes.p, n_ref, bpp, rows.p))) { (void)hipStreamSynchronize(c->stream); return rc; }
-            hipLaunchKernelGGL(oa::k_pose_solve, dim3((unsigned)n_ref), dim3(64), 0, c->stream, (const double *)rows.p, bpp, c->pivot[0], c->pivot[1], c->pivot[2],
+            hipLaunchKernelGGL(oa::k_pose_solve, dim3((unsigned)n_ref), dim3(64), 0, c->stream, (const double *)rows.p, bpp, c->src.pivot[0], c->src.pivot[1], c->src.pivot[2],
                                d_poses.p, d_iposes.p);
             HIPCHK(hipGetLastError());
         }
@@ -5306,22 +5267,18 @@ namespace {
 struct KnnTree {
     oa::BvhParams bp{};
     const float4 *box = nullptr, *prims = nullptr;
-    float4 *own_box = nullptr, *own_prims = nullptr;
-    KnnTree() = default;
-    KnnTree(const KnnTree &) = delete;
-    KnnTree &operator=(const KnnTree &) = delete;
-    ~KnnTree() { dev_free(own_box); dev_free(own_prims); }
+    DevBuf<float4> own_box, own_prims;
 };
 
 // the box of the target's finite coordinates, base-local (all zero when there is none)
 int target_bbox(oa_ctx *c, double lo[3], double hi[3])
 {
     for (int a = 0; a < 3; ++a) { lo[a] = 0.0; hi[a] = 0.0; }
-    if (c->filter_ok) { for (int a = 0; a < 3; ++a) { lo[a] = c->bb_lo[a]; hi[a] = c->bb_hi[a]; } return OA_OK; }
+    if (c->tgt.filter_ok) { for (int a = 0; a < 3; ++a) { lo[a] = c->bb_lo[a]; hi[a] = c->bb_hi[a]; } return OA_OK; }
     const int nb = 256;
     DevTmp<float> d_bb;
     HIPCHK(d_bb.alloc(6 * (size_t)nb));
-    hipLaunchKernelGGL(oa::k_bbox_finite, dim3(nb), dim3(256), 0, c->stream, (const float *)c->d_tgt_xyz, c->nt, d_bb.p);
+    hipLaunchKernelGGL(oa::k_bbox_finite, dim3(nb), dim3(256), 0, c->stream, (const float *)c->tgt.d_tgt_xyz, c->tgt.nt, d_bb.p);
     HIPCHK(hipGetLastError());
     std::vector<float> bb(6 * (size_t)nb);
     const int rc = read_small(c, bb.data(), d_bb.p, sizeof(float) * bb.size());
@@ -5335,11 +5292,11 @@ int target_bbox(oa_ctx *c, double lo[3], double hi[3])
 
 int knn_tree(oa_ctx *c, KnnTree &t)
 {
-    if (c->bvh_ok && c->d_bvh_box && c->d_bvh_prims) { t.bp = c->bvh; t.box = c->d_bvh_box; t.prims = c->d_bvh_prims; return OA_OK; }
+    if (c->tgt.bvh_ok && c->tgt.d_bvh_box && c->tgt.d_bvh_prims) { t.bp = c->tgt.bvh; t.box = c->tgt.d_bvh_box; t.prims = c->tgt.d_bvh_prims; return OA_OK; }
     double lo[3], hi[3];
     { const int rcb = target_bbox(c, lo, hi); if (rcb) return rcb; }
     bool ok = false;
-    const int rc = build_bvh_arrays(c, false, c->d_tgt_xyz, 3, c->nt, lo, hi, t.bp, t.own_box, t.own_prims, ok);
+    const int rc = build_bvh_arrays(c, false, c->tgt.d_tgt_xyz, 3, c->tgt.nt, lo, hi, t.bp, t.own_box, t.own_prims, ok);
     if (rc) return rc;
     if (!ok) return fail(OA_E_CAPACITY, "the target's box tree would need more than %d levels", oa::BVH_MAX_LEVELS);
     t.box = t.own_box; t.prims = t.own_prims;
@@ -5349,10 +5306,10 @@ int knn_tree(oa_ctx *c, KnnTree &t)
 // what both calls check and do first; a running sequence ends the way oa_set_target_normals ends one
 int knn_call_begin(oa_ctx *c, const char *who, int k, int k_min)
 {
-    if (c->nt <= 0) return fail(OA_E_STATE, "%s: call oa_set_target first", who);
-    if (c->surface) return fail(OA_E_STATE, "%s: a surface target (oa_set_target_mesh) uses its triangles' geometric normals", who);
-    if (k < k_min || k > oa::KNN_MAX_K || k > c->nt)
-        return fail(OA_E_BAD_ARG, "%s: k = %d outside %d .. min(%d, %d target vertices)", who, k, k_min, oa::KNN_MAX_K, c->nt);
+    if (c->tgt.nt <= 0) return fail(OA_E_STATE, "%s: call oa_set_target first", who);
+    if (c->tgt.surface) return fail(OA_E_STATE, "%s: a surface target (oa_set_target_mesh) uses its triangles' geometric normals", who);
+    if (k < k_min || k > oa::KNN_MAX_K || k > c->tgt.nt)
+        return fail(OA_E_BAD_ARG, "%s: k = %d outside %d .. min(%d, %d target vertices)", who, k, k_min, oa::KNN_MAX_K, c->tgt.nt);
     const int rc = use_device(c);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -5367,7 +5324,7 @@ int knn_launch(oa_ctx *c, const KnnTree &t, int k, int32_t *d_idx, float *d_d2, 
     const int leaves = t.bp.cnt[1];
     const unsigned blocks = (unsigned)std::max(1, std::min((leaves + wpb - 1) / wpb, c->n_cu * 32));
     hipLaunchKernelGGL((oa::k_bvh_knn<PCA>), dim3(blocks), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, k, d_idx, d_d2,
-                       (const float *)c->d_tgt_xyz, orient, d_n, d_curv);
+                       (const float *)c->tgt.d_tgt_xyz, orient, d_n, d_curv);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
@@ -5383,7 +5340,7 @@ OA_EXPORT int oa_target_knn(oa_ctx *c, int k, int32_t *out_idx, float *out_d2)
     if (rc) return rc;
     KnnTree tree;
     if ((rc = knn_tree(c, tree))) return rc;
-    const size_t n = (size_t)c->nt * (size_t)k;
+    const size_t n = (size_t)c->tgt.nt * (size_t)k;
     DevTmp<int32_t> d_idx;
     DevTmp<float> d_d2;
     if (out_idx) HIPCHK(d_idx.alloc(n));
@@ -5415,16 +5372,16 @@ OA_EXPORT int oa_estimate_target_normals(oa_ctx *c, int k, int orient, const flo
         if (orient_point) { for (int a = 0; a < 3; ++a) ko.p[a] = (double)orient_point[a]; }
         else {
             static const float eye16[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
-            if ((rc = centroid_of<3>(c, c->d_tgt_xyz, c->nt, eye16, ko.p, "oa_estimate_target_normals: the target"))) return rc;
+            if ((rc = centroid_of<3>(c, c->tgt.d_tgt_xyz, c->tgt.nt, eye16, ko.p, "oa_estimate_target_normals: the target"))) return rc;
         }
     }
-    const size_t nt = (size_t)c->nt;
+    const size_t nt = (size_t)c->tgt.nt;
     DevTmp<float> tmp_n, d_curv;
     float *d_n = nullptr;
     if (install) {                                                   // (the stream is idle: the array the loops read is replaced in place)
-        if (!c->d_tgt_n) HIPCHK(dev_malloc(&c->d_tgt_n, sizeof(float) * 3 * nt));
-        c->bnd_ok = false;                                           // (a boundary mask was built from the old normals)
-        d_n = c->d_tgt_n;
+        if (!c->tgt.d_tgt_n) HIPCHK(dev_malloc(&c->tgt.d_tgt_n, sizeof(float) * 3 * nt));
+        c->tgt.bnd_ok = false;                                           // (a boundary mask was built from the old normals)
+        d_n = c->tgt.d_tgt_n;
     } else if (out_normals) { HIPCHK(tmp_n.alloc(3 * nt)); d_n = tmp_n.p; }
     if (out_curvature) HIPCHK(d_curv.alloc(nt));
     if ((rc = knn_launch<true>(c, tree, k, nullptr, nullptr, ko, d_n, d_curv.p))) return rc;
@@ -5512,10 +5469,10 @@ OA_EXPORT int oa_target_fpfh(oa_ctx *c, int k, float *out, int keep)
     OA_NOT_MULTI(c, "oa_target_fpfh");
     int rc = knn_call_begin(c, "oa_target_fpfh", k, 4);
     if (rc) return rc;
-    if (!c->d_tgt_n) return fail(OA_E_STATE, "oa_target_fpfh: the target has no normals (oa_set_target_normals, oa_set_normals or oa_estimate_target_normals with install)");
+    if (!c->tgt.d_tgt_n) return fail(OA_E_STATE, "oa_target_fpfh: the target has no normals (oa_set_target_normals, oa_set_normals or oa_estimate_target_normals with install)");
     KnnTree tree;
     if ((rc = knn_tree(c, tree))) return rc;
-    const size_t nt = (size_t)c->nt;
+    const size_t nt = (size_t)c->tgt.nt;
     DevTmp<int32_t> d_idx;
     DevTmp<double> d_spfh;
     DevTmp<float> tmp;
@@ -5523,15 +5480,15 @@ OA_EXPORT int oa_target_fpfh(oa_ctx *c, int k, float *out, int keep)
     HIPCHK(d_spfh.alloc(nt * oa::FPFH_DIM));
     float *d_out = nullptr;
     if (keep) {                                                     // (the stream is idle: a kept table is replaced in place)
-        if (!c->d_tgt_feat) HIPCHK(dev_malloc(&c->d_tgt_feat, sizeof(float) * oa::FPFH_DIM * nt));
-        d_out = c->d_tgt_feat;
+        if (!c->tgt.d_tgt_feat) HIPCHK(dev_malloc(&c->tgt.d_tgt_feat, sizeof(float) * oa::FPFH_DIM * nt));
+        d_out = c->tgt.d_tgt_feat;
     } else { HIPCHK(tmp.alloc(oa::FPFH_DIM * nt)); d_out = tmp.p; }
     if ((rc = knn_launch<false>(c, tree, k, d_idx.p, nullptr, oa::KnnOrient{}, nullptr, nullptr))) return rc;
     const dim3 grid((unsigned)((nt + oa::FPFH_THREADS - 1) / oa::FPFH_THREADS)), block(oa::FPFH_THREADS);
-    hipLaunchKernelGGL((oa::k_fpfh<false>), grid, block, 0, c->stream, (const float *)c->d_tgt_xyz, (const float *)c->d_tgt_n, (const int32_t *)d_idx.p,
-                       c->nt, k, d_spfh.p, (float *)nullptr);
-    hipLaunchKernelGGL((oa::k_fpfh<true>), grid, block, 0, c->stream, (const float *)c->d_tgt_xyz, (const float *)c->d_tgt_n, (const int32_t *)d_idx.p,
-                       c->nt, k, d_spfh.p, d_out);
+    hipLaunchKernelGGL((oa::k_fpfh<false>), grid, block, 0, c->stream, (const float *)c->tgt.d_tgt_xyz, (const float *)c->tgt.d_tgt_n, (const int32_t *)d_idx.p,
+                       c->tgt.nt, k, d_spfh.p, (float *)nullptr);
+    hipLaunchKernelGGL((oa::k_fpfh<true>), grid, block, 0, c->stream, (const float *)c->tgt.d_tgt_xyz, (const float *)c->tgt.d_tgt_n, (const int32_t *)d_idx.p,
+                       c->tgt.nt, k, d_spfh.p, d_out);
     HIPCHK(hipGetLastError());
     if (out) HIPCHK(hipMemcpyAsync(out, d_out, sizeof(float) * oa::FPFH_DIM * nt, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -5556,24 +5513,24 @@ OA_EXPORT int oa_feature_candidates(oa_ctx *c, const float *src_feat, int64_t n_
     OA_NOT_MULTI(c, "oa_feature_candidates");
     int rc = pose_call_ready(c);
     if (rc) return rc;
-    if (c->surface) return fail(OA_E_STATE, "oa_feature_candidates: a surface target (oa_set_target_mesh) has no per-vertex descriptors");
-    if (!tgt_feat && !c->d_tgt_feat) return fail(OA_E_STATE, "oa_feature_candidates: no descriptors are resident for the target (oa_target_fpfh with keep), and none were passed");
+    if (c->tgt.surface) return fail(OA_E_STATE, "oa_feature_candidates: a surface target (oa_set_target_mesh) has no per-vertex descriptors");
+    if (!tgt_feat && !c->tgt.d_tgt_feat) return fail(OA_E_STATE, "oa_feature_candidates: no descriptors are resident for the target (oa_target_fpfh with keep), and none were passed");
     if (!tgt_feat && fs->dim != oa::FPFH_DIM) return fail(OA_E_BAD_ARG, "oa_feature_candidates: the resident descriptors have %d floats, the settings say %d", oa::FPFH_DIM, fs->dim);
-    if (c->ns <= 0) return fail(OA_E_STATE, "oa_feature_candidates: the selection is empty");
-    if (n_verts != c->src_n_verts) return fail(OA_E_BAD_ARG, "oa_feature_candidates: %lld descriptor rows for %lld source vertices", (long long)n_verts, c->src_n_verts);
+    if (c->src.ns <= 0) return fail(OA_E_STATE, "oa_feature_candidates: the selection is empty");
+    if (n_verts != c->src.src_n_verts) return fail(OA_E_BAD_ARG, "oa_feature_candidates: %lld descriptor rows for %lld source vertices", (long long)n_verts, c->src.src_n_verts);
     const int dim = fs->dim;
     if (dim < 1 || dim > oa::FEAT_MAX_DIM || fs->n_hyp < 1 || fs->n_hyp > 65535 || !(fs->ratio > 0.0) || !(fs->edge_tol > 0.0) || !(fs->edge_tol <= 1.0) ||
         !(fs->min_edge < INFINITY))
         return fail(OA_E_BAD_ARG, "oa_feature_candidates: dim 1 .. %d, n_hyp 1 .. 65535, ratio > 0, 0 < edge_tol <= 1 and a finite min_edge", oa::FEAT_MAX_DIM);
-    if (c->ns > (1 << 24) || c->nt > (1 << 24)) return fail(OA_E_BAD_ARG, "oa_feature_candidates: more than 2^24 rows on a side");
+    if (c->src.ns > (1 << 24) || c->tgt.nt > (1 << 24)) return fail(OA_E_BAD_ARG, "oa_feature_candidates: more than 2^24 rows on a side");
     memset(rep, 0, sizeof *rep);
     *n_out = 0;
     const auto t0 = std::chrono::steady_clock::now();
     auto ms_since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
-    const int ns = c->ns, nt = c->nt, n_hyp = fs->n_hyp;
+    const int ns = c->src.ns, nt = c->tgt.nt, n_hyp = fs->n_hyp;
     // the selection's rows, in slot order
     std::vector<int> sel((size_t)ns);
-    HIPCHK(hipMemcpyAsync(sel.data(), c->d_sel, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(sel.data(), c->src.d_sel, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     std::vector<float> fsel((size_t)ns * dim);
     for (int s = 0; s < ns; ++s) {
@@ -5583,7 +5540,7 @@ OA_EXPORT int oa_feature_candidates(oa_ctx *c, const float *src_feat, int64_t n_
     std::vector<float> kept;
     if (!tgt_feat) {                                                // the kept table (matching takes host rows)
         kept.resize((size_t)nt * oa::FPFH_DIM);
-        HIPCHK(hipMemcpyAsync(kept.data(), c->d_tgt_feat, sizeof(float) * kept.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(kept.data(), c->tgt.d_tgt_feat, sizeof(float) * kept.size(), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         tgt_feat = kept.data();
     }
@@ -5654,7 +5611,7 @@ OA_EXPORT int oa_feature_candidates(oa_ctx *c, const float *src_feat, int64_t n_
     for (int k = 0; k < 16; ++k) ma.m[k] = (double)c->h_state.mx1[k];
     constexpr int WPB = 4;
     hipLaunchKernelGGL((oa::k_triple_poses<WPB>), dim3((unsigned)((n_hyp + WPB - 1) / WPB)), dim3(WPB * 64), 0, c->stream, (const int *)d_ps.p,
-                       (const int *)d_pt.p, n_pairs, (const int *)d_tri.p, n_hyp, (const float4 *)c->d_src4, (const float *)c->d_tgt_xyz, m1, m2, ma,
+                       (const int *)d_pt.p, n_pairs, (const int *)d_tri.p, n_hyp, (const float4 *)c->src.d_src4, (const float *)c->tgt.d_tgt_xyz, m1, m2, ma,
                        fs->edge_tol, min_edge, d_poses.p, d_flags.p);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(oa::k_triple_compact, dim3(1), dim3(256), 0, c->stream, (const float *)d_poses.p, (const int *)d_flags.p, n_hyp, d_out.p, d_n.p);
@@ -5853,19 +5810,18 @@ namespace {
 // upload, shared by the pseudo-normals and the boundary masks (both walk the rows)
 int ensure_corner_rows(oa_ctx *c)
 {
-    if (c->corner_ok) return OA_OK;
-    const size_t n_corners = 3 * (size_t)c->n_tris, nv = (size_t)c->nt;
+    if (c->tgt.corner_ok) return OA_OK;
+    const size_t n_corners = 3 * (size_t)c->tgt.n_tris, nv = (size_t)c->tgt.nt;
     if (n_corners > (size_t)0x7FF00000) return fail(OA_E_CAPACITY, "the mesh's corner rows: %zu corners (the sort takes fewer than 2^31 - 2^20)", n_corners);
-    dev_free(c->d_corner_order); dev_free(c->d_corner_row);
-    HIPCHK(dev_malloc(&c->d_corner_order, sizeof(int) * n_corners));
-    HIPCHK(dev_malloc(&c->d_corner_row, sizeof(long long) * (nv + 1)));
+    HIPCHK(dev_malloc(&c->tgt.d_corner_order, sizeof(int) * n_corners));
+    HIPCHK(dev_malloc(&c->tgt.d_corner_row, sizeof(long long) * (nv + 1)));
     // (the indices were checked at upload: all in 0 .. nt - 1, so they are their own keys; oa_sort.hpp adds 10-bit passes as the bits ask)
-    const int rc = sort_order_bits(c, (const unsigned *)c->d_tris, c->d_corner_order, n_corners, bits_for((long long)nv));
+    const int rc = sort_order_bits(c, (const unsigned *)c->tgt.d_tris, c->tgt.d_corner_order, n_corners, bits_for((long long)nv));
     if (rc) return rc;
-    hipLaunchKernelGGL(oa::k_pn_row_start, dim3((unsigned)((nv + 1 + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->d_tris, (const int *)c->d_corner_order,
-                       (long long)n_corners, (int)nv, c->d_corner_row);
+    hipLaunchKernelGGL(oa::k_pn_row_start, dim3((unsigned)((nv + 1 + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->tgt.d_tris, (const int *)c->tgt.d_corner_order,
+                       (long long)n_corners, (int)nv, c->tgt.d_corner_row);
     HIPCHK(hipGetLastError());
-    c->corner_ok = true;
+    c->tgt.corner_ok = true;
     return OA_OK;
 }
 
@@ -5873,29 +5829,28 @@ int ensure_corner_rows(oa_ctx *c)
 // per (triangle, edge)
 int ensure_pseudonormals(oa_ctx *c)
 {
-    if (c->pn_ok) return OA_OK;
-    if (!c->surface || !c->d_tris || c->n_tris < 1 || c->nt < 1) return fail(OA_E_STATE, "pseudo-normals need a mesh target (oa_set_target_mesh)");
+    if (c->tgt.pn_ok) return OA_OK;
+    if (!c->tgt.surface || !c->tgt.d_tris || c->tgt.n_tris < 1 || c->tgt.nt < 1) return fail(OA_E_STATE, "pseudo-normals need a mesh target (oa_set_target_mesh)");
     const auto t0 = std::chrono::steady_clock::now();
-    const size_t n_tris = (size_t)c->n_tris, n_corners = 3 * n_tris, nv = (size_t)c->nt;
-    dev_free(c->d_pn_face); dev_free(c->d_pn_vertex); dev_free(c->d_pn_edge);
-    HIPCHK(dev_malloc(&c->d_pn_face, sizeof(double) * 3 * n_tris));
-    HIPCHK(dev_malloc(&c->d_pn_vertex, sizeof(float) * 3 * nv));
-    HIPCHK(dev_malloc(&c->d_pn_edge, sizeof(float) * 9 * n_tris));
+    const size_t n_tris = (size_t)c->tgt.n_tris, n_corners = 3 * n_tris, nv = (size_t)c->tgt.nt;
+    HIPCHK(dev_malloc(&c->tgt.d_pn_face, sizeof(double) * 3 * n_tris));
+    HIPCHK(dev_malloc(&c->tgt.d_pn_vertex, sizeof(float) * 3 * nv));
+    HIPCHK(dev_malloc(&c->tgt.d_pn_edge, sizeof(float) * 9 * n_tris));
     DevTmp<double> d_angle;
     HIPCHK(d_angle.alloc(n_corners));
     const unsigned t_blocks = (unsigned)((n_tris + 255) / 256), c_blocks = (unsigned)((n_corners + 255) / 256);
-    hipLaunchKernelGGL(oa::k_pn_face, dim3(t_blocks), dim3(256), 0, c->stream, (const float *)c->d_tgt_xyz, (const int *)c->d_tris, (int)n_tris, c->d_pn_face,
+    hipLaunchKernelGGL(oa::k_pn_face, dim3(t_blocks), dim3(256), 0, c->stream, (const float *)c->tgt.d_tgt_xyz, (const int *)c->tgt.d_tris, (int)n_tris, c->tgt.d_pn_face,
                        d_angle.p);
     HIPCHK(hipGetLastError());
     const int rc = ensure_corner_rows(c);
     if (rc) return rc;
-    hipLaunchKernelGGL(oa::k_pn_vertex, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->d_corner_order, (const long long *)c->d_corner_row, (int)nv,
-                       (const double *)c->d_pn_face, (const double *)d_angle.p, c->d_pn_vertex);
-    hipLaunchKernelGGL(oa::k_pn_edge, dim3(c_blocks), dim3(256), 0, c->stream, (const int *)c->d_tris, (int)n_tris, (const int *)c->d_corner_order,
-                       (const long long *)c->d_corner_row, (const double *)c->d_pn_face, c->d_pn_edge);
+    hipLaunchKernelGGL(oa::k_pn_vertex, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream, (const int *)c->tgt.d_corner_order, (const long long *)c->tgt.d_corner_row, (int)nv,
+                       (const double *)c->tgt.d_pn_face, (const double *)d_angle.p, c->tgt.d_pn_vertex);
+    hipLaunchKernelGGL(oa::k_pn_edge, dim3(c_blocks), dim3(256), 0, c->stream, (const int *)c->tgt.d_tris, (int)n_tris, (const int *)c->tgt.d_corner_order,
+                       (const long long *)c->tgt.d_corner_row, (const double *)c->tgt.d_pn_face, c->tgt.d_pn_edge);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));                        // (the temporaries go back to the cache behind this)
-    c->pn_ok = true;
+    c->tgt.pn_ok = true;
     c->last_pn_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return OA_OK;
 }
@@ -5922,48 +5877,48 @@ namespace {
 // also until its normals or (k, angle_deg) change.  The device and the stream are the caller's (use_device); no loop is running
 int ensure_boundary(oa_ctx *c, int k, double angle_deg)
 {
-    if (c->nt <= 0) return fail(OA_E_STATE, "the target's boundary: call oa_set_target or oa_set_target_mesh first");
-    if (c->surface) {
-        if (c->bnd_ok) return OA_OK;
-        if (!c->d_tris || c->n_tris < 1) return fail(OA_E_STATE, "the target's boundary: the mesh has no triangles");
+    if (c->tgt.nt <= 0) return fail(OA_E_STATE, "the target's boundary: call oa_set_target or oa_set_target_mesh first");
+    if (c->tgt.surface) {
+        if (c->tgt.bnd_ok) return OA_OK;
+        if (!c->tgt.d_tris || c->tgt.n_tris < 1) return fail(OA_E_STATE, "the target's boundary: the mesh has no triangles");
     } else {
-        if (!c->d_tgt_n)
+        if (!c->tgt.d_tgt_n)
             return fail(OA_E_STATE, "the boundary of a point-cloud target needs its normals: call oa_set_target_normals (or oa_set_normals, or install an estimate) first");
-        const int rcp = check_boundary_params("the target's boundary", k, angle_deg, c->nt);
+        const int rcp = check_boundary_params("the target's boundary", k, angle_deg, c->tgt.nt);
         if (rcp) return rcp;
-        if (c->bnd_ok && c->bnd_built_k == k && c->bnd_built_angle == angle_deg) return OA_OK;
+        if (c->tgt.bnd_ok && c->tgt.bnd_built_k == k && c->tgt.bnd_built_angle == angle_deg) return OA_OK;
     }
     const auto t0 = std::chrono::steady_clock::now();
-    c->bnd_ok = false;
-    const size_t nv = (size_t)c->nt;
-    if (!c->d_bnd_vmask) HIPCHK(dev_malloc(&c->d_bnd_vmask, nv));
+    c->tgt.bnd_ok = false;
+    const size_t nv = (size_t)c->tgt.nt;
+    if (!c->tgt.d_bnd_vmask) HIPCHK(dev_malloc(&c->tgt.d_bnd_vmask, nv));
     int rc;
-    if (c->surface) {
-        const size_t n_tris = (size_t)c->n_tris;
-        if (!c->d_bnd_emask) HIPCHK(dev_malloc(&c->d_bnd_emask, n_tris));
+    if (c->tgt.surface) {
+        const size_t n_tris = (size_t)c->tgt.n_tris;
+        if (!c->tgt.d_bnd_emask) HIPCHK(dev_malloc(&c->tgt.d_bnd_emask, n_tris));
         if ((rc = ensure_corner_rows(c))) return rc;
-        HIPCHK(hipMemsetAsync(c->d_bnd_vmask, 0, nv, c->stream));
+        HIPCHK(hipMemsetAsync(c->tgt.d_bnd_vmask, 0, nv, c->stream));
         constexpr size_t per_block = (size_t)(oa::BND_EDGES_PER_WAVE / 3) * (oa::BND_THREADS / 64);
-        hipLaunchKernelGGL(oa::k_mesh_boundary, dim3((unsigned)((n_tris + per_block - 1) / per_block)), dim3(oa::BND_THREADS), 0, c->stream, (const int *)c->d_tris,
-                           (int)n_tris, (const int *)c->d_corner_order, (const long long *)c->d_corner_row, c->d_bnd_emask, c->d_bnd_vmask);
+        hipLaunchKernelGGL(oa::k_mesh_boundary, dim3((unsigned)((n_tris + per_block - 1) / per_block)), dim3(oa::BND_THREADS), 0, c->stream, (const int *)c->tgt.d_tris,
+                           (int)n_tris, (const int *)c->tgt.d_corner_order, (const long long *)c->tgt.d_corner_row, c->tgt.d_bnd_emask, c->tgt.d_bnd_vmask);
         HIPCHK(hipGetLastError());
-        if ((rc = boundary_count(c, c->d_bnd_emask, n_tris, c->bnd_n_edges))) return rc;
+        if ((rc = boundary_count(c, c->tgt.d_bnd_emask, n_tris, c->tgt.bnd_n_edges))) return rc;
     } else {
         KnnTree tree;
         if ((rc = knn_tree(c, tree))) return rc;
         DevTmp<int32_t> d_idx;
         HIPCHK(d_idx.alloc(nv * (size_t)(k + 1)));
         if ((rc = knn_launch<false>(c, tree, k + 1, d_idx.p, nullptr, oa::KnnOrient{}, nullptr, nullptr))) return rc;
-        const unsigned blocks = (unsigned)std::max(1, std::min((c->nt + oa::BND_WPB - 1) / oa::BND_WPB, c->n_cu * 32));
-        hipLaunchKernelGGL(oa::k_cloud_boundary, dim3(blocks), dim3(oa::BND_WPB * 64), 0, c->stream, (const float *)c->d_tgt_xyz, (const float *)c->d_tgt_n,
-                           (const int32_t *)d_idx.p, c->nt, k, angle_deg * 3.14159265358979323846 / 180.0, c->d_bnd_vmask);
+        const unsigned blocks = (unsigned)std::max(1, std::min((c->tgt.nt + oa::BND_WPB - 1) / oa::BND_WPB, c->n_cu * 32));
+        hipLaunchKernelGGL(oa::k_cloud_boundary, dim3(blocks), dim3(oa::BND_WPB * 64), 0, c->stream, (const float *)c->tgt.d_tgt_xyz, (const float *)c->tgt.d_tgt_n,
+                           (const int32_t *)d_idx.p, c->tgt.nt, k, angle_deg * 3.14159265358979323846 / 180.0, c->tgt.d_bnd_vmask);
         HIPCHK(hipGetLastError());
-        c->bnd_n_edges = 0;
-        c->bnd_built_k = k; c->bnd_built_angle = angle_deg;
-        if ((rc = boundary_count(c, c->d_bnd_vmask, nv, c->bnd_n_vertices))) return rc;   // (waits: the temporaries go back behind it)
+        c->tgt.bnd_n_edges = 0;
+        c->tgt.bnd_built_k = k; c->tgt.bnd_built_angle = angle_deg;
+        if ((rc = boundary_count(c, c->tgt.d_bnd_vmask, nv, c->tgt.bnd_n_vertices))) return rc;   // (waits: the temporaries go back behind it)
     }
-    if (c->surface && (rc = boundary_count(c, c->d_bnd_vmask, nv, c->bnd_n_vertices))) return rc;
-    c->bnd_ok = true;
+    if (c->tgt.surface && (rc = boundary_count(c, c->tgt.d_bnd_vmask, nv, c->tgt.bnd_n_vertices))) return rc;
+    c->tgt.bnd_ok = true;
     c->last_bnd_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return OA_OK;
 }
@@ -5973,14 +5928,14 @@ OA_EXPORT int oa_target_boundary(oa_ctx *c, int k, double angle_deg, uint8_t *ve
 {
     if (!c) return fail(OA_E_BAD_ARG, "null context");
     OA_NOT_MULTI(c, "oa_target_boundary (single-device)");
-    if (c->nt <= 0) return fail(OA_E_STATE, "oa_target_boundary: call oa_set_target or oa_set_target_mesh first");
-    if (!c->surface && edge_mask) return fail(OA_E_BAD_ARG, "oa_target_boundary: a point-cloud target has no edges (pass edge_mask = NULL)");
+    if (c->tgt.nt <= 0) return fail(OA_E_STATE, "oa_target_boundary: call oa_set_target or oa_set_target_mesh first");
+    if (!c->tgt.surface && edge_mask) return fail(OA_E_BAD_ARG, "oa_target_boundary: a point-cloud target has no edges (pass edge_mask = NULL)");
     int rc = use_device(c);
     if (rc) return rc;
     if (c->loop_active) { HIPCHK(hipStreamSynchronize(c->stream)); c->loop_active = false; }   // a running sequence ends, as with oa_target_knn
     if ((rc = ensure_boundary(c, k, angle_deg))) return rc;
-    if (vertex_mask) HIPCHK(hipMemcpyAsync(vertex_mask, c->d_bnd_vmask, (size_t)c->nt, hipMemcpyDeviceToHost, c->stream));
-    if (edge_mask) HIPCHK(hipMemcpyAsync(edge_mask, c->d_bnd_emask, (size_t)c->n_tris, hipMemcpyDeviceToHost, c->stream));
+    if (vertex_mask) HIPCHK(hipMemcpyAsync(vertex_mask, c->tgt.d_bnd_vmask, (size_t)c->tgt.nt, hipMemcpyDeviceToHost, c->stream));
+    if (edge_mask) HIPCHK(hipMemcpyAsync(edge_mask, c->tgt.d_bnd_emask, (size_t)c->tgt.n_tris, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return OA_OK;
 }
@@ -5989,12 +5944,12 @@ OA_EXPORT int oa_get_mesh_pseudonormals(oa_ctx *c, float *vertex_n, float *edge_
 {
     if (!c) return fail(OA_E_BAD_ARG, "null context");
     OA_ROUTE_FIRST(c, oa_get_mesh_pseudonormals(sub, vertex_n, edge_n));   // (the target is replicated: the same bits everywhere)
-    if (!c->surface || c->nt <= 0) return fail(OA_E_STATE, "oa_get_mesh_pseudonormals: no mesh target (oa_set_target_mesh)");
+    if (!c->tgt.surface || c->tgt.nt <= 0) return fail(OA_E_STATE, "oa_get_mesh_pseudonormals: no mesh target (oa_set_target_mesh)");
     int rc = use_device(c);
     if (rc) return rc;
     if ((rc = ensure_pseudonormals(c))) return rc;
-    if (vertex_n) HIPCHK(hipMemcpyAsync(vertex_n, c->d_pn_vertex, sizeof(float) * 3 * (size_t)c->nt, hipMemcpyDeviceToHost, c->stream));
-    if (edge_n) HIPCHK(hipMemcpyAsync(edge_n, c->d_pn_edge, sizeof(float) * 9 * (size_t)c->n_tris, hipMemcpyDeviceToHost, c->stream));
+    if (vertex_n) HIPCHK(hipMemcpyAsync(vertex_n, c->tgt.d_pn_vertex, sizeof(float) * 3 * (size_t)c->tgt.nt, hipMemcpyDeviceToHost, c->stream));
+    if (edge_n) HIPCHK(hipMemcpyAsync(edge_n, c->tgt.d_pn_edge, sizeof(float) * 9 * (size_t)c->tgt.n_tris, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return OA_OK;
 }
@@ -6016,8 +5971,8 @@ OA_EXPORT int oa_deviation(oa_ctx *c, const oa_deviation_settings *ds, double *s
     if (rc) return rc;
     int sign_mode = oa::DEV_SIGN_NONE;
     if (ds->signed_mode != 0) {
-        if (c->surface) sign_mode = oa::DEV_SIGN_MESH;
-        else if (c->d_tgt_n) sign_mode = oa::DEV_SIGN_VERTEX;
+        if (c->tgt.surface) sign_mode = oa::DEV_SIGN_MESH;
+        else if (c->tgt.d_tgt_n) sign_mode = oa::DEV_SIGN_VERTEX;
         else if (ds->signed_mode == 1)
             return fail(OA_E_STATE, "oa_deviation: signed distances to a point-cloud target need its normals (oa_set_target_normals, oa_set_normals or an estimate)");
     }
@@ -6027,9 +5982,9 @@ OA_EXPORT int oa_deviation(oa_ctx *c, const oa_deviation_settings *ds, double *s
     if ((rc = ensure_events(c, 1))) return rc;
     oa_deviation_report r;
     memset(&r, 0, sizeof r);
-    r.n = c->ns;
+    r.n = c->src.ns;
     r.max_index = -1;
-    r.surface = c->surface ? 1 : 0;
+    r.surface = c->tgt.surface ? 1 : 0;
     r.signed_used = sign_mode;
     r.n_quantiles = ds->n_quantiles;
     const double nan = std::nan("");
@@ -6038,15 +5993,15 @@ OA_EXPORT int oa_deviation(oa_ctx *c, const oa_deviation_settings *ds, double *s
     const bool with_hist = hist && ds->n_bins > 0;
     if (with_hist) for (int b = 0; b < ds->n_bins + 2; ++b) hist[b] = 0;
     if (sign_mode == oa::DEV_SIGN_MESH) {
-        const bool built = c->pn_ok;
+        const bool built = c->tgt.pn_ok;
         if ((rc = ensure_pseudonormals(c))) return rc;
         if (!built) r.pseudonormal_ms = c->last_pn_ms;
     }
     // the device state as oa_nn_search stages it (no search radius: every slot gets its nearest primitive); a running sequence ends
     if ((rc = push_state_for_oneshot(c, 1.0, false))) return rc;
-    if (c->ns <= 0) { r.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); if (rep) *rep = r; return OA_OK; }
-    const size_t ns = (size_t)c->ns;
-    const int n_rows = (c->ns_pad + oa::DEV_THREADS - 1) / oa::DEV_THREADS, nq = ds->n_quantiles;
+    if (c->src.ns <= 0) { r.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); if (rep) *rep = r; return OA_OK; }
+    const size_t ns = (size_t)c->src.ns;
+    const int n_rows = (c->src.ns_pad + oa::DEV_THREADS - 1) / oa::DEV_THREADS, nq = ds->n_quantiles;
     DevTmp<long long> d_idx;
     DevTmp<float> d_closest;
     DevTmp<double> d_dist, d_signed;
@@ -6080,18 +6035,18 @@ OA_EXPORT int oa_deviation(oa_ctx *c, const oa_deviation_settings *ds, double *s
     if ((rc = launch_nn(c, choose_search(c), false))) return rc;
     HIPCHK(hipEventRecord(c->ev[1], c->stream));
     const oa::DevOut out{ d_idx.p, d_closest.p, d_dist.p, d_signed.p, d_feature.p };
-    hipLaunchKernelGGL(oa::k_deviation, dim3((unsigned)n_rows), dim3(oa::DEV_THREADS), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->d_src4,
-                       c->ns, c->ns_pad, (const float *)c->d_tgt_xyz, c->d_keys, c->surface ? (const float4 *)nullptr : (const float4 *)c->d_win,
-                       c->surface ? (const float4 *)c->d_tri9 : (const float4 *)nullptr, ds->thresh, sign_mode, (const int *)c->d_tris,
-                       (const double *)c->d_pn_face, (const float *)c->d_pn_vertex, (const float *)c->d_pn_edge, (const float *)c->d_tgt_n,
-                       (const int *)c->d_perm, out, d_dkeys.p, hg, with_hist ? d_hist.p : (unsigned long long *)nullptr, d_rows.p);
+    hipLaunchKernelGGL(oa::k_deviation, dim3((unsigned)n_rows), dim3(oa::DEV_THREADS), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->src.d_src4,
+                       c->src.ns, c->src.ns_pad, (const float *)c->tgt.d_tgt_xyz, c->src.d_keys, c->tgt.surface ? (const float4 *)nullptr : (const float4 *)c->src.d_win,
+                       c->tgt.surface ? (const float4 *)c->tgt.d_tri9 : (const float4 *)nullptr, ds->thresh, sign_mode, (const int *)c->tgt.d_tris,
+                       (const double *)c->tgt.d_pn_face, (const float *)c->tgt.d_pn_vertex, (const float *)c->tgt.d_pn_edge, (const float *)c->tgt.d_tgt_n,
+                       (const int *)c->src.d_perm, out, d_dkeys.p, hg, with_hist ? d_hist.p : (unsigned long long *)nullptr, d_rows.p);
     hipLaunchKernelGGL(oa::k_dev_finish, dim3(1), dim3(oa::DEV_FIN_THREADS), 0, c->stream, (const oa::DevRow *)d_rows.p, n_rows, d_rows.p + n_rows);
     HIPCHK(hipGetLastError());
     if (nq > 0) {
-        const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
+        const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->src.ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
         for (int level = 0; level < oa::SEL_LEVELS; ++level) {
             hipLaunchKernelGGL(oa::k_dev_select_hist, dim3(hist_blocks, (unsigned)nq), dim3(oa::SEL_THREADS), 0, c->stream, (const oa::DevSelect *)d_sel.p,
-                               (const uint32_t *)d_dkeys.p, c->ns, level, d_qhist.p);
+                               (const uint32_t *)d_dkeys.p, c->src.ns, level, d_qhist.p);
             hipLaunchKernelGGL(oa::k_dev_select_scan, dim3((unsigned)nq), dim3(oa::SEL_THREADS), 0, c->stream, d_sel.p, (const uint32_t *)d_qhist.p, level);
         }
         HIPCHK(hipGetLastError());
