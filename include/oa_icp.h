@@ -514,6 +514,20 @@ int oa_reset_seeds(oa_ctx *ctx);
 #define OA_STAT_TARGET_BOUNDARY 46   /* 1 when the boundary masks are built for the current target */
 #define OA_STAT_BOUNDARY_VERTICES 47 /* flagged vertices of the built masks (0 when not built) */
 #define OA_STAT_BOUNDARY_EDGES  48   /* boundary edges of the built masks (0 for a cloud, or when not built) */
+#define OA_STAT_ACC_PATH       49   /* which pair accumulation the last step (loop, oa_iterate, oa_iter_partial, oa_make_pairs) launched, OA_ACC_* below; 0 before
+                                      * the first step.  A host integer written where the launch is decided: no device read.  First device */
+#define OA_STAT_ACC_ROWS       50   /* rows of per-workgroup partials the last step's reduce launch was given (DUAL: the grid's rows; the tree's
+                                      * are chosen on the device); 0 before the first step.  First device */
+#define OA_ACC_CANON            1   /* k_pair_accumulate_canon behind a search: one thread per (slot, lane of the query) */
+#define OA_ACC_STRIDE           2   /* the grid-stride k_pair_accumulate */
+#define OA_ACC_WEIGHTED         3   /* k_pair_accumulate_weighted */
+#define OA_ACC_PLANE            4   /* k_pair_accumulate_plane */
+#define OA_ACC_GICP             5   /* k_pair_accumulate_gicp */
+#define OA_ACC_FUSED_GRID       6   /* the epilogue of the vertex grid search */
+#define OA_ACC_FUSED_TRI_GRID   7   /* the epilogue of the triangle grid search */
+#define OA_ACC_FUSED_TREE       8   /* the epilogue of the whole-shard tree search, vertex target */
+#define OA_ACC_FUSED_TRI_TREE   9   /* ... mesh target */
+#define OA_ACC_DUAL            10   /* tree and grid searches both enqueued, both accumulate; DevState::tree_turn picks on the device */
 #define OA_STAT_ENQUEUED_CHILD  1000  /* + i: the same count for child i alone */
 int oa_get_stat(oa_ctx *ctx, int what, double *value);
 /* why the exchange is what it is (AUTO's reason for not taking RCCL, librccl's error, "RCCL was aborted: ..."), or "" */

@@ -55,6 +55,10 @@ OA_STAT_BOUNDARY_REJECTED = 45
 OA_STAT_TARGET_BOUNDARY = 46
 OA_STAT_BOUNDARY_VERTICES = 47
 OA_STAT_BOUNDARY_EDGES = 48
+OA_STAT_ACC_PATH = 49
+OA_STAT_ACC_ROWS = 50
+(OA_ACC_CANON, OA_ACC_STRIDE, OA_ACC_WEIGHTED, OA_ACC_PLANE, OA_ACC_GICP, OA_ACC_FUSED_GRID, OA_ACC_FUSED_TRI_GRID, OA_ACC_FUSED_TREE,
+ OA_ACC_FUSED_TRI_TREE, OA_ACC_DUAL) = range(1, 11)
 
 # every symbol include/oa_icp.h declares (tests check that the library exports all of them)
 SYMBOLS = [

@@ -497,6 +497,7 @@ struct oa_ctx {
     int iter_enq = 0;                       // iterations enqueued since the loop began
     int fast_iters = 0;                     // ... of which the grid search finished its own leftovers and accumulated (OA_STAT_FAST_ITERATIONS)
     bool fast_prev = false;                 // what the last iteration's grid search did
+    int last_acc_path = 0, last_acc_rows = 0;   // OA_STAT_ACC_PATH / _ROWS: the last step's accumulation (OA_ACC_*) and the reduce launch's first row count
     int last_todo_wave_max = -1;            // most queries one wave handed over in the last iteration the host heard of (-1: unknown)
     // timing
     std::vector<hipEvent_t> ev;
@@ -1337,7 +1338,9 @@ int launch_accumulate_as(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
     float4 *win = c->tgt.surface ? (float4 *)nullptr : c->src.d_win;
     const float4 *tri9 = c->tgt.surface ? (const float4 *)c->tgt.d_tri9 : (const float4 *)nullptr;
     const float *plane_tn = c->tgt.surface ? (const float *)nullptr : (const float *)c->tgt.d_tgt_n;
-    auto launch = [&](auto *kern, int blocks, int threads, const auto &... tail) {
+    // path: OA_ACC_* of the arm, for OA_STAT_ACC_PATH / _ROWS (one row of partials per workgroup)
+    auto launch = [&](int path, auto *kern, int blocks, int threads, const auto &... tail) {
+        c->last_acc_path = path; c->last_acc_rows = blocks;
         hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3((unsigned)threads), 0, c->stream, (const oa::DevState *)c->d_state,
                            (const float4 *)c->src.d_src4, c->src.ns, (const float *)c->tgt.d_tgt_xyz, c->src.d_keys, c->src.d_prev, win, tri9, nrm, tail...);
     };
@@ -1347,21 +1350,21 @@ int launch_accumulate_as(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
     const float *w_slot = c->src.d_w;
     if (emit) {
         po.valid = c->src.d_valid; po.b = c->src.d_b; po.dist = c->src.d_dist; po.nn_idx = nn_idx; po.nn_d2 = nn_d2; po.perm = c->src.d_perm;
-        launch(oa::k_pair_accumulate<true, RECIP>, c->acc_blocks, oa::ACC_THREADS, c->d_partials, po, (unsigned long long *)nullptr);
+        launch(OA_ACC_STRIDE, oa::k_pair_accumulate<true, RECIP>, c->acc_blocks, oa::ACC_THREADS, c->d_partials, po, (unsigned long long *)nullptr);
     } else if (c->metric == OA_METRIC_PLANE) {
         auto *kern = weighted(c) ? oa::k_pair_accumulate_plane<true, RECIP> : oa::k_pair_accumulate_plane<false, RECIP>;
-        launch(kern, plane_blocks(c), plane_threads(c), plane_tn, w_slot, c->d_partials, stamp_w);
+        launch(OA_ACC_PLANE, kern, plane_blocks(c), plane_threads(c), plane_tn, w_slot, c->d_partials, stamp_w);
     } else if (c->metric == OA_METRIC_GICP) {
         // (begin_loop refuses an estimated scale under this metric: the search always ends here)
         auto *kern = weighted(c) ? oa::k_pair_accumulate_gicp<true, RECIP> : oa::k_pair_accumulate_gicp<false, RECIP>;
-        launch(kern, plane_blocks(c), plane_threads(c), plane_tn, (const float *)c->src.d_src_n, w_slot, c->d_partials, stamp);
+        launch(OA_ACC_GICP, kern, plane_blocks(c), plane_threads(c), plane_tn, (const float *)c->src.d_src_n, w_slot, c->d_partials, stamp);
     } else if (weighted(c)) {
         static_assert(oa::WEIGHTED_THREADS == oa::PLANE_THREADS, "plane_threads / plane_blocks size both launches");
-        launch(oa::k_pair_accumulate_weighted<RECIP>, plane_blocks(c), plane_threads(c), w_slot, c->d_partials, stamp_w);
+        launch(OA_ACC_WEIGHTED, oa::k_pair_accumulate_weighted<RECIP>, plane_blocks(c), plane_threads(c), w_slot, c->d_partials, stamp_w);
     } else if (canon_blocks(c) > 0) {
-        launch(oa::k_pair_accumulate_canon<RECIP>, canon_blocks(c), canon_threads(c), canon_lanes(c), c->d_partials, stamp);
+        launch(OA_ACC_CANON, oa::k_pair_accumulate_canon<RECIP>, canon_blocks(c), canon_threads(c), canon_lanes(c), c->d_partials, stamp);
     } else {
-        launch(oa::k_pair_accumulate<false, RECIP>, c->acc_blocks, oa::ACC_THREADS, c->d_partials, po, stamp);
+        launch(OA_ACC_STRIDE, oa::k_pair_accumulate<false, RECIP>, c->acc_blocks, oa::ACC_THREADS, c->d_partials, po, stamp);
     }
     HIPCHK(hipGetLastError());
     return OA_OK;
@@ -1496,6 +1499,9 @@ int launch_search_accumulate(oa_ctx *c, bool timed, oa::RowSel &sel, bool &fused
     const int tree_rows = (int)bvh_blocks(c, false, true);
     if (s.plan == PLAN_TREE) sel = oa::RowSel{ tree_rows, 0, 0 };
     else sel = oa::RowSel{ canon_blocks(c), s.plan == PLAN_DUAL ? tree_rows : 0, s.plan == PLAN_DUAL ? 1 : 0 };
+    c->last_acc_path = s.plan == PLAN_TREE ? (c->tgt.surface ? OA_ACC_FUSED_TRI_TREE : OA_ACC_FUSED_TREE)
+                       : s.plan == PLAN_DUAL ? OA_ACC_DUAL : (c->tgt.surface ? OA_ACC_FUSED_TRI_GRID : OA_ACC_FUSED_GRID);
+    c->last_acc_rows = sel.n;
     return OA_OK;
 }
 
@@ -4249,6 +4255,8 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
         *value = (double)brute_kernel(c);
         return OA_OK;
     case OA_STAT_FAST_ITERATIONS: *value = (double)c->fast_iters; return OA_OK;
+    case OA_STAT_ACC_PATH: *value = (double)c->last_acc_path; return OA_OK;
+    case OA_STAT_ACC_ROWS: *value = (double)c->last_acc_rows; return OA_OK;
     case OA_STAT_HANDOVER_ENTRIES: *value = c->h_poll ? (double)c->h_poll[2] : 0.0; return OA_OK;
     case OA_STAT_HANDOVER_WAVE_MAX: *value = c->h_poll ? (double)c->h_poll[3] : 0.0; return OA_OK;
     case OA_STAT_SAFE_RADII: *value = (c->tune.grid_safe && c->tgt.safe_ok) ? 1.0 : 0.0; return OA_OK;

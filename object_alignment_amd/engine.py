@@ -421,7 +421,8 @@ class IcpEngine:
              "target_features": 35, "mesh_pseudonormals": 36,
              "reciprocal": 37, "reciprocal_ratio": 38, "recip_rejected": 39,
              "trim": 40, "trim_candidates": 41, "trim_kept": 42, "trim_cut": 43,
-             "reject_boundary": 44, "boundary_rejected": 45, "target_boundary": 46, "boundary_vertices": 47, "boundary_edges": 48}
+             "reject_boundary": 44, "boundary_rejected": 45, "target_boundary": 46, "boundary_vertices": 47, "boundary_edges": 48,
+             "acc_path": 49, "acc_rows": 50}
     EXCHANGE_NAMES = {-1: None, 0: "mailbox (pinned host memory)", 1: "rccl", 2: "mailbox (peer-mapped device memory)"}
 
     def exchange_info(self):
