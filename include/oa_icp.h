@@ -212,6 +212,7 @@ int oa_set_normals(oa_ctx *ctx, const float *src_normals, int64_t n_verts, const
 #define OA_METRIC_POINT 0   /* default: Besl-McKay, today's loop */
 #define OA_METRIC_PLANE 1   /* Chen-Medioni */
 #define OA_METRIC_GICP  2   /* plane-to-plane (Generalized-ICP: Segal, Haehnel, Thrun 2009), see oa_set_gicp */
+#define OA_METRIC_SYMMETRIC 3   /* symmetric point-to-plane (Rusinkiewicz 2019): the rotation split between both sides, see below */
 int oa_set_metric(oa_ctx *ctx, int metric);
 /* OA_METRIC_GICP: every pair is weighted by a 3 x 3 matrix built from the local surface of BOTH sides.  For a
  * pair that passes the point metric's tests (thresh, the normal-angle test when it is on), with a', b' the pair about the
@@ -238,6 +239,30 @@ int oa_set_metric(oa_ctx *ctx, int metric);
  * oa_set_gicp: epsilon must be finite and in [1e-6, 1], else OA_E_BAD_ARG; default 1e-3 (the paper's).  It survives uploads and
  * oa_set_matrices; changing it ends a running oa_iterate sequence, as oa_set_metric does. */
 int oa_set_gicp(oa_ctx *ctx, double epsilon);
+/* OA_METRIC_SYMMETRIC: the symmetric objective (Rusinkiewicz, "A Symmetric Objective Function for ICP", SIGGRAPH 2019;
+ * DESIGN.md 3.20).  It uses the two normals of OA_METRIC_GICP, has no parameter, and its row is rank one: the plane metric's
+ * 32-double row, 6 x 6 minimum-norm solve (OA_STAT_PLANE_RANK) and everything after the step's matrix serve it.  A pair takes
+ * part if it passes the point metric's tests (thresh, the normal-angle test when it is on, the reciprocal / trim verdict).  With
+ * a', b' the pair about the context's pivot exactly as under OA_METRIC_PLANE, n_b the correspondence's unit normal exactly as
+ * under OA_METRIC_PLANE, and n_a the source vertex's normal normalised as under OA_METRIC_GICP (n * (1 / sqrt((x x + y y) + z z));
+ * a source normal of zero or non-finite length drops the pair from the step and from K):
+ *   s = (n_a . n_b < 0) ? -1 : +1                 (left-to-right sum; an exact 0 counts as +1)
+ *   n = (n_b + s n_a) / 2                         |n|^2 = (1 + |cos|) / 2 in [1/2, 1]: never zero, never dropped
+ *   r = n . (a' - b'),   J = [ (a' + b') x n , n ],   step x = (a~, t~) minimises sum w (r + J . x)^2
+ *   theta = atan(|a~|),  R = exp(theta [a~ / |a~|]x),  t = t~ cos(theta)          (|a~| = 0: R = I, t = t~)
+ *   M = T(c) R T(t) R T(-c)                       c the pivot: half the rotation before the translation, half after
+ *   - r is exactly zero for a pair on a patch of constant curvature, whatever the rotation between the two sides; the plane
+ *     metric's error is first order in that rotation.
+ *   - Flipping the sign of any n_a leaves n the same bits.  Flipping any n_b flips n, J and r together, so every term of
+ *     sum J J^T and sum J r keeps its bits: the signs of estimated, unoriented normals do not matter.
+ *   - For agreeing normals |n| = 1 and r is the plane metric's distance in the plane metric's units: res_scale, oa_set_robust's
+ *     scale and the sum of r^2 mean what they mean under OA_METRIC_PLANE.  Weighted: w = w_vertex psi(res_scale |r|).
+ *   - oa_set_trim (fixed and estimated share) and oa_set_robust_auto work under this metric, on the key res_scale |r|.
+ * Under OA_METRIC_SYMMETRIC, when a loop starts: with_scale != 0: OA_E_BAD_ARG; a vertex-mode target without normals, or a
+ * source without normals (oa_set_source_normals / oa_set_normals): OA_E_STATE; a shard of more than 8 388 608 points:
+ * OA_E_CAPACITY; multi-device contexts and the split-phase calls: OA_E_STATE, as under OA_METRIC_PLANE.  Each refusal leaves the
+ * context usable.  OA_STAT_ACC_PATH reports OA_ACC_PLANE (the plane kernel's row and epilogue).  oa_make_pairs, oa_nn_search,
+ * oa_kabsch*, oa_point_to_plane, oa_symmetric_step, oa_coarse_align do not look at the metric. */
 /* per-vertex source normals (align-local, n_verts x 3 float32, host; n_verts as given to oa_set_source) for OA_METRIC_GICP,
  * without switching the normal-angle test on: the counterpart of oa_set_target_normals.  The array is the one oa_set_normals
  * fills and the normal-angle test reads -- either call overwrites it, switching the test off keeps it, a new source upload
@@ -490,8 +515,8 @@ int oa_reset_seeds(oa_ctx *ctx);
                                        * workgroup dispatched mid-launch); 0 when that kernel did not run.  Multi-device context: its first device */
 #define OA_STAT_BRUTE_QUEUE_WGS     27   /* workgroups of the last k_nn_search_sorted launch that took their (split, block) items off the work
                                        * queue (long launches: as many as the chip holds); 0 = one workgroup per item, in launch order */
-#define OA_STAT_METRIC          28   /* OA_METRIC_POINT / OA_METRIC_PLANE / OA_METRIC_GICP */
-#define OA_STAT_PLANE_RANK      29   /* eigenvalues the last plane solve kept (6 = fully determined); loop or oa_point_to_plane */
+#define OA_STAT_METRIC          28   /* OA_METRIC_POINT / OA_METRIC_PLANE / OA_METRIC_GICP / OA_METRIC_SYMMETRIC */
+#define OA_STAT_PLANE_RANK      29   /* eigenvalues the last plane solve kept (6 = fully determined); loop, oa_point_to_plane or oa_symmetric_step */
 #define OA_STAT_ROBUST_LOSS     30   /* OA_LOSS_* */
 #define OA_STAT_WEIGHT_SUM      31   /* sum w of the last step (loop or iterate); K when weighting is off */
 #define OA_STAT_ROBUST_SCALE    32   /* the c the last step used: oa_set_robust's scale, or c_i of oa_set_robust_auto; 0 with OA_LOSS_NONE */
@@ -521,7 +546,7 @@ int oa_reset_seeds(oa_ctx *ctx);
 #define OA_ACC_CANON            1   /* k_pair_accumulate_canon behind a search: one thread per (slot, lane of the query) */
 #define OA_ACC_STRIDE           2   /* the grid-stride k_pair_accumulate */
 #define OA_ACC_WEIGHTED         3   /* k_pair_accumulate_weighted */
-#define OA_ACC_PLANE            4   /* k_pair_accumulate_plane */
+#define OA_ACC_PLANE            4   /* k_pair_accumulate_plane; OA_METRIC_SYMMETRIC: its sibling k_pair_accumulate_symm (the same row and epilogue) */
 #define OA_ACC_GICP             5   /* k_pair_accumulate_gicp */
 #define OA_ACC_FUSED_GRID       6   /* the epilogue of the vertex grid search */
 #define OA_ACC_FUSED_TRI_GRID   7   /* the epilogue of the triangle grid search */
@@ -567,6 +592,11 @@ int oa_get_pivot(oa_ctx *ctx, double pivot[3]);
  * system depends on the frame of (omega, t), so the pivot is part of the contract.  M maps A towards B's tangent planes
  * (the M of oa_kabsch's convention).  K < 3: OA_E_TOO_FEW_PAIRS.  Does not look at the context's metric. */
 int oa_point_to_plane(oa_ctx *ctx, const double *A, const double *B, const double *N, int64_t K, int64_t ld, double M[16]);
+/* the symmetric step (OA_METRIC_SYMMETRIC's) from caller-supplied pairs: A, B, NA, NB are 3 x K row-major doubles, leading
+ * dimension ld; NA (the normals at A) and NB (at B) need not be unit -- they are normalised as the loop normalises its own, and
+ * a pair with a normal of zero or non-finite length on either side is left out.  Pivot c = A's first column.  K < 3 (or fewer
+ * than 3 usable pairs): OA_E_TOO_FEW_PAIRS.  Sets OA_STAT_PLANE_RANK.  Does not look at the context's metric. */
+int oa_symmetric_step(oa_ctx *ctx, const double *A, const double *B, const double *NA, const double *NB, int64_t K, int64_t ld, double M[16]);
 
 /* ---- fused fast path: the operator loop (operators/icp_align.py:91-151) ----------------------- */
 /* one iteration, synchronous (the modal operator's per-tick step, icp_align_feedback.py:250-288):

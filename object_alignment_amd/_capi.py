@@ -30,6 +30,7 @@ OA_NSUMS = 24
 OA_METRIC_POINT = 0
 OA_METRIC_PLANE = 1
 OA_METRIC_GICP = 2
+OA_METRIC_SYMMETRIC = 3
 OA_LOSS_NONE = 0
 OA_LOSS_HUBER = 1
 OA_LOSS_TUKEY = 2
@@ -75,6 +76,7 @@ SYMBOLS = [
     "oa_score_poses", "oa_coarse_candidates", "oa_coarse_align",
     "oa_target_knn", "oa_estimate_target_normals",
     "oa_set_gicp", "oa_set_source_normals",
+    "oa_symmetric_step",
     "oa_coarse_align_poses", "oa_target_fpfh", "oa_match_features", "oa_feature_candidates",
     "oa_voxel_downsample",
     "oa_deviation", "oa_get_mesh_pseudonormals",
@@ -218,6 +220,7 @@ def load(experiments: bool = False):
     L.oa_set_gicp.argtypes = [vp, C.c_double]
     L.oa_set_source_normals.argtypes = [vp, fp, C.c_int64]
     L.oa_point_to_plane.argtypes = [vp, dp, dp, dp, C.c_int64, C.c_int64, dp]
+    L.oa_symmetric_step.argtypes = [vp, dp, dp, dp, dp, C.c_int64, C.c_int64, dp]
     L.oa_set_robust.argtypes = [vp, C.c_int, C.c_double]
     L.oa_set_source_weights.argtypes = [vp, fp, C.c_int64]
     L.oa_set_robust_auto.argtypes = [vp, C.c_double, C.c_double]

@@ -104,11 +104,13 @@
 // ---- the reciprocal check: one wave per slot through the source's box tree (oa_recip.hpp): oa_fam_recip.hip -----------
 #define OA_FAMILY_RECIP(X) OA_K(X, k_recip_check, OA_SIG_RECIP_CHECK, false) OA_K(X, k_recip_check, OA_SIG_RECIP_CHECK, true)
 
-// ---- Trimmed ICP: the GICP instance of the residual keys (oa_trim.hpp): oa_fam_trim.hip --------------------------------
+// ---- Trimmed ICP: the GICP and symmetric instances of the residual keys (oa_trim.hpp): oa_fam_trim.hip -----------------
 #define OA_SIG_RKEYS_GICP(TEST) const DevState *, const float4 *, int, const float *, const unsigned long long *, const float4 *, const float4 *, TEST, const float *, const float *, const float *, uint32_t *, uint32_t *, unsigned long long *
-// (RECIP = true alone: the trim always hands the verdict bytes over -- all ones unless k_recip_check wrote them)
+// (GICP: RECIP = true alone -- the trim always hands the verdict bytes over, all ones unless k_recip_check wrote them; the
+//  symmetric metric also serves oa_set_robust_auto, which runs without them: both)
 #define OA_FAMILY_TRIM(X)                                                                                               \
-    OA_K(X, k_residual_keys_gicp, OA_SIG_RKEYS_GICP(NormalTestRecip), true)
+    OA_K(X, k_residual_keys_gicp, OA_SIG_RKEYS_GICP(NormalTestRecip), true)                                             \
+    OA_K(X, k_residual_keys_symm, OA_SIG_RKEYS_GICP(NormalTest), false) OA_K(X, k_residual_keys_symm, OA_SIG_RKEYS_GICP(NormalTestRecip), true)
 
 // ---- experiments (OA_EXPERIMENTS only): oa_fam_exp.hip --------------------------------------------------------------
 #define OA_FAMILY_EXP(X)                                                                                                \

@@ -1074,8 +1074,8 @@ struct SearchChoice {
 };
 // a loss or per-vertex weights are set: the loop's pairs carry weights (weighted kernels, the PLAIN plan)
 inline bool weighted(const oa_ctx *c) { return c->loss != OA_LOSS_NONE || c->src.d_w != nullptr; }
-// the metrics that sum the wide row (NSUMS_PLANE) and take the 6 x 6 solve: point-to-plane and plane-to-plane (GICP)
-inline bool plane_row_metric(const oa_ctx *c) { return c->metric == OA_METRIC_PLANE || c->metric == OA_METRIC_GICP; }
+// the metrics that sum the wide row (NSUMS_PLANE) and take the 6 x 6 solve: point-to-plane, plane-to-plane (GICP) and symmetric
+inline bool plane_row_metric(const oa_ctx *c) { return c->metric == OA_METRIC_PLANE || c->metric == OA_METRIC_GICP || c->metric == OA_METRIC_SYMMETRIC; }
 // ... and the loss takes its scale from the step's own residuals (oa_set_robust_auto; inert without a loss)
 inline bool auto_scale(const oa_ctx *c) { return c->loss != OA_LOSS_NONE && c->robust_p > 0.0; }
 
@@ -1093,7 +1093,7 @@ SearchChoice choose_search(const oa_ctx *c)
         s.settle_front = c->tgt.surface && c->tgt.tri_fine_ok && c->seeded && !s.dual;
         s.accept_front = c->tgt.surface && c->tune.tri_split && c->seeded && !s.dual;
     }
-    // (the plane and GICP metrics have no accumulating search epilogue: search, then k_pair_accumulate_plane / _gicp -- as with
+    // (the plane, GICP and symmetric metrics have no accumulating search epilogue: search, then k_pair_accumulate_plane / _gicp / _symm -- as with
     //  fused_acc off; nor does a weighted step: no search epilogue knows about weights -- nor about the reciprocal check or the trim)
     if (!c->tune.fused_acc || !c->loop_active || c->src.ns <= 0 || plane_row_metric(c) || weighted(c) || verdict_on(c)) return s;
     // (the accumulating tree search needs twice the registers of the plain one: worth it while the shard is small enough
@@ -1358,6 +1358,10 @@ int launch_accumulate_as(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
         // (begin_loop refuses an estimated scale under this metric: the search always ends here)
         auto *kern = weighted(c) ? oa::k_pair_accumulate_gicp<true, RECIP> : oa::k_pair_accumulate_gicp<false, RECIP>;
         launch(OA_ACC_GICP, kern, plane_blocks(c), plane_threads(c), plane_tn, (const float *)c->src.d_src_n, w_slot, c->d_partials, stamp);
+    } else if (c->metric == OA_METRIC_SYMMETRIC) {
+        // (the plane kernel's row and epilogue: OA_ACC_PLANE)
+        auto *kern = weighted(c) ? oa::k_pair_accumulate_symm<true, RECIP> : oa::k_pair_accumulate_symm<false, RECIP>;
+        launch(OA_ACC_PLANE, kern, plane_blocks(c), plane_threads(c), plane_tn, (const float *)c->src.d_src_n, w_slot, c->d_partials, stamp_w);
     } else if (weighted(c)) {
         static_assert(oa::WEIGHTED_THREADS == oa::PLANE_THREADS, "plane_threads / plane_blocks size both launches");
         launch(OA_ACC_WEIGHTED, oa::k_pair_accumulate_weighted<RECIP>, plane_blocks(c), plane_threads(c), w_slot, c->d_partials, stamp_w);
@@ -1376,7 +1380,7 @@ int launch_accumulate(oa_ctx *c, bool emit, int *nn_idx, float *nn_d2)
 
 // oa_set_robust_auto: between the search and the weighted accumulation of a loop step, the loss's scale from the residuals of
 // the pairs that accumulation is about to form -- six launches, all on the loop's stream (oa_kernels.hpp, k_residual_keys)
-// metric: whose residual (OA_METRIC_*; GICP: the trim's alone); hist: the level-0 counts of the select that follows
+// metric: whose residual (OA_METRIC_*; GICP: the trim's alone; symmetric: either's); hist: the level-0 counts of the select that follows
 template <bool RECIP>
 void launch_residual_keys(oa_ctx *c, int metric, uint32_t *hist)
 {
@@ -1390,6 +1394,7 @@ void launch_residual_keys(oa_ctx *c, int metric, uint32_t *hist)
                            &c->d_state->t_acc_start);
     };
     if constexpr (RECIP) { if (metric == OA_METRIC_GICP) { launch(oa::k_residual_keys_gicp<true>, (const float *)c->src.d_src_n); return; } }
+    if (metric == OA_METRIC_SYMMETRIC) { launch(oa::k_residual_keys_symm<RECIP>, (const float *)c->src.d_src_n); return; }
     if (metric == OA_METRIC_PLANE) launch(oa::k_residual_keys<true, RECIP>); else launch(oa::k_residual_keys<false, RECIP>);
 }
 int launch_robust_scale(oa_ctx *c)
@@ -1615,6 +1620,8 @@ void init_loop_state(oa_ctx *c, const oa_settings *st, int iters, bool cutoff = 
     }
     s.weight_sum = 0.0;
     s.gicp_eps = c->gicp_eps;
+    s.symmetric = c->metric == OA_METRIC_SYMMETRIC ? 1 : 0;
+    s.pad4 = 0;
     // the scale from the residuals: robust_c is then the multiplier, and k_select_scan writes the scale before every accumulation
     const bool auto_c = auto_scale(c);
     s.robust_mult = auto_c ? c->robust_c : 0.0;
@@ -1650,6 +1657,14 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
             return fail(OA_E_STATE, "the GICP metric takes a robust loss with a fixed scale only: call oa_set_robust_auto(ctx, 0, 0) (or oa_set_metric(ctx, OA_METRIC_PLANE))");
         if ((long long)c->src.ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
             return fail(OA_E_CAPACITY, "the GICP metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->src.ns);
+    } else if (c->metric == OA_METRIC_SYMMETRIC) {
+        if (st->with_scale) return fail(OA_E_BAD_ARG, "the symmetric metric solves for a rigid step: with_scale must be 0 (or call oa_set_metric(ctx, OA_METRIC_POINT))");
+        if (!c->tgt.surface && !c->tgt.d_tgt_n)
+            return fail(OA_E_STATE, "the symmetric metric needs target normals: call oa_set_target_normals (or oa_set_normals) after oa_set_target, or upload a mesh with oa_set_target_mesh");
+        if (!c->src.d_src_n)
+            return fail(OA_E_STATE, "the symmetric metric needs source normals: call oa_set_source_normals (or oa_set_normals) after oa_set_source");
+        if ((long long)c->src.ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
+            return fail(OA_E_CAPACITY, "the symmetric metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->src.ns);
     } else if (weighted(c) && (long long)c->src.ns > (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS)
         return fail(OA_E_CAPACITY, "a weighted loop takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS, c->src.ns);
     if ((rc = refuse_recip_shard(c, "a loop"))) return rc;
@@ -3844,8 +3859,8 @@ OA_EXPORT int oa_set_normals(oa_ctx *c, const float *src_normals, int64_t n_vert
 OA_EXPORT int oa_set_metric(oa_ctx *c, int metric)
 {
     if (!c) return fail(OA_E_BAD_ARG, "null context");
-    if (metric != OA_METRIC_POINT && metric != OA_METRIC_PLANE && metric != OA_METRIC_GICP)
-        return fail(OA_E_BAD_ARG, "metric %d (use OA_METRIC_POINT / OA_METRIC_PLANE / OA_METRIC_GICP)", metric);
+    if (metric != OA_METRIC_POINT && metric != OA_METRIC_PLANE && metric != OA_METRIC_GICP && metric != OA_METRIC_SYMMETRIC)
+        return fail(OA_E_BAD_ARG, "metric %d (use OA_METRIC_POINT / OA_METRIC_PLANE / OA_METRIC_GICP / OA_METRIC_SYMMETRIC)", metric);
     if (metric == c->metric) return OA_OK;
     // a changed metric ends the running sequence: the next oa_iterate starts a new one from the current matrix_world
     if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
@@ -4652,7 +4667,44 @@ OA_EXPORT int oa_point_to_plane(oa_ctx *c, const double *A, const double *B, con
     hipLaunchKernelGGL(oa::k_accumulate_pairs_plane, dim3(blocks), dim3(oa::ACC_THREADS), 0, c->stream, (const double *)dA.p, (const double *)dB.p,
                        (const double *)dN.p, (long long)K, (long long)K, pv[0], pv[1], pv[2], c->d_partials);
     hipLaunchKernelGGL(oa::k_reduce_partials_plane, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, (const double *)c->d_partials, blocks, c->d_sums);
-    hipLaunchKernelGGL(oa::k_solve_only_plane, dim3(1), dim3(64), 0, c->stream, (const double *)c->d_sums, pv[0], pv[1], pv[2], c->d_solve);
+    hipLaunchKernelGGL(oa::k_solve_only_plane, dim3(1), dim3(64), 0, c->stream, (const double *)c->d_sums, pv[0], pv[1], pv[2], 0, c->d_solve);
+    HIPCHK(hipGetLastError());
+    double out[18];
+    { int rcr = read_small(c, out, c->d_solve, sizeof out); if (rcr) return rcr; }
+    if (out[16] != 1.0) return fail(OA_E_TOO_FEW_PAIRS, "input arrays are of wrong shape or type");   // (pairs with unusable normals do not count)
+    memcpy(M, out, sizeof(double) * 16);
+    c->last_plane_rank = (int)out[17];
+    return OA_OK;
+}
+
+// the symmetric step from caller-supplied pairs (oa_point_to_plane with both sides' normals): k_accumulate_pairs_symm ->
+// k_reduce_partials_plane -> k_solve_only_plane.  Does not look at the context's metric.
+OA_EXPORT int oa_symmetric_step(oa_ctx *c, const double *A, const double *B, const double *NA, const double *NB, int64_t K, int64_t ld, double M[16])
+{
+    if (!c || !M) return fail(OA_E_BAD_ARG, "oa_symmetric_step: null argument");
+    OA_ROUTE_FIRST(c, oa_symmetric_step(sub, A, B, NA, NB, K, ld, M));
+    if (K < 3) return fail(OA_E_TOO_FEW_PAIRS, "input arrays are of wrong shape or type");   // the point metric's rule (general.py:150-157)
+    if (!A || !B || !NA || !NB || ld < K) return fail(OA_E_BAD_ARG, "oa_symmetric_step: bad arrays");
+    int rc = use_device(c);
+    if (rc) return rc;
+    if ((rc = ensure_common(c))) return rc;
+    DevTmp<double> dA, dB, dNA, dNB;
+    HIPCHK(dA.alloc(3 * (size_t)K));
+    HIPCHK(dB.alloc(3 * (size_t)K));
+    HIPCHK(dNA.alloc(3 * (size_t)K));
+    HIPCHK(dNB.alloc(3 * (size_t)K));
+    for (int a = 0; a < 3; ++a) {
+        HIPCHK(hipMemcpyAsync(dA.p + (size_t)a * K, A + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dB.p + (size_t)a * K, B + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dNA.p + (size_t)a * K, NA + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dNB.p + (size_t)a * K, NB + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
+    }
+    const double pv[3] = { A[0], A[ld], A[2 * ld] };
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(oa::ACC_MAX_BLOCKS, (K + oa::ACC_THREADS - 1) / oa::ACC_THREADS));
+    hipLaunchKernelGGL(oa::k_accumulate_pairs_symm, dim3(blocks), dim3(oa::ACC_THREADS), 0, c->stream, (const double *)dA.p, (const double *)dB.p,
+                       (const double *)dNA.p, (const double *)dNB.p, (long long)K, (long long)K, pv[0], pv[1], pv[2], c->d_partials);
+    hipLaunchKernelGGL(oa::k_reduce_partials_plane, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, (const double *)c->d_partials, blocks, c->d_sums);
+    hipLaunchKernelGGL(oa::k_solve_only_plane, dim3(1), dim3(64), 0, c->stream, (const double *)c->d_sums, pv[0], pv[1], pv[2], 1, c->d_solve);
     HIPCHK(hipGetLastError());
     double out[18];
     { int rcr = read_small(c, out, c->d_solve, sizeof out); if (rcr) return rcr; }
@@ -4757,6 +4809,7 @@ int run_begin(oa_ctx *c, const oa_settings *st)
 }
 // the exchange of the sums between devices and ranks carries OA_NSUMS doubles: the plane metric's wider row does not go through it
 const char *const GICP_ONE_DEVICE = ": the GICP metric runs on a single-device context through oa_run / oa_iterate (call oa_set_metric(ctx, OA_METRIC_POINT) for this path)";
+const char *const SYMM_ONE_DEVICE = ": the symmetric metric runs on a single-device context through oa_run / oa_iterate (call oa_set_metric(ctx, OA_METRIC_POINT) for this path)";
 const char *const PLANE_ONE_DEVICE = ": the plane metric runs on a single-device context through oa_run / oa_iterate (call oa_set_metric(ctx, OA_METRIC_POINT) for this path)";
 // ... and a quantile of the world's residuals needs the world's histogram, not OA_NSUMS doubles
 const char *const AUTO_ONE_DEVICE = ": a robust scale estimated from the residuals runs on a single-device context through oa_run / oa_iterate (call oa_set_robust_auto(ctx, 0, 0) for this path)";
@@ -4768,6 +4821,7 @@ int refuse_wide_row(const oa_ctx *c, const char *who, bool estimated_scale_too =
     if (c->bnd_on) return fail(OA_E_STATE, "%s%s", who, BND_ONE_DEVICE);
     if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "%s%s", who, PLANE_ONE_DEVICE);
     if (c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "%s%s", who, GICP_ONE_DEVICE);
+    if (c->metric == OA_METRIC_SYMMETRIC) return fail(OA_E_STATE, "%s%s", who, SYMM_ONE_DEVICE);
     if (estimated_scale_too && auto_scale(c)) return fail(OA_E_STATE, "%s%s", who, AUTO_ONE_DEVICE);
     return OA_OK;
 }

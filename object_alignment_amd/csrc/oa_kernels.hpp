@@ -133,6 +133,8 @@ struct DevState {
     uint32_t sel_rank;        // ... and the 0-based rank wanted among the keys that share them
     uint32_t pad3;
     double gicp_eps;          // GICP metric (oa_set_gicp): the covariances' small eigenvalue, C = I - (1 - eps) n n^T; set when the loop starts
+    int32_t symmetric;        // symmetric metric (OA_METRIC_SYMMETRIC): 1 = the plane solve composes its step with symm_step_matrix; set when the loop starts
+    int32_t pad4;
 };
 
 // Squared local search radius for the query p (rounded up to float).  Derivation: the pair test measures
@@ -578,11 +580,49 @@ __host__ __device__ inline void plane_step_matrix(const double x[6], const doubl
     M[12] = 0.0; M[13] = 0.0; M[14] = 0.0; M[15] = 1.0;
 }
 
+// The symmetric metric's step (Rusinkiewicz 2019), x = (a~, t~) the solution of its linear system: the rotation is split between
+// both sides, M = T(c) R T(t) R T(-c) with theta = atan(|a~|), R = exp(theta [a~ / |a~|]x), t = t~ cos(theta).  With K = [a~]x,
+// R = I + a K + b K K, a = sin(theta) / |a~|, b = (1 - cos(theta)) / |a~|^2 -- both finite as |a~| -> 0 (1 and 1/2).
+__host__ __device__ inline void symm_step_matrix(const double x[6], const double c[3], double M[16])
+{
+    const double wx = x[0], wy = x[1], wz = x[2];
+    const double a2 = (wx * wx + wy * wy) + wz * wz;
+    double ct, a, b;                                                        // cos(theta), sin(theta) / |a~|, (1 - cos(theta)) / |a~|^2
+    if (a2 < 1e-8) {                                                        // |a~| < 1e-4: the series in |a~|^2, next term |a~|^6
+        ct = 1.0 - a2 / 2.0 * (1.0 - a2 * 0.75);
+        a = ct;                                                             // (sin(atan u) / u = cos(atan u))
+        b = 0.5 - a2 * 0.375 * (1.0 - a2 / 1.2);
+    } else {
+        const double u = sqrt(a2), th = atan(u), sh = sin(0.5 * th);
+        ct = cos(th);
+        a = sin(th) / u;
+        b = 2.0 * sh * sh / a2;
+    }
+    const double d = 1.0 - b * a2;
+    double R[9], t[3], Rt[3];
+    R[0] = d + b * wx * wx;      R[1] = b * wx * wy - a * wz; R[2] = b * wx * wz + a * wy;
+    R[3] = b * wx * wy + a * wz; R[4] = d + b * wy * wy;      R[5] = b * wy * wz - a * wx;
+    R[6] = b * wx * wz - a * wy; R[7] = b * wy * wz + a * wx; R[8] = d + b * wz * wz;
+    for (int i = 0; i < 3; ++i) t[i] = x[3 + i] * ct;
+    for (int i = 0; i < 3; ++i) Rt[i] = (R[3 * i] * t[0] + R[3 * i + 1] * t[1]) + R[3 * i + 2] * t[2];
+    for (int i = 0; i < 3; ++i) {                                           // M v = c + R (t + R (v - c))
+        double tr = c[i] + Rt[i];
+        for (int j = 0; j < 3; ++j) {
+            const double r2 = (R[3 * i] * R[j] + R[3 * i + 1] * R[3 + j]) + R[3 * i + 2] * R[6 + j];
+            M[4 * i + j] = r2;
+            tr -= r2 * c[j];
+        }
+        M[4 * i + 3] = tr;
+    }
+    M[12] = 0.0; M[13] = 0.0; M[14] = 0.0; M[15] = 1.0;
+}
+
 // s: the NSUMS_PLANE sums (readable by every caller); A, V: 36 doubles of workspace each, shared by the callers (LDS on the
 // device); [k0, k1): see sym6_jacobi.  Returns false when K < 3 (OA_E_TOO_FEW_PAIRS, as the point metric); rank = the
 // eigenvalues kept (6 = the pairs determine the whole step).  Called by all lanes of one wave / by one host thread.
+// symmetric: the sums are the symmetric metric's (symm_row) and x composes through symm_step_matrix.
 __host__ __device__ inline bool plane_solve_from_sums(const double *s, const double pivot[3], double *A, double *V, int k0, int k1,
-                                                      double M[16], int &rank, bool weighted = false)
+                                                      double M[16], int &rank, bool weighted = false, bool symmetric = false)
 {
     rank = 0;
     if (!(s[P_K] >= 3.0)) return false;
@@ -607,7 +647,7 @@ __host__ __device__ inline bool plane_solve_from_sums(const double *s, const dou
 #pragma unroll
         for (int j = 0; j < 6; ++j) x[j] += f * V[6 * j + i];
     }
-    plane_step_matrix(x, pivot, M);
+    if (symmetric) symm_step_matrix(x, pivot, M); else plane_step_matrix(x, pivot, M);
     return true;
 }
 
@@ -2628,6 +2668,32 @@ __device__ __forceinline__ void plane_row(double a0, double a1, double a2, doubl
     j[3] = nx; j[4] = ny; j[5] = nz;
 }
 
+// The symmetric metric's row (OA_METRIC_SYMMETRIC; Rusinkiewicz, "A Symmetric Objective Function for ICP", 2019): plane_row's
+// shape -- rank one -- with n = (n_b + s n_a) / 2, s = the sign of n_a . n_b (left-to-right sum, an exact 0 counts as +1), and
+// the lever arm a + b.  na, nb unit.  |n|^2 = (1 + |cos|) / 2 >= 1/2: never zero.  Flipping n_a leaves n the same bits
+// (s flips with it); flipping n_b flips n, j and r together, so no product j j^T, j r moves.
+__device__ __forceinline__ void symm_row(double a0, double a1, double a2, double b0, double b1, double b2, double ax, double ay, double az,
+                                         double bx, double by, double bz, double (&j)[6], double &r)
+{
+    const double s = ((ax * bx + ay * by) + az * bz) < 0.0 ? -1.0 : 1.0;
+    const double nx = 0.5 * (bx + s * ax), ny = 0.5 * (by + s * ay), nz = 0.5 * (bz + s * az);
+    const double m0 = a0 + b0, m1 = a1 + b1, m2 = a2 + b2;
+    r = (nx * (a0 - b0) + ny * (a1 - b1)) + nz * (a2 - b2);
+    j[0] = m1 * nz - m2 * ny; j[1] = m2 * nx - m0 * nz; j[2] = m0 * ny - m1 * nx;
+    j[3] = nx; j[4] = ny; j[5] = nz;
+}
+
+// a float32 source normal (slot i of src_n) -> unit fp64 in plane_normal's order, n * (1 / sqrt(n2)); false: zero or non-finite length
+__device__ __forceinline__ bool symm_source_normal(const float *__restrict__ src_n, long long i, double &sx, double &sy, double &sz)
+{
+    const double s0 = (double)src_n[3 * i], s1 = (double)src_n[3 * i + 1], s2 = (double)src_n[3 * i + 2];
+    const double n2 = (s0 * s0 + s1 * s1) + s2 * s2;
+    if (!(n2 > 0.0) || !(n2 < INFINITY)) return false;
+    const double inv = 1.0 / sqrt(n2);
+    sx = s0 * inv; sy = s1 * inv; sz = s2 * inv;
+    return true;
+}
+
 // a pair's contribution to the row, in three slices of 12 + 12 + 8 sums (NSUMS_PLANE's layout)
 __device__ __forceinline__ void plane_terms_0(const double (&j)[6], double (&h)[12])
 {
@@ -2729,6 +2795,46 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_plane(const D
     const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
     double j[6], r;
     plane_row((double)f.p.x - pvx, (double)f.p.y - pvy, (double)f.p.z - pvz, (double)f.bx - pvx, (double)f.by - pvy, (double)f.bz - pvz, nx, ny, nz, j, r);
+    if constexpr (WEIGHTED) {
+        double w = 0.0;
+        if (valid) {
+            w = robust_psi(st->loss, st->res_scale * fabs(r), st->robust_c);
+            if (w_slot) w *= (double)w_slot[i];
+        }
+        block_store_plane<true>(valid, j, r, f.dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE, w);
+    } else
+        block_store_plane(valid, j, r, f.dist - st->d_pivot, red, partials + (long long)blockIdx.x * NSUMS_PLANE);
+}
+
+// k_pair_accumulate_plane's sibling for the symmetric metric: the same pair_fetch<true, true> and plane_normal for n_b, the slot's
+// source normal as k_pair_accumulate_gicp reads it (src_n: float32, align-local, slot order; zero or non-finite length drops the
+// pair from the step and from K), symm_row in plane_row's place, then the same block_store_plane -- the plane row's layout, reduce
+// and solve.  Launched like the plane kernel (plane_threads / plane_blocks).  WEIGHTED: w = w_vertex * psi(res_scale * |r|).
+template <bool WEIGHTED, bool RECIP = false>
+__global__ __launch_bounds__(PLANE_THREADS) void k_pair_accumulate_symm(const DevState *__restrict__ st, const float4 *__restrict__ src4,
+                                                              int ns, const float *__restrict__ tgt_xyz,
+                                                              unsigned long long *__restrict__ keys, int *__restrict__ prev,
+                                                              float4 *__restrict__ win, const float4 *__restrict__ tri9,
+                                                              PairTest<RECIP> nrm, const float *__restrict__ plane_tn,
+                                                              const float *__restrict__ src_n, const float *__restrict__ w_slot,
+                                                              double *__restrict__ partials, unsigned long long *__restrict__ t_acc_start)
+{
+    __shared__ double red[PLANE_THREADS / 64][NSUMS_PLANE];
+    if (t_acc_start && blockIdx.x == 0 && threadIdx.x == 0) *t_acc_start = wall_clock64();   // ~ the end of the search
+    if (st->halt) return;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool valid = false;
+    double nx = 0.0, ny = 0.0, nz = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+    PairFetch f = {};
+    if (i < ns) {
+        valid = pair_fetch<true, true, RECIP>(st, src4, i, tgt_xyz, keys, prev, win, tri9, nrm, plane_tn, st->thresh, f);
+        if (valid) valid = plane_normal(st, f.tn, nx, ny, nz);
+        if (valid) valid = symm_source_normal(src_n, i, sx, sy, sz);
+    }
+    const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
+    double j[6], r;
+    symm_row((double)f.p.x - pvx, (double)f.p.y - pvy, (double)f.p.z - pvz, (double)f.bx - pvx, (double)f.by - pvy, (double)f.bz - pvz,
+             sx, sy, sz, nx, ny, nz, j, r);
     if constexpr (WEIGHTED) {
         double w = 0.0;
         if (valid) {
@@ -3205,14 +3311,49 @@ __global__ __launch_bounds__(ACC_THREADS) void k_accumulate_pairs_plane(const do
     block_finish_plane(red, partials + (long long)blockIdx.x * NSUMS_PLANE);
 }
 
+// the symmetric row over explicit pairs (oa_symmetric_step): k_accumulate_pairs_plane with both sides' normals.  NA, NB need not
+// be unit; a pair with a normal of zero or non-finite length on either side is left out.
+__global__ __launch_bounds__(ACC_THREADS) void k_accumulate_pairs_symm(const double *__restrict__ A, const double *__restrict__ B,
+                                                                       const double *__restrict__ NA, const double *__restrict__ NB,
+                                                                       long long K, long long ld, double pvx, double pvy, double pvz,
+                                                                       double *__restrict__ partials)
+{
+    __shared__ double red[ACC_THREADS / 64][NSUMS_PLANE];
+    double acc0[12], acc1[12], acc2[8];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { acc0[k] = 0.0; acc1[k] = 0.0; }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc2[k] = 0.0;
+    for (long long i = (long long)blockIdx.x * ACC_THREADS + threadIdx.x; i < K; i += (long long)gridDim.x * ACC_THREADS) {
+        const double p0 = NA[i], p1 = NA[ld + i], p2 = NA[2 * ld + i], q0 = NB[i], q1 = NB[ld + i], q2 = NB[2 * ld + i];
+        const double pp = (p0 * p0 + p1 * p1) + p2 * p2, qq = (q0 * q0 + q1 * q1) + q2 * q2;
+        if (!(pp > 0.0) || !(pp < INFINITY) || !(qq > 0.0) || !(qq < INFINITY)) continue;
+        const double pinv = 1.0 / sqrt(pp), qinv = 1.0 / sqrt(qq);
+        double j[6], r, h0[12], h1[12], h2[8];
+        symm_row(A[i] - pvx, A[ld + i] - pvy, A[2 * ld + i] - pvz, B[i] - pvx, B[ld + i] - pvy, B[2 * ld + i] - pvz,
+                 p0 * pinv, p1 * pinv, p2 * pinv, q0 * qinv, q1 * qinv, q2 * qinv, j, r);
+        plane_terms_0(j, h0); plane_terms_1(j, r, h1); plane_terms_2(j, r, 1.0, 0.0, h2);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { acc0[k] += h0[k]; acc1[k] += h1[k]; }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc2[k] += h2[k];
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    wave_reduce_scatter<12>(acc0, lane, &red[wave][0]);
+    wave_reduce_scatter<12>(acc1, lane, &red[wave][12]);
+    wave_reduce_scatter<8>(acc2, lane, &red[wave][24]);
+    block_finish_plane(red, partials + (long long)blockIdx.x * NSUMS_PLANE);
+}
+
 // rows of the plane layout -> sums (oa_point_to_plane; the loop reduces inside k_reduce_solve_update_plane)
 __global__ __launch_bounds__(RED_THREADS) void k_reduce_partials_plane(const double *__restrict__ partials, int n_rows, double *__restrict__ sums_out)
 {
     reduce_rows_block<NSUMS_PLANE>(partials, n_rows, sums_out);
 }
 
-// one wave: the plane solve only (oa_point_to_plane).  out[0..15] = M, out[16] = ok flag, out[17] = rank
-__global__ __launch_bounds__(64) void k_solve_only_plane(const double *__restrict__ sums, double pvx, double pvy, double pvz, double *__restrict__ out)
+// one wave: the plane solve only (oa_point_to_plane; symmetric: oa_symmetric_step).  out[0..15] = M, out[16] = ok flag, out[17] = rank
+__global__ __launch_bounds__(64) void k_solve_only_plane(const double *__restrict__ sums, double pvx, double pvy, double pvz, int symmetric,
+                                                         double *__restrict__ out)
 {
     __shared__ double sh_s[NSUMS_PLANE], sh_A[36], sh_V[36];
     const int lane = threadIdx.x;
@@ -3221,7 +3362,7 @@ __global__ __launch_bounds__(64) void k_solve_only_plane(const double *__restric
     const double pv[3] = { pvx, pvy, pvz };
     double M[16];
     int rank;
-    const bool ok = plane_solve_from_sums(sh_s, pv, sh_A, sh_V, lane < 6 ? lane : 6, lane < 6 ? lane + 1 : 6, M, rank);
+    const bool ok = plane_solve_from_sums(sh_s, pv, sh_A, sh_V, lane < 6 ? lane : 6, lane < 6 ? lane + 1 : 6, M, rank, false, symmetric != 0);
     if (lane == 0) {
         for (int k = 0; k < 16; ++k) out[k] = ok ? M[k] : 0.0;
         out[16] = ok ? 1.0 : 0.0;
@@ -3299,7 +3440,8 @@ __device__ __forceinline__ void solve_update_block(DevState *__restrict__ st, co
         if constexpr (PLANE) {
             __shared__ double sh_A[36], sh_V[36];
             int rank;
-            ok = plane_solve_from_sums(sums, cs->pivot, sh_A, sh_V, lane < 6 ? lane : 6, lane < 6 ? lane + 1 : 6, M, rank, cs->weighted != 0);
+            ok = plane_solve_from_sums(sums, cs->pivot, sh_A, sh_V, lane < 6 ? lane : 6, lane < 6 ? lane + 1 : 6, M, rank, cs->weighted != 0,
+                                       cs->symmetric != 0);
             if (lane == 0) st->plane_rank = rank;
         } else {
             double s[NSUMS];

@@ -4,7 +4,7 @@
 // The contract (include/oa_icp.h):
 //   The candidates of a step are the K_q pairs that would be counted in K and carry a vertex weight > 0 -- k_residual_keys' keys
 //   other than RKEY_NONE; with oa_set_reciprocal on, the pairs that passed it.  Each has the float32-rounded residual r the losses
-//   use (point: the world-space pair distance; plane: s |n . (a - b)|; GICP: s sqrt(e^T W e)); its key is the bits of r.
+//   use (point: the world-space pair distance; plane and symmetric: s |n . (a - b)|; GICP: s sqrt(e^T W e)); its key is the bits of r.
 //     - fixed share f:     k = clamp(ceil(f K_q), min(3, K_q), K_q), the cut q = the k-th smallest r.
 //     - estimated share:   S_j = sum_{i <= j} (double)r_(i)^2 over the sorted residuals, J(j) = S_j j^-(1 + 2 lambda);
 //                          k = the smallest j in [k_min, K_q] that minimises J, k_min = clamp(ceil(f_min K_q), min(3, K_q), K_q);
@@ -16,7 +16,7 @@
 // is the existing RECIP = true instantiation of whatever kernel the step would run -- no accumulation kernel knows about trimming.
 // The launches of a step, all on the loop's stream, no host round trip, no float atomics, no workgroup waiting for another:
 //   (bytes := 1 unless k_recip_check has just written them; the select's histograms := 0)
-//   k_residual_keys<PLANE, RECIP> / k_residual_keys_gicp<RECIP>      the keys (+ the select's level-0 counts)
+//   k_residual_keys<PLANE, RECIP> / k_residual_keys_gicp<RECIP> / k_residual_keys_symm<RECIP>      the keys (+ the select's level-0 counts)
 //   fixed:      k_dev_select_scan 0, _hist 1, _scan 1, _hist 2, _scan 2 (oa_deviation.hpp: the radix select of oa_set_robust_auto
 //               with its state outside DevState -- DevTrim::sel, so both selections can run in one step)
 //   estimated:  sort_order over all 32 key bits (oa_sort.hpp; RKEY_NONE sorts last) + k_gather_int -> the sorted keys
@@ -98,6 +98,46 @@ __global__ __launch_bounds__(PLANE_THREADS) void k_residual_keys_gicp(const DevS
                 const double u0 = (W[0] * e0 + W[1] * e1) + W[2] * e2, u1 = (W[1] * e0 + W[3] * e1) + W[4] * e2, u2 = (W[2] * e0 + W[4] * e1) + W[5] * e2;
                 const double rr = (e0 * u0 + e1 * u1) + e2 * u2;
                 rkey = (uint32_t)__float_as_int((float)(st->res_scale * sqrt(fmax(rr, 0.0))));
+            }
+        }
+        rkeys[i] = rkey;
+    }
+    sel_count(bins, rkey != RKEY_NONE, sel_digit(rkey, 0));
+    sel_flush(bins, hist);
+}
+
+// The symmetric metric's instance: the residual k_pair_accumulate_symm hands to robust_psi, formed exactly as that kernel forms
+// it -- pair_fetch<false, true> (read-only), plane_normal for n_b, symm_source_normal, symm_row -- as the bits of
+// (float)(res_scale |r|).  Serves the trim (RECIP = true) and oa_set_robust_auto (either RECIP).
+template <bool RECIP>
+__global__ __launch_bounds__(PLANE_THREADS) void k_residual_keys_symm(const DevState *__restrict__ st, const float4 *__restrict__ src4, int ns,
+                                                                  const float *__restrict__ tgt_xyz,
+                                                                  const unsigned long long *__restrict__ keys,
+                                                                  const float4 *__restrict__ win, const float4 *__restrict__ tri9,
+                                                                  PairTest<RECIP> nrm, const float *__restrict__ plane_tn,
+                                                                  const float *__restrict__ src_n, const float *__restrict__ w_slot,
+                                                                  uint32_t *__restrict__ rkeys, uint32_t *__restrict__ hist,
+                                                                  unsigned long long *__restrict__ t_acc_start)
+{
+    __shared__ uint32_t bins[SEL_BINS];
+    if (t_acc_start && blockIdx.x == 0 && threadIdx.x == 0) *t_acc_start = wall_clock64();   // ~ the end of the search
+    if (st->halt) return;
+    sel_clear(bins);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t rkey = RKEY_NONE;
+    if (i < ns) {
+        PairFetch f;
+        if (pair_fetch<false, true, RECIP>(st, src4, i, tgt_xyz, keys, nullptr, win, tri9, nrm, plane_tn, st->thresh, f)) {
+            double nx = 0.0, ny = 0.0, nz = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+            bool valid = plane_normal(st, f.tn, nx, ny, nz);
+            if (valid) valid = symm_source_normal(src_n, i, sx, sy, sz);
+            if (valid && w_slot) valid = w_slot[i] > 0.f;
+            if (valid) {
+                const double pvx = st->pivot[0], pvy = st->pivot[1], pvz = st->pivot[2];
+                double j[6], r;
+                symm_row((double)f.p.x - pvx, (double)f.p.y - pvy, (double)f.p.z - pvz, (double)f.bx - pvx, (double)f.by - pvy, (double)f.bz - pvz,
+                         sx, sy, sz, nx, ny, nz, j, r);
+                rkey = (uint32_t)__float_as_int((float)(st->res_scale * fabs(r)));
             }
         }
         rkeys[i] = rkey;

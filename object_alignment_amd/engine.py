@@ -267,16 +267,19 @@ class IcpEngine:
         self._chk(self._L.oa_set_normals(self._h, capi.fptr(sn), len(sn), capi.fptr(tn) if tn is not None else None,
                                           len(tn) if tn is not None else 0, float(max_angle_deg)))
 
-    METRICS = {"point": capi.OA_METRIC_POINT, "plane": capi.OA_METRIC_PLANE, "gicp": capi.OA_METRIC_GICP}
+    METRICS = {"point": capi.OA_METRIC_POINT, "plane": capi.OA_METRIC_PLANE, "gicp": capi.OA_METRIC_GICP,
+               "symmetric": capi.OA_METRIC_SYMMETRIC}
 
     def set_metric(self, metric):
         """What a loop step minimises: 'point' (Besl-McKay, the reference's loop, default), 'plane' (Chen-Medioni: the distance
         to the tangent plane at the correspondence) or 'gicp' (plane-to-plane, Generalized-ICP: every pair weighted by both sides'
-        normals -- needs set_source_normals, see set_gicp); the last two on single-device contexts, run() / iterate(), no scale.
+        normals -- needs set_source_normals, see set_gicp) or 'symmetric' (Rusinkiewicz 2019: the plane metric's row with the mean
+        of both sides' normals and the rotation split between the two sides -- needs set_source_normals, no parameter); the last
+        three on single-device contexts, run() / iterate(), no scale.
         Survives uploads and set_matrices; stat("metric") reads it back."""
         if isinstance(metric, str):
             if metric not in self.METRICS:
-                raise ValueError("metric %r (use 'point', 'plane' or 'gicp')" % (metric,))
+                raise ValueError("metric %r (use 'point', 'plane', 'gicp' or 'symmetric')" % (metric,))
             metric = self.METRICS[metric]
         self._chk(self._L.oa_set_metric(self._h, int(metric)))
 
@@ -293,7 +296,7 @@ class IcpEngine:
 
     def set_source_normals(self, src_normals):
         """One align-local normal per source vertex (the array uploaded with set_source, not the selection), for the 'gicp'
-        metric; the normal-angle test stays as it is.  Call after set_source; a new source upload forgets them."""
+        and 'symmetric' metrics; the normal-angle test stays as it is.  Call after set_source; a new source upload forgets them."""
         sn = capi.as_f32(src_normals).reshape(-1, 3)
         self._chk(self._L.oa_set_source_normals(self._h, capi.fptr(sn), len(sn)))
 
@@ -538,6 +541,20 @@ class IcpEngine:
             raise ValueError(REF_VALUEERROR)
         M = np.empty((4, 4), np.float64)
         rc = self._L.oa_point_to_plane(self._h, capi.dptr(A), capi.dptr(B), capi.dptr(N), A.shape[1], A.shape[1], capi.dptr(M))
+        if rc == capi.OA_E_TOO_FEW_PAIRS:
+            raise ValueError(REF_VALUEERROR)
+        self._chk(rc)
+        return M
+
+    def symmetric_step(self, A, B, NA, NB) -> np.ndarray:
+        """The symmetric metric's step from explicit pairs (3 x K each; NA, NB: the normals at A and at B, any length, either
+        sign): the 4 x 4 that moves A towards B about the pivot A[:, 0], half of its rotation on either side of the translation;
+        minimum-norm where the pairs leave the step undetermined (stat("plane_rank")).  A pair with a zero normal is left out."""
+        A, B, NA, NB = (np.ascontiguousarray(x, np.float64) for x in (A, B, NA, NB))
+        if A.ndim != 2 or A.shape[0] != 3 or B.shape != A.shape or NA.shape != A.shape or NB.shape != A.shape:
+            raise ValueError(REF_VALUEERROR)
+        M = np.empty((4, 4), np.float64)
+        rc = self._L.oa_symmetric_step(self._h, capi.dptr(A), capi.dptr(B), capi.dptr(NA), capi.dptr(NB), A.shape[1], A.shape[1], capi.dptr(M))
         if rc == capi.OA_E_TOO_FEW_PAIRS:
             raise ValueError(REF_VALUEERROR)
         self._chk(rc)

@@ -42,6 +42,8 @@ class IcpSettings:
     # to the tangent plane at the correspondence (Chen-Medioni; rigid only, one GPU), which lets a surface slide along itself
     # "gicp": plane-to-plane (Generalized-ICP; rigid only, one GPU): every pair weighted by the normals of both sides -- needs
     # run(..., source_normals=...); gicp_epsilon is the small eigenvalue of its covariances, in [1e-6, 1]
+    # "symmetric": the symmetric objective (Rusinkiewicz 2019; rigid only, one GPU): the plane metric's row with the mean of both
+    # sides' normals, the rotation split between the two sides -- needs run(..., source_normals=...), no parameter
     metric: str = "point"
     gicp_epsilon: float = 1e-3
     # nor these: the weight of a pair in a step is a robust loss of its residual -- "none" (every pair weighs one, the
@@ -371,8 +373,8 @@ class IcpAlign:
         "estimate": PCA normals from every target vertex's settings.normal_k nearest neighbours, computed on the device after
         the upload and oriented away from the target's centroid (point-cloud targets only: a mesh has its triangles').
         source_weights: one weight per vertex of source_xyz (finite, >= 0) -- "trust this region less"; None = all one.
-        source_normals: one align-local normal per vertex of source_xyz -- what settings.metric == "gicp" needs -- or "estimate":
-        object_alignment_amd.estimate_normals(source_xyz, k=settings.normal_k), in a context of its own (that metric does not
+        source_normals: one align-local normal per vertex of source_xyz -- what settings.metric == "gicp" / "symmetric" needs -- or "estimate":
+        object_alignment_amd.estimate_normals(source_xyz, k=settings.normal_k), in a context of its own (those metrics do not
         look at the normals' signs, so they are left unoriented).
         coarse: a CoarseSettings (operators/coarse_align.py) -- the coarse global stage runs on the same engine in front of the
         loop, which then starts from the pose it found (self.last_coarse holds its report); None: the loop alone.
