@@ -859,6 +859,68 @@ int oa_deviation(oa_ctx *ctx, const oa_deviation_settings *settings, double *sig
  * NULL.  OA_E_STATE without a mesh target. */
 int oa_get_mesh_pseudonormals(oa_ctx *ctx, float *vertex_n /* nv x 3 */, float *edge_n /* nt x 3 x 3 */);
 
+/* ---- EXTENSION: normal-space sampling and the stability report of a selection -- which points enter the loop, and which motions
+ *      they leave free.  Both calls need no target, source or matrices and touch nothing a loop reads (as
+ *      oa_voxel_downsample); OA_E_STATE on a multi-device context.  Inputs: host arrays or (on_device != 0) device memory;
+ *      outputs: host memory. ------------------------------------------------------------------------------------------------ */
+typedef struct oa_sample_report {
+    int64_t n_in, n_eligible;       /* normals given; those that take part */
+    int64_t bins_occupied;          /* bins with at least one member */
+    int64_t level;                  /* t below; the largest count when every eligible point is given */
+    int64_t max_bin_count;          /* most members of one bin */
+    double  total_ms;               /* host time of the call */
+} oa_sample_report;
+/* Normal-space sampling (Rusinkiewicz & Levoy 2001, 3.1): bucket the normals, draw evenly across the buckets -- m points of n,
+ * as ascending original indices (a vlist for oa_set_source).  Every formula is plain IEEE fp64 with the grouping written, no fused
+ * multiply-add; no float is ever added to another, and two calls give the same bits.
+ * Eligible: a normal with three finite components whose l2 = (x x + y y) + z z, in fp64, is finite and > 0.
+ * Bin (G = grid): a = the axis of the largest |component| (ties: the lowest axis), b = (a + 1) % 3, c = (a + 2) % 3.
+ *   unoriented == 0: face f = 2 a + (n_a < 0), u = n_b / |n_a|, v = n_c / |n_a|   (6 G G bins)
+ *   unoriented != 0: face f = a, u = n_b / n_a, v = n_c / n_a                     (3 G G bins; n and -n share a bin)
+ *   iu = min(G - 1, (int)floor((u + 1.0) * (0.5 * G))), iv likewise from v; bin = (f G + iv) G + iu.
+ * No square root and no normalisation: the bin depends on the direction alone.
+ * Order inside a bin: ascending h(i) = (uint32)((i ^ seed) * 0x9E3779B1u), a bijection of the index: no ties.
+ * Shares: with the bins' counts c_b, the level t is the largest integer with sum_b min(c_b, t) <= m; the remainder
+ * r = m - sum_b min(c_b, t) goes one each to the first r bins, in ascending bin id, with c_b > t.  Bin b gives its first
+ * min(c_b, t) (+ 1) members in hash order.  m >= n_eligible: every eligible point is given and level = max_bin_count.
+ * out_idx (room for cap): the points given, ascending; *n_out = min(m, n_eligible) their number.  out_bin: n entries or NULL, the
+ * bin of every point, -1 for one that is not eligible.
+ * OA_E_BAD_ARG: m < 1; grid outside 1 .. 32; n outside 1 .. 2^31 - 2^20; no eligible point.  cap < *n_out: OA_E_CAPACITY with
+ * *n_out and the report filled and nothing written to out_idx or out_bin. */
+int oa_normal_space_sample(oa_ctx *ctx, const float *normals /* n x 3 */, int64_t n, int on_device, int64_t m, int32_t grid,
+                           int32_t unoriented, uint32_t seed, int64_t cap, int64_t *out_idx /* cap */, int32_t *out_bin /* n, or NULL */,
+                           int64_t *n_out, oa_sample_report *rep);
+
+typedef struct oa_stability_report {
+    int64_t n_used;                 /* eligible points among those analysed */
+    double  centroid[3];            /* c */
+    double  scale;                  /* s; 0 when the mean distance to c is 0 or not finite */
+    double  C[36];                  /* row-major, symmetric */
+    double  eigenvalues[6];         /* descending */
+    double  eigenvectors[36];       /* row-major; COLUMN k belongs to eigenvalues[k] */
+    int32_t rank, reserved;         /* eigenvalues > 1e-10 x the largest; 0 when scale is 0 */
+    double  cond;                   /* eigenvalues[0] / eigenvalues[5]; +inf when eigenvalues[5] <= 0 or scale is 0 */
+    double  total_ms;               /* host time of the call */
+} oa_stability_report;
+/* The 6 x 6 constraint matrix of a selection under the point-to-plane metric (Gelfand, Ikemoto, Rusinkiewicz & Levoy 2003) and
+ * its eigen-decomposition: which rigid motions the selection resists.  xyz, normals: n x 3 float32 on the same side; idx: NULL
+ * (all n points) or n_idx HOST indices in 0 .. n - 1 (a point listed twice counts twice).
+ * Eligible: the normal as for oa_normal_space_sample, and three finite coordinates.  Over the eligible points, all fp64:
+ *   c = (sum p) / n_used per coordinate;  s = 1 / ((sum sqrt((dx dx + dy dy) + dz dz)) / n_used), d = (double)p - c
+ *   nh = n * (1 / sqrt(l2));  q = ((double)p - c) * s
+ *   v = [q x nh ; nh], the cross product (q_y nh_z - q_z nh_y, q_z nh_x - q_x nh_z, q_x nh_y - q_y nh_x);  C = sum v v^T.
+ * The order of the sums depends on the input alone -- no atomics, two calls give the same bits.  With N the number of points
+ * analysed (n_idx, or n), B = min(256, ceil(N / 256)) and the points taken in the order given: sum g of 256 B adds the points at
+ * positions g, g + 256 B, g + 512 B, ... in ascending order, from +0 (a point that is not eligible adds nothing); the sums
+ * 64 k .. 64 k + 63 are joined by the butterfly t_l = s_l + s_(l ^ 32), then strides 16, 8, 4, 2, 1 likewise, into w_k; block b
+ * of four gives ((w_4b + w_4b+1) + w_4b+2) + w_4b+3; then 64 sums z_l = block l + block (l + 64) + ... joined by the same butterfly.
+ * Eigenvalues by cyclic Jacobi rotations in fp64, descending; eigenvector k is column k, signed so that its component of largest
+ * magnitude (the lowest index on ties) is positive.  Rows 0-2 of a vector: a rotation about c in the normalised units (lengths
+ * times s); rows 3-5: a translation.  A small eigenvalue: the selection does not resist that screw motion.
+ * OA_E_BAD_ARG: n or n_idx outside 1 .. 2^31 - 2^20; an index outside 0 .. n - 1; no eligible point. */
+int oa_stability(oa_ctx *ctx, const float *xyz, const float *normals, int64_t n, int on_device, const int64_t *idx /* host, or NULL */,
+                 int64_t n_idx, oa_stability_report *rep);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,26 @@ def voxel_downsample(xyz, voxel, normals=None, origin=None, device=0):
         return eng.voxel_downsample(xyz, voxel, normals=normals, origin=origin)
 
 
+def normal_space_sample(normals, m, grid=8, unoriented=False, seed=0, device=0):
+    """Normal-space sampling of ANY cloud's normals on the GPU: m points drawn evenly across the buckets of a cube map of the
+    normals, so that small features keep their say (a dict: idx -- a vlist --, bin, report; IcpEngine.normal_space_sample).  Opens
+    a context of its own on `device`."""
+    from .engine import IcpEngine, _sample_args
+    normals, m, grid, unoriented, seed = _sample_args(normals, m, grid, unoriented, seed)
+    with IcpEngine(int(device)) as eng:
+        return eng.normal_space_sample(normals, m, grid=grid, unoriented=bool(unoriented), seed=seed)
+
+
+def stability(xyz, normals, idx=None, device=0):
+    """Which rigid motions a selection of ANY cloud resists under the point-to-plane metric: the 6 x 6 constraint matrix of the
+    points idx lists (None: all), its eigenvalues and eigenvectors, rank and condition number (a dict; IcpEngine.stability says
+    how to read it).  Opens a context of its own on `device`."""
+    from .engine import IcpEngine, _stability_args
+    xyz, normals, idx = _stability_args(xyz, normals, idx)
+    with IcpEngine(int(device)) as eng:
+        return eng.stability(xyz, normals, idx=idx)
+
+
 def deviation(source_xyz, target_xyz, target_tris=None, mx_align=None, mx_base=None, target_normals=None, device=0, **kw):
     """The deviation report of a source against a target at given matrices (identity when None): signed per-point distances and
     fit statistics (IcpEngine.deviation; **kw are its arguments).  target_tris: the target is a mesh and the sign comes from its

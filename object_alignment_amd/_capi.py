@@ -82,6 +82,7 @@ SYMBOLS = [
     "oa_deviation", "oa_get_mesh_pseudonormals",
     "oa_set_reciprocal", "oa_set_trim",
     "oa_target_boundary", "oa_set_reject_boundary",
+    "oa_normal_space_sample", "oa_stability",
 ]
 
 
@@ -134,6 +135,17 @@ class DeviationReport(C.Structure):
                 ("mean_signed", C.c_double), ("max_dist", C.c_double), ("quantile_values", C.c_double * 8), ("n_quantiles", C.c_int32),
                 ("signed_used", C.c_int32), ("surface", C.c_int32), ("reserved", C.c_int32), ("search_ms", C.c_double),
                 ("total_ms", C.c_double), ("pseudonormal_ms", C.c_double)]
+
+
+class SampleReport(C.Structure):
+    _fields_ = [("n_in", C.c_int64), ("n_eligible", C.c_int64), ("bins_occupied", C.c_int64), ("level", C.c_int64),
+                ("max_bin_count", C.c_int64), ("total_ms", C.c_double)]
+
+
+class StabilityReport(C.Structure):
+    _fields_ = [("n_used", C.c_int64), ("centroid", C.c_double * 3), ("scale", C.c_double), ("C", C.c_double * 36),
+                ("eigenvalues", C.c_double * 6), ("eigenvectors", C.c_double * 36), ("rank", C.c_int32), ("reserved", C.c_int32),
+                ("cond", C.c_double), ("total_ms", C.c_double)]
 
 
 class OaError(RuntimeError):
@@ -242,6 +254,9 @@ def load(experiments: bool = False):
     L.oa_target_boundary.argtypes = [vp, C.c_int, C.c_double, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
     L.oa_set_reject_boundary.argtypes = [vp, C.c_int, C.c_int, C.c_double]
     L.oa_set_trim.argtypes = [vp, C.c_double, C.c_double, C.c_double]
+    L.oa_normal_space_sample.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_int64, ip, i32p, ip,
+                                         C.POINTER(SampleReport)]
+    L.oa_stability.argtypes = [vp, vp, vp, C.c_int64, C.c_int, ip, C.c_int64, C.POINTER(StabilityReport)]
     _libs[experiments] = L
     return L
 

@@ -19,6 +19,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "oa_all.hpp"                // every kernel header + oa_families.hpp: the heavy templates are `extern` here, compiled in oa_fam_*.hip
 #include "oa_sort.hpp"
 #include "oa_voxel.hpp"
+#include "oa_sample.hpp"
 #include "oa_deviation.hpp"
 #include "oa_boundary.hpp"
 #include "oa_tunables.hpp"            // every OA_* knob: read once, oa_ctx::tune (plain C++)
@@ -5861,6 +5862,167 @@ OA_EXPORT int oa_voxel_downsample(oa_ctx *c, const float *xyz, int64_t n, int on
     if (n_out) *n_out = n_rows;
     if (rep) *rep = r;
     if (!fits) return fail(OA_E_CAPACITY, "oa_voxel_downsample: %lld occupied voxels, room for %lld rows", n_rows, (long long)cap);
+    return OA_OK;
+}
+
+// ================================================================================================
+// normal-space sampling and the stability report (EXTENSION; oa_sample.hpp)
+// ================================================================================================
+OA_EXPORT int oa_normal_space_sample(oa_ctx *c, const float *normals, int64_t n, int on_device, int64_t m, int32_t grid, int32_t unoriented, uint32_t seed,
+                                     int64_t cap, int64_t *out_idx, int32_t *out_bin, int64_t *n_out, oa_sample_report *rep)
+{
+    if (!c || !normals) return fail(OA_E_BAD_ARG, "oa_normal_space_sample: null argument");
+    OA_NOT_MULTI(c, "oa_normal_space_sample");
+    if (m < 1) return fail(OA_E_BAD_ARG, "oa_normal_space_sample: m = %lld points wanted (>= 1)", (long long)m);
+    if (grid < 1 || grid > oa::NSS_MAX_GRID) return fail(OA_E_BAD_ARG, "oa_normal_space_sample: grid = %d (1 .. %d)", (int)grid, oa::NSS_MAX_GRID);
+    if (n < 1 || n > (int64_t)2147483648ll - (1 << 20)) return fail(OA_E_BAD_ARG, "oa_normal_space_sample: %lld normals (1 .. 2^31 - 2^20)", (long long)n);
+    if (cap < 0 || !out_idx) cap = 0;
+    int rc = use_device(c);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    oa_sample_report r;
+    memset(&r, 0, sizeof r);
+    r.n_in = n;
+    if (n_out) *n_out = 0;
+    if (rep) *rep = r;
+    const int ni = (int)n, G = (int)grid, n_bins = (unoriented ? 3 : 6) * G * G;
+    const size_t sn = (size_t)n;
+    const long long room = (long long)std::min<int64_t>(m, n);     // the most rows there can be
+    const unsigned pt_blocks = (unsigned)((sn + oa::NSS_THREADS - 1) / oa::NSS_THREADS);
+    DevTmp<float> tmp_nrm;
+    const float *d_nrm = nullptr;
+    if ((rc = stage_floats(c, normals, 3 * sn, on_device, tmp_nrm, d_nrm))) return rc;
+    // 1. bins and hash keys
+    DevTmp<int> d_bin, d_by_hash, d_stage, d_order, d_counts, d_share, d_flag;
+    DevTmp<uint32_t> d_bin_key, d_hash, d_key_sorted;
+    DevTmp<long long> d_start, d_off, d_out;
+    DevTmp<oa::NssInfo> d_info;
+    DevTmp<char> scan_tmp;
+    HIPCHK(d_bin.alloc(sn)); HIPCHK(d_bin_key.alloc(sn)); HIPCHK(d_hash.alloc(sn));
+    HIPCHK(d_by_hash.alloc(sn)); HIPCHK(d_key_sorted.alloc(sn)); HIPCHK(d_stage.alloc(sn)); HIPCHK(d_order.alloc(sn));
+    HIPCHK(d_counts.alloc((size_t)n_bins)); HIPCHK(d_share.alloc((size_t)n_bins)); HIPCHK(d_start.alloc((size_t)n_bins));
+    HIPCHK(d_flag.alloc(sn)); HIPCHK(d_off.alloc(sn + 1)); HIPCHK(d_out.alloc((size_t)room)); HIPCHK(d_info.alloc(1));
+    hipLaunchKernelGGL(oa::k_nss_keys, dim3(pt_blocks), dim3(oa::NSS_THREADS), 0, c->stream, d_nrm, ni, G, unoriented ? 1 : 0, seed, n_bins, d_bin.p, d_bin_key.p,
+                       d_hash.p);
+    HIPCHK(hipGetLastError());
+    // 2. by hash, then stably by bin: argsort the hashes, argsort the bins read through that order, compose (as voxel_sort_keys)
+    if ((rc = sort_order_bits(c, d_hash.p, d_by_hash.p, sn, 32))) return rc;
+    hipLaunchKernelGGL(oa::k_gather_int, dim3((unsigned)((sn + 255) / 256)), dim3(256), 0, c->stream, (const int *)d_bin_key.p, (const int *)d_by_hash.p, ni,
+                       (int *)d_key_sorted.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = sort_order_bits(c, d_key_sorted.p, d_stage.p, sn, bits_for((long long)n_bins + 1)))) return rc;
+    hipLaunchKernelGGL(oa::k_gather_int, dim3((unsigned)((sn + 255) / 256)), dim3(256), 0, c->stream, (const int *)d_by_hash.p, (const int *)d_stage.p, ni, d_order.p);
+    HIPCHK(hipGetLastError());
+    // 3., 4. the bins' counts, the level and every bin's share
+    HIPCHK(hipMemsetAsync(d_counts.p, 0, sizeof(int) * (size_t)n_bins, c->stream));
+    hipLaunchKernelGGL(oa::k_nss_hist, dim3(std::min<unsigned>(pt_blocks, oa::NSS_HIST_BLOCKS)), dim3(oa::NSS_THREADS), 0, c->stream, (const int *)d_bin.p, ni, n_bins,
+                       d_counts.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(oa::k_nss_level, dim3(1), dim3(oa::NSS_LEVEL_THREADS), 0, c->stream, (const int *)d_counts.p, n_bins, (long long)m, d_share.p, d_start.p,
+                       d_info.p);
+    HIPCHK(hipGetLastError());
+    // 5., 6. the points taken, then their indices in ascending order
+    HIPCHK(hipMemsetAsync(d_flag.p, 0, sizeof(int) * sn, c->stream));
+    hipLaunchKernelGGL(oa::k_nss_flag, dim3(pt_blocks), dim3(oa::NSS_THREADS), 0, c->stream, (const int *)d_order.p, (const int *)d_bin.p, ni, n_bins,
+                       (const int *)d_share.p, (const long long *)d_start.p, d_flag.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = scan_counts(c, d_flag.p, ni, d_off.p, scan_tmp))) return rc;
+    hipLaunchKernelGGL(oa::k_nss_compact, dim3(pt_blocks), dim3(oa::NSS_THREADS), 0, c->stream, (const int *)d_flag.p, (const long long *)d_off.p, ni, room, d_out.p,
+                       d_info.p);
+    HIPCHK(hipGetLastError());
+    oa::NssInfo info;
+    if ((rc = read_small(c, &info, d_info.p, sizeof info))) return rc;                   // (waits for everything above)
+    r.n_eligible = info.n_eligible; r.bins_occupied = info.bins_occupied; r.level = info.level; r.max_bin_count = info.max_bin_count;
+    r.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rep) *rep = r;
+    if (info.n_eligible < 1) return fail(OA_E_BAD_ARG, "oa_normal_space_sample: none of the %lld normals is finite and of length > 0", (long long)n);
+    if (info.n_eligible > n || info.n_out != std::min<long long>((long long)m, info.n_eligible))
+        return fail(OA_E_HIP, "oa_normal_space_sample: %lld rows for m = %lld of %lld eligible points", info.n_out, (long long)m, info.n_eligible);
+    if (n_out) *n_out = info.n_out;
+    if (cap < info.n_out) return fail(OA_E_CAPACITY, "oa_normal_space_sample: %lld points given, room for %lld", info.n_out, (long long)cap);
+    static_assert(sizeof(long long) == sizeof(int64_t), "out_idx is copied as it is");
+    HIPCHK(hipMemcpyAsync(out_idx, d_out.p, sizeof(int64_t) * (size_t)info.n_out, hipMemcpyDeviceToHost, c->stream));
+    if (out_bin) HIPCHK(hipMemcpyAsync(out_bin, d_bin.p, sizeof(int32_t) * sn, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    r.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rep) *rep = r;
+    return OA_OK;
+}
+
+OA_EXPORT int oa_stability(oa_ctx *c, const float *xyz, const float *normals, int64_t n, int on_device, const int64_t *idx, int64_t n_idx, oa_stability_report *rep)
+{
+    if (!c || !xyz || !normals || !rep) return fail(OA_E_BAD_ARG, "oa_stability: null argument");
+    OA_NOT_MULTI(c, "oa_stability");
+    constexpr int64_t most = (int64_t)2147483648ll - (1 << 20);
+    if (n < 1 || n > most) return fail(OA_E_BAD_ARG, "oa_stability: %lld points (1 .. 2^31 - 2^20)", (long long)n);
+    if (idx) {
+        if (n_idx < 1 || n_idx > most) return fail(OA_E_BAD_ARG, "oa_stability: %lld indices (1 .. 2^31 - 2^20)", (long long)n_idx);
+        for (int64_t k = 0; k < n_idx; ++k)
+            if (idx[k] < 0 || idx[k] >= n) return fail(OA_E_BAD_ARG, "oa_stability: idx[%lld] = %lld outside 0 .. %lld", (long long)k, (long long)idx[k], (long long)n - 1);
+    }
+    int rc = use_device(c);
+    if (rc) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    memset(rep, 0, sizeof *rep);
+    const long long n_used = idx ? (long long)n_idx : (long long)n;
+    DevTmp<float> tmp_xyz, tmp_nrm;
+    const float *d_xyz = nullptr, *d_nrm = nullptr;
+    DevTmp<long long> d_idx, d_pcount;
+    DevTmp<double> d_partial;
+    DevTmp<oa::StabOut> d_st;
+    std::vector<float> rows_xyz, rows_nrm;                          // (alive until the stream has been waited for)
+    const long long *d_sel = nullptr;
+    if (idx && !on_device) {
+        // host arrays and a list: only the listed rows go up, in the list's order -- the same terms at the same positions, so the
+        // same sums as through the index (the order of summation depends on the number of points analysed alone)
+        rows_xyz.resize(3 * (size_t)n_idx); rows_nrm.resize(3 * (size_t)n_idx);
+        for (size_t k = 0; k < (size_t)n_idx; ++k)
+            for (int a = 0; a < 3; ++a) {
+                rows_xyz[3 * k + a] = xyz[3 * (size_t)idx[k] + a];
+                rows_nrm[3 * k + a] = normals[3 * (size_t)idx[k] + a];
+            }
+        if ((rc = stage_floats(c, rows_xyz.data(), rows_xyz.size(), 0, tmp_xyz, d_xyz))) return rc;
+        if ((rc = stage_floats(c, rows_nrm.data(), rows_nrm.size(), 0, tmp_nrm, d_nrm))) return rc;
+    } else {
+        if ((rc = stage_floats(c, xyz, 3 * (size_t)n, on_device, tmp_xyz, d_xyz))) return rc;
+        if ((rc = stage_floats(c, normals, 3 * (size_t)n, on_device, tmp_nrm, d_nrm))) return rc;
+        if (idx) {                                                  // a device-resident cloud is read through the list
+            static_assert(sizeof(long long) == sizeof(int64_t), "idx is copied as it is");
+            HIPCHK(d_idx.alloc((size_t)n_idx));
+            HIPCHK(hipMemcpyAsync(d_idx.p, idx, sizeof(int64_t) * (size_t)n_idx, hipMemcpyHostToDevice, c->stream));
+            d_sel = d_idx.p;
+        }
+    }
+    const int nb = (int)std::min<long long>(oa::STAB_MAX_BLOCKS, (n_used + oa::STAB_THREADS - 1) / oa::STAB_THREADS);   // (part of the summation order)
+    HIPCHK(d_partial.alloc((size_t)nb * oa::STAB_NT)); HIPCHK(d_pcount.alloc((size_t)nb)); HIPCHK(d_st.alloc(1));
+    HIPCHK(hipMemsetAsync(d_st.p, 0, sizeof(oa::StabOut), c->stream));
+    for (int phase = 0; phase < 3; ++phase) {
+        if (phase == 0)
+            hipLaunchKernelGGL(oa::k_stab_accum<0>, dim3((unsigned)nb), dim3(oa::STAB_THREADS), 0, c->stream, d_xyz, d_nrm, d_sel, n_used, (const oa::StabOut *)d_st.p,
+                               d_partial.p, d_pcount.p);
+        else if (phase == 1)
+            hipLaunchKernelGGL(oa::k_stab_accum<1>, dim3((unsigned)nb), dim3(oa::STAB_THREADS), 0, c->stream, d_xyz, d_nrm, d_sel, n_used, (const oa::StabOut *)d_st.p,
+                               d_partial.p, d_pcount.p);
+        else
+            hipLaunchKernelGGL(oa::k_stab_accum<2>, dim3((unsigned)nb), dim3(oa::STAB_THREADS), 0, c->stream, d_xyz, d_nrm, d_sel, n_used, (const oa::StabOut *)d_st.p,
+                               d_partial.p, d_pcount.p);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(oa::k_stab_join, dim3(1), dim3(64), 0, c->stream, (const double *)d_partial.p, (const long long *)d_pcount.p, nb, phase, d_st.p);
+        HIPCHK(hipGetLastError());
+    }
+    oa::StabOut st;
+    if ((rc = read_small(c, &st, d_st.p, sizeof st))) return rc;                         // (waits for everything above: the host's rows and idx included)
+    rep->n_used = st.n_used;
+    rep->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (st.n_used < 1) return fail(OA_E_BAD_ARG, "oa_stability: none of the %lld points has finite coordinates and a finite normal of length > 0", n_used);
+    for (int a = 0; a < 3; ++a) rep->centroid[a] = st.c[a];
+    rep->scale = st.s;
+    memcpy(rep->C, st.C, sizeof st.C);
+    memcpy(rep->eigenvalues, st.eig, sizeof st.eig);
+    memcpy(rep->eigenvectors, st.vec, sizeof st.vec);
+    rep->rank = st.rank;
+    rep->cond = st.cond;
+    rep->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return OA_OK;
 }
 

@@ -95,6 +95,56 @@ def _voxel_args(xyz, voxel, normals, origin, name="voxel_downsample"):
     return xyz, normals, origin
 
 
+MOST_POINTS = 2 ** 31 - 2 ** 20       # what the library's sorts and scans take
+
+
+def _rows3(a, name, what):
+    """An (n, 3) cloud for a standalone call: a torch device tensor as it is, anything else as a contiguous float32 array."""
+    if hasattr(a, "data_ptr") and hasattr(a, "is_cuda"):          # torch tensor, without importing torch
+        if a.dim() != 2 or a.shape[1] != 3 or "float32" not in str(a.dtype):
+            raise ValueError("%s: %s must be (n, 3) float32, got %s %s" % (name, what, tuple(a.shape), a.dtype))
+    else:
+        a = np.asarray(a)
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError("%s: %s must be (n, 3), got shape %s" % (name, what, a.shape))
+        if a.dtype.kind not in "fiu":
+            raise ValueError("%s: %s has dtype %s (numbers)" % (name, what, a.dtype))
+        a = np.ascontiguousarray(a, dtype=np.float32)
+    if not 1 <= a.shape[0] <= MOST_POINTS:
+        raise ValueError("%s: %d rows of %s (1 .. 2^31 - 2^20)" % (name, a.shape[0], what))
+    return a
+
+
+def _whole(v, name, what, lo, hi=None):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+        raise ValueError("%s: %s = %r (a whole number %s)" % (name, what, v, ">= %d" % lo if hi is None else "in %d .. %d" % (lo, hi)))
+    return int(v)
+
+
+def _sample_args(normals, m, grid=8, unoriented=False, seed=0, name="normal_space_sample"):
+    """The arguments of a normal-space sample, checked before any call reaches the library: (normals, m, grid, unoriented, seed)."""
+    normals = _rows3(normals, name, "normals")
+    return (normals, _whole(m, name, "m", 1), _whole(grid, name, "grid", 1, 32), int(bool(unoriented)),
+            _whole(seed, name, "seed", 0, 0xFFFFFFFF))
+
+
+def _stability_args(xyz, normals, idx=None, name="stability"):
+    """The arguments of a stability report, checked before any call reaches the library: (xyz, normals, idx or None)."""
+    xyz, normals = _rows3(xyz, name, "xyz"), _rows3(normals, name, "normals")
+    if tuple(normals.shape) != tuple(xyz.shape):
+        raise ValueError("%s: %s normals for %s points" % (name, tuple(normals.shape), tuple(xyz.shape)))
+    if bool(getattr(xyz, "is_cuda", False)) != bool(getattr(normals, "is_cuda", False)):
+        raise ValueError("%s: xyz and normals must be on the same side (both host arrays or both device tensors)" % name)
+    if idx is not None:
+        idx = np.asarray(idx)
+        if idx.ndim != 1 or idx.dtype.kind not in "iu" or not 1 <= len(idx) <= MOST_POINTS:
+            raise ValueError("%s: idx must be a list of 1 .. 2^31 - 2^20 whole numbers" % name)
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        if idx.min() < 0 or idx.max() >= xyz.shape[0]:
+            raise ValueError("%s: idx reaches outside 0 .. %d" % (name, xyz.shape[0] - 1))
+    return xyz, normals, idx
+
+
 DEVIATION_OUTPUTS = ("signed_d", "dist", "closest", "idx", "feature")
 DEVIATION_SIGNED = {"auto": -1, "never": 0, "required": 1, None: -1, False: 0, True: 1}
 
@@ -738,6 +788,49 @@ class IcpEngine:
                   "dims": tuple(rep.dims), "origin": tuple(rep.origin), "total_ms": rep.total_ms}
         return {"xyz": out[:rows].copy(), "normals": out_n[:rows].copy() if out_n is not None else None, "count": cnt[:rows].copy(),
                 "rep": idx[:rows].copy(), "report": report}
+
+    def normal_space_sample(self, normals, m, grid=8, unoriented=False, seed=0):
+        """Normal-space sampling (Rusinkiewicz & Levoy 2001) of ANY cloud's normals (no target, source or matrices needed; nothing a
+        loop reads is touched): the normals are bucketed on a cube map of grid x grid cells per face and m points are drawn evenly
+        across the buckets, so that the few normals of a small feature are all kept before a flat region gives its second point.
+        normals: (n, 3) host array or torch device tensor, any length; zero and non-finite rows take no part.  unoriented: n and
+        -n share a bucket (estimated normals).  seed: which members of a bucket come first (a hash of the index).  Returns a dict:
+        idx int64 (min(m, eligible),) ascending -- a vlist --, bin int32 (n,) every point's bucket (-1: no part), report."""
+        normals, m, grid, unoriented, seed = _sample_args(normals, m, grid, unoriented, seed)
+        p, on_dev, keep, n = _device_ptr(normals)
+        rep = capi.SampleReport()
+        got = C.c_int64(0)
+        cap = min(m, n)
+        idx = np.empty(cap, np.int64)
+        bins = np.empty(n, np.int32)
+        self._chk(self._L.oa_normal_space_sample(self._h, p, n, on_dev, m, grid, unoriented, seed, cap, capi.iptr(idx),
+                                                 bins.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(got), C.byref(rep)))
+        del keep
+        report = {name: getattr(rep, name) for name, _ in capi.SampleReport._fields_}
+        return {"idx": idx[: int(got.value)].copy(), "bin": bins, "report": report}
+
+    def stability(self, xyz, normals, idx=None):
+        """Which rigid motions does a selection resist under the point-to-plane metric (Gelfand et al. 2003): the 6 x 6 matrix
+        C = sum v v^T, v = [q x n ; n] over the points idx lists (None: all), q = (p - centroid) * scale with scale = 1 / mean
+        |p - centroid|, and its eigen-decomposition.  xyz, normals: (n, 3) host arrays or torch device tensors (both on the same
+        side); rows with a zero or non-finite normal or a non-finite coordinate take no part.  Returns a dict: n_used, centroid
+        (3,), scale, C (6, 6), eigenvalues (6,) descending, eigenvectors (6, 6) -- COLUMN k belongs to eigenvalue k; its rows 0-2
+        are a rotation about the centroid (in lengths times scale), its rows 3-5 a translation --, rank (eigenvalues above 1e-10
+        times the largest), cond (largest over smallest eigenvalue), total_ms.
+        How to read it: a small eigenvalue says that the selection does not resist this screw -- a loop over these points can slide
+        along that motion, and noise decides that part of the pose.  rank < 6: some motion is not constrained at all (a plane
+        3, a sphere 3, a cylinder 4); a large cond: one is constrained much more weakly than another."""
+        xyz, normals, idx = _stability_args(xyz, normals, idx)
+        p, on_dev, keep, n = _device_ptr(xyz)
+        pn, _, keep_n, _ = _device_ptr(normals)
+        rep = capi.StabilityReport()
+        self._chk(self._L.oa_stability(self._h, p, pn, n, on_dev, capi.iptr(idx) if idx is not None else None,
+                                       len(idx) if idx is not None else 0, C.byref(rep)))
+        del keep, keep_n
+        return {"n_used": int(rep.n_used), "centroid": np.array(rep.centroid, np.float64), "scale": float(rep.scale),
+                "C": np.array(rep.C, np.float64).reshape(6, 6), "eigenvalues": np.array(rep.eigenvalues, np.float64),
+                "eigenvectors": np.array(rep.eigenvectors, np.float64).reshape(6, 6), "rank": int(rep.rank), "cond": float(rep.cond),
+                "total_ms": float(rep.total_ms)}
 
     def deviation(self, thresh=float("inf"), signed="auto", quantiles=(0.5, 0.9, 0.95, 0.99), bins=0, hist_range=None,
                   outputs=("signed_d", "closest", "idx", "feature")):

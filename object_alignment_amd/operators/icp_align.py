@@ -83,6 +83,12 @@ class IcpSettings:
     # covered twice does not weigh twice; sample_fraction then applies to that list, as to any vlist.  0 = off: the selection is
     # thinned by index alone, as in the reference
     sample_voxel: float = 0.0
+    # nor these: sample_normal_space > 0 keeps that many of the vertices the loop would have used, drawn evenly across the buckets
+    # of their NORMALS (normal-space sampling, Rusinkiewicz & Levoy 2001; IcpEngine.normal_space_sample with sample_normal_grid
+    # cells per edge of a cube face) -- on a mostly flat part the few vertices of a groove or a rim are all that stops sliding, and
+    # a uniform sample holds next to none of them.  Needs run(..., source_normals=...).  0 = off
+    sample_normal_space: int = 0
+    sample_normal_grid: int = 8
 
 
 @dataclass
@@ -269,6 +275,20 @@ def sample_voxel_of(settings) -> float:
     return float(v)
 
 
+def sample_normal_space_of(settings):
+    """(points, grid) from IcpSettings.sample_normal_space / sample_normal_grid, checked: points 0 (off) or a whole number > 0,
+    grid a whole number in 1 .. 32."""
+    m = getattr(settings, "sample_normal_space", 0)
+    g = getattr(settings, "sample_normal_grid", 8)
+    m = 0 if m is None else m
+    g = 8 if g is None else g
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or m < 0:
+        raise ValueError("IcpSettings.sample_normal_space = %r (0 = off, or a whole number of points > 0)" % (m,))
+    if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 1 <= g <= 32:
+        raise ValueError("IcpSettings.sample_normal_grid = %r (a whole number in 1 .. 32)" % (g,))
+    return int(m), int(g)
+
+
 def world_scale(mx) -> float:
     """cbrt(|det(mx[:3, :3])|): what carries a world-space length to the object's local space."""
     return float(np.cbrt(abs(np.linalg.det(np.asarray(mx, np.float64).reshape(4, 4)[:3, :3]))))
@@ -297,6 +317,34 @@ def voxel_vlist(engine, source_xyz, vlist, mx_align, sample_voxel):
         down = call(pts, sample_voxel / s)
     rep = down["rep"]
     return np.sort(sel[rep] if sel is not None else rep)
+
+
+def _host_rows(a):
+    if hasattr(a, "is_cuda"):
+        a = a.detach().cpu().numpy()
+    return np.asarray(a, np.float32).reshape(-1, 3)
+
+
+def normal_space_vlist(engine, source_xyz, source_normals, vlist, stride, m, grid, unoriented):
+    """m of the vertices a loop over (vlist, stride) would use -- vlist[0::stride], None: every vertex --, drawn evenly across
+    the buckets of their normals (IcpEngine.normal_space_sample): {"idx": their indices into source_xyz, in the candidates' order
+    -- a vlist for stride 1 --, "report": the sampling report, "stability": IcpEngine.stability of the picked set}."""
+    normals = _host_rows(source_normals)
+    n = len(normals)
+    cand = np.arange(n, dtype=np.int64) if vlist is None else np.ascontiguousarray(vlist, dtype=np.int64)
+    cand = cand[:: max(1, int(stride))]
+    if getattr(engine, "multi", False):                        # (a multi-device context has no calls of its own for these)
+        from .. import normal_space_sample, stability
+        dev = {"device": engine.device}
+    else:
+        normal_space_sample, stability = getattr(engine, "normal_space_sample", None), getattr(engine, "stability", None)
+        if normal_space_sample is None or stability is None:
+            raise RuntimeError("this engine has no normal-space sampling")
+        dev = {}
+    drawn = normal_space_sample(normals if vlist is None and max(1, int(stride)) == 1 else normals[cand], m, grid=grid,
+                                unoriented=unoriented, **dev)
+    picked = cand[drawn["idx"]]
+    return {"idx": picked, "report": drawn["report"], "stability": stability(_host_rows(source_xyz), normals, idx=picked, **dev)}
 
 
 def build_vlist(align_obj):
@@ -380,6 +428,11 @@ class IcpAlign:
         loop, which then starts from the pose it found (self.last_coarse holds its report); None: the loop alone.
         settings.sample_voxel > 0: the vertices vlist selects are first thinned to one representative per voxel of that edge
         (voxel_vlist); sample_fraction then applies to that list.
+        settings.sample_normal_space > 0: of the vertices the loop would then use -- vlist, thinned by sample_voxel, every
+        round(1 / sample_fraction)-th of that -- that many are kept, drawn evenly across the buckets of their normals
+        (normal_space_vlist; n and -n share a bucket when the normals were estimated).  Needs source_normals (ValueError
+        otherwise).  self.last_sampling holds the picked indices, the sampling report and the stability report of the picked set;
+        None while the setting is off.
         deviation: a DeviationSettings -- after the loop the deviation report and its arrays are taken at the final pose on the same
         engine (over the points the loop used) and attached as RunResult.deviation; None: nothing else changes."""
         s = self.settings
@@ -393,6 +446,9 @@ class IcpAlign:
         if deviation is not None and not isinstance(deviation, DeviationSettings):
             raise TypeError("deviation %r (a DeviationSettings, or None)" % (deviation,))
         sample_voxel = sample_voxel_of(s)
+        sample_normals, sample_grid = sample_normal_space_of(s)
+        if sample_normals > 0 and source_normals is None:
+            raise ValueError("IcpSettings.sample_normal_space needs source_normals (an array of normals, or 'estimate')")
         thresh = s.min_start                                   # :83
         factor = round(1 / s.sample_fraction)                  # :89  (ZeroDivisionError at 0, as the reference)
         if not thresh > 0:
@@ -414,12 +470,25 @@ class IcpAlign:
         apply_boundary(eng, s)
         if sample_voxel > 0.0:
             vlist = voxel_vlist(eng, source_xyz, vlist, mx_align, sample_voxel)
+        estimate_source = isinstance(source_normals, str)
+
+        def estimated_source_normals():
+            from .. import estimate_normals
+            return estimate_normals(source_xyz, k=int(getattr(s, "normal_k", 16)))[0]
+
+        # the source's normals are estimated ONCE: in front of the upload when the sample needs them, else behind it, where the
+        # estimate has always stood (so that a run without the sample makes its calls in the order it always did)
+        self.last_sampling = None
+        if sample_normals > 0:
+            if estimate_source:
+                source_normals = estimated_source_normals()
+            self.last_sampling = normal_space_vlist(eng, source_xyz, source_normals, vlist, factor, sample_normals, sample_grid, estimate_source)
+            vlist, factor = self.last_sampling["idx"], 1
         eng.set_source(source_xyz, vlist=vlist, stride=factor)
         if source_weights is not None:
             eng.set_source_weights(source_weights)
-        if isinstance(source_normals, str):
-            from .. import estimate_normals
-            source_normals = estimate_normals(source_xyz, k=int(getattr(s, "normal_k", 16)))[0]
+        if estimate_source and sample_normals == 0:
+            source_normals = estimated_source_normals()
         if source_normals is not None:
             eng.set_source_normals(source_normals)
         eng.set_matrices(mx_align, mx_base)
