@@ -775,30 +775,89 @@ oa::PairTest<RECIP> pair_test(const oa_ctx *c)
     return nrm;
 }
 
-// oa_set_reciprocal: what a step with the check on needs, before its loop starts (allocations, and the tree build waits for the
-// stream): the verdict bytes, the counters, and -- once per oa_set_source -- the box tree over the selected source points in
-// align-local space, inside the box of their finite coordinates.  The pose never enters: oa_set_matrices does not touch it.
-// k_recip_check's counters back to zero, and the host waits: whatever stream the next step runs on finds them cleared.  Called
-// with no step in flight (a new source, a changed setting, the allocation): OA_STAT_RECIP_REJECTED never speaks of an older one
-int recip_clear_count(oa_ctx *c)
+// the target normals of a cloud (a surface target takes its triangles' geometric normals: null)
+inline const float *plane_tn(const oa_ctx *c) { return c->tgt.surface ? (const float *)nullptr : (const float *)c->tgt.d_tgt_n; }
+
+// One launch of a kernel that opens with pair_fetch and only reads the pairs (the filters' stages, k_residual_keys): its leading
+// arguments, as launch_accumulate_as's lambda holds the writing kernels'; each caller adds its own behind the test
+template <class Kern, class Test, class... Tail>
+void launch_pair_reader(oa_ctx *c, Kern *kern, unsigned blocks, unsigned threads, const Test &nrm, const Tail &... tail)
 {
-    if (!c->d_recip_count) return OA_OK;
-    HIPCHK(hipMemsetAsync(c->d_recip_count, 0, sizeof(unsigned) * oa::RECIP_COUNT_WORDS, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->src.d_src4, c->src.ns,
+                       (const float *)c->tgt.d_tgt_xyz, (const unsigned long long *)c->src.d_keys,
+                       c->tgt.surface ? (const float4 *)nullptr : (const float4 *)c->src.d_win, c->tgt.surface ? (const float4 *)c->tgt.d_tri9 : (const float4 *)nullptr,
+                       nrm, tail...);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The pair filters, between the search and the accumulation: the reciprocal check (oa_set_reciprocal, oa_recip.hpp),
+// the boundary rejection (oa_set_reject_boundary, oa_boundary.hpp) and the trim (oa_set_trim, oa_trim.hpp).  Each leaves its
+// verdict in src.d_recip_ok, one byte per slot, and a step with any of them on accumulates through the RECIP kernels.  What every
+// caller needs of the three is said once each: on? (verdict_on), the refusals (refuse_filters_shard, refuse_filters_multi), what
+// a step needs before its loop (ensure_filters), the counters back to zero (filters_clear), and the stages of a step in their
+// order (launch_filters, behind launch_trim).  A new filter is added to these and to nothing else.
+// ------------------------------------------------------------------------------------------------
+inline bool trim_on(const oa_ctx *c) { return c->trim_fraction != 0.0; }
+inline bool trim_auto(const oa_ctx *c) { return c->trim_fraction < 0.0; }
+inline bool verdict_on(const oa_ctx *c) { return c->recip_on || trim_on(c) || c->bnd_on; }
+
+// The step counters of the filters in `which` back to zero (those that exist), and the host waits: whatever stream the next step
+// runs on finds them cleared.  Called with no step in flight (a new source, a changed setting, the allocation): the
+// OA_STAT_*_REJECTED and OA_STAT_TRIM_* figures never speak of an older one
+enum : unsigned { FILTER_RECIP = 1u, FILTER_BND = 2u, FILTER_TRIM = 4u, FILTER_ALL = 7u };
+int filters_clear(oa_ctx *c, unsigned which = FILTER_ALL)
+{
+    auto clear = [&](void *d_block, size_t bytes) -> int {
+        if (!d_block) return OA_OK;
+        HIPCHK(hipMemsetAsync(d_block, 0, bytes, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return OA_OK;
+    };
+    int rc = OA_OK;
+    if (which & FILTER_RECIP) rc = clear(c->d_recip_count, sizeof(unsigned) * oa::RECIP_COUNT_WORDS);
+    if (!rc && (which & FILTER_BND)) rc = clear(c->d_bnd_count, sizeof(unsigned) * oa::BND_COUNT_WORDS);
+    if (!rc && (which & FILTER_TRIM)) rc = clear(c->d_trim, sizeof(oa::DevTrim));     // (the last step's figures and the running counters)
+    return rc;
+}
+
+// `who` on a context that holds a shard.  The reciprocal check needs every selected source point, and the trim's cut is an order
+// statistic of the world's residuals: a shard cannot see the other shards'.  The target is replicated, so a shard could answer
+// the boundary question for itself -- but the verdict byte's path has never run in shards.
+// The order is reciprocal, trim, boundary -- not the stages' order: with the trim and the boundary both on, the error names oa_set_trim
+int refuse_filters_shard(const oa_ctx *c, const char *who)
+{
+    if (!verdict_on(c) || !(c->parent || c->src_shards > 1)) return OA_OK;
+    if (c->recip_on)
+        return fail(OA_E_STATE, "%s with the reciprocal check on needs the whole selection on one context: this one holds a shard (upload shard 0 of 1, or call oa_set_reciprocal(ctx, 0, 1))", who);
+    if (trim_on(c))
+        return fail(OA_E_STATE, "%s with oa_set_trim on needs the whole selection on one context: this one holds a shard (upload shard 0 of 1, or call oa_set_trim(ctx, 0, 0, 2))", who);
+    return fail(OA_E_STATE, "%s with oa_set_reject_boundary on needs the whole selection on one context: this one holds a shard (upload shard 0 of 1, or call oa_set_reject_boundary(ctx, 0, 16, 90))", who);
+}
+
+// ... and `who` on a multi-device context, or in the split-phase loop (refuse_wide_row): in the same order
+int refuse_filters_multi(const oa_ctx *c, const char *who)
+{
+    if (c->recip_on)
+        return fail(OA_E_STATE, "%s: the reciprocal check needs every selected source point on one device: it runs on a single-device context through oa_run / oa_iterate / oa_make_pairs (call oa_set_reciprocal(ctx, 0, 1) for this path)", who);
+    if (trim_on(c))
+        return fail(OA_E_STATE, "%s: oa_set_trim needs every selected source point's residual on one device: it runs on a single-device context through oa_run / oa_iterate / oa_make_pairs (call oa_set_trim(ctx, 0, 0, 2) for this path)", who);
+    if (c->bnd_on)
+        return fail(OA_E_STATE, "%s: oa_set_reject_boundary runs on a single-device context through oa_run / oa_iterate / oa_make_pairs (call oa_set_reject_boundary(ctx, 0, 16, 90) for this path)", who);
     return OA_OK;
 }
 
+// oa_set_reciprocal: what a step with the check on needs, before its loop starts (allocations, and the tree build waits for the
+// stream): the counters, and -- once per oa_set_source -- the box tree over the selected source points in align-local space,
+// inside the box of their finite coordinates.  The pose never enters: oa_set_matrices does not touch it.
 int ensure_recip(oa_ctx *c)
 {
     if (!c->recip_on) return OA_OK;
     if (!c->d_recip_count) {                                        // (whatever ns is: an empty selection still reads the stat)
         HIPCHK(dev_malloc(&c->d_recip_count, sizeof(unsigned) * oa::RECIP_COUNT_WORDS));
-        const int rcc = recip_clear_count(c);
+        const int rcc = filters_clear(c, FILTER_RECIP);
         if (rcc) return rcc;
     }
-    if (c->src.ns <= 0) return OA_OK;                                   // an empty selection: no slot, no verdict, no tree -- and no launch (launch_recip)
-    if (!c->src.d_recip_ok) HIPCHK(dev_malloc(&c->src.d_recip_ok, (size_t)c->src.ns));
-    if (c->src.sbvh_ok) return OA_OK;
+    if (c->src.ns <= 0 || c->src.sbvh_ok) return OA_OK;                 // (an empty selection: no slot, no tree -- and no launch)
     c->src.d_sbvh_box.reset(); c->src.d_sbvh_prims.reset();
     const int nb = oa::RECIP_FRAME_BLOCKS;
     DevTmp<float> d_bb;
@@ -820,104 +879,43 @@ int ensure_recip(oa_ctx *c)
     return OA_OK;
 }
 
-// search -> THIS -> the accumulation (or k_residual_keys first): one wave per slot, the verdict bytes and the step's count.
+// the reciprocal check's stage: one wave per slot, every verdict byte and the step's count.
 // metric_n: the pair_fetch<.., METRIC_N> of the accumulation that follows (the plane and GICP metrics; never the emitting one)
 int launch_recip(oa_ctx *c, bool metric_n)
 {
-    if (c->src.ns <= 0) return OA_OK;                                   // no slot to judge: nothing is allocated for it either (ensure_recip)
-    const oa::NormalTest nrm = normal_test(c);                      // (without the verdict: this launch forms it)
     auto *kern = metric_n ? oa::k_recip_check<true> : oa::k_recip_check<false>;
     const unsigned blocks = (unsigned)std::max(1, std::min((c->src.ns + oa::RECIP_WPB - 1) / oa::RECIP_WPB, c->n_cu * 16));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(oa::RECIP_WPB * 64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->src.d_src4, c->src.ns,
-                       (const float *)c->tgt.d_tgt_xyz, (const unsigned long long *)c->src.d_keys,
-                       c->tgt.surface ? (const float4 *)nullptr : (const float4 *)c->src.d_win, c->tgt.surface ? (const float4 *)c->tgt.d_tri9 : (const float4 *)nullptr, nrm,
-                       c->tgt.surface ? (const float *)nullptr : (const float *)c->tgt.d_tgt_n, c->src.sbvh, (const float4 *)c->src.d_sbvh_box,
-                       (const float4 *)c->src.d_sbvh_prims, (float)(c->recip_ratio * c->recip_ratio), c->src.d_recip_ok, c->d_recip_count);
+    // (the test without the verdict: this launch forms it)
+    launch_pair_reader(c, kern, blocks, (unsigned)(oa::RECIP_WPB * 64), normal_test(c), plane_tn(c), c->src.sbvh, (const float4 *)c->src.d_sbvh_box,
+                       (const float4 *)c->src.d_sbvh_prims, (float)(c->recip_ratio * c->recip_ratio), (unsigned char *)c->src.d_recip_ok, (unsigned *)c->d_recip_count);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
 
-// the check needs every selected source point: a context that holds only a shard cannot see the other shards' 
-const char *const RECIP_ONE_DEVICE = ": the reciprocal check needs every selected source point on one device: it runs on a single-device context through oa_run / oa_iterate / oa_make_pairs (call oa_set_reciprocal(ctx, 0, 1) for this path)";
-int refuse_recip_shard(const oa_ctx *c, const char *who)
-{
-    if (c->recip_on && (c->parent || c->src_shards > 1))
-        return fail(OA_E_STATE, "%s with the reciprocal check on needs the whole selection on one context: this one holds a shard (upload shard 0 of 1, or call oa_set_reciprocal(ctx, 0, 1))", who);
-    return OA_OK;
-}
-
-// oa_set_trim (oa_trim.hpp): the verdict bytes are the reciprocal check's, so a trimmed step accumulates through the RECIP kernels
-inline bool trim_on(const oa_ctx *c) { return c->trim_fraction != 0.0; }
-inline bool trim_auto(const oa_ctx *c) { return c->trim_fraction < 0.0; }
-inline bool verdict_on(const oa_ctx *c) { return c->recip_on || trim_on(c) || c->bnd_on; }
-
-// oa_set_reject_boundary (oa_boundary.hpp): the verdict goes into the reciprocal check's bytes too.  The target is replicated, so a
-// shard could answer for itself -- but the verdict byte's path has never run in shards
-const char *const BND_ONE_DEVICE = ": oa_set_reject_boundary runs on a single-device context through oa_run / oa_iterate / oa_make_pairs (call oa_set_reject_boundary(ctx, 0, 16, 90) for this path)";
-int refuse_bnd_shard(const oa_ctx *c, const char *who)
-{
-    if (c->bnd_on && (c->parent || c->src_shards > 1))
-        return fail(OA_E_STATE, "%s with oa_set_reject_boundary on needs the whole selection on one context: this one holds a shard (upload shard 0 of 1, or call oa_set_reject_boundary(ctx, 0, 16, 90))", who);
-    return OA_OK;
-}
-
-// k_boundary_verdict's counters back to zero, and the host waits (recip_clear_count's reasons)
-int bnd_clear_count(oa_ctx *c)
-{
-    if (!c->d_bnd_count) return OA_OK;
-    HIPCHK(hipMemsetAsync(c->d_bnd_count, 0, sizeof(unsigned) * oa::BND_COUNT_WORDS, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return OA_OK;
-}
-
-// what a step with the setting on needs, before its loop starts: the counters, the verdict bytes and the target's masks
+// oa_set_reject_boundary: what a step with the setting on needs, before its loop starts: the counters and the target's masks
 int ensure_bnd_step(oa_ctx *c)
 {
     if (!c->bnd_on) return OA_OK;
     if (!c->d_bnd_count) {
         HIPCHK(dev_malloc(&c->d_bnd_count, sizeof(unsigned) * oa::BND_COUNT_WORDS));
-        const int rcc = bnd_clear_count(c);
+        const int rcc = filters_clear(c, FILTER_BND);
         if (rcc) return rcc;
     }
-    if (c->src.ns > 0 && !c->src.d_recip_ok) HIPCHK(dev_malloc(&c->src.d_recip_ok, (size_t)c->src.ns));
     return ensure_boundary(c, c->bnd_k, c->bnd_angle);
 }
 
-// search -> [k_recip_check] -> THIS -> [the trim] -> ... -> the accumulation: byte 0 for every pair on the target's boundary
+// the boundary rejection's stage: byte 0 for every pair on the target's boundary
 int launch_boundary(oa_ctx *c)
 {
-    if (c->src.ns <= 0) return OA_OK;                                   // no slot to judge
-    if (!c->recip_on) HIPCHK(hipMemsetAsync(c->src.d_recip_ok, 1, (size_t)c->src.ns, c->stream));   // (else k_recip_check has just written every byte)
     const unsigned blocks = (unsigned)std::max(1, std::min((c->src.ns + oa::BND_VERDICT_THREADS - 1) / oa::BND_VERDICT_THREADS, c->n_cu * 2));
-    hipLaunchKernelGGL(oa::k_boundary_verdict, dim3(blocks), dim3(oa::BND_VERDICT_THREADS), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->src.d_src4,
-                       c->src.ns, (const float *)c->tgt.d_tgt_xyz, (const unsigned long long *)c->src.d_keys,
-                       c->tgt.surface ? (const float4 *)nullptr : (const float4 *)c->src.d_win, c->tgt.surface ? (const float4 *)c->tgt.d_tri9 : (const float4 *)nullptr,
-                       normal_test(c), (const int *)c->tgt.d_tris, (const unsigned char *)c->tgt.d_bnd_emask, (const unsigned char *)c->tgt.d_bnd_vmask,
-                       c->src.d_recip_ok, c->d_bnd_count);
+    launch_pair_reader(c, oa::k_boundary_verdict, blocks, (unsigned)oa::BND_VERDICT_THREADS, normal_test(c), (const int *)c->tgt.d_tris,
+                       (const unsigned char *)c->tgt.d_bnd_emask, (const unsigned char *)c->tgt.d_bnd_vmask, (unsigned char *)c->src.d_recip_ok, (unsigned *)c->d_bnd_count);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
 
-// the cut is an order statistic of the world's residuals: a context that holds only a shard cannot form it
-const char *const TRIM_ONE_DEVICE = ": oa_set_trim needs every selected source point's residual on one device: it runs on a single-device context through oa_run / oa_iterate / oa_make_pairs (call oa_set_trim(ctx, 0, 0, 2) for this path)";
-int refuse_trim_shard(const oa_ctx *c, const char *who)
-{
-    if (trim_on(c) && (c->parent || c->src_shards > 1))
-        return fail(OA_E_STATE, "%s with oa_set_trim on needs the whole selection on one context: this one holds a shard (upload shard 0 of 1, or call oa_set_trim(ctx, 0, 0, 2))", who);
-    return OA_OK;
-}
-
-// the last step's figures and the running counters back to zero, and the host waits (recip_clear_count's reasons)
-int trim_clear(oa_ctx *c)
-{
-    if (!c->d_trim) return OA_OK;
-    HIPCHK(hipMemsetAsync(c->d_trim, 0, sizeof(oa::DevTrim), c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return OA_OK;
-}
-
-// what a step with the trim on needs, before its loop starts: the verdict bytes, the keys, the trim's state with the setting in
-// it, and the buffers of the mode in force -- never allocated inside the loop
+// oa_set_trim: what a step with the trim on needs, before its loop starts: the keys, the trim's state with the setting in it, and
+// the buffers of the mode in force -- never allocated inside the loop
 int ensure_trim(oa_ctx *c)
 {
     if (!trim_on(c)) return OA_OK;
@@ -925,7 +923,7 @@ int ensure_trim(oa_ctx *c)
         return fail(OA_E_CAPACITY, "oa_set_trim: the estimated share takes up to %lld points (this selection: %d)", oa::TRIM_AUTO_MAX, c->src.ns);
     if (!c->d_trim) {
         HIPCHK(dev_malloc(&c->d_trim, sizeof(oa::DevTrim)));
-        const int rcc = trim_clear(c);
+        const int rcc = filters_clear(c, FILTER_TRIM);
         if (rcc) return rcc;
     }
     {   // the setting: everything in front of the counters (the stream is idle or about to be waited for; the figures stay)
@@ -937,9 +935,8 @@ int ensure_trim(oa_ctx *c)
         HIPCHK(hipMemcpyAsync(c->d_trim, &h, offsetof(oa::DevTrim, running), hipMemcpyHostToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
-    if (c->src.ns <= 0) return OA_OK;                                   // an empty selection: no slot, no launch (launch_trim)
+    if (c->src.ns <= 0) return OA_OK;                                   // an empty selection: no slot, no launch
     const size_t ns = (size_t)c->src.ns;
-    if (!c->src.d_recip_ok) HIPCHK(dev_malloc(&c->src.d_recip_ok, ns));
     if (!c->src.d_rkeys) HIPCHK(dev_malloc(&c->src.d_rkeys, sizeof(uint32_t) * ns));
     if (!c->d_trim_hist) HIPCHK(dev_malloc(&c->d_trim_hist, sizeof(uint32_t) * oa::SEL_LEVELS * oa::SEL_BINS));
     if (trim_auto(c)) {
@@ -951,6 +948,18 @@ int ensure_trim(oa_ctx *c)
         if (!c->src.d_trim_min) HIPCHK(dev_malloc(&c->src.d_trim_min, sizeof(oa::TrimTileMin) * n_tiles));
     }
     return OA_OK;
+}
+
+// What a step needs of the filters that are on, before its loop starts and never inside it: the verdict bytes (allocated here and
+// nowhere else; an empty selection has no slot and gets none), then each filter's own -- the source tree, the trim's state, the
+// target's masks, all on this stream
+int ensure_filters(oa_ctx *c)
+{
+    int rc;
+    if (verdict_on(c) && c->src.ns > 0 && !c->src.d_recip_ok) HIPCHK(dev_malloc(&c->src.d_recip_ok, (size_t)c->src.ns));
+    if ((rc = ensure_recip(c))) return rc;
+    if ((rc = ensure_trim(c))) return rc;
+    return ensure_bnd_step(c);
 }
 
 // acc: a whole-shard search of the loop that also takes the pair test and the sums (k_bvh_search<TRI, true>)
@@ -1077,6 +1086,11 @@ struct SearchChoice {
 inline bool weighted(const oa_ctx *c) { return c->loss != OA_LOSS_NONE || c->src.d_w != nullptr; }
 // the metrics that sum the wide row (NSUMS_PLANE) and take the 6 x 6 solve: point-to-plane, plane-to-plane (GICP) and symmetric
 inline bool plane_row_metric(const oa_ctx *c) { return c->metric == OA_METRIC_PLANE || c->metric == OA_METRIC_GICP || c->metric == OA_METRIC_SYMMETRIC; }
+// ... by the name the error texts give them ("the %s metric"); null: the point metric
+inline const char *normal_metric_noun(int metric)
+{
+    return metric == OA_METRIC_PLANE ? "plane" : metric == OA_METRIC_GICP ? "GICP" : metric == OA_METRIC_SYMMETRIC ? "symmetric" : nullptr;
+}
 // ... and the loss takes its scale from the step's own residuals (oa_set_robust_auto; inert without a loss)
 inline bool auto_scale(const oa_ctx *c) { return c->loss != OA_LOSS_NONE && c->robust_p > 0.0; }
 
@@ -1386,13 +1400,10 @@ template <bool RECIP>
 void launch_residual_keys(oa_ctx *c, int metric, uint32_t *hist)
 {
     const oa::PairTest<RECIP> nrm = pair_test<RECIP>(c);
-    // (launch_accumulate's leading arguments and selections, read-only and without prev; <false> never reads plane_tn)
+    // (launch_accumulate's selections; <false> never reads plane_tn)
     auto launch = [&](auto *kern, auto... tail) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)plane_blocks(c)), dim3((unsigned)plane_threads(c)), 0, c->stream, (const oa::DevState *)c->d_state,
-                           (const float4 *)c->src.d_src4, c->src.ns, (const float *)c->tgt.d_tgt_xyz, (const unsigned long long *)c->src.d_keys,
-                           c->tgt.surface ? (const float4 *)nullptr : (const float4 *)c->src.d_win, c->tgt.surface ? (const float4 *)c->tgt.d_tri9 : (const float4 *)nullptr, nrm,
-                           c->tgt.surface ? (const float *)nullptr : (const float *)c->tgt.d_tgt_n, tail..., (const float *)c->src.d_w, c->src.d_rkeys, hist,
-                           &c->d_state->t_acc_start);
+        launch_pair_reader(c, kern, (unsigned)plane_blocks(c), (unsigned)plane_threads(c), nrm, plane_tn(c), tail..., (const float *)c->src.d_w,
+                           (uint32_t *)c->src.d_rkeys, hist, &c->d_state->t_acc_start);
     };
     if constexpr (RECIP) { if (metric == OA_METRIC_GICP) { launch(oa::k_residual_keys_gicp<true>, (const float *)c->src.d_src_n); return; } }
     if (metric == OA_METRIC_SYMMETRIC) { launch(oa::k_residual_keys_symm<RECIP>, (const float *)c->src.d_src_n); return; }
@@ -1412,13 +1423,10 @@ int launch_robust_scale(oa_ctx *c)
     return OA_OK;
 }
 
-// oa_set_trim: search -> [k_recip_check] -> THIS -> [launch_robust_scale, over the survivors] -> the accumulation.  The keys of the
-// candidates, the cut (fixed share: the radix select with DevTrim::sel as its state; estimated: sort, prefix sums of r^2, argmin of
-// J), the verdict bytes -- all on the loop's stream (oa_trim.hpp).  metric: whose residual (oa_make_pairs: the point metric's)
+// the trim's stage: the keys of the candidates, the cut (fixed share: the radix select with DevTrim::sel as its state; estimated:
+// sort, prefix sums of r^2, argmin of J), the verdict bytes -- all on the loop's stream (oa_trim.hpp).  metric: whose residual
 int launch_trim(oa_ctx *c, int metric)
 {
-    if (c->src.ns <= 0) return OA_OK;                                   // no slot to judge: nothing is allocated for it either (ensure_trim)
-    if (!c->recip_on && !c->bnd_on) HIPCHK(hipMemsetAsync(c->src.d_recip_ok, 1, (size_t)c->src.ns, c->stream));   // (else k_recip_check / launch_boundary has just written every byte)
     HIPCHK(hipMemsetAsync(c->d_trim_hist, 0, sizeof(uint32_t) * oa::SEL_LEVELS * oa::SEL_BINS, c->stream));
     launch_residual_keys<true>(c, metric, c->d_trim_hist);
     const oa::DevState *st = c->d_state;
@@ -1447,6 +1455,22 @@ int launch_trim(oa_ctx *c, int metric)
     const unsigned vblocks = (unsigned)std::min(oa::TRIM_VERDICT_MAX_BLOCKS, std::max(1, (c->src.ns + oa::TRIM_THREADS - 1) / oa::TRIM_THREADS));
     hipLaunchKernelGGL(oa::k_trim_verdict, dim3(vblocks), dim3(oa::TRIM_THREADS), 0, c->stream, st, c->d_trim, (const uint32_t *)c->src.d_rkeys, c->src.ns, c->src.d_recip_ok);
     HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+
+// The filters' stages of one step, on the step's stream: search -> k_recip_check -> k_boundary_verdict -> the trim ->
+// [launch_robust_scale, over the survivors] -> the accumulation.  This function alone holds the order and decides who
+// writes the verdict bytes first: k_recip_check writes every byte; without it the bytes are set to 1 ahead of the first stage that
+// is on, and every later stage only takes pairs away.  metric, metric_n: the accumulation that follows (whose residual the trim
+// cuts on, and its pair_fetch<.., METRIC_N>); oa_make_pairs does not look at the metric: the point residual
+int launch_filters(oa_ctx *c, int metric, bool metric_n)
+{
+    int rc;
+    if (!verdict_on(c) || c->src.ns <= 0) return OA_OK;                 // (no slot to judge: nothing is allocated for it either, ensure_filters)
+    if (!c->recip_on) HIPCHK(hipMemsetAsync(c->src.d_recip_ok, 1, (size_t)c->src.ns, c->stream));
+    if (c->recip_on && (rc = launch_recip(c, metric_n))) return rc;
+    if (c->bnd_on && (rc = launch_boundary(c))) return rc;
+    if (trim_on(c) && (rc = launch_trim(c, metric))) return rc;
     return OA_OK;
 }
 
@@ -1494,9 +1518,7 @@ int launch_search_accumulate(oa_ctx *c, bool timed, oa::RowSel &sel, bool &fused
         c->ev_used++;
     }
     if (!fused) {
-        if (c->recip_on && (rc = launch_recip(c, plane_row_metric(c)))) return rc;
-        if (c->bnd_on && (rc = launch_boundary(c))) return rc;
-        if (trim_on(c) && (rc = launch_trim(c, c->metric))) return rc;
+        if ((rc = launch_filters(c, c->metric, plane_row_metric(c)))) return rc;
         if (auto_scale(c) && (rc = launch_robust_scale(c))) return rc;
         if ((rc = launch_accumulate(c, false, nullptr, nullptr))) return rc;
         sel = plain_rows(c);
@@ -1642,40 +1664,22 @@ int begin_loop(oa_ctx *c, const oa_settings *st, int iters)
     if (rc) return rc;
     if (!st) return fail(OA_E_BAD_ARG, "null settings");
     if (!(st->thresh > 0.0)) return fail(OA_E_BAD_THRESH, "thresh must be > 0 (the reference's make_pairs returns None)");
-    if (c->metric == OA_METRIC_PLANE) {
-        if (st->with_scale) return fail(OA_E_BAD_ARG, "the plane metric solves for a rigid step: with_scale must be 0 (or call oa_set_metric(ctx, OA_METRIC_POINT))");
+    if (const char *noun = normal_metric_noun(c->metric)) {            // the metrics that read normals: a rigid step, and the wider row
+        if (st->with_scale) return fail(OA_E_BAD_ARG, "the %s metric solves for a rigid step: with_scale must be 0 (or call oa_set_metric(ctx, OA_METRIC_POINT))", noun);
         if (!c->tgt.surface && !c->tgt.d_tgt_n)
-            return fail(OA_E_STATE, "the plane metric needs target normals: call oa_set_target_normals (or oa_set_normals) after oa_set_target, or upload a mesh with oa_set_target_mesh");
-        if ((long long)c->src.ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
-            return fail(OA_E_CAPACITY, "the plane metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->src.ns);
-    } else if (c->metric == OA_METRIC_GICP) {
-        if (st->with_scale) return fail(OA_E_BAD_ARG, "the GICP metric solves for a rigid step: with_scale must be 0 (or call oa_set_metric(ctx, OA_METRIC_POINT))");
-        if (!c->tgt.surface && !c->tgt.d_tgt_n)
-            return fail(OA_E_STATE, "the GICP metric needs target normals: call oa_set_target_normals (or oa_set_normals) after oa_set_target, or upload a mesh with oa_set_target_mesh");
-        if (!c->src.d_src_n)
-            return fail(OA_E_STATE, "the GICP metric needs source normals: call oa_set_source_normals (or oa_set_normals) after oa_set_source");
-        if (auto_scale(c))
+            return fail(OA_E_STATE, "the %s metric needs target normals: call oa_set_target_normals (or oa_set_normals) after oa_set_target, or upload a mesh with oa_set_target_mesh", noun);
+        if (c->metric != OA_METRIC_PLANE && !c->src.d_src_n)          // (the plane metric reads the target's alone)
+            return fail(OA_E_STATE, "the %s metric needs source normals: call oa_set_source_normals (or oa_set_normals) after oa_set_source", noun);
+        if (c->metric == OA_METRIC_GICP && auto_scale(c))             // (GICP alone: its loss takes a fixed scale)
             return fail(OA_E_STATE, "the GICP metric takes a robust loss with a fixed scale only: call oa_set_robust_auto(ctx, 0, 0) (or oa_set_metric(ctx, OA_METRIC_PLANE))");
         if ((long long)c->src.ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
-            return fail(OA_E_CAPACITY, "the GICP metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->src.ns);
-    } else if (c->metric == OA_METRIC_SYMMETRIC) {
-        if (st->with_scale) return fail(OA_E_BAD_ARG, "the symmetric metric solves for a rigid step: with_scale must be 0 (or call oa_set_metric(ctx, OA_METRIC_POINT))");
-        if (!c->tgt.surface && !c->tgt.d_tgt_n)
-            return fail(OA_E_STATE, "the symmetric metric needs target normals: call oa_set_target_normals (or oa_set_normals) after oa_set_target, or upload a mesh with oa_set_target_mesh");
-        if (!c->src.d_src_n)
-            return fail(OA_E_STATE, "the symmetric metric needs source normals: call oa_set_source_normals (or oa_set_normals) after oa_set_source");
-        if ((long long)c->src.ns > (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS)
-            return fail(OA_E_CAPACITY, "the symmetric metric takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->src.ns);
+            return fail(OA_E_CAPACITY, "the %s metric takes shards of up to %lld points (this one: %d): use more shards", noun, (long long)oa::PLANE_MAX_BLOCKS * oa::PLANE_THREADS, c->src.ns);
     } else if (weighted(c) && (long long)c->src.ns > (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS)
         return fail(OA_E_CAPACITY, "a weighted loop takes shards of up to %lld points (this one: %d): use more shards", (long long)oa::PLANE_MAX_BLOCKS * oa::WEIGHTED_THREADS, c->src.ns);
-    if ((rc = refuse_recip_shard(c, "a loop"))) return rc;
-    if ((rc = refuse_trim_shard(c, "a loop"))) return rc;
-    if ((rc = refuse_bnd_shard(c, "a loop"))) return rc;
+    if ((rc = refuse_filters_shard(c, "a loop"))) return rc;
     if ((rc = use_device(c))) return rc;
     if ((rc = ensure_common(c))) return rc;
-    if ((rc = ensure_recip(c))) return rc;                          // (the source tree: before the loop starts, never inside it)
-    if ((rc = ensure_trim(c))) return rc;
-    if ((rc = ensure_bnd_step(c))) return rc;                       // (the target's masks: on this stream, before the loop starts)
+    if ((rc = ensure_filters(c))) return rc;
     if ((rc = ensure_history(c, iters == ITERATE_OPEN ? ITERATE_RING : iters))) return rc;   // oa_iterate: a small ring
     if (auto_scale(c)) {                                          // the selection's buffers; its histograms start (and are kept) at zero
         if (!c->src.d_rkeys) HIPCHK(dev_malloc(&c->src.d_rkeys, sizeof(uint32_t) * (size_t)std::max(1, c->src.ns)));
@@ -3584,9 +3588,7 @@ int source_reset(oa_ctx *c, long long count, long long begin, long long n_verts)
     HIPCHK(hipStreamSynchronize(c->stream));
     c->loop_active = false;                                         // an open oa_iterate sequence ends with the old source
     c->src = {};                                                    // the old shard: its points, seeds, tree, verdicts and scratch
-    { const int rcc = recip_clear_count(c); if (rcc) return rcc; }  // ... and the old source's counts
-    { const int rcc = bnd_clear_count(c); if (rcc) return rcc; }
-    { const int rcc = trim_clear(c); if (rcc) return rcc; }         // (oa_set_trim's figures spoke of the old source)
+    { const int rcc = filters_clear(c); if (rcc) return rcc; }      // ... and the old source's counts and figures
     c->src.shard_begin = begin;
     c->normals_on = false;
     c->src.src_n_verts = n_verts;
@@ -3857,20 +3859,39 @@ OA_EXPORT int oa_set_normals(oa_ctx *c, const float *src_normals, int64_t n_vert
     return OA_OK;
 }
 
+namespace {
+// A changed setting ends the running sequence: the next oa_iterate starts a new one from the current matrix_world (a
+// single-device context fetches it first)
+int end_sequence(oa_ctx *c)
+{
+    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); }
+    else if (c->loop_active) {
+        int rc = use_device(c);
+        if (rc) return rc;
+        if ((rc = fetch_state(c))) return rc;
+    }
+    c->loop_active = false;
+    return OA_OK;
+}
+
+// ... and a changed filter setting (`which`, counters = its block if it exists) also clears that filter's counters: the last
+// step's figures were the old setting's.  (A multi-device parent keeps the setting itself and refuses the loops: its children
+// never see it.)
+int filter_setting_changed(oa_ctx *c, unsigned which, const void *counters)
+{
+    if (!counters) return OA_OK;
+    const int rc = use_device(c);
+    return rc ? rc : filters_clear(c, which);
+}
+}  // namespace
+
 OA_EXPORT int oa_set_metric(oa_ctx *c, int metric)
 {
     if (!c) return fail(OA_E_BAD_ARG, "null context");
     if (metric != OA_METRIC_POINT && metric != OA_METRIC_PLANE && metric != OA_METRIC_GICP && metric != OA_METRIC_SYMMETRIC)
         return fail(OA_E_BAD_ARG, "metric %d (use OA_METRIC_POINT / OA_METRIC_PLANE / OA_METRIC_GICP / OA_METRIC_SYMMETRIC)", metric);
     if (metric == c->metric) return OA_OK;
-    // a changed metric ends the running sequence: the next oa_iterate starts a new one from the current matrix_world
-    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
-    else if (c->loop_active) {
-        int rc = use_device(c);
-        if (rc) return rc;
-        if ((rc = fetch_state(c))) return rc;
-        c->loop_active = false;
-    }
+    if (const int rc = end_sequence(c)) return rc;
     c->metric = metric;
     OA_ROUTE_ALL(c, oa_set_metric(sub, metric));
     return OA_OK;
@@ -3881,14 +3902,7 @@ OA_EXPORT int oa_set_gicp(oa_ctx *c, double epsilon)
     if (!c) return fail(OA_E_BAD_ARG, "null context");
     if (!(epsilon >= 1e-6 && epsilon <= 1.0)) return fail(OA_E_BAD_ARG, "oa_set_gicp: epsilon must be finite and in [1e-6, 1]");
     if (epsilon == c->gicp_eps) return OA_OK;
-    // a changed setting ends the running sequence, as a changed metric does
-    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
-    else if (c->loop_active) {
-        int rc = use_device(c);
-        if (rc) return rc;
-        if ((rc = fetch_state(c))) return rc;
-        c->loop_active = false;
-    }
+    if (const int rc = end_sequence(c)) return rc;
     c->gicp_eps = epsilon;
     OA_ROUTE_ALL(c, oa_set_gicp(sub, epsilon));
     return OA_OK;
@@ -3903,14 +3917,7 @@ OA_EXPORT int oa_set_robust(oa_ctx *c, int loss, double scale)
         return fail(OA_E_BAD_ARG, "oa_set_robust: the scale must be finite and > 0 (world units, like thresh)");
     if (loss == OA_LOSS_NONE) scale = 0.0;
     if (loss == c->loss && scale == c->robust_c) return OA_OK;
-    // a changed loss ends the running sequence, as a changed metric does
-    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
-    else if (c->loop_active) {
-        int rc = use_device(c);
-        if (rc) return rc;
-        if ((rc = fetch_state(c))) return rc;
-        c->loop_active = false;
-    }
+    if (const int rc = end_sequence(c)) return rc;
     c->loss = loss;
     c->robust_c = scale;
     c->last_robust_c = 0.0;
@@ -3927,14 +3934,7 @@ OA_EXPORT int oa_set_robust_auto(oa_ctx *c, double quantile, double scale_min)
         return fail(OA_E_BAD_ARG, "oa_set_robust_auto: the floor of the scale must be finite and > 0 (world units, like thresh)");
     if (quantile == 0.0) scale_min = 0.0;
     if (quantile == c->robust_p && scale_min == c->robust_cmin) return OA_OK;
-    // a changed setting ends the running sequence, as oa_set_robust does
-    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
-    else if (c->loop_active) {
-        int rc = use_device(c);
-        if (rc) return rc;
-        if ((rc = fetch_state(c))) return rc;
-        c->loop_active = false;
-    }
+    if (const int rc = end_sequence(c)) return rc;
     c->robust_p = quantile;
     c->robust_cmin = scale_min;
     c->last_robust_c = 0.0;
@@ -3948,23 +3948,10 @@ OA_EXPORT int oa_set_reciprocal(oa_ctx *c, int on, double ratio)
     if (!(ratio >= 1.0 && ratio <= 16.0)) return fail(OA_E_BAD_ARG, "oa_set_reciprocal: the ratio must be in [1, 16] (1: strictly mutual)");
     const bool want = on != 0;
     if (want == c->recip_on && ratio == c->recip_ratio) return OA_OK;
-    // a changed setting ends the running sequence, as oa_set_robust does
-    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
-    else if (c->loop_active) {
-        int rc = use_device(c);
-        if (rc) return rc;
-        if ((rc = fetch_state(c))) return rc;
-        c->loop_active = false;
-    }
-    // (a multi-device parent keeps the setting itself and refuses the loops: its children never see it)
+    if (const int rc = end_sequence(c)) return rc;
     c->recip_on = want;
     c->recip_ratio = ratio;
-    if (c->d_recip_count) {                                         // the last step's count was the old setting's
-        int rc = use_device(c);
-        if (rc) return rc;
-        if ((rc = recip_clear_count(c))) return rc;
-    }
-    return OA_OK;
+    return filter_setting_changed(c, FILTER_RECIP, c->d_recip_count);
 }
 
 OA_EXPORT int oa_set_trim(oa_ctx *c, double fraction, double fraction_min, double lambda)
@@ -3977,24 +3964,11 @@ OA_EXPORT int oa_set_trim(oa_ctx *c, double fraction, double fraction_min, doubl
     if (!(lambda >= 0.5 && lambda <= 8.0)) return fail(OA_E_BAD_ARG, "oa_set_trim: lambda must be in [0.5, 8]");
     if (!est) fraction_min = c->trim_min;                           // (ignored: the stored one stays)
     if (fraction == c->trim_fraction && fraction_min == c->trim_min && lambda == c->trim_lambda) return OA_OK;
-    // a changed setting ends the running sequence, as oa_set_reciprocal does
-    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
-    else if (c->loop_active) {
-        int rc = use_device(c);
-        if (rc) return rc;
-        if ((rc = fetch_state(c))) return rc;
-        c->loop_active = false;
-    }
-    // (a multi-device parent keeps the setting itself and refuses the loops: its children never see it)
+    if (const int rc = end_sequence(c)) return rc;
     c->trim_fraction = fraction;
     c->trim_min = fraction_min;
     c->trim_lambda = lambda;
-    if (c->d_trim) {                                                // the last step's figures were the old setting's
-        int rc = use_device(c);
-        if (rc) return rc;
-        if ((rc = trim_clear(c))) return rc;
-    }
-    return OA_OK;
+    return filter_setting_changed(c, FILTER_TRIM, c->d_trim);
 }
 
 namespace {
@@ -4017,35 +3991,18 @@ OA_EXPORT int oa_set_reject_boundary(oa_ctx *c, int on, int k, double angle_deg)
     if (rc) return rc;
     const bool want = on != 0;
     if (want == c->bnd_on && k == c->bnd_k && angle_deg == c->bnd_angle) return OA_OK;
-    // a changed setting ends the running sequence, as oa_set_reciprocal does
-    if (!c->subs.empty()) { if (c->loop_active) multi_abort(c); c->loop_active = false; }
-    else if (c->loop_active) {
-        if ((rc = use_device(c))) return rc;
-        if ((rc = fetch_state(c))) return rc;
-        c->loop_active = false;
-    }
-    // (a multi-device parent keeps the setting itself and refuses the loops: its children never see it)
+    if ((rc = end_sequence(c))) return rc;
     c->bnd_on = want;
     c->bnd_k = k;
     c->bnd_angle = angle_deg;
-    if (c->d_bnd_count) {                                           // the last step's count was the old setting's
-        if ((rc = use_device(c))) return rc;
-        if ((rc = bnd_clear_count(c))) return rc;
-    }
-    return OA_OK;
+    return filter_setting_changed(c, FILTER_BND, c->d_bnd_count);
 }
 
 OA_EXPORT int oa_set_source_weights(oa_ctx *c, const float *w, int64_t n_verts)
 {
     if (!c) return fail(OA_E_BAD_ARG, "null context");
-    if (!c->subs.empty() && c->loop_active) multi_abort(c);
+    if (const int rc = end_sequence(c)) return rc;
     OA_ROUTE_ALL_PAR(c, oa_set_source_weights(sub, w, n_verts));      // every child gathers its own shard
-    if (c->loop_active) {
-        int rc = use_device(c);
-        if (rc) return rc;
-        if ((rc = fetch_state(c))) return rc;
-        c->loop_active = false;
-    }
     if (!w) {                                                        // switched off
         if (c->src.d_w) { int rc = use_device(c); if (rc) return rc; HIPCHK(hipStreamSynchronize(c->stream)); c->src.d_w.reset(); }
         return OA_OK;
@@ -4228,27 +4185,19 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
     }
     if (what == OA_STAT_RECIPROCAL) { *value = c->recip_on ? 1.0 : 0.0; return OA_OK; }
     if (what == OA_STAT_RECIPROCAL_RATIO) { *value = c->recip_ratio; return OA_OK; }
-    if (what == OA_STAT_RECIP_REJECTED) {
+    if (what == OA_STAT_RECIP_REJECTED || what == OA_STAT_BOUNDARY_REJECTED) {     // word 2 of the filter's counters: the last step's
+        const bool recip = what == OA_STAT_RECIP_REJECTED;
+        const unsigned *d_count = recip ? c->d_recip_count : c->d_bnd_count;
         *value = 0.0;
-        if (!c->recip_on || !c->d_recip_count) return OA_OK;
+        if (!(recip ? c->recip_on : c->bnd_on) || !d_count) return OA_OK;
         int rc = use_device(c);
         if (rc) return rc;
         unsigned n = 0;
-        if ((rc = read_small(c, &n, c->d_recip_count + 2, sizeof n))) return rc;
+        if ((rc = read_small(c, &n, d_count + 2, sizeof n))) return rc;
         *value = (double)n;
         return OA_OK;
     }
     if (what == OA_STAT_REJECT_BOUNDARY) { *value = c->bnd_on ? 1.0 : 0.0; return OA_OK; }
-    if (what == OA_STAT_BOUNDARY_REJECTED) {
-        *value = 0.0;
-        if (!c->bnd_on || !c->d_bnd_count) return OA_OK;
-        int rc = use_device(c);
-        if (rc) return rc;
-        unsigned n = 0;
-        if ((rc = read_small(c, &n, c->d_bnd_count + 2, sizeof n))) return rc;
-        *value = (double)n;
-        return OA_OK;
-    }
     if (what == OA_STAT_TRIM) { *value = c->trim_fraction; return OA_OK; }
     if (what == OA_STAT_TRIM_CANDIDATES || what == OA_STAT_TRIM_KEPT || what == OA_STAT_TRIM_CUT) {
         *value = 0.0;
@@ -4453,13 +4402,25 @@ OA_EXPORT int oa_nn_search(oa_ctx *c, int64_t *idx, float *d2, double *kernel_ms
 // ================================================================================================
 // contract 1: make_pairs
 // ================================================================================================
+namespace {
+// one pass over the pairs, around the pivot c->d_pivot0: the state, the search, the filters (on the point residual: oa_make_pairs
+// does not look at the metric), the emitting accumulation (k_pair_accumulate<true>) and its reduce
+int make_pairs_pass(oa_ctx *c, double thresh)
+{
+    int rc;
+    if ((rc = push_state_for_oneshot(c, thresh, true))) return rc;
+    if ((rc = launch_nn(c, choose_search(c), false))) return rc;
+    if ((rc = launch_filters(c, OA_METRIC_POINT, false))) return rc;
+    if ((rc = launch_accumulate(c, true, nullptr, nullptr))) return rc;
+    return launch_reduce(c, c->d_sums, oa::RowSel{ c->acc_blocks, 0, 0 }, false);
+}
+}  // namespace
+
 OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A, double *B, int64_t cap, int64_t *K,
                             double dstats[2])
 {
-    if (c && !c->subs.empty() && c->recip_on) return fail(OA_E_STATE, "oa_make_pairs on a multi-device context%s", RECIP_ONE_DEVICE);
-    if (c && !c->subs.empty() && trim_on(c)) return fail(OA_E_STATE, "oa_make_pairs on a multi-device context%s", TRIM_ONE_DEVICE);
-    if (c && !c->subs.empty() && c->bnd_on) return fail(OA_E_STATE, "oa_make_pairs on a multi-device context%s", BND_ONE_DEVICE);
     if (c && !c->subs.empty()) {
+        if (const int rcf = refuse_filters_multi(c, "oa_make_pairs on a multi-device context")) return rcf;
         // multi-device: every child pairs its shard (its pairs come out in ascending selection position, with that
         // position); the shards are merged back into vlist order on the host.  Statistics: the children's two-pass
         // means and population deviations combine exactly (K-weighted mean; variance = within + between).
@@ -4520,14 +4481,10 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
     if (rc) return rc;
     if (!K || cap < 0 || (cap > 0 && (!A || !B))) return fail(OA_E_BAD_ARG, "oa_make_pairs: bad output arguments");
     if (!(thresh > 0.0)) return fail(OA_E_BAD_THRESH, "thresh must be > 0 (the reference's make_pairs returns None)");
-    if ((rc = refuse_recip_shard(c, "oa_make_pairs"))) return rc;
-    if ((rc = refuse_trim_shard(c, "oa_make_pairs"))) return rc;
-    if ((rc = refuse_bnd_shard(c, "oa_make_pairs"))) return rc;
+    if ((rc = refuse_filters_shard(c, "oa_make_pairs"))) return rc;
     if ((rc = use_device(c))) return rc;
     if ((rc = ensure_common(c))) return rc;
-    if ((rc = ensure_recip(c))) return rc;
-    if ((rc = ensure_trim(c))) return rc;
-    if ((rc = ensure_bnd_step(c))) return rc;
+    if ((rc = ensure_filters(c))) return rc;
     *K = 0;
     if (dstats) { dstats[0] = NAN; dstats[1] = NAN; }
     if (c->src.ns == 0) return OA_OK;
@@ -4545,13 +4502,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
         c->src.emit_cap = c->src.ns;
     }
     c->d_pivot0 = 0.0;
-    if ((rc = push_state_for_oneshot(c, thresh, true))) return rc;
-    if ((rc = launch_nn(c, choose_search(c), false))) return rc;
-    if (c->recip_on && (rc = launch_recip(c, false))) return rc;
-    if (c->bnd_on && (rc = launch_boundary(c))) return rc;
-    if (trim_on(c) && (rc = launch_trim(c, OA_METRIC_POINT))) return rc;   // (the point residual: oa_make_pairs does not look at the metric)
-    if ((rc = launch_accumulate(c, true, nullptr, nullptr))) return rc;
-    if ((rc = launch_reduce(c, c->d_sums, oa::RowSel{ c->acc_blocks, 0, 0 }, false))) return rc;   // (emitting accumulation: k_pair_accumulate<true>)
+    if ((rc = make_pairs_pass(c, thresh))) return rc;
     if (calc_stats) {
         // np.std is two-pass; redo the (cheap) accumulation around the mean of the first pass so that the
         // population std is accurate even when it is tiny compared with the mean
@@ -4559,14 +4510,7 @@ OA_EXPORT int oa_make_pairs(oa_ctx *c, double thresh, int calc_stats, double *A,
         { int rcr = read_small(c, s1, c->d_sums, sizeof s1); if (rcr) return rcr; }
         if (s1[oa::S_K] > 0.0) {
             c->d_pivot0 = s1[oa::S_D] / s1[oa::S_K];
-            if ((rc = push_state_for_oneshot(c, thresh, true))) { c->d_pivot0 = 0.0; return rc; }
-            rc = launch_nn(c, choose_search(c), false);
-            if (!rc && c->recip_on) rc = launch_recip(c, false);
-            if (!rc && c->bnd_on) rc = launch_boundary(c);
-            if (!rc && trim_on(c)) rc = launch_trim(c, OA_METRIC_POINT);
-            if (!rc) rc = launch_accumulate(c, true, nullptr, nullptr);
-            if (!rc) rc = launch_reduce(c, c->d_sums, oa::RowSel{ c->acc_blocks, 0, 0 }, false);
-            if (rc) { c->d_pivot0 = 0.0; return rc; }
+            if ((rc = make_pairs_pass(c, thresh))) { c->d_pivot0 = 0.0; return rc; }
         }
     }
     hipLaunchKernelGGL(oa::k_block_counts, dim3(n_blocks), dim3(256), 0, c->stream, c->src.d_valid, c->src.ns, c->src.d_counts);
@@ -4809,21 +4753,15 @@ int run_begin(oa_ctx *c, const oa_settings *st)
     return OA_OK;
 }
 // the exchange of the sums between devices and ranks carries OA_NSUMS doubles: the plane metric's wider row does not go through it
-const char *const GICP_ONE_DEVICE = ": the GICP metric runs on a single-device context through oa_run / oa_iterate (call oa_set_metric(ctx, OA_METRIC_POINT) for this path)";
-const char *const SYMM_ONE_DEVICE = ": the symmetric metric runs on a single-device context through oa_run / oa_iterate (call oa_set_metric(ctx, OA_METRIC_POINT) for this path)";
-const char *const PLANE_ONE_DEVICE = ": the plane metric runs on a single-device context through oa_run / oa_iterate (call oa_set_metric(ctx, OA_METRIC_POINT) for this path)";
-// ... and a quantile of the world's residuals needs the world's histogram, not OA_NSUMS doubles
-const char *const AUTO_ONE_DEVICE = ": a robust scale estimated from the residuals runs on a single-device context through oa_run / oa_iterate (call oa_set_robust_auto(ctx, 0, 0) for this path)";
+// ... and a quantile of the world's residuals needs the world's histogram, not OA_NSUMS doubles.
 // `who` (the split-phase loop, or a loop on a multi-device context) cannot carry these rows: the error that says so, or OA_OK
 int refuse_wide_row(const oa_ctx *c, const char *who, bool estimated_scale_too = true)
 {
-    if (c->recip_on) return fail(OA_E_STATE, "%s%s", who, RECIP_ONE_DEVICE);
-    if (trim_on(c)) return fail(OA_E_STATE, "%s%s", who, TRIM_ONE_DEVICE);
-    if (c->bnd_on) return fail(OA_E_STATE, "%s%s", who, BND_ONE_DEVICE);
-    if (c->metric == OA_METRIC_PLANE) return fail(OA_E_STATE, "%s%s", who, PLANE_ONE_DEVICE);
-    if (c->metric == OA_METRIC_GICP) return fail(OA_E_STATE, "%s%s", who, GICP_ONE_DEVICE);
-    if (c->metric == OA_METRIC_SYMMETRIC) return fail(OA_E_STATE, "%s%s", who, SYMM_ONE_DEVICE);
-    if (estimated_scale_too && auto_scale(c)) return fail(OA_E_STATE, "%s%s", who, AUTO_ONE_DEVICE);
+    if (const int rc = refuse_filters_multi(c, who)) return rc;
+    if (const char *noun = normal_metric_noun(c->metric))
+        return fail(OA_E_STATE, "%s: the %s metric runs on a single-device context through oa_run / oa_iterate (call oa_set_metric(ctx, OA_METRIC_POINT) for this path)", who, noun);
+    if (estimated_scale_too && auto_scale(c))
+        return fail(OA_E_STATE, "%s: a robust scale estimated from the residuals runs on a single-device context through oa_run / oa_iterate (call oa_set_robust_auto(ctx, 0, 0) for this path)", who);
     return OA_OK;
 }
 }  // namespace

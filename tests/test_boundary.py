@@ -673,32 +673,33 @@ def test_gpu_step_parity(orc, case, tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("with_", ["reciprocal", "trim"])
+@pytest.mark.parametrize("with_", ["reciprocal", "trim", "reciprocal+trim"])
 def test_gpu_composition(orc, with_, tmp_path):
     """With the reciprocal check on the rejected count is over the mutual pairs; with trim = 0.5 the candidates exclude the boundary
-    pairs.  Three steps against the reference."""
+    pairs.  Three steps against the reference.  reciprocal+trim: all three filters in one step -- the one combination in which
+    every stage finds the verdict bytes written by the stage before it."""
     from object_alignment_amd.engine import IcpEngine
     d = step_case("point")
     vmask, emask = masks_of(d)
     piv = d["src"][0].astype(np.float64)
+    recip, trim = "reciprocal" in with_, "trim" in with_
     with IcpEngine(0) as e:
         e.set_reject_boundary(True)
-        if with_ == "reciprocal":
+        if recip:
             e.set_reciprocal(True)
-        else:
+        if trim:
             e.set_trim(0.5)
         open_step_case(e, d)
         s_world = world_scale(e.matrix_world())
         for it in range(3):
-            ref = ref_step_of(orc, d, e.matrix_world(), vmask, emask, tmp_path, piv, s_world, recip=with_ == "reciprocal",
-                              trim=0.5 if with_ == "trim" else 0.0)
+            ref = ref_step_of(orc, d, e.matrix_world(), vmask, emask, tmp_path, piv, s_world, recip=recip, trim=0.5 if trim else 0.0)
             M, st = e.iterate(thresh=THRESH, target_d=1e-4)
             dM = float(np.max(np.abs(M - ref["M"])))
             print("step %d: K %d / %d, rejected %d / %d, |dM| %.3g" % (it, st["K"], ref["K"], int(e.stat("boundary_rejected")), ref["rejected"], dM))
             assert st["K"] == ref["K"] and e.stat("boundary_rejected") == float(ref["rejected"]) and ref["rejected"] > 0
-            if with_ == "trim":
+            if trim:
                 assert e.stat("trim_candidates") == float(ref["candidates"]) and e.stat("trim_kept") == float(ref["K"])
-            else:
+            if recip:
                 assert e.stat("recip_rejected") > 0.0
             assert ref["spread"] < TOL and dM <= TOL
 
