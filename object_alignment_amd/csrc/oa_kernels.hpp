@@ -1401,6 +1401,13 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_filt
 //                       vertex pass); thr1 = +inf (unseeded) passes every chunk.  (A NaN v sorts to a block's ends; such a
 //                       vertex never wins, and max() of a NaN and a number is the number, which bounds the rest alone.)
 //   levels 1, 2, 3      as k_nn_search_filtered (2-D score, 3-D score, exact metric), reached by ~6 % of the blocks at 1M <-> 1M.
+//                       Round 17 (VCHUNK = true): level 1 per CHUNK of level 0v, not per group -- the chunk's 12 tile reads issued
+//                       together, its 16 scores and four group minima in one straight line, one test of their minimum and one
+//                       branch per chunk; a chunk some lane still wants is then walked group by group in the order of before, a
+//                       lane entering level 2 where the group's stored minimum is not above its thr2 as it stands then
+//                       (sorted_level1_min / sorted_finish_level2; the same groups reach level 2 as before, so the thresholds
+//                       fall as before).  Per-workgroup stamps: 14.8 % of all wave time was this path, 16 700 cycles per hit block;
+//                       15 000 since, and the seeded launch 16.19 -> 15.64 ms (profiles/r17a_hit_path.txt).
 // Indices: position j of the sorted images holds original vertex tidx[j]; the exact path compares and reports ORIGINAL indices
 // (lowest index on ties, as everywhere).  A split owns a seed when seed index mod splits = split (no position lookup).
 // Tiles are visited middle-out from the slab nearest to the workgroup's first point: an unseeded search (the first iteration of a
@@ -1483,19 +1490,24 @@ __device__ __forceinline__ void sorted_thresholds(float best, float hu, float hv
     thr2 = round_up_to_float(base - P2);
 }
 
-// Levels 1 .. 3 of the sorted kernels for ONE point and ONE group of 4 sorted positions (AU / AV / W2: the group's -2qu, -2qv,
-// qu^2+qv^2).  Returns true when the point's best improved (its thresholds are then already renewed).
-__device__ __forceinline__ bool sorted_finish_group(const float4 AU, const float4 AV, const float4 W2, long long group,
-                                                    const float4 *__restrict__ tf3s, const float4 *__restrict__ tgs,
-                                                    const int4 *__restrict__ tidx, const float4 *__restrict__ pco, float hu, float hv,
-                                                    float hd, double qmax, float &best, uint32_t &bidx, float &thr1, float &thr2)
+// Level 1 of the sorted kernels for ONE point and ONE group of 4 sorted positions (AU / AV / W2: the group's -2qu, -2qv,
+// qu^2+qv^2): the smallest of the four 2-D scores.  The group is ruled out when it is > thr2 (a NaN is not: it goes on).
+__device__ __forceinline__ float sorted_level1_min(const float4 AU, const float4 AV, const float4 W2, float hu, float hv)
 {
-    // level 1: the 2-D score
     const float c0 = __builtin_fmaf(hu, AU.x, __builtin_fmaf(hv, AV.x, W2.x));
     const float c1 = __builtin_fmaf(hu, AU.y, __builtin_fmaf(hv, AV.y, W2.y));
     const float c2 = __builtin_fmaf(hu, AU.z, __builtin_fmaf(hv, AV.z, W2.z));
     const float c3 = __builtin_fmaf(hu, AU.w, __builtin_fmaf(hv, AV.w, W2.w));
-    if (__builtin_fminf(__builtin_fminf(c0, c1), __builtin_fminf(c2, c3)) > thr2) return false;
+    return __builtin_fminf(__builtin_fminf(c0, c1), __builtin_fminf(c2, c3));
+}
+
+// Levels 2 and 3 for a group level 1 could not rule out.  Returns true when the point's best improved (its thresholds are then
+// already renewed).
+__device__ __forceinline__ bool sorted_finish_level2(const float4 AU, const float4 AV, long long group,
+                                                     const float4 *__restrict__ tf3s, const float4 *__restrict__ tgs,
+                                                     const int4 *__restrict__ tidx, const float4 *__restrict__ pco, float hu, float hv,
+                                                     float hd, double qmax, float &best, uint32_t &bidx, float &thr1, float &thr2)
+{
     // level 2: the 3-D score
     const float4 AD = tf3s[2ll * group], W3 = tf3s[2ll * group + 1];
     const float e0s = __builtin_fmaf(hu, AU.x, __builtin_fmaf(hv, AV.x, __builtin_fmaf(hd, AD.x, W3.x)));
@@ -1527,6 +1539,16 @@ __device__ __forceinline__ bool sorted_finish_group(const float4 AU, const float
     best = b;
     bidx = (b < INFINITY) ? bi : IDX_NONE;                        // overflowed distances (+inf) never win
     return improved;
+}
+
+// Levels 1 .. 3 for ONE point and ONE group, one after the other.
+__device__ __forceinline__ bool sorted_finish_group(const float4 AU, const float4 AV, const float4 W2, long long group,
+                                                    const float4 *__restrict__ tf3s, const float4 *__restrict__ tgs,
+                                                    const int4 *__restrict__ tidx, const float4 *__restrict__ pco, float hu, float hv,
+                                                    float hd, double qmax, float &best, uint32_t &bidx, float &thr1, float &thr2)
+{
+    if (sorted_level1_min(AU, AV, W2, hu, hv) > thr2) return false;
+    return sorted_finish_level2(AU, AV, group, tf3s, tgs, tidx, pco, hu, hv, hd, qmax, best, bidx, thr1, thr2);
 }
 
 // Everything k_nn_search_sorted needs to know about a point that does not depend on the split, once per search instead of once
@@ -2083,22 +2105,69 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                             todo |= (cmask_t)1 << c;
                         }
                     }
+                    // round 17: level 1 for a passing chunk's 4 CG vertices in one pass -- its 3 CG tile reads issued together and
+                    // consumed in their order (the compiler counts the waits down, lgkmcnt(9) .. (0), but opens with a full one: a
+                    // scalar load of level 2 may be pending on the back edge), the CG group minima kept, ONE test of their minimum per lane and one
+                    // branch per chunk; only a chunk some lane still wants is walked group by group, in the order of before, a lane
+                    // entering level 2 for a group whose stored minimum is not above its thr2 AS IT STANDS THEN (thr2 only falls, at
+                    // level 3): the same groups reach level 2 as when each was scored on its own trip.  (One difference, which no
+                    // answer can see: a group whose four scores are all NaN -- four non-finite vertices -- no longer carries its
+                    // chunk past the test when the other groups' scores are numbers; such vertices never win.  A non-finite POINT
+                    // makes every score NaN and passes everything, as before.)  The serial form spent three dependent LDS round
+                    // trips and a branch per group: 4 of each per 32 FMA.
+                    constexpr bool CHUNK_L1 = !OA_SORTED_VREFINE && CG >= 2 && CG <= 4;
                     for (; todo; todo &= todo - 1) {
-                        const int c = (NC > 32) ? __builtin_ctzll((unsigned long long)todo) : __builtin_ctz((uint32_t)todo);
+                        // (todo is the wave's: made of ballots.  Said so, the chunk's tile addresses are scalar arithmetic)
+                        const int c = __builtin_amdgcn_readfirstlane((NC > 32) ? __builtin_ctzll((unsigned long long)todo) : __builtin_ctz((uint32_t)todo));
                         const bool mine = (cm >> c) & 1;
+                        if constexpr (CHUNK_L1) {
+                            const float4 *cg = &tile[cur][3 * (g + CG * c)];
+                            float4 Q[CG], AV[CG], W2[CG];
+#pragma unroll
+                            for (int k = 0; k < CG; ++k) { Q[k] = cg[3 * k]; AV[k] = cg[3 * k + 1]; W2[k] = cg[3 * k + 2]; }
+                            float gmin[CG];
+#pragma unroll
+                            for (int k = 0; k < CG; ++k)
+                                gmin[k] = sorted_level1_min(make_float4(-2.0f * Q[k].x, -2.0f * Q[k].y, -2.0f * Q[k].z, -2.0f * Q[k].w), AV[k], W2[k],
+                                                            hu[r], hv[r]);
+                            float cmin = gmin[0];
+#pragma unroll
+                            for (int k = 1; k < CG; ++k) cmin = __builtin_fminf(cmin, gmin[k]);   // v_min3_f32 (+ v_min_f32)
+                            const bool want = mine & !(cmin > thr2[r]);
+                            if (!__ballot(want)) continue;
+                            // (the minima rotate through gmin[0] and the group's images come from the tile again: a loop of one
+                            //  copy of levels 2-3 per point, as before, and no register held for them through level 1)
 #pragma unroll 1
-                        for (int k = CG * c; k < CG * c + CG; ++k) {  // one group of 4 targets at a time
-                            const float4 Q = tile[cur][3 * (g + k)], AV = tile[cur][3 * (g + k) + 1], W2 = tile[cur][3 * (g + k) + 2];
-                            bool want = mine;
-                            if (OA_SORTED_VREFINE && n_in >= 4 * GW && (4 * k) % SORTED_VBLOCK != 0) {   // the same test, per group
-                                const float F = __builtin_fmaf(0.5f, AV.x, hv[r]), L = __builtin_fmaf(0.5f, AV.w, hv[r]);
-                                want = want && !(__builtin_fmaxf(L, -F) > thr1[r]);
-                                if (!__ballot(want)) continue;
+                            for (int k = 0; k < CG; ++k) {
+                                if (want && !(gmin[0] > thr2[r])) {
+                                    // (the point through laundered copies: what levels 2-3 derive from it alone -- the double
+                                    //  precision terms of the thresholds, a square root among them -- is then computed where a
+                                    //  lane needs it, not ahead of this loop for every block and point, and held in registers)
+                                    float lu = hu[r], lv = hv[r], ld = hd[r];
+                                    asm volatile("" : "+v"(lu), "+v"(lv), "+v"(ld));
+                                    const float4 Qk = cg[3 * k], AVk = cg[3 * k + 1];
+                                    sorted_finish_level2(make_float4(-2.0f * Qk.x, -2.0f * Qk.y, -2.0f * Qk.z, -2.0f * Qk.w), AVk, gbase + g + CG * c + k,
+                                                         tf3s, tgs, tidx, rec + 2 * ns_pad + rec0 + 64 * r, lu, lv, ld, qmax, best[r], bidx[r],
+                                                         thr1[r], thr2[r]);
+                                }
+#pragma unroll
+                                for (int j = 0; j + 1 < CG; ++j) gmin[j] = gmin[j + 1];
                             }
-                            const float4 AU = make_float4(-2.0f * Q.x, -2.0f * Q.y, -2.0f * Q.z, -2.0f * Q.w);   // exact
-                            if (want)
-                                sorted_finish_group(AU, AV, W2, gbase + g + k, tf3s, tgs, tidx, rec + 2 * ns_pad + rec0 + 64 * r, hu[r], hv[r], hd[r],
-                                                    qmax, best[r], bidx[r], thr1[r], thr2[r]);
+                        } else {                                   // (OA_SORTED_VREFINE, other chunk sizes) the serial form of rounds 7-13
+#pragma unroll 1
+                            for (int k = CG * c; k < CG * c + CG; ++k) {  // one group of 4 targets at a time
+                                const float4 Q = tile[cur][3 * (g + k)], AV = tile[cur][3 * (g + k) + 1], W2 = tile[cur][3 * (g + k) + 2];
+                                bool want = mine;
+                                if (OA_SORTED_VREFINE && n_in >= 4 * GW && (4 * k) % SORTED_VBLOCK != 0) {   // the same test, per group
+                                    const float F = __builtin_fmaf(0.5f, AV.x, hv[r]), L = __builtin_fmaf(0.5f, AV.w, hv[r]);
+                                    want = want && !(__builtin_fmaxf(L, -F) > thr1[r]);
+                                    if (!__ballot(want)) continue;
+                                }
+                                const float4 AU = make_float4(-2.0f * Q.x, -2.0f * Q.y, -2.0f * Q.z, -2.0f * Q.w);   // exact
+                                if (want)
+                                    sorted_finish_group(AU, AV, W2, gbase + g + k, tf3s, tgs, tidx, rec + 2 * ns_pad + rec0 + 64 * r, hu[r], hv[r],
+                                                        hd[r], qmax, best[r], bidx[r], thr1[r], thr2[r]);
+                            }
                         }
                     }
                 }
