@@ -302,6 +302,47 @@ int oa_target_knn(oa_ctx *ctx, int k, int32_t *out_idx, float *out_d2);
  * (the target is replicated: the same bits everywhere); the host outputs are the first child's. */
 int oa_estimate_target_normals(oa_ctx *ctx, int k, int orient, const float orient_point[3], int install,
                                float *out_normals, float *out_curvature);
+/* EXTENSION: one consistent sign for the normals of a point-cloud target -- Hoppe, DeRose, Duchamp, McDonald &
+ * Stuetzle 1992: signs handed along the minimum spanning forest of the neighbour graph.  The orient rules above point every normal
+ * at or away from ONE point, which is right only for a star-shaped object seen from there; this call needs no such point.
+ * Vertex-mode targets, single-device contexts.
+ * Normals: `normals` (nt x 3, host), or with NULL the context's own (OA_E_STATE when it has none).  A vertex is ELIGIBLE when its
+ * normal is finite and not (0, 0, 0) and its coordinates are finite; every other vertex is left out: its normal comes back as it
+ * was, flipped 0, component -1, counted in n_left_out.
+ * Graph: with the rows of oa_target_knn(k), an undirected edge {i, j}, i != j, when j is in row(i) or i is in row(j), both ends
+ * are eligible and, with max_dist > 0, the row's d2 <= (float)max_dist * (float)max_dist (float32; max_dist = 0: no cap).
+ * Weight and flip, float32 with one rounding per operation: d = (nx_i nx_j + ny_i ny_j) + nz_i nz_j; t = 1 - |d|;
+ * w = t > 0 ? t : 0; the edge flips iff d < 0.
+ * Tree: the minimum spanning forest under the strict total order (w, min(i, j), max(i, j)), indices in the caller's order: it is
+ * unique.  Within a component the sign of v relative to u is the product of the flips on the tree path between them.
+ * Seed: per component one vertex decides the overall sign --
+ *   OA_SEED_KEEP    the lowest index; it keeps the sign it came with
+ *   OA_SEED_TOWARD  the vertex nearest to point:    n . (point - v) >= 0
+ *   OA_SEED_AWAY    the vertex farthest from point: n . (v - point) >= 0; a NULL point is the target's fp64 centroid
+ * nearest / farthest by the fp64 squared distance (dx dx + dy dy) + dz dz, d = (double)v - (double)point, the lowest index on
+ * ties; the sign test is the fp64 dot product (x x + y y) + z z, and a dot of exactly 0 keeps the sign.
+ * Outputs (host, each may be NULL): out_normals = the normals with the sign bit of all three components toggled or not -- no
+ * renormalisation, so given the rows the result is exact; out_flipped 0 / 1; out_component = the lowest index of the vertex's
+ * component.  rep: the number of components, of vertices left out and of vertices flipped, and the merging rounds that ran.
+ * install != 0: the result becomes the context's target normals on the device, as after oa_estimate_target_normals with install
+ * (in place, without a host round trip, when they were the input).  Integer atomics and comparisons only: two calls give the
+ * same bits.  The call ends a running oa_iterate sequence, as oa_estimate_target_normals does.
+ * OA_E_BAD_ARG: k outside 2 .. min(64, nt); seed outside 0 .. 2; OA_SEED_TOWARD with a NULL point; a non-finite point; max_dist
+ * negative or not finite.  OA_E_STATE: no target, a surface target, a multi-device context, NULL normals and none installed.
+ * OA_E_CAPACITY: nt k > 2^31 - 2^20.  OA_E_HIP should a round's bound be exceeded (never seen).  Each refusal leaves the context usable. */
+typedef struct oa_orient_report {
+    int64_t n_components;           /* components of the graph over the eligible vertices */
+    int64_t n_left_out;             /* vertices that are not eligible */
+    int64_t n_flipped;              /* vertices whose normal changed sign */
+    int32_t rounds, reserved;       /* Boruvka rounds in which components merged */
+} oa_orient_report;
+#define OA_SEED_KEEP   0   /* each component's lowest-index vertex keeps the sign it came with */
+#define OA_SEED_TOWARD 1   /* each component's vertex NEAREST to point: n . (point - v) >= 0   (a scanner position) */
+#define OA_SEED_AWAY   2   /* each component's vertex FARTHEST from point: n . (v - point) >= 0; NULL point = the target's fp64 centroid */
+int oa_orient_target_normals(oa_ctx *ctx, int k, double max_dist, int seed, const float point[3],
+                             const float *normals /* nt x 3 host, or NULL: the context's target normals */, int install,
+                             float *out_normals /* nt x 3 */, uint8_t *out_flipped /* nt */, int32_t *out_component /* nt */,
+                             oa_orient_report *rep);
 /* EXTENSION (no counterpart in the reference, whose only protection against bad correspondences is the hard cut thresh): pair
  * weights.  Every pair of a loop step (oa_run, oa_iterate, the split-phase calls) carries the weight
  *   w = w_vertex * psi(r),   c = scale (world units, like thresh):

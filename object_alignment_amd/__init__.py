@@ -11,6 +11,24 @@ def estimate_normals(xyz, k=16, orient="none", orient_point=None, device=0):
         return eng.estimate_target_normals(k=k, orient=orient, orient_point=orient_point, install=False)
 
 
+def orient_normals(xyz, normals, k=8, max_dist=0.0, seed="away", point=None, device=0):
+    """One consistent sign for the normals of ANY point cloud, on the GPU: signs handed along the minimum spanning forest of the
+    k-nearest graph (Hoppe et al. 1992) -- (normals float32 (n, 3), flipped uint8 (n,), component int32 (n,), report dict;
+    IcpEngine.orient_target_normals says how to read them).  Opens a context of its own on `device`, uploads xyz as its target
+    and closes."""
+    import numpy as np
+    from .engine import IcpEngine, _orient_args
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or len(xyz) < 2:
+        raise ValueError("orient_normals: xyz must be (n >= 2, 3), got shape %s" % (xyz.shape,))
+    if normals is None:
+        raise ValueError("orient_normals: normals must be (n, 3) numbers, got None")
+    k, max_dist, seed, point, normals = _orient_args(k, max_dist, seed, point, normals, n=len(xyz), name="orient_normals")
+    with IcpEngine(int(device)) as eng:
+        eng.set_target(xyz)
+        return eng.orient_target_normals(k=k, max_dist=max_dist, seed=seed, point=point, normals=normals, install=False)
+
+
 def fpfh(xyz, normals=None, k=16, normal_k=16, device=0):
     """Fast Point Feature Histograms of ANY point cloud (the source's included), computed on the GPU: (n, 33) float32, an
     all-zero row meaning "no descriptor".  Opens a context of its own on `device` and uploads xyz as its target; without

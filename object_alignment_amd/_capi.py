@@ -39,6 +39,9 @@ OA_POSE_NSCORE = 4
 OA_ORIENT_NONE = 0
 OA_ORIENT_TOWARD = 1
 OA_ORIENT_AWAY = 2
+OA_SEED_KEEP = 0
+OA_SEED_TOWARD = 1
+OA_SEED_AWAY = 2
 OA_FPFH_DIM = 33
 OA_FEAT_TOO_FEW_PAIRS = 1
 OA_FEAT_NO_POSE = 2
@@ -83,6 +86,7 @@ SYMBOLS = [
     "oa_set_reciprocal", "oa_set_trim",
     "oa_target_boundary", "oa_set_reject_boundary",
     "oa_normal_space_sample", "oa_stability",
+    "oa_orient_target_normals",
 ]
 
 
@@ -146,6 +150,11 @@ class StabilityReport(C.Structure):
     _fields_ = [("n_used", C.c_int64), ("centroid", C.c_double * 3), ("scale", C.c_double), ("C", C.c_double * 36),
                 ("eigenvalues", C.c_double * 6), ("eigenvectors", C.c_double * 36), ("rank", C.c_int32), ("reserved", C.c_int32),
                 ("cond", C.c_double), ("total_ms", C.c_double)]
+
+
+class OrientReport(C.Structure):
+    _fields_ = [("n_components", C.c_int64), ("n_left_out", C.c_int64), ("n_flipped", C.c_int64), ("rounds", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class OaError(RuntimeError):
@@ -257,6 +266,8 @@ def load(experiments: bool = False):
     L.oa_normal_space_sample.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_uint32, C.c_int64, ip, i32p, ip,
                                          C.POINTER(SampleReport)]
     L.oa_stability.argtypes = [vp, vp, vp, C.c_int64, C.c_int, ip, C.c_int64, C.POINTER(StabilityReport)]
+    L.oa_orient_target_normals.argtypes = [vp, C.c_int, C.c_double, C.c_int, fp, fp, C.c_int, fp, C.POINTER(C.c_uint8), i32p,
+                                           C.POINTER(OrientReport)]
     _libs[experiments] = L
     return L
 

@@ -20,6 +20,7 @@ typedef enum { ncclSum = 0 } ncclRedOp_t;
 #include "oa_sort.hpp"
 #include "oa_voxel.hpp"
 #include "oa_sample.hpp"
+#include "oa_orient.hpp"
 #include "oa_deviation.hpp"
 #include "oa_boundary.hpp"
 #include "oa_tunables.hpp"            // every OA_* knob: read once, oa_ctx::tune (plain C++)
@@ -5389,6 +5390,154 @@ OA_EXPORT int oa_estimate_target_normals(oa_ctx *c, int k, int orient, const flo
     if (out_normals) HIPCHK(hipMemcpyAsync(out_normals, d_n, sizeof(float) * 3 * nt, hipMemcpyDeviceToHost, c->stream));
     if (out_curvature) HIPCHK(hipMemcpyAsync(out_curvature, d_curv.p, sizeof(float) * nt, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
+// ================================================================================================
+// one consistent sign for a cloud's normals: a minimum spanning forest of the neighbour graph (EXTENSION; oa_orient.hpp)
+// ================================================================================================
+OA_EXPORT int oa_orient_target_normals(oa_ctx *c, int k, double max_dist, int seed, const float point[3], const float *normals, int install,
+                                       float *out_normals, uint8_t *out_flipped, int32_t *out_component, oa_orient_report *rep)
+{
+    static const char who[] = "oa_orient_target_normals";
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    OA_NOT_MULTI(c, "oa_orient_target_normals");
+    if (rep) memset(rep, 0, sizeof *rep);
+    if (seed != OA_SEED_KEEP && seed != OA_SEED_TOWARD && seed != OA_SEED_AWAY)
+        return fail(OA_E_BAD_ARG, "%s: seed %d (use OA_SEED_KEEP / OA_SEED_TOWARD / OA_SEED_AWAY)", who, seed);
+    if (seed == OA_SEED_TOWARD && !point) return fail(OA_E_BAD_ARG, "%s: OA_SEED_TOWARD needs a point", who);
+    if (point)
+        for (int a = 0; a < 3; ++a)
+            if (!(fabsf(point[a]) < INFINITY)) return fail(OA_E_BAD_ARG, "%s: point[%d] = %g is not finite", who, a, (double)point[a]);
+    if (!(max_dist >= 0.0) || !(max_dist < (double)INFINITY)) return fail(OA_E_BAD_ARG, "%s: max_dist = %g (finite and >= 0; 0: no cap)", who, max_dist);
+    int rc = knn_call_begin(c, who, k, 2);
+    if (rc) return rc;
+    if (!normals && !c->tgt.d_tgt_n)
+        return fail(OA_E_STATE, "%s: no normals given and the target has none (oa_set_target_normals, oa_set_normals or oa_estimate_target_normals with install)", who);
+    const int nt = c->tgt.nt;
+    const long long n_ent = (long long)nt * k;
+    if (n_ent > 2147483648ll - (1 << 20)) return fail(OA_E_CAPACITY, "%s: %d vertices x k = %d is %lld entries (at most 2^31 - 2^20)", who, nt, k, n_ent);
+    oa::OrientSeed sd{};
+    sd.mode = seed;
+    if (seed != OA_SEED_KEEP) {
+        if (point) { for (int a = 0; a < 3; ++a) sd.p[a] = (double)point[a]; }
+        else {
+            static const float eye16[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
+            if ((rc = centroid_of<3>(c, c->tgt.d_tgt_xyz, nt, eye16, sd.p, "oa_orient_target_normals: the target"))) return rc;
+        }
+    }
+    const size_t snt = (size_t)nt, sne = (size_t)n_ent;
+    const float *d_xyz = c->tgt.d_tgt_xyz;
+    DevTmp<float> tmp_in;
+    const float *d_nrm = c->tgt.d_tgt_n;
+    if (normals && (rc = stage_floats(c, normals, 3 * snt, 0, tmp_in, d_nrm))) return rc;
+    // 1. the rows of oa_target_knn(k)
+    KnnTree tree;
+    if ((rc = knn_tree(c, tree))) return rc;
+    DevTmp<int32_t> d_idx;
+    DevTmp<float> d_d2;
+    HIPCHK(d_idx.alloc(sne)); HIPCHK(d_d2.alloc(sne));
+    if ((rc = knn_launch<false>(c, tree, k, d_idx.p, d_d2.p, oa::KnnOrient{}, nullptr, nullptr))) return rc;
+    // 2. the entries that are edges, their keys, and their places in the order (w, lo, hi): three stable passes, the last key first
+    const unsigned v_blocks = (unsigned)((snt + oa::ORI_THREADS - 1) / oa::ORI_THREADS), e_blocks = (unsigned)((sne + oa::ORI_THREADS - 1) / oa::ORI_THREADS);
+    const dim3 blk(oa::ORI_THREADS);
+    DevTmp<uint8_t> d_elig, d_cflip;
+    DevTmp<uint32_t> d_P, d_Q, d_best, d_ent, d_kw, d_klo, d_khi, d_part;
+    DevTmp<int> d_ord, d_ord2, d_stage;
+    DevTmp<oa::OrientRound> d_round;
+    HIPCHK(d_elig.alloc(snt)); HIPCHK(d_cflip.alloc(snt)); HIPCHK(d_P.alloc(snt)); HIPCHK(d_Q.alloc(snt)); HIPCHK(d_best.alloc(snt));
+    HIPCHK(d_ent.alloc(sne)); HIPCHK(d_kw.alloc(sne)); HIPCHK(d_klo.alloc(sne)); HIPCHK(d_khi.alloc(sne)); HIPCHK(d_part.alloc(sne));
+    HIPCHK(d_ord.alloc(sne)); HIPCHK(d_ord2.alloc(sne)); HIPCHK(d_stage.alloc(sne)); HIPCHK(d_round.alloc(1));
+    const float md = (float)max_dist, cap2 = md * md;
+    hipLaunchKernelGGL(oa::k_orient_init, dim3(v_blocks), blk, 0, c->stream, d_xyz, d_nrm, nt, d_elig.p, d_P.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(oa::k_orient_entries, dim3(e_blocks), blk, 0, c->stream, (const int32_t *)d_idx.p, (const float *)d_d2.p, d_nrm, (const uint8_t *)d_elig.p, nt, k,
+                       n_ent, max_dist > 0.0 ? 1 : 0, cap2, d_ent.p, d_kw.p, d_klo.p, d_khi.p);
+    HIPCHK(hipGetLastError());
+    const unsigned g_blocks = (unsigned)((sne + 255) / 256);
+    const int idx_bits = bits_for((long long)nt);
+    if ((rc = sort_order_bits(c, d_khi.p, d_ord.p, sne, idx_bits))) return rc;
+    hipLaunchKernelGGL(oa::k_gather_int, dim3(g_blocks), dim3(256), 0, c->stream, (const int *)d_klo.p, (const int *)d_ord.p, (int)n_ent, (int *)d_part.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = sort_order_bits(c, d_part.p, d_stage.p, sne, idx_bits))) return rc;
+    hipLaunchKernelGGL(oa::k_gather_int, dim3(g_blocks), dim3(256), 0, c->stream, (const int *)d_ord.p, (const int *)d_stage.p, (int)n_ent, d_ord2.p);
+    hipLaunchKernelGGL(oa::k_gather_int, dim3(g_blocks), dim3(256), 0, c->stream, (const int *)d_kw.p, (const int *)d_ord2.p, (int)n_ent, (int *)d_part.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = sort_order_bits(c, d_part.p, d_stage.p, sne, oa::ORI_W_BITS))) return rc;
+    hipLaunchKernelGGL(oa::k_gather_int, dim3(g_blocks), dim3(256), 0, c->stream, (const int *)d_ord2.p, (const int *)d_stage.p, (int)n_ent, d_ord.p);
+    uint32_t *const d_rank = d_khi.p;                               // (the keys have been read)
+    hipLaunchKernelGGL(oa::k_orient_rank, dim3(e_blocks), blk, 0, c->stream, (const int *)d_ord.p, n_ent, d_rank);
+    HIPCHK(hipGetLastError());
+    // 3. Boruvka rounds.  Every round with a hook at least halves the components that still have an edge out, and one round more
+    //    finds none: at most ceil(log2 nt) + 1.  After the hooks nobody stands deeper than `roots` below a root, a jump halves
+    //    the depth and one jump more changes nothing: at most ceil(log2 roots) + 1 jumps.  One read per round.
+    const int max_rounds = bits_for((long long)nt) + 1;
+    long long roots = nt;
+    int rounds = 0;
+    bool done = false;
+    for (int r = 0; r < max_rounds && !done; ++r) {
+        HIPCHK(hipMemsetAsync(d_best.p, 0xff, sizeof(uint32_t) * snt, c->stream));
+        HIPCHK(hipMemsetAsync(d_round.p, 0, sizeof(oa::OrientRound), c->stream));
+        hipLaunchKernelGGL(oa::k_orient_min, dim3(e_blocks), blk, 0, c->stream, (const uint32_t *)d_ent.p, (const uint32_t *)d_rank, (const uint32_t *)d_P.p, k, n_ent,
+                           d_best.p);
+        hipLaunchKernelGGL(oa::k_orient_hook, dim3(v_blocks), blk, 0, c->stream, (const uint32_t *)d_P.p, (const uint32_t *)d_best.p, (const int *)d_ord.p,
+                           (const uint32_t *)d_ent.p, nt, k, n_ent, d_Q.p, d_round.p);
+        const int jumps = std::min(oa::ORI_MAX_JUMPS, bits_for(std::max(roots, 2ll)) + 1);
+        for (int j = 1; j <= jumps; ++j)
+            hipLaunchKernelGGL(oa::k_orient_jump, dim3(v_blocks), blk, 0, c->stream, (const uint32_t *)((j & 1) ? d_Q.p : d_P.p), (j & 1) ? d_P.p : d_Q.p, nt, j, d_round.p);
+        HIPCHK(hipGetLastError());
+        oa::OrientRound h;
+        if ((rc = read_small(c, &h, d_round.p, sizeof h))) return rc;
+        if (h.changed[jumps]) return fail(OA_E_HIP, "%s: round %d did not settle in %d pointer jumps (internal)", who, r + 1, jumps);
+        if (h.hooked < 0 || h.hooked >= roots) return fail(OA_E_HIP, "%s: round %d hooked %d of %lld roots (internal)", who, r + 1, h.hooked, roots);
+        if (h.hooked == 0) done = true;
+        else { ++rounds; roots -= h.hooked; }
+    }
+    if (!done) return fail(OA_E_HIP, "%s: components still merging after %d rounds (internal)", who, max_rounds);
+    // 4. labels, seeds, every component's sign, the normals
+    DevTmp<unsigned long long> d_dkey;
+    DevTmp<uint32_t> d_seed_of;
+    DevTmp<oa::OrientInfo> d_info;
+    DevTmp<float> tmp_out;
+    DevTmp<uint8_t> d_flipped;
+    DevTmp<int32_t> d_comp;
+    HIPCHK(d_info.alloc(1));
+    if (out_flipped) HIPCHK(d_flipped.alloc(snt));
+    if (out_component) HIPCHK(d_comp.alloc(snt));
+    uint32_t *const d_label = d_best.p;
+    HIPCHK(hipMemsetAsync(d_label, 0xff, sizeof(uint32_t) * snt, c->stream));
+    HIPCHK(hipMemsetAsync(d_info.p, 0, sizeof(oa::OrientInfo), c->stream));
+    if (seed != OA_SEED_KEEP) {
+        HIPCHK(d_dkey.alloc(snt)); HIPCHK(d_seed_of.alloc(snt));
+        HIPCHK(hipMemsetAsync(d_dkey.p, seed == OA_SEED_TOWARD ? 0xff : 0, sizeof(unsigned long long) * snt, c->stream));
+        HIPCHK(hipMemsetAsync(d_seed_of.p, 0xff, sizeof(uint32_t) * snt, c->stream));
+    }
+    hipLaunchKernelGGL(oa::k_orient_label, dim3(v_blocks), blk, 0, c->stream, (const uint32_t *)d_P.p, (const uint8_t *)d_elig.p, d_xyz, nt, sd, d_label, d_dkey.p);
+    if (seed != OA_SEED_KEEP)
+        hipLaunchKernelGGL(oa::k_orient_seed, dim3(v_blocks), blk, 0, c->stream, (const uint32_t *)d_P.p, (const uint8_t *)d_elig.p, d_xyz, nt, sd,
+                           (const unsigned long long *)d_dkey.p, d_seed_of.p);
+    hipLaunchKernelGGL(oa::k_orient_sign, dim3(v_blocks), blk, 0, c->stream, (const uint32_t *)d_P.p, (const uint8_t *)d_elig.p, d_xyz, d_nrm, nt, sd,
+                       (const uint32_t *)(seed != OA_SEED_KEEP ? d_seed_of.p : d_label), d_cflip.p, d_info.p);
+    HIPCHK(hipGetLastError());
+    float *d_out = nullptr;
+    if (install) {                                                   // (the stream carries this call alone: the array the loops read is replaced in place)
+        if (!c->tgt.d_tgt_n) HIPCHK(dev_malloc(&c->tgt.d_tgt_n, sizeof(float) * 3 * snt));
+        c->tgt.bnd_ok = false;                                           // (a boundary mask was built from the old normals)
+        d_out = c->tgt.d_tgt_n;
+    } else if (out_normals) { HIPCHK(tmp_out.alloc(3 * snt)); d_out = tmp_out.p; }
+    hipLaunchKernelGGL(oa::k_orient_apply, dim3(v_blocks), blk, 0, c->stream, (const uint32_t *)d_P.p, (const uint8_t *)d_elig.p, (const uint8_t *)d_cflip.p,
+                       (const uint32_t *)d_label, d_nrm, nt, d_out, d_flipped.p, d_comp.p, d_info.p);
+    HIPCHK(hipGetLastError());
+    oa::OrientInfo info;
+    if ((rc = read_small(c, &info, d_info.p, sizeof info))) return rc;
+    if (out_normals) HIPCHK(hipMemcpyAsync(out_normals, d_out, sizeof(float) * 3 * snt, hipMemcpyDeviceToHost, c->stream));
+    if (out_flipped) HIPCHK(hipMemcpyAsync(out_flipped, d_flipped.p, snt, hipMemcpyDeviceToHost, c->stream));
+    if (out_component) HIPCHK(hipMemcpyAsync(out_component, d_comp.p, sizeof(int32_t) * snt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (rep) {
+        rep->n_components = (int64_t)info.n_components; rep->n_left_out = (int64_t)info.n_left_out; rep->n_flipped = (int64_t)info.n_flipped;
+        rep->rounds = rounds; rep->reserved = 0;
+    }
     return OA_OK;
 }
 

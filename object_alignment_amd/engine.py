@@ -145,6 +145,37 @@ def _stability_args(xyz, normals, idx=None, name="stability"):
     return xyz, normals, idx
 
 
+ORIENT_SEEDS = {"keep": capi.OA_SEED_KEEP, "toward": capi.OA_SEED_TOWARD, "away": capi.OA_SEED_AWAY}
+
+
+def _orient_args(k=8, max_dist=0.0, seed="away", point=None, normals=None, n=None, name="orient_target_normals"):
+    """The arguments of a consistent orientation, checked before any call reaches the library: (k, max_dist, seed, point or None,
+    normals or None).  n: the number of vertices, when it is known."""
+    k = _whole(k, name, "k", 2, 64)
+    if n is not None and k > n:
+        raise ValueError("%s: k = %d for %d vertices (2 .. min(64, n))" % (name, k, n))
+    if isinstance(max_dist, bool) or not isinstance(max_dist, (int, float, np.integer, np.floating)) or not 0 <= max_dist < float("inf"):
+        raise ValueError("%s: max_dist = %r (finite and >= 0; 0: no cap)" % (name, max_dist))
+    if isinstance(seed, str):
+        if seed not in ORIENT_SEEDS:
+            raise ValueError("%s: seed %r (use 'keep', 'toward' or 'away')" % (name, seed))
+        seed = ORIENT_SEEDS[seed]
+    elif isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed not in (0, 1, 2):
+        raise ValueError("%s: seed %r (use 'keep', 'toward' or 'away')" % (name, seed))
+    if point is not None:
+        point = np.ascontiguousarray(point, dtype=np.float32)
+        if point.shape != (3,) or not np.isfinite(point).all():
+            raise ValueError("%s: point must be three finite numbers, got %r" % (name, point))
+    elif seed == capi.OA_SEED_TOWARD:
+        raise ValueError("%s: seed 'toward' needs a point" % name)
+    if normals is not None:
+        normals = np.asarray(normals)
+        if normals.ndim != 2 or normals.shape[1] != 3 or normals.dtype.kind not in "fiu" or (n is not None and len(normals) != n):
+            raise ValueError("%s: normals must be (%s, 3) numbers, got %s %s" % (name, "n" if n is None else n, normals.shape, normals.dtype))
+        normals = np.ascontiguousarray(normals, dtype=np.float32)
+    return k, float(max_dist), int(seed), point, normals
+
+
 DEVIATION_OUTPUTS = ("signed_d", "dist", "closest", "idx", "feature")
 DEVIATION_SIGNED = {"auto": -1, "never": 0, "required": 1, None: -1, False: 0, True: 1}
 
@@ -377,6 +408,29 @@ class IcpEngine:
         self._chk(self._L.oa_estimate_target_normals(self._h, int(k), int(orient), capi.fptr(pt) if pt is not None else None,
                                                       int(bool(install)), capi.fptr(nrm), capi.fptr(curv)))
         return nrm[: self.n_target], curv[: self.n_target]
+
+    def orient_target_normals(self, k=8, max_dist=0.0, seed="away", point=None, normals=None, install=True):
+        """Vertex-mode targets: one consistent sign for the cloud's normals, on the device (Hoppe et al. 1992): the minimum
+        spanning forest of the k-nearest graph under the weights 1 - |n_i . n_j|, signs handed along its edges -- no view point
+        needed, so a torus, an arch or a bent tube come out right where orient='away' cannot.  normals: (nt, 3), or None for
+        the target's own (an installed estimate).  max_dist > 0 drops graph edges longer than that (a speck of noise then stays
+        a component of its own).  seed: what fixes each component's overall sign -- 'keep' (its lowest vertex keeps its sign),
+        'toward' point (its vertex nearest to point faces it) or 'away' from point (its farthest vertex faces away; None = the
+        target's centroid).  Returns (normals float32 (nt, 3), flipped uint8 (nt,), component int32 (nt,) -- the lowest index of
+        the vertex's component, -1 for a vertex without a usable normal --, report dict).  install: the result becomes the
+        target's normals.  2 <= k <= min(64, nt)."""
+        k, max_dist, seed, point, normals = _orient_args(k, max_dist, seed, point, normals, n=self.n_target or None)
+        n = max(1, self.n_target)
+        out = np.empty((n, 3), np.float32)
+        flipped = np.empty(n, np.uint8)
+        comp = np.empty(n, np.int32)
+        rep = capi.OrientReport()
+        self._chk(self._L.oa_orient_target_normals(self._h, k, max_dist, seed, capi.fptr(point) if point is not None else None,
+                                                    capi.fptr(normals) if normals is not None else None, int(bool(install)),
+                                                    capi.fptr(out), flipped.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                    comp.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rep)))
+        report = {name: int(getattr(rep, name)) for name, _ in capi.OrientReport._fields_ if name != "reserved"}
+        return out[: self.n_target], flipped[: self.n_target], comp[: self.n_target], report
 
     LOSSES = {"none": capi.OA_LOSS_NONE, "huber": capi.OA_LOSS_HUBER, "tukey": capi.OA_LOSS_TUKEY, "cauchy": capi.OA_LOSS_CAUCHY}
 

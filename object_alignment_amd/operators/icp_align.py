@@ -78,6 +78,13 @@ class IcpSettings:
     boundary_angle: float = 90.0
     # neighbours per vertex when run(..., target_normals="estimate") estimates a point-cloud target's normals on the device
     normal_k: int = 16
+    # nor this: how an ESTIMATED normal field gets its signs, wherever run() estimates one (target_normals="estimate",
+    # source_normals="estimate").  "away": every normal away from the cloud's centroid -- right for a star-shaped object only.
+    # "consistent": the estimate is followed by IcpEngine.orient_target_normals (k = normal_k, seed away from the centroid, no
+    # edge cap): signs handed along the minimum spanning forest of the neighbour graph (Hoppe et al. 1992), right for a torus, an
+    # arch or a bent tube as well.  The normal-angle test, the sign of a cloud target's deviation and oriented normal-space
+    # sampling read those signs
+    normal_orient: str = "away"
     # nor this: > 0 thins the selection in SPACE before the loop -- one vertex per occupied cell of a grid of this edge (world
     # units, like min_start): the member nearest to the cell's mean (IcpEngine.voxel_downsample) -- so that a region the scanner
     # covered twice does not weigh twice; sample_fraction then applies to that list, as to any vlist.  0 = off: the selection is
@@ -289,6 +296,27 @@ def sample_normal_space_of(settings):
     return int(m), int(g)
 
 
+NORMAL_ORIENTS = ("away", "consistent")
+
+
+def normal_orient_of(settings) -> str:
+    """IcpSettings.normal_orient, checked: "away" or "consistent"."""
+    v = getattr(settings, "normal_orient", "away")
+    if not isinstance(v, str) or v not in NORMAL_ORIENTS:
+        raise ValueError("IcpSettings.normal_orient = %r (use 'away' or 'consistent')" % (v,))
+    return v
+
+
+def estimate_consistent_normals(xyz, k, device=0):
+    """PCA normals of a cloud with one consistent sign: the estimate, then IcpEngine.orient_target_normals on it (seed away from
+    the centroid), in a context of its own."""
+    from ..engine import IcpEngine
+    with IcpEngine(int(device)) as eng:
+        eng.set_target(xyz)
+        eng.estimate_target_normals(k=k, orient="none", install=True)
+        return eng.orient_target_normals(k=k, max_dist=0.0, seed="away", install=False)[0]
+
+
 def world_scale(mx) -> float:
     """cbrt(|det(mx[:3, :3])|): what carries a world-space length to the object's local space."""
     return float(np.cbrt(abs(np.linalg.det(np.asarray(mx, np.float64).reshape(4, 4)[:3, :3]))))
@@ -419,11 +447,12 @@ class IcpAlign:
         semantics); None -> nearest target vertex (point-cloud targets, BASELINE's configurations).
         target_normals: one normal per target vertex -- what settings.metric == "plane" needs of a point-cloud target -- or
         "estimate": PCA normals from every target vertex's settings.normal_k nearest neighbours, computed on the device after
-        the upload and oriented away from the target's centroid (point-cloud targets only: a mesh has its triangles').
+        the upload and oriented away from the target's centroid -- or, with settings.normal_orient == "consistent", along the
+        minimum spanning forest of the neighbour graph (point-cloud targets only: a mesh has its triangles').
         source_weights: one weight per vertex of source_xyz (finite, >= 0) -- "trust this region less"; None = all one.
         source_normals: one align-local normal per vertex of source_xyz -- what settings.metric == "gicp" / "symmetric" needs -- or "estimate":
         object_alignment_amd.estimate_normals(source_xyz, k=settings.normal_k), in a context of its own (those metrics do not
-        look at the normals' signs, so they are left unoriented).
+        look at the normals' signs, so they are left unoriented; settings.normal_orient == "consistent" gives them one sign).
         coarse: a CoarseSettings (operators/coarse_align.py) -- the coarse global stage runs on the same engine in front of the
         loop, which then starts from the pose it found (self.last_coarse holds its report); None: the loop alone.
         settings.sample_voxel > 0: the vertices vlist selects are first thinned to one representative per voxel of that edge
@@ -447,6 +476,7 @@ class IcpAlign:
             raise TypeError("deviation %r (a DeviationSettings, or None)" % (deviation,))
         sample_voxel = sample_voxel_of(s)
         sample_normals, sample_grid = sample_normal_space_of(s)
+        consistent = normal_orient_of(s) == "consistent"
         if sample_normals > 0 and source_normals is None:
             raise ValueError("IcpSettings.sample_normal_space needs source_normals (an array of normals, or 'estimate')")
         thresh = s.min_start                                   # :83
@@ -461,6 +491,8 @@ class IcpAlign:
             eng.set_target(target_xyz)
             if estimate:
                 eng.estimate_target_normals(k=int(getattr(s, "normal_k", 16)), orient="away", install=True)
+                if consistent:
+                    eng.orient_target_normals(k=int(getattr(s, "normal_k", 16)), max_dist=0.0, seed="away", install=True)
             elif target_normals is not None:
                 eng.set_target_normals(target_normals)
         apply_metric(eng, s)
@@ -473,6 +505,8 @@ class IcpAlign:
         estimate_source = isinstance(source_normals, str)
 
         def estimated_source_normals():
+            if consistent:
+                return estimate_consistent_normals(source_xyz, int(getattr(s, "normal_k", 16)))
             from .. import estimate_normals
             return estimate_normals(source_xyz, k=int(getattr(s, "normal_k", 16)))[0]
 
