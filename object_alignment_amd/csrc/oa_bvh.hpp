@@ -67,7 +67,7 @@ __device__ __forceinline__ unsigned bvh_spread10(unsigned v)
 // (the target: 3; the packed source rows of the reciprocal check's tree, oa_recip.hpp: 4)
 template <bool TRI>
 __global__ void k_bvh_keys(const float *__restrict__ xyz, int stride, const float4 *__restrict__ tri9, int n, float lx, float ly,
-                           float lz, float sx, float sy, float sz, unsigned *__restrict__ keys, int *__restrict__ ids)
+                           float lz, float sx, float sy, float sz, unsigned *__restrict__ keys)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -84,7 +84,6 @@ __global__ void k_bvh_keys(const float *__restrict__ xyz, int stride, const floa
     const float fx = fminf(fmaxf((cx - lx) * sx, 0.f), 1023.f), fy = fminf(fmaxf((cy - ly) * sy, 0.f), 1023.f),
                 fz = fminf(fmaxf((cz - lz) * sz, 0.f), 1023.f);      // NaN -> 0 through fmaxf
     keys[i] = bvh_spread10((unsigned)fx) | (bvh_spread10((unsigned)fy) << 1) | (bvh_spread10((unsigned)fz) << 2);
-    ids[i] = i;
 }
 
 // sorted primitive images.  vertex: float4 {x, y, z, bits(original index)}; triangle: the tri9 image with the original

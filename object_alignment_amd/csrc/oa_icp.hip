@@ -699,9 +699,8 @@ inline bool bvh_whole(const oa_ctx *c, bool ok, int auto_max)
 int build_grid(oa_ctx *c);
 int build_safe_radii(oa_ctx *c);
 // Stable argsort of keys of `bits` bits (30: Morton keys) on the context's stream, no wait: order = the indices in the keys' stable
-// ascending order.  The library's own sorts (oa_sort.hpp): one workgroup up to SORT_SMALL_MAX keys, the three-pass LSD argsort
-// above that; rounds 4-5 still fell back on rocprim outside 65k .. 3M keys -- 628 of the library's 749 kernels were its
-// instantiations.
+// ascending order.  The library's own sorts (oa_sort.hpp): one workgroup up to SORT_SMALL_MAX keys, the LSD argsort above that, at
+// most oa::SORT_MAX_N keys.
 int sort_order_bits(oa_ctx *c, const unsigned *keys, int *order, size_t n, int bits)
 {
     DevTmp<char> tmp;
@@ -716,6 +715,15 @@ int sort_ints(oa_ctx *c, const int *keys, int *sorted, int *order, size_t n, int
     if (rc || n == 0) return rc;
     hipLaunchKernelGGL(oa::k_gather_int, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, keys, (const int *)order, (int)n, sorted);
     HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+// one more, more significant key on top of an order (oa_sort.hpp, lex_order_next): order = by keys, equal keys as prev has them.  The
+// keys are overwritten.  On the context's stream, no wait.
+int lex_order_next(oa_ctx *c, unsigned *keys, int bits, const int *prev, int *order, size_t n)
+{
+    DevTmp<char> tmp;
+    HIPCHK(tmp.alloc(oa::lex_order_tmp_bytes(n)));
+    HIPCHK(oa::lex_order_next((void *)tmp.p, keys, bits, prev, order, n, c->stream));
     return OA_OK;
 }
 inline int bits_for(long long n_values) { int b = 1; while (b < 32 && (1ll << b) < n_values) ++b; return b; }
@@ -1410,10 +1418,23 @@ void launch_residual_keys(oa_ctx *c, int metric, uint32_t *hist)
     if (metric == OA_METRIC_SYMMETRIC) { launch(oa::k_residual_keys_symm<RECIP>, (const float *)c->src.d_src_n); return; }
     if (metric == OA_METRIC_PLANE) launch(oa::k_residual_keys<true, RECIP>); else launch(oa::k_residual_keys<false, RECIP>);
 }
+// workgroups of a select's histogram launch: k_select_hist and k_dev_select_hist stride over the keys
+inline unsigned select_hist_blocks(int ns) { return (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS)); }
+// n_sel radix selects over keys[0 .. ns), one DevSelect and one block of SEL_LEVELS x SEL_BINS zeroed counts each (oa_deviation.hpp):
+// per level the histogram, then the scan, on the context's stream.  level0_counted: the kernel that wrote the keys counted level 0
+void launch_dev_select(oa_ctx *c, oa::DevSelect *sel, int n_sel, const uint32_t *keys, uint32_t *hist, bool level0_counted)
+{
+    for (int level = 0; level < oa::SEL_LEVELS; ++level) {
+        if (level > 0 || !level0_counted)
+            hipLaunchKernelGGL(oa::k_dev_select_hist, dim3(select_hist_blocks(c->src.ns), (unsigned)n_sel), dim3(oa::SEL_THREADS), 0, c->stream,
+                               (const oa::DevSelect *)sel, keys, c->src.ns, level, hist);
+        hipLaunchKernelGGL(oa::k_dev_select_scan, dim3((unsigned)n_sel), dim3(oa::SEL_THREADS), 0, c->stream, sel, (const uint32_t *)hist, level);
+    }
+}
 int launch_robust_scale(oa_ctx *c)
 {
     if (verdict_on(c)) launch_residual_keys<true>(c, c->metric, c->d_sel_hist); else launch_residual_keys<false>(c, c->metric, c->d_sel_hist);
-    const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->src.ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
+    const unsigned hist_blocks = select_hist_blocks(c->src.ns);
     for (int level = 0; level < oa::SEL_LEVELS; ++level) {
         if (level > 0)
             hipLaunchKernelGGL(oa::k_select_hist, dim3(hist_blocks), dim3(oa::SEL_THREADS), 0, c->stream, (const oa::DevState *)c->d_state,
@@ -1432,13 +1453,7 @@ int launch_trim(oa_ctx *c, int metric)
     launch_residual_keys<true>(c, metric, c->d_trim_hist);
     const oa::DevState *st = c->d_state;
     if (!trim_auto(c)) {
-        const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->src.ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
-        for (int level = 0; level < oa::SEL_LEVELS; ++level) {
-            if (level > 0)
-                hipLaunchKernelGGL(oa::k_dev_select_hist, dim3(hist_blocks, 1), dim3(oa::SEL_THREADS), 0, c->stream, (const oa::DevSelect *)&c->d_trim->sel,
-                                   (const uint32_t *)c->src.d_rkeys, c->src.ns, level, c->d_trim_hist);
-            hipLaunchKernelGGL(oa::k_dev_select_scan, dim3(1), dim3(oa::SEL_THREADS), 0, c->stream, &c->d_trim->sel, (const uint32_t *)c->d_trim_hist, level);
-        }
+        launch_dev_select(c, &c->d_trim->sel, 1, (const uint32_t *)c->src.d_rkeys, c->d_trim_hist, true);
     } else {
         const int n_tiles = oa::trim_tiles(c->src.ns);
         // (all 32 bits: RKEY_NONE sorts last, and the one-workgroup sort and the LSD passes agree on every key)
@@ -2685,6 +2700,21 @@ int bbox_partials(oa_ctx *c, const float *d_xyz, long long n, int nb, float *out
     HIPCHK(hipGetLastError());
     return read_small(c, out, d_bb, sizeof(float) * 6 * (size_t)nb);
 }
+// nb rows of {lo[3], hi[3]} (k_bbox_partial, k_bbox_finite, k_voxel_bbox) folded in row order -> lo / hi; true if an entry is NaN.
+// No row, or none that compares: lo = +inf, hi = -inf.  What an empty box or a NaN means is the caller's to say.
+bool fold_bbox(const float *bb, int nb, float lo[3], float hi[3])
+{
+    bool any_nan = false;
+    for (int a = 0; a < 3; ++a) { lo[a] = INFINITY; hi[a] = -INFINITY; }
+    for (int b = 0; b < nb; ++b)
+        for (int a = 0; a < 3; ++a) {
+            const float l = bb[6 * (size_t)b + a], h = bb[6 * (size_t)b + 3 + a];
+            if (l != l || h != h) any_nan = true;
+            if (l < lo[a]) lo[a] = l;
+            if (h > hi[a]) hi[a] = h;
+        }
+    return any_nan;
+}
 
 // filter image for k_nn_search_filtered: bbox centre, centred -2q / |q|^2 arrays, max |q - centre|
 // k_nn_search_sorted's images: the target in the order of its coordinate along the longest axis (30-bit quantised key through
@@ -2704,10 +2734,10 @@ int build_sorted_images(oa_ctx *c)
     const double ext = hi[su] - lo[su];
     const int blocks = (c->tgt.n_groups_pad + 255) / 256;
     DevTmp<unsigned> k_in;
-    DevTmp<int> v_in, v_out;
-    HIPCHK(k_in.alloc((size_t)c->tgt.nt)); HIPCHK(v_in.alloc((size_t)c->tgt.nt)); HIPCHK(v_out.alloc((size_t)c->tgt.nt));
+    DevTmp<int> v_out;
+    HIPCHK(k_in.alloc((size_t)c->tgt.nt)); HIPCHK(v_out.alloc((size_t)c->tgt.nt));
     hipLaunchKernelGGL(oa::k_sort_keys_axis, dim3((c->tgt.nt + 255) / 256), dim3(256), 0, c->stream, (const float *)c->tgt.d_tgt_xyz, c->tgt.nt, su, lo[su],
-                       ext > 0.0 ? 1073741823.0 / ext : 0.0, k_in.p, v_in.p);
+                       ext > 0.0 ? 1073741823.0 / ext : 0.0, k_in.p);
     HIPCHK(hipGetLastError());
     { const int rcs = sort_order_bits(c, k_in.p, v_out.p, (size_t)c->tgt.nt, 30); if (rcs) return rcs; }
     if (c->tune.nn_vchunk) {                                           // every block of the u order by v, its first vertex kept (k_sort_blocks_v)
@@ -2733,15 +2763,9 @@ int build_filter(oa_ctx *c, bool vertex_target)
     const int nb = 256;
     std::vector<float> bb(6 * nb);
     { int rcb = bbox_partials(c, c->tgt.d_tgt_xyz, c->tgt.nt, nb, bb.data()); if (rcb) return rcb; }
-    double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-    bool finite = true;
-    for (int b = 0; b < nb; ++b)
-        for (int a = 0; a < 3; ++a) {
-            const float l = bb[6 * b + a], h = bb[6 * b + 3 + a];
-            if (l != l || h != h) finite = false;
-            if (l < lo[a]) lo[a] = l;
-            if (h > hi[a]) hi[a] = h;
-        }
+    float lof[3], hif[3];
+    bool finite = !fold_bbox(bb.data(), nb, lof, hif);
+    const double lo[3] = { lof[0], lof[1], lof[2] }, hi[3] = { hif[0], hif[1], hif[2] };
     for (int a = 0; a < 3; ++a) if (!(lo[a] <= hi[a]) || !(fabs(lo[a]) < 1e18) || !(fabs(hi[a]) < 1e18)) finite = false;
     if (!finite) return OA_OK;                                   // exact kernel only
     for (int a = 0; a < 3; ++a) { c->tc[a] = (float)(0.5 * (lo[a] + hi[a])); c->bb_lo[a] = lo[a]; c->bb_hi[a] = hi[a]; }
@@ -3009,13 +3033,13 @@ int build_bvh_arrays(oa_ctx *c, bool tri, const float *d_xyz, int stride, int n,
     bp.slack = 1e-10 * scale + 1e-300;
     const int n_pad = bp.cnt[1] * oa::BVH_W;
     DevTmp<unsigned> k_in;
-    DevTmp<int> v_in, v_out;
-    HIPCHK(k_in.alloc((size_t)n)); HIPCHK(v_in.alloc((size_t)n)); HIPCHK(v_out.alloc((size_t)n));
+    DevTmp<int> v_out;
+    HIPCHK(k_in.alloc((size_t)n)); HIPCHK(v_out.alloc((size_t)n));
     const dim3 blk(256), grd((unsigned)((n + 255) / 256));
     if (tri) hipLaunchKernelGGL(oa::k_bvh_keys<true>, grd, blk, 0, c->stream, d_xyz, stride, (const float4 *)c->tgt.d_tri9,
-                                n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
+                                n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p);
     else hipLaunchKernelGGL(oa::k_bvh_keys<false>, grd, blk, 0, c->stream, d_xyz, stride, (const float4 *)nullptr,
-                            n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
+                            n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p);
     HIPCHK(hipGetLastError());
     { const int rcs = sort_order_bits(c, k_in.p, v_out.p, (size_t)n, 30); if (rcs) return rcs; }
     HIPCHK(dev_malloc(&d_prims, sizeof(float4) * (tri ? 3 : 1) * (size_t)n_pad));
@@ -3050,14 +3074,8 @@ int morton_frame(oa_ctx *c, const float *d_xyz, long long n_verts, float lo[3], 
     const int nb = 256;
     std::vector<float> bb(6 * nb);
     { int rcb = bbox_partials(c, d_xyz, n_verts, nb, bb.data()); if (rcb) return rcb; }
-    float hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-    lo[0] = lo[1] = lo[2] = INFINITY;
-    for (int b = 0; b < nb; ++b)
-        for (int a = 0; a < 3; ++a) {
-            const float l = bb[6 * b + a], h = bb[6 * b + 3 + a];
-            if (l != l || h != h) return OA_OK;                     // non-finite coordinates: keep the caller's order
-            lo[a] = std::min(lo[a], l); hi[a] = std::max(hi[a], h);
-        }
+    float hi[3];
+    if (fold_bbox(bb.data(), nb, lo, hi)) return OA_OK;             // non-finite coordinates: keep the caller's order
     for (int a = 0; a < 3; ++a) {
         if (!(lo[a] <= hi[a]) || !(fabsf(lo[a]) < 1e18f) || !(fabsf(hi[a]) < 1e18f)) return OA_OK;
         sc[a] = hi[a] > lo[a] ? 1023.0f / (hi[a] - lo[a]) : 0.f;
@@ -3066,10 +3084,35 @@ int morton_frame(oa_ctx *c, const float *d_xyz, long long n_verts, float lo[3], 
     return OA_OK;
 }
 
+// order[0 .. n) = the Morton order of the packed points pts[0 .. n): stable by the 30-bit key (10 bits an axis) in morton_frame's
+// frame, equal keys in index order.  On the context's stream, no wait.
+int morton_order(oa_ctx *c, const float4 *pts, int n, const float lo[3], const float sc[3], int *order)
+{
+    DevTmp<unsigned> keys;
+    HIPCHK(keys.alloc((size_t)n));
+    hipLaunchKernelGGL(oa::k_morton_keys, dim3((n + 255) / 256), dim3(256), 0, c->stream, pts, n, lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], keys.p);
+    HIPCHK(hipGetLastError());
+    return sort_order_bits(c, keys.p, order, (size_t)n, 30);
+}
+
+// The whole selection of n points packed in selection order (pts, sel: k_pack_source's images) and its Morton order: order[j] =
+// the selection position of the j-th point.  ok = false and nothing allocated for non-finite coordinates.  No wait behind the sort.
+int selection_morton_order(oa_ctx *c, const float *d_xyz, long long n_verts, const long long *d_vlist, long long step, int n,
+                           DevTmp<float4> &pts, DevTmp<int> &sel, DevTmp<int> &order, bool &ok)
+{
+    float lo[3], sc[3];
+    const int rc = morton_frame(c, d_xyz, n_verts, lo, sc, ok);   // (synchronises the stream)
+    if (rc || !ok) return rc;
+    HIPCHK(pts.alloc((size_t)n)); HIPCHK(sel.alloc((size_t)n)); HIPCHK(order.alloc((size_t)n));
+    hipLaunchKernelGGL(oa::k_pack_source, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_xyz, d_vlist, step, 0ll, (const int *)nullptr, n, n, pts.p, sel.p);
+    HIPCHK(hipGetLastError());
+    return morton_order(c, pts.p, n, lo, sc, order.p);
+}
+
 // Are the shards of a selection ranges of its Morton order (compact regions of space), or of the caller's order?
 bool spatial_sharding(const oa_ctx *c, long long n_sel, int shards)
 {
-    return shards > 1 && n_sel < 0x7FF00000ll && c->tune.sort_source && c->tune.shard_spatial;
+    return shards > 1 && n_sel < oa::SORT_MAX_N && c->tune.sort_source && c->tune.shard_spatial;
 }
 
 // Positions (in the selection) of the points shard [begin, begin + count) of the Morton-ordered selection holds, in
@@ -3077,22 +3120,11 @@ bool spatial_sharding(const oa_ctx *c, long long n_sel, int shards)
 int spatial_shard_members(oa_ctx *c, const float *d_xyz, long long n_verts, const long long *d_vlist, long long step,
                           long long n_sel, long long begin, int count, DevTmp<int> &members)
 {
-    float lo[3], sc[3];
     bool ok = false;
-    int rc = morton_frame(c, d_xyz, n_verts, lo, sc, ok);
-    if (rc || !ok) return rc;
-    const int n = (int)n_sel;
     DevTmp<float4> all4;
-    DevTmp<int> all_sel, v_in, order, picked;
-    DevTmp<unsigned> k_in;
-    HIPCHK(all4.alloc((size_t)n)); HIPCHK(all_sel.alloc((size_t)n)); HIPCHK(v_in.alloc((size_t)n)); HIPCHK(order.alloc((size_t)n));
-    HIPCHK(k_in.alloc((size_t)n));
-    hipLaunchKernelGGL(oa::k_pack_source, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_xyz, d_vlist, step, 0ll,
-                       (const int *)nullptr, n, n, all4.p, all_sel.p);
-    hipLaunchKernelGGL(oa::k_morton_keys, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float4 *)all4.p, n,
-                       lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
-    HIPCHK(hipGetLastError());
-    { const int rcs = sort_order_bits(c, k_in.p, order.p, (size_t)n, 30); if (rcs) return rcs; }
+    DevTmp<int> all_sel, order;
+    const int rc = selection_morton_order(c, d_xyz, n_verts, d_vlist, step, (int)n_sel, all4, all_sel, order, ok);
+    if (rc || !ok) return rc;
     // this shard's range of the order, back in ascending selection position (= the caller's order inside the shard)
     HIPCHK(members.alloc((size_t)count));
     DevTmp<int> ord2;
@@ -3108,14 +3140,8 @@ int sort_source_slots(oa_ctx *c, const float *d_xyz, long long n_verts)
     bool ok = false;
     int rcf = morton_frame(c, d_xyz, n_verts, lo, sc, ok);
     if (rcf || !ok) return rcf;
-    DevTmp<unsigned> k_in;
-    DevTmp<int> v_in;
-    HIPCHK(k_in.alloc((size_t)c->src.ns)); HIPCHK(v_in.alloc((size_t)c->src.ns));
     HIPCHK(dev_malloc(&c->src.d_perm, sizeof(int) * (size_t)c->src.ns));
-    hipLaunchKernelGGL(oa::k_morton_keys, dim3((c->src.ns + 255) / 256), dim3(256), 0, c->stream, (const float4 *)c->src.d_src4, c->src.ns,
-                       lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
-    HIPCHK(hipGetLastError());
-    { const int rcs = sort_order_bits(c, k_in.p, c->src.d_perm, (size_t)c->src.ns, 30); if (rcs) return rcs; }
+    { const int rcs = morton_order(c, (const float4 *)c->src.d_src4, c->src.ns, lo, sc, c->src.d_perm); if (rcs) return rcs; }
     // d_src4 / d_sel become the sorted images: the packed buffers change names (they ARE the caller-order copy now) and
     // k_apply_perm fills new ones -- every slot up to ns_pad -- instead of two device-to-device copies in front of it
     // (both new buffers first, the context's pointers only when both exist: a failed allocation leaves the unsorted source in
@@ -3626,7 +3652,7 @@ int set_source_single(oa_ctx *c, const float *xyz, int64_t n_verts, int on_devic
     const long long per = (n_sel + shard_count - 1) / shard_count;
     const long long begin = std::min(n_sel, per * shard_index);
     const long long count = std::max(0ll, std::min(per, n_sel - begin));
-    if (count > 0x7FF00000ll) return fail(OA_E_BAD_ARG, "shard too large");
+    if (count > oa::SORT_MAX_N) return fail(OA_E_BAD_ARG, "shard too large");
     int rc = use_device(c);
     if (rc) return rc;
     if ((rc = source_reset(c, count, begin, n_verts))) return rc;
@@ -3686,8 +3712,8 @@ int set_source_single(oa_ctx *c, const float *xyz, int64_t n_verts, int on_devic
 // The whole selection packed and Morton-sorted ONCE, on one device of a multi-device context (round 2: every device
 // sorted the whole selection to find its range -- at 10M points, 8 sorts of 10M keys).  Slot j of the order holds the
 // point at selection position pos[j]; shard g of n is the range [g per, g per + count_g) of it -- exactly the slots the
-// per-context path (spatial_shard_members + sort_source_slots) ends up with, in the same order: both sort by the same
-// 30-bit key with ties in selection order.
+// per-context path (spatial_shard_members + sort_source_slots) ends up with, in the same order: both order the selection with
+// selection_morton_order, and sort_source_slots' morton_order of a shard keeps that order (same frame, same key, ties by position).
 struct SelectionOrder {
     DevTmp<float4> pts;
     DevTmp<int> sel, pos;
@@ -3712,23 +3738,13 @@ int build_selection_order(oa_ctx *c, const float *xyz, int64_t n_verts, int on_d
     const long long v0 = vlist ? vlist[0] : 0;
     if (on_device) HIPCHK(hipMemcpyAsync(o.p0, d_xyz + 3 * v0, sizeof o.p0, hipMemcpyDeviceToHost, c->stream));
     else memcpy(o.p0, xyz + 3 * v0, sizeof o.p0);
-    float lo[3], sc[3];
-    bool finite = false;
-    if ((rc = morton_frame(c, d_xyz, n_verts, lo, sc, finite))) return rc;   // synchronises the stream
-    if (!finite) return OA_OK;                                     // caller falls back to contiguous ranges
     const int n = (int)n_sel;
+    bool finite = false;
     DevTmp<float4> all4;
-    DevTmp<int> all_sel, v_in;
-    DevTmp<unsigned> k_in;
-    HIPCHK(all4.alloc((size_t)n)); HIPCHK(all_sel.alloc((size_t)n)); HIPCHK(v_in.alloc((size_t)n));
-    HIPCHK(k_in.alloc((size_t)n));
-    HIPCHK(o.pts.alloc((size_t)n)); HIPCHK(o.sel.alloc((size_t)n)); HIPCHK(o.pos.alloc((size_t)n));
-    hipLaunchKernelGGL(oa::k_pack_source, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_xyz, (const long long *)d_vlist.p, step, 0ll,
-                       (const int *)nullptr, n, n, all4.p, all_sel.p);
-    hipLaunchKernelGGL(oa::k_morton_keys, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float4 *)all4.p, n,
-                       lo[0], lo[1], lo[2], sc[0], sc[1], sc[2], k_in.p, v_in.p);
-    HIPCHK(hipGetLastError());
-    { const int rcs = sort_order_bits(c, k_in.p, o.pos.p, (size_t)n, 30); if (rcs) return rcs; }
+    DevTmp<int> all_sel;
+    if ((rc = selection_morton_order(c, d_xyz, n_verts, (const long long *)d_vlist.p, step, n, all4, all_sel, o.pos, finite))) return rc;
+    if (!finite) return OA_OK;                                     // caller falls back to contiguous ranges
+    HIPCHK(o.pts.alloc((size_t)n)); HIPCHK(o.sel.alloc((size_t)n));
     hipLaunchKernelGGL(oa::k_apply_perm, dim3((n + 255) / 256), dim3(256), 0, c->stream, (const float4 *)all4.p, (const int *)all_sel.p,
                        (const int *)o.pos.p, n, n, o.pts.p, o.sel.p);
     HIPCHK(hipGetLastError());
@@ -4558,6 +4574,28 @@ int solve_on_device(oa_ctx *c, const double *d_sums, const double pv[3], int wit
     memcpy(M, out, sizeof(double) * 16);
     return OA_OK;
 }
+// `rows` rows of K doubles, row a at h + a ld on the host -> a fresh d, row a at d + a K; the copies on the context's stream
+int upload_rows(oa_ctx *c, DevTmp<double> &d, const double *h, int rows, int64_t K, int64_t ld)
+{
+    HIPCHK(d.alloc((size_t)rows * (size_t)K));
+    for (int a = 0; a < rows; ++a)
+        HIPCHK(hipMemcpyAsync(d.p + (size_t)a * K, h + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
+    return OA_OK;
+}
+// the end of a plane-row step from caller-supplied pairs (point-to-plane, symmetric): the blocks' partial rows -> their sums -> the
+// 6x6 solve -> M and the rank.  Pairs with unusable normals do not count towards the three a step needs.
+int plane_step_finish(oa_ctx *c, int blocks, const double pv[3], int symmetric, double M[16])
+{
+    hipLaunchKernelGGL(oa::k_reduce_partials_plane, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, (const double *)c->d_partials, blocks, c->d_sums);
+    hipLaunchKernelGGL(oa::k_solve_only_plane, dim3(1), dim3(64), 0, c->stream, (const double *)c->d_sums, pv[0], pv[1], pv[2], symmetric, c->d_solve);
+    HIPCHK(hipGetLastError());
+    double out[18];
+    { int rcr = read_small(c, out, c->d_solve, sizeof out); if (rcr) return rcr; }
+    if (out[16] != 1.0) return fail(OA_E_TOO_FEW_PAIRS, "input arrays are of wrong shape or type");
+    memcpy(M, out, sizeof(double) * 16);
+    c->last_plane_rank = (int)out[17];
+    return OA_OK;
+}
 }  // namespace
 
 OA_EXPORT int oa_kabsch(oa_ctx *c, const double *A, const double *B, int64_t K, int64_t ld, int with_scale, double M[16])
@@ -4570,12 +4608,7 @@ OA_EXPORT int oa_kabsch(oa_ctx *c, const double *A, const double *B, int64_t K, 
     if (rc) return rc;
     if ((rc = ensure_common(c))) return rc;
     DevTmp<double> dA, dB;
-    HIPCHK(dA.alloc(3 * (size_t)K));
-    HIPCHK(dB.alloc(3 * (size_t)K));
-    for (int a = 0; a < 3; ++a) {
-        HIPCHK(hipMemcpyAsync(dA.p + (size_t)a * K, A + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(dB.p + (size_t)a * K, B + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-    }
+    if ((rc = upload_rows(c, dA, A, 3, K, ld)) || (rc = upload_rows(c, dB, B, 3, K, ld))) return rc;
     const double pv[3] = { A[0], A[ld], A[2 * ld] };
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(oa::ACC_MAX_BLOCKS, (K + oa::ACC_THREADS - 1) / oa::ACC_THREADS));
     hipLaunchKernelGGL(oa::k_accumulate_pairs, dim3(blocks), dim3(oa::ACC_THREADS), 0, c->stream, (const double *)dA.p,
@@ -4600,27 +4633,12 @@ OA_EXPORT int oa_point_to_plane(oa_ctx *c, const double *A, const double *B, con
     if (rc) return rc;
     if ((rc = ensure_common(c))) return rc;
     DevTmp<double> dA, dB, dN;
-    HIPCHK(dA.alloc(3 * (size_t)K));
-    HIPCHK(dB.alloc(3 * (size_t)K));
-    HIPCHK(dN.alloc(3 * (size_t)K));
-    for (int a = 0; a < 3; ++a) {
-        HIPCHK(hipMemcpyAsync(dA.p + (size_t)a * K, A + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(dB.p + (size_t)a * K, B + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(dN.p + (size_t)a * K, N + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-    }
+    if ((rc = upload_rows(c, dA, A, 3, K, ld)) || (rc = upload_rows(c, dB, B, 3, K, ld)) || (rc = upload_rows(c, dN, N, 3, K, ld))) return rc;
     const double pv[3] = { A[0], A[ld], A[2 * ld] };
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(oa::ACC_MAX_BLOCKS, (K + oa::ACC_THREADS - 1) / oa::ACC_THREADS));
     hipLaunchKernelGGL(oa::k_accumulate_pairs_plane, dim3(blocks), dim3(oa::ACC_THREADS), 0, c->stream, (const double *)dA.p, (const double *)dB.p,
                        (const double *)dN.p, (long long)K, (long long)K, pv[0], pv[1], pv[2], c->d_partials);
-    hipLaunchKernelGGL(oa::k_reduce_partials_plane, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, (const double *)c->d_partials, blocks, c->d_sums);
-    hipLaunchKernelGGL(oa::k_solve_only_plane, dim3(1), dim3(64), 0, c->stream, (const double *)c->d_sums, pv[0], pv[1], pv[2], 0, c->d_solve);
-    HIPCHK(hipGetLastError());
-    double out[18];
-    { int rcr = read_small(c, out, c->d_solve, sizeof out); if (rcr) return rcr; }
-    if (out[16] != 1.0) return fail(OA_E_TOO_FEW_PAIRS, "input arrays are of wrong shape or type");   // (pairs with unusable normals do not count)
-    memcpy(M, out, sizeof(double) * 16);
-    c->last_plane_rank = (int)out[17];
-    return OA_OK;
+    return plane_step_finish(c, blocks, pv, 0, M);
 }
 
 // the symmetric step from caller-supplied pairs (oa_point_to_plane with both sides' normals): k_accumulate_pairs_symm ->
@@ -4635,29 +4653,13 @@ OA_EXPORT int oa_symmetric_step(oa_ctx *c, const double *A, const double *B, con
     if (rc) return rc;
     if ((rc = ensure_common(c))) return rc;
     DevTmp<double> dA, dB, dNA, dNB;
-    HIPCHK(dA.alloc(3 * (size_t)K));
-    HIPCHK(dB.alloc(3 * (size_t)K));
-    HIPCHK(dNA.alloc(3 * (size_t)K));
-    HIPCHK(dNB.alloc(3 * (size_t)K));
-    for (int a = 0; a < 3; ++a) {
-        HIPCHK(hipMemcpyAsync(dA.p + (size_t)a * K, A + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(dB.p + (size_t)a * K, B + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(dNA.p + (size_t)a * K, NA + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(dNB.p + (size_t)a * K, NB + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-    }
+    if ((rc = upload_rows(c, dA, A, 3, K, ld)) || (rc = upload_rows(c, dB, B, 3, K, ld))) return rc;
+    if ((rc = upload_rows(c, dNA, NA, 3, K, ld)) || (rc = upload_rows(c, dNB, NB, 3, K, ld))) return rc;
     const double pv[3] = { A[0], A[ld], A[2 * ld] };
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(oa::ACC_MAX_BLOCKS, (K + oa::ACC_THREADS - 1) / oa::ACC_THREADS));
     hipLaunchKernelGGL(oa::k_accumulate_pairs_symm, dim3(blocks), dim3(oa::ACC_THREADS), 0, c->stream, (const double *)dA.p, (const double *)dB.p,
                        (const double *)dNA.p, (const double *)dNB.p, (long long)K, (long long)K, pv[0], pv[1], pv[2], c->d_partials);
-    hipLaunchKernelGGL(oa::k_reduce_partials_plane, dim3(1), dim3(oa::RED_THREADS), 0, c->stream, (const double *)c->d_partials, blocks, c->d_sums);
-    hipLaunchKernelGGL(oa::k_solve_only_plane, dim3(1), dim3(64), 0, c->stream, (const double *)c->d_sums, pv[0], pv[1], pv[2], 1, c->d_solve);
-    HIPCHK(hipGetLastError());
-    double out[18];
-    { int rcr = read_small(c, out, c->d_solve, sizeof out); if (rcr) return rcr; }
-    if (out[16] != 1.0) return fail(OA_E_TOO_FEW_PAIRS, "input arrays are of wrong shape or type");   // (pairs with unusable normals do not count)
-    memcpy(M, out, sizeof(double) * 16);
-    c->last_plane_rank = (int)out[17];
-    return OA_OK;
+    return plane_step_finish(c, blocks, pv, 1, M);
 }
 
 // the reference's full signature: any ndims (2..8 on the fixed-size kernels, up to 64 through a device workspace), shear (full
@@ -4679,13 +4681,9 @@ OA_EXPORT int oa_affine_from_points(oa_ctx *c, const double *v0, const double *v
         // Gram entry, the solve with its matrices in a device workspace
         const int D = n <= 16 ? 16 : (n <= 32 ? 32 : 64), m = 2 * n;
         DevTmp<double> d0, d1, d_cs, d_gram, d_out, d_ws;
-        HIPCHK(d0.alloc((size_t)n * K)); HIPCHK(d1.alloc((size_t)n * K));
+        if ((rc = upload_rows(c, d0, v0, n, K, ld)) || (rc = upload_rows(c, d1, v1, n, K, ld))) return rc;
         HIPCHK(d_cs.alloc((size_t)2 * D)); HIPCHK(d_gram.alloc((size_t)m * m)); HIPCHK(d_out.alloc((size_t)w * w + 1));
         HIPCHK(d_ws.alloc(oa::aff_ws_doubles(D)));
-        for (int a = 0; a < n; ++a) {
-            HIPCHK(hipMemcpyAsync(d0.p + (size_t)a * K, v0 + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipMemcpyAsync(d1.p + (size_t)a * K, v1 + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-        }
         hipLaunchKernelGGL(oa::k_affine_rowsum_any, dim3((unsigned)m), dim3(256), 0, c->stream, (const double *)d0.p, (const double *)d1.p, n, D,
                            (long long)K, (long long)K, d_cs.p);
         hipLaunchKernelGGL(oa::k_affine_gram_any, dim3((unsigned)(m * m)), dim3(256), 0, c->stream, (const double *)d0.p, (const double *)d1.p, n, D,
@@ -4705,13 +4703,9 @@ OA_EXPORT int oa_affine_from_points(oa_ctx *c, const double *v0, const double *v
     const long long cols_per_block = ((K + blocks - 1) / blocks + oa::AFF_TILE - 1) / oa::AFF_TILE * oa::AFF_TILE;
     const int gblocks = (int)((K + cols_per_block - 1) / cols_per_block);
     DevTmp<double> d0, d1, p1, p2, d_cs, d_gram, d_out;
-    HIPCHK(d0.alloc((size_t)n * K)); HIPCHK(d1.alloc((size_t)n * K));
+    if ((rc = upload_rows(c, d0, v0, n, K, ld)) || (rc = upload_rows(c, d1, v1, n, K, ld))) return rc;
     HIPCHK(p1.alloc((size_t)blocks * oa::AFF_M2)); HIPCHK(p2.alloc((size_t)gblocks * oa::AFF_M2 * oa::AFF_M2));
     HIPCHK(d_cs.alloc(oa::AFF_M2)); HIPCHK(d_gram.alloc(oa::AFF_M2 * oa::AFF_M2)); HIPCHK(d_out.alloc((size_t)w * w + 1));
-    for (int a = 0; a < n; ++a) {
-        HIPCHK(hipMemcpyAsync(d0.p + (size_t)a * K, v0 + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(d1.p + (size_t)a * K, v1 + (size_t)a * ld, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, c->stream));
-    }
     hipLaunchKernelGGL(oa::k_affine_colsums, dim3(blocks), dim3(256), 0, c->stream, (const double *)d0.p, (const double *)d1.p, n,
                        (long long)K, (long long)K, p1.p);
     hipLaunchKernelGGL(oa::k_affine_reduce, dim3(1), dim3(64), 0, c->stream, (const double *)p1.p, blocks, oa::AFF_M2, d_cs.p);
@@ -5285,10 +5279,23 @@ int target_bbox(oa_ctx *c, double lo[3], double hi[3])
     std::vector<float> bb(6 * (size_t)nb);
     const int rc = read_small(c, bb.data(), d_bb.p, sizeof(float) * bb.size());
     if (rc) return rc;
-    float l[3] = { INFINITY, INFINITY, INFINITY }, h[3] = { -INFINITY, -INFINITY, -INFINITY };
-    for (int b = 0; b < nb; ++b)
-        for (int a = 0; a < 3; ++a) { l[a] = std::min(l[a], bb[6 * (size_t)b + a]); h[a] = std::max(h[a], bb[6 * (size_t)b + 3 + a]); }
+    float l[3], h[3];
+    (void)fold_bbox(bb.data(), nb, l, h);                            // (k_bbox_finite leaves the non-finite coordinates out)
     for (int a = 0; a < 3; ++a) if (l[a] <= h[a]) { lo[a] = l[a]; hi[a] = h[a]; }     // (no finite coordinate: any frame will do)
+    return OA_OK;
+}
+
+// Where a call writes the target normals it computes.  install: the target's own array, allocated on first use -- the stream
+// carries this call alone, so the array the loops read is replaced in place, and a boundary mask built from the old normals no
+// longer holds.  Else `tmp` when the caller wants them (wanted), else nowhere (d_n stays null).
+int new_normals_dest(oa_ctx *c, int install, bool wanted, DevTmp<float> &tmp, float *&d_n)
+{
+    const size_t nt = (size_t)c->tgt.nt;
+    if (install) {
+        if (!c->tgt.d_tgt_n) HIPCHK(dev_malloc(&c->tgt.d_tgt_n, sizeof(float) * 3 * nt));
+        c->tgt.bnd_ok = false;
+        d_n = c->tgt.d_tgt_n;
+    } else if (wanted) { HIPCHK(tmp.alloc(3 * nt)); d_n = tmp.p; }
     return OA_OK;
 }
 
@@ -5380,11 +5387,7 @@ OA_EXPORT int oa_estimate_target_normals(oa_ctx *c, int k, int orient, const flo
     const size_t nt = (size_t)c->tgt.nt;
     DevTmp<float> tmp_n, d_curv;
     float *d_n = nullptr;
-    if (install) {                                                   // (the stream is idle: the array the loops read is replaced in place)
-        if (!c->tgt.d_tgt_n) HIPCHK(dev_malloc(&c->tgt.d_tgt_n, sizeof(float) * 3 * nt));
-        c->tgt.bnd_ok = false;                                           // (a boundary mask was built from the old normals)
-        d_n = c->tgt.d_tgt_n;
-    } else if (out_normals) { HIPCHK(tmp_n.alloc(3 * nt)); d_n = tmp_n.p; }
+    if ((rc = new_normals_dest(c, install, out_normals != nullptr, tmp_n, d_n))) return rc;
     if (out_curvature) HIPCHK(d_curv.alloc(nt));
     if ((rc = knn_launch<true>(c, tree, k, nullptr, nullptr, ko, d_n, d_curv.p))) return rc;
     if (out_normals) HIPCHK(hipMemcpyAsync(out_normals, d_n, sizeof(float) * 3 * nt, hipMemcpyDeviceToHost, c->stream));
@@ -5416,7 +5419,7 @@ OA_EXPORT int oa_orient_target_normals(oa_ctx *c, int k, double max_dist, int se
         return fail(OA_E_STATE, "%s: no normals given and the target has none (oa_set_target_normals, oa_set_normals or oa_estimate_target_normals with install)", who);
     const int nt = c->tgt.nt;
     const long long n_ent = (long long)nt * k;
-    if (n_ent > 2147483648ll - (1 << 20)) return fail(OA_E_CAPACITY, "%s: %d vertices x k = %d is %lld entries (at most 2^31 - 2^20)", who, nt, k, n_ent);
+    if (n_ent > oa::SORT_MAX_N) return fail(OA_E_CAPACITY, "%s: %d vertices x k = %d is %lld entries (at most 2^31 - 2^20)", who, nt, k, n_ent);
     oa::OrientSeed sd{};
     sd.mode = seed;
     if (seed != OA_SEED_KEEP) {
@@ -5442,29 +5445,22 @@ OA_EXPORT int oa_orient_target_normals(oa_ctx *c, int k, double max_dist, int se
     const unsigned v_blocks = (unsigned)((snt + oa::ORI_THREADS - 1) / oa::ORI_THREADS), e_blocks = (unsigned)((sne + oa::ORI_THREADS - 1) / oa::ORI_THREADS);
     const dim3 blk(oa::ORI_THREADS);
     DevTmp<uint8_t> d_elig, d_cflip;
-    DevTmp<uint32_t> d_P, d_Q, d_best, d_ent, d_kw, d_klo, d_khi, d_part;
-    DevTmp<int> d_ord, d_ord2, d_stage;
+    DevTmp<uint32_t> d_P, d_Q, d_best, d_ent, d_kw, d_klo, d_khi;
+    DevTmp<int> d_ord, d_ord2;
     DevTmp<oa::OrientRound> d_round;
     HIPCHK(d_elig.alloc(snt)); HIPCHK(d_cflip.alloc(snt)); HIPCHK(d_P.alloc(snt)); HIPCHK(d_Q.alloc(snt)); HIPCHK(d_best.alloc(snt));
-    HIPCHK(d_ent.alloc(sne)); HIPCHK(d_kw.alloc(sne)); HIPCHK(d_klo.alloc(sne)); HIPCHK(d_khi.alloc(sne)); HIPCHK(d_part.alloc(sne));
-    HIPCHK(d_ord.alloc(sne)); HIPCHK(d_ord2.alloc(sne)); HIPCHK(d_stage.alloc(sne)); HIPCHK(d_round.alloc(1));
+    HIPCHK(d_ent.alloc(sne)); HIPCHK(d_kw.alloc(sne)); HIPCHK(d_klo.alloc(sne)); HIPCHK(d_khi.alloc(sne));
+    HIPCHK(d_ord.alloc(sne)); HIPCHK(d_ord2.alloc(sne)); HIPCHK(d_round.alloc(1));
     const float md = (float)max_dist, cap2 = md * md;
     hipLaunchKernelGGL(oa::k_orient_init, dim3(v_blocks), blk, 0, c->stream, d_xyz, d_nrm, nt, d_elig.p, d_P.p);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(oa::k_orient_entries, dim3(e_blocks), blk, 0, c->stream, (const int32_t *)d_idx.p, (const float *)d_d2.p, d_nrm, (const uint8_t *)d_elig.p, nt, k,
                        n_ent, max_dist > 0.0 ? 1 : 0, cap2, d_ent.p, d_kw.p, d_klo.p, d_khi.p);
     HIPCHK(hipGetLastError());
-    const unsigned g_blocks = (unsigned)((sne + 255) / 256);
     const int idx_bits = bits_for((long long)nt);
     if ((rc = sort_order_bits(c, d_khi.p, d_ord.p, sne, idx_bits))) return rc;
-    hipLaunchKernelGGL(oa::k_gather_int, dim3(g_blocks), dim3(256), 0, c->stream, (const int *)d_klo.p, (const int *)d_ord.p, (int)n_ent, (int *)d_part.p);
-    HIPCHK(hipGetLastError());
-    if ((rc = sort_order_bits(c, d_part.p, d_stage.p, sne, idx_bits))) return rc;
-    hipLaunchKernelGGL(oa::k_gather_int, dim3(g_blocks), dim3(256), 0, c->stream, (const int *)d_ord.p, (const int *)d_stage.p, (int)n_ent, d_ord2.p);
-    hipLaunchKernelGGL(oa::k_gather_int, dim3(g_blocks), dim3(256), 0, c->stream, (const int *)d_kw.p, (const int *)d_ord2.p, (int)n_ent, (int *)d_part.p);
-    HIPCHK(hipGetLastError());
-    if ((rc = sort_order_bits(c, d_part.p, d_stage.p, sne, oa::ORI_W_BITS))) return rc;
-    hipLaunchKernelGGL(oa::k_gather_int, dim3(g_blocks), dim3(256), 0, c->stream, (const int *)d_ord2.p, (const int *)d_stage.p, (int)n_ent, d_ord.p);
+    if ((rc = lex_order_next(c, d_klo.p, idx_bits, d_ord.p, d_ord2.p, sne))) return rc;
+    if ((rc = lex_order_next(c, d_kw.p, oa::ORI_W_BITS, d_ord2.p, d_ord.p, sne))) return rc;
     uint32_t *const d_rank = d_khi.p;                               // (the keys have been read)
     hipLaunchKernelGGL(oa::k_orient_rank, dim3(e_blocks), blk, 0, c->stream, (const int *)d_ord.p, n_ent, d_rank);
     HIPCHK(hipGetLastError());
@@ -5520,11 +5516,7 @@ OA_EXPORT int oa_orient_target_normals(oa_ctx *c, int k, double max_dist, int se
                        (const uint32_t *)(seed != OA_SEED_KEEP ? d_seed_of.p : d_label), d_cflip.p, d_info.p);
     HIPCHK(hipGetLastError());
     float *d_out = nullptr;
-    if (install) {                                                   // (the stream carries this call alone: the array the loops read is replaced in place)
-        if (!c->tgt.d_tgt_n) HIPCHK(dev_malloc(&c->tgt.d_tgt_n, sizeof(float) * 3 * snt));
-        c->tgt.bnd_ok = false;                                           // (a boundary mask was built from the old normals)
-        d_out = c->tgt.d_tgt_n;
-    } else if (out_normals) { HIPCHK(tmp_out.alloc(3 * snt)); d_out = tmp_out.p; }
+    if ((rc = new_normals_dest(c, install, out_normals != nullptr, tmp_out, d_out))) return rc;
     hipLaunchKernelGGL(oa::k_orient_apply, dim3(v_blocks), blk, 0, c->stream, (const uint32_t *)d_P.p, (const uint8_t *)d_elig.p, (const uint8_t *)d_cflip.p,
                        (const uint32_t *)d_label, d_nrm, nt, d_out, d_flipped.p, d_comp.p, d_info.p);
     HIPCHK(hipGetLastError());
@@ -5784,27 +5776,24 @@ namespace {
 // the cell of a coordinate, as k_voxel_keys computes it (the same three fp64 operations), kept a double: it may be huge
 inline double voxel_cell_of(float x, double o, double h) { return floor(((double)x - o) / h); }
 
-// order[0 .. n) = the stable ascending order of the keys' low `bits` bits (1 .. 64): one argsort for up to 32 bits, else an LSD
-// sort in stages of 30 bits -- argsort the slice read through the order so far, compose the two orders (stability does the rest)
+// order[0 .. n) = the stable ascending order of the keys' low `bits` bits (1 .. 64): one argsort for up to 32 bits, else the
+// lexicographic order of their 30-bit slices, the lowest slice first
 int voxel_sort_keys(oa_ctx *c, const unsigned long long *d_keys, int n, int bits, DevTmp<int> &order)
 {
     const unsigned blocks = (unsigned)(((size_t)n + oa::VOX_THREADS - 1) / oa::VOX_THREADS);
     const int width = bits <= 32 ? bits : 30;
     DevTmp<uint32_t> part;
-    DevTmp<int> stage_order, composed;
+    DevTmp<int> prev;
     HIPCHK(part.alloc((size_t)n)); HIPCHK(order.alloc((size_t)n));
-    if (bits > width) { HIPCHK(stage_order.alloc((size_t)n)); HIPCHK(composed.alloc((size_t)n)); }
+    if (bits > width) HIPCHK(prev.alloc((size_t)n));
     for (int shift = 0; shift < bits; shift += width) {
         const int w = std::min(width, bits - shift);
         const unsigned mask = w >= 32 ? 0xFFFFFFFFu : ((1u << w) - 1u);
-        hipLaunchKernelGGL(oa::k_voxel_key_part, dim3(blocks), dim3(oa::VOX_THREADS), 0, c->stream, d_keys, shift ? (const int *)order.p : (const int *)nullptr, n,
-                           shift, mask, part.p);
+        hipLaunchKernelGGL(oa::k_voxel_key_part, dim3(blocks), dim3(oa::VOX_THREADS), 0, c->stream, d_keys, n, shift, mask, part.p);
         HIPCHK(hipGetLastError());
-        if (shift == 0) { const int rc = sort_order_bits(c, part.p, order.p, (size_t)n, w); if (rc) return rc; continue; }
-        { const int rc = sort_order_bits(c, part.p, stage_order.p, (size_t)n, w); if (rc) return rc; }
-        hipLaunchKernelGGL(oa::k_gather_int, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, c->stream, (const int *)order.p, (const int *)stage_order.p, n, composed.p);
-        HIPCHK(hipGetLastError());
-        std::swap(order.p, composed.p);
+        if (shift) std::swap(order.p, prev.p);
+        const int rc = shift ? lex_order_next(c, part.p, w, prev.p, order.p, (size_t)n) : sort_order_bits(c, part.p, order.p, (size_t)n, w);
+        if (rc) return rc;
     }
     return OA_OK;
 }
@@ -5816,7 +5805,7 @@ OA_EXPORT int oa_voxel_downsample(oa_ctx *c, const float *xyz, int64_t n, int on
     if (!c || !xyz) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: null argument");
     OA_NOT_MULTI(c, "oa_voxel_downsample");
     if (!(voxel > 0.0) || !(voxel < (double)INFINITY)) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: voxel = %g (finite and > 0)", voxel);
-    if (n < 1 || n > (int64_t)2147483648ll - (1 << 20)) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: %lld points (1 .. 2^31 - 2^20)", (long long)n);
+    if (n < 1 || n > (int64_t)oa::SORT_MAX_N) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: %lld points (1 .. 2^31 - 2^20)", (long long)n);
     if (normals && !out_normals) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: normals given and nowhere to put the rows' normals");
     if (origin)
         for (int a = 0; a < 3; ++a)
@@ -5850,11 +5839,9 @@ OA_EXPORT int oa_voxel_downsample(oa_ctx *c, const float *xyz, int64_t n, int on
         std::vector<int> cnt((size_t)nb);
         HIPCHK(hipMemcpyAsync(bb.data(), d_bb.p, sizeof(float) * bb.size(), hipMemcpyDeviceToHost, c->stream));
         if ((rc = read_small(c, cnt.data(), d_cnt.p, sizeof(int) * cnt.size()))) return rc;
-        float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-        for (int b = 0; b < nb; ++b) {
-            r.n_finite += cnt[(size_t)b];
-            for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], bb[6 * (size_t)b + a]); hi[a] = std::max(hi[a], bb[6 * (size_t)b + 3 + a]); }
-        }
+        float lo[3], hi[3];
+        (void)fold_bbox(bb.data(), nb, lo, hi);                      // (k_voxel_bbox leaves the non-finite points out)
+        for (int b = 0; b < nb; ++b) r.n_finite += cnt[(size_t)b];
         if (rep) *rep = r;
         if (r.n_finite < 1) return fail(OA_E_BAD_ARG, "oa_voxel_downsample: none of the %lld points has three finite coordinates", (long long)n);
         g.h = voxel;
@@ -5962,7 +5949,7 @@ OA_EXPORT int oa_normal_space_sample(oa_ctx *c, const float *normals, int64_t n,
     OA_NOT_MULTI(c, "oa_normal_space_sample");
     if (m < 1) return fail(OA_E_BAD_ARG, "oa_normal_space_sample: m = %lld points wanted (>= 1)", (long long)m);
     if (grid < 1 || grid > oa::NSS_MAX_GRID) return fail(OA_E_BAD_ARG, "oa_normal_space_sample: grid = %d (1 .. %d)", (int)grid, oa::NSS_MAX_GRID);
-    if (n < 1 || n > (int64_t)2147483648ll - (1 << 20)) return fail(OA_E_BAD_ARG, "oa_normal_space_sample: %lld normals (1 .. 2^31 - 2^20)", (long long)n);
+    if (n < 1 || n > (int64_t)oa::SORT_MAX_N) return fail(OA_E_BAD_ARG, "oa_normal_space_sample: %lld normals (1 .. 2^31 - 2^20)", (long long)n);
     if (cap < 0 || !out_idx) cap = 0;
     int rc = use_device(c);
     if (rc) return rc;
@@ -5980,26 +5967,21 @@ OA_EXPORT int oa_normal_space_sample(oa_ctx *c, const float *normals, int64_t n,
     const float *d_nrm = nullptr;
     if ((rc = stage_floats(c, normals, 3 * sn, on_device, tmp_nrm, d_nrm))) return rc;
     // 1. bins and hash keys
-    DevTmp<int> d_bin, d_by_hash, d_stage, d_order, d_counts, d_share, d_flag;
-    DevTmp<uint32_t> d_bin_key, d_hash, d_key_sorted;
+    DevTmp<int> d_bin, d_by_hash, d_order, d_counts, d_share, d_flag;
+    DevTmp<uint32_t> d_bin_key, d_hash;
     DevTmp<long long> d_start, d_off, d_out;
     DevTmp<oa::NssInfo> d_info;
     DevTmp<char> scan_tmp;
     HIPCHK(d_bin.alloc(sn)); HIPCHK(d_bin_key.alloc(sn)); HIPCHK(d_hash.alloc(sn));
-    HIPCHK(d_by_hash.alloc(sn)); HIPCHK(d_key_sorted.alloc(sn)); HIPCHK(d_stage.alloc(sn)); HIPCHK(d_order.alloc(sn));
+    HIPCHK(d_by_hash.alloc(sn)); HIPCHK(d_order.alloc(sn));
     HIPCHK(d_counts.alloc((size_t)n_bins)); HIPCHK(d_share.alloc((size_t)n_bins)); HIPCHK(d_start.alloc((size_t)n_bins));
     HIPCHK(d_flag.alloc(sn)); HIPCHK(d_off.alloc(sn + 1)); HIPCHK(d_out.alloc((size_t)room)); HIPCHK(d_info.alloc(1));
     hipLaunchKernelGGL(oa::k_nss_keys, dim3(pt_blocks), dim3(oa::NSS_THREADS), 0, c->stream, d_nrm, ni, G, unoriented ? 1 : 0, seed, n_bins, d_bin.p, d_bin_key.p,
                        d_hash.p);
     HIPCHK(hipGetLastError());
-    // 2. by hash, then stably by bin: argsort the hashes, argsort the bins read through that order, compose (as voxel_sort_keys)
+    // 2. the order (bin, hash): by hash, then stably by bin
     if ((rc = sort_order_bits(c, d_hash.p, d_by_hash.p, sn, 32))) return rc;
-    hipLaunchKernelGGL(oa::k_gather_int, dim3((unsigned)((sn + 255) / 256)), dim3(256), 0, c->stream, (const int *)d_bin_key.p, (const int *)d_by_hash.p, ni,
-                       (int *)d_key_sorted.p);
-    HIPCHK(hipGetLastError());
-    if ((rc = sort_order_bits(c, d_key_sorted.p, d_stage.p, sn, bits_for((long long)n_bins + 1)))) return rc;
-    hipLaunchKernelGGL(oa::k_gather_int, dim3((unsigned)((sn + 255) / 256)), dim3(256), 0, c->stream, (const int *)d_by_hash.p, (const int *)d_stage.p, ni, d_order.p);
-    HIPCHK(hipGetLastError());
+    if ((rc = lex_order_next(c, d_bin_key.p, bits_for((long long)n_bins + 1), d_by_hash.p, d_order.p, sn))) return rc;
     // 3., 4. the bins' counts, the level and every bin's share
     HIPCHK(hipMemsetAsync(d_counts.p, 0, sizeof(int) * (size_t)n_bins, c->stream));
     hipLaunchKernelGGL(oa::k_nss_hist, dim3(std::min<unsigned>(pt_blocks, oa::NSS_HIST_BLOCKS)), dim3(oa::NSS_THREADS), 0, c->stream, (const int *)d_bin.p, ni, n_bins,
@@ -6040,10 +6022,9 @@ OA_EXPORT int oa_stability(oa_ctx *c, const float *xyz, const float *normals, in
 {
     if (!c || !xyz || !normals || !rep) return fail(OA_E_BAD_ARG, "oa_stability: null argument");
     OA_NOT_MULTI(c, "oa_stability");
-    constexpr int64_t most = (int64_t)2147483648ll - (1 << 20);
-    if (n < 1 || n > most) return fail(OA_E_BAD_ARG, "oa_stability: %lld points (1 .. 2^31 - 2^20)", (long long)n);
+    if (n < 1 || n > (int64_t)oa::SORT_MAX_N) return fail(OA_E_BAD_ARG, "oa_stability: %lld points (1 .. 2^31 - 2^20)", (long long)n);
     if (idx) {
-        if (n_idx < 1 || n_idx > most) return fail(OA_E_BAD_ARG, "oa_stability: %lld indices (1 .. 2^31 - 2^20)", (long long)n_idx);
+        if (n_idx < 1 || n_idx > (int64_t)oa::SORT_MAX_N) return fail(OA_E_BAD_ARG, "oa_stability: %lld indices (1 .. 2^31 - 2^20)", (long long)n_idx);
         for (int64_t k = 0; k < n_idx; ++k)
             if (idx[k] < 0 || idx[k] >= n) return fail(OA_E_BAD_ARG, "oa_stability: idx[%lld] = %lld outside 0 .. %lld", (long long)k, (long long)idx[k], (long long)n - 1);
     }
@@ -6123,7 +6104,7 @@ int ensure_corner_rows(oa_ctx *c)
 {
     if (c->tgt.corner_ok) return OA_OK;
     const size_t n_corners = 3 * (size_t)c->tgt.n_tris, nv = (size_t)c->tgt.nt;
-    if (n_corners > (size_t)0x7FF00000) return fail(OA_E_CAPACITY, "the mesh's corner rows: %zu corners (the sort takes fewer than 2^31 - 2^20)", n_corners);
+    if (n_corners > (size_t)oa::SORT_MAX_N) return fail(OA_E_CAPACITY, "the mesh's corner rows: %zu corners (the sort takes fewer than 2^31 - 2^20)", n_corners);
     HIPCHK(dev_malloc(&c->tgt.d_corner_order, sizeof(int) * n_corners));
     HIPCHK(dev_malloc(&c->tgt.d_corner_row, sizeof(long long) * (nv + 1)));
     // (the indices were checked at upload: all in 0 .. nt - 1, so they are their own keys; oa_sort.hpp adds 10-bit passes as the bits ask)
@@ -6354,12 +6335,7 @@ OA_EXPORT int oa_deviation(oa_ctx *c, const oa_deviation_settings *ds, double *s
     hipLaunchKernelGGL(oa::k_dev_finish, dim3(1), dim3(oa::DEV_FIN_THREADS), 0, c->stream, (const oa::DevRow *)d_rows.p, n_rows, d_rows.p + n_rows);
     HIPCHK(hipGetLastError());
     if (nq > 0) {
-        const unsigned hist_blocks = (unsigned)std::min(oa::SEL_HIST_MAX_BLOCKS, std::max(1, (c->src.ns + oa::SEL_THREADS - 1) / oa::SEL_THREADS));
-        for (int level = 0; level < oa::SEL_LEVELS; ++level) {
-            hipLaunchKernelGGL(oa::k_dev_select_hist, dim3(hist_blocks, (unsigned)nq), dim3(oa::SEL_THREADS), 0, c->stream, (const oa::DevSelect *)d_sel.p,
-                               (const uint32_t *)d_dkeys.p, c->src.ns, level, d_qhist.p);
-            hipLaunchKernelGGL(oa::k_dev_select_scan, dim3((unsigned)nq), dim3(oa::SEL_THREADS), 0, c->stream, d_sel.p, (const uint32_t *)d_qhist.p, level);
-        }
+        launch_dev_select(c, d_sel.p, nq, (const uint32_t *)d_dkeys.p, d_qhist.p, false);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(h_sel, d_sel.p, sizeof(oa::DevSelect) * (size_t)nq, hipMemcpyDeviceToHost, c->stream));
     }

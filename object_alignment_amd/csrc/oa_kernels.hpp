@@ -785,7 +785,7 @@ __device__ __forceinline__ unsigned spread10(unsigned v)
 
 #if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
 __global__ void k_morton_keys(const float4 *__restrict__ src4, int ns, float lx, float ly, float lz, float sx, float sy,
-                              float sz, unsigned *__restrict__ keys, int *__restrict__ slots)
+                              float sz, unsigned *__restrict__ keys)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= ns) return;
@@ -793,7 +793,6 @@ __global__ void k_morton_keys(const float4 *__restrict__ src4, int ns, float lx,
     const float fx = fminf(fmaxf((p.x - lx) * sx, 0.f), 1023.f), fy = fminf(fmaxf((p.y - ly) * sy, 0.f), 1023.f),
                 fz = fminf(fmaxf((p.z - lz) * sz, 0.f), 1023.f);      // NaN -> 0 through fmaxf
     keys[i] = spread10((unsigned)fx) | (spread10((unsigned)fy) << 1) | (spread10((unsigned)fz) << 2);
-    slots[i] = i;
 }
 
 // sorted slot i takes original slot perm[i]; the padding repeats the last sorted point
@@ -1414,15 +1413,13 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_filt
 // loop) then finds a tight best at once instead of sweeping towards it, and a seeded one tightens its seeds at once (the order
 // never changes an answer, only how soon the thresholds are final).
 #if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
-__global__ void k_sort_keys_axis(const float *__restrict__ xyz, int nt, int axis, double lo, double scale, unsigned *__restrict__ keys,
-                                 int *__restrict__ ids)
+__global__ void k_sort_keys_axis(const float *__restrict__ xyz, int nt, int axis, double lo, double scale, unsigned *__restrict__ keys)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nt) return;
     double t = ((double)xyz[3ll * i + axis] - lo) * scale;
     t = t < 0.0 ? 0.0 : (t > 1073741823.0 ? 1073741823.0 : t);
     keys[i] = (unsigned)t;
-    ids[i] = i;
 }
 
 // images in sorted order, per group of 4 positions: tfs [qu][-2qv][qu^2+qv^2] (LDS tiles; -2qu is exact from qu), tf3s [-2qd][|q|^2],

@@ -23,6 +23,8 @@ namespace oa {
 
 constexpr int SORT_BITS = 10, SORT_BINS = 1 << SORT_BITS, SORT_THREADS = 256, SORT_WAVES = SORT_THREADS / 64;
 constexpr int SORT_ITEMS = 8, SORT_TILE = SORT_THREADS * SORT_ITEMS, SORT_WAVE_ITEMS = 64 * SORT_ITEMS;
+// the most items the callers hand to a sort, 2^31 - 2^20: n, the indices and the launches' thread counts are ints with room to round up
+constexpr long long SORT_MAX_N = 2147483648ll - (1 << 20);
 
 #if defined(__HIPCC__)
 
@@ -251,6 +253,28 @@ inline hipError_t sort_order(void *tmp, const uint32_t *keys, int *order, size_t
         return hipGetLastError();
     }
     return sort_order_lsd(tmp, keys, order, n, bits, stream);
+}
+
+// ---- orders by several keys ----------------------------------------------------------------------------------------------------
+// The stable order by (k_last, ..., k_1, k_0), k_0 the least significant: sort_order by k_0, then one lex_order_next per further
+// key -- argsort the key read through the order so far, read that order through the result.  Stability does the rest: items equal
+// in the new key keep the places the keys before gave them.
+//   order[j] = prev[the j-th place of the stable order of keys[prev[.]]]          (prev: a permutation of 0 .. n-1; order != prev)
+// keys[0 .. n) (low `bits` bits, the others zero) are READ AND THEN OVERWRITTEN: the stage's own argsort lands there.
+// tmp: lex_order_tmp_bytes(n) bytes, 8-byte aligned -- the gathered keys, then sort_order's.  Everything on `stream`, no wait.
+inline size_t lex_order_tmp_bytes(size_t n) { return 8 * ((n + 1) / 2) + (n > (size_t)SORT_SMALL_MAX ? sort_order_tmp_bytes(n) : 0); }
+
+inline hipError_t lex_order_next(void *tmp, uint32_t *keys, int bits, const int *prev, int *order, size_t n, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    uint32_t *part = (uint32_t *)tmp;
+    int *stage = (int *)keys;
+    const dim3 grid((unsigned)((n + 255) / 256)), blk(256);
+    hipLaunchKernelGGL(k_gather_int, grid, blk, 0, stream, (const int *)keys, prev, (int)n, (int *)part);
+    const hipError_t e = sort_order((void *)(part + 2 * ((n + 1) / 2)), part, stage, n, bits, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_gather_int, grid, blk, 0, stream, prev, (const int *)stage, (int)n, order);
+    return hipGetLastError();
 }
 #endif
 

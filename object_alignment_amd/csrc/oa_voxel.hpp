@@ -4,7 +4,7 @@
 //
 //   k_voxel_bbox         per workgroup {min xyz, max xyz} and the number of points whose three coordinates are finite
 //   k_voxel_keys         key = (c_z dims_y + c_y) dims_x + c_x, c = floor(((double)x - o) / voxel); all ones when not finite
-//   k_voxel_key_part     a <= 32-bit slice of the keys, read through the order so far: the input of one stage of the LSD sort
+//   k_voxel_key_part     a <= 32-bit slice of the keys: one key of the lexicographic order (oa_sort.hpp, lex_order_next)
 //   k_voxel_heads        1 where the sorted key changes
 //   k_voxel_row_start    first sorted position of every row (+ the end of the last)
 //   k_voxel_row_chunks   chunks a LONG row (more than VOX_CHUNK members) is cut into; 0 for a short one
@@ -111,13 +111,12 @@ __global__ __launch_bounds__(VOX_THREADS) void k_voxel_keys(const float *__restr
 }
 
 // out[j] = bits [shift, shift + width) of the key of the point at position j of `order` (order == nullptr: of point j)
-__global__ __launch_bounds__(VOX_THREADS) void k_voxel_key_part(const unsigned long long *__restrict__ keys, const int *__restrict__ order, int n,
-                                                                int shift, unsigned mask, uint32_t *__restrict__ out)
+__global__ __launch_bounds__(VOX_THREADS) void k_voxel_key_part(const unsigned long long *__restrict__ keys, int n, int shift, unsigned mask,
+                                                                uint32_t *__restrict__ out)
 {
     const long long j = (long long)blockIdx.x * VOX_THREADS + threadIdx.x;
     if (j >= n) return;
-    const unsigned long long k = keys[order ? order[j] : (int)j];
-    out[j] = (uint32_t)(k >> shift) & mask;
+    out[j] = (uint32_t)(keys[j] >> shift) & mask;
 }
 
 __global__ __launch_bounds__(VOX_THREADS) void k_voxel_heads(const unsigned long long *__restrict__ keys, const int *__restrict__ order, int n_finite,

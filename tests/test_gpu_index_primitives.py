@@ -6,7 +6,7 @@ compaction, k_gather_int, and the compaction itself end to end through IcpEngine
 tools/sort_check.exe (built by __graft_entry__.build_tools()) holds no reference: it reads inputs from files, runs the library's
 code and writes the device's output; it also keeps guard zones round every output and round a temporary buffer of exactly
 sort_order_tmp_bytes(n) / scan_tmp_bytes(n) bytes, and reads the inputs back.  The references are here:
-np.argsort(keys & mask, kind="stable"), np.cumsum in int64, src[idx].  One process per test, many cases each."""
+np.argsort(keys & mask, kind="stable"), np.lexsort for the orders by several keys (lex_order_next), np.cumsum in int64, src[idx].  One process per test, many cases each."""
 import os
 import subprocess
 
@@ -39,6 +39,15 @@ def sort_case(name, mode, bits, keys):
     assert np.array_equal(keys & mask_of(bits), keys), name     # (the sorts' contract: the bits above `bits` are zero)
     want = np.argsort(keys & mask_of(bits), kind="stable").astype(np.int32)
     return ("sort %s bits=%d n=%d %s" % (mode, bits, len(keys), name), ["sort", mode, str(bits), str(len(keys))], [keys], want)
+
+
+def lex_case(name, bits, keys):
+    """keys: the least significant key first, as np.lexsort takes them (its last key is the primary one)"""
+    keys = [np.ascontiguousarray(k, dtype=np.uint32) for k in keys]
+    for b, k in zip(bits, keys):
+        assert np.array_equal(k & mask_of(b), k), name
+    want = np.lexsort(keys).astype(np.int32)
+    return ("lex bits=%s n=%d %s" % (bits, len(keys[0]), name), ["lex", str(len(keys)), str(len(keys[0]))] + [str(b) for b in bits], keys, want)
 
 
 def scan_case(name, mode, counts):
@@ -193,6 +202,31 @@ def test_lsd_sort_keeps_index_order_in_every_key_pattern(tmp_path, n):
     """Three passes over patterns that put all items in one bin, all lanes of a round in one peer group or each in its own,
     and passes that are no-ops on the keys and must keep the order the others made."""
     run_cases(tmp_path, [sort_case(name, "lsd", 30, k) for name, k in lsd_patterns(n, 30, n)])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# orders by several keys: sort_order, then lex_order_next per further key
+# ---------------------------------------------------------------------------------------------------------------------
+LEX_WIDTHS = ((1, 1), (10, 11, 30), (32, 5), (3, 3, 3))              # the least significant key first
+LEX_FEW = {(1, 1): (0, 1), (10, 11, 30): (0,), (32, 5): (1,), (3, 3, 3): (1,)}   # the keys that draw from fewer than 8 values
+
+
+def test_lex_order_is_numpys_lexsort(tmp_path):
+    """The edge sort of the normal orientation (w, lo, hi), the sampling's (bin, hash) and the voxel keys' slices all go through
+    this: against np.lexsort, exactly, on either side of SORT_SMALL_MAX = 8192 (the only size at which the path switches), with
+    two and three keys of widths from 1 to 32 bits, at least one key of every tuple drawing from fewer than 8 values (a one-bit key
+    has two), and with all keys equal: then the order is the identity."""
+    cases = []
+    for n in (1, 2, 63, 8191, 8192, 8193, 20000):
+        for widths in LEX_WIDTHS:
+            keys = [keys_few(n, b, 1000 * n + 10 * j + b, distinct=min(5, 1 << b)) if j in LEX_FEW[widths] else keys_ties(n, b, 1000 * n + 10 * j + b)
+                    for j, b in enumerate(widths)]
+            assert all(len(np.unique(keys[j])) < 8 for j in LEX_FEW[widths])
+            cases.append(lex_case("ties", widths, keys))
+    for n in (8192, 20000):
+        cases.append(lex_case("all equal", (10, 11, 30), [np.full(n, v, np.uint32) for v in (1023, 5, 0x2AAAAAAA)]))
+        assert np.array_equal(cases[-1][3], np.arange(n, dtype=np.int32))
+    run_cases(tmp_path, cases)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,20 +1,25 @@
 // sort_check.hip -- the index builds' primitives run on caller-supplied inputs: the stable argsorts (oa_sort.hpp: k_sort_small,
-// the LSD passes), the prefix sums (scan_counts_ll; k_scan_counts of oa_kernels.hpp, launched as oa_make_pairs does) and
+// the LSD passes), the orders by several keys (lex_order_next), the prefix sums (scan_counts_ll; k_scan_counts of oa_kernels.hpp, launched as oa_make_pairs does) and
 // k_gather_int.  It holds no reference and makes no inputs: it reads them from files, runs the library's code on the device and
 // writes what the device returned; tests/test_gpu_index_primitives.py compares that with numpy.
 // build: __graft_entry__.build_tools()     run: tools/sort_check.exe MANIFEST
 // MANIFEST: one case per line (paths without blanks; '#' starts a comment line)
 //   sort auto|lsd BITS N KEYS OUT      uint32 keys[N] -> int32 order[N]        auto: oa::sort_order, lsd: oa::sort_order_lsd whatever N
-//   scan ll|block N COUNTS OUT         int32 counts[N] -> int64 offsets[N + 1] ll: oa::scan_counts_ll, block: oa::k_scan_counts <<<1, 1024>>>
+//   lex NKEYS N BITS.. KEYS.. OUT      NKEYS widths, then NKEYS files of uint32 keys[N], the LEAST significant key first -> int32 order[N]:
+//                                      oa::sort_order on the first key, oa::lex_order_next once per further key
+//   scan ll|block N COUNTS OUT        int32 counts[N] -> int64 offsets[N + 1] ll: oa::scan_counts_ll, block: oa::k_scan_counts <<<1, 1024>>>
 //   gather NSRC N SRC IDX OUT          int32 src[NSRC], idx[N] -> int32 out[N] oa::k_gather_int with sort_ints' launch shape
-// Every device output, and the temporary buffer of exactly sort_order_tmp_bytes(N) / scan_tmp_bytes(N) bytes, lies between two
-// guard zones filled with a byte pattern that must survive the run; the inputs are read back and must be unchanged.  One line
+// Every device output, and the temporary buffer of exactly sort_order_tmp_bytes(N) / lex_order_tmp_bytes(N) / scan_tmp_bytes(N)
+// bytes, lies between two guard zones filled with a byte pattern that must survive the run; the inputs are read back and must be
+// unchanged (lex_order_next overwrites its keys: it gets a guarded copy, the input stays).  One line
 // per case with the verdicts; the first HIP error or violated guard ends the process with a non-zero status.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <cstdint>
+#include <memory>
+#include <sstream>
 #include <string>
 #include <vector>
 #include "oa_kernels.hpp"
@@ -127,6 +132,39 @@ int main(int argc, char **argv)
             const bool g_out = order.intact(h.data()), g_tmp = tmp.intact(nullptr);
             write_file(line_no, f1, h.data(), sizeof(int) * h.size());
             verdict(line_no, lsd ? "sort lsd" : "sort auto", (size_t)n, g_out && g_tmp, keys.untouched());
+        } else if (strcmp(mode, "lex") == 0) {
+            int nk = 0; long long n = 0;
+            std::istringstream words(line);
+            std::string word;
+            words >> word >> nk >> n;
+            if (!words || nk < 1 || nk > 8 || n < 1 || n > n_max) die(line_no, "bad lex arguments");
+            std::vector<int> bits((size_t)nk);
+            std::vector<std::string> paths((size_t)nk + 1);
+            for (int &b : bits) { words >> b; if (!words || b < 1 || b > 32) die(line_no, "bad lex key width"); }
+            for (std::string &p : paths) if (!(words >> p)) die(line_no, "malformed lex line");
+            // key 0 is only read; a later key is the stage's scratch, so the function gets a guarded copy of it
+            std::vector<std::unique_ptr<Input<uint32_t>>> keys;
+            std::vector<std::unique_ptr<Guarded>> scratch;
+            for (int k = 0; k < nk; ++k) {
+                keys.emplace_back(new Input<uint32_t>(line_no, paths[(size_t)k].c_str(), (size_t)n));
+                if (k == 0) continue;
+                scratch.emplace_back(new Guarded(sizeof(uint32_t) * (size_t)n));
+                CHK(hipMemcpy(scratch.back()->p(), keys.back()->dev, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice));
+            }
+            Guarded tmp(oa::lex_order_tmp_bytes((size_t)n)), ord_a(sizeof(int) * (size_t)n), ord_b(sizeof(int) * (size_t)n);
+            Guarded *cur = &ord_a, *other = &ord_b;
+            CHK(oa::sort_order(tmp.p(), keys[0]->dev, (int *)cur->p(), (size_t)n, bits[0], 0));
+            for (int k = 1; k < nk; ++k) {
+                CHK(oa::lex_order_next(tmp.p(), (uint32_t *)scratch[(size_t)k - 1]->p(), bits[(size_t)k], (const int *)cur->p(), (int *)other->p(), (size_t)n, 0));
+                std::swap(cur, other);
+            }
+            CHK(hipDeviceSynchronize());
+            std::vector<int> h((size_t)n);
+            bool guards = cur->intact(h.data()) && other->intact(nullptr) && tmp.intact(nullptr), inputs = true;
+            for (const auto &s : scratch) guards = guards && s->intact(nullptr);
+            for (const auto &k : keys) inputs = inputs && k->untouched();
+            write_file(line_no, paths[(size_t)nk].c_str(), h.data(), sizeof(int) * h.size());
+            verdict(line_no, "lex", (size_t)n, guards, inputs);
         } else if (strcmp(mode, "scan") == 0) {
             long long n;
             if (sscanf(line, "%*s %15s %lld %2047s %2047s", sub, &n, f0, f1) != 4) die(line_no, "malformed scan line");
