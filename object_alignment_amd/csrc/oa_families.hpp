@@ -17,7 +17,7 @@
 // ---- signatures (explicit instantiation needs the parameter types) --------------------------------------------------
 #define OA_SIG_NN_SEARCH const DevState *, const float4 *, const float4 *, int, unsigned long long *
 #define OA_SIG_NN_FILTERED const DevState *, const float4 *, const float4 *, const float4 *, const float4 *, const float4 *, int, unsigned long long *
-#define OA_SIG_POINT_SETUP const DevState *, const float4 *, const float4 *, const unsigned long long *, int, int, int, int, int, int, float4 *
+#define OA_SIG_POINT_SETUP const DevState *, const float4 *, const float4 *, const unsigned long long *, int, int, int, int, int, int, float4 *, float
 #define OA_SIG_SEED_SORTED const DevState *, const float4 *, int, const float4 *, const float4 *, const int4 *, int, int, unsigned long long *
 #define OA_SIG_NN_SORTED const DevState *, const float4 *, const float4 *, const float4 *, const int4 *, int, unsigned long long *, int, const float4 *, int, int, const int *, int *, int, const float4 *
 #define OA_SIG_NN_GRID const DevState *, const float4 *, int, GridParams, const int *, const float4 *, float4 *, unsigned long long *, int *, int *, int, BvhParams, const float4 *, const float4 *, NormalTest, double *, unsigned long long *, const float *, uint2 *

@@ -329,6 +329,8 @@ struct oa_target {
     // the same images in the order of the coordinate along the cloud's longest axis (k_nn_search_sorted, round 5)
     DevBuf<float4> d_tfs, d_tf3s, d_tgs;   // 3 / 2 / 3 float4 per group of 4 sorted positions
     DevBuf<float4> d_tmw;            // level 0's pair images, 1 float4 per group: {m, w} of positions (0, 1) and (2, 3) (oa_pairgap.hpp)
+    DevBuf<float4> d_toct;           // level 0's quad images, 3 float4 per 4 groups: {mm}, {ww}, {ws} of a chunk of 16 positions (oa_octgap.hpp)
+    float oct_c = 0.0f;              // the cap d_toct was built with (0 while there are no images); k_sorted_point_setup gets it at launch
     DevBuf<int4> d_tidx;             // original index of every sorted position
     DevBuf<oa::half8> d_tfm;         // the MFMA experiment's image of the target
     bool filter_ok = false;
@@ -1274,7 +1276,8 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
         const dim3 ob((unsigned)(c->src.ns_pad / (64 * c->src.R)));
         dispatch<4, 1, 2, 8>(c->src.R, [&](auto R) {
             hipLaunchKernelGGL((oa::k_sorted_point_setup<decltype(R)::value>), ob, dim3(64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->src.d_src4,
-                               (const float4 *)c->src.d_win, (const unsigned long long *)c->src.d_keys, c->sax[0], c->sax[1], pass, c->tune.nn_wave_order ? 1 : 0, c->src.ns_pad, c->src.ns, c->src.d_prec);
+                               (const float4 *)c->src.d_win, (const unsigned long long *)c->src.d_keys, c->sax[0], c->sax[1], pass, c->tune.nn_wave_order ? 1 : 0, c->src.ns_pad, c->src.ns, c->src.d_prec,
+                               c->tgt.oct_c);                       // (the cap of the quad images this very search reads: oa_octgap.hpp)
         });
         HIPCHK(hipGetLastError());
     }
@@ -1287,9 +1290,12 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
     }
     if (queued) sgrid = dim3((unsigned)q_wgs);
     auto launch = [&](auto R, auto TG, auto VCHUNK) {
+        // level 0's own images: the quads' for the instances that fold them (round 18), else the pairs'
+        const bool oct = oa::sorted_oct(decltype(R)::value) && decltype(VCHUNK)::value;
+        const float4 *l0 = oct ? (const float4 *)c->tgt.d_toct : (const float4 *)c->tgt.d_tmw;
         hipLaunchKernelGGL((oa::k_nn_search_sorted<decltype(R)::value, decltype(TG)::value, decltype(VCHUNK)::value>), sgrid, dim3(oa::NN_THREADS), 0, c->stream,
                            c->d_state, (const float4 *)c->tgt.d_tgs, (const float4 *)c->tgt.d_tfs, (const float4 *)c->tgt.d_tf3s, (const int4 *)c->tgt.d_tidx,
-                           c->tgt.n_groups_pad, c->src.d_keys, pass, (const float4 *)c->src.d_prec, q_splits, q_blocks, c->src.d_homes, queued ? c->src.d_qcnt : nullptr, c->tgt.nt, (const float4 *)c->tgt.d_tmw);
+                           c->tgt.n_groups_pad, c->src.d_keys, pass, (const float4 *)c->src.d_prec, q_splits, q_blocks, c->src.d_homes, queued ? c->src.d_qcnt : nullptr, c->tgt.nt, l0);
     };
     auto search = [&](auto R) { dispatch<oa::FTILE_GROUPS, 64>(c->tile_groups, [&](auto TG) { if (c->tune.nn_vchunk) launch(R, TG, yes); else launch(R, TG, no); }); };
 #if defined(OA_EXPERIMENTS)
@@ -2723,7 +2729,7 @@ bool fold_bbox(const float *bb, int nb, float lo[3], float hi[3])
 // inside a loop.
 int build_sorted_images(oa_ctx *c)
 {
-    c->tgt.d_tfs.reset(); c->tgt.d_tf3s.reset(); c->tgt.d_tgs.reset(); c->tgt.d_tmw.reset(); c->tgt.d_tidx.reset();
+    c->tgt.d_tfs.reset(); c->tgt.d_tf3s.reset(); c->tgt.d_tgs.reset(); c->tgt.d_tmw.reset(); c->tgt.d_toct.reset(); c->tgt.oct_c = 0.0f; c->tgt.d_tidx.reset();
     if (!(c->tgt.filter_ok && c->tune.nn_sort && c->tgt.nt >= 2)) return OA_OK;
     const double *lo = c->bb_lo, *hi = c->bb_hi;
     const int ad = c->fax[2];
@@ -2750,8 +2756,17 @@ int build_sorted_images(oa_ctx *c)
     HIPCHK(dev_malloc(&c->tgt.d_tgs, sizeof(float4) * 3 * (size_t)c->tgt.n_groups_pad));
     HIPCHK(dev_malloc(&c->tgt.d_tidx, sizeof(int4) * (size_t)c->tgt.n_groups_pad));
     HIPCHK(dev_malloc(&c->tgt.d_tmw, sizeof(float4) * (size_t)c->tgt.n_groups_pad));
+    HIPCHK(dev_malloc(&c->tgt.d_toct, sizeof(float4) * 3 * (size_t)(c->tgt.n_groups_pad / 4)));
+    // level 0's cap (oa_octgap.hpp: any value >= 0 is valid, it only tunes what the quads' bound loses): the mean half-span in u
+    // of a block of 256 sorted vertices -- pairs of a quad further apart than that are the sparse regions' (OA_SORTED_OCT_CAP: a
+    // build-time factor for sweeps, oa_kernels.hpp)
+    {
+        const double cap = ext * 128.0 / (double)c->tgt.nt * (double)(OA_SORTED_OCT_CAP);
+        c->tgt.oct_c = (cap >= 0.0 && cap < 1e18) ? (float)cap : 0.0f;
+    }
     hipLaunchKernelGGL(oa::k_pack_sorted, dim3((unsigned)blocks), dim3(256), 0, c->stream, (const float *)c->tgt.d_tgt_xyz, c->tgt.nt, c->tgt.n_groups_pad,
-                       (const int *)v_out.p, c->tc[0], c->tc[1], c->tc[2], c->sax[0], c->sax[1], c->sax[2], c->tgt.d_tfs, c->tgt.d_tf3s, c->tgt.d_tgs, c->tgt.d_tidx, c->tgt.d_tmw);
+                       (const int *)v_out.p, c->tc[0], c->tc[1], c->tc[2], c->sax[0], c->sax[1], c->sax[2], c->tgt.d_tfs, c->tgt.d_tf3s, c->tgt.d_tgs, c->tgt.d_tidx, c->tgt.d_tmw,
+                       c->tgt.oct_c, c->tgt.d_toct);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));                      // (the temporaries are released on return)
     return OA_OK;
@@ -2796,7 +2811,7 @@ int build_filter(oa_ctx *c, bool vertex_target)
     for (double v : mx) if (v > m) m = v;
     c->qmax = sqrt(m) * (1.0 + 1e-6);
     c->tgt.filter_ok = (c->qmax < 1e18);
-    c->tgt.d_tfs.reset(); c->tgt.d_tf3s.reset(); c->tgt.d_tgs.reset(); c->tgt.d_tmw.reset(); c->tgt.d_tidx.reset();
+    c->tgt.d_tfs.reset(); c->tgt.d_tf3s.reset(); c->tgt.d_tgs.reset(); c->tgt.d_tmw.reset(); c->tgt.d_toct.reset(); c->tgt.oct_c = 0.0f; c->tgt.d_tidx.reset();
     // k_nn_search_sorted's images are built for the search mode that uses them: a target uploaded for the grid / tree searches
     // (OA_SEARCH_AUTO, the default) does not pay for them; oa_set_search_mode(OA_SEARCH_BRUTE) builds them when it finds none
     // (a mesh's surface searches never launch k_nn_search_sorted: no images, no sort -- ~36 B per vertex)

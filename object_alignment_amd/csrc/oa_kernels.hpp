@@ -23,6 +23,7 @@
 #include <type_traits>
 #include "oa_pairgap.hpp"
 #include "oa_quadgap.hpp"
+#include "oa_octgap.hpp"
 
 namespace oa {
 
@@ -1389,6 +1390,19 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_filt
 //                       in an arithmetic test, nothing from a block's bounds, any permutation of either side the same answers.
 //                       A pair that is not ruled out marks the block for both its points; level 0v and levels 1-3 then decide per
 //                       point, with their own thr1, as before.  OA_SORTED_QUAD=0 (build time): round 11's fold per point.
+//                       Round 18 (VCHUNK = true, R = 2 and 4; the R = 8 experiment stays on round 13's fold): a third nesting, on the two vertex pairs of a group.  The upload keeps
+//                       {mm, ww, ws} per group (toct, k_pack_sorted): the midpoint and half-distance of the pairs' midpoints, the
+//                       latter capped at c, and the wider pair's half-width plus what the cap cut off; the set-up keeps
+//                       hw' = max(hw, c) and adds e = hw' - hw to the pair's allowance.  ww <= c <= hw' whatever the widths, and
+//                           t = | | |mm - hm| - hw' | - ww | - ws     (signed; four subtractions for eight (vertex, point) pairs)
+//                       never exceeds the smallest of the eight gaps by more than e and the allowance (oa_octgap.hpp: the order
+//                       of the nesting is what makes it a bound, the cap is what makes the order true).  512 v_sub + 62 v_min3 +
+//                       2 v_min + 2 v_cmp per lane of four points and 256 vertices: 0.57 instructions per pair where round 13
+//                       takes 0.88, and three tile reads per 16 vertices instead of four.  Looser than round 13: the narrower
+//                       pair counts as wide as the wider, a quad whose pairs lie further apart than 2 c degrades towards an
+//                       interval, a lane whose points nearly share their u pays e <= c of reach (the instructions outside the fold: +0.7 % at 1M <-> 1M).
+//                       Still every quad and every point pair in its own arithmetic test, every tile visited, nothing decided
+//                       per block or tile.  OA_SORTED_OCT=0 (build time): round 13's fold.
 //   level 0v (rare)     for a block some lane hit (OA_NN_VCHUNK=1): the same gap along v, a_j = fl32(hv - qv_j) against the same
 //                       thr1, from the ENDS of each chunk of 4 OA_SORTED_VCG vertices.  Positions 1 .. n-1 of a block are in the
 //                       order of qv (k_sort_blocks_v), and rounding is monotone, so a_j does not increase along a chunk: with F, L
@@ -1426,9 +1440,11 @@ __global__ void k_sort_keys_axis(const float *__restrict__ xyz, int nt, int axis
 // tgs [x][y][z] (exact), tidx original indices.  Same centring and roundings as k_pack_filter / k_pack_target.
 // tmw (round 11): level 0's pair images {m01, w01, m23, w23} of the group's positions (0, 1) and (2, 3), from the same qu
 // (pair_image, oa_pairgap.hpp) -- positions of the FINAL order, k_sort_blocks_v's included.
+// toct (round 18): level 0's quad images {mm, ww, ws} of the group's two pairs under the cap oct_c (quad_image, oa_octgap.hpp), from
+// the same pair images; three float4 per chunk of 4 groups -- the chunk's four mm, its four ww, its four ws.
 __global__ void k_pack_sorted(const float *__restrict__ xyz, int nt, int n_groups_pad, const int *__restrict__ order, float cx, float cy,
                               float cz, int au, int av, int ad, float4 *__restrict__ tfs, float4 *__restrict__ tf3s,
-                              float4 *__restrict__ tgs, int4 *__restrict__ tidx, float4 *__restrict__ tmw)
+                              float4 *__restrict__ tgs, int4 *__restrict__ tidx, float4 *__restrict__ tmw, float oct_c, float4 *__restrict__ toct)
 {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_groups_pad) return;
@@ -1470,6 +1486,10 @@ __global__ void k_pack_sorted(const float *__restrict__ xyz, int nt, int n_group
     pair_image(qu[0], id[0] >= 0, qu[1], id[1] >= 0, mw.x, mw.y);
     pair_image(qu[2], id[2] >= 0, qu[3], id[3] >= 0, mw.z, mw.w);
     tmw[g] = mw;
+    float mm, ww, ws;
+    quad_image(mw.x, mw.y, id[0] >= 0, mw.z, mw.w, id[2] >= 0, oct_c, mm, ww, ws);
+    float *oc = reinterpret_cast<float *>(toct + 3ll * (g >> 2)) + (g & 3);      // (n_groups_pad is a multiple of 4: whole chunks)
+    oc[0] = mm; oc[4] = ww; oc[8] = ws;
 }
 #endif  // !OA_FAMILY_TU
 
@@ -1548,13 +1568,29 @@ __device__ __forceinline__ bool sorted_finish_group(const float4 AU, const float
     return sorted_finish_level2(AU, AV, group, tf3s, tgs, tidx, pco, hu, hv, hd, qmax, best, bidx, thr1, thr2);
 }
 
+#ifndef OA_SORTED_QUAD
+#define OA_SORTED_QUAD 1                  // 1: level 0 of the <R >= 2, TG, true> instances on pairs of the lane's points (round 13,
+#endif                                    //  oa_quadgap.hpp); 0: round 11's per-point fold alone (a build-time knob for sweeps)
+#ifndef OA_SORTED_OCT
+#define OA_SORTED_OCT 1                   // 1: ... and on quads of vertices, 4 subtracts per 8 gaps (round 18, oa_octgap.hpp);
+#endif                                    //  0: round 13's fold on pairs of vertices (a build-time knob for sweeps)
+#ifndef OA_SORTED_OCT_CAP
+#define OA_SORTED_OCT_CAP 1.0             // the quads' cap in mean half-spans of a block of 256 sorted vertices (build_sorted_images;
+#endif                                    //  any value >= 0 gives the same answers: profiles/r18a_vertex_quads.txt has the sweep)
+// which instances fold quads: R = 2 and 4 (the R = 8 experiment instances stay on round 13's fold); asked by the set-up, the kernel
+// and the launcher alike, so that they agree
+constexpr bool sorted_oct(int R) { return OA_SORTED_QUAD && OA_SORTED_OCT && R >= 2 && R <= 4; }
+
 // Everything k_nn_search_sorted needs to know about a point that does not depend on the split, once per search instead of once
 // per (split, block) item -- 136 times per point in a seeded 1M <-> 1M launch: co_find, the centred coordinates, the seed and
 // its distance, the thresholds.  One RECORD per slot, three float4 in three arrays of ns_pad entries (rec, rec + ns_pad,
 // rec + 2 ns_pad):
 //   [0] hu, hv, hd, the slot's index (int bits)     [1] best, bidx (uint bits), thr1, thr2     [2] px, py, pz (co_find), 0
 // and (R >= 2, round 13) a fourth array, rec + 3 ns_pad: per lane and pair of its points (2p, 2p + 1), at first + 64 p + lane of the
-// wave's records, {hm, hw, allowance, 0} -- the pair's image along u and what rounding can add to its gap (oa_quadgap.hpp).
+// wave's records, {hm, hw, allowance, 0} -- the pair's image along u and what rounding can add to its gap (oa_quadgap.hpp);
+// since round 18 (R = 2, 4) {hm, max(hw, c), allowance + e, 0} with the cap c = oct_c the target's quad images were built with
+// (oa_octgap.hpp) -- a launch argument, read from the target beside its images: the bound needs the SAME c on both sides, and the
+// images may be built while a sequence is open (oa_set_search_mode), after the device state was staged.
 // The seed is the slot's winner record (pass 0) or what k_nn_seed_sorted left in keys (pass 2: this kernel runs after it).
 // The arithmetic is the item prologue's of before, through the same device functions: the same floats.
 // WHERE a slot's record lies decides which lane takes it as its point r: record first + 64 r + lane of a wave's 64 R records
@@ -1569,7 +1605,8 @@ __device__ __forceinline__ bool sorted_finish_group(const float4 AU, const float
 template <int R>
 __global__ __launch_bounds__(64) void k_sorted_point_setup(const DevState *__restrict__ st, const float4 *__restrict__ src4,
                                                            const float4 *__restrict__ win, const unsigned long long *__restrict__ keys,
-                                                           int au, int av, int pass, int ranked, int ns_pad, int ns, float4 *__restrict__ rec)
+                                                           int au, int av, int pass, int ranked, int ns_pad, int ns, float4 *__restrict__ rec,
+                                                           float oct_c)
 {
     if (st->halt) return;
     constexpr int N = 64 * R;
@@ -1648,8 +1685,17 @@ __global__ __launch_bounds__(64) void k_sorted_point_setup(const DevState *__res
             const float h1 = pu[128 * p + t], h2 = pu[128 * p + 64 + t];
             const bool claim = (h1 - h1 == 0.0f) && (h2 - h2 == 0.0f) && key[128 * p + t] == key[128 * p + 64 + t];
             float hm, hw;
-            point_pair_image(h1, h2, hm, hw);
-            rec[3 * ns_pad + first + 64 * p + t] = make_float4(hm, hw, claim ? round_up_to_float(quad_allowance(qmax, h1, h2)) : INFINITY, 0.f);
+            if constexpr (sorted_oct(R)) {
+                // round 18: {hm, hw' = max(hw, c), allowance + e, 0} -- the half-width under the target's cap and what the cap adds
+                // to the pair's reach, in the allowance's place (oa_octgap.hpp (2), (3)): quad_threshold is fed as before
+                double e;
+                const float c = oct_c;
+                point_pair_image_capped(h1, h2, c, hm, hw, e);
+                rec[3 * ns_pad + first + 64 * p + t] = make_float4(hm, hw, claim ? round_up_to_float(oct_allowance(qmax, h1, h2, c) + e) : INFINITY, 0.f);
+            } else {
+                point_pair_image(h1, h2, hm, hw);
+                rec[3 * ns_pad + first + 64 * p + t] = make_float4(hm, hw, claim ? round_up_to_float(quad_allowance(qmax, h1, h2)) : INFINITY, 0.f);
+            }
         }
     }
 }
@@ -1741,9 +1787,6 @@ __global__ void k_sorted_block_homes(const DevState *__restrict__ st, const floa
 #ifndef OA_SORTED_VCG
 #define OA_SORTED_VCG 4                   // groups of 4 sorted vertices per chunk of level 0v (a build-time knob for sweeps;
 #endif                                    //  2 / 4 / 8: 25.46 / 24.99 / 24.94 ms at 1M <-> 1M, profiles/r08a_vends.txt)
-#ifndef OA_SORTED_QUAD
-#define OA_SORTED_QUAD 1                  // 1: level 0 of the <R >= 2, TG, true> instances on pairs of the lane's points (round 13,
-#endif                                    //  oa_quadgap.hpp); 0: round 11's per-point fold alone (a build-time knob for sweeps)
 #ifndef OA_SORTED_VREFINE
 #define OA_SORTED_VREFINE 0               // 1: level 0v's end test again per group of a passing chunk, ahead of level 1 (25.11 ms)
 #endif
@@ -1806,8 +1849,11 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
     __shared__ float4 tile[2][TILE_F4];
     // level 0's own tile (VCHUNK): the pair images of the same groups, one float4 per group -- beside the three of tfs, which
     // levels 0v-3 go on reading
+    // (round 18, R >= 2: the quad images instead, three float4 per chunk of 4 groups -- tmw then points at them, launch_brute_sorted)
     constexpr bool PAIRS = VCHUNK;
-    __shared__ float4 tilew[2][PAIRS ? TG : 1];
+    constexpr bool OCT = PAIRS && sorted_oct(R);
+    constexpr int TW = OCT ? TG / 4 * 3 : TG;                       // float4 of level 0's tile
+    __shared__ float4 tilew[2][PAIRS ? TW : 1];
     __shared__ unsigned long long clk0[2];
     __shared__ int s_item[3];                                       // the workgroup's item {split, block}; [2]: the queues found empty so far
     const int tid0 = threadIdx.x;
@@ -1908,9 +1954,9 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                                         : (((k) & 1) ? tile_s + (((k) + 1) >> 1) : tile_s - ((k) >> 1)))
 
     float4 stg0 = make_float4(0.f, 0.f, 0.f, 0.f), stg1 = stg0, stg2 = stg0, stgw = stg0;
-    const float4 *wsrc = tmw + g_begin;
-#define OA_STGW_ON (PAIRS && (TG >= NN_THREADS || tid < TG))
-    static_assert(TG <= NN_THREADS, "k_nn_search_sorted: one float4 of pair images per thread and tile");
+    const float4 *wsrc = tmw + (OCT ? g_begin / 4 * 3 : g_begin);   // (g_begin: a multiple of TG)
+#define OA_STGW_ON (PAIRS && (TW >= NN_THREADS || tid < TW))
+    static_assert(TW <= NN_THREADS && TG % 4 == 0, "k_nn_search_sorted: one float4 of level 0's images per thread and tile");
 #define OA_STG_ON(k) (WHOLE || (k) * NN_THREADS + tid < TILE_F4)
 #define OA_STG_EACH(OP)                                       \
     do {                                                      \
@@ -1923,7 +1969,7 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
 #define OA_STG_FIRST(k, reg) reg = fsrc[(k) * NN_THREADS + tid]; tile[0][(k) * NN_THREADS + tid] = reg
         OA_STG_EACH(OA_STG_FIRST);
 #undef OA_STG_FIRST
-        if (OA_STGW_ON) { stgw = wsrc[TG * OA_TILE_AT(0) + tid]; tilew[0][tid] = stgw; }
+        if (OA_STGW_ON) { stgw = wsrc[TW * OA_TILE_AT(0) + tid]; tilew[0][tid] = stgw; }
     }
     __syncthreads();
 
@@ -1940,7 +1986,7 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
 #define OA_STG_LOAD(k, reg) reg = nsrc[(k) * NN_THREADS + ltid]
             OA_STG_EACH(OA_STG_LOAD);
 #undef OA_STG_LOAD
-            if (OA_STGW_ON) stgw = wsrc[TG * nt1 + ltid];
+            if (OA_STGW_ON) stgw = wsrc[TW * nt1 + ltid];
         }
         const int gbase = g_begin + OA_TILE_AT(t) * TG;
         // 4 GW = 256 vertices x R points per skip test.  On gfx950 v_sub_f32 issues at full rate, v_min_f32, v_min3_f32 and v_cmp_*_f32
@@ -1960,23 +2006,41 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                 // t > qthr rules out both vertices for both points.  Per 16 vertices and point pair 24 subtracts and 4 min3 (no
                 // modifier on their sources) where the per-point fold below spends 32 and 8; the same tile reads
                 float qm[R / 2], qodd[R / 2];
+                if constexpr (OCT) {
+                    // round 18, on QUADS of vertices (proof in oa_octgap.hpp): the signed t = |||mm - hm| - hw'| - ww| - ws never
+                    // exceeds the smallest of the eight gaps by more than e and the pair's allowance, both inside qthr.  Per 16
+                    // vertices and point pair 16 subtracts and 2 min3, from three tile reads instead of four
 #pragma unroll
-                for (int c = 0; c < GW / 4; ++c) {
-                    float4 MW[4];
+                    for (int c = 0; c < GW / 4; ++c) {
+                        const float4 MM = tilew[cur][3 * (g / 4 + c)], WW = tilew[cur][3 * (g / 4 + c) + 1], WS = tilew[cur][3 * (g / 4 + c) + 2];
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) MW[k] = tilew[cur][g + 4 * c + k];
-#pragma unroll
-                    for (int p = 0; p < R / 2; ++p) {
-                        float a[8];
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            a[2 * k] = quad_gap(MW[k].x, MW[k].y, qhm[p], qhw[p]); a[2 * k + 1] = quad_gap(MW[k].z, MW[k].w, qhm[p], qhw[p]);
+                        for (int p = 0; p < R / 2; ++p) {
+                            const float a0 = oct_gap(MM.x, WW.x, WS.x, qhm[p], qhw[p]), a1 = oct_gap(MM.y, WW.y, WS.y, qhm[p], qhw[p]);
+                            const float a2 = oct_gap(MM.z, WW.z, WS.z, qhm[p], qhw[p]), a3 = oct_gap(MM.w, WW.w, WS.w, qhm[p], qhw[p]);
+                            const float v = c == 0 ? a0 : __builtin_fminf(__builtin_fminf(qm[p], qodd[p]), a0);
+                            qm[p] = __builtin_fminf(__builtin_fminf(v, a1), a2);                                      // v_min3_f32
+                            qodd[p] = a3;
                         }
-                        float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(qm[p], qodd[p]), a[0]);
+                    }
+                } else {
 #pragma unroll
-                        for (int k = 1; k + 1 < 8; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);   // v_min3_f32
-                        qm[p] = v;
-                        qodd[p] = a[7];
+                    for (int c = 0; c < GW / 4; ++c) {
+                        float4 MW[4];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) MW[k] = tilew[cur][g + 4 * c + k];
+#pragma unroll
+                        for (int p = 0; p < R / 2; ++p) {
+                            float a[8];
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                a[2 * k] = quad_gap(MW[k].x, MW[k].y, qhm[p], qhw[p]); a[2 * k + 1] = quad_gap(MW[k].z, MW[k].w, qhm[p], qhw[p]);
+                            }
+                            float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(qm[p], qodd[p]), a[0]);
+#pragma unroll
+                            for (int k = 1; k + 1 < 8; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);   // v_min3_f32
+                            qm[p] = v;
+                            qodd[p] = a[7];
+                        }
                     }
                 }
                 // a pair that cannot rule the block out marks BOTH its points: level 0v and levels 1-3 decide per point as they

@@ -1,11 +1,12 @@
 // Issue rates of the vector-ALU instructions the search kernels choose between, measured on the GPU box (not part of the library).
-//   hipcc --offload-arch=gfx950 -O3 -Wno-unused-value -o tools/_exp/valu_rates tools/valu_rates.hip     (here: cross-compiles)
+//   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -Wno-unused-value -I object_alignment_amd/csrc -o tools/_exp/valu_rates tools/valu_rates.hip
 //   gpurun -- 'tools/_exp/valu_rates'                                                                   (results: profiles/r05q_valu_rates.txt)
 // Each kernel runs 16 independent dependency chains of ONE instruction per lane, 8 waves per SIMD on every SIMD; the figure is
 // nanoseconds per wave-instruction per SIMD (1.0 ns ~ one instruction every two cycles at ~2 GHz = the full rate).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include "oa_octgap.hpp"
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 template <int OP> __global__ __launch_bounds__(256) void burn(float *out, int trips, float seed)
 {
@@ -57,6 +58,8 @@ template <int OP> __global__ __launch_bounds__(256) void burn(float *out, int tr
                 if (OP == 42) asm volatile("v_fma_f32 %0, |%0|, 1.0, -%1" : "+v"(a[k]) : "v"(b));         // the same value through the fma pipe
                 if (OP == 43) asm volatile("v_sub_f32 %0, %0, %1\n\tv_sub_f32_e64 %0, |%0|, %2\n\tv_sub_f32_e64 %0, |%0|, %1"    // round 13: the quad gap's chain
                                            : "+v"(a[k]) : "v"(b), "v"(c));                                   // (three instructions)
+                if (OP == 44) asm volatile("v_sub_f32 %0, %0, %1\n\tv_sub_f32_e64 %0, |%0|, %2\n\tv_sub_f32_e64 %0, |%0|, %1\n\tv_sub_f32_e64 %0, |%0|, %2"
+                                           : "+v"(a[k]) : "v"(b), "v"(c));                                   // round 18: the oct gap's chain (four)
                 if (OP == 19) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(*(double*)&a[k & ~1]) : "v"(*(double*)&b));
             }
     }
@@ -100,6 +103,71 @@ template <int MIX> __global__ __launch_bounds__(256) void mix(float *out, int tr
     }
     float s = 0; for (int k = 0; k < 16; ++k) s += a[k];
     if (s == 12345.678f) out[0] = s;
+}
+// Round 18: level 0's fold of a block of 256 vertices for a lane of 4 points (two point pairs) as k_nn_search_sorted writes it, the
+// tile registers fed by broadcast ds_read_b128 from LDS -- the compiler's own schedule of the library's own functions:
+//   OCT 0 (round 13)  per 16 vertices 4 float4 of pair images, 2 x 24 subtracts + 2 x 4 min3 (oa_quadgap.hpp)       6 : 1, 16 tile registers
+//   OCT 1 (round 18)  per 16 vertices 3 float4 of quad images, 2 x 16 subtracts + 2 x 2 min3 (oa_octgap.hpp)        8 : 1, 12 tile registers
+// A trip is one block: 256 vertices x 4 points = 1024 (vertex, point) pairs per lane.
+template <int OCT> __global__ __launch_bounds__(256, 2) void fold(float *out, int trips, float seed)
+{
+    __shared__ float4 tl[2][64];
+    if (threadIdx.x < 128) tl[threadIdx.x >> 6][threadIdx.x & 63] = make_float4(seed * 0.5f + threadIdx.x, seed, seed * 3.0f - threadIdx.x, seed * 0.125f);
+    __syncthreads();
+    float qhm[2] = {seed + threadIdx.x, seed * 2.0f - threadIdx.x}, qhw[2] = {seed * 0.25f, seed * 0.375f}, qthr[2] = {seed * 1e9f, seed * 2e9f};
+    int hits = 0;
+    for (int t = 0; t < trips; ++t) {
+        int cur = t & 1;
+        asm volatile("" : "+s"(cur));                          // (the tile anew every trip, as the kernel's)
+        float qm[2], qodd[2];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            if (OCT) {
+                const float4 MM = tl[cur][3 * c], WW = tl[cur][3 * c + 1], WS = tl[cur][3 * c + 2];
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    const float a0 = oa::oct_gap(MM.x, WW.x, WS.x, qhm[p], qhw[p]), a1 = oa::oct_gap(MM.y, WW.y, WS.y, qhm[p], qhw[p]);
+                    const float a2 = oa::oct_gap(MM.z, WW.z, WS.z, qhm[p], qhw[p]), a3 = oa::oct_gap(MM.w, WW.w, WS.w, qhm[p], qhw[p]);
+                    const float v = c == 0 ? a0 : __builtin_fminf(__builtin_fminf(qm[p], qodd[p]), a0);
+                    qm[p] = __builtin_fminf(__builtin_fminf(v, a1), a2);
+                    qodd[p] = a3;
+                }
+            } else {
+                float4 MW[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) MW[k] = tl[cur][4 * c + k];
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    float a[8];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        a[2 * k] = oa::quad_gap(MW[k].x, MW[k].y, qhm[p], qhw[p]); a[2 * k + 1] = oa::quad_gap(MW[k].z, MW[k].w, qhm[p], qhw[p]);
+                    }
+                    float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(qm[p], qodd[p]), a[0]);
+#pragma unroll
+                    for (int k = 1; k + 1 < 8; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);
+                    qm[p] = v;
+                    qodd[p] = a[7];
+                }
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < 2; ++p) hits += !(__builtin_fminf(qm[p], qodd[p]) > qthr[p]) ? 1 : 0;
+    }
+    if (hits == 12345) out[0] = (float)hits;
+}
+template <int OCT> void run_fold(const char *name, int wps)
+{
+    float *d; (void)hipMalloc(&d, 4);
+    hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    const int trips = 100000, blocks = 256 * wps;
+    fold<OCT><<<blocks, 256>>>(d, 100, 1.0f);
+    (void)hipDeviceSynchronize();
+    (void)hipEventRecord(e0); fold<OCT><<<blocks, 256>>>(d, trips, 1.0f); (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
+    float ms; (void)hipEventElapsedTime(&ms, e0, e1);
+    const double pairs = (double)wps * trips * 1024.0;        // (vertex, point) pairs per lane, per SIMD
+    printf("%-34s %8.3f ms  %d waves/SIMD  %.4f ns per (vertex, point) pair per SIMD\n", name, ms, wps, ms * 1e6 / pairs);
+    (void)hipFree(d);
 }
 // wps waves per SIMD (the search kernel runs at 4); per_step instructions and vertices per inner step
 template <int MIX> void run_mix(const char *name, int wps, int per_step, int vertices)
@@ -147,5 +215,12 @@ int main()
     run<17>("v_sub_f32 (again)"); run<43>("v_sub -> v_sub_e64 |.| -> v_sub_e64 |.|", 3);
     run_mix<1>("level 0 on pairs, sub (4:1)", 4, 5, 4); run_mix<3>("level 0 on point pairs (6:1)", 4, 7, 8);
     run_mix<1>("level 0 on pairs, sub (4:1)", 8, 5, 4); run_mix<3>("level 0 on point pairs (6:1)", 8, 7, 8);
+    // round 18 (profiles/r18a_vertex_quads.txt): the oct gap | | |mm - hm| - hw'| - ww | - ws, four dependent subtracts, and the
+    // block's fold from LDS tiles beside round 13's in the same run
+    run<17>("v_sub_f32 (again)"); run<43>("v_sub -> 2 x v_sub_e64 |.|", 3); run<44>("v_sub -> 3 x v_sub_e64 |.|", 4);
+    for (int rep = 0; rep < 2; ++rep) {
+        run_fold<0>("fold, point pairs (6:1, LDS)", 4); run_fold<1>("fold, vertex quads (8:1, LDS)", 4);
+        run_fold<0>("fold, point pairs (6:1, LDS)", 8); run_fold<1>("fold, vertex quads (8:1, LDS)", 8);
+    }
     return 0;
 }
