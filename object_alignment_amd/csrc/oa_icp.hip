@@ -329,7 +329,7 @@ struct oa_target {
     // the same images in the order of the coordinate along the cloud's longest axis (k_nn_search_sorted, round 5)
     DevBuf<float4> d_tfs, d_tf3s, d_tgs;   // 3 / 2 / 3 float4 per group of 4 sorted positions
     DevBuf<float4> d_tmw;            // level 0's pair images, 1 float4 per group: {m, w} of positions (0, 1) and (2, 3) (oa_pairgap.hpp)
-    DevBuf<float4> d_toct;           // level 0's quad images, 3 float4 per 4 groups: {mm}, {ww}, {ws} of a chunk of 16 positions (oa_octgap.hpp)
+    DevBuf<float4> d_toct;           // level 0's images of OA_SORTED_OCT_V positions each, 3 float4 per 4 images: their {mm}, {ww}, {ws} (oa_octgap.hpp)
     float oct_c = 0.0f;              // the cap d_toct was built with (0 while there are no images); k_sorted_point_setup gets it at launch
     DevBuf<int4> d_tidx;             // original index of every sorted position
     DevBuf<oa::half8> d_tfm;         // the MFMA experiment's image of the target
@@ -2756,7 +2756,8 @@ int build_sorted_images(oa_ctx *c)
     HIPCHK(dev_malloc(&c->tgt.d_tgs, sizeof(float4) * 3 * (size_t)c->tgt.n_groups_pad));
     HIPCHK(dev_malloc(&c->tgt.d_tidx, sizeof(int4) * (size_t)c->tgt.n_groups_pad));
     HIPCHK(dev_malloc(&c->tgt.d_tmw, sizeof(float4) * (size_t)c->tgt.n_groups_pad));
-    HIPCHK(dev_malloc(&c->tgt.d_toct, sizeof(float4) * 3 * (size_t)(c->tgt.n_groups_pad / 4)));
+    const int n_images = c->tgt.n_groups_pad / (OA_SORTED_OCT_V / 4);   // (n_groups_pad: a multiple of 256, whole images and whole fours of them)
+    HIPCHK(dev_malloc(&c->tgt.d_toct, sizeof(float4) * 3 * (size_t)(n_images / 4)));
     // level 0's cap (oa_octgap.hpp: any value >= 0 is valid, it only tunes what the quads' bound loses): the mean half-span in u
     // of a block of 256 sorted vertices -- pairs of a quad further apart than that are the sparse regions' (OA_SORTED_OCT_CAP: a
     // build-time factor for sweeps, oa_kernels.hpp)
@@ -2768,6 +2769,11 @@ int build_sorted_images(oa_ctx *c)
                        (const int *)v_out.p, c->tc[0], c->tc[1], c->tc[2], c->sax[0], c->sax[1], c->sax[2], c->tgt.d_tfs, c->tgt.d_tf3s, c->tgt.d_tgs, c->tgt.d_tidx, c->tgt.d_tmw,
                        c->tgt.oct_c, c->tgt.d_toct);
     HIPCHK(hipGetLastError());
+    if constexpr (OA_SORTED_OCT_V != 4) {                         // round 19: the images of 8 (16) positions, from what k_pack_sorted has written
+        hipLaunchKernelGGL((oa::k_group_images<OA_SORTED_OCT_V>), dim3((unsigned)((n_images + 255) / 256)), dim3(256), 0, c->stream, (const float4 *)c->tgt.d_tfs,
+                           (const int4 *)c->tgt.d_tidx, n_images, c->tgt.oct_c, c->tgt.d_toct);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipStreamSynchronize(c->stream));                      // (the temporaries are released on return)
     return OA_OK;
 }

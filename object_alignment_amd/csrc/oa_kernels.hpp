@@ -1403,7 +1403,18 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_filt
 //                       interval, a lane whose points nearly share their u pays e <= c of reach (the instructions outside the fold: +0.7 % at 1M <-> 1M).
 //                       Still every quad and every point pair in its own arithmetic test, every tile visited, nothing decided
 //                       per block or tile.  OA_SORTED_OCT=0 (build time): round 13's fold.
-//   level 0v (rare)     for a block some lane hit (OA_NN_VCHUNK=1): the same gap along v, a_j = fl32(hv - qv_j) against the same
+//                       Round 19 (the same instances): one image {mm, ww, ws} per V = OA_SORTED_OCT_V = 16 sorted positions instead of
+//                       per 4 (toct, k_group_images after k_pack_sorted): any three floats with 0 <= ww <= c and every vertex
+//                       of the group within ws of mm + ww or mm - ww, as stored (group_image, oa_octgap.hpp (1')-(6')).  The
+//                       chain, hw', e, the allowance and the threshold are round 18's, so is the trip's body (three tile
+//                       reads, 16 subtracts and 2 v_min3 per point pair); a trip now covers 4 V positions: per lane of four
+//                       points and 256 vertices 128 v_sub + 14 v_min3 + 2 v_min + 2 v_cmp + 1 = 147 instructions where round
+//                       18 takes 579 (V = 8: 291), 12 tile reads instead of 48.  An image never spans more than level 0v's
+//                       chunk.  Looser: an image is an interval pair around two centres, whatever lies inside; the hit is still
+//                       decided per block from the minimum over all its images, and a block spans 5e-4 of the axis against a
+//                       point's reach of 0.006-0.03 (the instructions outside the fold: profiles/r19a_vertex_octets.txt).
+//                       OA_SORTED_OCT_V=4 (build time): round 18's quads, bit for bit.
+//   level 0v (rare)    for a block some lane hit (OA_NN_VCHUNK=1): the same gap along v, a_j = fl32(hv - qv_j) against the same
 //                       thr1, from the ENDS of each chunk of 4 OA_SORTED_VCG vertices.  Positions 1 .. n-1 of a block are in the
 //                       order of qv (k_sort_blocks_v), and rounding is monotone, so a_j does not increase along a chunk: with F, L
 //                       its first and last, every |a_j| >= L when L > 0 and >= -F when F < 0.  max(L, -F) > thr1 (true; NaN:
@@ -1426,6 +1437,10 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_filt
 // Tiles are visited middle-out from the slab nearest to the workgroup's first point: an unseeded search (the first iteration of a
 // loop) then finds a tight best at once instead of sweeping towards it, and a seeded one tightens its seeds at once (the order
 // never changes an answer, only how soon the thresholds are final).
+#ifndef OA_SORTED_OCT_V
+#define OA_SORTED_OCT_V 16                // sorted positions per level-0 image of the <R = 2 / 4, TG, true> instances: 4 (round 18's quads,
+#endif                                    //  quad_image), 8 or 16 (round 19, group_image; a build-time knob for sweeps: 11.52 / 7.87 / 6.20 ms)
+static_assert(OA_SORTED_OCT_V == 4 || OA_SORTED_OCT_V == 8 || OA_SORTED_OCT_V == 16, "OA_SORTED_OCT_V: 4, 8 or 16 (an image never spans more than level 0v's chunk)");
 #if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
 __global__ void k_sort_keys_axis(const float *__restrict__ xyz, int nt, int axis, double lo, double scale, unsigned *__restrict__ keys)
 {
@@ -1486,9 +1501,36 @@ __global__ void k_pack_sorted(const float *__restrict__ xyz, int nt, int n_group
     pair_image(qu[0], id[0] >= 0, qu[1], id[1] >= 0, mw.x, mw.y);
     pair_image(qu[2], id[2] >= 0, qu[3], id[3] >= 0, mw.z, mw.w);
     tmw[g] = mw;
+    if constexpr (OA_SORTED_OCT_V == 4) {                        // (V = 8, 16: k_group_images writes toct, from tfs)
+        float mm, ww, ws;
+        quad_image(mw.x, mw.y, id[0] >= 0, mw.z, mw.w, id[2] >= 0, oct_c, mm, ww, ws);
+        float *oc = reinterpret_cast<float *>(toct + 3ll * (g >> 2)) + (g & 3);      // (n_groups_pad is a multiple of 4: whole chunks)
+        oc[0] = mm; oc[4] = ww; oc[8] = ws;
+    }
+}
+
+// toct (round 19, V = 8 or 16): level 0's image {mm, ww, ws} of every V consecutive positions of the FINAL order under the cap oct_c
+// (group_image, oa_octgap.hpp), from the qu k_pack_sorted left in tfs and the indices in tidx (a position is real when its index
+// is >= 0); three float4 per four images -- their four mm, their four ww, their four ws.  One thread per image, n_images =
+// 4 n_groups_pad / V (a multiple of 4: n_groups_pad is a multiple of 256).
+template <int V>
+__global__ void k_group_images(const float4 *__restrict__ tfs, const int4 *__restrict__ tidx, int n_images, float oct_c, float4 *__restrict__ toct)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_images) return;
+    float q[V];
+    int n_real = 0;
+#pragma unroll
+    for (int k = 0; k < V / 4; ++k) {
+        const long long g = (long long)i * (V / 4) + k;
+        const float4 Q = tfs[3ll * g];
+        const int4 J = tidx[g];
+        q[4 * k] = Q.x; q[4 * k + 1] = Q.y; q[4 * k + 2] = Q.z; q[4 * k + 3] = Q.w;
+        n_real += (J.x >= 0) + (J.y >= 0) + (J.z >= 0) + (J.w >= 0);     // (padding only ever follows the vertices)
+    }
     float mm, ww, ws;
-    quad_image(mw.x, mw.y, id[0] >= 0, mw.z, mw.w, id[2] >= 0, oct_c, mm, ww, ws);
-    float *oc = reinterpret_cast<float *>(toct + 3ll * (g >> 2)) + (g & 3);      // (n_groups_pad is a multiple of 4: whole chunks)
+    group_image<V>(q, n_real, oct_c, mm, ww, ws);
+    float *oc = reinterpret_cast<float *>(toct + 3ll * (i >> 2)) + (i & 3);
     oc[0] = mm; oc[4] = ww; oc[8] = ws;
 }
 #endif  // !OA_FAMILY_TU
@@ -1852,7 +1894,8 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
     // (round 18, R >= 2: the quad images instead, three float4 per chunk of 4 groups -- tmw then points at them, launch_brute_sorted)
     constexpr bool PAIRS = VCHUNK;
     constexpr bool OCT = PAIRS && sorted_oct(R);
-    constexpr int TW = OCT ? TG / 4 * 3 : TG;                       // float4 of level 0's tile
+    constexpr int OV = OA_SORTED_OCT_V;                             // positions per image (round 19: 16; 4 is round 18's quad)
+    constexpr int TW = OCT ? TG * 3 / OV : TG;                      // float4 of level 0's tile
     __shared__ float4 tilew[2][PAIRS ? TW : 1];
     __shared__ unsigned long long clk0[2];
     __shared__ int s_item[3];                                       // the workgroup's item {split, block}; [2]: the queues found empty so far
@@ -1954,9 +1997,9 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                                         : (((k) & 1) ? tile_s + (((k) + 1) >> 1) : tile_s - ((k) >> 1)))
 
     float4 stg0 = make_float4(0.f, 0.f, 0.f, 0.f), stg1 = stg0, stg2 = stg0, stgw = stg0;
-    const float4 *wsrc = tmw + (OCT ? g_begin / 4 * 3 : g_begin);   // (g_begin: a multiple of TG)
+    const float4 *wsrc = tmw + (OCT ? g_begin / OV * 3 : g_begin);  // (g_begin: a multiple of TG)
 #define OA_STGW_ON (PAIRS && (TW >= NN_THREADS || tid < TW))
-    static_assert(TW <= NN_THREADS && TG % 4 == 0, "k_nn_search_sorted: one float4 of level 0's images per thread and tile");
+    static_assert(TW <= NN_THREADS && TG % 16 == 0, "k_nn_search_sorted: one float4 of level 0's images per thread and tile");
 #define OA_STG_ON(k) (WHOLE || (k) * NN_THREADS + tid < TILE_F4)
 #define OA_STG_EACH(OP)                                       \
     do {                                                      \
@@ -2010,9 +2053,12 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                     // round 18, on QUADS of vertices (proof in oa_octgap.hpp): the signed t = |||mm - hm| - hw'| - ww| - ws never
                     // exceeds the smallest of the eight gaps by more than e and the pair's allowance, both inside qthr.  Per 16
                     // vertices and point pair 16 subtracts and 2 min3, from three tile reads instead of four
+                    // round 19: an image stands for OV = 16 (or 8) positions, so a trip of four images covers OV groups: GW / OV trips
+                    // per block where round 18 had GW / 4, the trip's body the same
+                    static_assert(GW % OV == 0, "k_nn_search_sorted: blocks of whole trips of four images");
 #pragma unroll
-                    for (int c = 0; c < GW / 4; ++c) {
-                        const float4 MM = tilew[cur][3 * (g / 4 + c)], WW = tilew[cur][3 * (g / 4 + c) + 1], WS = tilew[cur][3 * (g / 4 + c) + 2];
+                    for (int c = 0; c < GW / OV; ++c) {
+                        const float4 MM = tilew[cur][3 * (g / OV + c)], WW = tilew[cur][3 * (g / OV + c) + 1], WS = tilew[cur][3 * (g / OV + c) + 2];
 #pragma unroll
                         for (int p = 0; p < R / 2; ++p) {
                             const float a0 = oct_gap(MM.x, WW.x, WS.x, qhm[p], qhw[p]), a1 = oct_gap(MM.y, WW.y, WS.y, qhm[p], qhw[p]);

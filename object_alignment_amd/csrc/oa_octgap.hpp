@@ -46,11 +46,82 @@
 //     a skip is right.  A quad whose second pair is (vertex, padding) is an ordinary quad with Wb = 0.
 // (6) Where the bound is not claimed the set-up stores Q = +inf as before (oa_quadgap.hpp (6)): a point whose hu is not finite, a
 //     real slot of the source paired with a padding slot.  c = +inf (or a Hw that overflows) gives e = +inf and the same.
+//
+// Round 19: level 0 on GROUPS of V = 8 or 16 sorted positions (group_image<V> below; V = 4 is quad_image above, untouched).  The chain
+// of four subtractions, the point pair's {hm, hw' = max(Hw, c)}, e and the threshold are the same; only the image changes, and it is
+// defined by a property of the floats that are stored rather than by a formula:
+//     (P)  0 <= ww <= c,  ws >= 0,  and every real q_j of the group lies within ws of mm + ww or of mm - ww     (as real numbers,
+//          for the float32 mm, ww, ws as stored).
+// (1') Real numbers, A = hw' >= c >= ww = B.  Let q*, h be the vertex and the point of the smallest of the 2V gaps, T = |q* - h|.
+//     By (P) q* = mm + s1 ww + d with |d| <= ws, and h = Hm + s3 Hw.  With X = mm - Hm:  X - (s3 A - s1 B) = (q* - h) - d - s3 (A - Hw),
+//     so |X - (s3 A - s1 B)| <= T + ws + e, and D = |||X| - A| - B| is the distance from X to the nearest of {+-A +- B} ((1), which
+//     needs only A >= B >= 0):  D <= T + ws + e,  t = D - ws <= T + e.  ws stands where (1) has W(s1) + (WW - B).
+// (2') float32.  mm, ww, ws ARE the reals of (1'): (P) is a statement about the stored floats, so the terms |mm - MM|, |ww - B|,
+//     |ws - S| of (2) vanish.  What is left is |hm - Hm| and the four subtractions' own roundings, u (3 qmax + 4 hmax + 2 c) by (2)'s
+//     lines with |mm|, ww <= qmax (mm lies between the group's smallest and largest q, rounding being monotone; ww is half a
+//     distance of two such centres) -- inside oct_allowance = u (8 qmax + 5 hmax + 3 c) as it stands:
+//     k_sorted_point_setup and quad_threshold are unchanged, and (3) holds word for word.
+//     How group_image makes (P) true: mm and ww are rounded from double (any rounding is allowed: (P) is evaluated afterwards; ww <=
+//     c because rounding is monotone and c is a float), then for every real q_j the two distances |q_j - (mm -+ ww)| are evaluated
+//     in double FROM THE FLOATS mm, ww and bounded from above: s = fl64(mm + ww) is off by at most 2^-53 (|mm| + ww) (exact when ww =
+//     0), fl64(q_j - s) by 2^-53 relative, so  |q_j - (mm + ww)| <= fl64|q_j - s| (1 + 2^-51) + 2^-52 (|mm| + ww) [ww > 0]  with room
+//     for the roundings of that expression itself.  ws is the largest over j of the smaller of the two, rounded UP to float32.  A
+//     group of duplicates has mm = q, ww = 0 and every distance exactly 0: ws = 0.
+// (4') Flushed denormals: as (4); a flushed ws or ww moves t by less than 2^-126.
+// (5') Padding (only ever after the vertices).  Only real positions enter the centres and ws.  A group whose second half is all
+//     padding is the group of its first half, group_image<V / 2> (down to one vertex: {q, 0, 0}); a group of padding alone is
+//     {1e18, 0, 0} as (5).  1e18 never meets a vertex in one expression.
+// (6') Non-finite hu, a real slot beside a padding slot, c = +inf: Q = +inf from the set-up, as (6).  The target's q are finite
+//     (the images are only built for a finite target); a NaN q_j would drop out of every comparison here and can never win.
 #pragma once
 
 #include "oa_quadgap.hpp"
 
 namespace oa {
+
+// the smallest float32 >= v, for v >= 0 (or v = +inf)
+OA_PAIRGAP_FN float octgap_round_up(double v)
+{
+    float f = (float)v;
+    if ((double)f < v) {
+        unsigned b;
+        __builtin_memcpy(&b, &f, 4);
+        ++b;
+        __builtin_memcpy(&f, &b, 4);
+    }
+    return f;
+}
+
+// The image {mm, ww, ws} of V consecutive sorted positions with the centred float32 u q[0 .. V), the first n_real of them vertices,
+// under the cap c: property (P) of the header, (2').  mm and ww from the centres of the two halves (a half's centre: the midpoint
+// of its smallest and largest real q), ws from the stored mm and ww.
+template <int V>
+OA_PAIRGAP_FN void group_image(const float *q, int n_real, float c, float &mm, float &ww, float &ws)
+{
+    static_assert(V == 1 || V == 2 || V == 4 || V == 8 || V == 16, "group_image: halves of halves");
+    if (n_real <= 0) { mm = PAIR_PAD_U; ww = 0.0f; ws = 0.0f; return; }
+    if constexpr (V == 1) { mm = q[0]; ww = 0.0f; ws = 0.0f; return; }
+    else {
+        if (n_real <= V / 2) { group_image<V / 2>(q, n_real, c, mm, ww, ws); return; }
+        const int n = n_real < V ? n_real : V;
+        double lo_a = (double)q[0], hi_a = lo_a, lo_b = (double)q[V / 2], hi_b = lo_b;
+        for (int k = 1; k < V / 2; ++k) { const double v = (double)q[k]; lo_a = v < lo_a ? v : lo_a; hi_a = v > hi_a ? v : hi_a; }
+        for (int k = V / 2 + 1; k < n; ++k) { const double v = (double)q[k]; lo_b = v < lo_b ? v : lo_b; hi_b = v > hi_b ? v : hi_b; }
+        const double Ca = (lo_a + hi_a) / 2.0, Cb = (lo_b + hi_b) / 2.0;
+        const double WW = __builtin_fabs(Cb - Ca) / 2.0;
+        mm = (float)((Ca + Cb) / 2.0);
+        ww = (float)(WW < (double)c ? WW : (double)c);
+        const double sp = (double)mm + (double)ww, sm = (double)mm - (double)ww;
+        const double slack = ww > 0.0f ? 0x1p-52 * (__builtin_fabs((double)mm) + (double)ww) : 0.0;
+        double S = 0.0;
+        for (int k = 0; k < n; ++k) {
+            const double dp = __builtin_fabs((double)q[k] - sp), dm = __builtin_fabs((double)q[k] - sm);
+            const double d = (dp < dm ? dp : dm) * (1.0 + 0x1p-51) + slack;
+            S = d > S ? d : S;
+        }
+        ws = octgap_round_up(S);
+    }
+}
 
 // The image {mm, ww, ws} of a group's two vertex pairs {ma, wa}, {mb, wb} (pair_image's floats) under the cap c, formed in double
 // and rounded once.  real_a / real_b: the pair holds at least one vertex (padding only ever follows the vertices).

@@ -108,6 +108,8 @@ template <int MIX> __global__ __launch_bounds__(256) void mix(float *out, int tr
 // tile registers fed by broadcast ds_read_b128 from LDS -- the compiler's own schedule of the library's own functions:
 //   OCT 0 (round 13)  per 16 vertices 4 float4 of pair images, 2 x 24 subtracts + 2 x 4 min3 (oa_quadgap.hpp)       6 : 1, 16 tile registers
 //   OCT 1 (round 18)  per 16 vertices 3 float4 of quad images, 2 x 16 subtracts + 2 x 2 min3 (oa_octgap.hpp)        8 : 1, 12 tile registers
+//   OCT 2 (round 19)  V = 8: the same body per 32 vertices, 8 trips of the chunk loop per block                      16 : 1
+//   OCT 4 (round 19)  V = 16: the same body per 64 vertices, 4 trips                                                32 : 1
 // A trip is one block: 256 vertices x 4 points = 1024 (vertex, point) pairs per lane.
 template <int OCT> __global__ __launch_bounds__(256, 2) void fold(float *out, int trips, float seed)
 {
@@ -121,7 +123,7 @@ template <int OCT> __global__ __launch_bounds__(256, 2) void fold(float *out, in
         asm volatile("" : "+s"(cur));                          // (the tile anew every trip, as the kernel's)
         float qm[2], qodd[2];
 #pragma unroll
-        for (int c = 0; c < 16; ++c) {
+        for (int c = 0; c < (OCT >= 2 ? 16 / OCT : 16); ++c) {
             if (OCT) {
                 const float4 MM = tl[cur][3 * c], WW = tl[cur][3 * c + 1], WS = tl[cur][3 * c + 2];
 #pragma unroll
@@ -198,8 +200,18 @@ template <int OP> void run(const char *name, int per_step = 1)
     printf("%-34s %8.3f ms  %7.2f G wave-instr/s/SIMD  (%.3f ns per instr per SIMD)\n", name, ms, per_simd / ms / 1e6, ms * 1e6 / per_simd);
     (void)hipFree(d);
 }
-int main()
+static void fold_gate()
 {
+    // round 19 (profiles/r19a_vertex_octets.txt): the fold on images of 8 and 16 positions beside rounds 13 and 18, in one run
+    for (int rep = 0; rep < 2; ++rep)
+        for (int wps = 4; wps <= 8; wps += 4) {
+            run_fold<0>("fold, point pairs (6:1, LDS)", wps); run_fold<1>("fold, vertex quads V=4 (8:1, LDS)", wps);
+            run_fold<2>("fold, vertex octets V=8 (LDS)", wps); run_fold<4>("fold, groups of 16 V=16 (LDS)", wps);
+        }
+}
+int main(int argc, char **argv)
+{
+    if (argc > 1 && argv[1][0] == 'f') { fold_gate(); return 0; }      // "fold": the round-19 gate alone
     run<0>("v_add_f32 2src"); run<1>("v_fma_f32 3src"); run<17>("v_sub_f32"); run<6>("v_min_f32"); run<5>("v_min3_f32");
     run<2>("v_pk_fma_f16 3src"); run<7>("v_pk_fma_f16 (acc in src2)"); run<8>("v_pk_fma_f16 op_sel splat"); run<3>("v_pk_min_f16"); run<4>("v_pk_add_f16");
     run<12>("v_pk_mul_f16"); run<10>("v_pk_max_f16 neg (abs)"); run<9>("v_pk_min_i16"); run<14>("v_pk_min_u16"); run<11>("v_and_b32"); run<15>("v_min_u32"); run<16>("v_min_f16");
@@ -222,5 +234,6 @@ int main()
         run_fold<0>("fold, point pairs (6:1, LDS)", 4); run_fold<1>("fold, vertex quads (8:1, LDS)", 4);
         run_fold<0>("fold, point pairs (6:1, LDS)", 8); run_fold<1>("fold, vertex quads (8:1, LDS)", 8);
     }
+    fold_gate();
     return 0;
 }
