@@ -329,7 +329,7 @@ struct oa_target {
     // the same images in the order of the coordinate along the cloud's longest axis (k_nn_search_sorted, round 5)
     DevBuf<float4> d_tfs, d_tf3s, d_tgs;   // 3 / 2 / 3 float4 per group of 4 sorted positions
     DevBuf<float4> d_tmw;            // level 0's pair images, 1 float4 per group: {m, w} of positions (0, 1) and (2, 3) (oa_pairgap.hpp)
-    DevBuf<float4> d_toct;           // level 0's images of OA_SORTED_OCT_V positions each, 3 float4 per 4 images: their {mm}, {ww}, {ws} (oa_octgap.hpp)
+    DevBuf<float4> d_toct;           // level 0's images of SORTED_IMAGE_V positions each, 3 float4 per 4 images: their {mm}, {ww}, {ws} (oa_octgap.hpp)
     float oct_c = 0.0f;              // the cap d_toct was built with (0 while there are no images); k_sorted_point_setup gets it at launch
     DevBuf<int4> d_tidx;             // original index of every sorted position
     DevBuf<oa::half8> d_tfm;         // the MFMA experiment's image of the target
@@ -1277,7 +1277,7 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
         dispatch<4, 1, 2, 8>(c->src.R, [&](auto R) {
             hipLaunchKernelGGL((oa::k_sorted_point_setup<decltype(R)::value>), ob, dim3(64), 0, c->stream, (const oa::DevState *)c->d_state, (const float4 *)c->src.d_src4,
                                (const float4 *)c->src.d_win, (const unsigned long long *)c->src.d_keys, c->sax[0], c->sax[1], pass, c->tune.nn_wave_order ? 1 : 0, c->src.ns_pad, c->src.ns, c->src.d_prec,
-                               c->tgt.oct_c);                       // (the cap of the quad images this very search reads: oa_octgap.hpp)
+                               c->tgt.oct_c);                       // (the cap of the images this very search reads: oa_octgap.hpp)
         });
         HIPCHK(hipGetLastError());
     }
@@ -1290,9 +1290,9 @@ int launch_brute_sorted(oa_ctx *c, const dim3 grid)
     }
     if (queued) sgrid = dim3((unsigned)q_wgs);
     auto launch = [&](auto R, auto TG, auto VCHUNK) {
-        // level 0's own images: the quads' for the instances that fold them (round 18), else the pairs'
-        const bool oct = oa::sorted_oct(decltype(R)::value) && decltype(VCHUNK)::value;
-        const float4 *l0 = oct ? (const float4 *)c->tgt.d_toct : (const float4 *)c->tgt.d_tmw;
+        // level 0's own images: of 16 positions for the instances that fold them, else the pairs' (the per-vertex kind reads neither)
+        const bool images = oa::sorted_level0(decltype(R)::value, decltype(VCHUNK)::value) == oa::Level0::Images;
+        const float4 *l0 = images ? (const float4 *)c->tgt.d_toct : (const float4 *)c->tgt.d_tmw;
         hipLaunchKernelGGL((oa::k_nn_search_sorted<decltype(R)::value, decltype(TG)::value, decltype(VCHUNK)::value>), sgrid, dim3(oa::NN_THREADS), 0, c->stream,
                            c->d_state, (const float4 *)c->tgt.d_tgs, (const float4 *)c->tgt.d_tfs, (const float4 *)c->tgt.d_tf3s, (const int4 *)c->tgt.d_tidx,
                            c->tgt.n_groups_pad, c->src.d_keys, pass, (const float4 *)c->src.d_prec, q_splits, q_blocks, c->src.d_homes, queued ? c->src.d_qcnt : nullptr, c->tgt.nt, l0);
@@ -2756,24 +2756,21 @@ int build_sorted_images(oa_ctx *c)
     HIPCHK(dev_malloc(&c->tgt.d_tgs, sizeof(float4) * 3 * (size_t)c->tgt.n_groups_pad));
     HIPCHK(dev_malloc(&c->tgt.d_tidx, sizeof(int4) * (size_t)c->tgt.n_groups_pad));
     HIPCHK(dev_malloc(&c->tgt.d_tmw, sizeof(float4) * (size_t)c->tgt.n_groups_pad));
-    const int n_images = c->tgt.n_groups_pad / (OA_SORTED_OCT_V / 4);   // (n_groups_pad: a multiple of 256, whole images and whole fours of them)
+    // (every kind of level 0 gets its images -- tmw and toct: which a search reads follows from its source's R, oa::sorted_level0)
+    const int n_images = c->tgt.n_groups_pad / (oa::SORTED_IMAGE_V / 4);   // (n_groups_pad: a multiple of 256, whole images and whole fours of them)
     HIPCHK(dev_malloc(&c->tgt.d_toct, sizeof(float4) * 3 * (size_t)(n_images / 4)));
-    // level 0's cap (oa_octgap.hpp: any value >= 0 is valid, it only tunes what the quads' bound loses): the mean half-span in u
-    // of a block of 256 sorted vertices -- pairs of a quad further apart than that are the sparse regions' (OA_SORTED_OCT_CAP: a
-    // build-time factor for sweeps, oa_kernels.hpp)
+    // level 0's cap (oa_octgap.hpp: any value >= 0 is valid, it only tunes what the images' bound loses): the mean half-span in u
+    // of a block of 256 sorted vertices -- halves of an image further apart than that are the sparse regions'
     {
-        const double cap = ext * 128.0 / (double)c->tgt.nt * (double)(OA_SORTED_OCT_CAP);
+        const double cap = ext * 128.0 / (double)c->tgt.nt * oa::SORTED_OCT_CAP;
         c->tgt.oct_c = (cap >= 0.0 && cap < 1e18) ? (float)cap : 0.0f;
     }
     hipLaunchKernelGGL(oa::k_pack_sorted, dim3((unsigned)blocks), dim3(256), 0, c->stream, (const float *)c->tgt.d_tgt_xyz, c->tgt.nt, c->tgt.n_groups_pad,
-                       (const int *)v_out.p, c->tc[0], c->tc[1], c->tc[2], c->sax[0], c->sax[1], c->sax[2], c->tgt.d_tfs, c->tgt.d_tf3s, c->tgt.d_tgs, c->tgt.d_tidx, c->tgt.d_tmw,
-                       c->tgt.oct_c, c->tgt.d_toct);
+                       (const int *)v_out.p, c->tc[0], c->tc[1], c->tc[2], c->sax[0], c->sax[1], c->sax[2], c->tgt.d_tfs, c->tgt.d_tf3s, c->tgt.d_tgs, c->tgt.d_tidx, c->tgt.d_tmw);
     HIPCHK(hipGetLastError());
-    if constexpr (OA_SORTED_OCT_V != 4) {                         // round 19: the images of 8 (16) positions, from what k_pack_sorted has written
-        hipLaunchKernelGGL((oa::k_group_images<OA_SORTED_OCT_V>), dim3((unsigned)((n_images + 255) / 256)), dim3(256), 0, c->stream, (const float4 *)c->tgt.d_tfs,
-                           (const int4 *)c->tgt.d_tidx, n_images, c->tgt.oct_c, c->tgt.d_toct);
-        HIPCHK(hipGetLastError());
-    }
+    hipLaunchKernelGGL(oa::k_group_images, dim3((unsigned)((n_images + 255) / 256)), dim3(256), 0, c->stream, (const float4 *)c->tgt.d_tfs,
+                       (const int4 *)c->tgt.d_tidx, n_images, c->tgt.oct_c, c->tgt.d_toct);   // (from what k_pack_sorted has written)
+    HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));                      // (the temporaries are released on return)
     return OA_OK;
 }

@@ -24,6 +24,7 @@
 #include "oa_pairgap.hpp"
 #include "oa_quadgap.hpp"
 #include "oa_octgap.hpp"
+#include "oa_level0.hpp"
 
 namespace oa {
 
@@ -1352,95 +1353,76 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_filt
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_nn_search_sorted : k_nn_search_filtered with one more level in front (round 5) -- 1.84 VALU instructions per pair instead of 3.0
+// k_nn_search_sorted : k_nn_search_filtered with one more, cheaper level in front, over a target in sorted order
 // ------------------------------------------------------------------------------------------------
-// Still every (source, target) pair gets its own arithmetic; what changes is the ORDER of the target and a cheaper first test.
-//   The target's images are laid out in the order of the coordinate u along the cloud's longest axis (a 30-bit quantised key,
-//   stable sort; the order only matters for speed -- any permutation gives the same answers), so an LDS tile of 1024 vertices is
-//   a thin slab in u; the source points a wave owns are neighbours in space (Morton order).
-//   level 0 (hot loop)  the 1-D gap  a_j = |fl32(qu_j - hu)|:  ONE two-operand subtract + the min tree per pair (the |.| rides on
-//                       the min's source modifier).  With base the right-hand side of filter_thresholds (best inflated by every
-//                       rounding allowance of the 2-D / 3-D scores), a pair is a proven loser when its REAL gap t = |qu_j - hu|
-//                       has t^2 > base (the distance along one axis never exceeds the 3-D distance; no rounding at all on this
-//                       side of the inequality).  fl32(qu_j - hu) = (qu_j - hu)(1 + e), |e| <= 2^-24, so
-//                       a_j > T1 = round_up(sqrt(base) (1 + 2^-22))  =>  t >= a_j / (1 + 2^-24) > sqrt(base).
-//                       (Flushed denormals only ever make a_j smaller: fewer pairs skipped, never a wrong one.)
-//                       For all slabs but the few around the wave's own u range every pair fails here.
-//                       Round 11 (VCHUNK = true): level 0 on PAIRS of vertices.  For positions (4g, 4g+1) and (4g+2, 4g+3) of the
-//                       order the upload keeps the midpoint and half-width {m, w} of their u (tmw, k_pack_sorted), and
-//                           min(|q1 - hu|, |q2 - hu|) = | |M - hu| - W |                       (oa_pairgap.hpp)
-//                       is the smaller of the pair's two gaps in closed form: two subtractions per pair, as before, and a min tree
-//                       of half the leaves -- 63 v_min3_f32 per 256 vertices and point instead of 127, 1.25 instructions per pair
-//                       instead of 1.5.  Every vertex is still in an arithmetic test with every point; nothing is decided from a
-//                       block's bounds, and the vertex order still cannot change an answer.  In float32, a = fl(|fl(m - hu)| - w):
-//                           |a| <= (g + A)(1 + 2^-24),   A = 2^-24 (3 qmax + |hu|) >= 2^-24 (|M| + |m - hu| + W),
-//                       g the real smaller gap (proof: oa_pairgap.hpp).  With
-//                           T1 = round_up((sqrt(base) + A)(1 + 2^-22)),
-//                       |a| > T1  =>  (g + A)(1 + 2^-24) > (sqrt(base) + A)(1 + 2^-22)  =>  g > sqrt(base): both vertices of the
-//                       pair are proven losers.  A pair with padding has w = 0 and is the single gap of above.  The same T1 serves
-//                       level 0v and the VCHUNK = false instances (single gaps: they need no A, and a larger threshold only
-//                       prunes less).
-//                       Round 13 (VCHUNK = true, R >= 2): the same identity once more, on the lane's own points.  Points 2p and
-//                       2p + 1 of a lane have the midpoint hm and half-width hw along u (k_sorted_point_setup), and
-//                           t = | |m - hm| - hw | - w     (signed; three subtractions for four (vertex, point) pairs)
-//                       never exceeds the smallest of the four gaps by more than the pair's allowance (oa_quadgap.hpp, for either
-//                       order of hw and w): t > quad_threshold(thr1 of the two points, allowance) proves both vertices losers
-//                       for both points -- 384 v_sub + 63 v_min3 + v_min + v_cmp per point PAIR and 256 vertices, 0.88
-//                       instructions per pair where round 11 takes 1.25.  Still every vertex's and every point's own coordinate
-//                       in an arithmetic test, nothing from a block's bounds, any permutation of either side the same answers.
-//                       A pair that is not ruled out marks the block for both its points; level 0v and levels 1-3 then decide per
-//                       point, with their own thr1, as before.  OA_SORTED_QUAD=0 (build time): round 11's fold per point.
-//                       Round 18 (VCHUNK = true, R = 2 and 4; the R = 8 experiment stays on round 13's fold): a third nesting, on the two vertex pairs of a group.  The upload keeps
-//                       {mm, ww, ws} per group (toct, k_pack_sorted): the midpoint and half-distance of the pairs' midpoints, the
-//                       latter capped at c, and the wider pair's half-width plus what the cap cut off; the set-up keeps
-//                       hw' = max(hw, c) and adds e = hw' - hw to the pair's allowance.  ww <= c <= hw' whatever the widths, and
-//                           t = | | |mm - hm| - hw' | - ww | - ws     (signed; four subtractions for eight (vertex, point) pairs)
-//                       never exceeds the smallest of the eight gaps by more than e and the allowance (oa_octgap.hpp: the order
-//                       of the nesting is what makes it a bound, the cap is what makes the order true).  512 v_sub + 62 v_min3 +
-//                       2 v_min + 2 v_cmp per lane of four points and 256 vertices: 0.57 instructions per pair where round 13
-//                       takes 0.88, and three tile reads per 16 vertices instead of four.  Looser than round 13: the narrower
-//                       pair counts as wide as the wider, a quad whose pairs lie further apart than 2 c degrades towards an
-//                       interval, a lane whose points nearly share their u pays e <= c of reach (the instructions outside the fold: +0.7 % at 1M <-> 1M).
-//                       Still every quad and every point pair in its own arithmetic test, every tile visited, nothing decided
-//                       per block or tile.  OA_SORTED_OCT=0 (build time): round 13's fold.
-//                       Round 19 (the same instances): one image {mm, ww, ws} per V = OA_SORTED_OCT_V = 16 sorted positions instead of
-//                       per 4 (toct, k_group_images after k_pack_sorted): any three floats with 0 <= ww <= c and every vertex
-//                       of the group within ws of mm + ww or mm - ww, as stored (group_image, oa_octgap.hpp (1')-(6')).  The
-//                       chain, hw', e, the allowance and the threshold are round 18's, so is the trip's body (three tile
-//                       reads, 16 subtracts and 2 v_min3 per point pair); a trip now covers 4 V positions: per lane of four
-//                       points and 256 vertices 128 v_sub + 14 v_min3 + 2 v_min + 2 v_cmp + 1 = 147 instructions where round
-//                       18 takes 579 (V = 8: 291), 12 tile reads instead of 48.  An image never spans more than level 0v's
-//                       chunk.  Looser: an image is an interval pair around two centres, whatever lies inside; the hit is still
-//                       decided per block from the minimum over all its images, and a block spans 5e-4 of the axis against a
-//                       point's reach of 0.006-0.03 (the instructions outside the fold: profiles/r19a_vertex_octets.txt).
-//                       OA_SORTED_OCT_V=4 (build time): round 18's quads, bit for bit.
-//   level 0v (rare)    for a block some lane hit (OA_NN_VCHUNK=1): the same gap along v, a_j = fl32(hv - qv_j) against the same
-//                       thr1, from the ENDS of each chunk of 4 OA_SORTED_VCG vertices.  Positions 1 .. n-1 of a block are in the
-//                       order of qv (k_sort_blocks_v), and rounding is monotone, so a_j does not increase along a chunk: with F, L
-//                       its first and last, every |a_j| >= L when L > 0 and >= -F when F < 0.  max(L, -F) > thr1 (true; NaN:
-//                       false) therefore proves min |a_j| > thr1 -- what level 0's proof needs -- and the chunk is ruled out; a
-//                       chunk with F >= 0 >= L passes.  Every chunk the round-7 fold over all its a_j kept is kept (a superset:
-//                       a chunk whose interior straddles hv with no vertex near it passes in vain).  Position 0 of a block is
+// Every (source, target) pair still gets its own arithmetic; what differs is the ORDER of the target and the first test.  (How the
+// kernel came to this form, round by round and with each step's numbers: docs/HISTORY.md and DESIGN.md section 3.1.)
+// The target's images lie in the order of the coordinate u along the cloud's longest axis (a 30-bit quantised key, stable sort; the
+// order only matters for speed -- any permutation gives the same answers), so an LDS tile of 1024 vertices is a thin slab in u; the
+// source points a wave owns are neighbours in space (Morton order).  Within every block of 256 positions, positions 1 .. n-1 are in
+// the order of the second coordinate v (k_sort_blocks_v, OA_NN_VCHUNK=1).
+//   level 0 (hot loop)  the 1-D gap along u of a point -- or a pair of the lane's points -- and a vertex or an image of several,
+//                       folded over a block of 256 vertices into one minimum and ONE compare (oa_level0.hpp).  With base the
+//                       right-hand side of filter_thresholds (best inflated by every rounding allowance of the 2-D / 3-D scores),
+//                       a vertex is a proven loser when its REAL gap t = |qu - hu| has t^2 > base (the distance along one axis
+//                       never exceeds the 3-D distance).  Every kind computes in float32 a value that exceeds the smallest real
+//                       gap it stands for by no more than a stated allowance, and thr1 (sorted_thresholds) carries that
+//                       allowance: value > threshold proves every vertex behind it a loser.  (Flushed denormals only make a gap
+//                       smaller: fewer pairs skipped, never a wrong one.)  For all slabs but the few around the wave's own u
+//                       range every block fails here.  The four kinds (sorted_level0 below says which instance runs which):
+//     per vertex          a = |fl(qu - hu)| against thr1, from the tfs tile itself: fl(qu - hu) = (qu - hu)(1 + e), |e| <= 2^-24,
+//                         and thr1 >= round_up(sqrt(base)(1 + 2^-22)).  One subtract and half a v_min3_f32 per pair.
+//     vertex pairs        positions (4g, 4g+1) and (4g+2, 4g+3) as midpoint and half-width {m, w} of their u (tmw, k_pack_sorted):
+//                         min(|q1 - hu|, |q2 - hu|) = ||m - hu| - w| in closed form; in float32 within A = 2^-24 (3 qmax + |hu|) of
+//                         it, and thr1 = round_up((sqrt(base) + A)(1 + 2^-22)).  A pair with padding has w = 0: a single gap.
+//                         1.25 instructions per pair.  Proof: oa_pairgap.hpp.
+//     ... x point pairs   the same identity once more on the lane's points 2p, 2p + 1 ({hm, hw} and an allowance per pair,
+//                         k_sorted_point_setup): the signed t = ||m - hm| - hw| - w never exceeds the smallest of the four gaps
+//                         by more than the allowance, so t > quad_threshold(the two thr1, allowance) rules out both vertices for
+//                         both points.  0.88 instructions per pair.  Proof: oa_quadgap.hpp.
+//     images x point pairs  one image {mm, ww, ws} per SORTED_IMAGE_V = 16 sorted positions (toct, k_group_images): 0 <= ww <= c
+//                         and every vertex of the group within ws of mm + ww or mm - ww, as stored; the set-up keeps hw' =
+//                         max(hw, c) and adds e = hw' - hw to the pair's allowance.  The signed t = |||mm - hm| - hw'| - ww| - ws
+//                         never exceeds the smallest of the 32 gaps by more than e and the allowance.  Four subtracts per 32
+//                         pairs, a v_min3_f32 per 64: 0.14 instructions per pair.  An image never spans more than level 0v's
+//                         chunk.  Proof: oa_octgap.hpp, (1')-(6').
+//                       The point-pair kinds mark a hit block for BOTH points of a pair; levels 0v-3 decide per point with their own
+//                       thr1.  In every kind each vertex's and each point's own coordinate is in an arithmetic test, every tile is
+//                       visited, nothing is decided from a block's or a tile's bounds.
+//   level 0v (rare)     for a block some lane hit (VCHUNK): the same gap along v, a_j = fl32(hv - qv_j) against the same thr1, from
+//                       the ENDS of each chunk of 4 SORTED_VCG vertices.  Positions 1 .. n-1 of a block are in the order of qv, and
+//                       rounding is monotone, so a_j does not increase along a chunk: with F, L its first and last, every
+//                       |a_j| >= L when L > 0 and >= -F when F < 0.  max(L, -F) > thr1 (true; NaN: false) therefore proves
+//                       min |a_j| > thr1 -- what level 0's proof needs -- and the chunk is ruled out; a chunk with F >= 0 >= L
+//                       passes (one whose interior straddles hv with no vertex near it passes in vain).  Position 0 of a block is
 //                       not in that order and is tested on its own; a block with padding is not tested (its chunks that hold a
-//                       vertex pass); thr1 = +inf (unseeded) passes every chunk.  (A NaN v sorts to a block's ends; such a
-//                       vertex never wins, and max() of a NaN and a number is the number, which bounds the rest alone.)
+//                       vertex pass); thr1 = +inf (unseeded) passes every chunk.  (A NaN v sorts to a block's ends; such a vertex
+//                       never wins, and max() of a NaN and a number is the number, which bounds the rest alone.)
 //   levels 1, 2, 3      as k_nn_search_filtered (2-D score, 3-D score, exact metric), reached by ~6 % of the blocks at 1M <-> 1M.
-//                       Round 17 (VCHUNK = true): level 1 per CHUNK of level 0v, not per group -- the chunk's 12 tile reads issued
-//                       together, its 16 scores and four group minima in one straight line, one test of their minimum and one
-//                       branch per chunk; a chunk some lane still wants is then walked group by group in the order of before, a
-//                       lane entering level 2 where the group's stored minimum is not above its thr2 as it stands then
-//                       (sorted_level1_min / sorted_finish_level2; the same groups reach level 2 as before, so the thresholds
-//                       fall as before).  Per-workgroup stamps: 14.8 % of all wave time was this path, 16 700 cycles per hit block;
-//                       15 000 since, and the seeded launch 16.19 -> 15.64 ms (profiles/r17a_hit_path.txt).
+//                       VCHUNK: level 1 per chunk of level 0v, then levels 2-3 group by group; else group by group for the whole
+//                       block.
 // Indices: position j of the sorted images holds original vertex tidx[j]; the exact path compares and reports ORIGINAL indices
 // (lowest index on ties, as everywhere).  A split owns a seed when seed index mod splits = split (no position lookup).
 // Tiles are visited middle-out from the slab nearest to the workgroup's first point: an unseeded search (the first iteration of a
 // loop) then finds a tight best at once instead of sweeping towards it, and a seeded one tightens its seeds at once (the order
 // never changes an answer, only how soon the thresholds are final).
-#ifndef OA_SORTED_OCT_V
-#define OA_SORTED_OCT_V 16                // sorted positions per level-0 image of the <R = 2 / 4, TG, true> instances: 4 (round 18's quads,
-#endif                                    //  quad_image), 8 or 16 (round 19, group_image; a build-time knob for sweeps: 11.52 / 7.87 / 6.20 ms)
-static_assert(OA_SORTED_OCT_V == 4 || OA_SORTED_OCT_V == 8 || OA_SORTED_OCT_V == 16, "OA_SORTED_OCT_V: 4, 8 or 16 (an image never spans more than level 0v's chunk)");
+
+// The kinds of level 0, and THE decision which instance folds which -- asked by the kernel (its fold, its tile of images), by
+// k_sorted_point_setup (whether a point pair's record is capped) and by the launcher (which array of images to pass); the upload
+// builds every kind's images, since a target does not know its sources' R.  R = 8 exists in the experiments library only.
+enum class Level0 { PerVertex, VertexPairs, PointPairs, Images };
+constexpr Level0 sorted_level0(int R, bool VCHUNK)
+{
+    return !VCHUNK ? Level0::PerVertex : R == 1 ? Level0::VertexPairs : R <= 4 ? Level0::Images : Level0::PointPairs;
+}
+constexpr bool level0_on_point_pairs(Level0 k) { return k == Level0::PointPairs || k == Level0::Images; }
+constexpr int SORTED_IMAGE_V = 16;        // sorted positions per image (4 / 8 / 16: 11.52 / 7.87 / 6.20 ms per step, profiles/r19a_vertex_octets.txt)
+constexpr int SORTED_GW = 64;             // groups of 4 sorted vertices per block, level 0's skip test (the sweep: at the kernel)
+constexpr int SORTED_VCG = 4;             // groups per chunk of level 0v (2 / 4 / 8: 25.46 / 24.99 / 24.94 ms at 1M <-> 1M, profiles/r08a_vends.txt)
+constexpr double SORTED_OCT_CAP = 1.0;    // the images' cap c in mean half-spans of a block (any value >= 0 gives the same answers; sweep: profiles/r18a_vertex_quads.txt)
+// float4 of level 0's own images per tile of TG groups (none: the per-vertex kind reads the tfs tile)
+constexpr int level0_tile_f4(Level0 k, int TG) { return k == Level0::PerVertex ? 0 : k == Level0::Images ? TG * 3 / SORTED_IMAGE_V : TG; }
+static_assert(4 * SORTED_VCG % SORTED_IMAGE_V == 0, "an image never spans more than level 0v's chunk");
 #if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
 __global__ void k_sort_keys_axis(const float *__restrict__ xyz, int nt, int axis, double lo, double scale, unsigned *__restrict__ keys)
 {
@@ -1453,13 +1435,11 @@ __global__ void k_sort_keys_axis(const float *__restrict__ xyz, int nt, int axis
 
 // images in sorted order, per group of 4 positions: tfs [qu][-2qv][qu^2+qv^2] (LDS tiles; -2qu is exact from qu), tf3s [-2qd][|q|^2],
 // tgs [x][y][z] (exact), tidx original indices.  Same centring and roundings as k_pack_filter / k_pack_target.
-// tmw (round 11): level 0's pair images {m01, w01, m23, w23} of the group's positions (0, 1) and (2, 3), from the same qu
-// (pair_image, oa_pairgap.hpp) -- positions of the FINAL order, k_sort_blocks_v's included.
-// toct (round 18): level 0's quad images {mm, ww, ws} of the group's two pairs under the cap oct_c (quad_image, oa_octgap.hpp), from
-// the same pair images; three float4 per chunk of 4 groups -- the chunk's four mm, its four ww, its four ws.
+// tmw: level 0's pair images {m01, w01, m23, w23} of the group's positions (0, 1) and (2, 3), from the same qu
+// (pair_image, oa_pairgap.hpp) -- positions of the FINAL order, k_sort_blocks_v's included.  (toct: k_group_images, below.)
 __global__ void k_pack_sorted(const float *__restrict__ xyz, int nt, int n_groups_pad, const int *__restrict__ order, float cx, float cy,
                               float cz, int au, int av, int ad, float4 *__restrict__ tfs, float4 *__restrict__ tf3s,
-                              float4 *__restrict__ tgs, int4 *__restrict__ tidx, float4 *__restrict__ tmw, float oct_c, float4 *__restrict__ toct)
+                              float4 *__restrict__ tgs, int4 *__restrict__ tidx, float4 *__restrict__ tmw)
 {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_groups_pad) return;
@@ -1501,21 +1481,15 @@ __global__ void k_pack_sorted(const float *__restrict__ xyz, int nt, int n_group
     pair_image(qu[0], id[0] >= 0, qu[1], id[1] >= 0, mw.x, mw.y);
     pair_image(qu[2], id[2] >= 0, qu[3], id[3] >= 0, mw.z, mw.w);
     tmw[g] = mw;
-    if constexpr (OA_SORTED_OCT_V == 4) {                        // (V = 8, 16: k_group_images writes toct, from tfs)
-        float mm, ww, ws;
-        quad_image(mw.x, mw.y, id[0] >= 0, mw.z, mw.w, id[2] >= 0, oct_c, mm, ww, ws);
-        float *oc = reinterpret_cast<float *>(toct + 3ll * (g >> 2)) + (g & 3);      // (n_groups_pad is a multiple of 4: whole chunks)
-        oc[0] = mm; oc[4] = ww; oc[8] = ws;
-    }
 }
 
-// toct (round 19, V = 8 or 16): level 0's image {mm, ww, ws} of every V consecutive positions of the FINAL order under the cap oct_c
+// toct: level 0's image {mm, ww, ws} of every V = SORTED_IMAGE_V consecutive positions of the FINAL order under the cap oct_c
 // (group_image, oa_octgap.hpp), from the qu k_pack_sorted left in tfs and the indices in tidx (a position is real when its index
 // is >= 0); three float4 per four images -- their four mm, their four ww, their four ws.  One thread per image, n_images =
 // 4 n_groups_pad / V (a multiple of 4: n_groups_pad is a multiple of 256).
-template <int V>
 __global__ void k_group_images(const float4 *__restrict__ tfs, const int4 *__restrict__ tidx, int n_images, float oct_c, float4 *__restrict__ toct)
 {
+    constexpr int V = SORTED_IMAGE_V;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_images) return;
     float q[V];
@@ -1610,29 +1584,16 @@ __device__ __forceinline__ bool sorted_finish_group(const float4 AU, const float
     return sorted_finish_level2(AU, AV, group, tf3s, tgs, tidx, pco, hu, hv, hd, qmax, best, bidx, thr1, thr2);
 }
 
-#ifndef OA_SORTED_QUAD
-#define OA_SORTED_QUAD 1                  // 1: level 0 of the <R >= 2, TG, true> instances on pairs of the lane's points (round 13,
-#endif                                    //  oa_quadgap.hpp); 0: round 11's per-point fold alone (a build-time knob for sweeps)
-#ifndef OA_SORTED_OCT
-#define OA_SORTED_OCT 1                   // 1: ... and on quads of vertices, 4 subtracts per 8 gaps (round 18, oa_octgap.hpp);
-#endif                                    //  0: round 13's fold on pairs of vertices (a build-time knob for sweeps)
-#ifndef OA_SORTED_OCT_CAP
-#define OA_SORTED_OCT_CAP 1.0             // the quads' cap in mean half-spans of a block of 256 sorted vertices (build_sorted_images;
-#endif                                    //  any value >= 0 gives the same answers: profiles/r18a_vertex_quads.txt has the sweep)
-// which instances fold quads: R = 2 and 4 (the R = 8 experiment instances stay on round 13's fold); asked by the set-up, the kernel
-// and the launcher alike, so that they agree
-constexpr bool sorted_oct(int R) { return OA_SORTED_QUAD && OA_SORTED_OCT && R >= 2 && R <= 4; }
-
 // Everything k_nn_search_sorted needs to know about a point that does not depend on the split, once per search instead of once
 // per (split, block) item -- 136 times per point in a seeded 1M <-> 1M launch: co_find, the centred coordinates, the seed and
 // its distance, the thresholds.  One RECORD per slot, three float4 in three arrays of ns_pad entries (rec, rec + ns_pad,
 // rec + 2 ns_pad):
 //   [0] hu, hv, hd, the slot's index (int bits)     [1] best, bidx (uint bits), thr1, thr2     [2] px, py, pz (co_find), 0
-// and (R >= 2, round 13) a fourth array, rec + 3 ns_pad: per lane and pair of its points (2p, 2p + 1), at first + 64 p + lane of the
-// wave's records, {hm, hw, allowance, 0} -- the pair's image along u and what rounding can add to its gap (oa_quadgap.hpp);
-// since round 18 (R = 2, 4) {hm, max(hw, c), allowance + e, 0} with the cap c = oct_c the target's quad images were built with
-// (oa_octgap.hpp) -- a launch argument, read from the target beside its images: the bound needs the SAME c on both sides, and the
-// images may be built while a sequence is open (oa_set_search_mode), after the device state was staged.
+// and, where level 0 folds point pairs (sorted_level0), a fourth array, rec + 3 ns_pad: per lane and pair of its points (2p, 2p + 1),
+// at first + 64 p + lane of the wave's records, {hm, hw, allowance, 0} -- the pair's image along u and what rounding can add to its
+// gap (oa_quadgap.hpp); for the image kind {hm, max(hw, c), allowance + e, 0} with the cap c = oct_c the target's images were built
+// with (oa_octgap.hpp) -- a launch argument, read from the target beside its images: the bound needs the SAME c on both sides, and
+// the images may be built while a sequence is open (oa_set_search_mode), after the device state was staged.
 // The seed is the slot's winner record (pass 0) or what k_nn_seed_sorted left in keys (pass 2: this kernel runs after it).
 // The arithmetic is the item prologue's of before, through the same device functions: the same floats.
 // WHERE a slot's record lies decides which lane takes it as its point r: record first + 64 r + lane of a wave's 64 R records
@@ -1653,7 +1614,8 @@ __global__ __launch_bounds__(64) void k_sorted_point_setup(const DevState *__res
     if (st->halt) return;
     constexpr int N = 64 * R;
     __shared__ uint32_t key[N];
-    __shared__ float pu[R >= 2 ? N : 1];                           // round 13: the records' hu in the order the lanes read them
+    constexpr Level0 L0 = sorted_level0(R, true);                  // (the pairs' records are read by the VCHUNK instances alone)
+    __shared__ float pu[level0_on_point_pairs(L0) ? N : 1];        // the records' hu in the order the lanes read them
     const int t = threadIdx.x;
     const int first = (int)blockIdx.x * N;
     const double qmax = st->qmax;
@@ -1711,8 +1673,8 @@ __global__ __launch_bounds__(64) void k_sorted_point_setup(const DevState *__res
         rec[ns_pad + first + rank[r]] = rb[r];
         rec[2 * ns_pad + first + rank[r]] = rc[r];
     }
-    if constexpr (R >= 2) {
-        // round 13: the lane's point pairs (2p, 2p + 1) -- {hm, hw, allowance, 0} in record first + 64 p + lane of a fourth array
+    if constexpr (level0_on_point_pairs(L0)) {
+        // the lane's point pairs (2p, 2p + 1) -- {hm, hw, allowance, 0} in record first + 64 p + lane of a fourth array
         // -- formed from the records the search's lane will hold, first + 64 r + lane, so after the ranking.  A pair without a
         // claim (oa_quadgap.hpp, (6): a hu that is not finite; a padding slot of the source beside a real one) gets the
         // allowance +inf: its threshold is +inf whatever its points' thr1 become
@@ -1727,8 +1689,8 @@ __global__ __launch_bounds__(64) void k_sorted_point_setup(const DevState *__res
             const float h1 = pu[128 * p + t], h2 = pu[128 * p + 64 + t];
             const bool claim = (h1 - h1 == 0.0f) && (h2 - h2 == 0.0f) && key[128 * p + t] == key[128 * p + 64 + t];
             float hm, hw;
-            if constexpr (sorted_oct(R)) {
-                // round 18: {hm, hw' = max(hw, c), allowance + e, 0} -- the half-width under the target's cap and what the cap adds
+            if constexpr (L0 == Level0::Images) {
+                // {hm, hw' = max(hw, c), allowance + e, 0} -- the half-width under the target's cap and what the cap adds
                 // to the pair's reach, in the allowance's place (oa_octgap.hpp (2), (3)): quad_threshold is fed as before
                 double e;
                 const float c = oct_c;
@@ -1823,16 +1785,6 @@ __global__ void k_sorted_block_homes(const DevState *__restrict__ st, const floa
 }
 #endif  // !OA_FAMILY_TU
 
-#ifndef OA_SORTED_GW
-#define OA_SORTED_GW 64                   // groups of 4 sorted vertices per skip test of k_nn_search_sorted (a build-time knob for sweeps)
-#endif
-#ifndef OA_SORTED_VCG
-#define OA_SORTED_VCG 4                   // groups of 4 sorted vertices per chunk of level 0v (a build-time knob for sweeps;
-#endif                                    //  2 / 4 / 8: 25.46 / 24.99 / 24.94 ms at 1M <-> 1M, profiles/r08a_vends.txt)
-#ifndef OA_SORTED_VREFINE
-#define OA_SORTED_VREFINE 0               // 1: level 0v's end test again per group of a passing chunk, ahead of level 1 (25.11 ms)
-#endif
-
 // Blocks of the sorted images in the order of v (round 7, OA_NN_VCHUNK=1): the positions of every SORTED_VBLOCK consecutive
 // vertices -- the block level 0 tests in the smallest tile (64 groups) -- ordered by the centred float32 coordinate along the
 // second axis v (ties: the u position), so that level 0v (k_nn_search_sorted) finds a point's few vertices near it in v in a few
@@ -1841,7 +1793,7 @@ __global__ void k_sorted_block_homes(const DevState *__restrict__ st, const floa
 // point's home tile read (tfs[3 TG t].x: k_sorted_block_homes, k_nn_seed_sorted).  Padding
 // (positions >= nt) is only ever at the tail of the last block and stays there.  One workgroup per block, a rank sort in LDS;
 // at upload only.
-constexpr int SORTED_VBLOCK = 4 * (OA_SORTED_GW < 64 ? OA_SORTED_GW : 64);
+constexpr int SORTED_VBLOCK = 4 * (SORTED_GW < 64 ? SORTED_GW : 64);
 #if !defined(OA_FAMILY_TU)      // plain kernels are compiled once, in the host translation unit (oa_icp.hip)
 __global__ __launch_bounds__(SORTED_VBLOCK) void k_sort_blocks_v(const float *__restrict__ xyz, int nt, int av, float cv,
                                                                  int *__restrict__ order)
@@ -1869,6 +1821,127 @@ __global__ __launch_bounds__(SORTED_VBLOCK) void k_sort_blocks_v(const float *__
 }
 #endif  // !OA_FAMILY_TU
 
+// ---- the stages of k_nn_search_sorted that stand on their own, in the order the kernel calls them; level 0's folds: oa_level0.hpp.
+// (The compiler optimises a function before it inlines it, so a stage moved out of the kernel is not compiled as it was inside:
+//  loading the points, the per-vertex fold and levels 1-3 for a chunk stay written out in the body, each with what moving it cost;
+//  profiles/r20a_sorted_stages.txt.) ---------------------------------------------------------------------------------------------
+
+// Taking an item off the work queue (above): false when every queue is dry, else the item in {split, yblk}.  For the whole
+// workgroup (it holds a barrier); thread 0 pops, s_item carries the item and, in [2], the queues found dry so far.
+__device__ __forceinline__ bool sorted_take_item(int tid, int *qcnt, const int *__restrict__ homes, int n_splits, int n_blocks, int *s_item,
+                                                 int &split, int &yblk)
+{
+    if (tid == 0) {
+        // SORTED_QUEUES queues when they divide the splits (else one): queue q holds the splits s = q + nq j; item p of a queue
+        // is block p / per_q at rank p mod per_q, rank k being the split k steps (0, +1, -1, +2, ...) from the block's own
+        const int nq = (n_splits % SORTED_QUEUES == 0) ? SORTED_QUEUES : 1, per_q = n_splits / nq;
+        const int q_len = per_q * n_blocks;
+        unsigned xcc = 0;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        int got = -1, got_y = 0;
+        unsigned q_dry = (unsigned)s_item[2];
+        for (int a = 0; a < nq && got < 0; ++a) {
+            const int q = (int)((xcc + (unsigned)a) & (unsigned)(nq - 1));
+            if (q_dry & (1u << q)) continue;
+            const int pos = atomicAdd(qcnt + q * SORTED_QUEUE_STRIDE, 1);
+            if (pos >= q_len) { q_dry |= 1u << q; continue; }
+            got_y = pos / per_q;
+            const int k = pos - got_y * per_q;
+            int j0 = (homes[2 * got_y] - q + nq / 2) / nq;          // the queue's split nearest to the block's own
+            j0 = j0 < 0 ? 0 : (j0 >= per_q ? per_q - 1 : j0);
+            int j = (j0 + ((k & 1) ? (k + 1) / 2 : -(k / 2))) % per_q;
+            if (j < 0) j += per_q;
+            got = q + nq * j;
+        }
+        s_item[0] = got; s_item[1] = got_y; s_item[2] = (int)q_dry;
+    }
+    __syncthreads();
+    split = __builtin_amdgcn_readfirstlane(s_item[0]); yblk = __builtin_amdgcn_readfirstlane(s_item[1]);   // (scalar registers, as blockIdx was)
+    return split >= 0;                                              // (the whole workgroup: nothing left anywhere)
+}
+
+// Level 0v for ONE point and one block of GW groups (blk: its first group in the tfs tile): cm, the chunks of CG groups that
+// can hold a vertex within thr1 of the point along v for this lane, from each chunk's two ends; todo, the wave's union.  2 fma, a
+// max and a compare per chunk.  a_j = fma(0.5, -2qv_j, hv): the halving is exact, the one rounding is the subtraction's.  thr1
+// only falls while levels 1-3 run, so a mask taken before them stays conservative.  n_in: the block's positions that hold a
+// vertex; a block with padding at its tail (AV = 0 breaks the order) is not tested -- its chunks that hold a vertex pass.
+template <int GW, int CG, typename cmask_t>
+__device__ __forceinline__ void sorted_chunk_masks(const float4 *blk, int n_in, bool hit, float hv, float thr1, cmask_t &cm, cmask_t &todo)
+{
+    constexpr int NC = GW / CG;
+    cm = 0; todo = 0;
+    if (n_in >= 4 * GW) {
+        // chunk c passes for this lane when the lane has this point in the block and the ends do not rule it out
+        // (& rather than &&: no branch per chunk)
+#define OA_VCHUNK_PASS(c, out)                                                                                                      \
+        do {                                                                                                                        \
+            const bool p_ = hit & !(out);                                                                                          \
+            cm |= (cmask_t)p_ << (c);                                                                                              \
+            if (__builtin_amdgcn_ballot_w64(p_)) todo |= (cmask_t)1 << (c);                                                         \
+        } while (0)
+        {                                                          // chunk 0: the block's position 0 on its own
+            const float4 A0 = blk[1], A1 = blk[3 * (CG - 1) + 1];
+            const float F = __builtin_fmaf(0.5f, A0.y, hv), L = __builtin_fmaf(0.5f, A1.w, hv);
+            OA_VCHUNK_PASS(0, (__builtin_fmaxf(L, -F) > thr1) & (__builtin_fabsf(__builtin_fmaf(0.5f, A0.x, hv)) > thr1));
+        }
+#pragma unroll 5
+        for (int c = 1; c < NC; ++c) {
+            const float4 A0 = blk[3 * (CG * c) + 1], A1 = blk[3 * (CG * c + CG - 1) + 1];
+            const float L = __builtin_fmaf(0.5f, A1.w, hv);
+            if ((4 * GW > SORTED_VBLOCK) && (4 * CG * c) % SORTED_VBLOCK == 0) {   // (blocks of more than one: their 0s)
+                const float F = __builtin_fmaf(0.5f, A0.y, hv);
+                OA_VCHUNK_PASS(c, (__builtin_fmaxf(L, -F) > thr1) & (__builtin_fabsf(__builtin_fmaf(0.5f, A0.x, hv)) > thr1));
+            } else {
+                const float F = __builtin_fmaf(0.5f, A0.x, hv);
+                OA_VCHUNK_PASS(c, __builtin_fmaxf(L, -F) > thr1);
+            }
+        }
+#undef OA_VCHUNK_PASS
+    } else {
+#pragma unroll 1
+        for (int c = 0; c < NC && 4 * CG * c < n_in; ++c) {
+            cm |= (cmask_t)hit << c;
+            todo |= (cmask_t)1 << c;
+        }
+    }
+}
+
+// The report: the item's bests into keys.  A split reports when it has something to say (k_nn_search_filtered); the seed's
+// owner: seed index mod splits.  (The slot's index and the seed again from the record, instead of three registers per point
+// held through the scan: the laundered index makes these loads new ones the compiler cannot merge with the prologue's, and
+// that reload is what keeps the kernel at 0 B of scratch.)
+template <int R>
+__device__ __forceinline__ void sorted_report(const float4 *__restrict__ rec, int rec0, int ns_pad, unsigned long long *keys, int pass, int n_splits,
+                                              int split, const float (&best)[R], const uint32_t (&bidx)[R])
+{
+    int rec1 = rec0;
+    asm volatile("" : "+v"(rec1));
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const unsigned long long key = ((unsigned long long)__float_as_uint(best[r]) << 32) | bidx[r];
+        unsigned long long *dst = keys + __float_as_int(rec[rec1 + 64 * r].w);
+        if (pass != 0) {                                           // merges into whatever keys holds: monotone
+            if (key < __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(dst, key);
+        } else if (n_splits == 1) *dst = key;
+        else {
+            const float4 rb = rec[ns_pad + rec1 + 64 * r];
+            const float seed_d = rb.x;
+            const uint32_t seed_idx = __float_as_uint(rb.y);
+            const bool seeded = seed_idx != IDX_NONE;
+            const bool improved = bidx[r] != seed_idx || best[r] != seed_d;
+            const bool owner = seeded && (int)(seed_idx % (uint32_t)n_splits) == split;
+            if (!seeded || improved || owner) atomicMin(dst, key);
+        }
+    }
+}
+
+// The kernel: per item (split, block of NN_THREADS x R source points) a scan of the split's tiles, double-buffered in LDS; per
+// tile and block of GW groups level 0 for all the lane's points, and for a block some lane hit, point by point, level 0v and
+// levels 1-3 (VCHUNK) or levels 1-3 for every group (not VCHUNK).  l0img: level 0's own images -- tmw or toct, as
+// sorted_level0 says (launch_brute_sorted); not read by the per-vertex kind.
+// pass 0: seeds from the winner records of the last accumulation (none on the first search of a loop: every split then has to
+// find a best of its own before it can skip anything).  pass 2: seeds from keys, where k_nn_seed_sorted has left every point's
+// nearest vertex within its own slab -- a distance really achieved, usually a few times the true one: enough for level 0.
 template <int R, int TG = FTILE_GROUPS, bool VCHUNK = true>
 __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sorted(const DevState *__restrict__ st,
                                                                  const float4 *__restrict__ tgs,
@@ -1879,24 +1952,31 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                                                                  unsigned long long *keys, int pass,
                                                                  const float4 *__restrict__ rec,
                                                                  int n_splits, int n_blocks, const int *__restrict__ homes, int *qcnt,
-                                                                 int nt, const float4 *__restrict__ tmw)
+                                                                 int nt, const float4 *__restrict__ l0img)
 {
-    // pass 0: seeds from the winner records of the last accumulation (none on the first search of a loop: every split then has to
-    // find a best of its own before it can skip anything).  pass 2: seeds from keys, where k_nn_seed_sorted has left every point's
-    // nearest vertex within its own slab -- a distance really achieved, usually a few times the true one: enough for level 0.
     if (st->halt) return;
+    constexpr Level0 L0 = sorted_level0(R, VCHUNK);
+    constexpr bool OWN_TILE = L0 != Level0::PerVertex;              // level 0 reads images of its own, staged beside the tfs tile
+    constexpr bool POINT_PAIRS = level0_on_point_pairs(L0);
+    constexpr bool IMAGES = L0 == Level0::Images;
     constexpr int TILE_F4 = TG * 3, LOADS = (TILE_F4 + NN_THREADS - 1) / NN_THREADS;   // TG = 256: 3 whole rounds; TG = 64: 192 of 256 threads
     constexpr bool WHOLE = TILE_F4 % NN_THREADS == 0;
     static_assert(LOADS >= 1 && LOADS <= 3, "k_nn_search_sorted: 1 .. 3 float4 per thread and tile");
+    constexpr int TW = level0_tile_f4(L0, TG);                      // float4 of level 0's tile
+    // a block: 4 GW = 256 vertices x R points per skip test.  Which blocks go on to level 1 is decided by the slabs' u, not by
+    // the block size (256 sorted vertices of a million span 5e-4 of the axis, a point's reach 0.03), so larger blocks only save
+    // compares, branches and waits for the tile: 16 / 32 / 64 / 128 / 256 / 512 vertices 31.1 / 28.8 / 28.0 / 27.6 / 27.3 /
+    // 27.4 ms per iteration at 1M <-> 1M.  Folded 16 vertices (four images) at a time, fully unrolled (as a loop of four chunks
+    // per trip: 28.3 ms).
+    constexpr int GW = SORTED_GW < TG ? SORTED_GW : TG;
+    static_assert(GW % 4 == 0 && TG % GW == 0, "k_nn_search_sorted: blocks of whole chunks of 16 vertices");
+    static_assert(GW % SORTED_IMAGE_V == 0, "k_nn_search_sorted: blocks of whole trips of four images");
+    // level 0v's chunks: CG groups each, NC per block; a lane's chunk bits in ONE register, the wave's union in a scalar
+    constexpr int CG = SORTED_VCG, NC = GW / CG;
+    static_assert(CG >= 1 && GW % CG == 0 && NC <= 64, "k_nn_search_sorted: level 0v's chunks");
+    using cmask_t = typename std::conditional<(NC > 32), unsigned long long, uint32_t>::type;
     __shared__ float4 tile[2][TILE_F4];
-    // level 0's own tile (VCHUNK): the pair images of the same groups, one float4 per group -- beside the three of tfs, which
-    // levels 0v-3 go on reading
-    // (round 18, R >= 2: the quad images instead, three float4 per chunk of 4 groups -- tmw then points at them, launch_brute_sorted)
-    constexpr bool PAIRS = VCHUNK;
-    constexpr bool OCT = PAIRS && sorted_oct(R);
-    constexpr int OV = OA_SORTED_OCT_V;                             // positions per image (round 19: 16; 4 is round 18's quad)
-    constexpr int TW = OCT ? TG * 3 / OV : TG;                      // float4 of level 0's tile
-    __shared__ float4 tilew[2][PAIRS ? TW : 1];
+    __shared__ float4 tilew[2][OWN_TILE ? TW : 1];
     __shared__ unsigned long long clk0[2];
     __shared__ int s_item[3];                                       // the workgroup's item {split, block}; [2]: the queues found empty so far
     const int tid0 = threadIdx.x;
@@ -1910,43 +1990,18 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
     asm volatile("" : "+v"(tid));
     int split = (int)blockIdx.x, yblk = (int)blockIdx.y;
     if (queued) {
-        if (tid == 0) {
-            // SORTED_QUEUES queues when they divide the splits (else one): queue q holds the splits s = q + nq j; item p of a queue
-            // is block p / per_q at rank p mod per_q, rank k being the split k steps (0, +1, -1, +2, ...) from the block's own
-            const int nq = (n_splits % SORTED_QUEUES == 0) ? SORTED_QUEUES : 1, per_q = n_splits / nq;
-            const int q_len = per_q * n_blocks;
-            unsigned xcc = 0;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            int got = -1, got_y = 0;
-            unsigned q_dry = (unsigned)s_item[2];
-            for (int a = 0; a < nq && got < 0; ++a) {
-                const int q = (int)((xcc + (unsigned)a) & (unsigned)(nq - 1));
-                if (q_dry & (1u << q)) continue;
-                const int pos = atomicAdd(qcnt + q * SORTED_QUEUE_STRIDE, 1);
-                if (pos >= q_len) { q_dry |= 1u << q; continue; }
-                got_y = pos / per_q;
-                const int k = pos - got_y * per_q;
-                int j0 = (homes[2 * got_y] - q + nq / 2) / nq;          // the queue's split nearest to the block's own
-                j0 = j0 < 0 ? 0 : (j0 >= per_q ? per_q - 1 : j0);
-                int j = (j0 + ((k & 1) ? (k + 1) / 2 : -(k / 2))) % per_q;
-                if (j < 0) j += per_q;
-                got = q + nq * j;
-            }
-            s_item[0] = got; s_item[1] = got_y; s_item[2] = (int)q_dry;
-        }
-        __syncthreads();
-        split = __builtin_amdgcn_readfirstlane(s_item[0]); yblk = __builtin_amdgcn_readfirstlane(s_item[1]);   // (scalar registers, as blockIdx was)
-        if (split < 0) break;                                       // (the whole workgroup: nothing left anywhere)
+        if (!sorted_take_item(tid, qcnt, homes, n_splits, n_blocks, s_item, split, yblk)) break;
     } else { n_splits = (int)gridDim.x; n_blocks = (int)gridDim.y; }
     const bool clk_wg = (split == 0 && yblk == n_blocks / 2 && tid == 0);   // one workgroup's item from the middle of the launch
     if (clk_wg) { clk0[0] = (unsigned long long)__builtin_readcyclecounter(); clk0[1] = wall_clock64(); }
     const double qmax = st->qmax;
     // a wave owns R x 64 CONSECUTIVE slots (neighbours in space: the smallest extent in u, the fewest slabs it must look into), and
     // so R x 64 consecutive records (k_sorted_point_setup, which also decides WHICH of the wave's slots a lane takes as its point
-    // r): record rec0 + 64 r is point r of this lane -- coalesced loads, nothing to compute.  co_find itself (the record's third
-    // float4) is loaded where level 3 needs it: twelve registers (R = 4) not held through the scan, and no scratch left
+    // r): record rec0 + 64 r is point r of this lane -- coalesced loads, nothing to compute
     const int ns_pad = n_blocks * (NN_THREADS * R);
     const int rec0 = yblk * (NN_THREADS * R) + (tid >> 6) * (64 * R) + (tid & 63);
+    // -- the lane's points from their records (written out: as a function it put <4, 256, false> into scratch).  co_find itself
+    // (the record's third float4) is loaded where level 3 needs it: twelve registers (R = 4) not held through the scan --
     float hu[R], hv[R], hd[R], best[R], thr1[R], thr2[R];
     uint32_t bidx[R];
 #pragma unroll
@@ -1955,8 +2010,8 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
         hu[r] = ra.x; hv[r] = ra.y; hd[r] = ra.z;
         best[r] = rb.x; bidx[r] = __float_as_uint(rb.y); thr1[r] = rb.z; thr2[r] = rb.w;
         if (pass == 2) {
-            // (a 64-bit load: whatever another split has merged by now is as good.  keys only fall, so the key is the record's
-            //  seed or beats it; the thresholds depend on the distance alone)
+            // (the seed anew from keys, a 64-bit load: whatever another split has merged by now is as good.  keys only fall, so
+            //  the key is the record's seed or beats it; the thresholds depend on the distance alone)
             const unsigned long long k = __hip_atomic_load(keys + __float_as_int(ra.w), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const float kd = __uint_as_float((uint32_t)(k >> 32));
             if ((uint32_t)k != IDX_NONE && kd < INFINITY && k < (((unsigned long long)__float_as_uint(best[r]) << 32) | bidx[r])) {
@@ -1966,11 +2021,9 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
             }
         }
     }
-    // round 13: the lane's point pairs (2p, 2p + 1) for level 0 -- image and allowance from the set-up, the threshold from the two
-    // points' thr1 as they stand now (after pass 2's refresh above); renewed wherever thr1 can change (the end of the rare path)
-    constexpr bool QUAD = PAIRS && R >= 2 && OA_SORTED_QUAD;
-    float qhm[QUAD ? R / 2 : 1], qhw[QUAD ? R / 2 : 1], qthr[QUAD ? R / 2 : 1];
-    if constexpr (QUAD) {
+    // the lane's point pairs (2p, 2p + 1) for level 0: image from the set-up, the threshold from thr1 as it stands now
+    float qhm[POINT_PAIRS ? R / 2 : 1], qhw[POINT_PAIRS ? R / 2 : 1], qthr[POINT_PAIRS ? R / 2 : 1];
+    if constexpr (POINT_PAIRS) {
 #pragma unroll
         for (int p = 0; p < R / 2; ++p) {
             const float4 rq = rec[3 * ns_pad + rec0 + 64 * p];
@@ -1997,8 +2050,8 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                                         : (((k) & 1) ? tile_s + (((k) + 1) >> 1) : tile_s - ((k) >> 1)))
 
     float4 stg0 = make_float4(0.f, 0.f, 0.f, 0.f), stg1 = stg0, stg2 = stg0, stgw = stg0;
-    const float4 *wsrc = tmw + (OCT ? g_begin / OV * 3 : g_begin);  // (g_begin: a multiple of TG)
-#define OA_STGW_ON (PAIRS && (TW >= NN_THREADS || tid < TW))
+    const float4 *wsrc = l0img + (IMAGES ? g_begin / SORTED_IMAGE_V * 3 : g_begin);  // (g_begin: a multiple of TG)
+#define OA_STGW_ON (OWN_TILE && (TW >= NN_THREADS || tid < TW))
     static_assert(TW <= NN_THREADS && TG % 16 == 0, "k_nn_search_sorted: one float4 of level 0's images per thread and tile");
 #define OA_STG_ON(k) (WHOLE || (k) * NN_THREADS + tid < TILE_F4)
 #define OA_STG_EACH(OP)                                       \
@@ -2032,73 +2085,64 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
             if (OA_STGW_ON) stgw = wsrc[TW * nt1 + ltid];
         }
         const int gbase = g_begin + OA_TILE_AT(t) * TG;
-        // 4 GW = 256 vertices x R points per skip test.  On gfx950 v_sub_f32 issues at full rate, v_min_f32, v_min3_f32 and v_cmp_*_f32
-        // at half rate (tools/valu_rates.hip): the tree is all min3 (two comparisons per instruction), one compare per block.
-        // Which blocks go on to level 1 is decided by the slabs' u, not by the block size (256 sorted vertices of a million span
-        // 5e-4 of the axis, a point's reach 0.03), so larger blocks only save compares, branches and waits for the tile:
-        // 16 / 32 / 64 / 128 / 256 / 512 vertices 31.1 / 28.8 / 28.0 / 27.6 / 27.3 / 27.4 ms per iteration at 1M <-> 1M.
-        // The block is folded 16 vertices at a time, fully unrolled (the chain's value and the odd one out carried over; as a
-        // loop of four chunks per trip: 28.3 ms): 16 tile registers live.
-        constexpr int GW = OA_SORTED_GW < TG ? OA_SORTED_GW : TG;
-        static_assert(GW % 4 == 0 && TG % GW == 0, "k_nn_search_sorted: blocks of whole chunks of 16 vertices");
         for (int g = 0; g < TG; g += GW) {
-            bool hit0 = false, hit[R];
-            if constexpr (QUAD) {
-                // level 0 on pairs of vertices AND pairs of the lane's points (round 13; proof in oa_quadgap.hpp): the signed
-                // t = ||m - hm| - hw| - w never exceeds the smallest of the four gaps by more than the pair's allowance, so
-                // t > qthr rules out both vertices for both points.  Per 16 vertices and point pair 24 subtracts and 4 min3 (no
-                // modifier on their sources) where the per-point fold below spends 32 and 8; the same tile reads
-                float qm[R / 2], qodd[R / 2];
-                if constexpr (OCT) {
-                    // round 18, on QUADS of vertices (proof in oa_octgap.hpp): the signed t = |||mm - hm| - hw'| - ww| - ws never
-                    // exceeds the smallest of the eight gaps by more than e and the pair's allowance, both inside qthr.  Per 16
-                    // vertices and point pair 16 subtracts and 2 min3, from three tile reads instead of four
-                    // round 19: an image stands for OV = 16 (or 8) positions, so a trip of four images covers OV groups: GW / OV trips
-                    // per block where round 18 had GW / 4, the trip's body the same
-                    static_assert(GW % OV == 0, "k_nn_search_sorted: blocks of whole trips of four images");
+            const float4 *blk = &tile[cur][3 * g];                 // the block's groups in the tfs tile
+            // level 0 (oa_level0.hpp): the block's smallest gap per point -- or point pair --, a trip of 16 vertices or four images
+            // at a time, then ONE compare: can any of the lane's points not rule the whole block out?
+            constexpr int NM = POINT_PAIRS ? R / 2 : R, TRIPS = IMAGES ? GW / SORTED_IMAGE_V : GW / 4;
+            float m[NM], odd[NM];
 #pragma unroll
-                    for (int c = 0; c < GW / OV; ++c) {
-                        const float4 MM = tilew[cur][3 * (g / OV + c)], WW = tilew[cur][3 * (g / OV + c) + 1], WS = tilew[cur][3 * (g / OV + c) + 2];
+            for (int c = 0; c < TRIPS; ++c) {
+                if constexpr (L0 == Level0::PerVertex) {
+                    // per vertex, from the tfs tile itself: |qu - hu|, one subtract and half a min3 per (vertex, point) pair, the |.| on
+                    // the min's source modifier.  (Written out here: as a trip function like the point-pair kinds' it cost
+                    // <4, 256, false> 12 B of scratch and <2, 256, false> a wave of occupancy.)
+                    float4 QU[4];
 #pragma unroll
-                        for (int p = 0; p < R / 2; ++p) {
-                            const float a0 = oct_gap(MM.x, WW.x, WS.x, qhm[p], qhw[p]), a1 = oct_gap(MM.y, WW.y, WS.y, qhm[p], qhw[p]);
-                            const float a2 = oct_gap(MM.z, WW.z, WS.z, qhm[p], qhw[p]), a3 = oct_gap(MM.w, WW.w, WS.w, qhm[p], qhw[p]);
-                            const float v = c == 0 ? a0 : __builtin_fminf(__builtin_fminf(qm[p], qodd[p]), a0);
-                            qm[p] = __builtin_fminf(__builtin_fminf(v, a1), a2);                                      // v_min3_f32
-                            qodd[p] = a3;
+                    for (int k = 0; k < 4; ++k) QU[k] = blk[3 * (4 * c + k)];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        float a[16];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            a[4 * k] = __builtin_fabsf(QU[k].x - hu[r]); a[4 * k + 1] = __builtin_fabsf(QU[k].y - hu[r]);
+                            a[4 * k + 2] = __builtin_fabsf(QU[k].z - hu[r]); a[4 * k + 3] = __builtin_fabsf(QU[k].w - hu[r]);
                         }
-                    }
-                } else {
-#pragma unroll
-                    for (int c = 0; c < GW / 4; ++c) {
-                        float4 MW[4];
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) MW[k] = tilew[cur][g + 4 * c + k];
-#pragma unroll
-                        for (int p = 0; p < R / 2; ++p) {
-                            float a[8];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                a[2 * k] = quad_gap(MW[k].x, MW[k].y, qhm[p], qhw[p]); a[2 * k + 1] = quad_gap(MW[k].z, MW[k].w, qhm[p], qhw[p]);
-                            }
-                            float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(qm[p], qodd[p]), a[0]);
-#pragma unroll
-                            for (int k = 1; k + 1 < 8; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);   // v_min3_f32
-                            qm[p] = v;
-                            qodd[p] = a[7];
-                        }
+                        level0_chain(a, c == 0, m[r], odd[r]);
                     }
                 }
-                // a pair that cannot rule the block out marks BOTH its points: level 0v and levels 1-3 decide per point as they
-                // always did (a hit that the per-point fold of round 11 would not have given is wasted work there, never a
-                // wrong answer).  Folding the block again per point for exactly round 11's hit[r] measured slower: 17.17 against
-                // 16.03 ms per step at 1M <-> 1M (profiles/r13a_point_pairs.txt)
+                else if constexpr (L0 == Level0::VertexPairs) {
+                    // vertex pairs, per point: the pair images {m01, w01, m23, w23}, pair_gap -- per 16 vertices and point 16 subtracts
+                    // (8 with |.| on their first source) and 4 min3.  (Written out as well: as a trip function the fold was
+                    // scheduled differently and OA_NN_R=1 measured 29.05 -> 29.29 ms per step, outside the margin.)
+                    float4 MW[4];
 #pragma unroll
-                for (int p = 0; p < R / 2; ++p) {
-                    hit[2 * p] = hit[2 * p + 1] = !(__builtin_fminf(qm[p], qodd[p]) > qthr[p]);
-                    hit0 |= hit[2 * p];
+                    for (int k = 0; k < 4; ++k) MW[k] = tilew[cur][g + 4 * c + k];
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        float a[8];
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            a[2 * k] = pair_gap(MW[k].x, MW[k].y, hu[r]); a[2 * k + 1] = pair_gap(MW[k].z, MW[k].w, hu[r]);
+                        }
+                        level0_chain(a, c == 0, m[r], odd[r]);
+                    }
                 }
-                if (!hit0) continue;
+                else if constexpr (L0 == Level0::PointPairs) level0_point_pairs<R>(&tilew[cur][g + 4 * c], c == 0, qhm, qhw, m, odd);
+                else level0_images<R>(&tilew[cur][3 * (g / SORTED_IMAGE_V + c)], c == 0, qhm, qhw, m, odd);
+            }
+            bool hit[R], hit0;
+            if constexpr (POINT_PAIRS) hit0 = level0_pair_hits<R>(m, odd, qthr, hit);
+            else {                                                 // per point (a NaN is a hit)
+                hit0 = false;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    hit[r] = !(__builtin_fminf(m[r], odd[r]) > thr1[r]);
+                    hit0 |= hit[r];
+                }
+            }
+            if (!hit0) continue;
+            if constexpr (POINT_PAIRS) {
                 // the points' own coordinates from their records again, through a laundered index: the scan itself needs only
                 // the pairs' images, and 3 R registers held through it for the rare path's sake are what pushed <4, 256, true>
                 // into scratch
@@ -2109,176 +2153,68 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
                     const float4 ra = rec[rh + 64 * r];
                     hu[r] = ra.x; hv[r] = ra.y; hd[r] = ra.z;
                 }
-            } else {
-                float m[R], odd[R];
-#pragma unroll
-                for (int c = 0; c < GW / 4; ++c) {
-                    if constexpr (PAIRS) {
-                        // level 0 on pairs of vertices (round 11; proof in the header): per 16 vertices 4 float4 of pair images,
-                        // 16 subtracts (8 of them with |.| on their first source) and 4 min3 per point -- a quarter of a min3 per
-                        // pair where the single gaps below take half of one
-                        float4 MW[4];
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) MW[k] = tilew[cur][g + 4 * c + k];
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {
-                            float a[8];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                a[2 * k] = pair_gap(MW[k].x, MW[k].y, hu[r]); a[2 * k + 1] = pair_gap(MW[k].z, MW[k].w, hu[r]);
-                            }
-                            float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(m[r], odd[r]), a[0]);
-#pragma unroll
-                            for (int k = 1; k + 1 < 8; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);   // v_min3_f32
-                            m[r] = v;
-                            odd[r] = a[7];
-                        }
-                    } else {
-                        float4 QU[4];
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) QU[k] = tile[cur][3 * (g + 4 * c + k)];
-#pragma unroll
-                        for (int r = 0; r < R; ++r) {                  // level 0: one subtract + half a min3 per pair, no branch inside
-                            float a[16];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                a[4 * k] = __builtin_fabsf(QU[k].x - hu[r]); a[4 * k + 1] = __builtin_fabsf(QU[k].y - hu[r]);
-                                a[4 * k + 2] = __builtin_fabsf(QU[k].z - hu[r]); a[4 * k + 3] = __builtin_fabsf(QU[k].w - hu[r]);
-                            }
-                            float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(m[r], odd[r]), a[0]);
-#pragma unroll
-                            for (int k = 1; k + 1 < 16; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);   // v_min3_f32
-                            m[r] = v;
-                            odd[r] = a[15];
-                        }
-                    }
-                }
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    hit[r] = !(__builtin_fminf(m[r], odd[r]) > thr1[r]);
-                    hit0 |= hit[r];
-                }
-                if (!hit0) continue;
             }
             if constexpr (VCHUNK) {
-                // level 0v (round 8; proof in the header): which of the block's chunks of 4 CG vertices can hold a vertex within
-                // thr1 of the point along v, from each chunk's two ends -- 2 fma, a max and a compare per chunk where round 7 folded
-                // every vertex again (~430 instructions per block and point).  a_j = fma(0.5, -2qv_j, hv): the halving is exact, the
-                // one rounding is the subtraction's.  thr1 only falls while levels 1-3 run, so a mask taken before them stays
-                // conservative.  One point r at a time (the order in which groups are scored cannot change a lexicographic
-                // minimum): the lane's own chunk bits in ONE register, the wave's union in a scalar; then levels 1-3 for the groups
-                // of those chunks.  (All R masks kept at once and a group-major loop cost registers enough to spill the next tile's
-                // staging registers.)
-                constexpr int CG = OA_SORTED_VCG, NC = GW / CG;    // groups per chunk, chunks per block
-                static_assert(CG >= 1 && GW % CG == 0 && NC <= 64, "k_nn_search_sorted: level 0v's chunks");
-                using cmask_t = typename std::conditional<(NC > 32), unsigned long long, uint32_t>::type;
-                const int blk = __builtin_amdgcn_readfirstlane(gbase + g);   // the block's first group
-                const int n_in = nt - 4 * blk;                     // positions of the block that hold a vertex (when < 4 GW)
+                // One point r at a time (the order in which groups are scored cannot change a lexicographic minimum): level 0v's
+                // masks, then levels 1-3 for the chunks of the wave's.  (All R masks kept at once and a group-major loop cost
+                // registers enough to spill the next tile's staging registers.)
+                const int blk0 = __builtin_amdgcn_readfirstlane(gbase + g);   // the block's first group
+                const int n_in = nt - 4 * blk0;                    // positions of the block that hold a vertex (when < 4 GW)
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     if (!__ballot(hit[r])) continue;               // (uniform: no lane of the wave has this point in the block)
-                    cmask_t cm = 0, todo = 0;
-                    if (n_in >= 4 * GW) {
-                        // chunk c passes for this lane when the lane has this point in the block and the ends do not rule it out
-                        // (& rather than &&: no branch per chunk)
-#define OA_VCHUNK_PASS(c, out)                                                                                                      \
-                        do {                                                                                                        \
-                            const bool p_ = hit[r] & !(out);                                                                       \
-                            cm |= (cmask_t)p_ << (c);                                                                              \
-                            if (__builtin_amdgcn_ballot_w64(p_)) todo |= (cmask_t)1 << (c);                                         \
-                        } while (0)
-                        {                                                  // chunk 0: the block's position 0 on its own
-                            const float4 A0 = tile[cur][3 * g + 1], A1 = tile[cur][3 * (g + CG - 1) + 1];
-                            const float F = __builtin_fmaf(0.5f, A0.y, hv[r]), L = __builtin_fmaf(0.5f, A1.w, hv[r]);
-                            OA_VCHUNK_PASS(0, (__builtin_fmaxf(L, -F) > thr1[r]) & (__builtin_fabsf(__builtin_fmaf(0.5f, A0.x, hv[r])) > thr1[r]));
-                        }
-#pragma unroll 5
-                        for (int c = 1; c < NC; ++c) {
-                            const float4 A0 = tile[cur][3 * (g + CG * c) + 1], A1 = tile[cur][3 * (g + CG * c + CG - 1) + 1];
-                            const float L = __builtin_fmaf(0.5f, A1.w, hv[r]);
-                            if ((4 * GW > SORTED_VBLOCK) && (4 * CG * c) % SORTED_VBLOCK == 0) {   // (blocks of more than one: their 0s)
-                                const float F = __builtin_fmaf(0.5f, A0.y, hv[r]);
-                                OA_VCHUNK_PASS(c, (__builtin_fmaxf(L, -F) > thr1[r]) & (__builtin_fabsf(__builtin_fmaf(0.5f, A0.x, hv[r])) > thr1[r]));
-                            } else {
-                                const float F = __builtin_fmaf(0.5f, A0.x, hv[r]);
-                                OA_VCHUNK_PASS(c, __builtin_fmaxf(L, -F) > thr1[r]);
-                            }
-                        }
-#undef OA_VCHUNK_PASS
-                    } else {                                       // padding at the tail (AV = 0 breaks the order): the chunks that hold a vertex
-#pragma unroll 1
-                        for (int c = 0; c < NC && 4 * CG * c < n_in; ++c) {
-                            cm |= (cmask_t)hit[r] << c;
-                            todo |= (cmask_t)1 << c;
-                        }
-                    }
-                    // round 17: level 1 for a passing chunk's 4 CG vertices in one pass -- its 3 CG tile reads issued together and
-                    // consumed in their order (the compiler counts the waits down, lgkmcnt(9) .. (0), but opens with a full one: a
-                    // scalar load of level 2 may be pending on the back edge), the CG group minima kept, ONE test of their minimum per lane and one
-                    // branch per chunk; only a chunk some lane still wants is walked group by group, in the order of before, a lane
-                    // entering level 2 for a group whose stored minimum is not above its thr2 AS IT STANDS THEN (thr2 only falls, at
-                    // level 3): the same groups reach level 2 as when each was scored on its own trip.  (One difference, which no
-                    // answer can see: a group whose four scores are all NaN -- four non-finite vertices -- no longer carries its
-                    // chunk past the test when the other groups' scores are numbers; such vertices never win.  A non-finite POINT
-                    // makes every score NaN and passes everything, as before.)  The serial form spent three dependent LDS round
-                    // trips and a branch per group: 4 of each per 32 FMA.
-                    constexpr bool CHUNK_L1 = !OA_SORTED_VREFINE && CG >= 2 && CG <= 4;
+                    cmask_t cm, todo;
+                    sorted_chunk_masks<GW, CG, cmask_t>(blk, n_in, hit[r], hv[r], thr1[r], cm, todo);
                     for (; todo; todo &= todo - 1) {
                         // (todo is the wave's: made of ballots.  Said so, the chunk's tile addresses are scalar arithmetic)
                         const int c = __builtin_amdgcn_readfirstlane((NC > 32) ? __builtin_ctzll((unsigned long long)todo) : __builtin_ctz((uint32_t)todo));
                         const bool mine = (cm >> c) & 1;
-                        if constexpr (CHUNK_L1) {
-                            const float4 *cg = &tile[cur][3 * (g + CG * c)];
-                            float4 Q[CG], AV[CG], W2[CG];
+                        // -- levels 1-3 for this point and chunk c (written out: as a function it adds a v_cmp_f32 per point) --
+                        // Level 1 for the chunk's 4 CG vertices in one pass -- its 3 CG tile reads issued together and consumed in
+                        // their order (the compiler counts the waits down, lgkmcnt(9) .. (0), but opens with a full one: a scalar
+                        // load of level 2 may be pending on the back edge), the CG group minima kept, ONE test of their minimum per
+                        // lane and one branch per chunk; only a chunk some lane still wants is walked group by group, a lane
+                        // entering level 2 for a group whose stored minimum is not above its thr2 AS IT STANDS THEN (thr2 only
+                        // falls, at level 3): the same groups reach level 2 as when each is scored on its own trip.  (One
+                        // difference, which no answer can see: a group whose four scores are all NaN -- four non-finite vertices --
+                        // does not carry its chunk past the test when the other groups' scores are numbers; such vertices never
+                        // win.  A non-finite POINT makes every score NaN and passes everything.)
+                        static_assert(CG >= 2 && CG <= 4, "k_nn_search_sorted: a chunk is 2-4 groups (their minima are held in registers)");
+                        const float4 *cg = &tile[cur][3 * (g + CG * c)];
+                        float4 Q[CG], AV[CG], W2[CG];
 #pragma unroll
-                            for (int k = 0; k < CG; ++k) { Q[k] = cg[3 * k]; AV[k] = cg[3 * k + 1]; W2[k] = cg[3 * k + 2]; }
-                            float gmin[CG];
+                        for (int k = 0; k < CG; ++k) { Q[k] = cg[3 * k]; AV[k] = cg[3 * k + 1]; W2[k] = cg[3 * k + 2]; }
+                        float gmin[CG];
 #pragma unroll
-                            for (int k = 0; k < CG; ++k)
-                                gmin[k] = sorted_level1_min(make_float4(-2.0f * Q[k].x, -2.0f * Q[k].y, -2.0f * Q[k].z, -2.0f * Q[k].w), AV[k], W2[k],
-                                                            hu[r], hv[r]);
-                            float cmin = gmin[0];
+                        for (int k = 0; k < CG; ++k)
+                            gmin[k] = sorted_level1_min(make_float4(-2.0f * Q[k].x, -2.0f * Q[k].y, -2.0f * Q[k].z, -2.0f * Q[k].w), AV[k], W2[k],
+                                                        hu[r], hv[r]);
+                        float cmin = gmin[0];
 #pragma unroll
-                            for (int k = 1; k < CG; ++k) cmin = __builtin_fminf(cmin, gmin[k]);   // v_min3_f32 (+ v_min_f32)
-                            const bool want = mine & !(cmin > thr2[r]);
-                            if (!__ballot(want)) continue;
-                            // (the minima rotate through gmin[0] and the group's images come from the tile again: a loop of one
-                            //  copy of levels 2-3 per point, as before, and no register held for them through level 1)
+                        for (int k = 1; k < CG; ++k) cmin = __builtin_fminf(cmin, gmin[k]);   // v_min3_f32 (+ v_min_f32)
+                        const bool want = mine & !(cmin > thr2[r]);
+                        if (!__ballot(want)) continue;
+                        // (the minima rotate through gmin[0] and the group's images come from the tile again: a loop of one copy of
+                        //  levels 2-3 per point, and no register held for them through level 1)
 #pragma unroll 1
-                            for (int k = 0; k < CG; ++k) {
-                                if (want && !(gmin[0] > thr2[r])) {
-                                    // (the point through laundered copies: what levels 2-3 derive from it alone -- the double
-                                    //  precision terms of the thresholds, a square root among them -- is then computed where a
-                                    //  lane needs it, not ahead of this loop for every block and point, and held in registers)
-                                    float lu = hu[r], lv = hv[r], ld = hd[r];
-                                    asm volatile("" : "+v"(lu), "+v"(lv), "+v"(ld));
-                                    const float4 Qk = cg[3 * k], AVk = cg[3 * k + 1];
-                                    sorted_finish_level2(make_float4(-2.0f * Qk.x, -2.0f * Qk.y, -2.0f * Qk.z, -2.0f * Qk.w), AVk, gbase + g + CG * c + k,
-                                                         tf3s, tgs, tidx, rec + 2 * ns_pad + rec0 + 64 * r, lu, lv, ld, qmax, best[r], bidx[r],
-                                                         thr1[r], thr2[r]);
-                                }
+                        for (int k = 0; k < CG; ++k) {
+                            if (want && !(gmin[0] > thr2[r])) {
+                                // (the point through laundered copies: what levels 2-3 derive from it alone -- the double precision
+                                //  terms of the thresholds, a square root among them -- is then computed where a lane needs it,
+                                //  not ahead of this loop for every block and point, and held in registers)
+                                float lu = hu[r], lv = hv[r], ld = hd[r];
+                                asm volatile("" : "+v"(lu), "+v"(lv), "+v"(ld));
+                                const float4 Qk = cg[3 * k], AVk = cg[3 * k + 1];
+                                sorted_finish_level2(make_float4(-2.0f * Qk.x, -2.0f * Qk.y, -2.0f * Qk.z, -2.0f * Qk.w), AVk, gbase + g + CG * c + k,
+                                                     tf3s, tgs, tidx, rec + 2 * ns_pad + rec0 + 64 * r, lu, lv, ld, qmax, best[r], bidx[r],
+                                                     thr1[r], thr2[r]);
+                            }
 #pragma unroll
-                                for (int j = 0; j + 1 < CG; ++j) gmin[j] = gmin[j + 1];
-                            }
-                        } else {                                   // (OA_SORTED_VREFINE, other chunk sizes) the serial form of rounds 7-13
-#pragma unroll 1
-                            for (int k = CG * c; k < CG * c + CG; ++k) {  // one group of 4 targets at a time
-                                const float4 Q = tile[cur][3 * (g + k)], AV = tile[cur][3 * (g + k) + 1], W2 = tile[cur][3 * (g + k) + 2];
-                                bool want = mine;
-                                if (OA_SORTED_VREFINE && n_in >= 4 * GW && (4 * k) % SORTED_VBLOCK != 0) {   // the same test, per group
-                                    const float F = __builtin_fmaf(0.5f, AV.x, hv[r]), L = __builtin_fmaf(0.5f, AV.w, hv[r]);
-                                    want = want && !(__builtin_fmaxf(L, -F) > thr1[r]);
-                                    if (!__ballot(want)) continue;
-                                }
-                                const float4 AU = make_float4(-2.0f * Q.x, -2.0f * Q.y, -2.0f * Q.z, -2.0f * Q.w);   // exact
-                                if (want)
-                                    sorted_finish_group(AU, AV, W2, gbase + g + k, tf3s, tgs, tidx, rec + 2 * ns_pad + rec0 + 64 * r, hu[r], hv[r],
-                                                        hd[r], qmax, best[r], bidx[r], thr1[r], thr2[r]);
-                            }
+                            for (int j = 0; j + 1 < CG; ++j) gmin[j] = gmin[j + 1];
                         }
                     }
                 }
-                if constexpr (QUAD) {
+                if constexpr (POINT_PAIRS) {
                     // thr1 may have fallen: the point pairs' thresholds anew (the allowance again from the set-up's record, through
                     // a laundered index, instead of a register per pair held through the scan)
                     int rq = rec0;
@@ -2286,7 +2222,7 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
 #pragma unroll
                     for (int p = 0; p < R / 2; ++p) qthr[p] = quad_threshold(thr1[2 * p], thr1[2 * p + 1], rec[3 * ns_pad + rq + 64 * p].z);
                 }
-            } else {                                               // OA_NN_VCHUNK=0: the rare loop of round 6, as it was
+            } else {                                               // OA_NN_VCHUNK=0: levels 1-3 for every group of the block
 #pragma unroll 1
                 for (int k = 0; k < GW; ++k) {                     // rare from here on: one group of 4 targets at a time
                     const float4 Q = tile[cur][3 * (g + k)], AV = tile[cur][3 * (g + k) + 1], W2 = tile[cur][3 * (g + k) + 2];
@@ -2318,29 +2254,7 @@ __global__ __launch_bounds__(NN_THREADS, (R <= 4 ? 4 : 2)) void k_nn_search_sort
         ws->search_clk[0] = (unsigned long long)__builtin_readcyclecounter() - clk0[0];
         ws->search_clk[1] = wall_clock64() - clk0[1];
     }
-    // a split reports when it has something to say (k_nn_search_filtered); the seed's owner: seed index mod splits.
-    // (The slot's index and the seed again from the record, instead of three registers per point held through the scan: the
-    //  laundered index below makes these loads new ones the compiler cannot merge with the prologue's, and that reload is what
-    //  keeps the kernel at 0 B of scratch.)
-    int rec1 = rec0;
-    asm volatile("" : "+v"(rec1));
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const unsigned long long key = ((unsigned long long)__float_as_uint(best[r]) << 32) | bidx[r];
-        unsigned long long *dst = keys + __float_as_int(rec[rec1 + 64 * r].w);
-        if (pass != 0) {                                           // merges into whatever keys holds: monotone
-            if (key < __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(dst, key);
-        } else if (n_splits == 1) *dst = key;
-        else {
-            const float4 rb = rec[ns_pad + rec1 + 64 * r];
-            const float seed_d = rb.x;
-            const uint32_t seed_idx = __float_as_uint(rb.y);
-            const bool seeded = seed_idx != IDX_NONE;
-            const bool improved = bidx[r] != seed_idx || best[r] != seed_d;
-            const bool owner = seeded && (int)(seed_idx % (uint32_t)n_splits) == split;
-            if (!seeded || improved || owner) atomicMin(dst, key);
-        }
-    }
+    sorted_report<R>(rec, rec0, ns_pad, keys, pass, n_splits, split, best, bidx);
     if (!queued) break;
   }
 }

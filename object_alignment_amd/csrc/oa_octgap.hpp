@@ -125,6 +125,7 @@ OA_PAIRGAP_FN void group_image(const float *q, int n_real, float c, float &mm, f
 
 // The image {mm, ww, ws} of a group's two vertex pairs {ma, wa}, {mb, wb} (pair_image's floats) under the cap c, formed in double
 // and rounded once.  real_a / real_b: the pair holds at least one vertex (padding only ever follows the vertices).
+// (No device caller: kept because tests/c/oct_gap_bound.cpp checks (1)-(6) through it, and (1')-(6') build on them.)
 OA_PAIRGAP_FN void quad_image(float ma, float wa, bool real_a, float mb, float wb, bool real_b, float c, float &mm, float &ww, float &ws)
 {
     if (real_a && real_b) {

@@ -279,3 +279,62 @@ def test_sorted_kernel_on_a_2M_vertex_target(orc):
     moved = np.array([orc.mat4_mul_vec3(m, p) for p in src], np.float32)
     r2, rd22 = orc.nn_brute(moved, tgt)
     assert np.array_equal(idx2, r2) and np.array_equal(d22, rd22)
+
+
+_MATRIX_REF = {}
+
+
+def _matrix_problem(orc):
+    """One small problem for every instance: 5000 vertices (a padded tail block, 20 tiles of 256 or 5 of 1024: more than one per
+    split with 2 splits) and 700 points (padding slots for every R); the oracle's answers, computed once."""
+    if not _MATRIX_REF:
+        rng = np.random.default_rng(2020)
+        tgt = rng.uniform(-1, 1, size=(5000, 3)).astype(np.float32)
+        src = (tgt[rng.permutation(5000)[:700]] + rng.normal(0, 2e-2, size=(700, 3))).astype(np.float32)
+        eye = np.identity(4, dtype=np.float32)
+        m = eye.copy()
+        m[:3, 3] = np.float32([0.01, -0.02, 0.015])
+        moved = np.array([orc.mat4_mul_vec3(m, p) for p in src], np.float32)
+        _MATRIX_REF.update(tgt=tgt, src=src, eye=eye, m=m, first=orc.nn_brute(src, tgt), second=orc.nn_brute(moved, tgt))
+    return _MATRIX_REF
+
+
+@pytest.mark.parametrize("queue", ["grid", "queue"])
+@pytest.mark.parametrize("bigtile", ["0", "1"])
+@pytest.mark.parametrize("R", [1, 2, 4])
+def test_every_default_instance_unseeded_and_seeded(orc, R, bigtile, queue, monkeypatch):
+    """k_nn_search_sorted<R, 64 | 256, VCHUNK> of the default library, each launched from the grid and through the work queue,
+    unseeded (seed pass + a launch seeded from keys) and seeded from the winner records at a moved pose: the oracle's answers,
+    and OA_NN_VCHUNK=1 bit for bit what OA_NN_VCHUNK=0 gives.
+
+    No stat reports the R, the tile or the split count of a launch, so that the forced ones were launched rests on this: the
+    knobs' parse into Tunables is pinned by tests/test_tunables.py; the launcher dispatches on src.R = tune.nn_r, on the tile
+    plan_geometry takes from tune.nn_bigtile (64 groups for a target this small unless it is set) and on min(OA_NN_SPLITS, tiles)
+    splits, with nothing in between; and the queue is only ever used with more than one split, which the queued cases assert."""
+    from object_alignment_amd.engine import IcpEngine
+    ref = _matrix_problem(orc)
+    monkeypatch.setenv("OA_NN_R", str(R))
+    monkeypatch.setenv("OA_NN_BIGTILE", bigtile)
+    monkeypatch.setenv("OA_NN_SPLITS", "2")
+    if queue == "queue":
+        monkeypatch.setenv("OA_NN_QUEUE_MIN_ITEMS", "0")
+    got = {}
+    for vchunk in ("0", "1"):
+        monkeypatch.setenv("OA_NN_VCHUNK", vchunk)
+        with IcpEngine(0) as e:
+            e.set_search_mode("brute")
+            e.set_target(ref["tgt"])
+            e.set_source(ref["src"])
+            e.set_matrices(ref["eye"], ref["eye"])
+            idx, d2, _ = e.nn_search()
+            assert e.stat("brute_kernel") == 3.0
+            assert (e.stat("brute_queue_wgs") > 0) == (queue == "queue")
+            e.make_pairs(1e30)                               # winner records = seeds
+            e.set_matrices(ref["m"], ref["eye"])
+            idx2, d22, _ = e.nn_search()
+            assert (e.stat("brute_queue_wgs") > 0) == (queue == "queue")
+        got[vchunk] = (idx, d2, idx2, d22)
+        assert np.array_equal(idx, ref["first"][0]) and np.array_equal(d2, ref["first"][1]), (R, bigtile, queue, vchunk)
+        assert np.array_equal(idx2, ref["second"][0]) and np.array_equal(d22, ref["second"][1]), (R, bigtile, queue, vchunk, "seeded")
+    for a, b in zip(got["0"], got["1"]):
+        assert np.array_equal(a, b)

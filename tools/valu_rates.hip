@@ -6,7 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
-#include "oa_octgap.hpp"
+#include "oa_level0.hpp"
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 template <int OP> __global__ __launch_bounds__(256) void burn(float *out, int trips, float seed)
 {
@@ -121,40 +121,15 @@ template <int OCT> __global__ __launch_bounds__(256, 2) void fold(float *out, in
     for (int t = 0; t < trips; ++t) {
         int cur = t & 1;
         asm volatile("" : "+s"(cur));                          // (the tile anew every trip, as the kernel's)
-        float qm[2], qodd[2];
+        float qm[2], qodd[2];                                  // (the library's folds, oa_level0.hpp, as the kernel calls them)
 #pragma unroll
         for (int c = 0; c < (OCT >= 2 ? 16 / OCT : 16); ++c) {
-            if (OCT) {
-                const float4 MM = tl[cur][3 * c], WW = tl[cur][3 * c + 1], WS = tl[cur][3 * c + 2];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    const float a0 = oa::oct_gap(MM.x, WW.x, WS.x, qhm[p], qhw[p]), a1 = oa::oct_gap(MM.y, WW.y, WS.y, qhm[p], qhw[p]);
-                    const float a2 = oa::oct_gap(MM.z, WW.z, WS.z, qhm[p], qhw[p]), a3 = oa::oct_gap(MM.w, WW.w, WS.w, qhm[p], qhw[p]);
-                    const float v = c == 0 ? a0 : __builtin_fminf(__builtin_fminf(qm[p], qodd[p]), a0);
-                    qm[p] = __builtin_fminf(__builtin_fminf(v, a1), a2);
-                    qodd[p] = a3;
-                }
-            } else {
-                float4 MW[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) MW[k] = tl[cur][4 * c + k];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    float a[8];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        a[2 * k] = oa::quad_gap(MW[k].x, MW[k].y, qhm[p], qhw[p]); a[2 * k + 1] = oa::quad_gap(MW[k].z, MW[k].w, qhm[p], qhw[p]);
-                    }
-                    float v = c == 0 ? a[0] : __builtin_fminf(__builtin_fminf(qm[p], qodd[p]), a[0]);
-#pragma unroll
-                    for (int k = 1; k + 1 < 8; k += 2) v = __builtin_fminf(__builtin_fminf(v, a[k]), a[k + 1]);
-                    qm[p] = v;
-                    qodd[p] = a[7];
-                }
-            }
+            if (OCT) oa::level0_images<4>(&tl[cur][3 * c], c == 0, qhm, qhw, qm, qodd);
+            else oa::level0_point_pairs<4>(&tl[cur][4 * c], c == 0, qhm, qhw, qm, qodd);
         }
-#pragma unroll
-        for (int p = 0; p < 2; ++p) hits += !(__builtin_fminf(qm[p], qodd[p]) > qthr[p]) ? 1 : 0;
+        bool hit[4];                                           // (a hit marks both points of a pair)
+        oa::level0_pair_hits<4>(qm, qodd, qthr, hit);
+        hits += (hit[0] ? 1 : 0) + (hit[2] ? 1 : 0);
     }
     if (hits == 12345) out[0] = (float)hits;
 }
