@@ -343,6 +343,48 @@ int oa_orient_target_normals(oa_ctx *ctx, int k, double max_dist, int seed, cons
                              const float *normals /* nt x 3 host, or NULL: the context's target normals */, int install,
                              float *out_normals /* nt x 3 */, uint8_t *out_flipped /* nt */, int32_t *out_component /* nt */,
                              oa_orient_report *rep);
+/* EXTENSION: stray points of a point-cloud target -- flying pixels, dust, the scanner table.  Vertex-mode targets,
+ * single-device contexts.  Coordinates are the target's own (base-local), no matrices needed.
+ *
+ * oa_target_radius_count: count[i] = min(cap, #{ j : d2_metric(v_i, v_j) <= r2 }), r2 = (float)radius * (float)radius (float32, one
+ * rounding; the rule of oa_orient_target_normals' max_dist), in the caller's vertex order.  The vertex itself is included, so a
+ * finite vertex counts at least 1, and duplicates count.  cap = 0: no cap; else the count saturates at cap (the search of that
+ * vertex stops there; the value does not depend on the order of the search).  A vertex with a non-finite coordinate counts 0
+ * and is counted by nobody.  Exact: every hit is one evaluation of the float32 metric, and a pair at d2 = r2 is never lost.
+ *
+ * oa_target_outliers: a keep mask for the resident target and, with apply != 0, the target without the others.
+ *   OA_OUTLIER_STATISTICAL  score[i] = the mean distance from vertex i to its k nearest OTHER vertices: with the k + 1 entries of
+ *       oa_target_knn's row, S = sum over the m filled entries of sqrt((double)d2), in list order, fp64; score = S / (m - 1), +inf
+ *       for m < 2 (a non-finite vertex).  The vertex itself contributes 0.  n = the number of finite scores, mean = sum / n,
+ *       std = sqrt(sum (score - mean)^2 / (n - 1)) (two passes; 0 for n < 2), both fp64 in a fixed order without floating-point
+ *       atomics: two calls give the same bits.  threshold = mean + std_ratio std; keep[i] = score[i] <= threshold.
+ *   OA_OUTLIER_RADIUS       count[i] = oa_target_radius_count(radius, count_cap); keep[i] = count[i] - 1 >= min_neighbors.
+ * Outputs (host, each may be NULL): keep (nt bytes, 0 / 1); score (nt, STATISTICAL) or count (nt, RADIUS) -- the other is not
+ * written; kept_index = the kept vertices in ascending order (n_kept entries; give room for nt); rep.
+ * apply != 0: the resident target becomes the kept vertices in the caller's order, compacted on the device and taken the way
+ * oa_set_target(..., on_device = 1) takes them -- grid, tree and sorted images rebuilt, seeds reset, installed normals, descriptors
+ * and boundary masks forgotten: the context is what oa_set_target(xyz[keep]) would have left.  OA_STAT_TARGET_CLEANED then holds
+ * the number of vertices removed.  When no vertex would be kept: OA_E_TOO_FEW_PAIRS, nothing applied, the outputs written.
+ * Both calls end a running oa_iterate sequence, as oa_target_knn does; a context without a box tree builds one for the call.
+ * OA_E_BAD_ARG: an unknown method; the ranges beside the fields below; a radius that is not finite and > 0; cap < 0.
+ * OA_E_STATE: no target, a surface target, a multi-device context.  Each refusal leaves the context usable. */
+#define OA_OUTLIER_STATISTICAL 0
+#define OA_OUTLIER_RADIUS      1
+typedef struct oa_outlier_settings {
+    int32_t method, k;            /* STATISTICAL: 1 <= k <= min(63, nt - 1) */
+    double  std_ratio;            /* STATISTICAL: finite, >= 0 */
+    double  radius;               /* RADIUS: finite, > 0, the target's own (base-local) units */
+    int32_t min_neighbors;        /* RADIUS: >= 1; neighbours = count - 1 */
+    int32_t count_cap;            /* RADIUS: 0 = exact counts, else >= min_neighbors + 1: counts saturate there */
+} oa_outlier_settings;
+typedef struct oa_outlier_report {
+    int64_t n_kept, n_removed, n_nonfinite;   /* n_nonfinite: vertices with a non-finite coordinate (never kept) */
+    double  mean, std, threshold; /* STATISTICAL; 0 for RADIUS */
+} oa_outlier_report;
+int oa_target_outliers(oa_ctx *ctx, const oa_outlier_settings *s, int apply,
+                       uint8_t *keep /* nt */, double *score /* nt, STATISTICAL */, int32_t *count /* nt, RADIUS */,
+                       int32_t *kept_index /* n_kept entries, room for nt */, oa_outlier_report *rep);
+int oa_target_radius_count(oa_ctx *ctx, double radius, int32_t cap, int32_t *count /* nt */);
 /* EXTENSION (no counterpart in the reference, whose only protection against bad correspondences is the hard cut thresh): pair
  * weights.  Every pair of a loop step (oa_run, oa_iterate, the split-phase calls) carries the weight
  *   w = w_vertex * psi(r),   c = scale (world units, like thresh):
@@ -584,7 +626,8 @@ int oa_reset_seeds(oa_ctx *ctx);
                                       * the first step.  A host integer written where the launch is decided: no device read.  First device */
 #define OA_STAT_ACC_ROWS       50   /* rows of per-workgroup partials the last step's reduce launch was given (DUAL: the grid's rows; the tree's
                                       * are chosen on the device); 0 before the first step.  First device */
-#define OA_ACC_CANON            1   /* k_pair_accumulate_canon behind a search: one thread per (slot, lane of the query) */
+#define OA_STAT_TARGET_CLEANED 51   /* vertices the last oa_target_outliers(apply) removed from the resident target; 0 after a plain upload */
+#define OA_ACC_CANON            1  /* k_pair_accumulate_canon behind a search: one thread per (slot, lane of the query) */
 #define OA_ACC_STRIDE           2   /* the grid-stride k_pair_accumulate */
 #define OA_ACC_WEIGHTED         3   /* k_pair_accumulate_weighted */
 #define OA_ACC_PLANE            4   /* k_pair_accumulate_plane; OA_METRIC_SYMMETRIC: its sibling k_pair_accumulate_symm (the same row and epilogue) */

@@ -29,6 +29,24 @@ def orient_normals(xyz, normals, k=8, max_dist=0.0, seed="away", point=None, dev
         return eng.orient_target_normals(k=k, max_dist=max_dist, seed=seed, point=point, normals=normals, install=False)
 
 
+def remove_outliers(xyz, method="statistical", k=16, std_ratio=2.0, radius=0.0, min_neighbors=8, count_cap=0, device=0):
+    """Stray points of ANY point cloud, found on the GPU (IcpEngine.target_outliers says how): a dict with "xyz" (the kept points,
+    float32, in the caller's order), "index" (their indices, ascending), "keep" uint8 (n,), "score" or "count", and "report".
+    Opens a context of its own on `device`, uploads xyz as its target and closes."""
+    import numpy as np
+    from .engine import IcpEngine, _outlier_args
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or len(xyz) < 2:
+        raise ValueError("remove_outliers: xyz must be (n >= 2, 3), got shape %s" % (xyz.shape,))
+    _outlier_args(method, k, std_ratio, radius, min_neighbors, count_cap, n=len(xyz), name="remove_outliers")
+    with IcpEngine(int(device)) as eng:
+        eng.set_target(xyz)
+        out = eng.target_outliers(method=method, k=k, std_ratio=std_ratio, radius=radius, min_neighbors=min_neighbors,
+                                  count_cap=count_cap, apply=False)
+    out["xyz"] = xyz[out["index"]]
+    return out
+
+
 def fpfh(xyz, normals=None, k=16, normal_k=16, device=0):
     """Fast Point Feature Histograms of ANY point cloud (the source's included), computed on the GPU: (n, 33) float32, an
     all-zero row meaning "no descriptor".  Opens a context of its own on `device` and uploads xyz as its target; without

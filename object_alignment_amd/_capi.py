@@ -61,6 +61,9 @@ OA_STAT_BOUNDARY_VERTICES = 47
 OA_STAT_BOUNDARY_EDGES = 48
 OA_STAT_ACC_PATH = 49
 OA_STAT_ACC_ROWS = 50
+OA_STAT_TARGET_CLEANED = 51
+OA_OUTLIER_STATISTICAL = 0
+OA_OUTLIER_RADIUS = 1
 (OA_ACC_CANON, OA_ACC_STRIDE, OA_ACC_WEIGHTED, OA_ACC_PLANE, OA_ACC_GICP, OA_ACC_FUSED_GRID, OA_ACC_FUSED_TRI_GRID, OA_ACC_FUSED_TREE,
  OA_ACC_FUSED_TRI_TREE, OA_ACC_DUAL) = range(1, 11)
 
@@ -87,6 +90,7 @@ SYMBOLS = [
     "oa_target_boundary", "oa_set_reject_boundary",
     "oa_normal_space_sample", "oa_stability",
     "oa_orient_target_normals",
+    "oa_target_outliers", "oa_target_radius_count",
 ]
 
 
@@ -155,6 +159,16 @@ class StabilityReport(C.Structure):
 class OrientReport(C.Structure):
     _fields_ = [("n_components", C.c_int64), ("n_left_out", C.c_int64), ("n_flipped", C.c_int64), ("rounds", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class OutlierSettings(C.Structure):
+    _fields_ = [("method", C.c_int32), ("k", C.c_int32), ("std_ratio", C.c_double), ("radius", C.c_double),
+                ("min_neighbors", C.c_int32), ("count_cap", C.c_int32)]
+
+
+class OutlierReport(C.Structure):
+    _fields_ = [("n_kept", C.c_int64), ("n_removed", C.c_int64), ("n_nonfinite", C.c_int64), ("mean", C.c_double),
+                ("std", C.c_double), ("threshold", C.c_double)]
 
 
 class OaError(RuntimeError):
@@ -268,6 +282,9 @@ def load(experiments: bool = False):
     L.oa_stability.argtypes = [vp, vp, vp, C.c_int64, C.c_int, ip, C.c_int64, C.POINTER(StabilityReport)]
     L.oa_orient_target_normals.argtypes = [vp, C.c_int, C.c_double, C.c_int, fp, fp, C.c_int, fp, C.POINTER(C.c_uint8), i32p,
                                            C.POINTER(OrientReport)]
+    L.oa_target_outliers.argtypes = [vp, C.POINTER(OutlierSettings), C.c_int, C.POINTER(C.c_uint8), dp, i32p, i32p,
+                                     C.POINTER(OutlierReport)]
+    L.oa_target_radius_count.argtypes = [vp, C.c_double, C.c_int32, i32p]
     _libs[experiments] = L
     return L
 

@@ -9,6 +9,7 @@
 #include "oa_bvh.hpp"
 #include "oa_pose.hpp"
 #include "oa_knn.hpp"
+#include "oa_outlier.hpp"
 #include "oa_feat.hpp"
 #include "oa_affine.hpp"
 #include "oa_recip.hpp"

@@ -27,6 +27,7 @@
 #define OA_SIG_BVH_SEARCH const DevState *, const float4 *, int, BvhParams, const float4 *, const float4 *, const float4 *, int *, float4 *, unsigned long long *, const int *, const int *, int, NormalTest, double *, const float *, uint2 *
 #define OA_SIG_POSE_SCORE PoseBase, const float *, const float *, const float4 *, const int *, int, int, BvhParams, const float4 *, const float4 *, const float4 *, double *
 #define OA_SIG_BVH_KNN BvhParams, const float4 *, const float4 *, int, int32_t *, float *, const float *, KnnOrient, float *, float *
+#define OA_SIG_BVH_RADIUS_COUNT BvhParams, const float4 *, const float4 *, float, int, int32_t *
 #define OA_SIG_FPFH const float *, const float *, const int32_t *, int, int, double *, float *
 #define OA_SIG_MATCH_FEATURES const float *, const float *, const float *, int, int, int, unsigned long long *, unsigned long long *, float *
 #define OA_SIG_TRIPLE_POSES const int *, const int *, int, const int *, int, const float4 *, const float *, Mat4f, Mat4f, Mat4d, double, double, float *, int *
@@ -88,7 +89,10 @@
     OA_K(X, k_pose_score, OA_SIG_POSE_SCORE, true, false) OA_K(X, k_pose_score, OA_SIG_POSE_SCORE, true, true)
 
 // ---- k nearest target vertices of every target vertex / PCA normals from them (oa_knn.hpp): oa_fam_knn.hip ----------
-#define OA_FAMILY_KNN(X) OA_K(X, k_bvh_knn, OA_SIG_BVH_KNN, false) OA_K(X, k_bvh_knn, OA_SIG_BVH_KNN, true)
+// (+ the fixed-radius count of oa_outlier.hpp; its k_bvh_knn_score is a plain kernel that oa_outlier.hpp defines in this unit
+//  alone and declares everywhere else)
+#define OA_FAMILY_KNN(X) OA_K(X, k_bvh_knn, OA_SIG_BVH_KNN, false) OA_K(X, k_bvh_knn, OA_SIG_BVH_KNN, true)                   \
+    OA_K(X, k_bvh_radius_count, OA_SIG_BVH_RADIUS_COUNT, false) OA_K(X, k_bvh_radius_count, OA_SIG_BVH_RADIUS_COUNT, true)
 
 // ---- nearest rows in descriptor space / poses from triples of matched points (oa_feat.hpp): oa_fam_feat.hip -----------
 #define OA_FAMILY_FEAT(X)                                                                                               \

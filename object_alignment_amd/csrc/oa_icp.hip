@@ -380,6 +380,7 @@ struct oa_target {
     long long bnd_n_vertices = 0, bnd_n_edges = 0;                  // OA_STAT_BOUNDARY_VERTICES / _EDGES
     DevBuf<int> d_corner_order; DevBuf<long long> d_corner_row;     // the mesh's corners by vertex (CSR rows): the pseudo-normals and the
     bool corner_ok = false;                                         // boundary share them
+    long long cleaned = 0;                                          // OA_STAT_TARGET_CLEANED: what oa_target_outliers(apply) removed to get here
 };
 
 // The source shard: source_reset forgets all of it.
@@ -4273,6 +4274,7 @@ OA_EXPORT int oa_get_stat(oa_ctx *c, int what, double *value)
     case OA_STAT_BOUNDARY_VERTICES: *value = c->tgt.bnd_ok ? (double)c->tgt.bnd_n_vertices : 0.0; return OA_OK;
     case OA_STAT_BOUNDARY_EDGES: *value = c->tgt.bnd_ok ? (double)c->tgt.bnd_n_edges : 0.0; return OA_OK;
     case OA_STAT_MESH_PSEUDONORMALS: *value = (c->tgt.surface && c->tgt.pn_ok) ? 1.0 : 0.0; return OA_OK;
+    case OA_STAT_TARGET_CLEANED: *value = (double)c->tgt.cleaned; return OA_OK;
     default: return fail(OA_E_BAD_ARG, "oa_get_stat: unknown key %d", what);
     }
 }
@@ -5411,6 +5413,154 @@ OA_EXPORT int oa_estimate_target_normals(oa_ctx *c, int k, int orient, const flo
     if (out_normals) HIPCHK(hipMemcpyAsync(out_normals, d_n, sizeof(float) * 3 * nt, hipMemcpyDeviceToHost, c->stream));
     if (out_curvature) HIPCHK(hipMemcpyAsync(out_curvature, d_curv.p, sizeof(float) * nt, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
+// ================================================================================================
+// stray points of a point-cloud target: fixed-radius counts, mean k-nearest distances, removal (EXTENSION; oa_outlier.hpp)
+// ================================================================================================
+namespace {
+// what both calls check and do first (knn_call_begin without its k); a running sequence ends the way oa_target_knn ends one
+int outlier_call_begin(oa_ctx *c, const char *who)
+{
+    if (c->tgt.nt <= 0) return fail(OA_E_STATE, "%s: call oa_set_target first", who);
+    if (c->tgt.surface) return fail(OA_E_STATE, "%s: a surface target (oa_set_target_mesh) has no stray vertices to look for; upload a cloud", who);
+    const int rc = use_device(c);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->loop_active = false;
+    return OA_OK;
+}
+
+int radius_count_launch(oa_ctx *c, const KnnTree &t, double radius, int cap, int32_t *d_count)
+{
+    const float rf = (float)radius, r2 = rf * rf;
+    const int wpb = oa::KNN_WPB, leaves = t.bp.cnt[1];
+    const unsigned blocks = (unsigned)std::max(1, std::min((leaves + wpb - 1) / wpb, c->n_cu * 32));
+    if (cap > 0) hipLaunchKernelGGL((oa::k_bvh_radius_count<true>), dim3(blocks), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, r2, cap, d_count);
+    else hipLaunchKernelGGL((oa::k_bvh_radius_count<false>), dim3(blocks), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, r2, 0, d_count);
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+
+int knn_score_launch(oa_ctx *c, const KnnTree &t, int k, double *d_score)
+{
+    const int k1 = k + 1, wpb = oa::KNN_WPB, leaves = t.bp.cnt[1];
+    const unsigned blocks = (unsigned)std::max(1, std::min((leaves + wpb - 1) / wpb, c->n_cu * 32));
+    hipLaunchKernelGGL(oa::k_bvh_knn_score, dim3(blocks), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, k1, d_score);
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+}  // namespace
+
+OA_EXPORT int oa_target_radius_count(oa_ctx *c, double radius, int32_t cap, int32_t *count)
+{
+    static const char who[] = "oa_target_radius_count";
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    OA_NOT_MULTI(c, "oa_target_radius_count");
+    if (!(radius > 0.0) || !(radius < (double)INFINITY)) return fail(OA_E_BAD_ARG, "%s: radius = %g (finite and > 0)", who, radius);
+    if (cap < 0) return fail(OA_E_BAD_ARG, "%s: cap = %d (>= 0; 0: no cap)", who, (int)cap);
+    int rc = outlier_call_begin(c, who);
+    if (rc) return rc;
+    KnnTree tree;
+    if ((rc = knn_tree(c, tree))) return rc;
+    const size_t nt = (size_t)c->tgt.nt;
+    DevTmp<int32_t> d_count;
+    HIPCHK(d_count.alloc(nt));
+    if ((rc = radius_count_launch(c, tree, radius, cap, d_count.p))) return rc;
+    if (count) HIPCHK(hipMemcpyAsync(count, d_count.p, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
+OA_EXPORT int oa_target_outliers(oa_ctx *c, const oa_outlier_settings *s, int apply, uint8_t *keep, double *score, int32_t *count,
+                                 int32_t *kept_index, oa_outlier_report *rep)
+{
+    static const char who[] = "oa_target_outliers";
+    if (!c || !s) return fail(OA_E_BAD_ARG, "%s: null argument", who);
+    OA_NOT_MULTI(c, "oa_target_outliers");
+    if (rep) memset(rep, 0, sizeof *rep);
+    const bool statistical = s->method == OA_OUTLIER_STATISTICAL;
+    if (!statistical && s->method != OA_OUTLIER_RADIUS)
+        return fail(OA_E_BAD_ARG, "%s: method %d (use OA_OUTLIER_STATISTICAL / OA_OUTLIER_RADIUS)", who, (int)s->method);
+    if (statistical) {
+        if (s->k < 1 || s->k > oa::KNN_MAX_K - 1) return fail(OA_E_BAD_ARG, "%s: k = %d outside 1 .. %d", who, (int)s->k, oa::KNN_MAX_K - 1);
+        if (!(s->std_ratio >= 0.0) || !(s->std_ratio < (double)INFINITY)) return fail(OA_E_BAD_ARG, "%s: std_ratio = %g (finite and >= 0)", who, s->std_ratio);
+    } else {
+        if (!(s->radius > 0.0) || !(s->radius < (double)INFINITY)) return fail(OA_E_BAD_ARG, "%s: radius = %g (finite and > 0)", who, s->radius);
+        if (s->min_neighbors < 1) return fail(OA_E_BAD_ARG, "%s: min_neighbors = %d (>= 1)", who, (int)s->min_neighbors);
+        if (s->count_cap != 0 && (long long)s->count_cap < (long long)s->min_neighbors + 1)
+            return fail(OA_E_BAD_ARG, "%s: count_cap = %d (0: exact counts, or >= min_neighbors + 1 = %lld)", who, (int)s->count_cap, (long long)s->min_neighbors + 1);
+    }
+    int rc = outlier_call_begin(c, who);
+    if (rc) return rc;
+    const int nt = c->tgt.nt;
+    if (statistical && s->k > nt - 1) return fail(OA_E_BAD_ARG, "%s: k = %d outside 1 .. min(%d, %d target vertices - 1)", who, (int)s->k, oa::KNN_MAX_K - 1, nt);
+    KnnTree tree;
+    if ((rc = knn_tree(c, tree))) return rc;
+    const size_t snt = (size_t)nt;
+    const float *d_xyz = c->tgt.d_tgt_xyz;
+    // 1. the per-vertex figure
+    DevTmp<double> d_score;
+    DevTmp<int32_t> d_count;
+    DevTmp<oa::OutlierStats> d_st;
+    HIPCHK(d_st.alloc(1));
+    HIPCHK(hipMemsetAsync(d_st.p, 0, sizeof(oa::OutlierStats), c->stream));
+    if (statistical) {
+        HIPCHK(d_score.alloc(snt));
+        if ((rc = knn_score_launch(c, tree, s->k, d_score.p))) return rc;
+        // 2. mean, standard deviation and threshold of the finite scores: two passes, rows then one workgroup
+        const int rows = oa::outlier_rows((long long)nt);
+        DevTmp<double> d_row_sum;
+        DevTmp<long long> d_row_n;
+        HIPCHK(d_row_sum.alloc((size_t)rows)); HIPCHK(d_row_n.alloc((size_t)rows));
+        const dim3 blk(oa::OUT_THREADS);
+        hipLaunchKernelGGL((oa::k_outlier_rows<0>), dim3((unsigned)rows), blk, 0, c->stream, (const double *)d_score.p, (long long)nt, (const oa::OutlierStats *)d_st.p,
+                           d_row_sum.p, d_row_n.p);
+        hipLaunchKernelGGL((oa::k_outlier_finish<0>), dim3(1), blk, 0, c->stream, (const double *)d_row_sum.p, (const long long *)d_row_n.p, rows, s->std_ratio, d_st.p);
+        hipLaunchKernelGGL((oa::k_outlier_rows<1>), dim3((unsigned)rows), blk, 0, c->stream, (const double *)d_score.p, (long long)nt, (const oa::OutlierStats *)d_st.p,
+                           d_row_sum.p, d_row_n.p);
+        hipLaunchKernelGGL((oa::k_outlier_finish<1>), dim3(1), blk, 0, c->stream, (const double *)d_row_sum.p, (const long long *)d_row_n.p, rows, s->std_ratio, d_st.p);
+        HIPCHK(hipGetLastError());
+    } else {
+        HIPCHK(d_count.alloc(snt));
+        if ((rc = radius_count_launch(c, tree, s->radius, s->count_cap, d_count.p))) return rc;
+    }
+    // 3. flags, their scan, the kept vertices in ascending order (and, to apply, their coordinates)
+    DevTmp<int> d_flag;
+    DevTmp<unsigned char> d_keep;
+    DevTmp<long long> d_off;
+    DevTmp<int32_t> d_index;
+    DevTmp<float> d_kept_xyz;
+    DevTmp<char> scan_tmp;
+    HIPCHK(d_flag.alloc(snt)); HIPCHK(d_keep.alloc(snt)); HIPCHK(d_off.alloc(snt + 1)); HIPCHK(d_index.alloc(snt));
+    if (apply) HIPCHK(d_kept_xyz.alloc(3 * snt));
+    const unsigned v_blocks = (unsigned)((snt + oa::OUT_THREADS - 1) / oa::OUT_THREADS);
+    hipLaunchKernelGGL(oa::k_outlier_flags, dim3(v_blocks), dim3(oa::OUT_THREADS), 0, c->stream, statistical ? oa::OUT_STATISTICAL : oa::OUT_RADIUS, (const double *)d_score.p,
+                       (const int32_t *)d_count.p, d_xyz, nt, (int)s->min_neighbors, d_st.p, d_flag.p, d_keep.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = scan_counts(c, d_flag.p, nt, d_off.p, scan_tmp))) return rc;
+    hipLaunchKernelGGL(oa::k_outlier_compact, dim3(v_blocks), dim3(oa::OUT_THREADS), 0, c->stream, (const int *)d_flag.p, (const long long *)d_off.p, nt, d_xyz, d_index.p,
+                       d_kept_xyz.p, d_st.p);
+    HIPCHK(hipGetLastError());
+    oa::OutlierStats st;
+    if ((rc = read_small(c, &st, d_st.p, sizeof st))) return rc;   // (waits for everything above)
+    if (st.n_kept < 0 || st.n_kept > nt) return fail(OA_E_HIP, "%s: %lld of %d vertices kept (internal)", who, st.n_kept, nt);
+    if (keep) HIPCHK(hipMemcpyAsync(keep, d_keep.p, snt, hipMemcpyDeviceToHost, c->stream));
+    if (score && statistical) HIPCHK(hipMemcpyAsync(score, d_score.p, sizeof(double) * snt, hipMemcpyDeviceToHost, c->stream));
+    if (count && !statistical) HIPCHK(hipMemcpyAsync(count, d_count.p, sizeof(int32_t) * snt, hipMemcpyDeviceToHost, c->stream));
+    if (kept_index && st.n_kept > 0) HIPCHK(hipMemcpyAsync(kept_index, d_index.p, sizeof(int32_t) * (size_t)st.n_kept, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (rep) {
+        rep->n_kept = (int64_t)st.n_kept; rep->n_removed = (int64_t)nt - (int64_t)st.n_kept; rep->n_nonfinite = (int64_t)st.n_nonfinite;
+        if (statistical) { rep->mean = st.mean; rep->std = st.std; rep->threshold = st.threshold; }
+    }
+    if (!apply) return OA_OK;
+    if (st.n_kept < 1) return fail(OA_E_TOO_FEW_PAIRS, "%s: no vertex of %d would be kept; the target stays as it is", who, nt);
+    // 4. the kept vertices become the target, as an upload from device memory would make them (the tree of this call goes with the old one)
+    const long long removed = (long long)nt - st.n_kept;
+    if ((rc = set_target_common(c, d_kept_xyz.p, (int64_t)st.n_kept, 1, true))) return rc;
+    c->tgt.cleaned = removed;
     return OA_OK;
 }
 

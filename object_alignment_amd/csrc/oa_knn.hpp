@@ -17,6 +17,8 @@
 //                    PCA = true : the rows are parked in LDS (64 queries x k indices per wave); when the leaf is done LANE q
 //                    solves QUERY q -- mean, centred covariance (fp64, both summed in list order), cyclic Jacobi, smallest
 //                    eigenpair, sign rule -- so the eigen-solves of a leaf run 64 wide.
+//                    The per-query list is knn_wave_list, a __device__ function of its own: k_bvh_knn_score (oa_outlier.hpp) sums
+//                    the same list instead of writing it out.
 //   k_bbox_finite    bounding box of the finite coordinates (the Morton frame of a tree over a target that has others)
 //
 // Exactness of the cut-off: a box is skipped only when lb (1 - 1e-5) - 1e-30 > d2_k, d2_k = the k-th best squared distance so
@@ -136,6 +138,85 @@ __host__ __device__ inline void pca_normal(const double C[6], double vx, double 
     curv_out = (float)(l0c / tot);
 }
 
+// The list of ONE query by ONE wave (all 64 lanes call it together; p, leaf and k are wave-uniform): lane j returns the j-th best
+// key of query p, whose own leaf is `leaf` (its 64 vertices: `mine`, one per lane, original index my_idx).  Entries past the
+// last finite distance are KNN_EMPTY.  lds: this wave's scratch (bvh_wave_query's).  1 <= k <= 64.
+__device__ __forceinline__ unsigned long long knn_wave_list(const BvhParams &bp, const float4 *__restrict__ boxes, const float4 *__restrict__ prims,
+                                                            const BvhLds &lds, int leaf, const float4 mine, uint32_t my_idx, const float *p, int k,
+                                                            int lane)
+{
+    const int top = bp.levels;
+    // the list starts as the query's own leaf: the cut-off is tight at once
+    unsigned long long key;
+    {
+        const float d = d2_metric(p[0], p[1], p[2], mine.x, mine.y, mine.z);
+        key = (d < INFINITY && my_idx != IDX_NONE) ? (((unsigned long long)__float_as_uint(d) << 32) | my_idx) : KNN_EMPTY;
+        key = knn_wave_sort(key, lane);
+    }
+    unsigned long long kth = knn_lane_u64(key, k - 1);
+    float lim = __uint_as_float((uint32_t)(kth >> 32));
+    const bool finite = fabsf(p[0]) < INFINITY && fabsf(p[1]) < INFINITY && fabsf(p[2]) < INFINITY;
+    int level = top, node = 0;
+    bool fresh = true;
+    while (finite) {                                         // (a non-finite query has no finite distance: its list stays empty)
+        if (fresh) {
+            const long long ch = (long long)node * BVH_W + lane;
+            float lb = INFINITY;
+            bool pass = false;
+            if (ch < bp.cnt[level]) {
+                const float4 lo = boxes[2 * ((long long)bp.off[level] + ch)], hi = boxes[2 * ((long long)bp.off[level] + ch) + 1];
+                lb = bvh_box_bound<false>(p, lo, hi, 0.0);
+                pass = lb < INFINITY && !bvh_prune(lb, lim);
+                if (level == 1 && ch == leaf) pass = false;  // the own leaf is in the list already
+            }
+            lds.lb(level)[lane] = lb;
+            const unsigned long long m = __ballot(pass);
+            if (lane == 0) { *lds.mask(level) = m; *lds.node(level) = node; }
+            fresh = false;
+        }
+        const unsigned long long m = *lds.mask(level);
+        if (m == 0ull) {
+            if (level == top) break;
+            ++level;
+            continue;
+        }
+        const bool member = (m >> lane) & 1ull;
+        const uint32_t lbits = member ? __float_as_uint(lds.lb(level)[lane]) : 0xFFFFFFFFu;   // bounds are >= +0
+        const uint32_t mb = wave_min_u32(lbits);
+        if (bvh_prune(__uint_as_float(mb), lim)) {            // the nearest candidate is out: so are the others
+            if (lane == 0) *lds.mask(level) = 0ull;
+            continue;
+        }
+        const unsigned long long eq = __ballot(member && lbits == mb);
+        const int pick = __ffsll((long long)eq) - 1;
+        if (lane == 0) *lds.mask(level) = m & ~(1ull << pick);
+        const long long child = (long long)*lds.node(level) * BVH_W + pick;
+        if (level > 1) {
+            --level;
+            node = (int)child;
+            fresh = true;
+            continue;
+        }
+        // leaf: 64 vertices, one per lane; those below the k-th key enter the list one at a time
+        const float4 c4 = prims[child * BVH_W + lane];
+        const float d = d2_metric(p[0], p[1], p[2], c4.x, c4.y, c4.z);
+        const uint32_t ci = __float_as_uint(c4.w);
+        const unsigned long long ck = (d < INFINITY && ci != IDX_NONE) ? (((unsigned long long)__float_as_uint(d) << 32) | ci) : KNN_EMPTY;
+        unsigned long long cand = __ballot(ck < kth);
+        while (cand) {
+            const int b = __ffsll((long long)cand) - 1;
+            cand &= cand - 1;
+            const unsigned long long cnew = knn_lane_u64(ck, b);
+            if (!(cnew < kth)) continue;                     // (the k-th key has moved since the ballot)
+            const unsigned long long up = __shfl_up(key, 1, 64);
+            if (key > cnew) key = (lane > 0 && up > cnew) ? up : cnew;
+            kth = knn_lane_u64(key, k - 1);
+        }
+        lim = __uint_as_float((uint32_t)(kth >> 32));
+    }
+    return key;
+}
+
 // Launch: 64 * knn_waves_per_block(k) threads, any number of workgroups (the leaves are dealt wave by wave, grid stride).
 // out_idx / out_d2 (nt x k, the caller's vertex order, original indices; unfilled entries -1 / +inf) may be null.
 // PCA: xyz = the target in the caller's order (nt x 3), out_n (nt x 3) / out_curv (nt), each may be null.
@@ -154,7 +235,6 @@ __global__ __launch_bounds__(KNN_WPB * 64) void k_bvh_knn(BvhParams bp, const fl
     const BvhLds lds{ &s_lb[w][0][0], BVH_W, &s_mask[w][0], 1, &s_node[w][0], 1 };
     const int rstride = k | 1;
     int *const rows = PCA ? &s_rows[w * 64 * rstride] : nullptr;
-    const int top = bp.levels;
     if (PCA && (w + 1) * 64 * rstride > KNN_ROWS_INTS) return;      // (launched with more waves than the parked rows hold)
 
     for (int leaf = blockIdx.x * wpb + w; leaf < bp.cnt[1]; leaf += gridDim.x * wpb) {     // (wave-uniform)
@@ -164,74 +244,7 @@ __global__ __launch_bounds__(KNN_WPB * 64) void k_bvh_knn(BvhParams bp, const fl
             const uint32_t qi = (uint32_t)__builtin_amdgcn_readlane((int)my_idx, q);
             if (qi == IDX_NONE) break;                               // padding closes the last leaf
             const float p[3] = { knn_lane_f(mine.x, q), knn_lane_f(mine.y, q), knn_lane_f(mine.z, q) };
-            // the list starts as the query's own leaf: the cut-off is tight at once
-            unsigned long long key;
-            {
-                const float d = d2_metric(p[0], p[1], p[2], mine.x, mine.y, mine.z);
-                key = (d < INFINITY && my_idx != IDX_NONE) ? (((unsigned long long)__float_as_uint(d) << 32) | my_idx) : KNN_EMPTY;
-                key = knn_wave_sort(key, lane);
-            }
-            unsigned long long kth = knn_lane_u64(key, k - 1);
-            float lim = __uint_as_float((uint32_t)(kth >> 32));
-            const bool finite = fabsf(p[0]) < INFINITY && fabsf(p[1]) < INFINITY && fabsf(p[2]) < INFINITY;
-            int level = top, node = 0;
-            bool fresh = true;
-            while (finite) {                                         // (a non-finite query has no finite distance: its list stays empty)
-                if (fresh) {
-                    const long long ch = (long long)node * BVH_W + lane;
-                    float lb = INFINITY;
-                    bool pass = false;
-                    if (ch < bp.cnt[level]) {
-                        const float4 lo = boxes[2 * ((long long)bp.off[level] + ch)], hi = boxes[2 * ((long long)bp.off[level] + ch) + 1];
-                        lb = bvh_box_bound<false>(p, lo, hi, 0.0);
-                        pass = lb < INFINITY && !bvh_prune(lb, lim);
-                        if (level == 1 && ch == leaf) pass = false;  // the own leaf is in the list already
-                    }
-                    lds.lb(level)[lane] = lb;
-                    const unsigned long long m = __ballot(pass);
-                    if (lane == 0) { *lds.mask(level) = m; *lds.node(level) = node; }
-                    fresh = false;
-                }
-                const unsigned long long m = *lds.mask(level);
-                if (m == 0ull) {
-                    if (level == top) break;
-                    ++level;
-                    continue;
-                }
-                const bool member = (m >> lane) & 1ull;
-                const uint32_t lbits = member ? __float_as_uint(lds.lb(level)[lane]) : 0xFFFFFFFFu;   // bounds are >= +0
-                const uint32_t mb = wave_min_u32(lbits);
-                if (bvh_prune(__uint_as_float(mb), lim)) {            // the nearest candidate is out: so are the others
-                    if (lane == 0) *lds.mask(level) = 0ull;
-                    continue;
-                }
-                const unsigned long long eq = __ballot(member && lbits == mb);
-                const int pick = __ffsll((long long)eq) - 1;
-                if (lane == 0) *lds.mask(level) = m & ~(1ull << pick);
-                const long long child = (long long)*lds.node(level) * BVH_W + pick;
-                if (level > 1) {
-                    --level;
-                    node = (int)child;
-                    fresh = true;
-                    continue;
-                }
-                // leaf: 64 vertices, one per lane; those below the k-th key enter the list one at a time
-                const float4 c4 = prims[child * BVH_W + lane];
-                const float d = d2_metric(p[0], p[1], p[2], c4.x, c4.y, c4.z);
-                const uint32_t ci = __float_as_uint(c4.w);
-                const unsigned long long ck = (d < INFINITY && ci != IDX_NONE) ? (((unsigned long long)__float_as_uint(d) << 32) | ci) : KNN_EMPTY;
-                unsigned long long cand = __ballot(ck < kth);
-                while (cand) {
-                    const int b = __ffsll((long long)cand) - 1;
-                    cand &= cand - 1;
-                    const unsigned long long cnew = knn_lane_u64(ck, b);
-                    if (!(cnew < kth)) continue;                     // (the k-th key has moved since the ballot)
-                    const unsigned long long up = __shfl_up(key, 1, 64);
-                    if (key > cnew) key = (lane > 0 && up > cnew) ? up : cnew;
-                    kth = knn_lane_u64(key, k - 1);
-                }
-                lim = __uint_as_float((uint32_t)(kth >> 32));
-            }
+            const unsigned long long key = knn_wave_list(bp, boxes, prims, lds, leaf, mine, my_idx, p, k, lane);
             if (lane < k) {
                 const int32_t ni = (int32_t)(uint32_t)key;           // IDX_NONE -> -1
                 if (out_idx) out_idx[(long long)qi * k + lane] = ni;

@@ -176,6 +176,46 @@ def _orient_args(k=8, max_dist=0.0, seed="away", point=None, normals=None, n=Non
     return k, float(max_dist), int(seed), point, normals
 
 
+OUTLIER_METHODS = {"statistical": capi.OA_OUTLIER_STATISTICAL, "radius": capi.OA_OUTLIER_RADIUS}
+
+
+def _real(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def _outlier_args(method="statistical", k=16, std_ratio=2.0, radius=0.0, min_neighbors=8, count_cap=0, n=None,
+                  name="target_outliers"):
+    """The arguments of an outlier filter, checked before any call reaches the library: (method, k, std_ratio, radius,
+    min_neighbors, count_cap), with the other method's fields left at values the library ignores.  n: the number of vertices,
+    when it is known."""
+    if isinstance(method, str):
+        if method not in OUTLIER_METHODS:
+            raise ValueError("%s: method %r (use 'statistical' or 'radius')" % (name, method))
+        method = OUTLIER_METHODS[method]
+    elif isinstance(method, bool) or not isinstance(method, (int, np.integer)) or method not in (0, 1):
+        raise ValueError("%s: method %r (use 'statistical' or 'radius')" % (name, method))
+    if method == capi.OA_OUTLIER_STATISTICAL:
+        k = _whole(k, name, "k", 1, 63)
+        if n is not None and k > n - 1:
+            raise ValueError("%s: k = %d for %d vertices (1 .. min(63, n - 1))" % (name, k, n))
+        if not _real(std_ratio) or not 0 <= std_ratio < float("inf"):
+            raise ValueError("%s: std_ratio = %r (finite and >= 0)" % (name, std_ratio))
+        return int(method), k, float(std_ratio), 0.0, 1, 0
+    if not _real(radius) or not 0 < radius < float("inf"):
+        raise ValueError("%s: radius = %r (finite and > 0)" % (name, radius))
+    min_neighbors = _whole(min_neighbors, name, "min_neighbors", 1, 2**31 - 2)
+    count_cap = _whole(count_cap, name, "count_cap", 0, 2**31 - 1)
+    if count_cap != 0 and count_cap < min_neighbors + 1:
+        raise ValueError("%s: count_cap = %d (0: exact counts, or >= min_neighbors + 1 = %d)" % (name, count_cap, min_neighbors + 1))
+    return int(method), 1, 0.0, float(radius), min_neighbors, count_cap
+
+
+def _radius_count_args(radius, cap=0, name="target_radius_count"):
+    if not _real(radius) or not 0 < radius < float("inf"):
+        raise ValueError("%s: radius = %r (finite and > 0)" % (name, radius))
+    return float(radius), _whole(cap, name, "cap", 0, 2**31 - 1)
+
+
 DEVIATION_OUTPUTS = ("signed_d", "dist", "closest", "idx", "feature")
 DEVIATION_SIGNED = {"auto": -1, "never": 0, "required": 1, None: -1, False: 0, True: 1}
 
@@ -432,6 +472,46 @@ class IcpEngine:
         report = {name: int(getattr(rep, name)) for name, _ in capi.OrientReport._fields_ if name != "reserved"}
         return out[: self.n_target], flipped[: self.n_target], comp[: self.n_target], report
 
+    def target_radius_count(self, radius, cap=0):
+        """Vertex-mode targets: for every target vertex the number of target vertices within `radius` of it (the target's own
+        units; the float32 metric against (float32 radius)^2), itself included: int32 (nt,).  cap > 0: counts saturate there
+        and the search of a vertex stops when it is reached.  A vertex with a non-finite coordinate counts 0."""
+        radius, cap = _radius_count_args(radius, cap)
+        count = np.empty(max(1, self.n_target), np.int32)
+        self._chk(self._L.oa_target_radius_count(self._h, radius, cap, count.ctypes.data_as(C.POINTER(C.c_int32))))
+        return count[: self.n_target]
+
+    def target_outliers(self, method="statistical", k=16, std_ratio=2.0, radius=0.0, min_neighbors=8, count_cap=0, apply=False):
+        """Vertex-mode targets: which vertices are stray points.  method 'statistical': a vertex stays when the mean distance to
+        its k nearest other vertices is at most mean + std_ratio * std of that figure over the cloud; 'radius': when at least
+        min_neighbors other vertices lie within `radius` (the target's own units; count_cap > 0 lets the counts saturate there).
+        Returns {"keep": uint8 (nt,), "score": float64 (nt,) or "count": int32 (nt,), "index": int32 (n_kept,) -- the kept vertices,
+        ascending --, "report": dict}.  apply: the kept vertices become the target, exactly as set_target(xyz[keep]) would make
+        them (normals, descriptors and boundary masks of the old target are forgotten); stat("target_cleaned") then holds the
+        number removed."""
+        method, k, std_ratio, radius, min_neighbors, count_cap = _outlier_args(method, k, std_ratio, radius, min_neighbors, count_cap,
+                                                                                 n=self.n_target or None)
+        n = max(1, self.n_target)
+        st = capi.OutlierSettings(method, k, std_ratio, radius, min_neighbors, count_cap)
+        rep = capi.OutlierReport()
+        keep = np.empty(n, np.uint8)
+        index = np.empty(n, np.int32)
+        statistical = method == capi.OA_OUTLIER_STATISTICAL
+        score = np.empty(n, np.float64) if statistical else None
+        count = None if statistical else np.empty(n, np.int32)
+        i32p = C.POINTER(C.c_int32)
+        nt = self.n_target
+        self._chk(self._L.oa_target_outliers(self._h, C.byref(st), int(bool(apply)), keep.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                             capi.dptr(score) if statistical else None, None if statistical else count.ctypes.data_as(i32p),
+                                             index.ctypes.data_as(i32p), C.byref(rep)))
+        report = {name: (int if name.startswith("n_") else float)(getattr(rep, name)) for name, _ in capi.OutlierReport._fields_}
+        out = {"keep": keep[:nt], "index": index[: report["n_kept"]].copy(), "report": report}
+        out["score" if statistical else "count"] = (score if statistical else count)[:nt]
+        if apply:
+            self.n_target = report["n_kept"]
+            self.target_owner = None
+        return out
+
     LOSSES = {"none": capi.OA_LOSS_NONE, "huber": capi.OA_LOSS_HUBER, "tukey": capi.OA_LOSS_TUKEY, "cauchy": capi.OA_LOSS_CAUCHY}
 
     def set_robust(self, loss, scale=0.0):
@@ -529,7 +609,7 @@ class IcpEngine:
              "reciprocal": 37, "reciprocal_ratio": 38, "recip_rejected": 39,
              "trim": 40, "trim_candidates": 41, "trim_kept": 42, "trim_cut": 43,
              "reject_boundary": 44, "boundary_rejected": 45, "target_boundary": 46, "boundary_vertices": 47, "boundary_edges": 48,
-             "acc_path": 49, "acc_rows": 50}
+             "acc_path": 49, "acc_rows": 50, "target_cleaned": 51}
     EXCHANGE_NAMES = {-1: None, 0: "mailbox (pinned host memory)", 1: "rccl", 2: "mailbox (peer-mapped device memory)"}
 
     def exchange_info(self):

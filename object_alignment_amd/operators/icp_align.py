@@ -23,6 +23,31 @@ except Exception:                                 # outside Blender it is a plai
 
 
 @dataclass
+class OutlierSettings:
+    """What IcpSettings.clean_target / clean_source remove before anything else looks at a cloud (IcpEngine.target_outliers'
+    arguments; checked here, before any engine opens).  method "statistical": a point stays when the mean distance to its k
+    nearest neighbours is at most mean + std_ratio * std of that figure over the cloud; "radius": when at least min_neighbors other
+    points lie within `radius`.  Lengths are in world units, like min_start."""
+    method: str = "statistical"
+    k: int = 16
+    std_ratio: float = 2.0
+    radius: float = 0.0
+    min_neighbors: int = 8
+    count_cap: int = 0
+
+    def __post_init__(self):
+        from ..engine import _outlier_args
+        _outlier_args(**self.kwargs(1.0), name="OutlierSettings")
+
+    def kwargs(self, scale):
+        """The filter's arguments for a cloud whose local unit is `scale` world units (world_scale of its matrix)."""
+        from ..engine import _real
+        radius = self.radius / scale if _real(self.radius) else self.radius       # (anything else is for _outlier_args to refuse)
+        return dict(method=self.method, k=self.k, std_ratio=self.std_ratio, radius=radius, min_neighbors=self.min_neighbors,
+                    count_cap=self.count_cap)
+
+
+@dataclass
 class IcpSettings:
     """Names and defaults of the add-on preferences the loop reads (lib/preferences.py:31-72)."""
     icp_iterations: int = 50
@@ -96,6 +121,13 @@ class IcpSettings:
     # a uniform sample holds next to none of them.  Needs run(..., source_normals=...).  0 = off
     sample_normal_space: int = 0
     sample_normal_grid: int = 8
+    # nor these: an OutlierSettings removes the stray points of a raw scan -- flying pixels, dust, the scanner table -- before
+    # anything else looks at the cloud.  clean_target: the point-cloud target is cleaned on the device right after its upload
+    # (IcpEngine.target_outliers(apply=True)); normals are estimated, and every search runs, on what is left.  clean_source: the
+    # vertices vlist selects go through object_alignment_amd.remove_outliers first, and the removed ones leave the selection
+    # before sample_voxel thins it.  None = off.  One GPU
+    clean_target: object = None
+    clean_source: object = None
 
 
 @dataclass
@@ -353,6 +385,50 @@ def _host_rows(a):
     return np.asarray(a, np.float32).reshape(-1, 3)
 
 
+def clean_of(settings):
+    """(clean_target, clean_source) from IcpSettings: each an OutlierSettings or None."""
+    out = []
+    for name in ("clean_target", "clean_source"):
+        v = getattr(settings, name, None)
+        if v is not None and not isinstance(v, OutlierSettings):
+            raise TypeError("IcpSettings.%s = %r (an OutlierSettings, or None)" % (name, v))
+        out.append(v)
+    return tuple(out)
+
+
+def _local_scale(mx, what):
+    s = world_scale(mx)
+    if not (np.isfinite(s) and s > 0):
+        raise ValueError("%s needs an invertible matrix_world (scale %r)" % (what, s))
+    return s
+
+
+def clean_resident_target(engine, clean, mx_base):
+    """Remove the stray points of the engine's resident point-cloud target (IcpEngine.target_outliers(apply=True), lengths carried
+    from world units to the target's own by mx_base): {"index": the kept vertices in the caller's numbering, "keep", "report"}."""
+    call = getattr(engine, "target_outliers", None)
+    if call is None:
+        raise RuntimeError("this engine has no outlier removal")
+    out = call(apply=True, **clean.kwargs(_local_scale(mx_base, "clean_target")))
+    return {"index": out["index"], "keep": out["keep"], "report": out["report"]}
+
+
+def clean_selection(engine, clean, source_xyz, vlist, mx_align):
+    """The vertices vlist selects (None: all) without their stray points (object_alignment_amd.remove_outliers in a context of its
+    own, lengths carried to the source's own units by mx_align): {"vlist": what is left, as indices into source_xyz in vlist's
+    order, "index": the kept positions within the selection, "keep", "report"}."""
+    from .. import remove_outliers
+    scale = _local_scale(mx_align, "clean_source")
+    pts = _host_rows(source_xyz)
+    sel = None
+    if vlist is not None:
+        sel = np.ascontiguousarray(vlist, dtype=np.int64)
+        pts = pts[sel]
+    out = remove_outliers(pts, device=getattr(engine, "device", 0), **clean.kwargs(scale))
+    index = out["index"].astype(np.int64)
+    return {"vlist": sel[index] if sel is not None else index, "index": out["index"], "keep": out["keep"], "report": out["report"]}
+
+
 def normal_space_vlist(engine, source_xyz, source_normals, vlist, stride, m, grid, unoriented):
     """m of the vertices a loop over (vlist, stride) would use -- vlist[0::stride], None: every vertex --, drawn evenly across
     the buckets of their normals (IcpEngine.normal_space_sample): {"idx": their indices into source_xyz, in the candidates' order
@@ -462,6 +538,11 @@ class IcpAlign:
         (normal_space_vlist; n and -n share a bucket when the normals were estimated).  Needs source_normals (ValueError
         otherwise).  self.last_sampling holds the picked indices, the sampling report and the stability report of the picked set;
         None while the setting is off.
+        settings.clean_target / clean_source: an OutlierSettings each -- the point-cloud target loses its stray points right after
+        the upload (a target_normals array is gathered to what is left, an estimate sees only that; ValueError with target_tris),
+        the selection loses its own before sample_voxel.  self.last_cleaning = {"target": ..., "source": ...} holds the index maps
+        and reports (None for a side that was not cleaned); None while both settings are off.  An attached deviation report's idx
+        speaks of the caller's target vertices.
         deviation: a DeviationSettings -- after the loop the deviation report and its arrays are taken at the final pose on the same
         engine (over the points the loop used) and attached as RunResult.deviation; None: nothing else changes."""
         s = self.settings
@@ -479,16 +560,25 @@ class IcpAlign:
         consistent = normal_orient_of(s) == "consistent"
         if sample_normals > 0 and source_normals is None:
             raise ValueError("IcpSettings.sample_normal_space needs source_normals (an array of normals, or 'estimate')")
+        clean_target, clean_source = clean_of(s)
+        if clean_target is not None and target_tris is not None:
+            raise ValueError("IcpSettings.clean_target is for point-cloud targets: a mesh (target_tris) has no stray vertices to remove")
         thresh = s.min_start                                   # :83
         factor = round(1 / s.sample_fraction)                  # :89  (ZeroDivisionError at 0, as the reference)
         if not thresh > 0:
             # make_pairs returns None and `(A, B, d_stats) = None` raises   (:101, general.py:277)
             raise TypeError("cannot unpack non-iterable NoneType object")
         eng = self.engine
+        cleaning = {"target": None, "source": None}
+        self.last_cleaning = cleaning if (clean_target is not None or clean_source is not None) else None
         if target_tris is not None:
             eng.set_target_mesh(target_xyz, target_tris)
         else:
             eng.set_target(target_xyz)
+            if clean_target is not None:
+                cleaning["target"] = clean_resident_target(eng, clean_target, mx_base)
+                if target_normals is not None and not estimate:
+                    target_normals = np.asarray(target_normals).reshape(-1, 3)[cleaning["target"]["index"]]
             if estimate:
                 eng.estimate_target_normals(k=int(getattr(s, "normal_k", 16)), orient="away", install=True)
                 if consistent:
@@ -500,6 +590,9 @@ class IcpAlign:
         apply_reciprocal(eng, s)
         apply_trim(eng, s)
         apply_boundary(eng, s)
+        if clean_source is not None:
+            cleaning["source"] = clean_selection(eng, clean_source, source_xyz, vlist, mx_align)
+            vlist = cleaning["source"]["vlist"]
         if sample_voxel > 0.0:
             vlist = voxel_vlist(eng, source_xyz, vlist, mx_align, sample_voxel)
         estimate_source = isinstance(source_normals, str)
@@ -529,11 +622,17 @@ class IcpAlign:
         self.last_coarse = None
         if coarse is not None:
             from .coarse_align import coarse_stage
+            if cleaning["target"] is not None:                 # (the coarse stage thins the target it is given: the resident one)
+                target_xyz = _host_rows(target_xyz)[cleaning["target"]["index"]]
             self.last_coarse = coarse_stage(eng, coarse, target_xyz, mx_base, source_xyz=source_xyz)
         res = eng.run(iters=s.icp_iterations, thresh=thresh, target_d=s.target_d, use_target=s.use_target,
                       with_scale=(s.align_meth == "1"), early_exit=early_exit)
         if deviation is not None:
             res.deviation = eng.deviation(**deviation.kwargs(thresh))
+            if cleaning["target"] is not None and res.deviation.get("idx") is not None:
+                # the report speaks of the caller's vertices, not of the cleaned target's
+                idx, kept = res.deviation["idx"], cleaning["target"]["index"].astype(np.int64)
+                res.deviation["idx"] = np.where(idx >= 0, kept[np.maximum(idx, 0)], -1)
         return res
 
 
