@@ -385,6 +385,48 @@ int oa_target_outliers(oa_ctx *ctx, const oa_outlier_settings *s, int apply,
                        uint8_t *keep /* nt */, double *score /* nt, STATISTICAL */, int32_t *count /* nt, RADIUS */,
                        int32_t *kept_index /* n_kept entries, room for nt */, oa_outlier_report *rep);
 int oa_target_radius_count(oa_ctx *ctx, double radius, int32_t cap, int32_t *count /* nt */);
+/* EXTENSION: the parts of a point-cloud target -- DBSCAN labels, and the target without the scanner table, the
+ * clamp or a second object, which the filters above cannot remove because such parts are dense.  Vertex-mode targets,
+ * single-device contexts.  Coordinates are the target's own (base-local), no matrices needed.
+ *
+ * The contract, with r2 = (float)eps * (float)eps (float32, one rounding; oa_target_radius_count's rule) and d2_metric the float32
+ * metric of the searches, has exactly one answer:
+ *   count[i] = #{ j : d2_metric(v_i, v_j) <= r2 }; the vertex itself is included, duplicates count; a vertex with a non-finite
+ *       coordinate counts 0 and is counted by nobody.  core[i] = count[i] >= min_points.
+ *   Two core vertices are linked iff d2_metric <= r2.  d2_metric is symmetric bit for bit, so the graph is undirected.  A cluster
+ *       is a connected component of the core graph; clusters are numbered 0, 1, ... in ascending order of their lowest core index.
+ *   A non-core vertex with at least one core vertex within the radius is a border vertex: its label is the lowest label among the
+ *       clusters of those core vertices.  Everything else is noise, label -1.
+ *   sizes[c] = the core and border members of cluster c.  The largest cluster is the one of greatest size, on equal size the lowest label.
+ * This is what scikit-learn's DBSCAN(algorithm="brute") returns, numbering and border assignment included.  Integer atomics and
+ * comparisons only: two calls give the same bits, whichever order the device ran its waves in.
+ * keep[i]: OA_CLUSTER_KEEP_CLUSTERED label >= 0; _LARGEST label = the largest cluster's; _MIN_SIZE label >= 0 and sizes[label] >= min_size.
+ * Outputs (host, each may be NULL): label (nt); sizes (n_clusters entries; give room for nt); keep (nt bytes, 0 / 1); kept_index =
+ * the kept vertices in ascending order (n_kept entries; give room for nt); rep.
+ * apply != 0: as oa_target_outliers -- the resident target becomes the kept vertices in the caller's order, the context is what
+ * oa_set_target(xyz[keep]) would have left, OA_STAT_TARGET_CLEANED holds the number removed.  When no vertex would be kept:
+ * OA_E_TOO_FEW_PAIRS, nothing applied, the outputs written.
+ * The call ends a running oa_iterate sequence, as oa_target_knn does; a context without a box tree builds one for the call.
+ * OA_E_BAD_ARG (decided before any launch): NULL settings; eps not finite or not > 0; min_points < 1; an unknown keep; min_size < 0.
+ * OA_E_STATE: no target, a surface target, a multi-device context.  OA_E_HIP should the union-find's step bound be exceeded (never
+ * seen).  Each refusal leaves the context usable. */
+#define OA_CLUSTER_KEEP_CLUSTERED 0   /* label >= 0: the noise goes */
+#define OA_CLUSTER_KEEP_LARGEST   1
+#define OA_CLUSTER_KEEP_MIN_SIZE  2   /* sizes[label] >= min_size */
+typedef struct oa_cluster_settings {
+    double  eps;                  /* finite, > 0, the target's own (base-local) units */
+    int32_t min_points, keep;     /* min_points >= 1 (1: plain Euclidean clustering); keep: OA_CLUSTER_KEEP_* */
+    int64_t min_size;             /* >= 0; read by OA_CLUSTER_KEEP_MIN_SIZE alone */
+} oa_cluster_settings;
+typedef struct oa_cluster_report {
+    int64_t n_clusters, n_core, n_border;
+    int64_t n_noise, n_nonfinite; /* n_noise: every vertex of label -1, the n_nonfinite vertices with a non-finite coordinate among them */
+    int64_t largest_label, largest_size;      /* -1, 0 without a cluster */
+    int64_t n_kept, n_removed;
+} oa_cluster_report;
+int oa_target_clusters(oa_ctx *ctx, const oa_cluster_settings *s, int apply,
+                       int32_t *label /* nt */, int32_t *sizes /* n_clusters entries, room for nt */,
+                       uint8_t *keep /* nt */, int32_t *kept_index /* n_kept entries, room for nt */, oa_cluster_report *rep);
 /* EXTENSION (no counterpart in the reference, whose only protection against bad correspondences is the hard cut thresh): pair
  * weights.  Every pair of a loop step (oa_run, oa_iterate, the split-phase calls) carries the weight
  *   w = w_vertex * psi(r),   c = scale (world units, like thresh):
@@ -626,7 +668,7 @@ int oa_reset_seeds(oa_ctx *ctx);
                                       * the first step.  A host integer written where the launch is decided: no device read.  First device */
 #define OA_STAT_ACC_ROWS       50   /* rows of per-workgroup partials the last step's reduce launch was given (DUAL: the grid's rows; the tree's
                                       * are chosen on the device); 0 before the first step.  First device */
-#define OA_STAT_TARGET_CLEANED 51   /* vertices the last oa_target_outliers(apply) removed from the resident target; 0 after a plain upload */
+#define OA_STAT_TARGET_CLEANED 51   /* vertices the last oa_target_outliers(apply) or oa_target_clusters(apply) removed from the resident target; 0 after a plain upload */
 #define OA_ACC_CANON            1  /* k_pair_accumulate_canon behind a search: one thread per (slot, lane of the query) */
 #define OA_ACC_STRIDE           2   /* the grid-stride k_pair_accumulate */
 #define OA_ACC_WEIGHTED         3   /* k_pair_accumulate_weighted */

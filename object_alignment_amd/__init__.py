@@ -47,6 +47,23 @@ def remove_outliers(xyz, method="statistical", k=16, std_ratio=2.0, radius=0.0, 
     return out
 
 
+def cluster_dbscan(xyz, eps, min_points=8, keep="clustered", min_size=0, device=0):
+    """The parts of ANY point cloud, by DBSCAN on the GPU (IcpEngine.target_clusters says how): a dict with "label" int32 (n,) (-1:
+    noise), "sizes" int32 (n_clusters,), "keep" uint8 (n,), "index" (the kept points' indices, ascending), "xyz" (the kept points,
+    float32, in the caller's order) and "report".  Opens a context of its own on `device`, uploads xyz as its target and closes."""
+    import numpy as np
+    from .engine import IcpEngine, _cluster_args
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or len(xyz) < 1:
+        raise ValueError("cluster_dbscan: xyz must be (n >= 1, 3), got shape %s" % (xyz.shape,))
+    _cluster_args(eps, min_points, keep, min_size, name="cluster_dbscan")
+    with IcpEngine(int(device)) as eng:
+        eng.set_target(xyz)
+        out = eng.target_clusters(eps, min_points=min_points, keep=keep, min_size=min_size, apply=False)
+    out["xyz"] = xyz[out["index"]]
+    return out
+
+
 def fpfh(xyz, normals=None, k=16, normal_k=16, device=0):
     """Fast Point Feature Histograms of ANY point cloud (the source's included), computed on the GPU: (n, 33) float32, an
     all-zero row meaning "no descriptor".  Opens a context of its own on `device` and uploads xyz as its target; without

@@ -64,6 +64,9 @@ OA_STAT_ACC_ROWS = 50
 OA_STAT_TARGET_CLEANED = 51
 OA_OUTLIER_STATISTICAL = 0
 OA_OUTLIER_RADIUS = 1
+OA_CLUSTER_KEEP_CLUSTERED = 0
+OA_CLUSTER_KEEP_LARGEST = 1
+OA_CLUSTER_KEEP_MIN_SIZE = 2
 (OA_ACC_CANON, OA_ACC_STRIDE, OA_ACC_WEIGHTED, OA_ACC_PLANE, OA_ACC_GICP, OA_ACC_FUSED_GRID, OA_ACC_FUSED_TRI_GRID, OA_ACC_FUSED_TREE,
  OA_ACC_FUSED_TRI_TREE, OA_ACC_DUAL) = range(1, 11)
 
@@ -91,6 +94,7 @@ SYMBOLS = [
     "oa_normal_space_sample", "oa_stability",
     "oa_orient_target_normals",
     "oa_target_outliers", "oa_target_radius_count",
+    "oa_target_clusters",
 ]
 
 
@@ -169,6 +173,16 @@ class OutlierSettings(C.Structure):
 class OutlierReport(C.Structure):
     _fields_ = [("n_kept", C.c_int64), ("n_removed", C.c_int64), ("n_nonfinite", C.c_int64), ("mean", C.c_double),
                 ("std", C.c_double), ("threshold", C.c_double)]
+
+
+class ClusterSettings(C.Structure):
+    _fields_ = [("eps", C.c_double), ("min_points", C.c_int32), ("keep", C.c_int32), ("min_size", C.c_int64)]
+
+
+class ClusterReport(C.Structure):
+    _fields_ = [("n_clusters", C.c_int64), ("n_core", C.c_int64), ("n_border", C.c_int64), ("n_noise", C.c_int64),
+                ("n_nonfinite", C.c_int64), ("largest_label", C.c_int64), ("largest_size", C.c_int64), ("n_kept", C.c_int64),
+                ("n_removed", C.c_int64)]
 
 
 class OaError(RuntimeError):
@@ -285,6 +299,8 @@ def load(experiments: bool = False):
     L.oa_target_outliers.argtypes = [vp, C.POINTER(OutlierSettings), C.c_int, C.POINTER(C.c_uint8), dp, i32p, i32p,
                                      C.POINTER(OutlierReport)]
     L.oa_target_radius_count.argtypes = [vp, C.c_double, C.c_int32, i32p]
+    L.oa_target_clusters.argtypes = [vp, C.POINTER(ClusterSettings), C.c_int, i32p, i32p, C.POINTER(C.c_uint8), i32p,
+                                     C.POINTER(ClusterReport)]
     _libs[experiments] = L
     return L
 

@@ -10,6 +10,7 @@
 #include "oa_pose.hpp"
 #include "oa_knn.hpp"
 #include "oa_outlier.hpp"
+#include "oa_cluster.hpp"
 #include "oa_feat.hpp"
 #include "oa_affine.hpp"
 #include "oa_recip.hpp"

@@ -28,7 +28,8 @@
 #define OA_SIG_POSE_SCORE PoseBase, const float *, const float *, const float4 *, const int *, int, int, BvhParams, const float4 *, const float4 *, const float4 *, double *
 #define OA_SIG_BVH_KNN BvhParams, const float4 *, const float4 *, int, int32_t *, float *, const float *, KnnOrient, float *, float *
 #define OA_SIG_BVH_RADIUS_COUNT BvhParams, const float4 *, const float4 *, float, int, int32_t *
-#define OA_SIG_FPFH const float *, const float *, const int32_t *, int, int, double *, float *
+#define OA_SIG_BVH_CLUSTER BvhParams, const float4 *, const float4 *, float, int, const int32_t *, uint32_t *, const uint32_t *, uint32_t *, int, ClusterStats *
+#define OA_SIG_FPFH const float *,const float *, const int32_t *, int, int, double *, float *
 #define OA_SIG_MATCH_FEATURES const float *, const float *, const float *, int, int, int, unsigned long long *, unsigned long long *, float *
 #define OA_SIG_TRIPLE_POSES const int *, const int *, int, const int *, int, const float4 *, const float *, Mat4f, Mat4f, Mat4d, double, double, float *, int *
 #define OA_SIG_AFFINE_SOLVE const double *, const double *, int, long long, int, int, double *, double *
@@ -90,9 +91,10 @@
 
 // ---- k nearest target vertices of every target vertex / PCA normals from them (oa_knn.hpp): oa_fam_knn.hip ----------
 // (+ the fixed-radius count of oa_outlier.hpp; its k_bvh_knn_score is a plain kernel that oa_outlier.hpp defines in this unit
-//  alone and declares everywhere else)
+//  alone and declares everywhere else; + the link and border passes of oa_cluster.hpp, the same traversal)
 #define OA_FAMILY_KNN(X) OA_K(X, k_bvh_knn, OA_SIG_BVH_KNN, false) OA_K(X, k_bvh_knn, OA_SIG_BVH_KNN, true)                   \
-    OA_K(X, k_bvh_radius_count, OA_SIG_BVH_RADIUS_COUNT, false) OA_K(X, k_bvh_radius_count, OA_SIG_BVH_RADIUS_COUNT, true)
+    OA_K(X, k_bvh_radius_count, OA_SIG_BVH_RADIUS_COUNT, false) OA_K(X, k_bvh_radius_count, OA_SIG_BVH_RADIUS_COUNT, true)    \
+    OA_K(X, k_bvh_cluster, OA_SIG_BVH_CLUSTER, CL_LINK) OA_K(X, k_bvh_cluster, OA_SIG_BVH_CLUSTER, CL_BORDER)
 
 // ---- nearest rows in descriptor space / poses from triples of matched points (oa_feat.hpp): oa_fam_feat.hip -----------
 #define OA_FAMILY_FEAT(X)                                                                                               \

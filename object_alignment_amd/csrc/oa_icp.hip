@@ -5565,6 +5565,103 @@ OA_EXPORT int oa_target_outliers(oa_ctx *c, const oa_outlier_settings *s, int ap
 }
 
 // ================================================================================================
+// the parts of a point-cloud target: DBSCAN labels, sizes, the largest part (EXTENSION; oa_cluster.hpp)
+// ================================================================================================
+OA_EXPORT int oa_target_clusters(oa_ctx *c, const oa_cluster_settings *s, int apply, int32_t *label, int32_t *sizes, uint8_t *keep,
+                                 int32_t *kept_index, oa_cluster_report *rep)
+{
+    static const char who[] = "oa_target_clusters";
+    if (!c || !s) return fail(OA_E_BAD_ARG, "%s: null argument", who);
+    OA_NOT_MULTI(c, "oa_target_clusters");
+    if (rep) memset(rep, 0, sizeof *rep);
+    if (!(s->eps > 0.0) || !(s->eps < (double)INFINITY)) return fail(OA_E_BAD_ARG, "%s: eps = %g (finite and > 0)", who, s->eps);
+    if (s->min_points < 1) return fail(OA_E_BAD_ARG, "%s: min_points = %d (>= 1)", who, (int)s->min_points);
+    if (s->keep != OA_CLUSTER_KEEP_CLUSTERED && s->keep != OA_CLUSTER_KEEP_LARGEST && s->keep != OA_CLUSTER_KEEP_MIN_SIZE)
+        return fail(OA_E_BAD_ARG, "%s: keep = %d (use OA_CLUSTER_KEEP_CLUSTERED / _LARGEST / _MIN_SIZE)", who, (int)s->keep);
+    if (s->min_size < 0) return fail(OA_E_BAD_ARG, "%s: min_size = %lld (>= 0)", who, (long long)s->min_size);
+    int rc = outlier_call_begin(c, who);
+    if (rc) return rc;
+    const int nt = c->tgt.nt;
+    KnnTree tree;
+    if ((rc = knn_tree(c, tree))) return rc;
+    const size_t snt = (size_t)nt;
+    const float *d_xyz = c->tgt.d_tgt_xyz;
+    const float ef = (float)s->eps, r2 = ef * ef;
+    const int min_points = (int)s->min_points;
+    DevTmp<int32_t> d_count, d_label, d_sizes, d_index;
+    DevTmp<uint32_t> d_parent, d_root, d_border;
+    DevTmp<int> d_is_root, d_flag;
+    DevTmp<long long> d_dense, d_off;
+    DevTmp<unsigned char> d_keep;
+    DevTmp<float> d_kept_xyz;
+    DevTmp<oa::ClusterStats> d_st;
+    DevTmp<oa::OutlierStats> d_ost;                                  // (k_outlier_compact's n_kept)
+    DevTmp<char> scan_tmp, scan_tmp2;
+    HIPCHK(d_count.alloc(snt)); HIPCHK(d_label.alloc(snt)); HIPCHK(d_sizes.alloc(snt)); HIPCHK(d_index.alloc(snt));
+    HIPCHK(d_parent.alloc(snt)); HIPCHK(d_root.alloc(snt)); HIPCHK(d_border.alloc(snt));
+    HIPCHK(d_is_root.alloc(snt)); HIPCHK(d_flag.alloc(snt)); HIPCHK(d_dense.alloc(snt + 1)); HIPCHK(d_off.alloc(snt + 1));
+    HIPCHK(d_keep.alloc(snt)); HIPCHK(d_st.alloc(1)); HIPCHK(d_ost.alloc(1));
+    if (apply) HIPCHK(d_kept_xyz.alloc(3 * snt));
+    HIPCHK(hipMemsetAsync(d_st.p, 0, sizeof(oa::ClusterStats), c->stream));
+    HIPCHK(hipMemsetAsync(d_ost.p, 0, sizeof(oa::OutlierStats), c->stream));
+    HIPCHK(hipMemsetAsync(d_sizes.p, 0, sizeof(int32_t) * snt, c->stream));
+    HIPCHK(hipMemsetAsync(d_border.p, 0xff, sizeof(uint32_t) * snt, c->stream));
+    // 1. core flags: counts that saturate at min_points
+    if ((rc = radius_count_launch(c, tree, s->eps, min_points, d_count.p))) return rc;
+    // 2. the core graph's components (link, then flatten in a launch of its own), 3. the border vertices' lowest root
+    const int wpb = oa::KNN_WPB, leaves = tree.bp.cnt[1];
+    const unsigned t_blocks = (unsigned)std::max(1, std::min((leaves + wpb - 1) / wpb, c->n_cu * 32));
+    const unsigned v_blocks = (unsigned)((snt + oa::CL_THREADS - 1) / oa::CL_THREADS);
+    const int max_steps = (int)std::min<long long>(2ll * nt + 64, 0x7fffffffll);
+    const dim3 blk(oa::CL_THREADS);
+    hipLaunchKernelGGL(oa::k_cluster_init, dim3(v_blocks), blk, 0, c->stream, nt, d_parent.p);
+    hipLaunchKernelGGL((oa::k_bvh_cluster<oa::CL_LINK>), dim3(t_blocks), dim3(64 * wpb), 0, c->stream, tree.bp, tree.box, tree.prims, r2, min_points,
+                       (const int32_t *)d_count.p, d_parent.p, (const uint32_t *)nullptr, (uint32_t *)nullptr, max_steps, d_st.p);
+    hipLaunchKernelGGL(oa::k_cluster_flatten, dim3(v_blocks), blk, 0, c->stream, (const uint32_t *)d_parent.p, (const int32_t *)d_count.p, min_points, nt, d_root.p,
+                       d_is_root.p, d_st.p);
+    hipLaunchKernelGGL((oa::k_bvh_cluster<oa::CL_BORDER>), dim3(t_blocks), dim3(64 * wpb), 0, c->stream, tree.bp, tree.box, tree.prims, r2, min_points,
+                       (const int32_t *)d_count.p, (uint32_t *)nullptr, (const uint32_t *)d_root.p, d_border.p, max_steps, d_st.p);
+    HIPCHK(hipGetLastError());
+    // 4. dense labels in ascending root order, sizes, the largest cluster, the keep flags and their compaction
+    if ((rc = scan_counts(c, d_is_root.p, nt, d_dense.p, scan_tmp))) return rc;
+    hipLaunchKernelGGL(oa::k_cluster_label, dim3(v_blocks), blk, 0, c->stream, (const uint32_t *)d_root.p, (const uint32_t *)d_border.p, (const long long *)d_dense.p,
+                       d_xyz, nt, d_label.p, d_sizes.p, d_st.p);
+    hipLaunchKernelGGL(oa::k_cluster_largest, dim3(1), blk, 0, c->stream, (const int32_t *)d_sizes.p, d_st.p);
+    hipLaunchKernelGGL(oa::k_cluster_keep, dim3(v_blocks), blk, 0, c->stream, (const int32_t *)d_label.p, (const int32_t *)d_sizes.p, (const oa::ClusterStats *)d_st.p,
+                       (int)s->keep, (long long)s->min_size, nt, d_flag.p, d_keep.p);
+    HIPCHK(hipGetLastError());
+    if ((rc = scan_counts(c, d_flag.p, nt, d_off.p, scan_tmp2))) return rc;
+    hipLaunchKernelGGL(oa::k_outlier_compact, dim3(v_blocks), dim3(oa::OUT_THREADS), 0, c->stream, (const int *)d_flag.p, (const long long *)d_off.p, nt, d_xyz,
+                       d_index.p, d_kept_xyz.p, d_ost.p);
+    HIPCHK(hipGetLastError());
+    oa::ClusterStats st;
+    oa::OutlierStats ost;
+    if ((rc = read_small(c, &st, d_st.p, sizeof st))) return rc;    // (waits for everything above)
+    if ((rc = read_small(c, &ost, d_ost.p, sizeof ost))) return rc;
+    if (st.err) return fail(OA_E_HIP, "%s: the union-find ran out of its %d steps (flag %d; internal)", who, max_steps, st.err);
+    if (ost.n_kept < 0 || ost.n_kept > nt || st.n_clusters < 0 || st.n_clusters > nt)
+        return fail(OA_E_HIP, "%s: %lld of %d vertices kept in %lld clusters (internal)", who, ost.n_kept, nt, st.n_clusters);
+    if (label) HIPCHK(hipMemcpyAsync(label, d_label.p, sizeof(int32_t) * snt, hipMemcpyDeviceToHost, c->stream));
+    if (sizes && st.n_clusters > 0) HIPCHK(hipMemcpyAsync(sizes, d_sizes.p, sizeof(int32_t) * (size_t)st.n_clusters, hipMemcpyDeviceToHost, c->stream));
+    if (keep) HIPCHK(hipMemcpyAsync(keep, d_keep.p, snt, hipMemcpyDeviceToHost, c->stream));
+    if (kept_index && ost.n_kept > 0) HIPCHK(hipMemcpyAsync(kept_index, d_index.p, sizeof(int32_t) * (size_t)ost.n_kept, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (rep) {
+        rep->n_clusters = (int64_t)st.n_clusters; rep->n_core = (int64_t)st.n_core; rep->n_border = (int64_t)st.n_border;
+        rep->n_noise = (int64_t)st.n_noise; rep->n_nonfinite = (int64_t)st.n_nonfinite;
+        rep->largest_label = (int64_t)st.largest_label; rep->largest_size = (int64_t)st.largest_size;
+        rep->n_kept = (int64_t)ost.n_kept; rep->n_removed = (int64_t)nt - (int64_t)ost.n_kept;
+    }
+    if (!apply) return OA_OK;
+    if (ost.n_kept < 1) return fail(OA_E_TOO_FEW_PAIRS, "%s: no vertex of %d would be kept; the target stays as it is", who, nt);
+    // 5. the kept vertices become the target, as an upload from device memory would make them (oa_target_outliers' path)
+    const long long removed = (long long)nt - ost.n_kept;
+    if ((rc = set_target_common(c, d_kept_xyz.p, (int64_t)ost.n_kept, 1, true))) return rc;
+    c->tgt.cleaned = removed;
+    return OA_OK;
+}
+
+// ================================================================================================
 // one consistent sign for a cloud's normals: a minimum spanning forest of the neighbour graph (EXTENSION; oa_orient.hpp)
 // ================================================================================================
 OA_EXPORT int oa_orient_target_normals(oa_ctx *c, int k, double max_dist, int seed, const float point[3], const float *normals, int install,

@@ -216,6 +216,24 @@ def _radius_count_args(radius, cap=0, name="target_radius_count"):
     return float(radius), _whole(cap, name, "cap", 0, 2**31 - 1)
 
 
+CLUSTER_KEEP = {"clustered": capi.OA_CLUSTER_KEEP_CLUSTERED, "largest": capi.OA_CLUSTER_KEEP_LARGEST,
+                "min_size": capi.OA_CLUSTER_KEEP_MIN_SIZE}
+
+
+def _cluster_args(eps, min_points=8, keep="largest", min_size=0, name="target_clusters"):
+    """The arguments of a clustering, checked before any call reaches the library: (eps, min_points, keep, min_size)."""
+    if not _real(eps) or not 0 < eps < float("inf"):
+        raise ValueError("%s: eps = %r (finite and > 0)" % (name, eps))
+    min_points = _whole(min_points, name, "min_points", 1, 2**31 - 1)
+    if isinstance(keep, str):
+        if keep not in CLUSTER_KEEP:
+            raise ValueError("%s: keep %r (use 'clustered', 'largest' or 'min_size')" % (name, keep))
+        keep = CLUSTER_KEEP[keep]
+    elif isinstance(keep, bool) or not isinstance(keep, (int, np.integer)) or keep not in (0, 1, 2):
+        raise ValueError("%s: keep %r (use 'clustered', 'largest' or 'min_size')" % (name, keep))
+    return float(eps), min_points, int(keep), _whole(min_size, name, "min_size", 0, 2**63 - 1)
+
+
 DEVIATION_OUTPUTS = ("signed_d", "dist", "closest", "idx", "feature")
 DEVIATION_SIGNED = {"auto": -1, "never": 0, "required": 1, None: -1, False: 0, True: 1}
 
@@ -507,6 +525,34 @@ class IcpEngine:
         report = {name: (int if name.startswith("n_") else float)(getattr(rep, name)) for name, _ in capi.OutlierReport._fields_}
         out = {"keep": keep[:nt], "index": index[: report["n_kept"]].copy(), "report": report}
         out["score" if statistical else "count"] = (score if statistical else count)[:nt]
+        if apply:
+            self.n_target = report["n_kept"]
+            self.target_owner = None
+        return out
+
+    def target_clusters(self, eps, min_points=8, keep="largest", min_size=0, apply=False):
+        """Vertex-mode targets: the parts of the cloud, by DBSCAN (the answer scikit-learn's DBSCAN(algorithm="brute") gives, its
+        numbering and border assignment included).  A vertex with at least min_points vertices within eps (the target's own units;
+        itself included) is a core vertex; core vertices within eps of each other share a cluster, clusters are numbered by their
+        lowest core index; a non-core vertex within eps of a core vertex takes the lowest such cluster's label; the rest is noise,
+        -1.  keep: 'clustered' (label >= 0), 'largest' (the largest cluster; on equal size the lowest label) or 'min_size' (clusters
+        of at least min_size members).  Returns {"label": int32 (nt,), "sizes": int32 (n_clusters,), "keep": uint8 (nt,), "index":
+        int32 (n_kept,) -- the kept vertices, ascending --, "report": dict}.  apply: the kept vertices become the target, exactly as
+        set_target(xyz[keep]) would make them; stat("target_cleaned") then holds the number removed."""
+        eps, min_points, keep, min_size = _cluster_args(eps, min_points, keep, min_size)
+        nt = self.n_target
+        n = max(1, nt)
+        st = capi.ClusterSettings(eps, min_points, keep, min_size)
+        rep = capi.ClusterReport()
+        label, sizes, index = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+        mask = np.empty(n, np.uint8)
+        i32p = C.POINTER(C.c_int32)
+        rc = self._L.oa_target_clusters(self._h, C.byref(st), int(bool(apply)), label.ctypes.data_as(i32p), sizes.ctypes.data_as(i32p),
+                                        mask.ctypes.data_as(C.POINTER(C.c_uint8)), index.ctypes.data_as(i32p), C.byref(rep))
+        self._chk(rc)
+        report = {name: int(getattr(rep, name)) for name, _ in capi.ClusterReport._fields_}
+        out = {"label": label[:nt], "sizes": sizes[: report["n_clusters"]].copy(), "keep": mask[:nt],
+               "index": index[: report["n_kept"]].copy(), "report": report}
         if apply:
             self.n_target = report["n_kept"]
             self.target_owner = None

@@ -48,6 +48,30 @@ class OutlierSettings:
 
 
 @dataclass
+class ClusterSettings:
+    """What IcpSettings.segment_target / segment_source keep of a cloud: its DBSCAN clusters (IcpEngine.target_clusters' arguments;
+    checked here, before any engine opens).  A point with at least min_points points within eps (itself included) is a core point,
+    core points within eps of each other share a cluster, a point within eps of a core point joins its cluster, the rest is
+    noise.  keep "largest": the largest cluster alone -- the scanned object without the table, the clamp or a second object --;
+    "clustered": every cluster, the noise goes; "min_size": the clusters of at least min_size points.  eps is in world units, like
+    min_start."""
+    eps: float
+    min_points: int = 8
+    keep: str = "largest"
+    min_size: int = 0
+
+    def __post_init__(self):
+        from ..engine import _cluster_args
+        _cluster_args(**self.kwargs(1.0), name="ClusterSettings")
+
+    def kwargs(self, scale):
+        """The clustering's arguments for a cloud whose local unit is `scale` world units (world_scale of its matrix)."""
+        from ..engine import _real
+        eps = self.eps / scale if _real(self.eps) else self.eps               # (anything else is for _cluster_args to refuse)
+        return dict(eps=eps, min_points=self.min_points, keep=self.keep, min_size=self.min_size)
+
+
+@dataclass
 class IcpSettings:
     """Names and defaults of the add-on preferences the loop reads (lib/preferences.py:31-72)."""
     icp_iterations: int = 50
@@ -128,6 +152,12 @@ class IcpSettings:
     # before sample_voxel thins it.  None = off.  One GPU
     clean_target: object = None
     clean_source: object = None
+    # nor these: a ClusterSettings keeps the part of a raw scan that is the object -- what clean_* cannot remove because it is
+    # dense: the scanner table, a clamp, a second object on the turntable.  segment_target: the point-cloud target is clustered on
+    # the device right after clean_target (IcpEngine.target_clusters(apply=True)), before normals, features and the loop.
+    # segment_source: the selection, after clean_source, goes through object_alignment_amd.cluster_dbscan.  None = off.  One GPU
+    segment_target: object = None
+    segment_source: object = None
 
 
 @dataclass
@@ -396,6 +426,17 @@ def clean_of(settings):
     return tuple(out)
 
 
+def segment_of(settings):
+    """(segment_target, segment_source) from IcpSettings: each a ClusterSettings or None."""
+    out = []
+    for name in ("segment_target", "segment_source"):
+        v = getattr(settings, name, None)
+        if v is not None and not isinstance(v, ClusterSettings):
+            raise TypeError("IcpSettings.%s = %r (a ClusterSettings, or None)" % (name, v))
+        out.append(v)
+    return tuple(out)
+
+
 def _local_scale(mx, what):
     s = world_scale(mx)
     if not (np.isfinite(s) and s > 0):
@@ -427,6 +468,35 @@ def clean_selection(engine, clean, source_xyz, vlist, mx_align):
     out = remove_outliers(pts, device=getattr(engine, "device", 0), **clean.kwargs(scale))
     index = out["index"].astype(np.int64)
     return {"vlist": sel[index] if sel is not None else index, "index": out["index"], "keep": out["keep"], "report": out["report"]}
+
+
+def segment_resident_target(engine, seg, mx_base):
+    """Keep the clusters `seg` names of the engine's resident point-cloud target (IcpEngine.target_clusters(apply=True), eps carried
+    from world units to the target's own by mx_base): {"index": the kept vertices in the resident target's numbering, "label",
+    "sizes", "keep", "report"}."""
+    call = getattr(engine, "target_clusters", None)
+    if call is None:
+        raise RuntimeError("this engine has no clustering")
+    out = call(apply=True, **seg.kwargs(_local_scale(mx_base, "segment_target")))
+    return {name: out[name] for name in ("index", "label", "sizes", "keep", "report")}
+
+
+def segment_selection(engine, seg, source_xyz, vlist, mx_align):
+    """The vertices vlist selects (None: all) that lie in the clusters `seg` names (object_alignment_amd.cluster_dbscan in a context of
+    its own, eps carried to the source's own units by mx_align): {"vlist": what is left, as indices into source_xyz in vlist's
+    order, "index": the kept positions within the selection, "label", "sizes", "keep", "report"}."""
+    from .. import cluster_dbscan
+    scale = _local_scale(mx_align, "segment_source")
+    pts = _host_rows(source_xyz)
+    sel = None
+    if vlist is not None:
+        sel = np.ascontiguousarray(vlist, dtype=np.int64)
+        pts = pts[sel]
+    out = cluster_dbscan(pts, device=getattr(engine, "device", 0), **seg.kwargs(scale))
+    index = out["index"].astype(np.int64)
+    res = {name: out[name] for name in ("index", "label", "sizes", "keep", "report")}
+    res["vlist"] = sel[index] if sel is not None else index
+    return res
 
 
 def normal_space_vlist(engine, source_xyz, source_normals, vlist, stride, m, grid, unoriented):
@@ -543,6 +613,11 @@ class IcpAlign:
         the selection loses its own before sample_voxel.  self.last_cleaning = {"target": ..., "source": ...} holds the index maps
         and reports (None for a side that was not cleaned); None while both settings are off.  An attached deviation report's idx
         speaks of the caller's target vertices.
+        settings.segment_target / segment_source: a ClusterSettings each -- right after clean_target the point-cloud target keeps
+        the clusters the setting names (ValueError with target_tris), the selection its own right after clean_source.
+        self.last_segmentation = {"target": ..., "source": ...} holds, per side, "index" -- the kept vertices in the CALLER's
+        numbering (the target's vertices; positions within the selection), composed with a preceding clean step --, "label" and
+        "sizes" over the cloud the clustering saw, and the report; None while both settings are off.
         deviation: a DeviationSettings -- after the loop the deviation report and its arrays are taken at the final pose on the same
         engine (over the points the loop used) and attached as RunResult.deviation; None: nothing else changes."""
         s = self.settings
@@ -563,6 +638,9 @@ class IcpAlign:
         clean_target, clean_source = clean_of(s)
         if clean_target is not None and target_tris is not None:
             raise ValueError("IcpSettings.clean_target is for point-cloud targets: a mesh (target_tris) has no stray vertices to remove")
+        segment_target, segment_source = segment_of(s)
+        if segment_target is not None and target_tris is not None:
+            raise ValueError("IcpSettings.segment_target is for point-cloud targets: a mesh (target_tris) is one connected surface already")
         thresh = s.min_start                                   # :83
         factor = round(1 / s.sample_fraction)                  # :89  (ZeroDivisionError at 0, as the reference)
         if not thresh > 0:
@@ -571,14 +649,23 @@ class IcpAlign:
         eng = self.engine
         cleaning = {"target": None, "source": None}
         self.last_cleaning = cleaning if (clean_target is not None or clean_source is not None) else None
+        segmentation = {"target": None, "source": None}
+        self.last_segmentation = segmentation if (segment_target is not None or segment_source is not None) else None
+        target_kept = None                                     # the resident target's vertices in the caller's numbering, once some left
         if target_tris is not None:
             eng.set_target_mesh(target_xyz, target_tris)
         else:
             eng.set_target(target_xyz)
             if clean_target is not None:
                 cleaning["target"] = clean_resident_target(eng, clean_target, mx_base)
-                if target_normals is not None and not estimate:
-                    target_normals = np.asarray(target_normals).reshape(-1, 3)[cleaning["target"]["index"]]
+                target_kept = cleaning["target"]["index"]
+            if segment_target is not None:
+                segmentation["target"] = segment_resident_target(eng, segment_target, mx_base)
+                if target_kept is not None:
+                    segmentation["target"]["index"] = target_kept[segmentation["target"]["index"]]
+                target_kept = segmentation["target"]["index"]
+            if target_kept is not None and target_normals is not None and not estimate:
+                target_normals = np.asarray(target_normals).reshape(-1, 3)[target_kept]
             if estimate:
                 eng.estimate_target_normals(k=int(getattr(s, "normal_k", 16)), orient="away", install=True)
                 if consistent:
@@ -593,6 +680,11 @@ class IcpAlign:
         if clean_source is not None:
             cleaning["source"] = clean_selection(eng, clean_source, source_xyz, vlist, mx_align)
             vlist = cleaning["source"]["vlist"]
+        if segment_source is not None:
+            segmentation["source"] = segment_selection(eng, segment_source, source_xyz, vlist, mx_align)
+            vlist = segmentation["source"]["vlist"]
+            if cleaning["source"] is not None:
+                segmentation["source"]["index"] = cleaning["source"]["index"][segmentation["source"]["index"]]
         if sample_voxel > 0.0:
             vlist = voxel_vlist(eng, source_xyz, vlist, mx_align, sample_voxel)
         estimate_source = isinstance(source_normals, str)
@@ -622,16 +714,16 @@ class IcpAlign:
         self.last_coarse = None
         if coarse is not None:
             from .coarse_align import coarse_stage
-            if cleaning["target"] is not None:                 # (the coarse stage thins the target it is given: the resident one)
-                target_xyz = _host_rows(target_xyz)[cleaning["target"]["index"]]
+            if target_kept is not None:                        # (the coarse stage thins the target it is given: the resident one)
+                target_xyz = _host_rows(target_xyz)[target_kept]
             self.last_coarse = coarse_stage(eng, coarse, target_xyz, mx_base, source_xyz=source_xyz)
         res = eng.run(iters=s.icp_iterations, thresh=thresh, target_d=s.target_d, use_target=s.use_target,
                       with_scale=(s.align_meth == "1"), early_exit=early_exit)
         if deviation is not None:
             res.deviation = eng.deviation(**deviation.kwargs(thresh))
-            if cleaning["target"] is not None and res.deviation.get("idx") is not None:
+            if target_kept is not None and res.deviation.get("idx") is not None:
                 # the report speaks of the caller's vertices, not of the cleaned target's
-                idx, kept = res.deviation["idx"], cleaning["target"]["index"].astype(np.int64)
+                idx, kept = res.deviation["idx"], target_kept.astype(np.int64)
                 res.deviation["idx"] = np.where(idx >= 0, kept[np.maximum(idx, 0)], -1)
         return res
 
