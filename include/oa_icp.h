@@ -385,6 +385,35 @@ int oa_target_outliers(oa_ctx *ctx, const oa_outlier_settings *s, int apply,
                        uint8_t *keep /* nt */, double *score /* nt, STATISTICAL */, int32_t *count /* nt, RADIUS */,
                        int32_t *kept_index /* n_kept entries, room for nt */, oa_outlier_report *rep);
 int oa_target_radius_count(oa_ctx *ctx, double radius, int32_t cap, int32_t *count /* nt */);
+/* EXTENSION: radius-limited neighbourhoods.  The k nearest vertices reach as far as it takes: across a thin wall
+ * scanned from both sides, to the next tooth, over a hole narrower than their spread.  With a neighbour radius set, the rows of
+ * oa_target_knn are "the k nearest among the vertices with d2_metric(v_i, v_j) <= r2", r2 = radius * radius in float32 (one
+ * rounding; the constant oa_target_radius_count(radius) compares against): ascending (d2, index) as before, d2 = r2 included,
+ * shorter rows padded with -1 / +inf as rows of a target with non-finite vertices already are.  Exact: a vertex beyond r2 never
+ * enters a list and a box is skipped only when everything inside is strictly beyond min(k-th best, r2).
+ * The setting limits oa_target_knn, oa_estimate_target_normals (fewer than 3 neighbours: the zero normal), oa_target_fpfh (an
+ * unfilled entry takes no part) and the cloud criterion of oa_target_boundary / oa_set_reject_boundary (fewer than 3 usable
+ * neighbours: on the boundary; a mask built under another radius is rebuilt).  oa_orient_target_normals has its own max_dist and
+ * does not look at it; oa_target_outliers, oa_target_radius_count, oa_target_clusters and oa_target_spacing neither.
+ * radius: 0 = no limit (the default: every byte of every call is what it was without the setting); else finite, > 0, in the
+ * target's own (base-local) units, with a finite float32 square -- anything else is OA_E_BAD_ARG and changes nothing.  A setting
+ * like the metric: it survives uploads and oa_set_matrices, multi-device contexts hand it to every child, a change ends a running
+ * oa_iterate sequence, and it costs nothing until one of the four calls runs.  oa_get_neighbor_radius reads the float32 back. */
+int oa_set_neighbor_radius(oa_ctx *ctx, float radius);
+int oa_get_neighbor_radius(oa_ctx *ctx, float *radius);
+/* The cloud's own point spacing -- the scale a neighbour radius, a voxel edge or an eps is a multiple of.  Vertex-mode targets,
+ * single-device contexts.  s[i] = the distance from vertex i to the nearest OTHER vertex: oa_target_outliers' STATISTICAL score at
+ * k = 1, sqrt((double)d2) of entry 1 of oa_target_knn's row (a duplicate gives 0; the neighbour radius does not apply).  mean and std
+ * over the finite s[i] by that filter's fixed-order fp64 passes (std = sqrt(sum (s - mean)^2 / (n - 1)), 0 for n < 2): two calls
+ * give the same bits.  n_finite = the vertices with a finite s[i]; n_nonfinite = nt - n_finite: those with a non-finite
+ * coordinate (and a vertex that is the only finite one of its cloud).  Without a finite s[i] mean and std are 0.
+ * OA_E_BAD_ARG for a NULL argument; OA_E_STATE: no target, a surface target, a multi-device context.  Ends a running oa_iterate
+ * sequence, as oa_target_radius_count does.  Each refusal leaves the context usable. */
+typedef struct oa_spacing_report {
+    double  mean, std;
+    int64_t n_finite, n_nonfinite;
+} oa_spacing_report;
+int oa_target_spacing(oa_ctx *ctx, oa_spacing_report *rep);
 /* EXTENSION: the parts of a point-cloud target -- DBSCAN labels, and the target without the scanner table, the
  * clamp or a second object, which the filters above cannot remove because such parts are dense.  Vertex-mode targets,
  * single-device contexts.  Coordinates are the target's own (base-local), no matrices needed.

@@ -1,14 +1,31 @@
 """MI355X-native ICP alignment engine (hot path of patmo141/object_alignment)."""
 
 
-def estimate_normals(xyz, k=16, orient="none", orient_point=None, device=0):
+def estimate_normals(xyz, k=16, orient="none", orient_point=None, device=0, radius=None):
     """PCA normals of ANY point cloud (the source's included: the normal-angle test needs source normals too), estimated on
     the GPU: (normals float32 (n, 3), curvature float32 (n,)).  Opens a context of its own on `device`, uploads xyz as its
-    target, estimates from every point's k nearest neighbours (IcpEngine.estimate_target_normals) and closes."""
-    from .engine import IcpEngine
+    target, estimates from every point's k nearest neighbours (IcpEngine.estimate_target_normals) and closes.  radius: only
+    neighbours within it count (xyz's own units; IcpEngine.set_neighbor_radius); None: the k nearest however far."""
+    from .engine import IcpEngine, _radius_arg
+    if radius is not None:
+        radius = _radius_arg(radius, "estimate_normals")
     with IcpEngine(int(device)) as eng:
         eng.set_target(xyz)
-        return eng.estimate_target_normals(k=k, orient=orient, orient_point=orient_point, install=False)
+        return eng.estimate_target_normals(k=k, orient=orient, orient_point=orient_point, install=False, radius=radius)
+
+
+def cloud_spacing(xyz, device=0):
+    """The point spacing of ANY cloud, measured on the GPU: {"mean", "std"} of the distance from every point to the nearest other
+    point, "n_finite" and "n_nonfinite" (IcpEngine.target_spacing) -- the scale a neighbour radius, a voxel edge or a clustering
+    eps is a multiple of.  Opens a context of its own on `device`, uploads xyz as its target and closes."""
+    import numpy as np
+    from .engine import IcpEngine
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or len(xyz) < 1:
+        raise ValueError("cloud_spacing: xyz must be (n >= 1, 3), got shape %s" % (xyz.shape,))
+    with IcpEngine(int(device)) as eng:
+        eng.set_target(xyz)
+        return eng.target_spacing()
 
 
 def orient_normals(xyz, normals, k=8, max_dist=0.0, seed="away", point=None, device=0):
@@ -64,13 +81,17 @@ def cluster_dbscan(xyz, eps, min_points=8, keep="clustered", min_size=0, device=
     return out
 
 
-def fpfh(xyz, normals=None, k=16, normal_k=16, device=0):
+def fpfh(xyz, normals=None, k=16, normal_k=16, device=0, radius=None):
     """Fast Point Feature Histograms of ANY point cloud (the source's included), computed on the GPU: (n, 33) float32, an
     all-zero row meaning "no descriptor".  Opens a context of its own on `device` and uploads xyz as its target; without
-    `normals` (n, 3) they are estimated from every point's normal_k nearest neighbours, oriented away from the centroid."""
+    `normals` (n, 3) they are estimated from every point's normal_k nearest neighbours, oriented away from the centroid.
+    radius: only neighbours within it count, for the descriptors and for normals estimated here (xyz's own units;
+    IcpEngine.set_neighbor_radius); None: the k nearest however far."""
     import numpy as np
-    from .engine import IcpEngine, _fpfh_k
+    from .engine import IcpEngine, _fpfh_k, _radius_arg
     k = _fpfh_k(k)
+    if radius is not None:
+        radius = _radius_arg(radius, "fpfh")
     xyz = np.ascontiguousarray(xyz, dtype=np.float32)
     if xyz.ndim != 2 or xyz.shape[1] != 3 or len(xyz) < 4:
         raise ValueError("fpfh: xyz must be (n >= 4, 3), got shape %s" % (xyz.shape,))
@@ -83,10 +104,10 @@ def fpfh(xyz, normals=None, k=16, normal_k=16, device=0):
     with IcpEngine(int(device)) as eng:
         eng.set_target(xyz)
         if normals is None:
-            eng.estimate_target_normals(k=min(int(normal_k), len(xyz)), orient="away", install=True)
+            eng.estimate_target_normals(k=min(int(normal_k), len(xyz)), orient="away", install=True, radius=radius)
         else:
             eng.set_target_normals(normals)
-        return eng.target_fpfh(k=min(k, len(xyz)), keep=False)
+        return eng.target_fpfh(k=min(k, len(xyz)), keep=False, radius=radius)
 
 
 def mesh_boundary(verts, tris, device=0):
@@ -99,21 +120,25 @@ def mesh_boundary(verts, tris, device=0):
         return eng.target_boundary()
 
 
-def cloud_boundary(xyz, normals, k=16, angle_deg=90.0, device=0):
+def cloud_boundary(xyz, normals, k=16, angle_deg=90.0, device=0, radius=None):
     """The rim of ANY point cloud by the angle criterion, found on the GPU: vertex_mask uint8 (n,), 1 where the largest angular
     gap between a point's k nearest neighbours, seen in its tangent plane, exceeds angle_deg (IcpEngine.target_boundary).
     normals: (n, 3), or "estimate" (PCA normals from every point's k nearest neighbours).  Opens a context of its own on
-    `device` and uploads xyz as its target."""
-    from .engine import IcpEngine
+    `device` and uploads xyz as its target.  radius: only neighbours within it count, for the criterion and for normals estimated
+    here (xyz's own units; IcpEngine.set_neighbor_radius) -- the k nearest no longer reach across a hole narrower than their
+    spread; None: the k nearest however far."""
+    from .engine import IcpEngine, _radius_arg
     if isinstance(normals, str) and normals != "estimate":
         raise ValueError("cloud_boundary: normals %r (an array of normals, or 'estimate')" % (normals,))
+    if radius is not None:
+        radius = _radius_arg(radius, "cloud_boundary")
     with IcpEngine(int(device)) as eng:
         eng.set_target(xyz)
         if isinstance(normals, str):
-            eng.estimate_target_normals(k=int(k), orient="none", install=True)
+            eng.estimate_target_normals(k=int(k), orient="none", install=True, radius=radius)
         else:
             eng.set_target_normals(normals)
-        return eng.target_boundary(k=k, angle_deg=angle_deg)[0]
+        return eng.target_boundary(k=k, angle_deg=angle_deg, radius=radius)[0]
 
 
 def voxel_downsample(xyz, voxel, normals=None, origin=None, device=0):

@@ -95,6 +95,7 @@ SYMBOLS = [
     "oa_orient_target_normals",
     "oa_target_outliers", "oa_target_radius_count",
     "oa_target_clusters",
+    "oa_set_neighbor_radius", "oa_get_neighbor_radius", "oa_target_spacing",
 ]
 
 
@@ -183,6 +184,10 @@ class ClusterReport(C.Structure):
     _fields_ = [("n_clusters", C.c_int64), ("n_core", C.c_int64), ("n_border", C.c_int64), ("n_noise", C.c_int64),
                 ("n_nonfinite", C.c_int64), ("largest_label", C.c_int64), ("largest_size", C.c_int64), ("n_kept", C.c_int64),
                 ("n_removed", C.c_int64)]
+
+
+class SpacingReport(C.Structure):
+    _fields_ = [("mean", C.c_double), ("std", C.c_double), ("n_finite", C.c_int64), ("n_nonfinite", C.c_int64)]
 
 
 class OaError(RuntimeError):
@@ -301,6 +306,9 @@ def load(experiments: bool = False):
     L.oa_target_radius_count.argtypes = [vp, C.c_double, C.c_int32, i32p]
     L.oa_target_clusters.argtypes = [vp, C.POINTER(ClusterSettings), C.c_int, i32p, i32p, C.POINTER(C.c_uint8), i32p,
                                      C.POINTER(ClusterReport)]
+    L.oa_set_neighbor_radius.argtypes = [vp, C.c_float]
+    L.oa_get_neighbor_radius.argtypes = [vp, fp]
+    L.oa_target_spacing.argtypes = [vp, C.POINTER(SpacingReport)]
     _libs[experiments] = L
     return L
 

@@ -26,7 +26,7 @@
 #define OA_SIG_TRI_RING_BUILD float4 *, int, GridParams, const int *, const float4 *, double, int *, unsigned long long *
 #define OA_SIG_BVH_SEARCH const DevState *, const float4 *, int, BvhParams, const float4 *, const float4 *, const float4 *, int *, float4 *, unsigned long long *, const int *, const int *, int, NormalTest, double *, const float *, uint2 *
 #define OA_SIG_POSE_SCORE PoseBase, const float *, const float *, const float4 *, const int *, int, int, BvhParams, const float4 *, const float4 *, const float4 *, double *
-#define OA_SIG_BVH_KNN BvhParams, const float4 *, const float4 *, int, int32_t *, float *, const float *, KnnOrient, float *, float *
+#define OA_SIG_BVH_KNN BvhParams, const float4 *, const float4 *, int, float, int32_t *, float *, const float *, KnnOrient, float *, float *
 #define OA_SIG_BVH_RADIUS_COUNT BvhParams, const float4 *, const float4 *, float, int, int32_t *
 #define OA_SIG_BVH_CLUSTER BvhParams, const float4 *, const float4 *, float, int, const int32_t *, uint32_t *, const uint32_t *, uint32_t *, int, ClusterStats *
 #define OA_SIG_FPFH const float *,const float *, const int32_t *, int, int, double *, float *

@@ -377,6 +377,7 @@ struct oa_target {
     DevBuf<unsigned char> d_bnd_vmask, d_bnd_emask;                 // nt bytes; n_tris bytes (mesh targets)
     bool bnd_ok = false;
     int bnd_built_k = 0; double bnd_built_angle = 0.0;              // what a cloud's mask was built with
+    float bnd_built_r2 = INFINITY;                                  // ... and the neighbour radius' square then in force (+inf: none)
     long long bnd_n_vertices = 0, bnd_n_edges = 0;                  // OA_STAT_BOUNDARY_VERTICES / _EDGES
     DevBuf<int> d_corner_order; DevBuf<long long> d_corner_row;     // the mesh's corners by vertex (CSR rows): the pseudo-normals and the
     bool corner_ok = false;                                         // boundary share them
@@ -452,6 +453,7 @@ struct oa_ctx {
     int last_plane_rank = 0;         // OA_STAT_PLANE_RANK: eigenvalues the last plane solve kept (loop or oa_point_to_plane)
     int metric = OA_METRIC_POINT;    // oa_set_metric: what the loop minimises
     double gicp_eps = 1e-3;          // oa_set_gicp: the small eigenvalue of the GICP metric's covariances
+    float nbr_radius = 0.f;          // oa_set_neighbor_radius: what limits the neighbourhoods of oa_target_knn and its three consumers; 0 = off
     // weighted steps: a pair's weight is w_vertex * psi(residual).  Off (every weight 1, the unweighted kernels) unless set
     int loss = OA_LOSS_NONE;         // oa_set_robust
     double robust_c = 0.0;           // ... its scale, world units
@@ -5346,13 +5348,18 @@ int knn_call_begin(oa_ctx *c, const char *who, int k, int k_min)
     return OA_OK;
 }
 
+// the squared radius a limited search compares against: the float32 square of the float32 setting, rounded once
+// (radius_count_launch's constant); +inf while the setting is off
+inline float neighbor_r2(const oa_ctx *c) { return c->nbr_radius > 0.f ? c->nbr_radius * c->nbr_radius : INFINITY; }
+
+// r2: neighbor_r2(c) for the calls the setting limits, +inf for those it does not (oa_orient_target_normals)
 template <bool PCA>
-int knn_launch(oa_ctx *c, const KnnTree &t, int k, int32_t *d_idx, float *d_d2, const oa::KnnOrient &orient, float *d_n, float *d_curv)
+int knn_launch(oa_ctx *c, const KnnTree &t, int k, float r2, int32_t *d_idx, float *d_d2, const oa::KnnOrient &orient, float *d_n, float *d_curv)
 {
     const int wpb = oa::knn_waves_per_block(k);
     const int leaves = t.bp.cnt[1];
     const unsigned blocks = (unsigned)std::max(1, std::min((leaves + wpb - 1) / wpb, c->n_cu * 32));
-    hipLaunchKernelGGL((oa::k_bvh_knn<PCA>), dim3(blocks), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, k, d_idx, d_d2,
+    hipLaunchKernelGGL((oa::k_bvh_knn<PCA>), dim3(blocks), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, k, r2, d_idx, d_d2,
                        (const float *)c->tgt.d_tgt_xyz, orient, d_n, d_curv);
     HIPCHK(hipGetLastError());
     return OA_OK;
@@ -5374,7 +5381,7 @@ OA_EXPORT int oa_target_knn(oa_ctx *c, int k, int32_t *out_idx, float *out_d2)
     DevTmp<float> d_d2;
     if (out_idx) HIPCHK(d_idx.alloc(n));
     if (out_d2) HIPCHK(d_d2.alloc(n));
-    if ((rc = knn_launch<false>(c, tree, k, d_idx.p, d_d2.p, oa::KnnOrient{}, nullptr, nullptr))) return rc;
+    if ((rc = knn_launch<false>(c, tree, k, neighbor_r2(c), d_idx.p, d_d2.p, oa::KnnOrient{}, nullptr, nullptr))) return rc;
     if (out_idx) HIPCHK(hipMemcpyAsync(out_idx, d_idx.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
     if (out_d2) HIPCHK(hipMemcpyAsync(out_d2, d_d2.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -5409,7 +5416,7 @@ OA_EXPORT int oa_estimate_target_normals(oa_ctx *c, int k, int orient, const flo
     float *d_n = nullptr;
     if ((rc = new_normals_dest(c, install, out_normals != nullptr, tmp_n, d_n))) return rc;
     if (out_curvature) HIPCHK(d_curv.alloc(nt));
-    if ((rc = knn_launch<true>(c, tree, k, nullptr, nullptr, ko, d_n, d_curv.p))) return rc;
+    if ((rc = knn_launch<true>(c, tree, k, neighbor_r2(c), nullptr, nullptr, ko, d_n, d_curv.p))) return rc;
     if (out_normals) HIPCHK(hipMemcpyAsync(out_normals, d_n, sizeof(float) * 3 * nt, hipMemcpyDeviceToHost, c->stream));
     if (out_curvature) HIPCHK(hipMemcpyAsync(out_curvature, d_curv.p, sizeof(float) * nt, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -5470,6 +5477,67 @@ OA_EXPORT int oa_target_radius_count(oa_ctx *c, double radius, int32_t cap, int3
     if ((rc = radius_count_launch(c, tree, radius, cap, d_count.p))) return rc;
     if (count) HIPCHK(hipMemcpyAsync(count, d_count.p, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return OA_OK;
+}
+
+// ================================================================================================
+// radius-limited neighbourhoods and the cloud's own point spacing (EXTENSION; oa_knn.hpp)
+// ================================================================================================
+OA_EXPORT int oa_set_neighbor_radius(oa_ctx *c, float radius)
+{
+    if (!c) return fail(OA_E_BAD_ARG, "null context");
+    // 0 (either sign): off.  Else finite, > 0, and its float32 square finite -- the constant the searches compare against
+    if (!(radius >= 0.f) || !(radius < INFINITY) || !(radius * radius < INFINITY))
+        return fail(OA_E_BAD_ARG, "oa_set_neighbor_radius: radius = %g (0: no limit; else finite, > 0, and its float32 square finite)", (double)radius);
+    if (radius == 0.f) radius = 0.f;                                 // (-0 reads back as 0)
+    if (radius != c->nbr_radius) {
+        if (const int rc = end_sequence(c)) return rc;
+        c->nbr_radius = radius;
+    }
+    OA_ROUTE_ALL(c, oa_set_neighbor_radius(sub, radius));
+    return OA_OK;
+}
+
+OA_EXPORT int oa_get_neighbor_radius(oa_ctx *c, float *radius)
+{
+    if (!c || !radius) return fail(OA_E_BAD_ARG, "oa_get_neighbor_radius: null argument");
+    *radius = c->nbr_radius;
+    return OA_OK;
+}
+
+OA_EXPORT int oa_target_spacing(oa_ctx *c, oa_spacing_report *rep)
+{
+    static const char who[] = "oa_target_spacing";
+    if (!c || !rep) return fail(OA_E_BAD_ARG, "%s: null argument", who);
+    OA_NOT_MULTI(c, "oa_target_spacing");
+    memset(rep, 0, sizeof *rep);
+    int rc = outlier_call_begin(c, who);
+    if (rc) return rc;
+    const int nt = c->tgt.nt;
+    KnnTree tree;
+    if ((rc = knn_tree(c, tree))) return rc;
+    // the distance to the nearest other vertex = the statistical filter's score at k = 1; its mean and standard deviation by that
+    // filter's fixed-order passes
+    DevTmp<double> d_score, d_row_sum;
+    DevTmp<long long> d_row_n;
+    DevTmp<oa::OutlierStats> d_st;
+    const int rows = oa::outlier_rows((long long)nt);
+    HIPCHK(d_score.alloc((size_t)nt)); HIPCHK(d_row_sum.alloc((size_t)rows)); HIPCHK(d_row_n.alloc((size_t)rows)); HIPCHK(d_st.alloc(1));
+    HIPCHK(hipMemsetAsync(d_st.p, 0, sizeof(oa::OutlierStats), c->stream));
+    if ((rc = knn_score_launch(c, tree, 1, d_score.p))) return rc;
+    const dim3 blk(oa::OUT_THREADS);
+    hipLaunchKernelGGL((oa::k_outlier_rows<0>), dim3((unsigned)rows), blk, 0, c->stream, (const double *)d_score.p, (long long)nt, (const oa::OutlierStats *)d_st.p,
+                       d_row_sum.p, d_row_n.p);
+    hipLaunchKernelGGL((oa::k_outlier_finish<0>), dim3(1), blk, 0, c->stream, (const double *)d_row_sum.p, (const long long *)d_row_n.p, rows, 0.0, d_st.p);
+    hipLaunchKernelGGL((oa::k_outlier_rows<1>), dim3((unsigned)rows), blk, 0, c->stream, (const double *)d_score.p, (long long)nt, (const oa::OutlierStats *)d_st.p,
+                       d_row_sum.p, d_row_n.p);
+    hipLaunchKernelGGL((oa::k_outlier_finish<1>), dim3(1), blk, 0, c->stream, (const double *)d_row_sum.p, (const long long *)d_row_n.p, rows, 0.0, d_st.p);
+    HIPCHK(hipGetLastError());
+    oa::OutlierStats st;
+    if ((rc = read_small(c, &st, d_st.p, sizeof st))) return rc;   // (waits for everything above)
+    if (st.n_finite < 0 || st.n_finite > nt) return fail(OA_E_HIP, "%s: %lld of %d vertices with a spacing (internal)", who, st.n_finite, nt);
+    rep->mean = st.mean; rep->std = st.std;
+    rep->n_finite = (int64_t)st.n_finite; rep->n_nonfinite = (int64_t)nt - (int64_t)st.n_finite;
     return OA_OK;
 }
 
@@ -5705,7 +5773,7 @@ OA_EXPORT int oa_orient_target_normals(oa_ctx *c, int k, double max_dist, int se
     DevTmp<int32_t> d_idx;
     DevTmp<float> d_d2;
     HIPCHK(d_idx.alloc(sne)); HIPCHK(d_d2.alloc(sne));
-    if ((rc = knn_launch<false>(c, tree, k, d_idx.p, d_d2.p, oa::KnnOrient{}, nullptr, nullptr))) return rc;
+    if ((rc = knn_launch<false>(c, tree, k, INFINITY, d_idx.p, d_d2.p, oa::KnnOrient{}, nullptr, nullptr))) return rc;
     // 2. the entries that are edges, their keys, and their places in the order (w, lo, hi): three stable passes, the last key first
     const unsigned v_blocks = (unsigned)((snt + oa::ORI_THREADS - 1) / oa::ORI_THREADS), e_blocks = (unsigned)((sne + oa::ORI_THREADS - 1) / oa::ORI_THREADS);
     const dim3 blk(oa::ORI_THREADS);
@@ -5890,7 +5958,7 @@ OA_EXPORT int oa_target_fpfh(oa_ctx *c, int k, float *out, int keep)
         if (!c->tgt.d_tgt_feat) HIPCHK(dev_malloc(&c->tgt.d_tgt_feat, sizeof(float) * oa::FPFH_DIM * nt));
         d_out = c->tgt.d_tgt_feat;
     } else { HIPCHK(tmp.alloc(oa::FPFH_DIM * nt)); d_out = tmp.p; }
-    if ((rc = knn_launch<false>(c, tree, k, d_idx.p, nullptr, oa::KnnOrient{}, nullptr, nullptr))) return rc;
+    if ((rc = knn_launch<false>(c, tree, k, neighbor_r2(c), d_idx.p, nullptr, oa::KnnOrient{}, nullptr, nullptr))) return rc;
     const dim3 grid((unsigned)((nt + oa::FPFH_THREADS - 1) / oa::FPFH_THREADS)), block(oa::FPFH_THREADS);
     hipLaunchKernelGGL((oa::k_fpfh<false>), grid, block, 0, c->stream, (const float *)c->tgt.d_tgt_xyz, (const float *)c->tgt.d_tgt_n, (const int32_t *)d_idx.p,
                        c->tgt.nt, k, d_spfh.p, (float *)nullptr);
@@ -6443,7 +6511,7 @@ int ensure_boundary(oa_ctx *c, int k, double angle_deg)
             return fail(OA_E_STATE, "the boundary of a point-cloud target needs its normals: call oa_set_target_normals (or oa_set_normals, or install an estimate) first");
         const int rcp = check_boundary_params("the target's boundary", k, angle_deg, c->tgt.nt);
         if (rcp) return rcp;
-        if (c->tgt.bnd_ok && c->tgt.bnd_built_k == k && c->tgt.bnd_built_angle == angle_deg) return OA_OK;
+        if (c->tgt.bnd_ok && c->tgt.bnd_built_k == k && c->tgt.bnd_built_angle == angle_deg && c->tgt.bnd_built_r2 == neighbor_r2(c)) return OA_OK;
     }
     const auto t0 = std::chrono::steady_clock::now();
     c->tgt.bnd_ok = false;
@@ -6465,13 +6533,13 @@ int ensure_boundary(oa_ctx *c, int k, double angle_deg)
         if ((rc = knn_tree(c, tree))) return rc;
         DevTmp<int32_t> d_idx;
         HIPCHK(d_idx.alloc(nv * (size_t)(k + 1)));
-        if ((rc = knn_launch<false>(c, tree, k + 1, d_idx.p, nullptr, oa::KnnOrient{}, nullptr, nullptr))) return rc;
+        if ((rc = knn_launch<false>(c, tree, k + 1, neighbor_r2(c), d_idx.p, nullptr, oa::KnnOrient{}, nullptr, nullptr))) return rc;
         const unsigned blocks = (unsigned)std::max(1, std::min((c->tgt.nt + oa::BND_WPB - 1) / oa::BND_WPB, c->n_cu * 32));
         hipLaunchKernelGGL(oa::k_cloud_boundary, dim3(blocks), dim3(oa::BND_WPB * 64), 0, c->stream, (const float *)c->tgt.d_tgt_xyz, (const float *)c->tgt.d_tgt_n,
                            (const int32_t *)d_idx.p, c->tgt.nt, k, angle_deg * 3.14159265358979323846 / 180.0, c->tgt.d_bnd_vmask);
         HIPCHK(hipGetLastError());
         c->tgt.bnd_n_edges = 0;
-        c->tgt.bnd_built_k = k; c->tgt.bnd_built_angle = angle_deg;
+        c->tgt.bnd_built_k = k; c->tgt.bnd_built_angle = angle_deg; c->tgt.bnd_built_r2 = neighbor_r2(c);
         if ((rc = boundary_count(c, c->tgt.d_bnd_vmask, nv, c->tgt.bnd_n_vertices))) return rc;   // (waits: the temporaries go back behind it)
     }
     if (c->tgt.surface && (rc = boundary_count(c, c->tgt.d_bnd_vmask, nv, c->tgt.bnd_n_vertices))) return rc;

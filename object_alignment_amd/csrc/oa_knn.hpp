@@ -141,20 +141,27 @@ __host__ __device__ inline void pca_normal(const double C[6], double vx, double 
 // The list of ONE query by ONE wave (all 64 lanes call it together; p, leaf and k are wave-uniform): lane j returns the j-th best
 // key of query p, whose own leaf is `leaf` (its 64 vertices: `mine`, one per lane, original index my_idx).  Entries past the
 // last finite distance are KNN_EMPTY.  lds: this wave's scratch (bvh_wave_query's).  1 <= k <= 64.
+// r2 (wave-uniform): only vertices with d2_metric <= r2 are listed, +inf = no limit.  A vertex beyond r2 gets the
+// empty key where it is evaluated, and the cut-off is min(k-th best, r2) from the start -- r2 itself while the list holds fewer
+// than k (the empty key's d2 is +inf).  bvh_prune skips a box only when every vertex inside has d2 > limit STRICTLY (above, and
+// oa_outlier.hpp for a fixed r2), so d2 == r2 is never lost.  A candidate's two tests, d <= r2 and d < +inf, are ONE compare
+// against r2c = min(r2, FLT_MAX) (a finite d is <= FLT_MAX; +inf and NaN are not): with r2 = +inf it is the test d < +inf that
+// stood here before, and the limit is the k-th best itself.
 __device__ __forceinline__ unsigned long long knn_wave_list(const BvhParams &bp, const float4 *__restrict__ boxes, const float4 *__restrict__ prims,
                                                             const BvhLds &lds, int leaf, const float4 mine, uint32_t my_idx, const float *p, int k,
-                                                            int lane)
+                                                            float r2, int lane)
 {
     const int top = bp.levels;
+    const float r2c = fminf(r2, 3.402823466e+38f);
     // the list starts as the query's own leaf: the cut-off is tight at once
     unsigned long long key;
     {
         const float d = d2_metric(p[0], p[1], p[2], mine.x, mine.y, mine.z);
-        key = (d < INFINITY && my_idx != IDX_NONE) ? (((unsigned long long)__float_as_uint(d) << 32) | my_idx) : KNN_EMPTY;
+        key = (d <= r2c && my_idx != IDX_NONE) ? (((unsigned long long)__float_as_uint(d) << 32) | my_idx) : KNN_EMPTY;
         key = knn_wave_sort(key, lane);
     }
     unsigned long long kth = knn_lane_u64(key, k - 1);
-    float lim = __uint_as_float((uint32_t)(kth >> 32));
+    float lim = fminf(__uint_as_float((uint32_t)(kth >> 32)), r2);
     const bool finite = fabsf(p[0]) < INFINITY && fabsf(p[1]) < INFINITY && fabsf(p[2]) < INFINITY;
     int level = top, node = 0;
     bool fresh = true;
@@ -201,7 +208,7 @@ __device__ __forceinline__ unsigned long long knn_wave_list(const BvhParams &bp,
         const float4 c4 = prims[child * BVH_W + lane];
         const float d = d2_metric(p[0], p[1], p[2], c4.x, c4.y, c4.z);
         const uint32_t ci = __float_as_uint(c4.w);
-        const unsigned long long ck = (d < INFINITY && ci != IDX_NONE) ? (((unsigned long long)__float_as_uint(d) << 32) | ci) : KNN_EMPTY;
+        const unsigned long long ck = (d <= r2c && ci != IDX_NONE) ? (((unsigned long long)__float_as_uint(d) << 32) | ci) : KNN_EMPTY;
         unsigned long long cand = __ballot(ck < kth);
         while (cand) {
             const int b = __ffsll((long long)cand) - 1;
@@ -212,7 +219,7 @@ __device__ __forceinline__ unsigned long long knn_wave_list(const BvhParams &bp,
             if (key > cnew) key = (lane > 0 && up > cnew) ? up : cnew;
             kth = knn_lane_u64(key, k - 1);
         }
-        lim = __uint_as_float((uint32_t)(kth >> 32));
+        lim = fminf(__uint_as_float((uint32_t)(kth >> 32)), r2);
     }
     return key;
 }
@@ -221,9 +228,10 @@ __device__ __forceinline__ unsigned long long knn_wave_list(const BvhParams &bp,
 // out_idx / out_d2 (nt x k, the caller's vertex order, original indices; unfilled entries -1 / +inf) may be null.
 // PCA: xyz = the target in the caller's order (nt x 3), out_n (nt x 3) / out_curv (nt), each may be null.
 // 1 <= k <= 64.  Every real vertex is the query of exactly one (wave, q): every output row is written exactly once.
+// r2: the neighbourhood's squared radius (knn_wave_list), +inf = the k nearest however far; a shorter row is padded -1 / +inf.
 template <bool PCA>
 __global__ __launch_bounds__(KNN_WPB * 64) void k_bvh_knn(BvhParams bp, const float4 *__restrict__ boxes, const float4 *__restrict__ prims,
-                                                          int k, int32_t *__restrict__ out_idx, float *__restrict__ out_d2,
+                                                          int k, float r2, int32_t *__restrict__ out_idx, float *__restrict__ out_d2,
                                                           const float *__restrict__ xyz, KnnOrient orient, float *__restrict__ out_n,
                                                           float *__restrict__ out_curv)
 {
@@ -244,7 +252,7 @@ __global__ __launch_bounds__(KNN_WPB * 64) void k_bvh_knn(BvhParams bp, const fl
             const uint32_t qi = (uint32_t)__builtin_amdgcn_readlane((int)my_idx, q);
             if (qi == IDX_NONE) break;                               // padding closes the last leaf
             const float p[3] = { knn_lane_f(mine.x, q), knn_lane_f(mine.y, q), knn_lane_f(mine.z, q) };
-            const unsigned long long key = knn_wave_list(bp, boxes, prims, lds, leaf, mine, my_idx, p, k, lane);
+            const unsigned long long key = knn_wave_list(bp, boxes, prims, lds, leaf, mine, my_idx, p, k, r2, lane);
             if (lane < k) {
                 const int32_t ni = (int32_t)(uint32_t)key;           // IDX_NONE -> -1
                 if (out_idx) out_idx[(long long)qi * k + lane] = ni;

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(KNN_WPB * 64) void k_bvh_knn_score(BvhParams bp, co
             const uint32_t qi = (uint32_t)__builtin_amdgcn_readlane((int)my_idx, q);
             if (qi == IDX_NONE) break;                               // padding closes the last leaf
             const float p[3] = { knn_lane_f(mine.x, q), knn_lane_f(mine.y, q), knn_lane_f(mine.z, q) };
-            const unsigned long long key = knn_wave_list(bp, boxes, prims, lds, leaf, mine, my_idx, p, k1, lane);
+            const unsigned long long key = knn_wave_list(bp, boxes, prims, lds, leaf, mine, my_idx, p, k1, INFINITY, lane);
             // the filled entries come first (KNN_EMPTY is the largest key)
             const int m = __popcll(__ballot(lane < k1 && key != KNN_EMPTY));
             const double root = sqrt((double)__uint_as_float((uint32_t)(key >> 32)));

@@ -5,6 +5,7 @@ Holds no arithmetic of its own -- every number comes back from liboa_icp.so.
 from __future__ import annotations
 
 import ctypes as C
+from contextlib import contextmanager
 from dataclasses import dataclass
 
 import numpy as np
@@ -214,6 +215,21 @@ def _radius_count_args(radius, cap=0, name="target_radius_count"):
     if not _real(radius) or not 0 < radius < float("inf"):
         raise ValueError("%s: radius = %r (finite and > 0)" % (name, radius))
     return float(radius), _whole(cap, name, "cap", 0, 2**31 - 1)
+
+
+def _radius_arg(radius, name="set_neighbor_radius", what="radius", off_ok=False):
+    """A neighbour radius, checked before any call reaches the library: a number, finite and > 0, that is still > 0 as a float32 and
+    whose float32 square is finite (what the searches compare against).  off_ok: 0 is taken too and means "no limit".  Returns
+    the float32 value as a float."""
+    ok = _real(radius) and (radius > 0 or (off_ok and radius == 0))
+    if ok and radius != 0:
+        with np.errstate(over="ignore"):
+            r = np.float32(radius)
+            ok = bool(r > 0 and np.isfinite(r) and np.isfinite(r * r))
+    if not ok:
+        raise ValueError("%s: %s = %r (%sfinite and > 0, at most 1.8e19: its float32 square must be finite)"
+                         % (name, what, radius, "0 = no limit, else " if off_ok else ""))
+    return float(np.float32(radius))
 
 
 CLUSTER_KEEP = {"clustered": capi.OA_CLUSTER_KEEP_CLUSTERED, "largest": capi.OA_CLUSTER_KEEP_LARGEST,
@@ -441,21 +457,68 @@ class IcpEngine:
 
     ORIENTS = {"none": capi.OA_ORIENT_NONE, "toward": capi.OA_ORIENT_TOWARD, "away": capi.OA_ORIENT_AWAY}
 
-    def target_knn(self, k):
+    def set_neighbor_radius(self, radius):
+        """Limit the neighbourhoods of target_knn, estimate_target_normals, target_fpfh and the cloud criterion of target_boundary
+        / set_reject_boundary to the vertices within `radius` (the target's own units; the float32 metric against (float32
+        radius)^2, as target_radius_count): rows are "the k nearest among those", shorter rows padded with -1 / +inf -- so that
+        neighbours are not taken from the other side of a thin wall, the next tooth or across a hole.  0 or None: no limit (the
+        default).  orient_target_normals (its own max_dist), the outlier, clustering and spacing calls do not look at it.
+        Survives uploads and set_matrices; multi-device engines hand it to every child; neighbor_radius reads it back."""
+        r = 0.0 if radius is None else _radius_arg(radius, off_ok=True)
+        self._chk(self._L.oa_set_neighbor_radius(self._h, r))
+
+    @property
+    def neighbor_radius(self) -> float:
+        """The neighbour radius in force (the float32 the library holds); 0.0 = no limit."""
+        v = C.c_float(0.0)
+        self._chk(self._L.oa_get_neighbor_radius(self._h, C.byref(v)))
+        return float(v.value)
+
+    @contextmanager
+    def _radius_for(self, radius, name):
+        """radius=None: the engine's own setting holds.  Else that radius (checked before the library is touched) for the calls
+        inside, and the previous setting again behind them, refused calls included."""
+        if radius is None:
+            yield
+            return
+        r = _radius_arg(radius, name)
+        prev = self.neighbor_radius
+        self.set_neighbor_radius(r)
+        try:
+            yield
+        finally:
+            self.set_neighbor_radius(prev)
+
+    def target_spacing(self):
+        """Vertex-mode targets: the cloud's own point spacing -- {"mean", "std"} of the distance from every vertex to the nearest
+        other vertex (a duplicate gives 0; fixed-order fp64 sums: two calls give the same bits), "n_finite" the vertices that
+        have one and "n_nonfinite" the others (a non-finite coordinate).  What a neighbour radius, a voxel edge or an eps is a
+        multiple of.  The neighbour radius does not apply.  Single-device contexts."""
+        rep = capi.SpacingReport()
+        self._chk(self._L.oa_target_spacing(self._h, C.byref(rep)))
+        return {"mean": float(rep.mean), "std": float(rep.std), "n_finite": int(rep.n_finite), "n_nonfinite": int(rep.n_nonfinite)}
+
+    def target_knn(self, k, radius=None):
         """Vertex-mode targets: the k nearest target vertices of every target vertex (itself included), exact and ordered by
-        (d2, index): (idx int32 (nt, k), d2 float32 (nt, k)), in the caller's vertex order.  1 <= k <= min(64, nt)."""
+        (d2, index): (idx int32 (nt, k), d2 float32 (nt, k)), in the caller's vertex order.  1 <= k <= min(64, nt).
+        radius: this neighbour radius for the call (set_neighbor_radius; None: the engine's setting)."""
+        r = None if radius is None else _radius_arg(radius, "target_knn")
         k = int(k)
         shape = (max(1, self.n_target), max(1, k))
         idx = np.empty(shape, np.int32)
         d2 = np.empty(shape, np.float32)
-        self._chk(self._L.oa_target_knn(self._h, k, idx.ctypes.data_as(C.POINTER(C.c_int32)), capi.fptr(d2)))
+        with self._radius_for(r, "target_knn"):
+            self._chk(self._L.oa_target_knn(self._h, k, idx.ctypes.data_as(C.POINTER(C.c_int32)), capi.fptr(d2)))
         return idx[: self.n_target], d2[: self.n_target]
 
-    def estimate_target_normals(self, k=16, orient="none", orient_point=None, install=True):
+    def estimate_target_normals(self, k=16, orient="none", orient_point=None, install=True, radius=None):
         """Vertex-mode targets: PCA normals from every vertex's k nearest neighbours, computed on the device: (normals float32
         (nt, 3), curvature float32 (nt,)).  orient: 'none' (canonical sign), 'toward' orient_point (a scanner position) or 'away'
         from it (an interior point; None = the target's centroid).  install: the normals become the target's (as after
-        set_target_normals) without a host round trip.  Degenerate neighbourhoods give the zero normal.  3 <= k <= min(64, nt)."""
+        set_target_normals) without a host round trip.  Degenerate neighbourhoods give the zero normal.  3 <= k <= min(64, nt).
+        radius: this neighbour radius for the call (set_neighbor_radius; None: the engine's setting); a vertex with fewer than
+        three neighbours inside it gets the zero normal."""
+        r = None if radius is None else _radius_arg(radius, "estimate_target_normals")
         if isinstance(orient, str):
             if orient not in self.ORIENTS:
                 raise ValueError("orient %r (use 'none', 'toward' or 'away')" % (orient,))
@@ -463,8 +526,9 @@ class IcpEngine:
         pt = capi.as_f32(orient_point).reshape(3) if orient_point is not None else None
         nrm = np.empty((max(1, self.n_target), 3), np.float32)
         curv = np.empty(max(1, self.n_target), np.float32)
-        self._chk(self._L.oa_estimate_target_normals(self._h, int(k), int(orient), capi.fptr(pt) if pt is not None else None,
-                                                      int(bool(install)), capi.fptr(nrm), capi.fptr(curv)))
+        with self._radius_for(r, "estimate_target_normals"):
+            self._chk(self._L.oa_estimate_target_normals(self._h, int(k), int(orient), capi.fptr(pt) if pt is not None else None,
+                                                          int(bool(install)), capi.fptr(nrm), capi.fptr(curv)))
         return nrm[: self.n_target], curv[: self.n_target]
 
     def orient_target_normals(self, k=8, max_dist=0.0, seed="away", point=None, normals=None, install=True):
@@ -612,19 +676,23 @@ class IcpEngine:
         stat("boundary_rejected") the pairs the last step dropped for it."""
         self._chk(self._L.oa_set_reject_boundary(self._h, int(bool(on)), int(k), float(angle_deg)))
 
-    def target_boundary(self, k=16, angle_deg=90.0):
+    def target_boundary(self, k=16, angle_deg=90.0, radius=None):
         """The boundary of the resident target, built on the device if it is not there yet: (vertex_mask uint8 (n_verts,),
         edge_mask uint8 (n_tris,) or None).  Mesh targets: exact -- bit j of edge_mask[t] = local edge j (ab, bc, ca) of triangle
         t belongs to exactly one triangle; vertex_mask = the ends of such edges; k and angle_deg are ignored.  Cloud targets (with
         normals installed): vertex_mask by the angle criterion -- the largest gap between the tangent-plane directions to the k
         nearest neighbours exceeds angle_deg -- and edge_mask is None.  3 <= k <= min(63, nt - 1), 0 < angle_deg < 360.
-        stat("target_boundary") / stat("boundary_vertices") / stat("boundary_edges") describe the built masks."""
+        stat("target_boundary") / stat("boundary_vertices") / stat("boundary_edges") describe the built masks.
+        radius (cloud targets): this neighbour radius for the call (set_neighbor_radius; None: the engine's setting) -- the k
+        nearest no longer reach across a hole narrower than their spread; fewer than three neighbours inside it: on the rim."""
+        r = None if radius is None else _radius_arg(radius, "target_boundary")
         u8 = C.POINTER(C.c_uint8)
         vm = np.empty(max(1, self.n_target), np.uint8)
         n_tris = int(self.stat("n_tris")) if int(self.stat("surface")) else 0
         em = np.empty(max(1, n_tris), np.uint8) if n_tris > 0 else None
-        self._chk(self._L.oa_target_boundary(self._h, int(k), float(angle_deg), vm.ctypes.data_as(u8),
-                                             em.ctypes.data_as(u8) if em is not None else None))
+        with self._radius_for(r, "target_boundary"):
+            self._chk(self._L.oa_target_boundary(self._h, int(k), float(angle_deg), vm.ctypes.data_as(u8),
+                                                 em.ctypes.data_as(u8) if em is not None else None))
         return vm[: self.n_target], (em[:n_tris] if em is not None else None)
 
     def set_source_weights(self, weights):
@@ -883,13 +951,16 @@ class IcpEngine:
         out["matrix_world"] = self.matrix_world()
         return out
 
-    def target_fpfh(self, k=16, keep=True):
+    def target_fpfh(self, k=16, keep=True, radius=None):
         """Vertex-mode targets with normals: the Fast Point Feature Histogram of every target vertex from its k nearest
         neighbours, (nt, 33) float32; an all-zero row means "no descriptor".  keep: the descriptors stay on the device for
-        feature_candidates(tgt_feat=None) until the next set_target.  4 <= k <= min(64, nt)."""
+        feature_candidates(tgt_feat=None) until the next set_target.  4 <= k <= min(64, nt).
+        radius: this neighbour radius for the call (set_neighbor_radius; None: the engine's setting)."""
         k = _fpfh_k(k)
+        r = None if radius is None else _radius_arg(radius, "target_fpfh")
         out = np.empty((max(1, self.n_target), capi.OA_FPFH_DIM), np.float32)
-        self._chk(self._L.oa_target_fpfh(self._h, k, capi.fptr(out), int(bool(keep))))
+        with self._radius_for(r, "target_fpfh"):
+            self._chk(self._L.oa_target_fpfh(self._h, k, capi.fptr(out), int(bool(keep))))
         return out[: self.n_target]
 
     def match_features(self, fa, fb):

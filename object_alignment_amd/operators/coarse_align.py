@@ -42,8 +42,15 @@ class CoarseSettings:
     # method "features" / "both": None = descriptors of every target and source vertex; a length in world units = descriptors
     # of the two clouds' voxel downsamples of that edge (the coarse stage needs no more, and the matching is quadratic)
     voxel: float | None = None
+    # method "features" / "both": a length in world units that limits the neighbourhoods of the descriptors, and of the normals
+    # estimated for them, on both clouds (IcpEngine.set_neighbor_radius; each cloud's matrix carries it to its own units); None
+    # = the feature_k / normal_k nearest however far
+    feature_radius: object = None
 
     def __post_init__(self):
+        if self.feature_radius is not None:
+            from ..engine import _radius_arg
+            _radius_arg(self.feature_radius, "CoarseSettings", "feature_radius")
         if self.method not in METHODS:
             raise ValueError("CoarseSettings.method = %r (one of %s)" % (self.method, ", ".join(repr(m) for m in METHODS)))
         for name, lo, hi in (("feature_k", 4, 64), ("normal_k", 3, 64), ("n_hyp", 1, 65535), ("seed", 0, 0xFFFFFFFF)):
@@ -78,16 +85,33 @@ def default_thresh(target_xyz, mx_base) -> float:
     return THRESH_FRACTION * float(np.linalg.norm(w.max(axis=0) - w.min(axis=0)))
 
 
-def feature_poses(engine, settings: CoarseSettings, source_xyz) -> tuple:
+def _feature_radii(settings, mx_align, mx_base):
+    """({} or {"radius": r}) for the target's calls and for the source's: settings.feature_radius in each cloud's own units."""
+    r = getattr(settings, "feature_radius", None)
+    if r is None:
+        return {}, {}
+    from ..engine import _radius_arg
+    from .icp_align import local_radius
+    r = _radius_arg(r, "CoarseSettings", "feature_radius")
+    return ({"radius": local_radius(r, mx_base, "feature_radius")}, {"radius": local_radius(r, mx_align, "feature_radius")})
+
+
+def feature_poses(engine, settings: CoarseSettings, source_xyz, mx_base=None) -> tuple:
     """Candidate poses from matched FPFH descriptors on an engine whose vertex-mode target, source and matrices are set:
-    ((n, 4, 4) float32, report dict).  Installs estimated target normals (away from the centroid) when the target has none."""
+    ((n, 4, 4) float32, report dict).  Installs estimated target normals (away from the centroid) when the target has none.
+    mx_base: the target's matrix, what carries settings.feature_radius to the target's units (needed with that setting)."""
     from .. import fpfh
+    if getattr(settings, "feature_radius", None) is not None and mx_base is None:
+        raise ValueError("CoarseSettings.feature_radius needs mx_base")
+    kw_tgt, kw_src = {}, {}
+    if getattr(settings, "feature_radius", None) is not None:
+        kw_tgt, kw_src = _feature_radii(settings, engine.matrix_world(), mx_base)
     rep = {"estimated_target_normals": False}
     if engine.stat("target_normals") == 0.0:
-        engine.estimate_target_normals(k=min(settings.normal_k, engine.n_target), orient="away", install=True)
+        engine.estimate_target_normals(k=min(settings.normal_k, engine.n_target), orient="away", install=True, **kw_tgt)
         rep["estimated_target_normals"] = True
-    engine.target_fpfh(k=min(settings.feature_k, engine.n_target), keep=True)
-    src_feat = fpfh(source_xyz, k=settings.feature_k, normal_k=settings.normal_k, device=engine.device)
+    engine.target_fpfh(k=min(settings.feature_k, engine.n_target), keep=True, **kw_tgt)
+    src_feat = fpfh(source_xyz, k=settings.feature_k, normal_k=settings.normal_k, device=engine.device, **kw_src)
     poses, frep = engine.feature_candidates(src_feat, None, n_hyp=settings.n_hyp, ratio=settings.ratio, mutual=settings.mutual,
                                             edge_tol=settings.edge_tol, seed=settings.seed)
     rep.update(("feature_" + k, v) for k, v in frep.items())
@@ -108,6 +132,7 @@ def feature_poses_downsampled(engine, settings: CoarseSettings, target_xyz, mx_b
     rep = {"estimated_target_normals": True, "feature_voxel": h, "feature_n_target": 0, "feature_n_source": 0, "feature_n_pairs": 0,
            "feature_n_accepted": 0}
     none = np.zeros((0, 4, 4), np.float32)
+    kw_tgt, kw_src = _feature_radii(settings, mx_align, mx_base)
     with IcpEngine(engine.device) as side:
         down_tgt = side.voxel_downsample(target_xyz, h / world_scale(mx_base))["xyz"]
         down_src = side.voxel_downsample(source_xyz, h / world_scale(mx_align))["xyz"]
@@ -116,9 +141,9 @@ def feature_poses_downsampled(engine, settings: CoarseSettings, target_xyz, mx_b
             rep["feature_note"] = "%d target and %d source rows after the downsample (4 needed)" % (len(down_tgt), len(down_src))
             return none, rep
         side.set_target(down_tgt)
-        side.estimate_target_normals(k=min(settings.normal_k, len(down_tgt)), orient="away", install=True)
-        side.target_fpfh(k=min(settings.feature_k, len(down_tgt)), keep=True)
-        src_feat = fpfh(down_src, k=settings.feature_k, normal_k=settings.normal_k, device=engine.device)
+        side.estimate_target_normals(k=min(settings.normal_k, len(down_tgt)), orient="away", install=True, **kw_tgt)
+        side.target_fpfh(k=min(settings.feature_k, len(down_tgt)), keep=True, **kw_tgt)
+        src_feat = fpfh(down_src, k=settings.feature_k, normal_k=settings.normal_k, device=engine.device, **kw_src)
         side.set_source(down_src, stride=1)
         side.set_matrices(mx_align, mx_base)
         poses, frep = side.feature_candidates(src_feat, None, n_hyp=settings.n_hyp, ratio=settings.ratio, mutual=settings.mutual,
@@ -139,7 +164,7 @@ def coarse_stage(engine, settings: CoarseSettings, target_xyz, mx_base, source_x
     if source_xyz is None:
         raise ValueError("CoarseSettings.method = %r needs source_xyz" % (settings.method,))
     if settings.voxel is None:
-        poses, frep = feature_poses(engine, settings, source_xyz)
+        poses, frep = feature_poses(engine, settings, source_xyz, mx_base=mx_base)
     else:
         poses, frep = feature_poses_downsampled(engine, settings, target_xyz, mx_base, source_xyz)
     status = "ok"

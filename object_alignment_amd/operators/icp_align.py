@@ -158,6 +158,19 @@ class IcpSettings:
     # segment_source: the selection, after clean_source, goes through object_alignment_amd.cluster_dbscan.  None = off.  One GPU
     segment_target: object = None
     segment_source: object = None
+    # nor these: a radius, in world units like min_start, that limits the neighbourhoods of per-vertex estimates on a raw cloud
+    # (IcpEngine.set_neighbor_radius) -- the k nearest neighbours otherwise reach the other side of a thin wall, the next tooth or
+    # across a hole.  normal_radius: the normals run() estimates, the target's and the source's (normal_k nearest within it; fewer
+    # than three: the zero normal, which the metrics drop).  boundary_radius: the cloud criterion of reject_boundary.  Each is
+    # carried to the cloud's own units by its matrix.  None = the k nearest however far, as before
+    normal_radius: object = None
+    boundary_radius: object = None
+
+    def __post_init__(self):
+        from ..engine import _radius_arg
+        for name in ("normal_radius", "boundary_radius"):       # (checked again when a run reads them: neighbor_radii_of)
+            if getattr(self, name) is not None:
+                _radius_arg(getattr(self, name), "IcpSettings", name)
 
 
 @dataclass
@@ -358,6 +371,21 @@ def sample_normal_space_of(settings):
     return int(m), int(g)
 
 
+def neighbor_radii_of(settings):
+    """(normal_radius, boundary_radius) from IcpSettings, checked: each None (off) or a finite length > 0 in world units."""
+    from ..engine import _radius_arg
+    out = []
+    for name in ("normal_radius", "boundary_radius"):
+        v = getattr(settings, name, None)
+        out.append(None if v is None else _radius_arg(v, "IcpSettings", name))
+    return tuple(out)
+
+
+def local_radius(radius, mx, what):
+    """A world-space radius in the units of the cloud that mx places (None stays None), as ClusterSettings.kwargs carries eps."""
+    return None if radius is None else radius / _local_scale(mx, what)
+
+
 NORMAL_ORIENTS = ("away", "consistent")
 
 
@@ -369,13 +397,13 @@ def normal_orient_of(settings) -> str:
     return v
 
 
-def estimate_consistent_normals(xyz, k, device=0):
-    """PCA normals of a cloud with one consistent sign: the estimate, then IcpEngine.orient_target_normals on it (seed away from
-    the centroid), in a context of its own."""
+def estimate_consistent_normals(xyz, k, device=0, radius=None):
+    """PCA normals of a cloud with one consistent sign: the estimate (neighbours within `radius` of xyz's own units, None: the k
+    nearest), then IcpEngine.orient_target_normals on it (seed away from the centroid), in a context of its own."""
     from ..engine import IcpEngine
     with IcpEngine(int(device)) as eng:
         eng.set_target(xyz)
-        eng.estimate_target_normals(k=k, orient="none", install=True)
+        eng.estimate_target_normals(k=k, orient="none", install=True, radius=radius)
         return eng.orient_target_normals(k=k, max_dist=0.0, seed="away", install=False)[0]
 
 
@@ -619,8 +647,11 @@ class IcpAlign:
         numbering (the target's vertices; positions within the selection), composed with a preceding clean step --, "label" and
         "sizes" over the cloud the clustering saw, and the report; None while both settings are off.
         deviation: a DeviationSettings -- after the loop the deviation report and its arrays are taken at the final pose on the same
-        engine (over the points the loop used) and attached as RunResult.deviation; None: nothing else changes."""
+        engine (over the points the loop used) and attached as RunResult.deviation; None: nothing else changes.
+        settings.normal_radius / boundary_radius: world-space lengths that limit the neighbourhoods of the estimated normals (the
+        target's by mx_base's scale, the source's by mx_align's) and of the cloud criterion behind reject_boundary (mx_base's)."""
         s = self.settings
+        normal_radius, boundary_radius = neighbor_radii_of(s)
         estimate = isinstance(target_normals, str)
         if estimate and target_normals != "estimate":
             raise ValueError("target_normals %r (an array of normals, or 'estimate')" % (target_normals,))
@@ -647,6 +678,8 @@ class IcpAlign:
             # make_pairs returns None and `(A, B, d_stats) = None` raises   (:101, general.py:277)
             raise TypeError("cannot unpack non-iterable NoneType object")
         eng = self.engine
+        normal_r_tgt = local_radius(normal_radius, mx_base, "normal_radius") if estimate else None
+        boundary_r = local_radius(boundary_radius, mx_base, "boundary_radius") if (boundary_of(s)[0] and target_tris is None) else None
         cleaning = {"target": None, "source": None}
         self.last_cleaning = cleaning if (clean_target is not None or clean_source is not None) else None
         segmentation = {"target": None, "source": None}
@@ -667,7 +700,10 @@ class IcpAlign:
             if target_kept is not None and target_normals is not None and not estimate:
                 target_normals = np.asarray(target_normals).reshape(-1, 3)[target_kept]
             if estimate:
-                eng.estimate_target_normals(k=int(getattr(s, "normal_k", 16)), orient="away", install=True)
+                if normal_r_tgt is None:
+                    eng.estimate_target_normals(k=int(getattr(s, "normal_k", 16)), orient="away", install=True)
+                else:
+                    eng.estimate_target_normals(k=int(getattr(s, "normal_k", 16)), orient="away", install=True, radius=normal_r_tgt)
                 if consistent:
                     eng.orient_target_normals(k=int(getattr(s, "normal_k", 16)), max_dist=0.0, seed="away", install=True)
             elif target_normals is not None:
@@ -690,10 +726,11 @@ class IcpAlign:
         estimate_source = isinstance(source_normals, str)
 
         def estimated_source_normals():
+            kw = {} if normal_radius is None else {"radius": local_radius(normal_radius, mx_align, "normal_radius")}
             if consistent:
-                return estimate_consistent_normals(source_xyz, int(getattr(s, "normal_k", 16)))
+                return estimate_consistent_normals(source_xyz, int(getattr(s, "normal_k", 16)), **kw)
             from .. import estimate_normals
-            return estimate_normals(source_xyz, k=int(getattr(s, "normal_k", 16)))[0]
+            return estimate_normals(source_xyz, k=int(getattr(s, "normal_k", 16)), **kw)[0]
 
         # the source's normals are estimated ONCE: in front of the upload when the sample needs them, else behind it, where the
         # estimate has always stood (so that a run without the sample makes its calls in the order it always did)
@@ -717,8 +754,19 @@ class IcpAlign:
             if target_kept is not None:                        # (the coarse stage thins the target it is given: the resident one)
                 target_xyz = _host_rows(target_xyz)[target_kept]
             self.last_coarse = coarse_stage(eng, coarse, target_xyz, mx_base, source_xyz=source_xyz)
-        res = eng.run(iters=s.icp_iterations, thresh=thresh, target_d=s.target_d, use_target=s.use_target,
-                      with_scale=(s.align_meth == "1"), early_exit=early_exit)
+        if boundary_r is None:
+            res = eng.run(iters=s.icp_iterations, thresh=thresh, target_d=s.target_d, use_target=s.use_target,
+                          with_scale=(s.align_meth == "1"), early_exit=early_exit)
+        else:
+            # the loop builds the target's mask when it starts: the radius is the engine's setting for that long, and the mask
+            # stays keyed by it (target_boundary(radius=...) afterwards returns the mask the loop used)
+            prev = eng.neighbor_radius
+            eng.set_neighbor_radius(boundary_r)
+            try:
+                res = eng.run(iters=s.icp_iterations, thresh=thresh, target_d=s.target_d, use_target=s.use_target,
+                              with_scale=(s.align_meth == "1"), early_exit=early_exit)
+            finally:
+                eng.set_neighbor_radius(prev)
         if deviation is not None:
             res.deviation = eng.deviation(**deviation.kwargs(thresh))
             if target_kept is not None and res.deviation.get("idx") is not None:
