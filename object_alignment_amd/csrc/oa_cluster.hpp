@@ -12,8 +12,8 @@
 //
 //   k_bvh_radius_count<true>  (oa_outlier.hpp, as it is) with cap = min_points: count saturates at min_points, so core_i = count_i >=
 //                    min_points and count_i <= 1 marks a vertex nobody but itself is near.
-//   k_bvh_cluster<CL_LINK>    k_bvh_radius_count's traversal: one wave per leaf, the leaf's vertices as queries one after the
-//                    other, the same bvh_prune test, every hit one evaluation of d2_metric.  Only CORE queries descend.  At a
+//   k_bvh_cluster<CL_LINK>    k_bvh_radius_count's launch shape and walk (bvh_radius_walk, oa_outlier.hpp): one wave per leaf, the
+//                    leaf's vertices as queries one after the other, every hit one evaluation of d2_metric.  Only CORE queries descend.  At a
 //                    visited leaf the lanes whose vertex is a hit, is core and has a LOWER index than the query are joined with
 //                    the query.  Lower index alone suffices: the edge {i, j}, j < i, is seen by query i (metric and pruning are
 //                    symmetric), so every edge is linked exactly once.  Joining is oa_unionfind.hpp's lock-free union-find on
@@ -25,7 +25,7 @@
 //                    differs from it issue a compare-and-swap.
 //   k_cluster_flatten         a separate launch, so plain loads see the finished forest: root_i for every core vertex = the
 //                    LOWEST core index of its component, whichever order the waves ran in.
-//   k_bvh_cluster<CL_BORDER>  the same traversal for the non-core queries with count >= 2: border_root_i = the minimum of root_j
+//   k_bvh_cluster<CL_BORDER>  the same walk for the non-core queries with count >= 2: border_root_i = the minimum of root_j
 //                    over the core hits, a wave minimum per leaf, no atomics.  Labels ascend with the root, so the lowest root is
 //                    the lowest label.
 //   k_cluster_label / _largest / _keep   dense labels from the scan of the root flags (scan_counts_ll: ascending root order), sizes
@@ -72,59 +72,28 @@ __global__ __launch_bounds__(KNN_WPB * 64) void k_bvh_cluster(BvhParams bp, cons
     __shared__ int s_node[KNN_WPB][BVH_MAX_LEVELS + 1];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     const BvhLds lds{ nullptr, 0, &s_mask[w][0], 1, &s_node[w][0], 1 };      // (no bounds: nothing is ordered by them)
-    const int top = bp.levels;
     bool spent = false;
 
     for (int leaf = blockIdx.x * wpb + w; leaf < bp.cnt[1]; leaf += gridDim.x * wpb) {     // (wave-uniform)
         const float4 mine = prims[(long long)leaf * BVH_W + lane];
         const uint32_t my_idx = __float_as_uint(mine.w);
         for (int q = 0; q < BVH_W; ++q) {
-            const uint32_t qi = (uint32_t)__builtin_amdgcn_readlane((int)my_idx, q);
-            if (qi == IDX_NONE) break;                               // padding closes the last leaf
+            uint32_t qi; float p[3];
+            if (!knn_leaf_query(mine, my_idx, q, qi, p)) break;
             const int qc = count[qi];                                // (wave-uniform; 0 for a non-finite query)
             if (MODE == CL_LINK ? qc < min_points : (qc >= min_points || qc < 2)) continue;
-            const float p[3] = { knn_lane_f(mine.x, q), knn_lane_f(mine.y, q), knn_lane_f(mine.z, q) };
             uint32_t qr = MODE == CL_LINK ? qi : IDX_NONE;            // LINK: the query's running root; BORDER: the lowest root so far
-            int level = top, node = 0;
-            bool fresh = true;
-            for (;;) {
-                if (fresh) {
-                    const long long ch = (long long)node * BVH_W + lane;
-                    bool pass = false;
-                    if (ch < bp.cnt[level]) {
-                        const float4 lo = boxes[2 * ((long long)bp.off[level] + ch)], hi = boxes[2 * ((long long)bp.off[level] + ch) + 1];
-                        const float lb = bvh_box_bound<false>(p, lo, hi, 0.0);
-                        pass = lb < INFINITY && !bvh_prune(lb, r2);
-                    }
-                    const unsigned long long m = __ballot(pass);
-                    if (lane == 0) { *lds.mask(level) = m; *lds.node(level) = node; }
-                    fresh = false;
-                }
-                const unsigned long long m = *lds.mask(level);
-                if (m == 0ull) {
-                    if (level == top) break;
-                    ++level;
-                    continue;
-                }
-                const int pick = __ffsll((long long)m) - 1;
-                if (lane == 0) *lds.mask(level) = m & (m - 1ull);
-                const long long child = (long long)*lds.node(level) * BVH_W + pick;
-                if (level > 1) {
-                    --level;
-                    node = (int)child;
-                    fresh = true;
-                    continue;
-                }
+            bvh_radius_walk(bp, boxes, lds, p, r2, lane, [&](long long child) {
                 // leaf: 64 vertices, one per lane
                 const float4 c4 = prims[child * BVH_W + lane];
                 const float d = d2_metric(p[0], p[1], p[2], c4.x, c4.y, c4.z);
                 const uint32_t ci = __float_as_uint(c4.w);
                 bool hit = d <= r2 && d < INFINITY && ci != IDX_NONE && (MODE == CL_BORDER || ci < qi);
                 if (hit) hit = count[ci] >= min_points;              // core
-                if (__ballot(hit) == 0ull) continue;
+                if (__ballot(hit) == 0ull) return false;
                 if (MODE == CL_BORDER) {
                     qr = min(qr, wave_min_u32(hit ? root[ci] : IDX_NONE));
-                    continue;
+                    return false;
                 }
                 int budget = max_steps, qbudget = max_steps;
                 const uint32_t r = hit ? uf_find_compress<UfDeviceAtomics>(parent, ci, budget) : IDX_NONE;
@@ -134,7 +103,8 @@ __global__ __launch_bounds__(KNN_WPB * 64) void k_bvh_cluster(BvhParams bp, cons
                 if (lane == 0 && qr != lowest) uf_link<UfDeviceAtomics>(parent, qr, lowest, qbudget);
                 qr = lowest;
                 spent |= budget <= 0 || qbudget <= 0;
-            }
+                return false;                                        // (a cluster pass visits every leaf in reach)
+            });
             if (MODE == CL_BORDER) { if (lane == 0) border_root[qi] = qr; }
             else if (lane == 0 && qr != qi) atomicMin(&parent[qi], qr);      // (the next query that meets qi walks one step)
         }

@@ -91,7 +91,7 @@
 
 // ---- k nearest target vertices of every target vertex / PCA normals from them (oa_knn.hpp): oa_fam_knn.hip ----------
 // (+ the fixed-radius count of oa_outlier.hpp; its k_bvh_knn_score is a plain kernel that oa_outlier.hpp defines in this unit
-//  alone and declares everywhere else; + the link and border passes of oa_cluster.hpp, the same traversal)
+//  alone and declares everywhere else; + the link and border passes of oa_cluster.hpp, which share its bvh_radius_walk)
 #define OA_FAMILY_KNN(X) OA_K(X, k_bvh_knn, OA_SIG_BVH_KNN, false) OA_K(X, k_bvh_knn, OA_SIG_BVH_KNN, true)                   \
     OA_K(X, k_bvh_radius_count, OA_SIG_BVH_RADIUS_COUNT, false) OA_K(X, k_bvh_radius_count, OA_SIG_BVH_RADIUS_COUNT, true)    \
     OA_K(X, k_bvh_cluster, OA_SIG_BVH_CLUSTER, CL_LINK) OA_K(X, k_bvh_cluster, OA_SIG_BVH_CLUSTER, CL_BORDER)

@@ -1607,11 +1607,12 @@ void search_radius(const oa_ctx *c, const float *mx2, double thresh, double &cut
     }
 }
 
+const float EYE16[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };   // the 4 x 4 identity
+
 // DevState / PoseBatch::mx2_identity: the target's matrix is the identity, bit for bit -- the searches skip its products
 int mx2_identity(const oa_ctx *c, const float *mx2)
 {
-    static const float eye16[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
-    return (memcmp(mx2, eye16, sizeof eye16) == 0 && !c->tune.no_identity_path) ? 1 : 0;
+    return (memcmp(mx2, EYE16, sizeof EYE16) == 0 && !c->tune.no_identity_path) ? 1 : 0;
 }
 
 void init_loop_state(oa_ctx *c, const oa_settings *st, int iters, bool cutoff = true)
@@ -5334,18 +5335,32 @@ int knn_tree(oa_ctx *c, KnnTree &t)
     return OA_OK;
 }
 
-// what both calls check and do first; a running sequence ends the way oa_set_target_normals ends one
-int knn_call_begin(oa_ctx *c, const char *who, int k, int k_min)
+// What every call on a point-cloud target checks and does first; a running sequence ends the way oa_set_target_normals ends
+// one.  what: the sentence a surface target gets.  k_min > 0: the call takes a k, k_min .. min(KNN_MAX_K, nt), refused after the
+// target and before the device is touched, so that a refused call leaves a running sequence alone.
+enum class CloudCall { NEIGHBOURS, STRAYS };
+int cloud_call_begin(oa_ctx *c, const char *who, CloudCall what, int k = 0, int k_min = 0)
 {
     if (c->tgt.nt <= 0) return fail(OA_E_STATE, "%s: call oa_set_target first", who);
-    if (c->tgt.surface) return fail(OA_E_STATE, "%s: a surface target (oa_set_target_mesh) uses its triangles' geometric normals", who);
-    if (k < k_min || k > oa::KNN_MAX_K || k > c->tgt.nt)
+    if (c->tgt.surface && what == CloudCall::NEIGHBOURS) return fail(OA_E_STATE, "%s: a surface target (oa_set_target_mesh) uses its triangles' geometric normals", who);
+    if (c->tgt.surface) return fail(OA_E_STATE, "%s: a surface target (oa_set_target_mesh) has no stray vertices to look for; upload a cloud", who);
+    if (k_min > 0 && (k < k_min || k > oa::KNN_MAX_K || k > c->tgt.nt))
         return fail(OA_E_BAD_ARG, "%s: k = %d outside %d .. min(%d, %d target vertices)", who, k, k_min, oa::KNN_MAX_K, c->tgt.nt);
     const int rc = use_device(c);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     c->loop_active = false;
     return OA_OK;
+}
+
+// workgroups of a grid-stride launch that deals `items` (leaves of the vertex tree, vertices) to waves, per_block to a workgroup
+inline unsigned wave_blocks(const oa_ctx *c, int items, int per_block) { return (unsigned)std::max(1, std::min((items + per_block - 1) / per_block, c->n_cu * 32)); }
+
+// the point a sign rule looks toward or away from: the caller's, or (null) the centroid of the target's finite vertices
+int orient_point_or_centroid(oa_ctx *c, const char *who, const float point[3], double out[3])
+{
+    if (point) { for (int a = 0; a < 3; ++a) out[a] = (double)point[a]; return OA_OK; }
+    return centroid_of<3>(c, c->tgt.d_tgt_xyz, c->tgt.nt, EYE16, out, (std::string(who) + ": the target").c_str());
 }
 
 // the squared radius a limited search compares against: the float32 square of the float32 setting, rounded once
@@ -5357,9 +5372,7 @@ template <bool PCA>
 int knn_launch(oa_ctx *c, const KnnTree &t, int k, float r2, int32_t *d_idx, float *d_d2, const oa::KnnOrient &orient, float *d_n, float *d_curv)
 {
     const int wpb = oa::knn_waves_per_block(k);
-    const int leaves = t.bp.cnt[1];
-    const unsigned blocks = (unsigned)std::max(1, std::min((leaves + wpb - 1) / wpb, c->n_cu * 32));
-    hipLaunchKernelGGL((oa::k_bvh_knn<PCA>), dim3(blocks), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, k, r2, d_idx, d_d2,
+    hipLaunchKernelGGL((oa::k_bvh_knn<PCA>), dim3(wave_blocks(c, t.bp.cnt[1], wpb)), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, k, r2, d_idx, d_d2,
                        (const float *)c->tgt.d_tgt_xyz, orient, d_n, d_curv);
     HIPCHK(hipGetLastError());
     return OA_OK;
@@ -5372,7 +5385,7 @@ OA_EXPORT int oa_target_knn(oa_ctx *c, int k, int32_t *out_idx, float *out_d2)
     if (!c->subs.empty() && c->loop_active) multi_abort(c);
     // (the target is replicated: every child computes the same bits; the first one's go out)
     OA_ROUTE_ALL_PAR(c, oa_target_knn(sub, k, sub->rank == 0 ? out_idx : nullptr, sub->rank == 0 ? out_d2 : nullptr));
-    int rc = knn_call_begin(c, "oa_target_knn", k, 1);
+    int rc = cloud_call_begin(c, "oa_target_knn", CloudCall::NEIGHBOURS, k, 1);
     if (rc) return rc;
     KnnTree tree;
     if ((rc = knn_tree(c, tree))) return rc;
@@ -5398,19 +5411,14 @@ OA_EXPORT int oa_estimate_target_normals(oa_ctx *c, int k, int orient, const flo
     if (!c->subs.empty() && c->loop_active) multi_abort(c);
     OA_ROUTE_ALL_PAR(c, oa_estimate_target_normals(sub, k, orient, orient_point, install, sub->rank == 0 ? out_normals : nullptr,
                                                    sub->rank == 0 ? out_curvature : nullptr));
-    int rc = knn_call_begin(c, "oa_estimate_target_normals", k, 3);
+    static const char who[] = "oa_estimate_target_normals";
+    int rc = cloud_call_begin(c, who, CloudCall::NEIGHBOURS, k, 3);
     if (rc) return rc;
     KnnTree tree;
     if ((rc = knn_tree(c, tree))) return rc;
     oa::KnnOrient ko{};
     ko.mode = orient;
-    if (orient != OA_ORIENT_NONE) {
-        if (orient_point) { for (int a = 0; a < 3; ++a) ko.p[a] = (double)orient_point[a]; }
-        else {
-            static const float eye16[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
-            if ((rc = centroid_of<3>(c, c->tgt.d_tgt_xyz, c->tgt.nt, eye16, ko.p, "oa_estimate_target_normals: the target"))) return rc;
-        }
-    }
+    if (orient != OA_ORIENT_NONE && (rc = orient_point_or_centroid(c, who, orient_point, ko.p))) return rc;
     const size_t nt = (size_t)c->tgt.nt;
     DevTmp<float> tmp_n, d_curv;
     float *d_n = nullptr;
@@ -5427,23 +5435,11 @@ OA_EXPORT int oa_estimate_target_normals(oa_ctx *c, int k, int orient, const flo
 // stray points of a point-cloud target: fixed-radius counts, mean k-nearest distances, removal (EXTENSION; oa_outlier.hpp)
 // ================================================================================================
 namespace {
-// what both calls check and do first (knn_call_begin without its k); a running sequence ends the way oa_target_knn ends one
-int outlier_call_begin(oa_ctx *c, const char *who)
-{
-    if (c->tgt.nt <= 0) return fail(OA_E_STATE, "%s: call oa_set_target first", who);
-    if (c->tgt.surface) return fail(OA_E_STATE, "%s: a surface target (oa_set_target_mesh) has no stray vertices to look for; upload a cloud", who);
-    const int rc = use_device(c);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->loop_active = false;
-    return OA_OK;
-}
-
 int radius_count_launch(oa_ctx *c, const KnnTree &t, double radius, int cap, int32_t *d_count)
 {
     const float rf = (float)radius, r2 = rf * rf;
-    const int wpb = oa::KNN_WPB, leaves = t.bp.cnt[1];
-    const unsigned blocks = (unsigned)std::max(1, std::min((leaves + wpb - 1) / wpb, c->n_cu * 32));
+    const int wpb = oa::KNN_WPB;
+    const unsigned blocks = wave_blocks(c, t.bp.cnt[1], wpb);
     if (cap > 0) hipLaunchKernelGGL((oa::k_bvh_radius_count<true>), dim3(blocks), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, r2, cap, d_count);
     else hipLaunchKernelGGL((oa::k_bvh_radius_count<false>), dim3(blocks), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, r2, 0, d_count);
     HIPCHK(hipGetLastError());
@@ -5452,12 +5448,72 @@ int radius_count_launch(oa_ctx *c, const KnnTree &t, double radius, int cap, int
 
 int knn_score_launch(oa_ctx *c, const KnnTree &t, int k, double *d_score)
 {
-    const int k1 = k + 1, wpb = oa::KNN_WPB, leaves = t.bp.cnt[1];
-    const unsigned blocks = (unsigned)std::max(1, std::min((leaves + wpb - 1) / wpb, c->n_cu * 32));
-    hipLaunchKernelGGL(oa::k_bvh_knn_score, dim3(blocks), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, k1, d_score);
+    const int k1 = k + 1, wpb = oa::KNN_WPB;
+    hipLaunchKernelGGL(oa::k_bvh_knn_score, dim3(wave_blocks(c, t.bp.cnt[1], wpb)), dim3(64 * wpb), 0, c->stream, t.bp, t.box, t.prims, k1, d_score);
     HIPCHK(hipGetLastError());
     return OA_OK;
 }
+
+// Mean, standard deviation and threshold = mean + std_ratio std of the finite entries of d_score (nt of them) into *d_st, which
+// the caller has zeroed: two passes in a fixed order, per-workgroup rows and then one workgroup (oa_outlier.hpp).  The rows are
+// this function's own (their release is ordered on the stream, behind the launches).
+int score_mean_std(oa_ctx *c, const double *d_score, int nt, double std_ratio, oa::OutlierStats *d_st)
+{
+    const int rows = oa::outlier_rows((long long)nt);
+    DevTmp<double> d_sum;
+    DevTmp<long long> d_n;
+    HIPCHK(d_sum.alloc((size_t)rows)); HIPCHK(d_n.alloc((size_t)rows));
+    const dim3 grid((unsigned)rows), blk(oa::OUT_THREADS);
+    hipLaunchKernelGGL((oa::k_outlier_rows<0>), grid, blk, 0, c->stream, d_score, (long long)nt, (const oa::OutlierStats *)d_st, d_sum.p, d_n.p);
+    hipLaunchKernelGGL((oa::k_outlier_finish<0>), dim3(1), blk, 0, c->stream, (const double *)d_sum.p, (const long long *)d_n.p, rows, std_ratio, d_st);
+    hipLaunchKernelGGL((oa::k_outlier_rows<1>), grid, blk, 0, c->stream, d_score, (long long)nt, (const oa::OutlierStats *)d_st, d_sum.p, d_n.p);
+    hipLaunchKernelGGL((oa::k_outlier_finish<1>), dim3(1), blk, 0, c->stream, (const double *)d_sum.p, (const long long *)d_n.p, rows, std_ratio, d_st);
+    HIPCHK(hipGetLastError());
+    return OA_OK;
+}
+
+// What a keep mask leaves of a cloud target (oa_target_outliers, oa_target_clusters): the flags' scan, the kept vertices' indices
+// in ascending order and, to apply, their coordinates.
+struct KeptVertices {
+    DevTmp<long long> d_off;
+    DevTmp<int32_t> d_index;
+    DevTmp<float> d_xyz;
+    DevTmp<char> scan_tmp;
+
+    int alloc(size_t nt, int apply)
+    {
+        HIPCHK(d_off.alloc(nt + 1)); HIPCHK(d_index.alloc(nt));
+        if (apply) HIPCHK(d_xyz.alloc(3 * nt));
+        return OA_OK;
+    }
+
+    // d_flag: one int per vertex, 1 = keep; d_st->n_kept = their number (nothing else of *d_st is written)
+    int compact(oa_ctx *c, const int *d_flag, oa::OutlierStats *d_st)
+    {
+        const int nt = c->tgt.nt;
+        if (const int rc = scan_counts(c, d_flag, nt, d_off.p, scan_tmp)) return rc;
+        hipLaunchKernelGGL(oa::k_outlier_compact, dim3((unsigned)(((size_t)nt + oa::OUT_THREADS - 1) / oa::OUT_THREADS)), dim3(oa::OUT_THREADS), 0, c->stream, d_flag,
+                           (const long long *)d_off.p, nt, (const float *)c->tgt.d_tgt_xyz, d_index.p, d_xyz.p, d_st);
+        HIPCHK(hipGetLastError());
+        return OA_OK;
+    }
+
+    // The caller has read n_kept back and checked it: keep and kept_index go out (each may be null), the stream is waited for.
+    // apply: the kept vertices become the target, as an upload from device memory would make them (the tree of this call goes
+    // with the old target); with nothing kept the call is refused and the target stays.
+    int finish(oa_ctx *c, const char *who, long long n_kept, int apply, const unsigned char *d_keep, uint8_t *keep, int32_t *kept_index)
+    {
+        const int nt = c->tgt.nt;
+        if (keep) HIPCHK(hipMemcpyAsync(keep, d_keep, (size_t)nt, hipMemcpyDeviceToHost, c->stream));
+        if (kept_index && n_kept > 0) HIPCHK(hipMemcpyAsync(kept_index, d_index.p, sizeof(int32_t) * (size_t)n_kept, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (!apply) return OA_OK;
+        if (n_kept < 1) return fail(OA_E_TOO_FEW_PAIRS, "%s: no vertex of %d would be kept; the target stays as it is", who, nt);
+        if (const int rc = set_target_common(c, d_xyz.p, (int64_t)n_kept, 1, true)) return rc;
+        c->tgt.cleaned = (long long)nt - n_kept;
+        return OA_OK;
+    }
+};
 }  // namespace
 
 OA_EXPORT int oa_target_radius_count(oa_ctx *c, double radius, int32_t cap, int32_t *count)
@@ -5467,7 +5523,7 @@ OA_EXPORT int oa_target_radius_count(oa_ctx *c, double radius, int32_t cap, int3
     OA_NOT_MULTI(c, "oa_target_radius_count");
     if (!(radius > 0.0) || !(radius < (double)INFINITY)) return fail(OA_E_BAD_ARG, "%s: radius = %g (finite and > 0)", who, radius);
     if (cap < 0) return fail(OA_E_BAD_ARG, "%s: cap = %d (>= 0; 0: no cap)", who, (int)cap);
-    int rc = outlier_call_begin(c, who);
+    int rc = cloud_call_begin(c, who, CloudCall::STRAYS);
     if (rc) return rc;
     KnnTree tree;
     if ((rc = knn_tree(c, tree))) return rc;
@@ -5511,28 +5567,19 @@ OA_EXPORT int oa_target_spacing(oa_ctx *c, oa_spacing_report *rep)
     if (!c || !rep) return fail(OA_E_BAD_ARG, "%s: null argument", who);
     OA_NOT_MULTI(c, "oa_target_spacing");
     memset(rep, 0, sizeof *rep);
-    int rc = outlier_call_begin(c, who);
+    int rc = cloud_call_begin(c, who, CloudCall::STRAYS);
     if (rc) return rc;
     const int nt = c->tgt.nt;
     KnnTree tree;
     if ((rc = knn_tree(c, tree))) return rc;
     // the distance to the nearest other vertex = the statistical filter's score at k = 1; its mean and standard deviation by that
     // filter's fixed-order passes
-    DevTmp<double> d_score, d_row_sum;
-    DevTmp<long long> d_row_n;
+    DevTmp<double> d_score;
     DevTmp<oa::OutlierStats> d_st;
-    const int rows = oa::outlier_rows((long long)nt);
-    HIPCHK(d_score.alloc((size_t)nt)); HIPCHK(d_row_sum.alloc((size_t)rows)); HIPCHK(d_row_n.alloc((size_t)rows)); HIPCHK(d_st.alloc(1));
+    HIPCHK(d_score.alloc((size_t)nt)); HIPCHK(d_st.alloc(1));
     HIPCHK(hipMemsetAsync(d_st.p, 0, sizeof(oa::OutlierStats), c->stream));
     if ((rc = knn_score_launch(c, tree, 1, d_score.p))) return rc;
-    const dim3 blk(oa::OUT_THREADS);
-    hipLaunchKernelGGL((oa::k_outlier_rows<0>), dim3((unsigned)rows), blk, 0, c->stream, (const double *)d_score.p, (long long)nt, (const oa::OutlierStats *)d_st.p,
-                       d_row_sum.p, d_row_n.p);
-    hipLaunchKernelGGL((oa::k_outlier_finish<0>), dim3(1), blk, 0, c->stream, (const double *)d_row_sum.p, (const long long *)d_row_n.p, rows, 0.0, d_st.p);
-    hipLaunchKernelGGL((oa::k_outlier_rows<1>), dim3((unsigned)rows), blk, 0, c->stream, (const double *)d_score.p, (long long)nt, (const oa::OutlierStats *)d_st.p,
-                       d_row_sum.p, d_row_n.p);
-    hipLaunchKernelGGL((oa::k_outlier_finish<1>), dim3(1), blk, 0, c->stream, (const double *)d_row_sum.p, (const long long *)d_row_n.p, rows, 0.0, d_st.p);
-    HIPCHK(hipGetLastError());
+    if ((rc = score_mean_std(c, d_score.p, nt, 0.0, d_st.p))) return rc;
     oa::OutlierStats st;
     if ((rc = read_small(c, &st, d_st.p, sizeof st))) return rc;   // (waits for everything above)
     if (st.n_finite < 0 || st.n_finite > nt) return fail(OA_E_HIP, "%s: %lld of %d vertices with a spacing (internal)", who, st.n_finite, nt);
@@ -5560,7 +5607,7 @@ OA_EXPORT int oa_target_outliers(oa_ctx *c, const oa_outlier_settings *s, int ap
         if (s->count_cap != 0 && (long long)s->count_cap < (long long)s->min_neighbors + 1)
             return fail(OA_E_BAD_ARG, "%s: count_cap = %d (0: exact counts, or >= min_neighbors + 1 = %lld)", who, (int)s->count_cap, (long long)s->min_neighbors + 1);
     }
-    int rc = outlier_call_begin(c, who);
+    int rc = cloud_call_begin(c, who, CloudCall::STRAYS);
     if (rc) return rc;
     const int nt = c->tgt.nt;
     if (statistical && s->k > nt - 1) return fail(OA_E_BAD_ARG, "%s: k = %d outside 1 .. min(%d, %d target vertices - 1)", who, (int)s->k, oa::KNN_MAX_K - 1, nt);
@@ -5577,19 +5624,8 @@ OA_EXPORT int oa_target_outliers(oa_ctx *c, const oa_outlier_settings *s, int ap
     if (statistical) {
         HIPCHK(d_score.alloc(snt));
         if ((rc = knn_score_launch(c, tree, s->k, d_score.p))) return rc;
-        // 2. mean, standard deviation and threshold of the finite scores: two passes, rows then one workgroup
-        const int rows = oa::outlier_rows((long long)nt);
-        DevTmp<double> d_row_sum;
-        DevTmp<long long> d_row_n;
-        HIPCHK(d_row_sum.alloc((size_t)rows)); HIPCHK(d_row_n.alloc((size_t)rows));
-        const dim3 blk(oa::OUT_THREADS);
-        hipLaunchKernelGGL((oa::k_outlier_rows<0>), dim3((unsigned)rows), blk, 0, c->stream, (const double *)d_score.p, (long long)nt, (const oa::OutlierStats *)d_st.p,
-                           d_row_sum.p, d_row_n.p);
-        hipLaunchKernelGGL((oa::k_outlier_finish<0>), dim3(1), blk, 0, c->stream, (const double *)d_row_sum.p, (const long long *)d_row_n.p, rows, s->std_ratio, d_st.p);
-        hipLaunchKernelGGL((oa::k_outlier_rows<1>), dim3((unsigned)rows), blk, 0, c->stream, (const double *)d_score.p, (long long)nt, (const oa::OutlierStats *)d_st.p,
-                           d_row_sum.p, d_row_n.p);
-        hipLaunchKernelGGL((oa::k_outlier_finish<1>), dim3(1), blk, 0, c->stream, (const double *)d_row_sum.p, (const long long *)d_row_n.p, rows, s->std_ratio, d_st.p);
-        HIPCHK(hipGetLastError());
+        // 2. mean, standard deviation and threshold of the finite scores
+        if ((rc = score_mean_std(c, d_score.p, nt, s->std_ratio, d_st.p))) return rc;
     } else {
         HIPCHK(d_count.alloc(snt));
         if ((rc = radius_count_launch(c, tree, s->radius, s->count_cap, d_count.p))) return rc;
@@ -5597,39 +5633,25 @@ OA_EXPORT int oa_target_outliers(oa_ctx *c, const oa_outlier_settings *s, int ap
     // 3. flags, their scan, the kept vertices in ascending order (and, to apply, their coordinates)
     DevTmp<int> d_flag;
     DevTmp<unsigned char> d_keep;
-    DevTmp<long long> d_off;
-    DevTmp<int32_t> d_index;
-    DevTmp<float> d_kept_xyz;
-    DevTmp<char> scan_tmp;
-    HIPCHK(d_flag.alloc(snt)); HIPCHK(d_keep.alloc(snt)); HIPCHK(d_off.alloc(snt + 1)); HIPCHK(d_index.alloc(snt));
-    if (apply) HIPCHK(d_kept_xyz.alloc(3 * snt));
+    KeptVertices kept;
+    HIPCHK(d_flag.alloc(snt)); HIPCHK(d_keep.alloc(snt));
+    if ((rc = kept.alloc(snt, apply))) return rc;
     const unsigned v_blocks = (unsigned)((snt + oa::OUT_THREADS - 1) / oa::OUT_THREADS);
     hipLaunchKernelGGL(oa::k_outlier_flags, dim3(v_blocks), dim3(oa::OUT_THREADS), 0, c->stream, statistical ? oa::OUT_STATISTICAL : oa::OUT_RADIUS, (const double *)d_score.p,
                        (const int32_t *)d_count.p, d_xyz, nt, (int)s->min_neighbors, d_st.p, d_flag.p, d_keep.p);
     HIPCHK(hipGetLastError());
-    if ((rc = scan_counts(c, d_flag.p, nt, d_off.p, scan_tmp))) return rc;
-    hipLaunchKernelGGL(oa::k_outlier_compact, dim3(v_blocks), dim3(oa::OUT_THREADS), 0, c->stream, (const int *)d_flag.p, (const long long *)d_off.p, nt, d_xyz, d_index.p,
-                       d_kept_xyz.p, d_st.p);
-    HIPCHK(hipGetLastError());
+    if ((rc = kept.compact(c, d_flag.p, d_st.p))) return rc;
     oa::OutlierStats st;
     if ((rc = read_small(c, &st, d_st.p, sizeof st))) return rc;   // (waits for everything above)
     if (st.n_kept < 0 || st.n_kept > nt) return fail(OA_E_HIP, "%s: %lld of %d vertices kept (internal)", who, st.n_kept, nt);
-    if (keep) HIPCHK(hipMemcpyAsync(keep, d_keep.p, snt, hipMemcpyDeviceToHost, c->stream));
     if (score && statistical) HIPCHK(hipMemcpyAsync(score, d_score.p, sizeof(double) * snt, hipMemcpyDeviceToHost, c->stream));
     if (count && !statistical) HIPCHK(hipMemcpyAsync(count, d_count.p, sizeof(int32_t) * snt, hipMemcpyDeviceToHost, c->stream));
-    if (kept_index && st.n_kept > 0) HIPCHK(hipMemcpyAsync(kept_index, d_index.p, sizeof(int32_t) * (size_t)st.n_kept, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
     if (rep) {
         rep->n_kept = (int64_t)st.n_kept; rep->n_removed = (int64_t)nt - (int64_t)st.n_kept; rep->n_nonfinite = (int64_t)st.n_nonfinite;
         if (statistical) { rep->mean = st.mean; rep->std = st.std; rep->threshold = st.threshold; }
     }
-    if (!apply) return OA_OK;
-    if (st.n_kept < 1) return fail(OA_E_TOO_FEW_PAIRS, "%s: no vertex of %d would be kept; the target stays as it is", who, nt);
-    // 4. the kept vertices become the target, as an upload from device memory would make them (the tree of this call goes with the old one)
-    const long long removed = (long long)nt - st.n_kept;
-    if ((rc = set_target_common(c, d_kept_xyz.p, (int64_t)st.n_kept, 1, true))) return rc;
-    c->tgt.cleaned = removed;
-    return OA_OK;
+    // 4. keep and kept_index go out; to apply, the kept vertices become the target
+    return kept.finish(c, who, st.n_kept, apply, d_keep.p, keep, kept_index);
 }
 
 // ================================================================================================
@@ -5647,7 +5669,7 @@ OA_EXPORT int oa_target_clusters(oa_ctx *c, const oa_cluster_settings *s, int ap
     if (s->keep != OA_CLUSTER_KEEP_CLUSTERED && s->keep != OA_CLUSTER_KEEP_LARGEST && s->keep != OA_CLUSTER_KEEP_MIN_SIZE)
         return fail(OA_E_BAD_ARG, "%s: keep = %d (use OA_CLUSTER_KEEP_CLUSTERED / _LARGEST / _MIN_SIZE)", who, (int)s->keep);
     if (s->min_size < 0) return fail(OA_E_BAD_ARG, "%s: min_size = %lld (>= 0)", who, (long long)s->min_size);
-    int rc = outlier_call_begin(c, who);
+    int rc = cloud_call_begin(c, who, CloudCall::STRAYS);
     if (rc) return rc;
     const int nt = c->tgt.nt;
     KnnTree tree;
@@ -5656,20 +5678,20 @@ OA_EXPORT int oa_target_clusters(oa_ctx *c, const oa_cluster_settings *s, int ap
     const float *d_xyz = c->tgt.d_tgt_xyz;
     const float ef = (float)s->eps, r2 = ef * ef;
     const int min_points = (int)s->min_points;
-    DevTmp<int32_t> d_count, d_label, d_sizes, d_index;
+    DevTmp<int32_t> d_count, d_label, d_sizes;
     DevTmp<uint32_t> d_parent, d_root, d_border;
     DevTmp<int> d_is_root, d_flag;
-    DevTmp<long long> d_dense, d_off;
+    DevTmp<long long> d_dense;
     DevTmp<unsigned char> d_keep;
-    DevTmp<float> d_kept_xyz;
+    KeptVertices kept;
     DevTmp<oa::ClusterStats> d_st;
-    DevTmp<oa::OutlierStats> d_ost;                                  // (k_outlier_compact's n_kept)
-    DevTmp<char> scan_tmp, scan_tmp2;
-    HIPCHK(d_count.alloc(snt)); HIPCHK(d_label.alloc(snt)); HIPCHK(d_sizes.alloc(snt)); HIPCHK(d_index.alloc(snt));
+    DevTmp<oa::OutlierStats> d_ost;                                  // (the number kept)
+    DevTmp<char> scan_tmp;
+    HIPCHK(d_count.alloc(snt)); HIPCHK(d_label.alloc(snt)); HIPCHK(d_sizes.alloc(snt));
     HIPCHK(d_parent.alloc(snt)); HIPCHK(d_root.alloc(snt)); HIPCHK(d_border.alloc(snt));
-    HIPCHK(d_is_root.alloc(snt)); HIPCHK(d_flag.alloc(snt)); HIPCHK(d_dense.alloc(snt + 1)); HIPCHK(d_off.alloc(snt + 1));
+    HIPCHK(d_is_root.alloc(snt)); HIPCHK(d_flag.alloc(snt)); HIPCHK(d_dense.alloc(snt + 1));
     HIPCHK(d_keep.alloc(snt)); HIPCHK(d_st.alloc(1)); HIPCHK(d_ost.alloc(1));
-    if (apply) HIPCHK(d_kept_xyz.alloc(3 * snt));
+    if ((rc = kept.alloc(snt, apply))) return rc;
     HIPCHK(hipMemsetAsync(d_st.p, 0, sizeof(oa::ClusterStats), c->stream));
     HIPCHK(hipMemsetAsync(d_ost.p, 0, sizeof(oa::OutlierStats), c->stream));
     HIPCHK(hipMemsetAsync(d_sizes.p, 0, sizeof(int32_t) * snt, c->stream));
@@ -5677,8 +5699,8 @@ OA_EXPORT int oa_target_clusters(oa_ctx *c, const oa_cluster_settings *s, int ap
     // 1. core flags: counts that saturate at min_points
     if ((rc = radius_count_launch(c, tree, s->eps, min_points, d_count.p))) return rc;
     // 2. the core graph's components (link, then flatten in a launch of its own), 3. the border vertices' lowest root
-    const int wpb = oa::KNN_WPB, leaves = tree.bp.cnt[1];
-    const unsigned t_blocks = (unsigned)std::max(1, std::min((leaves + wpb - 1) / wpb, c->n_cu * 32));
+    const int wpb = oa::KNN_WPB;
+    const unsigned t_blocks = wave_blocks(c, tree.bp.cnt[1], wpb);
     const unsigned v_blocks = (unsigned)((snt + oa::CL_THREADS - 1) / oa::CL_THREADS);
     const int max_steps = (int)std::min<long long>(2ll * nt + 64, 0x7fffffffll);
     const dim3 blk(oa::CL_THREADS);
@@ -5698,10 +5720,7 @@ OA_EXPORT int oa_target_clusters(oa_ctx *c, const oa_cluster_settings *s, int ap
     hipLaunchKernelGGL(oa::k_cluster_keep, dim3(v_blocks), blk, 0, c->stream, (const int32_t *)d_label.p, (const int32_t *)d_sizes.p, (const oa::ClusterStats *)d_st.p,
                        (int)s->keep, (long long)s->min_size, nt, d_flag.p, d_keep.p);
     HIPCHK(hipGetLastError());
-    if ((rc = scan_counts(c, d_flag.p, nt, d_off.p, scan_tmp2))) return rc;
-    hipLaunchKernelGGL(oa::k_outlier_compact, dim3(v_blocks), dim3(oa::OUT_THREADS), 0, c->stream, (const int *)d_flag.p, (const long long *)d_off.p, nt, d_xyz,
-                       d_index.p, d_kept_xyz.p, d_ost.p);
-    HIPCHK(hipGetLastError());
+    if ((rc = kept.compact(c, d_flag.p, d_ost.p))) return rc;
     oa::ClusterStats st;
     oa::OutlierStats ost;
     if ((rc = read_small(c, &st, d_st.p, sizeof st))) return rc;    // (waits for everything above)
@@ -5711,22 +5730,14 @@ OA_EXPORT int oa_target_clusters(oa_ctx *c, const oa_cluster_settings *s, int ap
         return fail(OA_E_HIP, "%s: %lld of %d vertices kept in %lld clusters (internal)", who, ost.n_kept, nt, st.n_clusters);
     if (label) HIPCHK(hipMemcpyAsync(label, d_label.p, sizeof(int32_t) * snt, hipMemcpyDeviceToHost, c->stream));
     if (sizes && st.n_clusters > 0) HIPCHK(hipMemcpyAsync(sizes, d_sizes.p, sizeof(int32_t) * (size_t)st.n_clusters, hipMemcpyDeviceToHost, c->stream));
-    if (keep) HIPCHK(hipMemcpyAsync(keep, d_keep.p, snt, hipMemcpyDeviceToHost, c->stream));
-    if (kept_index && ost.n_kept > 0) HIPCHK(hipMemcpyAsync(kept_index, d_index.p, sizeof(int32_t) * (size_t)ost.n_kept, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
     if (rep) {
         rep->n_clusters = (int64_t)st.n_clusters; rep->n_core = (int64_t)st.n_core; rep->n_border = (int64_t)st.n_border;
         rep->n_noise = (int64_t)st.n_noise; rep->n_nonfinite = (int64_t)st.n_nonfinite;
         rep->largest_label = (int64_t)st.largest_label; rep->largest_size = (int64_t)st.largest_size;
         rep->n_kept = (int64_t)ost.n_kept; rep->n_removed = (int64_t)nt - (int64_t)ost.n_kept;
     }
-    if (!apply) return OA_OK;
-    if (ost.n_kept < 1) return fail(OA_E_TOO_FEW_PAIRS, "%s: no vertex of %d would be kept; the target stays as it is", who, nt);
-    // 5. the kept vertices become the target, as an upload from device memory would make them (oa_target_outliers' path)
-    const long long removed = (long long)nt - ost.n_kept;
-    if ((rc = set_target_common(c, d_kept_xyz.p, (int64_t)ost.n_kept, 1, true))) return rc;
-    c->tgt.cleaned = removed;
-    return OA_OK;
+    // 5. keep and kept_index go out; to apply, the kept vertices become the target
+    return kept.finish(c, who, ost.n_kept, apply, d_keep.p, keep, kept_index);
 }
 
 // ================================================================================================
@@ -5746,7 +5757,7 @@ OA_EXPORT int oa_orient_target_normals(oa_ctx *c, int k, double max_dist, int se
         for (int a = 0; a < 3; ++a)
             if (!(fabsf(point[a]) < INFINITY)) return fail(OA_E_BAD_ARG, "%s: point[%d] = %g is not finite", who, a, (double)point[a]);
     if (!(max_dist >= 0.0) || !(max_dist < (double)INFINITY)) return fail(OA_E_BAD_ARG, "%s: max_dist = %g (finite and >= 0; 0: no cap)", who, max_dist);
-    int rc = knn_call_begin(c, who, k, 2);
+    int rc = cloud_call_begin(c, who, CloudCall::NEIGHBOURS, k, 2);
     if (rc) return rc;
     if (!normals && !c->tgt.d_tgt_n)
         return fail(OA_E_STATE, "%s: no normals given and the target has none (oa_set_target_normals, oa_set_normals or oa_estimate_target_normals with install)", who);
@@ -5755,13 +5766,7 @@ OA_EXPORT int oa_orient_target_normals(oa_ctx *c, int k, double max_dist, int se
     if (n_ent > oa::SORT_MAX_N) return fail(OA_E_CAPACITY, "%s: %d vertices x k = %d is %lld entries (at most 2^31 - 2^20)", who, nt, k, n_ent);
     oa::OrientSeed sd{};
     sd.mode = seed;
-    if (seed != OA_SEED_KEEP) {
-        if (point) { for (int a = 0; a < 3; ++a) sd.p[a] = (double)point[a]; }
-        else {
-            static const float eye16[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };
-            if ((rc = centroid_of<3>(c, c->tgt.d_tgt_xyz, nt, eye16, sd.p, "oa_orient_target_normals: the target"))) return rc;
-        }
-    }
+    if (seed != OA_SEED_KEEP && (rc = orient_point_or_centroid(c, who, point, sd.p))) return rc;
     const size_t snt = (size_t)nt, sne = (size_t)n_ent;
     const float *d_xyz = c->tgt.d_tgt_xyz;
     DevTmp<float> tmp_in;
@@ -5942,7 +5947,7 @@ OA_EXPORT int oa_target_fpfh(oa_ctx *c, int k, float *out, int keep)
 {
     if (!c) return fail(OA_E_BAD_ARG, "null context");
     OA_NOT_MULTI(c, "oa_target_fpfh");
-    int rc = knn_call_begin(c, "oa_target_fpfh", k, 4);
+    int rc = cloud_call_begin(c, "oa_target_fpfh", CloudCall::NEIGHBOURS, k, 4);
     if (rc) return rc;
     if (!c->tgt.d_tgt_n) return fail(OA_E_STATE, "oa_target_fpfh: the target has no normals (oa_set_target_normals, oa_set_normals or oa_estimate_target_normals with install)");
     KnnTree tree;
@@ -6534,8 +6539,7 @@ int ensure_boundary(oa_ctx *c, int k, double angle_deg)
         DevTmp<int32_t> d_idx;
         HIPCHK(d_idx.alloc(nv * (size_t)(k + 1)));
         if ((rc = knn_launch<false>(c, tree, k + 1, neighbor_r2(c), d_idx.p, nullptr, oa::KnnOrient{}, nullptr, nullptr))) return rc;
-        const unsigned blocks = (unsigned)std::max(1, std::min((c->tgt.nt + oa::BND_WPB - 1) / oa::BND_WPB, c->n_cu * 32));
-        hipLaunchKernelGGL(oa::k_cloud_boundary, dim3(blocks), dim3(oa::BND_WPB * 64), 0, c->stream, (const float *)c->tgt.d_tgt_xyz, (const float *)c->tgt.d_tgt_n,
+        hipLaunchKernelGGL(oa::k_cloud_boundary, dim3(wave_blocks(c, c->tgt.nt, oa::BND_WPB)), dim3(oa::BND_WPB * 64), 0, c->stream, (const float *)c->tgt.d_tgt_xyz, (const float *)c->tgt.d_tgt_n,
                            (const int32_t *)d_idx.p, c->tgt.nt, k, angle_deg * 3.14159265358979323846 / 180.0, c->tgt.d_bnd_vmask);
         HIPCHK(hipGetLastError());
         c->tgt.bnd_n_edges = 0;

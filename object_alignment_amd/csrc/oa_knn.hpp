@@ -138,6 +138,16 @@ __host__ __device__ inline void pca_normal(const double C[6], double vx, double 
     curv_out = (float)(l0c / tot);
 }
 
+// What a one-wave-per-leaf kernel opens query q with (q wave-uniform; the leaf's 64 vertices are `mine`, one per lane, original
+// index my_idx): the query's index and coordinates, broadcast from lane q.  false: padding, which closes the last leaf.
+__device__ __forceinline__ bool knn_leaf_query(const float4 &mine, uint32_t my_idx, int q, uint32_t &qi, float p[3])
+{
+    qi = (uint32_t)__builtin_amdgcn_readlane((int)my_idx, q);
+    if (qi == IDX_NONE) return false;
+    p[0] = knn_lane_f(mine.x, q); p[1] = knn_lane_f(mine.y, q); p[2] = knn_lane_f(mine.z, q);
+    return true;
+}
+
 // The list of ONE query by ONE wave (all 64 lanes call it together; p, leaf and k are wave-uniform): lane j returns the j-th best
 // key of query p, whose own leaf is `leaf` (its 64 vertices: `mine`, one per lane, original index my_idx).  Entries past the
 // last finite distance are KNN_EMPTY.  lds: this wave's scratch (bvh_wave_query's).  1 <= k <= 64.
@@ -249,9 +259,8 @@ __global__ __launch_bounds__(KNN_WPB * 64) void k_bvh_knn(BvhParams bp, const fl
         const float4 mine = prims[(long long)leaf * BVH_W + lane];
         const uint32_t my_idx = __float_as_uint(mine.w);
         for (int q = 0; q < BVH_W; ++q) {
-            const uint32_t qi = (uint32_t)__builtin_amdgcn_readlane((int)my_idx, q);
-            if (qi == IDX_NONE) break;                               // padding closes the last leaf
-            const float p[3] = { knn_lane_f(mine.x, q), knn_lane_f(mine.y, q), knn_lane_f(mine.z, q) };
+            uint32_t qi; float p[3];
+            if (!knn_leaf_query(mine, my_idx, q, qi, p)) break;
             const unsigned long long key = knn_wave_list(bp, boxes, prims, lds, leaf, mine, my_idx, p, k, r2, lane);
             if (lane < k) {
                 const int32_t ni = (int32_t)(uint32_t)key;           // IDX_NONE -> -1

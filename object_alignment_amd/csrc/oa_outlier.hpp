@@ -7,8 +7,8 @@
 //
 //   k_bvh_radius_count<CAPPED>  count_i = min(cap, #{ j : d2_metric(v_i, v_j) <= r2 }), r2 a float32 the host squares once.  Self
 //                    and duplicates count; a vertex with a non-finite coordinate counts 0 and is counted by nobody.  A child box
-//                    is visited iff !bvh_prune(lb, r2); the cut-off never moves, so the children are taken in lane order (no
-//                    bounds parked, no minimum over the wave).  At a leaf every lane evaluates one vertex, a ballot and a popcount
+//                    is visited iff !bvh_prune(lb, r2) (bvh_radius_walk below, the one fixed-radius descent; oa_cluster.hpp's
+//                    passes walk with it too).  At a leaf every lane evaluates one vertex, a ballot and a popcount
 //                    add the hits to a wave-uniform count.  The own leaf is one more leaf.  CAPPED: the query stops descending
 //                    once `cap` is reached and reports cap -- whichever order the leaves came in, so two runs give the same bits.
 //   k_bvh_knn_score  the statistical filter's score without an nt x k buffer: knn_wave_list with k + 1 entries, then
@@ -16,12 +16,6 @@
 //                    m < 2.  Lane j takes the root of entry j (IEEE, 64 wide); the sum is wave-uniform.  The query itself adds
 //                    exactly 0 (or, pushed out of its own row by more than k duplicates of lower index, every entry is 0), so no
 //                    "which entry is me" test, and equal distances add the same terms in any order of their indices.
-//
-// Exactness of the radius test: a box is skipped only when lb (1 - 1e-5) - 1e-30 > r2 (bvh_prune).  lb never exceeds the true
-// squared gap D to the box by more than the margin absorbs and the metric is >= D (1 - 5.01u) for every vertex inside
-// (oa_bvh.hpp), so every vertex of a skipped box has d2_metric > r2 STRICTLY: it is not a hit, and d2 = r2 is never lost.  There
-// is no "whole box inside the radius" shortcut: every hit is one evaluation of d2_metric, the same float32 the brute-force
-// restatement compares.
 //
 // The rest is plain kernels in the host unit: mean and standard deviation of the finite scores (fp64, two passes, fixed order:
 // per-workgroup rows by a butterfly and the waves in order, the rows by one workgroup's fixed tree -- k_deviation / k_dev_finish's
@@ -50,6 +44,55 @@ inline int outlier_rows(long long n)
 
 #if defined(__HIPCC__)
 
+// The fixed-radius descent of ONE finite query p by ONE wave (all 64 lanes call it together; p and r2 are wave-uniform): every
+// leaf whose box may hold a vertex with d2_metric <= r2, the query's own among them, goes to at_leaf(child) in the order visited
+// (its 64 vertices: prims[child * BVH_W + lane]); at_leaf returns true to end the query.  lds: this wave's scratch, per level a
+// mask of children still to visit and the node; the cut-off never moves, so the children are taken in lane order (no bounds
+// parked, no minimum over the wave).
+// Exactness of the radius test: a box is skipped only when lb (1 - 1e-5) - 1e-30 > r2 (bvh_prune).  lb never exceeds the true
+// squared gap D to the box by more than the margin absorbs and the metric is >= D (1 - 5.01u) for every vertex inside
+// (oa_bvh.hpp), so every vertex of a skipped box has d2_metric > r2 STRICTLY: it is not a hit, and d2 = r2 is never lost.  There
+// is no "whole box inside the radius" shortcut: every hit is one evaluation of d2_metric by at_leaf, the same float32 the
+// brute-force restatement compares.
+template <class AtLeaf>
+__device__ __forceinline__ void bvh_radius_walk(const BvhParams &bp, const float4 *__restrict__ boxes, const BvhLds &lds, const float *p, float r2, int lane,
+                                                AtLeaf &&at_leaf)
+{
+    const int top = bp.levels;
+    int level = top, node = 0;
+    bool fresh = true;
+    for (;;) {
+        if (fresh) {
+            const long long ch = (long long)node * BVH_W + lane;
+            bool pass = false;
+            if (ch < bp.cnt[level]) {
+                const float4 lo = boxes[2 * ((long long)bp.off[level] + ch)], hi = boxes[2 * ((long long)bp.off[level] + ch) + 1];
+                const float lb = bvh_box_bound<false>(p, lo, hi, 0.0);
+                pass = lb < INFINITY && !bvh_prune(lb, r2);
+            }
+            const unsigned long long m = __ballot(pass);
+            if (lane == 0) { *lds.mask(level) = m; *lds.node(level) = node; }
+            fresh = false;
+        }
+        const unsigned long long m = *lds.mask(level);
+        if (m == 0ull) {
+            if (level == top) break;
+            ++level;
+            continue;
+        }
+        const int pick = __ffsll((long long)m) - 1;
+        if (lane == 0) *lds.mask(level) = m & (m - 1ull);
+        const long long child = (long long)*lds.node(level) * BVH_W + pick;
+        if (level > 1) {
+            --level;
+            node = (int)child;
+            fresh = true;
+            continue;
+        }
+        if (at_leaf(child)) break;
+    }
+}
+
 // Launch: 64 * KNN_WPB threads (or fewer whole waves), any number of workgroups (the leaves are dealt wave by wave, grid stride).
 // count: nt, the caller's vertex order; every real vertex is the query of exactly one (wave, q): one store per query.
 template <bool CAPPED>
@@ -60,53 +103,24 @@ __global__ __launch_bounds__(KNN_WPB * 64) void k_bvh_radius_count(BvhParams bp,
     __shared__ int s_node[KNN_WPB][BVH_MAX_LEVELS + 1];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     const BvhLds lds{ nullptr, 0, &s_mask[w][0], 1, &s_node[w][0], 1 };      // (no bounds: nothing is ordered by them)
-    const int top = bp.levels;
 
     for (int leaf = blockIdx.x * wpb + w; leaf < bp.cnt[1]; leaf += gridDim.x * wpb) {     // (wave-uniform)
         const float4 mine = prims[(long long)leaf * BVH_W + lane];
         const uint32_t my_idx = __float_as_uint(mine.w);
         for (int q = 0; q < BVH_W; ++q) {
-            const uint32_t qi = (uint32_t)__builtin_amdgcn_readlane((int)my_idx, q);
-            if (qi == IDX_NONE) break;                               // padding closes the last leaf
-            const float p[3] = { knn_lane_f(mine.x, q), knn_lane_f(mine.y, q), knn_lane_f(mine.z, q) };
+            uint32_t qi; float p[3];
+            if (!knn_leaf_query(mine, my_idx, q, qi, p)) break;
             const bool finite = fabsf(p[0]) < INFINITY && fabsf(p[1]) < INFINITY && fabsf(p[2]) < INFINITY;
             int n = 0;                                               // (wave-uniform)
-            int level = top, node = 0;
-            bool fresh = true;
-            while (finite) {                                         // (a non-finite query has no finite distance: it counts 0)
-                if (fresh) {
-                    const long long ch = (long long)node * BVH_W + lane;
-                    bool pass = false;
-                    if (ch < bp.cnt[level]) {
-                        const float4 lo = boxes[2 * ((long long)bp.off[level] + ch)], hi = boxes[2 * ((long long)bp.off[level] + ch) + 1];
-                        const float lb = bvh_box_bound<false>(p, lo, hi, 0.0);
-                        pass = lb < INFINITY && !bvh_prune(lb, r2);
-                    }
-                    const unsigned long long m = __ballot(pass);
-                    if (lane == 0) { *lds.mask(level) = m; *lds.node(level) = node; }
-                    fresh = false;
-                }
-                const unsigned long long m = *lds.mask(level);
-                if (m == 0ull) {
-                    if (level == top) break;
-                    ++level;
-                    continue;
-                }
-                const int pick = __ffsll((long long)m) - 1;
-                if (lane == 0) *lds.mask(level) = m & (m - 1ull);
-                const long long child = (long long)*lds.node(level) * BVH_W + pick;
-                if (level > 1) {
-                    --level;
-                    node = (int)child;
-                    fresh = true;
-                    continue;
-                }
-                // leaf: 64 vertices, one per lane
-                const float4 c4 = prims[child * BVH_W + lane];
-                const float d = d2_metric(p[0], p[1], p[2], c4.x, c4.y, c4.z);
-                n += __popcll(__ballot(d <= r2 && d < INFINITY && __float_as_uint(c4.w) != IDX_NONE));
-                if (CAPPED && n >= cap) { n = cap; break; }
-            }
+            if (finite)                                              // (a non-finite query has no finite distance: it counts 0)
+                bvh_radius_walk(bp, boxes, lds, p, r2, lane, [&](long long child) {
+                    // leaf: 64 vertices, one per lane
+                    const float4 c4 = prims[child * BVH_W + lane];
+                    const float d = d2_metric(p[0], p[1], p[2], c4.x, c4.y, c4.z);
+                    n += __popcll(__ballot(d <= r2 && d < INFINITY && __float_as_uint(c4.w) != IDX_NONE));
+                    if (CAPPED && n >= cap) { n = cap; return true; }
+                    return false;
+                });
             if (lane == 0) count[qi] = n;
         }
     }
@@ -130,9 +144,8 @@ __global__ __launch_bounds__(KNN_WPB * 64) void k_bvh_knn_score(BvhParams bp, co
         const float4 mine = prims[(long long)leaf * BVH_W + lane];
         const uint32_t my_idx = __float_as_uint(mine.w);
         for (int q = 0; q < BVH_W; ++q) {
-            const uint32_t qi = (uint32_t)__builtin_amdgcn_readlane((int)my_idx, q);
-            if (qi == IDX_NONE) break;                               // padding closes the last leaf
-            const float p[3] = { knn_lane_f(mine.x, q), knn_lane_f(mine.y, q), knn_lane_f(mine.z, q) };
+            uint32_t qi; float p[3];
+            if (!knn_leaf_query(mine, my_idx, q, qi, p)) break;
             const unsigned long long key = knn_wave_list(bp, boxes, prims, lds, leaf, mine, my_idx, p, k1, INFINITY, lane);
             // the filled entries come first (KNN_EMPTY is the largest key)
             const int m = __popcll(__ballot(lane < k1 && key != KNN_EMPTY));
